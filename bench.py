@@ -236,6 +236,39 @@ def pack_banks(h, problems, first_bank=0, use_weights=True):
     return recs_per_bank, bytes_per_bank, pops_per_bank, nodes_per_bank, t_grow
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, recs, Hp, limit=DUMP_LIMIT_BYTES):
+    """Writes the result records `recs` as a caller decodes them (pdmpc.iteration_data.info_from_record): every field cut to the
+    horizon Hp, one row per vehicle slot, as out_dir/<field>.npy in float64 (ids and counts are exact in it), plus slot.npy: the slot
+    of each row.  An exhausted search carries no plan: its plan fields are written as zeros (the decoder's NaN trajectory included;
+    `status` marks the row).  Beyond `limit` bytes in all, a fixed sample of the slots (seed 0) is written."""
+    horizon = {"tree_path": Hp + 1, "predicted_trims": Hp, "shape_cols": Hp, "y_predicted": Hp, "shapes": Hp, "path_nodes": Hp + 1}
+    no_plan = np.asarray(recs["status"]) != 0
+    out = {}
+    for f in PARITY_FIELDS:
+        a = np.array(recs[f], dtype=np.float64)
+        if f in horizon:
+            a = a[:, : horizon[f]]
+            a[no_plan] = 0.0
+        if not np.isfinite(a).all():
+            raise SystemExit("bench.py: the result field %s of the last timed step is not finite" % f)
+        out[f] = a
+    n = len(recs)
+    row_bytes = 8 * (1 + sum(a[0].size for a in out.values())) if n else 8
+    slots = np.arange(n)
+    budget = limit - 4096 * (len(out) + 1)  # (the .npy headers)
+    if n * row_bytes > budget:
+        slots = np.sort(np.random.default_rng(0).choice(n, size=max(1, budget // row_bytes), replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "slot.npy"), slots.astype(np.float64))
+    for f, a in out.items():
+        np.save(os.path.join(out_dir, f + ".npy"), np.ascontiguousarray(a[slots]))
+    return {"dir": out_dir, "files": ["slot.npy"] + [f + ".npy" for f in out], "records": n, "rows_written": len(slots),
+            "bytes": len(slots) * row_bytes, "horizon": Hp}
+
+
 def scaling_reference(args_in, local_rank, torch):
     """The C4 rate on this one GPU (few recorded steps, replayed): the N = 1 point of the strong-scaling curve `--gpus N > 1` reports."""
     import copy
@@ -311,6 +344,9 @@ def main():
                     help="N > 1, sharded workloads: `group` = the C ABI's own multi-GPU path (pdmpc_group_*: ONE process drives all N devices, RCCL through "
                     "ncclCommInitAll; rank 0 plans, the other ranks of the launcher only take part in the barriers) with a fall-back to `dist` if the group "
                     "cannot be created; `dist` = one process per GPU through torch.distributed (pdmpc.distributed)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the result records of the last timed step (what a caller of the timed path "
+                    "receives) as DIR/<field>.npy in float64, at most 64 MB in all (a seeded sample of the vehicles beyond that)")
     ap.add_argument("--shard", default="components", choices=["components", "levels"],
                     help="multi-GPU mode of c3/c4: whole coupling-graph components per rank (one speculative launch per rank and step, one "
                     "all-gather of results) or block-partitioned levels (one all-gather per level).  (pdmpc.distributed.plan_step_hybrid -- whole components, a dominating one split by level -- is a library call: the tiled benchmark maps have no dominating component)")
@@ -471,6 +507,25 @@ def main():
         store, gate_key = _get_default_store(), "pdmpc_bench_group_done"
         host_gate = (lambda: store.set(gate_key, "1")) if rank == 0 else (lambda: store.wait([gate_key]))
     elapsed, lat = measure_replay(h, problems, args.steps, args.warmup, one_step, dist, torch, reset_extra=grp.reset_stats if grp is not None else None, host_gate=host_gate)
+    dumped = None
+    if args.dump_outputs:
+        # the records of the last timed step as its caller receives them, read before anything else is launched
+        last = (args.steps - 1) % S
+        n_last = len(full_problems[last]["iters"])
+        if use_group:
+            last_recs = grp.fetch(last, n_last) if grp is not None else None
+        elif gather_bufs is not None:
+            from pdmpc.distributed import REC_BYTES, assemble_records
+
+            per = gather_bufs[0].numel() // REC_BYTES
+            recv = gather_bufs[1].cpu().numpy()
+            last_recs = assemble_records([recv[r * per * REC_BYTES:(r + 1) * per * REC_BYTES] for r in range(world)], parts[last], n_last)
+        else:
+            last_recs = h.fetch(n_last)
+        if rank == 0 and last_recs is not None:
+            dumped = dump_outputs(args.dump_outputs, last_recs, options.Hp)
+            dumped["step"] = args.steps - 1
+            dumped["recorded_step"] = last
     # the group: counts summed over the ranks, kernel time of the rank whose kernels ran longest (backend.Group.stats_all); the
     # roofline below is PER DEVICE (the step's algorithmic bytes / ranks, over that time) against one device's peak
     st = grp.stats_all() if (use_group and grp is not None) else h.stats()
@@ -730,6 +785,7 @@ def main():
                 "queue_fallbacks_per_step": st["queue_fallbacks"] / args.steps,
             },
             "scaling_reference": scal_ref,
+            "dump_outputs": dumped,
         }
         parity_mismatches = 0
         if world == 1 and not args.no_cpu_baseline:
