@@ -163,9 +163,10 @@ typedef struct {
 /* Tuning.  The graph search's knobs (round sizes, helper workgroups, tiles, the open set's lists) and its A/B and test switches have
  * measured defaults; ONE environment variable, read once in pdmpc_create, overrides them for benchmarking and tests:
  *     PDMPC_TUNING="key=value,key=value,..."
- * keys: round0 round ramp ready share_min own_div tile mid_min mid_fill (rounds and lists), tentative fast_arrival speculate helpers
- * helpers_oversub helpers_first seat_nodes waves (A/B switches), force_tie reverse_dispatch spin_limit (testing), debug_tail debug_lds debug_host debug_progress
- * (diagnostics); csrc/api.cpp: struct Tuning documents each.  No setting changes a result; an unknown key fails pdmpc_create. */
+ * keys: round0 round ramp ready share_min tile mid_min mid_fill (rounds and lists), tentative fast_arrival speculate helpers
+ * helpers_oversub helpers_first seat_nodes waves compact (A/B switches; compact takes -1, 0 or 1), force_tie reverse_dispatch
+ * spin_limit (testing), debug_tail debug_lds debug_host debug_progress (diagnostics); csrc/api.cpp: struct Tuning documents each.
+ * No setting changes a result; an unknown key fails pdmpc_create. */
 
 /* ---- life cycle (replaces GraphSearch() construction in OptimizerInterface.get_optimizer, :26-27,
  *      and the MEX instance table of priority_queue_interface_mex.cpp:48-53,111) ---- */
@@ -269,7 +270,8 @@ int pdmpc_reset_stats(pdmpc_handle* handle);
  * searches out by priority — the largest expected work among a vehicle and its descendants in the coupling DAG, descending — instead
  * of slot order: still a topological order (whoever a search waits for was dispatched before it), but in a launch of more searches
  * than CUs the heavy searches of late computation levels start with the launch instead of behind the finished searches that wait for
- * their predecessors.  Slots, records and results are the same bit for bit.  Optional: without it searches go out in slot order. */
+ * their predecessors.  Slots, records and results are the same bit for bit.  Optional: without it searches go out in slot order.
+ * A pack that fails consumes the weights too: the pack after it has none. */
 int pdmpc_set_step_weights(pdmpc_handle* handle, int32_t n_vehicles, const double* weights);
 int pdmpc_pack_step(pdmpc_handle* handle, int32_t n_vehicles, const pdmpc_vehicle_in* in,
                     const int32_t* pred_offset, const int32_t* pred_index,

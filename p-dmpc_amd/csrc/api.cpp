@@ -185,7 +185,6 @@ struct Tuning {
     int ramp = -1;          // a round grows by 1 / ramp of the nodes processed so far (-1: 2 with helper workgroups, else 4)
     int ready = 2048;       // entries of the ready list with helper workgroups (half of it without): the most a round can take
     int share_min = -1;     // a round with at least this many nodes is shared with the helper workgroups (-1: by the number of helpers per search, launch_range)
-    int own_div = 8;        // (accepted, no effect since round 5: the owner takes an equal share of a shared round)
     int tile = -1;          // the most nodes of a shared round one seated helper takes (-1: 256; what it stages in LDS: at most 768)
     int mid_min = 24576;    // far lists longer than this feed near through the mid list (a band of far's smallest keys)
     int mid_fill = 12288;   // entries a refill of mid aims at
@@ -196,11 +195,7 @@ struct Tuning {
     int seat_nodes = 256;   // a search may hold its share of the launch's helpers (helpers / searches) per this many nodes it has processed
     int helpers_first = -1; // ... of them dispatched in front of the searches (-1: half the CUs when most searches of the launch have predecessors)
     int speculate = 1;      // 0: every search waits for all its predecessors before it starts
-    int dispatch_order = 1; // 0: ignore pdmpc_set_step_weights (slots in level order, never by priority)
-    int fast_select = 1;    // 0: every selection goes through the sixteen-wavefront histogram, also while the open set is small (A/B)
-    int poll_every = 1;     // a search that has just run a round looks for arrived predecessors at every K-th round boundary only (1 .. 8)
-    int lazy_verify = 0;    // 1: an arrival into a RUNNING search brings the parked nodes back at once but re-checks the collision-free nodes only when the search stalls or is done
-    int compact = -1;       // 1: the kernel built for two workgroups per CU (8 wavefronts, <= 80 KB of LDS: bulk_kernel_compact.hip) where it applies (InterX, one mask word, the soup fits); 0: never; -1: for launches of more than two searches per CU; 2-5: layout experiments (one workgroup per CU with the compact kernel, slack behind the layout)
+    int compact = -1;       // 1: the kernel built for two workgroups per CU (8 wavefronts, <= 80 KB of LDS: bulk_kernel_compact.hip) where it applies (InterX, one mask word, the soup fits); 0: never; -1: for launches of more than two searches per CU
     int waves = -1;         // wavefronts per workgroup (4 .. PDMPC_MAX_WAVES; -1: 16 for the InterX kernels — 12 for a launch of more than two searches per CU —, 12 for the separating-axis kernel)
     uint32_t spin_limit = 1u << 22;  // the watchdog's limit of polls / rounds (debugging: fail fast)
     int force_tie = 0;      // testing only: every search ends on the replay through the reference's binary heap (as if it had met equal keys)
@@ -216,9 +211,9 @@ namespace {
 bool parse_tuning(const char* text, Tuning& T, std::string& err) {
     struct Key { const char* name; int* dst; };
     int spin = (int)T.spin_limit;
-    const Key keys[] = {{"round0", &T.round0}, {"round", &T.round}, {"ramp", &T.ramp}, {"ready", &T.ready}, {"share_min", &T.share_min}, {"own_div", &T.own_div},
+    const Key keys[] = {{"round0", &T.round0}, {"round", &T.round}, {"ramp", &T.ramp}, {"ready", &T.ready}, {"share_min", &T.share_min},
                         {"tile", &T.tile}, {"mid_min", &T.mid_min}, {"mid_fill", &T.mid_fill}, {"tentative", &T.tentative}, {"fast_arrival", &T.fast_arrival}, {"helpers_first", &T.helpers_first}, {"seat_nodes", &T.seat_nodes},
-                        {"helpers", &T.helpers}, {"helpers_oversub", &T.helpers_oversub}, {"speculate", &T.speculate}, {"waves", &T.waves}, {"compact", &T.compact}, {"lazy_verify", &T.lazy_verify}, {"poll_every", &T.poll_every}, {"fast_select", &T.fast_select}, {"dispatch_order", &T.dispatch_order}, {"spin_limit", &spin},
+                        {"helpers", &T.helpers}, {"helpers_oversub", &T.helpers_oversub}, {"speculate", &T.speculate}, {"waves", &T.waves}, {"compact", &T.compact}, {"spin_limit", &spin},
                         {"force_tie", &T.force_tie}, {"reverse_dispatch", &T.reverse_dispatch}, {"debug_tail", &T.debug_tail}, {"debug_lds", &T.debug_lds},
                         {"debug_host", &T.debug_host}, {"debug_progress", &T.debug_progress}};
     std::string str(text ? text : "");
@@ -252,12 +247,15 @@ bool parse_tuning(const char* text, Tuning& T, std::string& err) {
             return false;
         }
     }
+    if (T.compact < -1 || T.compact > 1) {
+        err = "PDMPC_TUNING: compact takes -1, 0 or 1";
+        return false;
+    }
     if (T.round0 >= 0) T.round0 = std::max(1, T.round0);
     if (T.round >= 0) T.round = std::max(1, T.round);
     if (T.ramp >= 0) T.ramp = std::max(1, T.ramp);
     T.ready = std::min(2048, std::max(256, T.ready)) & ~63;
     if (T.share_min >= 0) T.share_min = std::max(32, T.share_min);
-    T.own_div = std::max(1, T.own_div);
     if (T.tile >= 0) T.tile = std::min(768, std::max(8, T.tile));
     T.mid_min = std::max(0, T.mid_min);
     T.mid_fill = std::max(256, T.mid_fill);
@@ -414,11 +412,7 @@ int compute_lds_bulk(pdmpc_handle* h, int n_launch, int soup_cap) {
         uint32_t nv = 0, nl = 0;
         const int waves = h->tune.waves >= 0 ? std::min(h->tune.waves, PDMPC_LK_COMPACT_WAVES) : PDMPC_LK_COMPACT_WAVES;
         const int ready = std::min(std::min(h->bk_ready_launch, 3 * PDMPC_WAVE * waves), (int)PDMPC_LK_COMPACT_READY_CAP);
-        // (compact=2, debugging: the compact kernel with the whole CU's LDS, i.e. ONE workgroup per CU — its layout without the co-residency)
-        // (compact=3: a little more than half — still one workgroup per CU, but with the small budget's few LDS-resident nodes)
-        if (layout_bulk(h, h->tune.compact == 2 ? kLdsMax : (h->tune.compact == 3 ? kLdsMax / 2 + 4096 : (h->tune.compact == 5 ? kLdsMax / 2 - 4096 : kLdsMax / 2)), waves, 0, soup_cap, L, nv, nl, (uint32_t)ready, true)) {
-            if (h->tune.compact == 5) L.total += 4096;  // (debugging: two workgroups per CU with 4 KB of slack behind the layout)
-            if (h->tune.compact == 4) L.total += 4096;  // (debugging: the half-CU layout, allocated too large for two workgroups per CU)
+        if (layout_bulk(h, kLdsMax / 2, waves, 0, soup_cap, L, nv, nl, (uint32_t)ready, true)) {
             if (h->tune.debug_lds)
                 fprintf(stderr, "pdmpc LDS layout (compact): launch %d waves %d near %u ready %d nv %u nl %u total %u\n", n_launch, waves, PDMPC_LK_COMPACT_BK_PER * (uint32_t)waves * PDMPC_WAVE, ready, nv, nl, L.total);
             h->bk_ready_launch = ready;
@@ -504,6 +498,9 @@ int check_set(const pdmpc_polygon_set& s, const char* what) {
 int pack_common(pdmpc_handle* h, int n, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index,
                 const pdmpc_polygon_set* fallback) {
     if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    // the weights are this pack's, whether it succeeds or not: a failed pack must not leave them to reorder the next one
+    const std::vector<double> weights = std::move(h->next_weights);
+    h->next_weights.clear();
     if (!h->has_mpa) return fail(PDMPC_ERR_NO_MPA, "pdmpc_upload_mpa has not been called");
     if (n < 0 || (n > 0 && !in)) return fail(PDMPC_ERR_INVALID, "bad vehicle array");
     if (n > h->max_vehicles) return fail(PDMPC_ERR_CAPACITY, "batch larger than config.max_vehicles");
@@ -553,7 +550,7 @@ int pack_common(pdmpc_handle* h, int n, const pdmpc_vehicle_in* in, const int32_
     // DAG, descending; ties by level, then by the caller's index.  A predecessor's priority is at least its successors' and its level
     // is lower, so this is a topological order too — every predecessor in a lower slot: the forward-progress argument holds
     // unchanged — and the records go back in the caller's order as for any batch the library reorders.
-    const bool by_priority = h->tune.dispatch_order && (int)h->next_weights.size() == n && n > 1 && pred_offset != nullptr;
+    const bool by_priority = (int)weights.size() == n && n > 1 && pred_offset != nullptr;
     if (pred_offset) {
         bool ordered = true;
         for (int i = 0; i < n && ordered; ++i)
@@ -596,7 +593,7 @@ int pack_common(pdmpc_handle* h, int n, const pdmpc_vehicle_in* in, const int32_
             if (by_priority) {
                 std::vector<double> prio((size_t)n);
                 for (int i = 0; i < n; ++i) {
-                    const double w = h->next_weights[(size_t)i];
+                    const double w = weights[(size_t)i];
                     prio[(size_t)i] = (w == w && w > 0) ? w : 0.0;
                 }
                 for (size_t qi = queue.size(); qi-- > 0;) {  // (reverse topological order: a vehicle after all its successors)
@@ -620,7 +617,6 @@ int pack_common(pdmpc_handle* h, int n, const pdmpc_vehicle_in* in, const int32_
             }
         }
     }
-    h->next_weights.clear();
     const bool permuted = !B.perm.empty();
     // Vehicles that hand over THE SAME ARRAYS (same pointers, same counts: the prioritization instances of an explorative step share
     // every input but the predecessor lists, PrioritizedExplorativeController.m:25-91; step_controller.cpp builds one set per distinct
@@ -904,7 +900,6 @@ int launch_range(pdmpc_handle* h, int first, int count, bool safe = false) {
     a.bk_round0 = T.round0 > 0 ? T.round0 : 24;  // (C3's class: below, once the helpers are counted)
     a.bk_round = std::min(h->bk_ready_launch / 2 - 16, std::max(a.bk_round0, T.round > 0 ? T.round : (helped ? 1000 : 256)));
     a.bk_ramp = T.ramp > 0 ? T.ramp : (helped ? 2 : 4);
-    a.bk_flags = (T.fast_select ? 1 : 0) | (T.lazy_verify ? 2 : 0) | ((std::min(8, std::max(1, T.poll_every)) - 1) << 2);
     a.bk_mid_min = T.mid_min;
     a.bk_mid_fill = T.mid_fill;
     a.bk_tile = T.tile > 0 ? T.tile : 256;

@@ -9,16 +9,6 @@
 #define PDMPC_BK_PER 2
 #define PDMPC_BULK_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
 #include <hip/hip_runtime.h>
-#ifdef PDMPC_COMPACT_FULL_BARRIER
-// (experiment: every workgroup barrier also waits for this wave's global stores and loads)
-__device__ __forceinline__ void pdmpc_full_barrier() {
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // (invalidates this CU's L1)
-}
-#define __syncthreads() pdmpc_full_barrier()
-#endif
 #include "bulk_search.hpp"
 
 PDMPC_BULK_KERNEL(pdmpc_bulk_kernel_compact, pdmpc_launch_bulk_compact, 1, PDMPC_CHECK_INTERX, PDMPC_LK_COMPACT_WAVES)

@@ -41,9 +41,6 @@
 #include "frontier_common.hpp"
 
 // shared words of the bulk kernel (aliases of words the frontier kernel uses for things this kernel does not have)
-#ifndef PDMPC_BK_CULL
-#define PDMPC_BK_CULL 0
-#endif
 #define BK_P2 3                   // ready entries a thread handles in the verdict pass (the ready list holds at most BK_P2 * blockDim entries)
 #define BK_PER PDMPC_BK_PER       // near entries per thread a selection pass holds in registers (near capacity = BK_PER * blockDim)
 #define BK_FAST_PER 4             // ... and per lane of the first wavefront when it selects alone (a small open set: at most 256 entries)
@@ -254,50 +251,6 @@ __device__ __forceinline__ void bk_check_items(const BkCheck& C, const Src& src,
         // (segments of the slots of predecessors that are still planning — `pend` — hold expected areas: a crossing there is tentative)
         const int rel0 = (which == 0 && base == so) ? t0 - C.l_lit[k - 1] : -(1 << 20);
         uint32_t found = 0;  // 1: crosses a real area, 2: crosses an expected one
-#if PDMPC_BK_CULL
-        // The exact bounding-box cull, built to be measured (-DPDMPC_BK_CULL=1; off in the product): a segment whose supporting line has
-        // the area's bounding box strictly on one side cannot pass C2 — the expression (y dx2 - x dy2) - S2 is monotone in x and in y
-        // under IEEE rounding, so its extremes over the box are taken at two corners and bound every point's value.  Survivors are
-        // collected in a bit mask first and tested afterwards (a lane-level skip inside the segment loop saves nothing: some lane of
-        // the 64 always needs the full test).  Results identical; C2 / C3 / C4 / C5: 1 040 / 1 003 / 69.6 / 458 steps/s against
-        // 1 067 / 1 031 / 71.3 / 478 without — the corner tests cost what the skipped C2 halves save, the survivors' loop runs as
-        // long as the lane with the most survivors, and eleven more live registers spill.
-        double bx0 = pt[0].x, bx1 = pt[0].x, by0 = pt[0].y, by1 = pt[0].y;
-#pragma unroll
-        for (int i = 1; i < PDMPC_VMAX; ++i) {
-            const bool in = i < ncols;
-            bx0 = (in && pt[i].x < bx0) ? pt[i].x : bx0;
-            bx1 = (in && pt[i].x > bx1) ? pt[i].x : bx1;
-            by0 = (in && pt[i].y < by0) ? pt[i].y : by0;
-            by1 = (in && pt[i].y > by1) ? pt[i].y : by1;
-        }
-        uint32_t surv = 0;
-        {
-            d2 c0 = q0;
-            for (int t = 0; t < tn; ++t) {
-                const d2 c1 = q[t + 1];
-                const double dx2 = c1.x - c0.x, dy2 = c1.y - c0.y;
-                const double S2 = dx2 * c0.y - dy2 * c0.x;
-                const double yhi = dx2 >= 0 ? by1 : by0, ylo = dx2 >= 0 ? by0 : by1;
-                const double xlo = dy2 >= 0 ? bx0 : bx1, xhi = dy2 >= 0 ? bx1 : bx0;
-                const double emax = (yhi * dx2 - xlo * dy2) - S2, emin = (ylo * dx2 - xhi * dy2) - S2;
-                const bool culled = emin > 0 || emax < 0;
-                surv |= culled ? 0u : (1u << t);
-                c0 = c1;
-            }
-        }
-        while (surv && !(found & 1u)) {
-            const int t = __builtin_ctz(surv);
-            surv &= surv - 1u;
-            asm volatile("" : "+v"(pt[0].x), "+v"(pt[0].y), "+v"(pt[1].x), "+v"(pt[1].y), "+v"(pt[2].x), "+v"(pt[2].y), "+v"(pt[3].x), "+v"(pt[3].y), "+v"(pt[4].x), "+v"(pt[4].y),
-                         "+v"(pt[5].x), "+v"(pt[5].y), "+v"(pt[6].x), "+v"(pt[6].y), "+v"(pt[7].x), "+v"(pt[7].y));
-            if (interx_segment_n<PDMPC_VMAX>(pt, ncols - 1, q[t], q[t + 1])) {
-                const int rel = rel0 + t;
-                const bool tent = rel >= 0 && ((pend >> (rel >> 3)) & 1ull) != 0ull;
-                found |= tent ? 2u : 1u;
-            }
-        }
-#else
         for (int t = 0; t < tn && !(found & 1u); ++t) {
             // (the area's points are made opaque per segment: the compiler would otherwise hoist the seven edges' dx1, dy1, S1 of the
             // C1 test out of this loop — 42 registers for a test that one segment in ten reaches)
@@ -311,7 +264,6 @@ __device__ __forceinline__ void bk_check_items(const BkCheck& C, const Src& src,
             }
             q0 = q1;
         }
-#endif
         if (found) __hip_atomic_fetch_or((lds_u32*)&r_flag[r], found, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
 }
@@ -422,35 +374,20 @@ __device__ __forceinline__ void bk_select(const lds_u32* bins, uint32_t target, 
 }
 
 // The areas of a result record and their column counts — all a successor reads of it (PrioritizedController.m:476-491) — go to memory
-// with agent-scope stores and are read with agent-scope loads: coherent across the XCDs' L2s by themselves.  PDMPC_BK_AREA_FENCES=1
-// (build switch) puts the release / acquire fences of rounds 2-4 back around them (a write-back / invalidation of the whole L2).
-#ifndef PDMPC_BK_AREA_FENCES
-#define PDMPC_BK_AREA_FENCES 0
-#endif
+// with agent-scope stores and are read with agent-scope loads: coherent across the XCDs' L2s by themselves, without the release /
+// acquire fences of rounds 2-4 (a write-back / invalidation of the whole L2).
 // The records a shared round posts for its helpers and everything else owner and helpers exchange likewise go through agent-scope
-// stores and loads; PDMPC_BK_POST_FENCES=1 (build switch) posts with plain stores behind a release fence and reads behind an acquire
-// fence instead, as rounds 2-4 did (every fence writes back / invalidates the whole L2 of its XCD: with a helper on every idle CU
-// that is every L2 of the chip, once per round).
-#ifndef PDMPC_BK_POST_FENCES
-#define PDMPC_BK_POST_FENCES 0
-#endif
+// stores and loads, not plain stores behind a release fence and reads behind an acquire fence as in rounds 2-4 (every fence writes
+// back / invalidates the whole L2 of its XCD: with a helper on every idle CU that is every L2 of the chip, once per round).
 __device__ __forceinline__ void bk_post_store(d2* p, d2 v) {
-#if PDMPC_BK_POST_FENCES
-    *p = v;
-#else
     __hip_atomic_store((double*)p, (double)v.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store((double*)p + 1, (double)v.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
 }
 __device__ __forceinline__ d2 bk_post_load(const d2* p) {
-#if PDMPC_BK_POST_FENCES
-    return *p;
-#else
     d2 v;
     v.x = __hip_atomic_load((const double*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     v.y = __hip_atomic_load((const double*)p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return v;
-#endif
 }
 __device__ __forceinline__ void bk_area_store(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void bk_area_store_u32(int32_t* p, int v) { __hip_atomic_store(p, (int32_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -573,10 +510,6 @@ __device__ __forceinline__ void bk_publish_flag(const KernelArgs& A, int slot, i
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     wave_sync();
     if (lane == 0) {
-#if PDMPC_BK_AREA_FENCES
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
         __hip_atomic_store(A.done_flag + slot, A.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
@@ -591,12 +524,6 @@ __device__ __forceinline__ unsigned long long bk_poll_flags(const KernelArgs& A,
     bool d = false;
     if ((want >> lane) & 1ull) d = __hip_atomic_load(A.done_flag + P.pred[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == A.epoch;
     const unsigned long long got = __ballot(d);
-#if PDMPC_BK_AREA_FENCES
-    if (got) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-#endif
     return got;
 }
 
@@ -746,10 +673,6 @@ __device__ __forceinline__ void bk_wait_done(const uint32_t* done_flag, const in
                 __builtin_amdgcn_s_sleep(1);
                 continue;
             }
-#if PDMPC_BK_AREA_FENCES
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
             bk_incorporate_body(out, pred, l_soup, l_soff, l_lit, Hp, got, lane, PDMPC_WAVE, chg);
             wave_sync();
             pend &= ~got;
@@ -791,10 +714,6 @@ __device__ __forceinline__ void bk_wait_done(const uint32_t* done_flag, const in
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             wave_sync();
             if (lane == 0) {
-#if PDMPC_BK_AREA_FENCES
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
                 __hip_atomic_store((uint32_t*)done_flag + slot, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (tk_pub) *tk_pub = __builtin_amdgcn_s_memrealtime();
             }
@@ -1210,7 +1129,6 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
     bool rec_valid = false, rec_written = false;  // the result record in HBM is the one this search would publish now / some record has been written
     bool vs_copied = false;                       // the LDS validity bytes have been copied to HBM since the tree last changed
     bool tie_replayed = false;                    // the search ended on bk_replay (its pop sequence is in the arena: pdmpc_debug_pop_trace)
-    bool unpark_req = false;                      // (bk_flags bit 1) parked nodes come back at the next boundary; the re-check of the collision-free nodes waits
     bool verify_req = false;                      // the next round boundary verifies the tree against the areas that were copied since the last verification (BK_FD)
     // shared rounds (helper workgroups)
     unsigned long long* board = A.help_board + (size_t)slot * PDMPC_HB_WORDS;
@@ -1232,7 +1150,6 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
         lane = l__;                                        \
     }
         // ================= a round =================
-        const bool ran_round = Rn != 0u;
         if (Rn) {
             pb_valid = false;  // (the tree grows: phase B's result is stale)
             rec_valid = false;
@@ -1263,7 +1180,7 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
                 share = seats != 0u;
             }
             if (share) {  // (uniform)
-                // the owner's part: a share as large as a helper's, less what posting and waiting cost it (1 / own_div of the round at most)
+                // the owner's part: a share as large as a helper's, and what the helpers' cap (bk_tile) leaves of the round
                 per_h = (Rn + seats) / (seats + 1u);
                 {
                     const uint32_t cap = (uint32_t)A.bk_tile;  // (a helper stages its range's records in LDS)
@@ -1289,9 +1206,6 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
                         const unsigned long long all = P.n_pred >= 64 ? ~0ull : ((1ull << P.n_pred) - 1ull);
                         __hip_atomic_store(board + PDMPC_HB_N, (unsigned long long)Rn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         __hip_atomic_store(board + PDMPC_HB_MASK, all & ~sh_load64(sh, SH_PEND_LO), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#if PDMPC_BK_POST_FENCES
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-#endif
                     }
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     wave_sync();
@@ -1338,9 +1252,6 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
                     }
                     if (lane == 0) {
                         if (bad) atomicOr((uint32_t*)&sh[FR_FLAGS], FRF_BUG);  // reported as an error status: must never happen
-#if PDMPC_BK_POST_FENCES
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
                         atomicAdd(A.work_count + 4, 1ull);
                         atomicAdd(A.work_count + 5, (unsigned long long)(Rn - own_n));
                     }
@@ -1583,11 +1494,7 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
         // for everybody who has arrived meanwhile; a running search verifies right behind the copy (measured: putting it off until
         // the search has nothing else to do leaves parked nodes parked and dead subtrees alive — C2's heavy steps 1.35 -> 1.75 ms).
         BK_MARK2
-        // (bk_flags bits 2-4, PDMPC_TUNING=poll_every=K: a search that has just run a round looks for arrivals at every K-th boundary
-        // only — an arrival event costs a running light search 15-25 us whatever it brings; a search that stalls or is done polls at once)
-        const uint32_t poll_k = ((uint32_t)A.bk_flags >> 2) & 7u;
-        const bool skip_poll = ran_round && poll_k != 0u && (sh[FR_ROUNDS] % (poll_k + 1u)) != 0u && sh[SH_STATE] != ST_ARRIVED;
-        if (!skip_poll && sh_load64(sh, SH_PEND_LO) != 0ull) {  // (uniform: written by thread 0 between barriers)
+        if (sh_load64(sh, SH_PEND_LO) != 0ull) {  // (uniform: written by thread 0 between barriers)
             if (wave == 0 && sh[SH_STATE] != ST_ARRIVED) (void)bk_poll_predecessors(A, P, sh, 0ull, lane);  // (a waiting search has polled already: bk_wait)
             __syncthreads();
             if (sh[SH_STATE] == ST_ARRIVED) {  // (uniform)
@@ -1610,42 +1517,11 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
                 }
                 __syncthreads();
                 // (putting the whole verification off until the search stalls or is done: C2 1 382 -> 1 212, C3 1 100 -> 939, C4 82.8 -> 71.4
-                // steps/s — parked nodes stayed parked.  bk_flags bit 1, PDMPC_TUNING=lazy_verify=1: the parked nodes come back at once,
-                // only the re-check of the collision-free nodes — which can take edges away, never add any — waits)
-                if (A.bk_flags & 2)
-                    unpark_req = true;
-                else
-                    verify_req = true;
+                // steps/s — parked nodes stayed parked)
+                verify_req = true;
             }
         }
         BK_TICK2(0)
-        if (unpark_req && !verify_req) {  // (uniform) the arrival's cheap half: parked nodes are open again and meet the real areas in a round
-            const uint32_t n_parked = sh[BK_NTENT];
-            uint32_t nn = sh[FR_NNODES];
-            nn = nn < S.max_nodes ? nn : S.max_nodes;
-            if (n_parked) {  // (uniform)
-                const bool fits = sh[FR_NEAR_N] + n_parked <= OC;
-                const double l_far = sh_ld_d(sh, FR_L_FAR);
-                for (uint32_t base = 0; base < nn; base += (uint32_t)bd) {  // (uniform trip count: wave-wide appends inside)
-                    const uint32_t i0 = base + (uint32_t)tid;
-                    const bool tent = i0 < nn && vs_load(VS, i0 < nn ? i0 : 0u) == VS_TENT;
-                    const double k = tent ? F.gkey[i0] : 0.0;
-                    if (tent) vs_store(VS, i0, VS_UNKNOWN);
-                    to_near(tent && fits && !(k > l_far), k, i0 + 1u);
-                    to_far(tent && !(fits && !(k > l_far)), k, i0 + 1u);
-                }
-                flush_near();
-                flush_far();
-                vs_copied = false;
-                __syncthreads();
-                if (tid == 0) {
-                    sh[BK_NTENT] = 0;
-                    sh_st_d(sh, BK_TENT_MIN, inf);
-                }
-                __syncthreads();
-            }
-        }
-        unpark_req = false;
         if (verify_req) {  // (uniform)
             verify_req = false;
             const unsigned long long arr = sh_load64(sh, BK_FD_LO);  // everybody whose areas were copied since the last verification
@@ -2167,7 +2043,7 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
         // entries a round takes decides when they are processed, not what the search finds), classifies and compacts with ballots.
         // No histogram, no workgroup scan, two barriers — the sixteen-wavefront selection below costs a light round 3.6-4.7 of its
         // 13-17 us (profiles/r05_step_profile_passes.txt).
-        if (nn_near <= (uint32_t)(BK_FAST_PER * PDMPC_WAVE) && (A.bk_flags & 1)) {  // (uniform)
+        if (nn_near <= (uint32_t)(BK_FAST_PER * PDMPC_WAVE)) {  // (uniform)
             BK_TICK3(4)
             // (the other wavefronts may be anywhere behind the last barrier, still reading the shared words the boundary's decisions
             // rest on — near's count and key range, the flags —: they are through before the first wavefront rewrites them)
@@ -2625,11 +2501,6 @@ __device__ __forceinline__ void bulk_helper_body(const KernelArgs& A) {
             uint32_t cmd = 0;
             if (seq != last_seq && seq != 0u) {
                 cmd = 1;
-#if PDMPC_BK_POST_FENCES
-                // what the owner wrote before it assigned (and the predecessors it had seen) is visible from here on; not on an idle
-                // poll: the fence empties this XCD's L2, which searches on neighbouring CUs share
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
                 const unsigned long long mask = __hip_atomic_load(board + PDMPC_HB_MASK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (lane == 0) {
                     hs[HS_FIRST] = (uint32_t)((w >> 20) & 0xfffffull);

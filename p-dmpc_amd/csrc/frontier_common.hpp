@@ -528,9 +528,6 @@ __device__ PhaseB fr_phase_b(const KernelArgs& A, Ctx& X, const Frontier& F, con
     const int n = EE.n, nw = NW > 0 ? NW : EE.nw;
     lds_u32* pkw = cnt_ch + PDMPC_HP_MAX + 2;                              // [HP_MAX + 1] packed words of the path nodes
     ch_d[tid] = 0;
-#ifdef PDMPC_PB_INVALIDATE_L1
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // (experiment: phase B reads nothing from this CU's L1 that was cached before)
-#endif
     // G's path: the selection's relevance tables hold it when G was the best candidate at the last round boundary (the usual
     // end of a search) — then its keys and packed words are one parallel load; else walked from G
     const bool have_path = goal && F.sh[FR_PATH_FOR] == goal;

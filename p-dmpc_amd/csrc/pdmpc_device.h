@@ -213,7 +213,6 @@ struct KernelArgs {
     // helper workgroups (blockIdx >= n_searches): CUs the launch leaves idle check tiles of other workgroups' large rounds
     int32_t n_searches;              // workgroups of this launch that run a search (the first ones)
     int32_t n_helpers;               // helper workgroups behind them (0: none)
-    int32_t bk_flags;                // bit 0: a small open set is selected by the first wavefront alone (PDMPC_TUNING=fast_select; bulk_search.hpp)
     unsigned long long* help_board;  // [slot][PDMPC_HB_WORDS]: see above
     uint32_t* help_verdict;          // [slot][PDMPC_HELP_CAP] 1 collision-free, 2 colliding, 3 crosses expected areas only (written by helpers)
     uint32_t* help_finished;         // searches that have published their result (runs on from launch to launch) ...

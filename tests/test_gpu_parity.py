@@ -261,6 +261,29 @@ def test_a_failed_pack_leaves_its_bank_empty():
     h.close()
 
 
+def test_a_failed_pack_consumes_the_step_weights():
+    """pdmpc_set_step_weights holds for the next pack only, also when that pack fails: weights that would put the batch into priority
+    order, a pack that fails (its coupling graph has a cycle), then a level-ordered batch packed without weights keeps its slots —
+    a range launch on it is allowed (include/pdmpc.h) — and its records are the oracle's."""
+    from pdmpc.backend import BackendError
+
+    options, mpa, iters = problems.problem_set("interx", 11, 4, Hp=6)
+    preds = [[], [], [0], [1]]  # (levels 1, 1, 2, 2: vehicle 3's weight puts its predecessor 1 in front of vehicle 0)
+    prob = {"iters": iters, "preds": preds, "fallback": [None] * 4, "level_sizes": [2, 2]}
+    ref, _ = _oracle().plan_step(options, mpa, prob)
+    h = Handle(options)
+    h.upload_mpa(mpa)
+    h.set_step_weights([1.0, 1.0, 1.0, 100.0])
+    with pytest.raises(BackendError):
+        h.pack_step(iters[:2], [[1], [0]], [[], []])
+    h.pack_step(iters, preds, [[]] * 4)
+    h.begin_step()
+    h.launch_range(0, 1)
+    h.launch_range(1, 3)
+    assert_records_equal(h.fetch(4), ref, "level order after a failed weighted pack")
+    h.close()
+
+
 def test_interx_with_hdv_reachable_sets():
     """are_constraints_satisfied_interx.m:23-31: the HDV soup is a third curve set checked with the normal-offset area."""
     options, mpa, iters = problems.problem_set("interx", 31, 16, Hp=6, n_hdv=2)
@@ -325,8 +348,8 @@ def test_random_road_problems_never_fall_back():
         "waves=5,round0=7",
         "helpers=0",
         "helpers=3,share_min=64,tile=32",
-        "helpers=200,share_min=64,own_div=2",
-        "share_min=64,own_div=64,tile=128",
+        "helpers=200,share_min=64",
+        "share_min=64,tile=128",
         "round0=1,ramp=16",
         "round0=200,round=512,ramp=1",
         "round0=1000,round=1000,ramp=1,share_min=64,tile=32",  # rounds of up to two thousand nodes, most of them shared
@@ -354,8 +377,12 @@ def test_tuning_switches_do_not_change_results(tuning, monkeypatch):
     check_batch(options, mpa, iters)
 
 
-def test_unknown_tuning_key_is_an_error(monkeypatch):
-    monkeypatch.setenv("PDMPC_TUNING", "round0=24,no_such_knob=1")
+# (retired keys: removed switches of experiments that were measured and dropped; compact takes -1, 0 or 1)
+@pytest.mark.parametrize(
+    "entry", ["no_such_knob=1", "lazy_verify=1", "poll_every=2", "fast_select=0", "own_div=8", "dispatch_order=0", "compact=2"]
+)
+def test_unknown_tuning_key_is_an_error(monkeypatch, entry):
+    monkeypatch.setenv("PDMPC_TUNING", "round0=24," + entry)
     options = problems.make_options("interx", Hp=6)
     with pytest.raises(Exception):
         Handle(options)
