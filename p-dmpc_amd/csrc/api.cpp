@@ -289,7 +289,7 @@ struct pdmpc_handle {
     DevBuf<NodeRec> anodes;
     DevBuf<double> akey, afark, amidk, apbk, awalk;
     DevBuf<unsigned long long> alink;
-    DevBuf<uint32_t> afari, amidi, apbd, achild0;
+    DevBuf<uint32_t> afari, amidi, apbd, achild0, avlist;
     DevBuf<uint8_t> avs;
     DevBuf<pdmpc_vehicle_out> d_out;
     DevBuf<uint32_t> d_flag;
@@ -804,6 +804,8 @@ int pack_common(pdmpc_handle* h, int n, const pdmpc_vehicle_in* in, const int32_
 
 // per-vehicle arenas for `nodes` tree nodes each (contents are scratch: every search starts from an empty tree)
 const size_t kArenaBytesPerNode = sizeof(NodeRec) + 8 + 8 + 1 + 8 + 4 + 8 + 4 + 8 + 4 + 16 + 4;
+// ... and the verification's lists (NodeArena::vlist): Hp + 1 entries of 4 bytes per node
+size_t arena_bytes_per_node(const pdmpc_handle* h) { return kArenaBytesPerNode + 4 * (size_t)(h->cfg.Hp + 1); }
 int alloc_arenas(pdmpc_handle* h, uint32_t nodes) {
     nodes = (nodes + 1u) & ~1u;
     const size_t tot = (size_t)h->max_vehicles * nodes;
@@ -819,10 +821,12 @@ int alloc_arenas(pdmpc_handle* h, uint32_t nodes) {
     h->apbd.release();
     h->awalk.release();
     h->achild0.release();
+    h->avlist.release();
     h->max_nodes = 0;
     int bad = 0;
     bad |= h->anodes.ensure_exact(tot) | h->akey.ensure_exact(tot) | h->alink.ensure_exact(tot) | h->avs.ensure_exact(tot) | h->afark.ensure_exact(tot) | h->afari.ensure_exact(tot);
     bad |= h->amidk.ensure_exact(tot) | h->amidi.ensure_exact(tot) | h->apbk.ensure_exact(tot) | h->apbd.ensure_exact(tot) | h->awalk.ensure_exact(2 * tot) | h->achild0.ensure_exact(tot);
+    bad |= h->avlist.ensure_exact(tot * (size_t)(h->cfg.Hp + 1));
     if (bad) return bad;
     h->max_nodes = nodes;
     return 0;
@@ -872,6 +876,7 @@ int launch_range(pdmpc_handle* h, int first, int count, bool safe = false) {
     a.arena.pb_d = h->apbd.p;
     a.arena.walk = h->awalk.p;
     a.arena.child0 = h->achild0.p;
+    a.arena.vlist = h->avlist.p;
     a.max_nodes = h->max_nodes;
     a.tree_size = h->d_tree_size.p;
     a.lds = h->lds;
@@ -1123,6 +1128,7 @@ int pdmpc_destroy(pdmpc_handle* h) {
     h->apbd.release();
     h->awalk.release();
     h->achild0.release();
+    h->avlist.release();
     h->d_out.release();
     h->h_out.release();
     h->h_lean.release();
@@ -1409,7 +1415,7 @@ int plan_packed_growing(pdmpc_handle* h, int32_t n, pdmpc_vehicle_out* out, int3
         if ((h->max_nodes_limit && next > h->max_nodes_limit) || next > (1ull << 30)) return PDMPC_OK;  // statuses tell
         size_t free_b = 0, total_b = 0;
         (void)hipMemGetInfo(&free_b, &total_b);
-        const size_t per_node = kArenaBytesPerNode;
+        const size_t per_node = arena_bytes_per_node(h);
         const size_t have = (size_t)h->max_vehicles * h->max_nodes * per_node;
         if ((size_t)h->max_vehicles * next * per_node > free_b + have) return PDMPC_OK;  // no room to grow
         const uint32_t before = h->max_nodes;

@@ -281,18 +281,28 @@ __device__ __forceinline__ int nth_bit(uint64_t mask, int rk) {
     return (int)__builtin_ctzll(mask);
 }
 
-// Late predecessors (PrioritizedController.m:476-491): the collision-free nodes of `list` against the areas of the predecessors in
-// `arr`, which have just entered the soup, as far as those differ from the areas the edges were checked against (chg, see
-// bk_incorporate_body).  item = (node, j): the j-th such predecessor of the node's step, j < maxc = the most any step has; the edge's
+// Late predecessors (PrioritizedController.m:476-491): the collision-free nodes of the steps' lists (vlist: list k - 1 of step k at
+// k - 1 times cap, vcnt[k - 1] entries) against the areas of the predecessors in `arr`, which have just entered the soup, as far as
+// those differ from the areas the edges were checked against (chg, see bk_incorporate_body).  item = (entry, j): the j-th such
+// predecessor of the entry's step, dense over the steps (items = the sum over k of entries x due predecessors; predecessor-major
+// within a step, so that a wave reads consecutive entries); entries that have lost their edge since are skipped.  The edge's
 // area is transformed once, the predecessor's polygon of the node's step goes through interx_segment_n segment by segment
 // (InterX.m:63-76 restricted to those polygons).
 template <int CHECKER>
-__device__ __forceinline__ void bk_recheck_items(const Search& S, const VState& VS, const BkCheck& C, const SpecCtx& P, const lds_u32* list, uint32_t count, unsigned long long arr,
-                                                 const lds_u64s* chg, uint32_t maxc, volatile lds_u32* sh, int tid, int nthreads) {
-    const uint32_t items = count * maxc;
+__device__ __forceinline__ void bk_recheck_items(const Search& S, const VState& VS, const BkCheck& C, const SpecCtx& P, const uint32_t* vlist, const lds_u32* vcnt, uint32_t cap,
+                                                 uint32_t items, unsigned long long arr, const lds_u64s* chg, volatile lds_u32* sh, int tid, int nthreads) {
     for (uint32_t item = (uint32_t)tid; item < items; item += (uint32_t)nthreads) {
-        const uint32_t v = item / maxc, a = item - v * maxc;
-        const uint32_t i0 = list[v];
+        uint32_t v = item, n_k = 0;
+        int ks = 1;
+        for (; ks <= C.Hp; ++ks) {  // the step whose items hold this one
+            n_k = vcnt[ks - 1] < cap ? vcnt[ks - 1] : cap;
+            const uint32_t m = n_k * (uint32_t)__builtin_popcountll(chg[ks - 1] & arr);
+            if (v < m) break;
+            v -= m;
+        }
+        const uint32_t a = v / n_k;
+        const uint32_t i0 = vlist[(size_t)(ks - 1) * cap + (v - a * n_k)];
+        if (vs_load(VS, i0) != VS_VALID) continue;
         uint32_t parent, packed;
         piece_link(node_piece(S, i0, 3), parent, packed);
         if (!parent) continue;
@@ -1007,8 +1017,17 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
         tk[TK_MARK] = tk[TK_START] = __builtin_amdgcn_s_memrealtime();
     }
     lds_u64s* chg = (lds_u64s*)((lds_u32*)((lds_d2*)(X.lsm + PDMPC_LK_PSHAPE) + Hp * PDMPC_VMAX) + PDMPC_HP_MAX);  // [HP_MAX] areas that differ from the expected ones (bk_incorporate_body)
-    if (tid < PDMPC_HP_MAX) chg[tid] = 0ull;  // (read behind the barriers of the first round)
-    lds_vu64* tk2 = (lds_vu64*)(gp_path + 242);  // [7] (diagnostics) the arrival handling in detail: poll + copy, re-check, parked nodes, bookkeeping + candidates, record + flag of a finished search
+    // The collision-free nodes of step k (1..Hp) in the order the rounds found them, and the parked nodes: Hp + 1 lists of max_nodes
+    // entries in the arena (a node is collision-free at most once: that verdict can only be withdrawn; it is parked at most once
+    // between two verifications).  What a verification visits; their lengths are the LDS words vcnt[k - 1] and BK_NTENT.
+    lds_u32* vcnt = (lds_u32*)(chg + PDMPC_HP_MAX);  // [HP_MAX]
+#define BK_VLIST(k) (A.arena.vlist + ((size_t)slot * (size_t)(Hp + 1) + (size_t)((k) - 1)) * A.max_nodes)
+#define BK_PLIST BK_VLIST(Hp + 1)
+    if (tid < PDMPC_HP_MAX) {  // (read behind the barriers of the first round)
+        chg[tid] = 0ull;
+        vcnt[tid] = 0u;
+    }
+    lds_vu64* tk2 = (lds_vu64*)(gp_path + 242);  // [7] (diagnostics) the arrival handling in detail: poll + copy, re-check items, parked nodes' return, bookkeeping + candidates, record + flag of a finished search, finding the nodes to re-check; mark
     if (ticking)
         for (int i = 0; i < 7; ++i) tk2[i] = 0ull;
 #define BK_TICK2(i)                                                        \
@@ -1299,8 +1318,19 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
                     piece_link(node_piece(S, i0, 3), parent, packed);
                     const int k = NODE_K(packed);
                     vs_store(VS, i0, valid ? VS_VALID : (parked ? VS_TENT : VS_INVALID));
+                    if (valid && parent) {  // into the list of its step (one LDS atomic per lane; the list's order does not matter)
+                        const uint32_t pos = __hip_atomic_fetch_add((lds_u32*)&vcnt[k - 1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if (pos < A.max_nodes)
+                            BK_VLIST(k)[pos] = i0;
+                        else
+                            atomicOr((uint32_t*)&sh[FR_FLAGS], FRF_BUG);  // (a node entered twice: must never happen)
+                    }
                     if (parked) {  // (rare: one LDS atomic each)
-                        sh_add(sh, BK_NTENT, 1u);
+                        const uint32_t pos = sh_add(sh, BK_NTENT, 1u);
+                        if (pos < A.max_nodes)
+                            BK_PLIST[pos] = i0;
+                        else
+                            atomicOr((uint32_t*)&sh[FR_FLAGS], FRF_BUG);
                         sh_min_d(sh, BK_TENT_MIN, F.gkey[i0]);
                     }
                     if (parent) {  // the pairs the reference's InterX forms for this edge (InterX.m:63-76): (V - 1) x (M - 1) per soup
@@ -1528,44 +1558,22 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
             uint32_t nn = sh[FR_NNODES];
             nn = nn < S.max_nodes ? nn : S.max_nodes;
             // Only collision-free nodes can lose their edge, and only to an area that differs from the one their edge was checked
-            // against (chg: for a predecessor that carries on with its last plan that is the horizon's step alone).  They are gathered
-            // first, a list's worth of the tree at a time, so that the items are dense: an item is a chain of two dependent reads of
-            // the tree and seven segment tests, and lanes that skip theirs cost what the busy lanes of their wave cost (C2's last
-            // vehicles, 15 predecessors each: 25-30 us per arrival event with every node x predecessor an item).
-            uint32_t maxc = 0;
-            for (int k = 0; k < Hp; ++k) {  // (uniform)
-                const uint32_t c = (uint32_t)__builtin_popcountll(chg[k] & arr);
-                maxc = c > maxc ? c : maxc;
-            }
+            // against (chg: for a predecessor that carries on with its last plan that is the horizon's step alone).  The lists of the
+            // steps with such areas hold them (and nodes that have lost their edge since: skipped); item = (entry, j), the j-th due
+            // predecessor of that step, dense over the steps' lists — an item is a chain of two dependent reads of the tree and seven
+            // segment tests, and lanes without one cost what the busy lanes of their wave cost.  No pass over the tree.
+            uint32_t items = 0;
+            for (int k = 0; k < Hp; ++k)  // (uniform; a count beyond max_nodes is FRF_BUG: the append has reported it)
+                items += (vcnt[k] < A.max_nodes ? vcnt[k] : A.max_nodes) * (uint32_t)__builtin_popcountll(chg[k] & arr);
             if (ticking) {
                 unsigned long long due = 0;
                 for (int k = 0; k < Hp; ++k) due += (unsigned long long)__builtin_popcountll(chg[k] & arr);
                 atomicAdd(A.work_count + 14, due);
                 atomicAdd(A.work_count + 15, (unsigned long long)(Hp * __builtin_popcountll(arr)));
             }
-#pragma unroll 1
-            for (uint32_t base0 = 0; base0 < nn && maxc != 0u;) {  // (uniform trip counts: barriers inside)
-                if (tid == 0) sh[FR_VLIST_N] = 0;
-                __syncthreads();
-                uint32_t b = base0;
-                for (; b < nn && b - base0 + (uint32_t)bd <= (uint32_t)FR_NBINS; b += (uint32_t)bd) {  // (the list holds FR_NBINS nodes)
-                    const uint32_t i0 = b + (uint32_t)tid;
-                    const uint32_t j0 = i0 < nn ? i0 : 0u;
-                    const int k = NODE_K((uint32_t)(F.glink[j0] >> 32));
-                    const bool v = i0 < nn && k > 0 && vs_load(VS, j0) == VS_VALID && (chg[k > 0 ? k - 1 : 0] & arr) != 0ull;
-                    const unsigned long long bal = __ballot(v);
-                    if (bal) {
-                        const uint32_t pos0 = sh_add_uniform(sh, FR_VLIST_N, (uint32_t)__builtin_popcountll(bal), lane);
-                        if (v) hist[pos0 + lane_rank(bal, lane)] = i0;
-                    }
-                }
-                __syncthreads();
-                base0 = b;
-                BK_TICK2(5)
-                const uint32_t cnt = sh[FR_VLIST_N];
-                bk_recheck_items<CHECKER>(S, VS, CK, P, hist, cnt, arr, chg, maxc, sh, tid, bd);
-                __syncthreads();
-            }
+            BK_TICK2(5)
+            bk_recheck_items<CHECKER>(S, VS, CK, P, BK_VLIST(1), vcnt, A.max_nodes, items, arr, chg, sh, tid, bd);
+            __syncthreads();
             BK_TICK2(1)
             flags = sh[FR_FLAGS];
             // Nodes lost their edges.  The best candidate survives unless one of its own path did (a published plan's path always
@@ -1582,12 +1590,14 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
             // parked nodes (their edges crossed expected areas only) come back into the open set: never evaluated, as far as anybody
             // can tell — a round will check them against what the soup holds then.  (reopen: the rebuild below finds them in the tree)
             const uint32_t n_parked = sh[BK_NTENT];
-            if (n_parked) {  // (uniform)
+            if (n_parked) {  // (uniform) the list of parked nodes, not the tree
                 const bool fits = sh[FR_NEAR_N] + n_parked <= OC;
                 const double l_far = sh_ld_d(sh, FR_L_FAR);
-                for (uint32_t base = 0; base < nn; base += (uint32_t)bd) {  // (uniform trip count: wave-wide appends inside)
-                    const uint32_t i0 = base + (uint32_t)tid;
-                    const bool tent = i0 < nn && vs_load(VS, i0 < nn ? i0 : 0u) == VS_TENT;
+                const uint32_t n_list = n_parked < A.max_nodes ? n_parked : A.max_nodes;
+                for (uint32_t base = 0; base < n_list; base += (uint32_t)bd) {  // (uniform trip count: wave-wide appends inside)
+                    const uint32_t e = base + (uint32_t)tid;
+                    const uint32_t i0 = e < n_list ? BK_PLIST[e] : 0u;
+                    const bool tent = e < n_list && vs_load(VS, i0) == VS_TENT;
                     const double k = tent ? F.gkey[i0] : 0.0;
                     if (tent) vs_store(VS, i0, VS_UNKNOWN);
                     const bool push = tent && !reopen;

@@ -9,7 +9,7 @@
 #define FR_NNODES 32    // tree size (atomic reservation of node indices)
 #define FR_RD_HEAD 33   // ready list: next entry to claim
 #define FR_RD_TAIL 34   // ready list: entries reserved
-#define FR_VLIST_N 35   // arrival handling: entries of the list of collision-free nodes that are being re-checked
+#define FR_VLIST_N 35   // (free since the verification reads lists kept by the rounds, bulk_search.hpp BK_VLIST; still in the debug stage record)
 #define FR_NEAR_N 36
 #define FR_FAR_N 37
 #define FR_FLAGS 38     // FRF_*

@@ -115,7 +115,7 @@ struct LdsLayout {
 #define PDMPC_LKX_HIST(W, RC, P) (PDMPC_LKX_READY(W, P) + (uint32_t)(RC) * 8u)
 #define PDMPC_LKX_MISC(W, RC, P) (PDMPC_LKX_HIST(W, RC, P) + 3072u * 4u)
 #define PDMPC_LKX_PSHAPE(W, RC, P) (PDMPC_LKX_MISC(W, RC, P) + 2048u)
-#define PDMPC_LKX_FIXED_END(W, RC, P) (PDMPC_LKX_PSHAPE(W, RC, P) + PDMPC_LK_ALIGN16(PDMPC_HP_MAX * PDMPC_VMAX * 16u + PDMPC_HP_MAX * 4u + PDMPC_HP_MAX * 8u))
+#define PDMPC_LKX_FIXED_END(W, RC, P) (PDMPC_LKX_PSHAPE(W, RC, P) + PDMPC_LK_ALIGN16(PDMPC_HP_MAX * PDMPC_VMAX * 16u + PDMPC_HP_MAX * 4u + PDMPC_HP_MAX * 8u + PDMPC_HP_MAX * 4u))
 #ifndef PDMPC_BK_PER
 #define PDMPC_BK_PER 4
 #endif
@@ -147,6 +147,7 @@ struct NodeArena {  // HBM arrays, per-vehicle stride = max_nodes entries
     uint32_t* pb_d;    // phase B: where a node's branch leaves the goal's path; a replay: the node's id in the reference's tree
     double* walk;      // per node, 16 bytes: what its branch to the goal candidate's path looks like (bk_classify_wave)
     uint32_t* child0;  // 1-based arena index of a node's first child (its children are consecutive, ascending trim), 0 while it has none: what the replay of a tied search descends by
+    uint32_t* vlist;   // per vehicle Hp + 1 lists of max_nodes entries: the collision-free nodes of steps 1 .. Hp, the parked nodes (what a verification visits)
 };
 
 // the fixed part of the graph search's layout for (W wavefronts, ready list of RC entries): what the kernel built with those two

@@ -1,6 +1,7 @@
 """Where a time step's time goes in the frontier kernel: per vehicle rounds, nodes processed vs popped, and the 100 MHz
 tick counters of the round phases and of the helper workgroups (PDMPC_TUNING=debug_tail=1, set here); PROFILE_CHAIN=1: when every
-vehicle's areas went out; PROFILE_ROUNDS=1: the round sizes of the heaviest search; PROFILE_TOP=n: the n slowest vehicles per step."""
+vehicle's areas went out and what its verifications cost (re-check = scan, which finds the
+collision-free nodes due for a re-check, + items, the re-checks themselves); PROFILE_ROUNDS=1: the round sizes of the heaviest search; PROFILE_TOP=n: the n slowest vehicles per step."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "p-dmpc_amd"), os.path.join(ROOT, "tests")]
@@ -49,8 +50,9 @@ for b, prob in enumerate(probs):
             pr = prob["preds"][v]
             last = max([pub[q] for q in pr], default=0.0)
             la = (T[v][14][7] - origin) / 100.0 if T[v][14][7] > 0 else 0.0
-            print("   chain veh %2d level %2d preds %2d | busy %4.0f us | areas out %4.0f us (hop %4.0f) | end %4.0f us | last arrival into the running search %4.0f us at round %2d of %2d | %2d verifications %3.0f us (copy %.0f re-check %.0f parked %.0f candidates %.0f record+flag %.0f; of the re-check: gathering %.0f)" % (
-                v, prob["levels"][v], len(pr), T[v][14][0] / 100.0 + T[v][15][0] / 100.0 + T[v][15][2] / 100.0, pub[v], pub[v] - last, end[v], la, int(T[v][14][6]), int(T[v][16][0]), int(T[v][16][6]), T[v][15][1] / 100.0, T[v][13][0] / 100.0, T[v][13][1] / 100.0, T[v][13][2] / 100.0, T[v][13][3] / 100.0, T[v][13][4] / 100.0, T[v][13][5] / 100.0))
+            print("   chain veh %2d level %2d preds %2d | busy %4.0f us | areas out %4.0f us (hop %4.0f) | end %4.0f us | last arrival into the running search %4.0f us at round %2d of %2d | %2d verifications %3.0f us (copy %.0f re-check %.0f [scan %.0f items %.0f] parked %.0f candidates %.0f record+flag %.0f)" % (
+                v, prob["levels"][v], len(pr), T[v][14][0] / 100.0 + T[v][15][0] / 100.0 + T[v][15][2] / 100.0, pub[v], pub[v] - last, end[v], la, int(T[v][14][6]), int(T[v][16][0]), int(T[v][16][6]), T[v][15][1] / 100.0, T[v][13][0] / 100.0,
+                (T[v][13][1] + T[v][13][5]) / 100.0, T[v][13][5] / 100.0, T[v][13][1] / 100.0, T[v][13][2] / 100.0, T[v][13][3] / 100.0, T[v][13][4] / 100.0))
     if os.environ.get("PROFILE_SEATS"):  # the P1 passes of the step's largest search by the number of seated helpers
         v = max(range(len(recs)), key=lambda i: np.asarray(recs[i]["path_nodes"])[16][1])
         t = np.asarray(recs[v]["path_nodes"])
