@@ -32,6 +32,7 @@ extern "C" {
 
 #define PDMPC_HP_MAX 16 /* largest prediction horizon Hp accepted (BASELINE configs use 5..10) */
 #define PDMPC_VMAX 8    /* columns reserved per maneuver area (reference: 5, 6 or 7; generate_maneuver.m:74-101) */
+#define PDMPC_JOINT_MAX 4 /* vehicles per joint problem (pdmpc_plan_joint) */
 
 /* status codes (function results and pdmpc_vehicle_out.status) */
 enum {
@@ -148,7 +149,9 @@ typedef struct {
     int64_t edge_checks;       /* eval_edge_exact evaluations since pdmpc_create / pdmpc_reset_stats (incl. the ones the reference never makes) */
     int64_t segment_pair_tests;/* (area segment, obstacle segment) pairs those checks stand for: sum of (V-1)(M-1) per soup,
                                   InterX.m:63-76 (InterX checker only) */
-    int64_t kernel;            /* kernel of the last launch: 2 the graph search (bulk-synchronous rounds), 3 the sampled optimizer */
+    int64_t kernel;            /* kernel of the last launch: 2 the graph search (bulk-synchronous rounds), 3 the sampled optimizer,
+                                  4 the joint search of centralized control (pdmpc_plan_joint: n_vehicles, nodes_popped and
+                                  nodes_generated count each problem once; obstacle_columns and algorithmic_bytes are 0) */
     int64_t nodes_processed;   /* nodes whose edge was evaluated (same period; the reference pops nodes_popped of them, the rest is what
                                   the parallel rounds overshoot) */
     int64_t rounds;            /* rounds (select a batch of the smallest open keys, process it) */
@@ -342,6 +345,21 @@ int pdmpc_debug_heap_script(pdmpc_handle* handle, int32_t n, const int32_t* op, 
  * chosen descent, path_nodes rows with g = -1 except the cost of the chosen node, h = -1, k = 1..Hp+1 (:223-244). */
 int pdmpc_plan_batch_sampled(pdmpc_handle* handle, int32_t n_vehicles, const pdmpc_vehicle_in* in, const uint32_t* seeds,
                              pdmpc_vehicle_out* out);
+
+/* ---- centralized control: one joint graph search over several vehicles (CentralizedController.m:34-46, GraphSearch.do_graph_search
+ *      with iter.amount = N; separating-axis checker only) ----
+ * n_problems independent joint searches in one launch.  Problem p = vehicles in[problem_offset[p] .. problem_offset[p+1]), 1 to
+ * PDMPC_JOINT_MAX of them.  Each vehicle's obstacles and dynamic_obstacles are the sets its own check reads (a caller mirroring the
+ * reference passes the scenario's sets to every vehicle); hdv_reachable_sets is ignored.  A tree node holds one pose and trim per
+ * vehicle; children are the Cartesian product of the vehicles' successor trims, vehicle 1 varying fastest (expand_node.m:15-29), and
+ * a node is valid iff no vehicle's area meets an obstacle, a lower-numbered vehicle's area of the same node, or its lanelet boundary
+ * (GraphSearch.m:130-193, are_constraints_satisfied_sat.m).  out[i] = vehicle i's slice of its problem's ControlResultsInfo:
+ * status / n_expanded / n_popped / tree_path shared by the problem, its own predicted_trims, y_predicted, shapes; path_nodes rows
+ * (x_v, y_v, yaw_v, trim_v, g, h, k, 1) with the joint g and h.  The arena holds config.max_nodes joint nodes per problem and grows
+ * as for pdmpc_plan_batch (PDMPC_ARENA_OVERFLOW only at the limit).  PDMPC_ERR_INVALID for a handle whose checker is not
+ * PDMPC_CHECK_SAT, for a problem of 0 or more than PDMPC_JOINT_MAX vehicles, and for a NULL out with vehicles to plan. */
+int pdmpc_plan_joint(pdmpc_handle* handle, int32_t n_problems, const int32_t* problem_offset, const pdmpc_vehicle_in* in,
+                     pdmpc_vehicle_out* out);
 
 /* ---- the caller's side of the boundary, natively (csrc/step_controller.cpp) ----
  * One MPC time step of the prioritized sequential controller around pdmpc_plan_step, without any interpreter in the loop:

@@ -19,6 +19,8 @@
  *                            predecessors' solved areas handed over on the device (PrioritizedController.m:476-491)
  *   pdmpc_ml_group_plan_step the same step over several GPUs: the per-level exchange of solved areas between the vehicles
  *                            (hlc/communication/PredictionsCommunication.m:34-63) as an RCCL all-gather between the devices
+ *   pdmpc_ml_plan_joint      the centralized controller's run_optimizer call (CentralizedController.m:34-46): ONE joint search
+ *                            over the iter.amount vehicles of an unfiltered IterationData (GraphSearch.do_graph_search)
  *   pdmpc_ml_record_arrays   the fields of ControlResultsInfo in MATLAB's layout (OptimizerInterface.m:63-101)
  */
 #ifndef PDMPC_MATLAB_H
@@ -92,6 +94,28 @@ int pdmpc_ml_plan_step_weighted(pdmpc_handle* handle, const pdmpc_ml_step* step,
 int pdmpc_ml_group_plan_step(pdmpc_group* group, const pdmpc_ml_step* s, const double* weights, int32_t mode, pdmpc_vehicle_out* out);
 /* convenience: n uncoupled vehicles (one computation level) in one launch */
 int pdmpc_ml_plan_level(pdmpc_handle* handle, int32_t Hp, int32_t n, const pdmpc_ml_iter* iters, pdmpc_vehicle_out* out);
+
+/* ---- centralized control: the IterationData of ALL vehicles (IterationData.m:4-33, amount = N) ----
+ * Row v of every per-vehicle field is vehicle v; obstacles and dynamic_obstacle_area are the scenario's, shared by the vehicles
+ * (are_constraints_satisfied_sat.m reads iter.obstacles / iter.dynamic_obstacle_area for every vehicle). */
+typedef struct {
+    int32_t amount;                            /* iter.amount = N, 1 .. PDMPC_JOINT_MAX */
+    pdmpc_ml_matrix x0;                        /* iter.x0: N x (>= 3): x, y, yaw (, speed ...) per row */
+    pdmpc_ml_matrix trim_indices;              /* iter.trim_indices: N elements, 1-based */
+    const double* reference_trajectory_points; /* iter.reference_trajectory_points: N x Hp x 2, (v, k, c) at v + k N + c N Hp */
+    pdmpc_ml_matrix v_ref;                     /* iter.v_ref: N x Hp */
+    int32_t boundary_rows, boundary_cols;      /* size(iter.predicted_lanelet_boundary(:, 1:2)): N x 2 (left, right), or 0 x 0: none */
+    const pdmpc_ml_matrix* predicted_lanelet_boundary; /* cells of 2 x P or empty */
+    int32_t n_obstacles;                       /* numel(iter.obstacles) */
+    const pdmpc_ml_matrix* obstacles;          /* cells of 2 x V */
+    int32_t dyn_rows, dyn_cols;                /* size(iter.dynamic_obstacle_area): n_d x Hp */
+    const pdmpc_ml_matrix* dynamic_obstacle_area;
+} pdmpc_ml_joint_iter;
+/* the N one-vehicle inputs of the joint problem in the form pdmpc_plan_joint receives them (read with pdmpc_ml_step_problem: slot v
+ * = vehicle v + 1, no predecessors, no fallback areas) */
+int pdmpc_ml_joint_step_create(int32_t Hp, const pdmpc_ml_joint_iter* iter, pdmpc_ml_step** out);
+/* plans the joint problem (pdmpc_plan_joint, one problem); out[v] = vehicle v's slice of the joint ControlResultsInfo */
+int pdmpc_ml_plan_joint(pdmpc_handle* handle, int32_t Hp, const pdmpc_ml_joint_iter* iter, pdmpc_vehicle_out* out);
 
 /* ---- results in MATLAB's layout ----
  * predicted_trims, shape_cols: 1 x Hp; y_predicted: Hp x 3; shapes: Hp x 2 x PDMPC_VMAX; path_nodes: (Hp + 1) x 8 (rows in

@@ -303,6 +303,8 @@ struct pdmpc_handle {
     int sampled_n_random = 0;
     bool sampled_launch = false;
     bool last_launch_search = false;     // the last launch ran the graph search (not the sampled optimizer)
+    bool last_launch_joint = false;      // the last launch ran the joint search of centralized control (pdmpc_plan_joint)
+    DevBuf<int32_t> d_joint_off;         // pdmpc_plan_joint: the problems' first slots
     int last_first = 0, last_count = 0;  // slots of the last launch_range
     bool last_safe = false;              // ... and whether it went out in resident slices
     int device_share = 1;                // handles of one process that launch on this device side by side (pdmpc_set_device_share: a group's logical ranks)
@@ -1005,6 +1007,7 @@ int launch_range(pdmpc_handle* h, int first, int count, bool safe = false) {
     auto& ev = h->events[h->events_used++];
     HIPCHK(hipEventRecord(ev.first, h->stream));
     h->last_launch_search = search;
+    h->last_launch_joint = false;
     h->last_first = first;
     h->last_count = count;
     h->last_safe = safe;
@@ -1602,6 +1605,158 @@ int pdmpc_plan_batch_sampled(pdmpc_handle* h, int32_t n, const pdmpc_vehicle_in*
     return pdmpc_fetch_results(h, n, out);
 }
 
+namespace {
+// LDS layout of the joint search (one wavefront per problem): MPA tables, every vehicle's reference, the node's areas, offsets and the
+// path, successor lists, the problem's soups, then the LDS part of the open list.  Aimed at 64 KB (two workgroups per CU and more);
+// a problem whose tables and soups do not leave room for 256 heap entries there may take up to the whole 160 KB.
+int layout_joint(pdmpc_handle* h, int soup_cap, JointLds& L, uint32_t& heap_lds, int& areas_in_lds) {
+    for (int pass = 0; pass < 4; ++pass) {
+        const bool areas = pass == 0 || pass == 2;
+        const size_t budget = pass < 2 ? 64 * 1024 : kLdsMax;
+        uint32_t off = 0;
+        L.mask = off;
+        off = align16(off + (uint32_t)h->mask_bytes);
+        L.man_index = off;
+        off = align16(off + (uint32_t)h->mi_bytes);
+        L.pose = off;
+        off = align16(off + (uint32_t)(h->n_man * sizeof(DevManPose)));
+        L.area = off;
+        if (areas) off = align16(off + (uint32_t)(h->n_man * 3 * PDMPC_VMAX * 16));
+        L.ref = off;
+        off += PDMPC_JOINT_MAX * 3 * PDMPC_HP_MAX * 8;
+        L.shape = off;
+        off += PDMPC_JOINT_MAX * 2 * PDMPC_VMAX * 16;
+        L.ints = off;
+        off = align16(off + PDMPC_JOINT_INTS * 4);
+        L.succ = off;
+        off = align16(off + (uint32_t)(PDMPC_JOINT_MAX * h->n_trims * 4));
+        L.soup = off;
+        off = align16(off + (uint32_t)std::max(soup_cap, 1) * 16);
+        if (off + 256 * 12 > budget) continue;
+        const uint32_t entries = std::min<uint32_t>(8192u, (uint32_t)((budget - off) / 12) & ~63u);
+        L.heap_key = off;
+        off += entries * 8;
+        L.heap_id = off;
+        off += entries * 4;
+        L.total = align16(off);
+        heap_lds = entries;
+        areas_in_lds = areas ? 1 : 0;
+        return PDMPC_OK;
+    }
+    return fail(PDMPC_ERR_CAPACITY, "the MPA tables and a joint problem's obstacle soups do not fit into LDS");
+}
+}  // namespace
+
+int pdmpc_plan_joint(pdmpc_handle* h, int32_t n_problems, const int32_t* problem_offset, const pdmpc_vehicle_in* in, pdmpc_vehicle_out* out) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    if (h->cfg.checker != PDMPC_CHECK_SAT) return fail(PDMPC_ERR_INVALID, "pdmpc_plan_joint: joint searches use the separating-axis checker (PDMPC_CHECK_SAT)");
+    if (n_problems < 0 || (n_problems > 0 && !problem_offset)) return fail(PDMPC_ERR_INVALID, "pdmpc_plan_joint: bad problem list");
+    if (n_problems > 0 && problem_offset[0] != 0) return fail(PDMPC_ERR_INVALID, "pdmpc_plan_joint: problem_offset[0] must be 0");
+    for (int p = 0; p < n_problems; ++p) {
+        const int m = problem_offset[p + 1] - problem_offset[p];
+        if (m < 1 || m > PDMPC_JOINT_MAX) return fail(PDMPC_ERR_INVALID, "pdmpc_plan_joint: a problem holds 1 to PDMPC_JOINT_MAX vehicles");
+    }
+    const int n = n_problems > 0 ? problem_offset[n_problems] : 0;
+    if (n > 0 && (!in || !out)) return fail(PDMPC_ERR_INVALID, "pdmpc_plan_joint: null vehicle or record array");
+    ON_DEVICE(h->cfg.device);
+    int rc = pdmpc_pack_batch(h, n, in);
+    if (rc) return rc;
+    if (n == 0) return PDMPC_OK;
+    PackedStep& B = h->banks[h->bank];
+    const int Hp = h->cfg.Hp;
+    int soup_cap = 0;
+    for (int p = 0; p < n_problems; ++p) {
+        int need = 0;
+        for (int i = problem_offset[p]; i < problem_offset[p + 1]; ++i) {
+            const DevVehicle& d = B.h_veh[i];
+            need += (d.lit_off[Hp] - d.lit_off[0]) + d.ll_len;
+        }
+        soup_cap = std::max(soup_cap, need);
+    }
+    JointLds L{};
+    uint32_t heap_lds = 0;
+    int areas_in_lds = 0;
+    if ((rc = layout_joint(h, soup_cap + 2, L, heap_lds, areas_in_lds))) return rc;
+    if (h->d_joint_off.ensure((size_t)n_problems + 1)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the problem offsets");
+    HIPCHK(hipMemcpyAsync(h->d_joint_off.p, problem_offset, ((size_t)n_problems + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    for (;;) {
+        JointArgs a{};
+        a.succ_mask = h->d_mask.p;
+        a.man_index = h->d_mi.p;
+        a.man_pose = h->d_pose.p;
+        a.man_area = h->d_area.p;
+        a.n_trims = h->n_trims;
+        a.n_words = h->n_words;
+        a.n_man = h->n_man;
+        a.Hp = Hp;
+        a.areas_in_lds = areas_in_lds;
+        a.dt = h->cfg.dt_seconds;
+        a.veh = B.d_veh;
+        a.points = B.d_pts;
+        a.problem_off = h->d_joint_off.p;
+        a.out = h->d_out.p;
+        a.nodes = h->anodes.p;
+        a.far_key = h->afark.p;
+        a.far_id = h->afari.p;
+        a.max_nodes = h->max_nodes;
+        a.heap_lds = heap_lds;
+        a.tree_size = h->d_tree_size.p;
+        a.work_count = h->d_work_count.p;
+        a.lds = L;
+        if (h->events_used == h->events.size()) {
+            hipEvent_t e0, e1;
+            HIPCHK(hipEventCreate(&e0));
+            HIPCHK(hipEventCreate(&e1));
+            h->events.emplace_back(e0, e1);
+        }
+        auto& ev = h->events[h->events_used++];
+        HIPCHK(hipEventRecord(ev.first, h->stream));
+        const int lrc = pdmpc_launch_joint(&a, n_problems, (void*)h->stream);
+        if (lrc != 0) {
+            char buf[256];
+            snprintf(buf, sizeof buf, "joint kernel launch failed: %s (LDS %u B)", hipGetErrorString((hipError_t)lrc), L.total);
+            return fail(PDMPC_ERR_HIP, buf);
+        }
+        HIPCHK(hipEventRecord(ev.second, h->stream));
+        h->last_launch_search = false;
+        h->last_launch_joint = true;
+        if ((rc = pdmpc_fetch_results(h, n, out))) return rc;
+        bool overflow = false;
+        for (int i = 0; i < n; ++i) overflow = overflow || out[i].status == PDMPC_ARENA_OVERFLOW;
+        if (!overflow) break;
+        // the arena is too small for some problem: plan the call again with arenas twice as large (pdmpc_plan_batch's rule)
+        const uint64_t next = (uint64_t)h->max_nodes * 2u;
+        if ((h->max_nodes_limit && next > h->max_nodes_limit) || next > (1ull << 30)) break;
+        size_t free_b = 0, total_b = 0;
+        (void)hipMemGetInfo(&free_b, &total_b);
+        const size_t per_node = arena_bytes_per_node(h);
+        if ((size_t)h->max_vehicles * next * per_node > free_b + (size_t)h->max_vehicles * h->max_nodes * per_node) break;
+        const uint32_t before = h->max_nodes;
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (alloc_arenas(h, (uint32_t)next)) {
+            if (alloc_arenas(h, before)) return fail(PDMPC_ERR_HIP, "hipMalloc failed while restoring the arenas");
+            break;
+        }
+        h->arena_regrows += 1;
+    }
+    // counters per problem (every vehicle's record carries its problem's n_popped / n_expanded); the per-plan byte formula and
+    // obstacle-column count that pdmpc_fetch_results evaluates are the single-vehicle search's and do not
+    // describe a joint search: they are reported as 0
+    pdmpc_stats& s = h->stats;
+    s.n_vehicles = n;
+    s.obstacle_columns = 0;
+    s.algorithmic_bytes = 0;
+    s.nodes_popped = s.nodes_generated = 0;
+    for (int p = 0; p < n_problems; ++p) {
+        const pdmpc_vehicle_out& o = out[problem_offset[p]];
+        s.nodes_popped += o.n_popped;
+        s.nodes_generated += std::max(o.n_expanded - 1, 0);
+    }
+    s.lds_bytes = L.total;
+    s.lds_nodes = 0;
+    return PDMPC_OK;
+}
+
 int pdmpc_result_device_buffer(pdmpc_handle* h, void** dev_ptr, size_t* nbytes) {
     if (!h || !dev_ptr || !nbytes) return fail(PDMPC_ERR_INVALID, "null argument");
     if (!h->banks[h->bank].perm.empty()) return fail(PDMPC_ERR_INVALID, "the packed batch was put into level order by the library: raw slots are not the caller's vehicles (pack it in level order to use the device-resident record path)");
@@ -1676,7 +1831,7 @@ int pdmpc_get_last_stats(pdmpc_handle* h, pdmpc_stats* stats) {
     HIPCHK(hipMemcpy(work, h->d_work_count.p, sizeof work, hipMemcpyDeviceToHost));
     h->stats.edge_checks = (int64_t)work[0];
     h->stats.segment_pair_tests = (int64_t)work[1];
-    h->stats.kernel = h->last_launch_search ? 2 : 3;
+    h->stats.kernel = h->last_launch_joint ? 4 : (h->last_launch_search ? 2 : 3);
     h->stats.nodes_processed = (int64_t)work[2];
     h->stats.rounds = (int64_t)work[3];
     h->stats.shared_rounds = (int64_t)work[4];

@@ -320,6 +320,58 @@ int pdmpc_ml_group_plan_step(pdmpc_group* g, const pdmpc_ml_step* s, const doubl
     return PDMPC_OK;
 }
 
+int pdmpc_ml_joint_step_create(int32_t Hp, const pdmpc_ml_joint_iter* J, pdmpc_ml_step** out) {
+    if (!out || !J || Hp < 1 || Hp > PDMPC_HP_MAX) return ml_fail(PDMPC_ERR_INVALID, "pdmpc_ml_joint_step_create: bad argument");
+    const int N = J->amount;
+    if (N < 1 || N > PDMPC_JOINT_MAX) return ml_fail(PDMPC_ERR_INVALID, "pdmpc_ml_joint_step_create: iter.amount must be 1 .. PDMPC_JOINT_MAX");
+    if (!J->x0.data || J->x0.rows != N || J->x0.cols < 3) return ml_fail(PDMPC_ERR_INVALID, "pdmpc_ml_joint_step_create: x0 must be N x (>= 3)");
+    if (!J->trim_indices.data || (int64_t)J->trim_indices.rows * J->trim_indices.cols != N)
+        return ml_fail(PDMPC_ERR_INVALID, "pdmpc_ml_joint_step_create: trim_indices must hold N elements");
+    if (!J->reference_trajectory_points) return ml_fail(PDMPC_ERR_INVALID, "pdmpc_ml_joint_step_create: reference_trajectory_points missing");
+    if (!J->v_ref.data || J->v_ref.rows != N || J->v_ref.cols != Hp) return ml_fail(PDMPC_ERR_INVALID, "pdmpc_ml_joint_step_create: v_ref must be N x Hp");
+    const bool has_boundary = (int64_t)J->boundary_rows * J->boundary_cols != 0;
+    if (has_boundary && (J->boundary_rows != N || J->boundary_cols < 2 || !J->predicted_lanelet_boundary))
+        return ml_fail(PDMPC_ERR_INVALID, "pdmpc_ml_joint_step_create: predicted_lanelet_boundary must be an N x 2 cell");
+    // row v of the N-row fields as vehicle v's one-vehicle slice (IterationData.filter, IterationData.m:95-114); the step copies it all
+    std::vector<std::vector<double>> x0((size_t)N), ref((size_t)N), vref((size_t)N);
+    std::vector<pdmpc_ml_iter> its((size_t)N);
+    for (int v = 0; v < N; ++v) {
+        for (int c = 0; c < J->x0.cols; ++c) x0[(size_t)v].push_back(J->x0.data[(size_t)v + (size_t)c * N]);
+        for (int c = 0; c < 2; ++c)  // Hp x 2, column-major
+            for (int k = 0; k < Hp; ++k) ref[(size_t)v].push_back(J->reference_trajectory_points[(size_t)v + (size_t)k * N + (size_t)c * N * Hp]);
+        for (int k = 0; k < Hp; ++k) vref[(size_t)v].push_back(J->v_ref.data[(size_t)v + (size_t)k * N]);
+        pdmpc_ml_iter& it = its[(size_t)v];
+        it = pdmpc_ml_iter{};
+        it.x0 = x0[(size_t)v].data();
+        it.n_x0 = J->x0.cols;
+        it.trim_index = (int32_t)J->trim_indices.data[v];
+        it.reference_trajectory_points = {ref[(size_t)v].data(), Hp, 2};
+        it.v_ref = {vref[(size_t)v].data(), 1, Hp};
+        it.n_obstacles = J->n_obstacles;
+        it.obstacles = J->obstacles;
+        it.dyn_rows = J->dyn_rows;
+        it.dyn_cols = J->dyn_cols;
+        it.dynamic_obstacle_area = J->dynamic_obstacle_area;
+        if (has_boundary)
+            for (int side = 0; side < 2; ++side) it.lanelet_boundary[side] = J->predicted_lanelet_boundary[(size_t)v + (size_t)side * N];
+        it.hdv_rows = 0;
+        it.hdv_cols = 0;
+        it.hdv_reachable_sets = nullptr;
+    }
+    return pdmpc_ml_step_create(Hp, N, its.data(), nullptr, nullptr, out);
+}
+
+int pdmpc_ml_plan_joint(pdmpc_handle* h, int32_t Hp, const pdmpc_ml_joint_iter* J, pdmpc_vehicle_out* out) {
+    pdmpc_ml_step* s = nullptr;
+    int rc = pdmpc_ml_joint_step_create(Hp, J, &s);
+    if (rc) return rc;
+    const int32_t off[2] = {0, s->n};
+    rc = pdmpc_plan_joint(h, 1, off, s->in.data(), out);  // (no couplings: slot v = vehicle v)
+    if (rc) g_ml_err = pdmpc_last_error();
+    pdmpc_ml_step_destroy(s);
+    return rc;
+}
+
 int pdmpc_ml_plan_level(pdmpc_handle* h, int32_t Hp, int32_t n, const pdmpc_ml_iter* iters, pdmpc_vehicle_out* out) {
     pdmpc_ml_step* s = nullptr;
     int rc = pdmpc_ml_step_create(Hp, n, iters, nullptr, nullptr, &s);

@@ -239,6 +239,44 @@ struct KernelArgs {
                                // dispatched before their predecessors -- the adversarial order the watchdog + resident slices must survive
 };
 
+// The joint search of centralized control (joint_kernel.hip): one workgroup per problem, problem p = packed slots
+// [problem_off[p], problem_off[p + 1]).  Joint node i of a problem is the N records nodes[(first slot + v) * max_nodes + i], v < N:
+// vehicle v's pose and trim, k, parent, and the node's joint g and h in every one of them.  The open list keeps its first heap_lds
+// entries in LDS and the rest in far_key / far_id of the problem's first slot.
+struct JointLds {  // byte offsets into the dynamic LDS allocation (api.cpp: layout_joint)
+    uint32_t mask, man_index, pose, area;  // MPA tables (area: only if areas_in_lds)
+    uint32_t ref;                          // double [PDMPC_JOINT_MAX][3][PDMPC_HP_MAX]: ref_x, ref_y, v_ref per vehicle
+    uint32_t shape;                        // double2 [PDMPC_JOINT_MAX][2][PDMPC_VMAX]: area, boundary-check area of the node's edge
+    uint32_t ints;                         // int32: soup offsets [JOINT_MAX][HP_MAX + 1], boundary base / length / columns [3][JOINT_MAX], path [HP_MAX + 1]
+    uint32_t succ;                         // int32 [PDMPC_JOINT_MAX][n_trims]: successor trims of the node being expanded
+    uint32_t soup;                         // double2 [soup_cap]: the problem's obstacle soups, vehicle after vehicle
+    uint32_t heap_key, heap_id;            // the LDS part of the open list: double [heap_lds], uint32 [heap_lds]
+    uint32_t total;
+};
+#define PDMPC_JOINT_INTS (PDMPC_JOINT_MAX * (PDMPC_HP_MAX + 1) + 3 * PDMPC_JOINT_MAX + PDMPC_HP_MAX + 1)
+
+struct JointArgs {
+    const uint64_t* succ_mask;
+    const int16_t* man_index;
+    const DevManPose* man_pose;
+    const double* man_area;  // double2 pairs
+    int32_t n_trims, n_words, n_man, Hp;
+    int32_t areas_in_lds;
+    double dt;
+    const DevVehicle* veh;
+    const double* points;      // double2 pairs
+    const int32_t* problem_off;  // [n_problems + 1]
+    pdmpc_vehicle_out* out;      // per slot
+    NodeRec* nodes;              // per slot: max_nodes records
+    double* far_key;             // per slot: max_nodes entries (a problem uses its first slot's)
+    uint32_t* far_id;
+    uint32_t max_nodes;
+    uint32_t heap_lds;
+    int32_t* tree_size;          // per slot: nodes in the problem's tree after the search
+    unsigned long long* work_count;  // [0] edge checks (one per popped node that has a parent), [2] nodes popped
+    JointLds lds;
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -257,6 +295,8 @@ int pdmpc_launch_sampled(const KernelArgs* args, int count, void* stream);
 // debug_kernels.hip: the open-list command script on one wavefront, and the collision primitives on given polygons (one wavefront per case)
 int pdmpc_launch_heap_script(const int32_t* op, const int32_t* id, const double* key, int n, int32_t* out, unsigned long long* stats, double* gkey, uint32_t* gid, int HL,
                              void* stream);
+// joint_kernel.hip: centralized control, one workgroup of one wavefront per joint problem
+int pdmpc_launch_joint(const JointArgs* args, int n_problems, void* stream);
 int pdmpc_launch_edge_check(int mode, int n_cases, const int32_t* a_off, const double* a_x, const double* a_y, const int32_t* b_off, const double* b_x,
                             const double* b_y, int32_t* hit, void* stream);
 #ifdef __cplusplus

@@ -33,12 +33,19 @@ classdef GraphSearchHip < OptimizerInterface
         end
 
         function info = run_optimizer(obj, ~, iter, mpa, options, ~)
-            % Same contract as GraphSearch.run_optimizer (GraphSearch.m:14-17): one vehicle.
-            assert(iter.amount == 1);
+            % Same contract as GraphSearch.run_optimizer (GraphSearch.m:14-17).
 
             if ~obj.mpa_uploaded
                 pdmpc_mex('upload_mpa', obj.handle, mpa.transition_matrix_single, mpa.maneuvers);
                 obj.mpa_uploaded = true;
+            end
+
+            if iter.amount > 1
+                % CentralizedController.m:34-46: ONE search over the joint state of all vehicles (pdmpc_plan_joint; the
+                % separating-axis checker, which is_prioritized = false selects through are_any_obstacles_non_convex)
+                outs = pdmpc_mex('plan_joint', obj.handle, pdmpc_joint_iter_struct(iter));
+                info = GraphSearchHip.info_from_joint_records(iter, options, outs);
+                return
             end
 
             % libpdmpc_hip.so flattens the cells of iter into pdmpc_vehicle_in (csrc/matlab_marshal.cpp) and returns pdmpc_vehicle_out
@@ -50,6 +57,35 @@ classdef GraphSearchHip < OptimizerInterface
     end
 
     methods (Static)
+
+        function info = info_from_joint_records(iter, options, outs)
+            % outs(v) = vehicle v's slice of the joint search's result -> ControlResultsInfo(iter.amount, Hp)
+            % (GraphSearch.m:81-90 with nVeh = iter.amount)
+            Hp = options.Hp;
+            info = ControlResultsInfo(iter.amount, Hp);
+            info.n_expanded = outs(1).n_expanded;
+
+            if outs(1).status == 2
+                error('GraphSearchHip:arena', 'joint search tree outgrew the arena and could not be grown (status PDMPC_ARENA_OVERFLOW)');
+            elseif outs(1).status < 0
+                error('GraphSearchHip:backend', 'pdmpc_plan_joint reported status %d in the result record', outs(1).status);
+            end
+
+            info.is_exhausted = outs(1).status == 1; % PDMPC_EXHAUSTED
+            info.needs_fallback = info.is_exhausted;
+
+            if info.is_exhausted
+                return
+            end
+
+            for v = 1:iter.amount
+                info.y_predicted(:, :, v) = outs(v).y_predicted(1:Hp, :)';
+                info.predicted_trims(v, :) = outs(v).predicted_trims(1:Hp);
+                info.shapes(v, :) = arrayfun(@(k) squeeze(outs(v).shapes(k, :, 1:outs(v).shape_cols(k))), 1:Hp, UniformOutput = false);
+            end
+
+            info.tree_path = outs(1).tree_path;
+        end
 
         function info = info_from_record(iter, options, out)
             % pdmpc_vehicle_out (as the struct pdmpc_mex returns) -> ControlResultsInfo; also used by

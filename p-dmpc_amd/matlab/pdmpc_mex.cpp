@@ -8,17 +8,22 @@
 //     out  = pdmpc_mex('plan', h, iter_struct)                     one run_optimizer call (GraphSearchHip.m)
 //     out  = pdmpc_mex('plan_sampled', h, iter_struct, seed)       the sampled optimizer (MonteCarloTreeSearchHip.m)
 //     outs = pdmpc_mex('plan_level', h, iter_structs)              one computation level: n vehicles, one launch
+//     outs = pdmpc_mex('plan_joint', h, joint_struct)              centralized control: ONE joint search over iter.amount
+//                                                                  vehicles (GraphSearchHip.m, iter.amount > 1)
 //     outs = pdmpc_mex('plan_step', h, iter_structs, directed_coupling_sequential, fallback_areas [, weights])
 //                                                                  ALL levels of a time step in one launch
 //                                                                  (PrioritizedSequentialHipController.m)
 //            pdmpc_mex('destroy', h)
 // iter_struct(s): struct (array) with fields x0, trim_index, reference_trajectory_points (Hp x 2), v_ref, obstacles (cell),
 // dynamic_obstacle_area (n_d x Hp cell), lanelet_boundary (1 x 2 cell), hdv_reachable_sets (n_h x Hp cell).
+// joint_struct: struct with fields x0 (N x 4), trim_indices (N x 1), reference_trajectory_points (N x Hp x 2), v_ref (N x Hp),
+// predicted_lanelet_boundary (N x 2 cell or {}), obstacles (cell), dynamic_obstacle_area (n_d x Hp cell): IterationData itself.
 //
 // This file holds NO index arithmetic: it turns matlab::data arrays into the (pointer, rows, cols) descriptors of
 // include/pdmpc_matlab.h; the marshalling itself (cell order, column-major matrices, kahn levels, slot order) is
 // csrc/matlab_marshal.cpp, compiled into libpdmpc_hip.so and unit-tested without MATLAB (tests/test_matlab_marshal.py).
 // It replaces the command protocol of priority_queue_interface_mex.cpp:33-40: the queue now lives inside the kernel.
+#include <algorithm>
 #include <deque>
 #include <string>
 #include <vector>
@@ -180,6 +185,30 @@ public:
                 if (group && pdmpc_group_handle(group, r, &h) != PDMPC_OK) fail("pdmpc_group_handle", pdmpc_last_error());
                 if (pdmpc_ml_upload_mpa(h, T.data, n, T.cols / n, cells.data()) != PDMPC_OK) fail("pdmpc_ml_upload_mpa", pdmpc_ml_last_error());
             }
+            return;
+        }
+        if (cmd == "plan_joint") {
+            Pins pins;
+            const StructArray js = inputs[2];
+            pdmpc_ml_joint_iter J{};
+            J.x0 = pins.matrix(js[0]["x0"]);
+            J.amount = J.x0.rows;
+            J.trim_indices = pins.matrix(js[0]["trim_indices"]);
+            const pdmpc_ml_matrix ref = pins.matrix(js[0]["reference_trajectory_points"]);  // N x Hp x 2
+            if (ref.data == nullptr || (size_t)ref.rows != (size_t)J.amount || (size_t)ref.cols != 2 * Hp)
+                fail("plan_joint", "reference_trajectory_points must be N x Hp x 2");
+            J.reference_trajectory_points = ref.data;
+            J.v_ref = pins.matrix(js[0]["v_ref"]);
+            int32_t r = 0, c = 0;
+            if (!Array(js[0]["predicted_lanelet_boundary"]).isEmpty())
+                J.predicted_lanelet_boundary = pins.cell(js[0]["predicted_lanelet_boundary"], J.boundary_rows, J.boundary_cols);
+            J.obstacles = pins.cell(js[0]["obstacles"], r, c);
+            J.n_obstacles = r * c;
+            J.dynamic_obstacle_area = pins.cell(js[0]["dynamic_obstacle_area"], J.dyn_rows, J.dyn_cols);
+            std::vector<pdmpc_vehicle_out> out((size_t)std::max(J.amount, 1));
+            if (pdmpc_ml_plan_joint(h, (int32_t)Hp, &J, out.data()) != PDMPC_OK) fail("pdmpc_ml_plan_joint", pdmpc_ml_last_error());
+            out.resize((size_t)J.amount);
+            outputs[0] = records(out, Hp);
             return;
         }
         if (cmd == "plan" || cmd == "plan_sampled" || cmd == "plan_level" || cmd == "plan_step" || cmd == "group_plan_step") {

@@ -10,6 +10,7 @@ import numpy as np
 
 HP_MAX = 16
 VMAX = 8
+JOINT_MAX = 4  # vehicles per joint problem (pdmpc_plan_joint)
 
 OK, EXHAUSTED, ARENA_OVERFLOW = 0, 1, 2
 CHECK_SAT, CHECK_INTERX = 0, 1

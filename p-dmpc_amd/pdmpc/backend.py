@@ -23,6 +23,7 @@ EXPORTS = [
     "pdmpc_get_config",
     "pdmpc_plan_batch",
     "pdmpc_plan_batch_sampled",
+    "pdmpc_plan_joint",
     "pdmpc_pack_batch",
     "pdmpc_launch_packed",
     "pdmpc_launch_range",
@@ -144,6 +145,7 @@ def load_library(path=None):
     L.pdmpc_export_results_async.argtypes = [H, C.c_int32, C.c_int32, C.c_void_p]
     L.pdmpc_stream.argtypes = [H, C.POINTER(C.c_void_p)]
     L.pdmpc_plan_batch_sampled.argtypes = [H, C.c_int32, C.POINTER(abi.VehicleIn), C.POINTER(C.c_uint32), C.POINTER(abi.VehicleOut)]
+    L.pdmpc_plan_joint.argtypes = [H, C.c_int32, abi.c_int32_p, C.POINTER(abi.VehicleIn), C.POINTER(abi.VehicleOut)]
     L.pdmpc_get_last_stats.argtypes = [H, C.POINTER(abi.Stats)]
     L.pdmpc_debug_heap_script.argtypes = [H, C.c_int32, abi.c_int32_p, abi.c_int32_p, abi.c_double_p, C.c_int32, abi.c_int32_p, abi.c_int32_p, abi.c_double_p, abi.c_double_p]
     L.pdmpc_debug_pop_trace.argtypes = [H, C.c_int32, C.c_int32, abi.c_int32_p, abi.c_int32_p]
@@ -359,6 +361,20 @@ class Handle:
         _check(self.L, self.L.pdmpc_plan_batch_sampled(self.h, n, arr, sd, abi.out_ptr(out)), "pdmpc_plan_batch_sampled")
         del keep
         return out[:n]
+
+    def plan_joint(self, problems):
+        """Centralized control: list of problems, each a list of 1 to JOINT_MAX VehicleIter, one joint search per problem ->
+        numpy records (abi.VEHICLE_OUT_DTYPE), one per vehicle in input order (pdmpc_plan_joint)."""
+        off = np.zeros(len(problems) + 1, dtype=np.int32)
+        for p, prob in enumerate(problems):
+            off[p + 1] = off[p] + len(prob)
+        iters = [it for prob in problems for it in prob]
+        n = len(iters)
+        arr, keep = abi.pack_vehicles(iters, self.Hp)
+        out = abi.out_array(n)
+        _check(self.L, self.L.pdmpc_plan_joint(self.h, len(problems), off.ctypes.data_as(abi.c_int32_p), arr, abi.out_ptr(out)), "pdmpc_plan_joint")
+        del keep
+        return self._checked(out[:n])
 
     # ---- device-resident path ----
     def pack_batch(self, iters):
