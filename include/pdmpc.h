@@ -361,6 +361,19 @@ int pdmpc_plan_batch_sampled(pdmpc_handle* handle, int32_t n_vehicles, const pdm
 int pdmpc_plan_joint(pdmpc_handle* handle, int32_t n_problems, const int32_t* problem_offset, const pdmpc_vehicle_in* in,
                      pdmpc_vehicle_out* out);
 
+/* ---- the unique prioritizations of a coupling graph (Prioritizer.unique_priorities, priority/Prioritizer.m:97-140) ----
+ * adjacency: n x n, row-major, non-zero = coupled; only the strict upper triangle is read (triu(adjacency, 1)).  Edge e (0-based, in
+ * the order of find(triu(adjacency, 1)): by column, then by row) runs row -> column unless it is flipped; orientation m (0 .. 2^E - 1)
+ * flips edge e exactly when bit E - 1 - e of m is set (dec2bin(m, E)).  Out: the acyclic orientations in ascending m, masks[k] = m and
+ * priorities[k * n + v] = position (1-based) of vehicle v in the orientation's lexicographically smallest topological order
+ * (toposort(..., 'Order', 'stable')).  *n_out = K, the number of acyclic orientations, whatever max_out is (-1 for a graph outside
+ * the limits).  PDMPC_ERR_CAPACITY without a launch for n > 64 or E > 32, and PDMPC_ERR_CAPACITY with nothing written for K > max_out:
+ * the list is never truncated.  pdmpc_unique_priorities runs on the handle's device (csrc/priority_kernel.hip);
+ * pdmpc_unique_priorities_host is its C++ twin and checker (csrc/step_controller.cpp, no GPU needed). */
+int pdmpc_unique_priorities(pdmpc_handle* handle, int32_t n, const uint8_t* adjacency, int64_t max_out, int64_t* n_out, uint32_t* masks,
+                            int32_t* priorities);
+int pdmpc_unique_priorities_host(int32_t n, const uint8_t* adjacency, int64_t max_out, int64_t* n_out, uint32_t* masks, int32_t* priorities);
+
 /* ---- the caller's side of the boundary, natively (csrc/step_controller.cpp) ----
  * One MPC time step of the prioritized sequential controller around pdmpc_plan_step, without any interpreter in the loop:
  * traffic info, coupling, priorities, grouping, computation levels, obstacle assembly, ONE launch, exhaustion handling,
@@ -448,6 +461,23 @@ int pdmpc_controller_explore_run(pdmpc_controller* c, int32_t n_perm, int32_t n_
  * as the resident replay) */
 int pdmpc_controller_explore_follow_own(pdmpc_controller* c, int32_t on);
 int pdmpc_controller_explore_result(pdmpc_controller* c, int32_t* chosen, int32_t* n_graphs, const double** cost, const pdmpc_vehicle_out** records);
+/* The optimal-priority time step (PrioritizedOptimalController.m:25-114, PrioritizedOptimalSequentialController.m): the step's traffic
+ * state under EVERY unique prioritization of its coupling graph (pdmpc_unique_priorities on the controller's device; the host twin for
+ * a controller without a handle), flattened into one batch whose slots are ordered by (level, instance, slot).  Instance p plans with
+ * constant priorities = prioritization p, grouped as the controller groups (max_num_CLs); instance 0 (mask 0) is the problem
+ * pdmpc_controller_build_step builds with constant priorities.  optimal_build advances the time step like build_step and leaves the
+ * batch readable with pdmpc_controller_explore_problem; PDMPC_ERR_CAPACITY if more than max_instances prioritizations exist (and for
+ * the limits of pdmpc_unique_priorities).  optimal_choose: for every vehicle v the instance with the smallest sum over ALL vehicles
+ * of the cost-to-come of their final nodes (v's own first, then the others by index), round(., 8), the first minimum (:56-114); an
+ * exhausted search makes its instance infinitely expensive.  chosen[v]; cost (may be NULL) = n x K, row v = vehicle v's sums.  Every
+ * vehicle goes on with the couplings of its chosen instance.  optimal_step = build + ONE launch + choose + apply; optimal_run =
+ * n_steps of them reading back status and final cost of every plan and the chosen records only; optimal_result: chosen instance per
+ * vehicle, K, the cost table and (after optimal_step) the batch's records. */
+int pdmpc_controller_optimal_build(pdmpc_controller* c, int32_t max_instances);
+int pdmpc_controller_optimal_choose(pdmpc_controller* c, const pdmpc_vehicle_out* records, int32_t* chosen, double* cost);
+int pdmpc_controller_optimal_step(pdmpc_controller* c, int32_t max_instances);
+int pdmpc_controller_optimal_run(pdmpc_controller* c, int32_t max_instances, int32_t n_steps, double* ms);
+int pdmpc_controller_optimal_result(pdmpc_controller* c, int32_t* chosen, int32_t* n_instances, const double** cost, const pdmpc_vehicle_out** records);
 /* host wall-clock milliseconds of the last pdmpc_controller_step / pdmpc_controller_explore_step, by part: [0] build the step problem(s)
  * on the host, [1] pack, [2] enqueue, [3] wait + read-back, [4] choice among the prioritizations (explorative step), [5] apply */
 int pdmpc_controller_last_timing(pdmpc_controller* c, double* ms6);

@@ -305,6 +305,9 @@ struct pdmpc_handle {
     bool last_launch_search = false;     // the last launch ran the graph search (not the sampled optimizer)
     bool last_launch_joint = false;      // the last launch ran the joint search of centralized control (pdmpc_plan_joint)
     DevBuf<int32_t> d_joint_off;         // pdmpc_plan_joint: the problems' first slots
+    DevBuf<uint32_t> d_prio_count, d_prio_mask;  // pdmpc_unique_priorities: acyclic masks per tile, the acyclic masks
+    DevBuf<int64_t> d_prio_off;                  // ... exclusive offsets of the tiles (entry n_tiles: the total)
+    DevBuf<int32_t> d_prio_order;                // ... the priorities of every acyclic mask
     int last_first = 0, last_count = 0;  // slots of the last launch_range
     bool last_safe = false;              // ... and whether it went out in resident slices
     int device_share = 1;                // handles of one process that launch on this device side by side (pdmpc_set_device_share: a group's logical ranks)
@@ -1145,6 +1148,10 @@ int pdmpc_destroy(pdmpc_handle* h) {
     h->d_bk_post.release();
     h->d_help_finished.release();
     h->d_random.release();
+    h->d_prio_count.release();
+    h->d_prio_mask.release();
+    h->d_prio_off.release();
+    h->d_prio_order.release();
     for (auto& b : h->banks) b.release();
     if (h->progress) (void)hipHostFree(h->progress);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1754,6 +1761,62 @@ int pdmpc_plan_joint(pdmpc_handle* h, int32_t n_problems, const int32_t* problem
     }
     s.lds_bytes = L.total;
     s.lds_nodes = 0;
+    return PDMPC_OK;
+}
+
+// Prioritizer.unique_priorities (Prioritizer.m:97-140) on the device: priority_kernel.hip.  The acyclic orientations are counted
+// first; the true count K is reported whatever max_out is, and only a K that fits is written (never a truncated list).
+int pdmpc_unique_priorities(pdmpc_handle* h, int32_t n, const uint8_t* adjacency, int64_t max_out, int64_t* n_out, uint32_t* masks, int32_t* priorities) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    if (n_out) *n_out = -1;
+    if (n < 1 || !adjacency || !n_out || max_out < 0 || (max_out > 0 && (!masks || !priorities)))
+        return fail(PDMPC_ERR_INVALID, "pdmpc_unique_priorities: bad argument");
+    if (n > PDMPC_PRIO_MAX_N) return fail(PDMPC_ERR_CAPACITY, "pdmpc_unique_priorities: more than 64 vehicles");
+    PriorityArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.n = n;
+    int E = 0;
+    for (int c = 0; c < n; ++c)  // find(triu(adjacency, 1)): by column, then by row
+        for (int r = 0; r < c; ++r)
+            if (adjacency[(size_t)r * n + c]) ++E;
+    if (E > PDMPC_PRIO_MAX_E) return fail(PDMPC_ERR_CAPACITY, "pdmpc_unique_priorities: more than 32 coupling edges");
+    for (int c = 0, e = 0; c < n; ++c)
+        for (int r = 0; r < c; ++r)
+            if (adjacency[(size_t)r * n + c]) {
+                const uint32_t bit = 1u << (E - 1 - e);  // dec2bin(m, E): edge 1 is the most significant bit
+                A.in_base[c] |= bit;
+                A.out_base[r] |= bit;
+                ++e;
+            }
+    for (int v = 0; v < n; ++v)
+        if (A.in_base[v] | A.out_base[v]) A.active[A.n_active++] = v;
+    A.E = E;
+    A.all_edges = E == 32 ? 0xffffffffu : (1u << E) - 1u;
+    A.n_masks = 1ull << E;
+    const int64_t n_tiles = (int64_t)((A.n_masks + PDMPC_PRIO_TILE - 1) / PDMPC_PRIO_TILE);
+    ON_DEVICE(h->cfg.device);
+    if (h->d_prio_count.ensure((size_t)n_tiles) || h->d_prio_off.ensure((size_t)n_tiles + 1))
+        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the tile counts of pdmpc_unique_priorities");
+    int lrc = pdmpc_launch_priority_count(&A, n_tiles, h->d_prio_count.p, (void*)h->stream);
+    if (!lrc) lrc = pdmpc_launch_priority_scan(h->d_prio_count.p, n_tiles, h->d_prio_off.p, (void*)h->stream);
+    if (lrc) return fail(PDMPC_ERR_HIP, std::string("priority kernel launch failed: ") + hipGetErrorString((hipError_t)lrc));
+    int64_t K = 0;
+    HIPCHK(hipMemcpyAsync(&K, h->d_prio_off.p + n_tiles, sizeof K, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(sync_stream(h));
+    *n_out = K;
+    if (K > max_out) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "pdmpc_unique_priorities: %lld unique prioritizations, max_out is %lld", (long long)K, (long long)max_out);
+        return fail(PDMPC_ERR_CAPACITY, buf);
+    }
+    if (h->d_prio_mask.ensure((size_t)K) || h->d_prio_order.ensure((size_t)K * n))
+        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the output of pdmpc_unique_priorities");
+    lrc = pdmpc_launch_priority_write(&A, n_tiles, h->d_prio_off.p, K, h->d_prio_mask.p, (void*)h->stream);
+    if (!lrc) lrc = pdmpc_launch_priority_order(&A, h->d_prio_mask.p, K, h->d_prio_order.p, (void*)h->stream);
+    if (lrc) return fail(PDMPC_ERR_HIP, std::string("priority kernel launch failed: ") + hipGetErrorString((hipError_t)lrc));
+    HIPCHK(hipMemcpyAsync(masks, h->d_prio_mask.p, (size_t)K * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(priorities, h->d_prio_order.p, (size_t)K * n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(sync_stream(h));
     return PDMPC_OK;
 }
 

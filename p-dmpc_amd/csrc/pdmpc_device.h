@@ -277,6 +277,23 @@ struct JointArgs {
     JointLds lds;
 };
 
+// The unique prioritizations of a coupling graph (priority_kernel.hip; Prioritizer.unique_priorities, Prioritizer.m:97-140): edge e
+// (0-based, find(triu(adjacency, 1)) order: by column, then by row) runs edge_row -> edge_col unless orientation m flips it, which it
+// does exactly when bit E - 1 - e of m is set (dec2bin(m, E): edge 1 is the most significant bit).  So the flip set of lane m IS m.
+#define PDMPC_PRIO_MAX_N 64
+#define PDMPC_PRIO_MAX_E 32
+#define PDMPC_PRIO_THREADS 256  // a workgroup: four wavefronts
+#define PDMPC_PRIO_ROUNDS 16    // a tile: this many rounds of PDMPC_PRIO_THREADS consecutive masks
+#define PDMPC_PRIO_TILE (PDMPC_PRIO_THREADS * PDMPC_PRIO_ROUNDS)
+struct PriorityArgs {                          // passed by value: the kernels read it from the kernel arguments (uniform, scalar loads)
+    uint32_t in_base[PDMPC_PRIO_MAX_N];        // per vertex: the edges (as bits of m) that point INTO it when not flipped
+    uint32_t out_base[PDMPC_PRIO_MAX_N];       // ... that point OUT of it when not flipped (flipped, they point into it)
+    int32_t active[PDMPC_PRIO_MAX_N];          // the vertices that have edges, ascending
+    int32_t n, E, n_active;
+    uint32_t all_edges;                        // the E low bits
+    uint64_t n_masks;                          // 2^E
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -297,6 +314,12 @@ int pdmpc_launch_heap_script(const int32_t* op, const int32_t* id, const double*
                              void* stream);
 // joint_kernel.hip: centralized control, one workgroup of one wavefront per joint problem
 int pdmpc_launch_joint(const JointArgs* args, int n_problems, void* stream);
+// priority_kernel.hip: the acyclic orientations of a coupling graph in ascending mask order, compacted in two passes over tiles of
+// PDMPC_PRIO_TILE masks (count per tile, exclusive int64 scan, write), and the priorities of every written orientation
+int pdmpc_launch_priority_count(const PriorityArgs* args, int64_t n_tiles, uint32_t* tile_count, void* stream);
+int pdmpc_launch_priority_scan(const uint32_t* tile_count, int64_t n_tiles, int64_t* tile_off, void* stream);
+int pdmpc_launch_priority_write(const PriorityArgs* args, int64_t n_tiles, const int64_t* tile_off, int64_t capacity, uint32_t* masks, void* stream);
+int pdmpc_launch_priority_order(const PriorityArgs* args, const uint32_t* masks, int64_t count, int32_t* priorities, void* stream);
 int pdmpc_launch_edge_check(int mode, int n_cases, const int32_t* a_off, const double* a_x, const double* a_y, const int32_t* b_off, const double* b_x,
                             const double* b_y, int32_t* hit, void* stream);
 #ifdef __cplusplus

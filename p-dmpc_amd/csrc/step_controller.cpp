@@ -177,8 +177,12 @@ struct pdmpc_controller {
     std::vector<int32_t> x_pred_offset, x_pred_index, x_instance, x_vehicle, x_level, x_slot;  // x_slot[p * n + vehicle] = slot in the flattened batch
     std::vector<pdmpc_vehicle_out> x_out;
     std::vector<int32_t> x_chosen;  // per vehicle: the instance its sub-graph chose
-    std::vector<double> x_cost;     // n_perm x n_graphs
+    std::vector<double> x_cost;     // n_perm x n_graphs (the optimal step: n x K, row v = vehicle v's sums)
     int x_graphs = 0;
+    // optimal-priority step (PrioritizedOptimalController): the unique prioritizations of the step's coupling graph
+    std::vector<uint32_t> o_masks;  // [K] the acyclic orientations (pdmpc_unique_priorities)
+    std::vector<int32_t> o_prio;    // [K x n] their priorities
+    std::vector<double> o_val;      // [K x n] choice scratch: cost-to-come of the final node per (instance, vehicle), inf if exhausted
     std::string err;
 };
 
@@ -1322,13 +1326,87 @@ int pdmpc_exploration_permutations(int32_t n_levels, int32_t n_perm, uint32_t se
 // PrioritizedExplorativeController.m:25-91: the step's traffic state under n_perm prioritizations, one flattened batch: instance p
 // permutes the computation levels of the base prioritization (prepare_permutation :42-58: a vehicle of level L gets the position
 // of L in permutation p as its priority), slots ordered by (level, instance, slot).  Advances the time step like build_step.
+namespace {
+struct Exploring {  // (the memos of the obstacle sets are on while a step's prioritizations are assembled)
+    pdmpc_controller* c;
+    explicit Exploring(pdmpc_controller* ctl) : c(ctl) { c->exploring = true; }
+    ~Exploring() { c->exploring = false; }
+};
+
+// the batch of K instances: sized before the first keep_instance (copies into vectors that are kept from step to step: no allocation
+// once warm)
+void begin_instances(pdmpc_controller* c, int K) {
+    if (c->x_parts.size() < (size_t)K) c->x_parts.resize((size_t)K);
+    if (c->inst.size() != (size_t)K) c->inst.resize((size_t)K);
+}
+
+// the problem assemble_step just left in the controller becomes instance p
+void keep_instance(pdmpc_controller* c, int p) {
+    pdmpc_controller::Part& P = c->x_parts[(size_t)p];
+    P.in = c->in;
+    P.fb = c->fb;
+    P.pred_offset = c->pred_offset;
+    P.pred_index = c->pred_index;
+    pdmpc_controller::Instance& I = c->inst[(size_t)p];
+    I.directed = c->directed;
+    I.directed_seq = c->directed_seq;
+    I.levels = c->levels;
+    I.order = c->order;
+    I.slot_of = c->slot_of;
+}
+
+// flatten instances 0 .. K-1 into one batch, slots ordered by (level, instance, slot); then instance 0 is the controller's problem again
+void flatten_instances(pdmpc_controller* c, int K) {
+    const int n = c->n;
+    const std::vector<pdmpc_controller::Part>& parts = c->x_parts;
+    struct Key {
+        int32_t level, p, s;
+    };
+    std::vector<Key> flat;
+    for (int p = 0; p < K; ++p)
+        for (int s = 0; s < n; ++s) flat.push_back(Key{c->inst[(size_t)p].levels[(size_t)c->inst[(size_t)p].order[(size_t)s]], p, s});
+    std::stable_sort(flat.begin(), flat.end(), [](const Key& a, const Key& b) { return a.level < b.level; });  // (generated in (p, s) order)
+    const int N = K * n;
+    std::vector<int32_t> slot_of((size_t)N);  // [p * n + s]
+    for (int i = 0; i < N; ++i) slot_of[(size_t)flat[(size_t)i].p * n + flat[(size_t)i].s] = i;
+    c->x_in.resize((size_t)N);
+    c->x_fb.resize((size_t)N);
+    c->x_pred_offset.assign((size_t)N + 1, 0);
+    c->x_pred_index.clear();
+    c->x_instance.resize((size_t)N);
+    c->x_vehicle.resize((size_t)N);
+    c->x_level.resize((size_t)N);
+    c->x_slot.assign((size_t)N, 0);
+    for (int i = 0; i < N; ++i) {
+        const Key& k = flat[(size_t)i];
+        const pdmpc_controller::Part& P = parts[(size_t)k.p];
+        c->x_in[(size_t)i] = P.in[(size_t)k.s];
+        c->x_fb[(size_t)i] = P.fb[(size_t)k.s];
+        for (int32_t q = P.pred_offset[(size_t)k.s]; q < P.pred_offset[(size_t)k.s + 1]; ++q) c->x_pred_index.push_back(slot_of[(size_t)k.p * n + P.pred_index[(size_t)q]]);
+        c->x_pred_offset[(size_t)i + 1] = (int32_t)c->x_pred_index.size();
+        c->x_instance[(size_t)i] = k.p;
+        c->x_vehicle[(size_t)i] = c->inst[(size_t)k.p].order[(size_t)k.s];
+        c->x_level[(size_t)i] = k.level;
+        c->x_slot[(size_t)k.p * n + c->x_vehicle[(size_t)i]] = i;
+    }
+    c->x_pred_index.push_back(0);
+    // the controller's own problem again (instance 0)
+    c->in = parts[0].in;
+    c->fb = parts[0].fb;
+    c->pred_offset = parts[0].pred_offset;
+    c->pred_index = parts[0].pred_index;
+    const pdmpc_controller::Instance& I0 = c->inst[0];
+    c->directed = I0.directed;
+    c->directed_seq = I0.directed_seq;
+    c->levels = I0.levels;
+    c->order = I0.order;
+    c->slot_of = I0.slot_of;
+}
+}  // namespace
+
 int pdmpc_controller_explore_build(pdmpc_controller* c, int32_t n_perm, uint32_t seed) {
     if (!c || n_perm < 1) return cfail(c, PDMPC_ERR_INVALID, "bad argument");
-    struct Exploring {  // (the memos of the obstacle sets are on while this step's prioritizations are assembled)
-        pdmpc_controller* c;
-        explicit Exploring(pdmpc_controller* ctl) : c(ctl) { c->exploring = true; }
-        ~Exploring() { c->exploring = false; }
-    } exploring(c);
+    Exploring exploring(c);
     int rc = pdmpc_controller_build_step(c);  // instance 0: the controller's own prioritization
     if (rc) return rc;
     const int n = c->n;
@@ -1340,25 +1418,8 @@ int pdmpc_controller_explore_build(pdmpc_controller* c, int32_t n_perm, uint32_t
     std::vector<int32_t> perms((size_t)n_perm * n_levels);
     rc = pdmpc_exploration_permutations(n_levels, n_perm, seed, perms.data());
     if (rc) return rc;
-    // (copies into vectors that are kept from step to step: no allocation once warm)
-    using Part = pdmpc_controller::Part;
-    std::vector<Part>& parts = c->x_parts;
-    if (parts.size() < (size_t)n_perm) parts.resize((size_t)n_perm);
-    if (c->inst.size() != (size_t)n_perm) c->inst.resize((size_t)n_perm);
-    auto keep = [&](int p) {
-        Part& P = parts[(size_t)p];
-        P.in = c->in;
-        P.fb = c->fb;
-        P.pred_offset = c->pred_offset;
-        P.pred_index = c->pred_index;
-        pdmpc_controller::Instance& I = c->inst[(size_t)p];
-        I.directed = c->directed;
-        I.directed_seq = c->directed_seq;
-        I.levels = c->levels;
-        I.order = c->order;
-        I.slot_of = c->slot_of;
-    };
-    keep(0);
+    begin_instances(c, n_perm);
+    keep_instance(c, 0);
     std::vector<int32_t> where;
     for (int p = 1; p < n_perm; ++p) {
         where.assign((size_t)n_levels + 1, 0);
@@ -1381,51 +1442,9 @@ int pdmpc_controller_explore_build(pdmpc_controller* c, int32_t n_perm, uint32_t
                 }
         rc = assemble_step(c, true);
         if (rc) return rc;
-        keep(p);
+        keep_instance(c, p);
     }
-    // flatten: (level, instance, slot)
-    struct Key {
-        int32_t level, p, s;
-    };
-    std::vector<Key> flat;
-    for (int p = 0; p < n_perm; ++p)
-        for (int s = 0; s < n; ++s) flat.push_back(Key{c->inst[(size_t)p].levels[(size_t)c->inst[(size_t)p].order[(size_t)s]], p, s});
-    std::stable_sort(flat.begin(), flat.end(), [](const Key& a, const Key& b) { return a.level < b.level; });  // (generated in (p, s) order)
-    const int N = n_perm * n;
-    std::vector<int32_t> slot_of((size_t)N);  // [p * n + s]
-    for (int i = 0; i < N; ++i) slot_of[(size_t)flat[(size_t)i].p * n + flat[(size_t)i].s] = i;
-    c->x_in.resize((size_t)N);
-    c->x_fb.resize((size_t)N);
-    c->x_pred_offset.assign((size_t)N + 1, 0);
-    c->x_pred_index.clear();
-    c->x_instance.resize((size_t)N);
-    c->x_vehicle.resize((size_t)N);
-    c->x_level.resize((size_t)N);
-    c->x_slot.assign((size_t)N, 0);
-    for (int i = 0; i < N; ++i) {
-        const Key& k = flat[(size_t)i];
-        const Part& P = parts[(size_t)k.p];
-        c->x_in[(size_t)i] = P.in[(size_t)k.s];
-        c->x_fb[(size_t)i] = P.fb[(size_t)k.s];
-        for (int32_t q = P.pred_offset[(size_t)k.s]; q < P.pred_offset[(size_t)k.s + 1]; ++q) c->x_pred_index.push_back(slot_of[(size_t)k.p * n + P.pred_index[(size_t)q]]);
-        c->x_pred_offset[(size_t)i + 1] = (int32_t)c->x_pred_index.size();
-        c->x_instance[(size_t)i] = k.p;
-        c->x_vehicle[(size_t)i] = c->inst[(size_t)k.p].order[(size_t)k.s];
-        c->x_level[(size_t)i] = k.level;
-        c->x_slot[(size_t)k.p * n + c->x_vehicle[(size_t)i]] = i;
-    }
-    c->x_pred_index.push_back(0);
-    // the controller's own problem again (instance 0)
-    c->in = parts[0].in;
-    c->fb = parts[0].fb;
-    c->pred_offset = parts[0].pred_offset;
-    c->pred_index = parts[0].pred_index;
-    const pdmpc_controller::Instance& I0 = c->inst[0];
-    c->directed = I0.directed;
-    c->directed_seq = I0.directed_seq;
-    c->levels = I0.levels;
-    c->order = I0.order;
-    c->slot_of = I0.slot_of;
+    flatten_instances(c, n_perm);
     return PDMPC_OK;
 }
 
@@ -1512,12 +1531,12 @@ int explore_choose_on(pdmpc_controller* c, const int32_t* status, const double* 
 }
 }  // namespace
 
-// One explorative time step: build the batch, plan all prioritizations with ONE launch, choose per sub-graph, apply the chosen plans.
-int pdmpc_controller_explore_step(pdmpc_controller* c, int32_t n_perm) {
-    if (!c || !c->h) return cfail(c, PDMPC_ERR_INVALID, "controller has no backend handle");
-    auto t = std::chrono::steady_clock::now();
-    int rc = pdmpc_controller_explore_build(c, n_perm, (uint32_t)(c->k + 1));  // RandStream("mt19937ar", Seed = obj.k) (:249)
-    if (rc) return rc;
+// One time step over a batch of prioritizations (explorative or optimal): the batch is built, ONE launch plans all of it, `choose`
+// picks per vehicle the instance it goes on with (c->x_chosen), and the chosen plans are applied.
+extern "C++" {
+namespace {
+template <class Choose>
+int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, bool follow_own, Choose&& choose) {
     c->timing[0] = ms_since(t);
     const int N = (int)c->x_in.size();
     c->x_out.resize((size_t)N);
@@ -1526,6 +1545,7 @@ int pdmpc_controller_explore_step(pdmpc_controller* c, int32_t n_perm) {
         for (int i = 0; i < N; ++i) w[(size_t)i] = c->last_pops[(size_t)c->x_vehicle[(size_t)i]] + 1.0;
         (void)pdmpc_set_step_weights(c->h, N, w.data());
     }
+    int rc;
     if (c->lean_explore) {
         // the closed loop keeps the chosen plans only (obj.iter = obj.iter_array_tmp{chosen_solution}, :157-158): status and final
         // cost of every plan come back for the choice, the chosen vehicles' records afterwards — not 2.9 KB for each of the N plans
@@ -1536,12 +1556,12 @@ int pdmpc_controller_explore_step(pdmpc_controller* c, int32_t n_perm) {
         if (rc) return cfail(c, rc, pdmpc_last_error());
         add_call_timing(c);
         t = std::chrono::steady_clock::now();
-        rc = explore_choose_on(c, c->x_status.data(), c->x_final_cost.data(), nullptr, nullptr, nullptr);
+        rc = choose(c->x_status.data(), c->x_final_cost.data());
         if (rc) return rc;
         std::vector<int32_t> want((size_t)c->n);
         for (int s = 0; s < c->n; ++s) {
             const int v = c->order[(size_t)s];
-            want[(size_t)s] = c->x_slot[(size_t)(c->follow_own ? 0 : c->x_chosen[(size_t)v]) * c->n + v];
+            want[(size_t)s] = c->x_slot[(size_t)(follow_own ? 0 : c->x_chosen[(size_t)v]) * c->n + v];
         }
         c->out.resize((size_t)c->n);
         rc = pdmpc_fetch_records_at(c->h, c->n, want.data(), c->out.data());
@@ -1551,15 +1571,21 @@ int pdmpc_controller_explore_step(pdmpc_controller* c, int32_t n_perm) {
         if (rc) return cfail(c, rc, pdmpc_last_error());
         add_call_timing(c);
         t = std::chrono::steady_clock::now();
-        rc = pdmpc_controller_explore_choose(c, c->x_out.data(), nullptr, nullptr, nullptr);
+        c->x_status.resize((size_t)N);
+        c->x_final_cost.resize((size_t)N);
+        for (int s = 0; s < N; ++s) {
+            c->x_status[(size_t)s] = c->x_out[(size_t)s].status;
+            c->x_final_cost[(size_t)s] = c->x_out[(size_t)s].path_nodes[c->Hp][4];
+        }
+        rc = choose(c->x_status.data(), c->x_final_cost.data());
         if (rc) return rc;
         c->out.resize((size_t)c->n);
         for (int s = 0; s < c->n; ++s) {
             const int v = c->order[(size_t)s];
-            c->out[(size_t)s] = c->x_out[(size_t)c->x_slot[(size_t)(c->follow_own ? 0 : c->x_chosen[(size_t)v]) * c->n + v]];
+            c->out[(size_t)s] = c->x_out[(size_t)c->x_slot[(size_t)(follow_own ? 0 : c->x_chosen[(size_t)v]) * c->n + v]];
         }
     }
-    if (c->follow_own) {  // (the couplings of instance 0 again: what apply's fallback handling sees)
+    if (follow_own) {  // (the couplings of instance 0 again: what apply's fallback handling sees)
         c->directed = c->inst[0].directed;
         c->directed_seq = c->inst[0].directed_seq;
     }
@@ -1570,6 +1596,17 @@ int pdmpc_controller_explore_step(pdmpc_controller* c, int32_t n_perm) {
     for (int i = 0; i < 6; ++i) c->timing_sum[i] += c->timing[i];
     c->timing_steps += 1;
     return rc;
+}
+}  // namespace
+}  // extern "C++"
+
+// One explorative time step: build the batch, plan all prioritizations with ONE launch, choose per sub-graph, apply the chosen plans.
+int pdmpc_controller_explore_step(pdmpc_controller* c, int32_t n_perm) {
+    if (!c || !c->h) return cfail(c, PDMPC_ERR_INVALID, "controller has no backend handle");
+    const auto t = std::chrono::steady_clock::now();
+    const int rc = pdmpc_controller_explore_build(c, n_perm, (uint32_t)(c->k + 1));  // RandStream("mt19937ar", Seed = obj.k) (:249)
+    if (rc) return rc;
+    return batch_step(c, t, c->follow_own, [c](const int32_t* status, const double* final_cost) { return explore_choose_on(c, status, final_cost, nullptr, nullptr, nullptr); });
 }
 
 int pdmpc_controller_explore_follow_own(pdmpc_controller* c, int32_t on) {
@@ -1599,6 +1636,189 @@ int pdmpc_controller_explore_result(pdmpc_controller* c, int32_t* chosen, int32_
     if (!c || c->x_chosen.empty()) return cfail(c, PDMPC_ERR_INVALID, "no explorative step has been chosen");
     if (chosen) std::copy(c->x_chosen.begin(), c->x_chosen.end(), chosen);
     if (n_graphs) *n_graphs = c->x_graphs;
+    if (cost) *cost = c->x_cost.data();
+    if (records) *records = c->x_out.empty() ? nullptr : c->x_out.data();
+    return PDMPC_OK;
+}
+
+// Prioritizer.unique_priorities (Prioritizer.m:97-140) on the host: the twin of the device enumeration (csrc/priority_kernel.hip) and its
+// checker.  Every orientation is tested by peeling its sources off vertex by vertex over explicit edge lists (the kernel peels bit sets);
+// the priorities follow the smallest-index-first topological order (toposort(..., 'Order', 'stable')).
+int pdmpc_unique_priorities_host(int32_t n, const uint8_t* adjacency, int64_t max_out, int64_t* n_out, uint32_t* masks, int32_t* priorities) {
+    if (n_out) *n_out = -1;
+    if (n < 1 || !adjacency || !n_out || max_out < 0 || (max_out > 0 && (!masks || !priorities)))
+        return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_unique_priorities_host: bad argument");
+    if (n > 64) return cfail(nullptr, PDMPC_ERR_CAPACITY, "pdmpc_unique_priorities_host: more than 64 vehicles");
+    std::vector<int> er, ec;  // [edge_row, edge_col] = find(triu(adjacency, 1)): by column, then by row
+    for (int c = 0; c < n; ++c)
+        for (int r = 0; r < c; ++r)
+            if (adjacency[(size_t)r * n + c]) {
+                er.push_back(r);
+                ec.push_back(c);
+            }
+    const int E = (int)er.size();
+    if (E > 32) return cfail(nullptr, PDMPC_ERR_CAPACITY, "pdmpc_unique_priorities_host: more than 32 coupling edges");
+    const uint64_t n_masks = 1ull << E;
+    std::vector<int> head((size_t)E), tail((size_t)E), indeg((size_t)n), order((size_t)n);
+    std::vector<uint8_t> placed((size_t)n);
+    // the lexicographically smallest topological order of orientation m, false if m has a cycle (Kahn, smallest available vertex first)
+    auto toposort = [&](uint64_t m) {
+        std::fill(indeg.begin(), indeg.end(), 0);
+        for (int e = 0; e < E; ++e) {
+            const bool flip = (m >> (E - 1 - e)) & 1u;  // dec2bin(m, E) == '1': edge 1 is the most significant bit
+            tail[(size_t)e] = flip ? ec[(size_t)e] : er[(size_t)e];
+            head[(size_t)e] = flip ? er[(size_t)e] : ec[(size_t)e];
+            ++indeg[(size_t)head[(size_t)e]];
+        }
+        std::fill(placed.begin(), placed.end(), 0);
+        for (int pos = 0; pos < n; ++pos) {
+            int v = 0;
+            while (v < n && (placed[(size_t)v] || indeg[(size_t)v] != 0)) ++v;
+            if (v == n) return false;
+            placed[(size_t)v] = 1;
+            order[(size_t)pos] = v;
+            for (int e = 0; e < E; ++e)
+                if (tail[(size_t)e] == v) --indeg[(size_t)head[(size_t)e]];
+        }
+        return true;
+    };
+    int64_t K = 0;
+    for (uint64_t m = 0; m < n_masks; ++m) {
+        if (!toposort(m)) continue;
+        if (K < max_out) {
+            masks[K] = (uint32_t)m;
+            for (int pos = 0; pos < n; ++pos) priorities[(size_t)K * n + order[(size_t)pos]] = pos + 1;  // priority(topological_order) = 1:n
+        }
+        ++K;
+    }
+    *n_out = K;
+    if (K > max_out) return cfail(nullptr, PDMPC_ERR_CAPACITY, "pdmpc_unique_priorities_host: more unique prioritizations than max_out");
+    return PDMPC_OK;
+}
+
+// ---- the optimal-priority step (PrioritizedOptimalController.m; twin of pdmpc.optimal.build_optimal_batch / choose_solution / optimal_step)
+// :25-53 + controller (:134-152): the step's traffic state under every unique prioritization of its coupling graph, one flattened batch:
+// prepare_permutation = prioritize() with constant priorities = prioritization p, then group(); slots ordered by (level, instance, slot).
+int pdmpc_controller_optimal_build(pdmpc_controller* c, int32_t max_instances) {
+    if (!c || max_instances < 1) return cfail(c, PDMPC_ERR_INVALID, "bad argument");
+    Exploring exploring(c);
+    int rc = pdmpc_controller_build_step(c);  // traffic info and coupling of the step (and the controller's own problem, replaced below)
+    if (rc) return rc;
+    const int n = c->n;
+    c->o_masks.resize((size_t)max_instances);
+    c->o_prio.resize((size_t)max_instances * n);
+    int64_t K = 0;
+    if (c->h) {
+        rc = pdmpc_unique_priorities(c->h, n, c->adjacency.data(), max_instances, &K, c->o_masks.data(), c->o_prio.data());
+        if (rc) return cfail(c, rc, pdmpc_last_error());
+    } else {
+        rc = pdmpc_unique_priorities_host(n, c->adjacency.data(), max_instances, &K, c->o_masks.data(), c->o_prio.data());
+        if (rc) return cfail(c, rc, g_cerr);
+    }
+    c->o_masks.resize((size_t)K);
+    c->o_prio.resize((size_t)K * n);
+    begin_instances(c, (int)K);
+    for (int p = 0; p < (int)K; ++p) {
+        // ConstantPrioritizer on the given priorities + directed_coupling_from_priorities (Prioritizer.m:64-77): keep i -> j iff
+        // priority(i) <= priority(j); then assemble_step groups (cuts to max_num_CLs levels) per instance
+        const int32_t* pr = c->o_prio.data() + (size_t)p * n;
+        c->directed.assign((size_t)n * n, 0);
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < n; ++j)
+                if (at(c->adjacency, n, i, j) && !(pr[j] < pr[i])) at(c->directed, n, i, j) = 1;
+        rc = assemble_step(c);
+        if (rc) return rc;
+        keep_instance(c, p);
+    }
+    flatten_instances(c, (int)K);
+    return PDMPC_OK;
+}
+
+// compute_solution_cost / receive_solution_cost / choose_solution (:56-114): every vehicle sums the solution costs of ALL vehicles per
+// instance (its own first, then the others' messages in ascending index), rounds to 8 decimals and takes the first minimum
+namespace {
+int optimal_choose_on(pdmpc_controller* c, const int32_t* status, const double* final_cost) {
+    const int n = c->n, K = (int)c->inst.size();
+    std::vector<double>& val = c->o_val;  // [p * n + v]
+    val.assign((size_t)K * n, 0.0);
+    for (int s = 0; s < K * n; ++s) {
+        if (status[s] != PDMPC_OK && status[s] != PDMPC_EXHAUSTED) return cfail(c, PDMPC_ERR_HIP, "a result record carries an error status: not a planning result");
+        val[(size_t)c->x_instance[(size_t)s] * n + c->x_vehicle[(size_t)s]] = status[s] == PDMPC_OK ? final_cost[s] : std::numeric_limits<double>::infinity();
+    }
+    c->x_cost.assign((size_t)n * K, 0.0);
+    c->x_chosen.resize((size_t)n);
+    for (int v = 0; v < n; ++v) {
+        double* row = c->x_cost.data() + (size_t)v * K;
+        for (int p = 0; p < K; ++p) {
+            double sum = val[(size_t)p * n + v];
+            for (int j = 0; j < n; ++j)
+                if (j != v) sum += val[(size_t)p * n + j];
+            row[p] = std::nearbyint(sum * 1e8) / 1e8;
+        }
+        int best = 0;
+        for (int p = 1; p < K; ++p)
+            if (row[p] < row[best]) best = p;  // [~, chosen_solution] = min(.): the first minimum
+        c->x_chosen[(size_t)v] = best;
+    }
+    c->x_graphs = K;
+    // obj.iter = obj.iter_array_tmp{chosen_solution} (:100): every vehicle goes on with the couplings of its chosen instance
+    for (int i = 0; i < n; ++i) {
+        const pdmpc_controller::Instance& I = c->inst[(size_t)c->x_chosen[(size_t)i]];
+        for (int j = 0; j < n; ++j) {
+            at(c->directed, n, i, j) = at(I.directed, n, i, j);
+            at(c->directed_seq, n, i, j) = at(I.directed_seq, n, i, j);
+        }
+    }
+    return PDMPC_OK;
+}
+}  // namespace
+
+int pdmpc_controller_optimal_choose(pdmpc_controller* c, const pdmpc_vehicle_out* recs, int32_t* chosen, double* cost) {
+    if (!c || !recs || c->inst.empty() || c->o_masks.size() != c->inst.size()) return cfail(c, PDMPC_ERR_INVALID, "no optimal-priority batch has been built");
+    const int N = (int)c->inst.size() * c->n;
+    std::vector<int32_t> st((size_t)N);
+    std::vector<double> fc((size_t)N);
+    for (int s = 0; s < N; ++s) {
+        st[(size_t)s] = recs[s].status;
+        fc[(size_t)s] = recs[s].path_nodes[c->Hp][4];
+    }
+    const int rc = optimal_choose_on(c, st.data(), fc.data());
+    if (rc) return rc;
+    if (chosen) std::copy(c->x_chosen.begin(), c->x_chosen.end(), chosen);
+    if (cost) std::copy(c->x_cost.begin(), c->x_cost.end(), cost);
+    return PDMPC_OK;
+}
+
+// One optimal-priority time step: every unique prioritization planned with ONE launch, the choice per vehicle, the chosen plans applied.
+int pdmpc_controller_optimal_step(pdmpc_controller* c, int32_t max_instances) {
+    if (!c || !c->h) return cfail(c, PDMPC_ERR_INVALID, "controller has no backend handle");
+    const auto t = std::chrono::steady_clock::now();
+    const int rc = pdmpc_controller_optimal_build(c, max_instances);
+    if (rc) return rc;
+    return batch_step(c, t, false, [c](const int32_t* status, const double* final_cost) { return optimal_choose_on(c, status, final_cost); });
+}
+
+int pdmpc_controller_optimal_run(pdmpc_controller* c, int32_t max_instances, int32_t n_steps, double* ms) {
+    if (!c) return cfail(c, PDMPC_ERR_INVALID, "null argument");
+    struct Lean {  // (nobody looks at the plans that were not chosen)
+        pdmpc_controller* c;
+        bool was;
+        ~Lean() { c->lean_explore = was; }
+    } lean{c, c->lean_explore};
+    c->lean_explore = true;
+    for (int i = 0; i < n_steps; ++i) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const int rc = pdmpc_controller_optimal_step(c, max_instances);
+        if (rc) return rc;
+        if (ms) ms[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_optimal_result(pdmpc_controller* c, int32_t* chosen, int32_t* n_instances, const double** cost, const pdmpc_vehicle_out** records) {
+    if (!c || c->x_chosen.empty() || c->o_masks.size() != c->inst.size()) return cfail(c, PDMPC_ERR_INVALID, "no optimal-priority step has been chosen");
+    if (chosen) std::copy(c->x_chosen.begin(), c->x_chosen.end(), chosen);
+    if (n_instances) *n_instances = (int32_t)c->inst.size();
     if (cost) *cost = c->x_cost.data();
     if (records) *records = c->x_out.empty() ? nullptr : c->x_out.data();
     return PDMPC_OK;

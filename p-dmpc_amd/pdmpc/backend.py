@@ -91,6 +91,13 @@ EXPORTS = [
     "pdmpc_controller_explore_step",
     "pdmpc_controller_explore_run",
     "pdmpc_controller_explore_result",
+    "pdmpc_unique_priorities",
+    "pdmpc_unique_priorities_host",
+    "pdmpc_controller_optimal_build",
+    "pdmpc_controller_optimal_choose",
+    "pdmpc_controller_optimal_step",
+    "pdmpc_controller_optimal_run",
+    "pdmpc_controller_optimal_result",
     "pdmpc_last_error",
     "pdmpc_version",
 ]
@@ -98,6 +105,45 @@ EXPORTS = [
 
 class BackendError(RuntimeError):
     pass
+
+
+class CapacityError(BackendError):
+    """PDMPC_ERR_CAPACITY from pdmpc_unique_priorities(_host): `count` is the true number of unique prioritizations (-1 when the
+    graph is outside the limits: more than 64 vehicles or 32 coupling edges)."""
+
+    def __init__(self, msg, count):
+        super().__init__(msg)
+        self.count = count
+
+
+ERR_CAPACITY = -4
+
+
+def unique_priorities_call(adjacency, max_out, handle=None):
+    """pdmpc_unique_priorities on `handle`'s device, or pdmpc_unique_priorities_host without one -> (priorities n x K, masks [K]),
+    the reference's column layout.  Raises CapacityError for PDMPC_ERR_CAPACITY."""
+    L = load_library()
+    A = np.ascontiguousarray(np.asarray(adjacency) != 0, dtype=np.uint8)
+    n = A.shape[0]
+    cap = max(int(max_out), 0)
+    masks = np.zeros(max(cap, 1), dtype=np.uint32)
+    prio = np.zeros(max(cap, 1) * n, dtype=np.int32)
+    K = C.c_int64(0)
+    args = [n, A.ctypes.data_as(abi.c_uint8_p), cap, C.byref(K), masks.ctypes.data_as(C.POINTER(C.c_uint32)), prio.ctypes.data_as(abi.c_int32_p)]
+    if handle is not None:
+        rc = L.pdmpc_unique_priorities(handle.h, *args)
+        what = "pdmpc_unique_priorities"
+    else:
+        rc = L.pdmpc_unique_priorities_host(*args)
+        what = "pdmpc_unique_priorities_host"
+    if rc == ERR_CAPACITY:
+        raise CapacityError("%s: capacity (%d unique prioritizations, max_out %d)" % (what, K.value, cap), K.value)
+    if handle is not None:
+        _check(L, rc, what)
+    elif rc != 0:
+        raise BackendError("%s failed with status %d" % (what, rc))
+    k = K.value
+    return prio[: k * n].reshape(k, n).T.astype(np.int64), masks[:k].astype(np.int64)
 
 
 def load_library(path=None):
@@ -153,6 +199,8 @@ def load_library(path=None):
     L.pdmpc_debug_raw_tree.argtypes = [H, C.c_int32, C.c_int32] + [abi.c_double_p] * 5 + [abi.c_int32_p] * 3 + [abi.c_double_p, abi.c_uint8_p, abi.c_int32_p]
     L.pdmpc_debug_edge_check.argtypes = [H, C.c_int32, C.c_int32, abi.c_int32_p, abi.c_double_p, abi.c_double_p, abi.c_int32_p, abi.c_double_p, abi.c_double_p, abi.c_int32_p]
     L.pdmpc_debug_progress.argtypes = [H, C.c_int32, C.POINTER(C.c_uint32)]
+    L.pdmpc_unique_priorities.argtypes = [H, C.c_int32, abi.c_uint8_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), abi.c_int32_p]
+    L.pdmpc_unique_priorities_host.argtypes = [C.c_int32, abi.c_uint8_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), abi.c_int32_p]
     L.pdmpc_last_error.restype = C.c_char_p
     L.pdmpc_version.restype = C.c_char_p
     for name in EXPORTS:
@@ -375,6 +423,10 @@ class Handle:
         _check(self.L, self.L.pdmpc_plan_joint(self.h, len(problems), off.ctypes.data_as(abi.c_int32_p), arr, abi.out_ptr(out)), "pdmpc_plan_joint")
         del keep
         return self._checked(out[:n])
+
+    def unique_priorities(self, adjacency, max_out):
+        """Prioritizer.unique_priorities on this handle's device (pdmpc_unique_priorities) -> (priorities n x K, masks [K])."""
+        return unique_priorities_call(adjacency, max_out, handle=self)
 
     # ---- device-resident path ----
     def pack_batch(self, iters):

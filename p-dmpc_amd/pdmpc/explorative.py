@@ -118,6 +118,17 @@ def build_exploration_batch(ctl, n_perm, seed):
                         seq[i, j], seq[j, i] = False, True
             prob = ctl.build_step_problem(refresh=False, couplings=(directed, seq))
         parts.append(prob)
+    out = flatten_instances(parts)
+    out["n_instances"] = n_perm
+    out["adjacency"] = np.array(ctl.last_adjacency)
+    out["graph_coupling"] = np.array(base["directed_seq"])  # the sub-graphs of the cost choice: conncomp(directed_coupling_sequential) of the base prioritization (:94-112)
+    return out
+
+
+def flatten_instances(parts):
+    """Step problems of the same traffic state (one per prioritization) -> one problem, slots ordered by (level, instance, slot), with
+    `instance` and `vehicle` per slot and every instance's sequential coupling (`directed_seq`: what a vehicle that goes on with it
+    inherits)."""
     flat = []
     for p, prob in enumerate(parts):
         for s in range(len(prob["iters"])):
@@ -136,10 +147,7 @@ def build_exploration_batch(ctl, n_perm, seed):
         out["vehicle"].append(prob["order"][s])
     lv = np.array(out["levels"])
     out["level_sizes"] = [int(np.sum(lv == l)) for l in range(1, int(lv.max()) + 1)]
-    out["n_instances"] = n_perm
-    out["adjacency"] = np.array(ctl.last_adjacency)
-    out["graph_coupling"] = np.array(base["directed_seq"])  # the sub-graphs of the cost choice: conncomp(directed_coupling_sequential) of the base prioritization (:94-112)
-    out["directed_seq"] = [prob["directed_seq"] for prob in parts]  # per instance: what a vehicle that goes on with it inherits
+    out["directed_seq"] = [prob["directed_seq"] for prob in parts]
     return out
 
 

@@ -64,8 +64,14 @@ def _declare(L):
     L.pdmpc_controller_explore_step.argtypes = [H, C.c_int32]
     L.pdmpc_controller_explore_run.argtypes = [H, C.c_int32, C.c_int32, abi.c_double_p]
     L.pdmpc_controller_explore_result.argtypes = [H, abi.c_int32_p, C.POINTER(C.c_int32), C.POINTER(abi.c_double_p), C.POINTER(C.POINTER(abi.VehicleOut))]
+    L.pdmpc_controller_optimal_build.argtypes = [H, C.c_int32]
+    L.pdmpc_controller_optimal_choose.argtypes = [H, C.POINTER(abi.VehicleOut), abi.c_int32_p, abi.c_double_p]
+    L.pdmpc_controller_optimal_step.argtypes = [H, C.c_int32]
+    L.pdmpc_controller_optimal_run.argtypes = [H, C.c_int32, C.c_int32, abi.c_double_p]
+    L.pdmpc_controller_optimal_result.argtypes = [H, abi.c_int32_p, C.POINTER(C.c_int32), C.POINTER(abi.c_double_p), C.POINTER(C.POINTER(abi.VehicleOut))]
     for name in ("pdmpc_controller_explore_build", "pdmpc_controller_explore_problem", "pdmpc_controller_explore_choose", "pdmpc_controller_explore_step",
-                 "pdmpc_controller_explore_run", "pdmpc_controller_explore_result"):
+                 "pdmpc_controller_explore_run", "pdmpc_controller_explore_result", "pdmpc_controller_optimal_build", "pdmpc_controller_optimal_choose",
+                 "pdmpc_controller_optimal_step", "pdmpc_controller_optimal_run", "pdmpc_controller_optimal_result"):
         getattr(L, name).restype = C.c_int
     for name in ("pdmpc_controller_create", "pdmpc_controller_destroy", "pdmpc_controller_step", "pdmpc_controller_build_step", "pdmpc_controller_apply",
                  "pdmpc_controller_problem", "pdmpc_controller_state"):
@@ -278,6 +284,45 @@ class NativeController:
     def explore_run(self, n_perm, n_steps):
         ms = np.zeros(max(n_steps, 1))
         self._check(self.L.pdmpc_controller_explore_run(self.c, n_perm, n_steps, ms.ctypes.data_as(abi.c_double_p)), "pdmpc_controller_explore_run")
+        return ms[:n_steps]
+
+    # ---- the optimal-priority step: twin of pdmpc.optimal
+    def optimal_build(self, max_instances):
+        """Every unique prioritization of the step as one batch (pdmpc_controller_optimal_build) -> K."""
+        self._check(self.L.pdmpc_controller_optimal_build(self.c, max_instances), "pdmpc_controller_optimal_build")
+        n = C.c_int32()
+        self._check(self.L.pdmpc_controller_explore_problem(self.c, C.byref(n), None, None, None, None, None, None, None), "pdmpc_controller_explore_problem")
+        self.n_perm = n.value // self.n
+        return self.n_perm
+
+    def optimal_problem(self):
+        """The flattened batch of the last optimal_build in the dict form of optimal.build_optimal_batch (for tests)."""
+        return self.explore_problem()
+
+    def optimal_choose(self, records):
+        """-> (instance chosen per vehicle, cost table n x K)."""
+        recs = np.ascontiguousarray(records)
+        chosen = np.zeros(self.n, dtype=np.int32)
+        cost = np.zeros(self.n * self.n_perm)
+        self._check(self.L.pdmpc_controller_optimal_choose(self.c, abi.out_ptr(recs), chosen.ctypes.data_as(abi.c_int32_p), cost.ctypes.data_as(abi.c_double_p)),
+                    "pdmpc_controller_optimal_choose")
+        return chosen, cost.reshape(self.n, self.n_perm)
+
+    def optimal_step(self, max_instances):
+        """One optimal-priority time step natively (batch, ONE launch, choice, apply) -> (records of the batch, chosen instance per vehicle)."""
+        self._check(self.L.pdmpc_controller_optimal_step(self.c, max_instances), "pdmpc_controller_optimal_step")
+        chosen = np.zeros(self.n, dtype=np.int32)
+        k = C.c_int32()
+        p = C.POINTER(abi.VehicleOut)()
+        self._check(self.L.pdmpc_controller_optimal_result(self.c, chosen.ctypes.data_as(abi.c_int32_p), C.byref(k), None, C.byref(p)), "pdmpc_controller_optimal_result")
+        self.n_perm = k.value
+        recs = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(self.n * k.value * abi.VEHICLE_OUT_DTYPE.itemsize,)).view(abi.VEHICLE_OUT_DTYPE).copy()
+        return recs, chosen
+
+    def optimal_run(self, max_instances, n_steps):
+        """n_steps optimal-priority steps in one native call (status + final cost of every plan, the chosen records only) -> ms per step."""
+        ms = np.zeros(max(n_steps, 1))
+        self._check(self.L.pdmpc_controller_optimal_run(self.c, max_instances, n_steps, ms.ctypes.data_as(abi.c_double_p)), "pdmpc_controller_optimal_run")
         return ms[:n_steps]
 
     def state(self):
