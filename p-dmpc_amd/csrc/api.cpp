@@ -18,6 +18,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/pdmpc.h"
@@ -69,21 +70,18 @@ struct DeviceGuard {
 
 inline uint32_t align16(uint32_t v) { return (v + 15u) & ~15u; }
 
+// Buffers own their memory: move-only (a vector of banks moves them when it grows), freed with their owner.
 template <class T>
 struct DevBuf {
     T* p = nullptr;
     size_t cap = 0;  // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    ~DevBuf() { release(); }
     int ensure(size_t n) {
-        if (n <= cap) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = std::max(n, (size_t)64);
-        want += want / 2;
-        hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
-        if (e != hipSuccess) return (int)e;
-        cap = want;
-        return 0;
+        const size_t want = std::max(n, (size_t)64);
+        return n <= cap ? 0 : ensure_exact(want + want / 2);
     }
     int ensure_exact(size_t n) {  // no head room: the arenas are sized in gigabytes
         if (n <= cap) return 0;
@@ -106,19 +104,12 @@ template <class T>
 struct PinnedBuf {
     T* p = nullptr;
     size_t cap = 0;
-    int ensure(size_t n) {
-        if (n <= cap) return 0;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = std::max(n, (size_t)64);
-        want += want / 2;
-        hipError_t e = hipHostMalloc((void**)&p, want * sizeof(T), hipHostMallocDefault);
-        if (e != hipSuccess) return (int)e;
-        cap = want;
-        return 0;
-    }
-    int ensure_keep(size_t n, size_t keep) {  // as ensure, the first `keep` elements carried over
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf(PinnedBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    ~PinnedBuf() { release(); }
+    int ensure(size_t n) { return ensure_keep(n, 0); }
+    int ensure_keep(size_t n, size_t keep) {  // the first `keep` elements carried over
         if (n <= cap) return 0;
         size_t want = std::max(n, (size_t)64);
         want += want / 2;
@@ -138,7 +129,58 @@ struct PinnedBuf {
     }
 };
 
+// The per-vehicle arenas of the searches (NodeArena, pdmpc_device.h): max_nodes entries per vehicle in every array (contents are
+// scratch: every search starts from an empty tree).
+struct Arenas {
+    uint32_t max_nodes = 0;
+    DevBuf<NodeRec> nodes;
+    DevBuf<double> key, far_key, mid_key, pb_key, walk;
+    DevBuf<unsigned long long> link;
+    DevBuf<uint32_t> far_id, mid_id, pb_d, child0, vlist;
+    DevBuf<uint8_t> vstate;
+    // every array with its entries per node: walk holds 16 bytes per node, vlist the verification's Hp + 1 lists
+    template <class Self, class F>
+    static void each(Self& a, int Hp, F&& f) {
+        f(a.nodes, 1);
+        f(a.key, 1);
+        f(a.link, 1);
+        f(a.vstate, 1);
+        f(a.far_key, 1);
+        f(a.far_id, 1);
+        f(a.mid_key, 1);
+        f(a.mid_id, 1);
+        f(a.pb_key, 1);
+        f(a.pb_d, 1);
+        f(a.walk, 2);
+        f(a.child0, 1);
+        f(a.vlist, Hp + 1);
+    }
+    size_t bytes_per_node(int Hp) const {
+        size_t sum = 0;
+        each(*this, Hp, [&](const auto& b, int per) { sum += (size_t)per * sizeof *b.p; });
+        return sum;
+    }
+    // everything released first (the arenas are sized in gigabytes); on failure max_nodes is 0 and the caller allocates again
+    int alloc(int max_vehicles, uint32_t n, int Hp) {
+        n = (n + 1u) & ~1u;
+        const size_t tot = (size_t)max_vehicles * n;
+        each(*this, Hp, [](auto& b, int) { b.release(); });
+        max_nodes = 0;
+        int bad = 0;
+        each(*this, Hp, [&](auto& b, int per) { bad |= b.ensure_exact(tot * (size_t)per); });
+        if (bad) return bad;
+        max_nodes = n;
+        return 0;
+    }
+    NodeArena view() const {
+        return {nodes.p, key.p, link.p, vstate.p, far_key.p, far_id.p, mid_key.p, mid_id.p, pb_key.p, pb_d.p, walk.p, child0.p, vlist.p};
+    }
+};
+
 const size_t kLdsMax = 160 * 1024;  // gfx950: 160 KiB per CU (MI355X_MICROARCH.md)
+
+// pdmpc_stats.kernel: what the last launch ran
+enum LaunchKind : int32_t { kLaunchSearch = 2, kLaunchSampled = 3, kLaunchJoint = 4 };
 
 }  // namespace
 
@@ -161,24 +203,17 @@ struct PackedStep {
     std::vector<int64_t> lit_cols;  // per slot: literal soup + boundary columns (for the bytes formula)
     std::vector<int32_t> perm;      // empty: slot s holds the caller's vehicle s; else slot s holds vehicle perm[s] (pack_common put the batch into level order)
     std::vector<int32_t> inv;       // ... and vehicle v sits in slot inv[v]
-    void release() {
-        h_blob.release();
-        d_blob.release();
-        h_veh = d_veh = nullptr;
-        h_pts = d_pts = nullptr;
-        h_pred = d_pred = nullptr;
-    }
 };
 
-// Tuning knobs and A/B / test switches of the graph search.  The defaults are the measured optima quoted next to their use; every
-// setting leaves the results bit-identical.  ONE environment variable overrides them, read once in pdmpc_create (a launch makes no
-// getenv call):  PDMPC_TUNING="key=value,key=value,..."  with the keys below (include/pdmpc.h documents the variable).
 // what pack_common tells vehicles that hand over the same arrays by: the pointers and counts of a vehicle's polygon sets
 struct SoupKey {
     const void* p[13];
     int32_t c[6];
 };
 
+// Tuning knobs and A/B / test switches of the graph search.  The defaults are the measured optima quoted next to their use; every
+// setting leaves the results bit-identical.  ONE environment variable overrides them, read once in pdmpc_create (a launch makes no
+// getenv call):  PDMPC_TUNING="key=value,key=value,..."  with the keys below (include/pdmpc.h documents the variable).
 struct Tuning {
     int round0 = -1;        // nodes a round of a young search takes (-1: 24; 32 for a launch that leaves CUs idle but has fewer than four helpers per search, C3, and for one of more than two searches per CU, C5)
     int round = -1;         // the most a round takes (-1: 1000 with helper workgroups, else 256)
@@ -279,18 +314,12 @@ struct pdmpc_handle {
     DevBuf<double> d_area;
     size_t mask_bytes = 0, mi_bytes = 0;
     int64_t mpa_alg_bytes = 0;
-    // arenas (NodeArena, pdmpc_device.h)
-    uint32_t max_nodes = 0;
+    Arenas arena;
     uint32_t max_nodes_limit = 0;  // pdmpc_plan_* may grow the arenas up to this many nodes per vehicle (0: as far as HBM allows)
     int64_t arena_regrows = 0;     // times an overflowed call was re-planned with larger arenas
     int64_t safe_replans = 0;      // times a call was re-planned in resident slices after a predecessor time-out
     bool safe_launches = false;    // pdmpc_set_safe_launch: every launch in resident slices
     int max_vehicles = 0;
-    DevBuf<NodeRec> anodes;
-    DevBuf<double> akey, afark, amidk, apbk, awalk;
-    DevBuf<unsigned long long> alink;
-    DevBuf<uint32_t> afari, amidi, apbd, achild0, avlist;
-    DevBuf<uint8_t> avs;
     DevBuf<pdmpc_vehicle_out> d_out;
     DevBuf<uint32_t> d_flag;
     DevBuf<int32_t> d_tree_size;
@@ -301,15 +330,11 @@ struct pdmpc_handle {
     DevBuf<double> d_bk_post;                 // records posted for the helper workgroups
     DevBuf<double> d_random;  // sampled optimizer: random numbers of the batch
     int sampled_n_random = 0;
-    bool sampled_launch = false;
-    bool last_launch_search = false;     // the last launch ran the graph search (not the sampled optimizer)
-    bool last_launch_joint = false;      // the last launch ran the joint search of centralized control (pdmpc_plan_joint)
+    LaunchKind launch_kind = kLaunchSampled;  // of the last launch (before the first one: what pdmpc_get_last_stats always reported)
     DevBuf<int32_t> d_joint_off;         // pdmpc_plan_joint: the problems' first slots
     DevBuf<uint32_t> d_prio_count, d_prio_mask;  // pdmpc_unique_priorities: acyclic masks per tile, the acyclic masks
     DevBuf<int64_t> d_prio_off;                  // ... exclusive offsets of the tiles (entry n_tiles: the total)
     DevBuf<int32_t> d_prio_order;                // ... the priorities of every acyclic mask
-    int last_first = 0, last_count = 0;  // slots of the last launch_range
-    bool last_safe = false;              // ... and whether it went out in resident slices
     int device_share = 1;                // handles of one process that launch on this device side by side (pdmpc_set_device_share: a group's logical ranks)
     bool boards_dirty = true;            // the helper boards / the finished counter need clearing before the helper workgroups may read them
     uint32_t help_fin_total = 0;         // value of the finished counter once every launch so far has ended
@@ -339,13 +364,23 @@ struct pdmpc_handle {
     LdsLayout lds{};
     int NL = 0, NV = 0, areas_in_lds = 0;
     pdmpc_stats stats{};
+    // the buffers free themselves after this: the stream is idle by then
+    ~pdmpc_handle() {
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (auto& ev : events) {
+            (void)hipEventDestroy(ev.first);
+            (void)hipEventDestroy(ev.second);
+        }
+        if (progress) (void)hipHostFree(progress);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
 };
 
 namespace {
 
 // The dynamic LDS size of a kernel is an attribute of the function ON THE DEVICE, not of a handle (hipFuncSetAttribute sets a
 // maximum): the largest size set so far is kept per device and kernel (0 bulk, 1 bulk wide, 2 bulk SAT, 3 bulk compact), shared by every handle.
-const size_t kMaxLaunchEvents = 4096;  // event pairs a handle keeps before it folds their times (launch_range)
+const size_t kMaxLaunchEvents = 4096;  // event pairs a handle keeps before it folds their times (begin_timed_launch)
 std::mutex g_lds_mutex;
 uint32_t g_lds_high_water[64][4];
 
@@ -354,6 +389,21 @@ inline hipError_t sync_stream(pdmpc_handle* h) {
     const hipError_t e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess) h->sync_serial += 1;
     return e;
+}
+
+// The automaton's tables, the front of every LDS layout from `off` on: successor masks, maneuver index, poses, then the maneuver
+// areas (only with `areas`: else they are read from L2).  Returns the first free byte.
+template <class Layout>
+uint32_t layout_mpa(const pdmpc_handle* h, uint32_t off, bool areas, Layout& L) {
+    L.mask = off;
+    off = align16(off + (uint32_t)h->mask_bytes);
+    L.man_index = off;
+    off = align16(off + (uint32_t)h->mi_bytes);
+    L.pose = off;
+    off = align16(off + (uint32_t)(h->n_man * sizeof(DevManPose)));
+    L.area = off;
+    if (areas) off = align16(off + (uint32_t)(h->n_man * 3 * PDMPC_VMAX * 16));
+    return off;
 }
 
 // LDS layout of the graph search: MPA tables, reference, per-wave tallies, shared words, obstacle soup, phase B's chunk state (12 B per
@@ -366,15 +416,7 @@ bool layout_bulk(pdmpc_handle* h, size_t budget, int n_waves, int areas, int sou
     if (ready_cap > lk_ready || (uint32_t)n_waves > lk_waves) return false;
     // the regions of fixed size at the kernel's compile-time offsets (pdmpc_device.h: PDMPC_LK_*) ...
     // ... the automaton's tables and the soup behind them
-    uint32_t off = pdmpc_lk_fixed(lk_waves, lk_ready, lk_per, &L);
-    L.mask = off;
-    off = align16(off + (uint32_t)h->mask_bytes);
-    L.man_index = off;
-    off = align16(off + (uint32_t)h->mi_bytes);
-    L.pose = off;
-    off = align16(off + (uint32_t)(h->n_man * sizeof(DevManPose)));
-    L.area = off;
-    if (areas) off = align16(off + (uint32_t)(h->n_man * 3 * PDMPC_VMAX * 16));
+    uint32_t off = layout_mpa(h, pdmpc_lk_fixed(lk_waves, lk_ready, lk_per, &L), areas, L);
     L.soup = off;
     off = align16(off + (uint32_t)std::max(soup_cap, 1) * 16);
     L.tree16 = L.bk_hist;  // (the sampled optimizer's region: not part of this layout)
@@ -382,14 +424,24 @@ bool layout_bulk(pdmpc_handle* h, size_t budget, int n_waves, int areas, int sou
     if ((size_t)off + min_nodes + 256 > budget) return false;
     const uint32_t rest = (uint32_t)(budget - off - 256);
     nv = std::min<uint32_t>(16384u, std::max<uint32_t>(compact ? 512u : 1024u, rest / 6));
-    nv = std::min(nv, h->max_nodes) & ~15u;
-    nl = std::min((rest - nv) / (uint32_t)sizeof(NodeRec), h->max_nodes);
+    nv = std::min(nv, h->arena.max_nodes) & ~15u;
+    nl = std::min((rest - nv) / (uint32_t)sizeof(NodeRec), h->arena.max_nodes);
     L.vstate = off;
     off += align16(nv);
     L.nodes = off;
     off += nl * (uint32_t)sizeof(NodeRec);
     L.total = align16(off);
     return L.total <= budget;
+}
+
+// the layout the next launch_range goes out with
+int use_layout(pdmpc_handle* h, const LdsLayout& L, int n_waves, uint32_t nl, uint32_t nv, int areas_in_lds) {
+    h->lds = L;
+    h->n_waves = n_waves;
+    h->NL = (int)nl;
+    h->NV = (int)nv;
+    h->areas_in_lds = areas_in_lds;
+    return PDMPC_OK;
 }
 
 // helper workgroups serve the launches that leave CUs idle (launch_range)
@@ -421,13 +473,8 @@ int compute_lds_bulk(pdmpc_handle* h, int n_launch, int soup_cap) {
             if (h->tune.debug_lds)
                 fprintf(stderr, "pdmpc LDS layout (compact): launch %d waves %d near %u ready %d nv %u nl %u total %u\n", n_launch, waves, PDMPC_LK_COMPACT_BK_PER * (uint32_t)waves * PDMPC_WAVE, ready, nv, nl, L.total);
             h->bk_ready_launch = ready;
-            h->lds = L;
-            h->n_waves = waves;
-            h->NL = (int)nl;
-            h->NV = (int)nv;
-            h->areas_in_lds = 0;
             h->compact_layout = true;
-            return PDMPC_OK;
+            return use_layout(h, L, waves, nl, nv, 0);
         }
     }
     const int waves = h->tune.waves >= 0 ? std::min(h->tune.waves, cap) : (n_launch > 2 * h->n_cu ? std::min(12, cap) : cap);
@@ -440,12 +487,7 @@ int compute_lds_bulk(pdmpc_handle* h, int n_launch, int soup_cap) {
             fprintf(stderr, "pdmpc LDS layout: launch %d waves %d areas %d near %u ready %d nv %u nl %u total %u\n", n_launch, waves, areas, PDMPC_BK_PER * (uint32_t)waves * PDMPC_WAVE, ready,
                     nv, nl, L.total);
         h->bk_ready_launch = ready;
-        h->lds = L;
-        h->n_waves = waves;
-        h->NL = (int)nl;
-        h->NV = (int)nv;
-        h->areas_in_lds = areas;
-        return PDMPC_OK;
+        return use_layout(h, L, waves, nl, nv, areas);
     }
     char buf[256];
     snprintf(buf, sizeof buf, "obstacle soup (%d columns) + MPA tables do not fit into %zu B of LDS", soup_cap, kLdsMax);
@@ -457,15 +499,7 @@ int compute_lds_bulk(pdmpc_handle* h, int n_launch, int soup_cap) {
 int compute_lds_sampled(pdmpc_handle* h, int soup_cap, int cand_cap) {
     for (int areas = 1; areas >= 0; --areas) {
         LdsLayout L{};
-        uint32_t off = 0;
-        L.mask = off;
-        off = align16(off + (uint32_t)h->mask_bytes);
-        L.man_index = off;
-        off = align16(off + (uint32_t)h->mi_bytes);
-        L.pose = off;
-        off = align16(off + (uint32_t)(h->n_man * sizeof(DevManPose)));
-        L.area = off;
-        if (areas) off = align16(off + (uint32_t)(h->n_man * 3 * PDMPC_VMAX * 16));
+        uint32_t off = layout_mpa(h, 0, areas, L);
         L.ref = off;
         off += 3 * PDMPC_HP_MAX * 8;
         L.shape = off;
@@ -481,17 +515,42 @@ int compute_lds_sampled(pdmpc_handle* h, int soup_cap, int cand_cap) {
         L.tree16 = off;
         off += align16(288u * 18u * 2u);
         L.total = align16(off);
-        if (L.total > kLdsMax / 2) continue;
-        h->lds = L;
-        h->n_waves = 1;
-        h->NL = 0;
-        h->NV = 0;
-        h->areas_in_lds = areas;
-        return PDMPC_OK;
+        if (L.total <= kLdsMax / 2) return use_layout(h, L, 1, 0, 0, areas);
     }
     return fail(PDMPC_ERR_CAPACITY, "obstacle soup + MPA tables do not fit into the LDS budget of the sampled optimizer");
 }
 
+// LDS layout of the joint search (one wavefront per problem): MPA tables, every vehicle's reference, the node's areas, offsets and the
+// path, successor lists, the problem's soups, then the LDS part of the open list.  Aimed at 64 KB (two workgroups per CU and more);
+// a problem whose tables and soups do not leave room for 256 heap entries there may take up to the whole 160 KB.
+int layout_joint(pdmpc_handle* h, int soup_cap, JointLds& L, uint32_t& heap_lds, int& areas_in_lds) {
+    for (int pass = 0; pass < 4; ++pass) {
+        const bool areas = pass == 0 || pass == 2;
+        const size_t budget = pass < 2 ? 64 * 1024 : kLdsMax;
+        uint32_t off = layout_mpa(h, 0, areas, L);
+        L.ref = off;
+        off += PDMPC_JOINT_MAX * 3 * PDMPC_HP_MAX * 8;
+        L.shape = off;
+        off += PDMPC_JOINT_MAX * 2 * PDMPC_VMAX * 16;
+        L.ints = off;
+        off = align16(off + PDMPC_JOINT_INTS * 4);
+        L.succ = off;
+        off = align16(off + (uint32_t)(PDMPC_JOINT_MAX * h->n_trims * 4));
+        L.soup = off;
+        off = align16(off + (uint32_t)std::max(soup_cap, 1) * 16);
+        if (off + 256 * 12 > budget) continue;
+        const uint32_t entries = std::min<uint32_t>(8192u, (uint32_t)((budget - off) / 12) & ~63u);
+        L.heap_key = off;
+        off += entries * 8;
+        L.heap_id = off;
+        off += entries * 4;
+        L.total = align16(off);
+        heap_lds = entries;
+        areas_in_lds = areas ? 1 : 0;
+        return PDMPC_OK;
+    }
+    return fail(PDMPC_ERR_CAPACITY, "the MPA tables and a joint problem's obstacle soups do not fit into LDS");
+}
 int check_set(const pdmpc_polygon_set& s, const char* what) {
     if (s.n_polygons < 0) return fail(PDMPC_ERR_INVALID, std::string(what) + ": negative polygon count");
     if (s.n_polygons > 0 && (!s.offset || !s.x || !s.y)) return fail(PDMPC_ERR_INVALID, std::string(what) + ": null pointer");
@@ -807,50 +866,10 @@ int pack_common(pdmpc_handle* h, int n, const pdmpc_vehicle_in* in, const int32_
     return PDMPC_OK;
 }
 
-// per-vehicle arenas for `nodes` tree nodes each (contents are scratch: every search starts from an empty tree)
-const size_t kArenaBytesPerNode = sizeof(NodeRec) + 8 + 8 + 1 + 8 + 4 + 8 + 4 + 8 + 4 + 16 + 4;
-// ... and the verification's lists (NodeArena::vlist): Hp + 1 entries of 4 bytes per node
-size_t arena_bytes_per_node(const pdmpc_handle* h) { return kArenaBytesPerNode + 4 * (size_t)(h->cfg.Hp + 1); }
-int alloc_arenas(pdmpc_handle* h, uint32_t nodes) {
-    nodes = (nodes + 1u) & ~1u;
-    const size_t tot = (size_t)h->max_vehicles * nodes;
-    h->anodes.release();
-    h->akey.release();
-    h->alink.release();
-    h->avs.release();
-    h->afark.release();
-    h->afari.release();
-    h->amidk.release();
-    h->amidi.release();
-    h->apbk.release();
-    h->apbd.release();
-    h->awalk.release();
-    h->achild0.release();
-    h->avlist.release();
-    h->max_nodes = 0;
-    int bad = 0;
-    bad |= h->anodes.ensure_exact(tot) | h->akey.ensure_exact(tot) | h->alink.ensure_exact(tot) | h->avs.ensure_exact(tot) | h->afark.ensure_exact(tot) | h->afari.ensure_exact(tot);
-    bad |= h->amidk.ensure_exact(tot) | h->amidi.ensure_exact(tot) | h->apbk.ensure_exact(tot) | h->apbd.ensure_exact(tot) | h->awalk.ensure_exact(2 * tot) | h->achild0.ensure_exact(tot);
-    bad |= h->avlist.ensure_exact(tot * (size_t)(h->cfg.Hp + 1));
-    if (bad) return bad;
-    h->max_nodes = nodes;
-    return 0;
-}
-
-// safe == true: the recovery path after a predecessor time-out (plan_packed_growing): slices that are resident as a whole,
-// no helper workgroups next to an oversubscribed launch, the default spin limit.
-int launch_range(pdmpc_handle* h, int first, int count, bool safe = false) {
-    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
-    PackedStep& B = h->banks[h->bank];
-    if (B.pack_failed) return fail(PDMPC_ERR_INVALID, "the last pack into this bank failed: nothing is packed");
-    if (first < 0 || count < 0 || first + count > B.n_packed) return fail(PDMPC_ERR_INVALID, "launch range outside the packed batch");
-    if (!B.perm.empty() && (first != 0 || count != B.n_packed)) return fail(PDMPC_ERR_INVALID, "range launches need a batch packed in level order (predecessors in lower slots)");
-    if (count == 0) return PDMPC_OK;
-    const Tuning& T = h->tune;
-    const bool search = !h->sampled_launch;
-    int rc = search ? compute_lds_bulk(h, count, B.soup_cap) : compute_lds_sampled(h, B.soup_cap, B.cand_cap);
-    if (rc) return rc;
-    KernelArgs a{};
+// what the graph search, the sampled optimizer and the joint search (KernelArgs, JointArgs) all read: the automaton, the packed
+// batch, the records, the arenas' size, the tree sizes and work counters
+template <class Args>
+void set_batch_args(const pdmpc_handle* h, const PackedStep& B, int areas_in_lds, Args& a) {
     a.succ_mask = h->d_mask.p;
     a.man_index = h->d_mi.p;
     a.man_pose = h->d_pose.p;
@@ -859,31 +878,66 @@ int launch_range(pdmpc_handle* h, int first, int count, bool safe = false) {
     a.n_words = h->n_words;
     a.n_man = h->n_man;
     a.Hp = h->cfg.Hp;
-    a.checker = h->cfg.checker;
-    a.areas_in_lds = h->areas_in_lds;
+    a.areas_in_lds = areas_in_lds;
     a.dt = h->cfg.dt_seconds;
     a.veh = B.d_veh;
     a.points = B.d_pts;
-    a.pred = B.d_pred;
     a.out = h->d_out.p;
+    a.max_nodes = h->arena.max_nodes;
+    a.tree_size = h->d_tree_size.p;
+    a.work_count = h->d_work_count.p;
+}
+
+// The next event pair of the handle, its start recorded on the stream; end_timed_launch records its end behind the launch.
+int begin_timed_launch(pdmpc_handle* h, LaunchKind kind) {
+    if (h->events_used == kMaxLaunchEvents) {
+        // a caller that launches resident banks for ever (no pack, no pdmpc_reset_stats in between) must not make the handle hold an
+        // event pair per launch: the pairs' times are folded into a sum and the pairs used again
+        HIPCHK(hipStreamSynchronize(h->stream));
+        for (size_t i = 0; i < h->events_used; ++i) {
+            float t = 0.f;
+            if (hipEventElapsedTime(&t, h->events[i].first, h->events[i].second) == hipSuccess) h->folded_kernel_ms += t;
+        }
+        h->folded_launches += (int64_t)h->events_used;
+        h->events_used = 0;
+    }
+    if (h->events_used == h->events.size()) {
+        hipEvent_t e0, e1;
+        HIPCHK(hipEventCreate(&e0));
+        HIPCHK(hipEventCreate(&e1));
+        h->events.emplace_back(e0, e1);
+    }
+    HIPCHK(hipEventRecord(h->events[h->events_used++].first, h->stream));
+    h->launch_kind = kind;
+    return PDMPC_OK;
+}
+
+int end_timed_launch(pdmpc_handle* h) {
+    HIPCHK(hipEventRecord(h->events[h->events_used - 1].second, h->stream));
+    return PDMPC_OK;
+}
+
+// safe == true: the recovery path after a predecessor time-out (plan_packed_growing): slices that are resident as a whole,
+// no helper workgroups next to an oversubscribed launch, the default spin limit.
+int launch_range(pdmpc_handle* h, LaunchKind kind, int first, int count, bool safe) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    PackedStep& B = h->banks[h->bank];
+    if (B.pack_failed) return fail(PDMPC_ERR_INVALID, "the last pack into this bank failed: nothing is packed");
+    if (first < 0 || count < 0 || first + count > B.n_packed) return fail(PDMPC_ERR_INVALID, "launch range outside the packed batch");
+    if (!B.perm.empty() && (first != 0 || count != B.n_packed)) return fail(PDMPC_ERR_INVALID, "range launches need a batch packed in level order (predecessors in lower slots)");
+    if (count == 0) return PDMPC_OK;
+    const Tuning& T = h->tune;
+    const bool search = kind == kLaunchSearch;
+    int rc = search ? compute_lds_bulk(h, count, B.soup_cap) : compute_lds_sampled(h, B.soup_cap, B.cand_cap);
+    if (rc) return rc;
+    KernelArgs a{};
+    set_batch_args(h, B, h->areas_in_lds, a);
+    a.checker = h->cfg.checker;
+    a.pred = B.d_pred;
     a.done_flag = h->d_flag.p;
     a.epoch = h->epoch;
     a.first = first;
-    a.arena.nodes = h->anodes.p;
-    a.arena.key = h->akey.p;
-    a.arena.link = h->alink.p;
-    a.arena.vstate = h->avs.p;
-    a.arena.far_key = h->afark.p;
-    a.arena.far_id = h->afari.p;
-    a.arena.mid_key = h->amidk.p;
-    a.arena.mid_id = h->amidi.p;
-    a.arena.pb_key = h->apbk.p;
-    a.arena.pb_d = h->apbd.p;
-    a.arena.walk = h->awalk.p;
-    a.arena.child0 = h->achild0.p;
-    a.arena.vlist = h->avlist.p;
-    a.max_nodes = h->max_nodes;
-    a.tree_size = h->d_tree_size.p;
+    a.arena = h->arena.view();
     a.lds = h->lds;
     a.NL = h->NL;
     a.NV = h->NV;
@@ -891,7 +945,6 @@ int launch_range(pdmpc_handle* h, int first, int count, bool safe = false) {
     a.cand_cap = B.cand_cap;
     a.n_waves = h->n_waves;
     a.tie_count = h->d_tie_count.p;
-    a.work_count = h->d_work_count.p;
     a.sampled_random = h->d_random.p;
     a.sampled_n_random = h->sampled_n_random;
     a.spin_limit = safe ? (1u << 22) : T.spin_limit;
@@ -990,30 +1043,7 @@ int launch_range(pdmpc_handle* h, int first, int count, bool safe = false) {
         h->help_fin_total = (uint32_t)count;
         h->boards_dirty = false;
     }
-    if (h->events_used == kMaxLaunchEvents) {
-        // a caller that launches resident banks for ever (no pack, no pdmpc_reset_stats in between) must not make the handle hold an
-        // event pair per launch: the pairs' times are folded into a sum and the pairs used again
-        HIPCHK(hipStreamSynchronize(h->stream));
-        for (size_t i = 0; i < h->events_used; ++i) {
-            float t = 0.f;
-            if (hipEventElapsedTime(&t, h->events[i].first, h->events[i].second) == hipSuccess) h->folded_kernel_ms += t;
-        }
-        h->folded_launches += (int64_t)h->events_used;
-        h->events_used = 0;
-    }
-    if (h->events_used == h->events.size()) {
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
-        h->events.emplace_back(e0, e1);
-    }
-    auto& ev = h->events[h->events_used++];
-    HIPCHK(hipEventRecord(ev.first, h->stream));
-    h->last_launch_search = search;
-    h->last_launch_joint = false;
-    h->last_first = first;
-    h->last_count = count;
-    h->last_safe = safe;
+    if ((rc = begin_timed_launch(h, kind))) return rc;
     // Oversubscribed launches (more searches than CUs).  A resident search spins for predecessors of the same launch; slots are in
     // level order (pack_common sees to it), so as long as the hardware hands out workgroups in index order every predecessor was
     // dispatched before its successors and the launch cannot stall.  That order is not a documented guarantee: should a launch ever
@@ -1048,12 +1078,18 @@ int launch_range(pdmpc_handle* h, int first, int count, bool safe = false) {
         snprintf(buf, sizeof buf, "kernel launch failed: %s (LDS %u B)", hipGetErrorString((hipError_t)lrc), h->lds.total);
         return fail(PDMPC_ERR_HIP, buf);
     }
-    HIPCHK(hipEventRecord(ev.second, h->stream));
+    if ((rc = end_timed_launch(h))) return rc;
     h->stats.lds_bytes = h->lds.total;
     h->stats.lds_nodes = h->NL;
     return PDMPC_OK;
 }
 
+// the device-resident record path addresses slots: the caller's vehicles only if the library kept the batch's order
+int check_result_slots(const pdmpc_handle* h, int32_t first, int32_t n) {
+    if (!h->banks[h->bank].perm.empty()) return fail(PDMPC_ERR_INVALID, "the packed batch was put into level order by the library: raw slots are not the caller's vehicles (pack it in level order to use the device-resident record path)");
+    if (first < 0 || n < 0 || first + n > h->max_vehicles) return fail(PDMPC_ERR_INVALID, "slot range out of bounds");
+    return PDMPC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1092,12 +1128,12 @@ int pdmpc_create(const pdmpc_config* config, pdmpc_handle** out_handle) {
         delete h;
         return fail(PDMPC_ERR_HIP, "hipStreamCreate failed");
     }
-    int bad = alloc_arenas(h, want_nodes);
+    int bad = h->arena.alloc(h->max_vehicles, want_nodes, h->cfg.Hp);
     bad |= h->d_out.ensure((size_t)h->max_vehicles) | h->d_flag.ensure((size_t)h->max_vehicles) | h->d_tree_size.ensure((size_t)h->max_vehicles) | h->d_tie_count.ensure(4) | h->d_work_count.ensure(16);
     bad |= h->d_help_board.ensure((size_t)h->max_vehicles * PDMPC_HB_WORDS) | h->d_help_verdict.ensure((size_t)h->max_vehicles * PDMPC_HELP_CAP) | h->d_help_finished.ensure(16);
     bad |= h->d_bk_post.ensure((size_t)h->max_vehicles * (size_t)h->tune.ready * 6);
     if (bad) {
-        pdmpc_destroy(h);
+        delete h;
         return fail(PDMPC_ERR_HIP, "hipMalloc failed for the per-vehicle arenas (lower max_nodes / max_vehicles)");
     }
     (void)hipMemsetAsync(h->d_flag.p, 0, h->d_flag.cap * sizeof(uint32_t), h->stream);
@@ -1113,48 +1149,6 @@ int pdmpc_create(const pdmpc_config* config, pdmpc_handle** out_handle) {
 int pdmpc_destroy(pdmpc_handle* h) {
     if (!h) return PDMPC_OK;
     DeviceGuard device_guard__(h->cfg.device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (auto& ev : h->events) {
-        (void)hipEventDestroy(ev.first);
-        (void)hipEventDestroy(ev.second);
-    }
-    h->d_mask.release();
-    h->d_mi.release();
-    h->d_pose.release();
-    h->d_area.release();
-    h->anodes.release();
-    h->akey.release();
-    h->alink.release();
-    h->avs.release();
-    h->afark.release();
-    h->afari.release();
-    h->amidk.release();
-    h->amidi.release();
-    h->apbk.release();
-    h->apbd.release();
-    h->awalk.release();
-    h->achild0.release();
-    h->avlist.release();
-    h->d_out.release();
-    h->h_out.release();
-    h->h_lean.release();
-    h->d_lean.release();
-    h->d_flag.release();
-    h->d_tree_size.release();
-    h->d_tie_count.release();
-    h->d_work_count.release();
-    h->d_help_board.release();
-    h->d_help_verdict.release();
-    h->d_bk_post.release();
-    h->d_help_finished.release();
-    h->d_random.release();
-    h->d_prio_count.release();
-    h->d_prio_mask.release();
-    h->d_prio_off.release();
-    h->d_prio_order.release();
-    for (auto& b : h->banks) b.release();
-    if (h->progress) (void)hipHostFree(h->progress);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return PDMPC_OK;
 }
@@ -1213,11 +1207,7 @@ int pdmpc_upload_mpa(pdmpc_handle* h, const pdmpc_mpa* mpa) {
     return PDMPC_OK;
 }
 
-int pdmpc_pack_batch(pdmpc_handle* h, int32_t n, const pdmpc_vehicle_in* in) {
-    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
-    ON_DEVICE(h->cfg.device);
-    return pack_common(h, n, in, nullptr, nullptr, nullptr);
-}
+int pdmpc_pack_batch(pdmpc_handle* h, int32_t n, const pdmpc_vehicle_in* in) { return pdmpc_pack_step(h, n, in, nullptr, nullptr, nullptr); }
 
 int pdmpc_pack_step(pdmpc_handle* h, int32_t n, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index,
                     const pdmpc_polygon_set* fallback_shapes) {
@@ -1237,7 +1227,7 @@ int pdmpc_launch_packed(pdmpc_handle* h) {
     if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
     ON_DEVICE(h->cfg.device);
     h->epoch += 1;  // a new step: results of earlier launches no longer satisfy predecessor waits
-    return launch_range(h, 0, h->banks[h->bank].n_packed, h->safe_launches);
+    return launch_range(h, kLaunchSearch, 0, h->banks[h->bank].n_packed, h->safe_launches);
 }
 
 int pdmpc_set_device_share(pdmpc_handle* h, int32_t n_handles) {
@@ -1281,7 +1271,7 @@ int pdmpc_reset_stats(pdmpc_handle* h) {
 int pdmpc_launch_range(pdmpc_handle* h, int32_t first, int32_t count) {
     if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
     ON_DEVICE(h->cfg.device);
-    return launch_range(h, first, count, h->safe_launches);
+    return launch_range(h, kLaunchSearch, first, count, h->safe_launches);
 }
 
 int pdmpc_synchronize(pdmpc_handle* h) {
@@ -1337,6 +1327,22 @@ int pdmpc_fetch_results(pdmpc_handle* h, int32_t n, pdmpc_vehicle_out* out) {
     return PDMPC_OK;
 }
 
+int pdmpc_fetch_records_at(pdmpc_handle* h, int32_t count, const int32_t* vehicles, pdmpc_vehicle_out* out) {
+    if (!h || count < 0 || (count > 0 && (!vehicles || !out))) return fail(PDMPC_ERR_INVALID, "null argument");
+    ON_DEVICE(h->cfg.device);
+    PackedStep& B = h->banks[h->bank];
+    if (h->h_out.ensure((size_t)std::max(count, 1))) return fail(PDMPC_ERR_HIP, "hipHostMalloc failed");
+    for (int i = 0; i < count; ++i) {
+        const int v = vehicles[i];
+        if (v < 0 || v >= B.n_packed) return fail(PDMPC_ERR_INVALID, "vehicle index outside the packed batch");
+        const int sl = B.perm.empty() ? v : B.inv[(size_t)v];
+        HIPCHK(hipMemcpyAsync(h->h_out.p + i, h->d_out.p + sl, sizeof(pdmpc_vehicle_out), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(sync_stream(h));
+    if (count > 0) std::memcpy(out, h->h_out.p, (size_t)count * sizeof(pdmpc_vehicle_out));
+    return PDMPC_OK;
+}
+
 namespace {
 // What a caller that keeps only a few of a batch's plans needs of ALL of them (the explorative step: the choice among the
 // prioritizations rests on the cost-to-come of every vehicle's final node, PrioritizedExplorativeController.m:94-112): status and
@@ -1360,40 +1366,58 @@ int fetch_lean(pdmpc_handle* h, int32_t n, int32_t* status, double* cost) {
     }
     return PDMPC_OK;
 }
-}  // namespace
 
-int pdmpc_fetch_records_at(pdmpc_handle* h, int32_t count, const int32_t* vehicles, pdmpc_vehicle_out* out) {
-    if (!h || count < 0 || (count > 0 && (!vehicles || !out))) return fail(PDMPC_ERR_INVALID, "null argument");
-    ON_DEVICE(h->cfg.device);
-    PackedStep& B = h->banks[h->bank];
-    if (h->h_out.ensure((size_t)std::max(count, 1))) return fail(PDMPC_ERR_HIP, "hipHostMalloc failed");
-    for (int i = 0; i < count; ++i) {
-        const int v = vehicles[i];
-        if (v < 0 || v >= B.n_packed) return fail(PDMPC_ERR_INVALID, "vehicle index outside the packed batch");
-        const int sl = B.perm.empty() ? v : B.inv[(size_t)v];
-        HIPCHK(hipMemcpyAsync(h->h_out.p + i, h->d_out.p + sl, sizeof(pdmpc_vehicle_out), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(sync_stream(h));
-    if (count > 0) std::memcpy(out, h->h_out.p, (size_t)count * sizeof(pdmpc_vehicle_out));
+// Where a plan's read-back lands: every record, or (lean) the (status, cost) pair of every vehicle (fetch_lean).  Caller's order.
+struct Sink {
+    bool lean;
+    pdmpc_vehicle_out* out;
+    int32_t* status;
+    double* cost;
+    static Sink records(pdmpc_vehicle_out* out) { return {false, out, nullptr, nullptr}; }
+    static Sink lean_pair(int32_t* status, double* cost) { return {true, nullptr, status, cost}; }
+    int fetch(pdmpc_handle* h, int32_t n) const { return lean ? fetch_lean(h, n, status, cost) : pdmpc_fetch_results(h, n, out); }
+    int32_t status_at(int i) const { return lean ? status[i] : out[i].status; }
+};
+
+// Arenas of `nodes` nodes per vehicle, or (grown == false) the ones there were if HBM has no room for them.
+int realloc_arenas(pdmpc_handle* h, uint32_t nodes, bool& grown) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const uint32_t before = h->arena.max_nodes;
+    grown = h->arena.alloc(h->max_vehicles, nodes, h->cfg.Hp) == 0;
+    if (!grown && h->arena.alloc(h->max_vehicles, before, h->cfg.Hp)) return fail(PDMPC_ERR_HIP, "hipMalloc failed while restoring the arenas");
     return PDMPC_OK;
 }
 
-namespace {
 // The reference's tree grows without bound (Tree.m:54-70); the arenas here are finite.  A call whose search outgrows them
 // is planned again from scratch with arenas twice as large (searches are deterministic, so the vehicles that did fit
 // produce the same records again) until it fits, the limit set with pdmpc_set_arena_limit is reached, or HBM runs out.
-int plan_packed_growing(pdmpc_handle* h, int32_t n, pdmpc_vehicle_out* out, int32_t* lean_status = nullptr, double* lean_cost = nullptr) {
+// grown == false: the arenas stay as they are and the records' statuses report the overflow.
+int grow_after_overflow(pdmpc_handle* h, bool& grown) {
+    grown = false;
+    const uint64_t next = (uint64_t)h->arena.max_nodes * 2u;
+    if ((h->max_nodes_limit && next > h->max_nodes_limit) || next > (1ull << 30)) return PDMPC_OK;
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    const size_t per_node = h->arena.bytes_per_node(h->cfg.Hp);
+    const size_t have = (size_t)h->max_vehicles * h->arena.max_nodes * per_node;
+    if ((size_t)h->max_vehicles * next * per_node > free_b + have) return PDMPC_OK;  // no room to grow
+    const int rc = realloc_arenas(h, (uint32_t)next, grown);
+    if (grown) h->arena_regrows += 1;
+    return rc;
+}
+
+int plan_packed_growing(pdmpc_handle* h, int32_t n, const Sink& sink) {
     bool safe = h->safe_launches;
     for (;;) {
         const bool dbg = h->tune.debug_host == 1;
-        if (dbg) fprintf(stderr, "pdmpc: launching %d vehicles, arena %u nodes%s\n", n, h->max_nodes, safe ? " (resident slices)" : "");
+        if (dbg) fprintf(stderr, "pdmpc: launching %d vehicles, arena %u nodes%s\n", n, h->arena.max_nodes, safe ? " (resident slices)" : "");
         ON_DEVICE(h->cfg.device);
         h->epoch += 1;  // a new step: results of earlier launches no longer satisfy predecessor waits
         const auto t0 = std::chrono::steady_clock::now();
-        int rc = launch_range(h, 0, h->banks[h->bank].n_packed, safe);
+        int rc = launch_range(h, kLaunchSearch, 0, h->banks[h->bank].n_packed, safe);
         if (rc) return rc;
         const auto t1 = std::chrono::steady_clock::now();
-        rc = out ? pdmpc_fetch_results(h, n, out) : fetch_lean(h, n, lean_status, lean_cost);
+        rc = sink.fetch(h, n);
         if (rc) return rc;
         h->last_us[1] += std::chrono::duration<double, std::micro>(t1 - t0).count();
         h->last_us[2] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t1).count();
@@ -1403,10 +1427,10 @@ int plan_packed_growing(pdmpc_handle* h, int32_t n, pdmpc_vehicle_out* out, int3
             float ms = 0.f;
             if (h->events_used > 0 && hipEventElapsedTime(&ms, h->events[h->events_used - 1].first, h->events[h->events_used - 1].second) == hipSuccess) h->dbg_us[3] += 1e3 * ms;
         }
-        if (dbg) fprintf(stderr, "pdmpc: fetched, status[0] %d\n", n > 0 ? (out ? out[0].status : lean_status[0]) : 0);
+        if (dbg) fprintf(stderr, "pdmpc: fetched, status[0] %d\n", n > 0 ? sink.status_at(0) : 0);
         bool overflow = false, timed_out = false;
         for (int i = 0; i < n; ++i) {
-            const int st = out ? out[i].status : lean_status[i];
+            const int st = sink.status_at(i);
             overflow = overflow || st == PDMPC_ARENA_OVERFLOW;
             timed_out = timed_out || st == PDMPC_ERR_HIP;
         }
@@ -1421,54 +1445,43 @@ int plan_packed_growing(pdmpc_handle* h, int32_t n, pdmpc_vehicle_out* out, int3
             continue;
         }
         if (!overflow) return PDMPC_OK;
-        const uint64_t next = (uint64_t)h->max_nodes * 2u;
-        if ((h->max_nodes_limit && next > h->max_nodes_limit) || next > (1ull << 30)) return PDMPC_OK;  // statuses tell
-        size_t free_b = 0, total_b = 0;
-        (void)hipMemGetInfo(&free_b, &total_b);
-        const size_t per_node = arena_bytes_per_node(h);
-        const size_t have = (size_t)h->max_vehicles * h->max_nodes * per_node;
-        if ((size_t)h->max_vehicles * next * per_node > free_b + have) return PDMPC_OK;  // no room to grow
-        const uint32_t before = h->max_nodes;
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (alloc_arenas(h, (uint32_t)next)) {
-            if (alloc_arenas(h, before)) return fail(PDMPC_ERR_HIP, "hipMalloc failed while restoring the arenas");
-            return PDMPC_OK;
-        }
-        h->arena_regrows += 1;
+        bool grown = false;
+        if ((rc = grow_after_overflow(h, grown))) return rc;
+        if (!grown) return PDMPC_OK;  // statuses tell
     }
+}
+
+// The prologue of pdmpc_plan_batch / _step / _step_lean: the pack, timed for pdmpc_last_call_timing.
+int timed_pack(pdmpc_handle* h, int32_t n, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index, const pdmpc_polygon_set* fallback_shapes) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = pdmpc_pack_step(h, n, in, pred_offset, pred_index, fallback_shapes);
+    if (rc) return rc;
+    h->last_us[0] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    h->last_us[1] = h->last_us[2] = 0;
+    return PDMPC_OK;
 }
 }  // namespace
 
 int pdmpc_plan_batch(pdmpc_handle* h, int32_t n, const pdmpc_vehicle_in* in, pdmpc_vehicle_out* out) {
-    const bool dbg = h && h->tune.debug_host == 2;
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = pdmpc_pack_batch(h, n, in);
+    if (n > 0 && !out) return fail(PDMPC_ERR_INVALID, "null argument");
+    const int rc = timed_pack(h, n, in, nullptr, nullptr, nullptr);
     if (rc) return rc;
-    if (dbg) h->dbg_us[0] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    h->last_us[0] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    h->last_us[1] = h->last_us[2] = 0;
-    return plan_packed_growing(h, n, out);
+    if (h->tune.debug_host == 2) h->dbg_us[0] += h->last_us[0];
+    return plan_packed_growing(h, n, Sink::records(out));
 }
 
 int pdmpc_plan_step(pdmpc_handle* h, int32_t n, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index,
                     const pdmpc_polygon_set* fallback_shapes, pdmpc_vehicle_out* out) {
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = pdmpc_pack_step(h, n, in, pred_offset, pred_index, fallback_shapes);
-    if (rc) return rc;
-    h->last_us[0] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    h->last_us[1] = h->last_us[2] = 0;
-    return plan_packed_growing(h, n, out);
+    if (n > 0 && !out) return fail(PDMPC_ERR_INVALID, "null argument");
+    const int rc = timed_pack(h, n, in, pred_offset, pred_index, fallback_shapes);
+    return rc ? rc : plan_packed_growing(h, n, Sink::records(out));
 }
 
 int pdmpc_plan_step_lean(pdmpc_handle* h, int32_t n, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index, const pdmpc_polygon_set* fallback_shapes,
                          int32_t* status, double* final_cost) {
     if (!h || n < 0 || (n > 0 && (!status || !final_cost))) return fail(PDMPC_ERR_INVALID, "null argument");
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = pdmpc_pack_step(h, n, in, pred_offset, pred_index, fallback_shapes);
-    if (rc) return rc;
-    h->last_us[0] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    h->last_us[1] = h->last_us[2] = 0;
-    return plan_packed_growing(h, n, nullptr, status, final_cost);
+    const int rc = timed_pack(h, n, in, pred_offset, pred_index, fallback_shapes);
+    return rc ? rc : plan_packed_growing(h, n, Sink::lean_pair(status, final_cost));
 }
 
 int pdmpc_last_call_timing(pdmpc_handle* h, double* us3) {
@@ -1552,7 +1565,7 @@ int pdmpc_get_config(pdmpc_handle* h, pdmpc_config* config, int32_t* mpa_uploade
     if (config) {
         *config = h->cfg;
         config->max_vehicles = h->max_vehicles;
-        config->max_nodes = (int32_t)h->max_nodes;
+        config->max_nodes = (int32_t)h->arena.max_nodes;
     }
     if (mpa_uploaded) *mpa_uploaded = h->has_mpa ? 1 : 0;
     return PDMPC_OK;
@@ -1567,19 +1580,16 @@ int pdmpc_set_arena_limit(pdmpc_handle* h, int32_t max_nodes_limit) {
 int pdmpc_grow_arena(pdmpc_handle* h, int32_t max_nodes) {
     if (!h || max_nodes <= 0) return fail(PDMPC_ERR_INVALID, "bad argument");
     ON_DEVICE(h->cfg.device);
-    if ((uint32_t)max_nodes <= h->max_nodes) return PDMPC_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    const uint32_t before = h->max_nodes;
-    if (alloc_arenas(h, (uint32_t)max_nodes)) {
-        if (alloc_arenas(h, before)) return fail(PDMPC_ERR_HIP, "hipMalloc failed while restoring the arenas");
-        return fail(PDMPC_ERR_CAPACITY, "not enough HBM for arenas of that size");
-    }
-    return PDMPC_OK;
+    if ((uint32_t)max_nodes <= h->arena.max_nodes) return PDMPC_OK;
+    bool grown = false;
+    const int rc = realloc_arenas(h, (uint32_t)max_nodes, grown);
+    if (rc || grown) return rc;
+    return fail(PDMPC_ERR_CAPACITY, "not enough HBM for arenas of that size");
 }
 
 int pdmpc_arena_nodes(pdmpc_handle* h, int32_t* max_nodes, int64_t* regrows) {
     if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
-    if (max_nodes) *max_nodes = (int32_t)h->max_nodes;
+    if (max_nodes) *max_nodes = (int32_t)h->arena.max_nodes;
     if (regrows) *regrows = h->arena_regrows;
     return PDMPC_OK;
 }
@@ -1605,54 +1615,11 @@ int pdmpc_plan_batch_sampled(pdmpc_handle* h, int32_t n, const pdmpc_vehicle_in*
     HIPCHK(hipMemcpyAsync(h->d_random.p, rnd.data(), rnd.size() * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));  // (rnd goes out of scope)
     h->sampled_n_random = per;
-    h->sampled_launch = true;
-    rc = pdmpc_launch_packed(h);
-    h->sampled_launch = false;
+    h->epoch += 1;  // a new step: results of earlier launches no longer satisfy predecessor waits
+    rc = launch_range(h, kLaunchSampled, 0, h->banks[h->bank].n_packed, h->safe_launches);
     if (rc) return rc;
     return pdmpc_fetch_results(h, n, out);
 }
-
-namespace {
-// LDS layout of the joint search (one wavefront per problem): MPA tables, every vehicle's reference, the node's areas, offsets and the
-// path, successor lists, the problem's soups, then the LDS part of the open list.  Aimed at 64 KB (two workgroups per CU and more);
-// a problem whose tables and soups do not leave room for 256 heap entries there may take up to the whole 160 KB.
-int layout_joint(pdmpc_handle* h, int soup_cap, JointLds& L, uint32_t& heap_lds, int& areas_in_lds) {
-    for (int pass = 0; pass < 4; ++pass) {
-        const bool areas = pass == 0 || pass == 2;
-        const size_t budget = pass < 2 ? 64 * 1024 : kLdsMax;
-        uint32_t off = 0;
-        L.mask = off;
-        off = align16(off + (uint32_t)h->mask_bytes);
-        L.man_index = off;
-        off = align16(off + (uint32_t)h->mi_bytes);
-        L.pose = off;
-        off = align16(off + (uint32_t)(h->n_man * sizeof(DevManPose)));
-        L.area = off;
-        if (areas) off = align16(off + (uint32_t)(h->n_man * 3 * PDMPC_VMAX * 16));
-        L.ref = off;
-        off += PDMPC_JOINT_MAX * 3 * PDMPC_HP_MAX * 8;
-        L.shape = off;
-        off += PDMPC_JOINT_MAX * 2 * PDMPC_VMAX * 16;
-        L.ints = off;
-        off = align16(off + PDMPC_JOINT_INTS * 4);
-        L.succ = off;
-        off = align16(off + (uint32_t)(PDMPC_JOINT_MAX * h->n_trims * 4));
-        L.soup = off;
-        off = align16(off + (uint32_t)std::max(soup_cap, 1) * 16);
-        if (off + 256 * 12 > budget) continue;
-        const uint32_t entries = std::min<uint32_t>(8192u, (uint32_t)((budget - off) / 12) & ~63u);
-        L.heap_key = off;
-        off += entries * 8;
-        L.heap_id = off;
-        off += entries * 4;
-        L.total = align16(off);
-        heap_lds = entries;
-        areas_in_lds = areas ? 1 : 0;
-        return PDMPC_OK;
-    }
-    return fail(PDMPC_ERR_CAPACITY, "the MPA tables and a joint problem's obstacle soups do not fit into LDS");
-}
-}  // namespace
 
 int pdmpc_plan_joint(pdmpc_handle* h, int32_t n_problems, const int32_t* problem_offset, const pdmpc_vehicle_in* in, pdmpc_vehicle_out* out) {
     if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
@@ -1688,63 +1655,29 @@ int pdmpc_plan_joint(pdmpc_handle* h, int32_t n_problems, const int32_t* problem
     HIPCHK(hipMemcpyAsync(h->d_joint_off.p, problem_offset, ((size_t)n_problems + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     for (;;) {
         JointArgs a{};
-        a.succ_mask = h->d_mask.p;
-        a.man_index = h->d_mi.p;
-        a.man_pose = h->d_pose.p;
-        a.man_area = h->d_area.p;
-        a.n_trims = h->n_trims;
-        a.n_words = h->n_words;
-        a.n_man = h->n_man;
-        a.Hp = Hp;
-        a.areas_in_lds = areas_in_lds;
-        a.dt = h->cfg.dt_seconds;
-        a.veh = B.d_veh;
-        a.points = B.d_pts;
+        set_batch_args(h, B, areas_in_lds, a);
         a.problem_off = h->d_joint_off.p;
-        a.out = h->d_out.p;
-        a.nodes = h->anodes.p;
-        a.far_key = h->afark.p;
-        a.far_id = h->afari.p;
-        a.max_nodes = h->max_nodes;
+        a.nodes = h->arena.nodes.p;
+        a.far_key = h->arena.far_key.p;
+        a.far_id = h->arena.far_id.p;
         a.heap_lds = heap_lds;
-        a.tree_size = h->d_tree_size.p;
-        a.work_count = h->d_work_count.p;
         a.lds = L;
-        if (h->events_used == h->events.size()) {
-            hipEvent_t e0, e1;
-            HIPCHK(hipEventCreate(&e0));
-            HIPCHK(hipEventCreate(&e1));
-            h->events.emplace_back(e0, e1);
-        }
-        auto& ev = h->events[h->events_used++];
-        HIPCHK(hipEventRecord(ev.first, h->stream));
+        if ((rc = begin_timed_launch(h, kLaunchJoint))) return rc;
         const int lrc = pdmpc_launch_joint(&a, n_problems, (void*)h->stream);
         if (lrc != 0) {
             char buf[256];
             snprintf(buf, sizeof buf, "joint kernel launch failed: %s (LDS %u B)", hipGetErrorString((hipError_t)lrc), L.total);
             return fail(PDMPC_ERR_HIP, buf);
         }
-        HIPCHK(hipEventRecord(ev.second, h->stream));
-        h->last_launch_search = false;
-        h->last_launch_joint = true;
+        if ((rc = end_timed_launch(h))) return rc;
         if ((rc = pdmpc_fetch_results(h, n, out))) return rc;
         bool overflow = false;
         for (int i = 0; i < n; ++i) overflow = overflow || out[i].status == PDMPC_ARENA_OVERFLOW;
         if (!overflow) break;
         // the arena is too small for some problem: plan the call again with arenas twice as large (pdmpc_plan_batch's rule)
-        const uint64_t next = (uint64_t)h->max_nodes * 2u;
-        if ((h->max_nodes_limit && next > h->max_nodes_limit) || next > (1ull << 30)) break;
-        size_t free_b = 0, total_b = 0;
-        (void)hipMemGetInfo(&free_b, &total_b);
-        const size_t per_node = arena_bytes_per_node(h);
-        if ((size_t)h->max_vehicles * next * per_node > free_b + (size_t)h->max_vehicles * h->max_nodes * per_node) break;
-        const uint32_t before = h->max_nodes;
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (alloc_arenas(h, (uint32_t)next)) {
-            if (alloc_arenas(h, before)) return fail(PDMPC_ERR_HIP, "hipMalloc failed while restoring the arenas");
-            break;
-        }
-        h->arena_regrows += 1;
+        bool grown = false;
+        if ((rc = grow_after_overflow(h, grown))) return rc;
+        if (!grown) break;
     }
     // counters per problem (every vehicle's record carries its problem's n_popped / n_expanded); the per-plan byte formula and
     // obstacle-column count that pdmpc_fetch_results evaluates are the single-vehicle search's and do not
@@ -1822,7 +1755,7 @@ int pdmpc_unique_priorities(pdmpc_handle* h, int32_t n, const uint8_t* adjacency
 
 int pdmpc_result_device_buffer(pdmpc_handle* h, void** dev_ptr, size_t* nbytes) {
     if (!h || !dev_ptr || !nbytes) return fail(PDMPC_ERR_INVALID, "null argument");
-    if (!h->banks[h->bank].perm.empty()) return fail(PDMPC_ERR_INVALID, "the packed batch was put into level order by the library: raw slots are not the caller's vehicles (pack it in level order to use the device-resident record path)");
+    if (int rc = check_result_slots(h, 0, 0)) return rc;
     *dev_ptr = h->d_out.p;
     *nbytes = (size_t)h->max_vehicles * sizeof(pdmpc_vehicle_out);
     return PDMPC_OK;
@@ -1830,8 +1763,7 @@ int pdmpc_result_device_buffer(pdmpc_handle* h, void** dev_ptr, size_t* nbytes) 
 
 int pdmpc_import_results(pdmpc_handle* h, int32_t first, int32_t n, const void* dev_records) {
     if (!h || (n > 0 && !dev_records)) return fail(PDMPC_ERR_INVALID, "null argument");
-    if (!h->banks[h->bank].perm.empty()) return fail(PDMPC_ERR_INVALID, "the packed batch was put into level order by the library: raw slots are not the caller's vehicles (pack it in level order to use the device-resident record path)");
-    if (first < 0 || n < 0 || first + n > h->max_vehicles) return fail(PDMPC_ERR_INVALID, "slot range out of bounds");
+    if (int rc = check_result_slots(h, first, n)) return rc;
     ON_DEVICE(h->cfg.device);
     if (n == 0) return PDMPC_OK;
     const void* dst = (const void*)(h->d_out.p + first);
@@ -1842,19 +1774,16 @@ int pdmpc_import_results(pdmpc_handle* h, int32_t first, int32_t n, const void* 
 }
 
 int pdmpc_export_results(pdmpc_handle* h, int32_t first, int32_t n, void* dev_records) {
-    if (!h || (n > 0 && !dev_records)) return fail(PDMPC_ERR_INVALID, "null argument");
-    if (!h->banks[h->bank].perm.empty()) return fail(PDMPC_ERR_INVALID, "the packed batch was put into level order by the library: raw slots are not the caller's vehicles (pack it in level order to use the device-resident record path)");
-    if (first < 0 || n < 0 || first + n > h->max_vehicles) return fail(PDMPC_ERR_INVALID, "slot range out of bounds");
+    const int rc = pdmpc_export_results_async(h, first, n, dev_records);
+    if (rc) return rc;
     ON_DEVICE(h->cfg.device);
-    if (n > 0) HIPCHK(hipMemcpyAsync(dev_records, h->d_out.p + first, (size_t)n * sizeof(pdmpc_vehicle_out), hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return PDMPC_OK;
 }
 
 int pdmpc_export_results_async(pdmpc_handle* h, int32_t first, int32_t n, void* dev_records) {
     if (!h || (n > 0 && !dev_records)) return fail(PDMPC_ERR_INVALID, "null argument");
-    if (!h->banks[h->bank].perm.empty()) return fail(PDMPC_ERR_INVALID, "the packed batch was put into level order by the library: raw slots are not the caller's vehicles (pack it in level order to use the device-resident record path)");
-    if (first < 0 || n < 0 || first + n > h->max_vehicles) return fail(PDMPC_ERR_INVALID, "slot range out of bounds");
+    if (int rc = check_result_slots(h, first, n)) return rc;
     ON_DEVICE(h->cfg.device);
     if (n > 0) HIPCHK(hipMemcpyAsync(dev_records, h->d_out.p + first, (size_t)n * sizeof(pdmpc_vehicle_out), hipMemcpyDeviceToDevice, h->stream));
     return PDMPC_OK;
@@ -1894,7 +1823,7 @@ int pdmpc_get_last_stats(pdmpc_handle* h, pdmpc_stats* stats) {
     HIPCHK(hipMemcpy(work, h->d_work_count.p, sizeof work, hipMemcpyDeviceToHost));
     h->stats.edge_checks = (int64_t)work[0];
     h->stats.segment_pair_tests = (int64_t)work[1];
-    h->stats.kernel = h->last_launch_joint ? 4 : (h->last_launch_search ? 2 : 3);
+    h->stats.kernel = h->launch_kind;
     h->stats.nodes_processed = (int64_t)work[2];
     h->stats.rounds = (int64_t)work[3];
     h->stats.shared_rounds = (int64_t)work[4];
@@ -1910,39 +1839,27 @@ int pdmpc_debug_heap_script(pdmpc_handle* h, int32_t n, const int32_t* op, const
     if (!h || n < 0 || (n > 0 && (!op || !id || !key)) || !popped || !n_popped) return fail(PDMPC_ERR_INVALID, "null argument");
     if (lds_entries < 64 || lds_entries > 8192 || (lds_entries & 1)) return fail(PDMPC_ERR_INVALID, "lds_entries must be even and in 64..8192");
     ON_DEVICE(h->cfg.device);
-    int32_t *d_op = nullptr, *d_id = nullptr, *d_out = nullptr;
-    double *d_key = nullptr, *d_gkey = nullptr;
-    uint32_t* d_gid = nullptr;
-    unsigned long long* d_stats = nullptr;
     const size_t m = (size_t)std::max(n, 1);
-    HIPCHK(hipMalloc((void**)&d_op, m * 4));
-    HIPCHK(hipMalloc((void**)&d_id, m * 4));
-    HIPCHK(hipMalloc((void**)&d_out, m * 4));
-    HIPCHK(hipMalloc((void**)&d_key, m * 8));
-    HIPCHK(hipMalloc((void**)&d_gkey, (m + 2) * 8));
-    HIPCHK(hipMalloc((void**)&d_gid, (m + 2) * 4));
-    HIPCHK(hipMalloc((void**)&d_stats, 4 * 8));
-    HIPCHK(hipMemcpy(d_op, op, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_id, id, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_key, key, (size_t)n * 8, hipMemcpyHostToDevice));
-    int lrc = pdmpc_launch_heap_script(d_op, d_id, d_key, n, d_out, d_stats, d_gkey, d_gid, lds_entries, (void*)h->stream);
+    DevBuf<int32_t> d_op, d_id, d_out;
+    DevBuf<double> d_key, d_gkey;
+    DevBuf<uint32_t> d_gid;
+    DevBuf<unsigned long long> d_stats;
+    if (d_op.ensure_exact(m) | d_id.ensure_exact(m) | d_out.ensure_exact(m) | d_key.ensure_exact(m) | d_gkey.ensure_exact(m + 2) | d_gid.ensure_exact(m + 2) | d_stats.ensure_exact(4))
+        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the heap script");
+    HIPCHK(hipMemcpy(d_op.p, op, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_id.p, id, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_key.p, key, (size_t)n * 8, hipMemcpyHostToDevice));
+    int lrc = pdmpc_launch_heap_script(d_op.p, d_id.p, d_key.p, n, d_out.p, d_stats.p, d_gkey.p, d_gid.p, lds_entries, (void*)h->stream);
     if (lrc != 0) return fail(PDMPC_ERR_HIP, "heap script launch failed");
     HIPCHK(hipStreamSynchronize(h->stream));
     unsigned long long st[4];
-    HIPCHK(hipMemcpy(st, d_stats, sizeof st, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(st, d_stats.p, sizeof st, hipMemcpyDeviceToHost));
     int cnt = 0;
     for (int i = 0; i < n; ++i) cnt += op[i] == 1;
     *n_popped = cnt;
-    if (cnt > 0) HIPCHK(hipMemcpy(popped, d_out, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+    if (cnt > 0) HIPCHK(hipMemcpy(popped, d_out.p, (size_t)cnt * 4, hipMemcpyDeviceToHost));
     if (cycles_per_pop) *cycles_per_pop = st[1] ? (double)st[0] / (double)st[1] : 0.0;
     if (cycles_per_push) *cycles_per_push = st[3] ? (double)st[2] / (double)st[3] : 0.0;
-    (void)hipFree(d_op);
-    (void)hipFree(d_id);
-    (void)hipFree(d_out);
-    (void)hipFree(d_key);
-    (void)hipFree(d_gkey);
-    (void)hipFree(d_gid);
-    (void)hipFree(d_stats);
     return PDMPC_OK;
 }
 
@@ -1956,6 +1873,42 @@ namespace {
 // and independently of the kernel's phase B (it sorts the popped nodes instead of counting them), for the debug read-backs
 // the parity tests use.  Order (bulk_search.hpp): X is popped before Y iff X is an ancestor of Y or the largest key on
 // the path (LCA, X] is smaller than the largest key on (LCA, Y].
+// the slot a debug read-back's vehicle was planned in (pack_common may have put the batch into level order)
+int debug_slot(const pdmpc_handle* h, int vehicle) {
+    const PackedStep& B = h->banks[h->bank];
+    return !B.inv.empty() && vehicle < B.n_packed ? B.inv[(size_t)vehicle] : vehicle;
+}
+
+// the column arrays of pdmpc_debug_tree / pdmpc_debug_raw_tree (a null column is not written)
+struct TreeColumns {
+    double *x, *y, *yaw, *g, *hh;
+    int32_t *trim, *k, *parent;
+    void put(size_t i, const NodeRec& r, int32_t parent_id) const {
+        if (x) x[i] = r.x;
+        if (y) y[i] = r.y;
+        if (yaw) yaw[i] = r.yaw;
+        if (g) g[i] = r.g;
+        if (hh) hh[i] = r.h;
+        if (parent) parent[i] = parent_id;
+        if (trim) trim[i] = NODE_TRIM(r.packed);
+        if (k) k[i] = NODE_K(r.packed);
+    }
+};
+
+// the first min(sz, capacity) records of a slot's arena as they are (and their keys / validity bytes where asked for)
+int copy_raw_tree(pdmpc_handle* h, int slot, int32_t sz, int32_t capacity, const TreeColumns& cols, double* key, uint8_t* validity, int32_t* n) {
+    *n = sz;
+    const size_t m = (size_t)std::max(std::min(sz, capacity), 0);
+    if (m == 0) return PDMPC_OK;
+    const size_t off = (size_t)slot * h->arena.max_nodes;
+    std::vector<NodeRec> rec(m);
+    HIPCHK(hipMemcpy(rec.data(), h->arena.nodes.p + off, m * sizeof(NodeRec), hipMemcpyDeviceToHost));
+    if (key) HIPCHK(hipMemcpy(key, h->arena.key.p + off, m * 8, hipMemcpyDeviceToHost));
+    if (validity) HIPCHK(hipMemcpy(validity, h->arena.vstate.p + off, m, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < m; ++i) cols.put(i, rec[i], (int32_t)rec[i].parent);
+    return PDMPC_OK;
+}
+
 struct RefTree {
     std::vector<NodeRec> rec;        // raw records
     std::vector<uint32_t> pops;      // raw indices in the reference's pop order
@@ -1963,14 +1916,14 @@ struct RefTree {
     std::vector<uint32_t> ref_id;    // raw index -> reference id (0: not in the reference's tree)
 };
 int reconstruct_reference_tree(pdmpc_handle* h, int vehicle, uint32_t raw_n, RefTree& T, bool replayed = false) {
-    const size_t off = (size_t)vehicle * h->max_nodes;
+    const size_t off = (size_t)vehicle * h->arena.max_nodes;
     const int Hp = h->cfg.Hp;
     T.rec.resize(raw_n);
     std::vector<double> key(raw_n);
     std::vector<uint8_t> vs(raw_n);
-    HIPCHK(hipMemcpy(T.rec.data(), h->anodes.p + off, (size_t)raw_n * sizeof(NodeRec), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(key.data(), h->akey.p + off, (size_t)raw_n * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(vs.data(), h->avs.p + off, (size_t)raw_n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(T.rec.data(), h->arena.nodes.p + off, (size_t)raw_n * sizeof(NodeRec), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(key.data(), h->arena.key.p + off, (size_t)raw_n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(vs.data(), h->arena.vstate.p + off, (size_t)raw_n, hipMemcpyDeviceToHost));
     pdmpc_vehicle_out out;
     HIPCHK(hipMemcpy(&out, h->d_out.p + vehicle, sizeof out, hipMemcpyDeviceToHost));
     const std::vector<NodeRec>& R = T.rec;
@@ -2012,7 +1965,7 @@ int reconstruct_reference_tree(pdmpc_handle* h, int vehicle, uint32_t raw_n, Ref
     if (replayed) {
         // equal keys: the order is the binary heap's, which the kernel's replay has run (bulk_search.hpp, bk_replay) and left behind
         T.pops.resize((size_t)std::max(out.n_popped, 0));
-        if (!T.pops.empty()) HIPCHK(hipMemcpy(T.pops.data(), h->amidi.p + off, T.pops.size() * 4, hipMemcpyDeviceToHost));
+        if (!T.pops.empty()) HIPCHK(hipMemcpy(T.pops.data(), h->arena.mid_id.p + off, T.pops.size() * 4, hipMemcpyDeviceToHost));
     } else {
         for (uint32_t i = 0; i < raw_n; ++i)
             if (alive[i] && (goal < 0 || i == (uint32_t)goal || before(i, (uint32_t)goal) < 0)) T.pops.push_back(i);
@@ -2043,20 +1996,18 @@ int reconstruct_reference_tree(pdmpc_handle* h, int vehicle, uint32_t raw_n, Ref
 int pdmpc_debug_pop_trace(pdmpc_handle* h, int32_t vehicle, int32_t capacity, int32_t* ids, int32_t* n) {
     if (!h || !ids || !n) return fail(PDMPC_ERR_INVALID, "null argument");
     if (vehicle < 0 || vehicle >= h->max_vehicles) return fail(PDMPC_ERR_INVALID, "vehicle slot out of range");
-    if (!h->banks[h->bank].inv.empty() && vehicle < h->banks[h->bank].n_packed) vehicle = h->banks[h->bank].inv[(size_t)vehicle];  // (the batch was put into level order)
+    vehicle = debug_slot(h, vehicle);
     ON_DEVICE(h->cfg.device);
     HIPCHK(hipStreamSynchronize(h->stream));
-    {
-        int32_t sz = 0;
-        HIPCHK(hipMemcpy(&sz, h->d_tree_size.p + vehicle, 4, hipMemcpyDeviceToHost));
-        if (sz & PDMPC_TREE_FRONTIER) {
-            RefTree T;
-            int rc = reconstruct_reference_tree(h, vehicle, (uint32_t)PDMPC_TREE_SIZE(sz), T, (sz & PDMPC_TREE_REPLAYED) != 0);
-            if (rc) return rc;
-            *n = (int32_t)T.pops.size();
-            for (size_t i = 0; i < T.pops.size() && (int)i < capacity; ++i) ids[i] = (int32_t)T.ref_id[T.pops[i]];
-            return PDMPC_OK;
-        }
+    int32_t sz = 0;
+    HIPCHK(hipMemcpy(&sz, h->d_tree_size.p + vehicle, 4, hipMemcpyDeviceToHost));
+    if (sz & PDMPC_TREE_FRONTIER) {
+        RefTree T;
+        int rc = reconstruct_reference_tree(h, vehicle, (uint32_t)PDMPC_TREE_SIZE(sz), T, (sz & PDMPC_TREE_REPLAYED) != 0);
+        if (rc) return rc;
+        *n = (int32_t)T.pops.size();
+        for (size_t i = 0; i < T.pops.size() && (int)i < capacity; ++i) ids[i] = (int32_t)T.ref_id[T.pops[i]];
+        return PDMPC_OK;
     }
     return fail(PDMPC_ERR_INVALID, "no graph search has run in that slot");
 }
@@ -2073,37 +2024,25 @@ int pdmpc_debug_edge_check(pdmpc_handle* h, int32_t mode, int32_t n_cases, const
     }
     ON_DEVICE(h->cfg.device);
     const size_t ta = (size_t)a_off[n_cases], tb = (size_t)b_off[n_cases];
-    // (DevBuf-style owners: every early return frees what was allocated)
-    struct Owned {
-        void* p = nullptr;
-        ~Owned() {
-            if (p) (void)hipFree(p);
-        }
-        hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 8)); }
-    } o_ao, o_bo, o_hit, o_ax, o_ay, o_bx, o_by;
-    HIPCHK(o_ao.alloc(((size_t)n_cases + 1) * 4));
-    HIPCHK(o_bo.alloc(((size_t)n_cases + 1) * 4));
-    HIPCHK(o_hit.alloc((size_t)n_cases * 4));
-    HIPCHK(o_ax.alloc(ta * 8));
-    HIPCHK(o_ay.alloc(ta * 8));
-    HIPCHK(o_bx.alloc(tb * 8));
-    HIPCHK(o_by.alloc(tb * 8));
-    int32_t *d_ao = (int32_t*)o_ao.p, *d_bo = (int32_t*)o_bo.p, *d_hit = (int32_t*)o_hit.p;
-    double *d_ax = (double*)o_ax.p, *d_ay = (double*)o_ay.p, *d_bx = (double*)o_bx.p, *d_by = (double*)o_by.p;
-    HIPCHK(hipMemcpy(d_ao, a_off, ((size_t)n_cases + 1) * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_bo, b_off, ((size_t)n_cases + 1) * 4, hipMemcpyHostToDevice));
+    DevBuf<int32_t> d_ao, d_bo, d_hit;
+    DevBuf<double> d_ax, d_ay, d_bx, d_by;
+    if (d_ao.ensure_exact((size_t)n_cases + 1) | d_bo.ensure_exact((size_t)n_cases + 1) | d_hit.ensure_exact((size_t)n_cases) | d_ax.ensure_exact(ta) | d_ay.ensure_exact(ta) |
+        d_bx.ensure_exact(tb) | d_by.ensure_exact(tb))
+        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the edge-check cases");
+    HIPCHK(hipMemcpy(d_ao.p, a_off, ((size_t)n_cases + 1) * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_bo.p, b_off, ((size_t)n_cases + 1) * 4, hipMemcpyHostToDevice));
     if (ta) {
-        HIPCHK(hipMemcpy(d_ax, a_x, ta * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_ay, a_y, ta * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_ax.p, a_x, ta * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_ay.p, a_y, ta * 8, hipMemcpyHostToDevice));
     }
     if (tb) {
-        HIPCHK(hipMemcpy(d_bx, b_x, tb * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_by, b_y, tb * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_bx.p, b_x, tb * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_by.p, b_y, tb * 8, hipMemcpyHostToDevice));
     }
-    const int lrc = pdmpc_launch_edge_check(mode, n_cases, d_ao, d_ax, d_ay, d_bo, d_bx, d_by, d_hit, (void*)h->stream);
+    const int lrc = pdmpc_launch_edge_check(mode, n_cases, d_ao.p, d_ax.p, d_ay.p, d_bo.p, d_bx.p, d_by.p, d_hit.p, (void*)h->stream);
     if (lrc != 0) return fail(PDMPC_ERR_HIP, "edge-check launch failed");
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(hit, d_hit, (size_t)n_cases * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hit, d_hit.p, (size_t)n_cases * 4, hipMemcpyDeviceToHost));
     return PDMPC_OK;
 }
 
@@ -2111,36 +2050,17 @@ int pdmpc_debug_raw_tree(pdmpc_handle* h, int32_t vehicle, int32_t capacity, dou
                          int32_t* k, int32_t* parent, double* key, uint8_t* validity, int32_t* n) {
     if (!h || !n) return fail(PDMPC_ERR_INVALID, "null argument");
     if (vehicle < 0 || vehicle >= h->max_vehicles) return fail(PDMPC_ERR_INVALID, "vehicle slot out of range");
-    if (!h->banks[h->bank].inv.empty() && vehicle < h->banks[h->bank].n_packed) vehicle = h->banks[h->bank].inv[(size_t)vehicle];  // (the batch was put into level order)
+    vehicle = debug_slot(h, vehicle);
     ON_DEVICE(h->cfg.device);
     HIPCHK(hipStreamSynchronize(h->stream));
     int32_t sz = 0;
     HIPCHK(hipMemcpy(&sz, h->d_tree_size.p + vehicle, 4, hipMemcpyDeviceToHost));
-    sz = PDMPC_TREE_SIZE(sz);
-    *n = sz;
-    const size_t m = (size_t)std::max(std::min(sz, capacity), 0);
-    if (m == 0) return PDMPC_OK;
-    const size_t off = (size_t)vehicle * h->max_nodes;
-    std::vector<NodeRec> rec(m);
-    HIPCHK(hipMemcpy(rec.data(), h->anodes.p + off, m * sizeof(NodeRec), hipMemcpyDeviceToHost));
-    if (key) HIPCHK(hipMemcpy(key, h->akey.p + off, m * 8, hipMemcpyDeviceToHost));
-    if (validity) HIPCHK(hipMemcpy(validity, h->avs.p + off, m, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < m; ++i) {
-        if (x) x[i] = rec[i].x;
-        if (y) y[i] = rec[i].y;
-        if (yaw) yaw[i] = rec[i].yaw;
-        if (g) g[i] = rec[i].g;
-        if (hh) hh[i] = rec[i].h;
-        if (parent) parent[i] = (int32_t)rec[i].parent;
-        if (trim) trim[i] = NODE_TRIM(rec[i].packed);
-        if (k) k[i] = NODE_K(rec[i].packed);
-    }
-    return PDMPC_OK;
+    return copy_raw_tree(h, vehicle, PDMPC_TREE_SIZE(sz), capacity, {x, y, yaw, g, hh, trim, k, parent}, key, validity, n);
 }
 
 int pdmpc_debug_progress(pdmpc_handle* h, int32_t vehicle, uint32_t* words16) {
     if (!h || !words16 || vehicle < 0 || vehicle >= h->max_vehicles) return fail(PDMPC_ERR_INVALID, "bad argument");
-    if (!h->banks[h->bank].inv.empty() && vehicle < h->banks[h->bank].n_packed) vehicle = h->banks[h->bank].inv[(size_t)vehicle];  // (the batch was put into level order)
+    vehicle = debug_slot(h, vehicle);
     for (int i = 0; i < 32; ++i) words16[i] = h->progress ? ((volatile uint32_t*)h->progress)[vehicle * 64 + i] : 0u;
     return PDMPC_OK;
 }
@@ -2149,11 +2069,12 @@ int pdmpc_debug_tree(pdmpc_handle* h, int32_t vehicle, int32_t capacity, double*
                      int32_t* trim, int32_t* k, int32_t* parent, int32_t* n) {
     if (!h || !n) return fail(PDMPC_ERR_INVALID, "null argument");
     if (vehicle < 0 || vehicle >= h->max_vehicles) return fail(PDMPC_ERR_INVALID, "vehicle slot out of range");
-    if (!h->banks[h->bank].inv.empty() && vehicle < h->banks[h->bank].n_packed) vehicle = h->banks[h->bank].inv[(size_t)vehicle];  // (the batch was put into level order)
+    vehicle = debug_slot(h, vehicle);
     ON_DEVICE(h->cfg.device);
     HIPCHK(hipStreamSynchronize(h->stream));
     int32_t sz = 0;
     HIPCHK(hipMemcpy(&sz, h->d_tree_size.p + vehicle, 4, hipMemcpyDeviceToHost));
+    const TreeColumns cols{x, y, yaw, g, hh, trim, k, parent};
     if (sz & PDMPC_TREE_FRONTIER) {
         RefTree T;
         int rc = reconstruct_reference_tree(h, vehicle, (uint32_t)PDMPC_TREE_SIZE(sz), T, (sz & PDMPC_TREE_REPLAYED) != 0);
@@ -2161,34 +2082,11 @@ int pdmpc_debug_tree(pdmpc_handle* h, int32_t vehicle, int32_t capacity, double*
         *n = (int32_t)T.ref_nodes.size();
         for (size_t i = 0; i < T.ref_nodes.size() && (int)i < capacity; ++i) {
             const NodeRec& r = T.rec[T.ref_nodes[i]];
-            if (x) x[i] = r.x;
-            if (y) y[i] = r.y;
-            if (yaw) yaw[i] = r.yaw;
-            if (g) g[i] = r.g;
-            if (hh) hh[i] = r.h;
-            if (parent) parent[i] = r.parent ? (int32_t)T.ref_id[r.parent - 1] : 0;
-            if (trim) trim[i] = NODE_TRIM(r.packed);
-            if (k) k[i] = NODE_K(r.packed);
+            cols.put(i, r, r.parent ? (int32_t)T.ref_id[r.parent - 1] : 0);
         }
         return PDMPC_OK;
     }
-    *n = sz;
-    const size_t m = (size_t)std::max(std::min(sz, capacity), 0);
-    if (m == 0) return PDMPC_OK;
-    const size_t off = (size_t)vehicle * h->max_nodes;
-    std::vector<NodeRec> rec(m);
-    HIPCHK(hipMemcpy(rec.data(), h->anodes.p + off, m * sizeof(NodeRec), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < m; ++i) {
-        if (x) x[i] = rec[i].x;
-        if (y) y[i] = rec[i].y;
-        if (yaw) yaw[i] = rec[i].yaw;
-        if (g) g[i] = rec[i].g;
-        if (hh) hh[i] = rec[i].h;
-        if (parent) parent[i] = (int32_t)rec[i].parent;
-        if (trim) trim[i] = NODE_TRIM(rec[i].packed);
-        if (k) k[i] = NODE_K(rec[i].packed);
-    }
-    return PDMPC_OK;
+    return copy_raw_tree(h, vehicle, sz, capacity, cols, nullptr, nullptr, n);
 }
 
 }  // extern "C"

@@ -284,6 +284,21 @@ def test_a_failed_pack_consumes_the_step_weights():
     h.close()
 
 
+def test_a_plan_without_a_record_array_is_refused():
+    """pdmpc_plan_batch and pdmpc_plan_step with vehicles to plan but a null record pointer return PDMPC_ERR_INVALID, as
+    pdmpc_fetch_results does, and the same handle plans the next batch as if nothing had happened."""
+    options, mpa, iters = problems.problem_set("interx", 7, 6, Hp=6)
+    _, ref, _ = _oracle().plan_batch(options, mpa, iters)
+    h = Handle(options)
+    h.upload_mpa(mpa)
+    arr, keep = abi.pack_vehicles(iters, h.Hp)
+    assert h.L.pdmpc_plan_batch(h.h, len(iters), arr, None) == -1  # PDMPC_ERR_INVALID
+    assert h.L.pdmpc_plan_step(h.h, len(iters), arr, None, None, None, None) == -1
+    del keep
+    assert_records_equal(h.plan_batch(iters), ref, "after")
+    h.close()
+
+
 def test_interx_with_hdv_reachable_sets():
     """are_constraints_satisfied_interx.m:23-31: the HDV soup is a third curve set checked with the normal-offset area."""
     options, mpa, iters = problems.problem_set("interx", 31, 16, Hp=6, n_hdv=2)
