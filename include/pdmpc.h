@@ -374,6 +374,26 @@ int pdmpc_unique_priorities(pdmpc_handle* handle, int32_t n, const uint8_t* adja
                             int32_t* priorities);
 int pdmpc_unique_priorities_host(int32_t n, const uint8_t* adjacency, int64_t max_out, int64_t* n_out, uint32_t* masks, int32_t* priorities);
 
+/* ---- reachable sets (csrc/reachable_sets.cpp, csrc/reachable_kernel.hip) ----
+ * pdmpc_local_reachable_sets: MotionPrimitiveAutomaton.local_reachable_sets_conv (reachability_analysis_offline_DP,
+ * MotionPrimitiveAutomaton.m:394-647, convexified) of an automaton: polygon trim * Hp + k (0-based trim and k) is the convex hull
+ * of what the trim reaches at step k + 1 from the origin, clockwise from its smallest-x (then smallest-y) vertex, open (first vertex
+ * not repeated).  offset has n_trims * Hp + 1 entries and is always written; x and y (capacity entries each) only if the table fits,
+ * PDMPC_ERR_CAPACITY otherwise (call with capacity 0 to size them). */
+int pdmpc_local_reachable_sets(const pdmpc_mpa* mpa, int32_t capacity, int32_t* offset, double* x, double* y);
+/* ReachableSetCoupler.couple (ReachableSetCoupler.m:5-56) on the step-Hp hulls of n vehicles at (x, y, yaw) in trim (1-based):
+ * bounding-box pre-filter (boxes that only touch are not coupled), then coupled iff the overlap area exceeds 1e-3.  adjacency is
+ * n x n bytes (symmetric, zero diagonal); area (n x n, or NULL) holds the area of every pair that passed the box test, 0 elsewhere.
+ * cos_yaw / sin_yaw are the caller's cos(yaw) / sin(yaw): the sets move with the caller's libm. */
+#define PDMPC_REACHABLE_MAX_COLS 256 /* vertices of one local hull the device coupler accepts (single_speed Hp 10: 146 at most) */
+int pdmpc_upload_reachable_sets(pdmpc_handle* handle, int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* local_sets);
+int pdmpc_reachable_set_coupling(pdmpc_handle* handle, int32_t n, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw,
+                                 const int32_t* trim, uint8_t* adjacency, double* area);
+int pdmpc_reachable_set_coupling_host(int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* local_sets, int32_t n, const double* x, const double* y,
+                                      const double* cos_yaw, const double* sin_yaw, const int32_t* trim, uint8_t* adjacency, double* area);
+/* kernel time (HIP events, ms) of the last pdmpc_reachable_set_coupling */
+int pdmpc_reachable_set_coupling_kernel_ms(pdmpc_handle* handle, double* ms);
+
 /* ---- the caller's side of the boundary, natively (csrc/step_controller.cpp) ----
  * One MPC time step of the prioritized sequential controller around pdmpc_plan_step, without any interpreter in the loop:
  * traffic info, coupling, priorities, grouping, computation levels, obstacle assembly, ONE launch, exhaustion handling,
@@ -382,6 +402,12 @@ int pdmpc_unique_priorities_host(int32_t n, const uint8_t* adjacency, int64_t ma
  * PrioritizedController.m:297-324,375-389,449-718; plant/Simulation.m:86-100).  p-dmpc_amd/pdmpc/controller.py is the same
  * logic in Python (it also offers the random and FCA prioritizers); the two build bit-identical step problems. */
 enum { PDMPC_COUPLING_FULL = 0, PDMPC_COUPLING_DISTANCE = 1, PDMPC_COUPLING_NONE = 2 };          /* Coupler.m:31-32, DistanceCoupler.m:15-50 */
+enum { PDMPC_COUPLING_REACHABLE_SET = 3 };                                                     /* ReachableSetCoupler.m:5-56 */
+/* how a parallel predecessor (a higher-priority coupled vehicle whose coupling was cut into another computation level) enters a
+ * vehicle's search (Config.isDealPredictionInconsistency, PrioritizedController.m:29-33): its previous plan shifted by one step
+ * (parallel_coupling_previous_trajectory, :409-447) or its Hp reachable sets at its current pose (parallel_coupling_reachability,
+ * :391-407) */
+enum { PDMPC_PARALLEL_PREVIOUS_TRAJECTORY = 0, PDMPC_PARALLEL_REACHABLE_SETS = 1 };
 enum { PDMPC_PRIORITY_CONSTANT = 0, PDMPC_PRIORITY_COLORING = 1 };                             /* ConstantPrioritizer.m, ColoringPrioritizer.m */
 enum { PDMPC_WEIGHT_DISTANCE = 0, PDMPC_WEIGHT_CONSTANT = 1 };                                 /* weight/DistanceWeigher.m, ConstantWeigher.m */
 enum { PDMPC_SUCCESSOR_NONE = 0, PDMPC_SUCCESSOR_AREA_OF_STANDSTILL = 1, PDMPC_SUCCESSOR_AREA_OF_PREVIOUS_TRAJECTORY = 2 }; /* ConstraintFromSuccessor.m */
@@ -484,6 +510,12 @@ int pdmpc_controller_last_timing(pdmpc_controller* c, double* ms6);
 /* ... and summed over the steps since the last call with reset != 0 (n_steps: how many) */
 int pdmpc_controller_timing_sum(pdmpc_controller* c, double* ms6, int64_t* n_steps, int32_t reset);
 const char* pdmpc_controller_last_error(void);
+/* The reachable-set features of the controller.  pdmpc_controller_set_reachability computes the automaton's local
+ * reachable sets (pdmpc_local_reachable_sets) and, for a controller with a handle, uploads them (pdmpc_upload_reachable_sets); a step
+ * with PDMPC_COUPLING_REACHABLE_SET or PDMPC_PARALLEL_REACHABLE_SETS but without them returns PDMPC_ERR_INVALID.  With a handle the
+ * coupling runs on the device (pdmpc_reachable_set_coupling), without one on the host twin (pdmpc_reachable_set_coupling_host). */
+int pdmpc_controller_set_reachability(pdmpc_controller* c, const pdmpc_mpa* mpa);
+int pdmpc_controller_set_parallel_coupling(pdmpc_controller* c, int32_t mode); /* PDMPC_PARALLEL_*, default PREVIOUS_TRAJECTORY */
 
 /* ---- several GPUs behind the same boundary (csrc/group.cpp) ----
  * The reference's vehicles exchange their solved areas after every computation level: each publishes a Predictions message that every

@@ -335,6 +335,17 @@ struct pdmpc_handle {
     DevBuf<uint32_t> d_prio_count, d_prio_mask;  // pdmpc_unique_priorities: acyclic masks per tile, the acyclic masks
     DevBuf<int64_t> d_prio_off;                  // ... exclusive offsets of the tiles (entry n_tiles: the total)
     DevBuf<int32_t> d_prio_order;                // ... the priorities of every acyclic mask
+    // pdmpc_upload_reachable_sets / pdmpc_reachable_set_coupling (reachable_kernel.hip): the step-Hp local hulls, the workspace and
+    // the pinned staging of inputs and outputs, all sized at upload for max_vehicles vehicles
+    bool has_reach = false;
+    int reach_trims = 0, reach_Hp = 0, reach_cols = 0;
+    DevBuf<double> d_reach_local;      // x of every trim's step-Hp hull, then y
+    DevBuf<int32_t> d_reach_off;       // [n_trims + 1]
+    DevBuf<unsigned char> d_reach_ws;  // inputs [4 n] + trims [n] | moved hulls | hull sizes | boxes | adjacency [n x n] (8-aligned) + areas [n x n]
+    PinnedBuf<unsigned char> h_reach_in, h_reach_out;
+    std::vector<int32_t> reach_off_host;
+    hipEvent_t reach_ev[2] = {nullptr, nullptr};
+    float reach_kernel_ms = 0.0f;
     int device_share = 1;                // handles of one process that launch on this device side by side (pdmpc_set_device_share: a group's logical ranks)
     bool boards_dirty = true;            // the helper boards / the finished counter need clearing before the helper workgroups may read them
     uint32_t help_fin_total = 0;         // value of the finished counter once every launch so far has ended
@@ -1149,6 +1160,8 @@ int pdmpc_create(const pdmpc_config* config, pdmpc_handle** out_handle) {
 int pdmpc_destroy(pdmpc_handle* h) {
     if (!h) return PDMPC_OK;
     DeviceGuard device_guard__(h->cfg.device);
+    for (hipEvent_t& e : h->reach_ev)
+        if (e) (void)hipEventDestroy(e);
     delete h;
     return PDMPC_OK;
 }
@@ -1750,6 +1763,126 @@ int pdmpc_unique_priorities(pdmpc_handle* h, int32_t n, const uint8_t* adjacency
     HIPCHK(hipMemcpyAsync(masks, h->d_prio_mask.p, (size_t)K * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(priorities, h->d_prio_order.p, (size_t)K * n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(sync_stream(h));
+    return PDMPC_OK;
+}
+
+// ---- the reachable-set coupler on the device (reachable_kernel.hip)
+namespace {
+struct ReachLayout {  // byte offsets into d_reach_ws / the pinned staging for n vehicles (computed the same way at upload and per call)
+    size_t in, trim, hull_x, hull_y, hull_n, box, adj, area, in_bytes, out_bytes, total;
+};
+inline size_t align_up8(size_t v) { return (v + 7) & ~(size_t)7; }
+ReachLayout reach_layout(int n, int cols) {
+    ReachLayout L;
+    L.in = 0;
+    L.trim = L.in + (size_t)4 * n * sizeof(double);
+    L.in_bytes = align_up8(L.trim + (size_t)n * sizeof(int32_t));
+    L.hull_x = L.in_bytes;
+    L.hull_y = L.hull_x + (size_t)n * cols * sizeof(double);
+    L.box = L.hull_y + (size_t)n * cols * sizeof(double);
+    L.hull_n = L.box + (size_t)4 * n * sizeof(double);
+    L.adj = align_up8(L.hull_n + (size_t)n * sizeof(int32_t));
+    L.area = L.adj + align_up8((size_t)n * n);
+    L.out_bytes = L.area + (size_t)n * n * sizeof(double) - L.adj;
+    L.total = L.area + (size_t)n * n * sizeof(double);
+    return L;
+}
+}  // namespace
+
+int pdmpc_upload_reachable_sets(pdmpc_handle* h, int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* sets) {
+    if (!h || !sets || !sets->offset || n_trims < 1 || Hp < 1) return fail(PDMPC_ERR_INVALID, "pdmpc_upload_reachable_sets: bad argument");
+    if (Hp != h->cfg.Hp) return fail(PDMPC_ERR_INVALID, "pdmpc_upload_reachable_sets: Hp differs from the handle's config.Hp");
+    if (sets->n_polygons != n_trims * Hp) return fail(PDMPC_ERR_INVALID, "pdmpc_upload_reachable_sets: expected n_trims * Hp polygons");
+    int cols = 1;
+    for (int p = 0; p < sets->n_polygons; ++p) {
+        const int m = sets->offset[p + 1] - sets->offset[p];
+        if (m < 1) return fail(PDMPC_ERR_INVALID, "pdmpc_upload_reachable_sets: empty polygon");
+        if (m > PDMPC_REACHABLE_MAX_COLS) return fail(PDMPC_ERR_CAPACITY, "pdmpc_upload_reachable_sets: a hull has more than PDMPC_REACHABLE_MAX_COLS vertices");
+        cols = std::max(cols, m);
+    }
+    if (!sets->x || !sets->y) return fail(PDMPC_ERR_INVALID, "pdmpc_upload_reachable_sets: null coordinates");
+    // only step Hp is coupled on (ReachableSetCoupler.m:9-12: reachable_sets(:, end))
+    std::vector<int32_t> off((size_t)n_trims + 1, 0);
+    for (int t = 0; t < n_trims; ++t) {
+        const int p = t * Hp + Hp - 1;
+        off[t + 1] = off[t] + (sets->offset[p + 1] - sets->offset[p]);
+    }
+    const int tot = off[n_trims];
+    std::vector<double> xy((size_t)2 * tot);
+    for (int t = 0; t < n_trims; ++t) {
+        const int p = t * Hp + Hp - 1, a = sets->offset[p], m = sets->offset[p + 1] - a;
+        std::memcpy(xy.data() + off[t], sets->x + a, (size_t)m * sizeof(double));
+        std::memcpy(xy.data() + tot + off[t], sets->y + a, (size_t)m * sizeof(double));
+    }
+    ON_DEVICE(h->cfg.device);
+    h->has_reach = false;
+    const ReachLayout L = reach_layout(h->max_vehicles, cols);
+    if (h->d_reach_local.ensure_exact(xy.size()) || h->d_reach_off.ensure_exact(off.size()) || h->d_reach_ws.ensure_exact(L.total) ||
+        h->h_reach_in.ensure(L.in_bytes) || h->h_reach_out.ensure(L.out_bytes))
+        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the reachable-set coupler");
+    for (hipEvent_t& e : h->reach_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipMemcpy(h->d_reach_local.p, xy.data(), xy.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_reach_off.p, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    h->reach_off_host = off;
+    h->reach_trims = n_trims;
+    h->reach_Hp = Hp;
+    h->reach_cols = cols;
+    h->has_reach = true;
+    return PDMPC_OK;
+}
+
+int pdmpc_reachable_set_coupling(pdmpc_handle* h, int32_t n, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw, const int32_t* trim,
+                                 uint8_t* adjacency, double* area) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    if (!h->has_reach) return fail(PDMPC_ERR_INVALID, "pdmpc_reachable_set_coupling before pdmpc_upload_reachable_sets");
+    if (n < 0 || !adjacency || (n > 0 && (!x || !y || !cos_yaw || !sin_yaw || !trim))) return fail(PDMPC_ERR_INVALID, "pdmpc_reachable_set_coupling: bad argument");
+    if (n > h->max_vehicles) return fail(PDMPC_ERR_CAPACITY, "pdmpc_reachable_set_coupling: more vehicles than config.max_vehicles");
+    if (n == 0) return PDMPC_OK;
+    for (int v = 0; v < n; ++v)
+        if (trim[v] < 1 || trim[v] > h->reach_trims) return fail(PDMPC_ERR_INVALID, "pdmpc_reachable_set_coupling: trim out of range");
+    ON_DEVICE(h->cfg.device);
+    const ReachLayout L = reach_layout(n, h->reach_cols);
+    unsigned char* hin = h->h_reach_in.p;
+    std::memcpy(hin + L.in, x, (size_t)n * sizeof(double));
+    std::memcpy(hin + L.in + (size_t)n * sizeof(double), y, (size_t)n * sizeof(double));
+    std::memcpy(hin + L.in + (size_t)2 * n * sizeof(double), cos_yaw, (size_t)n * sizeof(double));
+    std::memcpy(hin + L.in + (size_t)3 * n * sizeof(double), sin_yaw, (size_t)n * sizeof(double));
+    int32_t* ht = (int32_t*)(hin + L.trim);
+    for (int v = 0; v < n; ++v) ht[v] = trim[v] - 1;
+    unsigned char* ws = h->d_reach_ws.p;
+    ReachArgs A;
+    A.n = n;
+    A.max_cols = h->reach_cols;
+    A.local_x = h->d_reach_local.p;
+    A.local_y = h->d_reach_local.p + h->reach_off_host[h->reach_trims];
+    A.local_off = h->d_reach_off.p;
+    A.in = (const double*)(ws + L.in);
+    A.trim = (const int32_t*)(ws + L.trim);
+    A.hull_x = (double*)(ws + L.hull_x);
+    A.hull_y = (double*)(ws + L.hull_y);
+    A.hull_n = (int32_t*)(ws + L.hull_n);
+    A.box = (double*)(ws + L.box);
+    A.adjacency = (uint8_t*)(ws + L.adj);
+    A.area = (double*)(ws + L.area);
+    HIPCHK(hipMemcpyAsync(ws, hin, L.in_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipEventRecord(h->reach_ev[0], h->stream));
+    const int lrc = pdmpc_launch_reachable_coupling(&A, (void*)h->stream);
+    if (lrc) return fail(PDMPC_ERR_HIP, std::string("reachable-set coupling kernel launch failed: ") + hipGetErrorString((hipError_t)lrc));
+    HIPCHK(hipEventRecord(h->reach_ev[1], h->stream));
+    const size_t out_bytes = area ? L.out_bytes : (size_t)n * n;
+    HIPCHK(hipMemcpyAsync(h->h_reach_out.p, ws + L.adj, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(sync_stream(h));
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, h->reach_ev[0], h->reach_ev[1]) == hipSuccess) h->reach_kernel_ms = ms;
+    std::memcpy(adjacency, h->h_reach_out.p, (size_t)n * n);
+    if (area) std::memcpy(area, h->h_reach_out.p + (L.area - L.adj), (size_t)n * n * sizeof(double));
+    return PDMPC_OK;
+}
+
+int pdmpc_reachable_set_coupling_kernel_ms(pdmpc_handle* h, double* ms) {
+    if (!h || !ms) return fail(PDMPC_ERR_INVALID, "null argument");
+    *ms = (double)h->reach_kernel_ms;
     return PDMPC_OK;
 }
 

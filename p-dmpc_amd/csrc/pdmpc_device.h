@@ -294,9 +294,30 @@ struct PriorityArgs {                          // passed by value: the kernels r
     uint64_t n_masks;                          // 2^E
 };
 
+// The reachable-set coupler (reachable_kernel.hip; ReachableSetCoupler.m:5-56): every vehicle's step-Hp hull moved to its pose,
+// then the pairs i < j.  All arrays are the handle's, sized at pdmpc_upload_reachable_sets.
+#define PDMPC_REACH_MAX_COLS 256  // vertices of one local hull (pdmpc_upload_reachable_sets returns PDMPC_ERR_CAPACITY above)
+#define PDMPC_REACH_WAVE 64       // a workgroup of pass 2 is one wavefront
+struct ReachArgs {
+    int32_t n, max_cols;
+    const double* local_x;        // the local step-Hp hulls of the trims, clockwise, open: trim t = columns local_off[t] .. local_off[t + 1] - 1
+    const double* local_y;
+    const int32_t* local_off;     // [n_trims + 1]
+    const double* in;             // [4 n]: x, y, cos(yaw), sin(yaw) of every vehicle (host libm)
+    const int32_t* trim;          // [n] 0-based, checked on the host
+    double* hull_x;               // [n * max_cols] the moved hulls
+    double* hull_y;
+    int32_t* hull_n;              // [n]
+    double* box;                  // [4 n] x0, x1, y0, y1
+    uint8_t* adjacency;           // [n * n]
+    double* area;                 // [n * n] overlap area of every pair that passed the box test, 0 elsewhere
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+// reachable_kernel.hip: the two passes of the reachable-set coupler on the handle's stream
+int pdmpc_launch_reachable_coupling(const ReachArgs* args, void* stream);
 // bulk_kernel*.hip: the graph search as bulk-synchronous passes (count searches + args->n_helpers helper workgroups in ONE launch) for the
 // InterX checker with one successor-mask word / with any number of them, and for the separating-axis checker; lds_high_water = the
 // handle's record of the dynamic LDS size set so far on that kernel

@@ -8,7 +8,8 @@
 //   reference trajectory      hlc/controller/common/get_reference_trajectory.m:27-46, sample_reference_trajectory.m:1-99,
 //                             get_arc_distance_to_endpoint.m:39-114, projection_2d.m:14-42
 //   predicted lanelets        hlc/controller/common/get_predicted_lanelets.m:25-62, get_lanelets_boundary.m:18-68
-//   coupling                  Coupler.m:31-32 (full), DistanceCoupler.m:15-50 (distance)
+//   coupling                  Coupler.m:31-32 (full), DistanceCoupler.m:15-50 (distance), ReachableSetCoupler.m:5-56 (reachable sets,
+//                             reachable_sets.cpp / reachable_kernel.hip)
 //   priorities -> DAG         ConstantPrioritizer.m:14-20, Prioritizer.m:36-77, ColoringPrioritizer.m:11-131
 //   grouping                  PrioritizedController.group (hlc/controller/prioritized/PrioritizedController.m:375-389),
 //                             weight/DistanceWeigher.m:12-39, weight/ConstantWeigher.m:15-17, cut/GreedyCutter.m:5-86
@@ -31,6 +32,7 @@
 #include <vector>
 
 #include "../../include/pdmpc.h"
+#include "../../include/pdmpc_geometry.h"
 #include "mt19937ar.hpp"
 
 namespace {
@@ -183,6 +185,14 @@ struct pdmpc_controller {
     std::vector<uint32_t> o_masks;  // [K] the acyclic orientations (pdmpc_unique_priorities)
     std::vector<int32_t> o_prio;    // [K x n] their priorities
     std::vector<double> o_val;      // [K x n] choice scratch: cost-to-come of the final node per (instance, vehicle), inf if exhausted
+    // reachable sets (pdmpc_controller_set_reachability): the automaton's local hulls, polygon trim * Hp + k, and per
+    // step every vehicle's Hp sets at its pose, closed (HighLevelController.m:219-263)
+    int parallel_mode = PDMPC_PARALLEL_PREVIOUS_TRAJECTORY;
+    bool has_reach = false;
+    std::vector<int32_t> reach_off;
+    std::vector<double> reach_x, reach_y;
+    std::vector<std::vector<Poly>> reach_sets;
+    std::vector<double> reach_cos, reach_sin;
     std::string err;
 };
 
@@ -811,6 +821,40 @@ int pdmpc_controller_create(pdmpc_handle* handle, const pdmpc_controller_config*
     return PDMPC_OK;
 }
 
+int pdmpc_controller_set_parallel_coupling(pdmpc_controller* c, int32_t mode) {
+    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
+    if (mode != PDMPC_PARALLEL_PREVIOUS_TRAJECTORY && mode != PDMPC_PARALLEL_REACHABLE_SETS) return cfail(c, PDMPC_ERR_INVALID, "unknown parallel coupling mode");
+    c->parallel_mode = mode;
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_set_reachability(pdmpc_controller* c, const pdmpc_mpa* mpa) {
+    if (!c || !mpa) return cfail(c, PDMPC_ERR_INVALID, "null argument");
+    if (mpa->Hp != c->Hp) return cfail(c, PDMPC_ERR_INVALID, "the automaton's Hp differs from the controller's");
+    if (mpa->n_trims != (int32_t)c->trim_speed.size()) return cfail(c, PDMPC_ERR_INVALID, "the automaton's trims differ from the scenario's");
+    c->has_reach = false;
+    std::vector<int32_t> off((size_t)mpa->n_trims * mpa->Hp + 1, 0);
+    int rc = pdmpc_local_reachable_sets(mpa, 0, off.data(), nullptr, nullptr);
+    if (rc != PDMPC_OK && rc != PDMPC_ERR_CAPACITY) return cfail(c, rc, "pdmpc_local_reachable_sets failed");
+    std::vector<double> x((size_t)off.back() + 1), y((size_t)off.back() + 1);
+    rc = pdmpc_local_reachable_sets(mpa, off.back(), off.data(), x.data(), y.data());
+    if (rc) return cfail(c, rc, "pdmpc_local_reachable_sets failed");
+    if (c->h) {
+        pdmpc_polygon_set ps;
+        ps.n_polygons = (int32_t)off.size() - 1;
+        ps.offset = off.data();
+        ps.x = x.data();
+        ps.y = y.data();
+        rc = pdmpc_upload_reachable_sets(c->h, mpa->n_trims, mpa->Hp, &ps);
+        if (rc) return cfail(c, rc, std::string("pdmpc_upload_reachable_sets: ") + pdmpc_last_error());
+    }
+    c->reach_off = std::move(off);
+    c->reach_x = std::move(x);
+    c->reach_y = std::move(y);
+    c->has_reach = true;
+    return PDMPC_OK;
+}
+
 int pdmpc_controller_destroy(pdmpc_controller* c) {
     delete c;
     return PDMPC_OK;
@@ -825,6 +869,9 @@ int assemble_step(pdmpc_controller* c, bool seq_given = false);
 int pdmpc_controller_build_step(pdmpc_controller* c) {
     if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
     const int n = c->n, Hp = c->Hp;
+    const bool reach_coupling = c->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET, reach_parallel = c->parallel_mode == PDMPC_PARALLEL_REACHABLE_SETS;
+    if ((reach_coupling || reach_parallel) && !c->has_reach)
+        return cfail(c, PDMPC_ERR_INVALID, "reachable-set coupling / parallel coupling by reachable sets need pdmpc_controller_set_reachability first");
     c->k += 1;
     c->arena.reset();
     if (c->exploring) {
@@ -862,9 +909,47 @@ int pdmpc_controller_build_step(pdmpc_controller* c) {
         sample_reference(Hp, c->veh[v].px, c->veh[v].py, c->mx[v], c->my[v], step, c->ref_x[v], c->ref_y[v], pidx, cpi);
         lanelet_boundary(*c, v, pidx, cpi, c->bnd_left[v], c->bnd_right[v]);
     }
+    // ---- reachable sets at the vehicles' poses (reachable_sets_at_pose, MotionPrimitiveAutomaton.m:649-687), closed by repeating the
+    // first vertex (HighLevelController.m:258-263); only when a feature reads them
+    if (reach_coupling || reach_parallel) {
+        c->reach_sets.resize(n);
+        c->reach_cos.resize(n);
+        c->reach_sin.resize(n);
+        for (int v = 0; v < n; ++v) {
+            const double cy = std::cos(c->myaw[v]), sy = std::sin(c->myaw[v]);
+            c->reach_cos[v] = cy;
+            c->reach_sin[v] = sy;
+            std::vector<Poly>& sets = c->reach_sets[v];
+            sets.resize(Hp);
+            for (int q = 0; q < Hp; ++q) {
+                const int p = (c->trims[v] - 1) * Hp + q, a = c->reach_off[p], m = c->reach_off[p + 1] - a;
+                Poly& P = sets[q];
+                P.x.resize(m + 1);
+                P.y.resize(m + 1);
+                for (int r = 0; r < m; ++r) pdmpc_move_point(cy, sy, c->mx[v], c->my[v], c->reach_x[a + r], c->reach_y[a + r], &P.x[r], &P.y[r]);
+                P.x[m] = P.x[0];
+                P.y[m] = P.y[0];
+            }
+        }
+    }
     // ---- coupling
     c->adjacency.assign((size_t)n * n, 0);
-    if (c->cfg.coupling == PDMPC_COUPLING_FULL) {
+    if (reach_coupling) {  // ReachableSetCoupler.couple (ReachableSetCoupler.m:5-56): on the device with a handle, else the host twin
+        int rc;
+        if (c->h) {
+            rc = pdmpc_reachable_set_coupling(c->h, n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(), c->trims.data(), c->adjacency.data(), nullptr);
+            if (rc) return cfail(c, rc, std::string("pdmpc_reachable_set_coupling: ") + pdmpc_last_error());
+        } else {
+            pdmpc_polygon_set ps;
+            ps.n_polygons = (int32_t)c->reach_off.size() - 1;
+            ps.offset = c->reach_off.data();
+            ps.x = c->reach_x.data();
+            ps.y = c->reach_y.data();
+            rc = pdmpc_reachable_set_coupling_host((int32_t)c->trim_speed.size(), Hp, &ps, n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(),
+                                                   c->trims.data(), c->adjacency.data(), nullptr);
+            if (rc) return cfail(c, rc, "pdmpc_reachable_set_coupling_host failed");
+        }
+    } else if (c->cfg.coupling == PDMPC_COUPLING_FULL) {
         for (int a = 0; a < n; ++a)
             for (int b = 0; b < n; ++b) at(c->adjacency, n, a, b) = a != b;
     } else if (c->cfg.coupling == PDMPC_COUPLING_DISTANCE) {
@@ -975,7 +1060,8 @@ int assemble_step(pdmpc_controller* c, bool seq_given) {
         for (const int32_t* q = dir_pred.begin(i); q != dir_pred.end(i); ++q) {
             const int j = *q;
             if (at(c->directed_seq, n, j, i)) continue;
-            if (c->info_old[j].present && c->k > 1) {
+            // (parallel_coupling_reachability, :391-407: the predecessor's reachable sets exist from the first step on)
+            if (c->parallel_mode == PDMPC_PARALLEL_REACHABLE_SETS || (c->info_old[j].present && c->k > 1)) {
                 dplp[ndp++] = j;
                 if (memo) dk.w[j >> 6] |= 1ull << (j & 63);
             }
@@ -1002,7 +1088,13 @@ int assemble_step(pdmpc_controller* c, bool seq_given) {
         };
         auto build_dyn = [&]() {
             SetBuilder dyn(*c);
-            for (int q = 0; q < ndp; ++q) add_shifted(dyn, c->info_old[dplp[q]].shapes);
+            for (int q = 0; q < ndp; ++q) {
+                if (c->parallel_mode == PDMPC_PARALLEL_REACHABLE_SETS) {
+                    for (const Poly& p : c->reach_sets[dplp[q]]) dyn.add(p);
+                } else {
+                    add_shifted(dyn, c->info_old[dplp[q]].shapes);
+                }
+            }
             for (int q = 0; q < nds; ++q) add_shifted(dyn, c->info_old[dslp[q]].shapes);
             return dyn.finish();
         };

@@ -5,6 +5,7 @@ present, construction raises.  The library is built in-tree by `__graft_entry__.
 `make -C p-dmpc_amd/csrc`.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -98,6 +99,13 @@ EXPORTS = [
     "pdmpc_controller_optimal_step",
     "pdmpc_controller_optimal_run",
     "pdmpc_controller_optimal_result",
+    "pdmpc_local_reachable_sets",
+    "pdmpc_upload_reachable_sets",
+    "pdmpc_reachable_set_coupling",
+    "pdmpc_reachable_set_coupling_host",
+    "pdmpc_reachable_set_coupling_kernel_ms",
+    "pdmpc_controller_set_reachability",
+    "pdmpc_controller_set_parallel_coupling",
     "pdmpc_last_error",
     "pdmpc_version",
 ]
@@ -144,6 +152,64 @@ def unique_priorities_call(adjacency, max_out, handle=None):
         raise BackendError("%s failed with status %d" % (what, rc))
     k = K.value
     return prio[: k * n].reshape(k, n).T.astype(np.int64), masks[:k].astype(np.int64)
+
+
+def local_reachable_sets_native(mpa):
+    """pdmpc_local_reachable_sets (csrc/reachable_sets.cpp), the C++ twin of MotionPrimitiveAutomaton.local_reachable_sets_conv
+    -> [trim][k] (2, m) arrays."""
+    L = load_library()
+    s, keep = abi.pack_mpa(mpa)
+    n, Hp = mpa.n_trims, mpa.Hp
+    off = np.zeros(n * Hp + 1, dtype=np.int32)
+    rc = L.pdmpc_local_reachable_sets(C.byref(s), 0, off.ctypes.data_as(abi.c_int32_p), None, None)
+    if rc not in (0, ERR_CAPACITY):
+        raise BackendError("pdmpc_local_reachable_sets failed with status %d" % rc)
+    tot = int(off[-1])
+    x = np.zeros(max(tot, 1))
+    y = np.zeros(max(tot, 1))
+    rc = L.pdmpc_local_reachable_sets(C.byref(s), tot, off.ctypes.data_as(abi.c_int32_p), x.ctypes.data_as(abi.c_double_p), y.ctypes.data_as(abi.c_double_p))
+    if rc != 0:
+        raise BackendError("pdmpc_local_reachable_sets failed with status %d" % rc)
+    del keep
+    return [[np.array([x[off[i * Hp + k] : off[i * Hp + k + 1]], y[off[i * Hp + k] : off[i * Hp + k + 1]]]) for k in range(Hp)] for i in range(n)]
+
+
+def pack_local_sets(local_sets):
+    """[trim][k] (2, m) hulls -> (pdmpc_polygon_set, keep-alive) with polygon trim * Hp + k."""
+    keep = abi._Keep()
+    return abi.pack_polygon_set([h for row in local_sets for h in row], keep), keep
+
+
+def _coupling_args(x, y, yaw, trim):
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    yaw = np.asarray(yaw, dtype=np.float64)
+    c = np.array([math.cos(float(a)) for a in yaw], dtype=np.float64)  # the host's libm, as the Python twin moves the sets
+    s = np.array([math.sin(float(a)) for a in yaw], dtype=np.float64)
+    t = np.ascontiguousarray(trim, dtype=np.int32)
+    return x, y, c, s, t
+
+
+def reachable_set_coupling_call(local_sets, x, y, yaw, trim, handle=None):
+    """ReachableSetCoupler.couple natively: on `handle`'s device (pdmpc_reachable_set_coupling; the handle must hold the table, see
+    Handle.upload_reachable_sets) or, without one, on the host twin (pdmpc_reachable_set_coupling_host).  trim is 1-based.
+    -> (adjacency (n, n) uint8, areas (n, n))."""
+    L = load_library()
+    x, y, c, s, t = _coupling_args(x, y, yaw, trim)
+    n = x.size
+    adj = np.zeros(max(n * n, 1), dtype=np.uint8)
+    area = np.zeros(max(n * n, 1), dtype=np.float64)
+    ptrs = [x.ctypes.data_as(abi.c_double_p), y.ctypes.data_as(abi.c_double_p), c.ctypes.data_as(abi.c_double_p), s.ctypes.data_as(abi.c_double_p),
+            t.ctypes.data_as(abi.c_int32_p), adj.ctypes.data_as(abi.c_uint8_p), area.ctypes.data_as(abi.c_double_p)]
+    if handle is not None:
+        _check(L, L.pdmpc_reachable_set_coupling(handle.h, n, *ptrs), "pdmpc_reachable_set_coupling")
+    else:
+        ps, keep = pack_local_sets(local_sets)
+        rc = L.pdmpc_reachable_set_coupling_host(len(local_sets), len(local_sets[0]), C.byref(ps), n, *ptrs)
+        del keep
+        if rc != 0:
+            raise BackendError("pdmpc_reachable_set_coupling_host failed with status %d" % rc)
+    return adj[: n * n].reshape(n, n), area[: n * n].reshape(n, n)
 
 
 def load_library(path=None):
@@ -201,6 +267,13 @@ def load_library(path=None):
     L.pdmpc_debug_progress.argtypes = [H, C.c_int32, C.POINTER(C.c_uint32)]
     L.pdmpc_unique_priorities.argtypes = [H, C.c_int32, abi.c_uint8_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), abi.c_int32_p]
     L.pdmpc_unique_priorities_host.argtypes = [C.c_int32, abi.c_uint8_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), abi.c_int32_p]
+    L.pdmpc_local_reachable_sets.argtypes = [C.POINTER(abi.Mpa), C.c_int32, abi.c_int32_p, abi.c_double_p, abi.c_double_p]
+    L.pdmpc_upload_reachable_sets.argtypes = [H, C.c_int32, C.c_int32, C.POINTER(abi.PolygonSet)]
+    L.pdmpc_reachable_set_coupling.argtypes = [H, C.c_int32] + [abi.c_double_p] * 4 + [abi.c_int32_p, abi.c_uint8_p, abi.c_double_p]
+    L.pdmpc_reachable_set_coupling_host.argtypes = [C.c_int32, C.c_int32, C.POINTER(abi.PolygonSet), C.c_int32] + [abi.c_double_p] * 4 + [abi.c_int32_p, abi.c_uint8_p, abi.c_double_p]
+    L.pdmpc_reachable_set_coupling_kernel_ms.argtypes = [H, abi.c_double_p]
+    L.pdmpc_controller_set_reachability.argtypes = [H, C.POINTER(abi.Mpa)]
+    L.pdmpc_controller_set_parallel_coupling.argtypes = [H, C.c_int32]
     L.pdmpc_last_error.restype = C.c_char_p
     L.pdmpc_version.restype = C.c_char_p
     for name in EXPORTS:
@@ -423,6 +496,21 @@ class Handle:
         _check(self.L, self.L.pdmpc_plan_joint(self.h, len(problems), off.ctypes.data_as(abi.c_int32_p), arr, abi.out_ptr(out)), "pdmpc_plan_joint")
         del keep
         return self._checked(out[:n])
+
+    def upload_reachable_sets(self, local_sets):
+        """pdmpc_upload_reachable_sets: the automaton's local hulls ([trim][k] (2, m), e.g. mpa.local_reachable_sets_conv)."""
+        ps, keep = pack_local_sets(local_sets)
+        _check(self.L, self.L.pdmpc_upload_reachable_sets(self.h, len(local_sets), len(local_sets[0]), C.byref(ps)), "pdmpc_upload_reachable_sets")
+        del keep
+
+    def reachable_set_coupling(self, x, y, yaw, trim):
+        """ReachableSetCoupler.couple on this handle's device (pdmpc_reachable_set_coupling) -> (adjacency (n, n) uint8, areas (n, n))."""
+        return reachable_set_coupling_call(None, x, y, yaw, trim, handle=self)
+
+    def reachable_set_coupling_kernel_ms(self):
+        ms = C.c_double(0.0)
+        _check(self.L, self.L.pdmpc_reachable_set_coupling_kernel_ms(self.h, C.byref(ms)), "pdmpc_reachable_set_coupling_kernel_ms")
+        return ms.value
 
     def unique_priorities(self, adjacency, max_out):
         """Prioritizer.unique_priorities on this handle's device (pdmpc_unique_priorities) -> (priorities n x K, masks [K])."""

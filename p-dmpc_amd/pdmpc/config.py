@@ -48,6 +48,10 @@ class Config:
     recursive_feasibility: bool = True  # Config.m:47
     time_per_tick: float = 0.01  # Config.m:48
     offset: float = 0.01  # Config.m:49
+    # Config.m:45 (isDealPredictionInconsistency): a parallel predecessor enters the search as its Hp reachable sets, not as its
+    # previous plan shifted by one step (PrioritizedController.m:29-33, 391-407).  The reference's default is true; this backend keeps
+    # false so that configurations written before the feature existed plan as they did.
+    is_deal_prediction_inconsistency: bool = False
     # backend sizing (no reference counterpart)
     device: int = 0
     max_nodes: int = 0

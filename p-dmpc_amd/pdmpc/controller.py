@@ -4,7 +4,8 @@ Restates what the reference does around `run_optimizer` for prioritized planning
 be produced and timed without MATLAB:
 
     traffic info per step        HighLevelController.update_controlled_vehicles_traffic_info (HighLevelController.m:167-270)
-    coupling                     Coupler (full_coupling: Coupler.m:31-32; distance: DistanceCoupler.m:15-50)
+    coupling                     Coupler (full_coupling: Coupler.m:31-32; distance: DistanceCoupler.m:15-50;
+                                 reachable_set: ReachableSetCoupler.m:5-56, reachability.py)
     priorities -> DAG            ConstantPrioritizer.m:14-20, Prioritizer.directed_coupling_from_priorities (Prioritizer.m:64-77)
     computation levels           utility/kahn.m:1-24
     level loop                   PrioritizedSequentialController.controller (PrioritizedSequentialController.m:77-94)
@@ -131,6 +132,15 @@ class PrioritizedSequentialController:
             self.v_ref[i] = v_ref
             if o.scenario_type != ScenarioType.circle and self.boundary_provider is not None:
                 self.boundary[i] = self.boundary_provider(i, veh, points_index, cpi)
+        # HighLevelController.m:219-263: the Hp reachable sets at the vehicle's pose, closed; only when a feature reads them (the
+        # lanelet bounding of :241-246 is not applied)
+        self.reachable_sets = [None] * n
+        if self.coupling == "reachable_set" or o.is_deal_prediction_inconsistency:
+            from .reachability import reachable_sets_at_pose
+
+            local = self.mpa.local_reachable_sets_conv
+            for i, m in enumerate(self.meas):
+                self.reachable_sets[i] = reachable_sets_at_pose(local, m.x, m.y, m.yaw, int(self.trims[i]))
 
     def _couple(self):
         n = self.n
@@ -146,6 +156,10 @@ class PrioritizedSequentialController:
                     d = math.hypot(self.x0[a, 0] - self.x0[b, 0], self.x0[a, 1] - self.x0[b, 1])
                     adj[a, b] = adj[b, a] = int(d <= max_distance)
             return adj
+        if self.coupling == "reachable_set":  # ReachableSetCoupler.m:5-56 on the step-Hp sets
+            from .reachability import reachable_set_coupling
+
+            return reachable_set_coupling([r[-1] for r in self.reachable_sets])[0]
         raise ValueError(self.coupling)
 
     # ---- PrioritizedController.plan: obstacle assembly (PrioritizedController.m:297-324)
@@ -163,6 +177,8 @@ class PrioritizedSequentialController:
                 if device_handoff:
                     continue
                 dyn.append(list(self.infos[j].shapes))  # this step's /vehicle_prediction :476-491
+            elif o.is_deal_prediction_inconsistency:  # parallel_coupling_reachability :391-407 (from the first step on)
+                dyn.append(list(self.reachable_sets[j]))
             else:
                 old = self.info_old[j]  # parallel_coupling_previous_trajectory :409-447
                 if old is not None and self.k > 1:

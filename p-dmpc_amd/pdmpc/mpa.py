@@ -12,8 +12,8 @@ module regenerates the fields the optimizer reads:
 
 The ODE is integrated with classical RK4 on 50 sub-steps per tick (global error ~1e-15), where the
 reference uses ode45 at RelTol = AbsTol = 1e-8: tables agree with MATLAB's to ~1e-8.  They are *inputs*
-of the hot path, so kernel-vs-oracle parity does not depend on that difference.  Reachable sets
-(MotionPrimitiveAutomaton.m:252-394) are used only by the reference's coupler and are out of scope.
+of the hot path, so kernel-vs-oracle parity does not depend on that difference.  The convexified local reachable sets
+(reachability_analysis_offline_DP, MotionPrimitiveAutomaton.m:394-647) are computed lazily by reachability.py.
 """
 import math
 from dataclasses import dataclass
@@ -257,6 +257,17 @@ class MotionPrimitiveAutomaton:
                 T[:, dist > k_to_go, k - 1] = 0
         self.transition_matrix_single = T
         self.adjacency = adjacency
+        self._local_reachable_sets_conv = None
+
+    @property
+    def local_reachable_sets_conv(self):
+        """[trim][k] (2, m) convex hulls of the area reachable at step k+1 (MotionPrimitiveAutomaton.m:394-647, reachability.py);
+        computed on first use and kept with the automaton."""
+        if self._local_reachable_sets_conv is None:
+            from .reachability import local_reachable_sets_conv
+
+            self._local_reachable_sets_conv = local_reachable_sets_conv(self)
+        return self._local_reachable_sets_conv
 
     def get_max_speed_of_mpa(self) -> float:  # :182-185
         return max(t.speed for t in self.trims)

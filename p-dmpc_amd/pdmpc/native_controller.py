@@ -1,7 +1,7 @@
 """ctypes wrapper of the native step controller (csrc/step_controller.cpp, declared in include/pdmpc.h).
 
 `NativeController` is the C++ twin of `pdmpc.controller.PrioritizedSequentialController` (constant and colouring priorities,
-full / distance coupling, GreedyCutter grouping): a whole MPC time step — traffic info, coupling, levels, obstacle assembly,
+full / distance / reachable-set coupling, parallel predecessors by previous plan or by reachable sets, GreedyCutter grouping): a whole MPC time step — traffic info, coupling, levels, obstacle assembly,
 one kernel launch, fallbacks, plant update — is one C call (`pdmpc_controller_step`), so a closed loop has no interpreter
 on its critical path.  The scenario is handed over once as flat arrays.
 """
@@ -13,7 +13,8 @@ from . import abi
 from .backend import BackendError, load_library
 from .config import ConstraintFromSuccessor
 
-COUPLING = {"full": 0, "distance": 1, "none": 2}
+COUPLING = {"full": 0, "distance": 1, "none": 2, "reachable_set": 3}
+PARALLEL_PREVIOUS_TRAJECTORY, PARALLEL_REACHABLE_SETS = 0, 1
 PRIORITY = {"constant": 0, "coloring": 1}
 WEIGHT = {"distance": 0, "constant": 1}
 SUCCESSOR = {ConstraintFromSuccessor.none: 0, ConstraintFromSuccessor.area_of_standstill: 1, ConstraintFromSuccessor.area_of_previous_trajectory: 2}
@@ -153,6 +154,13 @@ class NativeController:
         rc = self.L.pdmpc_controller_create(handle.h if handle is not None else None, C.byref(cfg), C.byref(s), C.byref(self.c))
         self._check(rc, "pdmpc_controller_create")
         del keep
+        if coupling == "reachable_set" or options.is_deal_prediction_inconsistency:
+            # the automaton's local reachable sets, computed natively (and uploaded to the handle's device, if any)
+            ms, mkeep = abi.pack_mpa(mpa)
+            self._check(self.L.pdmpc_controller_set_reachability(self.c, C.byref(ms)), "pdmpc_controller_set_reachability")
+            del mkeep
+        if options.is_deal_prediction_inconsistency:
+            self._check(self.L.pdmpc_controller_set_parallel_coupling(self.c, PARALLEL_REACHABLE_SETS), "pdmpc_controller_set_parallel_coupling")
 
     def _check(self, rc, what):
         if rc != 0:
