@@ -393,6 +393,30 @@ int pdmpc_reachable_set_coupling_host(int32_t n_trims, int32_t Hp, const pdmpc_p
                                       const double* cos_yaw, const double* sin_yaw, const int32_t* trim, uint8_t* adjacency, double* area);
 /* kernel time (HIP events, ms) of the last pdmpc_reachable_set_coupling */
 int pdmpc_reachable_set_coupling_kernel_ms(pdmpc_handle* handle, double* ms);
+/* Lanelet bounding of the reachable sets (bound_reachable_sets.m, HighLevelController.m:241-246; the rules are in
+ * include/pdmpc_geometry.h).  Vehicle v's sets at its pose (x, y, yaw, 1-based trim, as for the coupler) are
+ * intersected with lanelet_polygons polygon v: its raw predicted-lanelet polygon (left boundary, then the reversed right boundary;
+ * 0 vertices: not bounded).  all_steps != 0: sets of steps 1 .. Hp, polygon v * Hp + k; all_steps == 0: step Hp only, polygon v.
+ * Every result is closed (first vertex repeated).  offset (one entry more than polygons) is always written; out_x / out_y
+ * (capacity entries each) and flags (PDMPC_BOUND_*, one per polygon, or NULL) only if the result fits, PDMPC_ERR_CAPACITY otherwise
+ * (the offsets size a second call).  A lanelet polygon over PDMPC_LANELET_POLY_MAX_COLS vertices, or a bounded set over
+ * PDMPC_BOUNDED_MAX_COLS (closing vertex included), is PDMPC_ERR_CAPACITY as well. */
+#define PDMPC_LANELET_POLY_MAX_COLS 512
+#define PDMPC_BOUNDED_MAX_COLS 1024
+int pdmpc_bound_reachable_sets(pdmpc_handle* handle, int32_t n, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw,
+                               const int32_t* trim, const pdmpc_polygon_set* lanelet_polygons, int32_t all_steps, int32_t capacity, int32_t* offset,
+                               double* out_x, double* out_y, uint8_t* flags);
+int pdmpc_bound_reachable_sets_host(int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* local_sets, int32_t n, const double* x, const double* y,
+                                    const double* cos_yaw, const double* sin_yaw, const int32_t* trim, const pdmpc_polygon_set* lanelet_polygons,
+                                    int32_t all_steps, int32_t capacity, int32_t* offset, double* out_x, double* out_y, uint8_t* flags);
+/* ReachableSetCoupler.couple on the bounded step-Hp sets of the last successful pdmpc_bound_reachable_sets, on the device (the sets
+ * never leave it): the box pre-filter, then the overlap area of two simple polygons (pdmpc_edge_overlap_term) for every pair that
+ * passes it, coupled iff it exceeds 1e-3.  adjacency / area as for pdmpc_reachable_set_coupling. */
+int pdmpc_bounded_set_coupling(pdmpc_handle* handle, uint8_t* adjacency, double* area);
+/* ... its host twin for any n simple clockwise polygons (closed or open) */
+int pdmpc_polygon_set_coupling_host(const pdmpc_polygon_set* sets, int32_t n, uint8_t* adjacency, double* area);
+/* kernel times (HIP events, ms) of the last pdmpc_bound_reachable_sets and pdmpc_bounded_set_coupling: ms2[0] bounding, ms2[1] coupling */
+int pdmpc_bounded_reachable_kernel_ms(pdmpc_handle* handle, double* ms2);
 
 /* ---- the caller's side of the boundary, natively (csrc/step_controller.cpp) ----
  * One MPC time step of the prioritized sequential controller around pdmpc_plan_step, without any interpreter in the loop:
@@ -516,6 +540,11 @@ const char* pdmpc_controller_last_error(void);
  * coupling runs on the device (pdmpc_reachable_set_coupling), without one on the host twin (pdmpc_reachable_set_coupling_host). */
 int pdmpc_controller_set_reachability(pdmpc_controller* c, const pdmpc_mpa* mpa);
 int pdmpc_controller_set_parallel_coupling(pdmpc_controller* c, int32_t mode); /* PDMPC_PARALLEL_*, default PREVIOUS_TRAJECTORY */
+/* on != 0: the reachable sets a step computes (for PDMPC_COUPLING_REACHABLE_SET or PDMPC_PARALLEL_REACHABLE_SETS) are bounded by every
+ * vehicle's predicted lanelets (pdmpc_bound_reachable_sets on the device with a handle, its host twin without one) and the coupler
+ * runs on the bounded step-Hp sets (pdmpc_bounded_set_coupling / pdmpc_polygon_set_coupling_host).  Vehicles without lanelets
+ * (the circle scenario) are not bounded.  Default off. */
+int pdmpc_controller_set_lanelet_bounding(pdmpc_controller* c, int32_t on);
 
 /* ---- several GPUs behind the same boundary (csrc/group.cpp) ----
  * The reference's vehicles exchange their solved areas after every computation level: each publishes a Predictions message that every

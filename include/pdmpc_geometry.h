@@ -70,4 +70,335 @@ PDMPC_HD static inline int pdmpc_boxes_overlap(const double* bi, const double* b
     return !(bi[0] >= bj[1] || bi[2] >= bj[3] || bi[1] <= bj[0] || bi[3] <= bj[2]);
 }
 
+/* ---- lanelet bounding of the reachable sets (bound_reachable_sets.m, HighLevelController.m:241-246) ----
+ *
+ * K is a vehicle's convex reachable set at its pose (clockwise, open), L its predicted-lanelet polygon (the left boundary, then the
+ * reversed right boundary; get_lanelets_boundary.m:69-74), made clockwise by pdmpc_lanelet_polygon_normalize.  The bounded set is
+ * the region of K ∩ L that pdmpc_bound_region keeps:
+ *   - the parts of L's edges strictly inside K (Cyrus–Beck, pdmpc_clip_edge_t) form chains: entry point, the L vertices inside,
+ *     exit point.  Consecutive edges e, e + 1 belong to one chain iff both have a part inside, e's part ends at t = 1 and e + 1's
+ *     starts at t = 0; every other part ends with an exit and starts with an entry.  A part of zero length does not exist
+ *     (tmin < tmax), so chains of zero length never arise; an L edge along a K edge (either direction) has no part inside.
+ *   - entries and exits lie on ∂K at (K edge k, parameter s in [0, 1)): k is the edge whose line the point is farthest outside of
+ *     (the first on a tie), s its projection onto that edge clamped to [0, 1), s = 1 meaning (k + 1, 0) (pdmpc_boundary_position).
+ *   - every exit links to the next entry clockwise along ∂K (an entry at the exit's own position included), and the K vertices in
+ *     between are inserted (the last one left out if the entry sits at s = 0 on it).  The chains are visited in the order of the
+ *     L edge they start on; each not yet visited one starts a region, which follows the links until it meets a visited chain.
+ *   - a region with fewer than 3 vertices is dropped.  Of the rest the one with the most vertices is kept, on a tie the one whose
+ *     first chain starts on the smaller L edge; it starts at that chain's entry point.  More than one region sets
+ *     PDMPC_BOUND_MULTIPLE (bound_reachable_sets.m:24-38).
+ *   - no chain: if every L edge lies inside K and all of them link, the result is L (from its first vertex); otherwise K if the
+ *     mean of K's vertices lies inside L (crossing-number test), and if not, K ∩ L is empty: K is returned with
+ *     PDMPC_BOUND_RESTORED (bound_reachable_sets.m:40-46), as it is when every region was dropped.
+ *   - K or L with fewer than 3 vertices: K, unflagged.
+ * The result is closed by repeating its first vertex (HighLevelController.m:258-263).
+ */
+#define PDMPC_BOUND_RESTORED 1u /* K ∩ L was empty: K returned unchanged */
+#define PDMPC_BOUND_MULTIPLE 2u /* K ∩ L had more than one region: the one with the most vertices was kept */
+
+/* The clockwise lanelet polygon of the raw polygon (ix, iy)[0 .. n): a vertex equal to the previous one is dropped, so are trailing
+ * vertices equal to the first; if the signed area (shoelace sum in vertex order, running) is positive, the order is reversed.
+ * Writes (ox, oy) (n entries suffice) and returns the vertex count. */
+PDMPC_HD static inline int pdmpc_lanelet_polygon_normalize(const double* ix, const double* iy, int n, double* ox, double* oy) {
+    int m = 0;
+    for (int i = 0; i < n; ++i) {
+        if (m > 0 && ix[i] == ox[m - 1] && iy[i] == oy[m - 1]) continue;
+        ox[m] = ix[i];
+        oy[m] = iy[i];
+        ++m;
+    }
+    while (m > 1 && ox[m - 1] == ox[0] && oy[m - 1] == oy[0]) --m;
+    double s = 0.0;
+    for (int i = 0; i < m; ++i) {
+        const int j = i + 1 == m ? 0 : i + 1;
+        s = s + (ox[i] * oy[j] - ox[j] * oy[i]);
+    }
+    if (s > 0.0) {
+        for (int i = 0, j = m - 1; i < j; ++i, --j) {
+            const double tx = ox[i], ty = oy[i];
+            ox[i] = ox[j];
+            oy[i] = oy[j];
+            ox[j] = tx;
+            oy[j] = ty;
+        }
+    }
+    return m;
+}
+
+/* Cyrus–Beck of (ax, ay) -> (bx, by) against the clockwise convex polygon (qx, qy)[0 .. m), strictly inside: the parameters
+ * [*tmin, *tmax] of the part inside (it exists iff *tmin < *tmax; an edge parallel to a polygon edge and not strictly inside its
+ * half-plane gets 1, 0).  The same arithmetic as pdmpc_clip_edge with strict = 1. */
+PDMPC_HD static inline void pdmpc_clip_edge_t(double ax, double ay, double bx, double by, const double* qx, const double* qy, int m, double* tmin_out,
+                                              double* tmax_out) {
+    const double dx = bx - ax, dy = by - ay;
+    double tmin = 0.0, tmax = 1.0;
+    for (int k = 0; k < m; ++k) {
+        const int k1 = k + 1 == m ? 0 : k + 1;
+        const double ux = qx[k1] - qx[k], uy = qy[k1] - qy[k];
+        const double num = ux * (ay - qy[k]) - uy * (ax - qx[k]);
+        const double den = ux * dy - uy * dx;
+        if (den == 0.0) {
+            if (num >= 0.0) {
+                tmin = 1.0;
+                tmax = 0.0;
+                break;
+            }
+        } else {
+            const double t = -num / den;
+            if (den < 0.0) {
+                if (t > tmin) tmin = t;
+            } else {
+                if (t < tmax) tmax = t;
+            }
+        }
+    }
+    *tmin_out = tmin;
+    *tmax_out = tmax;
+}
+
+/* position of the point (px, py) on the boundary of the clockwise convex polygon (qx, qy)[0 .. m) (see above) */
+PDMPC_HD static inline void pdmpc_boundary_position(double px, double py, const double* qx, const double* qy, int m, int* k_out, double* s_out) {
+    int best = 0;
+    double bv = 0.0;
+    for (int k = 0; k < m; ++k) {
+        const int k1 = k + 1 == m ? 0 : k + 1;
+        const double v = (qx[k1] - qx[k]) * (py - qy[k]) - (qy[k1] - qy[k]) * (px - qx[k]);
+        if (k == 0 || v > bv) {
+            bv = v;
+            best = k;
+        }
+    }
+    const int b1 = best + 1 == m ? 0 : best + 1;
+    const double ux = qx[b1] - qx[best], uy = qy[b1] - qy[best];
+    double s = ((px - qx[best]) * ux + (py - qy[best]) * uy) / (ux * ux + uy * uy);
+    if (s < 0.0) s = 0.0;
+    if (s >= 1.0) {
+        best = b1;
+        s = 0.0;
+    }
+    *k_out = best;
+    *s_out = s;
+}
+
+/* The scratch of pdmpc_bound_region: one entry per chain (at most the number of L edges) */
+typedef struct pdmpc_bound_chains {
+    int *start, *end, *kin, *kout, *next, *region;
+    double *sin, *sout;
+} pdmpc_bound_chains;
+
+/* K steps clockwise along ∂K from chain c's exit to chain d's entry, and the K vertices inserted on the way */
+PDMPC_HD static inline int pdmpc_bound_link_steps(const pdmpc_bound_chains* C, int c, int d, int m) {
+    int dk = C->kin[d] - C->kout[c];
+    if (dk < 0) dk += m;
+    if (dk == 0 && C->sin[d] < C->sout[c]) dk = m;
+    return dk;
+}
+PDMPC_HD static inline int pdmpc_bound_link_vertices(const pdmpc_bound_chains* C, int c, int d, int m) {
+    const int dk = pdmpc_bound_link_steps(C, c, d, m);
+    return dk > 0 && C->sin[d] == 0.0 ? dk - 1 : dk;
+}
+
+/* pdmpc_bound_region's output: writes vertex *count of (ox, oy) if it fits the capacity cap */
+PDMPC_HD static inline void pdmpc_bound_put(double x, double y, double* ox, double* oy, int cap, int* count) {
+    if (*count < cap) {
+        ox[*count] = x;
+        oy[*count] = y;
+    }
+    *count += 1;
+}
+
+/* The bounded set of K = (kx, ky)[0 .. m) and the normalized L = (lx, ly)[0 .. nl), given the strict Cyrus–Beck parameters
+ * tmin[e], tmax[e] of every L edge e (pdmpc_clip_edge_t against K): the kept region, closed, into (ox, oy) (capacity cap),
+ * *count = its vertex count (closing vertex included; written even if it exceeds cap), *flags = PDMPC_BOUND_*.  Returns 0, or 1
+ * if the result did not fit (nothing beyond cap is written). */
+PDMPC_HD static inline int pdmpc_bound_region(const double* kx, const double* ky, int m, const double* lx, const double* ly, int nl, const double* tmin,
+                                              const double* tmax, pdmpc_bound_chains* C, double* ox, double* oy, int cap, int* count,
+                                              unsigned* flags) {
+    *flags = 0u;
+    *count = 0;
+    int mode = 0; /* 0: K, 1: L, 2: the kept region */
+    int n_chains = 0, best = -1, best_steps = 0;
+    if (m >= 3 && nl >= 3) {
+        int all_linked = 1;
+        for (int e = 0; e < nl; ++e) {
+            const int e1 = e + 1 == nl ? 0 : e + 1;
+            const int link = tmin[e] < tmax[e] && tmin[e1] < tmax[e1] && tmax[e] == 1.0 && tmin[e1] == 0.0;
+            C->end[e] = link; /* (scratch: the link flags, overwritten below) */
+            if (!link) all_linked = 0;
+        }
+        if (all_linked) {
+            mode = 1;
+        } else {
+            for (int e = 0; e < nl; ++e) {
+                const int ep = e == 0 ? nl - 1 : e - 1;
+                if (tmin[e] < tmax[e] && !C->end[ep]) C->kin[n_chains++] = e;
+            }
+            for (int c = 0; c < n_chains; ++c) C->start[c] = C->kin[c];
+            for (int c = 0; c < n_chains; ++c) { /* the chain's last edge: follow the links (C->end still holds them) */
+                int e = C->start[c];
+                while (C->end[e]) e = e + 1 == nl ? 0 : e + 1;
+                C->next[c] = e;
+            }
+            for (int c = 0; c < n_chains; ++c) {
+                const int s = C->start[c], s1 = s + 1 == nl ? 0 : s + 1;
+                const int e = C->next[c], e1 = e + 1 == nl ? 0 : e + 1;
+                C->end[c] = e;
+                const double sdx = lx[s1] - lx[s], sdy = ly[s1] - ly[s];
+                const double edx = lx[e1] - lx[e], edy = ly[e1] - ly[e];
+                pdmpc_boundary_position(lx[s] + tmin[s] * sdx, ly[s] + tmin[s] * sdy, kx, ky, m, &C->kin[c], &C->sin[c]);
+                pdmpc_boundary_position(lx[e] + tmax[e] * edx, ly[e] + tmax[e] * edy, kx, ky, m, &C->kout[c], &C->sout[c]);
+            }
+            for (int c = 0; c < n_chains; ++c) { /* the next entry clockwise along ∂K */
+                int bd = -1, bk = 0;
+                for (int d = 0; d < n_chains; ++d) {
+                    const int dk = pdmpc_bound_link_steps(C, c, d, m);
+                    if (bd < 0 || dk < bk || (dk == bk && C->sin[d] < C->sin[bd])) {
+                        bd = d;
+                        bk = dk;
+                    }
+                }
+                C->next[c] = bd;
+                C->region[c] = 0;
+            }
+            int n_regions = 0, best_count = 0;
+            for (int c = 0; c < n_chains; ++c) {
+                if (C->region[c]) continue;
+                int cnt = 0, steps = 0, cur = c;
+                do {
+                    C->region[cur] = c + 1;
+                    int links = C->end[cur] - C->start[cur];
+                    if (links < 0) links += nl;
+                    cnt += 2 + links + pdmpc_bound_link_vertices(C, cur, C->next[cur], m);
+                    ++steps;
+                    cur = C->next[cur];
+                } while (!C->region[cur]);
+                if (cnt >= 3) {
+                    ++n_regions;
+                    if (cnt > best_count) {
+                        best_count = cnt;
+                        best = c;
+                        best_steps = steps;
+                    }
+                }
+            }
+            if (n_chains == 0) {
+                /* no L edge reaches into K: K ⊂ L, or K ∩ L is empty */
+                double cx = 0.0, cy = 0.0;
+                for (int q = 0; q < m; ++q) {
+                    cx = cx + kx[q];
+                    cy = cy + ky[q];
+                }
+                cx = cx / (double)m;
+                cy = cy / (double)m;
+                int inside = 0;
+                for (int i = 0; i < nl; ++i) {
+                    const int j = i + 1 == nl ? 0 : i + 1;
+                    if ((ly[i] > cy) != (ly[j] > cy)) {
+                        const double xi = lx[i] + (cy - ly[i]) * (lx[j] - lx[i]) / (ly[j] - ly[i]);
+                        if (cx < xi) inside = !inside;
+                    }
+                }
+                if (!inside) *flags |= PDMPC_BOUND_RESTORED;
+            } else if (n_regions == 0) {
+                *flags |= PDMPC_BOUND_RESTORED;
+            } else {
+                mode = 2;
+                if (n_regions > 1) *flags |= PDMPC_BOUND_MULTIPLE;
+            }
+        }
+    }
+    if (mode == 0) {
+        for (int q = 0; q < m; ++q) pdmpc_bound_put(kx[q], ky[q], ox, oy, cap, count);
+    } else if (mode == 1) {
+        for (int q = 0; q < nl; ++q) pdmpc_bound_put(lx[q], ly[q], ox, oy, cap, count);
+    } else {
+        int cur = best;
+        for (int r = 0; r < best_steps; ++r) {
+            const int s = C->start[cur], s1 = s + 1 == nl ? 0 : s + 1;
+            const int e = C->end[cur], e1 = e + 1 == nl ? 0 : e + 1;
+            pdmpc_bound_put(lx[s] + tmin[s] * (lx[s1] - lx[s]), ly[s] + tmin[s] * (ly[s1] - ly[s]), ox, oy, cap, count);
+            int links = e - s;
+            if (links < 0) links += nl;
+            for (int q = 1; q <= links; ++q) {
+                const int v = (s + q) % nl;
+                pdmpc_bound_put(lx[v], ly[v], ox, oy, cap, count);
+            }
+            pdmpc_bound_put(lx[e] + tmax[e] * (lx[e1] - lx[e]), ly[e] + tmax[e] * (ly[e1] - ly[e]), ox, oy, cap, count);
+            const int nx = C->next[cur], nk = pdmpc_bound_link_vertices(C, cur, nx, m);
+            for (int q = 1; q <= nk; ++q) {
+                const int v = (C->kout[cur] + q) % m;
+                pdmpc_bound_put(kx[v], ky[v], ox, oy, cap, count);
+            }
+            cur = nx;
+        }
+    }
+    if (*count > 0) {
+        const double fx = *count <= cap ? ox[0] : 0.0, fy = *count <= cap ? oy[0] : 0.0;
+        pdmpc_bound_put(fx, fy, ox, oy, cap, count);
+    }
+    return *count > cap ? 1 : 0;
+}
+
+/* ---- overlap area of two simple polygons (the coupler on bounded sets) ----
+ * Green's theorem over the boundary of A ∩ B, both clockwise: every edge a -> b of A contributes (the length of its part inside B,
+ * as a fraction of the edge) x cross(a, b), and so does every edge of B by its part inside A; the area is minus half the sum.  The
+ * fraction needs no sorting: (Σ t over the edge's exits from the other polygon − Σ t over its entries + [the point just before b
+ * lies inside]), t in (0, 1), the last term being the parity of the crossings at t >= 1 (the ray on from b).  A crossing is a
+ * polygon edge c -> e whose ends lie on different sides of the line a -> b; an end on the line counts as left of it for A's edges
+ * (the edge taken a hair to its right, into A: an A edge along a B edge in the same direction lies inside B) and as right of it
+ * for B's edges (taken a hair to their left); the crossing's t is the projection of that end if one end lies on the line, the
+ * lines' intersection otherwise.  For B's edges the part along an A edge in the opposite direction is taken off again: B's edges
+ * count only strictly inside A, so a shared edge is counted once and an edge where the two only touch not at all. */
+PDMPC_HD static inline double pdmpc_edge_inside_fraction(double ax, double ay, double bx, double by, const double* px, const double* py, int mp, int strict) {
+    const double dx = bx - ax, dy = by - ay;
+    const double dd = dx * dx + dy * dy;
+    if (dd == 0.0) return 0.0;
+    double acc = 0.0, corr = 0.0;
+    int par = 0;
+    for (int k = 0; k < mp; ++k) {
+        const int k1 = k + 1 == mp ? 0 : k + 1;
+        const double cx = px[k], cy = py[k], ex = px[k1], ey = py[k1];
+        const double oc = dx * (cy - ay) - dy * (cx - ax);
+        const double oe = dx * (ey - ay) - dy * (ex - ax);
+        const int lc = strict ? oc > 0.0 : oc >= 0.0;
+        const int le = strict ? oe > 0.0 : oe >= 0.0;
+        if (lc != le) {
+            double t;
+            if (oc == 0.0) {
+                t = ((cx - ax) * dx + (cy - ay) * dy) / dd;
+            } else if (oe == 0.0) {
+                t = ((ex - ax) * dx + (ey - ay) * dy) / dd;
+            } else {
+                const double wx = ex - cx, wy = ey - cy;
+                t = ((cx - ax) * wy - (cy - ay) * wx) / (dx * wy - dy * wx);
+            }
+            if (t >= 1.0) {
+                par ^= 1;
+            } else if (t > 0.0) {
+                acc = acc + (lc ? t : -t); /* c left, e right: an exit */
+            }
+        } else if (strict && oc == 0.0 && oe == 0.0) {
+            const double wx = ex - cx, wy = ey - cy;
+            if (dx * wx + dy * wy < 0.0) {
+                const double tc = ((cx - ax) * dx + (cy - ay) * dy) / dd, te = ((ex - ax) * dx + (ey - ay) * dy) / dd;
+                double lo = tc < te ? tc : te, hi = tc < te ? te : tc;
+                if (lo < 0.0) lo = 0.0;
+                if (hi > 1.0) hi = 1.0;
+                if (hi > lo) corr = corr + (hi - lo);
+            }
+        }
+    }
+    double f = acc + (par ? 1.0 : 0.0);
+    f = f - corr;
+    return f;
+}
+
+/* ... the contribution of A's edges (strict = 0, against B) or B's (strict = 1, against A), edge e, coordinates relative to A's first
+ * vertex: the fraction times cross(a, b) */
+PDMPC_HD static inline double pdmpc_edge_overlap_term(const double* ax, const double* ay, int ma, int e, const double* px, const double* py, int mp, int strict) {
+    const int e1 = e + 1 == ma ? 0 : e + 1;
+    const double f = pdmpc_edge_inside_fraction(ax[e], ay[e], ax[e1], ay[e1], px, py, mp, strict);
+    return f * (ax[e] * ay[e1] - ax[e1] * ay[e]);
+}
+
 #endif /* PDMPC_GEOMETRY_H */

@@ -23,6 +23,7 @@
 
 #include "../../include/pdmpc.h"
 #include "mt19937ar.hpp"
+#include "../../include/pdmpc_geometry.h"
 #include "pdmpc_device.h"
 
 namespace {
@@ -346,6 +347,22 @@ struct pdmpc_handle {
     std::vector<int32_t> reach_off_host;
     hipEvent_t reach_ev[2] = {nullptr, nullptr};
     float reach_kernel_ms = 0.0f;
+    DevBuf<double> d_reach_all;        // every trim's local hulls of every step (x, then y), for pdmpc_bound_reachable_sets
+    DevBuf<int32_t> d_reach_all_off;   // [n_trims * Hp + 1]
+    int reach_all_tot = 0;
+    // pdmpc_bound_reachable_sets / pdmpc_bounded_set_coupling (bounded_kernel.hip): the sets of the last bound call stay here
+    bool bound_valid = false;
+    int bound_n = 0, bound_S = 0, bound_n_lan = 0;
+    DevBuf<unsigned char> d_bound_in;  // inputs [4 n] + trims [n] + lanelet offsets [n + 1] (8-aligned) + lanelet x, y
+    DevBuf<double> d_bound_sets;       // slots: x of every set, then y
+    DevBuf<int32_t> d_bound_n, d_bound_pairs;  // vertices per set | the pair list, then its counter
+    DevBuf<uint8_t> d_bound_flags;
+    DevBuf<double> d_bound_box;
+    DevBuf<unsigned char> d_bound_out; // adjacency [n x n] (8-aligned) + areas [n x n]
+    PinnedBuf<unsigned char> h_bound_in, h_bound_out;
+    PinnedBuf<double> h_bound_xy;
+    hipEvent_t bound_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    float bound_kernel_ms[2] = {0.0f, 0.0f};
     int device_share = 1;                // handles of one process that launch on this device side by side (pdmpc_set_device_share: a group's logical ranks)
     bool boards_dirty = true;            // the helper boards / the finished counter need clearing before the helper workgroups may read them
     uint32_t help_fin_total = 0;         // value of the finished counter once every launch so far has ended
@@ -1162,6 +1179,8 @@ int pdmpc_destroy(pdmpc_handle* h) {
     DeviceGuard device_guard__(h->cfg.device);
     for (hipEvent_t& e : h->reach_ev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t& e : h->bound_ev)
+        if (e) (void)hipEventDestroy(e);
     delete h;
     return PDMPC_OK;
 }
@@ -1824,6 +1843,19 @@ int pdmpc_upload_reachable_sets(pdmpc_handle* h, int32_t n_trims, int32_t Hp, co
         if (!e) HIPCHK(hipEventCreate(&e));
     HIPCHK(hipMemcpy(h->d_reach_local.p, xy.data(), xy.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->d_reach_off.p, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    // ... and every step's hulls for the lanelet bounding (pdmpc_bound_reachable_sets)
+    h->bound_valid = false;
+    const int all_tot = sets->offset[sets->n_polygons] - sets->offset[0];
+    std::vector<double> all_xy((size_t)2 * all_tot);
+    std::vector<int32_t> all_off((size_t)sets->n_polygons + 1);
+    for (int p = 0; p <= sets->n_polygons; ++p) all_off[p] = sets->offset[p] - sets->offset[0];
+    std::memcpy(all_xy.data(), sets->x + sets->offset[0], (size_t)all_tot * sizeof(double));
+    std::memcpy(all_xy.data() + all_tot, sets->y + sets->offset[0], (size_t)all_tot * sizeof(double));
+    if (h->d_reach_all.ensure_exact(all_xy.size()) || h->d_reach_all_off.ensure_exact(all_off.size()))
+        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the reachable-set table");
+    HIPCHK(hipMemcpy(h->d_reach_all.p, all_xy.data(), all_xy.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_reach_all_off.p, all_off.data(), all_off.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    h->reach_all_tot = all_tot;
     h->reach_off_host = off;
     h->reach_trims = n_trims;
     h->reach_Hp = Hp;
@@ -1877,6 +1909,168 @@ int pdmpc_reachable_set_coupling(pdmpc_handle* h, int32_t n, const double* x, co
     if (hipEventElapsedTime(&ms, h->reach_ev[0], h->reach_ev[1]) == hipSuccess) h->reach_kernel_ms = ms;
     std::memcpy(adjacency, h->h_reach_out.p, (size_t)n * n);
     if (area) std::memcpy(area, h->h_reach_out.p + (L.area - L.adj), (size_t)n * n * sizeof(double));
+    return PDMPC_OK;
+}
+
+// ---- lanelet bounding and the coupler on the bounded sets (bounded_kernel.hip)
+namespace {
+BoundArgs bound_args(pdmpc_handle* h, int n, int S, int n_lan) {
+    BoundArgs A;
+    unsigned char* in = h->d_bound_in.p;
+    const size_t lan_xy = align_up8((size_t)4 * n * sizeof(double) + (size_t)n * sizeof(int32_t) + (size_t)(n + 1) * sizeof(int32_t));
+    A.n = n;
+    A.S = S;
+    A.Hp = h->reach_Hp;
+    A.all_steps = S == h->reach_Hp && S > 1 ? 1 : 0;
+    A.local_x = h->d_reach_all.p;
+    A.local_y = h->d_reach_all.p + h->reach_all_tot;
+    A.local_off = h->d_reach_all_off.p;
+    A.in = (const double*)in;
+    A.trim = (const int32_t*)(in + (size_t)4 * n * sizeof(double));
+    A.lan_off = A.trim + n;
+    A.lan_x = (const double*)(in + lan_xy);
+    A.lan_y = A.lan_x + n_lan;
+    const size_t slots = (size_t)n * S * PDMPC_BOUND_SLOT;
+    A.set_x = h->d_bound_sets.p;
+    A.set_y = h->d_bound_sets.p + slots;
+    A.set_n = h->d_bound_n.p;
+    A.set_flags = h->d_bound_flags.p;
+    A.box = h->d_bound_box.p;
+    A.adjacency = h->d_bound_out.p;
+    A.area = (double*)(h->d_bound_out.p + align_up8((size_t)n * n));
+    A.pairs = h->d_bound_pairs.p;
+    A.n_pairs = h->d_bound_pairs.p + (n > 1 ? (size_t)n * (n - 1) / 2 : 0);
+    return A;
+}
+}  // namespace
+
+int pdmpc_bound_reachable_sets(pdmpc_handle* h, int32_t n, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw, const int32_t* trim,
+                               const pdmpc_polygon_set* lan, int32_t all_steps, int32_t capacity, int32_t* offset, double* out_x, double* out_y, uint8_t* flags) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    if (!h->has_reach) return fail(PDMPC_ERR_INVALID, "pdmpc_bound_reachable_sets before pdmpc_upload_reachable_sets");
+    if (n < 0 || !offset || !lan || lan->n_polygons != n || (n > 0 && (!x || !y || !cos_yaw || !sin_yaw || !trim || !lan->offset)))
+        return fail(PDMPC_ERR_INVALID, "pdmpc_bound_reachable_sets: bad argument");
+    if (n > h->max_vehicles) return fail(PDMPC_ERR_CAPACITY, "pdmpc_bound_reachable_sets: more vehicles than config.max_vehicles");
+    const int Hp = h->reach_Hp, S = all_steps ? Hp : 1;
+    h->bound_valid = false;
+    offset[0] = 0;
+    if (n == 0) {
+        h->bound_n = 0;
+        h->bound_S = S;
+        h->bound_valid = true;
+        return PDMPC_OK;
+    }
+    int n_lan = 0;
+    for (int v = 0; v < n; ++v) {
+        if (trim[v] < 1 || trim[v] > h->reach_trims) return fail(PDMPC_ERR_INVALID, "pdmpc_bound_reachable_sets: trim out of range");
+        const int nl = lan->offset[v + 1] - lan->offset[v];
+        if (nl < 0) return fail(PDMPC_ERR_INVALID, "pdmpc_bound_reachable_sets: bad lanelet offsets");
+        if (nl > PDMPC_LANELET_POLY_MAX_COLS) return fail(PDMPC_ERR_CAPACITY, "pdmpc_bound_reachable_sets: a lanelet polygon has more than PDMPC_LANELET_POLY_MAX_COLS vertices");
+        if (nl && (!lan->x || !lan->y)) return fail(PDMPC_ERR_INVALID, "pdmpc_bound_reachable_sets: null lanelet coordinates");
+        n_lan += nl;
+    }
+    ON_DEVICE(h->cfg.device);
+    const size_t lan_xy = align_up8((size_t)4 * n * sizeof(double) + (size_t)n * sizeof(int32_t) + (size_t)(n + 1) * sizeof(int32_t));
+    const size_t in_bytes = lan_xy + (size_t)2 * n_lan * sizeof(double);
+    const size_t sets = (size_t)n * S, max_pairs = (size_t)n * (n - 1) / 2;
+    const size_t out_bytes = align_up8((size_t)n * n) + (size_t)n * n * sizeof(double);
+    if (h->d_bound_in.ensure(in_bytes) || h->d_bound_sets.ensure(2 * sets * PDMPC_BOUND_SLOT) || h->d_bound_n.ensure(sets) || h->d_bound_flags.ensure(sets) ||
+        h->d_bound_box.ensure((size_t)4 * n) || h->d_bound_out.ensure(out_bytes) || h->d_bound_pairs.ensure(max_pairs + 1) || h->h_bound_in.ensure(in_bytes) ||
+        h->h_bound_out.ensure(out_bytes + sets * (sizeof(int32_t) + 1)))
+        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the lanelet bounding");
+    for (hipEvent_t& e : h->bound_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    // inputs: poses, 0-based trims, the normalized lanelet polygons (pdmpc_lanelet_polygon_normalize, as the host twin)
+    unsigned char* hin = h->h_bound_in.p;
+    std::memcpy(hin, x, (size_t)n * sizeof(double));
+    std::memcpy(hin + (size_t)n * sizeof(double), y, (size_t)n * sizeof(double));
+    std::memcpy(hin + (size_t)2 * n * sizeof(double), cos_yaw, (size_t)n * sizeof(double));
+    std::memcpy(hin + (size_t)3 * n * sizeof(double), sin_yaw, (size_t)n * sizeof(double));
+    int32_t* ht = (int32_t*)(hin + (size_t)4 * n * sizeof(double));
+    int32_t* hoff = ht + n;
+    double* hlx = (double*)(hin + lan_xy);
+    double* hly = hlx + n_lan;
+    hoff[0] = 0;
+    for (int v = 0; v < n; ++v) {
+        ht[v] = trim[v] - 1;
+        const int a = lan->offset[v], nl = lan->offset[v + 1] - a;
+        const int m = nl ? pdmpc_lanelet_polygon_normalize(lan->x + a, lan->y + a, nl, hlx + hoff[v], hly + hoff[v]) : 0;
+        hoff[v + 1] = hoff[v] + m;
+    }
+    const int n_norm = hoff[n];
+    if (n_norm != n_lan) {  // (duplicates dropped: x and y of the normalized polygons are contiguous again)
+        std::memmove(hlx + n_norm, hly, (size_t)n_norm * sizeof(double));
+    }
+    HIPCHK(hipMemcpyAsync(h->d_bound_in.p, hin, lan_xy + (size_t)2 * n_norm * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    const BoundArgs A = bound_args(h, n, S, n_norm);
+    HIPCHK(hipEventRecord(h->bound_ev[0], h->stream));
+    const int lrc = pdmpc_launch_bound_sets(&A, (void*)h->stream);
+    if (lrc) return fail(PDMPC_ERR_HIP, std::string("lanelet bounding kernel launch failed: ") + hipGetErrorString((hipError_t)lrc));
+    HIPCHK(hipEventRecord(h->bound_ev[1], h->stream));
+    int32_t* hn = (int32_t*)h->h_bound_out.p;
+    uint8_t* hf = (uint8_t*)(hn + sets);
+    HIPCHK(hipMemcpyAsync(hn, h->d_bound_n.p, sets * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(hf, h->d_bound_flags.p, sets, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(sync_stream(h));
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, h->bound_ev[0], h->bound_ev[1]) == hipSuccess) h->bound_kernel_ms[0] = ms;
+    bool over = false;
+    int maxc = 0;
+    for (size_t o = 0; o < sets; ++o) {
+        if (hf[o] & PDMPC_BOUND_OVERFLOW) over = true;
+        offset[o + 1] = offset[o] + hn[o];
+        maxc = std::max(maxc, (int)hn[o]);
+    }
+    if (over) return fail(PDMPC_ERR_CAPACITY, "pdmpc_bound_reachable_sets: a bounded set has more than PDMPC_BOUNDED_MAX_COLS vertices");
+    h->bound_n = n;
+    h->bound_S = S;
+    h->bound_n_lan = n_norm;
+    h->bound_valid = true;
+    if (!out_x || !out_y || capacity < offset[sets]) return fail(PDMPC_ERR_CAPACITY, "pdmpc_bound_reachable_sets: capacity too small for the bounded sets");
+    // read back the used part of every slot (a pitched copy), then pack
+    if (h->h_bound_xy.ensure(2 * sets * (size_t)maxc)) return fail(PDMPC_ERR_HIP, "hipHostMalloc failed for the bounded sets");
+    double* bx = h->h_bound_xy.p;
+    double* by = bx + sets * (size_t)maxc;
+    const size_t pitch = (size_t)PDMPC_BOUND_SLOT * sizeof(double), width = (size_t)maxc * sizeof(double);
+    HIPCHK(hipMemcpy2DAsync(bx, width, A.set_x, pitch, width, sets, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpy2DAsync(by, width, A.set_y, pitch, width, sets, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(sync_stream(h));
+    for (size_t o = 0; o < sets; ++o) {
+        std::memcpy(out_x + offset[o], bx + o * maxc, (size_t)hn[o] * sizeof(double));
+        std::memcpy(out_y + offset[o], by + o * maxc, (size_t)hn[o] * sizeof(double));
+    }
+    if (flags) std::memcpy(flags, hf, sets);
+    return PDMPC_OK;
+}
+
+int pdmpc_bounded_set_coupling(pdmpc_handle* h, uint8_t* adjacency, double* area) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    if (!adjacency) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling: null adjacency");
+    if (!h->bound_valid) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling without a successful pdmpc_bound_reachable_sets");
+    const int n = h->bound_n;
+    if (n == 0) return PDMPC_OK;
+    ON_DEVICE(h->cfg.device);
+    const BoundArgs A = bound_args(h, n, h->bound_S, h->bound_n_lan);
+    HIPCHK(hipMemsetAsync(A.n_pairs, 0, sizeof(int32_t), h->stream));
+    HIPCHK(hipEventRecord(h->bound_ev[2], h->stream));
+    const int lrc = pdmpc_launch_bounded_coupling(&A, (void*)h->stream);
+    if (lrc) return fail(PDMPC_ERR_HIP, std::string("bounded-set coupling kernel launch failed: ") + hipGetErrorString((hipError_t)lrc));
+    HIPCHK(hipEventRecord(h->bound_ev[3], h->stream));
+    const size_t area_at = align_up8((size_t)n * n);
+    const size_t out_bytes = area ? area_at + (size_t)n * n * sizeof(double) : (size_t)n * n;
+    HIPCHK(hipMemcpyAsync(h->h_bound_out.p, h->d_bound_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(sync_stream(h));
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, h->bound_ev[2], h->bound_ev[3]) == hipSuccess) h->bound_kernel_ms[1] = ms;
+    std::memcpy(adjacency, h->h_bound_out.p, (size_t)n * n);
+    if (area) std::memcpy(area, h->h_bound_out.p + area_at, (size_t)n * n * sizeof(double));
+    return PDMPC_OK;
+}
+
+int pdmpc_bounded_reachable_kernel_ms(pdmpc_handle* h, double* ms2) {
+    if (!h || !ms2) return fail(PDMPC_ERR_INVALID, "null argument");
+    ms2[0] = (double)h->bound_kernel_ms[0];
+    ms2[1] = (double)h->bound_kernel_ms[1];
     return PDMPC_OK;
 }
 

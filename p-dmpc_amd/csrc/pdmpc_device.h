@@ -313,11 +313,41 @@ struct ReachArgs {
     double* area;                 // [n * n] overlap area of every pair that passed the box test, 0 elsewhere
 };
 
+// Lanelet bounding and the coupler on the bounded sets (bounded_kernel.hip; include/pdmpc_geometry.h).  Set o = v * S + q holds vehicle v's
+// step (all_steps ? q + 1 : Hp) set in slot o of set_x / set_y (stride PDMPC_BOUND_SLOT), closed; every array is the handle's.
+#define PDMPC_BOUND_SLOT 1024       // = PDMPC_BOUNDED_MAX_COLS
+#define PDMPC_BOUND_LANELET_MAX 512 // = PDMPC_LANELET_POLY_MAX_COLS
+#define PDMPC_BOUND_OVERFLOW 0x80   // set_flags: the set did not fit its slot
+#define PDMPC_BOUND_PAIR_BLOCKS 2048 // workgroups of the pair pass (grid-stride over the survivors of the box test)
+struct BoundArgs {
+    int32_t n, S, Hp, all_steps;
+    const double* local_x;     // every trim's local hulls of every step, polygon trim * Hp + k, x then y
+    const double* local_y;
+    const int32_t* local_off;  // [n_trims * Hp + 1]
+    const double* in;          // [4 n]: x, y, cos(yaw), sin(yaw)
+    const int32_t* trim;       // [n] 0-based, checked on the host
+    const int32_t* lan_off;    // [n + 1] the normalized lanelet polygons (0 vertices: not bounded)
+    const double* lan_x;
+    const double* lan_y;
+    double* set_x;             // [n S PDMPC_BOUND_SLOT]
+    double* set_y;
+    int32_t* set_n;            // [n S] vertices (closing one included)
+    uint8_t* set_flags;        // [n S] PDMPC_BOUND_* | PDMPC_BOUND_OVERFLOW
+    double* box;               // [4 n] x0, x1, y0, y1 of the step-Hp sets
+    uint8_t* adjacency;        // [n n]
+    double* area;              // [n n]
+    int32_t* pairs;            // [n (n - 1) / 2] i * n + j of the pairs that pass the box test
+    int32_t* n_pairs;          // [1] their count (cleared before the box pass)
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
 // reachable_kernel.hip: the two passes of the reachable-set coupler on the handle's stream
 int pdmpc_launch_reachable_coupling(const ReachArgs* args, void* stream);
+// bounded_kernel.hip: the bounding pass (one wavefront per set) and the two passes of the coupler on the step-Hp sets
+int pdmpc_launch_bound_sets(const BoundArgs* args, void* stream);
+int pdmpc_launch_bounded_coupling(const BoundArgs* args, void* stream);
 // bulk_kernel*.hip: the graph search as bulk-synchronous passes (count searches + args->n_helpers helper workgroups in ONE launch) for the
 // InterX checker with one successor-mask word / with any number of them, and for the separating-axis checker; lds_high_water = the
 // handle's record of the dynamic LDS size set so far on that kernel

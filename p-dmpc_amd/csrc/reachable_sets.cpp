@@ -200,6 +200,75 @@ double clipped_sum(const double* ax, const double* ay, int ma, const double* bx,
     return total;
 }
 
+
+// ---- lanelet bounding (pdmpc_bound_region) and the coupler on simple polygons, host side (reachability.bound_reachable_set,
+// reachability.polygon_overlap_area)
+struct BoundScratch {
+    std::vector<int> ints;
+    std::vector<double> dbls, tmin, tmax;
+    pdmpc_bound_chains chains(int nl) {
+        ints.resize((size_t)6 * nl + 6);
+        dbls.resize((size_t)2 * nl + 2);
+        tmin.resize((size_t)nl + 1);
+        tmax.resize((size_t)nl + 1);
+        const size_t s = (size_t)nl + 1;
+        pdmpc_bound_chains C;
+        C.start = ints.data();
+        C.end = C.start + s;
+        C.kin = C.end + s;
+        C.kout = C.kin + s;
+        C.next = C.kout + s;
+        C.region = C.next + s;
+        C.sin = dbls.data();
+        C.sout = C.sin + s;
+        return C;
+    }
+};
+
+// the bounded set of K (open, m vertices) and the normalized L, closed, into (ox, oy); returns its flags
+unsigned bound_one(const double* kx, const double* ky, int m, const double* lx, const double* ly, int nl, BoundScratch& S, std::vector<double>& ox,
+                   std::vector<double>& oy) {
+    pdmpc_bound_chains C = S.chains(nl);
+    if (nl >= 3 && m >= 3)
+        for (int e = 0; e < nl; ++e) {
+            const int e1 = e + 1 == nl ? 0 : e + 1;
+            pdmpc_clip_edge_t(lx[e], ly[e], lx[e1], ly[e1], kx, ky, m, &S.tmin[e], &S.tmax[e]);
+        }
+    int cap = m + 3 * nl + 2, cnt = 0;
+    unsigned fl = 0;
+    for (;;) {
+        ox.resize((size_t)cap);
+        oy.resize((size_t)cap);
+        if (!pdmpc_bound_region(kx, ky, m, lx, ly, nl, S.tmin.data(), S.tmax.data(), &C, ox.data(), oy.data(), cap, &cnt, &fl)) break;
+        cap = cnt;
+    }
+    ox.resize((size_t)cnt);
+    oy.resize((size_t)cnt);
+    return fl;
+}
+
+}  // namespace
+
+// area of the intersection of two simple clockwise polygons given open (reachability.polygon_overlap_area)
+double pdmpc_polygon_overlap_area_host(const double* ax, const double* ay, int ma, const double* bx, const double* by, int mb) {
+    std::vector<double> r((size_t)2 * (ma + mb));
+    double *rax = r.data(), *ray = rax + ma, *rbx = ray + ma, *rby = rbx + mb;
+    const double ox = ax[0], oy = ay[0];
+    for (int q = 0; q < ma; ++q) {
+        rax[q] = ax[q] - ox;
+        ray[q] = ay[q] - oy;
+    }
+    for (int q = 0; q < mb; ++q) {
+        rbx[q] = bx[q] - ox;
+        rby[q] = by[q] - oy;
+    }
+    double total = 0.0;
+    for (int e = 0; e < ma; ++e) total = total + pdmpc_edge_overlap_term(rax, ray, ma, e, rbx, rby, mb, 0);
+    for (int e = 0; e < mb; ++e) total = total + pdmpc_edge_overlap_term(rbx, rby, mb, e, rax, ray, ma, 1);
+    return -0.5 * total;
+}
+
+namespace {
 }  // namespace
 
 // overlap area of two clockwise convex polygons given open (reachability.overlap_area): coordinates relative to a's first vertex
@@ -276,6 +345,85 @@ int pdmpc_reachable_set_coupling_host(int32_t n_trims, int32_t Hp, const pdmpc_p
             if (!pdmpc_boxes_overlap(box.data() + 4 * i, box.data() + 4 * j)) continue;
             const double A = pdmpc_overlap_area_host(gx.data() + off[i], gy.data() + off[i], off[i + 1] - off[i], gx.data() + off[j], gy.data() + off[j],
                                                      off[j + 1] - off[j]);
+            if (area) area[(size_t)i * n + j] = area[(size_t)j * n + i] = A;
+            adjacency[(size_t)i * n + j] = adjacency[(size_t)j * n + i] = A > PDMPC_COUPLING_AREA_THRESHOLD;
+        }
+    return PDMPC_OK;
+}
+
+int pdmpc_bound_reachable_sets_host(int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* local_sets, int32_t n, const double* x, const double* y,
+                                    const double* cos_yaw, const double* sin_yaw, const int32_t* trim, const pdmpc_polygon_set* lanelet_polygons,
+                                    int32_t all_steps, int32_t capacity, int32_t* offset, double* out_x, double* out_y, uint8_t* flags) {
+    if (!local_sets || !local_sets->offset || n < 0 || n_trims < 1 || Hp < 1 || local_sets->n_polygons != n_trims * Hp || !offset || !lanelet_polygons ||
+        lanelet_polygons->n_polygons != n || (n && (!x || !y || !cos_yaw || !sin_yaw || !trim || !lanelet_polygons->offset)))
+        return PDMPC_ERR_INVALID;
+    for (int v = 0; v < n; ++v) {
+        if (trim[v] < 1 || trim[v] > n_trims) return PDMPC_ERR_INVALID;
+        const int nl = lanelet_polygons->offset[v + 1] - lanelet_polygons->offset[v];
+        if (nl < 0) return PDMPC_ERR_INVALID;
+        if (nl > PDMPC_LANELET_POLY_MAX_COLS) return PDMPC_ERR_CAPACITY;
+        if (nl && (!lanelet_polygons->x || !lanelet_polygons->y)) return PDMPC_ERR_INVALID;
+    }
+    const int S = all_steps ? Hp : 1;
+    std::vector<std::vector<double>> rx((size_t)n * S), ry((size_t)n * S);
+    std::vector<uint8_t> fl((size_t)n * S, 0);
+    std::vector<double> lx, ly, kx, ky;
+    BoundScratch scratch;
+    bool too_big = false;
+    for (int v = 0; v < n; ++v) {
+        const int la = lanelet_polygons->offset[v], nl0 = lanelet_polygons->offset[v + 1] - la;
+        lx.resize((size_t)nl0 + 1);
+        ly.resize((size_t)nl0 + 1);
+        const int nl = nl0 ? pdmpc_lanelet_polygon_normalize(lanelet_polygons->x + la, lanelet_polygons->y + la, nl0, lx.data(), ly.data()) : 0;
+        for (int q = 0; q < S; ++q) {
+            const int p = (trim[v] - 1) * Hp + (all_steps ? q : Hp - 1);
+            const int a = local_sets->offset[p], m = local_sets->offset[p + 1] - a;
+            if (m < 1) return PDMPC_ERR_INVALID;
+            kx.resize((size_t)m);
+            ky.resize((size_t)m);
+            for (int r = 0; r < m; ++r) pdmpc_move_point(cos_yaw[v], sin_yaw[v], x[v], y[v], local_sets->x[a + r], local_sets->y[a + r], &kx[r], &ky[r]);
+            const size_t o = (size_t)v * S + q;
+            fl[o] = (uint8_t)bound_one(kx.data(), ky.data(), m, lx.data(), ly.data(), nl, scratch, rx[o], ry[o]);
+            if (rx[o].size() > (size_t)PDMPC_BOUNDED_MAX_COLS) too_big = true;
+        }
+    }
+    offset[0] = 0;
+    for (size_t o = 0; o < rx.size(); ++o) offset[o + 1] = offset[o] + (int32_t)rx[o].size();
+    if (too_big) return PDMPC_ERR_CAPACITY;
+    if (!out_x || !out_y || capacity < offset[rx.size()]) return PDMPC_ERR_CAPACITY;
+    for (size_t o = 0; o < rx.size(); ++o) {
+        std::memcpy(out_x + offset[o], rx[o].data(), rx[o].size() * sizeof(double));
+        std::memcpy(out_y + offset[o], ry[o].data(), ry[o].size() * sizeof(double));
+    }
+    if (flags) std::memcpy(flags, fl.data(), fl.size());
+    return PDMPC_OK;
+}
+
+int pdmpc_polygon_set_coupling_host(const pdmpc_polygon_set* sets, int32_t n, uint8_t* adjacency, double* area) {
+    if (!sets || n < 0 || sets->n_polygons != n || !adjacency || (n && (!sets->offset || !sets->x || !sets->y))) return PDMPC_ERR_INVALID;
+    std::vector<int> a((size_t)n), m((size_t)n);
+    std::vector<double> box((size_t)4 * n);
+    for (int v = 0; v < n; ++v) {
+        a[v] = sets->offset[v];
+        int c = sets->offset[v + 1] - a[v];
+        if (c < 1) return PDMPC_ERR_INVALID;
+        double* b = box.data() + 4 * v;
+        for (int q = 0; q < c; ++q) {
+            const double px = sets->x[a[v] + q], py = sets->y[a[v] + q];
+            if (q == 0 || px < b[0]) b[0] = px;
+            if (q == 0 || px > b[1]) b[1] = px;
+            if (q == 0 || py < b[2]) b[2] = py;
+            if (q == 0 || py > b[3]) b[3] = py;
+        }
+        if (c > 1 && sets->x[a[v]] == sets->x[a[v] + c - 1] && sets->y[a[v]] == sets->y[a[v] + c - 1]) --c;  // closed: drop the repeat
+        m[v] = c;
+    }
+    std::memset(adjacency, 0, (size_t)n * n);
+    if (area) std::memset(area, 0, (size_t)n * n * sizeof(double));
+    for (int i = 0; i + 1 < n; ++i)
+        for (int j = i + 1; j < n; ++j) {
+            if (!pdmpc_boxes_overlap(box.data() + 4 * i, box.data() + 4 * j)) continue;
+            const double A = pdmpc_polygon_overlap_area_host(sets->x + a[i], sets->y + a[i], m[i], sets->x + a[j], sets->y + a[j], m[j]);
             if (area) area[(size_t)i * n + j] = area[(size_t)j * n + i] = A;
             adjacency[(size_t)i * n + j] = adjacency[(size_t)j * n + i] = A > PDMPC_COUPLING_AREA_THRESHOLD;
         }

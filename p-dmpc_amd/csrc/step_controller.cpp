@@ -193,6 +193,10 @@ struct pdmpc_controller {
     std::vector<double> reach_x, reach_y;
     std::vector<std::vector<Poly>> reach_sets;
     std::vector<double> reach_cos, reach_sin;
+    // lanelet bounding of those sets (pdmpc_controller_set_lanelet_bounding): the raw lanelet polygons and the bounded sets of the step
+    bool lanelet_bounding = false;
+    std::vector<int32_t> bound_off, lan_off;
+    std::vector<double> bound_x, bound_y, lan_x, lan_y;
     std::string err;
 };
 
@@ -828,6 +832,12 @@ int pdmpc_controller_set_parallel_coupling(pdmpc_controller* c, int32_t mode) {
     return PDMPC_OK;
 }
 
+int pdmpc_controller_set_lanelet_bounding(pdmpc_controller* c, int32_t on) {
+    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
+    c->lanelet_bounding = on != 0;
+    return PDMPC_OK;
+}
+
 int pdmpc_controller_set_reachability(pdmpc_controller* c, const pdmpc_mpa* mpa) {
     if (!c || !mpa) return cfail(c, PDMPC_ERR_INVALID, "null argument");
     if (mpa->Hp != c->Hp) return cfail(c, PDMPC_ERR_INVALID, "the automaton's Hp differs from the controller's");
@@ -932,9 +942,88 @@ int pdmpc_controller_build_step(pdmpc_controller* c) {
             }
         }
     }
+    // ---- lanelet bounding of those sets (bound_reachable_sets.m, HighLevelController.m:241-246; not on scenarios without lanelets):
+    // every step's sets when parallel predecessors read them, else step Hp only (the coupler's)
+    bool bounded = false;
+    if ((reach_coupling || reach_parallel) && c->lanelet_bounding) {
+        for (int v = 0; v < n && !bounded; ++v) bounded = !c->veh[v].lanelets_index.empty();
+    }
+    if (bounded) {
+        c->lan_off.assign((size_t)n + 1, 0);
+        c->lan_x.clear();
+        c->lan_y.clear();
+        for (int v = 0; v < n; ++v) {  // the left boundary, then the reversed right boundary (get_lanelets_boundary.m:69-74)
+            const Poly &L = c->bnd_left[v], &R = c->bnd_right[v];
+            c->lan_x.insert(c->lan_x.end(), L.x.begin(), L.x.end());
+            c->lan_y.insert(c->lan_y.end(), L.y.begin(), L.y.end());
+            c->lan_x.insert(c->lan_x.end(), R.x.rbegin(), R.x.rend());
+            c->lan_y.insert(c->lan_y.end(), R.y.rbegin(), R.y.rend());
+            c->lan_off[v + 1] = (int32_t)c->lan_x.size();
+        }
+        c->lan_x.push_back(0.0);  // (never empty)
+        c->lan_y.push_back(0.0);
+        pdmpc_polygon_set lan;
+        lan.n_polygons = n;
+        lan.offset = c->lan_off.data();
+        lan.x = c->lan_x.data();
+        lan.y = c->lan_y.data();
+        pdmpc_polygon_set local;
+        local.n_polygons = (int32_t)c->reach_off.size() - 1;
+        local.offset = c->reach_off.data();
+        local.x = c->reach_x.data();
+        local.y = c->reach_y.data();
+        const int all_steps = reach_parallel ? 1 : 0, S = all_steps ? Hp : 1;
+        c->bound_off.assign((size_t)n * S + 1, 0);
+        auto bound = [&](int32_t cap, double* ox, double* oy) {
+            if (c->h)
+                return pdmpc_bound_reachable_sets(c->h, n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(), c->trims.data(), &lan, all_steps, cap,
+                                                  c->bound_off.data(), ox, oy, nullptr);
+            return pdmpc_bound_reachable_sets_host((int32_t)c->trim_speed.size(), Hp, &local, n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(),
+                                                   c->trims.data(), &lan, all_steps, cap, c->bound_off.data(), ox, oy, nullptr);
+        };
+        int rc = bound((int32_t)c->bound_x.size(), c->bound_x.empty() ? nullptr : c->bound_x.data(), c->bound_y.empty() ? nullptr : c->bound_y.data());
+        if (rc == PDMPC_ERR_CAPACITY && c->bound_off.back() > (int32_t)c->bound_x.size()) {
+            c->bound_x.resize((size_t)c->bound_off.back());
+            c->bound_y.resize((size_t)c->bound_off.back());
+            rc = bound((int32_t)c->bound_x.size(), c->bound_x.data(), c->bound_y.data());
+        }
+        if (rc) return cfail(c, rc, std::string("pdmpc_bound_reachable_sets: ") + (c->h ? pdmpc_last_error() : "host twin failed"));
+        if (reach_parallel) {  // the parallel predecessors' obstacles are the bounded sets
+            for (int v = 0; v < n; ++v)
+                for (int q = 0; q < Hp; ++q) {
+                    const int o = v * Hp + q, a = c->bound_off[o], m = c->bound_off[o + 1] - a;
+                    Poly& P = c->reach_sets[v][q];
+                    P.x.assign(c->bound_x.begin() + a, c->bound_x.begin() + a + m);
+                    P.y.assign(c->bound_y.begin() + a, c->bound_y.begin() + a + m);
+                }
+        }
+    }
     // ---- coupling
     c->adjacency.assign((size_t)n * n, 0);
-    if (reach_coupling) {  // ReachableSetCoupler.couple (ReachableSetCoupler.m:5-56): on the device with a handle, else the host twin
+    if (reach_coupling && bounded) {  // ... on the bounded step-Hp sets: on the device (they are still there), else the host twin
+        int rc;
+        if (c->h) {
+            rc = pdmpc_bounded_set_coupling(c->h, c->adjacency.data(), nullptr);
+            if (rc) return cfail(c, rc, std::string("pdmpc_bounded_set_coupling: ") + pdmpc_last_error());
+        } else {
+            const int S = reach_parallel ? Hp : 1;
+            std::vector<int32_t> off((size_t)n + 1, 0);
+            std::vector<double> sx, sy;
+            for (int v = 0; v < n; ++v) {
+                const int o = v * S + S - 1, a = c->bound_off[o], m = c->bound_off[o + 1] - a;
+                sx.insert(sx.end(), c->bound_x.begin() + a, c->bound_x.begin() + a + m);
+                sy.insert(sy.end(), c->bound_y.begin() + a, c->bound_y.begin() + a + m);
+                off[v + 1] = off[v] + m;
+            }
+            pdmpc_polygon_set ps;
+            ps.n_polygons = n;
+            ps.offset = off.data();
+            ps.x = sx.data();
+            ps.y = sy.data();
+            rc = pdmpc_polygon_set_coupling_host(&ps, n, c->adjacency.data(), nullptr);
+            if (rc) return cfail(c, rc, "pdmpc_polygon_set_coupling_host failed");
+        }
+    } else if (reach_coupling) {  // ReachableSetCoupler.couple (ReachableSetCoupler.m:5-56): on the device with a handle, else the host twin
         int rc;
         if (c->h) {
             rc = pdmpc_reachable_set_coupling(c->h, n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(), c->trims.data(), c->adjacency.data(), nullptr);

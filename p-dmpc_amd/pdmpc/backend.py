@@ -106,6 +106,12 @@ EXPORTS = [
     "pdmpc_reachable_set_coupling_kernel_ms",
     "pdmpc_controller_set_reachability",
     "pdmpc_controller_set_parallel_coupling",
+    "pdmpc_bound_reachable_sets",
+    "pdmpc_bound_reachable_sets_host",
+    "pdmpc_bounded_set_coupling",
+    "pdmpc_polygon_set_coupling_host",
+    "pdmpc_bounded_reachable_kernel_ms",
+    "pdmpc_controller_set_lanelet_bounding",
     "pdmpc_last_error",
     "pdmpc_version",
 ]
@@ -212,6 +218,61 @@ def reachable_set_coupling_call(local_sets, x, y, yaw, trim, handle=None):
     return adj[: n * n].reshape(n, n), area[: n * n].reshape(n, n)
 
 
+def _pack_lanelet_polygons(lanelet_polys):
+    """[vehicle] raw lanelet polygon (2, P) or None (not bounded) -> (pdmpc_polygon_set, keep-alive)."""
+    keep = abi._Keep()
+    polys = [np.zeros((2, 0)) if p is None else np.asarray(p, dtype=np.float64).reshape(2, -1) for p in lanelet_polys]
+    return abi.pack_polygon_set(polys, keep), keep
+
+
+def bound_reachable_sets_call(local_sets, x, y, yaw, trim, lanelet_polys, all_steps=True, handle=None):
+    """bound_reachable_sets natively: on `handle`'s device (pdmpc_bound_reachable_sets; the handle must hold the table, see
+    Handle.upload_reachable_sets) or, without one, on the host twin.  trim is 1-based; lanelet_polys[v] is vehicle v's raw lanelet
+    polygon (reachability.lanelet_polygon) or None.  -> (sets: [vehicle][step] closed (2, c) arrays (one step, Hp, unless
+    all_steps), flags (n, steps) uint8)."""
+    L = load_library()
+    x, y, c, s, t = _coupling_args(x, y, yaw, trim)
+    n = x.size
+    lp, lkeep = _pack_lanelet_polygons(lanelet_polys)
+    S = (handle.options.Hp if handle is not None else len(local_sets[0])) if all_steps else 1
+    off = np.zeros(n * S + 1, dtype=np.int32)
+    flags = np.zeros(max(n * S, 1), dtype=np.uint8)
+    head = [x.ctypes.data_as(abi.c_double_p), y.ctypes.data_as(abi.c_double_p), c.ctypes.data_as(abi.c_double_p), s.ctypes.data_as(abi.c_double_p),
+            t.ctypes.data_as(abi.c_int32_p), C.byref(lp), int(bool(all_steps))]
+    if handle is None:
+        ps, keep = pack_local_sets(local_sets)
+        fn = lambda *tail: L.pdmpc_bound_reachable_sets_host(len(local_sets), len(local_sets[0]), C.byref(ps), n, *head, *tail)  # noqa: E731
+    else:
+        fn = lambda *tail: L.pdmpc_bound_reachable_sets(handle.h, n, *head, *tail)  # noqa: E731
+    rc = fn(0, off.ctypes.data_as(abi.c_int32_p), None, None, None)
+    if rc not in (0, ERR_CAPACITY) or (rc == ERR_CAPACITY and n and int(off[-1]) == 0):
+        raise BackendError("pdmpc_bound_reachable_sets failed with status %d: %s" % (rc, L.pdmpc_last_error().decode()))
+    tot = int(off[-1])
+    bx = np.zeros(max(tot, 1))
+    by = np.zeros(max(tot, 1))
+    rc = fn(tot, off.ctypes.data_as(abi.c_int32_p), bx.ctypes.data_as(abi.c_double_p), by.ctypes.data_as(abi.c_double_p), flags.ctypes.data_as(abi.c_uint8_p))
+    del lkeep
+    if rc != 0:
+        raise BackendError("pdmpc_bound_reachable_sets failed with status %d: %s" % (rc, L.pdmpc_last_error().decode()))
+    sets = [[np.array([bx[off[v * S + q] : off[v * S + q + 1]], by[off[v * S + q] : off[v * S + q + 1]]]) for q in range(S)] for v in range(n)]
+    return sets, flags[: n * S].reshape(n, S)
+
+
+def polygon_set_coupling_call(sets):
+    """pdmpc_polygon_set_coupling_host: ReachableSetCoupler.couple on any simple clockwise polygons -> (adjacency (n, n) uint8, areas)."""
+    L = load_library()
+    keep = abi._Keep()
+    n = len(sets)
+    ps = abi.pack_polygon_set([np.asarray(p, dtype=np.float64) for p in sets], keep)
+    adj = np.zeros(max(n * n, 1), dtype=np.uint8)
+    area = np.zeros(max(n * n, 1), dtype=np.float64)
+    rc = L.pdmpc_polygon_set_coupling_host(C.byref(ps), n, adj.ctypes.data_as(abi.c_uint8_p), area.ctypes.data_as(abi.c_double_p))
+    del keep
+    if rc != 0:
+        raise BackendError("pdmpc_polygon_set_coupling_host failed with status %d" % rc)
+    return adj[: n * n].reshape(n, n), area[: n * n].reshape(n, n)
+
+
 def load_library(path=None):
     """dlopen the HIP backend and declare every prototype of include/pdmpc.h."""
     global _LIB
@@ -274,6 +335,13 @@ def load_library(path=None):
     L.pdmpc_reachable_set_coupling_kernel_ms.argtypes = [H, abi.c_double_p]
     L.pdmpc_controller_set_reachability.argtypes = [H, C.POINTER(abi.Mpa)]
     L.pdmpc_controller_set_parallel_coupling.argtypes = [H, C.c_int32]
+    bound_tail = [abi.c_double_p] * 4 + [abi.c_int32_p, C.POINTER(abi.PolygonSet), C.c_int32, C.c_int32, abi.c_int32_p, abi.c_double_p, abi.c_double_p, abi.c_uint8_p]
+    L.pdmpc_bound_reachable_sets.argtypes = [H, C.c_int32] + bound_tail
+    L.pdmpc_bound_reachable_sets_host.argtypes = [C.c_int32, C.c_int32, C.POINTER(abi.PolygonSet), C.c_int32] + bound_tail
+    L.pdmpc_bounded_set_coupling.argtypes = [H, abi.c_uint8_p, abi.c_double_p]
+    L.pdmpc_polygon_set_coupling_host.argtypes = [C.POINTER(abi.PolygonSet), C.c_int32, abi.c_uint8_p, abi.c_double_p]
+    L.pdmpc_bounded_reachable_kernel_ms.argtypes = [H, abi.c_double_p]
+    L.pdmpc_controller_set_lanelet_bounding.argtypes = [H, C.c_int32]
     L.pdmpc_last_error.restype = C.c_char_p
     L.pdmpc_version.restype = C.c_char_p
     for name in EXPORTS:
@@ -506,6 +574,27 @@ class Handle:
     def reachable_set_coupling(self, x, y, yaw, trim):
         """ReachableSetCoupler.couple on this handle's device (pdmpc_reachable_set_coupling) -> (adjacency (n, n) uint8, areas (n, n))."""
         return reachable_set_coupling_call(None, x, y, yaw, trim, handle=self)
+
+    def bound_reachable_sets(self, x, y, yaw, trim, lanelet_polys, all_steps=True):
+        """pdmpc_bound_reachable_sets on this handle's device -> (sets [vehicle][step], flags (n, steps)); the sets stay on the device
+        for bounded_set_coupling."""
+        out = bound_reachable_sets_call(None, x, y, yaw, trim, lanelet_polys, all_steps, handle=self)
+        self._bound_n = len(out[0])
+        return out
+
+    def bounded_set_coupling(self):
+        """pdmpc_bounded_set_coupling on the step-Hp sets of the last bound_reachable_sets -> (adjacency (n, n) uint8, areas (n, n))."""
+        n = getattr(self, "_bound_n", 0)
+        adj = np.zeros(max(n * n, 1), dtype=np.uint8)
+        area = np.zeros(max(n * n, 1), dtype=np.float64)
+        _check(self.L, self.L.pdmpc_bounded_set_coupling(self.h, adj.ctypes.data_as(abi.c_uint8_p), area.ctypes.data_as(abi.c_double_p)), "pdmpc_bounded_set_coupling")
+        return adj[: n * n].reshape(n, n), area[: n * n].reshape(n, n)
+
+    def bounded_reachable_kernel_ms(self):
+        """kernel times (ms) of the last bound_reachable_sets and bounded_set_coupling"""
+        ms = np.zeros(2)
+        _check(self.L, self.L.pdmpc_bounded_reachable_kernel_ms(self.h, ms.ctypes.data_as(abi.c_double_p)), "pdmpc_bounded_reachable_kernel_ms")
+        return float(ms[0]), float(ms[1])
 
     def reachable_set_coupling_kernel_ms(self):
         ms = C.c_double(0.0)

@@ -52,6 +52,10 @@ class Config:
     # previous plan shifted by one step (PrioritizedController.m:29-33, 391-407).  The reference's default is true; this backend keeps
     # false so that configurations written before the feature existed plan as they did.
     is_deal_prediction_inconsistency: bool = False
+    # HighLevelController.m:241-246 (bound_reachable_sets): the reachable sets of road-network steps are intersected with the vehicle's
+    # predicted-lanelet polygon before they are coupled on or enter a search as a parallel predecessor.  Off by default
+    # so that configurations written before the feature existed plan as they did.
+    bound_reachable_sets: bool = False
     # backend sizing (no reference counterpart)
     device: int = 0
     max_nodes: int = 0

@@ -132,15 +132,22 @@ class PrioritizedSequentialController:
             self.v_ref[i] = v_ref
             if o.scenario_type != ScenarioType.circle and self.boundary_provider is not None:
                 self.boundary[i] = self.boundary_provider(i, veh, points_index, cpi)
-        # HighLevelController.m:219-263: the Hp reachable sets at the vehicle's pose, closed; only when a feature reads them (the
-        # lanelet bounding of :241-246 is not applied)
+        # HighLevelController.m:219-263: the Hp reachable sets at the vehicle's pose, closed; only when a feature reads them.  With
+        # Config.bound_reachable_sets they are bounded by the predicted lanelets on road networks (:241-246).
         self.reachable_sets = [None] * n
+        self.reachable_sets_bounded = False
         if self.coupling == "reachable_set" or o.is_deal_prediction_inconsistency:
-            from .reachability import reachable_sets_at_pose
+            from .reachability import bound_reachable_sets, lanelet_polygon, reachable_sets_at_pose
 
             local = self.mpa.local_reachable_sets_conv
             for i, m in enumerate(self.meas):
                 self.reachable_sets[i] = reachable_sets_at_pose(local, m.x, m.y, m.yaw, int(self.trims[i]))
+            if o.bound_reachable_sets and o.scenario_type != ScenarioType.circle and self.boundary_provider is not None:
+                self.reachable_sets_bounded = True
+                for i in range(n):
+                    left, right = self.boundary[i]
+                    if left is not None:
+                        self.reachable_sets[i], _ = bound_reachable_sets(self.reachable_sets[i], lanelet_polygon(left, right))
 
     def _couple(self):
         n = self.n
@@ -157,8 +164,10 @@ class PrioritizedSequentialController:
                     adj[a, b] = adj[b, a] = int(d <= max_distance)
             return adj
         if self.coupling == "reachable_set":  # ReachableSetCoupler.m:5-56 on the step-Hp sets
-            from .reachability import reachable_set_coupling
+            from .reachability import polygon_set_coupling, reachable_set_coupling
 
+            if self.reachable_sets_bounded:  # bounded sets need not be convex: the overlap of two simple polygons
+                return polygon_set_coupling([r[-1] for r in self.reachable_sets])[0]
             return reachable_set_coupling([r[-1] for r in self.reachable_sets])[0]
         raise ValueError(self.coupling)
 

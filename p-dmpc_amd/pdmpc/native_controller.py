@@ -161,6 +161,8 @@ class NativeController:
             del mkeep
         if options.is_deal_prediction_inconsistency:
             self._check(self.L.pdmpc_controller_set_parallel_coupling(self.c, PARALLEL_REACHABLE_SETS), "pdmpc_controller_set_parallel_coupling")
+        if options.bound_reachable_sets:
+            self._check(self.L.pdmpc_controller_set_lanelet_bounding(self.c, 1), "pdmpc_controller_set_lanelet_bounding")
 
     def _check(self, rc, what):
         if rc != 0:

@@ -214,3 +214,282 @@ def reachable_set_coupling(sets):
             if a > COUPLING_AREA_THRESHOLD:
                 adj[i, j] = adj[j, i] = 1
     return adj, areas
+
+
+# ---- lanelet bounding of the reachable sets (bound_reachable_sets.m, HighLevelController.m:241-246; include/pdmpc_geometry.h) ----
+BOUND_RESTORED = 1  # K ∩ L was empty: K returned unchanged
+BOUND_MULTIPLE = 2  # K ∩ L had more than one region: the one with the most vertices was kept
+
+
+def lanelet_polygon(left, right) -> np.ndarray:
+    """The predicted-lanelet polygon of get_lanelets_boundary.m:69-74: the left boundary, then the reversed right boundary, (2, P)."""
+    left = np.asarray(left, dtype=np.float64).reshape(2, -1)
+    right = np.asarray(right, dtype=np.float64).reshape(2, -1)
+    return np.concatenate([left, right[:, ::-1]], axis=1)
+
+
+def normalize_lanelet_polygon(poly) -> np.ndarray:
+    """pdmpc_lanelet_polygon_normalize: consecutive duplicate vertices (and trailing copies of the first) dropped, reversed if the
+    signed area is positive -> clockwise (2, m)."""
+    p = np.asarray(poly, dtype=np.float64).reshape(2, -1)
+    xs, ys = [], []
+    for x, y in zip(p[0].tolist(), p[1].tolist()):
+        if xs and x == xs[-1] and y == ys[-1]:
+            continue
+        xs.append(x)
+        ys.append(y)
+    while len(xs) > 1 and xs[-1] == xs[0] and ys[-1] == ys[0]:
+        xs.pop()
+        ys.pop()
+    x = np.array(xs, dtype=np.float64)
+    y = np.array(ys, dtype=np.float64)
+    if x.size:
+        terms = x * np.roll(y, -1) - np.roll(x, -1) * y
+        if np.cumsum(terms)[-1] > 0.0:
+            x, y = x[::-1].copy(), y[::-1].copy()
+    return np.array([x, y]).reshape(2, -1)
+
+
+def _clip_table(lx, ly, kx, ky):
+    """pdmpc_clip_edge_t for every edge of L (open) against the clockwise convex K (open) -> (tmin, tmax) per L edge."""
+    dx, dy = np.roll(lx, -1) - lx, np.roll(ly, -1) - ly
+    ux, uy = np.roll(kx, -1) - kx, np.roll(ky, -1) - ky
+    num = ux[None, :] * (ly[:, None] - ky[None, :]) - uy[None, :] * (lx[:, None] - kx[None, :])
+    den = ux[None, :] * dy[:, None] - uy[None, :] * dx[:, None]
+    dead = ((den == 0.0) & (num >= 0.0)).any(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = -num / den
+    tmin = np.max(np.where(den < 0.0, t, 0.0), axis=1, initial=0.0) + 0.0  # (+ 0.0: the C loop never holds -0.0)
+    tmax = np.min(np.where(den > 0.0, t, 1.0), axis=1, initial=1.0)
+    tmin[dead] = 1.0
+    tmax[dead] = 0.0
+    return tmin.tolist(), tmax.tolist()
+
+
+def _boundary_position(px, py, kx, ky):
+    """pdmpc_boundary_position -> (K edge, parameter)."""
+    m = len(kx)
+    best, bv = 0, 0.0
+    for k in range(m):
+        k1 = 0 if k + 1 == m else k + 1
+        v = (kx[k1] - kx[k]) * (py - ky[k]) - (ky[k1] - ky[k]) * (px - kx[k])
+        if k == 0 or v > bv:
+            bv, best = v, k
+    b1 = 0 if best + 1 == m else best + 1
+    ux, uy = kx[b1] - kx[best], ky[b1] - ky[best]
+    s = ((px - kx[best]) * ux + (py - ky[best]) * uy) / (ux * ux + uy * uy)
+    if s < 0.0:
+        s = 0.0
+    if s >= 1.0:
+        best, s = b1, 0.0
+    return best, s
+
+
+def bound_reachable_set(K, L):
+    """bound_reachable_sets.m for one set: K (2, m) convex, clockwise (a closing repeated vertex is ignored), L the vehicle's
+    normalized lanelet polygon (normalize_lanelet_polygon; fewer than 3 vertices: no clipping) -> (the kept region of K ∩ L, closed,
+    (2, c); flags BOUND_*).  The rules are pdmpc_bound_region's (include/pdmpc_geometry.h), operation by operation."""
+    K = np.asarray(K, dtype=np.float64)
+    if K.shape[1] > 1 and K[0, 0] == K[0, -1] and K[1, 0] == K[1, -1]:
+        K = K[:, :-1]
+    kx, ky = K[0].tolist(), K[1].tolist()
+    m = len(kx)
+    L = np.asarray(L, dtype=np.float64).reshape(2, -1)
+    lx, ly = L[0].tolist(), L[1].tolist()
+    nl = len(lx)
+    flags = 0
+    out = None
+    if m >= 3 and nl >= 3:
+        tmin, tmax = _clip_table(L[0], L[1], K[0], K[1])
+        alive = [tmin[e] < tmax[e] for e in range(nl)]
+        link = [alive[e] and alive[(e + 1) % nl] and tmax[e] == 1.0 and tmin[(e + 1) % nl] == 0.0 for e in range(nl)]
+        if all(link):
+            out = (lx, ly)
+        else:
+            starts = [e for e in range(nl) if alive[e] and not link[nl - 1 if e == 0 else e - 1]]
+            C = len(starts)
+            ends, kin, sin, kout, sout = [], [], [], [], []
+            for s in starts:
+                e = s
+                while link[e]:
+                    e = 0 if e + 1 == nl else e + 1
+                ends.append(e)
+                s1, e1 = (s + 1) % nl, (e + 1) % nl
+                k, p = _boundary_position(lx[s] + tmin[s] * (lx[s1] - lx[s]), ly[s] + tmin[s] * (ly[s1] - ly[s]), kx, ky)
+                kin.append(k)
+                sin.append(p)
+                k, p = _boundary_position(lx[e] + tmax[e] * (lx[e1] - lx[e]), ly[e] + tmax[e] * (ly[e1] - ly[e]), kx, ky)
+                kout.append(k)
+                sout.append(p)
+
+            def steps(c, d):
+                dk = kin[d] - kout[c]
+                if dk < 0:
+                    dk += m
+                if dk == 0 and sin[d] < sout[c]:
+                    dk = m
+                return dk
+
+            def link_vertices(c, d):
+                dk = steps(c, d)
+                return dk - 1 if dk > 0 and sin[d] == 0.0 else dk
+
+            nxt = []
+            for c in range(C):
+                bd, bk = -1, 0
+                for d in range(C):
+                    dk = steps(c, d)
+                    if bd < 0 or dk < bk or (dk == bk and sin[d] < sin[bd]):
+                        bd, bk = d, dk
+                nxt.append(bd)
+            region = [0] * C
+            n_regions, best, best_count, best_steps = 0, -1, 0, 0
+            for c in range(C):
+                if region[c]:
+                    continue
+                cnt = n_steps = 0
+                cur = c
+                while True:
+                    region[cur] = c + 1
+                    cnt += 2 + (ends[cur] - starts[cur]) % nl + link_vertices(cur, nxt[cur])
+                    n_steps += 1
+                    cur = nxt[cur]
+                    if region[cur]:
+                        break
+                if cnt >= 3:
+                    n_regions += 1
+                    if cnt > best_count:
+                        best_count, best, best_steps = cnt, c, n_steps
+            if C == 0:  # K ⊂ L, or K ∩ L is empty
+                cx = cy = 0.0
+                for q in range(m):
+                    cx = cx + kx[q]
+                    cy = cy + ky[q]
+                cx = cx / float(m)
+                cy = cy / float(m)
+                inside = False
+                for i in range(nl):
+                    j = 0 if i + 1 == nl else i + 1
+                    if (ly[i] > cy) != (ly[j] > cy):
+                        xi = lx[i] + (cy - ly[i]) * (lx[j] - lx[i]) / (ly[j] - ly[i])
+                        if cx < xi:
+                            inside = not inside
+                if not inside:
+                    flags |= BOUND_RESTORED
+            elif n_regions == 0:
+                flags |= BOUND_RESTORED
+            else:
+                if n_regions > 1:
+                    flags |= BOUND_MULTIPLE
+                ox, oy = [], []
+                cur = best
+                for _ in range(best_steps):
+                    s, e = starts[cur], ends[cur]
+                    s1, e1 = (s + 1) % nl, (e + 1) % nl
+                    ox.append(lx[s] + tmin[s] * (lx[s1] - lx[s]))
+                    oy.append(ly[s] + tmin[s] * (ly[s1] - ly[s]))
+                    for q in range(1, (e - s) % nl + 1):
+                        ox.append(lx[(s + q) % nl])
+                        oy.append(ly[(s + q) % nl])
+                    ox.append(lx[e] + tmax[e] * (lx[e1] - lx[e]))
+                    oy.append(ly[e] + tmax[e] * (ly[e1] - ly[e]))
+                    d = nxt[cur]
+                    for q in range(1, link_vertices(cur, d) + 1):
+                        ox.append(kx[(kout[cur] + q) % m])
+                        oy.append(ky[(kout[cur] + q) % m])
+                    cur = d
+                out = (ox, oy)
+    if out is None:
+        out = (kx, ky)
+    x = np.array(list(out[0]) + [out[0][0]], dtype=np.float64)
+    y = np.array(list(out[1]) + [out[1][0]], dtype=np.float64)
+    return np.array([x, y]), flags
+
+
+def bound_reachable_sets(sets, lanelet_poly):
+    """bound_reachable_sets.m on a vehicle's Hp closed sets (reachable_sets_at_pose) with its raw lanelet polygon (lanelet_polygon;
+    None or fewer than 3 distinct vertices: not clipped) -> (bounded closed sets, flags per set)."""
+    if lanelet_poly is None:
+        return list(sets), [0] * len(sets)
+    L = normalize_lanelet_polygon(lanelet_poly)
+    out, flags = [], []
+    for K in sets:
+        r, f = bound_reachable_set(K, L)
+        out.append(r)
+        flags.append(f)
+    return out, flags
+
+
+def _inside_fractions(ax, ay, px, py, strict):
+    """pdmpc_edge_inside_fraction for every edge of (ax, ay) (open) against the polygon (px, py) (open)."""
+    bx, by = np.roll(ax, -1), np.roll(ay, -1)
+    dx, dy = bx - ax, by - ay
+    dd = dx * dx + dy * dy
+    cx, cy = px[None, :], py[None, :]
+    ex, ey = np.roll(px, -1)[None, :], np.roll(py, -1)[None, :]
+    AX, AY, DX, DY, DD = ax[:, None], ay[:, None], dx[:, None], dy[:, None], dd[:, None]
+    oc = DX * (cy - AY) - DY * (cx - AX)
+    oe = DX * (ey - AY) - DY * (ex - AX)
+    lc = oc > 0.0 if strict else oc >= 0.0
+    le = oe > 0.0 if strict else oe >= 0.0
+    cross = lc != le
+    wx, wy = ex - cx, ey - cy
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tc = ((cx - AX) * DX + (cy - AY) * DY) / DD
+        te = ((ex - AX) * DX + (ey - AY) * DY) / DD
+        tl = ((cx - AX) * wy - (cy - AY) * wx) / (DX * wy - DY * wx)
+    t = np.where(oc == 0.0, tc, np.where(oe == 0.0, te, tl))
+    inner = cross & (t < 1.0) & (t > 0.0)
+    acc = np.cumsum(np.where(inner, np.where(lc, t, -t), 0.0), axis=1)[:, -1] if px.size else np.zeros(ax.size)
+    par = (np.count_nonzero(cross & (t >= 1.0), axis=1) & 1).astype(np.float64)
+    f = acc + par
+    if strict:
+        opp = ~cross & (oc == 0.0) & (oe == 0.0) & (DX * wx + DY * wy < 0.0)
+        lo = np.maximum(np.minimum(tc, te), 0.0)  # (no NaN: DD > 0 where it is read)
+        hi = np.minimum(np.maximum(tc, te), 1.0)
+        use = opp & (hi > lo)
+        corr = np.cumsum(np.where(use, hi - lo, 0.0), axis=1)[:, -1] if px.size else np.zeros(ax.size)
+        f = f - corr
+    f = np.where(dd == 0.0, 0.0, f)
+    return f
+
+
+def polygon_overlap_area(a, b) -> float:
+    """Area of the intersection of two simple clockwise polygons (2, m) (a closing repeated vertex is ignored): Green's theorem
+    over the boundary of A ∩ B with the crossing rule of pdmpc_edge_inside_fraction (include/pdmpc_geometry.h), in coordinates
+    relative to a's first vertex, A's edge terms then B's summed in edge order."""
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    if a.shape[1] > 1 and a[0, 0] == a[0, -1] and a[1, 0] == a[1, -1]:
+        a = a[:, :-1]
+    if b.shape[1] > 1 and b[0, 0] == b[0, -1] and b[1, 0] == b[1, -1]:
+        b = b[:, :-1]
+    ox, oy = a[0, 0], a[1, 0]
+    ax, ay = a[0] - ox, a[1] - oy
+    bx, by = b[0] - ox, b[1] - oy
+    fa = _inside_fractions(ax, ay, bx, by, False)
+    fb = _inside_fractions(bx, by, ax, ay, True)
+    ta = fa * (ax * np.roll(ay, -1) - np.roll(ax, -1) * ay)
+    tb = fb * (bx * np.roll(by, -1) - np.roll(bx, -1) * by)
+    total = np.cumsum(np.concatenate([[0.0], ta, tb]))[-1]
+    return -0.5 * float(total)
+
+
+def polygon_set_coupling(sets):
+    """ReachableSetCoupler.couple on any simple closed clockwise sets (the bounded step-Hp sets): the box pre-filter of
+    reachable_set_coupling, polygon_overlap_area for every pair that passes it -> (adjacency (n, n) int64, areas (n, n))."""
+    n = len(sets)
+    adj = np.zeros((n, n), dtype=np.int64)
+    areas = np.zeros((n, n), dtype=np.float64)
+    boxes = [(float(np.min(s[0])), float(np.max(s[0])), float(np.min(s[1])), float(np.max(s[1]))) for s in sets]
+    for i in range(n - 1):
+        xi0, xi1, yi0, yi1 = boxes[i]
+        for j in range(i + 1, n):
+            xj0, xj1, yj0, yj1 = boxes[j]
+            if xi0 >= xj1 or yi0 >= yj1 or xi1 <= xj0 or yi1 <= yj0:
+                continue
+            a = polygon_overlap_area(sets[i], sets[j])
+            areas[i, j] = areas[j, i] = a
+            if a > COUPLING_AREA_THRESHOLD:
+                adj[i, j] = adj[j, i] = 1
+    return adj, areas
