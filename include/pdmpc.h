@@ -345,6 +345,23 @@ int pdmpc_debug_heap_script(pdmpc_handle* handle, int32_t n, const int32_t* op, 
  * chosen descent, path_nodes rows with g = -1 except the cost of the chosen node, h = -1, k = 1..Hp+1 (:223-244). */
 int pdmpc_plan_batch_sampled(pdmpc_handle* handle, int32_t n_vehicles, const pdmpc_vehicle_in* in, const uint32_t* seeds,
                              pdmpc_vehicle_out* out);
+/* A whole time step of the sampled optimizer in one launch: arguments, slot order, level reordering, fallback areas
+ * and records as for pdmpc_plan_step; seeds[v] = time_step + vehicle_index of the caller's vehicle v.  A slot waits on the device for
+ * its predecessors (blocking, no speculation) and plans against their areas — a predecessor's solved areas, or its fallback areas if
+ * it was exhausted, which an exhausted slot publishes in its record.  Every slot draws its first Hp * 250 numbers of mt19937ar(seed)
+ * itself.  A watchdog time-out is re-planned in resident slices as for pdmpc_plan_step; there are no arenas to grow.  Stats: kernel 3.
+ * Equivalent to pdmpc_set_step_seeds(seeds) + pdmpc_plan_step.  PDMPC_ERR_INVALID for a NULL handle and for NULL seeds with n > 0. */
+int pdmpc_plan_step_sampled(pdmpc_handle* handle, int32_t n_vehicles, const pdmpc_vehicle_in* in, const int32_t* pred_offset,
+                            const int32_t* pred_index, const pdmpc_polygon_set* fallback_shapes, const uint32_t* seeds,
+                            pdmpc_vehicle_out* out);
+/* Seeds of the sampled optimizer per vehicle of the NEXT packed step (the caller's vehicle order), consumed by the next
+ * pdmpc_pack_step / pdmpc_plan_step / pdmpc_plan_step_lean / pdmpc_pack_batch, which then packs a SAMPLED bank: every launch of that
+ * bank (pdmpc_launch_packed, pdmpc_launch_range, the plan calls) runs the sampled optimizer instead of the graph search, and the
+ * resident path (pack once, launch many; pdmpc_fetch_records_at) works as for the graph search.  A pack without seeds packs a graph
+ * search bank.  A pack that fails consumes the seeds too; a pack of another vehicle count than n_vehicles fails (PDMPC_ERR_INVALID). */
+int pdmpc_set_step_seeds(pdmpc_handle* handle, int32_t n_vehicles, const uint32_t* seeds);
+/* the sampled optimizer's device generator on its own: out[i * n + j] = the j-th double of mt19937ar(seeds[i]) (n <= 4000) */
+int pdmpc_debug_random_numbers(pdmpc_handle* handle, int32_t count, const uint32_t* seeds, int32_t n, double* out);
 
 /* ---- centralized control: one joint graph search over several vehicles (CentralizedController.m:34-46, GraphSearch.do_graph_search
  *      with iter.amount = N; separating-axis checker only) ----
@@ -545,6 +562,15 @@ int pdmpc_controller_set_parallel_coupling(pdmpc_controller* c, int32_t mode); /
  * runs on the bounded step-Hp sets (pdmpc_bounded_set_coupling / pdmpc_polygon_set_coupling_host).  Vehicles without lanelets
  * (the circle scenario) are not bounded.  Default off. */
 int pdmpc_controller_set_lanelet_bounding(pdmpc_controller* c, int32_t on);
+/* The optimizer of the controller's steps (OptimizerType): the graph search (default) or the sampled optimizer
+ * (MonteCarloTreeSearch.m, pdmpc_set_step_seeds + the plan calls).  pdmpc_controller_step / _run, _explore_step / _run and
+ * _optimal_step / _run follow it.  The sampled optimizer's seeds are time_step + vehicle_index (1-based, MonteCarloTreeSearch.m:31-32,
+ * PrioritizedController.m:335-341), the same for every instance of an explorative or optimal batch. */
+enum { PDMPC_OPTIMIZER_GRAPH_SEARCH = 0, PDMPC_OPTIMIZER_SAMPLED = 1 };
+int pdmpc_controller_set_optimizer(pdmpc_controller* c, int32_t which); /* PDMPC_OPTIMIZER_*; anything else: PDMPC_ERR_INVALID */
+/* the sampled optimizer's seed per slot of the last built step or batch (pdmpc_controller_build_step / _explore_build / _optimal_build),
+ * whichever optimizer is selected: *n slots, *seeds valid until the next build */
+int pdmpc_controller_seeds(pdmpc_controller* c, int32_t* n, const uint32_t** seeds);
 
 /* ---- several GPUs behind the same boundary (csrc/group.cpp) ----
  * The reference's vehicles exchange their solved areas after every computation level: each publishes a Predictions message that every

@@ -17,6 +17,7 @@
  *                            (hlc/controller/prioritized/PrioritizedSequentialController.m:86-88), n run_optimizer calls at once
  *   pdmpc_ml_plan_step       the whole double loop (:77-94) in one call: kahn.m levels from directed_coupling_sequential, the
  *                            predecessors' solved areas handed over on the device (PrioritizedController.m:476-491)
+ *   pdmpc_ml_plan_step_sampled  the same step with the sampled optimizer (MonteCarloTreeSearch.m), one launch
  *   pdmpc_ml_group_plan_step the same step over several GPUs: the per-level exchange of solved areas between the vehicles
  *                            (hlc/communication/PredictionsCommunication.m:34-63) as an RCCL all-gather between the devices
  *   pdmpc_ml_plan_joint      the centralized controller's run_optimizer call (CentralizedController.m:34-46): ONE joint search
@@ -88,6 +89,9 @@ int pdmpc_ml_plan_step(pdmpc_handle* handle, const pdmpc_ml_step* s, pdmpc_vehic
 /* ... with the expected work per VEHICLE (MATLAB's vehicle order; e.g. n_popped of each vehicle's last plan; NULL: none): the launch
  * fills its slots by priority (pdmpc_set_step_weights).  Same records. */
 int pdmpc_ml_plan_step_weighted(pdmpc_handle* handle, const pdmpc_ml_step* step, const double* weights, pdmpc_vehicle_out* out);
+/* the same step with the sampled optimizer (OptimizerType.MatlabSampled, MonteCarloTreeSearch.m; pdmpc_plan_step_sampled): seeds[v] =
+ * time_step + v of VEHICLE v (1-based, MonteCarloTreeSearch.m:31-32).  out[v] = record of vehicle v. */
+int pdmpc_ml_plan_step_sampled(pdmpc_handle* handle, const pdmpc_ml_step* step, const uint32_t* seeds, pdmpc_vehicle_out* out);
 /* the same step over the GPUs of a group (pdmpc_group_*, include/pdmpc.h): weights[v] (may be NULL) = expected work of VEHICLE v,
  * mode = PDMPC_SHARD_*; out[v] = record of vehicle v.  What PredictionsCommunication.m:34-63 does between the vehicles' processes
  * happens between the devices: an RCCL all-gather of the solved areas. */

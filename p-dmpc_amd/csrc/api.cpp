@@ -22,7 +22,6 @@
 #include <vector>
 
 #include "../../include/pdmpc.h"
-#include "mt19937ar.hpp"
 #include "../../include/pdmpc_geometry.h"
 #include "pdmpc_device.h"
 
@@ -199,6 +198,7 @@ struct PackedStep {
     uint64_t staged_serial = ~0ull;  // the handle's sync_serial when the copy out of h_blob was queued (pack_common)
     int n_packed = 0;
     bool pack_failed = false;  // the last pack into this bank did not finish: nothing to launch or fetch
+    bool sampled = false;      // packed with seeds (pdmpc_set_step_seeds): a sampled bank, its launches run the sampled optimizer
     int soup_cap = 0;
     int cand_cap = 0;  // most segments any single edge check can see (one step's soups + the boundary)
     std::vector<int64_t> lit_cols;  // per slot: literal soup + boundary columns (for the bytes formula)
@@ -329,8 +329,6 @@ struct pdmpc_handle {
     DevBuf<unsigned long long> d_help_board;  // helper workgroups (pdmpc_device.h)
     DevBuf<uint32_t> d_help_verdict, d_help_finished;
     DevBuf<double> d_bk_post;                 // records posted for the helper workgroups
-    DevBuf<double> d_random;  // sampled optimizer: random numbers of the batch
-    int sampled_n_random = 0;
     LaunchKind launch_kind = kLaunchSampled;  // of the last launch (before the first one: what pdmpc_get_last_stats always reported)
     DevBuf<int32_t> d_joint_off;         // pdmpc_plan_joint: the problems' first slots
     DevBuf<uint32_t> d_prio_count, d_prio_mask;  // pdmpc_unique_priorities: acyclic masks per tile, the acyclic masks
@@ -373,6 +371,8 @@ struct pdmpc_handle {
     std::vector<SoupKey> pack_soup_keys;  // pack_common's scratch: the distinct soup keys of the batch, the slots they were packed in, the hash table over them
     std::vector<int32_t> pack_soup_slot, pack_soup_table;
     std::vector<double> next_weights;    // pdmpc_set_step_weights: expected work per vehicle of the NEXT packed step (the caller's order); consumed by that pack
+    std::vector<uint32_t> next_seeds;    // pdmpc_set_step_seeds: the sampled optimizer's seed per vehicle of the NEXT packed step (the caller's order) ...
+    bool seeds_set = false;              // ... consumed by that pack, which makes its bank a sampled bank
     PinnedBuf<double> h_lean;            // fetch_lean: (cost, status) per slot
     DevBuf<double> d_lean;
     PinnedBuf<pdmpc_vehicle_out> h_out;  // pdmpc_fetch_results: the records land in pinned memory (a copy into the caller's pageable array goes through the runtime's staging otherwise)
@@ -523,9 +523,15 @@ int compute_lds_bulk(pdmpc_handle* h, int n_launch, int soup_cap) {
 }
 
 // LDS layout of the sampled optimizer (one wavefront per vehicle): MPA tables, reference, the wave's two shapes, offsets, obstacle
-// soup, the candidate segments of one edge check, and its tree (288 nodes x (16 children + parent + trim) x 2 B).
+// soup (with the predecessors' columns pack_common counts into soup_cap), the candidate segments of one edge check, its tree
+// (288 nodes x (16 children + parent + trim) x 2 B; the random generator's state before the tree is set up) and its Hp * 250 random
+// numbers (32 000 B at Hp 16).  80 KB first (two workgroups per CU), then the whole 160 KB (one); the automaton's areas go to L2
+// before a layout takes the larger budget.
 int compute_lds_sampled(pdmpc_handle* h, int soup_cap, int cand_cap) {
-    for (int areas = 1; areas >= 0; --areas) {
+    static_assert(288u * 16u * 2u >= 624u * 4u, "the tree region holds the generator's state");
+    for (int pass = 0; pass < 4; ++pass) {
+        const int areas = pass == 0 || pass == 2;
+        const size_t budget = pass < 2 ? kLdsMax / 2 : kLdsMax;
         LdsLayout L{};
         uint32_t off = layout_mpa(h, 0, areas, L);
         L.ref = off;
@@ -542,8 +548,10 @@ int compute_lds_sampled(pdmpc_handle* h, int soup_cap, int cand_cap) {
         off += (2 * PDMPC_HP_MAX * PDMPC_HP_MAX) * 8 + 16 * 16;
         L.tree16 = off;
         off += align16(288u * 18u * 2u);
+        L.rand = off;
+        off += align16((uint32_t)h->cfg.Hp * 250u * 8u);
         L.total = align16(off);
-        if (L.total <= kLdsMax / 2) return use_layout(h, L, 1, 0, 0, areas);
+        if (L.total <= budget) return use_layout(h, L, 1, 0, 0, areas);
     }
     return fail(PDMPC_ERR_CAPACITY, "obstacle soup + MPA tables do not fit into the LDS budget of the sampled optimizer");
 }
@@ -593,6 +601,11 @@ int pack_common(pdmpc_handle* h, int n, const pdmpc_vehicle_in* in, const int32_
     // the weights are this pack's, whether it succeeds or not: a failed pack must not leave them to reorder the next one
     const std::vector<double> weights = std::move(h->next_weights);
     h->next_weights.clear();
+    // ... and so are the seeds: a pack that fails leaves no sampled bank behind it
+    const bool sampled = h->seeds_set;
+    const std::vector<uint32_t> seeds = std::move(h->next_seeds);
+    h->next_seeds.clear();
+    h->seeds_set = false;
     if (!h->has_mpa) return fail(PDMPC_ERR_NO_MPA, "pdmpc_upload_mpa has not been called");
     if (n < 0 || (n > 0 && !in)) return fail(PDMPC_ERR_INVALID, "bad vehicle array");
     if (n > h->max_vehicles) return fail(PDMPC_ERR_CAPACITY, "batch larger than config.max_vehicles");
@@ -611,6 +624,8 @@ int pack_common(pdmpc_handle* h, int n, const pdmpc_vehicle_in* in, const int32_
     const size_t pts_base = veh_bytes + pred_bytes;
     B.n_packed = 0;  // (a pack that fails leaves the bank empty: the batch that was in it is being overwritten)
     B.pack_failed = true;
+    B.sampled = sampled;
+    if (sampled && (int)seeds.size() != n) return fail(PDMPC_ERR_INVALID, "pdmpc_set_step_seeds: the seeds are not one per vehicle of the packed step");
     B.h_veh = nullptr;
     B.h_pts = nullptr;
     B.h_pred = nullptr;
@@ -790,6 +805,7 @@ int pack_common(pdmpc_handle* h, int n, const pdmpc_vehicle_in* in, const int32_
         d.y0 = v.y0;
         d.yaw0 = v.yaw0;
         d.trim0 = v.trim0;
+        d.seed = sampled ? seeds[(size_t)vi] : 0u;
         for (int k = 0; k < Hp; ++k) {
             d.ref_x[k] = v.ref_x[k];
             d.ref_y[k] = v.ref_y[k];
@@ -947,9 +963,11 @@ int end_timed_launch(pdmpc_handle* h) {
 
 // safe == true: the recovery path after a predecessor time-out (plan_packed_growing): slices that are resident as a whole,
 // no helper workgroups next to an oversubscribed launch, the default spin limit.
-int launch_range(pdmpc_handle* h, LaunchKind kind, int first, int count, bool safe) {
+// The bank's kind decides the kernel: the graph search, or the sampled optimizer for a bank packed with seeds.
+int launch_range(pdmpc_handle* h, int first, int count, bool safe) {
     if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
     PackedStep& B = h->banks[h->bank];
+    const LaunchKind kind = B.sampled ? kLaunchSampled : kLaunchSearch;
     if (B.pack_failed) return fail(PDMPC_ERR_INVALID, "the last pack into this bank failed: nothing is packed");
     if (first < 0 || count < 0 || first + count > B.n_packed) return fail(PDMPC_ERR_INVALID, "launch range outside the packed batch");
     if (!B.perm.empty() && (first != 0 || count != B.n_packed)) return fail(PDMPC_ERR_INVALID, "range launches need a batch packed in level order (predecessors in lower slots)");
@@ -973,8 +991,6 @@ int launch_range(pdmpc_handle* h, LaunchKind kind, int first, int count, bool sa
     a.cand_cap = B.cand_cap;
     a.n_waves = h->n_waves;
     a.tie_count = h->d_tie_count.p;
-    a.sampled_random = h->d_random.p;
-    a.sampled_n_random = h->sampled_n_random;
     a.spin_limit = safe ? (1u << 22) : T.spin_limit;
     a.debug_tail = T.debug_tail;
     if (T.debug_progress && !h->progress) {
@@ -1089,7 +1105,14 @@ int launch_range(pdmpc_handle* h, LaunchKind kind, int first, int count, bool sa
     };
     int lrc = 0;
     if (!search) {
-        lrc = pdmpc_launch_sampled(&a, count, (void*)h->stream);
+        // (no arenas: the tree is the fixed 288-node tree in LDS.  Resident slices: two workgroups per CU at <= 80 KB, else one)
+        const int resident = h->lds.total <= kLdsMax / 2 ? 2 * h->n_cu : h->n_cu;
+        for (int done = 0; done < count && lrc == 0; done += safe ? resident : count) {
+            KernelArgs part = a;
+            part.first = first + done;
+            part.n_searches = safe ? std::min(resident, count - done) : count;
+            lrc = pdmpc_launch_sampled(&part, part.n_searches, (void*)h->stream);
+        }
     } else if (safe && count > h->n_cu) {
         for (int done = 0; done < count && lrc == 0; done += h->n_cu) {
             KernelArgs part = a;
@@ -1255,11 +1278,18 @@ int pdmpc_set_step_weights(pdmpc_handle* h, int32_t n, const double* weights) {
     return PDMPC_OK;
 }
 
+int pdmpc_set_step_seeds(pdmpc_handle* h, int32_t n, const uint32_t* seeds) {
+    if (!h || n < 0 || (n > 0 && !seeds)) return fail(PDMPC_ERR_INVALID, "pdmpc_set_step_seeds: bad argument");
+    h->next_seeds.assign(seeds, seeds + n);
+    h->seeds_set = true;
+    return PDMPC_OK;
+}
+
 int pdmpc_launch_packed(pdmpc_handle* h) {
     if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
     ON_DEVICE(h->cfg.device);
     h->epoch += 1;  // a new step: results of earlier launches no longer satisfy predecessor waits
-    return launch_range(h, kLaunchSearch, 0, h->banks[h->bank].n_packed, h->safe_launches);
+    return launch_range(h, 0, h->banks[h->bank].n_packed, h->safe_launches);
 }
 
 int pdmpc_set_device_share(pdmpc_handle* h, int32_t n_handles) {
@@ -1303,7 +1333,7 @@ int pdmpc_reset_stats(pdmpc_handle* h) {
 int pdmpc_launch_range(pdmpc_handle* h, int32_t first, int32_t count) {
     if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
     ON_DEVICE(h->cfg.device);
-    return launch_range(h, kLaunchSearch, first, count, h->safe_launches);
+    return launch_range(h, first, count, h->safe_launches);
 }
 
 int pdmpc_synchronize(pdmpc_handle* h) {
@@ -1446,7 +1476,7 @@ int plan_packed_growing(pdmpc_handle* h, int32_t n, const Sink& sink) {
         ON_DEVICE(h->cfg.device);
         h->epoch += 1;  // a new step: results of earlier launches no longer satisfy predecessor waits
         const auto t0 = std::chrono::steady_clock::now();
-        int rc = launch_range(h, kLaunchSearch, 0, h->banks[h->bank].n_packed, safe);
+        int rc = launch_range(h, 0, h->banks[h->bank].n_packed, safe);
         if (rc) return rc;
         const auto t1 = std::chrono::steady_clock::now();
         rc = sink.fetch(h, n);
@@ -1626,31 +1656,24 @@ int pdmpc_arena_nodes(pdmpc_handle* h, int32_t* max_nodes, int64_t* regrows) {
     return PDMPC_OK;
 }
 
-namespace {
-// what MATLAB's rand(RandStream('mt19937ar', Seed = s), 1, n) draws (MonteCarloTreeSearch.m:32,53)
-void mt19937ar_doubles(uint32_t seed, int n, double* out) {
-    Mt19937ar rng(seed);
-    for (int i = 0; i < n; ++i) out[i] = rng.rand();
-}
-}  // namespace
-
+// One computation level: a sampled bank without predecessors (the kernel draws every slot's random numbers itself).
 int pdmpc_plan_batch_sampled(pdmpc_handle* h, int32_t n, const pdmpc_vehicle_in* in, const uint32_t* seeds, pdmpc_vehicle_out* out) {
     if (!h || n < 0 || (n > 0 && (!in || !seeds || !out))) return fail(PDMPC_ERR_INVALID, "null argument");
-    int rc = pdmpc_pack_batch(h, n, in);
+    int rc = pdmpc_set_step_seeds(h, n, seeds);
     if (rc) return rc;
+    if ((rc = pdmpc_pack_batch(h, n, in))) return rc;
     if (n == 0) return PDMPC_OK;
     ON_DEVICE(h->cfg.device);
-    const int per = h->cfg.Hp * 250;  // Hp * n_expansions_max                             MonteCarloTreeSearch.m:53
-    std::vector<double> rnd((size_t)n * per);
-    for (int i = 0; i < n; ++i) mt19937ar_doubles(seeds[i], per, rnd.data() + (size_t)i * per);
-    if (h->d_random.ensure(rnd.size())) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the random numbers");
-    HIPCHK(hipMemcpyAsync(h->d_random.p, rnd.data(), rnd.size() * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));  // (rnd goes out of scope)
-    h->sampled_n_random = per;
-    h->epoch += 1;  // a new step: results of earlier launches no longer satisfy predecessor waits
-    rc = launch_range(h, kLaunchSampled, 0, h->banks[h->bank].n_packed, h->safe_launches);
-    if (rc) return rc;
-    return pdmpc_fetch_results(h, n, out);
+    return plan_packed_growing(h, n, Sink::records(out));
+}
+
+// A whole time step of the sampled optimizer: seeds for the next pack, then pdmpc_plan_step (one launch; predecessors' areas handed
+// over on the device; the recovery in resident slices after a watchdog time-out).
+int pdmpc_plan_step_sampled(pdmpc_handle* h, int32_t n, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index,
+                            const pdmpc_polygon_set* fallback_shapes, const uint32_t* seeds, pdmpc_vehicle_out* out) {
+    if (!h || n < 0 || (n > 0 && (!seeds || !out))) return fail(PDMPC_ERR_INVALID, "pdmpc_plan_step_sampled: bad argument");
+    const int rc = pdmpc_set_step_seeds(h, n, seeds);
+    return rc ? rc : pdmpc_plan_step(h, n, in, pred_offset, pred_index, fallback_shapes, out);
 }
 
 int pdmpc_plan_joint(pdmpc_handle* h, int32_t n_problems, const int32_t* problem_offset, const pdmpc_vehicle_in* in, pdmpc_vehicle_out* out) {
@@ -2158,6 +2181,21 @@ int pdmpc_get_last_stats(pdmpc_handle* h, pdmpc_stats* stats) {
     h->stats.safe_replans = h->safe_replans;
     h->stats.bad_status_plans = (int64_t)work[6];
     *stats = h->stats;
+    return PDMPC_OK;
+}
+
+int pdmpc_debug_random_numbers(pdmpc_handle* h, int32_t count, const uint32_t* seeds, int32_t n, double* out) {
+    if (!h || count < 0 || n < 0 || n > 4000 || (count > 0 && n > 0 && (!seeds || !out))) return fail(PDMPC_ERR_INVALID, "pdmpc_debug_random_numbers: bad argument");
+    if (count == 0 || n == 0) return PDMPC_OK;
+    ON_DEVICE(h->cfg.device);
+    DevBuf<uint32_t> d_seeds;
+    DevBuf<double> d_out;
+    if (d_seeds.ensure_exact((size_t)count) | d_out.ensure_exact((size_t)count * n)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the generator test");
+    HIPCHK(hipMemcpy(d_seeds.p, seeds, (size_t)count * 4, hipMemcpyHostToDevice));
+    const int lrc = pdmpc_launch_debug_mt19937(d_seeds.p, count, n, d_out.p, (void*)h->stream);
+    if (lrc != 0) return fail(PDMPC_ERR_HIP, "generator launch failed");
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(out, d_out.p, (size_t)count * n * 8, hipMemcpyDeviceToHost));
     return PDMPC_OK;
 }
 

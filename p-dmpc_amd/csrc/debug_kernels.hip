@@ -17,6 +17,7 @@ namespace {
 #include "search_state.hpp"
 #include "heap_queue.hpp"
 #include "edge_checks.hpp"
+#include "mt19937_device.hpp"
 }  // namespace
 
 #define DBG_MAX_B 1024
@@ -83,6 +84,26 @@ extern "C" int pdmpc_launch_edge_check(int mode, int n_cases, const int32_t* a_o
                                        const double* b_y, int32_t* hit, void* stream) {
     if (n_cases <= 0) return 0;
     hipLaunchKernelGGL(pdmpc_edge_check_kernel, dim3(n_cases), dim3(PDMPC_WAVE), 0, (hipStream_t)stream, mode, n_cases, a_off, a_x, a_y, b_off, b_x, b_y, hit);
+    return (int)hipGetLastError();
+}
+
+// The sampled optimizer's random numbers on their own: workgroup i writes the first n doubles of mt19937ar(seeds[i]) to out[i][0 .. n),
+// by the device function the sampled kernel calls (mt19937_device.hpp), into LDS first as there.
+#define DBG_MT_MAX 4000 /* Hp * 250 at PDMPC_HP_MAX = 16 */
+extern "C" __global__ __launch_bounds__(PDMPC_WAVE) void pdmpc_debug_random_numbers_kernel(const uint32_t* seeds, int n, double* out) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[624 * 4 + DBG_MT_MAX * 8];
+    LDS_AS unsigned char* lsm = (LDS_AS unsigned char*)smem;
+    lds_u32* mt = (lds_u32*)lsm;
+    lds_f64* l_rand = (lds_f64*)(lsm + 624 * 4);
+    const int lane = threadIdx.x;
+    mt19937_doubles_wave(seeds[blockIdx.x], n, mt, l_rand, lane);
+    for (int i = lane; i < n; i += PDMPC_WAVE) out[(size_t)blockIdx.x * n + i] = l_rand[i];
+}
+
+extern "C" int pdmpc_launch_debug_mt19937(const uint32_t* seeds, int count, int n, double* out, void* stream) {
+    if (count <= 0 || n <= 0) return 0;
+    if (n > DBG_MT_MAX) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(pdmpc_debug_random_numbers_kernel, dim3(count), dim3(PDMPC_WAVE), 0, (hipStream_t)stream, seeds, n, out);
     return (int)hipGetLastError();
 }
 

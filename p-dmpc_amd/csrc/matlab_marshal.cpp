@@ -302,6 +302,20 @@ int pdmpc_ml_plan_step_weighted(pdmpc_handle* h, const pdmpc_ml_step* s, const d
     return pdmpc_ml_plan_step(h, s, out);
 }
 
+int pdmpc_ml_plan_step_sampled(pdmpc_handle* h, const pdmpc_ml_step* s, const uint32_t* seeds, pdmpc_vehicle_out* out) {
+    if (!h || !s || (s->n > 0 && (!seeds || !out))) return ml_fail(PDMPC_ERR_INVALID, "pdmpc_ml_plan_step_sampled: null argument");
+    std::vector<uint32_t> sd((size_t)std::max(s->n, 1));  // (per vehicle -> per slot of the step as it is handed to pdmpc_plan_step_sampled)
+    for (int sl = 0; sl < s->n; ++sl) sd[(size_t)sl] = seeds[(size_t)s->order[(size_t)sl] - 1];
+    std::vector<pdmpc_vehicle_out> slots((size_t)std::max(s->n, 1));
+    const int rc = pdmpc_plan_step_sampled(h, s->n, s->in.data(), s->pred_offset.data(), s->pred_index.data(), s->any_fallback ? s->fallback.data() : nullptr, sd.data(), slots.data());
+    if (rc) {
+        g_ml_err = pdmpc_last_error();
+        return rc;
+    }
+    for (int sl = 0; sl < s->n; ++sl) out[(size_t)s->order[(size_t)sl] - 1] = slots[(size_t)sl];
+    return PDMPC_OK;
+}
+
 int pdmpc_ml_group_plan_step(pdmpc_group* g, const pdmpc_ml_step* s, const double* weights, int32_t mode, pdmpc_vehicle_out* out) {
     if (!g || !s || (s->n > 0 && !out)) return ml_fail(PDMPC_ERR_INVALID, "pdmpc_ml_group_plan_step: null argument");
     std::vector<pdmpc_vehicle_out> slots((size_t)std::max(s->n, 1));

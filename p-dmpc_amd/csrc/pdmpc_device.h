@@ -47,7 +47,7 @@ struct DevVehicle {
     int32_t lit_off[PDMPC_HP_MAX + 1];  // literal vehicle-obstacle soup of step k: points[lit_off[k] .. lit_off[k+1])
     int32_t hdv_off[PDMPC_HP_MAX + 1];  // literal HDV soup of step k
     int32_t fb_off[PDMPC_HP_MAX + 1];   // fallback areas (one polygon per step, no separators); fb_off[0] < 0: none
-    int32_t pad;
+    uint32_t seed;                      // sampled optimizer: RandStream('mt19937ar', Seed = seed) (MonteCarloTreeSearch.m:32)
 };
 
 // One search-tree node (Tree.m:3-13 row + what the check of this node's children needs), 64 bytes so a node is four
@@ -76,6 +76,7 @@ struct LdsLayout {
     uint32_t vstate;                       // uint8[NV]: validity bytes
     uint32_t expand;                       // d_traveled table: dcum[16][16] doubles (+ the sampled optimizer's expansion scratch)
     uint32_t tree16;                       // sampled optimizer: its tree (children, parent, trim as uint16)
+    uint32_t rand;                         // sampled optimizer: its Hp * 250 random numbers (double)
     uint32_t nodes;                        // NodeRec[NL]
     uint32_t total;
     uint32_t bk_near_key, bk_near_id;      // double[BK_PER * threads], uint32[BK_PER * threads]: the LDS part of the open set (the heap of a replay)
@@ -205,8 +206,6 @@ struct KernelArgs {
     LdsLayout lds;
     int32_t NL, NV, soup_cap, cand_cap;
     int32_t n_waves;                   // wavefronts per workgroup of this launch (workgroup size / 64)
-    const double* sampled_random;      // sampled optimizer: [max_vehicles][sampled_n_random] mt19937ar doubles (host-generated)
-    int32_t sampled_n_random;
     unsigned long long* work_count;    // [0] edge checks evaluated, [1] segment pairs they stand for, [2] nodes processed, [3] rounds, [4] shared rounds, [5] nodes checked by helpers, [6] plans that are not planning results (cumulative, all vehicles)
     int32_t* tie_count;                // [0] searches that ended on the binary heap (equal keys), [2] arrival events (cumulative)
     uint32_t* progress;    // host-mapped (pinned) words, 64 per slot: live counters, for debugging a launch that does not end (or null)
@@ -360,6 +359,8 @@ int pdmpc_launch_bulk_compact(const KernelArgs* args, int count, void* stream, u
 int pdmpc_launch_gather_lean(const pdmpc_vehicle_out* out, int n, int Hp, double* lean, void* stream);
 // sampled_kernel.hip: the sampled optimizer (MonteCarloTreeSearch.m), `count` workgroups of one wavefront
 int pdmpc_launch_sampled(const KernelArgs* args, int count, void* stream);
+// debug_kernels.hip: the first n doubles of mt19937ar(seeds[i]) for every i, by the sampled kernel's device generator (out: [count][n])
+int pdmpc_launch_debug_mt19937(const uint32_t* seeds, int count, int n, double* out, void* stream);
 // debug_kernels.hip: the open-list command script on one wavefront, and the collision primitives on given polygons (one wavefront per case)
 int pdmpc_launch_heap_script(const int32_t* op, const int32_t* id, const double* key, int n, int32_t* out, unsigned long long* stats, double* gkey, uint32_t* gid, int HL,
                              void* stream);

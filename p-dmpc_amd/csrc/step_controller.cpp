@@ -92,6 +92,8 @@ struct pdmpc_controller {
     double timing_sum[6] = {0, 0, 0, 0, 0, 0};  // ... summed over the steps since the last pdmpc_controller_timing_sum(reset)
     int64_t timing_steps = 0;
     std::vector<double> last_pops;  // per vehicle: nodes its search popped in the last step (the next step's expected work, pdmpc_set_step_weights)
+    int optimizer = PDMPC_OPTIMIZER_GRAPH_SEARCH;  // pdmpc_controller_set_optimizer
+    std::vector<uint32_t> seeds;    // per slot of the last built step or batch: time_step + vehicle_index (the sampled optimizer's seeds)
     // per step
     std::vector<int32_t> trims;
     std::vector<Poly> occ_offset, occ_plain;
@@ -832,6 +834,20 @@ int pdmpc_controller_set_parallel_coupling(pdmpc_controller* c, int32_t mode) {
     return PDMPC_OK;
 }
 
+int pdmpc_controller_set_optimizer(pdmpc_controller* c, int32_t which) {
+    if (!c) return cfail(c, PDMPC_ERR_INVALID, "null controller");
+    if (which != PDMPC_OPTIMIZER_GRAPH_SEARCH && which != PDMPC_OPTIMIZER_SAMPLED) return cfail(c, PDMPC_ERR_INVALID, "optimizer must be PDMPC_OPTIMIZER_GRAPH_SEARCH or PDMPC_OPTIMIZER_SAMPLED");
+    c->optimizer = which;
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_seeds(pdmpc_controller* c, int32_t* n, const uint32_t** seeds) {
+    if (!c || !n || !seeds) return cfail(c, PDMPC_ERR_INVALID, "null argument");
+    *n = (int32_t)c->seeds.size();
+    *seeds = c->seeds.data();
+    return PDMPC_OK;
+}
+
 int pdmpc_controller_set_lanelet_bounding(pdmpc_controller* c, int32_t on) {
     if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
     c->lanelet_bounding = on != 0;
@@ -875,6 +891,21 @@ int pdmpc_controller_destroy(pdmpc_controller* c) {
 namespace {
 int assemble_step(pdmpc_controller* c, bool seq_given = false);
 }
+
+namespace {
+// RandStream('mt19937ar', Seed = time_step + vehicle_index) of every slot (MonteCarloTreeSearch.m:31-32; PrioritizedController.m:335-341
+// calls run_optimizer with obj.k, so every instance of a batch draws the same stream for the same vehicle)
+void set_seeds(pdmpc_controller* c, const std::vector<int32_t>& vehicle_of_slot) {
+    c->seeds.resize(vehicle_of_slot.size());
+    for (size_t s = 0; s < vehicle_of_slot.size(); ++s) c->seeds[s] = (uint32_t)(c->k + vehicle_of_slot[s] + 1);
+}
+// the seeds of the problem about to be planned, for the next pack (a sampled bank); nothing for the graph search
+int seeds_for_next_pack(pdmpc_controller* c) {
+    if (c->optimizer != PDMPC_OPTIMIZER_SAMPLED) return PDMPC_OK;
+    const int rc = pdmpc_set_step_seeds(c->h, (int32_t)c->seeds.size(), c->seeds.data());
+    return rc ? cfail(c, rc, pdmpc_last_error()) : PDMPC_OK;
+}
+}  // namespace
 
 int pdmpc_controller_build_step(pdmpc_controller* c) {
     if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
@@ -1067,7 +1098,10 @@ int pdmpc_controller_build_step(pdmpc_controller* c) {
             for (int j = 0; j < n; ++j)
                 if (at(c->adjacency, n, i, j) && !(j < i)) at(c->directed, n, i, j) = 1;
     }
-    return assemble_step(c);
+    const int rc = assemble_step(c);
+    if (rc) return rc;
+    set_seeds(c, c->order);
+    return PDMPC_OK;
 }
 
 namespace {
@@ -1397,6 +1431,7 @@ int pdmpc_controller_step(pdmpc_controller* c) {
         for (int s = 0; s < c->n; ++s) w[(size_t)s] = c->last_pops[(size_t)c->order[(size_t)s]] + 1.0;
         (void)pdmpc_set_step_weights(c->h, c->n, w.data());
     }
+    if ((rc = seeds_for_next_pack(c))) return rc;
     rc = pdmpc_plan_step(c->h, c->n, c->in.data(), c->pred_offset.data(), c->pred_index.data(), c->fb.data(), c->out.data());
     if (rc) return cfail(c, rc, pdmpc_last_error());
     add_call_timing(c);
@@ -1626,6 +1661,7 @@ int pdmpc_controller_explore_build(pdmpc_controller* c, int32_t n_perm, uint32_t
         keep_instance(c, p);
     }
     flatten_instances(c, n_perm);
+    set_seeds(c, c->x_vehicle);
     return PDMPC_OK;
 }
 
@@ -1726,7 +1762,8 @@ int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, boo
         for (int i = 0; i < N; ++i) w[(size_t)i] = c->last_pops[(size_t)c->x_vehicle[(size_t)i]] + 1.0;
         (void)pdmpc_set_step_weights(c->h, N, w.data());
     }
-    int rc;
+    int rc = seeds_for_next_pack(c);
+    if (rc) return rc;
     if (c->lean_explore) {
         // the closed loop keeps the chosen plans only (obj.iter = obj.iter_array_tmp{chosen_solution}, :157-158): status and final
         // cost of every plan come back for the choice, the chosen vehicles' records afterwards — not 2.9 KB for each of the N plans
@@ -1912,6 +1949,7 @@ int pdmpc_controller_optimal_build(pdmpc_controller* c, int32_t max_instances) {
         keep_instance(c, p);
     }
     flatten_instances(c, (int)K);
+    set_seeds(c, c->x_vehicle);
     return PDMPC_OK;
 }
 

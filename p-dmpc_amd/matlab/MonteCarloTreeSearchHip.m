@@ -38,9 +38,19 @@ classdef MonteCarloTreeSearchHip < OptimizerInterface
                 obj.mpa_uploaded = true;
             end
 
-            Hp = options.Hp;
-            info = ControlResultsInfo(iter.amount, Hp);
             out = pdmpc_mex('plan_sampled', obj.handle, pdmpc_iter_struct(iter), time_step + vehicle_index);
+            info = MonteCarloTreeSearchHip.info_from_record(options, out);
+        end
+
+    end
+
+    methods (Static)
+
+        function info = info_from_record(options, out)
+            % ControlResultsInfo of a sampled record (one vehicle): what run_optimizer returns, and what
+            % PrioritizedSequentialHipController's step (pdmpc_mex('plan_step_sampled', ...)) hands to finish_step_plan
+            Hp = options.Hp;
+            info = ControlResultsInfo(1, Hp);
 
             info.n_expanded = out.n_expanded; % MonteCarloTreeSearch.m:209
             info.is_exhausted = out.status ~= 0; % :212-215

@@ -109,6 +109,10 @@ classdef PrioritizedSequentialHipController < PrioritizedSequentialController
                 % the levels of a shared component as an all-gather (pdmpc_group_plan_step); same records
                 outs = pdmpc_mex('group_plan_step', obj.handle, iters, double(directed_coupling_sequential), fallback_areas, obj.last_work, obj.shard_mode);
                 obj.last_work = double([outs.n_expanded]);
+            elseif options.optimizer_type == OptimizerType.HipSampled
+                % the sampled optimizer (MonteCarloTreeSearch.m), the whole step in one launch as well: vehicle v draws from
+                % RandStream('mt19937ar', Seed = k + v) (:31-32, called with obj.k by PrioritizedController.m:335-341)
+                outs = pdmpc_mex('plan_step_sampled', obj.handle, iters, double(directed_coupling_sequential), fallback_areas, obj.hlcs(1).k);
             else
                 % (the work of every vehicle's last search as the expected work of this one: the launch hands its searches out by
                 % priority, heavy ones and their predecessors first — pdmpc_set_step_weights; results are the same bit for bit)
@@ -167,7 +171,11 @@ end
 %
 %   function finish_step_plan(obj, iter_v, out)
 %       obj.timing.start('plan', obj.k);
-%       obj.info = GraphSearchHip.info_from_record(iter_v, obj.options, out);   % the tail of GraphSearchHip.run_optimizer
+%       if obj.options.optimizer_type == OptimizerType.HipSampled
+%           obj.info = MonteCarloTreeSearchHip.info_from_record(obj.options, out);  % the tail of MonteCarloTreeSearchHip.run_optimizer
+%       else
+%           obj.info = GraphSearchHip.info_from_record(iter_v, obj.options, out);   % the tail of GraphSearchHip.run_optimizer
+%       end
 %       if obj.info.is_exhausted                                                % :344-352
 %           obj.info = obj.handle_graph_search_exhaustion(obj.info, iter_v);
 %           if obj.info.needs_fallback

@@ -13,6 +13,9 @@
 //     outs = pdmpc_mex('plan_step', h, iter_structs, directed_coupling_sequential, fallback_areas [, weights])
 //                                                                  ALL levels of a time step in one launch
 //                                                                  (PrioritizedSequentialHipController.m)
+//     outs = pdmpc_mex('plan_step_sampled', h, iter_structs, directed_coupling_sequential, fallback_areas, time_step)
+//                                                                  the same step with the sampled optimizer: vehicle v draws
+//                                                                  from mt19937ar(time_step + v) (MonteCarloTreeSearch.m:31-32)
 //            pdmpc_mex('destroy', h)
 // iter_struct(s): struct (array) with fields x0, trim_index, reference_trajectory_points (Hp x 2), v_ref, obstacles (cell),
 // dynamic_obstacle_area (n_d x Hp cell), lanelet_boundary (1 x 2 cell), hdv_reachable_sets (n_h x Hp cell).
@@ -211,14 +214,14 @@ public:
             outputs[0] = records(out, Hp);
             return;
         }
-        if (cmd == "plan" || cmd == "plan_sampled" || cmd == "plan_level" || cmd == "plan_step" || cmd == "group_plan_step") {
+        if (cmd == "plan" || cmd == "plan_sampled" || cmd == "plan_level" || cmd == "plan_step" || cmd == "plan_step_sampled" || cmd == "group_plan_step") {
             Pins pins;
             const StructArray iters = inputs[2];
             const size_t n = iters.getNumberOfElements();
             std::vector<pdmpc_ml_iter> its;
             for (size_t i = 0; i < n; ++i) its.push_back(iter_from_struct(iters, i, pins));
             std::vector<pdmpc_vehicle_out> out(n);
-            if (cmd == "plan_step" || cmd == "group_plan_step") {
+            if (cmd == "plan_step" || cmd == "plan_step_sampled" || cmd == "group_plan_step") {
                 const pdmpc_ml_matrix seq = pins.matrix(inputs[3]);  // n x n directed_coupling_sequential
                 // pdmpc_ml_step_create indexes seq[i + j * n] and fallback[v + k * n]: anything smaller reads outside MATLAB's arrays,
                 // and an empty coupling matrix would silently plan the step without couplings
@@ -236,6 +239,13 @@ public:
                     if (w.data != nullptr && (size_t)w.rows * (size_t)w.cols != n) fail("group_plan_step", "weights must hold one value per vehicle");
                     const int32_t mode = inputs.size() > 6 ? (int32_t)inputs[6][0] : PDMPC_SHARD_AUTO;
                     rc = pdmpc_ml_group_plan_step(group, step, w.data, mode, out.data());
+                } else if (cmd == "plan_step_sampled") {
+                    // 5th argument: the time step k; vehicle v (1-based) draws from RandStream('mt19937ar', Seed = k + v)
+                    if (inputs.size() < 6 || inputs[5].isEmpty()) fail("plan_step_sampled", "the time step is missing");
+                    const double k = (double)inputs[5][0];
+                    std::vector<uint32_t> seeds(std::max<size_t>(n, 1));
+                    for (size_t v = 0; v < n; ++v) seeds[v] = (uint32_t)(k + (double)(v + 1));
+                    rc = pdmpc_ml_plan_step_sampled(h, step, seeds.data(), out.data());
                 } else {
                     // optional 5th argument: 1 x n expected work per vehicle (e.g. the n_popped of its last plan), [] = none: the launch
                     // fills its slots by priority (pdmpc_ml_plan_step_weighted -> pdmpc_set_step_weights)
@@ -244,7 +254,7 @@ public:
                     rc = pdmpc_ml_plan_step_weighted(h, step, w.data, out.data());
                 }
                 pdmpc_ml_step_destroy(step);
-                if (rc != PDMPC_OK) fail(group ? "pdmpc_ml_group_plan_step" : "pdmpc_ml_plan_step", pdmpc_ml_last_error());
+                if (rc != PDMPC_OK) fail(group ? "pdmpc_ml_group_plan_step" : (cmd == "plan_step_sampled" ? "pdmpc_ml_plan_step_sampled" : "pdmpc_ml_plan_step"), pdmpc_ml_last_error());
             } else if (cmd == "plan_sampled") {
                 pdmpc_ml_step* step = nullptr;
                 if (pdmpc_ml_step_create((int32_t)Hp, (int32_t)n, its.data(), nullptr, nullptr, &step) != PDMPC_OK) fail("pdmpc_ml_step_create", pdmpc_ml_last_error());

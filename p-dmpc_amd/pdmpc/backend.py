@@ -112,6 +112,11 @@ EXPORTS = [
     "pdmpc_polygon_set_coupling_host",
     "pdmpc_bounded_reachable_kernel_ms",
     "pdmpc_controller_set_lanelet_bounding",
+    "pdmpc_plan_step_sampled",
+    "pdmpc_set_step_seeds",
+    "pdmpc_debug_random_numbers",
+    "pdmpc_controller_set_optimizer",
+    "pdmpc_controller_seeds",
     "pdmpc_last_error",
     "pdmpc_version",
 ]
@@ -318,6 +323,10 @@ def load_library(path=None):
     L.pdmpc_export_results_async.argtypes = [H, C.c_int32, C.c_int32, C.c_void_p]
     L.pdmpc_stream.argtypes = [H, C.POINTER(C.c_void_p)]
     L.pdmpc_plan_batch_sampled.argtypes = [H, C.c_int32, C.POINTER(abi.VehicleIn), C.POINTER(C.c_uint32), C.POINTER(abi.VehicleOut)]
+    L.pdmpc_plan_step_sampled.argtypes = [H, C.c_int32, C.POINTER(abi.VehicleIn), abi.c_int32_p, abi.c_int32_p, C.POINTER(abi.PolygonSet), C.POINTER(C.c_uint32),
+                                          C.POINTER(abi.VehicleOut)]
+    L.pdmpc_set_step_seeds.argtypes = [H, C.c_int32, C.POINTER(C.c_uint32)]
+    L.pdmpc_debug_random_numbers.argtypes = [H, C.c_int32, C.POINTER(C.c_uint32), C.c_int32, abi.c_double_p]
     L.pdmpc_plan_joint.argtypes = [H, C.c_int32, abi.c_int32_p, C.POINTER(abi.VehicleIn), C.POINTER(abi.VehicleOut)]
     L.pdmpc_get_last_stats.argtypes = [H, C.POINTER(abi.Stats)]
     L.pdmpc_debug_heap_script.argtypes = [H, C.c_int32, abi.c_int32_p, abi.c_int32_p, abi.c_double_p, C.c_int32, abi.c_int32_p, abi.c_int32_p, abi.c_double_p, abi.c_double_p]
@@ -550,6 +559,33 @@ class Handle:
         _check(self.L, self.L.pdmpc_plan_batch_sampled(self.h, n, arr, sd, abi.out_ptr(out)), "pdmpc_plan_batch_sampled")
         del keep
         return out[:n]
+
+    def plan_step_sampled(self, iters, predecessors, fallback_shapes, seeds):
+        """A whole time step of the sampled optimizer in one call (pdmpc_plan_step_sampled): arguments as for plan_step, seeds[i] =
+        time_step + vehicle_index of vehicle i (MonteCarloTreeSearch.m:32)."""
+        n = len(iters)
+        arr, off, idx, fb, keep = self._step_args(iters, predecessors, fallback_shapes)
+        out = abi.out_array(n)
+        sd = (C.c_uint32 * max(n, 1))(*[int(s) for s in seeds])
+        _check(
+            self.L,
+            self.L.pdmpc_plan_step_sampled(self.h, n, arr, off.ctypes.data_as(abi.c_int32_p), idx.ctypes.data_as(abi.c_int32_p), fb, sd, abi.out_ptr(out)),
+            "pdmpc_plan_step_sampled",
+        )
+        del keep
+        return self._checked(out[:n])
+
+    def set_step_seeds(self, seeds):
+        """Seeds of the next packed step (pdmpc_set_step_seeds): that pack makes a sampled bank, whose launches run the sampled optimizer."""
+        sd = (C.c_uint32 * max(len(seeds), 1))(*[int(s) for s in seeds])
+        _check(self.L, self.L.pdmpc_set_step_seeds(self.h, len(seeds), sd), "pdmpc_set_step_seeds")
+
+    def debug_random_numbers(self, seeds, n):
+        """The sampled kernel's device generator on its own (pdmpc_debug_random_numbers) -> (len(seeds), n) doubles."""
+        sd = (C.c_uint32 * max(len(seeds), 1))(*[int(s) for s in seeds])
+        out = np.zeros(max(len(seeds) * n, 1))
+        _check(self.L, self.L.pdmpc_debug_random_numbers(self.h, len(seeds), sd, int(n), out.ctypes.data_as(abi.c_double_p)), "pdmpc_debug_random_numbers")
+        return out[: len(seeds) * n].reshape(len(seeds), n)
 
     def plan_joint(self, problems):
         """Centralized control: list of problems, each a list of 1 to JOINT_MAX VehicleIter, one joint search per problem ->

@@ -148,6 +148,7 @@ def flatten_instances(parts):
     lv = np.array(out["levels"])
     out["level_sizes"] = [int(np.sum(lv == l)) for l in range(1, int(lv.max()) + 1)]
     out["directed_seq"] = [prob["directed_seq"] for prob in parts]
+    out["time_step"] = parts[0].get("time_step")  # (the seeds of the sampled optimizer: time_step + vehicle, the same in every instance)
     return out
 
 

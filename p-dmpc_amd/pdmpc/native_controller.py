@@ -17,6 +17,7 @@ COUPLING = {"full": 0, "distance": 1, "none": 2, "reachable_set": 3}
 PARALLEL_PREVIOUS_TRAJECTORY, PARALLEL_REACHABLE_SETS = 0, 1
 PRIORITY = {"constant": 0, "coloring": 1}
 WEIGHT = {"distance": 0, "constant": 1}
+OPTIMIZER = {"graph_search": 0, "sampled": 1}  # PDMPC_OPTIMIZER_*
 SUCCESSOR = {ConstraintFromSuccessor.none: 0, ConstraintFromSuccessor.area_of_standstill: 1, ConstraintFromSuccessor.area_of_previous_trajectory: 2}
 
 
@@ -99,7 +100,7 @@ def _polys(ps):
 
 
 class NativeController:
-    def __init__(self, options, scenario, mpa, handle=None, coupling="full", priority_strategy="constant", weight_strategy="distance"):
+    def __init__(self, options, scenario, mpa, handle=None, coupling="full", priority_strategy="constant", weight_strategy="distance", optimizer="graph_search"):
         if scenario.dynamic_obstacle_area:
             raise ValueError("the native controller takes static scenario obstacles only")
         self.L = _declare(load_library())
@@ -163,6 +164,23 @@ class NativeController:
             self._check(self.L.pdmpc_controller_set_parallel_coupling(self.c, PARALLEL_REACHABLE_SETS), "pdmpc_controller_set_parallel_coupling")
         if options.bound_reachable_sets:
             self._check(self.L.pdmpc_controller_set_lanelet_bounding(self.c, 1), "pdmpc_controller_set_lanelet_bounding")
+        if optimizer != "graph_search":
+            self.set_optimizer(optimizer)
+
+    def set_optimizer(self, which):
+        """"graph_search" (default) or "sampled" (pdmpc_controller_set_optimizer): what step / run, explore_* and optimal_* plan with."""
+        self.L.pdmpc_controller_set_optimizer.argtypes = [C.c_void_p, C.c_int32]
+        self.L.pdmpc_controller_set_optimizer.restype = C.c_int
+        self._check(self.L.pdmpc_controller_set_optimizer(self.c, OPTIMIZER[which] if isinstance(which, str) else int(which)), "pdmpc_controller_set_optimizer")
+
+    def seeds(self):
+        """The sampled optimizer's seed per slot of the last built step or batch (pdmpc_controller_seeds)."""
+        self.L.pdmpc_controller_seeds.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.POINTER(C.c_uint32))]
+        self.L.pdmpc_controller_seeds.restype = C.c_int
+        n = C.c_int32()
+        p = C.POINTER(C.c_uint32)()
+        self._check(self.L.pdmpc_controller_seeds(self.c, C.byref(n), C.byref(p)), "pdmpc_controller_seeds")
+        return [int(p[i]) for i in range(n.value)]
 
     def _check(self, rc, what):
         if rc != 0:
