@@ -435,13 +435,36 @@ int pdmpc_polygon_set_coupling_host(const pdmpc_polygon_set* sets, int32_t n, ui
 /* kernel times (HIP events, ms) of the last pdmpc_bound_reachable_sets and pdmpc_bounded_set_coupling: ms2[0] bounding, ms2[1] coupling */
 int pdmpc_bounded_reachable_kernel_ms(pdmpc_handle* handle, double* ms2);
 
+/* ---- future collision assessment (FcaPrioritizer.m:11-92; csrc/fca.cpp, csrc/fca_kernel.hip) ----
+ * Vehicle v's footprint at step k is the box [-1,-1,1,1]·(length/2 + offset), [-1,1,1,-1]·(width/2 + offset) rotated by
+ * (cos_yaw, sin_yaw)[v * Hp + k] and moved to (x, y)[v * Hp + k], its reference point (calculate_yaw of the reference points, central
+ * differences with one-sided ends, and its cos / sin are the caller's: the footprints are built from the caller's libm).  Counted
+ * with intersect_sat (intersect_sat.m:1-42), per step k:
+ *   every coupled pair (pairs[2 p], pairs[2 p + 1]) that meets counts once for each of its two vehicles;
+ *   every vehicle v < n - 1 (the reference's outer loop stops at n - 1) counts once per static obstacle (obstacles, or NULL) and once
+ *   per dynamic obstacle row r (polygon r * Hp + k of dynamic_rows, or NULL; n_polygons a multiple of Hp) that its footprint meets.
+ * pairs: n_pairs coupled pairs a < b, ascending by (a, b), no repeats.  Out: collisions[n], and priorities[n] = the index vector
+ * (1-based) of a stable descending sort of the counts — what the reference passes to directed_coupling_from_priorities as it is.
+ * PDMPC_ERR_INVALID for n < 1, Hp < 2 (the yaw needs two points), a malformed pair list or an empty polygon.
+ * pdmpc_fca_collisions runs on the handle's device (buffers kept on the handle: one copy in, one copy out); pdmpc_fca_collisions_host
+ * is its C++ twin and checker (no GPU needed).  The counts are integers: both give the same counts in any order of the tests. */
+int pdmpc_fca_collisions(pdmpc_handle* handle, int32_t n, int32_t Hp, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw,
+                         int32_t n_pairs, const int32_t* pairs, const pdmpc_polygon_set* obstacles, const pdmpc_polygon_set* dynamic_rows, double length,
+                         double width, double offset, int32_t* collisions, int32_t* priorities);
+int pdmpc_fca_collisions_host(int32_t n, int32_t Hp, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw, int32_t n_pairs,
+                              const int32_t* pairs, const pdmpc_polygon_set* obstacles, const pdmpc_polygon_set* dynamic_rows, double length, double width,
+                              double offset, int32_t* collisions, int32_t* priorities);
+/* kernel time (HIP events, ms) of the last pdmpc_fca_collisions */
+int pdmpc_fca_kernel_ms(pdmpc_handle* handle, double* ms);
+
 /* ---- the caller's side of the boundary, natively (csrc/step_controller.cpp) ----
  * One MPC time step of the prioritized sequential controller around pdmpc_plan_step, without any interpreter in the loop:
  * traffic info, coupling, priorities, grouping, computation levels, obstacle assembly, ONE launch, exhaustion handling,
  * fallbacks, plant update (HighLevelController.main_control_loop, hlc/controller/HighLevelController.m:334-373;
  * PrioritizedSequentialController.controller, hlc/controller/prioritized/PrioritizedSequentialController.m:77-94;
  * PrioritizedController.m:297-324,375-389,449-718; plant/Simulation.m:86-100).  p-dmpc_amd/pdmpc/controller.py is the same
- * logic in Python (it also offers the random and FCA prioritizers); the two build bit-identical step problems. */
+ * logic in Python; the two build bit-identical step problems with every priority and weight strategy below.  FCA priorities run on
+ * the device (pdmpc_fca_collisions) for a controller with a handle, on the host twin without one. */
 enum { PDMPC_COUPLING_FULL = 0, PDMPC_COUPLING_DISTANCE = 1, PDMPC_COUPLING_NONE = 2 };          /* Coupler.m:31-32, DistanceCoupler.m:15-50 */
 enum { PDMPC_COUPLING_REACHABLE_SET = 3 };                                                     /* ReachableSetCoupler.m:5-56 */
 /* how a parallel predecessor (a higher-priority coupled vehicle whose coupling was cut into another computation level) enters a
@@ -449,8 +472,12 @@ enum { PDMPC_COUPLING_REACHABLE_SET = 3 };                                      
  * (parallel_coupling_previous_trajectory, :409-447) or its Hp reachable sets at its current pose (parallel_coupling_reachability,
  * :391-407) */
 enum { PDMPC_PARALLEL_PREVIOUS_TRAJECTORY = 0, PDMPC_PARALLEL_REACHABLE_SETS = 1 };
-enum { PDMPC_PRIORITY_CONSTANT = 0, PDMPC_PRIORITY_COLORING = 1 };                             /* ConstantPrioritizer.m, ColoringPrioritizer.m */
-enum { PDMPC_WEIGHT_DISTANCE = 0, PDMPC_WEIGHT_CONSTANT = 1 };                                 /* weight/DistanceWeigher.m, ConstantWeigher.m */
+/* ConstantPrioritizer.m, ColoringPrioritizer.m, RandomPrioritizer.m (a Fisher-Yates shuffle on mt19937ar doubles seeded with the time
+ * step), FcaPrioritizer.m (pdmpc_fca_collisions on the step's reference points and the scenario's obstacles) */
+enum { PDMPC_PRIORITY_CONSTANT = 0, PDMPC_PRIORITY_COLORING = 1, PDMPC_PRIORITY_RANDOM = 2, PDMPC_PRIORITY_FCA = 3 };
+/* weight/DistanceWeigher.m, ConstantWeigher.m, RandomWeigher.m (one mt19937ar double per directed edge in find() order, seeded with
+ * the time step) */
+enum { PDMPC_WEIGHT_DISTANCE = 0, PDMPC_WEIGHT_CONSTANT = 1, PDMPC_WEIGHT_RANDOM = 2 };
 enum { PDMPC_SUCCESSOR_NONE = 0, PDMPC_SUCCESSOR_AREA_OF_STANDSTILL = 1, PDMPC_SUCCESSOR_AREA_OF_PREVIOUS_TRAJECTORY = 2 }; /* ConstraintFromSuccessor.m */
 
 typedef struct {
@@ -546,7 +573,8 @@ int pdmpc_controller_optimal_step(pdmpc_controller* c, int32_t max_instances);
 int pdmpc_controller_optimal_run(pdmpc_controller* c, int32_t max_instances, int32_t n_steps, double* ms);
 int pdmpc_controller_optimal_result(pdmpc_controller* c, int32_t* chosen, int32_t* n_instances, const double** cost, const pdmpc_vehicle_out** records);
 /* host wall-clock milliseconds of the last pdmpc_controller_step / pdmpc_controller_explore_step, by part: [0] build the step problem(s)
- * on the host, [1] pack, [2] enqueue, [3] wait + read-back, [4] choice among the prioritizations (explorative step), [5] apply */
+ * on the host (FCA priorities included, on the device or not), [1] pack, [2] enqueue, [3] wait + read-back, [4] choice among the
+ * prioritizations (explorative step), [5] apply */
 int pdmpc_controller_last_timing(pdmpc_controller* c, double* ms6);
 /* ... and summed over the steps since the last call with reset != 0 (n_steps: how many) */
 int pdmpc_controller_timing_sum(pdmpc_controller* c, double* ms6, int64_t* n_steps, int32_t reset);

@@ -14,6 +14,8 @@
 #ifndef PDMPC_GEOMETRY_H
 #define PDMPC_GEOMETRY_H
 
+#include <math.h>
+
 #include "pdmpc_math.h" /* PDMPC_HD */
 
 #define PDMPC_COUPLING_AREA_THRESHOLD 1e-3 /* ReachableSetCoupler.m:48 */
@@ -399,6 +401,50 @@ PDMPC_HD static inline double pdmpc_edge_overlap_term(const double* ax, const do
     const int e1 = e + 1 == ma ? 0 : e + 1;
     const double f = pdmpc_edge_inside_fraction(ax[e], ay[e], ax[e1], ay[e1], px, py, mp, strict);
     return f * (ax[e] * ay[e1] - ax[e1] * ay[e]);
+}
+
+/* ---- future collision assessment (FcaPrioritizer.m:11-92) ----
+ * The footprint of a vehicle at one reference point: the corners [-1,-1,1,1]·(length/2 + offset), [-1,1,1,-1]·(width/2 + offset)
+ * (FcaPrioritizer.m:21-22, translate_global.m) rotated by (c, s) and moved to (x0, y0), in the operation order of pdmpc_move_point. */
+PDMPC_HD static inline void pdmpc_fca_footprint(double c, double s, double x0, double y0, double length, double width, double offset, double* fx,
+                                                double* fy) {
+    const double hl = length / 2 + offset, hw = width / 2 + offset;
+    const double xl[4] = {-hl, -hl, hl, hl}, yl[4] = {-hw, hw, hw, -hw};
+    for (int q = 0; q < 4; ++q) pdmpc_move_point(c, s, x0, y0, xl[q], yl[q], &fx[q], &fy[q]);
+}
+/* Does the axis normal to the edge (e0x, e0y) -> (e1x, e1y) separate polygon A from polygon B?  intersect_sat.m:19-40 with the
+ * arithmetic of sat_axis_separates (csrc/edge_checks.hpp): normal (-ey, ex) / its norm, projections nx * x + ny * y, separated iff
+ * min1 - max2 > 0 or min2 - max1 > 0; a zero-length edge gives a NaN axis whose comparisons are false. */
+PDMPC_HD static inline int pdmpc_sat_axis_separates(const double* ax, const double* ay, int na, const double* bx, const double* by, int nb, double e0x,
+                                                    double e0y, double e1x, double e1y) {
+    const double ex = e1x - e0x, ey = e1y - e0y;
+    const double vx = -ey, vy = ex;
+    const double nrm = sqrt(vx * vx + vy * vy);
+    const double nx = vx / nrm, ny = vy / nrm;
+    double minA = 0, maxA = 0, minB = 0, maxB = 0;
+    for (int v = 0; v < na; ++v) {
+        const double d = nx * ax[v] + ny * ay[v];
+        minA = (v == 0 || d < minA) ? d : minA;
+        maxA = (v == 0 || d > maxA) ? d : maxA;
+    }
+    for (int v = 0; v < nb; ++v) {
+        const double d = nx * bx[v] + ny * by[v];
+        minB = (v == 0 || d < minB) ? d : minB;
+        maxB = (v == 0 || d > maxB) ? d : maxB;
+    }
+    return (minA - maxB > 0) || (minB - maxA > 0);
+}
+/* intersect_sat(A, B) (intersect_sat.m:1-42): 1 iff no axis of either polygon separates them (open polygons, edges wrap to the first
+ * vertex; A's axes first, then B's — the order of sat_pair_lane — and the first separating axis ends the test). */
+PDMPC_HD static inline int pdmpc_sat_intersect(const double* ax, const double* ay, int na, const double* bx, const double* by, int nb) {
+    for (int a = 0; a < na + nb; ++a) {
+        const int own = a < na;
+        const int e = own ? a : a - na, m = own ? na : nb, e1 = e + 1 == m ? 0 : e + 1;
+        const double* px = own ? ax : bx;
+        const double* py = own ? ay : by;
+        if (pdmpc_sat_axis_separates(ax, ay, na, bx, by, nb, px[e], py[e], px[e1], py[e1])) return 0;
+    }
+    return 1;
 }
 
 #endif /* PDMPC_GEOMETRY_H */

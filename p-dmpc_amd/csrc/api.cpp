@@ -345,6 +345,13 @@ struct pdmpc_handle {
     std::vector<int32_t> reach_off_host;
     hipEvent_t reach_ev[2] = {nullptr, nullptr};
     float reach_kernel_ms = 0.0f;
+    // pdmpc_fca_collisions (fca_kernel.hip): inputs | footprints | counts on the device, pinned staging of the inputs and of the counts;
+    // grown when a call needs more, kept otherwise
+    DevBuf<unsigned char> d_fca_ws;
+    PinnedBuf<unsigned char> h_fca_in;
+    PinnedBuf<int32_t> h_fca_out;
+    hipEvent_t fca_ev[2] = {nullptr, nullptr};
+    float fca_kernel_ms = 0.0f;
     DevBuf<double> d_reach_all;        // every trim's local hulls of every step (x, then y), for pdmpc_bound_reachable_sets
     DevBuf<int32_t> d_reach_all_off;   // [n_trims * Hp + 1]
     int reach_all_tot = 0;
@@ -1203,6 +1210,8 @@ int pdmpc_destroy(pdmpc_handle* h) {
     for (hipEvent_t& e : h->reach_ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t& e : h->bound_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t& e : h->fca_ev)
         if (e) (void)hipEventDestroy(e);
     delete h;
     return PDMPC_OK;
@@ -2100,6 +2109,92 @@ int pdmpc_bounded_reachable_kernel_ms(pdmpc_handle* h, double* ms2) {
 int pdmpc_reachable_set_coupling_kernel_ms(pdmpc_handle* h, double* ms) {
     if (!h || !ms) return fail(PDMPC_ERR_INVALID, "null argument");
     *ms = (double)h->reach_kernel_ms;
+    return PDMPC_OK;
+}
+
+// ---- future collision assessment on the device (fca_kernel.hip)
+int pdmpc_fca_collisions(pdmpc_handle* h, int32_t n, int32_t Hp, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw,
+                         int32_t n_pairs, const int32_t* pairs, const pdmpc_polygon_set* obstacles, const pdmpc_polygon_set* dynamic_rows, double length,
+                         double width, double offset, int32_t* collisions, int32_t* priorities) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    const char* why = nullptr;
+    if (const int rc = pdmpc_fca_check_args(n, Hp, x, y, cos_yaw, sin_yaw, n_pairs, pairs, obstacles, dynamic_rows, collisions, priorities, &why))
+        return fail(rc, std::string("pdmpc_fca_collisions: ") + why);
+    const int m = n * Hp;
+    const int S = obstacles ? obstacles->n_polygons : 0, D = dynamic_rows ? dynamic_rows->n_polygons : 0, R = D / Hp;
+    const int s0 = S ? obstacles->offset[0] : 0, Ns = S ? obstacles->offset[S] - s0 : 0;
+    const int d0 = D ? dynamic_rows->offset[0] : 0, Nd = D ? dynamic_rows->offset[D] - d0 : 0;
+    // the staged inputs (one copy in): doubles x, y, cos, sin [4 m] | static x, y | dynamic x, y, then int32 pairs [2 P] | static
+    // offsets [S + 1] | dynamic offsets [D + 1] (both rebased to 0); on the device behind them footprints [8 m] and counts [n]
+    const size_t o_sx = (size_t)4 * m, o_dx = o_sx + (size_t)2 * Ns, n_dbl = o_dx + (size_t)2 * Nd;
+    const size_t o_pairs = n_dbl * sizeof(double), o_soff = o_pairs + (size_t)2 * n_pairs * sizeof(int32_t), o_doff = o_soff + ((size_t)S + 1) * sizeof(int32_t);
+    const size_t in_bytes = (o_doff + ((size_t)D + 1) * sizeof(int32_t) + 7) & ~(size_t)7;
+    const size_t o_fp = in_bytes, o_cnt = o_fp + (size_t)8 * m * sizeof(double), total = o_cnt + (size_t)n * sizeof(int32_t);
+    ON_DEVICE(h->cfg.device);
+    if (h->d_fca_ws.ensure(total) || h->h_fca_in.ensure(in_bytes) || h->h_fca_out.ensure((size_t)n))
+        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the collision assessment");
+    for (hipEvent_t& e : h->fca_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    unsigned char* hin = h->h_fca_in.p;
+    double* hd = (double*)hin;
+    std::memcpy(hd, x, (size_t)m * sizeof(double));
+    std::memcpy(hd + m, y, (size_t)m * sizeof(double));
+    std::memcpy(hd + 2 * (size_t)m, cos_yaw, (size_t)m * sizeof(double));
+    std::memcpy(hd + 3 * (size_t)m, sin_yaw, (size_t)m * sizeof(double));
+    if (Ns) {
+        std::memcpy(hd + o_sx, obstacles->x + s0, (size_t)Ns * sizeof(double));
+        std::memcpy(hd + o_sx + Ns, obstacles->y + s0, (size_t)Ns * sizeof(double));
+    }
+    if (Nd) {
+        std::memcpy(hd + o_dx, dynamic_rows->x + d0, (size_t)Nd * sizeof(double));
+        std::memcpy(hd + o_dx + Nd, dynamic_rows->y + d0, (size_t)Nd * sizeof(double));
+    }
+    if (n_pairs) std::memcpy(hin + o_pairs, pairs, (size_t)2 * n_pairs * sizeof(int32_t));
+    int32_t* soff = (int32_t*)(hin + o_soff);
+    int32_t* doff = (int32_t*)(hin + o_doff);
+    for (int p = 0; p <= S; ++p) soff[p] = S ? obstacles->offset[p] - s0 : 0;
+    for (int p = 0; p <= D; ++p) doff[p] = D ? dynamic_rows->offset[p] - d0 : 0;
+    unsigned char* ws = h->d_fca_ws.p;
+    const double* wd = (const double*)ws;
+    FcaArgs A;
+    A.n = n;
+    A.Hp = Hp;
+    A.n_pairs = n_pairs;
+    A.n_static = S;
+    A.n_rows = R;
+    A.length = length;
+    A.width = width;
+    A.offset = offset;
+    A.n_pair_items = (int64_t)n_pairs * Hp;
+    A.n_static_items = (int64_t)(n - 1) * Hp * S;
+    A.n_items = A.n_pair_items + A.n_static_items + (int64_t)(n - 1) * Hp * R;
+    A.in = wd;
+    A.static_x = wd + o_sx;
+    A.static_y = wd + o_sx + Ns;
+    A.dyn_x = wd + o_dx;
+    A.dyn_y = wd + o_dx + Nd;
+    A.pairs = (const int32_t*)(ws + o_pairs);
+    A.static_off = (const int32_t*)(ws + o_soff);
+    A.dyn_off = (const int32_t*)(ws + o_doff);
+    A.fp = (double*)(ws + o_fp);
+    A.counts = (int32_t*)(ws + o_cnt);
+    HIPCHK(hipMemcpyAsync(ws, hin, in_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipEventRecord(h->fca_ev[0], h->stream));
+    const int lrc = pdmpc_launch_fca(&A, (void*)h->stream);
+    if (lrc) return fail(PDMPC_ERR_HIP, std::string("collision assessment kernel launch failed: ") + hipGetErrorString((hipError_t)lrc));
+    HIPCHK(hipEventRecord(h->fca_ev[1], h->stream));
+    HIPCHK(hipMemcpyAsync(h->h_fca_out.p, ws + o_cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(sync_stream(h));
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, h->fca_ev[0], h->fca_ev[1]) == hipSuccess) h->fca_kernel_ms = ms;
+    std::memcpy(collisions, h->h_fca_out.p, (size_t)n * sizeof(int32_t));
+    pdmpc_fca_sort_index(n, collisions, priorities);
+    return PDMPC_OK;
+}
+
+int pdmpc_fca_kernel_ms(pdmpc_handle* h, double* ms) {
+    if (!h || !ms) return fail(PDMPC_ERR_INVALID, "null argument");
+    *ms = (double)h->fca_kernel_ms;
     return PDMPC_OK;
 }
 

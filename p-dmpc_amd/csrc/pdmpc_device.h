@@ -339,9 +339,38 @@ struct BoundArgs {
     int32_t* n_pairs;          // [1] their count (cleared before the box pass)
 };
 
+// Future collision assessment (fca_kernel.hip; FcaPrioritizer.m:11-92): the footprints of every (vehicle, step), then
+// one lane per work item — (pair, step), (vehicle < n - 1, step, static obstacle), (vehicle < n - 1, step, dynamic row), in this order
+// of the flat item index — with integer atomics into the counts.  All arrays are the handle's (api.cpp: pdmpc_fca_collisions).
+#define PDMPC_FCA_BLOCK 256         // lanes per workgroup of both passes
+#define PDMPC_FCA_MAX_BLOCKS 4096   // workgroups of the item pass at most (grid-stride beyond)
+struct FcaArgs {
+    int32_t n, Hp, n_pairs, n_static, n_rows;
+    double length, width, offset;
+    int64_t n_pair_items, n_static_items, n_items;  // n_pairs Hp, (n - 1) Hp n_static, and the total with (n - 1) Hp n_rows
+    const double* in;           // [4 n Hp]: x, y, cos(yaw), sin(yaw) of every reference point (point k of vehicle v at v Hp + k)
+    const int32_t* pairs;       // [2 n_pairs] a < b, checked on the host
+    const int32_t* static_off;  // [n_static + 1]
+    const double* static_x;
+    const double* static_y;
+    const int32_t* dyn_off;     // [n_rows Hp + 1]: row r at step k is polygon r Hp + k
+    const double* dyn_x;
+    const double* dyn_y;
+    double* fp;                 // [8 n Hp] footprint of (v, k) at 8 (v Hp + k): the x of its 4 corners, then their y
+    int32_t* counts;            // [n]
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+// fca_kernel.hip: the footprint pass (which also clears the counts) and the item pass on the handle's stream
+int pdmpc_launch_fca(const FcaArgs* args, void* stream);
+// fca.cpp: the argument checks pdmpc_fca_collisions and its host twin share (PDMPC_OK, or an error code with *why set), and the
+// stable descending sort of the counts (priorities = 1-based index vector)
+int pdmpc_fca_check_args(int32_t n, int32_t Hp, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw, int32_t n_pairs,
+                         const int32_t* pairs, const pdmpc_polygon_set* obstacles, const pdmpc_polygon_set* dynamic_rows, const int32_t* collisions,
+                         const int32_t* priorities, const char** why);
+void pdmpc_fca_sort_index(int32_t n, const int32_t* collisions, int32_t* priorities);
 // reachable_kernel.hip: the two passes of the reachable-set coupler on the handle's stream
 int pdmpc_launch_reachable_coupling(const ReachArgs* args, void* stream);
 // bounded_kernel.hip: the bounding pass (one wavefront per set) and the two passes of the coupler on the step-Hp sets

@@ -10,9 +10,11 @@
 //   predicted lanelets        hlc/controller/common/get_predicted_lanelets.m:25-62, get_lanelets_boundary.m:18-68
 //   coupling                  Coupler.m:31-32 (full), DistanceCoupler.m:15-50 (distance), ReachableSetCoupler.m:5-56 (reachable sets,
 //                             reachable_sets.cpp / reachable_kernel.hip)
-//   priorities -> DAG         ConstantPrioritizer.m:14-20, Prioritizer.m:36-77, ColoringPrioritizer.m:11-131
+//   priorities -> DAG         ConstantPrioritizer.m:14-20, Prioritizer.m:36-77, ColoringPrioritizer.m:11-131, RandomPrioritizer.m:15-25,
+//                             FcaPrioritizer.m:11-92 (fca.cpp / fca_kernel.hip)
 //   grouping                  PrioritizedController.group (hlc/controller/prioritized/PrioritizedController.m:375-389),
-//                             weight/DistanceWeigher.m:12-39, weight/ConstantWeigher.m:15-17, cut/GreedyCutter.m:5-86
+//                             weight/DistanceWeigher.m:12-39, weight/ConstantWeigher.m:15-17, weight/RandomWeigher.m:13-21,
+//                             cut/GreedyCutter.m:5-86
 //   computation levels        utility/kahn.m:1-24
 //   obstacle assembly         PrioritizedController.plan / consider_predecessors / consider_successors (:297-324, 449-566)
 //   exhaustion, fallbacks     handle_graph_search_exhaustion / plan_fallback (:568-616, 678-718), check_others_fallback (:623-676),
@@ -199,6 +201,10 @@ struct pdmpc_controller {
     bool lanelet_bounding = false;
     std::vector<int32_t> bound_off, lan_off;
     std::vector<double> bound_x, bound_y, lan_x, lan_y;
+    // priorities of the random and FCA strategies (1-based per vehicle) and the FCA inputs of the step: every reference point with the
+    // cos / sin of its calculate_yaw heading, the coupled pairs a < b, the scenario's obstacles as one polygon set
+    std::vector<int32_t> prio, fca_pairs, fca_count, fca_obst_off;
+    std::vector<double> fca_x, fca_y, fca_cos, fca_sin, fca_obst_x, fca_obst_y;
     std::string err;
 };
 
@@ -651,6 +657,7 @@ bool group(pdmpc_controller& c, const std::vector<uint8_t>& directed, const List
     std::vector<Edge> edges;
     const double vmax = *std::max_element(c.trim_speed.begin(), c.trim_speed.end());
     const double max_distance = 2 * vmax * c.cfg.dt_seconds * c.Hp;
+    Mt19937ar rng((uint32_t)c.k);  // RandomWeigher (weight/RandomWeigher.m:13-21): one draw per edge in find() order, seeded with the time step
     for (int b = 0; b < n; ++b)
         for (const int32_t* q = dir_pred.begin(b); q != dir_pred.end(b); ++q) {
             const int a = *q;
@@ -658,6 +665,8 @@ bool group(pdmpc_controller& c, const std::vector<uint8_t>& directed, const List
             if (c.cfg.weight_strategy == PDMPC_WEIGHT_DISTANCE) {
                 const double dx = c.mx[a] - c.mx[b], dy = c.my[a] - c.my[b];
                 w = 1 - std::sqrt(dx * dx + dy * dy) / max_distance;
+            } else if (c.cfg.weight_strategy == PDMPC_WEIGHT_RANDOM) {
+                w = rng.rand();
             }
             if (w != 0) edges.push_back({a, b, w});  // (find() on the weighted matrix skips exact zeros)
         }
@@ -757,6 +766,8 @@ const char* pdmpc_controller_last_error(void) { return g_cerr.c_str(); }
 int pdmpc_controller_create(pdmpc_handle* handle, const pdmpc_controller_config* cfg, const pdmpc_scenario* sc, pdmpc_controller** out) {
     if (!cfg || !sc || !out) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
     if (sc->n_vehicles < 1 || cfg->Hp < 1 || cfg->Hp > PDMPC_HP_MAX || sc->n_trims < 1) return cfail(nullptr, PDMPC_ERR_INVALID, "bad sizes");
+    if (cfg->priority_strategy < PDMPC_PRIORITY_CONSTANT || cfg->priority_strategy > PDMPC_PRIORITY_FCA) return cfail(nullptr, PDMPC_ERR_INVALID, "unknown priority strategy");
+    if (cfg->weight_strategy < PDMPC_WEIGHT_DISTANCE || cfg->weight_strategy > PDMPC_WEIGHT_RANDOM) return cfail(nullptr, PDMPC_ERR_INVALID, "unknown weight strategy");
     if (handle) {
         // the backend reads Hp entries of every reference and writes one record per vehicle: a handle created for another
         // horizon or a smaller batch must not be driven by this controller
@@ -809,6 +820,12 @@ int pdmpc_controller_create(pdmpc_handle* handle, const pdmpc_controller_config*
         o.x.assign(sc->obstacles.x + sc->obstacles.offset[p], sc->obstacles.x + sc->obstacles.offset[p + 1]);
         o.y.assign(sc->obstacles.y + sc->obstacles.offset[p], sc->obstacles.y + sc->obstacles.offset[p + 1]);
         c->static_obstacles.push_back(std::move(o));
+    }
+    c->fca_obst_off.assign(1, 0);
+    for (const Poly& o : c->static_obstacles) {
+        c->fca_obst_x.insert(c->fca_obst_x.end(), o.x.begin(), o.x.end());
+        c->fca_obst_y.insert(c->fca_obst_y.end(), o.y.begin(), o.y.end());
+        c->fca_obst_off.push_back((int32_t)c->fca_obst_x.size());
     }
     // Simulation.setup: initial speed = steering = 0 (Simulation.m:52-65)
     c->mx.resize(c->n);
@@ -904,6 +921,62 @@ int seeds_for_next_pack(pdmpc_controller* c) {
     if (c->optimizer != PDMPC_OPTIMIZER_SAMPLED) return PDMPC_OK;
     const int rc = pdmpc_set_step_seeds(c->h, (int32_t)c->seeds.size(), c->seeds.data());
     return rc ? cfail(c, rc, pdmpc_last_error()) : PDMPC_OK;
+}
+
+// RandomPrioritizer.m:15-25 (prioritizer.random_priorities): a Fisher-Yates shuffle of 1 .. n on the mt19937ar doubles of the time step
+void random_priorities(int time_step, int n, std::vector<int32_t>& p) {
+    Mt19937ar rng((uint32_t)time_step);
+    for (int i = n - 1; i > 0; --i) {
+        const int j = (int)(rng.rand() * (i + 1));
+        std::swap(p[i], p[j]);
+    }
+}
+
+// FcaPrioritizer.m:11-92 on the step's reference points and the scenario's obstacles: on the device with a handle, else the host twin
+int fca_priorities(pdmpc_controller* c) {
+    const int n = c->n, Hp = c->Hp;
+    if (Hp < 2) return cfail(c, PDMPC_ERR_INVALID, "FCA priorities need Hp >= 2 (calculate_yaw needs two reference points)");
+    c->fca_x.resize((size_t)n * Hp);
+    c->fca_y.resize((size_t)n * Hp);
+    c->fca_cos.resize((size_t)n * Hp);
+    c->fca_sin.resize((size_t)n * Hp);
+    for (int v = 0; v < n; ++v) {
+        const double *px = c->ref_x[v].data(), *py = c->ref_y[v].data();
+        for (int q = 0; q < Hp; ++q) {
+            // calculate_yaw.m: central differences, one-sided at the ends (prioritizer.calculate_yaw)
+            const int a = q == 0 ? 0 : (q == Hp - 1 ? Hp - 2 : q - 1), b = q == 0 ? 1 : (q == Hp - 1 ? Hp - 1 : q + 1);
+            const double yaw = std::atan2(py[b] - py[a], px[b] - px[a]);
+            const size_t i = (size_t)v * Hp + q;
+            c->fca_x[i] = px[q];
+            c->fca_y[i] = py[q];
+            c->fca_cos[i] = std::cos(yaw);
+            c->fca_sin[i] = std::sin(yaw);
+        }
+    }
+    c->fca_pairs.clear();
+    for (int a = 0; a < n; ++a)
+        for_each_set(c->adjacency.data() + (size_t)a * n + a + 1, n - a - 1, [&](int q) {
+            c->fca_pairs.push_back(a);
+            c->fca_pairs.push_back(a + 1 + q);
+        });
+    pdmpc_polygon_set obst;
+    obst.n_polygons = (int32_t)c->fca_obst_off.size() - 1;
+    obst.offset = c->fca_obst_off.data();
+    obst.x = c->fca_obst_x.data();
+    obst.y = c->fca_obst_y.data();
+    c->fca_count.resize(n);
+    const int32_t n_pairs = (int32_t)(c->fca_pairs.size() / 2);
+    const pdmpc_controller_config& g = c->cfg;
+    if (c->h) {
+        const int rc = pdmpc_fca_collisions(c->h, n, Hp, c->fca_x.data(), c->fca_y.data(), c->fca_cos.data(), c->fca_sin.data(), n_pairs, c->fca_pairs.data(), &obst,
+                                            nullptr, g.vehicle_length, g.vehicle_width, g.offset, c->fca_count.data(), c->prio.data());
+        if (rc) return cfail(c, rc, std::string("pdmpc_fca_collisions: ") + pdmpc_last_error());
+    } else {
+        const int rc = pdmpc_fca_collisions_host(n, Hp, c->fca_x.data(), c->fca_y.data(), c->fca_cos.data(), c->fca_sin.data(), n_pairs, c->fca_pairs.data(), &obst,
+                                                 nullptr, g.vehicle_length, g.vehicle_width, g.offset, c->fca_count.data(), c->prio.data());
+        if (rc) return cfail(c, rc, "pdmpc_fca_collisions_host failed");
+    }
+    return PDMPC_OK;
 }
 }  // namespace
 
@@ -1092,11 +1165,22 @@ int pdmpc_controller_build_step(pdmpc_controller* c) {
     // ---- priorities -> directed coupling
     if (c->cfg.priority_strategy == PDMPC_PRIORITY_COLORING) {
         coloring_directed(c->adjacency, n, c->directed);
-    } else {  // constant priorities = vehicle index (ConstantPrioritizer.m:14-20): keep i -> j iff i <= j
+    } else {
+        // constant priorities = vehicle index (ConstantPrioritizer.m:14-20); random and FCA priorities as below
+        // (Prioritizer.directed_coupling_from_priorities, Prioritizer.m:64-77: keep i -> j iff priority(j) is not below priority(i))
+        c->prio.resize(n);
+        for (int v = 0; v < n; ++v) c->prio[v] = v + 1;
+        if (c->cfg.priority_strategy == PDMPC_PRIORITY_RANDOM) {
+            random_priorities(c->k, n, c->prio);
+        } else if (c->cfg.priority_strategy == PDMPC_PRIORITY_FCA) {
+            const int rc = fca_priorities(c);
+            if (rc) return rc;
+        }
         c->directed.assign((size_t)n * n, 0);
         for (int i = 0; i < n; ++i)
-            for (int j = 0; j < n; ++j)
-                if (at(c->adjacency, n, i, j) && !(j < i)) at(c->directed, n, i, j) = 1;
+            for_each_set(c->adjacency.data() + (size_t)i * n, n, [&](int j) {
+                if (!(c->prio[j] < c->prio[i])) at(c->directed, n, i, j) = 1;
+            });
     }
     const int rc = assemble_step(c);
     if (rc) return rc;

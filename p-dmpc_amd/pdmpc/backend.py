@@ -111,6 +111,9 @@ EXPORTS = [
     "pdmpc_bounded_set_coupling",
     "pdmpc_polygon_set_coupling_host",
     "pdmpc_bounded_reachable_kernel_ms",
+    "pdmpc_fca_collisions",
+    "pdmpc_fca_collisions_host",
+    "pdmpc_fca_kernel_ms",
     "pdmpc_controller_set_lanelet_bounding",
     "pdmpc_plan_step_sampled",
     "pdmpc_set_step_seeds",
@@ -221,6 +224,59 @@ def reachable_set_coupling_call(local_sets, x, y, yaw, trim, handle=None):
         if rc != 0:
             raise BackendError("pdmpc_reachable_set_coupling_host failed with status %d" % rc)
     return adj[: n * n].reshape(n, n), area[: n * n].reshape(n, n)
+
+
+def fca_pairs(adjacency):
+    """The coupled pairs a < b of an adjacency matrix in the order pdmpc_fca_collisions takes them: (P, 2) int32, ascending by (a, b)."""
+    A = np.asarray(adjacency) != 0
+    a, b = np.nonzero(np.triu(A, 1))
+    return np.ascontiguousarray(np.stack([a, b], axis=1), dtype=np.int32).reshape(-1, 2)
+
+
+def fca_pack(reference_points, pairs, length, width, offset, obstacles=(), dynamic_obstacle_area=()):
+    """The arguments of pdmpc_fca_collisions(_host) after the handle -> (args, (collisions, priorities) output arrays, keep-alive).
+    The headings are prioritizer.calculate_yaw's and their cos / sin the host's libm, as prioritizer.fca_priorities builds them."""
+    from .prioritizer import calculate_yaw
+
+    ref = [np.asarray(r, dtype=np.float64).reshape(-1, 2) for r in reference_points]
+    n = len(ref)
+    Hp = ref[0].shape[0] if n else 0
+    if any(r.shape[0] != Hp for r in ref):
+        raise ValueError("every vehicle needs Hp reference points")
+    x = np.ascontiguousarray(np.concatenate([r[:, 0] for r in ref]) if n else np.zeros(1), dtype=np.float64)
+    y = np.ascontiguousarray(np.concatenate([r[:, 1] for r in ref]) if n else np.zeros(1), dtype=np.float64)
+    yaw = [a for r in ref for a in (calculate_yaw(r) if Hp >= 2 else np.zeros(Hp))]
+    c = np.array([math.cos(float(a)) for a in yaw] or [0.0], dtype=np.float64)
+    s = np.array([math.sin(float(a)) for a in yaw] or [0.0], dtype=np.float64)
+    pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    keep = abi._Keep()
+    keep.refs += [x, y, c, s, pr]
+    obst = abi.pack_polygon_set([np.asarray(o, dtype=np.float64) for o in obstacles], keep)
+    dyn = abi.pack_polygon_set([np.asarray(p, dtype=np.float64) for row in dynamic_obstacle_area for p in row], keep) if len(dynamic_obstacle_area) else None
+    keep.refs += [obst, dyn]
+    coll = np.zeros(max(n, 1), dtype=np.int32)
+    prio = np.zeros(max(n, 1), dtype=np.int32)
+    args = [n, Hp, x.ctypes.data_as(abi.c_double_p), y.ctypes.data_as(abi.c_double_p), c.ctypes.data_as(abi.c_double_p), s.ctypes.data_as(abi.c_double_p),
+            len(pr), pr.ctypes.data_as(abi.c_int32_p) if len(pr) else None, C.byref(obst), C.byref(dyn) if dyn is not None else None,
+            float(length), float(width), float(offset), coll.ctypes.data_as(abi.c_int32_p), prio.ctypes.data_as(abi.c_int32_p)]
+    return args, (coll[:n], prio[:n]), keep
+
+
+def fca_collisions_host(reference_points, pairs, length, width, offset, obstacles=(), dynamic_obstacle_area=(), handle=None):
+    """FcaPrioritizer natively (pdmpc_fca_collisions_host; on `handle`'s device, pdmpc_fca_collisions, if one is given).
+    reference_points: per vehicle an (Hp, 2) array; pairs: (P, 2) coupled pairs a < b, ascending (fca_pairs); obstacles: (2, V) arrays;
+    dynamic_obstacle_area: rows of Hp (2, V) arrays.  -> (collisions (n,) int32, priorities (n,) int32: the 1-based index vector of the
+    stable descending sort, as the reference passes it on)."""
+    L = load_library()
+    args, out, keep = fca_pack(reference_points, pairs, length, width, offset, obstacles, dynamic_obstacle_area)
+    if handle is not None:
+        _check(L, L.pdmpc_fca_collisions(handle.h, *args), "pdmpc_fca_collisions")
+    else:
+        rc = L.pdmpc_fca_collisions_host(*args)
+        if rc != 0:
+            raise BackendError("pdmpc_fca_collisions_host failed with status %d" % rc)
+    del keep
+    return out
 
 
 def _pack_lanelet_polygons(lanelet_polys):
@@ -350,6 +406,11 @@ def load_library(path=None):
     L.pdmpc_bounded_set_coupling.argtypes = [H, abi.c_uint8_p, abi.c_double_p]
     L.pdmpc_polygon_set_coupling_host.argtypes = [C.POINTER(abi.PolygonSet), C.c_int32, abi.c_uint8_p, abi.c_double_p]
     L.pdmpc_bounded_reachable_kernel_ms.argtypes = [H, abi.c_double_p]
+    fca_tail = [C.c_int32, C.c_int32] + [abi.c_double_p] * 4 + [C.c_int32, abi.c_int32_p, C.POINTER(abi.PolygonSet), C.POINTER(abi.PolygonSet)] + \
+        [C.c_double] * 3 + [abi.c_int32_p, abi.c_int32_p]
+    L.pdmpc_fca_collisions.argtypes = [H] + fca_tail
+    L.pdmpc_fca_collisions_host.argtypes = fca_tail
+    L.pdmpc_fca_kernel_ms.argtypes = [H, abi.c_double_p]
     L.pdmpc_controller_set_lanelet_bounding.argtypes = [H, C.c_int32]
     L.pdmpc_last_error.restype = C.c_char_p
     L.pdmpc_version.restype = C.c_char_p
@@ -631,6 +692,16 @@ class Handle:
         ms = np.zeros(2)
         _check(self.L, self.L.pdmpc_bounded_reachable_kernel_ms(self.h, ms.ctypes.data_as(abi.c_double_p)), "pdmpc_bounded_reachable_kernel_ms")
         return float(ms[0]), float(ms[1])
+
+    def fca_collisions(self, reference_points, pairs, length, width, offset, obstacles=(), dynamic_obstacle_area=()):
+        """FcaPrioritizer on this handle's device (pdmpc_fca_collisions) -> (collisions, priorities); see fca_collisions_host."""
+        return fca_collisions_host(reference_points, pairs, length, width, offset, obstacles, dynamic_obstacle_area, handle=self)
+
+    def fca_kernel_ms(self):
+        """kernel time (ms) of the last fca_collisions"""
+        ms = C.c_double(0.0)
+        _check(self.L, self.L.pdmpc_fca_kernel_ms(self.h, C.byref(ms)), "pdmpc_fca_kernel_ms")
+        return ms.value
 
     def reachable_set_coupling_kernel_ms(self):
         ms = C.c_double(0.0)

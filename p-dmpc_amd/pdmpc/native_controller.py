@@ -15,8 +15,8 @@ from .config import ConstraintFromSuccessor
 
 COUPLING = {"full": 0, "distance": 1, "none": 2, "reachable_set": 3}
 PARALLEL_PREVIOUS_TRAJECTORY, PARALLEL_REACHABLE_SETS = 0, 1
-PRIORITY = {"constant": 0, "coloring": 1}
-WEIGHT = {"distance": 0, "constant": 1}
+PRIORITY = {"constant": 0, "coloring": 1, "random": 2, "fca": 3}
+WEIGHT = {"distance": 0, "constant": 1, "random": 2}
 OPTIMIZER = {"graph_search": 0, "sampled": 1}  # PDMPC_OPTIMIZER_*
 SUCCESSOR = {ConstraintFromSuccessor.none: 0, ConstraintFromSuccessor.area_of_standstill: 1, ConstraintFromSuccessor.area_of_previous_trajectory: 2}
 

@@ -11,6 +11,8 @@ loop needs.
 Few colours = few computation levels = short dependency chains: the number of levels of a colouring is bounded by the
 maximum degree + 1, whereas constant priorities can chain all vehicles of a connected component.
 """
+import math
+
 import numpy as np
 
 
@@ -100,8 +102,9 @@ def intersect_sat(shape1, shape2):
         edges = np.diff(closed, axis=1)
         normals = np.stack([-edges[1], edges[0]])
         normals = normals / np.sqrt(normals[0] ** 2 + normals[1] ** 2)
-        pa = normals.T @ a
-        pb = normals.T @ b
+        # nx * x + ny * y as two products and one sum (a matrix product may fuse them): the arithmetic of the native twins
+        pa = normals[0][:, None] * a[0][None, :] + normals[1][:, None] * a[1][None, :]
+        pb = normals[0][:, None] * b[0][None, :] + normals[1][:, None] * b[1][None, :]
         return bool(np.any((pa.min(axis=1) - pb.max(axis=1) > 0) | (pb.min(axis=1) - pa.max(axis=1) > 0)))
 
     s1 = np.asarray(shape1, dtype=np.float64)
@@ -111,13 +114,14 @@ def intersect_sat(shape1, shape2):
 
 
 def calculate_yaw(path):
-    """utility/calculate_yaw.m: heading of every point of a (n, 2) path (central differences, one-sided at the ends)."""
+    """utility/calculate_yaw.m: heading of every point of a (n, 2) path (central differences, one-sided at the ends).  atan2 is the
+    host's libm (math.atan2, not numpy's vectorised one), as in the native controller."""
     path = np.asarray(path, dtype=np.float64)
     yaw = np.zeros(len(path))
     d = path[2:] - path[:-2]
-    yaw[1:-1] = np.arctan2(d[:, 1], d[:, 0])
-    yaw[0] = np.arctan2(path[1, 1] - path[0, 1], path[1, 0] - path[0, 0])
-    yaw[-1] = np.arctan2(path[-1, 1] - path[-2, 1], path[-1, 0] - path[-2, 0])
+    yaw[1:-1] = [math.atan2(float(dy), float(dx)) for dx, dy in d]
+    yaw[0] = math.atan2(float(path[1, 1] - path[0, 1]), float(path[1, 0] - path[0, 0]))
+    yaw[-1] = math.atan2(float(path[-1, 1] - path[-2, 1]), float(path[-1, 0] - path[-2, 0]))
     return yaw
 
 
@@ -135,7 +139,7 @@ def fca_priorities(adjacency, reference_points, length, width, offset, obstacles
     yaws = [calculate_yaw(reference_points[v]) for v in range(n)]
 
     def footprint(v, s):
-        c, si = np.cos(yaws[v][s]), np.sin(yaws[v][s])
+        c, si = math.cos(float(yaws[v][s])), math.sin(float(yaws[v][s]))  # the host's libm, as the native twins take them
         x0, y0 = reference_points[v][s]
         return np.stack([c * xl - si * yl + x0, si * xl + c * yl + y0])
 
