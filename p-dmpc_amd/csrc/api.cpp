@@ -21,228 +21,17 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/pdmpc.h"
 #include "../../include/pdmpc_geometry.h"
-#include "pdmpc_device.h"
+#include "handle.hpp"
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-#define HIPCHK(expr)                                                                                 \
-    do {                                                                                             \
-        hipError_t e__ = (expr);                                                                     \
-        if (e__ != hipSuccess) {                                                                     \
-            char buf__[512];                                                                         \
-            snprintf(buf__, sizeof buf__, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return fail(PDMPC_ERR_HIP, buf__);                                                       \
-        }                                                                                            \
-    } while (0)
-
-// The current device belongs to the caller (torch reads it with hipGetDevice: a collective issued after a call into this library
-// must not find itself on another GPU).  Every entry point that works on the handle's device switches to it through this guard,
-// which puts the caller's device back on every exit path.
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) {
-            err = hipSetDevice(dev);
-            switched = err == hipSuccess;
-        }
-    }
-    ~DeviceGuard() {
-        if (switched && prev >= 0) (void)hipSetDevice(prev);
-    }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
-#define ON_DEVICE(dev)                 \
-    DeviceGuard device_guard__((dev)); \
-    HIPCHK(device_guard__.err)
+thread_local std::string g_err;  // pdmpc_last_error: every translation unit reports through pdmpc_set_last_error (fail, handle.hpp)
 
 inline uint32_t align16(uint32_t v) { return (v + 15u) & ~15u; }
 
-// Buffers own their memory: move-only (a vector of banks moves them when it grows), freed with their owner.
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;  // elements
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
-    ~DevBuf() { release(); }
-    int ensure(size_t n) {
-        const size_t want = std::max(n, (size_t)64);
-        return n <= cap ? 0 : ensure_exact(want + want / 2);
-    }
-    int ensure_exact(size_t n) {  // no head room: the arenas are sized in gigabytes
-        if (n <= cap) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc((void**)&p, std::max(n, (size_t)64) * sizeof(T));
-        if (e != hipSuccess) return (int)e;
-        cap = std::max(n, (size_t)64);
-        return 0;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
-template <class T>
-struct PinnedBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    PinnedBuf() = default;
-    PinnedBuf(const PinnedBuf&) = delete;
-    PinnedBuf(PinnedBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
-    ~PinnedBuf() { release(); }
-    int ensure(size_t n) { return ensure_keep(n, 0); }
-    int ensure_keep(size_t n, size_t keep) {  // the first `keep` elements carried over
-        if (n <= cap) return 0;
-        size_t want = std::max(n, (size_t)64);
-        want += want / 2;
-        T* q = nullptr;
-        hipError_t e = hipHostMalloc((void**)&q, want * sizeof(T), hipHostMallocDefault);
-        if (e != hipSuccess) return (int)e;
-        if (p && keep) std::memcpy(q, p, std::min(keep, cap) * sizeof(T));
-        if (p) (void)hipHostFree(p);
-        p = q;
-        cap = want;
-        return 0;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
-// The per-vehicle arenas of the searches (NodeArena, pdmpc_device.h): max_nodes entries per vehicle in every array (contents are
-// scratch: every search starts from an empty tree).
-struct Arenas {
-    uint32_t max_nodes = 0;
-    DevBuf<NodeRec> nodes;
-    DevBuf<double> key, far_key, mid_key, pb_key, walk;
-    DevBuf<unsigned long long> link;
-    DevBuf<uint32_t> far_id, mid_id, pb_d, child0, vlist;
-    DevBuf<uint8_t> vstate;
-    // every array with its entries per node: walk holds 16 bytes per node, vlist the verification's Hp + 1 lists
-    template <class Self, class F>
-    static void each(Self& a, int Hp, F&& f) {
-        f(a.nodes, 1);
-        f(a.key, 1);
-        f(a.link, 1);
-        f(a.vstate, 1);
-        f(a.far_key, 1);
-        f(a.far_id, 1);
-        f(a.mid_key, 1);
-        f(a.mid_id, 1);
-        f(a.pb_key, 1);
-        f(a.pb_d, 1);
-        f(a.walk, 2);
-        f(a.child0, 1);
-        f(a.vlist, Hp + 1);
-    }
-    size_t bytes_per_node(int Hp) const {
-        size_t sum = 0;
-        each(*this, Hp, [&](const auto& b, int per) { sum += (size_t)per * sizeof *b.p; });
-        return sum;
-    }
-    // everything released first (the arenas are sized in gigabytes); on failure max_nodes is 0 and the caller allocates again
-    int alloc(int max_vehicles, uint32_t n, int Hp) {
-        n = (n + 1u) & ~1u;
-        const size_t tot = (size_t)max_vehicles * n;
-        each(*this, Hp, [](auto& b, int) { b.release(); });
-        max_nodes = 0;
-        int bad = 0;
-        each(*this, Hp, [&](auto& b, int per) { bad |= b.ensure_exact(tot * (size_t)per); });
-        if (bad) return bad;
-        max_nodes = n;
-        return 0;
-    }
-    NodeArena view() const {
-        return {nodes.p, key.p, link.p, vstate.p, far_key.p, far_id.p, mid_key.p, mid_id.p, pb_key.p, pb_d.p, walk.p, child0.p, vlist.p};
-    }
-};
-
 const size_t kLdsMax = 160 * 1024;  // gfx950: 160 KiB per CU (MI355X_MICROARCH.md)
 
-// pdmpc_stats.kernel: what the last launch ran
-enum LaunchKind : int32_t { kLaunchSearch = 2, kLaunchSampled = 3, kLaunchJoint = 4 };
-
-}  // namespace
-
-// one packed batch: host mirror (pinned) + device copy, each ONE allocation -- [DevVehicle records | points pool | predecessor slots] --
-// so a pack is one host-to-device copy
-struct PackedStep {
-    PinnedBuf<unsigned char> h_blob;
-    DevBuf<unsigned char> d_blob;
-    DevVehicle* h_veh = nullptr;  // (views into the blobs, set by pack_common)
-    double* h_pts = nullptr;
-    int32_t* h_pred = nullptr;
-    DevVehicle* d_veh = nullptr;
-    double* d_pts = nullptr;
-    int32_t* d_pred = nullptr;
-    uint64_t staged_serial = ~0ull;  // the handle's sync_serial when the copy out of h_blob was queued (pack_common)
-    int n_packed = 0;
-    bool pack_failed = false;  // the last pack into this bank did not finish: nothing to launch or fetch
-    bool sampled = false;      // packed with seeds (pdmpc_set_step_seeds): a sampled bank, its launches run the sampled optimizer
-    int soup_cap = 0;
-    int cand_cap = 0;  // most segments any single edge check can see (one step's soups + the boundary)
-    std::vector<int64_t> lit_cols;  // per slot: literal soup + boundary columns (for the bytes formula)
-    std::vector<int32_t> perm;      // empty: slot s holds the caller's vehicle s; else slot s holds vehicle perm[s] (pack_common put the batch into level order)
-    std::vector<int32_t> inv;       // ... and vehicle v sits in slot inv[v]
-};
-
-// what pack_common tells vehicles that hand over the same arrays by: the pointers and counts of a vehicle's polygon sets
-struct SoupKey {
-    const void* p[13];
-    int32_t c[6];
-};
-
-// Tuning knobs and A/B / test switches of the graph search.  The defaults are the measured optima quoted next to their use; every
-// setting leaves the results bit-identical.  ONE environment variable overrides them, read once in pdmpc_create (a launch makes no
-// getenv call):  PDMPC_TUNING="key=value,key=value,..."  with the keys below (include/pdmpc.h documents the variable).
-struct Tuning {
-    int round0 = -1;        // nodes a round of a young search takes (-1: 24; 32 for a launch that leaves CUs idle but has fewer than four helpers per search, C3, and for one of more than two searches per CU, C5)
-    int round = -1;         // the most a round takes (-1: 1000 with helper workgroups, else 256)
-    int ramp = -1;          // a round grows by 1 / ramp of the nodes processed so far (-1: 2 with helper workgroups, else 4)
-    int ready = 2048;       // entries of the ready list with helper workgroups (half of it without): the most a round can take
-    int share_min = -1;     // a round with at least this many nodes is shared with the helper workgroups (-1: by the number of helpers per search, launch_range)
-    int tile = -1;          // the most nodes of a shared round one seated helper takes (-1: 256; what it stages in LDS: at most 768)
-    int mid_min = 24576;    // far lists longer than this feed near through the mid list (a band of far's smallest keys)
-    int mid_fill = 12288;   // entries a refill of mid aims at
-    int tentative = 1;      // expected areas of predecessors that are still planning (A/B switch)
-    int fast_arrival = 1;   // finished searches check arrivals against their plan's path first and publish early (A/B switch)
-    int helpers = -1;       // helper workgroups of a launch with at most one search per CU (-1: by launch size, 0: none)
-    int helpers_oversub = -1;  // ... of a launch with more searches than CUs (-1: 200)
-    int seat_nodes = 256;   // a search may hold its share of the launch's helpers (helpers / searches) per this many nodes it has processed
-    int helpers_first = -1; // ... of them dispatched in front of the searches (-1: half the CUs when most searches of the launch have predecessors)
-    int speculate = 1;      // 0: every search waits for all its predecessors before it starts
-    int compact = -1;       // 1: the kernel built for two workgroups per CU (8 wavefronts, <= 80 KB of LDS: bulk_kernel_compact.hip) where it applies (InterX, one mask word, the soup fits); 0: never; -1: for launches of more than two searches per CU
-    int waves = -1;         // wavefronts per workgroup (4 .. PDMPC_MAX_WAVES; -1: 16 for the InterX kernels — 12 for a launch of more than two searches per CU —, 12 for the separating-axis kernel)
-    uint32_t spin_limit = 1u << 22;  // the watchdog's limit of polls / rounds (debugging: fail fast)
-    int force_tie = 0;      // testing only: every search ends on the replay through the reference's binary heap (as if it had met equal keys)
-    int reverse_dispatch = 0;  // testing only: workgroup b takes slot n - 1 - b (successors dispatched before their predecessors)
-    int debug_tail = 0;     // round / node / tick counters of every search in the unused rows of its record's path_nodes (tools/fr_step_profile.py)
-    int debug_lds = 0;      // print the LDS layout of every launch
-    int debug_host = 0;     // 1: a line per launch; 2: the host-time breakdown of the literal path
-    int debug_progress = 0; // live counters in host-mapped memory (pdmpc_debug_progress)
-};
-
-namespace {
 // parses PDMPC_TUNING; an unknown key or a malformed entry is an error (a typo must not silently measure the default)
 bool parse_tuning(const char* text, Tuning& T, std::string& err) {
     struct Key { const char* name; int* dst; };
@@ -301,116 +90,6 @@ bool parse_tuning(const char* text, Tuning& T, std::string& err) {
 }
 }  // namespace
 
-struct pdmpc_handle {
-    pdmpc_config cfg{};
-    Tuning tune{};
-    hipStream_t stream = nullptr;
-    int n_cu = 256;
-    // MPA
-    bool has_mpa = false;
-    int n_trims = 0, n_words = 0, n_man = 0;
-    DevBuf<uint64_t> d_mask;
-    DevBuf<int16_t> d_mi;
-    DevBuf<DevManPose> d_pose;
-    DevBuf<double> d_area;
-    size_t mask_bytes = 0, mi_bytes = 0;
-    int64_t mpa_alg_bytes = 0;
-    Arenas arena;
-    uint32_t max_nodes_limit = 0;  // pdmpc_plan_* may grow the arenas up to this many nodes per vehicle (0: as far as HBM allows)
-    int64_t arena_regrows = 0;     // times an overflowed call was re-planned with larger arenas
-    int64_t safe_replans = 0;      // times a call was re-planned in resident slices after a predecessor time-out
-    bool safe_launches = false;    // pdmpc_set_safe_launch: every launch in resident slices
-    int max_vehicles = 0;
-    DevBuf<pdmpc_vehicle_out> d_out;
-    DevBuf<uint32_t> d_flag;
-    DevBuf<int32_t> d_tree_size;
-    DevBuf<int32_t> d_tie_count;
-    DevBuf<unsigned long long> d_work_count;
-    DevBuf<unsigned long long> d_help_board;  // helper workgroups (pdmpc_device.h)
-    DevBuf<uint32_t> d_help_verdict, d_help_finished;
-    DevBuf<double> d_bk_post;                 // records posted for the helper workgroups
-    LaunchKind launch_kind = kLaunchSampled;  // of the last launch (before the first one: what pdmpc_get_last_stats always reported)
-    DevBuf<int32_t> d_joint_off;         // pdmpc_plan_joint: the problems' first slots
-    DevBuf<uint32_t> d_prio_count, d_prio_mask;  // pdmpc_unique_priorities: acyclic masks per tile, the acyclic masks
-    DevBuf<int64_t> d_prio_off;                  // ... exclusive offsets of the tiles (entry n_tiles: the total)
-    DevBuf<int32_t> d_prio_order;                // ... the priorities of every acyclic mask
-    // pdmpc_upload_reachable_sets / pdmpc_reachable_set_coupling (reachable_kernel.hip): the step-Hp local hulls, the workspace and
-    // the pinned staging of inputs and outputs, all sized at upload for max_vehicles vehicles
-    bool has_reach = false;
-    int reach_trims = 0, reach_Hp = 0, reach_cols = 0;
-    DevBuf<double> d_reach_local;      // x of every trim's step-Hp hull, then y
-    DevBuf<int32_t> d_reach_off;       // [n_trims + 1]
-    DevBuf<unsigned char> d_reach_ws;  // inputs [4 n] + trims [n] | moved hulls | hull sizes | boxes | adjacency [n x n] (8-aligned) + areas [n x n]
-    PinnedBuf<unsigned char> h_reach_in, h_reach_out;
-    std::vector<int32_t> reach_off_host;
-    hipEvent_t reach_ev[2] = {nullptr, nullptr};
-    float reach_kernel_ms = 0.0f;
-    // pdmpc_fca_collisions (fca_kernel.hip): inputs | footprints | counts on the device, pinned staging of the inputs and of the counts;
-    // grown when a call needs more, kept otherwise
-    DevBuf<unsigned char> d_fca_ws;
-    PinnedBuf<unsigned char> h_fca_in;
-    PinnedBuf<int32_t> h_fca_out;
-    hipEvent_t fca_ev[2] = {nullptr, nullptr};
-    float fca_kernel_ms = 0.0f;
-    DevBuf<double> d_reach_all;        // every trim's local hulls of every step (x, then y), for pdmpc_bound_reachable_sets
-    DevBuf<int32_t> d_reach_all_off;   // [n_trims * Hp + 1]
-    int reach_all_tot = 0;
-    // pdmpc_bound_reachable_sets / pdmpc_bounded_set_coupling (bounded_kernel.hip): the sets of the last bound call stay here
-    bool bound_valid = false;
-    int bound_n = 0, bound_S = 0, bound_n_lan = 0;
-    DevBuf<unsigned char> d_bound_in;  // inputs [4 n] + trims [n] + lanelet offsets [n + 1] (8-aligned) + lanelet x, y
-    DevBuf<double> d_bound_sets;       // slots: x of every set, then y
-    DevBuf<int32_t> d_bound_n, d_bound_pairs;  // vertices per set | the pair list, then its counter
-    DevBuf<uint8_t> d_bound_flags;
-    DevBuf<double> d_bound_box;
-    DevBuf<unsigned char> d_bound_out; // adjacency [n x n] (8-aligned) + areas [n x n]
-    PinnedBuf<unsigned char> h_bound_in, h_bound_out;
-    PinnedBuf<double> h_bound_xy;
-    hipEvent_t bound_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    float bound_kernel_ms[2] = {0.0f, 0.0f};
-    int device_share = 1;                // handles of one process that launch on this device side by side (pdmpc_set_device_share: a group's logical ranks)
-    bool boards_dirty = true;            // the helper boards / the finished counter need clearing before the helper workgroups may read them
-    uint32_t help_fin_total = 0;         // value of the finished counter once every launch so far has ended
-    uint32_t launch_serial = 0;          // launches of this handle so far (KernelArgs::launch_id)
-    double last_us[3] = {0, 0, 0};       // pdmpc_last_call_timing: pack, enqueue, wait + read-back of the last pdmpc_plan_batch / pdmpc_plan_step
-    double dbg_us[4] = {0, 0, 0, 0};     // debug_host 2: pack, launch, fetch (host clock) and kernel (events) time of the plan_batch calls
-    uint64_t sync_serial = 0;            // stream synchronisations through sync_stream so far (PackedStep::staged_serial)
-    std::vector<SoupKey> pack_soup_keys;  // pack_common's scratch: the distinct soup keys of the batch, the slots they were packed in, the hash table over them
-    std::vector<int32_t> pack_soup_slot, pack_soup_table;
-    std::vector<double> next_weights;    // pdmpc_set_step_weights: expected work per vehicle of the NEXT packed step (the caller's order); consumed by that pack
-    std::vector<uint32_t> next_seeds;    // pdmpc_set_step_seeds: the sampled optimizer's seed per vehicle of the NEXT packed step (the caller's order) ...
-    bool seeds_set = false;              // ... consumed by that pack, which makes its bank a sampled bank
-    PinnedBuf<double> h_lean;            // fetch_lean: (cost, status) per slot
-    DevBuf<double> d_lean;
-    PinnedBuf<pdmpc_vehicle_out> h_out;  // pdmpc_fetch_results: the records land in pinned memory (a copy into the caller's pageable array goes through the runtime's staging otherwise)
-    int bk_ready_launch = 2048;          // entries of the ready list of the last layout
-    uint32_t* progress = nullptr;        // pinned, debug_progress
-    int n_waves = PDMPC_MAX_WAVES;       // of the last layout
-    bool compact_layout = false;         // the last layout is the compact kernel's (two workgroups per CU)
-    // batch blobs: several packed steps can stay resident side by side ("banks", pdmpc_select_bank)
-    std::vector<PackedStep> banks;
-    int bank = 0;
-    uint32_t epoch = 1;  // done flags start at 0, so no slot looks solved before its first launch
-    // launches
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-    size_t events_used = 0;
-    double folded_kernel_ms = 0.0;  // launches whose event pairs were recycled (resident launches without a pack or reset in between)
-    int64_t folded_launches = 0;
-    LdsLayout lds{};
-    int NL = 0, NV = 0, areas_in_lds = 0;
-    pdmpc_stats stats{};
-    // the buffers free themselves after this: the stream is idle by then
-    ~pdmpc_handle() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (auto& ev : events) {
-            (void)hipEventDestroy(ev.first);
-            (void)hipEventDestroy(ev.second);
-        }
-        if (progress) (void)hipHostFree(progress);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
 namespace {
 
 // The dynamic LDS size of a kernel is an attribute of the function ON THE DEVICE, not of a handle (hipFuncSetAttribute sets a
@@ -418,14 +97,6 @@ namespace {
 const size_t kMaxLaunchEvents = 4096;  // event pairs a handle keeps before it folds their times (begin_timed_launch)
 std::mutex g_lds_mutex;
 uint32_t g_lds_high_water[64][4];
-
-// hipStreamSynchronize on the launch stream, counted: a bank whose staging copy was queued before is free again (pack_common)
-inline hipError_t sync_stream(pdmpc_handle* h) {
-    const hipError_t e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) h->sync_serial += 1;
-    return e;
-}
-
 // The automaton's tables, the front of every LDS layout from `off` on: successor masks, maneuver index, poses, then the maneuver
 // areas (only with `areas`: else they are read from L2).  Returns the first free byte.
 template <class Layout>
@@ -1207,12 +878,6 @@ int pdmpc_create(const pdmpc_config* config, pdmpc_handle** out_handle) {
 int pdmpc_destroy(pdmpc_handle* h) {
     if (!h) return PDMPC_OK;
     DeviceGuard device_guard__(h->cfg.device);
-    for (hipEvent_t& e : h->reach_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t& e : h->bound_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t& e : h->fca_ev)
-        if (e) (void)hipEventDestroy(e);
     delete h;
     return PDMPC_OK;
 }
@@ -1758,443 +1423,6 @@ int pdmpc_plan_joint(pdmpc_handle* h, int32_t n_problems, const int32_t* problem
     }
     s.lds_bytes = L.total;
     s.lds_nodes = 0;
-    return PDMPC_OK;
-}
-
-// Prioritizer.unique_priorities (Prioritizer.m:97-140) on the device: priority_kernel.hip.  The acyclic orientations are counted
-// first; the true count K is reported whatever max_out is, and only a K that fits is written (never a truncated list).
-int pdmpc_unique_priorities(pdmpc_handle* h, int32_t n, const uint8_t* adjacency, int64_t max_out, int64_t* n_out, uint32_t* masks, int32_t* priorities) {
-    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
-    if (n_out) *n_out = -1;
-    if (n < 1 || !adjacency || !n_out || max_out < 0 || (max_out > 0 && (!masks || !priorities)))
-        return fail(PDMPC_ERR_INVALID, "pdmpc_unique_priorities: bad argument");
-    if (n > PDMPC_PRIO_MAX_N) return fail(PDMPC_ERR_CAPACITY, "pdmpc_unique_priorities: more than 64 vehicles");
-    PriorityArgs A;
-    std::memset(&A, 0, sizeof A);
-    A.n = n;
-    int E = 0;
-    for (int c = 0; c < n; ++c)  // find(triu(adjacency, 1)): by column, then by row
-        for (int r = 0; r < c; ++r)
-            if (adjacency[(size_t)r * n + c]) ++E;
-    if (E > PDMPC_PRIO_MAX_E) return fail(PDMPC_ERR_CAPACITY, "pdmpc_unique_priorities: more than 32 coupling edges");
-    for (int c = 0, e = 0; c < n; ++c)
-        for (int r = 0; r < c; ++r)
-            if (adjacency[(size_t)r * n + c]) {
-                const uint32_t bit = 1u << (E - 1 - e);  // dec2bin(m, E): edge 1 is the most significant bit
-                A.in_base[c] |= bit;
-                A.out_base[r] |= bit;
-                ++e;
-            }
-    for (int v = 0; v < n; ++v)
-        if (A.in_base[v] | A.out_base[v]) A.active[A.n_active++] = v;
-    A.E = E;
-    A.all_edges = E == 32 ? 0xffffffffu : (1u << E) - 1u;
-    A.n_masks = 1ull << E;
-    const int64_t n_tiles = (int64_t)((A.n_masks + PDMPC_PRIO_TILE - 1) / PDMPC_PRIO_TILE);
-    ON_DEVICE(h->cfg.device);
-    if (h->d_prio_count.ensure((size_t)n_tiles) || h->d_prio_off.ensure((size_t)n_tiles + 1))
-        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the tile counts of pdmpc_unique_priorities");
-    int lrc = pdmpc_launch_priority_count(&A, n_tiles, h->d_prio_count.p, (void*)h->stream);
-    if (!lrc) lrc = pdmpc_launch_priority_scan(h->d_prio_count.p, n_tiles, h->d_prio_off.p, (void*)h->stream);
-    if (lrc) return fail(PDMPC_ERR_HIP, std::string("priority kernel launch failed: ") + hipGetErrorString((hipError_t)lrc));
-    int64_t K = 0;
-    HIPCHK(hipMemcpyAsync(&K, h->d_prio_off.p + n_tiles, sizeof K, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(sync_stream(h));
-    *n_out = K;
-    if (K > max_out) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "pdmpc_unique_priorities: %lld unique prioritizations, max_out is %lld", (long long)K, (long long)max_out);
-        return fail(PDMPC_ERR_CAPACITY, buf);
-    }
-    if (h->d_prio_mask.ensure((size_t)K) || h->d_prio_order.ensure((size_t)K * n))
-        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the output of pdmpc_unique_priorities");
-    lrc = pdmpc_launch_priority_write(&A, n_tiles, h->d_prio_off.p, K, h->d_prio_mask.p, (void*)h->stream);
-    if (!lrc) lrc = pdmpc_launch_priority_order(&A, h->d_prio_mask.p, K, h->d_prio_order.p, (void*)h->stream);
-    if (lrc) return fail(PDMPC_ERR_HIP, std::string("priority kernel launch failed: ") + hipGetErrorString((hipError_t)lrc));
-    HIPCHK(hipMemcpyAsync(masks, h->d_prio_mask.p, (size_t)K * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(priorities, h->d_prio_order.p, (size_t)K * n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(sync_stream(h));
-    return PDMPC_OK;
-}
-
-// ---- the reachable-set coupler on the device (reachable_kernel.hip)
-namespace {
-struct ReachLayout {  // byte offsets into d_reach_ws / the pinned staging for n vehicles (computed the same way at upload and per call)
-    size_t in, trim, hull_x, hull_y, hull_n, box, adj, area, in_bytes, out_bytes, total;
-};
-inline size_t align_up8(size_t v) { return (v + 7) & ~(size_t)7; }
-ReachLayout reach_layout(int n, int cols) {
-    ReachLayout L;
-    L.in = 0;
-    L.trim = L.in + (size_t)4 * n * sizeof(double);
-    L.in_bytes = align_up8(L.trim + (size_t)n * sizeof(int32_t));
-    L.hull_x = L.in_bytes;
-    L.hull_y = L.hull_x + (size_t)n * cols * sizeof(double);
-    L.box = L.hull_y + (size_t)n * cols * sizeof(double);
-    L.hull_n = L.box + (size_t)4 * n * sizeof(double);
-    L.adj = align_up8(L.hull_n + (size_t)n * sizeof(int32_t));
-    L.area = L.adj + align_up8((size_t)n * n);
-    L.out_bytes = L.area + (size_t)n * n * sizeof(double) - L.adj;
-    L.total = L.area + (size_t)n * n * sizeof(double);
-    return L;
-}
-}  // namespace
-
-int pdmpc_upload_reachable_sets(pdmpc_handle* h, int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* sets) {
-    if (!h || !sets || !sets->offset || n_trims < 1 || Hp < 1) return fail(PDMPC_ERR_INVALID, "pdmpc_upload_reachable_sets: bad argument");
-    if (Hp != h->cfg.Hp) return fail(PDMPC_ERR_INVALID, "pdmpc_upload_reachable_sets: Hp differs from the handle's config.Hp");
-    if (sets->n_polygons != n_trims * Hp) return fail(PDMPC_ERR_INVALID, "pdmpc_upload_reachable_sets: expected n_trims * Hp polygons");
-    int cols = 1;
-    for (int p = 0; p < sets->n_polygons; ++p) {
-        const int m = sets->offset[p + 1] - sets->offset[p];
-        if (m < 1) return fail(PDMPC_ERR_INVALID, "pdmpc_upload_reachable_sets: empty polygon");
-        if (m > PDMPC_REACHABLE_MAX_COLS) return fail(PDMPC_ERR_CAPACITY, "pdmpc_upload_reachable_sets: a hull has more than PDMPC_REACHABLE_MAX_COLS vertices");
-        cols = std::max(cols, m);
-    }
-    if (!sets->x || !sets->y) return fail(PDMPC_ERR_INVALID, "pdmpc_upload_reachable_sets: null coordinates");
-    // only step Hp is coupled on (ReachableSetCoupler.m:9-12: reachable_sets(:, end))
-    std::vector<int32_t> off((size_t)n_trims + 1, 0);
-    for (int t = 0; t < n_trims; ++t) {
-        const int p = t * Hp + Hp - 1;
-        off[t + 1] = off[t] + (sets->offset[p + 1] - sets->offset[p]);
-    }
-    const int tot = off[n_trims];
-    std::vector<double> xy((size_t)2 * tot);
-    for (int t = 0; t < n_trims; ++t) {
-        const int p = t * Hp + Hp - 1, a = sets->offset[p], m = sets->offset[p + 1] - a;
-        std::memcpy(xy.data() + off[t], sets->x + a, (size_t)m * sizeof(double));
-        std::memcpy(xy.data() + tot + off[t], sets->y + a, (size_t)m * sizeof(double));
-    }
-    ON_DEVICE(h->cfg.device);
-    h->has_reach = false;
-    const ReachLayout L = reach_layout(h->max_vehicles, cols);
-    if (h->d_reach_local.ensure_exact(xy.size()) || h->d_reach_off.ensure_exact(off.size()) || h->d_reach_ws.ensure_exact(L.total) ||
-        h->h_reach_in.ensure(L.in_bytes) || h->h_reach_out.ensure(L.out_bytes))
-        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the reachable-set coupler");
-    for (hipEvent_t& e : h->reach_ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipMemcpy(h->d_reach_local.p, xy.data(), xy.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_reach_off.p, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    // ... and every step's hulls for the lanelet bounding (pdmpc_bound_reachable_sets)
-    h->bound_valid = false;
-    const int all_tot = sets->offset[sets->n_polygons] - sets->offset[0];
-    std::vector<double> all_xy((size_t)2 * all_tot);
-    std::vector<int32_t> all_off((size_t)sets->n_polygons + 1);
-    for (int p = 0; p <= sets->n_polygons; ++p) all_off[p] = sets->offset[p] - sets->offset[0];
-    std::memcpy(all_xy.data(), sets->x + sets->offset[0], (size_t)all_tot * sizeof(double));
-    std::memcpy(all_xy.data() + all_tot, sets->y + sets->offset[0], (size_t)all_tot * sizeof(double));
-    if (h->d_reach_all.ensure_exact(all_xy.size()) || h->d_reach_all_off.ensure_exact(all_off.size()))
-        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the reachable-set table");
-    HIPCHK(hipMemcpy(h->d_reach_all.p, all_xy.data(), all_xy.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_reach_all_off.p, all_off.data(), all_off.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    h->reach_all_tot = all_tot;
-    h->reach_off_host = off;
-    h->reach_trims = n_trims;
-    h->reach_Hp = Hp;
-    h->reach_cols = cols;
-    h->has_reach = true;
-    return PDMPC_OK;
-}
-
-int pdmpc_reachable_set_coupling(pdmpc_handle* h, int32_t n, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw, const int32_t* trim,
-                                 uint8_t* adjacency, double* area) {
-    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
-    if (!h->has_reach) return fail(PDMPC_ERR_INVALID, "pdmpc_reachable_set_coupling before pdmpc_upload_reachable_sets");
-    if (n < 0 || !adjacency || (n > 0 && (!x || !y || !cos_yaw || !sin_yaw || !trim))) return fail(PDMPC_ERR_INVALID, "pdmpc_reachable_set_coupling: bad argument");
-    if (n > h->max_vehicles) return fail(PDMPC_ERR_CAPACITY, "pdmpc_reachable_set_coupling: more vehicles than config.max_vehicles");
-    if (n == 0) return PDMPC_OK;
-    for (int v = 0; v < n; ++v)
-        if (trim[v] < 1 || trim[v] > h->reach_trims) return fail(PDMPC_ERR_INVALID, "pdmpc_reachable_set_coupling: trim out of range");
-    ON_DEVICE(h->cfg.device);
-    const ReachLayout L = reach_layout(n, h->reach_cols);
-    unsigned char* hin = h->h_reach_in.p;
-    std::memcpy(hin + L.in, x, (size_t)n * sizeof(double));
-    std::memcpy(hin + L.in + (size_t)n * sizeof(double), y, (size_t)n * sizeof(double));
-    std::memcpy(hin + L.in + (size_t)2 * n * sizeof(double), cos_yaw, (size_t)n * sizeof(double));
-    std::memcpy(hin + L.in + (size_t)3 * n * sizeof(double), sin_yaw, (size_t)n * sizeof(double));
-    int32_t* ht = (int32_t*)(hin + L.trim);
-    for (int v = 0; v < n; ++v) ht[v] = trim[v] - 1;
-    unsigned char* ws = h->d_reach_ws.p;
-    ReachArgs A;
-    A.n = n;
-    A.max_cols = h->reach_cols;
-    A.local_x = h->d_reach_local.p;
-    A.local_y = h->d_reach_local.p + h->reach_off_host[h->reach_trims];
-    A.local_off = h->d_reach_off.p;
-    A.in = (const double*)(ws + L.in);
-    A.trim = (const int32_t*)(ws + L.trim);
-    A.hull_x = (double*)(ws + L.hull_x);
-    A.hull_y = (double*)(ws + L.hull_y);
-    A.hull_n = (int32_t*)(ws + L.hull_n);
-    A.box = (double*)(ws + L.box);
-    A.adjacency = (uint8_t*)(ws + L.adj);
-    A.area = (double*)(ws + L.area);
-    HIPCHK(hipMemcpyAsync(ws, hin, L.in_bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipEventRecord(h->reach_ev[0], h->stream));
-    const int lrc = pdmpc_launch_reachable_coupling(&A, (void*)h->stream);
-    if (lrc) return fail(PDMPC_ERR_HIP, std::string("reachable-set coupling kernel launch failed: ") + hipGetErrorString((hipError_t)lrc));
-    HIPCHK(hipEventRecord(h->reach_ev[1], h->stream));
-    const size_t out_bytes = area ? L.out_bytes : (size_t)n * n;
-    HIPCHK(hipMemcpyAsync(h->h_reach_out.p, ws + L.adj, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(sync_stream(h));
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, h->reach_ev[0], h->reach_ev[1]) == hipSuccess) h->reach_kernel_ms = ms;
-    std::memcpy(adjacency, h->h_reach_out.p, (size_t)n * n);
-    if (area) std::memcpy(area, h->h_reach_out.p + (L.area - L.adj), (size_t)n * n * sizeof(double));
-    return PDMPC_OK;
-}
-
-// ---- lanelet bounding and the coupler on the bounded sets (bounded_kernel.hip)
-namespace {
-BoundArgs bound_args(pdmpc_handle* h, int n, int S, int n_lan) {
-    BoundArgs A;
-    unsigned char* in = h->d_bound_in.p;
-    const size_t lan_xy = align_up8((size_t)4 * n * sizeof(double) + (size_t)n * sizeof(int32_t) + (size_t)(n + 1) * sizeof(int32_t));
-    A.n = n;
-    A.S = S;
-    A.Hp = h->reach_Hp;
-    A.all_steps = S == h->reach_Hp && S > 1 ? 1 : 0;
-    A.local_x = h->d_reach_all.p;
-    A.local_y = h->d_reach_all.p + h->reach_all_tot;
-    A.local_off = h->d_reach_all_off.p;
-    A.in = (const double*)in;
-    A.trim = (const int32_t*)(in + (size_t)4 * n * sizeof(double));
-    A.lan_off = A.trim + n;
-    A.lan_x = (const double*)(in + lan_xy);
-    A.lan_y = A.lan_x + n_lan;
-    const size_t slots = (size_t)n * S * PDMPC_BOUND_SLOT;
-    A.set_x = h->d_bound_sets.p;
-    A.set_y = h->d_bound_sets.p + slots;
-    A.set_n = h->d_bound_n.p;
-    A.set_flags = h->d_bound_flags.p;
-    A.box = h->d_bound_box.p;
-    A.adjacency = h->d_bound_out.p;
-    A.area = (double*)(h->d_bound_out.p + align_up8((size_t)n * n));
-    A.pairs = h->d_bound_pairs.p;
-    A.n_pairs = h->d_bound_pairs.p + (n > 1 ? (size_t)n * (n - 1) / 2 : 0);
-    return A;
-}
-}  // namespace
-
-int pdmpc_bound_reachable_sets(pdmpc_handle* h, int32_t n, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw, const int32_t* trim,
-                               const pdmpc_polygon_set* lan, int32_t all_steps, int32_t capacity, int32_t* offset, double* out_x, double* out_y, uint8_t* flags) {
-    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
-    if (!h->has_reach) return fail(PDMPC_ERR_INVALID, "pdmpc_bound_reachable_sets before pdmpc_upload_reachable_sets");
-    if (n < 0 || !offset || !lan || lan->n_polygons != n || (n > 0 && (!x || !y || !cos_yaw || !sin_yaw || !trim || !lan->offset)))
-        return fail(PDMPC_ERR_INVALID, "pdmpc_bound_reachable_sets: bad argument");
-    if (n > h->max_vehicles) return fail(PDMPC_ERR_CAPACITY, "pdmpc_bound_reachable_sets: more vehicles than config.max_vehicles");
-    const int Hp = h->reach_Hp, S = all_steps ? Hp : 1;
-    h->bound_valid = false;
-    offset[0] = 0;
-    if (n == 0) {
-        h->bound_n = 0;
-        h->bound_S = S;
-        h->bound_valid = true;
-        return PDMPC_OK;
-    }
-    int n_lan = 0;
-    for (int v = 0; v < n; ++v) {
-        if (trim[v] < 1 || trim[v] > h->reach_trims) return fail(PDMPC_ERR_INVALID, "pdmpc_bound_reachable_sets: trim out of range");
-        const int nl = lan->offset[v + 1] - lan->offset[v];
-        if (nl < 0) return fail(PDMPC_ERR_INVALID, "pdmpc_bound_reachable_sets: bad lanelet offsets");
-        if (nl > PDMPC_LANELET_POLY_MAX_COLS) return fail(PDMPC_ERR_CAPACITY, "pdmpc_bound_reachable_sets: a lanelet polygon has more than PDMPC_LANELET_POLY_MAX_COLS vertices");
-        if (nl && (!lan->x || !lan->y)) return fail(PDMPC_ERR_INVALID, "pdmpc_bound_reachable_sets: null lanelet coordinates");
-        n_lan += nl;
-    }
-    ON_DEVICE(h->cfg.device);
-    const size_t lan_xy = align_up8((size_t)4 * n * sizeof(double) + (size_t)n * sizeof(int32_t) + (size_t)(n + 1) * sizeof(int32_t));
-    const size_t in_bytes = lan_xy + (size_t)2 * n_lan * sizeof(double);
-    const size_t sets = (size_t)n * S, max_pairs = (size_t)n * (n - 1) / 2;
-    const size_t out_bytes = align_up8((size_t)n * n) + (size_t)n * n * sizeof(double);
-    if (h->d_bound_in.ensure(in_bytes) || h->d_bound_sets.ensure(2 * sets * PDMPC_BOUND_SLOT) || h->d_bound_n.ensure(sets) || h->d_bound_flags.ensure(sets) ||
-        h->d_bound_box.ensure((size_t)4 * n) || h->d_bound_out.ensure(out_bytes) || h->d_bound_pairs.ensure(max_pairs + 1) || h->h_bound_in.ensure(in_bytes) ||
-        h->h_bound_out.ensure(out_bytes + sets * (sizeof(int32_t) + 1)))
-        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the lanelet bounding");
-    for (hipEvent_t& e : h->bound_ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    // inputs: poses, 0-based trims, the normalized lanelet polygons (pdmpc_lanelet_polygon_normalize, as the host twin)
-    unsigned char* hin = h->h_bound_in.p;
-    std::memcpy(hin, x, (size_t)n * sizeof(double));
-    std::memcpy(hin + (size_t)n * sizeof(double), y, (size_t)n * sizeof(double));
-    std::memcpy(hin + (size_t)2 * n * sizeof(double), cos_yaw, (size_t)n * sizeof(double));
-    std::memcpy(hin + (size_t)3 * n * sizeof(double), sin_yaw, (size_t)n * sizeof(double));
-    int32_t* ht = (int32_t*)(hin + (size_t)4 * n * sizeof(double));
-    int32_t* hoff = ht + n;
-    double* hlx = (double*)(hin + lan_xy);
-    double* hly = hlx + n_lan;
-    hoff[0] = 0;
-    for (int v = 0; v < n; ++v) {
-        ht[v] = trim[v] - 1;
-        const int a = lan->offset[v], nl = lan->offset[v + 1] - a;
-        const int m = nl ? pdmpc_lanelet_polygon_normalize(lan->x + a, lan->y + a, nl, hlx + hoff[v], hly + hoff[v]) : 0;
-        hoff[v + 1] = hoff[v] + m;
-    }
-    const int n_norm = hoff[n];
-    if (n_norm != n_lan) {  // (duplicates dropped: x and y of the normalized polygons are contiguous again)
-        std::memmove(hlx + n_norm, hly, (size_t)n_norm * sizeof(double));
-    }
-    HIPCHK(hipMemcpyAsync(h->d_bound_in.p, hin, lan_xy + (size_t)2 * n_norm * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    const BoundArgs A = bound_args(h, n, S, n_norm);
-    HIPCHK(hipEventRecord(h->bound_ev[0], h->stream));
-    const int lrc = pdmpc_launch_bound_sets(&A, (void*)h->stream);
-    if (lrc) return fail(PDMPC_ERR_HIP, std::string("lanelet bounding kernel launch failed: ") + hipGetErrorString((hipError_t)lrc));
-    HIPCHK(hipEventRecord(h->bound_ev[1], h->stream));
-    int32_t* hn = (int32_t*)h->h_bound_out.p;
-    uint8_t* hf = (uint8_t*)(hn + sets);
-    HIPCHK(hipMemcpyAsync(hn, h->d_bound_n.p, sets * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(hf, h->d_bound_flags.p, sets, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(sync_stream(h));
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, h->bound_ev[0], h->bound_ev[1]) == hipSuccess) h->bound_kernel_ms[0] = ms;
-    bool over = false;
-    int maxc = 0;
-    for (size_t o = 0; o < sets; ++o) {
-        if (hf[o] & PDMPC_BOUND_OVERFLOW) over = true;
-        offset[o + 1] = offset[o] + hn[o];
-        maxc = std::max(maxc, (int)hn[o]);
-    }
-    if (over) return fail(PDMPC_ERR_CAPACITY, "pdmpc_bound_reachable_sets: a bounded set has more than PDMPC_BOUNDED_MAX_COLS vertices");
-    h->bound_n = n;
-    h->bound_S = S;
-    h->bound_n_lan = n_norm;
-    h->bound_valid = true;
-    if (!out_x || !out_y || capacity < offset[sets]) return fail(PDMPC_ERR_CAPACITY, "pdmpc_bound_reachable_sets: capacity too small for the bounded sets");
-    // read back the used part of every slot (a pitched copy), then pack
-    if (h->h_bound_xy.ensure(2 * sets * (size_t)maxc)) return fail(PDMPC_ERR_HIP, "hipHostMalloc failed for the bounded sets");
-    double* bx = h->h_bound_xy.p;
-    double* by = bx + sets * (size_t)maxc;
-    const size_t pitch = (size_t)PDMPC_BOUND_SLOT * sizeof(double), width = (size_t)maxc * sizeof(double);
-    HIPCHK(hipMemcpy2DAsync(bx, width, A.set_x, pitch, width, sets, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpy2DAsync(by, width, A.set_y, pitch, width, sets, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(sync_stream(h));
-    for (size_t o = 0; o < sets; ++o) {
-        std::memcpy(out_x + offset[o], bx + o * maxc, (size_t)hn[o] * sizeof(double));
-        std::memcpy(out_y + offset[o], by + o * maxc, (size_t)hn[o] * sizeof(double));
-    }
-    if (flags) std::memcpy(flags, hf, sets);
-    return PDMPC_OK;
-}
-
-int pdmpc_bounded_set_coupling(pdmpc_handle* h, uint8_t* adjacency, double* area) {
-    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
-    if (!adjacency) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling: null adjacency");
-    if (!h->bound_valid) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling without a successful pdmpc_bound_reachable_sets");
-    const int n = h->bound_n;
-    if (n == 0) return PDMPC_OK;
-    ON_DEVICE(h->cfg.device);
-    const BoundArgs A = bound_args(h, n, h->bound_S, h->bound_n_lan);
-    HIPCHK(hipMemsetAsync(A.n_pairs, 0, sizeof(int32_t), h->stream));
-    HIPCHK(hipEventRecord(h->bound_ev[2], h->stream));
-    const int lrc = pdmpc_launch_bounded_coupling(&A, (void*)h->stream);
-    if (lrc) return fail(PDMPC_ERR_HIP, std::string("bounded-set coupling kernel launch failed: ") + hipGetErrorString((hipError_t)lrc));
-    HIPCHK(hipEventRecord(h->bound_ev[3], h->stream));
-    const size_t area_at = align_up8((size_t)n * n);
-    const size_t out_bytes = area ? area_at + (size_t)n * n * sizeof(double) : (size_t)n * n;
-    HIPCHK(hipMemcpyAsync(h->h_bound_out.p, h->d_bound_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(sync_stream(h));
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, h->bound_ev[2], h->bound_ev[3]) == hipSuccess) h->bound_kernel_ms[1] = ms;
-    std::memcpy(adjacency, h->h_bound_out.p, (size_t)n * n);
-    if (area) std::memcpy(area, h->h_bound_out.p + area_at, (size_t)n * n * sizeof(double));
-    return PDMPC_OK;
-}
-
-int pdmpc_bounded_reachable_kernel_ms(pdmpc_handle* h, double* ms2) {
-    if (!h || !ms2) return fail(PDMPC_ERR_INVALID, "null argument");
-    ms2[0] = (double)h->bound_kernel_ms[0];
-    ms2[1] = (double)h->bound_kernel_ms[1];
-    return PDMPC_OK;
-}
-
-int pdmpc_reachable_set_coupling_kernel_ms(pdmpc_handle* h, double* ms) {
-    if (!h || !ms) return fail(PDMPC_ERR_INVALID, "null argument");
-    *ms = (double)h->reach_kernel_ms;
-    return PDMPC_OK;
-}
-
-// ---- future collision assessment on the device (fca_kernel.hip)
-int pdmpc_fca_collisions(pdmpc_handle* h, int32_t n, int32_t Hp, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw,
-                         int32_t n_pairs, const int32_t* pairs, const pdmpc_polygon_set* obstacles, const pdmpc_polygon_set* dynamic_rows, double length,
-                         double width, double offset, int32_t* collisions, int32_t* priorities) {
-    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
-    const char* why = nullptr;
-    if (const int rc = pdmpc_fca_check_args(n, Hp, x, y, cos_yaw, sin_yaw, n_pairs, pairs, obstacles, dynamic_rows, collisions, priorities, &why))
-        return fail(rc, std::string("pdmpc_fca_collisions: ") + why);
-    const int m = n * Hp;
-    const int S = obstacles ? obstacles->n_polygons : 0, D = dynamic_rows ? dynamic_rows->n_polygons : 0, R = D / Hp;
-    const int s0 = S ? obstacles->offset[0] : 0, Ns = S ? obstacles->offset[S] - s0 : 0;
-    const int d0 = D ? dynamic_rows->offset[0] : 0, Nd = D ? dynamic_rows->offset[D] - d0 : 0;
-    // the staged inputs (one copy in): doubles x, y, cos, sin [4 m] | static x, y | dynamic x, y, then int32 pairs [2 P] | static
-    // offsets [S + 1] | dynamic offsets [D + 1] (both rebased to 0); on the device behind them footprints [8 m] and counts [n]
-    const size_t o_sx = (size_t)4 * m, o_dx = o_sx + (size_t)2 * Ns, n_dbl = o_dx + (size_t)2 * Nd;
-    const size_t o_pairs = n_dbl * sizeof(double), o_soff = o_pairs + (size_t)2 * n_pairs * sizeof(int32_t), o_doff = o_soff + ((size_t)S + 1) * sizeof(int32_t);
-    const size_t in_bytes = (o_doff + ((size_t)D + 1) * sizeof(int32_t) + 7) & ~(size_t)7;
-    const size_t o_fp = in_bytes, o_cnt = o_fp + (size_t)8 * m * sizeof(double), total = o_cnt + (size_t)n * sizeof(int32_t);
-    ON_DEVICE(h->cfg.device);
-    if (h->d_fca_ws.ensure(total) || h->h_fca_in.ensure(in_bytes) || h->h_fca_out.ensure((size_t)n))
-        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the collision assessment");
-    for (hipEvent_t& e : h->fca_ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    unsigned char* hin = h->h_fca_in.p;
-    double* hd = (double*)hin;
-    std::memcpy(hd, x, (size_t)m * sizeof(double));
-    std::memcpy(hd + m, y, (size_t)m * sizeof(double));
-    std::memcpy(hd + 2 * (size_t)m, cos_yaw, (size_t)m * sizeof(double));
-    std::memcpy(hd + 3 * (size_t)m, sin_yaw, (size_t)m * sizeof(double));
-    if (Ns) {
-        std::memcpy(hd + o_sx, obstacles->x + s0, (size_t)Ns * sizeof(double));
-        std::memcpy(hd + o_sx + Ns, obstacles->y + s0, (size_t)Ns * sizeof(double));
-    }
-    if (Nd) {
-        std::memcpy(hd + o_dx, dynamic_rows->x + d0, (size_t)Nd * sizeof(double));
-        std::memcpy(hd + o_dx + Nd, dynamic_rows->y + d0, (size_t)Nd * sizeof(double));
-    }
-    if (n_pairs) std::memcpy(hin + o_pairs, pairs, (size_t)2 * n_pairs * sizeof(int32_t));
-    int32_t* soff = (int32_t*)(hin + o_soff);
-    int32_t* doff = (int32_t*)(hin + o_doff);
-    for (int p = 0; p <= S; ++p) soff[p] = S ? obstacles->offset[p] - s0 : 0;
-    for (int p = 0; p <= D; ++p) doff[p] = D ? dynamic_rows->offset[p] - d0 : 0;
-    unsigned char* ws = h->d_fca_ws.p;
-    const double* wd = (const double*)ws;
-    FcaArgs A;
-    A.n = n;
-    A.Hp = Hp;
-    A.n_pairs = n_pairs;
-    A.n_static = S;
-    A.n_rows = R;
-    A.length = length;
-    A.width = width;
-    A.offset = offset;
-    A.n_pair_items = (int64_t)n_pairs * Hp;
-    A.n_static_items = (int64_t)(n - 1) * Hp * S;
-    A.n_items = A.n_pair_items + A.n_static_items + (int64_t)(n - 1) * Hp * R;
-    A.in = wd;
-    A.static_x = wd + o_sx;
-    A.static_y = wd + o_sx + Ns;
-    A.dyn_x = wd + o_dx;
-    A.dyn_y = wd + o_dx + Nd;
-    A.pairs = (const int32_t*)(ws + o_pairs);
-    A.static_off = (const int32_t*)(ws + o_soff);
-    A.dyn_off = (const int32_t*)(ws + o_doff);
-    A.fp = (double*)(ws + o_fp);
-    A.counts = (int32_t*)(ws + o_cnt);
-    HIPCHK(hipMemcpyAsync(ws, hin, in_bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipEventRecord(h->fca_ev[0], h->stream));
-    const int lrc = pdmpc_launch_fca(&A, (void*)h->stream);
-    if (lrc) return fail(PDMPC_ERR_HIP, std::string("collision assessment kernel launch failed: ") + hipGetErrorString((hipError_t)lrc));
-    HIPCHK(hipEventRecord(h->fca_ev[1], h->stream));
-    HIPCHK(hipMemcpyAsync(h->h_fca_out.p, ws + o_cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(sync_stream(h));
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, h->fca_ev[0], h->fca_ev[1]) == hipSuccess) h->fca_kernel_ms = ms;
-    std::memcpy(collisions, h->h_fca_out.p, (size_t)n * sizeof(int32_t));
-    pdmpc_fca_sort_index(n, collisions, priorities);
-    return PDMPC_OK;
-}
-
-int pdmpc_fca_kernel_ms(pdmpc_handle* h, double* ms) {
-    if (!h || !ms) return fail(PDMPC_ERR_INVALID, "null argument");
-    *ms = (double)h->fca_kernel_ms;
     return PDMPC_OK;
 }
 

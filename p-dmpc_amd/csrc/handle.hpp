@@ -1,0 +1,377 @@
+// handle.hpp — what the translation units of the C ABI's host side share (api.cpp: the searches; step_prep.cpp: the step-preparation
+// calls): error reporting, the device guard, the owning buffers and struct pdmpc_handle.  Private to the library.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/pdmpc.h"
+#include "pdmpc_device.h"
+
+extern "C" void pdmpc_set_last_error(const char* msg);  // api.cpp: the string pdmpc_last_error returns
+
+inline int fail(int code, const std::string& msg) {
+    pdmpc_set_last_error(msg.c_str());
+    return code;
+}
+
+#define HIPCHK(expr)                                                                                 \
+    do {                                                                                             \
+        hipError_t e__ = (expr);                                                                     \
+        if (e__ != hipSuccess) {                                                                     \
+            char buf__[512];                                                                         \
+            snprintf(buf__, sizeof buf__, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
+            return fail(PDMPC_ERR_HIP, buf__);                                                       \
+        }                                                                                            \
+    } while (0)
+
+// The current device belongs to the caller (torch reads it with hipGetDevice: a collective issued after a call into this library
+// must not find itself on another GPU).  Every entry point that works on the handle's device switches to it through this guard,
+// which puts the caller's device back on every exit path.
+struct DeviceGuard {
+    int prev = -1;
+    bool switched = false;
+    hipError_t err = hipSuccess;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) {
+            err = hipSetDevice(dev);
+            switched = err == hipSuccess;
+        }
+    }
+    ~DeviceGuard() {
+        if (switched && prev >= 0) (void)hipSetDevice(prev);
+    }
+    DeviceGuard(const DeviceGuard&) = delete;
+    DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+#define ON_DEVICE(dev)                 \
+    DeviceGuard device_guard__((dev)); \
+    HIPCHK(device_guard__.err)
+
+// Buffers own their memory: move-only (a vector of banks moves them when it grows), freed with their owner.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;  // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    ~DevBuf() { release(); }
+    int ensure(size_t n) {
+        const size_t want = std::max(n, (size_t)64);
+        return n <= cap ? 0 : ensure_exact(want + want / 2);
+    }
+    int ensure_exact(size_t n) {  // no head room: the arenas are sized in gigabytes
+        if (n <= cap) return 0;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        hipError_t e = hipMalloc((void**)&p, std::max(n, (size_t)64) * sizeof(T));
+        if (e != hipSuccess) return (int)e;
+        cap = std::max(n, (size_t)64);
+        return 0;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+template <class T>
+struct PinnedBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf(PinnedBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    ~PinnedBuf() { release(); }
+    int ensure(size_t n) { return ensure_keep(n, 0); }
+    int ensure_keep(size_t n, size_t keep) {  // the first `keep` elements carried over
+        if (n <= cap) return 0;
+        size_t want = std::max(n, (size_t)64);
+        want += want / 2;
+        T* q = nullptr;
+        hipError_t e = hipHostMalloc((void**)&q, want * sizeof(T), hipHostMallocDefault);
+        if (e != hipSuccess) return (int)e;
+        if (p && keep) std::memcpy(q, p, std::min(keep, cap) * sizeof(T));
+        if (p) (void)hipHostFree(p);
+        p = q;
+        cap = want;
+        return 0;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+// The per-vehicle arenas of the searches (NodeArena, pdmpc_device.h): max_nodes entries per vehicle in every array (contents are
+// scratch: every search starts from an empty tree).
+struct Arenas {
+    uint32_t max_nodes = 0;
+    DevBuf<NodeRec> nodes;
+    DevBuf<double> key, far_key, mid_key, pb_key, walk;
+    DevBuf<unsigned long long> link;
+    DevBuf<uint32_t> far_id, mid_id, pb_d, child0, vlist;
+    DevBuf<uint8_t> vstate;
+    // every array with its entries per node: walk holds 16 bytes per node, vlist the verification's Hp + 1 lists
+    template <class Self, class F>
+    static void each(Self& a, int Hp, F&& f) {
+        f(a.nodes, 1);
+        f(a.key, 1);
+        f(a.link, 1);
+        f(a.vstate, 1);
+        f(a.far_key, 1);
+        f(a.far_id, 1);
+        f(a.mid_key, 1);
+        f(a.mid_id, 1);
+        f(a.pb_key, 1);
+        f(a.pb_d, 1);
+        f(a.walk, 2);
+        f(a.child0, 1);
+        f(a.vlist, Hp + 1);
+    }
+    size_t bytes_per_node(int Hp) const {
+        size_t sum = 0;
+        each(*this, Hp, [&](const auto& b, int per) { sum += (size_t)per * sizeof *b.p; });
+        return sum;
+    }
+    // everything released first (the arenas are sized in gigabytes); on failure max_nodes is 0 and the caller allocates again
+    int alloc(int max_vehicles, uint32_t n, int Hp) {
+        n = (n + 1u) & ~1u;
+        const size_t tot = (size_t)max_vehicles * n;
+        each(*this, Hp, [](auto& b, int) { b.release(); });
+        max_nodes = 0;
+        int bad = 0;
+        each(*this, Hp, [&](auto& b, int per) { bad |= b.ensure_exact(tot * (size_t)per); });
+        if (bad) return bad;
+        max_nodes = n;
+        return 0;
+    }
+    NodeArena view() const {
+        return {nodes.p, key.p, link.p, vstate.p, far_key.p, far_id.p, mid_key.p, mid_id.p, pb_key.p, pb_d.p, walk.p, child0.p, vlist.p};
+    }
+};
+
+// pdmpc_stats.kernel: what the last launch ran
+enum LaunchKind : int32_t { kLaunchSearch = 2, kLaunchSampled = 3, kLaunchJoint = 4 };
+
+// one packed batch: host mirror (pinned) + device copy, each ONE allocation -- [DevVehicle records | points pool | predecessor slots] --
+// so a pack is one host-to-device copy
+struct PackedStep {
+    PinnedBuf<unsigned char> h_blob;
+    DevBuf<unsigned char> d_blob;
+    DevVehicle* h_veh = nullptr;  // (views into the blobs, set by pack_common)
+    double* h_pts = nullptr;
+    int32_t* h_pred = nullptr;
+    DevVehicle* d_veh = nullptr;
+    double* d_pts = nullptr;
+    int32_t* d_pred = nullptr;
+    uint64_t staged_serial = ~0ull;  // the handle's sync_serial when the copy out of h_blob was queued (pack_common)
+    int n_packed = 0;
+    bool pack_failed = false;  // the last pack into this bank did not finish: nothing to launch or fetch
+    bool sampled = false;      // packed with seeds (pdmpc_set_step_seeds): a sampled bank, its launches run the sampled optimizer
+    int soup_cap = 0;
+    int cand_cap = 0;  // most segments any single edge check can see (one step's soups + the boundary)
+    std::vector<int64_t> lit_cols;  // per slot: literal soup + boundary columns (for the bytes formula)
+    std::vector<int32_t> perm;      // empty: slot s holds the caller's vehicle s; else slot s holds vehicle perm[s] (pack_common put the batch into level order)
+    std::vector<int32_t> inv;       // ... and vehicle v sits in slot inv[v]
+};
+
+// what pack_common tells vehicles that hand over the same arrays by: the pointers and counts of a vehicle's polygon sets
+struct SoupKey {
+    const void* p[13];
+    int32_t c[6];
+};
+
+// Tuning knobs and A/B / test switches of the graph search.  The defaults are the measured optima quoted next to their use; every
+// setting leaves the results bit-identical.  ONE environment variable overrides them, read once in pdmpc_create (a launch makes no
+// getenv call):  PDMPC_TUNING="key=value,key=value,..."  with the keys below (include/pdmpc.h documents the variable).
+struct Tuning {
+    int round0 = -1;        // nodes a round of a young search takes (-1: 24; 32 for a launch that leaves CUs idle but has fewer than four helpers per search, C3, and for one of more than two searches per CU, C5)
+    int round = -1;         // the most a round takes (-1: 1000 with helper workgroups, else 256)
+    int ramp = -1;          // a round grows by 1 / ramp of the nodes processed so far (-1: 2 with helper workgroups, else 4)
+    int ready = 2048;       // entries of the ready list with helper workgroups (half of it without): the most a round can take
+    int share_min = -1;     // a round with at least this many nodes is shared with the helper workgroups (-1: by the number of helpers per search, launch_range)
+    int tile = -1;          // the most nodes of a shared round one seated helper takes (-1: 256; what it stages in LDS: at most 768)
+    int mid_min = 24576;    // far lists longer than this feed near through the mid list (a band of far's smallest keys)
+    int mid_fill = 12288;   // entries a refill of mid aims at
+    int tentative = 1;      // expected areas of predecessors that are still planning (A/B switch)
+    int fast_arrival = 1;   // finished searches check arrivals against their plan's path first and publish early (A/B switch)
+    int helpers = -1;       // helper workgroups of a launch with at most one search per CU (-1: by launch size, 0: none)
+    int helpers_oversub = -1;  // ... of a launch with more searches than CUs (-1: 200)
+    int seat_nodes = 256;   // a search may hold its share of the launch's helpers (helpers / searches) per this many nodes it has processed
+    int helpers_first = -1; // ... of them dispatched in front of the searches (-1: half the CUs when most searches of the launch have predecessors)
+    int speculate = 1;      // 0: every search waits for all its predecessors before it starts
+    int compact = -1;       // 1: the kernel built for two workgroups per CU (8 wavefronts, <= 80 KB of LDS: bulk_kernel_compact.hip) where it applies (InterX, one mask word, the soup fits); 0: never; -1: for launches of more than two searches per CU
+    int waves = -1;         // wavefronts per workgroup (4 .. PDMPC_MAX_WAVES; -1: 16 for the InterX kernels — 12 for a launch of more than two searches per CU —, 12 for the separating-axis kernel)
+    uint32_t spin_limit = 1u << 22;  // the watchdog's limit of polls / rounds (debugging: fail fast)
+    int force_tie = 0;      // testing only: every search ends on the replay through the reference's binary heap (as if it had met equal keys)
+    int reverse_dispatch = 0;  // testing only: workgroup b takes slot n - 1 - b (successors dispatched before their predecessors)
+    int debug_tail = 0;     // round / node / tick counters of every search in the unused rows of its record's path_nodes (tools/fr_step_profile.py)
+    int debug_lds = 0;      // print the LDS layout of every launch
+    int debug_host = 0;     // 1: a line per launch; 2: the host-time breakdown of the literal path
+    int debug_progress = 0; // live counters in host-mapped memory (pdmpc_debug_progress)
+};
+
+// ---- state of the step-preparation calls (step_prep.cpp): work that runs once per time step before the searches are packed
+
+// The event pair around one launch per call and its time (timed_launch in step_prep.cpp creates and records them): destroyed with
+// its owner (pdmpc_destroy deletes the handle on the handle's device, after the handle's destructor has synchronised the stream).
+struct TimedLaunch {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    float ms = 0.0f;  // of the last launch that was folded
+    TimedLaunch() = default;
+    TimedLaunch(const TimedLaunch&) = delete;
+    TimedLaunch& operator=(const TimedLaunch&) = delete;
+    ~TimedLaunch() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    void fold() {  // after the stream was synchronised behind ev[1]
+        float t = 0.0f;
+        if (hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) ms = t;
+    }
+};
+
+// pdmpc_unique_priorities (priority_kernel.hip)
+struct PrioState {
+    DevBuf<uint32_t> count, mask;  // acyclic masks per tile, the acyclic masks
+    DevBuf<int64_t> off;           // exclusive offsets of the tiles (entry n_tiles: the total)
+    DevBuf<int32_t> order;         // the priorities of every acyclic mask
+};
+
+// pdmpc_upload_reachable_sets / pdmpc_reachable_set_coupling (reachable_kernel.hip): the local hulls, and the coupler's workspace
+// and pinned staging (reach_layout), sized at upload for max_vehicles vehicles
+struct ReachState {
+    bool valid = false;  // an upload succeeded
+    int trims = 0, Hp = 0, cols = 0;
+    DevBuf<double> local;   // x of every trim's step-Hp hull, then y
+    DevBuf<int32_t> off;    // [n_trims + 1]
+    std::vector<int32_t> off_host;
+    DevBuf<unsigned char> ws;
+    PinnedBuf<unsigned char> h_in, h_out;
+    DevBuf<double> all;     // every trim's local hulls of every step (x, then y), for pdmpc_bound_reachable_sets
+    DevBuf<int32_t> all_off;  // [n_trims * Hp + 1]
+    int all_tot = 0;
+    TimedLaunch coupling;
+};
+
+// pdmpc_bound_reachable_sets / pdmpc_bounded_set_coupling (bounded_kernel.hip): the sets of the last bound call stay here; grown
+// when a call needs more, kept otherwise
+struct BoundState {
+    bool valid = false;  // the last bound call succeeded
+    int n = 0, S = 0, n_lan = 0;
+    DevBuf<unsigned char> in;   // the staged inputs (bound_layout)
+    DevBuf<double> sets;        // slots: x of every set, then y
+    DevBuf<int32_t> set_n, pairs;  // vertices per set | the pair list, then its counter
+    DevBuf<uint8_t> flags;
+    DevBuf<double> box;
+    DevBuf<unsigned char> out;  // adjacency and areas (carve_pair_out)
+    PinnedBuf<unsigned char> h_in, h_out;
+    PinnedBuf<double> h_xy;
+    TimedLaunch bounding, coupling;
+};
+
+// pdmpc_fca_collisions (fca_kernel.hip): workspace and pinned staging of the inputs (carved in the call) and of the counts; grown when a
+// call needs more, kept otherwise
+struct FcaState {
+    DevBuf<unsigned char> ws;
+    PinnedBuf<unsigned char> h_in;
+    PinnedBuf<int32_t> h_out;
+    TimedLaunch timed;
+};
+
+struct pdmpc_handle {
+    pdmpc_config cfg{};
+    Tuning tune{};
+    hipStream_t stream = nullptr;
+    int n_cu = 256;
+    // MPA
+    bool has_mpa = false;
+    int n_trims = 0, n_words = 0, n_man = 0;
+    DevBuf<uint64_t> d_mask;
+    DevBuf<int16_t> d_mi;
+    DevBuf<DevManPose> d_pose;
+    DevBuf<double> d_area;
+    size_t mask_bytes = 0, mi_bytes = 0;
+    int64_t mpa_alg_bytes = 0;
+    Arenas arena;
+    uint32_t max_nodes_limit = 0;  // pdmpc_plan_* may grow the arenas up to this many nodes per vehicle (0: as far as HBM allows)
+    int64_t arena_regrows = 0;     // times an overflowed call was re-planned with larger arenas
+    int64_t safe_replans = 0;      // times a call was re-planned in resident slices after a predecessor time-out
+    bool safe_launches = false;    // pdmpc_set_safe_launch: every launch in resident slices
+    int max_vehicles = 0;
+    DevBuf<pdmpc_vehicle_out> d_out;
+    DevBuf<uint32_t> d_flag;
+    DevBuf<int32_t> d_tree_size;
+    DevBuf<int32_t> d_tie_count;
+    DevBuf<unsigned long long> d_work_count;
+    DevBuf<unsigned long long> d_help_board;  // helper workgroups (pdmpc_device.h)
+    DevBuf<uint32_t> d_help_verdict, d_help_finished;
+    DevBuf<double> d_bk_post;                 // records posted for the helper workgroups
+    LaunchKind launch_kind = kLaunchSampled;  // of the last launch (before the first one: what pdmpc_get_last_stats always reported)
+    DevBuf<int32_t> d_joint_off;         // pdmpc_plan_joint: the problems' first slots
+    // the step-preparation calls (step_prep.cpp), one member per call family
+    PrioState prio;
+    ReachState reach;
+    BoundState bound;
+    FcaState fca;
+    int device_share = 1;                // handles of one process that launch on this device side by side (pdmpc_set_device_share: a group's logical ranks)
+    bool boards_dirty = true;            // the helper boards / the finished counter need clearing before the helper workgroups may read them
+    uint32_t help_fin_total = 0;         // value of the finished counter once every launch so far has ended
+    uint32_t launch_serial = 0;          // launches of this handle so far (KernelArgs::launch_id)
+    double last_us[3] = {0, 0, 0};       // pdmpc_last_call_timing: pack, enqueue, wait + read-back of the last pdmpc_plan_batch / pdmpc_plan_step
+    double dbg_us[4] = {0, 0, 0, 0};     // debug_host 2: pack, launch, fetch (host clock) and kernel (events) time of the plan_batch calls
+    uint64_t sync_serial = 0;            // stream synchronisations through sync_stream so far (PackedStep::staged_serial)
+    std::vector<SoupKey> pack_soup_keys;  // pack_common's scratch: the distinct soup keys of the batch, the slots they were packed in, the hash table over them
+    std::vector<int32_t> pack_soup_slot, pack_soup_table;
+    std::vector<double> next_weights;    // pdmpc_set_step_weights: expected work per vehicle of the NEXT packed step (the caller's order); consumed by that pack
+    std::vector<uint32_t> next_seeds;    // pdmpc_set_step_seeds: the sampled optimizer's seed per vehicle of the NEXT packed step (the caller's order) ...
+    bool seeds_set = false;              // ... consumed by that pack, which makes its bank a sampled bank
+    PinnedBuf<double> h_lean;            // fetch_lean: (cost, status) per slot
+    DevBuf<double> d_lean;
+    PinnedBuf<pdmpc_vehicle_out> h_out;  // pdmpc_fetch_results: the records land in pinned memory (a copy into the caller's pageable array goes through the runtime's staging otherwise)
+    int bk_ready_launch = 2048;          // entries of the ready list of the last layout
+    uint32_t* progress = nullptr;        // pinned, debug_progress
+    int n_waves = PDMPC_MAX_WAVES;       // of the last layout
+    bool compact_layout = false;         // the last layout is the compact kernel's (two workgroups per CU)
+    // batch blobs: several packed steps can stay resident side by side ("banks", pdmpc_select_bank)
+    std::vector<PackedStep> banks;
+    int bank = 0;
+    uint32_t epoch = 1;  // done flags start at 0, so no slot looks solved before its first launch
+    // launches
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+    size_t events_used = 0;
+    double folded_kernel_ms = 0.0;  // launches whose event pairs were recycled (resident launches without a pack or reset in between)
+    int64_t folded_launches = 0;
+    LdsLayout lds{};
+    int NL = 0, NV = 0, areas_in_lds = 0;
+    pdmpc_stats stats{};
+    // the buffers free themselves after this: the stream is idle by then
+    ~pdmpc_handle() {
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (auto& ev : events) {
+            (void)hipEventDestroy(ev.first);
+            (void)hipEventDestroy(ev.second);
+        }
+        if (progress) (void)hipHostFree(progress);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+
+// hipStreamSynchronize on the launch stream, counted: a bank whose staging copy was queued before is free again (pack_common)
+inline hipError_t sync_stream(pdmpc_handle* h) {
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) h->sync_serial += 1;
+    return e;
+}

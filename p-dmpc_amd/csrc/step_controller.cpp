@@ -44,6 +44,16 @@ struct Poly {  // 2 x V, MATLAB [x; y]
     int n() const { return (int)x.size(); }
 };
 
+// (offsets, x, y) vectors viewed as a polygon set of off.size() - 1 polygons (no copy: the vectors outlive the view)
+pdmpc_polygon_set view_polygons(const std::vector<int32_t>& off, const std::vector<double>& x, const std::vector<double>& y) {
+    pdmpc_polygon_set ps;
+    ps.n_polygons = (int32_t)off.size() - 1;
+    ps.offset = off.data();
+    ps.x = x.data();
+    ps.y = y.data();
+    return ps;
+}
+
 // the non-zero entries of a matrix as lists: by row (idx[off[i] .. off[i + 1]) = the columns of row i) or by column (the rows of
 // column j), ascending in both forms
 struct Lists {
@@ -883,11 +893,7 @@ int pdmpc_controller_set_reachability(pdmpc_controller* c, const pdmpc_mpa* mpa)
     rc = pdmpc_local_reachable_sets(mpa, off.back(), off.data(), x.data(), y.data());
     if (rc) return cfail(c, rc, "pdmpc_local_reachable_sets failed");
     if (c->h) {
-        pdmpc_polygon_set ps;
-        ps.n_polygons = (int32_t)off.size() - 1;
-        ps.offset = off.data();
-        ps.x = x.data();
-        ps.y = y.data();
+        const pdmpc_polygon_set ps = view_polygons(off, x, y);
         rc = pdmpc_upload_reachable_sets(c->h, mpa->n_trims, mpa->Hp, &ps);
         if (rc) return cfail(c, rc, std::string("pdmpc_upload_reachable_sets: ") + pdmpc_last_error());
     }
@@ -932,7 +938,60 @@ void random_priorities(int time_step, int n, std::vector<int32_t>& p) {
     }
 }
 
-// FcaPrioritizer.m:11-92 on the step's reference points and the scenario's obstacles: on the device with a handle, else the host twin
+// ---- the step-preparation calls: on the device with a handle, else the host twin
+int fca_collisions(pdmpc_controller* c, int32_t n_pairs, const pdmpc_polygon_set& obst) {
+    const pdmpc_controller_config& g = c->cfg;
+    if (c->h) {
+        const int rc = pdmpc_fca_collisions(c->h, c->n, c->Hp, c->fca_x.data(), c->fca_y.data(), c->fca_cos.data(), c->fca_sin.data(), n_pairs, c->fca_pairs.data(), &obst,
+                                            nullptr, g.vehicle_length, g.vehicle_width, g.offset, c->fca_count.data(), c->prio.data());
+        return rc ? cfail(c, rc, std::string("pdmpc_fca_collisions: ") + pdmpc_last_error()) : PDMPC_OK;
+    }
+    const int rc = pdmpc_fca_collisions_host(c->n, c->Hp, c->fca_x.data(), c->fca_y.data(), c->fca_cos.data(), c->fca_sin.data(), n_pairs, c->fca_pairs.data(), &obst,
+                                             nullptr, g.vehicle_length, g.vehicle_width, g.offset, c->fca_count.data(), c->prio.data());
+    return rc ? cfail(c, rc, "pdmpc_fca_collisions_host failed") : PDMPC_OK;
+}
+// (the status as it is: the caller tries again with more room after PDMPC_ERR_CAPACITY)
+int bound_sets(pdmpc_controller* c, const pdmpc_polygon_set& lan, int all_steps, int32_t cap, double* ox, double* oy) {
+    if (c->h)
+        return pdmpc_bound_reachable_sets(c->h, c->n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(), c->trims.data(), &lan, all_steps, cap,
+                                          c->bound_off.data(), ox, oy, nullptr);
+    const pdmpc_polygon_set local = view_polygons(c->reach_off, c->reach_x, c->reach_y);
+    return pdmpc_bound_reachable_sets_host((int32_t)c->trim_speed.size(), c->Hp, &local, c->n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(),
+                                           c->trims.data(), &lan, all_steps, cap, c->bound_off.data(), ox, oy, nullptr);
+}
+// on the bounded step-Hp sets (S sets per vehicle): on the device they are still there
+int couple_bounded_sets(pdmpc_controller* c, int S) {
+    const int n = c->n;
+    if (c->h) {
+        const int rc = pdmpc_bounded_set_coupling(c->h, c->adjacency.data(), nullptr);
+        return rc ? cfail(c, rc, std::string("pdmpc_bounded_set_coupling: ") + pdmpc_last_error()) : PDMPC_OK;
+    }
+    std::vector<int32_t> off((size_t)n + 1, 0);
+    std::vector<double> sx, sy;
+    for (int v = 0; v < n; ++v) {
+        const int o = v * S + S - 1, a = c->bound_off[o], m = c->bound_off[o + 1] - a;
+        sx.insert(sx.end(), c->bound_x.begin() + a, c->bound_x.begin() + a + m);
+        sy.insert(sy.end(), c->bound_y.begin() + a, c->bound_y.begin() + a + m);
+        off[v + 1] = off[v] + m;
+    }
+    const pdmpc_polygon_set ps = view_polygons(off, sx, sy);
+    const int rc = pdmpc_polygon_set_coupling_host(&ps, n, c->adjacency.data(), nullptr);
+    return rc ? cfail(c, rc, "pdmpc_polygon_set_coupling_host failed") : PDMPC_OK;
+}
+// ReachableSetCoupler.couple (ReachableSetCoupler.m:5-56)
+int couple_reachable_sets(pdmpc_controller* c) {
+    const int n = c->n;
+    if (c->h) {
+        const int rc = pdmpc_reachable_set_coupling(c->h, n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(), c->trims.data(), c->adjacency.data(), nullptr);
+        return rc ? cfail(c, rc, std::string("pdmpc_reachable_set_coupling: ") + pdmpc_last_error()) : PDMPC_OK;
+    }
+    const pdmpc_polygon_set ps = view_polygons(c->reach_off, c->reach_x, c->reach_y);
+    const int rc = pdmpc_reachable_set_coupling_host((int32_t)c->trim_speed.size(), c->Hp, &ps, n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(),
+                                                     c->trims.data(), c->adjacency.data(), nullptr);
+    return rc ? cfail(c, rc, "pdmpc_reachable_set_coupling_host failed") : PDMPC_OK;
+}
+
+// FcaPrioritizer.m:11-92 on the step's reference points and the scenario's obstacles
 int fca_priorities(pdmpc_controller* c) {
     const int n = c->n, Hp = c->Hp;
     if (Hp < 2) return cfail(c, PDMPC_ERR_INVALID, "FCA priorities need Hp >= 2 (calculate_yaw needs two reference points)");
@@ -959,47 +1018,13 @@ int fca_priorities(pdmpc_controller* c) {
             c->fca_pairs.push_back(a);
             c->fca_pairs.push_back(a + 1 + q);
         });
-    pdmpc_polygon_set obst;
-    obst.n_polygons = (int32_t)c->fca_obst_off.size() - 1;
-    obst.offset = c->fca_obst_off.data();
-    obst.x = c->fca_obst_x.data();
-    obst.y = c->fca_obst_y.data();
     c->fca_count.resize(n);
-    const int32_t n_pairs = (int32_t)(c->fca_pairs.size() / 2);
-    const pdmpc_controller_config& g = c->cfg;
-    if (c->h) {
-        const int rc = pdmpc_fca_collisions(c->h, n, Hp, c->fca_x.data(), c->fca_y.data(), c->fca_cos.data(), c->fca_sin.data(), n_pairs, c->fca_pairs.data(), &obst,
-                                            nullptr, g.vehicle_length, g.vehicle_width, g.offset, c->fca_count.data(), c->prio.data());
-        if (rc) return cfail(c, rc, std::string("pdmpc_fca_collisions: ") + pdmpc_last_error());
-    } else {
-        const int rc = pdmpc_fca_collisions_host(n, Hp, c->fca_x.data(), c->fca_y.data(), c->fca_cos.data(), c->fca_sin.data(), n_pairs, c->fca_pairs.data(), &obst,
-                                                 nullptr, g.vehicle_length, g.vehicle_width, g.offset, c->fca_count.data(), c->prio.data());
-        if (rc) return cfail(c, rc, "pdmpc_fca_collisions_host failed");
-    }
-    return PDMPC_OK;
+    return fca_collisions(c, (int32_t)(c->fca_pairs.size() / 2), view_polygons(c->fca_obst_off, c->fca_obst_x, c->fca_obst_y));
 }
-}  // namespace
 
-int pdmpc_controller_build_step(pdmpc_controller* c) {
-    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
+// ---- the stages of pdmpc_controller_build_step, in its order
+void traffic_info(pdmpc_controller* c) {
     const int n = c->n, Hp = c->Hp;
-    const bool reach_coupling = c->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET, reach_parallel = c->parallel_mode == PDMPC_PARALLEL_REACHABLE_SETS;
-    if ((reach_coupling || reach_parallel) && !c->has_reach)
-        return cfail(c, PDMPC_ERR_INVALID, "reachable-set coupling / parallel coupling by reachable sets need pdmpc_controller_set_reachability first");
-    c->k += 1;
-    c->arena.reset();
-    if (c->exploring) {
-        c->obst_memo.resize((size_t)n);
-        c->dyn_memo.resize((size_t)n);
-        for (int v = 0; v < n; ++v) {
-            c->obst_memo[(size_t)v].clear();
-            c->dyn_memo[(size_t)v].clear();
-        }
-    }
-    c->fb_of.assign(n, pdmpc_polygon_set());
-    c->fb_done.assign(n, 0);
-    c->empty_done = false;
-    // ---- traffic info
     c->trims.assign(n, 0);
     // (resized, not re-created: the per-vehicle vectors keep their capacity from step to step; every one of them is rewritten below)
     c->occ_offset.resize(n);
@@ -1023,131 +1048,82 @@ int pdmpc_controller_build_step(pdmpc_controller* c) {
         sample_reference(Hp, c->veh[v].px, c->veh[v].py, c->mx[v], c->my[v], step, c->ref_x[v], c->ref_y[v], pidx, cpi);
         lanelet_boundary(*c, v, pidx, cpi, c->bnd_left[v], c->bnd_right[v]);
     }
-    // ---- reachable sets at the vehicles' poses (reachable_sets_at_pose, MotionPrimitiveAutomaton.m:649-687), closed by repeating the
-    // first vertex (HighLevelController.m:258-263); only when a feature reads them
-    if (reach_coupling || reach_parallel) {
-        c->reach_sets.resize(n);
-        c->reach_cos.resize(n);
-        c->reach_sin.resize(n);
-        for (int v = 0; v < n; ++v) {
-            const double cy = std::cos(c->myaw[v]), sy = std::sin(c->myaw[v]);
-            c->reach_cos[v] = cy;
-            c->reach_sin[v] = sy;
-            std::vector<Poly>& sets = c->reach_sets[v];
-            sets.resize(Hp);
+}
+
+// reachable sets at the vehicles' poses (reachable_sets_at_pose, MotionPrimitiveAutomaton.m:649-687), closed by repeating the first
+// vertex (HighLevelController.m:258-263)
+void reachable_sets_at_poses(pdmpc_controller* c) {
+    const int n = c->n, Hp = c->Hp;
+    c->reach_sets.resize(n);
+    c->reach_cos.resize(n);
+    c->reach_sin.resize(n);
+    for (int v = 0; v < n; ++v) {
+        const double cy = std::cos(c->myaw[v]), sy = std::sin(c->myaw[v]);
+        c->reach_cos[v] = cy;
+        c->reach_sin[v] = sy;
+        std::vector<Poly>& sets = c->reach_sets[v];
+        sets.resize(Hp);
+        for (int q = 0; q < Hp; ++q) {
+            const int p = (c->trims[v] - 1) * Hp + q, a = c->reach_off[p], m = c->reach_off[p + 1] - a;
+            Poly& P = sets[q];
+            P.x.resize(m + 1);
+            P.y.resize(m + 1);
+            for (int r = 0; r < m; ++r) pdmpc_move_point(cy, sy, c->mx[v], c->my[v], c->reach_x[a + r], c->reach_y[a + r], &P.x[r], &P.y[r]);
+            P.x[m] = P.x[0];
+            P.y[m] = P.y[0];
+        }
+    }
+}
+
+// lanelet bounding of those sets (bound_reachable_sets.m, HighLevelController.m:241-246): every step's sets when parallel
+// predecessors read them (all_steps), else step Hp only (the coupler's)
+int bound_by_lanelets(pdmpc_controller* c, bool all_steps) {
+    const int n = c->n, Hp = c->Hp;
+    c->lan_off.assign((size_t)n + 1, 0);
+    c->lan_x.clear();
+    c->lan_y.clear();
+    for (int v = 0; v < n; ++v) {  // the left boundary, then the reversed right boundary (get_lanelets_boundary.m:69-74)
+        const Poly &L = c->bnd_left[v], &R = c->bnd_right[v];
+        c->lan_x.insert(c->lan_x.end(), L.x.begin(), L.x.end());
+        c->lan_y.insert(c->lan_y.end(), L.y.begin(), L.y.end());
+        c->lan_x.insert(c->lan_x.end(), R.x.rbegin(), R.x.rend());
+        c->lan_y.insert(c->lan_y.end(), R.y.rbegin(), R.y.rend());
+        c->lan_off[v + 1] = (int32_t)c->lan_x.size();
+    }
+    c->lan_x.push_back(0.0);  // (never empty)
+    c->lan_y.push_back(0.0);
+    const pdmpc_polygon_set lan = view_polygons(c->lan_off, c->lan_x, c->lan_y);
+    c->bound_off.assign((size_t)n * (all_steps ? Hp : 1) + 1, 0);
+    int rc = bound_sets(c, lan, all_steps, (int32_t)c->bound_x.size(), c->bound_x.empty() ? nullptr : c->bound_x.data(), c->bound_y.empty() ? nullptr : c->bound_y.data());
+    if (rc == PDMPC_ERR_CAPACITY && c->bound_off.back() > (int32_t)c->bound_x.size()) {
+        c->bound_x.resize((size_t)c->bound_off.back());
+        c->bound_y.resize((size_t)c->bound_off.back());
+        rc = bound_sets(c, lan, all_steps, (int32_t)c->bound_x.size(), c->bound_x.data(), c->bound_y.data());
+    }
+    if (rc) return cfail(c, rc, std::string("pdmpc_bound_reachable_sets: ") + (c->h ? pdmpc_last_error() : "host twin failed"));
+    if (all_steps) {  // the parallel predecessors' obstacles are the bounded sets
+        for (int v = 0; v < n; ++v)
             for (int q = 0; q < Hp; ++q) {
-                const int p = (c->trims[v] - 1) * Hp + q, a = c->reach_off[p], m = c->reach_off[p + 1] - a;
-                Poly& P = sets[q];
-                P.x.resize(m + 1);
-                P.y.resize(m + 1);
-                for (int r = 0; r < m; ++r) pdmpc_move_point(cy, sy, c->mx[v], c->my[v], c->reach_x[a + r], c->reach_y[a + r], &P.x[r], &P.y[r]);
-                P.x[m] = P.x[0];
-                P.y[m] = P.y[0];
+                const int o = v * Hp + q, a = c->bound_off[o], m = c->bound_off[o + 1] - a;
+                Poly& P = c->reach_sets[v][q];
+                P.x.assign(c->bound_x.begin() + a, c->bound_x.begin() + a + m);
+                P.y.assign(c->bound_y.begin() + a, c->bound_y.begin() + a + m);
             }
-        }
     }
-    // ---- lanelet bounding of those sets (bound_reachable_sets.m, HighLevelController.m:241-246; not on scenarios without lanelets):
-    // every step's sets when parallel predecessors read them, else step Hp only (the coupler's)
-    bool bounded = false;
-    if ((reach_coupling || reach_parallel) && c->lanelet_bounding) {
-        for (int v = 0; v < n && !bounded; ++v) bounded = !c->veh[v].lanelets_index.empty();
-    }
-    if (bounded) {
-        c->lan_off.assign((size_t)n + 1, 0);
-        c->lan_x.clear();
-        c->lan_y.clear();
-        for (int v = 0; v < n; ++v) {  // the left boundary, then the reversed right boundary (get_lanelets_boundary.m:69-74)
-            const Poly &L = c->bnd_left[v], &R = c->bnd_right[v];
-            c->lan_x.insert(c->lan_x.end(), L.x.begin(), L.x.end());
-            c->lan_y.insert(c->lan_y.end(), L.y.begin(), L.y.end());
-            c->lan_x.insert(c->lan_x.end(), R.x.rbegin(), R.x.rend());
-            c->lan_y.insert(c->lan_y.end(), R.y.rbegin(), R.y.rend());
-            c->lan_off[v + 1] = (int32_t)c->lan_x.size();
-        }
-        c->lan_x.push_back(0.0);  // (never empty)
-        c->lan_y.push_back(0.0);
-        pdmpc_polygon_set lan;
-        lan.n_polygons = n;
-        lan.offset = c->lan_off.data();
-        lan.x = c->lan_x.data();
-        lan.y = c->lan_y.data();
-        pdmpc_polygon_set local;
-        local.n_polygons = (int32_t)c->reach_off.size() - 1;
-        local.offset = c->reach_off.data();
-        local.x = c->reach_x.data();
-        local.y = c->reach_y.data();
-        const int all_steps = reach_parallel ? 1 : 0, S = all_steps ? Hp : 1;
-        c->bound_off.assign((size_t)n * S + 1, 0);
-        auto bound = [&](int32_t cap, double* ox, double* oy) {
-            if (c->h)
-                return pdmpc_bound_reachable_sets(c->h, n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(), c->trims.data(), &lan, all_steps, cap,
-                                                  c->bound_off.data(), ox, oy, nullptr);
-            return pdmpc_bound_reachable_sets_host((int32_t)c->trim_speed.size(), Hp, &local, n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(),
-                                                   c->trims.data(), &lan, all_steps, cap, c->bound_off.data(), ox, oy, nullptr);
-        };
-        int rc = bound((int32_t)c->bound_x.size(), c->bound_x.empty() ? nullptr : c->bound_x.data(), c->bound_y.empty() ? nullptr : c->bound_y.data());
-        if (rc == PDMPC_ERR_CAPACITY && c->bound_off.back() > (int32_t)c->bound_x.size()) {
-            c->bound_x.resize((size_t)c->bound_off.back());
-            c->bound_y.resize((size_t)c->bound_off.back());
-            rc = bound((int32_t)c->bound_x.size(), c->bound_x.data(), c->bound_y.data());
-        }
-        if (rc) return cfail(c, rc, std::string("pdmpc_bound_reachable_sets: ") + (c->h ? pdmpc_last_error() : "host twin failed"));
-        if (reach_parallel) {  // the parallel predecessors' obstacles are the bounded sets
-            for (int v = 0; v < n; ++v)
-                for (int q = 0; q < Hp; ++q) {
-                    const int o = v * Hp + q, a = c->bound_off[o], m = c->bound_off[o + 1] - a;
-                    Poly& P = c->reach_sets[v][q];
-                    P.x.assign(c->bound_x.begin() + a, c->bound_x.begin() + a + m);
-                    P.y.assign(c->bound_y.begin() + a, c->bound_y.begin() + a + m);
-                }
-        }
-    }
-    // ---- coupling
+    return PDMPC_OK;
+}
+
+// c->adjacency by the configured rule (reachable sets: the bounded ones, bounded_S per vehicle, when the step bounded them)
+int couple(pdmpc_controller* c, int bounded_S) {
+    const int n = c->n;
     c->adjacency.assign((size_t)n * n, 0);
-    if (reach_coupling && bounded) {  // ... on the bounded step-Hp sets: on the device (they are still there), else the host twin
-        int rc;
-        if (c->h) {
-            rc = pdmpc_bounded_set_coupling(c->h, c->adjacency.data(), nullptr);
-            if (rc) return cfail(c, rc, std::string("pdmpc_bounded_set_coupling: ") + pdmpc_last_error());
-        } else {
-            const int S = reach_parallel ? Hp : 1;
-            std::vector<int32_t> off((size_t)n + 1, 0);
-            std::vector<double> sx, sy;
-            for (int v = 0; v < n; ++v) {
-                const int o = v * S + S - 1, a = c->bound_off[o], m = c->bound_off[o + 1] - a;
-                sx.insert(sx.end(), c->bound_x.begin() + a, c->bound_x.begin() + a + m);
-                sy.insert(sy.end(), c->bound_y.begin() + a, c->bound_y.begin() + a + m);
-                off[v + 1] = off[v] + m;
-            }
-            pdmpc_polygon_set ps;
-            ps.n_polygons = n;
-            ps.offset = off.data();
-            ps.x = sx.data();
-            ps.y = sy.data();
-            rc = pdmpc_polygon_set_coupling_host(&ps, n, c->adjacency.data(), nullptr);
-            if (rc) return cfail(c, rc, "pdmpc_polygon_set_coupling_host failed");
-        }
-    } else if (reach_coupling) {  // ReachableSetCoupler.couple (ReachableSetCoupler.m:5-56): on the device with a handle, else the host twin
-        int rc;
-        if (c->h) {
-            rc = pdmpc_reachable_set_coupling(c->h, n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(), c->trims.data(), c->adjacency.data(), nullptr);
-            if (rc) return cfail(c, rc, std::string("pdmpc_reachable_set_coupling: ") + pdmpc_last_error());
-        } else {
-            pdmpc_polygon_set ps;
-            ps.n_polygons = (int32_t)c->reach_off.size() - 1;
-            ps.offset = c->reach_off.data();
-            ps.x = c->reach_x.data();
-            ps.y = c->reach_y.data();
-            rc = pdmpc_reachable_set_coupling_host((int32_t)c->trim_speed.size(), Hp, &ps, n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(),
-                                                   c->trims.data(), c->adjacency.data(), nullptr);
-            if (rc) return cfail(c, rc, "pdmpc_reachable_set_coupling_host failed");
-        }
-    } else if (c->cfg.coupling == PDMPC_COUPLING_FULL) {
+    if (c->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET) return bounded_S ? couple_bounded_sets(c, bounded_S) : couple_reachable_sets(c);
+    if (c->cfg.coupling == PDMPC_COUPLING_FULL) {
         for (int a = 0; a < n; ++a)
             for (int b = 0; b < n; ++b) at(c->adjacency, n, a, b) = a != b;
     } else if (c->cfg.coupling == PDMPC_COUPLING_DISTANCE) {
         const double vmax = *std::max_element(c->trim_speed.begin(), c->trim_speed.end());
-        const double max_distance = 2 * vmax * c->cfg.dt_seconds * Hp;
+        const double max_distance = 2 * vmax * c->cfg.dt_seconds * c->Hp;
         // (hypot(dx, dy) >= max(|dx|, |dy|), also as rounded: a pair farther apart along one axis alone is not coupled — most pairs of
         // a tiled network.  That test runs over the whole row, the distance itself over the survivors.)
         for (int a = 0; a < n; ++a) {
@@ -1162,31 +1138,69 @@ int pdmpc_controller_build_step(pdmpc_controller* c) {
             });
         }
     }
-    // ---- priorities -> directed coupling
+    return PDMPC_OK;
+}
+
+// priorities -> c->directed
+int direct_by_priorities(pdmpc_controller* c) {
+    const int n = c->n;
     if (c->cfg.priority_strategy == PDMPC_PRIORITY_COLORING) {
         coloring_directed(c->adjacency, n, c->directed);
-    } else {
-        // constant priorities = vehicle index (ConstantPrioritizer.m:14-20); random and FCA priorities as below
-        // (Prioritizer.directed_coupling_from_priorities, Prioritizer.m:64-77: keep i -> j iff priority(j) is not below priority(i))
-        c->prio.resize(n);
-        for (int v = 0; v < n; ++v) c->prio[v] = v + 1;
-        if (c->cfg.priority_strategy == PDMPC_PRIORITY_RANDOM) {
-            random_priorities(c->k, n, c->prio);
-        } else if (c->cfg.priority_strategy == PDMPC_PRIORITY_FCA) {
-            const int rc = fca_priorities(c);
-            if (rc) return rc;
-        }
-        c->directed.assign((size_t)n * n, 0);
-        for (int i = 0; i < n; ++i)
-            for_each_set(c->adjacency.data() + (size_t)i * n, n, [&](int j) {
-                if (!(c->prio[j] < c->prio[i])) at(c->directed, n, i, j) = 1;
-            });
+        return PDMPC_OK;
     }
-    const int rc = assemble_step(c);
+    // constant priorities = vehicle index (ConstantPrioritizer.m:14-20); random and FCA priorities as below
+    // (Prioritizer.directed_coupling_from_priorities, Prioritizer.m:64-77: keep i -> j iff priority(j) is not below priority(i))
+    c->prio.resize(n);
+    for (int v = 0; v < n; ++v) c->prio[v] = v + 1;
+    if (c->cfg.priority_strategy == PDMPC_PRIORITY_RANDOM) {
+        random_priorities(c->k, n, c->prio);
+    } else if (c->cfg.priority_strategy == PDMPC_PRIORITY_FCA) {
+        const int rc = fca_priorities(c);
+        if (rc) return rc;
+    }
+    c->directed.assign((size_t)n * n, 0);
+    for (int i = 0; i < n; ++i)
+        for_each_set(c->adjacency.data() + (size_t)i * n, n, [&](int j) {
+            if (!(c->prio[j] < c->prio[i])) at(c->directed, n, i, j) = 1;
+        });
+    return PDMPC_OK;
+}
+}  // namespace
+
+int pdmpc_controller_build_step(pdmpc_controller* c) {
+    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
+    const int n = c->n;
+    const bool reach_parallel = c->parallel_mode == PDMPC_PARALLEL_REACHABLE_SETS;
+    const bool reach = c->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET || reach_parallel;  // a feature reads the reachable sets
+    if (reach && !c->has_reach)
+        return cfail(c, PDMPC_ERR_INVALID, "reachable-set coupling / parallel coupling by reachable sets need pdmpc_controller_set_reachability first");
+    c->k += 1;
+    c->arena.reset();
+    if (c->exploring) {
+        c->obst_memo.resize((size_t)n);
+        c->dyn_memo.resize((size_t)n);
+        for (int v = 0; v < n; ++v) {
+            c->obst_memo[(size_t)v].clear();
+            c->dyn_memo[(size_t)v].clear();
+        }
+    }
+    c->fb_of.assign(n, pdmpc_polygon_set());
+    c->fb_done.assign(n, 0);
+    c->empty_done = false;
+    traffic_info(c);
+    if (reach) reachable_sets_at_poses(c);
+    bool bounded = false;  // (not on scenarios without lanelets)
+    if (reach && c->lanelet_bounding)
+        for (int v = 0; v < n && !bounded; ++v) bounded = !c->veh[v].lanelets_index.empty();
+    int rc = bounded ? bound_by_lanelets(c, reach_parallel) : PDMPC_OK;
+    if (!rc) rc = couple(c, bounded ? (reach_parallel ? c->Hp : 1) : 0);
+    if (!rc) rc = direct_by_priorities(c);
+    if (!rc) rc = assemble_step(c);
     if (rc) return rc;
     set_seeds(c, c->order);
     return PDMPC_OK;
 }
+
 
 namespace {
 // c->directed -> sequential couplings, levels, slot order and the per-slot inputs of pdmpc_plan_step (the arena is the caller's

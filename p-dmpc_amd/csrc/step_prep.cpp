@@ -1,0 +1,488 @@
+// step_prep.cpp — the step-preparation calls of the C ABI: device work that runs once per time step before the searches are packed
+// (unique prioritizations, reachable-set coupling, lanelet bounding and the coupling on the bounded sets, future collision assessment).
+//
+// Every call but pdmpc_unique_priorities follows one recipe: carve ONE pinned staging block and ONE device workspace with the same
+// offsets (Carver), stage the inputs, copy them in once, launch between an event pair (timed_launch), copy the result back, synchronise.
+#include "handle.hpp"
+
+#include "../../include/pdmpc_geometry.h"
+
+namespace {
+
+// Hands out the regions of one block in the order they are asked for.  A region starts at a multiple of its element's alignment
+// (or of `align`); the offsets hold for the pinned staging block and for the device workspace alike.
+struct Carver {
+    size_t at = 0;  // the first free byte: after the last region, the size of the block so far
+    template <class T>
+    size_t take(size_t count, size_t align = alignof(T)) {
+        at = (at + align - 1) & ~(align - 1);
+        const size_t offset = at;
+        at += count * sizeof(T);
+        return offset;
+    }
+    size_t end8() { return take<unsigned char>(0, 8); }  // the size so far, rounded up to 8
+};
+
+// poses as the kernels read them: x, y, cos_yaw, sin_yaw of m poses one array after the other, and the trims 0-based
+void stage_poses(double* in, size_t m, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw, int32_t* trim0 = nullptr,
+                 const int32_t* trim = nullptr) {
+    std::memcpy(in, x, m * sizeof(double));
+    std::memcpy(in + m, y, m * sizeof(double));
+    std::memcpy(in + 2 * m, cos_yaw, m * sizeof(double));
+    std::memcpy(in + 3 * m, sin_yaw, m * sizeof(double));
+    if (trim0)
+        for (size_t v = 0; v < m; ++v) trim0[v] = trim[v] - 1;
+}
+
+// one kernel launch between t's events, created on first use (t.fold() after the caller's synchronise)
+template <class Args>
+int timed_launch(pdmpc_handle* h, TimedLaunch& t, int (*launch)(const Args*, void*), const Args& a, const char* what) {
+    for (hipEvent_t& e : t.ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(t.ev[0], h->stream));
+    const int lrc = launch(&a, (void*)h->stream);
+    if (lrc) return fail(PDMPC_ERR_HIP, std::string(what) + " kernel launch failed: " + hipGetErrorString((hipError_t)lrc));
+    HIPCHK(hipEventRecord(t.ev[1], h->stream));
+    return PDMPC_OK;
+}
+
+// what a coupler writes: adjacency [n x n] (8-aligned), then areas [n x n]
+struct PairOut {
+    size_t adj, area;
+};
+PairOut carve_pair_out(Carver& c, int n) {
+    PairOut o;
+    o.adj = c.take<uint8_t>((size_t)n * n, 8);
+    o.area = c.take<double>((size_t)n * n);
+    return o;
+}
+// ... read back through `pinned` (the areas only when asked for) after t's launch; synchronises the stream
+int fetch_pair_out(pdmpc_handle* h, TimedLaunch& t, const unsigned char* dev, unsigned char* pinned, const PairOut& o, int n, uint8_t* adjacency, double* area) {
+    const size_t nn = (size_t)n * n, bytes = area ? o.area - o.adj + nn * sizeof(double) : nn;
+    HIPCHK(hipMemcpyAsync(pinned, dev + o.adj, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(sync_stream(h));
+    t.fold();
+    std::memcpy(adjacency, pinned, nn);
+    if (area) std::memcpy(area, pinned + (o.area - o.adj), nn * sizeof(double));
+    return PDMPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Prioritizer.unique_priorities (Prioritizer.m:97-140) on the device: priority_kernel.hip.  The acyclic orientations are counted
+// first; the true count K is reported whatever max_out is, and only a K that fits is written (never a truncated list).
+int pdmpc_unique_priorities(pdmpc_handle* h, int32_t n, const uint8_t* adjacency, int64_t max_out, int64_t* n_out, uint32_t* masks, int32_t* priorities) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    if (n_out) *n_out = -1;
+    if (n < 1 || !adjacency || !n_out || max_out < 0 || (max_out > 0 && (!masks || !priorities)))
+        return fail(PDMPC_ERR_INVALID, "pdmpc_unique_priorities: bad argument");
+    if (n > PDMPC_PRIO_MAX_N) return fail(PDMPC_ERR_CAPACITY, "pdmpc_unique_priorities: more than 64 vehicles");
+    PriorityArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.n = n;
+    int E = 0;
+    for (int c = 0; c < n; ++c)  // find(triu(adjacency, 1)): by column, then by row
+        for (int r = 0; r < c; ++r)
+            if (adjacency[(size_t)r * n + c]) ++E;
+    if (E > PDMPC_PRIO_MAX_E) return fail(PDMPC_ERR_CAPACITY, "pdmpc_unique_priorities: more than 32 coupling edges");
+    for (int c = 0, e = 0; c < n; ++c)
+        for (int r = 0; r < c; ++r)
+            if (adjacency[(size_t)r * n + c]) {
+                const uint32_t bit = 1u << (E - 1 - e);  // dec2bin(m, E): edge 1 is the most significant bit
+                A.in_base[c] |= bit;
+                A.out_base[r] |= bit;
+                ++e;
+            }
+    for (int v = 0; v < n; ++v)
+        if (A.in_base[v] | A.out_base[v]) A.active[A.n_active++] = v;
+    A.E = E;
+    A.all_edges = E == 32 ? 0xffffffffu : (1u << E) - 1u;
+    A.n_masks = 1ull << E;
+    const int64_t n_tiles = (int64_t)((A.n_masks + PDMPC_PRIO_TILE - 1) / PDMPC_PRIO_TILE);
+    ON_DEVICE(h->cfg.device);
+    PrioState& P = h->prio;
+    if (P.count.ensure((size_t)n_tiles) || P.off.ensure((size_t)n_tiles + 1))
+        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the tile counts of pdmpc_unique_priorities");
+    int lrc = pdmpc_launch_priority_count(&A, n_tiles, P.count.p, (void*)h->stream);
+    if (!lrc) lrc = pdmpc_launch_priority_scan(P.count.p, n_tiles, P.off.p, (void*)h->stream);
+    if (lrc) return fail(PDMPC_ERR_HIP, std::string("priority kernel launch failed: ") + hipGetErrorString((hipError_t)lrc));
+    int64_t K = 0;
+    HIPCHK(hipMemcpyAsync(&K, P.off.p + n_tiles, sizeof K, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(sync_stream(h));
+    *n_out = K;
+    if (K > max_out) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "pdmpc_unique_priorities: %lld unique prioritizations, max_out is %lld", (long long)K, (long long)max_out);
+        return fail(PDMPC_ERR_CAPACITY, buf);
+    }
+    if (P.mask.ensure((size_t)K) || P.order.ensure((size_t)K * n)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the output of pdmpc_unique_priorities");
+    lrc = pdmpc_launch_priority_write(&A, n_tiles, P.off.p, K, P.mask.p, (void*)h->stream);
+    if (!lrc) lrc = pdmpc_launch_priority_order(&A, P.mask.p, K, P.order.p, (void*)h->stream);
+    if (lrc) return fail(PDMPC_ERR_HIP, std::string("priority kernel launch failed: ") + hipGetErrorString((hipError_t)lrc));
+    HIPCHK(hipMemcpyAsync(masks, P.mask.p, (size_t)K * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(priorities, P.order.p, (size_t)K * n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(sync_stream(h));
+    return PDMPC_OK;
+}
+
+// ---- the reachable-set coupler on the device (reachable_kernel.hip)
+namespace {
+// ReachState::ws and its pinned staging for n vehicles (carved the same way at upload, for max_vehicles, and per call): the inputs are
+// the block's first in_bytes, the coupler's output its last
+struct ReachLayout {
+    size_t in, trim, in_bytes, hull_x, hull_y, box, hull_n, total;
+    PairOut out;
+};
+ReachLayout reach_layout(int n, int cols) {
+    Carver c;
+    ReachLayout L;
+    L.in = c.take<double>((size_t)4 * n);
+    L.trim = c.take<int32_t>((size_t)n);
+    L.in_bytes = c.end8();
+    L.hull_x = c.take<double>((size_t)n * cols);
+    L.hull_y = c.take<double>((size_t)n * cols);
+    L.box = c.take<double>((size_t)4 * n);
+    L.hull_n = c.take<int32_t>((size_t)n);
+    L.out = carve_pair_out(c, n);
+    L.total = c.at;
+    return L;
+}
+}  // namespace
+
+int pdmpc_upload_reachable_sets(pdmpc_handle* h, int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* sets) {
+    if (!h || !sets || !sets->offset || n_trims < 1 || Hp < 1) return fail(PDMPC_ERR_INVALID, "pdmpc_upload_reachable_sets: bad argument");
+    if (Hp != h->cfg.Hp) return fail(PDMPC_ERR_INVALID, "pdmpc_upload_reachable_sets: Hp differs from the handle's config.Hp");
+    if (sets->n_polygons != n_trims * Hp) return fail(PDMPC_ERR_INVALID, "pdmpc_upload_reachable_sets: expected n_trims * Hp polygons");
+    int cols = 1;
+    for (int p = 0; p < sets->n_polygons; ++p) {
+        const int m = sets->offset[p + 1] - sets->offset[p];
+        if (m < 1) return fail(PDMPC_ERR_INVALID, "pdmpc_upload_reachable_sets: empty polygon");
+        if (m > PDMPC_REACHABLE_MAX_COLS) return fail(PDMPC_ERR_CAPACITY, "pdmpc_upload_reachable_sets: a hull has more than PDMPC_REACHABLE_MAX_COLS vertices");
+        cols = std::max(cols, m);
+    }
+    if (!sets->x || !sets->y) return fail(PDMPC_ERR_INVALID, "pdmpc_upload_reachable_sets: null coordinates");
+    // only step Hp is coupled on (ReachableSetCoupler.m:9-12: reachable_sets(:, end))
+    std::vector<int32_t> off((size_t)n_trims + 1, 0);
+    for (int t = 0; t < n_trims; ++t) {
+        const int p = t * Hp + Hp - 1;
+        off[t + 1] = off[t] + (sets->offset[p + 1] - sets->offset[p]);
+    }
+    const int tot = off[n_trims];
+    std::vector<double> xy((size_t)2 * tot);
+    for (int t = 0; t < n_trims; ++t) {
+        const int p = t * Hp + Hp - 1, a = sets->offset[p], m = sets->offset[p + 1] - a;
+        std::memcpy(xy.data() + off[t], sets->x + a, (size_t)m * sizeof(double));
+        std::memcpy(xy.data() + tot + off[t], sets->y + a, (size_t)m * sizeof(double));
+    }
+    ON_DEVICE(h->cfg.device);
+    ReachState& R = h->reach;
+    R.valid = false;
+    const ReachLayout L = reach_layout(h->max_vehicles, cols);
+    if (R.local.ensure_exact(xy.size()) || R.off.ensure_exact(off.size()) || R.ws.ensure_exact(L.total) || R.h_in.ensure(L.in_bytes) ||
+        R.h_out.ensure(L.total - L.out.adj))
+        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the reachable-set coupler");
+    HIPCHK(hipMemcpy(R.local.p, xy.data(), xy.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(R.off.p, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    // ... and every step's hulls for the lanelet bounding (pdmpc_bound_reachable_sets)
+    h->bound.valid = false;
+    const int all_tot = sets->offset[sets->n_polygons] - sets->offset[0];
+    std::vector<double> all_xy((size_t)2 * all_tot);
+    std::vector<int32_t> all_off((size_t)sets->n_polygons + 1);
+    for (int p = 0; p <= sets->n_polygons; ++p) all_off[p] = sets->offset[p] - sets->offset[0];
+    std::memcpy(all_xy.data(), sets->x + sets->offset[0], (size_t)all_tot * sizeof(double));
+    std::memcpy(all_xy.data() + all_tot, sets->y + sets->offset[0], (size_t)all_tot * sizeof(double));
+    if (R.all.ensure_exact(all_xy.size()) || R.all_off.ensure_exact(all_off.size())) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the reachable-set table");
+    HIPCHK(hipMemcpy(R.all.p, all_xy.data(), all_xy.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(R.all_off.p, all_off.data(), all_off.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    R.all_tot = all_tot;
+    R.off_host = off;
+    R.trims = n_trims;
+    R.Hp = Hp;
+    R.cols = cols;
+    R.valid = true;
+    return PDMPC_OK;
+}
+
+int pdmpc_reachable_set_coupling(pdmpc_handle* h, int32_t n, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw, const int32_t* trim,
+                                 uint8_t* adjacency, double* area) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    ReachState& R = h->reach;
+    if (!R.valid) return fail(PDMPC_ERR_INVALID, "pdmpc_reachable_set_coupling before pdmpc_upload_reachable_sets");
+    if (n < 0 || !adjacency || (n > 0 && (!x || !y || !cos_yaw || !sin_yaw || !trim))) return fail(PDMPC_ERR_INVALID, "pdmpc_reachable_set_coupling: bad argument");
+    if (n > h->max_vehicles) return fail(PDMPC_ERR_CAPACITY, "pdmpc_reachable_set_coupling: more vehicles than config.max_vehicles");
+    if (n == 0) return PDMPC_OK;
+    for (int v = 0; v < n; ++v)
+        if (trim[v] < 1 || trim[v] > R.trims) return fail(PDMPC_ERR_INVALID, "pdmpc_reachable_set_coupling: trim out of range");
+    ON_DEVICE(h->cfg.device);
+    const ReachLayout L = reach_layout(n, R.cols);
+    unsigned char *hin = R.h_in.p, *ws = R.ws.p;
+    stage_poses((double*)(hin + L.in), (size_t)n, x, y, cos_yaw, sin_yaw, (int32_t*)(hin + L.trim), trim);
+    ReachArgs A;
+    A.n = n;
+    A.max_cols = R.cols;
+    A.local_x = R.local.p;
+    A.local_y = R.local.p + R.off_host[R.trims];
+    A.local_off = R.off.p;
+    A.in = (const double*)(ws + L.in);
+    A.trim = (const int32_t*)(ws + L.trim);
+    A.hull_x = (double*)(ws + L.hull_x);
+    A.hull_y = (double*)(ws + L.hull_y);
+    A.hull_n = (int32_t*)(ws + L.hull_n);
+    A.box = (double*)(ws + L.box);
+    A.adjacency = (uint8_t*)(ws + L.out.adj);
+    A.area = (double*)(ws + L.out.area);
+    HIPCHK(hipMemcpyAsync(ws, hin, L.in_bytes, hipMemcpyHostToDevice, h->stream));
+    if (const int rc = timed_launch(h, R.coupling, pdmpc_launch_reachable_coupling, A, "reachable-set coupling")) return rc;
+    return fetch_pair_out(h, R.coupling, ws, R.h_out.p, L.out, n, adjacency, area);
+}
+
+int pdmpc_reachable_set_coupling_kernel_ms(pdmpc_handle* h, double* ms) {
+    if (!h || !ms) return fail(PDMPC_ERR_INVALID, "null argument");
+    *ms = (double)h->reach.coupling.ms;
+    return PDMPC_OK;
+}
+
+// ---- lanelet bounding and the coupler on the bounded sets (bounded_kernel.hip)
+namespace {
+// BoundState::in and its pinned staging (the lanelet polygons: x of all n_lan vertices, then y), and BoundState::out
+struct BoundLayout {
+    size_t in, trim, lan_off, lan_xy, in_bytes, out_bytes;
+    PairOut out;
+};
+BoundLayout bound_layout(int n, int n_lan) {
+    Carver c;
+    BoundLayout L;
+    L.in = c.take<double>((size_t)4 * n);
+    L.trim = c.take<int32_t>((size_t)n);
+    L.lan_off = c.take<int32_t>((size_t)n + 1);
+    L.lan_xy = c.take<double>((size_t)2 * n_lan);
+    L.in_bytes = c.at;
+    Carver o;
+    L.out = carve_pair_out(o, n);
+    L.out_bytes = o.at;
+    return L;
+}
+BoundArgs bound_args(pdmpc_handle* h, int n, int S, int n_lan) {
+    const ReachState& R = h->reach;
+    BoundState& B = h->bound;
+    const BoundLayout L = bound_layout(n, n_lan);
+    BoundArgs A;
+    A.n = n;
+    A.S = S;
+    A.Hp = R.Hp;
+    A.all_steps = S == R.Hp && S > 1 ? 1 : 0;
+    A.local_x = R.all.p;
+    A.local_y = R.all.p + R.all_tot;
+    A.local_off = R.all_off.p;
+    A.in = (const double*)(B.in.p + L.in);
+    A.trim = (const int32_t*)(B.in.p + L.trim);
+    A.lan_off = (const int32_t*)(B.in.p + L.lan_off);
+    A.lan_x = (const double*)(B.in.p + L.lan_xy);
+    A.lan_y = A.lan_x + n_lan;
+    const size_t slots = (size_t)n * S * PDMPC_BOUND_SLOT;
+    A.set_x = B.sets.p;
+    A.set_y = B.sets.p + slots;
+    A.set_n = B.set_n.p;
+    A.set_flags = B.flags.p;
+    A.box = B.box.p;
+    A.adjacency = B.out.p + L.out.adj;
+    A.area = (double*)(B.out.p + L.out.area);
+    A.pairs = B.pairs.p;
+    A.n_pairs = B.pairs.p + (n > 1 ? (size_t)n * (n - 1) / 2 : 0);
+    return A;
+}
+}  // namespace
+
+int pdmpc_bound_reachable_sets(pdmpc_handle* h, int32_t n, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw, const int32_t* trim,
+                               const pdmpc_polygon_set* lan, int32_t all_steps, int32_t capacity, int32_t* offset, double* out_x, double* out_y, uint8_t* flags) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    if (!h->reach.valid) return fail(PDMPC_ERR_INVALID, "pdmpc_bound_reachable_sets before pdmpc_upload_reachable_sets");
+    if (n < 0 || !offset || !lan || lan->n_polygons != n || (n > 0 && (!x || !y || !cos_yaw || !sin_yaw || !trim || !lan->offset)))
+        return fail(PDMPC_ERR_INVALID, "pdmpc_bound_reachable_sets: bad argument");
+    if (n > h->max_vehicles) return fail(PDMPC_ERR_CAPACITY, "pdmpc_bound_reachable_sets: more vehicles than config.max_vehicles");
+    BoundState& B = h->bound;
+    const int Hp = h->reach.Hp, S = all_steps ? Hp : 1;
+    B.valid = false;
+    offset[0] = 0;
+    if (n == 0) {
+        B.n = 0;
+        B.S = S;
+        B.valid = true;
+        return PDMPC_OK;
+    }
+    int n_lan = 0;
+    for (int v = 0; v < n; ++v) {
+        if (trim[v] < 1 || trim[v] > h->reach.trims) return fail(PDMPC_ERR_INVALID, "pdmpc_bound_reachable_sets: trim out of range");
+        const int nl = lan->offset[v + 1] - lan->offset[v];
+        if (nl < 0) return fail(PDMPC_ERR_INVALID, "pdmpc_bound_reachable_sets: bad lanelet offsets");
+        if (nl > PDMPC_LANELET_POLY_MAX_COLS) return fail(PDMPC_ERR_CAPACITY, "pdmpc_bound_reachable_sets: a lanelet polygon has more than PDMPC_LANELET_POLY_MAX_COLS vertices");
+        if (nl && (!lan->x || !lan->y)) return fail(PDMPC_ERR_INVALID, "pdmpc_bound_reachable_sets: null lanelet coordinates");
+        n_lan += nl;
+    }
+    ON_DEVICE(h->cfg.device);
+    const BoundLayout L = bound_layout(n, n_lan);
+    const size_t sets = (size_t)n * S, max_pairs = (size_t)n * (n - 1) / 2;
+    // (the pinned output block serves this call's vertex counts and flags and the coupler's output)
+    if (B.in.ensure(L.in_bytes) || B.sets.ensure(2 * sets * PDMPC_BOUND_SLOT) || B.set_n.ensure(sets) || B.flags.ensure(sets) || B.box.ensure((size_t)4 * n) ||
+        B.out.ensure(L.out_bytes) || B.pairs.ensure(max_pairs + 1) || B.h_in.ensure(L.in_bytes) || B.h_out.ensure(L.out_bytes + sets * (sizeof(int32_t) + 1)))
+        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the lanelet bounding");
+    // inputs: poses, 0-based trims, the normalized lanelet polygons (pdmpc_lanelet_polygon_normalize, as the host twin)
+    unsigned char* hin = B.h_in.p;
+    stage_poses((double*)(hin + L.in), (size_t)n, x, y, cos_yaw, sin_yaw, (int32_t*)(hin + L.trim), trim);
+    int32_t* hoff = (int32_t*)(hin + L.lan_off);
+    double* hlx = (double*)(hin + L.lan_xy);
+    double* hly = hlx + n_lan;
+    hoff[0] = 0;
+    for (int v = 0; v < n; ++v) {
+        const int a = lan->offset[v], nl = lan->offset[v + 1] - a;
+        const int m = nl ? pdmpc_lanelet_polygon_normalize(lan->x + a, lan->y + a, nl, hlx + hoff[v], hly + hoff[v]) : 0;
+        hoff[v + 1] = hoff[v] + m;
+    }
+    const int n_norm = hoff[n];
+    if (n_norm != n_lan) {  // (duplicates dropped: x and y of the normalized polygons are contiguous again)
+        std::memmove(hlx + n_norm, hly, (size_t)n_norm * sizeof(double));
+    }
+    HIPCHK(hipMemcpyAsync(B.in.p, hin, bound_layout(n, n_norm).in_bytes, hipMemcpyHostToDevice, h->stream));
+    const BoundArgs A = bound_args(h, n, S, n_norm);
+    if (const int rc = timed_launch(h, B.bounding, pdmpc_launch_bound_sets, A, "lanelet bounding")) return rc;
+    int32_t* hn = (int32_t*)B.h_out.p;
+    uint8_t* hf = (uint8_t*)(hn + sets);
+    HIPCHK(hipMemcpyAsync(hn, B.set_n.p, sets * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(hf, B.flags.p, sets, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(sync_stream(h));
+    B.bounding.fold();
+    bool over = false;
+    int maxc = 0;
+    for (size_t o = 0; o < sets; ++o) {
+        if (hf[o] & PDMPC_BOUND_OVERFLOW) over = true;
+        offset[o + 1] = offset[o] + hn[o];
+        maxc = std::max(maxc, (int)hn[o]);
+    }
+    if (over) return fail(PDMPC_ERR_CAPACITY, "pdmpc_bound_reachable_sets: a bounded set has more than PDMPC_BOUNDED_MAX_COLS vertices");
+    B.n = n;
+    B.S = S;
+    B.n_lan = n_norm;
+    B.valid = true;
+    if (!out_x || !out_y || capacity < offset[sets]) return fail(PDMPC_ERR_CAPACITY, "pdmpc_bound_reachable_sets: capacity too small for the bounded sets");
+    // read back the used part of every slot (a pitched copy), then pack
+    if (B.h_xy.ensure(2 * sets * (size_t)maxc)) return fail(PDMPC_ERR_HIP, "hipHostMalloc failed for the bounded sets");
+    double* bx = B.h_xy.p;
+    double* by = bx + sets * (size_t)maxc;
+    const size_t pitch = (size_t)PDMPC_BOUND_SLOT * sizeof(double), width = (size_t)maxc * sizeof(double);
+    HIPCHK(hipMemcpy2DAsync(bx, width, A.set_x, pitch, width, sets, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpy2DAsync(by, width, A.set_y, pitch, width, sets, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(sync_stream(h));
+    for (size_t o = 0; o < sets; ++o) {
+        std::memcpy(out_x + offset[o], bx + o * maxc, (size_t)hn[o] * sizeof(double));
+        std::memcpy(out_y + offset[o], by + o * maxc, (size_t)hn[o] * sizeof(double));
+    }
+    if (flags) std::memcpy(flags, hf, sets);
+    return PDMPC_OK;
+}
+
+int pdmpc_bounded_set_coupling(pdmpc_handle* h, uint8_t* adjacency, double* area) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    if (!adjacency) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling: null adjacency");
+    BoundState& B = h->bound;
+    if (!B.valid) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling without a successful pdmpc_bound_reachable_sets");
+    const int n = B.n;
+    if (n == 0) return PDMPC_OK;
+    ON_DEVICE(h->cfg.device);
+    const BoundArgs A = bound_args(h, n, B.S, B.n_lan);
+    HIPCHK(hipMemsetAsync(A.n_pairs, 0, sizeof(int32_t), h->stream));
+    if (const int rc = timed_launch(h, B.coupling, pdmpc_launch_bounded_coupling, A, "bounded-set coupling")) return rc;
+    return fetch_pair_out(h, B.coupling, B.out.p, B.h_out.p, bound_layout(n, B.n_lan).out, n, adjacency, area);
+}
+
+int pdmpc_bounded_reachable_kernel_ms(pdmpc_handle* h, double* ms2) {
+    if (!h || !ms2) return fail(PDMPC_ERR_INVALID, "null argument");
+    ms2[0] = (double)h->bound.bounding.ms;
+    ms2[1] = (double)h->bound.coupling.ms;
+    return PDMPC_OK;
+}
+
+// ---- future collision assessment on the device (fca_kernel.hip)
+int pdmpc_fca_collisions(pdmpc_handle* h, int32_t n, int32_t Hp, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw,
+                         int32_t n_pairs, const int32_t* pairs, const pdmpc_polygon_set* obstacles, const pdmpc_polygon_set* dynamic_rows, double length,
+                         double width, double offset, int32_t* collisions, int32_t* priorities) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    const char* why = nullptr;
+    if (const int rc = pdmpc_fca_check_args(n, Hp, x, y, cos_yaw, sin_yaw, n_pairs, pairs, obstacles, dynamic_rows, collisions, priorities, &why))
+        return fail(rc, std::string("pdmpc_fca_collisions: ") + why);
+    const int m = n * Hp;
+    const int S = obstacles ? obstacles->n_polygons : 0, D = dynamic_rows ? dynamic_rows->n_polygons : 0, R = D / Hp;
+    const int s0 = S ? obstacles->offset[0] : 0, Ns = S ? obstacles->offset[S] - s0 : 0;
+    const int d0 = D ? dynamic_rows->offset[0] : 0, Nd = D ? dynamic_rows->offset[D] - d0 : 0;
+    // FcaState::ws and its pinned staging of the inputs, the block's first in_bytes (static and dynamic polygons: x of all their
+    // vertices, then y; their offsets rebased to 0); footprints and counts are on the device only
+    Carver c;
+    const size_t o_in = c.take<double>((size_t)4 * m);
+    const size_t o_stat = c.take<double>((size_t)2 * Ns);
+    const size_t o_dyn = c.take<double>((size_t)2 * Nd);
+    const size_t o_pairs = c.take<int32_t>((size_t)2 * n_pairs);
+    const size_t o_stat_off = c.take<int32_t>((size_t)S + 1);
+    const size_t o_dyn_off = c.take<int32_t>((size_t)D + 1);
+    const size_t in_bytes = c.end8();
+    const size_t o_fp = c.take<double>((size_t)8 * m);
+    const size_t o_counts = c.take<int32_t>((size_t)n);
+    const size_t total = c.at;
+    ON_DEVICE(h->cfg.device);
+    FcaState& F = h->fca;
+    if (F.ws.ensure(total) || F.h_in.ensure(in_bytes) || F.h_out.ensure((size_t)n)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the collision assessment");
+    unsigned char *hin = F.h_in.p, *ws = F.ws.p;
+    stage_poses((double*)(hin + o_in), (size_t)m, x, y, cos_yaw, sin_yaw);
+    double *hs = (double*)(hin + o_stat), *hdyn = (double*)(hin + o_dyn);
+    if (Ns) {
+        std::memcpy(hs, obstacles->x + s0, (size_t)Ns * sizeof(double));
+        std::memcpy(hs + Ns, obstacles->y + s0, (size_t)Ns * sizeof(double));
+    }
+    if (Nd) {
+        std::memcpy(hdyn, dynamic_rows->x + d0, (size_t)Nd * sizeof(double));
+        std::memcpy(hdyn + Nd, dynamic_rows->y + d0, (size_t)Nd * sizeof(double));
+    }
+    if (n_pairs) std::memcpy(hin + o_pairs, pairs, (size_t)2 * n_pairs * sizeof(int32_t));
+    int32_t* soff = (int32_t*)(hin + o_stat_off);
+    int32_t* doff = (int32_t*)(hin + o_dyn_off);
+    for (int p = 0; p <= S; ++p) soff[p] = S ? obstacles->offset[p] - s0 : 0;
+    for (int p = 0; p <= D; ++p) doff[p] = D ? dynamic_rows->offset[p] - d0 : 0;
+    FcaArgs A;
+    A.n = n;
+    A.Hp = Hp;
+    A.n_pairs = n_pairs;
+    A.n_static = S;
+    A.n_rows = R;
+    A.length = length;
+    A.width = width;
+    A.offset = offset;
+    A.n_pair_items = (int64_t)n_pairs * Hp;
+    A.n_static_items = (int64_t)(n - 1) * Hp * S;
+    A.n_items = A.n_pair_items + A.n_static_items + (int64_t)(n - 1) * Hp * R;
+    A.in = (const double*)(ws + o_in);
+    A.static_x = (const double*)(ws + o_stat);
+    A.static_y = A.static_x + Ns;
+    A.dyn_x = (const double*)(ws + o_dyn);
+    A.dyn_y = A.dyn_x + Nd;
+    A.pairs = (const int32_t*)(ws + o_pairs);
+    A.static_off = (const int32_t*)(ws + o_stat_off);
+    A.dyn_off = (const int32_t*)(ws + o_dyn_off);
+    A.fp = (double*)(ws + o_fp);
+    A.counts = (int32_t*)(ws + o_counts);
+    HIPCHK(hipMemcpyAsync(ws, hin, in_bytes, hipMemcpyHostToDevice, h->stream));
+    if (const int rc = timed_launch(h, F.timed, pdmpc_launch_fca, A, "collision assessment")) return rc;
+    HIPCHK(hipMemcpyAsync(F.h_out.p, ws + o_counts, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(sync_stream(h));
+    F.timed.fold();
+    std::memcpy(collisions, F.h_out.p, (size_t)n * sizeof(int32_t));
+    pdmpc_fca_sort_index(n, collisions, priorities);
+    return PDMPC_OK;
+}
+
+int pdmpc_fca_kernel_ms(pdmpc_handle* h, double* ms) {
+    if (!h || !ms) return fail(PDMPC_ERR_INVALID, "null argument");
+    *ms = (double)h->fca.timed.ms;
+    return PDMPC_OK;
+}
+
+}  // extern "C"

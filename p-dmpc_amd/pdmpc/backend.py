@@ -160,10 +160,7 @@ def unique_priorities_call(adjacency, max_out, handle=None):
         what = "pdmpc_unique_priorities_host"
     if rc == ERR_CAPACITY:
         raise CapacityError("%s: capacity (%d unique prioritizations, max_out %d)" % (what, K.value, cap), K.value)
-    if handle is not None:
-        _check(L, rc, what)
-    elif rc != 0:
-        raise BackendError("%s failed with status %d" % (what, rc))
+    _check(L, rc, what, message=handle is not None)
     k = K.value
     return prio[: k * n].reshape(k, n).T.astype(np.int64), masks[:k].astype(np.int64)
 
@@ -176,14 +173,13 @@ def local_reachable_sets_native(mpa):
     n, Hp = mpa.n_trims, mpa.Hp
     off = np.zeros(n * Hp + 1, dtype=np.int32)
     rc = L.pdmpc_local_reachable_sets(C.byref(s), 0, off.ctypes.data_as(abi.c_int32_p), None, None)
-    if rc not in (0, ERR_CAPACITY):
-        raise BackendError("pdmpc_local_reachable_sets failed with status %d" % rc)
+    if rc != ERR_CAPACITY:
+        _check(L, rc, "pdmpc_local_reachable_sets", message=False)
     tot = int(off[-1])
     x = np.zeros(max(tot, 1))
     y = np.zeros(max(tot, 1))
     rc = L.pdmpc_local_reachable_sets(C.byref(s), tot, off.ctypes.data_as(abi.c_int32_p), x.ctypes.data_as(abi.c_double_p), y.ctypes.data_as(abi.c_double_p))
-    if rc != 0:
-        raise BackendError("pdmpc_local_reachable_sets failed with status %d" % rc)
+    _check(L, rc, "pdmpc_local_reachable_sets", message=False)
     del keep
     return [[np.array([x[off[i * Hp + k] : off[i * Hp + k + 1]], y[off[i * Hp + k] : off[i * Hp + k + 1]]]) for k in range(Hp)] for i in range(n)]
 
@@ -204,6 +200,13 @@ def _coupling_args(x, y, yaw, trim):
     return x, y, c, s, t
 
 
+def _coupling_out(n):
+    """The outputs of a coupler, never empty -> (adjacency, areas, a call that returns them as (n, n) arrays)."""
+    adj = np.zeros(max(n * n, 1), dtype=np.uint8)
+    area = np.zeros(max(n * n, 1), dtype=np.float64)
+    return adj, area, lambda: (adj[: n * n].reshape(n, n), area[: n * n].reshape(n, n))
+
+
 def reachable_set_coupling_call(local_sets, x, y, yaw, trim, handle=None):
     """ReachableSetCoupler.couple natively: on `handle`'s device (pdmpc_reachable_set_coupling; the handle must hold the table, see
     Handle.upload_reachable_sets) or, without one, on the host twin (pdmpc_reachable_set_coupling_host).  trim is 1-based.
@@ -211,8 +214,7 @@ def reachable_set_coupling_call(local_sets, x, y, yaw, trim, handle=None):
     L = load_library()
     x, y, c, s, t = _coupling_args(x, y, yaw, trim)
     n = x.size
-    adj = np.zeros(max(n * n, 1), dtype=np.uint8)
-    area = np.zeros(max(n * n, 1), dtype=np.float64)
+    adj, area, shaped = _coupling_out(n)
     ptrs = [x.ctypes.data_as(abi.c_double_p), y.ctypes.data_as(abi.c_double_p), c.ctypes.data_as(abi.c_double_p), s.ctypes.data_as(abi.c_double_p),
             t.ctypes.data_as(abi.c_int32_p), adj.ctypes.data_as(abi.c_uint8_p), area.ctypes.data_as(abi.c_double_p)]
     if handle is not None:
@@ -221,9 +223,8 @@ def reachable_set_coupling_call(local_sets, x, y, yaw, trim, handle=None):
         ps, keep = pack_local_sets(local_sets)
         rc = L.pdmpc_reachable_set_coupling_host(len(local_sets), len(local_sets[0]), C.byref(ps), n, *ptrs)
         del keep
-        if rc != 0:
-            raise BackendError("pdmpc_reachable_set_coupling_host failed with status %d" % rc)
-    return adj[: n * n].reshape(n, n), area[: n * n].reshape(n, n)
+        _check(L, rc, "pdmpc_reachable_set_coupling_host", message=False)
+    return shaped()
 
 
 def fca_pairs(adjacency):
@@ -272,9 +273,7 @@ def fca_collisions_host(reference_points, pairs, length, width, offset, obstacle
     if handle is not None:
         _check(L, L.pdmpc_fca_collisions(handle.h, *args), "pdmpc_fca_collisions")
     else:
-        rc = L.pdmpc_fca_collisions_host(*args)
-        if rc != 0:
-            raise BackendError("pdmpc_fca_collisions_host failed with status %d" % rc)
+        _check(L, L.pdmpc_fca_collisions_host(*args), "pdmpc_fca_collisions_host", message=False)
     del keep
     return out
 
@@ -306,15 +305,14 @@ def bound_reachable_sets_call(local_sets, x, y, yaw, trim, lanelet_polys, all_st
     else:
         fn = lambda *tail: L.pdmpc_bound_reachable_sets(handle.h, n, *head, *tail)  # noqa: E731
     rc = fn(0, off.ctypes.data_as(abi.c_int32_p), None, None, None)
-    if rc not in (0, ERR_CAPACITY) or (rc == ERR_CAPACITY and n and int(off[-1]) == 0):
-        raise BackendError("pdmpc_bound_reachable_sets failed with status %d: %s" % (rc, L.pdmpc_last_error().decode()))
+    if rc != ERR_CAPACITY or (n and int(off[-1]) == 0):
+        _check(L, rc, "pdmpc_bound_reachable_sets")
     tot = int(off[-1])
     bx = np.zeros(max(tot, 1))
     by = np.zeros(max(tot, 1))
     rc = fn(tot, off.ctypes.data_as(abi.c_int32_p), bx.ctypes.data_as(abi.c_double_p), by.ctypes.data_as(abi.c_double_p), flags.ctypes.data_as(abi.c_uint8_p))
     del lkeep
-    if rc != 0:
-        raise BackendError("pdmpc_bound_reachable_sets failed with status %d: %s" % (rc, L.pdmpc_last_error().decode()))
+    _check(L, rc, "pdmpc_bound_reachable_sets")
     sets = [[np.array([bx[off[v * S + q] : off[v * S + q + 1]], by[off[v * S + q] : off[v * S + q + 1]]]) for q in range(S)] for v in range(n)]
     return sets, flags[: n * S].reshape(n, S)
 
@@ -325,13 +323,11 @@ def polygon_set_coupling_call(sets):
     keep = abi._Keep()
     n = len(sets)
     ps = abi.pack_polygon_set([np.asarray(p, dtype=np.float64) for p in sets], keep)
-    adj = np.zeros(max(n * n, 1), dtype=np.uint8)
-    area = np.zeros(max(n * n, 1), dtype=np.float64)
+    adj, area, shaped = _coupling_out(n)
     rc = L.pdmpc_polygon_set_coupling_host(C.byref(ps), n, adj.ctypes.data_as(abi.c_uint8_p), area.ctypes.data_as(abi.c_double_p))
     del keep
-    if rc != 0:
-        raise BackendError("pdmpc_polygon_set_coupling_host failed with status %d" % rc)
-    return adj[: n * n].reshape(n, n), area[: n * n].reshape(n, n)
+    _check(L, rc, "pdmpc_polygon_set_coupling_host", message=False)
+    return shaped()
 
 
 def load_library(path=None):
@@ -424,10 +420,11 @@ def load_library(path=None):
     return L
 
 
-def _check(L, rc, what):
+def _check(L, rc, what, message=True):
+    """A failing status of `what` -> BackendError, with the library's message (message=False: a host twin, which leaves none)."""
     if rc != 0:
-        msg = L.pdmpc_last_error()
-        raise BackendError("%s failed with status %d: %s" % (what, rc, msg.decode() if msg else ""))
+        msg = ": " + (L.pdmpc_last_error() or b"").decode() if message else ""
+        raise BackendError("%s failed with status %d%s" % (what, rc, msg))
 
 
 SHARD_AUTO, SHARD_COMPONENTS, SHARD_LEVELS = 0, 1, 2
