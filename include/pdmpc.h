@@ -168,7 +168,7 @@ typedef struct {
  *     PDMPC_TUNING="key=value,key=value,..."
  * keys: round0 round ramp ready share_min tile mid_min mid_fill (rounds and lists), tentative fast_arrival speculate helpers
  * helpers_oversub helpers_first seat_nodes waves compact (A/B switches; compact takes -1, 0 or 1), force_tie reverse_dispatch
- * spin_limit (testing), debug_tail debug_lds debug_host debug_progress (diagnostics); csrc/api.cpp: struct Tuning documents each.
+ * spin_limit (testing), debug_tail debug_lds debug_host debug_progress (diagnostics); csrc/handle.hpp: struct Tuning documents each.
  * No setting changes a result; an unknown key fails pdmpc_create. */
 
 /* ---- life cycle (replaces GraphSearch() construction in OptimizerInterface.get_optimizer, :26-27,

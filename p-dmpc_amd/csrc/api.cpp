@@ -1,8 +1,7 @@
 // api.cpp — host side of libpdmpc_hip.so: the C ABI declared in include/pdmpc.h.
 //
-// Responsibilities: own all device memory of a handle, flatten the caller's IterationData slices into
-// the pointer-free HBM blob of pdmpc_device.h (this is where vectorize_all_obstacles.m:36-62's
-// "[polygon, NaN]" concatenation happens for literal obstacles), size the LDS regions, launch the search
+// Responsibilities: own all device memory of a handle, hand the caller's IterationData slices to the packer
+// (pack.cpp: the pointer-free HBM blob of pdmpc_device.h), size the LDS regions, launch the search
 // kernel on the handle's stream and time it with HIP events, copy results back.
 // There is no CPU implementation of the search in this library: without a gfx950 device every planning
 // entry point fails with PDMPC_ERR_NO_DEVICE.
@@ -94,7 +93,6 @@ namespace {
 
 // The dynamic LDS size of a kernel is an attribute of the function ON THE DEVICE, not of a handle (hipFuncSetAttribute sets a
 // maximum): the largest size set so far is kept per device and kernel (0 bulk, 1 bulk wide, 2 bulk SAT, 3 bulk compact), shared by every handle.
-const size_t kMaxLaunchEvents = 4096;  // event pairs a handle keeps before it folds their times (begin_timed_launch)
 std::mutex g_lds_mutex;
 uint32_t g_lds_high_water[64][4];
 // The automaton's tables, the front of every LDS layout from `off` on: successor masks, maneuver index, poses, then the maneuver
@@ -116,8 +114,7 @@ uint32_t layout_mpa(const pdmpc_handle* h, uint32_t off, bool areas, Layout& L) 
 // thread), d_traveled table, the LDS part of the open set (PDMPC_BK_PER entries per thread), the ready list with its collision
 // flags, the histogram / goal list / expansion lists, 2 KB of small tables, the areas of the published path, validity bytes, then
 // as many node records as fit.
-bool layout_bulk(pdmpc_handle* h, size_t budget, int n_waves, int areas, int soup_cap, LdsLayout& L, uint32_t& nv, uint32_t& nl, uint32_t ready_cap, bool compact) {
-    (void)n_waves;
+bool layout_bulk(const pdmpc_handle* h, size_t budget, int n_waves, int areas, int soup_cap, LdsLayout& L, uint32_t& nv, uint32_t& nl, uint32_t ready_cap, bool compact) {
     const uint32_t lk_waves = compact ? PDMPC_LK_COMPACT_WAVES : PDMPC_MAX_WAVES, lk_ready = compact ? PDMPC_LK_COMPACT_READY_CAP : 2048u, lk_per = compact ? PDMPC_LK_COMPACT_BK_PER : PDMPC_BK_PER;
     if (ready_cap > lk_ready || (uint32_t)n_waves > lk_waves) return false;
     // the regions of fixed size at the kernel's compile-time offsets (pdmpc_device.h: PDMPC_LK_*) ...
@@ -140,26 +137,17 @@ bool layout_bulk(pdmpc_handle* h, size_t budget, int n_waves, int areas, int sou
     return L.total <= budget;
 }
 
-// the layout the next launch_range goes out with
-int use_layout(pdmpc_handle* h, const LdsLayout& L, int n_waves, uint32_t nl, uint32_t nv, int areas_in_lds) {
-    h->lds = L;
-    h->n_waves = n_waves;
-    h->NL = (int)nl;
-    h->NV = (int)nv;
-    h->areas_in_lds = areas_in_lds;
-    return PDMPC_OK;
+// helper workgroups serve the launches that leave CUs idle (launch_policy)
+bool bulk_has_helpers(const Tuning& T, int n_cu, int n_launch) {
+    if (!T.speculate || T.helpers == 0) return false;
+    if (n_launch > n_cu) return T.helpers_oversub != 0;  // (the tail of a launch with more searches than CUs)
+    return n_launch <= n_cu - 2;
 }
 
-// helper workgroups serve the launches that leave CUs idle (launch_range)
-bool bulk_has_helpers(const pdmpc_handle* h, int n_launch) {
-    if (!h->tune.speculate || h->tune.helpers == 0) return false;
-    if (n_launch > h->n_cu) return h->tune.helpers_oversub != 0;  // (the tail of a launch with more searches than CUs)
-    return n_launch <= h->n_cu - 2;
-}
-
-int compute_lds_bulk(pdmpc_handle* h, int n_launch, int soup_cap) {
+int compute_lds_bulk(const pdmpc_handle* h, int n_launch, int soup_cap, LaunchLayout& out) {
+    const Tuning& T = h->tune;
     // large rounds pay where helper workgroups share them; without helpers the LDS is better spent on node records
-    h->bk_ready_launch = bulk_has_helpers(h, n_launch) ? h->tune.ready : std::max(256, h->tune.ready / 2);
+    const int ready_want = bulk_has_helpers(T, h->n_cu, n_launch) ? T.ready : std::max(256, T.ready / 2);
     // Sixteen wavefronts where the kernel's registers allow four per SIMD (measured against twelve: C2 +1.5 %, C3 +1.3 %, C4 +7.5 %;
     // C5, five light searches per CU one after the other, -1.7 %: it keeps twelve and the LDS-resident nodes that go with them)
     const int cap = h->cfg.checker == PDMPC_CHECK_SAT ? PDMPC_MAX_WAVES_SAT : PDMPC_MAX_WAVES;
@@ -168,32 +156,29 @@ int compute_lds_bulk(pdmpc_handle* h, int n_launch, int soup_cap) {
     // bound by the latency of its own passes; two side by side fill each other's gaps (C5 557 -> 710 steps/s).  NOT for launches whose
     // step is one heavy search (C4, 512 searches: 94.6 -> 31 steps/s with it — half the lanes, a quarter of the near list, rounds of
     // 240 entries that are never shared).  InterX with one mask word only; falls back to the full layout if the soup does not fit.
-    const bool want_compact = h->cfg.checker == PDMPC_CHECK_INTERX && h->n_words == 1 && (h->tune.compact > 0 || (h->tune.compact < 0 && n_launch > 2 * h->n_cu));
-    h->compact_layout = false;
+    const bool want_compact = h->cfg.checker == PDMPC_CHECK_INTERX && h->n_words == 1 && (T.compact > 0 || (T.compact < 0 && n_launch > 2 * h->n_cu));
+    uint32_t nv = 0, nl = 0;
     if (want_compact) {
         LdsLayout L{};
-        uint32_t nv = 0, nl = 0;
-        const int waves = h->tune.waves >= 0 ? std::min(h->tune.waves, PDMPC_LK_COMPACT_WAVES) : PDMPC_LK_COMPACT_WAVES;
-        const int ready = std::min(std::min(h->bk_ready_launch, 3 * PDMPC_WAVE * waves), (int)PDMPC_LK_COMPACT_READY_CAP);
+        const int waves = T.waves >= 0 ? std::min(T.waves, PDMPC_LK_COMPACT_WAVES) : PDMPC_LK_COMPACT_WAVES;
+        const int ready = std::min(std::min(ready_want, 3 * PDMPC_WAVE * waves), (int)PDMPC_LK_COMPACT_READY_CAP);
         if (layout_bulk(h, kLdsMax / 2, waves, 0, soup_cap, L, nv, nl, (uint32_t)ready, true)) {
-            if (h->tune.debug_lds)
+            if (T.debug_lds)
                 fprintf(stderr, "pdmpc LDS layout (compact): launch %d waves %d near %u ready %d nv %u nl %u total %u\n", n_launch, waves, PDMPC_LK_COMPACT_BK_PER * (uint32_t)waves * PDMPC_WAVE, ready, nv, nl, L.total);
-            h->bk_ready_launch = ready;
-            h->compact_layout = true;
-            return use_layout(h, L, waves, nl, nv, 0);
+            out = {L, waves, (int)nl, (int)nv, 0, ready, true};
+            return PDMPC_OK;
         }
     }
-    const int waves = h->tune.waves >= 0 ? std::min(h->tune.waves, cap) : (n_launch > 2 * h->n_cu ? std::min(12, cap) : cap);
+    const int waves = T.waves >= 0 ? std::min(T.waves, cap) : (n_launch > 2 * h->n_cu ? std::min(12, cap) : cap);
     for (int areas = 1; areas >= 0; --areas) {  // (the maneuver areas fall back to L2 when the soup leaves no room)
         LdsLayout L{};
-        uint32_t nv = 0, nl = 0;
-        const int ready = std::min(h->bk_ready_launch, 3 * PDMPC_WAVE * waves);
+        const int ready = std::min(ready_want, 3 * PDMPC_WAVE * waves);
         if (!layout_bulk(h, kLdsMax, waves, areas, soup_cap, L, nv, nl, (uint32_t)ready, false)) continue;
-        if (h->tune.debug_lds)
+        if (T.debug_lds)
             fprintf(stderr, "pdmpc LDS layout: launch %d waves %d areas %d near %u ready %d nv %u nl %u total %u\n", n_launch, waves, areas, PDMPC_BK_PER * (uint32_t)waves * PDMPC_WAVE, ready,
                     nv, nl, L.total);
-        h->bk_ready_launch = ready;
-        return use_layout(h, L, waves, nl, nv, areas);
+        out = {L, waves, (int)nl, (int)nv, areas, ready, false};
+        return PDMPC_OK;
     }
     char buf[256];
     snprintf(buf, sizeof buf, "obstacle soup (%d columns) + MPA tables do not fit into %zu B of LDS", soup_cap, kLdsMax);
@@ -201,11 +186,11 @@ int compute_lds_bulk(pdmpc_handle* h, int n_launch, int soup_cap) {
 }
 
 // LDS layout of the sampled optimizer (one wavefront per vehicle): MPA tables, reference, the wave's two shapes, offsets, obstacle
-// soup (with the predecessors' columns pack_common counts into soup_cap), the candidate segments of one edge check, its tree
+// soup (with the predecessors' columns the packer counts into soup_cap), the candidate segments of one edge check, its tree
 // (288 nodes x (16 children + parent + trim) x 2 B; the random generator's state before the tree is set up) and its Hp * 250 random
 // numbers (32 000 B at Hp 16).  80 KB first (two workgroups per CU), then the whole 160 KB (one); the automaton's areas go to L2
 // before a layout takes the larger budget.
-int compute_lds_sampled(pdmpc_handle* h, int soup_cap, int cand_cap) {
+int compute_lds_sampled(const pdmpc_handle* h, int soup_cap, int cand_cap, LaunchLayout& out) {
     static_assert(288u * 16u * 2u >= 624u * 4u, "the tree region holds the generator's state");
     for (int pass = 0; pass < 4; ++pass) {
         const int areas = pass == 0 || pass == 2;
@@ -229,7 +214,10 @@ int compute_lds_sampled(pdmpc_handle* h, int soup_cap, int cand_cap) {
         L.rand = off;
         off += align16((uint32_t)h->cfg.Hp * 250u * 8u);
         L.total = align16(off);
-        if (L.total <= budget) return use_layout(h, L, 1, 0, 0, areas);
+        if (L.total <= budget) {
+            out = {L, 1, 0, 0, areas, h->tune.ready, false};  // (one wavefront, no ready list: the kernel reads none of the rounds' arguments)
+            return PDMPC_OK;
+        }
     }
     return fail(PDMPC_ERR_CAPACITY, "obstacle soup + MPA tables do not fit into the LDS budget of the sampled optimizer");
 }
@@ -265,329 +253,6 @@ int layout_joint(pdmpc_handle* h, int soup_cap, JointLds& L, uint32_t& heap_lds,
     }
     return fail(PDMPC_ERR_CAPACITY, "the MPA tables and a joint problem's obstacle soups do not fit into LDS");
 }
-int check_set(const pdmpc_polygon_set& s, const char* what) {
-    if (s.n_polygons < 0) return fail(PDMPC_ERR_INVALID, std::string(what) + ": negative polygon count");
-    if (s.n_polygons > 0 && (!s.offset || !s.x || !s.y)) return fail(PDMPC_ERR_INVALID, std::string(what) + ": null pointer");
-    for (int i = 0; i < s.n_polygons; ++i)
-        if (s.offset[i + 1] < s.offset[i]) return fail(PDMPC_ERR_INVALID, std::string(what) + ": offsets not monotone");
-    return PDMPC_OK;
-}
-
-int pack_common(pdmpc_handle* h, int n, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index,
-                const pdmpc_polygon_set* fallback) {
-    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
-    // the weights are this pack's, whether it succeeds or not: a failed pack must not leave them to reorder the next one
-    const std::vector<double> weights = std::move(h->next_weights);
-    h->next_weights.clear();
-    // ... and so are the seeds: a pack that fails leaves no sampled bank behind it
-    const bool sampled = h->seeds_set;
-    const std::vector<uint32_t> seeds = std::move(h->next_seeds);
-    h->next_seeds.clear();
-    h->seeds_set = false;
-    if (!h->has_mpa) return fail(PDMPC_ERR_NO_MPA, "pdmpc_upload_mpa has not been called");
-    if (n < 0 || (n > 0 && !in)) return fail(PDMPC_ERR_INVALID, "bad vehicle array");
-    if (n > h->max_vehicles) return fail(PDMPC_ERR_CAPACITY, "batch larger than config.max_vehicles");
-    const int Hp = h->cfg.Hp;
-    PackedStep& B = h->banks[h->bank];
-    const double qnan = std::numeric_limits<double>::quiet_NaN();
-    // the staging blob is reused: a copy out of it that may still be in flight (no stream synchronisation since it was queued) ends first
-    if (B.staged_serial == h->sync_serial) HIPCHK(sync_stream(h));
-    // The packed batch is written where it is copied from, the bank's pinned blob: [vehicles | predecessor slots | points].  The
-    // points come last — their number is known once they are written — and the blob grows with its contents kept.
-    size_t total_pred = 0;
-    if (pred_offset)
-        for (int vi = 0; vi < n; ++vi) total_pred += (size_t)std::max(0, pred_offset[vi + 1] - pred_offset[vi]);
-    const size_t veh_bytes = ((size_t)std::max(n, 1) * sizeof(DevVehicle) + 15) & ~(size_t)15;
-    const size_t pred_bytes = ((total_pred + 1) * sizeof(int32_t) + 15) & ~(size_t)15;
-    const size_t pts_base = veh_bytes + pred_bytes;
-    B.n_packed = 0;  // (a pack that fails leaves the bank empty: the batch that was in it is being overwritten)
-    B.pack_failed = true;
-    B.sampled = sampled;
-    if (sampled && (int)seeds.size() != n) return fail(PDMPC_ERR_INVALID, "pdmpc_set_step_seeds: the seeds are not one per vehicle of the packed step");
-    B.h_veh = nullptr;
-    B.h_pts = nullptr;
-    B.h_pred = nullptr;
-    if (B.h_blob.ensure_keep(pts_base + 4096, 0)) return fail(PDMPC_ERR_HIP, "hipHostMalloc failed");
-    DevVehicle* veh = (DevVehicle*)B.h_blob.p;
-    int32_t* pred = (int32_t*)(B.h_blob.p + veh_bytes);
-    double* pts = (double*)(B.h_blob.p + pts_base);
-    size_t n_pred_out = 0, n_pts = 0;  // entries of pred / POINTS (two doubles each) written
-    auto put = [&](double x, double y) {
-        pts[2 * n_pts] = x;
-        pts[2 * n_pts + 1] = y;
-        ++n_pts;
-    };
-    auto set_points = [](const pdmpc_polygon_set& s) -> size_t {  // points of a (checked) set + one separator per polygon
-        return s.n_polygons > 0 ? (size_t)(s.offset[s.n_polygons] - s.offset[0]) + (size_t)s.n_polygons : 0;
-    };
-    B.lit_cols.assign((size_t)n, 0);
-    int soup_cap = 0, cand_cap = 0;
-    // Slot order.  A search spins for predecessors of the same launch, so every predecessor must sit in a lower slot than its
-    // successors (launch_range: forward progress of oversubscribed launches).  Callers hand the vehicles over in level order
-    // (kahn.m); a batch that is not is put into level order here -- computation levels by longest path, stable within a level --
-    // and pdmpc_fetch_results hands the records back in the caller's order.
-    B.perm.clear();
-    B.inv.clear();
-    // Priority order (pdmpc_set_step_weights).  Workgroups are handed out in index order, and a launch of more searches than CUs
-    // starts its later workgroups when earlier ones end: in level order a heavy search of a late level starts late — behind finished
-    // searches that hold their CUs while they wait for predecessors (C4: 2.5-4 ms into a 10 ms step).  With an expected work per
-    // vehicle the slots are filled by PRIORITY instead: the largest expected work among a vehicle and its descendants in the coupling
-    // DAG, descending; ties by level, then by the caller's index.  A predecessor's priority is at least its successors' and its level
-    // is lower, so this is a topological order too — every predecessor in a lower slot: the forward-progress argument holds
-    // unchanged — and the records go back in the caller's order as for any batch the library reorders.
-    const bool by_priority = (int)weights.size() == n && n > 1 && pred_offset != nullptr;
-    if (pred_offset) {
-        bool ordered = true;
-        for (int i = 0; i < n && ordered; ++i)
-            for (int q = pred_offset[i]; q < pred_offset[i + 1]; ++q) {
-                const int ps = pred_index[q];
-                if (ps < 0 || ps >= h->max_vehicles) return fail(PDMPC_ERR_INVALID, "predecessor slot out of range");
-                if (ps < n && ps >= i) ordered = false;
-            }
-        if (!ordered || by_priority) {
-            std::vector<int32_t> level(n, 0), indeg(n, 0), succ_off(n + 1, 0), succ, queue;
-            for (int i = 0; i < n; ++i)
-                for (int q = pred_offset[i]; q < pred_offset[i + 1]; ++q)
-                    if (pred_index[q] >= 0 && pred_index[q] < n) {
-                        if (pred_index[q] == i) return fail(PDMPC_ERR_INVALID, "a vehicle is its own predecessor");
-                        succ_off[pred_index[q] + 1] += 1;
-                        indeg[i] += 1;
-                    }
-            for (int i = 0; i < n; ++i) succ_off[i + 1] += succ_off[i];
-            succ.resize((size_t)succ_off[n]);
-            std::vector<int32_t> fill(succ_off.begin(), succ_off.end() - 1);
-            for (int i = 0; i < n; ++i)
-                for (int q = pred_offset[i]; q < pred_offset[i + 1]; ++q)
-                    if (pred_index[q] >= 0 && pred_index[q] < n) succ[(size_t)fill[pred_index[q]]++] = i;
-            for (int i = 0; i < n; ++i)
-                if (indeg[i] == 0) {
-                    level[i] = 1;
-                    queue.push_back(i);
-                }
-            for (size_t qi = 0; qi < queue.size(); ++qi) {
-                const int u = queue[qi];
-                for (int q = succ_off[u]; q < succ_off[u + 1]; ++q) {
-                    const int w = succ[(size_t)q];
-                    level[w] = std::max(level[w], level[u] + 1);
-                    if (--indeg[w] == 0) queue.push_back(w);
-                }
-            }
-            if ((int)queue.size() != n) return fail(PDMPC_ERR_INVALID, "the sequential coupling graph has a cycle");
-            B.perm.resize((size_t)n);
-            for (int i = 0; i < n; ++i) B.perm[(size_t)i] = i;
-            if (by_priority) {
-                std::vector<double> prio((size_t)n);
-                for (int i = 0; i < n; ++i) {
-                    const double w = weights[(size_t)i];
-                    prio[(size_t)i] = (w == w && w > 0) ? w : 0.0;
-                }
-                for (size_t qi = queue.size(); qi-- > 0;) {  // (reverse topological order: a vehicle after all its successors)
-                    const int u = queue[qi];
-                    for (int q = succ_off[u]; q < succ_off[u + 1]; ++q) prio[(size_t)u] = std::max(prio[(size_t)u], prio[(size_t)succ[(size_t)q]]);
-                }
-                std::stable_sort(B.perm.begin(), B.perm.end(), [&](int32_t x, int32_t y) {
-                    if (prio[(size_t)x] != prio[(size_t)y]) return prio[(size_t)x] > prio[(size_t)y];
-                    return level[x] < level[y];
-                });
-            } else {
-                std::stable_sort(B.perm.begin(), B.perm.end(), [&](int32_t x, int32_t y) { return level[x] < level[y]; });
-            }
-            bool identity = true;
-            for (int i = 0; i < n && identity; ++i) identity = B.perm[(size_t)i] == i;
-            if (identity) {
-                B.perm.clear();  // (the caller's order is the order wanted: raw slots are the caller's vehicles)
-            } else {
-                B.inv.resize((size_t)n);
-                for (int sl = 0; sl < n; ++sl) B.inv[(size_t)B.perm[(size_t)sl]] = sl;
-            }
-        }
-    }
-    const bool permuted = !B.perm.empty();
-    // Vehicles that hand over THE SAME ARRAYS (same pointers, same counts: the prioritization instances of an explorative step share
-    // every input but the predecessor lists, PrioritizedExplorativeController.m:25-91; step_controller.cpp builds one set per distinct
-    // content) share one copy of their soups in the pool: a vehicle seen before takes over the offsets of the first one.
-    // (an open-addressing table over the slots that brought new arrays: a batch of 1 280 slots looks its key up 1 280 times)
-    std::vector<SoupKey>& soup_keys = h->pack_soup_keys;  // key of the q-th distinct vehicle, soup_slot[q] the slot it was packed in
-    std::vector<int32_t>& soup_slot = h->pack_soup_slot;
-    std::vector<int32_t>& soup_table = h->pack_soup_table;  // hash -> q + 1, 0 = empty
-    size_t table_size = 64;
-    while (table_size < (size_t)n * 2) table_size *= 2;
-    soup_keys.clear();
-    soup_slot.clear();
-    soup_table.assign(table_size, 0);
-    auto soup_hash = [](const SoupKey& k) {
-        uint64_t hsh = 1469598103934665603ull;
-        const uint64_t* w = (const uint64_t*)&k;
-        for (size_t q = 0; q < sizeof(SoupKey) / 8; ++q) hsh = (hsh ^ w[q]) * 1099511628211ull;
-        return hsh ^ (hsh >> 29);
-    };
-    static_assert(sizeof(SoupKey) % 8 == 0, "SoupKey is hashed by 64-bit words");
-    for (int slot_i = 0; slot_i < n; ++slot_i) {
-        const int i = slot_i;  // (slot: index into the packed arrays)
-        const int vi = permuted ? B.perm[(size_t)slot_i] : slot_i;  // (the caller's vehicle)
-        const pdmpc_vehicle_in& v = in[vi];
-        if (!v.ref_x || !v.ref_y || !v.v_ref) return fail(PDMPC_ERR_INVALID, "reference trajectory missing");
-        if (v.trim0 < 1 || v.trim0 > h->n_trims) return fail(PDMPC_ERR_INVALID, "trim0 out of range");
-        const bool has_fb = fallback && fallback[vi].n_polygons > 0;
-        // seen before?  (looked up first: a vehicle that hands over arrays that are packed already needs neither their checks nor room)
-        SoupKey key;
-        std::memset(&key, 0, sizeof key);
-        {
-            const pdmpc_polygon_set* fbv = has_fb ? &fallback[vi] : nullptr;
-            const void* ptrs[13] = {v.obstacles.offset, v.obstacles.x, v.obstacles.y, v.dynamic_obstacles.offset, v.dynamic_obstacles.x, v.dynamic_obstacles.y, v.hdv_reachable_sets.offset,
-                                    v.hdv_reachable_sets.x, v.left_x, v.right_x, fbv ? fbv->offset : nullptr, fbv ? fbv->x : nullptr, fbv ? fbv->y : nullptr};
-            for (int q = 0; q < 13; ++q) key.p[q] = ptrs[q];
-            key.c[0] = v.obstacles.n_polygons;
-            key.c[1] = v.dynamic_obstacles.n_polygons;
-            key.c[2] = v.hdv_reachable_sets.n_polygons;
-            key.c[3] = v.n_left;
-            key.c[4] = v.n_right;
-            key.c[5] = fbv ? fbv->n_polygons : 0;
-        }
-        size_t at_table = (size_t)soup_hash(key) & (table_size - 1);
-        int seen_slot = -1;
-        while (soup_table[at_table] != 0) {
-            const int q = soup_table[at_table] - 1;
-            if (std::memcmp(&soup_keys[(size_t)q], &key, sizeof key) == 0) {
-                seen_slot = soup_slot[(size_t)q];
-                break;
-            }
-            at_table = (at_table + 1) & (table_size - 1);
-        }
-        const pdmpc_vehicle_in* first_in = seen_slot >= 0 ? &in[permuted ? B.perm[(size_t)seen_slot] : seen_slot] : nullptr;
-        const bool shared = first_in && v.left_y == first_in->left_y && v.right_y == first_in->right_y && v.hdv_reachable_sets.y == first_in->hdv_reachable_sets.y;
-        if (!shared) {
-            int rc;
-            if ((rc = check_set(v.obstacles, "obstacles"))) return rc;
-            if ((rc = check_set(v.dynamic_obstacles, "dynamic_obstacles"))) return rc;
-            if ((rc = check_set(v.hdv_reachable_sets, "hdv_reachable_sets"))) return rc;
-            if (v.dynamic_obstacles.n_polygons % Hp) return fail(PDMPC_ERR_INVALID, "dynamic_obstacles must hold n_d * Hp polygons");
-            if (v.hdv_reachable_sets.n_polygons % Hp) return fail(PDMPC_ERR_INVALID, "hdv_reachable_sets must hold n_h * Hp polygons");
-            if (v.n_left < 0 || v.n_right < 0 || v.n_left == 1 || v.n_right == 1)
-                return fail(PDMPC_ERR_INVALID, "lanelet boundary needs 0 or >= 2 points per side");
-            if (has_fb) {
-                if (fallback[vi].n_polygons != Hp) return fail(PDMPC_ERR_INVALID, "fallback_shapes must hold Hp polygons per vehicle");
-                if ((rc = check_set(fallback[vi], "fallback_shapes"))) return rc;
-            }
-            // room for everything this vehicle can add (+ the batch's trailing pad)
-            const size_t most = (size_t)Hp * set_points(v.obstacles) + set_points(v.dynamic_obstacles) + set_points(v.hdv_reachable_sets) + (size_t)v.n_left + (size_t)v.n_right + 2 +
-                                (has_fb ? set_points(fallback[vi]) : 0) + 2;
-            if (B.h_blob.ensure_keep(pts_base + (n_pts + most) * 16, pts_base + n_pts * 16)) return fail(PDMPC_ERR_HIP, "hipHostMalloc failed");
-            veh = (DevVehicle*)B.h_blob.p;
-            pred = (int32_t*)(B.h_blob.p + veh_bytes);
-            pts = (double*)(B.h_blob.p + pts_base);
-        }
-        DevVehicle& d = veh[(size_t)i];
-        std::memset(&d, 0, sizeof d);
-        d.x0 = v.x0;
-        d.y0 = v.y0;
-        d.yaw0 = v.yaw0;
-        d.trim0 = v.trim0;
-        d.seed = sampled ? seeds[(size_t)vi] : 0u;
-        for (int k = 0; k < Hp; ++k) {
-            d.ref_x[k] = v.ref_x[k];
-            d.ref_y[k] = v.ref_y[k];
-            d.v_ref[k] = v.v_ref[k];
-        }
-        const int n_pred = pred_offset ? pred_offset[vi + 1] - pred_offset[vi] : 0;
-        d.n_pred = n_pred;
-        d.pred_off = (int32_t)n_pred_out;
-        for (int q = 0; q < n_pred; ++q) {
-            const int ps = pred_index[pred_offset[vi] + q];
-            if (ps < 0 || ps >= h->max_vehicles) return fail(PDMPC_ERR_INVALID, "predecessor slot out of range");
-            pred[n_pred_out++] = permuted && ps < n ? B.inv[(size_t)ps] : ps;
-        }
-        if (shared) {
-            const DevVehicle& f = veh[(size_t)seen_slot];  // (validated when it was packed)
-            std::memcpy(d.lit_off, f.lit_off, sizeof d.lit_off);
-            std::memcpy(d.hdv_off, f.hdv_off, sizeof d.hdv_off);
-            std::memcpy(d.fb_off, f.fb_off, sizeof d.fb_off);
-            d.ll_off = f.ll_off;
-            d.ll_len = f.ll_len;
-            B.lit_cols[i] = B.lit_cols[(size_t)seen_slot];
-            const int need = (d.lit_off[Hp] - d.lit_off[0]) + Hp * n_pred * PDMPC_VMAX + (d.hdv_off[Hp] - d.hdv_off[0]) + d.ll_len;
-            soup_cap = std::max(soup_cap, need);
-            for (int k = 0; k < Hp; ++k)
-                cand_cap = std::max(cand_cap, (d.lit_off[k + 1] - d.lit_off[k]) + n_pred * PDMPC_VMAX + (d.hdv_off[k + 1] - d.hdv_off[k]) + d.ll_len);
-            continue;
-        }
-        if (seen_slot < 0) {  // (a key met again with other y arrays keeps its first entry, as the map did)
-            soup_keys.push_back(key);
-            soup_slot.push_back(i);
-            soup_table[at_table] = (int32_t)soup_keys.size();
-        }
-        const int n_dyn = v.dynamic_obstacles.n_polygons / Hp;
-        const int n_hdv = v.hdv_reachable_sets.n_polygons / Hp;
-        auto append_poly = [&](const pdmpc_polygon_set& s, int p, bool sep) {
-            for (int q = s.offset[p]; q < s.offset[p + 1]; ++q) put(s.x[q], s.y[q]);
-            if (sep) put(qnan, qnan);
-        };
-        int need = 0;
-        // vehicle_obstacles{k} = [static..., dynamic(:, k)...], each followed by [NaN; NaN]   vectorize_all_obstacles.m:36-62
-        for (int k = 0; k < Hp; ++k) {
-            d.lit_off[k] = (int32_t)n_pts;
-            for (int p = 0; p < v.obstacles.n_polygons; ++p) append_poly(v.obstacles, p, true);
-            for (int r = 0; r < n_dyn; ++r) append_poly(v.dynamic_obstacles, r * Hp + k, true);
-            need += (int)n_pts - d.lit_off[k] + n_pred * PDMPC_VMAX;
-        }
-        d.lit_off[Hp] = (int32_t)n_pts;
-        B.lit_cols[i] = d.lit_off[Hp] - d.lit_off[0];
-        for (int k = 0; k < Hp; ++k) {
-            d.hdv_off[k] = (int32_t)n_pts;
-            for (int r = 0; r < n_hdv; ++r) append_poly(v.hdv_reachable_sets, r * Hp + k, true);
-        }
-        d.hdv_off[Hp] = (int32_t)n_pts;
-        need += d.hdv_off[Hp] - d.hdv_off[0];
-        // lanelet_boundary = [left, NaN, right, NaN]                                          vectorize_all_obstacles.m:27-30
-        d.ll_off = (int32_t)n_pts;
-        for (int q = 0; q < v.n_left; ++q) put(v.left_x[q], v.left_y[q]);
-        put(qnan, qnan);
-        for (int q = 0; q < v.n_right; ++q) put(v.right_x[q], v.right_y[q]);
-        put(qnan, qnan);
-        d.ll_len = (int32_t)n_pts - d.ll_off;
-        need += d.ll_len;
-        B.lit_cols[i] += d.ll_len;
-        if (has_fb) {
-            for (int k = 0; k < Hp; ++k) {
-                d.fb_off[k] = (int32_t)n_pts;
-                if (fallback[vi].offset[k + 1] - fallback[vi].offset[k] > PDMPC_VMAX)
-                    return fail(PDMPC_ERR_INVALID, "fallback area has more than PDMPC_VMAX columns");
-                append_poly(fallback[vi], k, false);
-            }
-            d.fb_off[Hp] = (int32_t)n_pts;
-        } else {
-            for (int k = 0; k <= Hp; ++k) d.fb_off[k] = -1;
-        }
-        soup_cap = std::max(soup_cap, need);
-        for (int k = 0; k < Hp; ++k)
-            cand_cap = std::max(cand_cap, (d.lit_off[k + 1] - d.lit_off[k]) + n_pred * PDMPC_VMAX + (d.hdv_off[k + 1] - d.hdv_off[k]) + d.ll_len);
-    }
-    // a trailing pad so 16-byte staged copies never run past the allocation (room: the blob's first 4096 bytes of points, or a vehicle's)
-    put(qnan, qnan);
-    pred[n_pred_out++] = 0;
-    B.soup_cap = soup_cap + 2;
-    B.cand_cap = (cand_cap + 4 + 3) & ~3;
-    const size_t pts_bytes = (n_pts * 16 + 15) & ~(size_t)15;
-    const size_t total = pts_base + pts_bytes;
-    if (B.d_blob.ensure(total)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the batch blob");
-    B.h_veh = veh;
-    B.h_pred = pred;
-    B.h_pts = pts;
-    B.d_veh = (DevVehicle*)B.d_blob.p;
-    B.d_pred = (int32_t*)(B.d_blob.p + veh_bytes);
-    B.d_pts = (double*)(B.d_blob.p + pts_base);
-    // one copy, not waited for: whatever the stream does next is ordered behind it, and the next pack into this bank waits (above)
-    HIPCHK(hipMemcpyAsync(B.d_blob.p, B.h_blob.p, total, hipMemcpyHostToDevice, h->stream));
-    B.staged_serial = h->sync_serial;
-    B.n_packed = n;
-    B.pack_failed = false;
-    h->events_used = 0;
-    h->folded_kernel_ms = 0.0;
-    h->folded_launches = 0;
-    std::memset(&h->stats, 0, sizeof h->stats);
-    return PDMPC_OK;
-}
-
 // what the graph search, the sampled optimizer and the joint search (KernelArgs, JointArgs) all read: the automaton, the packed
 // batch, the records, the arenas' size, the tree sizes and work counters
 template <class Args>
@@ -602,124 +267,45 @@ void set_batch_args(const pdmpc_handle* h, const PackedStep& B, int areas_in_lds
     a.Hp = h->cfg.Hp;
     a.areas_in_lds = areas_in_lds;
     a.dt = h->cfg.dt_seconds;
-    a.veh = B.d_veh;
-    a.points = B.d_pts;
+    a.veh = B.dev.veh;
+    a.points = B.dev.pts;
     a.out = h->d_out.p;
     a.max_nodes = h->arena.max_nodes;
     a.tree_size = h->d_tree_size.p;
     a.work_count = h->d_work_count.p;
 }
 
-// The next event pair of the handle, its start recorded on the stream; end_timed_launch records its end behind the launch.
-int begin_timed_launch(pdmpc_handle* h, LaunchKind kind) {
-    if (h->events_used == kMaxLaunchEvents) {
-        // a caller that launches resident banks for ever (no pack, no pdmpc_reset_stats in between) must not make the handle hold an
-        // event pair per launch: the pairs' times are folded into a sum and the pairs used again
-        HIPCHK(hipStreamSynchronize(h->stream));
-        for (size_t i = 0; i < h->events_used; ++i) {
-            float t = 0.f;
-            if (hipEventElapsedTime(&t, h->events[i].first, h->events[i].second) == hipSuccess) h->folded_kernel_ms += t;
-        }
-        h->folded_launches += (int64_t)h->events_used;
-        h->events_used = 0;
-    }
-    if (h->events_used == h->events.size()) {
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
-        h->events.emplace_back(e0, e1);
-    }
-    HIPCHK(hipEventRecord(h->events[h->events_used++].first, h->stream));
-    h->launch_kind = kind;
-    return PDMPC_OK;
-}
-
-int end_timed_launch(pdmpc_handle* h) {
-    HIPCHK(hipEventRecord(h->events[h->events_used - 1].second, h->stream));
-    return PDMPC_OK;
-}
-
-// safe == true: the recovery path after a predecessor time-out (plan_packed_growing): slices that are resident as a whole,
-// no helper workgroups next to an oversubscribed launch, the default spin limit.
-// The bank's kind decides the kernel: the graph search, or the sampled optimizer for a bank packed with seeds.
-int launch_range(pdmpc_handle* h, int first, int count, bool safe) {
-    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
-    PackedStep& B = h->banks[h->bank];
-    const LaunchKind kind = B.sampled ? kLaunchSampled : kLaunchSearch;
-    if (B.pack_failed) return fail(PDMPC_ERR_INVALID, "the last pack into this bank failed: nothing is packed");
-    if (first < 0 || count < 0 || first + count > B.n_packed) return fail(PDMPC_ERR_INVALID, "launch range outside the packed batch");
-    if (!B.perm.empty() && (first != 0 || count != B.n_packed)) return fail(PDMPC_ERR_INVALID, "range launches need a batch packed in level order (predecessors in lower slots)");
-    if (count == 0) return PDMPC_OK;
-    const Tuning& T = h->tune;
-    const bool search = kind == kLaunchSearch;
-    int rc = search ? compute_lds_bulk(h, count, B.soup_cap) : compute_lds_sampled(h, B.soup_cap, B.cand_cap);
-    if (rc) return rc;
-    KernelArgs a{};
-    set_batch_args(h, B, h->areas_in_lds, a);
-    a.checker = h->cfg.checker;
-    a.pred = B.d_pred;
-    a.done_flag = h->d_flag.p;
-    a.epoch = h->epoch;
-    a.first = first;
-    a.arena = h->arena.view();
-    a.lds = h->lds;
-    a.NL = h->NL;
-    a.NV = h->NV;
-    a.soup_cap = B.soup_cap;
-    a.cand_cap = B.cand_cap;
-    a.n_waves = h->n_waves;
-    a.tie_count = h->d_tie_count.p;
-    a.spin_limit = safe ? (1u << 22) : T.spin_limit;
-    a.debug_tail = T.debug_tail;
-    if (T.debug_progress && !h->progress) {
-        if (hipHostMalloc((void**)&h->progress, (size_t)h->max_vehicles * 64 * 4, hipHostMallocMapped) != hipSuccess) h->progress = nullptr;
-        if (h->progress) std::memset(h->progress, 0, (size_t)h->max_vehicles * 64 * 4);
-    }
-    a.progress = h->progress;
-    a.speculate = T.speculate;
-    a.reverse_dispatch = (!safe && T.reverse_dispatch) ? 1 : 0;
-
+// The launch policy: the sizes of a launch's rounds, its helper workgroups and where they sit -- bk_ready_cap, bk_round0, bk_round, bk_ramp,
+// bk_tile, bk_share_min, n_helpers and bk_helpers_first of `a`, and nothing else of it.  No HIP call, nothing of the handle touched: every
+// value it gives leaves the records bit-identical (struct Tuning), so only a benchmark sees it.  `slots`: the host records of the
+// launch's slots (read only where the place of the helpers depends on how many of them have predecessors).
+void launch_policy(const Tuning& T, int count, int n_cu, int device_share, bool safe, bool search, const LaunchLayout& lay, const DevVehicle* slots, KernelArgs& a) {
     // rounds: measured on C2 / C3 (20 / 128 searches, helpers): cap 256, ramp 4 -> 646 / 589 steps/s; 512, 2 -> 735 / 786; 1000, 2 -> 769 / 909; 1000, 1 -> 620 / 772
-    const bool helped = search && !safe && bulk_has_helpers(h, count);
-    a.bk_ready_cap = std::min(h->bk_ready_launch, 3 * PDMPC_WAVE * h->n_waves);  // (the verdict pass handles three entries per thread)
+    const bool helped = search && !safe && bulk_has_helpers(T, n_cu, count);
+    a.bk_ready_cap = std::min(lay.ready, 3 * PDMPC_WAVE * lay.n_waves);  // (the verdict pass handles three entries per thread)
     a.bk_round0 = T.round0 > 0 ? T.round0 : 24;  // (C3's class: below, once the helpers are counted)
-    a.bk_round = std::min(h->bk_ready_launch / 2 - 16, std::max(a.bk_round0, T.round > 0 ? T.round : (helped ? 1000 : 256)));
+    a.bk_round = std::min(lay.ready / 2 - 16, std::max(a.bk_round0, T.round > 0 ? T.round : (helped ? 1000 : 256)));
     a.bk_ramp = T.ramp > 0 ? T.ramp : (helped ? 2 : 4);
-    a.bk_mid_min = T.mid_min;
-    a.bk_mid_fill = T.mid_fill;
     a.bk_tile = T.tile > 0 ? T.tile : 256;
-    if (h->compact_layout) a.bk_tile = std::min(a.bk_tile, 256);  // (a helper stages its range in the near list's room: 12 KB in the compact layout)
-    a.bk_tentative = T.tentative;
-    a.bk_fast_arrival = T.fast_arrival;
-    a.bk_seat_nodes = std::max(1, T.seat_nodes);
-    a.bk_force_tie = T.force_tie;
-    a.bk_post = h->d_bk_post.p;
-    a.help_board = h->d_help_board.p;
-    a.help_verdict = h->d_help_verdict.p;
-    a.help_finished = h->d_help_finished.p;
-    a.help_fin_base = 0;
-    h->launch_serial += 1;
-    if (h->launch_serial == 0) h->launch_serial = 1;
-    a.launch_id = h->launch_serial;
+    if (lay.compact) a.bk_tile = std::min(a.bk_tile, 256);  // (a helper stages its range in the near list's room: 12 KB in the compact layout)
     // Helper workgroups: the trailing workgroups of the launch, on the CUs it leaves idle, check tiles of the searches' large rounds.
     // A launch with more searches than CUs gets them for its tail, when CUs fall idle while a few long searches still run (measured on
     // C4, 512 searches: none 25.6 steps/s, 32 helpers 41.5, 96: 42.8-45.9; C5, 1 280 searches: none 478 steps/s, 64 behind the searches 543,
     // 200: 549, with rounds shared from 64 nodes on 560 — the last levels' searches, which run when the CUs fall idle, are the tail of
     // the step).  In the safe mode a launch gets none: they would sit where a slice's search could run.
-    a.n_searches = count;
     a.n_helpers = 0;
     if (helped) {
-        if (count <= h->n_cu) {
+        if (count <= n_cu) {
             // every CU the launch leaves idle: a seated helper polls a word of its own, so helpers cost the searches nothing (measured on
             // C2, 20 searches: 32 helpers 1 110 steps/s, 64: 1 120, 96: 1 190, 128: 1 200, 200: 1 210, 230: 1 235; with the ticket word of
             // rounds 3-4 that all helpers polled and claimed from, 64 helpers were slower than 32 and 200 cost 40 %)
-            int want = h->n_cu - count;
+            int want = n_cu - count;
             if (T.helpers >= 0) want = T.helpers;
-            a.n_helpers = std::max(0, std::min(want, h->n_cu - count));
+            a.n_helpers = std::max(0, std::min(want, n_cu - count));
             if (a.n_helpers < 2) a.n_helpers = 0;
         } else {
             a.n_helpers = 200;  // (seated helpers cost the searches nothing: measured on C4 96 -> 76.9 steps/s, 160-250 -> 77.7)
-            if (T.helpers_oversub >= 0) a.n_helpers = std::min(T.helpers_oversub, 3 * h->n_cu);
+            if (T.helpers_oversub >= 0) a.n_helpers = std::min(T.helpers_oversub, 3 * n_cu);
             if (T.helpers >= 0) a.n_helpers = std::min(a.n_helpers, T.helpers);
         }
     }
@@ -730,49 +316,100 @@ int launch_range(pdmpc_handle* h, int first, int count, bool safe) {
     // 64: 86.5, 128: 90.2, 160: 88.0, 200: 54.6).  A launch of independent searches keeps every CU for them.
     // (handles that share a device — the logical ranks of a group — launch side by side: the idle CUs are the device's, not the
     // launch's, and helper workgroups in FRONT of every launch's searches would fill the chip before any search starts)
-    if (h->device_share > 1) a.n_helpers = a.n_helpers / h->device_share >= 2 ? a.n_helpers / h->device_share : 0;
+    if (device_share > 1) a.n_helpers = a.n_helpers / device_share >= 2 ? a.n_helpers / device_share : 0;
     a.bk_helpers_first = 0;
-    if (count > h->n_cu && a.n_helpers > 0 && h->device_share == 1) {
+    if (count > n_cu && a.n_helpers > 0 && device_share == 1) {
         int want = T.helpers_first;
-        if (want < 0 && count > 2 * h->n_cu) want = 0;  // (five searches per CU, C5: the searches need every CU — 128 in front 331 steps/s, 32: 515, none: 560)
+        if (want < 0 && count > 2 * n_cu) want = 0;  // (five searches per CU, C5: the searches need every CU — 128 in front 331 steps/s, 32: 515, none: 560)
         if (want < 0) {
             int chained = 0;
-            const DevVehicle* hv = h->banks[h->bank].h_veh + first;
-            for (int i = 0; i < count; ++i) chained += hv[i].n_pred > 0 ? 1 : 0;
-            want = 2 * chained >= count ? h->n_cu / 2 : 0;
+            for (int i = 0; i < count; ++i) chained += slots[i].n_pred > 0 ? 1 : 0;
+            want = 2 * chained >= count ? n_cu / 2 : 0;
         }
         a.bk_helpers_first = std::max(0, std::min(want, a.n_helpers));
     }
     // rounds are shared from 64 nodes on where helpers are plenty (C2: a dozen per search), from a few hundred on where there are
     // about as many helpers as searches or fewer (measured C3, 128 + 128: 64 -> 1 026 steps/s, 128-192 -> 1 070, 384 -> 986; C4, 512 + 96:
     // 64 -> 65.5, 192 -> 67, 512 -> 69; C5, 1 280 + 200 behind the searches, whose helpers only meet the medium searches of the tail: 32-128 -> 560)
-    a.bk_share_min = T.share_min > 0 ? T.share_min : (a.n_helpers >= 4 * count ? 64 : (count <= h->n_cu ? 128 : (count <= 2 * h->n_cu ? 512 : 64)));
+    a.bk_share_min = T.share_min > 0 ? T.share_min : (a.n_helpers >= 4 * count ? 64 : (count <= n_cu ? 128 : (count <= 2 * n_cu ? 512 : 64)));
     // (sixteen wavefronts: C3 — 128 searches + 128 helpers — 1 135 steps/s with young rounds of 24 nodes and sharing from 160 on, 1 175 with 32
     // and 128; 28: 1 154, 36: 1 137.  C2 / C4 / C5 with 32: -0.6 % / -1 % / +0.6 %: they stay at 24)
-    if (T.round0 < 0 && helped && ((count <= h->n_cu && a.n_helpers < 4 * count) || count > 2 * h->n_cu)) {  // (C5, 1 280 searches: 558 -> 565)
+    if (T.round0 < 0 && helped && ((count <= n_cu && a.n_helpers < 4 * count) || count > 2 * n_cu)) {  // (C5, 1 280 searches: 558 -> 565)
         a.bk_round0 = 32;
         a.bk_round = std::max(a.bk_round, a.bk_round0);
     }
-    if (a.n_helpers > 0 && !h->boards_dirty) {
+}
+
+// what a launch reads besides the batch and its layout: the handle's buffers, the tuning's switches, the launch's number
+void set_launch_args(pdmpc_handle* h, const PackedStep& B, const LaunchLayout& lay, int first, int count, bool safe, KernelArgs& a) {
+    const Tuning& T = h->tune;
+    set_batch_args(h, B, lay.areas_in_lds, a);
+    a.checker = h->cfg.checker;
+    a.pred = B.dev.pred;
+    a.done_flag = h->d_flag.p;
+    a.epoch = h->epoch;
+    a.first = first;
+    a.arena = h->arena.view();
+    a.lds = lay.lds;
+    a.NL = lay.NL;
+    a.NV = lay.NV;
+    a.soup_cap = B.soup_cap;
+    a.cand_cap = B.cand_cap;
+    a.n_waves = lay.n_waves;
+    a.tie_count = h->d_tie_count.p;
+    a.spin_limit = safe ? (1u << 22) : T.spin_limit;
+    a.debug_tail = T.debug_tail;
+    if (T.debug_progress && !h->progress) {
+        if (hipHostMalloc((void**)&h->progress, (size_t)h->max_vehicles * 64 * 4, hipHostMallocMapped) != hipSuccess) h->progress = nullptr;
+        if (h->progress) std::memset(h->progress, 0, (size_t)h->max_vehicles * 64 * 4);
+    }
+    a.progress = h->progress;
+    a.speculate = T.speculate;
+    a.reverse_dispatch = (!safe && T.reverse_dispatch) ? 1 : 0;
+    a.bk_mid_min = T.mid_min;
+    a.bk_mid_fill = T.mid_fill;
+    a.bk_tentative = T.tentative;
+    a.bk_fast_arrival = T.fast_arrival;
+    a.bk_seat_nodes = std::max(1, T.seat_nodes);
+    a.bk_force_tie = T.force_tie;
+    a.bk_post = h->d_bk_post.p;
+    a.help_board = h->d_help_board.p;
+    a.help_verdict = h->d_help_verdict.p;
+    a.help_finished = h->d_help_finished.p;
+    h->launch_serial += 1;
+    if (h->launch_serial == 0) h->launch_serial = 1;
+    a.launch_id = h->launch_serial;
+    a.n_searches = count;
+}
+
+// The helper boards of a launch with helper workgroups: where its count of finished searches starts (KernelArgs::help_fin_base).
+int prepare_boards(pdmpc_handle* h, int count, uint32_t& fin_base) {
+    fin_base = 0;
+    if (!h->boards_dirty) {
         // The boards stay closed between launches (a search closes every round it shares before it uses the verdicts, and a closed
         // ticket word offers nothing) and the count of finished searches runs on from launch to launch: nothing to clear -- two
         // memset dispatches less per launch.  A launch that ended with a watchdog status marks them dirty and the next one clears them.
-        a.help_fin_base = h->help_fin_total;
+        fin_base = h->help_fin_total;
         h->help_fin_total += (uint32_t)count;
-    } else if (a.n_helpers > 0) {
+    } else {
         HIPCHK(hipMemsetAsync(h->d_help_board.p, 0, (size_t)h->max_vehicles * PDMPC_HB_WORDS * sizeof(unsigned long long), h->stream));
         HIPCHK(hipMemsetAsync(h->d_help_finished.p, 0, 16 * sizeof(uint32_t), h->stream));
         h->help_fin_total = (uint32_t)count;
         h->boards_dirty = false;
     }
-    if ((rc = begin_timed_launch(h, kind))) return rc;
-    // Oversubscribed launches (more searches than CUs).  A resident search spins for predecessors of the same launch; slots are in
-    // level order (pack_common sees to it), so as long as the hardware hands out workgroups in index order every predecessor was
-    // dispatched before its successors and the launch cannot stall.  That order is not a documented guarantee: should a launch ever
-    // stall, the watchdog (spin_limit) ends the waiting searches with an error status and plan_packed_growing plans the call again
-    // with safe == true, in slices that are resident as a whole (a slice's predecessors are in it or in an earlier slice) -- forward
-    // progress then needs no assumption at all.
-    const int variant = h->compact_layout ? 3 : (h->cfg.checker == PDMPC_CHECK_SAT ? 2 : (h->n_words != 1 ? 1 : 0));
+    return PDMPC_OK;
+}
+
+// The kernel launches of one launch_range; returns the hipError_t of the first that failed.
+// Oversubscribed launches (more searches than CUs).  A resident search spins for predecessors of the same launch; slots are in
+// level order (the packer sees to it: coupling_order.hpp), so as long as the hardware hands out workgroups in index order every
+// predecessor was dispatched before its successors and the launch cannot stall.  That order is not a documented guarantee: should a
+// launch ever stall, the watchdog (spin_limit) ends the waiting searches with an error status and plan_packed_growing plans the call
+// again with safe == true, in slices that are resident as a whole (a slice's predecessors are in it or in an earlier slice) -- forward
+// progress then needs no assumption at all.
+int dispatch(const pdmpc_handle* h, const KernelArgs& a, const LaunchLayout& lay, bool search, bool safe) {
+    const int first = a.first, count = a.n_searches;
+    const int variant = lay.compact ? 3 : (h->cfg.checker == PDMPC_CHECK_SAT ? 2 : (h->n_words != 1 ? 1 : 0));
     auto launch_search = [&](const KernelArgs* ka, int cnt) -> int {
         std::lock_guard<std::mutex> lock(g_lds_mutex);
         uint32_t* hw = &g_lds_high_water[h->cfg.device & 63][variant];
@@ -781,35 +418,55 @@ int launch_range(pdmpc_handle* h, int first, int count, bool safe) {
         if (variant == 1) return pdmpc_launch_bulk_wide(ka, cnt, (void*)h->stream, hw);
         return pdmpc_launch_bulk(ka, cnt, (void*)h->stream, hw);
     };
-    int lrc = 0;
+    // a safe launch goes out in slices of `resident` searches, any other as a whole
+    auto in_slices = [&](int resident, auto&& launch) -> int {
+        int lrc = 0;
+        for (int done = 0; done < count && lrc == 0; done += resident) {
+            KernelArgs part = a;
+            part.first = first + done;
+            part.n_searches = std::min(resident, count - done);
+            lrc = launch(&part, part.n_searches);
+        }
+        return lrc;
+    };
     if (!search) {
         // (no arenas: the tree is the fixed 288-node tree in LDS.  Resident slices: two workgroups per CU at <= 80 KB, else one)
-        const int resident = h->lds.total <= kLdsMax / 2 ? 2 * h->n_cu : h->n_cu;
-        for (int done = 0; done < count && lrc == 0; done += safe ? resident : count) {
-            KernelArgs part = a;
-            part.first = first + done;
-            part.n_searches = safe ? std::min(resident, count - done) : count;
-            lrc = pdmpc_launch_sampled(&part, part.n_searches, (void*)h->stream);
-        }
-    } else if (safe && count > h->n_cu) {
-        for (int done = 0; done < count && lrc == 0; done += h->n_cu) {
-            KernelArgs part = a;
-            part.first = first + done;
-            part.n_searches = std::min(h->n_cu, count - done);
-            lrc = launch_search(&part, part.n_searches);
-        }
-    } else {
-        lrc = launch_search(&a, count);
+        const int resident = lay.lds.total <= kLdsMax / 2 ? 2 * h->n_cu : h->n_cu;
+        return in_slices(safe ? resident : count, [&](const KernelArgs* ka, int cnt) { return pdmpc_launch_sampled(ka, cnt, (void*)h->stream); });
     }
+    if (safe && count > h->n_cu) return in_slices(h->n_cu, launch_search);
+    return launch_search(&a, count);
+}
+
+// safe == true: the recovery path after a predecessor time-out (plan_packed_growing): slices that are resident as a whole,
+// no helper workgroups next to an oversubscribed launch, the default spin limit.
+// The bank's kind decides the kernel: the graph search, or the sampled optimizer for a bank packed with seeds.
+int launch_range(pdmpc_handle* h, int first, int count, bool safe) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    PackedStep& B = h->banks[h->bank];
+    const bool search = !B.sampled;
+    if (B.pack_failed) return fail(PDMPC_ERR_INVALID, "the last pack into this bank failed: nothing is packed");
+    if (first < 0 || count < 0 || first + count > B.n_packed) return fail(PDMPC_ERR_INVALID, "launch range outside the packed batch");
+    if (!B.perm.empty() && (first != 0 || count != B.n_packed)) return fail(PDMPC_ERR_INVALID, "range launches need a batch packed in level order (predecessors in lower slots)");
+    if (count == 0) return PDMPC_OK;
+    LaunchLayout lay;
+    int rc = search ? compute_lds_bulk(h, count, B.soup_cap, lay) : compute_lds_sampled(h, B.soup_cap, B.cand_cap, lay);
+    if (rc) return rc;
+    KernelArgs a{};
+    set_launch_args(h, B, lay, first, count, safe, a);
+    launch_policy(h->tune, count, h->n_cu, h->device_share, safe, search, lay, B.host.veh + first, a);
+    if (a.n_helpers > 0 && (rc = prepare_boards(h, count, a.help_fin_base))) return rc;
+    if ((rc = h->timer.begin(h->stream, search ? kLaunchSearch : kLaunchSampled))) return rc;
+    const int lrc = dispatch(h, a, lay, search, safe);
     if (lrc != 0) {
         h->boards_dirty = true;  // (the searches that were to count themselves finished never ran: the next launch starts from cleared counters)
         char buf[256];
-        snprintf(buf, sizeof buf, "kernel launch failed: %s (LDS %u B)", hipGetErrorString((hipError_t)lrc), h->lds.total);
+        snprintf(buf, sizeof buf, "kernel launch failed: %s (LDS %u B)", hipGetErrorString((hipError_t)lrc), lay.lds.total);
         return fail(PDMPC_ERR_HIP, buf);
     }
-    if ((rc = end_timed_launch(h))) return rc;
-    h->stats.lds_bytes = h->lds.total;
-    h->stats.lds_nodes = h->NL;
+    if ((rc = h->timer.end(h->stream))) return rc;
+    h->stats.lds_bytes = lay.lds.total;
+    h->stats.lds_nodes = lay.NL;
     return PDMPC_OK;
 }
 
@@ -996,9 +653,7 @@ int pdmpc_reset_stats(pdmpc_handle* h) {
     if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
     ON_DEVICE(h->cfg.device);
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->events_used = 0;
-    h->folded_kernel_ms = 0.0;
-    h->folded_launches = 0;
+    h->timer.reset();
     HIPCHK(hipMemsetAsync(h->d_tie_count.p, 0, 4 * sizeof(int32_t), h->stream));
     HIPCHK(hipMemsetAsync(h->d_work_count.p, 0, 16 * sizeof(unsigned long long), h->stream));
     return PDMPC_OK;
@@ -1037,10 +692,10 @@ int pdmpc_fetch_results(pdmpc_handle* h, int32_t n, pdmpc_vehicle_out* out) {
     int64_t bytes = h->mpa_alg_bytes;
     for (int i = 0; i < m; ++i) {
         const pdmpc_vehicle_out& o = rec[i];
-        const DevVehicle& d = B.h_veh[i];
+        const DevVehicle& d = B.host.veh[i];
         int64_t cols = B.lit_cols[i];
         for (int q = 0; q < d.n_pred; ++q) {
-            const int ps = B.h_pred[d.pred_off + q];
+            const int ps = B.host.pred[d.pred_off + q];
             if (ps < n)
                 for (int k = 0; k < Hp; ++k) cols += rec[ps].shape_cols[k] + 1;
         }
@@ -1161,7 +816,7 @@ int plan_packed_growing(pdmpc_handle* h, int32_t n, const Sink& sink) {
             h->dbg_us[1] += std::chrono::duration<double, std::micro>(t1 - t0).count();
             h->dbg_us[2] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t1).count();
             float ms = 0.f;
-            if (h->events_used > 0 && hipEventElapsedTime(&ms, h->events[h->events_used - 1].first, h->events[h->events_used - 1].second) == hipSuccess) h->dbg_us[3] += 1e3 * ms;
+            if (h->timer.last_ms(ms)) h->dbg_us[3] += 1e3 * ms;
         }
         if (dbg) fprintf(stderr, "pdmpc: fetched, status[0] %d\n", n > 0 ? sink.status_at(0) : 0);
         bool overflow = false, timed_out = false;
@@ -1371,7 +1026,7 @@ int pdmpc_plan_joint(pdmpc_handle* h, int32_t n_problems, const int32_t* problem
     for (int p = 0; p < n_problems; ++p) {
         int need = 0;
         for (int i = problem_offset[p]; i < problem_offset[p + 1]; ++i) {
-            const DevVehicle& d = B.h_veh[i];
+            const DevVehicle& d = B.host.veh[i];
             need += (d.lit_off[Hp] - d.lit_off[0]) + d.ll_len;
         }
         soup_cap = std::max(soup_cap, need);
@@ -1391,14 +1046,14 @@ int pdmpc_plan_joint(pdmpc_handle* h, int32_t n_problems, const int32_t* problem
         a.far_id = h->arena.far_id.p;
         a.heap_lds = heap_lds;
         a.lds = L;
-        if ((rc = begin_timed_launch(h, kLaunchJoint))) return rc;
+        if ((rc = h->timer.begin(h->stream, kLaunchJoint))) return rc;
         const int lrc = pdmpc_launch_joint(&a, n_problems, (void*)h->stream);
         if (lrc != 0) {
             char buf[256];
             snprintf(buf, sizeof buf, "joint kernel launch failed: %s (LDS %u B)", hipGetErrorString((hipError_t)lrc), L.total);
             return fail(PDMPC_ERR_HIP, buf);
         }
-        if ((rc = end_timed_launch(h))) return rc;
+        if ((rc = h->timer.end(h->stream))) return rc;
         if ((rc = pdmpc_fetch_results(h, n, out))) return rc;
         bool overflow = false;
         for (int i = 0; i < n; ++i) overflow = overflow || out[i].status == PDMPC_ARENA_OVERFLOW;
@@ -1480,14 +1135,7 @@ int pdmpc_get_last_stats(pdmpc_handle* h, pdmpc_stats* stats) {
     if (!h || !stats) return fail(PDMPC_ERR_INVALID, "null argument");
     ON_DEVICE(h->cfg.device);
     HIPCHK(hipStreamSynchronize(h->stream));
-    double ms = h->folded_kernel_ms;
-    for (size_t i = 0; i < h->events_used; ++i) {
-        float t = 0.f;
-        HIPCHK(hipEventElapsedTime(&t, h->events[i].first, h->events[i].second));
-        ms += t;
-    }
-    h->stats.kernel_ms = ms;
-    h->stats.n_launches = h->folded_launches + (int64_t)h->events_used;
+    if (int rc = h->timer.total(h->stats.kernel_ms, h->stats.n_launches)) return rc;
     int32_t ctr[4] = {0, 0, 0, 0};
     HIPCHK(hipMemcpy(ctr, h->d_tie_count.p, sizeof ctr, hipMemcpyDeviceToHost));
     h->stats.queue_fallbacks = ctr[0];
@@ -1496,7 +1144,7 @@ int pdmpc_get_last_stats(pdmpc_handle* h, pdmpc_stats* stats) {
     HIPCHK(hipMemcpy(work, h->d_work_count.p, sizeof work, hipMemcpyDeviceToHost));
     h->stats.edge_checks = (int64_t)work[0];
     h->stats.segment_pair_tests = (int64_t)work[1];
-    h->stats.kernel = h->launch_kind;
+    h->stats.kernel = h->timer.kind;
     h->stats.nodes_processed = (int64_t)work[2];
     h->stats.rounds = (int64_t)work[3];
     h->stats.shared_rounds = (int64_t)work[4];
@@ -1561,7 +1209,7 @@ namespace {
 // and independently of the kernel's phase B (it sorts the popped nodes instead of counting them), for the debug read-backs
 // the parity tests use.  Order (bulk_search.hpp): X is popped before Y iff X is an ancestor of Y or the largest key on
 // the path (LCA, X] is smaller than the largest key on (LCA, Y].
-// the slot a debug read-back's vehicle was planned in (pack_common may have put the batch into level order)
+// the slot a debug read-back's vehicle was planned in (the packer may have put the batch into level order)
 int debug_slot(const pdmpc_handle* h, int vehicle) {
     const PackedStep& B = h->banks[h->bank];
     return !B.inv.empty() && vehicle < B.n_packed ? B.inv[(size_t)vehicle] : vehicle;

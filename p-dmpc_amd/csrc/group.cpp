@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "../../include/pdmpc.h"
+#include "coupling_order.hpp"
 
 extern "C" void pdmpc_set_last_error(const char* msg);  // api.cpp
 
@@ -138,46 +139,14 @@ std::vector<int> weak_components(int n, const int32_t* off, const int32_t* idx) 
     return label;
 }
 
-// computation levels by longest path (kahn.m: a vehicle's level = 1 + the highest level among its predecessors); -1 on a cycle
-int levels_of(int n, const int32_t* off, const int32_t* idx, std::vector<int>& level) {
-    level.assign((size_t)n, 0);
-    std::vector<int> indeg((size_t)n, 0), succ_off((size_t)n + 1, 0), succ, queue;
-    if (off)
-        for (int i = 0; i < n; ++i)
-            for (int q = off[i]; q < off[i + 1]; ++q)
-                if (idx[q] >= 0 && idx[q] < n) {
-                    if (idx[q] == i) return -1;
-                    succ_off[(size_t)idx[q] + 1] += 1;
-                    indeg[(size_t)i] += 1;
-                }
-    for (int i = 0; i < n; ++i) succ_off[(size_t)i + 1] += succ_off[(size_t)i];
-    succ.resize((size_t)succ_off[(size_t)n]);
-    std::vector<int> fill(succ_off.begin(), succ_off.end() - 1);
-    if (off)
-        for (int i = 0; i < n; ++i)
-            for (int q = off[i]; q < off[i + 1]; ++q)
-                if (idx[q] >= 0 && idx[q] < n) succ[(size_t)fill[(size_t)idx[q]]++] = i;
-    for (int i = 0; i < n; ++i)
-        if (indeg[(size_t)i] == 0) {
-            level[(size_t)i] = 1;
-            queue.push_back(i);
-        }
-    for (size_t qi = 0; qi < queue.size(); ++qi) {
-        const int u = queue[qi];
-        for (int q = succ_off[(size_t)u]; q < succ_off[(size_t)u + 1]; ++q) {
-            const int w = succ[(size_t)q];
-            level[(size_t)w] = std::max(level[(size_t)w], level[(size_t)u] + 1);
-            if (--indeg[(size_t)w] == 0) queue.push_back(w);
-        }
-    }
-    return (int)queue.size() == n ? 0 : -1;
-}
-
 int make_partition(int n, const int32_t* off, const int32_t* idx, const double* weights, int world, int mode, Partition& P) {
     P.parts.assign((size_t)world, {});
     P.shared.clear();
     P.level_sizes.clear();
-    if (levels_of(n, off, idx, P.level_of)) return gfail(PDMPC_ERR_INVALID, "the sequential coupling graph has a cycle");
+    // (without predecessor lists the weights only balance the devices: every slot is its own component, in the caller's order)
+    CouplingOrder order;
+    if (order.build(n, off, idx, off ? weights : nullptr) != CouplingOrder::kOk) return gfail(PDMPC_ERR_INVALID, "the sequential coupling graph has a cycle");
+    P.level_of = order.level;
     const std::vector<int> label = weak_components(n, off, idx);
     std::vector<int> comp_ids;  // labels in ascending order
     std::vector<std::vector<int>> comp((size_t)n);
@@ -224,26 +193,12 @@ int make_partition(int n, const int32_t* off, const int32_t* idx, const double* 
     // a device's slots in a topological order of the coupling DAG: the sub-problem handed to pdmpc_pack_step then has its
     // predecessors in lower slots whatever order the caller's slots are in, so the handle does not permute it and the device-resident
     // record path (pdmpc_export_results_async) applies; group_fetch scatters back through these lists.  Without weights that is
-    // level order (ascending caller index within a level); with weights, PRIORITY order — the largest expected work among a vehicle
-    // and its descendants, descending, ties by level (api.cpp: pack_common does the same for a single handle, pdmpc_set_step_weights):
-    // a device with more searches than CUs starts its heavy searches with the launch, not behind the searches that wait.
-    std::vector<double> prio;
-    if (weights && off) {
-        prio.assign((size_t)n, 0.0);
-        for (int s = 0; s < n; ++s) prio[(size_t)s] = (weights[s] == weights[s] && weights[s] > 0) ? weights[s] : 0.0;
-        std::vector<int> by_level((size_t)n);
-        std::iota(by_level.begin(), by_level.end(), 0);
-        std::stable_sort(by_level.begin(), by_level.end(), [&](int a, int b) { return P.level_of[(size_t)a] > P.level_of[(size_t)b]; });
-        for (int s : by_level)  // (a vehicle after all its successors)
-            for (int q = off[s]; q < off[s + 1]; ++q)
-                if (idx[q] >= 0 && idx[q] < n) prio[(size_t)idx[q]] = std::max(prio[(size_t)idx[q]], prio[(size_t)s]);
-    }
+    // level order (ascending caller index within a level); with weights, PRIORITY order (coupling_order.hpp: the packer does the same
+    // for a single handle, pdmpc_set_step_weights): a device with more searches than CUs starts its heavy searches with the launch,
+    // not behind the searches that wait.
     for (auto& p : P.parts) {
         std::sort(p.begin(), p.end());
-        std::stable_sort(p.begin(), p.end(), [&](int a, int b) {
-            if (!prio.empty() && prio[(size_t)a] != prio[(size_t)b]) return prio[(size_t)a] > prio[(size_t)b];
-            return P.level_of[(size_t)a] < P.level_of[(size_t)b];
-        });
+        order.sort(p);
     }
     // the shared component in level order (levels by longest path, ascending vehicle index within a level: find(levels == i))
     if (!P.shared.empty()) {

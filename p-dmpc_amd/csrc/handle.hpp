@@ -1,5 +1,5 @@
-// handle.hpp — what the translation units of the C ABI's host side share (api.cpp: the searches; step_prep.cpp: the step-preparation
-// calls): error reporting, the device guard, the owning buffers and struct pdmpc_handle.  Private to the library.
+// handle.hpp — what the translation units of the C ABI's host side share (api.cpp: the searches; pack.cpp: the packer; step_prep.cpp:
+// the step-preparation calls): error reporting, the device guard, the owning buffers and struct pdmpc_handle.  Private to the library.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -164,17 +164,19 @@ struct Arenas {
 // pdmpc_stats.kernel: what the last launch ran
 enum LaunchKind : int32_t { kLaunchSearch = 2, kLaunchSampled = 3, kLaunchJoint = 4 };
 
-// one packed batch: host mirror (pinned) + device copy, each ONE allocation -- [DevVehicle records | points pool | predecessor slots] --
+// the regions of a batch blob: [vehicles | predecessor slots | points], each starting on a multiple of 16 bytes
+struct BlobRegions {
+    DevVehicle* veh = nullptr;
+    int32_t* pred = nullptr;
+    double* pts = nullptr;
+};
+
+// one packed batch: host mirror (pinned) + device copy, each ONE allocation -- BlobRegions --
 // so a pack is one host-to-device copy
 struct PackedStep {
     PinnedBuf<unsigned char> h_blob;
     DevBuf<unsigned char> d_blob;
-    DevVehicle* h_veh = nullptr;  // (views into the blobs, set by pack_common)
-    double* h_pts = nullptr;
-    int32_t* h_pred = nullptr;
-    DevVehicle* d_veh = nullptr;
-    double* d_pts = nullptr;
-    int32_t* d_pred = nullptr;
+    BlobRegions host, dev;  // (views into the blobs, set by pack_common)
     uint64_t staged_serial = ~0ull;  // the handle's sync_serial when the copy out of h_blob was queued (pack_common)
     int n_packed = 0;
     bool pack_failed = false;  // the last pack into this bank did not finish: nothing to launch or fetch
@@ -192,6 +194,41 @@ struct SoupKey {
     int32_t c[6];
 };
 
+// pack_common's scratch, kept with the handle for its allocations: an open-addressing table over the slots that brought new arrays
+// (a batch of 1 280 slots looks its key up 1 280 times)
+struct SoupTable {
+    std::vector<SoupKey> keys;   // key of the q-th distinct vehicle, slot[q] the slot it was packed in
+    std::vector<int32_t> slot;
+    std::vector<int32_t> table;  // hash -> q + 1, 0 = empty
+    static uint64_t hash(const SoupKey& k) {
+        static_assert(sizeof(SoupKey) % 8 == 0, "SoupKey is hashed by 64-bit words");
+        uint64_t hsh = 1469598103934665603ull;
+        const uint64_t* w = (const uint64_t*)&k;
+        for (size_t q = 0; q < sizeof(SoupKey) / 8; ++q) hsh = (hsh ^ w[q]) * 1099511628211ull;
+        return hsh ^ (hsh >> 29);
+    }
+    void reset(int n) {  // empty, with room for n keys
+        size_t size = 64;
+        while (size < (size_t)n * 2) size *= 2;
+        keys.clear();
+        slot.clear();
+        table.assign(size, 0);
+    }
+    // the slot the key was packed in, or -1 and `at`: where insert puts it
+    int find(const SoupKey& k, size_t& at) const {
+        for (at = (size_t)hash(k) & (table.size() - 1); table[at] != 0; at = (at + 1) & (table.size() - 1)) {
+            const int q = table[at] - 1;
+            if (std::memcmp(&keys[(size_t)q], &k, sizeof k) == 0) return slot[(size_t)q];
+        }
+        return -1;
+    }
+    void insert(const SoupKey& k, int packed_in, size_t at) {
+        keys.push_back(k);
+        slot.push_back(packed_in);
+        table[at] = (int32_t)keys.size();
+    }
+};
+
 // Tuning knobs and A/B / test switches of the graph search.  The defaults are the measured optima quoted next to their use; every
 // setting leaves the results bit-identical.  ONE environment variable overrides them, read once in pdmpc_create (a launch makes no
 // getenv call):  PDMPC_TUNING="key=value,key=value,..."  with the keys below (include/pdmpc.h documents the variable).
@@ -200,7 +237,7 @@ struct Tuning {
     int round = -1;         // the most a round takes (-1: 1000 with helper workgroups, else 256)
     int ramp = -1;          // a round grows by 1 / ramp of the nodes processed so far (-1: 2 with helper workgroups, else 4)
     int ready = 2048;       // entries of the ready list with helper workgroups (half of it without): the most a round can take
-    int share_min = -1;     // a round with at least this many nodes is shared with the helper workgroups (-1: by the number of helpers per search, launch_range)
+    int share_min = -1;     // a round with at least this many nodes is shared with the helper workgroups (-1: by the number of helpers per search, api.cpp: launch_policy)
     int tile = -1;          // the most nodes of a shared round one seated helper takes (-1: 256; what it stages in LDS: at most 768)
     int mid_min = 24576;    // far lists longer than this feed near through the mid list (a band of far's smallest keys)
     int mid_fill = 12288;   // entries a refill of mid aims at
@@ -220,6 +257,85 @@ struct Tuning {
     int debug_lds = 0;      // print the LDS layout of every launch
     int debug_host = 0;     // 1: a line per launch; 2: the host-time breakdown of the literal path
     int debug_progress = 0; // live counters in host-mapped memory (pdmpc_debug_progress)
+};
+
+// The LDS layout of one launch_range (api.cpp: compute_lds_bulk for the graph search, compute_lds_sampled for the sampled optimizer):
+// computed per launch and held by it, not by the handle.
+struct LaunchLayout {
+    LdsLayout lds{};
+    int n_waves = 0;       // wavefronts per workgroup
+    int NL = 0, NV = 0;    // node records / validity bytes in LDS
+    int areas_in_lds = 0;  // the automaton's maneuver areas are in LDS (else read from L2)
+    int ready = 0;         // entries of the ready list
+    bool compact = false;  // the compact kernel's (two workgroups per CU)
+};
+
+// The event pairs around the search launches of a handle (launch_range, pdmpc_plan_joint) and their times for pdmpc_get_last_stats:
+// a pair per launch since the last pack or pdmpc_reset_stats.
+struct LaunchTimer {
+    static constexpr size_t kMaxPairs = 4096;  // event pairs a handle keeps before it folds their times (begin)
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+    size_t used = 0;
+    double folded_ms = 0.0;  // launches whose event pairs were recycled (resident launches without a pack or reset in between)
+    int64_t folded_launches = 0;
+    LaunchKind kind = kLaunchSampled;  // of the last launch (before the first one: what pdmpc_get_last_stats always reported)
+    LaunchTimer() = default;
+    LaunchTimer(const LaunchTimer&) = delete;
+    LaunchTimer& operator=(const LaunchTimer&) = delete;
+    ~LaunchTimer() { release(); }
+    void release() {
+        for (auto& ev : events) {
+            (void)hipEventDestroy(ev.first);
+            (void)hipEventDestroy(ev.second);
+        }
+        events.clear();
+        used = 0;
+    }
+    // The next event pair, its start recorded on the stream; end records its end behind the launch.
+    int begin(hipStream_t stream, LaunchKind launch_kind) {
+        if (used == kMaxPairs) {
+            // a caller that launches resident banks for ever (no pack, no pdmpc_reset_stats in between) must not make the handle hold an
+            // event pair per launch: the pairs' times are folded into a sum and the pairs used again
+            HIPCHK(hipStreamSynchronize(stream));
+            for (size_t i = 0; i < used; ++i) {
+                float t = 0.f;
+                if (hipEventElapsedTime(&t, events[i].first, events[i].second) == hipSuccess) folded_ms += t;
+            }
+            folded_launches += (int64_t)used;
+            used = 0;
+        }
+        if (used == events.size()) {
+            hipEvent_t e0, e1;
+            HIPCHK(hipEventCreate(&e0));
+            HIPCHK(hipEventCreate(&e1));
+            events.emplace_back(e0, e1);
+        }
+        HIPCHK(hipEventRecord(events[used++].first, stream));
+        kind = launch_kind;
+        return PDMPC_OK;
+    }
+    int end(hipStream_t stream) {
+        HIPCHK(hipEventRecord(events[used - 1].second, stream));
+        return PDMPC_OK;
+    }
+    void reset() {  // the pairs stay for the next launches
+        used = 0;
+        folded_ms = 0.0;
+        folded_launches = 0;
+    }
+    // kernel time and number of the launches since the last reset, once the stream is idle
+    int total(double& ms, int64_t& launches) const {
+        ms = folded_ms;
+        for (size_t i = 0; i < used; ++i) {
+            float t = 0.f;
+            HIPCHK(hipEventElapsedTime(&t, events[i].first, events[i].second));
+            ms += t;
+        }
+        launches = folded_launches + (int64_t)used;
+        return PDMPC_OK;
+    }
+    // time of the last launch, once the stream is idle behind it; false: no launch, or its events are not readable
+    bool last_ms(float& ms) const { return used > 0 && hipEventElapsedTime(&ms, events[used - 1].first, events[used - 1].second) == hipSuccess; }
 };
 
 // ---- state of the step-preparation calls (step_prep.cpp): work that runs once per time step before the searches are packed
@@ -318,7 +434,6 @@ struct pdmpc_handle {
     DevBuf<unsigned long long> d_help_board;  // helper workgroups (pdmpc_device.h)
     DevBuf<uint32_t> d_help_verdict, d_help_finished;
     DevBuf<double> d_bk_post;                 // records posted for the helper workgroups
-    LaunchKind launch_kind = kLaunchSampled;  // of the last launch (before the first one: what pdmpc_get_last_stats always reported)
     DevBuf<int32_t> d_joint_off;         // pdmpc_plan_joint: the problems' first slots
     // the step-preparation calls (step_prep.cpp), one member per call family
     PrioState prio;
@@ -332,42 +447,28 @@ struct pdmpc_handle {
     double last_us[3] = {0, 0, 0};       // pdmpc_last_call_timing: pack, enqueue, wait + read-back of the last pdmpc_plan_batch / pdmpc_plan_step
     double dbg_us[4] = {0, 0, 0, 0};     // debug_host 2: pack, launch, fetch (host clock) and kernel (events) time of the plan_batch calls
     uint64_t sync_serial = 0;            // stream synchronisations through sync_stream so far (PackedStep::staged_serial)
-    std::vector<SoupKey> pack_soup_keys;  // pack_common's scratch: the distinct soup keys of the batch, the slots they were packed in, the hash table over them
-    std::vector<int32_t> pack_soup_slot, pack_soup_table;
+    SoupTable soups;                     // pack_common's scratch
     std::vector<double> next_weights;    // pdmpc_set_step_weights: expected work per vehicle of the NEXT packed step (the caller's order); consumed by that pack
     std::vector<uint32_t> next_seeds;    // pdmpc_set_step_seeds: the sampled optimizer's seed per vehicle of the NEXT packed step (the caller's order) ...
     bool seeds_set = false;              // ... consumed by that pack, which makes its bank a sampled bank
     PinnedBuf<double> h_lean;            // fetch_lean: (cost, status) per slot
     DevBuf<double> d_lean;
     PinnedBuf<pdmpc_vehicle_out> h_out;  // pdmpc_fetch_results: the records land in pinned memory (a copy into the caller's pageable array goes through the runtime's staging otherwise)
-    int bk_ready_launch = 2048;          // entries of the ready list of the last layout
     uint32_t* progress = nullptr;        // pinned, debug_progress
-    int n_waves = PDMPC_MAX_WAVES;       // of the last layout
-    bool compact_layout = false;         // the last layout is the compact kernel's (two workgroups per CU)
     // batch blobs: several packed steps can stay resident side by side ("banks", pdmpc_select_bank)
     std::vector<PackedStep> banks;
     int bank = 0;
     uint32_t epoch = 1;  // done flags start at 0, so no slot looks solved before its first launch
-    // launches
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-    size_t events_used = 0;
-    double folded_kernel_ms = 0.0;  // launches whose event pairs were recycled (resident launches without a pack or reset in between)
-    int64_t folded_launches = 0;
-    LdsLayout lds{};
-    int NL = 0, NV = 0, areas_in_lds = 0;
+    LaunchTimer timer;  // launches
     pdmpc_stats stats{};
     // the buffers free themselves after this: the stream is idle by then
     ~pdmpc_handle() {
         if (stream) (void)hipStreamSynchronize(stream);
-        for (auto& ev : events) {
-            (void)hipEventDestroy(ev.first);
-            (void)hipEventDestroy(ev.second);
-        }
+        timer.release();  // (the launches' events go before their stream)
         if (progress) (void)hipHostFree(progress);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
-
 
 // hipStreamSynchronize on the launch stream, counted: a bank whose staging copy was queued before is free again (pack_common)
 inline hipError_t sync_stream(pdmpc_handle* h) {
@@ -375,3 +476,7 @@ inline hipError_t sync_stream(pdmpc_handle* h) {
     if (e == hipSuccess) h->sync_serial += 1;
     return e;
 }
+
+// pack.cpp: the packer behind pdmpc_pack_step / pdmpc_pack_batch (flattens the caller's vehicles into the bank's blob and uploads it);
+// not an export of the library
+__attribute__((visibility("hidden"))) int pack_common(pdmpc_handle* h, int n, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index, const pdmpc_polygon_set* fallback);

@@ -1,4 +1,4 @@
-// pdmpc_device.h — HBM data layout shared by the host packer (api.cpp) and the search kernel.
+// pdmpc_device.h — HBM data layout shared by the host packer (pack.cpp) and the search kernel.
 //
 // Everything the kernel reads is a flat, pointer-free blob so one hipMemcpyAsync moves a whole batch:
 //
@@ -65,7 +65,7 @@ struct NodeRec {
 #define NODE_MAN(p) ((int)(((p) >> 15) & 4095u))
 #define NODE_COLS(p) ((int)(((p) >> 27) & 15u))
 
-// byte offsets of the regions of the dynamic LDS allocation (all multiples of 16; api.cpp: layout_bulk / layout_sampled)
+// byte offsets of the regions of the dynamic LDS allocation (all multiples of 16; api.cpp: layout_bulk / compute_lds_sampled)
 struct LdsLayout {
     uint32_t mask, man_index, pose, area;  // MPA tables
     uint32_t ref;                          // ref_x[16], ref_y[16], dtv[16]

@@ -153,7 +153,7 @@ struct pdmpc_controller {
     std::vector<uint8_t> fb_done;
     // obstacle sets of a vehicle by who contributes to them (a function of the vehicle and of those lists alone): the prioritizations
     // of an explorative step differ in a few couplings, so most of their vehicles share their sets — one build, one pointer, and
-    // pdmpc_pack_step packs a set it has seen under the same pointer once (api.cpp: pack_common)
+    // pdmpc_pack_step packs a set it has seen under the same pointer once (pack.cpp: pack_common)
     struct MemoKey {  // who contributes, as bit masks over the vehicles (up to 512: larger scenarios build every set)
         uint64_t w[16];
     };

@@ -9,7 +9,7 @@ mkdir -p build/asan
 CLANG=/opt/rocm/lib/llvm/bin/clang++
 FLAGS="-O1 -g -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude"
 for f in step_controller reachable_sets fca matlab_marshal; do $CLANG $FLAGS -c -o build/asan/$f.o p-dmpc_amd/csrc/$f.cpp; done
-OBJ=$(ls build/obj/*.hip.o build/obj/api.cpp.o build/obj/step_prep.cpp.o build/obj/group.cpp.o)
+OBJ=$(ls build/obj/*.hip.o build/obj/api.cpp.o build/obj/pack.cpp.o build/obj/step_prep.cpp.o build/obj/group.cpp.o)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -fsanitize=address,undefined -shared-libsan -o build/asan/libpdmpc_hip_asan.so $OBJ build/asan/step_controller.o build/asan/reachable_sets.o build/asan/fca.o build/asan/matlab_marshal.o -ldl
 RT=$(ls /opt/rocm/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.so | head -1)
 ASAN_OPTIONS=detect_leaks=0 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 LD_PRELOAD=$RT PDMPC_LIB=$PWD/build/asan/libpdmpc_hip_asan.so \
