@@ -144,6 +144,16 @@ def reachable_sets_at_pose(local_sets, x, y, yaw, trim) -> List[np.ndarray]:
     return out
 
 
+ORIENT_SNAP = 2.0**-40
+
+
+def _orient(dx, dy, rx, ry):
+    """pdmpc_orient: dx * ry - dy * rx, with rounding noise (below 2^-40 |d| (|d| + |r|), 1-norms) taken for 0."""
+    o = dx * ry - dy * rx
+    n = np.abs(dx) + np.abs(dy)
+    return np.where(np.abs(o) <= ORIENT_SNAP * (n * (n + (np.abs(rx) + np.abs(ry)))), 0.0, o)
+
+
 def _clipped_sum(ax, ay, bx, by, strict, total):
     """`total` plus, one edge after the other, cross(p0, p1) of the edges of polygon a (open, clockwise) clipped to polygon b
     (Cyrus-Beck).  closed (strict = False): the part inside b or on its boundary, an edge that runs along an edge of b in the same direction
@@ -155,8 +165,8 @@ def _clipped_sum(ax, ay, bx, by, strict, total):
     qx1, qy1 = np.roll(bx, -1), np.roll(by, -1)
     ux, uy = qx1 - qx0, qy1 - qy0
     # [edge of a, edge of b]: value of cross(u, p - q0) at the start of the a-edge, and its rate along the a-edge
-    num = ux[None, :] * (ey0[:, None] - qy0[None, :]) - uy[None, :] * (ex0[:, None] - qx0[None, :])
-    den = ux[None, :] * dy[:, None] - uy[None, :] * dx[:, None]
+    num = _orient(ux[None, :], uy[None, :], ex0[:, None] - qx0[None, :], ey0[:, None] - qy0[None, :])
+    den = _orient(ux[None, :], uy[None, :], dx[:, None], dy[:, None])
     par = den == 0.0
     if strict:
         dead = par & (num >= 0.0)
@@ -254,8 +264,8 @@ def _clip_table(lx, ly, kx, ky):
     """pdmpc_clip_edge_t for every edge of L (open) against the clockwise convex K (open) -> (tmin, tmax) per L edge."""
     dx, dy = np.roll(lx, -1) - lx, np.roll(ly, -1) - ly
     ux, uy = np.roll(kx, -1) - kx, np.roll(ky, -1) - ky
-    num = ux[None, :] * (ly[:, None] - ky[None, :]) - uy[None, :] * (lx[:, None] - kx[None, :])
-    den = ux[None, :] * dy[:, None] - uy[None, :] * dx[:, None]
+    num = _orient(ux[None, :], uy[None, :], lx[:, None] - kx[None, :], ly[:, None] - ky[None, :])
+    den = _orient(ux[None, :], uy[None, :], dx[:, None], dy[:, None])
     dead = ((den == 0.0) & (num >= 0.0)).any(axis=1)
     with np.errstate(divide="ignore", invalid="ignore"):
         t = -num / den
@@ -428,8 +438,8 @@ def _inside_fractions(ax, ay, px, py, strict):
     cx, cy = px[None, :], py[None, :]
     ex, ey = np.roll(px, -1)[None, :], np.roll(py, -1)[None, :]
     AX, AY, DX, DY, DD = ax[:, None], ay[:, None], dx[:, None], dy[:, None], dd[:, None]
-    oc = DX * (cy - AY) - DY * (cx - AX)
-    oe = DX * (ey - AY) - DY * (ex - AX)
+    oc = _orient(DX, DY, cx - AX, cy - AY)
+    oe = _orient(DX, DY, ex - AX, ey - AY)
     lc = oc > 0.0 if strict else oc >= 0.0
     le = oe > 0.0 if strict else oe >= 0.0
     cross = lc != le

@@ -2,8 +2,8 @@
 
 The Python twin (pdmpc.reachability.bound_reachable_set / polygon_overlap_area) and the C++ host twin
 (pdmpc_bound_reachable_sets_host / pdmpc_polygon_set_coupling_host) are bit-identical; the bounded sets meet hand-built answers and
-are valid (simple, clockwise, inside K and L); the overlap area of two simple polygons agrees with an independent answer (ear
-clipping, then the convex overlap_area over the triangle pairs); the native controller (no handle, oracle as planner) builds the same
+are valid (simple, clockwise, inside K and L, with the exact area of K ∩ L); the overlap area of two simple polygons agrees with the
+exact answer (tests/exact_geometry.py: ear clipping and Sutherland–Hodgman in fractions.Fraction); the native controller (no handle, oracle as planner) builds the same
 step problems as the Python controller with bounding on; and bounding drops couplings that exist only because the sets were not
 bounded."""
 import math
@@ -11,6 +11,7 @@ import math
 import numpy as np
 import pytest
 
+import exact_geometry as X
 from pdmpc import reachability as R
 from pdmpc.backend import bound_reachable_sets_call, polygon_set_coupling_call
 from pdmpc.config import Config, MpaType, ScenarioType
@@ -310,7 +311,7 @@ def test_bounded_sets_of_closed_loop_states_are_valid(closed_loop_states):
                     assert _inside_convex(ro, K, 1e-12), (name, v, q)
                     for px, py in zip(ro[0], ro[1]):
                         assert _inside_simple(px, py, Ln) or _dist_to_polygon_boundary(px, py, Ln) <= 1e-12, (name, v, q)
-                    full = R.polygon_overlap_area(K, _closed(Ln))
+                    full = float(X.area_convex_simple(X.poly(K), X.poly(Ln)))  # exact (tests/exact_geometry.py)
                     area = -_signed_area(ro)
                     assert area <= full * (1 + 1e-12) + 1e-15, (name, v, q)
                     if f & R.BOUND_MULTIPLE:
@@ -321,55 +322,12 @@ def test_bounded_sets_of_closed_loop_states_are_valid(closed_loop_states):
     assert checked > 100
 
 
-# ---- 4. overlap area against ear clipping + the convex overlap_area
-
-
-def _ear_clip(p):
-    """Triangles (each clockwise (2, 3)) of a simple clockwise polygon."""
-    pts = [tuple(c) for c in _open(p).T.tolist()]
-    tris = []
-
-    def cross(o, a, b):
-        return (a[0] - o[0]) * (b[1] - o[1]) - (a[1] - o[1]) * (b[0] - o[0])
-
-    guard = 0
-    while len(pts) > 3 and guard < 100000:
-        guard += 1
-        m = len(pts)
-        for i in range(m):
-            a, b, c = pts[i - 1], pts[i], pts[(i + 1) % m]
-            cr = cross(a, b, c)
-            if cr == 0:  # collinear: drop the vertex
-                pts.pop(i)
-                break
-            if cr > 0:  # reflex for a clockwise polygon
-                continue
-            ok = True
-            for j in range(m):
-                if j in (i - 1 if i > 0 else m - 1, i, (i + 1) % m):
-                    continue
-                p_ = pts[j]
-                if cross(a, b, p_) <= 0 and cross(b, c, p_) <= 0 and cross(c, a, p_) <= 0:
-                    ok = False
-                    break
-            if ok:
-                tris.append(np.array([[a[0], b[0], c[0]], [a[1], b[1], c[1]]]))
-                pts.pop(i)
-                break
-    if len(pts) == 3 and cross(*pts) < 0:
-        tris.append(np.array([[q[0] for q in pts], [q[1] for q in pts]]))
-    return tris
+# ---- 4. overlap area against the exact reference
 
 
 def _reference_area(A, B):
-    ta, tb = _ear_clip(A), _ear_clip(B)
-    total = 0.0
-    for a in ta:
-        for b in tb:
-            if a[0].min() >= b[0].max() or b[0].min() >= a[0].max() or a[1].min() >= b[1].max() or b[1].min() >= a[1].max():
-                continue
-            total += R.overlap_area(a, b)
-    return total
+    """the exact area of A ∩ B (tests/exact_geometry.py: ear clipping and Sutherland–Hodgman in fractions.Fraction)"""
+    return float(X.area_simple_simple(X.poly(A), X.poly(B)))
 
 
 def _star(rng, cx, cy, m, rmin=0.3, rmax=1.0):
