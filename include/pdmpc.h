@@ -434,6 +434,22 @@ int pdmpc_bounded_set_coupling(pdmpc_handle* handle, uint8_t* adjacency, double*
 int pdmpc_polygon_set_coupling_host(const pdmpc_polygon_set* sets, int32_t n, uint8_t* adjacency, double* area);
 /* kernel times (HIP events, ms) of the last pdmpc_bound_reachable_sets and pdmpc_bounded_set_coupling: ms2[0] bounding, ms2[1] coupling */
 int pdmpc_bounded_reachable_kernel_ms(pdmpc_handle* handle, double* ms2);
+/* The two couplers for several independent sets of vehicles at once.  The N = group_offset[n_groups] vehicles handed
+ * over are n_groups consecutive groups, group g = vehicles group_offset[g] .. group_offset[g + 1] - 1 (group_offset[0] = 0,
+ * non-decreasing; empty groups are legal); pairs are formed inside a group only.  adjacency / area: block g is n_g x n_g, row-major, at
+ * element offset sum_{h<g} n_h^2 (area may be NULL), and holds byte for byte what the ungrouped call returns for group g's vehicles alone.
+ * A call is one staging copy, the pose pass, one pair pass, one copy back and one synchronisation whatever n_groups is.
+ * pdmpc_bounded_set_coupling_grouped runs on the sets the last pdmpc_bound_reachable_sets left on the device: its groups cover exactly
+ * that call's vehicles.  PDMPC_ERR_INVALID for n_groups < 0, decreasing offsets, or a call before the upload / the bounding;
+ * PDMPC_ERR_CAPACITY for N > config.max_vehicles.  pdmpc_reachable_set_coupling_kernel_ms / pdmpc_bounded_reachable_kernel_ms report
+ * the grouped call when it was the last one.  The host twins loop over the ungrouped host twins. */
+int pdmpc_reachable_set_coupling_grouped(pdmpc_handle* handle, int32_t n_groups, const int32_t* group_offset, const double* x, const double* y,
+                                         const double* cos_yaw, const double* sin_yaw, const int32_t* trim, uint8_t* adjacency, double* area);
+int pdmpc_bounded_set_coupling_grouped(pdmpc_handle* handle, int32_t n_groups, const int32_t* group_offset, uint8_t* adjacency, double* area);
+int pdmpc_reachable_set_coupling_grouped_host(int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* local_sets, int32_t n_groups, const int32_t* group_offset,
+                                              const double* x, const double* y, const double* cos_yaw, const double* sin_yaw, const int32_t* trim,
+                                              uint8_t* adjacency, double* area);
+int pdmpc_polygon_set_coupling_grouped_host(const pdmpc_polygon_set* sets, int32_t n_groups, const int32_t* group_offset, uint8_t* adjacency, double* area);
 
 /* ---- future collision assessment (FcaPrioritizer.m:11-92; csrc/fca.cpp, csrc/fca_kernel.hip) ----
  * Vehicle v's footprint at step k is the box [-1,-1,1,1]·(length/2 + offset), [-1,1,1,-1]·(width/2 + offset) rotated by
@@ -599,6 +615,34 @@ int pdmpc_controller_set_optimizer(pdmpc_controller* c, int32_t which); /* PDMPC
 /* the sampled optimizer's seed per slot of the last built step or batch (pdmpc_controller_build_step / _explore_build / _optimal_build),
  * whichever optimizer is selected: *n slots, *seeds valid until the next build */
 int pdmpc_controller_seeds(pdmpc_controller* c, int32_t* n, const uint32_t** seeds);
+
+/* ---- several closed loops in lock-step (csrc/step_controller.cpp) ----
+ * A sweep borrows n_members controllers that were created on the same handle (or all without one) and steps them together: every
+ * member's build_step, with the device's step preparation grouped over the members (pdmpc_bound_reachable_sets on the concatenated
+ * vehicles, pdmpc_*_coupling_grouped: a pair of two members is never looked at), ONE pdmpc_plan_step for the concatenated problem,
+ * every member's apply.  After a sweep step each member is byte for byte where its own pdmpc_controller_step would have left it
+ * (state, records in its own slot order, problem, seeds, time step, expected work, fallback bookkeeping): a member can be taken out of
+ * a sweep and stepped alone afterwards.  Only the plain prioritized step is part of a sweep (graph search or sampled optimizer), not
+ * the explorative or the optimal-priority step.
+ * pdmpc_sweep_create checks before anything advances: members on the sweep's handle, or all without one; one Hp; one optimizer
+ * (PDMPC_ERR_INVALID each); no member twice (PDMPC_ERR_INVALID); sum of the members' vehicles <= the handle's max_vehicles
+ * (PDMPC_ERR_CAPACITY).  Members may differ in everything else.
+ * pdmpc_sweep_problem: the concatenated problem as pdmpc_plan_step receives it (the members' entries shallow-copied, pred_index
+ * shifted by the member's first slot); member[s] / member_slot[s] = whose slot s is and which slot of that member's own problem.
+ * pdmpc_sweep_apply takes records in that slot order.  pdmpc_sweep_last_timing: the six parts of pdmpc_controller_last_timing for
+ * the whole lock-step.
+ * An error while a step is built or planned is returned as the failing call returned it and leaves the sweep refusing further steps
+ * with PDMPC_ERR_INVALID: the members have then advanced UNEVENLY (some built or applied the step, others did not). */
+typedef struct pdmpc_sweep pdmpc_sweep;
+int pdmpc_sweep_create(pdmpc_handle* handle, int32_t n_members, pdmpc_controller* const* members, pdmpc_sweep** out);
+int pdmpc_sweep_destroy(pdmpc_sweep* s); /* the members stay the caller's */
+int pdmpc_sweep_build(pdmpc_sweep* s);
+int pdmpc_sweep_problem(pdmpc_sweep* s, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index,
+                        const pdmpc_polygon_set** fallback, const int32_t** member, const int32_t** member_slot);
+int pdmpc_sweep_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records);
+int pdmpc_sweep_step(pdmpc_sweep* s);
+int pdmpc_sweep_run(pdmpc_sweep* s, int32_t n_steps, double* ms);
+int pdmpc_sweep_last_timing(pdmpc_sweep* s, double* ms6);
 
 /* ---- several GPUs behind the same boundary (csrc/group.cpp) ----
  * The reference's vehicles exchange their solved areas after every computation level: each publishes a Predictions message that every

@@ -10,9 +10,14 @@
 //   pairs   PDMPC_BOUND_PAIR_BLOCKS wavefronts take the listed pairs grid-stride, one pair per wavefront at a time: lanes over the
 //           edges of both sets (pdmpc_edge_overlap_term), and lane 0 sums them in edge order — the host twin's additions.
 // Every output entry is written by exactly one lane, and a pair's area does not depend on where it landed in the list.
+//
+// The grouped coupler (pdmpc_bounded_set_coupling_grouped) runs box and pairs over consecutive groups of the bounded
+// vehicles: the box pass enumerates (row i, columns of i's own group) only and appends to the same list, and the pairs pass writes a
+// listed pair into its group's own n_g x n_g block.
 #include <hip/hip_runtime.h>
 
 #include "../../include/pdmpc_geometry.h"
+#include "pair_groups.hpp"
 #include "pdmpc_device.h"
 
 #define BOUND_WAVE 64
@@ -76,28 +81,32 @@ extern "C" __global__ __launch_bounds__(BOUND_WAVE) void pdmpc_bound_sets_kernel
     }
 }
 
-extern "C" __global__ __launch_bounds__(BOUND_WAVE) void pdmpc_bounded_box_kernel(const BoundArgs A) {
+namespace {
+template <bool GROUPED>
+__device__ inline void bounded_box(const BoundArgs& A) {
     const int n = A.n;
     const int i = (int)blockIdx.y;
-    const int j = (int)blockIdx.x * BOUND_WAVE + (int)threadIdx.x;
-    if (j >= n || j < i) return;
+    const RowOut o = row_out<GROUPED>(A.group, n, i);
+    const int j = o.first + (int)blockIdx.x * BOUND_WAVE + (int)threadIdx.x;
+    if (j >= o.end || j < i) return;
     if (j == i) {
-        A.adjacency[(size_t)i * n + i] = 0;
-        A.area[(size_t)i * n + i] = 0.0;
+        A.adjacency[o.at(i, i)] = 0;
+        A.area[o.at(i, i)] = 0.0;
         return;
     }
     if (pdmpc_boxes_overlap(A.box + 4 * i, A.box + 4 * j)) {
         const int slot = atomicAdd(A.n_pairs, 1);
         A.pairs[slot] = i * n + j;
     } else {
-        A.adjacency[(size_t)i * n + j] = 0;
-        A.adjacency[(size_t)j * n + i] = 0;
-        A.area[(size_t)i * n + j] = 0.0;
-        A.area[(size_t)j * n + i] = 0.0;
+        A.adjacency[o.at(i, j)] = 0;
+        A.adjacency[o.at(j, i)] = 0;
+        A.area[o.at(i, j)] = 0.0;
+        A.area[o.at(j, i)] = 0.0;
     }
 }
 
-extern "C" __global__ __launch_bounds__(BOUND_WAVE) void pdmpc_bounded_pairs_kernel(const BoundArgs A) {
+template <bool GROUPED>
+__device__ inline void bounded_pairs(const BoundArgs& A) {
     __shared__ double sax[PDMPC_BOUND_SLOT], say[PDMPC_BOUND_SLOT], sbx[PDMPC_BOUND_SLOT], sby[PDMPC_BOUND_SLOT];
     __shared__ double scr[2 * PDMPC_BOUND_SLOT];
     const int n = A.n, S = A.S;
@@ -106,6 +115,7 @@ extern "C" __global__ __launch_bounds__(BOUND_WAVE) void pdmpc_bounded_pairs_ker
     for (int pr = (int)blockIdx.x; pr < total; pr += (int)gridDim.x) {
         const int code = A.pairs[pr];
         const int i = code / n, j = code - i * n;
+        const RowOut o = row_out<GROUPED>(A.group, n, i);
         const size_t si = (size_t)i * S + S - 1, sj = (size_t)j * S + S - 1;
         const double* hix = A.set_x + si * PDMPC_BOUND_SLOT;
         const double* hiy = A.set_y + si * PDMPC_BOUND_SLOT;
@@ -135,14 +145,20 @@ extern "C" __global__ __launch_bounds__(BOUND_WAVE) void pdmpc_bounded_pairs_ker
             for (int e = 0; e < ma + mb; ++e) sum = sum + scr[e];
             const double ar = -0.5 * sum;
             const uint8_t cpl = ar > PDMPC_COUPLING_AREA_THRESHOLD ? 1 : 0;
-            A.area[(size_t)i * n + j] = ar;
-            A.area[(size_t)j * n + i] = ar;
-            A.adjacency[(size_t)i * n + j] = cpl;
-            A.adjacency[(size_t)j * n + i] = cpl;
+            A.area[o.at(i, j)] = ar;
+            A.area[o.at(j, i)] = ar;
+            A.adjacency[o.at(i, j)] = cpl;
+            A.adjacency[o.at(j, i)] = cpl;
         }
         __syncthreads();
     }
 }
+}  // namespace
+
+extern "C" __global__ __launch_bounds__(BOUND_WAVE) void pdmpc_bounded_box_kernel(const BoundArgs A) { bounded_box<false>(A); }
+extern "C" __global__ __launch_bounds__(BOUND_WAVE) void pdmpc_bounded_pairs_kernel(const BoundArgs A) { bounded_pairs<false>(A); }
+extern "C" __global__ __launch_bounds__(BOUND_WAVE) void pdmpc_bounded_box_grouped_kernel(const BoundArgs A) { bounded_box<true>(A); }
+extern "C" __global__ __launch_bounds__(BOUND_WAVE) void pdmpc_bounded_pairs_grouped_kernel(const BoundArgs A) { bounded_pairs<true>(A); }
 
 extern "C" int pdmpc_launch_bound_sets(const BoundArgs* args, void* stream) {
     const int sets = args->n * args->S;
@@ -160,6 +176,20 @@ extern "C" int pdmpc_launch_bounded_coupling(const BoundArgs* args, void* stream
         const long long max_pairs = (long long)n * (n - 1) / 2;
         const uint32_t blocks = (uint32_t)(max_pairs < PDMPC_BOUND_PAIR_BLOCKS ? max_pairs : PDMPC_BOUND_PAIR_BLOCKS);
         hipLaunchKernelGGL(pdmpc_bounded_pairs_kernel, dim3(blocks), dim3(BOUND_WAVE), 0, (hipStream_t)stream, *args);
+    }
+    return (int)hipGetLastError();
+}
+
+// the same two passes for consecutive groups (args->n vehicles in all): the box grid as wide as the largest group
+extern "C" int pdmpc_launch_bounded_coupling_grouped(const BoundArgs* args, void* stream) {
+    const int n = args->n, mg = args->max_group;
+    if (n <= 0 || mg <= 0) return 0;
+    const uint32_t col_blocks = (uint32_t)((mg + BOUND_WAVE - 1) / BOUND_WAVE);
+    hipLaunchKernelGGL(pdmpc_bounded_box_grouped_kernel, dim3(col_blocks, (uint32_t)n), dim3(BOUND_WAVE), 0, (hipStream_t)stream, *args);
+    if (mg >= 2) {
+        const long long max_pairs = (long long)n * (mg - 1) / 2;  // (an upper bound of the pairs inside the groups)
+        const uint32_t blocks = (uint32_t)(max_pairs < PDMPC_BOUND_PAIR_BLOCKS ? (max_pairs < 1 ? 1 : max_pairs) : PDMPC_BOUND_PAIR_BLOCKS);
+        hipLaunchKernelGGL(pdmpc_bounded_pairs_grouped_kernel, dim3(blocks), dim3(BOUND_WAVE), 0, (hipStream_t)stream, *args);
     }
     return (int)hipGetLastError();
 }

@@ -310,6 +310,14 @@ struct ReachArgs {
     double* box;                  // [4 n] x0, x1, y0, y1
     uint8_t* adjacency;           // [n * n]
     double* area;                 // [n * n] overlap area of every pair that passed the box test, 0 elsewhere
+    const int32_t* group;         // the grouped call only (PairGroup per vehicle): adjacency / area then hold one block per group
+    int32_t max_group;            // ... and its largest group
+};
+
+// Grouped couplers (pdmpc_*_coupling_grouped): the vehicles handed over are consecutive groups, pairs are formed inside a group only, and
+// group g's n_g x n_g results stand row-major at element offset sum_{h<g} n_h^2 of adjacency / area.  Per vehicle, staged by the host:
+struct PairGroup {
+    int32_t first, end, block;    // the vehicle's group is vehicles first .. end - 1; its block's element offset
 };
 
 // Lanelet bounding and the coupler on the bounded sets (bounded_kernel.hip; include/pdmpc_geometry.h).  Set o = v * S + q holds vehicle v's
@@ -337,6 +345,8 @@ struct BoundArgs {
     double* area;              // [n n]
     int32_t* pairs;            // [n (n - 1) / 2] i * n + j of the pairs that pass the box test
     int32_t* n_pairs;          // [1] their count (cleared before the box pass)
+    const int32_t* group;      // the grouped call only (PairGroup per vehicle)
+    int32_t max_group;         // ... and its largest group
 };
 
 // Future collision assessment (fca_kernel.hip; FcaPrioritizer.m:11-92): the footprints of every (vehicle, step), then
@@ -373,9 +383,11 @@ int pdmpc_fca_check_args(int32_t n, int32_t Hp, const double* x, const double* y
 void pdmpc_fca_sort_index(int32_t n, const int32_t* collisions, int32_t* priorities);
 // reachable_kernel.hip: the two passes of the reachable-set coupler on the handle's stream
 int pdmpc_launch_reachable_coupling(const ReachArgs* args, void* stream);
+int pdmpc_launch_reachable_coupling_grouped(const ReachArgs* args, void* stream);
 // bounded_kernel.hip: the bounding pass (one wavefront per set) and the two passes of the coupler on the step-Hp sets
 int pdmpc_launch_bound_sets(const BoundArgs* args, void* stream);
 int pdmpc_launch_bounded_coupling(const BoundArgs* args, void* stream);
+int pdmpc_launch_bounded_coupling_grouped(const BoundArgs* args, void* stream);
 // bulk_kernel*.hip: the graph search as bulk-synchronous passes (count searches + args->n_helpers helper workgroups in ONE launch) for the
 // InterX checker with one successor-mask word / with any number of them, and for the separating-axis checker; lds_high_water = the
 // handle's record of the dynamic LDS size set so far on that kernel

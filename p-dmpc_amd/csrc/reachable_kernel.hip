@@ -10,12 +10,20 @@
 //           the same sequence of additions as the host twin (reachable_sets.cpp) and reachability.py, so the 1e-3 decision and the
 //           area bits agree with both.
 // Every entry of the n x n outputs is written by exactly one lane: no clearing, no atomics, the same bits in any dispatch order.
+//
+// The grouped call (pdmpc_reachable_set_coupling_grouped) runs the same two passes over the concatenated vehicles of
+// several groups: pass 2's workgroup serves (row i, 64 columns of i's OWN group, counted from the group's first vehicle), so a pair of
+// two groups is neither box-tested nor written, and entry (i, j) goes to the group's own n_g x n_g block.  A pair's arithmetic does not
+// depend on which 64 columns it was served with: every block holds the bits of the ungrouped call on that group alone.
 #include <hip/hip_runtime.h>
 
 #include "../../include/pdmpc_geometry.h"
+#include "pair_groups.hpp"
 #include "pdmpc_device.h"
 
-extern "C" __global__ __launch_bounds__(PDMPC_REACH_WAVE) void pdmpc_reach_pose_kernel(const ReachArgs A) {
+namespace {
+template <bool GROUPED>
+__device__ inline void reach_pose(const ReachArgs& A) {
     const int v = (int)(blockIdx.x * PDMPC_REACH_WAVE + threadIdx.x);
     const int n = A.n;
     if (v >= n) return;
@@ -40,28 +48,30 @@ extern "C" __global__ __launch_bounds__(PDMPC_REACH_WAVE) void pdmpc_reach_pose_
     A.box[4 * v + 1] = b1;
     A.box[4 * v + 2] = b2;
     A.box[4 * v + 3] = b3;
-    A.adjacency[(size_t)v * n + v] = 0;
-    A.area[(size_t)v * n + v] = 0.0;
+    const RowOut o = row_out<GROUPED>(A.group, n, v);
+    A.adjacency[o.at(v, v)] = 0;
+    A.area[o.at(v, v)] = 0.0;
 }
 
-extern "C" __global__ __launch_bounds__(PDMPC_REACH_WAVE) void pdmpc_reach_pairs_kernel(const ReachArgs A) {
+template <bool GROUPED>
+__device__ inline void reach_pairs(const ReachArgs& A) {
     __shared__ double sax[PDMPC_REACH_MAX_COLS], say[PDMPC_REACH_MAX_COLS], sbx[PDMPC_REACH_MAX_COLS], sby[PDMPC_REACH_MAX_COLS];
     __shared__ double scr[2 * PDMPC_REACH_MAX_COLS];
     __shared__ uint8_t sok[2 * PDMPC_REACH_MAX_COLS];
-    const int n = A.n;
     const int i = (int)blockIdx.y;
     const int lane = (int)threadIdx.x;
-    const int j0 = (int)blockIdx.x * PDMPC_REACH_WAVE;
-    if (j0 + PDMPC_REACH_WAVE - 1 <= i) return;  // (uniform) no column of this block lies right of the diagonal
+    const RowOut o = row_out<GROUPED>(A.group, A.n, i);
+    const int j0 = o.first + (int)blockIdx.x * PDMPC_REACH_WAVE;
+    if (j0 + PDMPC_REACH_WAVE - 1 <= i || j0 >= o.end) return;  // (uniform) no column of this block lies right of the diagonal
     const int j = j0 + lane;
     bool cand = false;
-    if (j > i && j < n) {
+    if (j > i && j < o.end) {
         cand = pdmpc_boxes_overlap(A.box + 4 * i, A.box + 4 * j) != 0;
         if (!cand) {
-            A.adjacency[(size_t)i * n + j] = 0;
-            A.adjacency[(size_t)j * n + i] = 0;
-            A.area[(size_t)i * n + j] = 0.0;
-            A.area[(size_t)j * n + i] = 0.0;
+            A.adjacency[o.at(i, j)] = 0;
+            A.adjacency[o.at(j, i)] = 0;
+            A.area[o.at(i, j)] = 0.0;
+            A.area[o.at(j, i)] = 0.0;
         }
     }
     uint64_t pending = __ballot(cand);
@@ -105,14 +115,20 @@ extern "C" __global__ __launch_bounds__(PDMPC_REACH_WAVE) void pdmpc_reach_pairs
                 if (sok[e]) total = total + scr[e];
             const double ar = -0.5 * total;
             const uint8_t c = ar > PDMPC_COUPLING_AREA_THRESHOLD ? 1 : 0;
-            A.area[(size_t)i * n + jj] = ar;
-            A.area[(size_t)jj * n + i] = ar;
-            A.adjacency[(size_t)i * n + jj] = c;
-            A.adjacency[(size_t)jj * n + i] = c;
+            A.area[o.at(i, jj)] = ar;
+            A.area[o.at(jj, i)] = ar;
+            A.adjacency[o.at(i, jj)] = c;
+            A.adjacency[o.at(jj, i)] = c;
         }
         __syncthreads();
     }
 }
+}  // namespace
+
+extern "C" __global__ __launch_bounds__(PDMPC_REACH_WAVE) void pdmpc_reach_pose_kernel(const ReachArgs A) { reach_pose<false>(A); }
+extern "C" __global__ __launch_bounds__(PDMPC_REACH_WAVE) void pdmpc_reach_pairs_kernel(const ReachArgs A) { reach_pairs<false>(A); }
+extern "C" __global__ __launch_bounds__(PDMPC_REACH_WAVE) void pdmpc_reach_pose_grouped_kernel(const ReachArgs A) { reach_pose<true>(A); }
+extern "C" __global__ __launch_bounds__(PDMPC_REACH_WAVE) void pdmpc_reach_pairs_grouped_kernel(const ReachArgs A) { reach_pairs<true>(A); }
 
 extern "C" int pdmpc_launch_reachable_coupling(const ReachArgs* args, void* stream) {
     const int n = args->n;
@@ -120,5 +136,17 @@ extern "C" int pdmpc_launch_reachable_coupling(const ReachArgs* args, void* stre
     const uint32_t col_blocks = (uint32_t)((n + PDMPC_REACH_WAVE - 1) / PDMPC_REACH_WAVE);
     hipLaunchKernelGGL(pdmpc_reach_pose_kernel, dim3(col_blocks), dim3(PDMPC_REACH_WAVE), 0, (hipStream_t)stream, *args);
     if (n >= 2) hipLaunchKernelGGL(pdmpc_reach_pairs_kernel, dim3(col_blocks, (uint32_t)(n - 1)), dim3(PDMPC_REACH_WAVE), 0, (hipStream_t)stream, *args);
+    return (int)hipGetLastError();
+}
+
+// the same two passes for consecutive groups: as many launches as for one group, the pair grid as wide as the largest group
+extern "C" int pdmpc_launch_reachable_coupling_grouped(const ReachArgs* args, void* stream) {
+    const int n = args->n;
+    if (n <= 0) return 0;
+    const uint32_t pose_blocks = (uint32_t)((n + PDMPC_REACH_WAVE - 1) / PDMPC_REACH_WAVE);
+    const uint32_t col_blocks = (uint32_t)((args->max_group + PDMPC_REACH_WAVE - 1) / PDMPC_REACH_WAVE);
+    hipLaunchKernelGGL(pdmpc_reach_pose_grouped_kernel, dim3(pose_blocks), dim3(PDMPC_REACH_WAVE), 0, (hipStream_t)stream, *args);
+    if (args->max_group >= 2)
+        hipLaunchKernelGGL(pdmpc_reach_pairs_grouped_kernel, dim3(col_blocks, (uint32_t)(n - 1)), dim3(PDMPC_REACH_WAVE), 0, (hipStream_t)stream, *args);
     return (int)hipGetLastError();
 }

@@ -430,4 +430,47 @@ int pdmpc_polygon_set_coupling_host(const pdmpc_polygon_set* sets, int32_t n, ui
     return PDMPC_OK;
 }
 
+// ---- the grouped couplers' host twins: the ungrouped twin on every group alone, block after block
+namespace {
+bool groups_ok(int32_t n_groups, const int32_t* group_offset) {
+    if (n_groups < 0 || !group_offset || group_offset[0] != 0) return false;
+    for (int g = 0; g < n_groups; ++g)
+        if (group_offset[g + 1] < group_offset[g]) return false;
+    return true;
+}
+}  // namespace
+
+int pdmpc_reachable_set_coupling_grouped_host(int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* local_sets, int32_t n_groups, const int32_t* group_offset,
+                                              const double* x, const double* y, const double* cos_yaw, const double* sin_yaw, const int32_t* trim,
+                                              uint8_t* adjacency, double* area) {
+    if (!groups_ok(n_groups, group_offset) || !adjacency) return PDMPC_ERR_INVALID;
+    if (group_offset[n_groups] && (!x || !y || !cos_yaw || !sin_yaw || !trim)) return PDMPC_ERR_INVALID;
+    size_t block = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const int a = group_offset[g], m = group_offset[g + 1] - a;
+        if (m == 0) continue;
+        const int rc = pdmpc_reachable_set_coupling_host(n_trims, Hp, local_sets, m, x + a, y + a, cos_yaw + a, sin_yaw + a, trim + a, adjacency + block,
+                                                         area ? area + block : nullptr);
+        if (rc) return rc;
+        block += (size_t)m * m;
+    }
+    return PDMPC_OK;
+}
+
+int pdmpc_polygon_set_coupling_grouped_host(const pdmpc_polygon_set* sets, int32_t n_groups, const int32_t* group_offset, uint8_t* adjacency, double* area) {
+    if (!groups_ok(n_groups, group_offset) || !sets || sets->n_polygons != group_offset[n_groups] || !adjacency) return PDMPC_ERR_INVALID;
+    size_t block = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const int a = group_offset[g], m = group_offset[g + 1] - a;
+        if (m == 0) continue;
+        pdmpc_polygon_set part = *sets;  // (the offsets index the shared coordinate arrays: a group is a window of them)
+        part.n_polygons = m;
+        part.offset = sets->offset + a;
+        const int rc = pdmpc_polygon_set_coupling_host(&part, m, adjacency + block, area ? area + block : nullptr);
+        if (rc) return rc;
+        block += (size_t)m * m;
+    }
+    return PDMPC_OK;
+}
+
 }  // extern "C"

@@ -1077,8 +1077,10 @@ void reachable_sets_at_poses(pdmpc_controller* c) {
 
 // lanelet bounding of those sets (bound_reachable_sets.m, HighLevelController.m:241-246): every step's sets when parallel
 // predecessors read them (all_steps), else step Hp only (the coupler's)
-int bound_by_lanelets(pdmpc_controller* c, bool all_steps) {
-    const int n = c->n, Hp = c->Hp;
+// ... its two host halves, which the sweep runs per member around one device call for all members: the raw lanelet polygons in
+// c->lan_*, and the bounded sets in c->bound_* taken over as the parallel predecessors' obstacles
+void lanelet_polygons(pdmpc_controller* c) {
+    const int n = c->n;
     c->lan_off.assign((size_t)n + 1, 0);
     c->lan_x.clear();
     c->lan_y.clear();
@@ -1092,15 +1094,9 @@ int bound_by_lanelets(pdmpc_controller* c, bool all_steps) {
     }
     c->lan_x.push_back(0.0);  // (never empty)
     c->lan_y.push_back(0.0);
-    const pdmpc_polygon_set lan = view_polygons(c->lan_off, c->lan_x, c->lan_y);
-    c->bound_off.assign((size_t)n * (all_steps ? Hp : 1) + 1, 0);
-    int rc = bound_sets(c, lan, all_steps, (int32_t)c->bound_x.size(), c->bound_x.empty() ? nullptr : c->bound_x.data(), c->bound_y.empty() ? nullptr : c->bound_y.data());
-    if (rc == PDMPC_ERR_CAPACITY && c->bound_off.back() > (int32_t)c->bound_x.size()) {
-        c->bound_x.resize((size_t)c->bound_off.back());
-        c->bound_y.resize((size_t)c->bound_off.back());
-        rc = bound_sets(c, lan, all_steps, (int32_t)c->bound_x.size(), c->bound_x.data(), c->bound_y.data());
-    }
-    if (rc) return cfail(c, rc, std::string("pdmpc_bound_reachable_sets: ") + (c->h ? pdmpc_last_error() : "host twin failed"));
+}
+void adopt_bounded_sets(pdmpc_controller* c, bool all_steps) {
+    const int n = c->n, Hp = c->Hp;
     if (all_steps) {  // the parallel predecessors' obstacles are the bounded sets
         for (int v = 0; v < n; ++v)
             for (int q = 0; q < Hp; ++q) {
@@ -1110,12 +1106,28 @@ int bound_by_lanelets(pdmpc_controller* c, bool all_steps) {
                 P.y.assign(c->bound_y.begin() + a, c->bound_y.begin() + a + m);
             }
     }
+}
+int bound_by_lanelets(pdmpc_controller* c, bool all_steps) {
+    const int n = c->n, Hp = c->Hp;
+    lanelet_polygons(c);
+    const pdmpc_polygon_set lan = view_polygons(c->lan_off, c->lan_x, c->lan_y);
+    c->bound_off.assign((size_t)n * (all_steps ? Hp : 1) + 1, 0);
+    int rc = bound_sets(c, lan, all_steps, (int32_t)c->bound_x.size(), c->bound_x.empty() ? nullptr : c->bound_x.data(), c->bound_y.empty() ? nullptr : c->bound_y.data());
+    if (rc == PDMPC_ERR_CAPACITY && c->bound_off.back() > (int32_t)c->bound_x.size()) {
+        c->bound_x.resize((size_t)c->bound_off.back());
+        c->bound_y.resize((size_t)c->bound_off.back());
+        rc = bound_sets(c, lan, all_steps, (int32_t)c->bound_x.size(), c->bound_x.data(), c->bound_y.data());
+    }
+    if (rc) return cfail(c, rc, std::string("pdmpc_bound_reachable_sets: ") + (c->h ? pdmpc_last_error() : "host twin failed"));
+    adopt_bounded_sets(c, all_steps);
     return PDMPC_OK;
 }
 
 // c->adjacency by the configured rule (reachable sets: the bounded ones, bounded_S per vehicle, when the step bounded them)
-int couple(pdmpc_controller* c, int bounded_S) {
+int couple(pdmpc_controller* c, int bounded_S, bool reachable_given = false) {
     const int n = c->n;
+    // (reachable_given: the sweep's grouped call has written the member's block into c->adjacency already)
+    if (c->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET && reachable_given) return PDMPC_OK;
     c->adjacency.assign((size_t)n * n, 0);
     if (c->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET) return bounded_S ? couple_bounded_sets(c, bounded_S) : couple_reachable_sets(c);
     if (c->cfg.coupling == PDMPC_COUPLING_FULL) {
@@ -1167,8 +1179,14 @@ int direct_by_priorities(pdmpc_controller* c) {
 }
 }  // namespace
 
-int pdmpc_controller_build_step(pdmpc_controller* c) {
-    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
+namespace {
+// pdmpc_controller_build_step in three parts, so that a sweep can run the middle one -- the step preparation on the device -- once for
+// all its members: what the step reads of the reachable sets ...
+struct StepPrep {
+    bool reach_parallel = false, reach = false, bounded = false;
+};
+// ... everything before the step preparation (advances the time step),
+int begin_step(pdmpc_controller* c, StepPrep& P) {
     const int n = c->n;
     const bool reach_parallel = c->parallel_mode == PDMPC_PARALLEL_REACHABLE_SETS;
     const bool reach = c->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET || reach_parallel;  // a feature reads the reachable sets
@@ -1192,13 +1210,29 @@ int pdmpc_controller_build_step(pdmpc_controller* c) {
     bool bounded = false;  // (not on scenarios without lanelets)
     if (reach && c->lanelet_bounding)
         for (int v = 0; v < n && !bounded; ++v) bounded = !c->veh[v].lanelets_index.empty();
-    int rc = bounded ? bound_by_lanelets(c, reach_parallel) : PDMPC_OK;
-    if (!rc) rc = couple(c, bounded ? (reach_parallel ? c->Hp : 1) : 0);
-    if (!rc) rc = direct_by_priorities(c);
+    P.reach_parallel = reach_parallel;
+    P.reach = reach;
+    P.bounded = bounded;
+    return PDMPC_OK;
+}
+// ... and everything after it
+int finish_step(pdmpc_controller* c) {
+    int rc = direct_by_priorities(c);
     if (!rc) rc = assemble_step(c);
     if (rc) return rc;
     set_seeds(c, c->order);
     return PDMPC_OK;
+}
+}  // namespace
+
+int pdmpc_controller_build_step(pdmpc_controller* c) {
+    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
+    StepPrep P;
+    int rc = begin_step(c, P);
+    if (!rc && P.bounded) rc = bound_by_lanelets(c, P.reach_parallel);
+    if (!rc) rc = couple(c, P.bounded ? (P.reach_parallel ? c->Hp : 1) : 0);
+    if (!rc) rc = finish_step(c);
+    return rc;
 }
 
 
@@ -2142,5 +2176,384 @@ int pdmpc_controller_optimal_result(pdmpc_controller* c, int32_t* chosen, int32_
 }
 
 const pdmpc_vehicle_out* pdmpc_controller_records(pdmpc_controller* c) { return c && !c->out.empty() ? c->out.data() : nullptr; }
+
+}  // extern "C"
+
+// ---- several closed loops in lock-step: the members' own build / apply code around ONE step preparation on the
+// device and ONE pdmpc_plan_step for all of them.  Sweep slots are the members' problems one after the other, each in its own slot order.
+struct pdmpc_sweep {
+    pdmpc_handle* h = nullptr;
+    std::vector<pdmpc_controller*> members;
+    std::vector<int32_t> first;  // [M + 1] member m's first sweep slot (= its first vehicle among the concatenated vehicles)
+    bool broken = false;         // a step failed half way: the members have advanced unevenly
+    bool built = false;
+    double timing[6] = {0, 0, 0, 0, 0, 0};
+    std::vector<StepPrep> prep;
+    // the concatenated problem
+    std::vector<pdmpc_vehicle_in> in;
+    std::vector<pdmpc_polygon_set> fb;
+    std::vector<int32_t> pred_offset, pred_index, member, member_slot;
+    std::vector<uint32_t> seeds;
+    std::vector<double> weights;
+    std::vector<pdmpc_vehicle_out> out;
+    // one grouped step-preparation call: the vehicles of the members that take part, member after member
+    struct Call {
+        std::vector<int> who;                // members
+        std::vector<int32_t> group_offset;   // [who.size() + 1]
+        std::vector<double> x, y, cos_yaw, sin_yaw;
+        std::vector<int32_t> trim, lan_off, set_off;
+        std::vector<double> lan_x, lan_y, set_x, set_y;
+        std::vector<uint8_t> adjacency;      // the blocks
+    } call;
+};
+
+namespace {
+int N_of(const pdmpc_sweep* s) { return s->first.back(); }
+
+// the poses of the members `who` one after the other (and their lanelet polygons: with_lanelets)
+void gather(pdmpc_sweep* s, const std::vector<int>& who, bool with_lanelets) {
+    pdmpc_sweep::Call& C = s->call;
+    C.who = who;
+    C.group_offset.assign(1, 0);
+    C.x.clear();
+    C.y.clear();
+    C.cos_yaw.clear();
+    C.sin_yaw.clear();
+    C.trim.clear();
+    C.lan_off.assign(1, 0);
+    C.lan_x.clear();
+    C.lan_y.clear();
+    for (int m : who) {
+        pdmpc_controller* c = s->members[(size_t)m];
+        C.x.insert(C.x.end(), c->mx.begin(), c->mx.end());
+        C.y.insert(C.y.end(), c->my.begin(), c->my.end());
+        C.cos_yaw.insert(C.cos_yaw.end(), c->reach_cos.begin(), c->reach_cos.end());
+        C.sin_yaw.insert(C.sin_yaw.end(), c->reach_sin.begin(), c->reach_sin.end());
+        C.trim.insert(C.trim.end(), c->trims.begin(), c->trims.end());
+        C.group_offset.push_back((int32_t)C.x.size());
+        if (with_lanelets) {
+            lanelet_polygons(c);
+            const int32_t base = (int32_t)C.lan_x.size(), nl = c->lan_off[(size_t)c->n];
+            C.lan_x.insert(C.lan_x.end(), c->lan_x.begin(), c->lan_x.begin() + nl);
+            C.lan_y.insert(C.lan_y.end(), c->lan_y.begin(), c->lan_y.begin() + nl);
+            for (int v = 0; v < c->n; ++v) C.lan_off.push_back(base + c->lan_off[(size_t)v + 1]);
+        }
+    }
+    C.lan_x.push_back(0.0);  // (never empty)
+    C.lan_y.push_back(0.0);
+    size_t entries = 0;
+    for (size_t g = 0; g + 1 < C.group_offset.size(); ++g) entries += (size_t)(C.group_offset[g + 1] - C.group_offset[g]) * (C.group_offset[g + 1] - C.group_offset[g]);
+    C.adjacency.assign(entries + 1, 0);
+}
+// the blocks of a grouped coupler call -> c->adjacency of the members that couple by reachable sets
+void scatter_blocks(pdmpc_sweep* s) {
+    const pdmpc_sweep::Call& C = s->call;
+    size_t block = 0;
+    for (int m : C.who) {
+        pdmpc_controller* c = s->members[(size_t)m];
+        const size_t nn = (size_t)c->n * c->n;
+        if (c->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET) c->adjacency.assign(C.adjacency.begin() + block, C.adjacency.begin() + block + nn);
+        block += nn;
+    }
+}
+bool any_couples_by_sets(const pdmpc_sweep* s, const std::vector<int>& who) {
+    for (int m : who)
+        if (s->members[(size_t)m]->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET) return true;
+    return false;
+}
+
+// lanelet bounding of the members `who` (one all_steps for all of them) in ONE device call on the concatenated vehicles, then the
+// coupler on the bounded step-Hp sets, grouped by member
+int sweep_bound_on_device(pdmpc_sweep* s, const std::vector<int>& who, bool all_steps) {
+    if (who.empty()) return PDMPC_OK;
+    pdmpc_sweep::Call& C = s->call;
+    gather(s, who, true);
+    const int Hp = s->members[0]->Hp, S = all_steps ? Hp : 1, n = C.group_offset.back();
+    const pdmpc_polygon_set lan = view_polygons(C.lan_off, C.lan_x, C.lan_y);
+    C.set_off.assign((size_t)n * S + 1, 0);
+    auto bound = [&]() {
+        return pdmpc_bound_reachable_sets(s->h, n, C.x.data(), C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(), C.trim.data(), &lan, all_steps, (int32_t)C.set_x.size(),
+                                          C.set_off.data(), C.set_x.empty() ? nullptr : C.set_x.data(), C.set_y.empty() ? nullptr : C.set_y.data(), nullptr);
+    };
+    int rc = bound();
+    if (rc == PDMPC_ERR_CAPACITY && C.set_off.back() > (int32_t)C.set_x.size()) {
+        C.set_x.resize((size_t)C.set_off.back());
+        C.set_y.resize((size_t)C.set_off.back());
+        rc = bound();
+    }
+    if (rc) return cfail(nullptr, rc, std::string("pdmpc_bound_reachable_sets: ") + pdmpc_last_error());
+    for (size_t g = 0; g < who.size(); ++g) {  // every member's own sets, offsets from 0, as its own bounding call leaves them
+        pdmpc_controller* c = s->members[(size_t)who[g]];
+        const size_t o0 = (size_t)C.group_offset[g] * S, sets = (size_t)c->n * S;
+        const int32_t a = C.set_off[o0], total = C.set_off[o0 + sets] - a;
+        c->bound_off.resize(sets + 1);
+        for (size_t o = 0; o <= sets; ++o) c->bound_off[o] = C.set_off[o0 + o] - a;
+        if (c->bound_x.size() < (size_t)total) {
+            c->bound_x.resize((size_t)total);
+            c->bound_y.resize((size_t)total);
+        }
+        std::copy(C.set_x.begin() + a, C.set_x.begin() + a + total, c->bound_x.begin());
+        std::copy(C.set_y.begin() + a, C.set_y.begin() + a + total, c->bound_y.begin());
+        adopt_bounded_sets(c, all_steps);
+    }
+    if (!any_couples_by_sets(s, who)) return PDMPC_OK;
+    rc = pdmpc_bounded_set_coupling_grouped(s->h, (int32_t)who.size(), C.group_offset.data(), C.adjacency.data(), nullptr);
+    if (rc) return cfail(nullptr, rc, std::string("pdmpc_bounded_set_coupling_grouped: ") + pdmpc_last_error());
+    scatter_blocks(s);
+    return PDMPC_OK;
+}
+// ... without a handle: every member's own bounding on the host twin, then the grouped host twin on the members' step-Hp sets
+int sweep_bound_on_host(pdmpc_sweep* s, const std::vector<int>& who) {
+    if (who.empty()) return PDMPC_OK;
+    pdmpc_sweep::Call& C = s->call;
+    for (int m : who) {
+        pdmpc_controller* c = s->members[(size_t)m];
+        if (const int rc = bound_by_lanelets(c, s->prep[(size_t)m].reach_parallel)) return rc;
+    }
+    if (!any_couples_by_sets(s, who)) return PDMPC_OK;
+    gather(s, who, false);
+    C.set_off.assign(1, 0);
+    C.set_x.clear();
+    C.set_y.clear();
+    for (int m : who) {
+        pdmpc_controller* c = s->members[(size_t)m];
+        const int S = s->prep[(size_t)m].reach_parallel ? c->Hp : 1;
+        for (int v = 0; v < c->n; ++v) {
+            const int o = v * S + S - 1, a = c->bound_off[o], cnt = c->bound_off[o + 1] - a;
+            C.set_x.insert(C.set_x.end(), c->bound_x.begin() + a, c->bound_x.begin() + a + cnt);
+            C.set_y.insert(C.set_y.end(), c->bound_y.begin() + a, c->bound_y.begin() + a + cnt);
+            C.set_off.push_back((int32_t)C.set_x.size());
+        }
+    }
+    C.set_x.push_back(0.0);
+    C.set_y.push_back(0.0);
+    const pdmpc_polygon_set ps = view_polygons(C.set_off, C.set_x, C.set_y);
+    const int rc = pdmpc_polygon_set_coupling_grouped_host(&ps, (int32_t)who.size(), C.group_offset.data(), C.adjacency.data(), nullptr);
+    if (rc) return cfail(nullptr, rc, "pdmpc_polygon_set_coupling_grouped_host failed");
+    scatter_blocks(s);
+    return PDMPC_OK;
+}
+// the coupler on the unbounded step-Hp hulls of the members `who`, grouped by member.  With a handle the members share its table of
+// local hulls (as they share its automaton); without one, members that hold the same table share a call of the grouped host twin.
+int sweep_couple_hulls(pdmpc_sweep* s, const std::vector<int>& who) {
+    if (who.empty()) return PDMPC_OK;
+    pdmpc_sweep::Call& C = s->call;
+    if (s->h) {
+        gather(s, who, false);
+        const int rc = pdmpc_reachable_set_coupling_grouped(s->h, (int32_t)who.size(), C.group_offset.data(), C.x.data(), C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(),
+                                                            C.trim.data(), C.adjacency.data(), nullptr);
+        if (rc) return cfail(nullptr, rc, std::string("pdmpc_reachable_set_coupling_grouped: ") + pdmpc_last_error());
+        scatter_blocks(s);
+        return PDMPC_OK;
+    }
+    std::vector<int> rest = who, same, other;
+    while (!rest.empty()) {
+        const pdmpc_controller* c0 = s->members[(size_t)rest[0]];
+        same.clear();
+        other.clear();
+        for (int m : rest) {
+            const pdmpc_controller* c = s->members[(size_t)m];
+            (c->reach_off == c0->reach_off && c->reach_x == c0->reach_x && c->reach_y == c0->reach_y ? same : other).push_back(m);
+        }
+        gather(s, same, false);
+        const pdmpc_polygon_set ps = view_polygons(c0->reach_off, c0->reach_x, c0->reach_y);
+        const int rc = pdmpc_reachable_set_coupling_grouped_host((int32_t)c0->trim_speed.size(), c0->Hp, &ps, (int32_t)same.size(), C.group_offset.data(), C.x.data(),
+                                                                 C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(), C.trim.data(), C.adjacency.data(), nullptr);
+        if (rc) return cfail(nullptr, rc, "pdmpc_reachable_set_coupling_grouped_host failed");
+        scatter_blocks(s);
+        rest = other;
+    }
+    return PDMPC_OK;
+}
+
+int sweep_build(pdmpc_sweep* s) {
+    const size_t M = s->members.size();
+    s->prep.assign(M, StepPrep());
+    for (size_t m = 0; m < M; ++m)
+        if (const int rc = begin_step(s->members[m], s->prep[m])) return rc;
+    // who takes part in which grouped call: bounded (step Hp only / every step: one bounding call each) or the plain hulls
+    std::vector<int> bounded_last, bounded_all, hulls;
+    for (size_t m = 0; m < M; ++m) {
+        const StepPrep& P = s->prep[m];
+        if (P.bounded)
+            (P.reach_parallel ? bounded_all : bounded_last).push_back((int)m);
+        else if (s->members[m]->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET)
+            hulls.push_back((int)m);
+    }
+    int rc = PDMPC_OK;
+    if (s->h) {
+        rc = sweep_bound_on_device(s, bounded_last, false);
+        if (!rc) rc = sweep_bound_on_device(s, bounded_all, true);
+    } else {
+        bounded_last.insert(bounded_last.end(), bounded_all.begin(), bounded_all.end());
+        std::sort(bounded_last.begin(), bounded_last.end());
+        rc = sweep_bound_on_host(s, bounded_last);
+    }
+    if (!rc) rc = sweep_couple_hulls(s, hulls);
+    if (rc) return rc;
+    for (size_t m = 0; m < M; ++m) {
+        pdmpc_controller* c = s->members[m];
+        const StepPrep& P = s->prep[m];
+        rc = couple(c, P.bounded ? (P.reach_parallel ? c->Hp : 1) : 0, true);
+        if (!rc) rc = finish_step(c);
+        if (rc) return rc;
+    }
+    // the concatenated problem: shallow copies, predecessor slots shifted by the member's first slot
+    const int N = N_of(s);
+    s->in.resize((size_t)N);
+    s->fb.resize((size_t)N);
+    s->member.resize((size_t)N);
+    s->member_slot.resize((size_t)N);
+    s->seeds.resize((size_t)N);
+    s->pred_offset.assign((size_t)N + 1, 0);
+    s->pred_index.clear();
+    for (size_t m = 0; m < M; ++m) {
+        const pdmpc_controller* c = s->members[m];
+        const int f = s->first[m];
+        for (int q = 0; q < c->n; ++q) {
+            s->in[(size_t)f + q] = c->in[(size_t)q];
+            s->fb[(size_t)f + q] = c->fb[(size_t)q];
+            s->member[(size_t)f + q] = (int32_t)m;
+            s->member_slot[(size_t)f + q] = q;
+            s->seeds[(size_t)f + q] = c->seeds[(size_t)q];
+            for (int e = c->pred_offset[(size_t)q]; e < c->pred_offset[(size_t)q + 1]; ++e) s->pred_index.push_back(f + c->pred_index[(size_t)e]);
+            s->pred_offset[(size_t)f + q + 1] = (int32_t)s->pred_index.size();
+        }
+    }
+    s->pred_index.push_back(0);
+    s->built = true;
+    return PDMPC_OK;
+}
+
+int sweep_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records, bool keep_records) {
+    for (size_t m = 0; m < s->members.size(); ++m) {
+        pdmpc_controller* c = s->members[m];
+        const pdmpc_vehicle_out* r = records + s->first[m];
+        if (keep_records) {  // (pdmpc_controller_records: the member's own records, in its own slot order)
+            c->out.assign(r, r + c->n);
+            r = c->out.data();
+        }
+        if (const int rc = pdmpc_controller_apply(c, r)) return rc;
+    }
+    return PDMPC_OK;
+}
+
+// a failed step leaves the members unevenly advanced: nothing more is stepped
+int sweep_guard(pdmpc_sweep* s, int rc) {
+    if (rc) s->broken = true;
+    return rc;
+}
+}  // namespace
+
+extern "C" {
+
+int pdmpc_sweep_create(pdmpc_handle* h, int32_t n_members, pdmpc_controller* const* members, pdmpc_sweep** out) {
+    if (!out || n_members < 1 || !members) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_create: bad argument");
+    *out = nullptr;
+    int64_t total = 0;
+    for (int m = 0; m < n_members; ++m) {
+        const pdmpc_controller* c = members[m];
+        if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_create: null member");
+        if (c->h != h) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_create: a member was not created on the sweep's handle");
+        if (c->Hp != members[0]->Hp) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_create: the members differ in Hp");
+        if (c->optimizer != members[0]->optimizer) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_create: the members select different optimizers");
+        for (int q = 0; q < m; ++q)
+            if (members[q] == c) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_create: a member is listed twice");
+        total += c->n;
+    }
+    if (h) {
+        pdmpc_config hc{};
+        int32_t has_mpa = 0;
+        if (pdmpc_get_config(h, &hc, &has_mpa) != PDMPC_OK) return cfail(nullptr, PDMPC_ERR_INVALID, "bad backend handle");
+        if (total > hc.max_vehicles) return cfail(nullptr, PDMPC_ERR_CAPACITY, "pdmpc_sweep_create: the members have more vehicles than the handle's max_vehicles");
+    }
+    pdmpc_sweep* s = new pdmpc_sweep();
+    s->h = h;
+    s->members.assign(members, members + n_members);
+    s->first.assign(1, 0);
+    for (int m = 0; m < n_members; ++m) s->first.push_back(s->first.back() + members[m]->n);
+    *out = s;
+    return PDMPC_OK;
+}
+
+int pdmpc_sweep_destroy(pdmpc_sweep* s) {
+    delete s;
+    return PDMPC_OK;
+}
+
+int pdmpc_sweep_build(pdmpc_sweep* s) {
+    if (!s) return cfail(nullptr, PDMPC_ERR_INVALID, "null sweep");
+    if (s->broken) return cfail(nullptr, PDMPC_ERR_INVALID, "an earlier step of the sweep failed: its members have advanced unevenly");
+    return sweep_guard(s, sweep_build(s));
+}
+
+int pdmpc_sweep_problem(pdmpc_sweep* s, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index,
+                        const pdmpc_polygon_set** fallback, const int32_t** member, const int32_t** member_slot) {
+    if (!s || !s->built) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_problem before pdmpc_sweep_build");
+    if (n_slots) *n_slots = N_of(s);
+    if (in) *in = s->in.data();
+    if (pred_offset) *pred_offset = s->pred_offset.data();
+    if (pred_index) *pred_index = s->pred_index.data();
+    if (fallback) *fallback = s->fb.data();
+    if (member) *member = s->member.data();
+    if (member_slot) *member_slot = s->member_slot.data();
+    return PDMPC_OK;
+}
+
+int pdmpc_sweep_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records) {
+    if (!s || !records) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
+    if (s->broken) return cfail(nullptr, PDMPC_ERR_INVALID, "an earlier step of the sweep failed: its members have advanced unevenly");
+    if (!s->built) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_apply before pdmpc_sweep_build");
+    return sweep_guard(s, sweep_apply(s, records, false));
+}
+
+int pdmpc_sweep_step(pdmpc_sweep* s) {
+    if (!s || !s->h) return cfail(nullptr, PDMPC_ERR_INVALID, "the sweep has no backend handle");
+    if (s->broken) return cfail(nullptr, PDMPC_ERR_INVALID, "an earlier step of the sweep failed: its members have advanced unevenly");
+    auto t = std::chrono::steady_clock::now();
+    int rc = sweep_build(s);
+    if (rc) return sweep_guard(s, rc);
+    s->timing[0] = ms_since(t);
+    s->timing[4] = 0;
+    const int N = N_of(s);
+    s->out.resize((size_t)N);
+    // the work of the last step as the expected work of this one, as pdmpc_controller_step hands it over (a member's first step: 1 each)
+    s->weights.assign((size_t)N, 1.0);
+    for (size_t m = 0; m < s->members.size(); ++m) {
+        const pdmpc_controller* c = s->members[m];
+        if (c->last_pops.size() != (size_t)c->n) continue;
+        for (int q = 0; q < c->n; ++q) s->weights[(size_t)s->first[m] + q] = c->last_pops[(size_t)c->order[(size_t)q]] + 1.0;
+    }
+    (void)pdmpc_set_step_weights(s->h, N, s->weights.data());
+    if (s->members[0]->optimizer == PDMPC_OPTIMIZER_SAMPLED) {
+        rc = pdmpc_set_step_seeds(s->h, N, s->seeds.data());
+        if (rc) return sweep_guard(s, cfail(nullptr, rc, pdmpc_last_error()));
+    }
+    rc = pdmpc_plan_step(s->h, N, s->in.data(), s->pred_offset.data(), s->pred_index.data(), s->fb.data(), s->out.data());
+    if (rc) return sweep_guard(s, cfail(nullptr, rc, pdmpc_last_error()));
+    double us[3] = {0, 0, 0};
+    if (pdmpc_last_call_timing(s->h, us) == PDMPC_OK)
+        for (int i = 0; i < 3; ++i) s->timing[1 + i] = us[i] * 1e-3;
+    t = std::chrono::steady_clock::now();
+    rc = sweep_apply(s, s->out.data(), true);
+    s->timing[5] = ms_since(t);
+    return sweep_guard(s, rc);
+}
+
+int pdmpc_sweep_run(pdmpc_sweep* s, int32_t n_steps, double* ms) {
+    for (int i = 0; i < n_steps; ++i) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const int rc = pdmpc_sweep_step(s);
+        if (rc) return rc;
+        if (ms) ms[i] = ms_since(t0);
+    }
+    return PDMPC_OK;
+}
+
+int pdmpc_sweep_last_timing(pdmpc_sweep* s, double* ms6) {
+    if (!s || !ms6) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
+    for (int i = 0; i < 6; ++i) ms6[i] = s->timing[i];
+    return PDMPC_OK;
+}
 
 }  // extern "C"

@@ -46,7 +46,7 @@ int timed_launch(pdmpc_handle* h, TimedLaunch& t, int (*launch)(const Args*, voi
     return PDMPC_OK;
 }
 
-// what a coupler writes: adjacency [n x n] (8-aligned), then areas [n x n]
+// what a coupler writes: adjacency [n x n] (8-aligned), then areas [n x n]; a grouped call fills the first sum n_g^2 entries of both
 struct PairOut {
     size_t adj, area;
 };
@@ -56,15 +56,36 @@ PairOut carve_pair_out(Carver& c, int n) {
     o.area = c.take<double>((size_t)n * n);
     return o;
 }
-// ... read back through `pinned` (the areas only when asked for) after t's launch; synchronises the stream
-int fetch_pair_out(pdmpc_handle* h, TimedLaunch& t, const unsigned char* dev, unsigned char* pinned, const PairOut& o, int n, uint8_t* adjacency, double* area) {
-    const size_t nn = (size_t)n * n, bytes = area ? o.area - o.adj + nn * sizeof(double) : nn;
+// ... read back through `pinned` (nn entries; the areas only when asked for) after t's launch; synchronises the stream
+int fetch_pair_out(pdmpc_handle* h, TimedLaunch& t, const unsigned char* dev, unsigned char* pinned, const PairOut& o, size_t nn, uint8_t* adjacency, double* area) {
+    const size_t bytes = area ? o.area - o.adj + nn * sizeof(double) : nn;
     HIPCHK(hipMemcpyAsync(pinned, dev + o.adj, bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(sync_stream(h));
     t.fold();
     std::memcpy(adjacency, pinned, nn);
     if (area) std::memcpy(area, pinned + (o.area - o.adj), nn * sizeof(double));
     return PDMPC_OK;
+}
+
+// The groups of a grouped coupler call as the kernels read them: one PairGroup per vehicle.  Returns the number of result entries
+// (sum n_g^2) and the largest group, or an error for offsets that do not start at 0 or decrease.
+int check_groups(const char* who, int32_t n_groups, const int32_t* group_offset, int* n_out) {
+    if (n_groups < 0 || !group_offset || group_offset[0] != 0) return fail(PDMPC_ERR_INVALID, std::string(who) + ": bad groups");
+    for (int g = 0; g < n_groups; ++g)
+        if (group_offset[g + 1] < group_offset[g]) return fail(PDMPC_ERR_INVALID, std::string(who) + ": group offsets decrease");
+    *n_out = group_offset[n_groups];
+    return PDMPC_OK;
+}
+size_t stage_groups(PairGroup* pg, int32_t n_groups, const int32_t* group_offset, int* max_group) {
+    size_t block = 0;
+    *max_group = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const int a = group_offset[g], b = group_offset[g + 1];
+        for (int v = a; v < b; ++v) pg[v] = PairGroup{a, b, (int32_t)block};
+        block += (size_t)(b - a) * (b - a);
+        *max_group = std::max(*max_group, b - a);
+    }
+    return block;
 }
 
 }  // namespace
@@ -132,7 +153,7 @@ namespace {
 // ReachState::ws and its pinned staging for n vehicles (carved the same way at upload, for max_vehicles, and per call): the inputs are
 // the block's first in_bytes, the coupler's output its last
 struct ReachLayout {
-    size_t in, trim, in_bytes, hull_x, hull_y, box, hull_n, total;
+    size_t in, trim, group, in_bytes, hull_x, hull_y, box, hull_n, total;
     PairOut out;
 };
 ReachLayout reach_layout(int n, int cols) {
@@ -140,6 +161,7 @@ ReachLayout reach_layout(int n, int cols) {
     ReachLayout L;
     L.in = c.take<double>((size_t)4 * n);
     L.trim = c.take<int32_t>((size_t)n);
+    L.group = c.take<int32_t>((size_t)3 * n);  // (PairGroup per vehicle: the grouped call's)
     L.in_bytes = c.end8();
     L.hull_x = c.take<double>((size_t)n * cols);
     L.hull_y = c.take<double>((size_t)n * cols);
@@ -205,21 +227,34 @@ int pdmpc_upload_reachable_sets(pdmpc_handle* h, int32_t n_trims, int32_t Hp, co
     return PDMPC_OK;
 }
 
-int pdmpc_reachable_set_coupling(pdmpc_handle* h, int32_t n, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw, const int32_t* trim,
-                                 uint8_t* adjacency, double* area) {
+namespace {
+// pdmpc_reachable_set_coupling (group_offset == NULL) and its grouped sibling: one staging copy, the pose pass over all n vehicles, one
+// pair pass, one copy back, one synchronisation -- whatever the number of groups
+int reachable_coupling(pdmpc_handle* h, const char* who, int32_t n_groups, const int32_t* group_offset, int32_t n, const double* x, const double* y,
+                       const double* cos_yaw, const double* sin_yaw, const int32_t* trim, uint8_t* adjacency, double* area) {
+    const std::string w(who);
     if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
     ReachState& R = h->reach;
-    if (!R.valid) return fail(PDMPC_ERR_INVALID, "pdmpc_reachable_set_coupling before pdmpc_upload_reachable_sets");
-    if (n < 0 || !adjacency || (n > 0 && (!x || !y || !cos_yaw || !sin_yaw || !trim))) return fail(PDMPC_ERR_INVALID, "pdmpc_reachable_set_coupling: bad argument");
-    if (n > h->max_vehicles) return fail(PDMPC_ERR_CAPACITY, "pdmpc_reachable_set_coupling: more vehicles than config.max_vehicles");
+    if (!R.valid) return fail(PDMPC_ERR_INVALID, w + " before pdmpc_upload_reachable_sets");
+    if (group_offset)
+        if (const int rc = check_groups(who, n_groups, group_offset, &n)) return rc;
+    if (n < 0 || !adjacency || (n > 0 && (!x || !y || !cos_yaw || !sin_yaw || !trim))) return fail(PDMPC_ERR_INVALID, w + ": bad argument");
+    if (n > h->max_vehicles) return fail(PDMPC_ERR_CAPACITY, w + ": more vehicles than config.max_vehicles");
     if (n == 0) return PDMPC_OK;
     for (int v = 0; v < n; ++v)
-        if (trim[v] < 1 || trim[v] > R.trims) return fail(PDMPC_ERR_INVALID, "pdmpc_reachable_set_coupling: trim out of range");
+        if (trim[v] < 1 || trim[v] > R.trims) return fail(PDMPC_ERR_INVALID, w + ": trim out of range");
     ON_DEVICE(h->cfg.device);
     const ReachLayout L = reach_layout(n, R.cols);
     unsigned char *hin = R.h_in.p, *ws = R.ws.p;
     stage_poses((double*)(hin + L.in), (size_t)n, x, y, cos_yaw, sin_yaw, (int32_t*)(hin + L.trim), trim);
     ReachArgs A;
+    A.group = nullptr;
+    A.max_group = n;
+    size_t entries = (size_t)n * n;
+    if (group_offset) {
+        entries = stage_groups((PairGroup*)(hin + L.group), n_groups, group_offset, &A.max_group);
+        A.group = (const int32_t*)(ws + L.group);
+    }
     A.n = n;
     A.max_cols = R.cols;
     A.local_x = R.local.p;
@@ -234,8 +269,21 @@ int pdmpc_reachable_set_coupling(pdmpc_handle* h, int32_t n, const double* x, co
     A.adjacency = (uint8_t*)(ws + L.out.adj);
     A.area = (double*)(ws + L.out.area);
     HIPCHK(hipMemcpyAsync(ws, hin, L.in_bytes, hipMemcpyHostToDevice, h->stream));
-    if (const int rc = timed_launch(h, R.coupling, pdmpc_launch_reachable_coupling, A, "reachable-set coupling")) return rc;
-    return fetch_pair_out(h, R.coupling, ws, R.h_out.p, L.out, n, adjacency, area);
+    if (const int rc = timed_launch(h, R.coupling, group_offset ? pdmpc_launch_reachable_coupling_grouped : pdmpc_launch_reachable_coupling, A, "reachable-set coupling"))
+        return rc;
+    return fetch_pair_out(h, R.coupling, ws, R.h_out.p, L.out, entries, adjacency, area);
+}
+}  // namespace
+
+int pdmpc_reachable_set_coupling(pdmpc_handle* h, int32_t n, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw, const int32_t* trim,
+                                 uint8_t* adjacency, double* area) {
+    return reachable_coupling(h, "pdmpc_reachable_set_coupling", 0, nullptr, n, x, y, cos_yaw, sin_yaw, trim, adjacency, area);
+}
+
+int pdmpc_reachable_set_coupling_grouped(pdmpc_handle* h, int32_t n_groups, const int32_t* group_offset, const double* x, const double* y, const double* cos_yaw,
+                                         const double* sin_yaw, const int32_t* trim, uint8_t* adjacency, double* area) {
+    if (!group_offset) return fail(PDMPC_ERR_INVALID, "pdmpc_reachable_set_coupling_grouped: null group offsets");
+    return reachable_coupling(h, "pdmpc_reachable_set_coupling_grouped", n_groups, group_offset, 0, x, y, cos_yaw, sin_yaw, trim, adjacency, area);
 }
 
 int pdmpc_reachable_set_coupling_kernel_ms(pdmpc_handle* h, double* ms) {
@@ -248,7 +296,7 @@ int pdmpc_reachable_set_coupling_kernel_ms(pdmpc_handle* h, double* ms) {
 namespace {
 // BoundState::in and its pinned staging (the lanelet polygons: x of all n_lan vertices, then y), and BoundState::out
 struct BoundLayout {
-    size_t in, trim, lan_off, lan_xy, in_bytes, out_bytes;
+    size_t in, trim, lan_off, lan_xy, in_bytes, group, in_total, out_bytes;
     PairOut out;
 };
 BoundLayout bound_layout(int n, int n_lan) {
@@ -259,6 +307,8 @@ BoundLayout bound_layout(int n, int n_lan) {
     L.lan_off = c.take<int32_t>((size_t)n + 1);
     L.lan_xy = c.take<double>((size_t)2 * n_lan);
     L.in_bytes = c.at;
+    L.group = c.take<int32_t>((size_t)3 * n);  // (PairGroup per vehicle: staged by the grouped coupler, after the bounding call's inputs)
+    L.in_total = c.at;
     Carver o;
     L.out = carve_pair_out(o, n);
     L.out_bytes = o.at;
@@ -291,6 +341,8 @@ BoundArgs bound_args(pdmpc_handle* h, int n, int S, int n_lan) {
     A.area = (double*)(B.out.p + L.out.area);
     A.pairs = B.pairs.p;
     A.n_pairs = B.pairs.p + (n > 1 ? (size_t)n * (n - 1) / 2 : 0);
+    A.group = (const int32_t*)(B.in.p + L.group);
+    A.max_group = n;
     return A;
 }
 }  // namespace
@@ -325,8 +377,8 @@ int pdmpc_bound_reachable_sets(pdmpc_handle* h, int32_t n, const double* x, cons
     const BoundLayout L = bound_layout(n, n_lan);
     const size_t sets = (size_t)n * S, max_pairs = (size_t)n * (n - 1) / 2;
     // (the pinned output block serves this call's vertex counts and flags and the coupler's output)
-    if (B.in.ensure(L.in_bytes) || B.sets.ensure(2 * sets * PDMPC_BOUND_SLOT) || B.set_n.ensure(sets) || B.flags.ensure(sets) || B.box.ensure((size_t)4 * n) ||
-        B.out.ensure(L.out_bytes) || B.pairs.ensure(max_pairs + 1) || B.h_in.ensure(L.in_bytes) || B.h_out.ensure(L.out_bytes + sets * (sizeof(int32_t) + 1)))
+    if (B.in.ensure(L.in_total) || B.sets.ensure(2 * sets * PDMPC_BOUND_SLOT) || B.set_n.ensure(sets) || B.flags.ensure(sets) || B.box.ensure((size_t)4 * n) ||
+        B.out.ensure(L.out_bytes) || B.pairs.ensure(max_pairs + 1) || B.h_in.ensure(L.in_total) || B.h_out.ensure(L.out_bytes + sets * (sizeof(int32_t) + 1)))
         return fail(PDMPC_ERR_HIP, "hipMalloc failed for the lanelet bounding");
     // inputs: poses, 0-based trims, the normalized lanelet polygons (pdmpc_lanelet_polygon_normalize, as the host twin)
     unsigned char* hin = B.h_in.p;
@@ -393,7 +445,27 @@ int pdmpc_bounded_set_coupling(pdmpc_handle* h, uint8_t* adjacency, double* area
     const BoundArgs A = bound_args(h, n, B.S, B.n_lan);
     HIPCHK(hipMemsetAsync(A.n_pairs, 0, sizeof(int32_t), h->stream));
     if (const int rc = timed_launch(h, B.coupling, pdmpc_launch_bounded_coupling, A, "bounded-set coupling")) return rc;
-    return fetch_pair_out(h, B.coupling, B.out.p, B.h_out.p, bound_layout(n, B.n_lan).out, n, adjacency, area);
+    return fetch_pair_out(h, B.coupling, B.out.p, B.h_out.p, bound_layout(n, B.n_lan).out, (size_t)n * n, adjacency, area);
+}
+
+int pdmpc_bounded_set_coupling_grouped(pdmpc_handle* h, int32_t n_groups, const int32_t* group_offset, uint8_t* adjacency, double* area) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    if (!adjacency) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling_grouped: null adjacency");
+    BoundState& B = h->bound;
+    if (!B.valid) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling_grouped without a successful pdmpc_bound_reachable_sets");
+    int n = 0;
+    if (const int rc = check_groups("pdmpc_bounded_set_coupling_grouped", n_groups, group_offset, &n)) return rc;
+    if (n > h->max_vehicles) return fail(PDMPC_ERR_CAPACITY, "pdmpc_bounded_set_coupling_grouped: more vehicles than config.max_vehicles");
+    if (n != B.n) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling_grouped: the groups do not cover the vehicles of the last pdmpc_bound_reachable_sets");
+    if (n == 0) return PDMPC_OK;
+    ON_DEVICE(h->cfg.device);
+    const BoundLayout L = bound_layout(n, B.n_lan);
+    BoundArgs A = bound_args(h, n, B.S, B.n_lan);
+    const size_t entries = stage_groups((PairGroup*)(B.h_in.p + L.group), n_groups, group_offset, &A.max_group);
+    HIPCHK(hipMemcpyAsync(B.in.p + L.group, B.h_in.p + L.group, (size_t)n * sizeof(PairGroup), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(A.n_pairs, 0, sizeof(int32_t), h->stream));
+    if (const int rc = timed_launch(h, B.coupling, pdmpc_launch_bounded_coupling_grouped, A, "bounded-set coupling")) return rc;
+    return fetch_pair_out(h, B.coupling, B.out.p, B.h_out.p, L.out, entries, adjacency, area);
 }
 
 int pdmpc_bounded_reachable_kernel_ms(pdmpc_handle* h, double* ms2) {

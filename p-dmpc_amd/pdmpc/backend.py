@@ -111,6 +111,18 @@ EXPORTS = [
     "pdmpc_bounded_set_coupling",
     "pdmpc_polygon_set_coupling_host",
     "pdmpc_bounded_reachable_kernel_ms",
+    "pdmpc_reachable_set_coupling_grouped",
+    "pdmpc_bounded_set_coupling_grouped",
+    "pdmpc_reachable_set_coupling_grouped_host",
+    "pdmpc_polygon_set_coupling_grouped_host",
+    "pdmpc_sweep_create",
+    "pdmpc_sweep_destroy",
+    "pdmpc_sweep_build",
+    "pdmpc_sweep_problem",
+    "pdmpc_sweep_apply",
+    "pdmpc_sweep_step",
+    "pdmpc_sweep_run",
+    "pdmpc_sweep_last_timing",
     "pdmpc_fca_collisions",
     "pdmpc_fca_collisions_host",
     "pdmpc_fca_kernel_ms",
@@ -225,6 +237,69 @@ def reachable_set_coupling_call(local_sets, x, y, yaw, trim, handle=None):
         del keep
         _check(L, rc, "pdmpc_reachable_set_coupling_host", message=False)
     return shaped()
+
+
+def _group_offsets(group_sizes):
+    off = np.zeros(len(group_sizes) + 1, dtype=np.int32)
+    off[1:] = np.cumsum(np.asarray(group_sizes, dtype=np.int64))
+    return off
+
+
+def _grouped_out(group_sizes):
+    """The outputs of a grouped coupler, never empty -> (adjacency, areas, a call that decodes the blocks into [(adjacency (n_g, n_g),
+    areas (n_g, n_g)) per group])."""
+    total = int(sum(int(g) * int(g) for g in group_sizes))
+    adj = np.zeros(max(total, 1), dtype=np.uint8)
+    area = np.zeros(max(total, 1), dtype=np.float64)
+
+    def blocks():
+        out, at = [], 0
+        for g in group_sizes:
+            g = int(g)
+            out.append((adj[at : at + g * g].reshape(g, g).copy(), area[at : at + g * g].reshape(g, g).copy()))
+            at += g * g
+        return out
+
+    return adj, area, blocks
+
+
+def reachable_set_coupling_grouped_call(local_sets, group_sizes, x, y, yaw, trim, handle=None):
+    """The reachable-set coupler for several independent sets of vehicles at once: the vehicles are consecutive groups of
+    `group_sizes` vehicles, pairs are formed inside a group only.  On `handle`'s device (pdmpc_reachable_set_coupling_grouped) or,
+    without one, on the host twin.  -> [(adjacency (n_g, n_g) uint8, areas (n_g, n_g)) per group]."""
+    L = load_library()
+    x, y, c, s, t = _coupling_args(x, y, yaw, trim)
+    off = _group_offsets(group_sizes)
+    if int(off[-1]) != x.size:
+        raise ValueError("the groups cover %d vehicles, %d were handed over" % (int(off[-1]), x.size))
+    adj, area, blocks = _grouped_out(group_sizes)
+    ptrs = [off.ctypes.data_as(abi.c_int32_p), x.ctypes.data_as(abi.c_double_p), y.ctypes.data_as(abi.c_double_p), c.ctypes.data_as(abi.c_double_p),
+            s.ctypes.data_as(abi.c_double_p), t.ctypes.data_as(abi.c_int32_p), adj.ctypes.data_as(abi.c_uint8_p), area.ctypes.data_as(abi.c_double_p)]
+    if handle is not None:
+        _check(L, L.pdmpc_reachable_set_coupling_grouped(handle.h, len(group_sizes), *ptrs), "pdmpc_reachable_set_coupling_grouped")
+    else:
+        ps, keep = pack_local_sets(local_sets)
+        rc = L.pdmpc_reachable_set_coupling_grouped_host(len(local_sets), len(local_sets[0]), C.byref(ps), len(group_sizes), *ptrs)
+        del keep
+        _check(L, rc, "pdmpc_reachable_set_coupling_grouped_host", message=False)
+    return blocks()
+
+
+def polygon_set_coupling_grouped_call(sets, group_sizes):
+    """pdmpc_polygon_set_coupling_grouped_host: polygon_set_coupling_call on consecutive groups of the polygons
+    -> [(adjacency, areas) per group]."""
+    L = load_library()
+    keep = abi._Keep()
+    off = _group_offsets(group_sizes)
+    if int(off[-1]) != len(sets):
+        raise ValueError("the groups cover %d polygons, %d were handed over" % (int(off[-1]), len(sets)))
+    ps = abi.pack_polygon_set([np.asarray(p, dtype=np.float64) for p in sets], keep)
+    adj, area, blocks = _grouped_out(group_sizes)
+    rc = L.pdmpc_polygon_set_coupling_grouped_host(C.byref(ps), len(group_sizes), off.ctypes.data_as(abi.c_int32_p), adj.ctypes.data_as(abi.c_uint8_p),
+                                                   area.ctypes.data_as(abi.c_double_p))
+    del keep
+    _check(L, rc, "pdmpc_polygon_set_coupling_grouped_host", message=False)
+    return blocks()
 
 
 def fca_pairs(adjacency):
@@ -402,6 +477,11 @@ def load_library(path=None):
     L.pdmpc_bounded_set_coupling.argtypes = [H, abi.c_uint8_p, abi.c_double_p]
     L.pdmpc_polygon_set_coupling_host.argtypes = [C.POINTER(abi.PolygonSet), C.c_int32, abi.c_uint8_p, abi.c_double_p]
     L.pdmpc_bounded_reachable_kernel_ms.argtypes = [H, abi.c_double_p]
+    L.pdmpc_reachable_set_coupling_grouped.argtypes = [H, C.c_int32, abi.c_int32_p] + [abi.c_double_p] * 4 + [abi.c_int32_p, abi.c_uint8_p, abi.c_double_p]
+    L.pdmpc_bounded_set_coupling_grouped.argtypes = [H, C.c_int32, abi.c_int32_p, abi.c_uint8_p, abi.c_double_p]
+    L.pdmpc_reachable_set_coupling_grouped_host.argtypes = [C.c_int32, C.c_int32, C.POINTER(abi.PolygonSet), C.c_int32, abi.c_int32_p] + [abi.c_double_p] * 4 + [
+        abi.c_int32_p, abi.c_uint8_p, abi.c_double_p]
+    L.pdmpc_polygon_set_coupling_grouped_host.argtypes = [C.POINTER(abi.PolygonSet), C.c_int32, abi.c_int32_p, abi.c_uint8_p, abi.c_double_p]
     fca_tail = [C.c_int32, C.c_int32] + [abi.c_double_p] * 4 + [C.c_int32, abi.c_int32_p, C.POINTER(abi.PolygonSet), C.POINTER(abi.PolygonSet)] + \
         [C.c_double] * 3 + [abi.c_int32_p, abi.c_int32_p]
     L.pdmpc_fca_collisions.argtypes = [H] + fca_tail
@@ -683,6 +763,20 @@ class Handle:
         area = np.zeros(max(n * n, 1), dtype=np.float64)
         _check(self.L, self.L.pdmpc_bounded_set_coupling(self.h, adj.ctypes.data_as(abi.c_uint8_p), area.ctypes.data_as(abi.c_double_p)), "pdmpc_bounded_set_coupling")
         return adj[: n * n].reshape(n, n), area[: n * n].reshape(n, n)
+
+    def reachable_set_coupling_grouped(self, group_sizes, x, y, yaw, trim):
+        """pdmpc_reachable_set_coupling_grouped on this handle's device: consecutive groups of `group_sizes` vehicles, pairs inside a
+        group only -> [(adjacency (n_g, n_g) uint8, areas (n_g, n_g)) per group]."""
+        return reachable_set_coupling_grouped_call(None, group_sizes, x, y, yaw, trim, handle=self)
+
+    def bounded_set_coupling_grouped(self, group_sizes):
+        """pdmpc_bounded_set_coupling_grouped on the step-Hp sets of the last bound_reachable_sets, as consecutive groups of
+        `group_sizes` vehicles -> [(adjacency, areas) per group]."""
+        off = _group_offsets(group_sizes)
+        adj, area, blocks = _grouped_out(group_sizes)
+        _check(self.L, self.L.pdmpc_bounded_set_coupling_grouped(self.h, len(group_sizes), off.ctypes.data_as(abi.c_int32_p), adj.ctypes.data_as(abi.c_uint8_p),
+                                                                 area.ctypes.data_as(abi.c_double_p)), "pdmpc_bounded_set_coupling_grouped")
+        return blocks()
 
     def bounded_reachable_kernel_ms(self):
         """kernel times (ms) of the last bound_reachable_sets and bounded_set_coupling"""

@@ -78,6 +78,18 @@ def _declare(L):
     for name in ("pdmpc_controller_create", "pdmpc_controller_destroy", "pdmpc_controller_step", "pdmpc_controller_build_step", "pdmpc_controller_apply",
                  "pdmpc_controller_problem", "pdmpc_controller_state"):
         getattr(L, name).restype = C.c_int
+    L.pdmpc_sweep_create.argtypes = [H, C.c_int32, C.POINTER(H), C.POINTER(H)]
+    L.pdmpc_sweep_destroy.argtypes = [H]
+    L.pdmpc_sweep_build.argtypes = [H]
+    L.pdmpc_sweep_problem.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.POINTER(abi.VehicleIn)), C.POINTER(abi.c_int32_p), C.POINTER(abi.c_int32_p),
+                                      C.POINTER(C.POINTER(abi.PolygonSet)), C.POINTER(abi.c_int32_p), C.POINTER(abi.c_int32_p)]
+    L.pdmpc_sweep_apply.argtypes = [H, C.POINTER(abi.VehicleOut)]
+    L.pdmpc_sweep_step.argtypes = [H]
+    L.pdmpc_sweep_run.argtypes = [H, C.c_int32, abi.c_double_p]
+    L.pdmpc_sweep_last_timing.argtypes = [H, C.c_void_p]
+    for name in ("pdmpc_sweep_create", "pdmpc_sweep_destroy", "pdmpc_sweep_build", "pdmpc_sweep_problem", "pdmpc_sweep_apply", "pdmpc_sweep_step", "pdmpc_sweep_run",
+                 "pdmpc_sweep_last_timing"):
+        getattr(L, name).restype = C.c_int
     L._controller_declared = True
     return L
 
@@ -191,6 +203,11 @@ class NativeController:
         if self.c:
             self.L.pdmpc_controller_destroy(self.c)
             self.c = C.c_void_p()
+
+    def records(self):
+        """The records of the member's last step in its own slot order (pdmpc_controller_records), also after a sweep's step."""
+        p = self.L.pdmpc_controller_records(self.c)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(self.n * abi.VEHICLE_OUT_DTYPE.itemsize,)).view(abi.VEHICLE_OUT_DTYPE).copy()
 
     def __del__(self):
         try:
@@ -360,3 +377,76 @@ class NativeController:
         k = C.c_int32()
         self._check(self.L.pdmpc_controller_state(self.c, *[a.ctypes.data_as(abi.c_double_p) for a in arr], nf.ctypes.data_as(abi.c_int32_p), C.byref(k)), "pdmpc_controller_state")
         return {"x": arr[0], "y": arr[1], "yaw": arr[2], "speed": arr[3], "steering": arr[4], "needs_fallback": nf != 0, "k": k.value}
+
+
+class NativeSweep:
+    """Several closed loops in lock-step (pdmpc_sweep_*): `members` are NativeControllers created on `handle` (or all
+    without one); a step is every member's build with the device's step preparation grouped over the members, ONE launch for all of
+    them, every member's apply.  Each member ends a sweep step byte for byte where its own step() would have left it.  The members
+    stay the caller's (and are kept alive by the sweep)."""
+
+    def __init__(self, members, handle=None):
+        self.members = list(members)
+        self.handle = handle
+        self.L = _declare(load_library())
+        self.n = sum(m.n for m in self.members)
+        self.s = C.c_void_p()
+        arr = (C.c_void_p * max(len(self.members), 1))(*[m.c for m in self.members])
+        rc = self.L.pdmpc_sweep_create(handle.h if handle is not None else None, len(self.members), arr, C.byref(self.s))
+        self._check(rc, "pdmpc_sweep_create")
+
+    def _check(self, rc, what):
+        if rc != 0:
+            msg = self.L.pdmpc_controller_last_error()
+            err = BackendError("%s failed with status %d: %s" % (what, rc, msg.decode() if msg else ""))
+            err.status = rc
+            raise err
+
+    def close(self):
+        if self.s:
+            self.L.pdmpc_sweep_destroy(self.s)
+            self.s = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def build(self):
+        self._check(self.L.pdmpc_sweep_build(self.s), "pdmpc_sweep_build")
+
+    def problem(self):
+        """The concatenated problem of the last build, decoded as NativeController.problem decodes a member's, plus member / member_slot
+        per sweep slot."""
+        n = C.c_int32()
+        vin = C.POINTER(abi.VehicleIn)()
+        po, pi, mem, slot = (abi.c_int32_p() for _ in range(4))
+        fb = C.POINTER(abi.PolygonSet)()
+        self._check(self.L.pdmpc_sweep_problem(self.s, C.byref(n), C.byref(vin), C.byref(po), C.byref(pi), C.byref(fb), C.byref(mem), C.byref(slot)), "pdmpc_sweep_problem")
+        iters, preds, fallback = self.members[0]._decode(n.value, vin, po, pi, fb)
+        return {"iters": iters, "preds": preds, "fallback": fallback, "member": [int(mem[q]) for q in range(n.value)],
+                "member_slot": [int(slot[q]) for q in range(n.value)]}
+
+    def apply(self, records):
+        recs = np.ascontiguousarray(records)
+        if recs.shape[0] != self.n:
+            raise ValueError("a sweep of %d slots takes %d records, not %d" % (self.n, self.n, recs.shape[0]))
+        self._check(self.L.pdmpc_sweep_apply(self.s, abi.out_ptr(recs)), "pdmpc_sweep_apply")
+
+    def step(self):
+        """One lock-step natively -> every member's records in its own slot order."""
+        self._check(self.L.pdmpc_sweep_step(self.s), "pdmpc_sweep_step")
+        return [m.records() for m in self.members]
+
+    def run(self, n_steps):
+        """n_steps lock-steps in one native call -> wall-clock milliseconds of every lock-step."""
+        ms = np.zeros(max(n_steps, 1))
+        self._check(self.L.pdmpc_sweep_run(self.s, n_steps, ms.ctypes.data_as(abi.c_double_p)), "pdmpc_sweep_run")
+        return ms[:n_steps]
+
+    def last_timing(self):
+        """Host milliseconds of the last lock-step by part (pdmpc_sweep_last_timing)."""
+        t = (C.c_double * 6)()
+        self._check(self.L.pdmpc_sweep_last_timing(self.s, t), "pdmpc_sweep_last_timing")
+        return dict(zip(("build", "pack", "enqueue", "wait_and_read_back", "choose", "apply"), (float(x) for x in t)))

@@ -1,0 +1,196 @@
+"""Timing of the sweep (pdmpc_sweep_run): M closed loops in lock-step against the same M loops stepped one after
+another by the parent commit's library.
+
+Workload: M in {1, 2, 4, 8} C2-like members (20 vehicles, Hp 8, seeds 1 .. M) on one handle, steps 21-40 of each closed loop, with
+  (a) distance coupling,
+  (b) reachable-set coupling with lanelet bounding.
+Sweep: the median wall time per lock-step of pdmpc_sweep_run and the six parts of pdmpc_sweep_last_timing.
+Baseline: a built checkout of the parent commit in a directory of its own (--baseline-root: its p-dmpc_amd/pdmpc package and its
+p-dmpc_amd/csrc/libpdmpc_hip.so); per lock-step every member takes one pdmpc_controller_run(1), the lock-step's time is their sum.
+Five alternating runs of baseline and sweep, each in a fresh process; reported are the median of the five medians and their spread
+(max - min).  For (b) also one grouped device call (pdmpc_bound_reachable_sets on all members' vehicles + pdmpc_bounded_set_coupling_grouped)
+against M ungrouped pairs of calls on the members' recorded states, in kernel time (HIP events) and as whole calls.
+
+    python tools/sweep_timing.py --baseline-root DIR [--rounds 5] [--out profiles/sweep_timing.txt]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MS = (1, 2, 4, 8)
+MODES = {"a": dict(coupling="distance"), "b": dict(coupling="reachable_set", bound_reachable_sets=True)}
+PARTS = ("build", "pack", "enqueue", "wait_and_read_back", "choose", "apply")
+WARMUP, TIMED = 20, 20
+
+
+def members_on_one_handle(M, mode):
+    import numpy as np  # noqa: F401
+    from pdmpc.backend import Handle
+    from pdmpc.config import Config, ScenarioType
+    from pdmpc.mpa import get_mpa
+    from pdmpc.native_controller import NativeController
+    from pdmpc.road_network import commonroad_scenario
+
+    kw = dict(MODES[mode])
+    coupling = kw.pop("coupling")
+    options = Config(scenario_type=ScenarioType.commonroad, amount=20, Hp=8, max_vehicles=max(32, 20 * M), max_nodes=1 << 17, **kw)
+    mpa = get_mpa(options)
+    h = Handle(options)
+    h.upload_mpa(mpa)
+    scs = [commonroad_scenario(options, seed=s) for s in range(1, M + 1)]
+    return options, mpa, h, scs, [NativeController(options, sc, mpa, h, coupling=coupling) for sc in scs]
+
+
+def worker(kind):
+    """One run: every mode and M on the tree this process imports -> one JSON line."""
+    import numpy as np
+
+    out = {}
+    for mode in MODES:
+        for M in MS:
+            options, mpa, h, scs, cs = members_on_one_handle(M, mode)
+            if kind == "baseline":
+                step_ms = []
+                for k in range(WARMUP + TIMED):
+                    step_ms.append(sum(float(c.run(1)[0]) for c in cs))
+                out["%s%d" % (mode, M)] = {"median": float(np.median(step_ms[WARMUP:]))}
+            else:
+                from pdmpc.native_controller import NativeSweep
+
+                sweep = NativeSweep(cs, h)
+                sweep.run(WARMUP)
+                ms, parts = [], []
+                for k in range(TIMED):
+                    ms.append(float(sweep.run(1)[0]))
+                    t = sweep.last_timing()
+                    parts.append([t[p] for p in PARTS])
+                out["%s%d" % (mode, M)] = {"median": float(np.median(ms)), "parts": [float(x) for x in np.median(np.array(parts), axis=0)]}
+                sweep.close()
+            for c in cs:
+                c.close()
+            h.close()
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+def grouped_calls(reps):
+    """(b): one grouped device call against M ungrouped ones on the members' states after 30 steps -> one JSON line."""
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from bounded_reachable_timing import lanelet_polygons
+
+    out = {}
+    for M in MS:
+        options, mpa, h, scs, cs = members_on_one_handle(M, "b")
+        from pdmpc.native_controller import NativeSweep
+
+        sweep = NativeSweep(cs, h)
+        sweep.run(30)
+        per = []
+        for c, sc in zip(cs, scs):
+            st = c.state()
+            lan, trim = lanelet_polygons(options, mpa, sc, (st["x"], st["y"], st["yaw"], st["speed"], st["steering"]))
+            per.append((st["x"].copy(), st["y"].copy(), st["yaw"].copy(), np.asarray(trim), lan))
+        x, y, yaw, trim = (np.concatenate([p[q] for p in per]) for q in range(4))
+        lan = [q for p in per for q in p[4]]
+        sizes = [len(p[0]) for p in per]
+        gk, gc, uk, uc = [], [], [], []
+        for r in range(reps + 2):
+            t0 = time.perf_counter()
+            h.bound_reachable_sets(x, y, yaw, trim, lan, False)
+            blocks = h.bounded_set_coupling_grouped(sizes)
+            t1 = time.perf_counter()
+            k = sum(h.bounded_reachable_kernel_ms())
+            tu, ku, alone = 0.0, 0.0, []
+            for p in per:
+                t2 = time.perf_counter()
+                h.bound_reachable_sets(p[0], p[1], p[2], p[3], p[4], False)
+                alone.append(h.bounded_set_coupling())
+                tu += time.perf_counter() - t2
+                ku += sum(h.bounded_reachable_kernel_ms())
+            assert all(np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint64), b[1].view(np.uint64)) for a, b in zip(blocks, alone))
+            if r >= 2:
+                gk.append(k)
+                gc.append(1e3 * (t1 - t0))
+                uk.append(ku)
+                uc.append(1e3 * tu)
+        out[str(M)] = [float(np.median(v)) for v in (gk, gc, uk, uc)]
+        sweep.close()
+        for c in cs:
+            c.close()
+        h.close()
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+def child(root, *args):
+    """A fresh process on the tree under `root` (its package and its library) -> the JSON of its RESULT line."""
+    env = dict(os.environ, PDMPC_TREE=root)
+    env.pop("PDMPC_LIB", None)
+    p = subprocess.run([sys.executable, os.path.abspath(__file__)] + list(args), env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    if p.returncode != 0:
+        sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
+        raise SystemExit("a timing run failed with status %d: nothing more is started" % p.returncode)
+    return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--baseline-root", help="a built checkout of the parent commit")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sweep_timing.txt"))
+    ap.add_argument("--worker")
+    args = ap.parse_args()
+    if args.worker:
+        tree = os.environ.get("PDMPC_TREE", ROOT)
+        sys.path[:0] = [tree, os.path.join(tree, "p-dmpc_amd")]
+        if args.worker == "grouped":
+            grouped_calls(args.reps)
+        else:
+            worker(args.worker)
+        return
+    if not args.baseline_root:
+        raise SystemExit("--baseline-root: a built checkout of the parent commit is needed")
+    import numpy as np
+
+    base, sweep = [], []
+    for r in range(args.rounds):
+        base.append(child(os.path.abspath(args.baseline_root), "--worker", "baseline"))
+        sweep.append(child(ROOT, "--worker", "sweep"))
+        print("round %d done" % (r + 1), flush=True)
+    grouped = child(ROOT, "--worker", "grouped", "--reps", str(args.reps))
+    lines = ["sweep against the parent commit's library: M C2-like members (20 vehicles, Hp 8, seeds 1..M), steps %d-%d, ms per lock-step;"
+             % (WARMUP + 1, WARMUP + TIMED),
+             "median and spread (max - min) of %d alternating runs' medians; baseline = sum of the members' pdmpc_controller_run(1)" % args.rounds]
+    for mode in MODES:
+        lines.append("(%s) %s" % (mode, "distance coupling" if mode == "a" else "reachable-set coupling with lanelet bounding"))
+        for M in MS:
+            key = "%s%d" % (mode, M)
+            b = [r[key]["median"] for r in base]
+            s = [r[key]["median"] for r in sweep]
+            mb, ms_, sb, ss = float(np.median(b)), float(np.median(s)), max(b) - min(b), max(s) - min(s)
+            spread = max(sb, ss)
+            if M == 1:
+                verdict = "agree within the spread" if abs(mb - ms_) <= spread else "DIFFER by more than the spread"
+            else:
+                verdict = "sweep faster by more than the spread" if mb - ms_ > spread else ("sweep faster, within the spread" if ms_ < mb else "sweep NOT faster")
+            parts = np.median(np.array([r[key]["parts"] for r in sweep]), axis=0)
+            lines.append("  M=%d  baseline %7.3f (spread %.3f)   sweep %7.3f (spread %.3f)   ratio %.2f   %s" % (M, mb, sb, ms_, ss, mb / ms_, verdict))
+            lines.append("        sweep parts: " + "  ".join("%s %.3f" % (p, v) for p, v in zip(PARTS, parts)))
+    lines.append("(b) step preparation on the members' states after 30 steps, median of %d: one pdmpc_bound_reachable_sets + pdmpc_bounded_set_coupling_grouped"
+                 " against M pairs of ungrouped calls" % args.reps)
+    for M in MS:
+        gk, gc, uk, uc = grouped[str(M)]
+        lines.append("  M=%d  kernels (events) grouped %.4f ms, ungrouped %.4f ms   whole calls grouped %.4f ms, ungrouped %.4f ms" % (M, gk, uk, gc, uc))
+    print("\n".join(lines), flush=True)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
