@@ -225,6 +225,49 @@ int pdmpc_pack_batch(pdmpc_handle* handle, int32_t n_vehicles, const pdmpc_vehic
 int pdmpc_plan_step_lean(pdmpc_handle* handle, int32_t n_vehicles, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index,
                          const pdmpc_polygon_set* fallback_shapes, int32_t* status, double* final_cost);
 int pdmpc_fetch_records_at(pdmpc_handle* handle, int32_t count, const int32_t* vehicles, pdmpc_vehicle_out* out);
+/* ---- the choice among the plans of a batch, as data (csrc/choice_kernel.hip) ----
+ * One description covers the explorative choice (PrioritizedExplorativeController.m:94-176), the optimal-priority choice
+ * (PrioritizedOptimalController.m:56-114), follow-own, and any concatenation of these over the members of a sweep.  Slots are the
+ * caller's slots of the planned batch.
+ *   cells   cell c = the sum, started at +0.0 and added IN LIST ORDER, over cell_slot[cell_offset[c] .. cell_offset[c + 1]) of
+ *           status == PDMPC_OK ? path_nodes[Hp][4] : +inf, then rounded as round(., 8): nearbyint(v * 1e8) / 1e8.  The order of the
+ *           list is the order of addition and part of the contract (the sums are doubles).
+ *   graphs  the candidates of graph g are the consecutive cells graph_offset[g] .. graph_offset[g + 1] - 1; chosen[g] = the index
+ *           among them of the first minimum ([~, i] = min(.)); all candidates +inf (or none): 0.
+ *   picks   pick i returns the record of slot pick_slot[pick_offset[i] + chosen[pick_graph[i]]]; with pick_graph[i] == -1 its single
+ *           listed slot (follow-own).
+ * Only PDMPC_OK and PDMPC_EXHAUSTED are planning results: any other status among the batch's n records — whether a cell lists the
+ * record or not — makes the choice fail with PDMPC_ERR_HIP.
+ * Checked before anything is launched (PDMPC_ERR_INVALID): offsets are not negative and do not decrease, graph offsets stay within the cells,
+ * slots lie within the batch, pick_graph within [-1, n_graphs), and a pick lists as many slots as its graph has candidates (one for
+ * pick_graph == -1). */
+typedef struct {
+    int32_t n_cells;
+    int32_t n_graphs;
+    int32_t n_picks;
+    int32_t _pad;
+    const int32_t* cell_offset;  /* [n_cells + 1] */
+    const int32_t* cell_slot;
+    const int32_t* graph_offset; /* [n_graphs + 1] */
+    const int32_t* pick_graph;   /* [n_picks] */
+    const int32_t* pick_offset;  /* [n_picks + 1] */
+    const int32_t* pick_slot;
+} pdmpc_choice;
+/* The choice on the host (no GPU needed): status[n] and final_cost[n] = path_nodes[Hp][4] of the batch's records; chosen[n_graphs] and
+ * cell_cost[n_cells] (either may be NULL).  Picks are validated and otherwise ignored.  The twin and checker of the device choice. */
+int pdmpc_choose_host(int32_t n, const int32_t* status, const double* final_cost, const pdmpc_choice* choice, int32_t* chosen, double* cell_cost);
+/* The choice on the device, on the n records resident in the current bank (after pdmpc_launch_packed, pdmpc_import_results, ...): the
+ * sums and the first minima in one launch, the gather of the picked records in a second, ONE copy back (picked records, chosen, cell
+ * costs and the status counters) and one synchronisation.  picks[n_picks]; chosen / cell_cost may be NULL.  Slots are the caller's
+ * vehicles also for a batch that pdmpc_pack_step put into level order (then n must be the packed batch). */
+int pdmpc_choose_resident(pdmpc_handle* handle, int32_t n, const pdmpc_choice* choice, int32_t* chosen, double* cell_cost, pdmpc_vehicle_out* picks);
+/* pdmpc_plan_step + the choice on the device: packs, launches and chooses with no host synchronisation between the search's launch
+ * and the read-back.  Arena overflow and predecessor time-outs are read from counters the choice keeps on the device and handled as
+ * pdmpc_plan_step handles them (planned again with larger arenas / in resident slices).  pdmpc_last_call_timing as for pdmpc_plan_step. */
+int pdmpc_plan_step_chosen(pdmpc_handle* handle, int32_t n_vehicles, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index,
+                           const pdmpc_polygon_set* fallback_shapes, const pdmpc_choice* choice, int32_t* chosen, double* cell_cost, pdmpc_vehicle_out* picks);
+/* kernel time (HIP events, ms) of the two launches of the last pdmpc_choose_resident / pdmpc_plan_step_chosen */
+int pdmpc_choice_kernel_ms(pdmpc_handle* handle, double* ms);
 /* host wall-clock microseconds of the last pdmpc_plan_batch / pdmpc_plan_step on this handle: [0] pack (flatten + queue the
  * host-to-device copy), [1] enqueue the launch, [2] wait for the kernel + copy the records back */
 int pdmpc_last_call_timing(pdmpc_handle* handle, double* us3);
@@ -615,6 +658,12 @@ int pdmpc_controller_set_optimizer(pdmpc_controller* c, int32_t which); /* PDMPC
 /* the sampled optimizer's seed per slot of the last built step or batch (pdmpc_controller_build_step / _explore_build / _optimal_build),
  * whichever optimizer is selected: *n slots, *seeds valid until the next build */
 int pdmpc_controller_seeds(pdmpc_controller* c, int32_t* n, const uint32_t** seeds);
+/* on != 0: pdmpc_controller_explore_run and pdmpc_controller_optimal_run (the steps that keep the chosen plans only) make ONE
+ * pdmpc_plan_step_chosen call per step -- the choice among the prioritizations and the gather of the chosen records run on the device
+ * directly behind the search, one read-back -- instead of pdmpc_plan_step_lean, the choice on the host and pdmpc_fetch_records_at.  The
+ * explorative step with and without follow-own and the optimal-priority step; state, chosen instances, cost table and kept records are
+ * the same byte for byte.  Default off; nothing changes for a controller without a handle. */
+int pdmpc_controller_set_device_choice(pdmpc_controller* c, int32_t on);
 
 /* ---- several closed loops in lock-step (csrc/step_controller.cpp) ----
  * A sweep borrows n_members controllers that were created on the same handle (or all without one) and steps them together: every
@@ -622,8 +671,8 @@ int pdmpc_controller_seeds(pdmpc_controller* c, int32_t* n, const uint32_t** see
  * vehicles, pdmpc_*_coupling_grouped: a pair of two members is never looked at), ONE pdmpc_plan_step for the concatenated problem,
  * every member's apply.  After a sweep step each member is byte for byte where its own pdmpc_controller_step would have left it
  * (state, records in its own slot order, problem, seeds, time step, expected work, fallback bookkeeping): a member can be taken out of
- * a sweep and stepped alone afterwards.  Only the plain prioritized step is part of a sweep (graph search or sampled optimizer), not
- * the explorative or the optimal-priority step.
+ * a sweep and stepped alone afterwards.  The plain prioritized step and the explorative step (below) are part of a sweep, with the
+ * graph search or the sampled optimizer; the optimal-priority step is not (its batch sizes differ per step and per member).
  * pdmpc_sweep_create checks before anything advances: members on the sweep's handle, or all without one; one Hp; one optimizer
  * (PDMPC_ERR_INVALID each); no member twice (PDMPC_ERR_INVALID); sum of the members' vehicles <= the handle's max_vehicles
  * (PDMPC_ERR_CAPACITY).  Members may differ in everything else.
@@ -643,6 +692,24 @@ int pdmpc_sweep_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records);
 int pdmpc_sweep_step(pdmpc_sweep* s);
 int pdmpc_sweep_run(pdmpc_sweep* s, int32_t n_steps, double* ms);
 int pdmpc_sweep_last_timing(pdmpc_sweep* s, double* ms6);
+/* The explorative step of a sweep: every member's explorative batch of n_perm prioritizations (seed = its time step),
+ * the step preparation grouped as for pdmpc_sweep_build, the members' flattened batches one after the other (predecessor slots shifted by
+ * the member's first slot), ONE pdmpc_plan_step_chosen with the members' choice descriptions concatenated -- one launch of the searches,
+ * the choice of every member on the device, one read-back --, every member's apply of its chosen plans.  After it each member is byte for
+ * byte where its own pdmpc_controller_explore_step would have left it (state, chosen instances, cost table, kept records, couplings,
+ * seeds, time step, expected work, fallback bookkeeping); pdmpc_controller_explore_result / _records read a member's part and
+ * pdmpc_controller_explore_follow_own is honoured per member.  A sweep may alternate plain and explorative steps.
+ * explore_problem: the concatenated batch; member / instance / vehicle / level per slot.  explore_apply takes the records of all its
+ * slots, chooses per member on the host and applies (works without a handle).  Refused before any member advances: n_perm < 1 and a
+ * broken sweep (PDMPC_ERR_INVALID), sum of n_m * n_perm > the handle's max_vehicles (PDMPC_ERR_CAPACITY), explore_step / explore_run
+ * without a handle (PDMPC_ERR_INVALID). */
+int pdmpc_sweep_explore_build(pdmpc_sweep* s, int32_t n_perm);
+int pdmpc_sweep_explore_problem(pdmpc_sweep* s, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index,
+                                const pdmpc_polygon_set** fallback, const int32_t** member, const int32_t** instance, const int32_t** vehicle,
+                                const int32_t** level);
+int pdmpc_sweep_explore_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records);
+int pdmpc_sweep_explore_step(pdmpc_sweep* s, int32_t n_perm);
+int pdmpc_sweep_explore_run(pdmpc_sweep* s, int32_t n_perm, int32_t n_steps, double* ms);
 
 /* ---- several GPUs behind the same boundary (csrc/group.cpp) ----
  * The reference's vehicles exchange their solved areas after every computation level: each publishes a Predictions message that every

@@ -758,16 +758,168 @@ int fetch_lean(pdmpc_handle* h, int32_t n, int32_t* status, double* cost) {
     return PDMPC_OK;
 }
 
-// Where a plan's read-back lands: every record, or (lean) the (status, cost) pair of every vehicle (fetch_lean).  Caller's order.
+// ---- the choice among the plans of a batch (pdmpc_choice, include/pdmpc.h; choice_kernel.hip)
+
+// what pdmpc_choice promises, checked before anything is launched or summed
+int check_choice(int32_t n, const pdmpc_choice* ch) {
+    if (!ch || n < 0 || ch->n_cells < 0 || ch->n_graphs < 0 || ch->n_picks < 0) return fail(PDMPC_ERR_INVALID, "pdmpc_choice: bad argument");
+    if ((ch->n_cells > 0 && !ch->cell_offset) || (ch->n_graphs > 0 && !ch->graph_offset) || (ch->n_picks > 0 && (!ch->pick_graph || !ch->pick_offset)))
+        return fail(PDMPC_ERR_INVALID, "pdmpc_choice: null list");
+    auto monotone = [](const int32_t* off, int count) {
+        if (off[0] < 0) return false;
+        for (int i = 0; i < count; ++i)
+            if (off[i + 1] < off[i]) return false;
+        return true;
+    };
+    auto slots_within = [n](const int32_t* slot, int first, int end) {
+        if (end > first && !slot) return false;
+        for (int q = first; q < end; ++q)
+            if (slot[q] < 0 || slot[q] >= n) return false;
+        return true;
+    };
+    if (ch->n_cells > 0) {
+        if (!monotone(ch->cell_offset, ch->n_cells)) return fail(PDMPC_ERR_INVALID, "pdmpc_choice: cell offsets are negative or decrease");
+        if (!slots_within(ch->cell_slot, 0, ch->cell_offset[ch->n_cells])) return fail(PDMPC_ERR_INVALID, "pdmpc_choice: a cell lists a slot outside the batch");
+    }
+    if (ch->n_graphs > 0) {
+        if (!monotone(ch->graph_offset, ch->n_graphs)) return fail(PDMPC_ERR_INVALID, "pdmpc_choice: graph offsets are negative or decrease");
+        if (ch->graph_offset[ch->n_graphs] > ch->n_cells) return fail(PDMPC_ERR_INVALID, "pdmpc_choice: a graph's candidates lie outside the cells");
+    }
+    if (ch->n_picks > 0) {
+        if (!monotone(ch->pick_offset, ch->n_picks)) return fail(PDMPC_ERR_INVALID, "pdmpc_choice: pick offsets are negative or decrease");
+        for (int i = 0; i < ch->n_picks; ++i) {
+            const int g = ch->pick_graph[i];
+            if (g < -1 || g >= ch->n_graphs) return fail(PDMPC_ERR_INVALID, "pdmpc_choice: pick_graph outside [-1, n_graphs)");
+            const int want = g < 0 ? 1 : ch->graph_offset[g + 1] - ch->graph_offset[g];
+            if (want < 1 || ch->pick_offset[i + 1] - ch->pick_offset[i] != want)
+                return fail(PDMPC_ERR_INVALID, "pdmpc_choice: a pick lists another number of slots than its graph has candidates");
+        }
+        if (!slots_within(ch->pick_slot, 0, ch->pick_offset[ch->n_picks])) return fail(PDMPC_ERR_INVALID, "pdmpc_choice: a pick lists a slot outside the batch");
+    }
+    return PDMPC_OK;
+}
+
+// The block a choice reads back in one copy: the status counters, chosen[n_graphs], cell_cost[n_cells], the picked records.
+struct ChoiceLayout {
+    size_t chosen = 0, cell_cost = 0, picks = 0, bytes = 0;  // (the counters are at 0)
+    explicit ChoiceLayout(const pdmpc_choice& ch) {
+        chosen = PDMPC_CHOICE_COUNTERS * sizeof(int32_t);
+        cell_cost = (chosen + (size_t)ch.n_graphs * sizeof(int32_t) + 7) & ~(size_t)7;
+        picks = cell_cost + (size_t)ch.n_cells * sizeof(double);
+        bytes = picks + (size_t)ch.n_picks * sizeof(pdmpc_vehicle_out);
+    }
+};
+
+// The lists of a checked choice on the n records of the current bank, staged in pinned memory with the caller's slots mapped to the
+// bank's (a batch that pack_common put into its own order) and queued for the device; A: what the kernels take.
+int stage_choice(pdmpc_handle* h, int32_t n, const pdmpc_choice& ch, const ChoiceLayout& L, ChoiceArgs& A) {
+    const PackedStep& B = h->banks[h->bank];
+    const bool permuted = !B.perm.empty();
+    if (permuted ? n != B.n_packed : n > h->max_vehicles) return fail(PDMPC_ERR_INVALID, "pdmpc_choice: the batch is not the one resident in this bank");
+    ChoiceState& S = h->choice;
+    const int n_cell_slots = ch.n_cells > 0 ? ch.cell_offset[ch.n_cells] : 0, n_pick_slots = ch.n_picks > 0 ? ch.pick_offset[ch.n_picks] : 0;
+    const size_t cell_offset = 0, cell_slot = cell_offset + (size_t)ch.n_cells + 1, graph_offset = cell_slot + (size_t)n_cell_slots, pick_graph = graph_offset + (size_t)ch.n_graphs + 1,
+                 pick_offset = pick_graph + (size_t)ch.n_picks, pick_slot = pick_offset + (size_t)ch.n_picks + 1, words = pick_slot + (size_t)n_pick_slots;
+    const bool first_use = !S.tally.p;
+    if (S.h_in.ensure(words) || S.h_out.ensure(L.bytes)) return fail(PDMPC_ERR_HIP, "hipHostMalloc failed for the choice");
+    if (S.in.ensure(words) || S.out.ensure(L.bytes) || S.tally.ensure(PDMPC_CHOICE_COUNTERS)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the choice");
+    if (first_use) HIPCHK(hipMemsetAsync(S.tally.p, 0, PDMPC_CHOICE_COUNTERS * sizeof(int32_t), h->stream));
+    int32_t* w = S.h_in.p;
+    auto to_bank = [&](int32_t* dst, const int32_t* slot, int count) {
+        for (int q = 0; q < count; ++q) dst[q] = permuted ? B.inv[(size_t)slot[q]] : slot[q];
+    };
+    w[cell_offset] = w[graph_offset] = w[pick_offset] = 0;
+    if (ch.n_cells > 0) std::memcpy(w + cell_offset, ch.cell_offset, ((size_t)ch.n_cells + 1) * sizeof(int32_t));
+    to_bank(w + cell_slot, ch.cell_slot, n_cell_slots);
+    if (ch.n_graphs > 0) std::memcpy(w + graph_offset, ch.graph_offset, ((size_t)ch.n_graphs + 1) * sizeof(int32_t));
+    if (ch.n_picks > 0) {
+        std::memcpy(w + pick_graph, ch.pick_graph, (size_t)ch.n_picks * sizeof(int32_t));
+        std::memcpy(w + pick_offset, ch.pick_offset, ((size_t)ch.n_picks + 1) * sizeof(int32_t));
+    }
+    to_bank(w + pick_slot, ch.pick_slot, n_pick_slots);
+    HIPCHK(hipMemcpyAsync(S.in.p, w, words * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    A = ChoiceArgs{};
+    A.rec = h->d_out.p;
+    A.n = n;
+    A.Hp = h->cfg.Hp;
+    A.n_cells = ch.n_cells;
+    A.n_graphs = ch.n_graphs;
+    A.n_picks = ch.n_picks;
+    A.first_graph_cell = ch.n_graphs > 0 ? ch.graph_offset[0] : 0;
+    A.end_graph_cell = ch.n_graphs > 0 ? ch.graph_offset[ch.n_graphs] : 0;
+    A.cell_offset = S.in.p + cell_offset;
+    A.cell_slot = S.in.p + cell_slot;
+    A.graph_offset = S.in.p + graph_offset;
+    A.pick_graph = S.in.p + pick_graph;
+    A.pick_offset = S.in.p + pick_offset;
+    A.pick_slot = S.in.p + pick_slot;
+    A.tally = S.tally.p;
+    A.counters = (int32_t*)S.out.p;
+    A.chosen = (int32_t*)(S.out.p + L.chosen);
+    A.cell_cost = (double*)(S.out.p + L.cell_cost);
+    A.picks = (pdmpc_vehicle_out*)(S.out.p + L.picks);
+    return PDMPC_OK;
+}
+
+// the two launches behind whatever the stream holds (the search's launch: no host synchronisation in between), ONE copy back, one wait
+int fetch_choice(pdmpc_handle* h, const ChoiceArgs& A, const ChoiceLayout& L) {
+    ChoiceState& S = h->choice;
+    for (hipEvent_t& e : S.timed.ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(S.timed.ev[0], h->stream));
+    const int lrc = pdmpc_launch_choice(&A, (void*)h->stream);
+    if (lrc) return fail(PDMPC_ERR_HIP, std::string("choice kernel launch failed: ") + hipGetErrorString((hipError_t)lrc));
+    HIPCHK(hipEventRecord(S.timed.ev[1], h->stream));
+    HIPCHK(hipMemcpyAsync(S.h_out.p, S.out.p, L.bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(sync_stream(h));
+    S.timed.fold();
+    return PDMPC_OK;
+}
+
+// a fetched choice into the caller's arrays; a record that is no planning result fails it as it fails the choice on the host
+int deliver_choice(const pdmpc_handle* h, const pdmpc_choice& ch, const ChoiceLayout& L, int32_t* chosen, double* cell_cost, pdmpc_vehicle_out* picks) {
+    const unsigned char* blk = h->choice.h_out.p;
+    const int32_t* counters = (const int32_t*)blk;
+    if (counters[PDMPC_CHOICE_OVERFLOW] || counters[PDMPC_CHOICE_TIMED_OUT] || counters[PDMPC_CHOICE_OTHER])
+        return fail(PDMPC_ERR_HIP, "a result record carries an error status: not a planning result");
+    if (chosen && ch.n_graphs > 0) std::memcpy(chosen, blk + L.chosen, (size_t)ch.n_graphs * sizeof(int32_t));
+    if (cell_cost && ch.n_cells > 0) std::memcpy(cell_cost, blk + L.cell_cost, (size_t)ch.n_cells * sizeof(double));
+    if (ch.n_picks > 0) std::memcpy(picks, blk + L.picks, (size_t)ch.n_picks * sizeof(pdmpc_vehicle_out));
+    return PDMPC_OK;
+}
+
+// Where a plan's read-back lands: every record, (lean) the (status, cost) pair of every vehicle (fetch_lean), or (chosen) the block of
+// a choice made on the device (fetch_choice).  Caller's order.
 struct Sink {
-    bool lean;
+    enum Kind { kRecords, kLean, kChosen } kind;
     pdmpc_vehicle_out* out;
     int32_t* status;
     double* cost;
-    static Sink records(pdmpc_vehicle_out* out) { return {false, out, nullptr, nullptr}; }
-    static Sink lean_pair(int32_t* status, double* cost) { return {true, nullptr, status, cost}; }
-    int fetch(pdmpc_handle* h, int32_t n) const { return lean ? fetch_lean(h, n, status, cost) : pdmpc_fetch_results(h, n, out); }
-    int32_t status_at(int i) const { return lean ? status[i] : out[i].status; }
+    const ChoiceArgs* choice;
+    const ChoiceLayout* layout;
+    static Sink records(pdmpc_vehicle_out* out) { return {kRecords, out, nullptr, nullptr, nullptr, nullptr}; }
+    static Sink lean_pair(int32_t* status, double* cost) { return {kLean, nullptr, status, cost, nullptr, nullptr}; }
+    static Sink chosen(const ChoiceArgs* choice, const ChoiceLayout* layout) { return {kChosen, nullptr, nullptr, nullptr, choice, layout}; }
+    int fetch(pdmpc_handle* h, int32_t n) const {
+        if (kind == kChosen) return fetch_choice(h, *choice, *layout);
+        return kind == kLean ? fetch_lean(h, n, status, cost) : pdmpc_fetch_results(h, n, out);
+    }
+    // which of the batch's records outgrew their arena / gave up waiting for a predecessor: from the records' statuses, or (chosen)
+    // from the counters the choice kept on the device
+    void verdict(const pdmpc_handle* h, int32_t n, bool& overflow, bool& timed_out) const {
+        overflow = timed_out = false;
+        if (kind == kChosen) {
+            const int32_t* counters = (const int32_t*)h->choice.h_out.p;
+            overflow = counters[PDMPC_CHOICE_OVERFLOW] != 0;
+            timed_out = counters[PDMPC_CHOICE_TIMED_OUT] != 0;
+            return;
+        }
+        for (int i = 0; i < n; ++i) {
+            const int st = kind == kLean ? status[i] : out[i].status;
+            overflow = overflow || st == PDMPC_ARENA_OVERFLOW;
+            timed_out = timed_out || st == PDMPC_ERR_HIP;
+        }
+    }
 };
 
 // Arenas of `nodes` nodes per vehicle, or (grown == false) the ones there were if HBM has no room for them.
@@ -818,13 +970,9 @@ int plan_packed_growing(pdmpc_handle* h, int32_t n, const Sink& sink) {
             float ms = 0.f;
             if (h->timer.last_ms(ms)) h->dbg_us[3] += 1e3 * ms;
         }
-        if (dbg) fprintf(stderr, "pdmpc: fetched, status[0] %d\n", n > 0 ? sink.status_at(0) : 0);
         bool overflow = false, timed_out = false;
-        for (int i = 0; i < n; ++i) {
-            const int st = sink.status_at(i);
-            overflow = overflow || st == PDMPC_ARENA_OVERFLOW;
-            timed_out = timed_out || st == PDMPC_ERR_HIP;
-        }
+        sink.verdict(h, n, overflow, timed_out);
+        if (dbg) fprintf(stderr, "pdmpc: fetched, overflow %d, timed out %d\n", (int)overflow, (int)timed_out);
         if (timed_out && safe)
             return fail(PDMPC_ERR_HIP, "a search gave up waiting for a predecessor although the call was planned in resident slices without helper workgroups (records carry PDMPC_ERR_HIP)");
         if (timed_out && !safe) {
@@ -873,6 +1021,64 @@ int pdmpc_plan_step_lean(pdmpc_handle* h, int32_t n, const pdmpc_vehicle_in* in,
     if (!h || n < 0 || (n > 0 && (!status || !final_cost))) return fail(PDMPC_ERR_INVALID, "null argument");
     const int rc = timed_pack(h, n, in, pred_offset, pred_index, fallback_shapes);
     return rc ? rc : plan_packed_growing(h, n, Sink::lean_pair(status, final_cost));
+}
+
+int pdmpc_choose_host(int32_t n, const int32_t* status, const double* final_cost, const pdmpc_choice* ch, int32_t* chosen, double* cell_cost) {
+    if (n > 0 && (!status || !final_cost)) return fail(PDMPC_ERR_INVALID, "null argument");
+    if (const int rc = check_choice(n, ch)) return rc;
+    for (int i = 0; i < n; ++i)
+        if (status[i] != PDMPC_OK && status[i] != PDMPC_EXHAUSTED) return fail(PDMPC_ERR_HIP, "a result record carries an error status: not a planning result");
+    std::vector<double> sums((size_t)ch->n_cells);
+    for (int c = 0; c < ch->n_cells; ++c) {
+        double sum = 0.0;
+        for (int q = ch->cell_offset[c]; q < ch->cell_offset[c + 1]; ++q) {  // (list order: the order of addition)
+            const int s = ch->cell_slot[q];
+            sum += status[s] == PDMPC_OK ? final_cost[s] : std::numeric_limits<double>::infinity();
+        }
+        sums[(size_t)c] = std::nearbyint(sum * 1e8) / 1e8;
+    }
+    if (chosen)
+        for (int g = 0; g < ch->n_graphs; ++g) {
+            const double* cand = sums.data() + ch->graph_offset[g];
+            const int count = ch->graph_offset[g + 1] - ch->graph_offset[g];
+            int best = 0;
+            for (int p = 1; p < count; ++p)
+                if (cand[p] < cand[best]) best = p;  // [~, i] = min(.): the first minimum
+            chosen[g] = best;
+        }
+    if (cell_cost && ch->n_cells > 0) std::memcpy(cell_cost, sums.data(), sums.size() * sizeof(double));
+    return PDMPC_OK;
+}
+
+int pdmpc_choose_resident(pdmpc_handle* h, int32_t n, const pdmpc_choice* ch, int32_t* chosen, double* cell_cost, pdmpc_vehicle_out* picks) {
+    if (!h || (ch && ch->n_picks > 0 && !picks)) return fail(PDMPC_ERR_INVALID, "null argument");
+    if (const int rc = check_choice(n, ch)) return rc;
+    ON_DEVICE(h->cfg.device);
+    const ChoiceLayout L(*ch);
+    ChoiceArgs A;
+    int rc = stage_choice(h, n, *ch, L, A);
+    if (!rc) rc = fetch_choice(h, A, L);
+    return rc ? rc : deliver_choice(h, *ch, L, chosen, cell_cost, picks);
+}
+
+int pdmpc_plan_step_chosen(pdmpc_handle* h, int32_t n, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index, const pdmpc_polygon_set* fallback_shapes,
+                           const pdmpc_choice* ch, int32_t* chosen, double* cell_cost, pdmpc_vehicle_out* picks) {
+    if (!h || (ch && ch->n_picks > 0 && !picks)) return fail(PDMPC_ERR_INVALID, "null argument");
+    if (const int rc = check_choice(n, ch)) return rc;
+    int rc = timed_pack(h, n, in, pred_offset, pred_index, fallback_shapes);
+    if (rc) return rc;
+    ON_DEVICE(h->cfg.device);
+    const ChoiceLayout L(*ch);
+    ChoiceArgs A;
+    rc = stage_choice(h, n, *ch, L, A);  // (once: a launch that is repeated with larger arenas or in slices chooses on the same lists)
+    if (!rc) rc = plan_packed_growing(h, n, Sink::chosen(&A, &L));
+    return rc ? rc : deliver_choice(h, *ch, L, chosen, cell_cost, picks);
+}
+
+int pdmpc_choice_kernel_ms(pdmpc_handle* h, double* ms) {
+    if (!h || !ms) return fail(PDMPC_ERR_INVALID, "null argument");
+    *ms = h->choice.timed.ms;
+    return PDMPC_OK;
 }
 
 int pdmpc_last_call_timing(pdmpc_handle* h, double* us3) {

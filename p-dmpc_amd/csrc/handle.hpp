@@ -406,6 +406,16 @@ struct FcaState {
     TimedLaunch timed;
 };
 
+// pdmpc_choose_resident / pdmpc_plan_step_chosen (choice_kernel.hip): the staged lists, the read-back block (counters, chosen, cell
+// costs, picked records: ChoiceLayout in api.cpp) and the status tally; grown when a call needs more, kept otherwise
+struct ChoiceState {
+    DevBuf<int32_t> in, tally;
+    PinnedBuf<int32_t> h_in;
+    DevBuf<unsigned char> out;
+    PinnedBuf<unsigned char> h_out;
+    TimedLaunch timed;
+};
+
 struct pdmpc_handle {
     pdmpc_config cfg{};
     Tuning tune{};
@@ -440,6 +450,7 @@ struct pdmpc_handle {
     ReachState reach;
     BoundState bound;
     FcaState fca;
+    ChoiceState choice;
     int device_share = 1;                // handles of one process that launch on this device side by side (pdmpc_set_device_share: a group's logical ranks)
     bool boards_dirty = true;            // the helper boards / the finished counter need clearing before the helper workgroups may read them
     uint32_t help_fin_total = 0;         // value of the finished counter once every launch so far has ended

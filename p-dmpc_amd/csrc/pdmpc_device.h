@@ -370,9 +370,34 @@ struct FcaArgs {
     int32_t* counts;            // [n]
 };
 
+// The choice among the plans of a batch (choice_kernel.hip; pdmpc_choice in include/pdmpc.h) on the result records
+// where the search left them.  The lists are the caller's with the slots mapped to record slots and checked on the host (api.cpp:
+// stage_choice); cells of no graph are the cells in front of first_graph_cell and from end_graph_cell on.
+#define PDMPC_CHOICE_GATHER_BLOCK 256  // lanes of the workgroup that copies one picked record
+enum { PDMPC_CHOICE_OVERFLOW = 0, PDMPC_CHOICE_TIMED_OUT = 1, PDMPC_CHOICE_OTHER = 2, PDMPC_CHOICE_COUNTERS = 4 };
+struct ChoiceArgs {
+    const pdmpc_vehicle_out* rec;  // the result records (the handle's d_out)
+    int32_t n, Hp;                 // records of the batch, the row of path_nodes whose g is the plan's cost
+    int32_t n_cells, n_graphs, n_picks;
+    int32_t first_graph_cell, end_graph_cell;
+    const int32_t* cell_offset;    // [n_cells + 1]
+    const int32_t* cell_slot;
+    const int32_t* graph_offset;   // [n_graphs + 1]
+    const int32_t* pick_graph;     // [n_picks]
+    const int32_t* pick_offset;    // [n_picks + 1]
+    const int32_t* pick_slot;
+    int32_t* tally;                // [PDMPC_CHOICE_COUNTERS] records per non-planning status, counted by the first pass; zero between calls
+    int32_t* counters;             // [PDMPC_CHOICE_COUNTERS] ... as the call reads them back (the second pass moves them here and clears the tally)
+    int32_t* chosen;               // [n_graphs]
+    double* cell_cost;             // [n_cells]
+    pdmpc_vehicle_out* picks;      // [n_picks]
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+// choice_kernel.hip: the sums, status counters and first minima in one launch, the gather of the picked records in a second
+int pdmpc_launch_choice(const ChoiceArgs* args, void* stream);
 // fca_kernel.hip: the footprint pass (which also clears the counts) and the item pass on the handle's stream
 int pdmpc_launch_fca(const FcaArgs* args, void* stream);
 // fca.cpp: the argument checks pdmpc_fca_collisions and its host twin share (PDMPC_OK, or an error code with *why set), and the

@@ -84,6 +84,33 @@ struct VehicleDef {
 
 }  // namespace
 
+// A choice among the plans of a batch as pdmpc_choose_host / pdmpc_plan_step_chosen take it (pdmpc_choice): the lists, kept from step to step
+struct ChoiceLists {
+    std::vector<int32_t> cell_offset, cell_slot, graph_offset, pick_graph, pick_offset, pick_slot;
+    std::vector<int32_t> graph_of;  // the explorative choice: per vehicle its sub-graph
+    int n_cells() const { return cell_offset.empty() ? 0 : (int)cell_offset.size() - 1; }
+    int n_graphs() const { return graph_offset.empty() ? 0 : (int)graph_offset.size() - 1; }
+    int n_picks() const { return (int)pick_graph.size(); }
+    void clear_picks() {
+        pick_graph.clear();
+        pick_slot.clear();
+        pick_offset.assign(1, 0);
+    }
+    pdmpc_choice view() const {
+        pdmpc_choice ch{};
+        ch.n_cells = n_cells();
+        ch.n_graphs = n_graphs();
+        ch.n_picks = n_picks();
+        ch.cell_offset = cell_offset.data();
+        ch.cell_slot = cell_slot.data();
+        ch.graph_offset = graph_offset.data();
+        ch.pick_graph = pick_graph.data();
+        ch.pick_offset = pick_offset.data();
+        ch.pick_slot = pick_slot.data();
+        return ch;
+    }
+};
+
 struct pdmpc_controller {
     pdmpc_handle* h = nullptr;
     pdmpc_controller_config cfg{};
@@ -98,8 +125,12 @@ struct pdmpc_controller {
     std::vector<Plan> info_old, infos;
     bool follow_own = false;                // the explorative step applies the plans of the controller's OWN prioritization (instance 0) whatever the choice: the traffic then follows pdmpc_controller_step's closed loop (measurement: the same steps as a recorded replay)
     bool lean_explore = false;              // the explorative step reads back status + final cost of every plan and the chosen plans' records only
+    bool device_choice = false;             // pdmpc_controller_set_device_choice: the lean step chooses and gathers on the device (pdmpc_plan_step_chosen)
     std::vector<int32_t> x_status;
     std::vector<double> x_final_cost;
+    ChoiceLists choice;                     // the choice of the last explorative / optimal-priority step as data, and what came back for it:
+    std::vector<int32_t> choice_chosen;     // [graphs] the candidate every graph chose
+    std::vector<double> choice_cost;        // [cells]
     double timing[6] = {0, 0, 0, 0, 0, 0};  // pdmpc_controller_last_timing
     double timing_sum[6] = {0, 0, 0, 0, 0, 0};  // ... summed over the steps since the last pdmpc_controller_timing_sum(reset)
     int64_t timing_steps = 0;
@@ -198,7 +229,6 @@ struct pdmpc_controller {
     // optimal-priority step (PrioritizedOptimalController): the unique prioritizations of the step's coupling graph
     std::vector<uint32_t> o_masks;  // [K] the acyclic orientations (pdmpc_unique_priorities)
     std::vector<int32_t> o_prio;    // [K x n] their priorities
-    std::vector<double> o_val;      // [K x n] choice scratch: cost-to-come of the final node per (instance, vehicle), inf if exhausted
     // reachable sets (pdmpc_controller_set_reachability): the automaton's local hulls, polygon trim * Hp + k, and per
     // step every vehicle's Hp sets at its pose, closed (HighLevelController.m:219-263)
     int parallel_mode = PDMPC_PARALLEL_PREVIOUS_TRAJECTORY;
@@ -1752,11 +1782,21 @@ void flatten_instances(pdmpc_controller* c, int K) {
 }
 }  // namespace
 
+namespace {
+int permute_instances(pdmpc_controller* c, int32_t n_perm, uint32_t seed);
+}
 int pdmpc_controller_explore_build(pdmpc_controller* c, int32_t n_perm, uint32_t seed) {
     if (!c || n_perm < 1) return cfail(c, PDMPC_ERR_INVALID, "bad argument");
     Exploring exploring(c);
     int rc = pdmpc_controller_build_step(c);  // instance 0: the controller's own prioritization
     if (rc) return rc;
+    return permute_instances(c, n_perm, seed);
+}
+namespace {
+// pdmpc_controller_explore_build behind its pdmpc_controller_build_step (a sweep runs that part for all its members at once, then this
+// one per member): the step just built is instance 0, instances 1 .. n_perm - 1 permute its computation levels
+int permute_instances(pdmpc_controller* c, int32_t n_perm, uint32_t seed) {
+    int rc = PDMPC_OK;
     const int n = c->n;
     // base levels: the computation levels of the controller's own prioritization -- kahn of the sequential coupling the step was
     // just built with, whatever the priority strategy (PrioritizedExplorativeController.m prepare_permutation :42-58 permutes
@@ -1796,6 +1836,7 @@ int pdmpc_controller_explore_build(pdmpc_controller* c, int32_t n_perm, uint32_t
     set_seeds(c, c->x_vehicle);
     return PDMPC_OK;
 }
+}  // namespace
 
 int pdmpc_controller_explore_problem(pdmpc_controller* c, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index,
                                      const pdmpc_polygon_set** fallback, const int32_t** instance, const int32_t** vehicle, const int32_t** level) {
@@ -1830,8 +1871,9 @@ int pdmpc_controller_explore_choose(pdmpc_controller* c, const pdmpc_vehicle_out
     return explore_choose_on(c, st.data(), fc.data(), chosen, n_graphs, cost);
 }
 namespace {
-// (status and cost-to-come of the final node per slot of the batch: all the choice looks at)
-int explore_choose_on(pdmpc_controller* c, const int32_t* status, const double* final_cost, int32_t* chosen, int32_t* n_graphs, double* cost) {
+// The explorative choice as data: graph g = a weakly connected sub-graph (ordered by smallest vehicle), its candidates the n_perm
+// instances, cell (g, p) = the slots of instance p whose vehicles belong to g in ascending slot order (the order the twin adds in).
+void explore_describe(pdmpc_controller* c, ChoiceLists& D) {
     const int n = c->n, K = (int)c->inst.size();
     std::vector<int> label((size_t)n);
     for (int i = 0; i < n; ++i) label[(size_t)i] = i;
@@ -1846,26 +1888,33 @@ int explore_choose_on(pdmpc_controller* c, const int32_t* status, const double* 
                 const int a = find(i), b = find(j);
                 if (a != b) label[(size_t)std::max(a, b)] = std::min(a, b);
             }
-    std::vector<int> graph_of((size_t)n), roots;
+    std::vector<int> roots;
     for (int i = 0; i < n; ++i)
         if (find(i) == i) roots.push_back(i);  // ascending: the graphs ordered by their smallest vehicle
-    for (int i = 0; i < n; ++i) graph_of[(size_t)i] = (int)(std::lower_bound(roots.begin(), roots.end(), find(i)) - roots.begin());
-    const int G = (int)roots.size();
+    D.graph_of.resize((size_t)n);
+    for (int i = 0; i < n; ++i) D.graph_of[(size_t)i] = (int32_t)(std::lower_bound(roots.begin(), roots.end(), find(i)) - roots.begin());
+    const int G = (int)roots.size(), N = K * n;
+    D.graph_offset.resize((size_t)G + 1);
+    for (int g = 0; g <= G; ++g) D.graph_offset[(size_t)g] = g * K;
+    // cell (g, p) at g * K + p: counted, then filled in slot order
+    D.cell_offset.assign((size_t)G * K + 1, 0);
+    auto cell_of = [&](int s) { return D.graph_of[(size_t)c->x_vehicle[(size_t)s]] * K + c->x_instance[(size_t)s]; };
+    for (int s = 0; s < N; ++s) D.cell_offset[(size_t)cell_of(s) + 1] += 1;
+    for (int q = 0; q < G * K; ++q) D.cell_offset[(size_t)q + 1] += D.cell_offset[(size_t)q];
+    D.cell_slot.resize((size_t)N);
+    std::vector<int32_t> fill(D.cell_offset.begin(), D.cell_offset.end() - 1);
+    for (int s = 0; s < N; ++s) D.cell_slot[(size_t)fill[(size_t)cell_of(s)]++] = s;
+    D.clear_picks();
+}
+// ... and what the sub-graphs chose becomes the controller's: cost table n_perm x n_graphs, the instance per vehicle, its couplings
+void explore_adopt(pdmpc_controller* c, const ChoiceLists& D, const int32_t* chosen, const double* cell_cost) {
+    const int n = c->n, K = (int)c->inst.size(), G = D.n_graphs();
     c->x_graphs = G;
-    c->x_cost.assign((size_t)K * G, 0.0);
-    const int N = K * n;
-    for (int s = 0; s < N; ++s) {  // (slot order: the order the twin adds in)
-        if (status[s] != PDMPC_OK && status[s] != PDMPC_EXHAUSTED) return cfail(c, PDMPC_ERR_HIP, "a result record carries an error status: not a planning result");
-        const double v = status[s] == PDMPC_OK ? final_cost[s] : std::numeric_limits<double>::infinity();
-        c->x_cost[(size_t)c->x_instance[(size_t)s] * G + graph_of[(size_t)c->x_vehicle[(size_t)s]]] += v;
-    }
-    for (double& v : c->x_cost) v = std::nearbyint(v * 1e8) / 1e8;
-    std::vector<int> best((size_t)G, 0);
-    for (int g = 0; g < G; ++g)
-        for (int p = 1; p < K; ++p)
-            if (c->x_cost[(size_t)p * G + g] < c->x_cost[(size_t)best[(size_t)g] * G + g]) best[(size_t)g] = p;  // [~, chosen] = min(.): the first minimum
+    c->x_cost.resize((size_t)K * G);
+    for (int p = 0; p < K; ++p)
+        for (int g = 0; g < G; ++g) c->x_cost[(size_t)p * G + g] = cell_cost[(size_t)g * K + p];
     c->x_chosen.resize((size_t)n);
-    for (int i = 0; i < n; ++i) c->x_chosen[(size_t)i] = best[(size_t)graph_of[(size_t)i]];
+    for (int i = 0; i < n; ++i) c->x_chosen[(size_t)i] = chosen[(size_t)D.graph_of[(size_t)i]];
     // obj.iter = obj.iter_array_tmp{chosen_solution} (:157-158): every vehicle goes on with the couplings of its sub-graph's choice
     for (int i = 0; i < n; ++i)
         for (int j = 0; j < n; ++j) {
@@ -1873,8 +1922,44 @@ int explore_choose_on(pdmpc_controller* c, const int32_t* status, const double* 
             at(c->directed, n, i, j) = at(I.directed, n, i, j);
             at(c->directed_seq, n, i, j) = at(I.directed_seq, n, i, j);
         }
+}
+
+// How a step over a batch of prioritizations chooses: the description of its choice (cells and graphs) and what adopts the result.
+struct BatchChoice {
+    void (*describe)(pdmpc_controller*, ChoiceLists&);
+    void (*adopt)(pdmpc_controller*, const ChoiceLists&, const int32_t*, const double*);
+    bool graph_per_vehicle;  // the optimal-priority choice: vehicle v's graph is graph v (else its sub-graph)
+};
+// the choice on the host twin (status and cost-to-come of the final node per slot of the batch: all the choice looks at)
+int choose_on_host(pdmpc_controller* c, const BatchChoice& how, const int32_t* status, const double* final_cost) {
+    ChoiceLists& D = c->choice;
+    how.describe(c, D);
+    c->choice_chosen.resize((size_t)D.n_graphs());
+    c->choice_cost.resize((size_t)D.n_cells());
+    const pdmpc_choice ch = D.view();
+    const int rc = pdmpc_choose_host((int32_t)c->x_in.size(), status, final_cost, &ch, c->choice_chosen.data(), c->choice_cost.data());
+    if (rc) return cfail(c, rc, pdmpc_last_error());
+    how.adopt(c, D, c->choice_chosen.data(), c->choice_cost.data());
+    return PDMPC_OK;
+}
+// the picks of a step that keeps the chosen plans only: per slot of the controller's own order its vehicle's record of the chosen
+// instance, or (follow_own) of instance 0
+void pick_chosen_plans(pdmpc_controller* c, ChoiceLists& D, bool follow_own, bool graph_per_vehicle) {
+    const int n = c->n, K = (int)c->inst.size();
+    D.clear_picks();
+    for (int s = 0; s < n; ++s) {
+        const int v = c->order[(size_t)s];
+        D.pick_graph.push_back(follow_own ? -1 : (graph_per_vehicle ? v : D.graph_of[(size_t)v]));
+        for (int p = 0; p < (follow_own ? 1 : K); ++p) D.pick_slot.push_back(c->x_slot[(size_t)p * n + v]);
+        D.pick_offset.push_back((int32_t)D.pick_slot.size());
+    }
+}
+const BatchChoice kExploreChoice = {explore_describe, explore_adopt, false};
+
+int explore_choose_on(pdmpc_controller* c, const int32_t* status, const double* final_cost, int32_t* chosen, int32_t* n_graphs, double* cost) {
+    if (const int rc = choose_on_host(c, kExploreChoice, status, final_cost)) return rc;
     if (chosen) std::copy(c->x_chosen.begin(), c->x_chosen.end(), chosen);
-    if (n_graphs) *n_graphs = G;
+    if (n_graphs) *n_graphs = c->x_graphs;
     if (cost) std::copy(c->x_cost.begin(), c->x_cost.end(), cost);
     return PDMPC_OK;
 }
@@ -1882,10 +1967,8 @@ int explore_choose_on(pdmpc_controller* c, const int32_t* status, const double* 
 
 // One time step over a batch of prioritizations (explorative or optimal): the batch is built, ONE launch plans all of it, `choose`
 // picks per vehicle the instance it goes on with (c->x_chosen), and the chosen plans are applied.
-extern "C++" {
 namespace {
-template <class Choose>
-int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, bool follow_own, Choose&& choose) {
+int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, bool follow_own, const BatchChoice& how) {
     c->timing[0] = ms_since(t);
     const int N = (int)c->x_in.size();
     c->x_out.resize((size_t)N);
@@ -1896,7 +1979,24 @@ int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, boo
     }
     int rc = seeds_for_next_pack(c);
     if (rc) return rc;
-    if (c->lean_explore) {
+    if (c->lean_explore && c->device_choice) {
+        // the closed loop keeps the chosen plans only, and the choice and their gather run on the device directly behind the search: ONE
+        // call and one read-back (the chosen records, the choice and the cost table)
+        c->x_out.clear();
+        ChoiceLists& D = c->choice;
+        how.describe(c, D);
+        pick_chosen_plans(c, D, follow_own, how.graph_per_vehicle);
+        c->choice_chosen.resize((size_t)D.n_graphs());
+        c->choice_cost.resize((size_t)D.n_cells());
+        c->out.resize((size_t)c->n);
+        const pdmpc_choice ch = D.view();
+        rc = pdmpc_plan_step_chosen(c->h, N, c->x_in.data(), c->x_pred_offset.data(), c->x_pred_index.data(), c->x_fb.data(), &ch, c->choice_chosen.data(),
+                                    c->choice_cost.data(), c->out.data());
+        if (rc) return cfail(c, rc, pdmpc_last_error());
+        add_call_timing(c);
+        t = std::chrono::steady_clock::now();
+        how.adopt(c, D, c->choice_chosen.data(), c->choice_cost.data());
+    } else if (c->lean_explore) {
         // the closed loop keeps the chosen plans only (obj.iter = obj.iter_array_tmp{chosen_solution}, :157-158): status and final
         // cost of every plan come back for the choice, the chosen vehicles' records afterwards — not 2.9 KB for each of the N plans
         c->x_out.clear();
@@ -1906,7 +2006,7 @@ int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, boo
         if (rc) return cfail(c, rc, pdmpc_last_error());
         add_call_timing(c);
         t = std::chrono::steady_clock::now();
-        rc = choose(c->x_status.data(), c->x_final_cost.data());
+        rc = choose_on_host(c, how, c->x_status.data(), c->x_final_cost.data());
         if (rc) return rc;
         std::vector<int32_t> want((size_t)c->n);
         for (int s = 0; s < c->n; ++s) {
@@ -1927,7 +2027,7 @@ int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, boo
             c->x_status[(size_t)s] = c->x_out[(size_t)s].status;
             c->x_final_cost[(size_t)s] = c->x_out[(size_t)s].path_nodes[c->Hp][4];
         }
-        rc = choose(c->x_status.data(), c->x_final_cost.data());
+        rc = choose_on_host(c, how, c->x_status.data(), c->x_final_cost.data());
         if (rc) return rc;
         c->out.resize((size_t)c->n);
         for (int s = 0; s < c->n; ++s) {
@@ -1948,7 +2048,6 @@ int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, boo
     return rc;
 }
 }  // namespace
-}  // extern "C++"
 
 // One explorative time step: build the batch, plan all prioritizations with ONE launch, choose per sub-graph, apply the chosen plans.
 int pdmpc_controller_explore_step(pdmpc_controller* c, int32_t n_perm) {
@@ -1956,7 +2055,13 @@ int pdmpc_controller_explore_step(pdmpc_controller* c, int32_t n_perm) {
     const auto t = std::chrono::steady_clock::now();
     const int rc = pdmpc_controller_explore_build(c, n_perm, (uint32_t)(c->k + 1));  // RandStream("mt19937ar", Seed = obj.k) (:249)
     if (rc) return rc;
-    return batch_step(c, t, c->follow_own, [c](const int32_t* status, const double* final_cost) { return explore_choose_on(c, status, final_cost, nullptr, nullptr, nullptr); });
+    return batch_step(c, t, c->follow_own, kExploreChoice);
+}
+
+int pdmpc_controller_set_device_choice(pdmpc_controller* c, int32_t on) {
+    if (!c) return cfail(c, PDMPC_ERR_INVALID, "null argument");
+    c->device_choice = on != 0;
+    return PDMPC_OK;
 }
 
 int pdmpc_controller_explore_follow_own(pdmpc_controller* c, int32_t on) {
@@ -2088,29 +2193,29 @@ int pdmpc_controller_optimal_build(pdmpc_controller* c, int32_t max_instances) {
 // compute_solution_cost / receive_solution_cost / choose_solution (:56-114): every vehicle sums the solution costs of ALL vehicles per
 // instance (its own first, then the others' messages in ascending index), rounds to 8 decimals and takes the first minimum
 namespace {
-int optimal_choose_on(pdmpc_controller* c, const int32_t* status, const double* final_cost) {
+// The optimal-priority choice as data: graph v = vehicle v, its candidates the K instances, cell (v, p) = vehicle v's slot of instance p,
+// then the other vehicles' slots of instance p in ascending vehicle index
+void optimal_describe(pdmpc_controller* c, ChoiceLists& D) {
     const int n = c->n, K = (int)c->inst.size();
-    std::vector<double>& val = c->o_val;  // [p * n + v]
-    val.assign((size_t)K * n, 0.0);
-    for (int s = 0; s < K * n; ++s) {
-        if (status[s] != PDMPC_OK && status[s] != PDMPC_EXHAUSTED) return cfail(c, PDMPC_ERR_HIP, "a result record carries an error status: not a planning result");
-        val[(size_t)c->x_instance[(size_t)s] * n + c->x_vehicle[(size_t)s]] = status[s] == PDMPC_OK ? final_cost[s] : std::numeric_limits<double>::infinity();
-    }
-    c->x_cost.assign((size_t)n * K, 0.0);
-    c->x_chosen.resize((size_t)n);
-    for (int v = 0; v < n; ++v) {
-        double* row = c->x_cost.data() + (size_t)v * K;
+    D.graph_of.clear();
+    D.graph_offset.resize((size_t)n + 1);
+    for (int v = 0; v <= n; ++v) D.graph_offset[(size_t)v] = v * K;
+    D.cell_offset.resize((size_t)n * K + 1);
+    for (int q = 0; q <= n * K; ++q) D.cell_offset[(size_t)q] = q * n;
+    D.cell_slot.resize((size_t)n * K * n);
+    int32_t* slot = D.cell_slot.data();
+    for (int v = 0; v < n; ++v)
         for (int p = 0; p < K; ++p) {
-            double sum = val[(size_t)p * n + v];
+            *slot++ = c->x_slot[(size_t)p * n + v];
             for (int j = 0; j < n; ++j)
-                if (j != v) sum += val[(size_t)p * n + j];
-            row[p] = std::nearbyint(sum * 1e8) / 1e8;
+                if (j != v) *slot++ = c->x_slot[(size_t)p * n + j];
         }
-        int best = 0;
-        for (int p = 1; p < K; ++p)
-            if (row[p] < row[best]) best = p;  // [~, chosen_solution] = min(.): the first minimum
-        c->x_chosen[(size_t)v] = best;
-    }
+    D.clear_picks();
+}
+void optimal_adopt(pdmpc_controller* c, const ChoiceLists&, const int32_t* chosen, const double* cell_cost) {
+    const int n = c->n, K = (int)c->inst.size();
+    c->x_cost.assign(cell_cost, cell_cost + (size_t)n * K);  // row v = vehicle v's sums
+    c->x_chosen.assign(chosen, chosen + n);
     c->x_graphs = K;
     // obj.iter = obj.iter_array_tmp{chosen_solution} (:100): every vehicle goes on with the couplings of its chosen instance
     for (int i = 0; i < n; ++i) {
@@ -2120,8 +2225,9 @@ int optimal_choose_on(pdmpc_controller* c, const int32_t* status, const double* 
             at(c->directed_seq, n, i, j) = at(I.directed_seq, n, i, j);
         }
     }
-    return PDMPC_OK;
 }
+const BatchChoice kOptimalChoice = {optimal_describe, optimal_adopt, true};
+int optimal_choose_on(pdmpc_controller* c, const int32_t* status, const double* final_cost) { return choose_on_host(c, kOptimalChoice, status, final_cost); }
 }  // namespace
 
 int pdmpc_controller_optimal_choose(pdmpc_controller* c, const pdmpc_vehicle_out* recs, int32_t* chosen, double* cost) {
@@ -2146,7 +2252,7 @@ int pdmpc_controller_optimal_step(pdmpc_controller* c, int32_t max_instances) {
     const auto t = std::chrono::steady_clock::now();
     const int rc = pdmpc_controller_optimal_build(c, max_instances);
     if (rc) return rc;
-    return batch_step(c, t, false, [c](const int32_t* status, const double* final_cost) { return optimal_choose_on(c, status, final_cost); });
+    return batch_step(c, t, false, kOptimalChoice);
 }
 
 int pdmpc_controller_optimal_run(pdmpc_controller* c, int32_t max_instances, int32_t n_steps, double* ms) {
@@ -2196,6 +2302,21 @@ struct pdmpc_sweep {
     std::vector<uint32_t> seeds;
     std::vector<double> weights;
     std::vector<pdmpc_vehicle_out> out;
+    // the concatenated explorative batch (pdmpc_sweep_explore_*): the members' flattened batches one after the other, and their choices
+    struct Batch {
+        int n_perm = 0;              // of the batch that is built (0: none)
+        std::vector<int32_t> first;  // [M + 1] member m's first slot of the batch
+        std::vector<pdmpc_vehicle_in> in;
+        std::vector<pdmpc_polygon_set> fb;
+        std::vector<int32_t> pred_offset, pred_index, member, instance, vehicle, level;
+        std::vector<uint32_t> seeds;
+        std::vector<double> weights;
+        std::vector<ChoiceLists> lists;                           // per member, slots of its own batch
+        ChoiceLists all;                                          // ... concatenated, slots of the whole batch
+        std::vector<int32_t> first_graph, first_cell, chosen;     // [M + 1] each member's part of `all`; what the graphs chose
+        std::vector<double> cell_cost;
+        std::vector<pdmpc_vehicle_out> picks;                     // member after member, each in its own slot order
+    } x;
     // one grouped step-preparation call: the vehicles of the members that take part, member after member
     struct Call {
         std::vector<int> who;                // members
@@ -2366,8 +2487,20 @@ int sweep_couple_hulls(pdmpc_sweep* s, const std::vector<int>& who) {
     return PDMPC_OK;
 }
 
-int sweep_build(pdmpc_sweep* s) {
+// every member's step problem, built with ONE step preparation for all of them; n_perm > 0: every member's explorative batch of n_perm
+// prioritizations behind it (pdmpc_controller_explore_build's statements, in its order, per member)
+int sweep_build_members(pdmpc_sweep* s, int n_perm) {
     const size_t M = s->members.size();
+    struct ExploringAll {  // (the members' memos of the obstacle sets are on while their prioritizations are assembled)
+        pdmpc_sweep* s;
+        bool on;
+        ExploringAll(pdmpc_sweep* sw, bool o) : s(sw), on(o) { set(on); }
+        ~ExploringAll() { set(false); }
+        void set(bool v) {
+            if (on)
+                for (pdmpc_controller* c : s->members) c->exploring = v;
+        }
+    } exploring(s, n_perm > 0);
     s->prep.assign(M, StepPrep());
     for (size_t m = 0; m < M; ++m)
         if (const int rc = begin_step(s->members[m], s->prep[m])) return rc;
@@ -2396,8 +2529,15 @@ int sweep_build(pdmpc_sweep* s) {
         const StepPrep& P = s->prep[m];
         rc = couple(c, P.bounded ? (P.reach_parallel ? c->Hp : 1) : 0, true);
         if (!rc) rc = finish_step(c);
+        if (!rc && n_perm > 0) rc = permute_instances(c, n_perm, (uint32_t)c->k);  // RandStream("mt19937ar", Seed = obj.k) (:249)
         if (rc) return rc;
     }
+    return PDMPC_OK;
+}
+
+int sweep_build(pdmpc_sweep* s) {
+    if (const int rc = sweep_build_members(s, 0)) return rc;
+    const size_t M = s->members.size();
     // the concatenated problem: shallow copies, predecessor slots shifted by the member's first slot
     const int N = N_of(s);
     s->in.resize((size_t)N);
@@ -2442,6 +2582,120 @@ int sweep_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records, bool keep_reco
 int sweep_guard(pdmpc_sweep* s, int rc) {
     if (rc) s->broken = true;
     return rc;
+}
+
+// ---- the explorative step of a sweep
+
+// what pdmpc_sweep_explore_* refuse before any member advances
+int explore_refusal(pdmpc_sweep* s, int32_t n_perm, bool needs_handle) {
+    if (!s) return cfail(nullptr, PDMPC_ERR_INVALID, "null sweep");
+    if (needs_handle && !s->h) return cfail(nullptr, PDMPC_ERR_INVALID, "the sweep has no backend handle");
+    if (s->broken) return cfail(nullptr, PDMPC_ERR_INVALID, "an earlier step of the sweep failed: its members have advanced unevenly");
+    if (n_perm < 1) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_explore: n_perm < 1");
+    if (s->h) {
+        pdmpc_config hc{};
+        int32_t has_mpa = 0;
+        if (pdmpc_get_config(s->h, &hc, &has_mpa) != PDMPC_OK) return cfail(nullptr, PDMPC_ERR_INVALID, "bad backend handle");
+        if ((int64_t)N_of(s) * n_perm > hc.max_vehicles)
+            return cfail(nullptr, PDMPC_ERR_CAPACITY, "pdmpc_sweep_explore: the members' prioritizations are more plans than the handle's max_vehicles");
+    }
+    return PDMPC_OK;
+}
+
+// every member's explorative batch, and the batches one after the other: shallow copies, predecessor slots shifted by the member's first slot
+int sweep_explore_build(pdmpc_sweep* s, int n_perm) {
+    pdmpc_sweep::Batch& X = s->x;
+    X.n_perm = 0;
+    if (const int rc = sweep_build_members(s, n_perm)) return rc;
+    const size_t M = s->members.size();
+    X.first.assign(1, 0);
+    for (size_t m = 0; m < M; ++m) X.first.push_back(X.first.back() + (int32_t)s->members[m]->x_in.size());
+    const int N = X.first.back();
+    X.in.resize((size_t)N);
+    X.fb.resize((size_t)N);
+    X.member.resize((size_t)N);
+    X.instance.resize((size_t)N);
+    X.vehicle.resize((size_t)N);
+    X.level.resize((size_t)N);
+    X.seeds.resize((size_t)N);
+    X.pred_offset.assign((size_t)N + 1, 0);
+    X.pred_index.clear();
+    for (size_t m = 0; m < M; ++m) {
+        const pdmpc_controller* c = s->members[m];
+        const int f = X.first[m];
+        for (int q = 0; q < X.first[m + 1] - f; ++q) {
+            X.in[(size_t)f + q] = c->x_in[(size_t)q];
+            X.fb[(size_t)f + q] = c->x_fb[(size_t)q];
+            X.member[(size_t)f + q] = (int32_t)m;
+            X.instance[(size_t)f + q] = c->x_instance[(size_t)q];
+            X.vehicle[(size_t)f + q] = c->x_vehicle[(size_t)q];
+            X.level[(size_t)f + q] = c->x_level[(size_t)q];
+            X.seeds[(size_t)f + q] = c->seeds[(size_t)q];
+            for (int e = c->x_pred_offset[(size_t)q]; e < c->x_pred_offset[(size_t)q + 1]; ++e) X.pred_index.push_back(f + c->x_pred_index[(size_t)e]);
+            X.pred_offset[(size_t)f + q + 1] = (int32_t)X.pred_index.size();
+        }
+    }
+    X.pred_index.push_back(0);
+    X.n_perm = n_perm;
+    return PDMPC_OK;
+}
+
+// the chosen plans (or, follow-own, the plans of its own prioritization) become the member's records; then its apply
+int apply_chosen(pdmpc_controller* c) {
+    if (c->follow_own) {  // (the couplings of instance 0 again: what apply's fallback handling sees)
+        c->directed = c->inst[0].directed;
+        c->directed_seq = c->inst[0].directed_seq;
+    }
+    return pdmpc_controller_apply(c, c->out.data());
+}
+
+// the records of the whole batch: every member chooses on the host and applies its chosen plans
+int sweep_explore_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records) {
+    const pdmpc_sweep::Batch& X = s->x;
+    for (size_t m = 0; m < s->members.size(); ++m) {
+        pdmpc_controller* c = s->members[m];
+        c->x_out.assign(records + X.first[m], records + X.first[m + 1]);
+        if (const int rc = pdmpc_controller_explore_choose(c, c->x_out.data(), nullptr, nullptr, nullptr)) return rc;
+        c->out.resize((size_t)c->n);
+        for (int q = 0; q < c->n; ++q) {
+            const int v = c->order[(size_t)q];
+            c->out[(size_t)q] = c->x_out[(size_t)c->x_slot[(size_t)(c->follow_own ? 0 : c->x_chosen[(size_t)v]) * c->n + v]];
+        }
+        if (const int rc = apply_chosen(c)) return rc;
+    }
+    return PDMPC_OK;
+}
+
+// the members' choices as ONE pdmpc_choice over the slots of the whole batch
+void concatenate_choices(pdmpc_sweep* s) {
+    pdmpc_sweep::Batch& X = s->x;
+    const size_t M = s->members.size();
+    X.lists.resize(M);
+    ChoiceLists& A = X.all;
+    A.cell_offset.assign(1, 0);
+    A.cell_slot.clear();
+    A.graph_offset.assign(1, 0);
+    A.clear_picks();
+    X.first_graph.assign(1, 0);
+    X.first_cell.assign(1, 0);
+    for (size_t m = 0; m < M; ++m) {
+        pdmpc_controller* c = s->members[m];
+        ChoiceLists& D = X.lists[m];
+        explore_describe(c, D);
+        pick_chosen_plans(c, D, c->follow_own, false);
+        const int32_t f = X.first[m], g0 = X.first_graph[m], c0 = X.first_cell[m], s0 = (int32_t)A.cell_slot.size(), p0 = (int32_t)A.pick_slot.size();
+        for (int q = 1; q <= D.n_cells(); ++q) A.cell_offset.push_back(s0 + D.cell_offset[(size_t)q]);
+        for (int32_t slot : D.cell_slot) A.cell_slot.push_back(f + slot);
+        for (int g = 1; g <= D.n_graphs(); ++g) A.graph_offset.push_back(c0 + D.graph_offset[(size_t)g]);
+        for (int32_t g : D.pick_graph) A.pick_graph.push_back(g < 0 ? -1 : g0 + g);
+        for (int i = 1; i <= D.n_picks(); ++i) A.pick_offset.push_back(p0 + D.pick_offset[(size_t)i]);
+        for (int32_t slot : D.pick_slot) A.pick_slot.push_back(f + slot);
+        X.first_graph.push_back(g0 + D.n_graphs());
+        X.first_cell.push_back(c0 + D.n_cells());
+    }
+    X.chosen.resize((size_t)X.first_graph.back());
+    X.cell_cost.resize((size_t)X.first_cell.back());
+    X.picks.resize((size_t)N_of(s));
 }
 }  // namespace
 
@@ -2553,6 +2807,86 @@ int pdmpc_sweep_run(pdmpc_sweep* s, int32_t n_steps, double* ms) {
 int pdmpc_sweep_last_timing(pdmpc_sweep* s, double* ms6) {
     if (!s || !ms6) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
     for (int i = 0; i < 6; ++i) ms6[i] = s->timing[i];
+    return PDMPC_OK;
+}
+
+int pdmpc_sweep_explore_build(pdmpc_sweep* s, int32_t n_perm) {
+    if (const int rc = explore_refusal(s, n_perm, false)) return rc;
+    return sweep_guard(s, sweep_explore_build(s, n_perm));
+}
+
+int pdmpc_sweep_explore_problem(pdmpc_sweep* s, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index,
+                                const pdmpc_polygon_set** fallback, const int32_t** member, const int32_t** instance, const int32_t** vehicle, const int32_t** level) {
+    if (!s || s->x.n_perm < 1) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_explore_problem before pdmpc_sweep_explore_build");
+    const pdmpc_sweep::Batch& X = s->x;
+    if (n_slots) *n_slots = X.first.back();
+    if (in) *in = X.in.data();
+    if (pred_offset) *pred_offset = X.pred_offset.data();
+    if (pred_index) *pred_index = X.pred_index.data();
+    if (fallback) *fallback = X.fb.data();
+    if (member) *member = X.member.data();
+    if (instance) *instance = X.instance.data();
+    if (vehicle) *vehicle = X.vehicle.data();
+    if (level) *level = X.level.data();
+    return PDMPC_OK;
+}
+
+int pdmpc_sweep_explore_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records) {
+    if (!s || !records) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
+    if (s->broken) return cfail(nullptr, PDMPC_ERR_INVALID, "an earlier step of the sweep failed: its members have advanced unevenly");
+    if (s->x.n_perm < 1) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_explore_apply before pdmpc_sweep_explore_build");
+    return sweep_guard(s, sweep_explore_apply(s, records));
+}
+
+int pdmpc_sweep_explore_step(pdmpc_sweep* s, int32_t n_perm) {
+    if (const int rc = explore_refusal(s, n_perm, true)) return rc;
+    auto t = std::chrono::steady_clock::now();
+    int rc = sweep_explore_build(s, n_perm);
+    if (rc) return sweep_guard(s, rc);
+    pdmpc_sweep::Batch& X = s->x;
+    s->timing[0] = ms_since(t);
+    const int N = X.first.back();
+    const size_t M = s->members.size();
+    // the work of the last step as the expected work of this one, as the members' own explorative steps hand it over
+    X.weights.assign((size_t)N, 1.0);
+    for (size_t m = 0; m < M; ++m) {
+        const pdmpc_controller* c = s->members[m];
+        if (c->last_pops.size() != (size_t)c->n) continue;
+        for (int q = X.first[m]; q < X.first[m + 1]; ++q) X.weights[(size_t)q] = c->last_pops[(size_t)X.vehicle[(size_t)q]] + 1.0;
+    }
+    (void)pdmpc_set_step_weights(s->h, N, X.weights.data());
+    if (s->members[0]->optimizer == PDMPC_OPTIMIZER_SAMPLED) {
+        rc = pdmpc_set_step_seeds(s->h, N, X.seeds.data());
+        if (rc) return sweep_guard(s, cfail(nullptr, rc, pdmpc_last_error()));
+    }
+    concatenate_choices(s);
+    const pdmpc_choice ch = X.all.view();
+    rc = pdmpc_plan_step_chosen(s->h, N, X.in.data(), X.pred_offset.data(), X.pred_index.data(), X.fb.data(), &ch, X.chosen.data(), X.cell_cost.data(), X.picks.data());
+    if (rc) return sweep_guard(s, cfail(nullptr, rc, pdmpc_last_error()));
+    double us[3] = {0, 0, 0};
+    if (pdmpc_last_call_timing(s->h, us) == PDMPC_OK)
+        for (int i = 0; i < 3; ++i) s->timing[1 + i] = us[i] * 1e-3;
+    t = std::chrono::steady_clock::now();
+    for (size_t m = 0; m < M; ++m) {  // every member adopts its part: as its own step that keeps the chosen plans only leaves it
+        pdmpc_controller* c = s->members[m];
+        explore_adopt(c, X.lists[m], X.chosen.data() + X.first_graph[m], X.cell_cost.data() + X.first_cell[m]);
+        c->x_out.clear();
+        c->out.assign(X.picks.begin() + s->first[m], X.picks.begin() + s->first[m + 1]);
+    }
+    s->timing[4] = ms_since(t);
+    t = std::chrono::steady_clock::now();
+    for (size_t m = 0; m < M && !rc; ++m) rc = apply_chosen(s->members[m]);
+    s->timing[5] = ms_since(t);
+    return sweep_guard(s, rc);
+}
+
+int pdmpc_sweep_explore_run(pdmpc_sweep* s, int32_t n_perm, int32_t n_steps, double* ms) {
+    for (int i = 0; i < n_steps; ++i) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const int rc = pdmpc_sweep_explore_step(s, n_perm);
+        if (rc) return rc;
+        if (ms) ms[i] = ms_since(t0);
+    }
     return PDMPC_OK;
 }
 

@@ -132,6 +132,16 @@ EXPORTS = [
     "pdmpc_debug_random_numbers",
     "pdmpc_controller_set_optimizer",
     "pdmpc_controller_seeds",
+    "pdmpc_choose_host",
+    "pdmpc_choose_resident",
+    "pdmpc_plan_step_chosen",
+    "pdmpc_choice_kernel_ms",
+    "pdmpc_controller_set_device_choice",
+    "pdmpc_sweep_explore_build",
+    "pdmpc_sweep_explore_problem",
+    "pdmpc_sweep_explore_apply",
+    "pdmpc_sweep_explore_step",
+    "pdmpc_sweep_explore_run",
     "pdmpc_last_error",
     "pdmpc_version",
 ]
@@ -405,6 +415,62 @@ def polygon_set_coupling_call(sets):
     return shaped()
 
 
+class ChoiceStruct(C.Structure):
+    """pdmpc_choice (include/pdmpc.h)."""
+
+    _fields_ = [
+        ("n_cells", C.c_int32), ("n_graphs", C.c_int32), ("n_picks", C.c_int32), ("_pad", C.c_int32),
+        ("cell_offset", abi.c_int32_p), ("cell_slot", abi.c_int32_p), ("graph_offset", abi.c_int32_p),
+        ("pick_graph", abi.c_int32_p), ("pick_offset", abi.c_int32_p), ("pick_slot", abi.c_int32_p),
+    ]
+
+
+class Choice:
+    """A choice among the plans of a batch as data (pdmpc_choice), packed for the C ABI.
+
+    cells: per cell the list of slots whose final costs are added, in this order; graphs: per graph its number of candidates (the
+    cells are the graphs' candidates one graph after the other, cells beyond the last graph belong to none) or an explicit offset
+    array; picks: per pick (graph, slots) -- a slot per candidate of the graph, or (-1, [slot])."""
+
+    def __init__(self, cells, graphs=(), picks=(), graph_offset=None):
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)  # noqa: E731
+        self.cell_offset = i32(np.concatenate([[0], np.cumsum([len(c) for c in cells])]))
+        self.cell_slot = i32([s for c in cells for s in c] + [0])
+        self.graph_offset = i32(graph_offset if graph_offset is not None else np.concatenate([[0], np.cumsum(list(graphs))]))
+        self.pick_graph = i32([g for g, _ in picks] + [0])
+        self.pick_offset = i32(np.concatenate([[0], np.cumsum([len(sl) for _, sl in picks])]))
+        self.pick_slot = i32([s for _, sl in picks for s in sl] + [0])
+        self.n_cells, self.n_graphs, self.n_picks = len(cells), len(self.graph_offset) - 1, len(picks)
+
+    def struct(self):
+        p = lambda a: a.ctypes.data_as(abi.c_int32_p)  # noqa: E731
+        return ChoiceStruct(self.n_cells, self.n_graphs, self.n_picks, 0, p(self.cell_offset), p(self.cell_slot), p(self.graph_offset), p(self.pick_graph),
+                            p(self.pick_offset), p(self.pick_slot))
+
+    def outputs(self):
+        return np.zeros(max(self.n_graphs, 1), dtype=np.int32), np.zeros(max(self.n_cells, 1)), abi.out_array(max(self.n_picks, 1))
+
+    def shaped(self, chosen, cost, picks=None):
+        out = (chosen[: self.n_graphs], cost[: self.n_cells])
+        return out if picks is None else out + (picks[: self.n_picks],)
+
+
+def choose_host_call(status, final_cost, choice):
+    """pdmpc_choose_host: the choice on the host twin (no GPU) -> (chosen per graph, rounded cost per cell)."""
+    L = load_library()
+    st = np.ascontiguousarray(status, dtype=np.int32)
+    fc = np.ascontiguousarray(final_cost, dtype=np.float64)
+    chosen, cost, _ = choice.outputs()
+    ch = choice.struct()
+    rc = L.pdmpc_choose_host(len(st), st.ctypes.data_as(abi.c_int32_p), fc.ctypes.data_as(abi.c_double_p), C.byref(ch), chosen.ctypes.data_as(abi.c_int32_p),
+                             cost.ctypes.data_as(abi.c_double_p))
+    if rc != 0:
+        err = BackendError("pdmpc_choose_host failed with status %d: %s" % (rc, (L.pdmpc_last_error() or b"").decode()))
+        err.status = rc
+        raise err
+    return choice.shaped(chosen, cost)
+
+
 def load_library(path=None):
     """dlopen the HIP backend and declare every prototype of include/pdmpc.h."""
     global _LIB
@@ -488,6 +554,12 @@ def load_library(path=None):
     L.pdmpc_fca_collisions_host.argtypes = fca_tail
     L.pdmpc_fca_kernel_ms.argtypes = [H, abi.c_double_p]
     L.pdmpc_controller_set_lanelet_bounding.argtypes = [H, C.c_int32]
+    choice_tail = [C.POINTER(ChoiceStruct), abi.c_int32_p, abi.c_double_p]
+    L.pdmpc_choose_host.argtypes = [C.c_int32, abi.c_int32_p, abi.c_double_p] + choice_tail
+    L.pdmpc_choose_resident.argtypes = [H, C.c_int32] + choice_tail + [C.POINTER(abi.VehicleOut)]
+    L.pdmpc_plan_step_chosen.argtypes = [H, C.c_int32, C.POINTER(abi.VehicleIn), abi.c_int32_p, abi.c_int32_p, C.POINTER(abi.PolygonSet)] + choice_tail + [
+        C.POINTER(abi.VehicleOut)]
+    L.pdmpc_choice_kernel_ms.argtypes = [H, abi.c_double_p]
     L.pdmpc_last_error.restype = C.c_char_p
     L.pdmpc_version.restype = C.c_char_p
     for name in EXPORTS:
@@ -856,6 +928,38 @@ class Handle:
         )
         del keep
         return self._checked(out[:n])
+
+    def _choice_call(self, what, call, choice):
+        chosen, cost, picks = choice.outputs()
+        ch = choice.struct()
+        rc = call(C.byref(ch), chosen.ctypes.data_as(abi.c_int32_p), cost.ctypes.data_as(abi.c_double_p), abi.out_ptr(picks))
+        if rc != 0:
+            err = BackendError("%s failed with status %d: %s" % (what, rc, (self.L.pdmpc_last_error() or b"").decode()))
+            err.status = rc
+            raise err
+        return choice.shaped(chosen, cost, picks)
+
+    def choose_resident(self, n, choice):
+        """pdmpc_choose_resident: the choice on the device on the n records resident in the current bank -> (chosen, cell costs, picked records)."""
+        return self._choice_call("pdmpc_choose_resident", lambda *tail: self.L.pdmpc_choose_resident(self.h, n, *tail), choice)
+
+    def plan_step_chosen(self, iters, predecessors, fallback_shapes, choice, weights=None):
+        """pdmpc_plan_step_chosen: pack, ONE launch of the searches, the choice on the device, one read-back -> (chosen, cell costs, picked records)."""
+        n = len(iters)
+        arr, off, idx, fb, keep = self._step_args(iters, predecessors, fallback_shapes)
+        if weights is not None:
+            self.set_step_weights(weights)
+        out = self._choice_call(
+            "pdmpc_plan_step_chosen",
+            lambda *tail: self.L.pdmpc_plan_step_chosen(self.h, n, arr, off.ctypes.data_as(abi.c_int32_p), idx.ctypes.data_as(abi.c_int32_p), fb, *tail), choice)
+        del keep
+        return out
+
+    def choice_kernel_ms(self):
+        """Kernel milliseconds (HIP events) of the two launches of the last choice on the device."""
+        ms = C.c_double()
+        _check(self.L, self.L.pdmpc_choice_kernel_ms(self.h, C.byref(ms)), "pdmpc_choice_kernel_ms")
+        return ms.value
 
     def step_args(self, iters, predecessors, fallback_shapes=None):
         """The marshalled arguments of pdmpc_plan_step / pdmpc_plan_step_literal, reusable across calls (bench.py times the calls,

@@ -87,8 +87,16 @@ def _declare(L):
     L.pdmpc_sweep_step.argtypes = [H]
     L.pdmpc_sweep_run.argtypes = [H, C.c_int32, abi.c_double_p]
     L.pdmpc_sweep_last_timing.argtypes = [H, C.c_void_p]
+    L.pdmpc_sweep_explore_build.argtypes = [H, C.c_int32]
+    L.pdmpc_sweep_explore_problem.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.POINTER(abi.VehicleIn)), C.POINTER(abi.c_int32_p), C.POINTER(abi.c_int32_p),
+                                              C.POINTER(C.POINTER(abi.PolygonSet))] + [C.POINTER(abi.c_int32_p)] * 4
+    L.pdmpc_sweep_explore_apply.argtypes = [H, C.POINTER(abi.VehicleOut)]
+    L.pdmpc_sweep_explore_step.argtypes = [H, C.c_int32]
+    L.pdmpc_sweep_explore_run.argtypes = [H, C.c_int32, C.c_int32, abi.c_double_p]
+    L.pdmpc_controller_set_device_choice.argtypes = [H, C.c_int32]
     for name in ("pdmpc_sweep_create", "pdmpc_sweep_destroy", "pdmpc_sweep_build", "pdmpc_sweep_problem", "pdmpc_sweep_apply", "pdmpc_sweep_step", "pdmpc_sweep_run",
-                 "pdmpc_sweep_last_timing"):
+                 "pdmpc_sweep_last_timing", "pdmpc_sweep_explore_build", "pdmpc_sweep_explore_problem", "pdmpc_sweep_explore_apply", "pdmpc_sweep_explore_step",
+                 "pdmpc_sweep_explore_run", "pdmpc_controller_set_device_choice"):
         getattr(L, name).restype = C.c_int
     L._controller_declared = True
     return L
@@ -316,6 +324,7 @@ class NativeController:
     def explore_step(self, n_perm):
         """One explorative time step natively (batch, ONE launch, choice, apply) -> (records of the batch, chosen instance per vehicle)."""
         self._check(self.L.pdmpc_controller_explore_step(self.c, n_perm), "pdmpc_controller_explore_step")
+        self.n_perm = n_perm
         chosen = np.zeros(self.n, dtype=np.int32)
         p = C.POINTER(abi.VehicleOut)()
         self._check(self.L.pdmpc_controller_explore_result(self.c, chosen.ctypes.data_as(abi.c_int32_p), None, None, C.byref(p)), "pdmpc_controller_explore_result")
@@ -326,7 +335,28 @@ class NativeController:
         self.L.pdmpc_controller_explore_follow_own.argtypes = [C.c_void_p, C.c_int32]
         self._check(self.L.pdmpc_controller_explore_follow_own(self.c, 1 if on else 0), "pdmpc_controller_explore_follow_own")
 
+    def set_device_choice(self, on=True):
+        """explore_run / optimal_run choose and gather the chosen plans on the device, ONE call per step (pdmpc_controller_set_device_choice)."""
+        self._check(self.L.pdmpc_controller_set_device_choice(self.c, 1 if on else 0), "pdmpc_controller_set_device_choice")
+
+    def explore_result(self):
+        """The last explorative choice, also of a sweep's member -> (instance chosen per vehicle, cost table n_perm x n_graphs)."""
+        chosen = np.zeros(self.n, dtype=np.int32)
+        g = C.c_int32()
+        cost = abi.c_double_p()
+        self._check(self.L.pdmpc_controller_explore_result(self.c, chosen.ctypes.data_as(abi.c_int32_p), C.byref(g), C.byref(cost), None), "pdmpc_controller_explore_result")
+        return chosen, np.array([cost[q] for q in range(self.n_perm * g.value)]).reshape(self.n_perm, g.value)
+
+    def optimal_result(self):
+        """The last optimal-priority choice -> (instance chosen per vehicle, cost table n x K)."""
+        chosen = np.zeros(self.n, dtype=np.int32)
+        k = C.c_int32()
+        cost = abi.c_double_p()
+        self._check(self.L.pdmpc_controller_optimal_result(self.c, chosen.ctypes.data_as(abi.c_int32_p), C.byref(k), C.byref(cost), None), "pdmpc_controller_optimal_result")
+        return chosen, np.array([cost[q] for q in range(self.n * k.value)]).reshape(self.n, k.value)
+
     def explore_run(self, n_perm, n_steps):
+        self.n_perm = n_perm
         ms = np.zeros(max(n_steps, 1))
         self._check(self.L.pdmpc_controller_explore_run(self.c, n_perm, n_steps, ms.ctypes.data_as(abi.c_double_p)), "pdmpc_controller_explore_run")
         return ms[:n_steps]
@@ -443,6 +473,49 @@ class NativeSweep:
         """n_steps lock-steps in one native call -> wall-clock milliseconds of every lock-step."""
         ms = np.zeros(max(n_steps, 1))
         self._check(self.L.pdmpc_sweep_run(self.s, n_steps, ms.ctypes.data_as(abi.c_double_p)), "pdmpc_sweep_run")
+        return ms[:n_steps]
+
+    # ---- the explorative step of a sweep (DESIGN.md §3.21)
+    def explore_build(self, n_perm):
+        self._check(self.L.pdmpc_sweep_explore_build(self.s, n_perm), "pdmpc_sweep_explore_build")
+        self._n_perm(n_perm)
+
+    def _n_perm(self, n_perm):
+        for m in self.members:
+            m.n_perm = n_perm
+
+    def explore_problem(self):
+        """The concatenated batch of the last explore_build, decoded as NativeController.explore_problem decodes a member's, plus the
+        member per slot."""
+        n = C.c_int32()
+        vin = C.POINTER(abi.VehicleIn)()
+        po, pi, mem, inst, veh, lvl = (abi.c_int32_p() for _ in range(6))
+        fb = C.POINTER(abi.PolygonSet)()
+        self._check(self.L.pdmpc_sweep_explore_problem(self.s, C.byref(n), C.byref(vin), C.byref(po), C.byref(pi), C.byref(fb), C.byref(mem), C.byref(inst), C.byref(veh),
+                                                       C.byref(lvl)), "pdmpc_sweep_explore_problem")
+        iters, preds, fallback = self.members[0]._decode(n.value, vin, po, pi, fb)
+        col = lambda a: [int(a[q]) for q in range(n.value)]  # noqa: E731
+        return {"iters": iters, "preds": preds, "fallback": fallback, "member": col(mem), "instance": col(inst), "vehicle": col(veh), "levels": col(lvl)}
+
+    def explore_apply(self, records):
+        """The records of every slot of the concatenated batch: the choice per member on the host, every member's apply."""
+        recs = np.ascontiguousarray(records)
+        want = sum(m.n * m.n_perm for m in self.members)
+        if recs.shape[0] != want:
+            raise ValueError("the explorative batch of this sweep has %d slots, not %d" % (want, recs.shape[0]))
+        self._check(self.L.pdmpc_sweep_explore_apply(self.s, abi.out_ptr(recs)), "pdmpc_sweep_explore_apply")
+
+    def explore_step(self, n_perm):
+        """One explorative lock-step natively -> every member's kept (chosen) records in its own slot order."""
+        self._check(self.L.pdmpc_sweep_explore_step(self.s, n_perm), "pdmpc_sweep_explore_step")
+        self._n_perm(n_perm)
+        return [m.records() for m in self.members]
+
+    def explore_run(self, n_perm, n_steps):
+        """n_steps explorative lock-steps in one native call -> wall-clock milliseconds of every lock-step."""
+        ms = np.zeros(max(n_steps, 1))
+        self._check(self.L.pdmpc_sweep_explore_run(self.s, n_perm, n_steps, ms.ctypes.data_as(abi.c_double_p)), "pdmpc_sweep_explore_run")
+        self._n_perm(n_perm)
         return ms[:n_steps]
 
     def last_timing(self):
