@@ -319,9 +319,10 @@ def fca_pairs(adjacency):
     return np.ascontiguousarray(np.stack([a, b], axis=1), dtype=np.int32).reshape(-1, 2)
 
 
-def fca_pack(reference_points, pairs, length, width, offset, obstacles=(), dynamic_obstacle_area=()):
+def fca_pack(reference_points, pairs, length, width, offset, obstacles=(), dynamic_obstacle_area=(), headings=None):
     """The arguments of pdmpc_fca_collisions(_host) after the handle -> (args, (collisions, priorities) output arrays, keep-alive).
-    The headings are prioritizer.calculate_yaw's and their cos / sin the host's libm, as prioritizer.fca_priorities builds them."""
+    The headings are prioritizer.calculate_yaw's and their cos / sin the host's libm, as prioritizer.fca_priorities builds them;
+    `headings` = (cos, sin), two (n, Hp) arrays, is passed to the C ABI as it is instead (an exact quarter turn has no yaw angle)."""
     from .prioritizer import calculate_yaw
 
     ref = [np.asarray(r, dtype=np.float64).reshape(-1, 2) for r in reference_points]
@@ -331,9 +332,16 @@ def fca_pack(reference_points, pairs, length, width, offset, obstacles=(), dynam
         raise ValueError("every vehicle needs Hp reference points")
     x = np.ascontiguousarray(np.concatenate([r[:, 0] for r in ref]) if n else np.zeros(1), dtype=np.float64)
     y = np.ascontiguousarray(np.concatenate([r[:, 1] for r in ref]) if n else np.zeros(1), dtype=np.float64)
-    yaw = [a for r in ref for a in (calculate_yaw(r) if Hp >= 2 else np.zeros(Hp))]
-    c = np.array([math.cos(float(a)) for a in yaw] or [0.0], dtype=np.float64)
-    s = np.array([math.sin(float(a)) for a in yaw] or [0.0], dtype=np.float64)
+    if headings is None:
+        yaw = [a for r in ref for a in (calculate_yaw(r) if Hp >= 2 else np.zeros(Hp))]
+        c = np.array([math.cos(float(a)) for a in yaw] or [0.0], dtype=np.float64)
+        s = np.array([math.sin(float(a)) for a in yaw] or [0.0], dtype=np.float64)
+    else:
+        c, s = (np.ascontiguousarray(np.asarray(h, dtype=np.float64).reshape(-1)) for h in headings)
+        if c.size != n * Hp or s.size != n * Hp:
+            raise ValueError("headings: a cosine and a sine per vehicle and step")
+        if not n * Hp:
+            c, s = np.zeros(1), np.zeros(1)
     pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
     keep = abi._Keep()
     keep.refs += [x, y, c, s, pr]
@@ -348,13 +356,13 @@ def fca_pack(reference_points, pairs, length, width, offset, obstacles=(), dynam
     return args, (coll[:n], prio[:n]), keep
 
 
-def fca_collisions_host(reference_points, pairs, length, width, offset, obstacles=(), dynamic_obstacle_area=(), handle=None):
+def fca_collisions_host(reference_points, pairs, length, width, offset, obstacles=(), dynamic_obstacle_area=(), handle=None, headings=None):
     """FcaPrioritizer natively (pdmpc_fca_collisions_host; on `handle`'s device, pdmpc_fca_collisions, if one is given).
     reference_points: per vehicle an (Hp, 2) array; pairs: (P, 2) coupled pairs a < b, ascending (fca_pairs); obstacles: (2, V) arrays;
     dynamic_obstacle_area: rows of Hp (2, V) arrays.  -> (collisions (n,) int32, priorities (n,) int32: the 1-based index vector of the
-    stable descending sort, as the reference passes it on)."""
+    stable descending sort, as the reference passes it on).  headings: (cos, sin) per vehicle and step in place of calculate_yaw's."""
     L = load_library()
-    args, out, keep = fca_pack(reference_points, pairs, length, width, offset, obstacles, dynamic_obstacle_area)
+    args, out, keep = fca_pack(reference_points, pairs, length, width, offset, obstacles, dynamic_obstacle_area, headings)
     if handle is not None:
         _check(L, L.pdmpc_fca_collisions(handle.h, *args), "pdmpc_fca_collisions")
     else:
@@ -856,9 +864,9 @@ class Handle:
         _check(self.L, self.L.pdmpc_bounded_reachable_kernel_ms(self.h, ms.ctypes.data_as(abi.c_double_p)), "pdmpc_bounded_reachable_kernel_ms")
         return float(ms[0]), float(ms[1])
 
-    def fca_collisions(self, reference_points, pairs, length, width, offset, obstacles=(), dynamic_obstacle_area=()):
+    def fca_collisions(self, reference_points, pairs, length, width, offset, obstacles=(), dynamic_obstacle_area=(), headings=None):
         """FcaPrioritizer on this handle's device (pdmpc_fca_collisions) -> (collisions, priorities); see fca_collisions_host."""
-        return fca_collisions_host(reference_points, pairs, length, width, offset, obstacles, dynamic_obstacle_area, handle=self)
+        return fca_collisions_host(reference_points, pairs, length, width, offset, obstacles, dynamic_obstacle_area, handle=self, headings=headings)
 
     def fca_kernel_ms(self):
         """kernel time (ms) of the last fca_collisions"""

@@ -125,21 +125,25 @@ def calculate_yaw(path):
     return yaw
 
 
-def fca_priorities(adjacency, reference_points, length, width, offset, obstacles=(), dynamic_obstacle_area=()):
+def fca_priorities(adjacency, reference_points, length, width, offset, obstacles=(), dynamic_obstacle_area=(), headings=None):
     """FcaPrioritizer.m:13-92 (future collision assessment): count, per vehicle, the steps at which its footprint on the
     reference trajectory overlaps an obstacle or the footprint of a coupled vehicle; more collisions = earlier.
     reference_points: per vehicle an (Hp, 2) array.  Returns the reference's `current_priorities` vector — the
-    *positions* of the descending sort, which the reference feeds to directed_coupling_from_priorities as they are."""
+    *positions* of the descending sort, which the reference feeds to directed_coupling_from_priorities as they are.
+    headings = (cos, sin), two (n, Hp) arrays, replaces calculate_yaw and libm (backend.fca_pack takes the same)."""
     A = np.asarray(adjacency) != 0
     n = A.shape[0]
     Hp = len(reference_points[0])
     collisions = np.zeros(n)
     xl = np.array([-1, -1, 1, 1]) * (length / 2 + offset)
     yl = np.array([-1, 1, 1, -1]) * (width / 2 + offset)
-    yaws = [calculate_yaw(reference_points[v]) for v in range(n)]
+    yaws = [calculate_yaw(reference_points[v]) for v in range(n)] if headings is None else None
 
     def footprint(v, s):
-        c, si = math.cos(float(yaws[v][s])), math.sin(float(yaws[v][s]))  # the host's libm, as the native twins take them
+        if headings is None:
+            c, si = math.cos(float(yaws[v][s])), math.sin(float(yaws[v][s]))  # the host's libm, as the native twins take them
+        else:
+            c, si = float(headings[0][v][s]), float(headings[1][v][s])
         x0, y0 = reference_points[v][s]
         return np.stack([c * xl - si * yl + x0, si * xl + c * yl + y0])
 
