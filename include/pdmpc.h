@@ -513,8 +513,28 @@ int pdmpc_fca_collisions(pdmpc_handle* handle, int32_t n, int32_t Hp, const doub
 int pdmpc_fca_collisions_host(int32_t n, int32_t Hp, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw, int32_t n_pairs,
                               const int32_t* pairs, const pdmpc_polygon_set* obstacles, const pdmpc_polygon_set* dynamic_rows, double length, double width,
                               double offset, int32_t* collisions, int32_t* priorities);
-/* kernel time (HIP events, ms) of the last pdmpc_fca_collisions */
+/* kernel time (HIP events, ms) of the last pdmpc_fca_collisions or pdmpc_fca_collisions_grouped */
 int pdmpc_fca_kernel_ms(pdmpc_handle* handle, double* ms);
+/* The assessment for several independent sets of vehicles at once: n_groups consecutive groups, each with its own
+ * coupled pairs (numbered inside the group), static obstacles, dynamic rows and vehicle sizes.  x, y, cos_yaw, sin_yaw hold the
+ * N * Hp reference points of the N = sum n_g vehicles group after group; collisions and priorities (N each) stand group after group
+ * too, priorities being every group's own 1-based index vector.  Group g's slices hold exactly what pdmpc_fca_collisions returns for
+ * group g alone: nothing is counted across groups, and the last vehicle of every group skips its group's obstacles.  Groups with
+ * n = 0 are legal and write nothing; so is n_groups = 0.  A call is one staging copy, the two kernel launches, one copy back and one
+ * synchronisation whatever n_groups is; the host twin loops over pdmpc_fca_collisions_host.
+ * PDMPC_ERR_INVALID for n_groups < 0, Hp < 2, a null array with N > 0 or a group that pdmpc_fca_collisions would refuse (the message
+ * names the group); PDMPC_ERR_CAPACITY for N > config.max_vehicles. */
+typedef struct pdmpc_fca_group {
+    int32_t n, n_pairs;
+    const int32_t* pairs;                  /* group-local, 0 <= a < b < n, ascending, no repeats */
+    const pdmpc_polygon_set* obstacles;    /* or NULL */
+    const pdmpc_polygon_set* dynamic_rows; /* or NULL; n_polygons a multiple of Hp */
+    double length, width, offset;
+} pdmpc_fca_group;
+int pdmpc_fca_collisions_grouped(pdmpc_handle* handle, int32_t n_groups, const pdmpc_fca_group* groups, int32_t Hp, const double* x, const double* y,
+                                 const double* cos_yaw, const double* sin_yaw, int32_t* collisions, int32_t* priorities);
+int pdmpc_fca_collisions_grouped_host(int32_t n_groups, const pdmpc_fca_group* groups, int32_t Hp, const double* x, const double* y, const double* cos_yaw,
+                                      const double* sin_yaw, int32_t* collisions, int32_t* priorities);
 
 /* ---- the caller's side of the boundary, natively (csrc/step_controller.cpp) ----
  * One MPC time step of the prioritized sequential controller around pdmpc_plan_step, without any interpreter in the loop:
@@ -658,6 +678,10 @@ int pdmpc_controller_set_optimizer(pdmpc_controller* c, int32_t which); /* PDMPC
 /* the sampled optimizer's seed per slot of the last built step or batch (pdmpc_controller_build_step / _explore_build / _optimal_build),
  * whichever optimizer is selected: *n slots, *seeds valid until the next build */
 int pdmpc_controller_seeds(pdmpc_controller* c, int32_t* n, const uint32_t** seeds);
+/* The priorities of the last built step with constant, random or FCA priorities (1-based, what directed_coupling_from_priorities
+ * received) and, after an FCA step, the collision counts behind them: pointers into the controller, valid until its next step; a
+ * length of 0 where the strategy has none. */
+int pdmpc_controller_priorities(pdmpc_controller* c, int32_t* n_priorities, const int32_t** priorities, int32_t* n_collisions, const int32_t** collisions);
 /* on != 0: pdmpc_controller_explore_run and pdmpc_controller_optimal_run (the steps that keep the chosen plans only) make ONE
  * pdmpc_plan_step_chosen call per step -- the choice among the prioritizations and the gather of the chosen records run on the device
  * directly behind the search, one read-back -- instead of pdmpc_plan_step_lean, the choice on the host and pdmpc_fetch_records_at.  The
@@ -668,7 +692,8 @@ int pdmpc_controller_set_device_choice(pdmpc_controller* c, int32_t on);
 /* ---- several closed loops in lock-step (csrc/step_controller.cpp) ----
  * A sweep borrows n_members controllers that were created on the same handle (or all without one) and steps them together: every
  * member's build_step, with the device's step preparation grouped over the members (pdmpc_bound_reachable_sets on the concatenated
- * vehicles, pdmpc_*_coupling_grouped: a pair of two members is never looked at), ONE pdmpc_plan_step for the concatenated problem,
+ * vehicles, pdmpc_*_coupling_grouped: a pair of two members is never looked at; pdmpc_fca_collisions_grouped for the members with FCA
+ * priorities, each with its own pairs, obstacles and sizes), ONE pdmpc_plan_step for the concatenated problem,
  * every member's apply.  After a sweep step each member is byte for byte where its own pdmpc_controller_step would have left it
  * (state, records in its own slot order, problem, seeds, time step, expected work, fallback bookkeeping): a member can be taken out of
  * a sweep and stepped alone afterwards.  The plain prioritized step and the explorative step (below) are part of a sweep, with the
@@ -692,6 +717,11 @@ int pdmpc_sweep_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records);
 int pdmpc_sweep_step(pdmpc_sweep* s);
 int pdmpc_sweep_run(pdmpc_sweep* s, int32_t n_steps, double* ms);
 int pdmpc_sweep_last_timing(pdmpc_sweep* s, double* ms6);
+/* The step-preparation calls the last build of the sweep made, whatever the number of members: calls4[0] lanelet bounding, [1] the
+ * coupler on the bounded sets, [2] the coupler on the plain hulls, [3] future collision assessment -- device calls, or calls of the
+ * host twins for a sweep without a handle (where lanelet bounding is one call per member and the hull coupler one per table of local
+ * hulls).  A bounding call that is repeated with more room counts once. */
+int pdmpc_sweep_last_prep_calls(pdmpc_sweep* s, int32_t* calls4);
 /* The explorative step of a sweep: every member's explorative batch of n_perm prioritizations (seed = its time step),
  * the step preparation grouped as for pdmpc_sweep_build, the members' flattened batches one after the other (predecessor slots shifted by
  * the member's first slot), ONE pdmpc_plan_step_chosen with the members' choice descriptions concatenated -- one launch of the searches,

@@ -1,9 +1,10 @@
 // fca.cpp — the host twin of the future collision assessment (FcaPrioritizer.m:11-92) and the parts it shares with
-// the device entry point (api.cpp: pdmpc_fca_collisions): the argument checks and the stable descending sort of the counts.  Host code
-// only; the C++ twin of pdmpc.prioritizer.fca_priorities.  The footprints and the separating-axis test are include/pdmpc_geometry.h,
+// the device entry points (step_prep.cpp: pdmpc_fca_collisions, pdmpc_fca_collisions_grouped): the argument checks and the stable
+// descending sort of the counts; the grouped host twin loops over the ungrouped one.  Host code only; the C++ twin of pdmpc.prioritizer.fca_priorities.  The footprints and the separating-axis test are include/pdmpc_geometry.h,
 // which the kernel (fca_kernel.hip) compiles too, so the twin and the kernel decide every test with the same bits.
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
 #include <vector>
 
 #include "../../include/pdmpc.h"
@@ -83,6 +84,58 @@ int pdmpc_fca_collisions_host(int32_t n, int32_t Hp, const double* x, const doub
         }
     }
     pdmpc_fca_sort_index(n, collisions, priorities);
+    return PDMPC_OK;
+}
+
+int pdmpc_fca_check_groups(int32_t n_groups, const pdmpc_fca_group* groups, int32_t Hp, const double* x, const double* y, const double* cos_yaw,
+                           const double* sin_yaw, const int32_t* collisions, const int32_t* priorities, int32_t* n_total, char* why, int32_t why_size) {
+    auto refuse = [&](int rc, int g, const char* what) {
+        if (g < 0)
+            snprintf(why, (size_t)why_size, "%s", what);
+        else
+            snprintf(why, (size_t)why_size, "group %d: %s", g, what);
+        return rc;
+    };
+    *n_total = 0;
+    if (n_groups < 0 || (n_groups > 0 && !groups)) return refuse(PDMPC_ERR_INVALID, -1, "bad groups");
+    if (Hp < 2) return refuse(PDMPC_ERR_INVALID, -1, "Hp must be at least 2 (calculate_yaw needs two reference points)");
+    int64_t N = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        if (groups[g].n < 0) return refuse(PDMPC_ERR_INVALID, g, "n must not be negative");
+        N += groups[g].n;
+    }
+    if (N * Hp > INT32_MAX) return refuse(PDMPC_ERR_CAPACITY, -1, "more than 2^31 reference points");
+    *n_total = (int32_t)N;
+    if (N > 0 && (!x || !y || !cos_yaw || !sin_yaw || !collisions || !priorities)) return refuse(PDMPC_ERR_INVALID, -1, "null argument");
+    size_t v0 = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const pdmpc_fca_group& G = groups[g];
+        if (G.n == 0) continue;  // (legal: nothing to assess, nothing written)
+        const size_t i0 = v0 * Hp;
+        const char* w = nullptr;
+        if (const int rc = pdmpc_fca_check_args(G.n, Hp, x + i0, y + i0, cos_yaw + i0, sin_yaw + i0, G.n_pairs, G.pairs, G.obstacles, G.dynamic_rows, collisions + v0,
+                                                priorities + v0, &w))
+            return refuse(rc, g, w);
+        v0 += (size_t)G.n;
+    }
+    return PDMPC_OK;
+}
+
+int pdmpc_fca_collisions_grouped_host(int32_t n_groups, const pdmpc_fca_group* groups, int32_t Hp, const double* x, const double* y, const double* cos_yaw,
+                                      const double* sin_yaw, int32_t* collisions, int32_t* priorities) {
+    char why[160];
+    int32_t N = 0;
+    if (const int rc = pdmpc_fca_check_groups(n_groups, groups, Hp, x, y, cos_yaw, sin_yaw, collisions, priorities, &N, why, (int32_t)sizeof why)) return rc;
+    size_t v0 = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const pdmpc_fca_group& G = groups[g];
+        if (G.n == 0) continue;
+        const size_t i0 = v0 * Hp;
+        if (const int rc = pdmpc_fca_collisions_host(G.n, Hp, x + i0, y + i0, cos_yaw + i0, sin_yaw + i0, G.n_pairs, G.pairs, G.obstacles, G.dynamic_rows, G.length,
+                                                     G.width, G.offset, collisions + v0, priorities + v0))
+            return rc;
+        v0 += (size_t)G.n;
+    }
     return PDMPC_OK;
 }
 

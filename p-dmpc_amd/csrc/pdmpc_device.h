@@ -370,6 +370,28 @@ struct FcaArgs {
     int32_t* counts;            // [n]
 };
 
+// The grouped form (pdmpc_fca_collisions_grouped): the n vehicles of `a` are n_groups consecutive groups, each with its
+// own sizes, static obstacles and dynamic rows.  a.pairs are rebased to the concatenated vehicles; a.static_off / a.dyn_off and the
+// vertices behind them hold the groups' polygons one group after the other; a.n_static_items / a.n_items are the sums over the groups
+// (a.n_static, a.n_rows, a.length, a.width, a.offset are not read).  Per group, staged by the host:
+struct FcaGroup {
+    int32_t first;                        // its first vehicle
+    int32_t n_static, n_rows;             // S_g static polygons, R_g rows of Hp polygons
+    int32_t static_polygon, dyn_polygon;  // its first polygon in a.static_off / a.dyn_off
+    double length, width, offset;
+};
+struct FcaGroups {
+    int32_t n_groups;
+    const FcaGroup* group;         // [n_groups]
+    const int32_t* vehicle_group;  // [n] every vehicle's group
+    const int64_t* static_first;   // [n_groups + 1] prefix sums of (n_g - 1) Hp S_g: where group g's static items start in the static range
+    const int64_t* dyn_first;      // [n_groups + 1] ... of (n_g - 1) Hp R_g, in the dynamic range (groups of no vehicle count 0 items)
+};
+struct FcaGroupedArgs {
+    FcaArgs a;
+    FcaGroups g;
+};
+
 // The choice among the plans of a batch (choice_kernel.hip; pdmpc_choice in include/pdmpc.h) on the result records
 // where the search left them.  The lists are the caller's with the slots mapped to record slots and checked on the host (api.cpp:
 // stage_choice); cells of no graph are the cells in front of first_graph_cell and from end_graph_cell on.
@@ -400,12 +422,17 @@ extern "C" {
 int pdmpc_launch_choice(const ChoiceArgs* args, void* stream);
 // fca_kernel.hip: the footprint pass (which also clears the counts) and the item pass on the handle's stream
 int pdmpc_launch_fca(const FcaArgs* args, void* stream);
+int pdmpc_launch_fca_grouped(const FcaGroupedArgs* args, void* stream);
 // fca.cpp: the argument checks pdmpc_fca_collisions and its host twin share (PDMPC_OK, or an error code with *why set), and the
 // stable descending sort of the counts (priorities = 1-based index vector)
 int pdmpc_fca_check_args(int32_t n, int32_t Hp, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw, int32_t n_pairs,
                          const int32_t* pairs, const pdmpc_polygon_set* obstacles, const pdmpc_polygon_set* dynamic_rows, const int32_t* collisions,
                          const int32_t* priorities, const char** why);
 void pdmpc_fca_sort_index(int32_t n, const int32_t* collisions, int32_t* priorities);
+// ... and of the grouped calls: n_groups, Hp, the arrays and every group with vehicles (pdmpc_fca_check_args on its slices); *n_total =
+// the vehicles of all groups, `why` (why_size bytes) names the group that was refused
+int pdmpc_fca_check_groups(int32_t n_groups, const pdmpc_fca_group* groups, int32_t Hp, const double* x, const double* y, const double* cos_yaw,
+                           const double* sin_yaw, const int32_t* collisions, const int32_t* priorities, int32_t* n_total, char* why, int32_t why_size);
 // reachable_kernel.hip: the two passes of the reachable-set coupler on the handle's stream
 int pdmpc_launch_reachable_coupling(const ReachArgs* args, void* stream);
 int pdmpc_launch_reachable_coupling_grouped(const ReachArgs* args, void* stream);

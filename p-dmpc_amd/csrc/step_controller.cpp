@@ -898,6 +898,16 @@ int pdmpc_controller_set_optimizer(pdmpc_controller* c, int32_t which) {
     return PDMPC_OK;
 }
 
+int pdmpc_controller_priorities(pdmpc_controller* c, int32_t* n_priorities, const int32_t** priorities, int32_t* n_collisions, const int32_t** collisions) {
+    if (!c || !n_priorities || !priorities || !n_collisions || !collisions) return cfail(c, PDMPC_ERR_INVALID, "null argument");
+    const bool has = c->cfg.priority_strategy != PDMPC_PRIORITY_COLORING, fca = c->cfg.priority_strategy == PDMPC_PRIORITY_FCA;
+    *n_priorities = has ? (int32_t)c->prio.size() : 0;
+    *priorities = c->prio.data();
+    *n_collisions = fca ? (int32_t)c->fca_count.size() : 0;
+    *collisions = c->fca_count.data();
+    return PDMPC_OK;
+}
+
 int pdmpc_controller_seeds(pdmpc_controller* c, int32_t* n, const uint32_t** seeds) {
     if (!c || !n || !seeds) return cfail(c, PDMPC_ERR_INVALID, "null argument");
     *n = (int32_t)c->seeds.size();
@@ -1022,7 +1032,9 @@ int couple_reachable_sets(pdmpc_controller* c) {
 }
 
 // FcaPrioritizer.m:11-92 on the step's reference points and the scenario's obstacles
-int fca_priorities(pdmpc_controller* c) {
+// ... its two host halves, which the sweep runs per member around one device call for all FCA members: the reference points, their
+// headings and the coupled pairs in c->fca_*, and the counts and priorities taken over
+int fca_inputs(pdmpc_controller* c) {
     const int n = c->n, Hp = c->Hp;
     if (Hp < 2) return cfail(c, PDMPC_ERR_INVALID, "FCA priorities need Hp >= 2 (calculate_yaw needs two reference points)");
     c->fca_x.resize((size_t)n * Hp);
@@ -1049,6 +1061,14 @@ int fca_priorities(pdmpc_controller* c) {
             c->fca_pairs.push_back(a + 1 + q);
         });
     c->fca_count.resize(n);
+    return PDMPC_OK;
+}
+void adopt_fca(pdmpc_controller* c, const int32_t* collisions, const int32_t* priorities) {
+    std::copy(collisions, collisions + c->n, c->fca_count.begin());
+    std::copy(priorities, priorities + c->n, c->prio.begin());
+}
+int fca_priorities(pdmpc_controller* c) {
+    if (const int rc = fca_inputs(c)) return rc;
     return fca_collisions(c, (int32_t)(c->fca_pairs.size() / 2), view_polygons(c->fca_obst_off, c->fca_obst_x, c->fca_obst_y));
 }
 
@@ -1184,7 +1204,8 @@ int couple(pdmpc_controller* c, int bounded_S, bool reachable_given = false) {
 }
 
 // priorities -> c->directed
-int direct_by_priorities(pdmpc_controller* c) {
+// (fca_given: the sweep's grouped call has assessed the member already -- its counts and priorities, c->fca_* filled by fca_inputs)
+int direct_by_priorities(pdmpc_controller* c, const int32_t* fca_given_collisions = nullptr, const int32_t* fca_given_priorities = nullptr) {
     const int n = c->n;
     if (c->cfg.priority_strategy == PDMPC_PRIORITY_COLORING) {
         coloring_directed(c->adjacency, n, c->directed);
@@ -1196,6 +1217,8 @@ int direct_by_priorities(pdmpc_controller* c) {
     for (int v = 0; v < n; ++v) c->prio[v] = v + 1;
     if (c->cfg.priority_strategy == PDMPC_PRIORITY_RANDOM) {
         random_priorities(c->k, n, c->prio);
+    } else if (c->cfg.priority_strategy == PDMPC_PRIORITY_FCA && fca_given_priorities) {
+        adopt_fca(c, fca_given_collisions, fca_given_priorities);
     } else if (c->cfg.priority_strategy == PDMPC_PRIORITY_FCA) {
         const int rc = fca_priorities(c);
         if (rc) return rc;
@@ -1246,8 +1269,8 @@ int begin_step(pdmpc_controller* c, StepPrep& P) {
     return PDMPC_OK;
 }
 // ... and everything after it
-int finish_step(pdmpc_controller* c) {
-    int rc = direct_by_priorities(c);
+int finish_step(pdmpc_controller* c, const int32_t* fca_given_collisions = nullptr, const int32_t* fca_given_priorities = nullptr) {
+    int rc = direct_by_priorities(c, fca_given_collisions, fca_given_priorities);
     if (!rc) rc = assemble_step(c);
     if (rc) return rc;
     set_seeds(c, c->order);
@@ -2294,6 +2317,7 @@ struct pdmpc_sweep {
     bool broken = false;         // a step failed half way: the members have advanced unevenly
     bool built = false;
     double timing[6] = {0, 0, 0, 0, 0, 0};
+    int32_t prep_calls[4] = {0, 0, 0, 0};  // of the last build: lanelet bounding, bounded coupling, hull coupling, collision assessment
     std::vector<StepPrep> prep;
     // the concatenated problem
     std::vector<pdmpc_vehicle_in> in;
@@ -2326,6 +2350,13 @@ struct pdmpc_sweep {
         std::vector<double> lan_x, lan_y, set_x, set_y;
         std::vector<uint8_t> adjacency;      // the blocks
     } call;
+    // the grouped collision assessment: the FCA members' reference points, member after member, and what it returns
+    struct Fca {
+        std::vector<pdmpc_fca_group> groups;
+        std::vector<pdmpc_polygon_set> obstacles;  // [groups.size()] views of the members' scenario obstacles
+        std::vector<double> x, y, cos_yaw, sin_yaw;
+        std::vector<int32_t> collisions, priorities;
+    } fca;
 };
 
 namespace {
@@ -2396,6 +2427,7 @@ int sweep_bound_on_device(pdmpc_sweep* s, const std::vector<int>& who, bool all_
         return pdmpc_bound_reachable_sets(s->h, n, C.x.data(), C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(), C.trim.data(), &lan, all_steps, (int32_t)C.set_x.size(),
                                           C.set_off.data(), C.set_x.empty() ? nullptr : C.set_x.data(), C.set_y.empty() ? nullptr : C.set_y.data(), nullptr);
     };
+    s->prep_calls[0] += 1;
     int rc = bound();
     if (rc == PDMPC_ERR_CAPACITY && C.set_off.back() > (int32_t)C.set_x.size()) {
         C.set_x.resize((size_t)C.set_off.back());
@@ -2418,6 +2450,7 @@ int sweep_bound_on_device(pdmpc_sweep* s, const std::vector<int>& who, bool all_
         adopt_bounded_sets(c, all_steps);
     }
     if (!any_couples_by_sets(s, who)) return PDMPC_OK;
+    s->prep_calls[1] += 1;
     rc = pdmpc_bounded_set_coupling_grouped(s->h, (int32_t)who.size(), C.group_offset.data(), C.adjacency.data(), nullptr);
     if (rc) return cfail(nullptr, rc, std::string("pdmpc_bounded_set_coupling_grouped: ") + pdmpc_last_error());
     scatter_blocks(s);
@@ -2429,6 +2462,7 @@ int sweep_bound_on_host(pdmpc_sweep* s, const std::vector<int>& who) {
     pdmpc_sweep::Call& C = s->call;
     for (int m : who) {
         pdmpc_controller* c = s->members[(size_t)m];
+        s->prep_calls[0] += 1;
         if (const int rc = bound_by_lanelets(c, s->prep[(size_t)m].reach_parallel)) return rc;
     }
     if (!any_couples_by_sets(s, who)) return PDMPC_OK;
@@ -2449,6 +2483,7 @@ int sweep_bound_on_host(pdmpc_sweep* s, const std::vector<int>& who) {
     C.set_x.push_back(0.0);
     C.set_y.push_back(0.0);
     const pdmpc_polygon_set ps = view_polygons(C.set_off, C.set_x, C.set_y);
+    s->prep_calls[1] += 1;
     const int rc = pdmpc_polygon_set_coupling_grouped_host(&ps, (int32_t)who.size(), C.group_offset.data(), C.adjacency.data(), nullptr);
     if (rc) return cfail(nullptr, rc, "pdmpc_polygon_set_coupling_grouped_host failed");
     scatter_blocks(s);
@@ -2461,6 +2496,7 @@ int sweep_couple_hulls(pdmpc_sweep* s, const std::vector<int>& who) {
     pdmpc_sweep::Call& C = s->call;
     if (s->h) {
         gather(s, who, false);
+        s->prep_calls[2] += 1;
         const int rc = pdmpc_reachable_set_coupling_grouped(s->h, (int32_t)who.size(), C.group_offset.data(), C.x.data(), C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(),
                                                             C.trim.data(), C.adjacency.data(), nullptr);
         if (rc) return cfail(nullptr, rc, std::string("pdmpc_reachable_set_coupling_grouped: ") + pdmpc_last_error());
@@ -2478,6 +2514,7 @@ int sweep_couple_hulls(pdmpc_sweep* s, const std::vector<int>& who) {
         }
         gather(s, same, false);
         const pdmpc_polygon_set ps = view_polygons(c0->reach_off, c0->reach_x, c0->reach_y);
+        s->prep_calls[2] += 1;
         const int rc = pdmpc_reachable_set_coupling_grouped_host((int32_t)c0->trim_speed.size(), c0->Hp, &ps, (int32_t)same.size(), C.group_offset.data(), C.x.data(),
                                                                  C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(), C.trim.data(), C.adjacency.data(), nullptr);
         if (rc) return cfail(nullptr, rc, "pdmpc_reachable_set_coupling_grouped_host failed");
@@ -2485,6 +2522,49 @@ int sweep_couple_hulls(pdmpc_sweep* s, const std::vector<int>& who) {
         rest = other;
     }
     return PDMPC_OK;
+}
+
+// future collision assessment of the members `who` (their adjacency is there) in ONE grouped call, every member with its own coupled
+// pairs, scenario obstacles and vehicle sizes; the counts and priorities then stand in s->fca, member after member
+int sweep_assess_collisions(pdmpc_sweep* s, const std::vector<int>& who) {
+    if (who.empty()) return PDMPC_OK;
+    pdmpc_sweep::Fca& F = s->fca;
+    F.groups.assign(who.size(), pdmpc_fca_group());
+    F.obstacles.resize(who.size());
+    F.x.clear();
+    F.y.clear();
+    F.cos_yaw.clear();
+    F.sin_yaw.clear();
+    for (size_t g = 0; g < who.size(); ++g) {
+        pdmpc_controller* c = s->members[(size_t)who[g]];
+        if (const int rc = fca_inputs(c)) return rc;
+        F.x.insert(F.x.end(), c->fca_x.begin(), c->fca_x.end());
+        F.y.insert(F.y.end(), c->fca_y.begin(), c->fca_y.end());
+        F.cos_yaw.insert(F.cos_yaw.end(), c->fca_cos.begin(), c->fca_cos.end());
+        F.sin_yaw.insert(F.sin_yaw.end(), c->fca_sin.begin(), c->fca_sin.end());
+        F.obstacles[g] = view_polygons(c->fca_obst_off, c->fca_obst_x, c->fca_obst_y);
+        pdmpc_fca_group& G = F.groups[g];
+        G.n = c->n;
+        G.n_pairs = (int32_t)(c->fca_pairs.size() / 2);
+        G.pairs = c->fca_pairs.data();
+        G.obstacles = &F.obstacles[g];
+        G.dynamic_rows = nullptr;
+        G.length = c->cfg.vehicle_length;
+        G.width = c->cfg.vehicle_width;
+        G.offset = c->cfg.offset;
+    }
+    const size_t n = F.x.size() / (size_t)s->members[0]->Hp;
+    F.collisions.assign(n, 0);
+    F.priorities.assign(n, 0);
+    s->prep_calls[3] += 1;
+    if (s->h) {
+        const int rc = pdmpc_fca_collisions_grouped(s->h, (int32_t)who.size(), F.groups.data(), s->members[0]->Hp, F.x.data(), F.y.data(), F.cos_yaw.data(),
+                                                    F.sin_yaw.data(), F.collisions.data(), F.priorities.data());
+        return rc ? cfail(nullptr, rc, std::string("pdmpc_fca_collisions_grouped: ") + pdmpc_last_error()) : PDMPC_OK;
+    }
+    const int rc = pdmpc_fca_collisions_grouped_host((int32_t)who.size(), F.groups.data(), s->members[0]->Hp, F.x.data(), F.y.data(), F.cos_yaw.data(), F.sin_yaw.data(),
+                                                     F.collisions.data(), F.priorities.data());
+    return rc ? cfail(nullptr, rc, "pdmpc_fca_collisions_grouped_host failed") : PDMPC_OK;
 }
 
 // every member's step problem, built with ONE step preparation for all of them; n_perm > 0: every member's explorative batch of n_perm
@@ -2502,6 +2582,7 @@ int sweep_build_members(pdmpc_sweep* s, int n_perm) {
         }
     } exploring(s, n_perm > 0);
     s->prep.assign(M, StepPrep());
+    std::fill(s->prep_calls, s->prep_calls + 4, 0);
     for (size_t m = 0; m < M; ++m)
         if (const int rc = begin_step(s->members[m], s->prep[m])) return rc;
     // who takes part in which grouped call: bounded (step Hp only / every step: one bounding call each) or the plain hulls
@@ -2524,11 +2605,23 @@ int sweep_build_members(pdmpc_sweep* s, int n_perm) {
     }
     if (!rc) rc = sweep_couple_hulls(s, hulls);
     if (rc) return rc;
+    std::vector<int> assessed;  // the members with FCA priorities: assessed together once every member's adjacency is there
     for (size_t m = 0; m < M; ++m) {
         pdmpc_controller* c = s->members[m];
         const StepPrep& P = s->prep[m];
-        rc = couple(c, P.bounded ? (P.reach_parallel ? c->Hp : 1) : 0, true);
-        if (!rc) rc = finish_step(c);
+        if (const int rc1 = couple(c, P.bounded ? (P.reach_parallel ? c->Hp : 1) : 0, true)) return rc1;
+        if (c->cfg.priority_strategy == PDMPC_PRIORITY_FCA) assessed.push_back((int)m);
+    }
+    if (const int rc1 = sweep_assess_collisions(s, assessed)) return rc1;
+    for (size_t m = 0, g = 0, v0 = 0; m < M; ++m) {
+        pdmpc_controller* c = s->members[m];
+        if (g < assessed.size() && assessed[g] == (int)m) {
+            rc = finish_step(c, s->fca.collisions.data() + v0, s->fca.priorities.data() + v0);
+            v0 += (size_t)c->n;
+            ++g;
+        } else {
+            rc = finish_step(c);
+        }
         if (!rc && n_perm > 0) rc = permute_instances(c, n_perm, (uint32_t)c->k);  // RandStream("mt19937ar", Seed = obj.k) (:249)
         if (rc) return rc;
     }
@@ -2807,6 +2900,12 @@ int pdmpc_sweep_run(pdmpc_sweep* s, int32_t n_steps, double* ms) {
 int pdmpc_sweep_last_timing(pdmpc_sweep* s, double* ms6) {
     if (!s || !ms6) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
     for (int i = 0; i < 6; ++i) ms6[i] = s->timing[i];
+    return PDMPC_OK;
+}
+
+int pdmpc_sweep_last_prep_calls(pdmpc_sweep* s, int32_t* calls4) {
+    if (!s || !calls4) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
+    std::copy(s->prep_calls, s->prep_calls + 4, calls4);
     return PDMPC_OK;
 }
 

@@ -551,6 +551,138 @@ int pdmpc_fca_collisions(pdmpc_handle* h, int32_t n, int32_t Hp, const double* x
     return PDMPC_OK;
 }
 
+// ... for several independent sets of vehicles in one call: the groups' reference points as they come, their polygons
+// one group after the other, their pairs rebased to the concatenated vehicles, and the tables the kernels locate an item's group with
+int pdmpc_fca_collisions_grouped(pdmpc_handle* h, int32_t n_groups, const pdmpc_fca_group* groups, int32_t Hp, const double* x, const double* y,
+                                 const double* cos_yaw, const double* sin_yaw, int32_t* collisions, int32_t* priorities) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    char why[160];
+    int32_t n = 0;
+    if (const int rc = pdmpc_fca_check_groups(n_groups, groups, Hp, x, y, cos_yaw, sin_yaw, collisions, priorities, &n, why, (int32_t)sizeof why))
+        return fail(rc, std::string("pdmpc_fca_collisions_grouped: ") + why);
+    if (n > h->max_vehicles) return fail(PDMPC_ERR_CAPACITY, "pdmpc_fca_collisions_grouped: more vehicles than config.max_vehicles");
+    if (n == 0) return PDMPC_OK;
+    const int m = n * Hp;
+    // what a group brings: S static polygons of Ns vertices from vertex s0 on, D = R Hp dynamic ones of Nd vertices from d0 on
+    struct Sizes {
+        int S, D, s0, Ns, d0, Nd;
+    };
+    auto sizes_of = [](const pdmpc_fca_group& G) {
+        Sizes z;
+        z.S = G.n && G.obstacles ? G.obstacles->n_polygons : 0;
+        z.D = G.n && G.dynamic_rows ? G.dynamic_rows->n_polygons : 0;
+        z.s0 = z.S ? G.obstacles->offset[0] : 0;
+        z.Ns = z.S ? G.obstacles->offset[z.S] - z.s0 : 0;
+        z.d0 = z.D ? G.dynamic_rows->offset[0] : 0;
+        z.Nd = z.D ? G.dynamic_rows->offset[z.D] - z.d0 : 0;
+        return z;
+    };
+    int64_t S = 0, D = 0, Ns = 0, Nd = 0, n_pairs = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const Sizes z = sizes_of(groups[g]);
+        S += z.S;
+        D += z.D;
+        Ns += z.Ns;
+        Nd += z.Nd;
+        n_pairs += groups[g].n ? groups[g].n_pairs : 0;
+    }
+    if (S > INT32_MAX || D > INT32_MAX || Ns > INT32_MAX || Nd > INT32_MAX || n_pairs > INT32_MAX)
+        return fail(PDMPC_ERR_CAPACITY, "pdmpc_fca_collisions_grouped: more than 2^31 polygons, vertices or pairs");
+    // FcaState::ws and its pinned staging of the inputs, the block's first in_bytes, as for the ungrouped call; then the group tables
+    Carver c;
+    const size_t o_in = c.take<double>((size_t)4 * m);
+    const size_t o_stat = c.take<double>((size_t)2 * Ns);
+    const size_t o_dyn = c.take<double>((size_t)2 * Nd);
+    const size_t o_stat_first = c.take<int64_t>((size_t)n_groups + 1);
+    const size_t o_dyn_first = c.take<int64_t>((size_t)n_groups + 1);
+    const size_t o_group = c.take<FcaGroup>((size_t)n_groups);
+    const size_t o_pairs = c.take<int32_t>((size_t)2 * n_pairs);
+    const size_t o_stat_off = c.take<int32_t>((size_t)S + 1);
+    const size_t o_dyn_off = c.take<int32_t>((size_t)D + 1);
+    const size_t o_vehicle_group = c.take<int32_t>((size_t)n);
+    const size_t in_bytes = c.end8();
+    const size_t o_fp = c.take<double>((size_t)8 * m);
+    const size_t o_counts = c.take<int32_t>((size_t)n);
+    const size_t total = c.at;
+    ON_DEVICE(h->cfg.device);
+    FcaState& F = h->fca;
+    if (F.ws.ensure(total) || F.h_in.ensure(in_bytes) || F.h_out.ensure((size_t)n)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the collision assessment");
+    unsigned char *hin = F.h_in.p, *ws = F.ws.p;
+    stage_poses((double*)(hin + o_in), (size_t)m, x, y, cos_yaw, sin_yaw);
+    double *hs = (double*)(hin + o_stat), *hdyn = (double*)(hin + o_dyn);
+    int64_t *stat_first = (int64_t*)(hin + o_stat_first), *dyn_first = (int64_t*)(hin + o_dyn_first);
+    FcaGroup* hg = (FcaGroup*)(hin + o_group);
+    int32_t *hp = (int32_t*)(hin + o_pairs), *soff = (int32_t*)(hin + o_stat_off), *doff = (int32_t*)(hin + o_dyn_off), *vg = (int32_t*)(hin + o_vehicle_group);
+    int v0 = 0, sp = 0, dp = 0, sv = 0, dv = 0;  // the next group's first vehicle, polygons and vertices
+    int64_t pairs_done = 0;
+    stat_first[0] = dyn_first[0] = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const pdmpc_fca_group& G = groups[g];
+        const Sizes z = sizes_of(G);
+        hg[g] = FcaGroup{v0, z.S, z.D / Hp, sp, dp, G.length, G.width, G.offset};
+        // (the reference's outer loop stops at n - 1, per group: the last vehicle of a group has no obstacle items)
+        stat_first[g + 1] = stat_first[g] + (G.n ? (int64_t)(G.n - 1) * Hp * z.S : 0);
+        dyn_first[g + 1] = dyn_first[g] + (G.n ? (int64_t)(G.n - 1) * Hp * (z.D / Hp) : 0);
+        if (G.n == 0) continue;
+        for (int v = 0; v < G.n; ++v) vg[v0 + v] = g;
+        for (int p = 0; p < 2 * G.n_pairs; ++p) hp[2 * pairs_done + p] = v0 + G.pairs[p];
+        pairs_done += G.n_pairs;
+        if (z.Ns) {
+            std::memcpy(hs + sv, G.obstacles->x + z.s0, (size_t)z.Ns * sizeof(double));
+            std::memcpy(hs + Ns + sv, G.obstacles->y + z.s0, (size_t)z.Ns * sizeof(double));
+        }
+        if (z.Nd) {
+            std::memcpy(hdyn + dv, G.dynamic_rows->x + z.d0, (size_t)z.Nd * sizeof(double));
+            std::memcpy(hdyn + Nd + dv, G.dynamic_rows->y + z.d0, (size_t)z.Nd * sizeof(double));
+        }
+        for (int p = 0; p < z.S; ++p) soff[sp + p] = sv + G.obstacles->offset[p] - z.s0;
+        for (int p = 0; p < z.D; ++p) doff[dp + p] = dv + G.dynamic_rows->offset[p] - z.d0;
+        v0 += G.n;
+        sp += z.S;
+        dp += z.D;
+        sv += z.Ns;
+        dv += z.Nd;
+    }
+    soff[S] = (int32_t)Ns;
+    doff[D] = (int32_t)Nd;
+    FcaGroupedArgs B;
+    std::memset(&B, 0, sizeof B);
+    FcaArgs& A = B.a;
+    A.n = n;
+    A.Hp = Hp;
+    A.n_pairs = (int32_t)n_pairs;
+    A.n_pair_items = n_pairs * Hp;
+    A.n_static_items = stat_first[n_groups];
+    A.n_items = A.n_pair_items + A.n_static_items + dyn_first[n_groups];
+    A.in = (const double*)(ws + o_in);
+    A.static_x = (const double*)(ws + o_stat);
+    A.static_y = A.static_x + Ns;
+    A.dyn_x = (const double*)(ws + o_dyn);
+    A.dyn_y = A.dyn_x + Nd;
+    A.pairs = (const int32_t*)(ws + o_pairs);
+    A.static_off = (const int32_t*)(ws + o_stat_off);
+    A.dyn_off = (const int32_t*)(ws + o_dyn_off);
+    A.fp = (double*)(ws + o_fp);
+    A.counts = (int32_t*)(ws + o_counts);
+    B.g.n_groups = n_groups;
+    B.g.group = (const FcaGroup*)(ws + o_group);
+    B.g.vehicle_group = (const int32_t*)(ws + o_vehicle_group);
+    B.g.static_first = (const int64_t*)(ws + o_stat_first);
+    B.g.dyn_first = (const int64_t*)(ws + o_dyn_first);
+    HIPCHK(hipMemcpyAsync(ws, hin, in_bytes, hipMemcpyHostToDevice, h->stream));
+    if (const int rc = timed_launch(h, F.timed, pdmpc_launch_fca_grouped, B, "collision assessment")) return rc;
+    HIPCHK(hipMemcpyAsync(F.h_out.p, ws + o_counts, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(sync_stream(h));
+    F.timed.fold();
+    std::memcpy(collisions, F.h_out.p, (size_t)n * sizeof(int32_t));
+    v0 = 0;
+    for (int g = 0; g < n_groups; ++g) {  // every group's own index vector
+        if (groups[g].n) pdmpc_fca_sort_index(groups[g].n, collisions + v0, priorities + v0);
+        v0 += groups[g].n;
+    }
+    return PDMPC_OK;
+}
+
 int pdmpc_fca_kernel_ms(pdmpc_handle* h, double* ms) {
     if (!h || !ms) return fail(PDMPC_ERR_INVALID, "null argument");
     *ms = (double)h->fca.timed.ms;

@@ -126,6 +126,10 @@ EXPORTS = [
     "pdmpc_fca_collisions",
     "pdmpc_fca_collisions_host",
     "pdmpc_fca_kernel_ms",
+    "pdmpc_fca_collisions_grouped",
+    "pdmpc_fca_collisions_grouped_host",
+    "pdmpc_controller_priorities",
+    "pdmpc_sweep_last_prep_calls",
     "pdmpc_controller_set_lanelet_bounding",
     "pdmpc_plan_step_sampled",
     "pdmpc_set_step_seeds",
@@ -371,6 +375,68 @@ def fca_collisions_host(reference_points, pairs, length, width, offset, obstacle
     return out
 
 
+class FcaGroup(C.Structure):
+    """pdmpc_fca_group (include/pdmpc.h)"""
+
+    _fields_ = [("n", C.c_int32), ("n_pairs", C.c_int32), ("pairs", abi.c_int32_p), ("obstacles", C.POINTER(abi.PolygonSet)),
+                ("dynamic_rows", C.POINTER(abi.PolygonSet)), ("length", C.c_double), ("width", C.c_double), ("offset", C.c_double)]
+
+
+def fca_grouped_pack(groups, Hp=None):
+    """The arguments of pdmpc_fca_collisions_grouped(_host) after the handle -> (args, a call that decodes the outputs into
+    [(collisions (n_g,), priorities (n_g,)) per group], keep-alive).  groups: per group a dict of fca_collisions_host's arguments
+    (reference_points, pairs, length, width, offset and, optionally, obstacles, dynamic_obstacle_area, headings); a group without
+    vehicles is legal.  Hp: the horizon, where no group has a vehicle to tell it.  An empty obstacle list is handed over as NULL."""
+    keeps, arr, parts, sizes = [], (FcaGroup * max(len(groups), 1))(), [[], [], [], []], []
+    for g, G in enumerate(groups):
+        G = dict(G)
+        refs = G.pop("reference_points")
+        obst, dyn = G.pop("obstacles", ()), G.pop("dynamic_obstacle_area", ())
+        args, _, keep = fca_pack(refs, G.pop("pairs"), G.pop("length"), G.pop("width"), G.pop("offset"), obst, dyn, G.pop("headings", None))
+        if G:
+            raise TypeError("unknown entries of group %d: %s" % (g, sorted(G)))
+        n, hp = args[0], args[1]
+        if n:
+            if Hp is not None and hp != Hp:
+                raise ValueError("group %d has Hp %d, the call %d" % (g, hp, Hp))
+            Hp = hp
+            for part, a in zip(parts, keep.refs[:4]):  # x, y, cos, sin of its reference points
+                part.append(a)
+        keeps.append(keep)
+        sizes.append(n)
+        arr[g].n, arr[g].n_pairs, arr[g].pairs = n, args[6], args[7] if args[6] else None
+        arr[g].obstacles = C.pointer(keep.refs[-2]) if len(obst) else None
+        arr[g].dynamic_rows = C.pointer(keep.refs[-1]) if keep.refs[-1] is not None else None
+        arr[g].length, arr[g].width, arr[g].offset = args[10], args[11], args[12]
+    x, y, c, s = (np.ascontiguousarray(np.concatenate(part + [np.zeros(1)])) for part in parts)
+    N = int(sum(sizes))
+    coll = np.zeros(max(N, 1), dtype=np.int32)
+    prio = np.zeros(max(N, 1), dtype=np.int32)
+    keeps += [arr, x, y, c, s]
+    args = [len(groups), arr, Hp if Hp is not None else 0] + [a.ctypes.data_as(abi.c_double_p) for a in (x, y, c, s)] + [
+        coll.ctypes.data_as(abi.c_int32_p), prio.ctypes.data_as(abi.c_int32_p)]
+    at = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+
+    def per_group():
+        return [(coll[at[g] : at[g + 1]].copy(), prio[at[g] : at[g + 1]].copy()) for g in range(len(groups))]
+
+    return args, per_group, keeps
+
+
+def fca_collisions_grouped_call(groups, Hp=None, handle=None):
+    """FcaPrioritizer for several independent sets of vehicles at once (pdmpc_fca_collisions_grouped_host; on `handle`'s device,
+    pdmpc_fca_collisions_grouped, if one is given); groups, Hp: see fca_grouped_pack.  -> [(collisions (n_g,), priorities (n_g,)) per
+    group]: what fca_collisions_host returns for each group alone."""
+    L = load_library()
+    args, per_group, keep = fca_grouped_pack(groups, Hp)
+    if handle is not None:
+        _check(L, L.pdmpc_fca_collisions_grouped(handle.h, *args), "pdmpc_fca_collisions_grouped")
+    else:
+        _check(L, L.pdmpc_fca_collisions_grouped_host(*args), "pdmpc_fca_collisions_grouped_host", message=False)
+    del keep
+    return per_group()
+
+
 def _pack_lanelet_polygons(lanelet_polys):
     """[vehicle] raw lanelet polygon (2, P) or None (not bounded) -> (pdmpc_polygon_set, keep-alive)."""
     keep = abi._Keep()
@@ -561,6 +627,9 @@ def load_library(path=None):
     L.pdmpc_fca_collisions.argtypes = [H] + fca_tail
     L.pdmpc_fca_collisions_host.argtypes = fca_tail
     L.pdmpc_fca_kernel_ms.argtypes = [H, abi.c_double_p]
+    fca_grouped_tail = [C.c_int32, C.POINTER(FcaGroup), C.c_int32] + [abi.c_double_p] * 4 + [abi.c_int32_p, abi.c_int32_p]
+    L.pdmpc_fca_collisions_grouped.argtypes = [H] + fca_grouped_tail
+    L.pdmpc_fca_collisions_grouped_host.argtypes = fca_grouped_tail
     L.pdmpc_controller_set_lanelet_bounding.argtypes = [H, C.c_int32]
     choice_tail = [C.POINTER(ChoiceStruct), abi.c_int32_p, abi.c_double_p]
     L.pdmpc_choose_host.argtypes = [C.c_int32, abi.c_int32_p, abi.c_double_p] + choice_tail
@@ -868,8 +937,12 @@ class Handle:
         """FcaPrioritizer on this handle's device (pdmpc_fca_collisions) -> (collisions, priorities); see fca_collisions_host."""
         return fca_collisions_host(reference_points, pairs, length, width, offset, obstacles, dynamic_obstacle_area, handle=self, headings=headings)
 
+    def fca_collisions_grouped(self, groups, Hp=None):
+        """pdmpc_fca_collisions_grouped on this handle's device -> [(collisions, priorities) per group]; see fca_collisions_grouped_call."""
+        return fca_collisions_grouped_call(groups, Hp, handle=self)
+
     def fca_kernel_ms(self):
-        """kernel time (ms) of the last fca_collisions"""
+        """kernel time (ms) of the last fca_collisions or fca_collisions_grouped"""
         ms = C.c_double(0.0)
         _check(self.L, self.L.pdmpc_fca_kernel_ms(self.h, C.byref(ms)), "pdmpc_fca_kernel_ms")
         return ms.value

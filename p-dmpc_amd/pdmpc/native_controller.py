@@ -87,6 +87,7 @@ def _declare(L):
     L.pdmpc_sweep_step.argtypes = [H]
     L.pdmpc_sweep_run.argtypes = [H, C.c_int32, abi.c_double_p]
     L.pdmpc_sweep_last_timing.argtypes = [H, C.c_void_p]
+    L.pdmpc_sweep_last_prep_calls.argtypes = [H, abi.c_int32_p]
     L.pdmpc_sweep_explore_build.argtypes = [H, C.c_int32]
     L.pdmpc_sweep_explore_problem.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.POINTER(abi.VehicleIn)), C.POINTER(abi.c_int32_p), C.POINTER(abi.c_int32_p),
                                               C.POINTER(C.POINTER(abi.PolygonSet))] + [C.POINTER(abi.c_int32_p)] * 4
@@ -95,7 +96,7 @@ def _declare(L):
     L.pdmpc_sweep_explore_run.argtypes = [H, C.c_int32, C.c_int32, abi.c_double_p]
     L.pdmpc_controller_set_device_choice.argtypes = [H, C.c_int32]
     for name in ("pdmpc_sweep_create", "pdmpc_sweep_destroy", "pdmpc_sweep_build", "pdmpc_sweep_problem", "pdmpc_sweep_apply", "pdmpc_sweep_step", "pdmpc_sweep_run",
-                 "pdmpc_sweep_last_timing", "pdmpc_sweep_explore_build", "pdmpc_sweep_explore_problem", "pdmpc_sweep_explore_apply", "pdmpc_sweep_explore_step",
+                 "pdmpc_sweep_last_timing", "pdmpc_sweep_last_prep_calls", "pdmpc_sweep_explore_build", "pdmpc_sweep_explore_problem", "pdmpc_sweep_explore_apply", "pdmpc_sweep_explore_step",
                  "pdmpc_sweep_explore_run", "pdmpc_controller_set_device_choice"):
         getattr(L, name).restype = C.c_int
     L._controller_declared = True
@@ -201,6 +202,16 @@ class NativeController:
         p = C.POINTER(C.c_uint32)()
         self._check(self.L.pdmpc_controller_seeds(self.c, C.byref(n), C.byref(p)), "pdmpc_controller_seeds")
         return [int(p[i]) for i in range(n.value)]
+
+    def priorities(self):
+        """(priorities, collisions) of the last built step (pdmpc_controller_priorities): the 1-based priorities of a constant, random or
+        FCA step and the collision counts of an FCA step; empty where the strategy has none."""
+        self.L.pdmpc_controller_priorities.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32), C.POINTER(abi.c_int32_p)] * 2
+        self.L.pdmpc_controller_priorities.restype = C.c_int
+        n_p, n_c = C.c_int32(), C.c_int32()
+        p, q = abi.c_int32_p(), abi.c_int32_p()
+        self._check(self.L.pdmpc_controller_priorities(self.c, C.byref(n_p), C.byref(p), C.byref(n_c), C.byref(q)), "pdmpc_controller_priorities")
+        return [int(p[i]) for i in range(n_p.value)], [int(q[i]) for i in range(n_c.value)]
 
     def _check(self, rc, what):
         if rc != 0:
@@ -517,6 +528,13 @@ class NativeSweep:
         self._check(self.L.pdmpc_sweep_explore_run(self.s, n_perm, n_steps, ms.ctypes.data_as(abi.c_double_p)), "pdmpc_sweep_explore_run")
         self._n_perm(n_perm)
         return ms[:n_steps]
+
+    def prep_calls(self):
+        """The step-preparation calls of the last build, whatever the number of members (pdmpc_sweep_last_prep_calls): [lanelet
+        bounding, coupler on the bounded sets, coupler on the plain hulls, future collision assessment]."""
+        calls = np.zeros(4, dtype=np.int32)
+        self._check(self.L.pdmpc_sweep_last_prep_calls(self.s, calls.ctypes.data_as(abi.c_int32_p)), "pdmpc_sweep_last_prep_calls")
+        return calls.tolist()
 
     def last_timing(self):
         """Host milliseconds of the last lock-step by part (pdmpc_sweep_last_timing)."""

@@ -3,15 +3,18 @@ another by the parent commit's library.
 
 Workload: M in {1, 2, 4, 8} C2-like members (20 vehicles, Hp 8, seeds 1 .. M) on one handle, steps 21-40 of each closed loop, with
   (a) distance coupling,
-  (b) reachable-set coupling with lanelet bounding.
+  (b) reachable-set coupling with lanelet bounding,
+  (c) distance coupling, FCA priorities.
 Sweep: the median wall time per lock-step of pdmpc_sweep_run and the six parts of pdmpc_sweep_last_timing.
 Baseline: a built checkout of the parent commit in a directory of its own (--baseline-root: its p-dmpc_amd/pdmpc package and its
 p-dmpc_amd/csrc/libpdmpc_hip.so); per lock-step every member takes one pdmpc_controller_run(1), the lock-step's time is their sum.
+In (c) the baseline is the parent commit's library stepping the SAME SWEEP: what changes is the collision assessment inside the
+lock-step, one grouped call here against one call per member there, so its lock-step and its build part are compared.
 Five alternating runs of baseline and sweep, each in a fresh process; reported are the median of the five medians and their spread
 (max - min).  For (b) also one grouped device call (pdmpc_bound_reachable_sets on all members' vehicles + pdmpc_bounded_set_coupling_grouped)
 against M ungrouped pairs of calls on the members' recorded states, in kernel time (HIP events) and as whole calls.
 
-    python tools/sweep_timing.py --baseline-root DIR [--rounds 5] [--out profiles/sweep_timing.txt]
+    python tools/sweep_timing.py --baseline-root DIR [--rounds 5] [--modes a,b,c] [--out profiles/sweep_timing.txt]
 """
 import argparse
 import json
@@ -22,7 +25,9 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MS = (1, 2, 4, 8)
-MODES = {"a": dict(coupling="distance"), "b": dict(coupling="reachable_set", bound_reachable_sets=True)}
+MODES = {"a": dict(coupling="distance"), "b": dict(coupling="reachable_set", bound_reachable_sets=True), "c": dict(coupling="distance", priority_strategy="fca")}
+TITLES = {"a": "distance coupling", "b": "reachable-set coupling with lanelet bounding", "c": "distance coupling, FCA priorities"}
+SWEEP_BASELINE = ("c",)  # the modes whose baseline is the parent's library stepping the same sweep
 PARTS = ("build", "pack", "enqueue", "wait_and_read_back", "choose", "apply")
 WARMUP, TIMED = 20, 20
 
@@ -37,23 +42,24 @@ def members_on_one_handle(M, mode):
 
     kw = dict(MODES[mode])
     coupling = kw.pop("coupling")
+    ctl = {k: kw.pop(k) for k in ("priority_strategy",) if k in kw}
     options = Config(scenario_type=ScenarioType.commonroad, amount=20, Hp=8, max_vehicles=max(32, 20 * M), max_nodes=1 << 17, **kw)
     mpa = get_mpa(options)
     h = Handle(options)
     h.upload_mpa(mpa)
     scs = [commonroad_scenario(options, seed=s) for s in range(1, M + 1)]
-    return options, mpa, h, scs, [NativeController(options, sc, mpa, h, coupling=coupling) for sc in scs]
+    return options, mpa, h, scs, [NativeController(options, sc, mpa, h, coupling=coupling, **ctl) for sc in scs]
 
 
-def worker(kind):
+def worker(kind, modes):
     """One run: every mode and M on the tree this process imports -> one JSON line."""
     import numpy as np
 
     out = {}
-    for mode in MODES:
+    for mode in modes:
         for M in MS:
             options, mpa, h, scs, cs = members_on_one_handle(M, mode)
-            if kind == "baseline":
+            if kind == "baseline" and mode not in SWEEP_BASELINE:
                 step_ms = []
                 for k in range(WARMUP + TIMED):
                     step_ms.append(sum(float(c.run(1)[0]) for c in cs))
@@ -143,15 +149,17 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sweep_timing.txt"))
+    ap.add_argument("--modes", default=",".join(MODES))
     ap.add_argument("--worker")
     args = ap.parse_args()
+    modes = [m for m in MODES if m in args.modes.split(",")]
     if args.worker:
         tree = os.environ.get("PDMPC_TREE", ROOT)
         sys.path[:0] = [tree, os.path.join(tree, "p-dmpc_amd")]
         if args.worker == "grouped":
             grouped_calls(args.reps)
         else:
-            worker(args.worker)
+            worker(args.worker, modes)
         return
     if not args.baseline_root:
         raise SystemExit("--baseline-root: a built checkout of the parent commit is needed")
@@ -159,15 +167,15 @@ def main():
 
     base, sweep = [], []
     for r in range(args.rounds):
-        base.append(child(os.path.abspath(args.baseline_root), "--worker", "baseline"))
-        sweep.append(child(ROOT, "--worker", "sweep"))
+        base.append(child(os.path.abspath(args.baseline_root), "--worker", "baseline", "--modes", ",".join(modes)))
+        sweep.append(child(ROOT, "--worker", "sweep", "--modes", ",".join(modes)))
         print("round %d done" % (r + 1), flush=True)
-    grouped = child(ROOT, "--worker", "grouped", "--reps", str(args.reps))
+    grouped = child(ROOT, "--worker", "grouped", "--reps", str(args.reps)) if "b" in modes else None
     lines = ["sweep against the parent commit's library: M C2-like members (20 vehicles, Hp 8, seeds 1..M), steps %d-%d, ms per lock-step;"
              % (WARMUP + 1, WARMUP + TIMED),
-             "median and spread (max - min) of %d alternating runs' medians; baseline = sum of the members' pdmpc_controller_run(1)" % args.rounds]
-    for mode in MODES:
-        lines.append("(%s) %s" % (mode, "distance coupling" if mode == "a" else "reachable-set coupling with lanelet bounding"))
+             "median and spread (max - min) of %d alternating runs' medians; baseline = sum of the members' pdmpc_controller_run(1) unless a block says otherwise" % args.rounds]
+    for mode in modes:
+        lines.append("(%s) %s" % (mode, TITLES[mode]) + ("; baseline = the parent commit's library stepping the same sweep" if mode in SWEEP_BASELINE else ""))
         for M in MS:
             key = "%s%d" % (mode, M)
             b = [r[key]["median"] for r in base]
@@ -181,11 +189,18 @@ def main():
             parts = np.median(np.array([r[key]["parts"] for r in sweep]), axis=0)
             lines.append("  M=%d  baseline %7.3f (spread %.3f)   sweep %7.3f (spread %.3f)   ratio %.2f   %s" % (M, mb, sb, ms_, ss, mb / ms_, verdict))
             lines.append("        sweep parts: " + "  ".join("%s %.3f" % (p, v) for p, v in zip(PARTS, parts)))
-    lines.append("(b) step preparation on the members' states after 30 steps, median of %d: one pdmpc_bound_reachable_sets + pdmpc_bounded_set_coupling_grouped"
-                 " against M pairs of ungrouped calls" % args.reps)
-    for M in MS:
-        gk, gc, uk, uc = grouped[str(M)]
-        lines.append("  M=%d  kernels (events) grouped %.4f ms, ungrouped %.4f ms   whole calls grouped %.4f ms, ungrouped %.4f ms" % (M, gk, uk, gc, uc))
+            if mode in SWEEP_BASELINE:  # the build part, where the collision assessment runs, by itself
+                bb = [r[key]["parts"][0] for r in base]
+                sb_ = [r[key]["parts"][0] for r in sweep]
+                mbb, msb, spread_b = float(np.median(bb)), float(np.median(sb_)), max(max(bb) - min(bb), max(sb_) - min(sb_))
+                lines.append("        build part: baseline %.4f  sweep %.4f  larger spread %.4f   %s"
+                             % (mbb, msb, spread_b, "below the baseline by more than the spread" if mbb - msb > spread_b else "NOT below the baseline by more than the spread"))
+    if grouped is not None:
+        lines.append("(b) step preparation on the members' states after 30 steps, median of %d: one pdmpc_bound_reachable_sets + pdmpc_bounded_set_coupling_grouped"
+                     " against M pairs of ungrouped calls" % args.reps)
+        for M in MS:
+            gk, gc, uk, uc = grouped[str(M)]
+            lines.append("  M=%d  kernels (events) grouped %.4f ms, ungrouped %.4f ms   whole calls grouped %.4f ms, ungrouped %.4f ms" % (M, gk, uk, gc, uc))
     print("\n".join(lines), flush=True)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
