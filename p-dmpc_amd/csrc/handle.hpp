@@ -445,7 +445,8 @@ struct pdmpc_handle {
     DevBuf<uint32_t> d_help_verdict, d_help_finished;
     DevBuf<double> d_bk_post;                 // records posted for the helper workgroups
     DevBuf<int32_t> d_joint_off;         // pdmpc_plan_joint: the problems' first slots
-    // the step-preparation calls (step_prep.cpp), one member per call family
+    // the step-preparation calls (step_prep.cpp), one member per call family: a family's ungrouped and grouped entry points stage
+    // through one body into the same buffers
     PrioState prio;
     ReachState reach;
     BoundState bound;

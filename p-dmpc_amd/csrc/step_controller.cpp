@@ -22,6 +22,12 @@
 //   plant                     Simulation.apply (plant/Simulation.m:86-100)
 // Every floating-point expression keeps the order of the Python twin (which keeps the reference's), and both call the
 // same libm, so the step problems the two build are bit-identical (tests/test_native_controller.py).
+//
+// One path for a controller alone and for a sweep of M: build_members prepares the step of a span of members -- the
+// device calls or their host twins, grouped by member, the only fork on the handle and the only capacity retry -- between the
+// per-member halves begin_step and finish_step (pdmpc_controller_build_step: M = 1, in the controller's own scratch); plan_built plans
+// what was built (weights, seeds, the backend call, timing[1..3]) for the step, the batch of prioritizations and both sweep steps;
+// timed_steps is the loop of every *_run.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -111,6 +117,32 @@ struct ChoiceLists {
     }
 };
 
+// What a member's step reads of the reachable sets (begin_step), and the scratch of ONE step preparation over a span of members
+// (prepare_members): a sweep owns one for its members, a controller one for the steps it takes alone.
+struct StepPrep {
+    bool reach_parallel = false, reach = false, bounded = false;
+};
+struct PrepScratch {
+    std::vector<StepPrep> prep;            // per member
+    int32_t prep_calls[4] = {0, 0, 0, 0};  // of the last build: lanelet bounding, bounded coupling, hull coupling, collision assessment
+    // one grouped bounding / coupler call: the vehicles of the members that take part, member after member
+    struct Call {
+        std::vector<int> who;                // members
+        std::vector<int32_t> group_offset;   // [who.size() + 1]
+        std::vector<double> x, y, cos_yaw, sin_yaw;
+        std::vector<int32_t> trim, lan_off, set_off;
+        std::vector<double> lan_x, lan_y, set_x, set_y;
+        std::vector<uint8_t> adjacency;      // the blocks
+    } call;
+    // the grouped collision assessment: the FCA members' reference points, member after member, and what it returns
+    struct Fca {
+        std::vector<pdmpc_fca_group> groups;
+        std::vector<pdmpc_polygon_set> obstacles;  // [groups.size()] views of the members' scenario obstacles
+        std::vector<double> x, y, cos_yaw, sin_yaw;
+        std::vector<int32_t> collisions, priorities;
+    } fca;
+};
+
 struct pdmpc_controller {
     pdmpc_handle* h = nullptr;
     pdmpc_controller_config cfg{};
@@ -135,6 +167,7 @@ struct pdmpc_controller {
     double timing_sum[6] = {0, 0, 0, 0, 0, 0};  // ... summed over the steps since the last pdmpc_controller_timing_sum(reset)
     int64_t timing_steps = 0;
     std::vector<double> last_pops;  // per vehicle: nodes its search popped in the last step (the next step's expected work, pdmpc_set_step_weights)
+    std::vector<double> weights;    // ... per slot of the problem about to be planned (plan_built's scratch)
     int optimizer = PDMPC_OPTIMIZER_GRAPH_SEARCH;  // pdmpc_controller_set_optimizer
     std::vector<uint32_t> seeds;    // per slot of the last built step or batch: time_step + vehicle_index (the sampled optimizer's seeds)
     // per step
@@ -245,6 +278,7 @@ struct pdmpc_controller {
     // cos / sin of its calculate_yaw heading, the coupled pairs a < b, the scenario's obstacles as one polygon set
     std::vector<int32_t> prio, fca_pairs, fca_count, fca_obst_off;
     std::vector<double> fca_x, fca_y, fca_cos, fca_sin, fca_obst_x, fca_obst_y;
+    PrepScratch prep;  // of the steps the controller builds alone (as a member of a sweep it is prepared in the sweep's)
     std::string err;
 };
 
@@ -797,6 +831,51 @@ int cfail(pdmpc_controller* c, int code, const std::string& msg) {
     return code;
 }
 
+// ---- the shared paths of the steps below (templates: outside the extern "C" block)
+// A bounding call that writes its sets into (x, y) of capacity x.size() and their offsets into off: after PDMPC_ERR_CAPACITY it is
+// made once more with the room it asked for (off.back()).  The one capacity retry of the step preparation.
+template <class Bound>
+int bound_with_room(std::vector<int32_t>& off, std::vector<double>& x, std::vector<double>& y, Bound&& bound) {
+    int rc = bound((int32_t)x.size(), x.empty() ? nullptr : x.data(), y.empty() ? nullptr : y.data());
+    if (rc == PDMPC_ERR_CAPACITY && off.back() > (int32_t)x.size()) {
+        x.resize((size_t)off.back());
+        y.resize((size_t)off.back());
+        rc = bound((int32_t)x.size(), x.data(), y.data());
+    }
+    return rc;
+}
+
+// Plans a problem of N slots that has been built -- a controller's, its batch of prioritizations or a sweep's -- on h: last step's work
+// as the expected work of this one (pops_of(slot) + 1: heavy searches are dispatched first; weigh = false: no step has been planned
+// yet), the slots' seeds for the next pack if the optimizer is the sampled one (a sampled bank; nothing for the graph search), the
+// backend call `plan` (pdmpc_plan_step, _lean or _chosen), and its parts (pdmpc_last_call_timing) into timing[1..3].  w: scratch.
+template <class Pops, class Call>
+int plan_built(pdmpc_handle* h, int N, bool weigh, std::vector<double>& w, Pops&& pops_of, int optimizer, const std::vector<uint32_t>& seeds, double* timing, Call&& plan) {
+    if (weigh) {
+        w.resize((size_t)N);
+        for (int s = 0; s < N; ++s) w[(size_t)s] = pops_of(s) + 1.0;
+        (void)pdmpc_set_step_weights(h, N, w.data());
+    }
+    if (optimizer == PDMPC_OPTIMIZER_SAMPLED)
+        if (const int rc = pdmpc_set_step_seeds(h, (int32_t)seeds.size(), seeds.data())) return cfail(nullptr, rc, pdmpc_last_error());
+    if (const int rc = plan()) return cfail(nullptr, rc, pdmpc_last_error());
+    double us[3] = {0, 0, 0};
+    if (pdmpc_last_call_timing(h, us) == PDMPC_OK)
+        for (int i = 0; i < 3; ++i) timing[1 + i] = us[i] * 1e-3;
+    return PDMPC_OK;
+}
+// n_steps closed-loop time steps in one call; ms[i] (may be NULL) receives the wall time of step i: build + pack + launch + fetch +
+// apply, everything a caller of the boundary pays per MPC step
+template <class Step>
+int timed_steps(int32_t n_steps, double* ms, Step&& step) {
+    for (int i = 0; i < n_steps; ++i) {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (const int rc = step()) return rc;
+        if (ms) ms[i] = ms_since(t0);
+    }
+    return PDMPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -949,24 +1028,12 @@ int pdmpc_controller_destroy(pdmpc_controller* c) {
     return PDMPC_OK;
 }
 
-// Everything one launch needs to plan the whole time step (controller.py: build_step_problem): vehicles in level order
-// (slot = position), per-slot predecessor slots, per-slot areas to publish on exhaustion.
-namespace {
-int assemble_step(pdmpc_controller* c, bool seq_given = false);
-}
-
 namespace {
 // RandStream('mt19937ar', Seed = time_step + vehicle_index) of every slot (MonteCarloTreeSearch.m:31-32; PrioritizedController.m:335-341
 // calls run_optimizer with obj.k, so every instance of a batch draws the same stream for the same vehicle)
 void set_seeds(pdmpc_controller* c, const std::vector<int32_t>& vehicle_of_slot) {
     c->seeds.resize(vehicle_of_slot.size());
     for (size_t s = 0; s < vehicle_of_slot.size(); ++s) c->seeds[s] = (uint32_t)(c->k + vehicle_of_slot[s] + 1);
-}
-// the seeds of the problem about to be planned, for the next pack (a sampled bank); nothing for the graph search
-int seeds_for_next_pack(pdmpc_controller* c) {
-    if (c->optimizer != PDMPC_OPTIMIZER_SAMPLED) return PDMPC_OK;
-    const int rc = pdmpc_set_step_seeds(c->h, (int32_t)c->seeds.size(), c->seeds.data());
-    return rc ? cfail(c, rc, pdmpc_last_error()) : PDMPC_OK;
 }
 
 // RandomPrioritizer.m:15-25 (prioritizer.random_priorities): a Fisher-Yates shuffle of 1 .. n on the mt19937ar doubles of the time step
@@ -978,62 +1045,9 @@ void random_priorities(int time_step, int n, std::vector<int32_t>& p) {
     }
 }
 
-// ---- the step-preparation calls: on the device with a handle, else the host twin
-int fca_collisions(pdmpc_controller* c, int32_t n_pairs, const pdmpc_polygon_set& obst) {
-    const pdmpc_controller_config& g = c->cfg;
-    if (c->h) {
-        const int rc = pdmpc_fca_collisions(c->h, c->n, c->Hp, c->fca_x.data(), c->fca_y.data(), c->fca_cos.data(), c->fca_sin.data(), n_pairs, c->fca_pairs.data(), &obst,
-                                            nullptr, g.vehicle_length, g.vehicle_width, g.offset, c->fca_count.data(), c->prio.data());
-        return rc ? cfail(c, rc, std::string("pdmpc_fca_collisions: ") + pdmpc_last_error()) : PDMPC_OK;
-    }
-    const int rc = pdmpc_fca_collisions_host(c->n, c->Hp, c->fca_x.data(), c->fca_y.data(), c->fca_cos.data(), c->fca_sin.data(), n_pairs, c->fca_pairs.data(), &obst,
-                                             nullptr, g.vehicle_length, g.vehicle_width, g.offset, c->fca_count.data(), c->prio.data());
-    return rc ? cfail(c, rc, "pdmpc_fca_collisions_host failed") : PDMPC_OK;
-}
-// (the status as it is: the caller tries again with more room after PDMPC_ERR_CAPACITY)
-int bound_sets(pdmpc_controller* c, const pdmpc_polygon_set& lan, int all_steps, int32_t cap, double* ox, double* oy) {
-    if (c->h)
-        return pdmpc_bound_reachable_sets(c->h, c->n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(), c->trims.data(), &lan, all_steps, cap,
-                                          c->bound_off.data(), ox, oy, nullptr);
-    const pdmpc_polygon_set local = view_polygons(c->reach_off, c->reach_x, c->reach_y);
-    return pdmpc_bound_reachable_sets_host((int32_t)c->trim_speed.size(), c->Hp, &local, c->n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(),
-                                           c->trims.data(), &lan, all_steps, cap, c->bound_off.data(), ox, oy, nullptr);
-}
-// on the bounded step-Hp sets (S sets per vehicle): on the device they are still there
-int couple_bounded_sets(pdmpc_controller* c, int S) {
-    const int n = c->n;
-    if (c->h) {
-        const int rc = pdmpc_bounded_set_coupling(c->h, c->adjacency.data(), nullptr);
-        return rc ? cfail(c, rc, std::string("pdmpc_bounded_set_coupling: ") + pdmpc_last_error()) : PDMPC_OK;
-    }
-    std::vector<int32_t> off((size_t)n + 1, 0);
-    std::vector<double> sx, sy;
-    for (int v = 0; v < n; ++v) {
-        const int o = v * S + S - 1, a = c->bound_off[o], m = c->bound_off[o + 1] - a;
-        sx.insert(sx.end(), c->bound_x.begin() + a, c->bound_x.begin() + a + m);
-        sy.insert(sy.end(), c->bound_y.begin() + a, c->bound_y.begin() + a + m);
-        off[v + 1] = off[v] + m;
-    }
-    const pdmpc_polygon_set ps = view_polygons(off, sx, sy);
-    const int rc = pdmpc_polygon_set_coupling_host(&ps, n, c->adjacency.data(), nullptr);
-    return rc ? cfail(c, rc, "pdmpc_polygon_set_coupling_host failed") : PDMPC_OK;
-}
-// ReachableSetCoupler.couple (ReachableSetCoupler.m:5-56)
-int couple_reachable_sets(pdmpc_controller* c) {
-    const int n = c->n;
-    if (c->h) {
-        const int rc = pdmpc_reachable_set_coupling(c->h, n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(), c->trims.data(), c->adjacency.data(), nullptr);
-        return rc ? cfail(c, rc, std::string("pdmpc_reachable_set_coupling: ") + pdmpc_last_error()) : PDMPC_OK;
-    }
-    const pdmpc_polygon_set ps = view_polygons(c->reach_off, c->reach_x, c->reach_y);
-    const int rc = pdmpc_reachable_set_coupling_host((int32_t)c->trim_speed.size(), c->Hp, &ps, n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(),
-                                                     c->trims.data(), c->adjacency.data(), nullptr);
-    return rc ? cfail(c, rc, "pdmpc_reachable_set_coupling_host failed") : PDMPC_OK;
-}
-
-// FcaPrioritizer.m:11-92 on the step's reference points and the scenario's obstacles
-// ... its two host halves, which the sweep runs per member around one device call for all FCA members: the reference points, their
-// headings and the coupled pairs in c->fca_*, and the counts and priorities taken over
+// FcaPrioritizer.m:11-92 on the step's reference points and the scenario's obstacles: the two per-member halves around the ONE
+// grouped assessment of all FCA members of a step preparation (prepare_members) -- the reference points, their headings and the
+// coupled pairs in c->fca_*, and the counts and priorities taken over
 int fca_inputs(pdmpc_controller* c) {
     const int n = c->n, Hp = c->Hp;
     if (Hp < 2) return cfail(c, PDMPC_ERR_INVALID, "FCA priorities need Hp >= 2 (calculate_yaw needs two reference points)");
@@ -1066,10 +1080,6 @@ int fca_inputs(pdmpc_controller* c) {
 void adopt_fca(pdmpc_controller* c, const int32_t* collisions, const int32_t* priorities) {
     std::copy(collisions, collisions + c->n, c->fca_count.begin());
     std::copy(priorities, priorities + c->n, c->prio.begin());
-}
-int fca_priorities(pdmpc_controller* c) {
-    if (const int rc = fca_inputs(c)) return rc;
-    return fca_collisions(c, (int32_t)(c->fca_pairs.size() / 2), view_polygons(c->fca_obst_off, c->fca_obst_x, c->fca_obst_y));
 }
 
 // ---- the stages of pdmpc_controller_build_step, in its order
@@ -1127,7 +1137,7 @@ void reachable_sets_at_poses(pdmpc_controller* c) {
 
 // lanelet bounding of those sets (bound_reachable_sets.m, HighLevelController.m:241-246): every step's sets when parallel
 // predecessors read them (all_steps), else step Hp only (the coupler's)
-// ... its two host halves, which the sweep runs per member around one device call for all members: the raw lanelet polygons in
+// ... its two per-member halves around the bounding call of a step preparation (prepare_members): the raw lanelet polygons in
 // c->lan_*, and the bounded sets in c->bound_* taken over as the parallel predecessors' obstacles
 void lanelet_polygons(pdmpc_controller* c) {
     const int n = c->n;
@@ -1157,29 +1167,13 @@ void adopt_bounded_sets(pdmpc_controller* c, bool all_steps) {
             }
     }
 }
-int bound_by_lanelets(pdmpc_controller* c, bool all_steps) {
-    const int n = c->n, Hp = c->Hp;
-    lanelet_polygons(c);
-    const pdmpc_polygon_set lan = view_polygons(c->lan_off, c->lan_x, c->lan_y);
-    c->bound_off.assign((size_t)n * (all_steps ? Hp : 1) + 1, 0);
-    int rc = bound_sets(c, lan, all_steps, (int32_t)c->bound_x.size(), c->bound_x.empty() ? nullptr : c->bound_x.data(), c->bound_y.empty() ? nullptr : c->bound_y.data());
-    if (rc == PDMPC_ERR_CAPACITY && c->bound_off.back() > (int32_t)c->bound_x.size()) {
-        c->bound_x.resize((size_t)c->bound_off.back());
-        c->bound_y.resize((size_t)c->bound_off.back());
-        rc = bound_sets(c, lan, all_steps, (int32_t)c->bound_x.size(), c->bound_x.data(), c->bound_y.data());
-    }
-    if (rc) return cfail(c, rc, std::string("pdmpc_bound_reachable_sets: ") + (c->h ? pdmpc_last_error() : "host twin failed"));
-    adopt_bounded_sets(c, all_steps);
-    return PDMPC_OK;
-}
 
-// c->adjacency by the configured rule (reachable sets: the bounded ones, bounded_S per vehicle, when the step bounded them)
-int couple(pdmpc_controller* c, int bounded_S, bool reachable_given = false) {
+// c->adjacency by the host rules: full and distance coupling (ReachableSetCoupler.m:5-56 is a call of the step preparation, which has
+// written the member's block into c->adjacency already)
+void couple(pdmpc_controller* c) {
     const int n = c->n;
-    // (reachable_given: the sweep's grouped call has written the member's block into c->adjacency already)
-    if (c->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET && reachable_given) return PDMPC_OK;
+    if (c->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET) return;
     c->adjacency.assign((size_t)n * n, 0);
-    if (c->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET) return bounded_S ? couple_bounded_sets(c, bounded_S) : couple_reachable_sets(c);
     if (c->cfg.coupling == PDMPC_COUPLING_FULL) {
         for (int a = 0; a < n; ++a)
             for (int b = 0; b < n; ++b) at(c->adjacency, n, a, b) = a != b;
@@ -1200,16 +1194,14 @@ int couple(pdmpc_controller* c, int bounded_S, bool reachable_given = false) {
             });
         }
     }
-    return PDMPC_OK;
 }
 
-// priorities -> c->directed
-// (fca_given: the sweep's grouped call has assessed the member already -- its counts and priorities, c->fca_* filled by fca_inputs)
-int direct_by_priorities(pdmpc_controller* c, const int32_t* fca_given_collisions = nullptr, const int32_t* fca_given_priorities = nullptr) {
+// priorities -> c->directed (FCA: the counts and priorities of the member's group in the step preparation's assessment)
+void direct_by_priorities(pdmpc_controller* c, const int32_t* fca_collisions, const int32_t* fca_priorities) {
     const int n = c->n;
     if (c->cfg.priority_strategy == PDMPC_PRIORITY_COLORING) {
         coloring_directed(c->adjacency, n, c->directed);
-        return PDMPC_OK;
+        return;
     }
     // constant priorities = vehicle index (ConstantPrioritizer.m:14-20); random and FCA priorities as below
     // (Prioritizer.directed_coupling_from_priorities, Prioritizer.m:64-77: keep i -> j iff priority(j) is not below priority(i))
@@ -1217,28 +1209,18 @@ int direct_by_priorities(pdmpc_controller* c, const int32_t* fca_given_collision
     for (int v = 0; v < n; ++v) c->prio[v] = v + 1;
     if (c->cfg.priority_strategy == PDMPC_PRIORITY_RANDOM) {
         random_priorities(c->k, n, c->prio);
-    } else if (c->cfg.priority_strategy == PDMPC_PRIORITY_FCA && fca_given_priorities) {
-        adopt_fca(c, fca_given_collisions, fca_given_priorities);
     } else if (c->cfg.priority_strategy == PDMPC_PRIORITY_FCA) {
-        const int rc = fca_priorities(c);
-        if (rc) return rc;
+        adopt_fca(c, fca_collisions, fca_priorities);
     }
     c->directed.assign((size_t)n * n, 0);
     for (int i = 0; i < n; ++i)
         for_each_set(c->adjacency.data() + (size_t)i * n, n, [&](int j) {
             if (!(c->prio[j] < c->prio[i])) at(c->directed, n, i, j) = 1;
         });
-    return PDMPC_OK;
 }
-}  // namespace
 
-namespace {
-// pdmpc_controller_build_step in three parts, so that a sweep can run the middle one -- the step preparation on the device -- once for
-// all its members: what the step reads of the reachable sets ...
-struct StepPrep {
-    bool reach_parallel = false, reach = false, bounded = false;
-};
-// ... everything before the step preparation (advances the time step),
+// A member's step in three parts around the step preparation, which runs once for all members that are built together: everything
+// before it (advances the time step; P: what the step reads of the reachable sets),
 int begin_step(pdmpc_controller* c, StepPrep& P) {
     const int n = c->n;
     const bool reach_parallel = c->parallel_mode == PDMPC_PARALLEL_REACHABLE_SETS;
@@ -1268,31 +1250,9 @@ int begin_step(pdmpc_controller* c, StepPrep& P) {
     P.bounded = bounded;
     return PDMPC_OK;
 }
-// ... and everything after it
-int finish_step(pdmpc_controller* c, const int32_t* fca_given_collisions = nullptr, const int32_t* fca_given_priorities = nullptr) {
-    int rc = direct_by_priorities(c, fca_given_collisions, fca_given_priorities);
-    if (!rc) rc = assemble_step(c);
-    if (rc) return rc;
-    set_seeds(c, c->order);
-    return PDMPC_OK;
-}
-}  // namespace
-
-int pdmpc_controller_build_step(pdmpc_controller* c) {
-    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
-    StepPrep P;
-    int rc = begin_step(c, P);
-    if (!rc && P.bounded) rc = bound_by_lanelets(c, P.reach_parallel);
-    if (!rc) rc = couple(c, P.bounded ? (P.reach_parallel ? c->Hp : 1) : 0);
-    if (!rc) rc = finish_step(c);
-    return rc;
-}
-
-
-namespace {
 // c->directed -> sequential couplings, levels, slot order and the per-slot inputs of pdmpc_plan_step (the arena is the caller's
 // to clear: the explorative step keeps several problems alive side by side)
-int assemble_step(pdmpc_controller* c, bool seq_given) {
+int assemble_step(pdmpc_controller* c, bool seq_given = false) {
     const int n = c->n, Hp = c->Hp;
     // (seq_given: c->directed_seq is the caller's -- the explorative step swaps single couplings of the base prioritization)
     // who a vehicle is coupled with, as lists: the loops below visit a vehicle's few couplings, not rows and columns of the matrices
@@ -1454,6 +1414,13 @@ int assemble_step(pdmpc_controller* c, bool seq_given) {
     c->pred_index.push_back(0);
     return PDMPC_OK;
 }
+// ... and everything after the step preparation
+int finish_step(pdmpc_controller* c, const int32_t* fca_collisions, const int32_t* fca_priorities) {
+    direct_by_priorities(c, fca_collisions, fca_priorities);
+    if (const int rc = assemble_step(c)) return rc;
+    set_seeds(c, c->order);
+    return PDMPC_OK;
+}
 }  // namespace
 
 // records of the step in slot order -> plans, exhaustion handling, fallbacks of coupled vehicles, plant update
@@ -1577,12 +1544,27 @@ int pdmpc_controller_apply(pdmpc_controller* c, const pdmpc_vehicle_out* recs) {
 
 // One pass of HighLevelController.main_control_loop (:334-373) in simulation: build, plan on the GPU (one launch), apply.
 namespace {
-// adds the parts of the step's one backend call (pdmpc_last_call_timing) to the controller's timing
-void add_call_timing(pdmpc_controller* c) {
-    double us[3] = {0, 0, 0};
-    if (pdmpc_last_call_timing(c->h, us) == PDMPC_OK)
-        for (int i = 0; i < 3; ++i) c->timing[1 + i] = us[i] * 1e-3;
+// a failure inside a step the controller takes alone is the controller's error too (the global message has it either way)
+int own(pdmpc_controller* c, int rc) {
+    if (rc) c->err = g_cerr;
+    return rc;
 }
+// the end of such a step: the records in c->out applied (timing[5]), and the step's parts added to the controller's sums
+int apply_and_account(pdmpc_controller* c) {
+    const auto t = std::chrono::steady_clock::now();
+    const int rc = pdmpc_controller_apply(c, c->out.data());
+    c->timing[5] = ms_since(t);
+    for (int i = 0; i < 6; ++i) c->timing_sum[i] += c->timing[i];
+    c->timing_steps += 1;
+    return rc;
+}
+// (nobody looks at the plans that were not chosen: the explorative and optimal-priority steps keep them all, their *_run loops do not)
+struct LeanRun {
+    pdmpc_controller* c;
+    bool was;
+    explicit LeanRun(pdmpc_controller* ctl) : c(ctl), was(ctl->lean_explore) { c->lean_explore = true; }
+    ~LeanRun() { c->lean_explore = was; }
+};
 }  // namespace
 
 int pdmpc_controller_last_timing(pdmpc_controller* c, double* ms6) {
@@ -1611,33 +1593,14 @@ int pdmpc_controller_step(pdmpc_controller* c) {
     c->timing[0] = ms_since(t);
     c->timing[4] = 0;
     c->out.resize(c->n);
-    if (c->last_pops.size() == (size_t)c->n) {  // the work of the last step as the expected work of this one: heavy searches are dispatched first
-        std::vector<double> w((size_t)c->n);
-        for (int s = 0; s < c->n; ++s) w[(size_t)s] = c->last_pops[(size_t)c->order[(size_t)s]] + 1.0;
-        (void)pdmpc_set_step_weights(c->h, c->n, w.data());
-    }
-    if ((rc = seeds_for_next_pack(c))) return rc;
-    rc = pdmpc_plan_step(c->h, c->n, c->in.data(), c->pred_offset.data(), c->pred_index.data(), c->fb.data(), c->out.data());
-    if (rc) return cfail(c, rc, pdmpc_last_error());
-    add_call_timing(c);
-    t = std::chrono::steady_clock::now();
-    rc = pdmpc_controller_apply(c, c->out.data());
-    c->timing[5] = ms_since(t);
-    for (int i = 0; i < 6; ++i) c->timing_sum[i] += c->timing[i];
-    c->timing_steps += 1;
-    return rc;
+    rc = plan_built(c->h, c->n, c->last_pops.size() == (size_t)c->n, c->weights, [&](int s) { return c->last_pops[(size_t)c->order[(size_t)s]]; }, c->optimizer, c->seeds,
+                    c->timing, [&] { return pdmpc_plan_step(c->h, c->n, c->in.data(), c->pred_offset.data(), c->pred_index.data(), c->fb.data(), c->out.data()); });
+    if (rc) return own(c, rc);
+    return apply_and_account(c);
 }
 
-// n_steps closed-loop time steps in one call; ms[i] (may be NULL) receives the wall time of step i: build + pack + launch +
-// fetch + apply, everything a caller of the boundary pays per MPC step
 int pdmpc_controller_run(pdmpc_controller* c, int32_t n_steps, double* ms) {
-    for (int i = 0; i < n_steps; ++i) {
-        const auto t0 = std::chrono::steady_clock::now();
-        const int rc = pdmpc_controller_step(c);
-        if (rc) return rc;
-        if (ms) ms[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return PDMPC_OK;
+    return timed_steps(n_steps, ms, [&] { return pdmpc_controller_step(c); });
 }
 
 int pdmpc_controller_problem(pdmpc_controller* c, int32_t* n, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index,
@@ -1806,18 +1769,8 @@ void flatten_instances(pdmpc_controller* c, int K) {
 }  // namespace
 
 namespace {
-int permute_instances(pdmpc_controller* c, int32_t n_perm, uint32_t seed);
-}
-int pdmpc_controller_explore_build(pdmpc_controller* c, int32_t n_perm, uint32_t seed) {
-    if (!c || n_perm < 1) return cfail(c, PDMPC_ERR_INVALID, "bad argument");
-    Exploring exploring(c);
-    int rc = pdmpc_controller_build_step(c);  // instance 0: the controller's own prioritization
-    if (rc) return rc;
-    return permute_instances(c, n_perm, seed);
-}
-namespace {
-// pdmpc_controller_explore_build behind its pdmpc_controller_build_step (a sweep runs that part for all its members at once, then this
-// one per member): the step just built is instance 0, instances 1 .. n_perm - 1 permute its computation levels
+// pdmpc_controller_explore_build behind its pdmpc_controller_build_step (build_members runs that part for all its members at once, then
+// this one per member): the step just built is instance 0, instances 1 .. n_perm - 1 permute its computation levels
 int permute_instances(pdmpc_controller* c, int32_t n_perm, uint32_t seed) {
     int rc = PDMPC_OK;
     const int n = c->n;
@@ -1861,6 +1814,293 @@ int permute_instances(pdmpc_controller* c, int32_t n_perm, uint32_t seed) {
 }
 }  // namespace
 
+// ---- ONE step preparation over a span of members: a sweep's members, or the one controller that steps alone
+namespace {
+// the poses of the members `who` one after the other (and their lanelet polygons: with_lanelets)
+void gather(pdmpc_controller* const* members, PrepScratch::Call& C, const std::vector<int>& who, bool with_lanelets) {
+    C.who = who;
+    C.group_offset.assign(1, 0);
+    C.x.clear();
+    C.y.clear();
+    C.cos_yaw.clear();
+    C.sin_yaw.clear();
+    C.trim.clear();
+    C.lan_off.assign(1, 0);
+    C.lan_x.clear();
+    C.lan_y.clear();
+    for (int m : who) {
+        pdmpc_controller* c = members[m];
+        C.x.insert(C.x.end(), c->mx.begin(), c->mx.end());
+        C.y.insert(C.y.end(), c->my.begin(), c->my.end());
+        C.cos_yaw.insert(C.cos_yaw.end(), c->reach_cos.begin(), c->reach_cos.end());
+        C.sin_yaw.insert(C.sin_yaw.end(), c->reach_sin.begin(), c->reach_sin.end());
+        C.trim.insert(C.trim.end(), c->trims.begin(), c->trims.end());
+        C.group_offset.push_back((int32_t)C.x.size());
+        if (with_lanelets) {
+            lanelet_polygons(c);
+            const int32_t base = (int32_t)C.lan_x.size(), nl = c->lan_off[(size_t)c->n];
+            C.lan_x.insert(C.lan_x.end(), c->lan_x.begin(), c->lan_x.begin() + nl);
+            C.lan_y.insert(C.lan_y.end(), c->lan_y.begin(), c->lan_y.begin() + nl);
+            for (int v = 0; v < c->n; ++v) C.lan_off.push_back(base + c->lan_off[(size_t)v + 1]);
+        }
+    }
+    C.lan_x.push_back(0.0);  // (never empty)
+    C.lan_y.push_back(0.0);
+    size_t entries = 0;
+    for (size_t g = 0; g + 1 < C.group_offset.size(); ++g) entries += (size_t)(C.group_offset[g + 1] - C.group_offset[g]) * (C.group_offset[g + 1] - C.group_offset[g]);
+    C.adjacency.assign(entries + 1, 0);
+}
+// the blocks of a grouped coupler call -> c->adjacency of the members that couple by reachable sets
+void scatter_blocks(pdmpc_controller* const* members, const PrepScratch::Call& C) {
+    size_t block = 0;
+    for (int m : C.who) {
+        pdmpc_controller* c = members[m];
+        const size_t nn = (size_t)c->n * c->n;
+        if (c->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET) c->adjacency.assign(C.adjacency.begin() + block, C.adjacency.begin() + block + nn);
+        block += nn;
+    }
+}
+bool any_couples_by_sets(pdmpc_controller* const* members, const std::vector<int>& who) {
+    for (int m : who)
+        if (members[m]->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET) return true;
+    return false;
+}
+
+// lanelet bounding of the members `who` (one all_steps for all of them) in ONE device call on the concatenated vehicles, then the
+// coupler on the bounded step-Hp sets (on the device they are still there), grouped by member
+int bound_on_device(pdmpc_handle* h, pdmpc_controller* const* members, PrepScratch& S, const std::vector<int>& who, bool all_steps) {
+    if (who.empty()) return PDMPC_OK;
+    PrepScratch::Call& C = S.call;
+    gather(members, C, who, true);
+    const int Hp = members[who[0]]->Hp, sets_each = all_steps ? Hp : 1, n = C.group_offset.back();
+    const pdmpc_polygon_set lan = view_polygons(C.lan_off, C.lan_x, C.lan_y);
+    C.set_off.assign((size_t)n * sets_each + 1, 0);
+    S.prep_calls[0] += 1;
+    int rc = bound_with_room(C.set_off, C.set_x, C.set_y, [&](int32_t cap, double* ox, double* oy) {
+        return pdmpc_bound_reachable_sets(h, n, C.x.data(), C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(), C.trim.data(), &lan, all_steps, cap, C.set_off.data(), ox, oy, nullptr);
+    });
+    if (rc) return cfail(nullptr, rc, std::string("pdmpc_bound_reachable_sets: ") + pdmpc_last_error());
+    for (size_t g = 0; g < who.size(); ++g) {  // every member's own sets, offsets from 0, as a bounding call for it alone leaves them
+        pdmpc_controller* c = members[who[g]];
+        const size_t o0 = (size_t)C.group_offset[g] * sets_each, sets = (size_t)c->n * sets_each;
+        const int32_t a = C.set_off[o0], total = C.set_off[o0 + sets] - a;
+        c->bound_off.resize(sets + 1);
+        for (size_t o = 0; o <= sets; ++o) c->bound_off[o] = C.set_off[o0 + o] - a;
+        if (c->bound_x.size() < (size_t)total) {
+            c->bound_x.resize((size_t)total);
+            c->bound_y.resize((size_t)total);
+        }
+        std::copy(C.set_x.begin() + a, C.set_x.begin() + a + total, c->bound_x.begin());
+        std::copy(C.set_y.begin() + a, C.set_y.begin() + a + total, c->bound_y.begin());
+        adopt_bounded_sets(c, all_steps);
+    }
+    if (!any_couples_by_sets(members, who)) return PDMPC_OK;
+    S.prep_calls[1] += 1;
+    rc = pdmpc_bounded_set_coupling_grouped(h, (int32_t)who.size(), C.group_offset.data(), C.adjacency.data(), nullptr);
+    if (rc) return cfail(nullptr, rc, std::string("pdmpc_bounded_set_coupling_grouped: ") + pdmpc_last_error());
+    scatter_blocks(members, C);
+    return PDMPC_OK;
+}
+// ... without a handle: every member's own bounding on the host twin (on its own table of local hulls), then the grouped host twin of
+// the coupler on the members' step-Hp sets
+int bound_on_host(pdmpc_controller* const* members, PrepScratch& S, const std::vector<int>& who) {
+    if (who.empty()) return PDMPC_OK;
+    PrepScratch::Call& C = S.call;
+    for (int m : who) {
+        pdmpc_controller* c = members[m];
+        const bool all_steps = S.prep[(size_t)m].reach_parallel;
+        lanelet_polygons(c);
+        const pdmpc_polygon_set lan = view_polygons(c->lan_off, c->lan_x, c->lan_y), local = view_polygons(c->reach_off, c->reach_x, c->reach_y);
+        c->bound_off.assign((size_t)c->n * (all_steps ? c->Hp : 1) + 1, 0);
+        S.prep_calls[0] += 1;
+        const int rc = bound_with_room(c->bound_off, c->bound_x, c->bound_y, [&](int32_t cap, double* ox, double* oy) {
+            return pdmpc_bound_reachable_sets_host((int32_t)c->trim_speed.size(), c->Hp, &local, c->n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(),
+                                                   c->trims.data(), &lan, all_steps, cap, c->bound_off.data(), ox, oy, nullptr);
+        });
+        if (rc) return cfail(c, rc, "pdmpc_bound_reachable_sets_host failed");
+        adopt_bounded_sets(c, all_steps);
+    }
+    if (!any_couples_by_sets(members, who)) return PDMPC_OK;
+    gather(members, C, who, false);
+    C.set_off.assign(1, 0);
+    C.set_x.clear();
+    C.set_y.clear();
+    for (int m : who) {
+        pdmpc_controller* c = members[m];
+        const int sets_each = S.prep[(size_t)m].reach_parallel ? c->Hp : 1;
+        for (int v = 0; v < c->n; ++v) {
+            const int o = v * sets_each + sets_each - 1, a = c->bound_off[o], cnt = c->bound_off[o + 1] - a;
+            C.set_x.insert(C.set_x.end(), c->bound_x.begin() + a, c->bound_x.begin() + a + cnt);
+            C.set_y.insert(C.set_y.end(), c->bound_y.begin() + a, c->bound_y.begin() + a + cnt);
+            C.set_off.push_back((int32_t)C.set_x.size());
+        }
+    }
+    C.set_x.push_back(0.0);
+    C.set_y.push_back(0.0);
+    const pdmpc_polygon_set ps = view_polygons(C.set_off, C.set_x, C.set_y);
+    S.prep_calls[1] += 1;
+    const int rc = pdmpc_polygon_set_coupling_grouped_host(&ps, (int32_t)who.size(), C.group_offset.data(), C.adjacency.data(), nullptr);
+    if (rc) return cfail(nullptr, rc, "pdmpc_polygon_set_coupling_grouped_host failed");
+    scatter_blocks(members, C);
+    return PDMPC_OK;
+}
+// the coupler on the unbounded step-Hp hulls of the members `who` (ReachableSetCoupler.m:5-56), grouped by member: with a handle the
+// members share its table of local hulls (as they share its automaton) ...
+int couple_hulls_on_device(pdmpc_handle* h, pdmpc_controller* const* members, PrepScratch& S, const std::vector<int>& who) {
+    if (who.empty()) return PDMPC_OK;
+    PrepScratch::Call& C = S.call;
+    gather(members, C, who, false);
+    S.prep_calls[2] += 1;
+    const int rc = pdmpc_reachable_set_coupling_grouped(h, (int32_t)who.size(), C.group_offset.data(), C.x.data(), C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(), C.trim.data(),
+                                                        C.adjacency.data(), nullptr);
+    if (rc) return cfail(nullptr, rc, std::string("pdmpc_reachable_set_coupling_grouped: ") + pdmpc_last_error());
+    scatter_blocks(members, C);
+    return PDMPC_OK;
+}
+// ... without one, members that hold the same table share a call of the grouped host twin
+int couple_hulls_on_host(pdmpc_controller* const* members, PrepScratch& S, const std::vector<int>& who) {
+    PrepScratch::Call& C = S.call;
+    std::vector<int> rest = who, same, other;
+    while (!rest.empty()) {
+        const pdmpc_controller* c0 = members[rest[0]];
+        same.clear();
+        other.clear();
+        for (int m : rest) {
+            const pdmpc_controller* c = members[m];
+            (c->reach_off == c0->reach_off && c->reach_x == c0->reach_x && c->reach_y == c0->reach_y ? same : other).push_back(m);
+        }
+        gather(members, C, same, false);
+        const pdmpc_polygon_set ps = view_polygons(c0->reach_off, c0->reach_x, c0->reach_y);
+        S.prep_calls[2] += 1;
+        const int rc = pdmpc_reachable_set_coupling_grouped_host((int32_t)c0->trim_speed.size(), c0->Hp, &ps, (int32_t)same.size(), C.group_offset.data(), C.x.data(),
+                                                                 C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(), C.trim.data(), C.adjacency.data(), nullptr);
+        if (rc) return cfail(nullptr, rc, "pdmpc_reachable_set_coupling_grouped_host failed");
+        scatter_blocks(members, C);
+        rest = other;
+    }
+    return PDMPC_OK;
+}
+
+// the inputs of the future collision assessment of the members `who` (their adjacency is there) as ONE grouped call takes them: every
+// member with its own coupled pairs, scenario obstacles and vehicle sizes, the reference points member after member
+int gather_fca(pdmpc_controller* const* members, PrepScratch::Fca& F, const std::vector<int>& who) {
+    F.groups.assign(who.size(), pdmpc_fca_group());
+    F.obstacles.resize(who.size());
+    F.x.clear();
+    F.y.clear();
+    F.cos_yaw.clear();
+    F.sin_yaw.clear();
+    size_t n = 0;
+    for (size_t g = 0; g < who.size(); ++g) {
+        pdmpc_controller* c = members[who[g]];
+        if (const int rc = fca_inputs(c)) return rc;
+        F.x.insert(F.x.end(), c->fca_x.begin(), c->fca_x.end());
+        F.y.insert(F.y.end(), c->fca_y.begin(), c->fca_y.end());
+        F.cos_yaw.insert(F.cos_yaw.end(), c->fca_cos.begin(), c->fca_cos.end());
+        F.sin_yaw.insert(F.sin_yaw.end(), c->fca_sin.begin(), c->fca_sin.end());
+        F.obstacles[g] = view_polygons(c->fca_obst_off, c->fca_obst_x, c->fca_obst_y);
+        pdmpc_fca_group& G = F.groups[g];
+        G.n = c->n;
+        G.n_pairs = (int32_t)(c->fca_pairs.size() / 2);
+        G.pairs = c->fca_pairs.data();
+        G.obstacles = &F.obstacles[g];
+        G.dynamic_rows = nullptr;
+        G.length = c->cfg.vehicle_length;
+        G.width = c->cfg.vehicle_width;
+        G.offset = c->cfg.offset;
+        n += (size_t)c->n;
+    }
+    F.collisions.assign(n, 0);
+    F.priorities.assign(n, 0);
+    return PDMPC_OK;
+}
+
+// The step problems of M members (of one Hp, all on the handle h or all without one), built with ONE step preparation for all of them:
+// with a handle the grouped device calls, without one the host twins.  This is the only place that asks which.  n_perm > 0: every
+// member's explorative batch of n_perm prioritizations behind its step (pdmpc_controller_explore_build's statements, in its order).
+int build_members(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, int n_perm, PrepScratch& S) {
+    struct ExploringAll {  // (the members' memos of the obstacle sets are on while their prioritizations are assembled)
+        pdmpc_controller* const* members;
+        size_t M;
+        bool on;
+        ExploringAll(pdmpc_controller* const* ms, size_t n, bool o) : members(ms), M(n), on(o) { set(on); }
+        ~ExploringAll() { set(false); }
+        void set(bool v) {
+            for (size_t m = 0; on && m < M; ++m) members[m]->exploring = v;
+        }
+    } exploring(members, M, n_perm > 0);
+    S.prep.assign(M, StepPrep());
+    std::fill(S.prep_calls, S.prep_calls + 4, 0);
+    for (size_t m = 0; m < M; ++m)
+        if (const int rc = begin_step(members[m], S.prep[m])) return rc;
+    // who takes part in which grouped call: bounded (step Hp only / every step: one bounding call each) or the plain hulls
+    std::vector<int> bounded_last, bounded_all, hulls;
+    for (size_t m = 0; m < M; ++m) {
+        const StepPrep& P = S.prep[m];
+        if (P.bounded)
+            (P.reach_parallel ? bounded_all : bounded_last).push_back((int)m);
+        else if (members[m]->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET)
+            hulls.push_back((int)m);
+    }
+    int rc = PDMPC_OK;
+    if (h) {
+        rc = bound_on_device(h, members, S, bounded_last, false);
+        if (!rc) rc = bound_on_device(h, members, S, bounded_all, true);
+        if (!rc) rc = couple_hulls_on_device(h, members, S, hulls);
+    } else {
+        bounded_last.insert(bounded_last.end(), bounded_all.begin(), bounded_all.end());
+        std::sort(bounded_last.begin(), bounded_last.end());
+        rc = bound_on_host(members, S, bounded_last);
+        if (!rc) rc = couple_hulls_on_host(members, S, hulls);
+    }
+    if (rc) return rc;
+    std::vector<int> assessed;  // the members with FCA priorities: assessed together once every member's adjacency is there
+    for (size_t m = 0; m < M; ++m) {
+        couple(members[m]);
+        if (members[m]->cfg.priority_strategy == PDMPC_PRIORITY_FCA) assessed.push_back((int)m);
+    }
+    PrepScratch::Fca& F = S.fca;
+    if (!assessed.empty()) {
+        if ((rc = gather_fca(members, F, assessed))) return rc;
+        const int Hp = members[0]->Hp;
+        S.prep_calls[3] += 1;
+        rc = h ? pdmpc_fca_collisions_grouped(h, (int32_t)F.groups.size(), F.groups.data(), Hp, F.x.data(), F.y.data(), F.cos_yaw.data(), F.sin_yaw.data(), F.collisions.data(),
+                                              F.priorities.data())
+               : pdmpc_fca_collisions_grouped_host((int32_t)F.groups.size(), F.groups.data(), Hp, F.x.data(), F.y.data(), F.cos_yaw.data(), F.sin_yaw.data(), F.collisions.data(),
+                                                   F.priorities.data());
+        if (rc) return cfail(nullptr, rc, h ? std::string("pdmpc_fca_collisions_grouped: ") + pdmpc_last_error() : "pdmpc_fca_collisions_grouped_host failed");
+    }
+    for (size_t m = 0, g = 0, v0 = 0; m < M; ++m) {
+        pdmpc_controller* c = members[m];
+        const bool fca = g < assessed.size() && assessed[g] == (int)m;
+        rc = finish_step(c, fca ? F.collisions.data() + v0 : nullptr, fca ? F.priorities.data() + v0 : nullptr);
+        if (fca) {
+            v0 += (size_t)c->n;
+            ++g;
+        }
+        if (!rc && n_perm > 0) rc = permute_instances(c, n_perm, (uint32_t)c->k);  // RandStream("mt19937ar", Seed = obj.k) (:249)
+        if (rc) return rc;
+    }
+    return PDMPC_OK;
+}
+}  // namespace
+
+// Everything one launch needs to plan the whole time step (controller.py: build_step_problem): vehicles in level order
+// (slot = position), per-slot predecessor slots, per-slot areas to publish on exhaustion.  A step alone is a sweep of one member.
+int pdmpc_controller_build_step(pdmpc_controller* c) {
+    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
+    const int rc = build_members(c->h, &c, 1, 0, c->prep);
+    if (rc) c->err = g_cerr;
+    return rc;
+}
+
+int pdmpc_controller_explore_build(pdmpc_controller* c, int32_t n_perm, uint32_t seed) {
+    if (!c || n_perm < 1) return cfail(c, PDMPC_ERR_INVALID, "bad argument");
+    Exploring exploring(c);
+    int rc = pdmpc_controller_build_step(c);  // instance 0: the controller's own prioritization
+    if (rc) return rc;
+    return permute_instances(c, n_perm, seed);
+}
 int pdmpc_controller_explore_problem(pdmpc_controller* c, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index,
                                      const pdmpc_polygon_set** fallback, const int32_t** instance, const int32_t** vehicle, const int32_t** level) {
     if (!c || c->x_in.empty()) return cfail(c, PDMPC_ERR_INVALID, "no exploration batch has been built");
@@ -1994,14 +2234,13 @@ namespace {
 int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, bool follow_own, const BatchChoice& how) {
     c->timing[0] = ms_since(t);
     const int N = (int)c->x_in.size();
-    c->x_out.resize((size_t)N);
-    if (c->last_pops.size() == (size_t)c->n) {
-        std::vector<double> w((size_t)N);
-        for (int i = 0; i < N; ++i) w[(size_t)i] = c->last_pops[(size_t)c->x_vehicle[(size_t)i]] + 1.0;
-        (void)pdmpc_set_step_weights(c->h, N, w.data());
-    }
-    int rc = seeds_for_next_pack(c);
-    if (rc) return rc;
+    auto plan = [&](auto&& call) {
+        const int rc = plan_built(c->h, N, c->last_pops.size() == (size_t)c->n, c->weights, [&](int s) { return c->last_pops[(size_t)c->x_vehicle[(size_t)s]]; }, c->optimizer,
+                                  c->seeds, c->timing, call);
+        t = std::chrono::steady_clock::now();
+        return own(c, rc);
+    };
+    int rc = PDMPC_OK;
     if (c->lean_explore && c->device_choice) {
         // the closed loop keeps the chosen plans only, and the choice and their gather run on the device directly behind the search: ONE
         // call and one read-back (the chosen records, the choice and the cost table)
@@ -2013,11 +2252,11 @@ int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, boo
         c->choice_cost.resize((size_t)D.n_cells());
         c->out.resize((size_t)c->n);
         const pdmpc_choice ch = D.view();
-        rc = pdmpc_plan_step_chosen(c->h, N, c->x_in.data(), c->x_pred_offset.data(), c->x_pred_index.data(), c->x_fb.data(), &ch, c->choice_chosen.data(),
-                                    c->choice_cost.data(), c->out.data());
-        if (rc) return cfail(c, rc, pdmpc_last_error());
-        add_call_timing(c);
-        t = std::chrono::steady_clock::now();
+        rc = plan([&] {
+            return pdmpc_plan_step_chosen(c->h, N, c->x_in.data(), c->x_pred_offset.data(), c->x_pred_index.data(), c->x_fb.data(), &ch, c->choice_chosen.data(),
+                                          c->choice_cost.data(), c->out.data());
+        });
+        if (rc) return rc;
         how.adopt(c, D, c->choice_chosen.data(), c->choice_cost.data());
     } else if (c->lean_explore) {
         // the closed loop keeps the chosen plans only (obj.iter = obj.iter_array_tmp{chosen_solution}, :157-158): status and final
@@ -2025,10 +2264,10 @@ int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, boo
         c->x_out.clear();
         c->x_status.resize((size_t)N);
         c->x_final_cost.resize((size_t)N);
-        rc = pdmpc_plan_step_lean(c->h, N, c->x_in.data(), c->x_pred_offset.data(), c->x_pred_index.data(), c->x_fb.data(), c->x_status.data(), c->x_final_cost.data());
-        if (rc) return cfail(c, rc, pdmpc_last_error());
-        add_call_timing(c);
-        t = std::chrono::steady_clock::now();
+        rc = plan([&] {
+            return pdmpc_plan_step_lean(c->h, N, c->x_in.data(), c->x_pred_offset.data(), c->x_pred_index.data(), c->x_fb.data(), c->x_status.data(), c->x_final_cost.data());
+        });
+        if (rc) return rc;
         rc = choose_on_host(c, how, c->x_status.data(), c->x_final_cost.data());
         if (rc) return rc;
         std::vector<int32_t> want((size_t)c->n);
@@ -2040,10 +2279,9 @@ int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, boo
         rc = pdmpc_fetch_records_at(c->h, c->n, want.data(), c->out.data());
         if (rc) return cfail(c, rc, pdmpc_last_error());
     } else {
-        rc = pdmpc_plan_step(c->h, N, c->x_in.data(), c->x_pred_offset.data(), c->x_pred_index.data(), c->x_fb.data(), c->x_out.data());
-        if (rc) return cfail(c, rc, pdmpc_last_error());
-        add_call_timing(c);
-        t = std::chrono::steady_clock::now();
+        c->x_out.resize((size_t)N);
+        rc = plan([&] { return pdmpc_plan_step(c->h, N, c->x_in.data(), c->x_pred_offset.data(), c->x_pred_index.data(), c->x_fb.data(), c->x_out.data()); });
+        if (rc) return rc;
         c->x_status.resize((size_t)N);
         c->x_final_cost.resize((size_t)N);
         for (int s = 0; s < N; ++s) {
@@ -2062,13 +2300,8 @@ int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, boo
         c->directed = c->inst[0].directed;
         c->directed_seq = c->inst[0].directed_seq;
     }
-    c->timing[4] = ms_since(t);
-    t = std::chrono::steady_clock::now();
-    rc = pdmpc_controller_apply(c, c->out.data());
-    c->timing[5] = ms_since(t);
-    for (int i = 0; i < 6; ++i) c->timing_sum[i] += c->timing[i];
-    c->timing_steps += 1;
-    return rc;
+    c->timing[4] = ms_since(t);  // (from the backend call's return on)
+    return apply_and_account(c);
 }
 }  // namespace
 
@@ -2095,19 +2328,8 @@ int pdmpc_controller_explore_follow_own(pdmpc_controller* c, int32_t on) {
 
 int pdmpc_controller_explore_run(pdmpc_controller* c, int32_t n_perm, int32_t n_steps, double* ms) {
     if (!c) return cfail(c, PDMPC_ERR_INVALID, "null argument");
-    struct Lean {  // (nobody looks at the plans that were not chosen: pdmpc_controller_explore_step keeps them all, this loop does not)
-        pdmpc_controller* c;
-        bool was;
-        ~Lean() { c->lean_explore = was; }
-    } lean{c, c->lean_explore};
-    c->lean_explore = true;
-    for (int i = 0; i < n_steps; ++i) {
-        const auto t0 = std::chrono::steady_clock::now();
-        const int rc = pdmpc_controller_explore_step(c, n_perm);
-        if (rc) return rc;
-        if (ms) ms[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return PDMPC_OK;
+    LeanRun lean(c);
+    return timed_steps(n_steps, ms, [&] { return pdmpc_controller_explore_step(c, n_perm); });
 }
 
 int pdmpc_controller_explore_result(pdmpc_controller* c, int32_t* chosen, int32_t* n_graphs, const double** cost, const pdmpc_vehicle_out** records) {
@@ -2280,19 +2502,8 @@ int pdmpc_controller_optimal_step(pdmpc_controller* c, int32_t max_instances) {
 
 int pdmpc_controller_optimal_run(pdmpc_controller* c, int32_t max_instances, int32_t n_steps, double* ms) {
     if (!c) return cfail(c, PDMPC_ERR_INVALID, "null argument");
-    struct Lean {  // (nobody looks at the plans that were not chosen)
-        pdmpc_controller* c;
-        bool was;
-        ~Lean() { c->lean_explore = was; }
-    } lean{c, c->lean_explore};
-    c->lean_explore = true;
-    for (int i = 0; i < n_steps; ++i) {
-        const auto t0 = std::chrono::steady_clock::now();
-        const int rc = pdmpc_controller_optimal_step(c, max_instances);
-        if (rc) return rc;
-        if (ms) ms[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return PDMPC_OK;
+    LeanRun lean(c);
+    return timed_steps(n_steps, ms, [&] { return pdmpc_controller_optimal_step(c, max_instances); });
 }
 
 int pdmpc_controller_optimal_result(pdmpc_controller* c, int32_t* chosen, int32_t* n_instances, const double** cost, const pdmpc_vehicle_out** records) {
@@ -2317,8 +2528,7 @@ struct pdmpc_sweep {
     bool broken = false;         // a step failed half way: the members have advanced unevenly
     bool built = false;
     double timing[6] = {0, 0, 0, 0, 0, 0};
-    int32_t prep_calls[4] = {0, 0, 0, 0};  // of the last build: lanelet bounding, bounded coupling, hull coupling, collision assessment
-    std::vector<StepPrep> prep;
+    PrepScratch prep;  // of the members' ONE step preparation (its prep_calls: pdmpc_sweep_last_prep_calls)
     // the concatenated problem
     std::vector<pdmpc_vehicle_in> in;
     std::vector<pdmpc_polygon_set> fb;
@@ -2341,296 +2551,14 @@ struct pdmpc_sweep {
         std::vector<double> cell_cost;
         std::vector<pdmpc_vehicle_out> picks;                     // member after member, each in its own slot order
     } x;
-    // one grouped step-preparation call: the vehicles of the members that take part, member after member
-    struct Call {
-        std::vector<int> who;                // members
-        std::vector<int32_t> group_offset;   // [who.size() + 1]
-        std::vector<double> x, y, cos_yaw, sin_yaw;
-        std::vector<int32_t> trim, lan_off, set_off;
-        std::vector<double> lan_x, lan_y, set_x, set_y;
-        std::vector<uint8_t> adjacency;      // the blocks
-    } call;
-    // the grouped collision assessment: the FCA members' reference points, member after member, and what it returns
-    struct Fca {
-        std::vector<pdmpc_fca_group> groups;
-        std::vector<pdmpc_polygon_set> obstacles;  // [groups.size()] views of the members' scenario obstacles
-        std::vector<double> x, y, cos_yaw, sin_yaw;
-        std::vector<int32_t> collisions, priorities;
-    } fca;
 };
 
 namespace {
 int N_of(const pdmpc_sweep* s) { return s->first.back(); }
 
-// the poses of the members `who` one after the other (and their lanelet polygons: with_lanelets)
-void gather(pdmpc_sweep* s, const std::vector<int>& who, bool with_lanelets) {
-    pdmpc_sweep::Call& C = s->call;
-    C.who = who;
-    C.group_offset.assign(1, 0);
-    C.x.clear();
-    C.y.clear();
-    C.cos_yaw.clear();
-    C.sin_yaw.clear();
-    C.trim.clear();
-    C.lan_off.assign(1, 0);
-    C.lan_x.clear();
-    C.lan_y.clear();
-    for (int m : who) {
-        pdmpc_controller* c = s->members[(size_t)m];
-        C.x.insert(C.x.end(), c->mx.begin(), c->mx.end());
-        C.y.insert(C.y.end(), c->my.begin(), c->my.end());
-        C.cos_yaw.insert(C.cos_yaw.end(), c->reach_cos.begin(), c->reach_cos.end());
-        C.sin_yaw.insert(C.sin_yaw.end(), c->reach_sin.begin(), c->reach_sin.end());
-        C.trim.insert(C.trim.end(), c->trims.begin(), c->trims.end());
-        C.group_offset.push_back((int32_t)C.x.size());
-        if (with_lanelets) {
-            lanelet_polygons(c);
-            const int32_t base = (int32_t)C.lan_x.size(), nl = c->lan_off[(size_t)c->n];
-            C.lan_x.insert(C.lan_x.end(), c->lan_x.begin(), c->lan_x.begin() + nl);
-            C.lan_y.insert(C.lan_y.end(), c->lan_y.begin(), c->lan_y.begin() + nl);
-            for (int v = 0; v < c->n; ++v) C.lan_off.push_back(base + c->lan_off[(size_t)v + 1]);
-        }
-    }
-    C.lan_x.push_back(0.0);  // (never empty)
-    C.lan_y.push_back(0.0);
-    size_t entries = 0;
-    for (size_t g = 0; g + 1 < C.group_offset.size(); ++g) entries += (size_t)(C.group_offset[g + 1] - C.group_offset[g]) * (C.group_offset[g + 1] - C.group_offset[g]);
-    C.adjacency.assign(entries + 1, 0);
-}
-// the blocks of a grouped coupler call -> c->adjacency of the members that couple by reachable sets
-void scatter_blocks(pdmpc_sweep* s) {
-    const pdmpc_sweep::Call& C = s->call;
-    size_t block = 0;
-    for (int m : C.who) {
-        pdmpc_controller* c = s->members[(size_t)m];
-        const size_t nn = (size_t)c->n * c->n;
-        if (c->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET) c->adjacency.assign(C.adjacency.begin() + block, C.adjacency.begin() + block + nn);
-        block += nn;
-    }
-}
-bool any_couples_by_sets(const pdmpc_sweep* s, const std::vector<int>& who) {
-    for (int m : who)
-        if (s->members[(size_t)m]->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET) return true;
-    return false;
-}
-
-// lanelet bounding of the members `who` (one all_steps for all of them) in ONE device call on the concatenated vehicles, then the
-// coupler on the bounded step-Hp sets, grouped by member
-int sweep_bound_on_device(pdmpc_sweep* s, const std::vector<int>& who, bool all_steps) {
-    if (who.empty()) return PDMPC_OK;
-    pdmpc_sweep::Call& C = s->call;
-    gather(s, who, true);
-    const int Hp = s->members[0]->Hp, S = all_steps ? Hp : 1, n = C.group_offset.back();
-    const pdmpc_polygon_set lan = view_polygons(C.lan_off, C.lan_x, C.lan_y);
-    C.set_off.assign((size_t)n * S + 1, 0);
-    auto bound = [&]() {
-        return pdmpc_bound_reachable_sets(s->h, n, C.x.data(), C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(), C.trim.data(), &lan, all_steps, (int32_t)C.set_x.size(),
-                                          C.set_off.data(), C.set_x.empty() ? nullptr : C.set_x.data(), C.set_y.empty() ? nullptr : C.set_y.data(), nullptr);
-    };
-    s->prep_calls[0] += 1;
-    int rc = bound();
-    if (rc == PDMPC_ERR_CAPACITY && C.set_off.back() > (int32_t)C.set_x.size()) {
-        C.set_x.resize((size_t)C.set_off.back());
-        C.set_y.resize((size_t)C.set_off.back());
-        rc = bound();
-    }
-    if (rc) return cfail(nullptr, rc, std::string("pdmpc_bound_reachable_sets: ") + pdmpc_last_error());
-    for (size_t g = 0; g < who.size(); ++g) {  // every member's own sets, offsets from 0, as its own bounding call leaves them
-        pdmpc_controller* c = s->members[(size_t)who[g]];
-        const size_t o0 = (size_t)C.group_offset[g] * S, sets = (size_t)c->n * S;
-        const int32_t a = C.set_off[o0], total = C.set_off[o0 + sets] - a;
-        c->bound_off.resize(sets + 1);
-        for (size_t o = 0; o <= sets; ++o) c->bound_off[o] = C.set_off[o0 + o] - a;
-        if (c->bound_x.size() < (size_t)total) {
-            c->bound_x.resize((size_t)total);
-            c->bound_y.resize((size_t)total);
-        }
-        std::copy(C.set_x.begin() + a, C.set_x.begin() + a + total, c->bound_x.begin());
-        std::copy(C.set_y.begin() + a, C.set_y.begin() + a + total, c->bound_y.begin());
-        adopt_bounded_sets(c, all_steps);
-    }
-    if (!any_couples_by_sets(s, who)) return PDMPC_OK;
-    s->prep_calls[1] += 1;
-    rc = pdmpc_bounded_set_coupling_grouped(s->h, (int32_t)who.size(), C.group_offset.data(), C.adjacency.data(), nullptr);
-    if (rc) return cfail(nullptr, rc, std::string("pdmpc_bounded_set_coupling_grouped: ") + pdmpc_last_error());
-    scatter_blocks(s);
-    return PDMPC_OK;
-}
-// ... without a handle: every member's own bounding on the host twin, then the grouped host twin on the members' step-Hp sets
-int sweep_bound_on_host(pdmpc_sweep* s, const std::vector<int>& who) {
-    if (who.empty()) return PDMPC_OK;
-    pdmpc_sweep::Call& C = s->call;
-    for (int m : who) {
-        pdmpc_controller* c = s->members[(size_t)m];
-        s->prep_calls[0] += 1;
-        if (const int rc = bound_by_lanelets(c, s->prep[(size_t)m].reach_parallel)) return rc;
-    }
-    if (!any_couples_by_sets(s, who)) return PDMPC_OK;
-    gather(s, who, false);
-    C.set_off.assign(1, 0);
-    C.set_x.clear();
-    C.set_y.clear();
-    for (int m : who) {
-        pdmpc_controller* c = s->members[(size_t)m];
-        const int S = s->prep[(size_t)m].reach_parallel ? c->Hp : 1;
-        for (int v = 0; v < c->n; ++v) {
-            const int o = v * S + S - 1, a = c->bound_off[o], cnt = c->bound_off[o + 1] - a;
-            C.set_x.insert(C.set_x.end(), c->bound_x.begin() + a, c->bound_x.begin() + a + cnt);
-            C.set_y.insert(C.set_y.end(), c->bound_y.begin() + a, c->bound_y.begin() + a + cnt);
-            C.set_off.push_back((int32_t)C.set_x.size());
-        }
-    }
-    C.set_x.push_back(0.0);
-    C.set_y.push_back(0.0);
-    const pdmpc_polygon_set ps = view_polygons(C.set_off, C.set_x, C.set_y);
-    s->prep_calls[1] += 1;
-    const int rc = pdmpc_polygon_set_coupling_grouped_host(&ps, (int32_t)who.size(), C.group_offset.data(), C.adjacency.data(), nullptr);
-    if (rc) return cfail(nullptr, rc, "pdmpc_polygon_set_coupling_grouped_host failed");
-    scatter_blocks(s);
-    return PDMPC_OK;
-}
-// the coupler on the unbounded step-Hp hulls of the members `who`, grouped by member.  With a handle the members share its table of
-// local hulls (as they share its automaton); without one, members that hold the same table share a call of the grouped host twin.
-int sweep_couple_hulls(pdmpc_sweep* s, const std::vector<int>& who) {
-    if (who.empty()) return PDMPC_OK;
-    pdmpc_sweep::Call& C = s->call;
-    if (s->h) {
-        gather(s, who, false);
-        s->prep_calls[2] += 1;
-        const int rc = pdmpc_reachable_set_coupling_grouped(s->h, (int32_t)who.size(), C.group_offset.data(), C.x.data(), C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(),
-                                                            C.trim.data(), C.adjacency.data(), nullptr);
-        if (rc) return cfail(nullptr, rc, std::string("pdmpc_reachable_set_coupling_grouped: ") + pdmpc_last_error());
-        scatter_blocks(s);
-        return PDMPC_OK;
-    }
-    std::vector<int> rest = who, same, other;
-    while (!rest.empty()) {
-        const pdmpc_controller* c0 = s->members[(size_t)rest[0]];
-        same.clear();
-        other.clear();
-        for (int m : rest) {
-            const pdmpc_controller* c = s->members[(size_t)m];
-            (c->reach_off == c0->reach_off && c->reach_x == c0->reach_x && c->reach_y == c0->reach_y ? same : other).push_back(m);
-        }
-        gather(s, same, false);
-        const pdmpc_polygon_set ps = view_polygons(c0->reach_off, c0->reach_x, c0->reach_y);
-        s->prep_calls[2] += 1;
-        const int rc = pdmpc_reachable_set_coupling_grouped_host((int32_t)c0->trim_speed.size(), c0->Hp, &ps, (int32_t)same.size(), C.group_offset.data(), C.x.data(),
-                                                                 C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(), C.trim.data(), C.adjacency.data(), nullptr);
-        if (rc) return cfail(nullptr, rc, "pdmpc_reachable_set_coupling_grouped_host failed");
-        scatter_blocks(s);
-        rest = other;
-    }
-    return PDMPC_OK;
-}
-
-// future collision assessment of the members `who` (their adjacency is there) in ONE grouped call, every member with its own coupled
-// pairs, scenario obstacles and vehicle sizes; the counts and priorities then stand in s->fca, member after member
-int sweep_assess_collisions(pdmpc_sweep* s, const std::vector<int>& who) {
-    if (who.empty()) return PDMPC_OK;
-    pdmpc_sweep::Fca& F = s->fca;
-    F.groups.assign(who.size(), pdmpc_fca_group());
-    F.obstacles.resize(who.size());
-    F.x.clear();
-    F.y.clear();
-    F.cos_yaw.clear();
-    F.sin_yaw.clear();
-    for (size_t g = 0; g < who.size(); ++g) {
-        pdmpc_controller* c = s->members[(size_t)who[g]];
-        if (const int rc = fca_inputs(c)) return rc;
-        F.x.insert(F.x.end(), c->fca_x.begin(), c->fca_x.end());
-        F.y.insert(F.y.end(), c->fca_y.begin(), c->fca_y.end());
-        F.cos_yaw.insert(F.cos_yaw.end(), c->fca_cos.begin(), c->fca_cos.end());
-        F.sin_yaw.insert(F.sin_yaw.end(), c->fca_sin.begin(), c->fca_sin.end());
-        F.obstacles[g] = view_polygons(c->fca_obst_off, c->fca_obst_x, c->fca_obst_y);
-        pdmpc_fca_group& G = F.groups[g];
-        G.n = c->n;
-        G.n_pairs = (int32_t)(c->fca_pairs.size() / 2);
-        G.pairs = c->fca_pairs.data();
-        G.obstacles = &F.obstacles[g];
-        G.dynamic_rows = nullptr;
-        G.length = c->cfg.vehicle_length;
-        G.width = c->cfg.vehicle_width;
-        G.offset = c->cfg.offset;
-    }
-    const size_t n = F.x.size() / (size_t)s->members[0]->Hp;
-    F.collisions.assign(n, 0);
-    F.priorities.assign(n, 0);
-    s->prep_calls[3] += 1;
-    if (s->h) {
-        const int rc = pdmpc_fca_collisions_grouped(s->h, (int32_t)who.size(), F.groups.data(), s->members[0]->Hp, F.x.data(), F.y.data(), F.cos_yaw.data(),
-                                                    F.sin_yaw.data(), F.collisions.data(), F.priorities.data());
-        return rc ? cfail(nullptr, rc, std::string("pdmpc_fca_collisions_grouped: ") + pdmpc_last_error()) : PDMPC_OK;
-    }
-    const int rc = pdmpc_fca_collisions_grouped_host((int32_t)who.size(), F.groups.data(), s->members[0]->Hp, F.x.data(), F.y.data(), F.cos_yaw.data(), F.sin_yaw.data(),
-                                                     F.collisions.data(), F.priorities.data());
-    return rc ? cfail(nullptr, rc, "pdmpc_fca_collisions_grouped_host failed") : PDMPC_OK;
-}
-
-// every member's step problem, built with ONE step preparation for all of them; n_perm > 0: every member's explorative batch of n_perm
-// prioritizations behind it (pdmpc_controller_explore_build's statements, in its order, per member)
-int sweep_build_members(pdmpc_sweep* s, int n_perm) {
-    const size_t M = s->members.size();
-    struct ExploringAll {  // (the members' memos of the obstacle sets are on while their prioritizations are assembled)
-        pdmpc_sweep* s;
-        bool on;
-        ExploringAll(pdmpc_sweep* sw, bool o) : s(sw), on(o) { set(on); }
-        ~ExploringAll() { set(false); }
-        void set(bool v) {
-            if (on)
-                for (pdmpc_controller* c : s->members) c->exploring = v;
-        }
-    } exploring(s, n_perm > 0);
-    s->prep.assign(M, StepPrep());
-    std::fill(s->prep_calls, s->prep_calls + 4, 0);
-    for (size_t m = 0; m < M; ++m)
-        if (const int rc = begin_step(s->members[m], s->prep[m])) return rc;
-    // who takes part in which grouped call: bounded (step Hp only / every step: one bounding call each) or the plain hulls
-    std::vector<int> bounded_last, bounded_all, hulls;
-    for (size_t m = 0; m < M; ++m) {
-        const StepPrep& P = s->prep[m];
-        if (P.bounded)
-            (P.reach_parallel ? bounded_all : bounded_last).push_back((int)m);
-        else if (s->members[m]->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET)
-            hulls.push_back((int)m);
-    }
-    int rc = PDMPC_OK;
-    if (s->h) {
-        rc = sweep_bound_on_device(s, bounded_last, false);
-        if (!rc) rc = sweep_bound_on_device(s, bounded_all, true);
-    } else {
-        bounded_last.insert(bounded_last.end(), bounded_all.begin(), bounded_all.end());
-        std::sort(bounded_last.begin(), bounded_last.end());
-        rc = sweep_bound_on_host(s, bounded_last);
-    }
-    if (!rc) rc = sweep_couple_hulls(s, hulls);
-    if (rc) return rc;
-    std::vector<int> assessed;  // the members with FCA priorities: assessed together once every member's adjacency is there
-    for (size_t m = 0; m < M; ++m) {
-        pdmpc_controller* c = s->members[m];
-        const StepPrep& P = s->prep[m];
-        if (const int rc1 = couple(c, P.bounded ? (P.reach_parallel ? c->Hp : 1) : 0, true)) return rc1;
-        if (c->cfg.priority_strategy == PDMPC_PRIORITY_FCA) assessed.push_back((int)m);
-    }
-    if (const int rc1 = sweep_assess_collisions(s, assessed)) return rc1;
-    for (size_t m = 0, g = 0, v0 = 0; m < M; ++m) {
-        pdmpc_controller* c = s->members[m];
-        if (g < assessed.size() && assessed[g] == (int)m) {
-            rc = finish_step(c, s->fca.collisions.data() + v0, s->fca.priorities.data() + v0);
-            v0 += (size_t)c->n;
-            ++g;
-        } else {
-            rc = finish_step(c);
-        }
-        if (!rc && n_perm > 0) rc = permute_instances(c, n_perm, (uint32_t)c->k);  // RandStream("mt19937ar", Seed = obj.k) (:249)
-        if (rc) return rc;
-    }
-    return PDMPC_OK;
-}
-
 int sweep_build(pdmpc_sweep* s) {
-    if (const int rc = sweep_build_members(s, 0)) return rc;
     const size_t M = s->members.size();
+    if (const int rc = build_members(s->h, s->members.data(), M, 0, s->prep)) return rc;
     // the concatenated problem: shallow copies, predecessor slots shifted by the member's first slot
     const int N = N_of(s);
     s->in.resize((size_t)N);
@@ -2699,8 +2627,8 @@ int explore_refusal(pdmpc_sweep* s, int32_t n_perm, bool needs_handle) {
 int sweep_explore_build(pdmpc_sweep* s, int n_perm) {
     pdmpc_sweep::Batch& X = s->x;
     X.n_perm = 0;
-    if (const int rc = sweep_build_members(s, n_perm)) return rc;
     const size_t M = s->members.size();
+    if (const int rc = build_members(s->h, s->members.data(), M, n_perm, s->prep)) return rc;
     X.first.assign(1, 0);
     for (size_t m = 0; m < M; ++m) X.first.push_back(X.first.back() + (int32_t)s->members[m]->x_in.size());
     const int N = X.first.back();
@@ -2864,23 +2792,14 @@ int pdmpc_sweep_step(pdmpc_sweep* s) {
     s->timing[4] = 0;
     const int N = N_of(s);
     s->out.resize((size_t)N);
-    // the work of the last step as the expected work of this one, as pdmpc_controller_step hands it over (a member's first step: 1 each)
-    s->weights.assign((size_t)N, 1.0);
-    for (size_t m = 0; m < s->members.size(); ++m) {
-        const pdmpc_controller* c = s->members[m];
-        if (c->last_pops.size() != (size_t)c->n) continue;
-        for (int q = 0; q < c->n; ++q) s->weights[(size_t)s->first[m] + q] = c->last_pops[(size_t)c->order[(size_t)q]] + 1.0;
-    }
-    (void)pdmpc_set_step_weights(s->h, N, s->weights.data());
-    if (s->members[0]->optimizer == PDMPC_OPTIMIZER_SAMPLED) {
-        rc = pdmpc_set_step_seeds(s->h, N, s->seeds.data());
-        if (rc) return sweep_guard(s, cfail(nullptr, rc, pdmpc_last_error()));
-    }
-    rc = pdmpc_plan_step(s->h, N, s->in.data(), s->pred_offset.data(), s->pred_index.data(), s->fb.data(), s->out.data());
-    if (rc) return sweep_guard(s, cfail(nullptr, rc, pdmpc_last_error()));
-    double us[3] = {0, 0, 0};
-    if (pdmpc_last_call_timing(s->h, us) == PDMPC_OK)
-        for (int i = 0; i < 3; ++i) s->timing[1 + i] = us[i] * 1e-3;
+    // (the work of the last step as pdmpc_controller_step hands it over; a member's first step: 1 for each of its slots)
+    auto pops_of = [&](int q) {
+        const pdmpc_controller* c = s->members[(size_t)s->member[(size_t)q]];
+        return c->last_pops.size() == (size_t)c->n ? c->last_pops[(size_t)c->order[(size_t)s->member_slot[(size_t)q]]] : 0.0;
+    };
+    rc = plan_built(s->h, N, true, s->weights, pops_of, s->members[0]->optimizer, s->seeds, s->timing,
+                    [&] { return pdmpc_plan_step(s->h, N, s->in.data(), s->pred_offset.data(), s->pred_index.data(), s->fb.data(), s->out.data()); });
+    if (rc) return sweep_guard(s, rc);
     t = std::chrono::steady_clock::now();
     rc = sweep_apply(s, s->out.data(), true);
     s->timing[5] = ms_since(t);
@@ -2888,13 +2807,7 @@ int pdmpc_sweep_step(pdmpc_sweep* s) {
 }
 
 int pdmpc_sweep_run(pdmpc_sweep* s, int32_t n_steps, double* ms) {
-    for (int i = 0; i < n_steps; ++i) {
-        const auto t0 = std::chrono::steady_clock::now();
-        const int rc = pdmpc_sweep_step(s);
-        if (rc) return rc;
-        if (ms) ms[i] = ms_since(t0);
-    }
-    return PDMPC_OK;
+    return timed_steps(n_steps, ms, [&] { return pdmpc_sweep_step(s); });
 }
 
 int pdmpc_sweep_last_timing(pdmpc_sweep* s, double* ms6) {
@@ -2905,7 +2818,7 @@ int pdmpc_sweep_last_timing(pdmpc_sweep* s, double* ms6) {
 
 int pdmpc_sweep_last_prep_calls(pdmpc_sweep* s, int32_t* calls4) {
     if (!s || !calls4) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
-    std::copy(s->prep_calls, s->prep_calls + 4, calls4);
+    std::copy(s->prep.prep_calls, s->prep.prep_calls + 4, calls4);
     return PDMPC_OK;
 }
 
@@ -2946,25 +2859,17 @@ int pdmpc_sweep_explore_step(pdmpc_sweep* s, int32_t n_perm) {
     s->timing[0] = ms_since(t);
     const int N = X.first.back();
     const size_t M = s->members.size();
-    // the work of the last step as the expected work of this one, as the members' own explorative steps hand it over
-    X.weights.assign((size_t)N, 1.0);
-    for (size_t m = 0; m < M; ++m) {
-        const pdmpc_controller* c = s->members[m];
-        if (c->last_pops.size() != (size_t)c->n) continue;
-        for (int q = X.first[m]; q < X.first[m + 1]; ++q) X.weights[(size_t)q] = c->last_pops[(size_t)X.vehicle[(size_t)q]] + 1.0;
-    }
-    (void)pdmpc_set_step_weights(s->h, N, X.weights.data());
-    if (s->members[0]->optimizer == PDMPC_OPTIMIZER_SAMPLED) {
-        rc = pdmpc_set_step_seeds(s->h, N, X.seeds.data());
-        if (rc) return sweep_guard(s, cfail(nullptr, rc, pdmpc_last_error()));
-    }
+    // (the work of the last step as the members' own explorative steps hand it over)
+    auto pops_of = [&](int q) {
+        const pdmpc_controller* c = s->members[(size_t)X.member[(size_t)q]];
+        return c->last_pops.size() == (size_t)c->n ? c->last_pops[(size_t)X.vehicle[(size_t)q]] : 0.0;
+    };
     concatenate_choices(s);
     const pdmpc_choice ch = X.all.view();
-    rc = pdmpc_plan_step_chosen(s->h, N, X.in.data(), X.pred_offset.data(), X.pred_index.data(), X.fb.data(), &ch, X.chosen.data(), X.cell_cost.data(), X.picks.data());
-    if (rc) return sweep_guard(s, cfail(nullptr, rc, pdmpc_last_error()));
-    double us[3] = {0, 0, 0};
-    if (pdmpc_last_call_timing(s->h, us) == PDMPC_OK)
-        for (int i = 0; i < 3; ++i) s->timing[1 + i] = us[i] * 1e-3;
+    rc = plan_built(s->h, N, true, X.weights, pops_of, s->members[0]->optimizer, X.seeds, s->timing, [&] {
+        return pdmpc_plan_step_chosen(s->h, N, X.in.data(), X.pred_offset.data(), X.pred_index.data(), X.fb.data(), &ch, X.chosen.data(), X.cell_cost.data(), X.picks.data());
+    });
+    if (rc) return sweep_guard(s, rc);
     t = std::chrono::steady_clock::now();
     for (size_t m = 0; m < M; ++m) {  // every member adopts its part: as its own step that keeps the chosen plans only leaves it
         pdmpc_controller* c = s->members[m];
@@ -2980,13 +2885,7 @@ int pdmpc_sweep_explore_step(pdmpc_sweep* s, int32_t n_perm) {
 }
 
 int pdmpc_sweep_explore_run(pdmpc_sweep* s, int32_t n_perm, int32_t n_steps, double* ms) {
-    for (int i = 0; i < n_steps; ++i) {
-        const auto t0 = std::chrono::steady_clock::now();
-        const int rc = pdmpc_sweep_explore_step(s, n_perm);
-        if (rc) return rc;
-        if (ms) ms[i] = ms_since(t0);
-    }
-    return PDMPC_OK;
+    return timed_steps(n_steps, ms, [&] { return pdmpc_sweep_explore_step(s, n_perm); });
 }
 
 }  // extern "C"

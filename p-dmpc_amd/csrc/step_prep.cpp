@@ -434,29 +434,12 @@ int pdmpc_bound_reachable_sets(pdmpc_handle* h, int32_t n, const double* x, cons
     return PDMPC_OK;
 }
 
-int pdmpc_bounded_set_coupling(pdmpc_handle* h, uint8_t* adjacency, double* area) {
-    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
-    if (!adjacency) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling: null adjacency");
+namespace {
+// pdmpc_bounded_set_coupling (one group over the bounded vehicles, the ungrouped launcher) and its grouped sibling behind their argument
+// checks: the groups cover the B.n vehicles of the last bounding call, whose sets are still on the device
+int bounded_coupling(pdmpc_handle* h, int32_t n_groups, const int32_t* group_offset, int (*launch)(const BoundArgs*, void*), uint8_t* adjacency, double* area) {
     BoundState& B = h->bound;
-    if (!B.valid) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling without a successful pdmpc_bound_reachable_sets");
     const int n = B.n;
-    if (n == 0) return PDMPC_OK;
-    ON_DEVICE(h->cfg.device);
-    const BoundArgs A = bound_args(h, n, B.S, B.n_lan);
-    HIPCHK(hipMemsetAsync(A.n_pairs, 0, sizeof(int32_t), h->stream));
-    if (const int rc = timed_launch(h, B.coupling, pdmpc_launch_bounded_coupling, A, "bounded-set coupling")) return rc;
-    return fetch_pair_out(h, B.coupling, B.out.p, B.h_out.p, bound_layout(n, B.n_lan).out, (size_t)n * n, adjacency, area);
-}
-
-int pdmpc_bounded_set_coupling_grouped(pdmpc_handle* h, int32_t n_groups, const int32_t* group_offset, uint8_t* adjacency, double* area) {
-    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
-    if (!adjacency) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling_grouped: null adjacency");
-    BoundState& B = h->bound;
-    if (!B.valid) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling_grouped without a successful pdmpc_bound_reachable_sets");
-    int n = 0;
-    if (const int rc = check_groups("pdmpc_bounded_set_coupling_grouped", n_groups, group_offset, &n)) return rc;
-    if (n > h->max_vehicles) return fail(PDMPC_ERR_CAPACITY, "pdmpc_bounded_set_coupling_grouped: more vehicles than config.max_vehicles");
-    if (n != B.n) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling_grouped: the groups do not cover the vehicles of the last pdmpc_bound_reachable_sets");
     if (n == 0) return PDMPC_OK;
     ON_DEVICE(h->cfg.device);
     const BoundLayout L = bound_layout(n, B.n_lan);
@@ -464,8 +447,28 @@ int pdmpc_bounded_set_coupling_grouped(pdmpc_handle* h, int32_t n_groups, const 
     const size_t entries = stage_groups((PairGroup*)(B.h_in.p + L.group), n_groups, group_offset, &A.max_group);
     HIPCHK(hipMemcpyAsync(B.in.p + L.group, B.h_in.p + L.group, (size_t)n * sizeof(PairGroup), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(A.n_pairs, 0, sizeof(int32_t), h->stream));
-    if (const int rc = timed_launch(h, B.coupling, pdmpc_launch_bounded_coupling_grouped, A, "bounded-set coupling")) return rc;
+    if (const int rc = timed_launch(h, B.coupling, launch, A, "bounded-set coupling")) return rc;
     return fetch_pair_out(h, B.coupling, B.out.p, B.h_out.p, L.out, entries, adjacency, area);
+}
+}  // namespace
+
+int pdmpc_bounded_set_coupling(pdmpc_handle* h, uint8_t* adjacency, double* area) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    if (!adjacency) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling: null adjacency");
+    if (!h->bound.valid) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling without a successful pdmpc_bound_reachable_sets");
+    const int32_t all[2] = {0, h->bound.n};
+    return bounded_coupling(h, 1, all, pdmpc_launch_bounded_coupling, adjacency, area);
+}
+
+int pdmpc_bounded_set_coupling_grouped(pdmpc_handle* h, int32_t n_groups, const int32_t* group_offset, uint8_t* adjacency, double* area) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    if (!adjacency) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling_grouped: null adjacency");
+    if (!h->bound.valid) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling_grouped without a successful pdmpc_bound_reachable_sets");
+    int n = 0;
+    if (const int rc = check_groups("pdmpc_bounded_set_coupling_grouped", n_groups, group_offset, &n)) return rc;
+    if (n > h->max_vehicles) return fail(PDMPC_ERR_CAPACITY, "pdmpc_bounded_set_coupling_grouped: more vehicles than config.max_vehicles");
+    if (n != h->bound.n) return fail(PDMPC_ERR_INVALID, "pdmpc_bounded_set_coupling_grouped: the groups do not cover the vehicles of the last pdmpc_bound_reachable_sets");
+    return bounded_coupling(h, n_groups, group_offset, pdmpc_launch_bounded_coupling_grouped, adjacency, area);
 }
 
 int pdmpc_bounded_reachable_kernel_ms(pdmpc_handle* h, double* ms2) {
@@ -476,92 +479,13 @@ int pdmpc_bounded_reachable_kernel_ms(pdmpc_handle* h, double* ms2) {
 }
 
 // ---- future collision assessment on the device (fca_kernel.hip)
-int pdmpc_fca_collisions(pdmpc_handle* h, int32_t n, int32_t Hp, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw,
-                         int32_t n_pairs, const int32_t* pairs, const pdmpc_polygon_set* obstacles, const pdmpc_polygon_set* dynamic_rows, double length,
-                         double width, double offset, int32_t* collisions, int32_t* priorities) {
-    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
-    const char* why = nullptr;
-    if (const int rc = pdmpc_fca_check_args(n, Hp, x, y, cos_yaw, sin_yaw, n_pairs, pairs, obstacles, dynamic_rows, collisions, priorities, &why))
-        return fail(rc, std::string("pdmpc_fca_collisions: ") + why);
-    const int m = n * Hp;
-    const int S = obstacles ? obstacles->n_polygons : 0, D = dynamic_rows ? dynamic_rows->n_polygons : 0, R = D / Hp;
-    const int s0 = S ? obstacles->offset[0] : 0, Ns = S ? obstacles->offset[S] - s0 : 0;
-    const int d0 = D ? dynamic_rows->offset[0] : 0, Nd = D ? dynamic_rows->offset[D] - d0 : 0;
-    // FcaState::ws and its pinned staging of the inputs, the block's first in_bytes (static and dynamic polygons: x of all their
-    // vertices, then y; their offsets rebased to 0); footprints and counts are on the device only
-    Carver c;
-    const size_t o_in = c.take<double>((size_t)4 * m);
-    const size_t o_stat = c.take<double>((size_t)2 * Ns);
-    const size_t o_dyn = c.take<double>((size_t)2 * Nd);
-    const size_t o_pairs = c.take<int32_t>((size_t)2 * n_pairs);
-    const size_t o_stat_off = c.take<int32_t>((size_t)S + 1);
-    const size_t o_dyn_off = c.take<int32_t>((size_t)D + 1);
-    const size_t in_bytes = c.end8();
-    const size_t o_fp = c.take<double>((size_t)8 * m);
-    const size_t o_counts = c.take<int32_t>((size_t)n);
-    const size_t total = c.at;
-    ON_DEVICE(h->cfg.device);
-    FcaState& F = h->fca;
-    if (F.ws.ensure(total) || F.h_in.ensure(in_bytes) || F.h_out.ensure((size_t)n)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the collision assessment");
-    unsigned char *hin = F.h_in.p, *ws = F.ws.p;
-    stage_poses((double*)(hin + o_in), (size_t)m, x, y, cos_yaw, sin_yaw);
-    double *hs = (double*)(hin + o_stat), *hdyn = (double*)(hin + o_dyn);
-    if (Ns) {
-        std::memcpy(hs, obstacles->x + s0, (size_t)Ns * sizeof(double));
-        std::memcpy(hs + Ns, obstacles->y + s0, (size_t)Ns * sizeof(double));
-    }
-    if (Nd) {
-        std::memcpy(hdyn, dynamic_rows->x + d0, (size_t)Nd * sizeof(double));
-        std::memcpy(hdyn + Nd, dynamic_rows->y + d0, (size_t)Nd * sizeof(double));
-    }
-    if (n_pairs) std::memcpy(hin + o_pairs, pairs, (size_t)2 * n_pairs * sizeof(int32_t));
-    int32_t* soff = (int32_t*)(hin + o_stat_off);
-    int32_t* doff = (int32_t*)(hin + o_dyn_off);
-    for (int p = 0; p <= S; ++p) soff[p] = S ? obstacles->offset[p] - s0 : 0;
-    for (int p = 0; p <= D; ++p) doff[p] = D ? dynamic_rows->offset[p] - d0 : 0;
-    FcaArgs A;
-    A.n = n;
-    A.Hp = Hp;
-    A.n_pairs = n_pairs;
-    A.n_static = S;
-    A.n_rows = R;
-    A.length = length;
-    A.width = width;
-    A.offset = offset;
-    A.n_pair_items = (int64_t)n_pairs * Hp;
-    A.n_static_items = (int64_t)(n - 1) * Hp * S;
-    A.n_items = A.n_pair_items + A.n_static_items + (int64_t)(n - 1) * Hp * R;
-    A.in = (const double*)(ws + o_in);
-    A.static_x = (const double*)(ws + o_stat);
-    A.static_y = A.static_x + Ns;
-    A.dyn_x = (const double*)(ws + o_dyn);
-    A.dyn_y = A.dyn_x + Nd;
-    A.pairs = (const int32_t*)(ws + o_pairs);
-    A.static_off = (const int32_t*)(ws + o_stat_off);
-    A.dyn_off = (const int32_t*)(ws + o_dyn_off);
-    A.fp = (double*)(ws + o_fp);
-    A.counts = (int32_t*)(ws + o_counts);
-    HIPCHK(hipMemcpyAsync(ws, hin, in_bytes, hipMemcpyHostToDevice, h->stream));
-    if (const int rc = timed_launch(h, F.timed, pdmpc_launch_fca, A, "collision assessment")) return rc;
-    HIPCHK(hipMemcpyAsync(F.h_out.p, ws + o_counts, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(sync_stream(h));
-    F.timed.fold();
-    std::memcpy(collisions, F.h_out.p, (size_t)n * sizeof(int32_t));
-    pdmpc_fca_sort_index(n, collisions, priorities);
-    return PDMPC_OK;
-}
-
-// ... for several independent sets of vehicles in one call: the groups' reference points as they come, their polygons
-// one group after the other, their pairs rebased to the concatenated vehicles, and the tables the kernels locate an item's group with
-int pdmpc_fca_collisions_grouped(pdmpc_handle* h, int32_t n_groups, const pdmpc_fca_group* groups, int32_t Hp, const double* x, const double* y,
-                                 const double* cos_yaw, const double* sin_yaw, int32_t* collisions, int32_t* priorities) {
-    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
-    char why[160];
-    int32_t n = 0;
-    if (const int rc = pdmpc_fca_check_groups(n_groups, groups, Hp, x, y, cos_yaw, sin_yaw, collisions, priorities, &n, why, (int32_t)sizeof why))
-        return fail(rc, std::string("pdmpc_fca_collisions_grouped: ") + why);
-    if (n > h->max_vehicles) return fail(PDMPC_ERR_CAPACITY, "pdmpc_fca_collisions_grouped: more vehicles than config.max_vehicles");
-    if (n == 0) return PDMPC_OK;
+namespace {
+// pdmpc_fca_collisions (one group, the ungrouped kernel) and pdmpc_fca_collisions_grouped behind their argument
+// checks, for n > 0 vehicles in all: the groups' reference points as they come, their polygons one group after the other, their pairs
+// rebased to the concatenated vehicles, and the tables the grouped kernels locate an item's group with.  The ungrouped kernel reads
+// the same arrays and none of the tables: with one group every offset of its own layout is the one staged here.
+int fca_assess(pdmpc_handle* h, const char* who, bool grouped, int32_t n_groups, const pdmpc_fca_group* groups, int32_t n, int32_t Hp, const double* x,
+               const double* y, const double* cos_yaw, const double* sin_yaw, int32_t* collisions, int32_t* priorities) {
     const int m = n * Hp;
     // what a group brings: S static polygons of Ns vertices from vertex s0 on, D = R Hp dynamic ones of Nd vertices from d0 on
     struct Sizes {
@@ -587,8 +511,9 @@ int pdmpc_fca_collisions_grouped(pdmpc_handle* h, int32_t n_groups, const pdmpc_
         n_pairs += groups[g].n ? groups[g].n_pairs : 0;
     }
     if (S > INT32_MAX || D > INT32_MAX || Ns > INT32_MAX || Nd > INT32_MAX || n_pairs > INT32_MAX)
-        return fail(PDMPC_ERR_CAPACITY, "pdmpc_fca_collisions_grouped: more than 2^31 polygons, vertices or pairs");
-    // FcaState::ws and its pinned staging of the inputs, the block's first in_bytes, as for the ungrouped call; then the group tables
+        return fail(PDMPC_ERR_CAPACITY, std::string(who) + ": more than 2^31 polygons, vertices or pairs");
+    // FcaState::ws and its pinned staging of the inputs, the block's first in_bytes (static and dynamic polygons: x of all their
+    // vertices, then y; their offsets rebased to 0), the group tables among them; footprints and counts are on the device only
     Carver c;
     const size_t o_in = c.take<double>((size_t)4 * m);
     const size_t o_stat = c.take<double>((size_t)2 * Ns);
@@ -669,8 +594,17 @@ int pdmpc_fca_collisions_grouped(pdmpc_handle* h, int32_t n_groups, const pdmpc_
     B.g.vehicle_group = (const int32_t*)(ws + o_vehicle_group);
     B.g.static_first = (const int64_t*)(ws + o_stat_first);
     B.g.dyn_first = (const int64_t*)(ws + o_dyn_first);
+    if (!grouped) {  // (what the ungrouped kernel reads in place of the group table)
+        A.n_static = hg[0].n_static;
+        A.n_rows = hg[0].n_rows;
+        A.length = hg[0].length;
+        A.width = hg[0].width;
+        A.offset = hg[0].offset;
+    }
     HIPCHK(hipMemcpyAsync(ws, hin, in_bytes, hipMemcpyHostToDevice, h->stream));
-    if (const int rc = timed_launch(h, F.timed, pdmpc_launch_fca_grouped, B, "collision assessment")) return rc;
+    if (const int rc = grouped ? timed_launch(h, F.timed, pdmpc_launch_fca_grouped, B, "collision assessment")
+                               : timed_launch(h, F.timed, pdmpc_launch_fca, A, "collision assessment"))
+        return rc;
     HIPCHK(hipMemcpyAsync(F.h_out.p, ws + o_counts, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(sync_stream(h));
     F.timed.fold();
@@ -681,6 +615,31 @@ int pdmpc_fca_collisions_grouped(pdmpc_handle* h, int32_t n_groups, const pdmpc_
         v0 += groups[g].n;
     }
     return PDMPC_OK;
+}
+
+}  // namespace
+
+int pdmpc_fca_collisions(pdmpc_handle* h, int32_t n, int32_t Hp, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw,
+                         int32_t n_pairs, const int32_t* pairs, const pdmpc_polygon_set* obstacles, const pdmpc_polygon_set* dynamic_rows, double length,
+                         double width, double offset, int32_t* collisions, int32_t* priorities) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    const char* why = nullptr;
+    if (const int rc = pdmpc_fca_check_args(n, Hp, x, y, cos_yaw, sin_yaw, n_pairs, pairs, obstacles, dynamic_rows, collisions, priorities, &why))
+        return fail(rc, std::string("pdmpc_fca_collisions: ") + why);
+    const pdmpc_fca_group all = {n, n_pairs, pairs, obstacles, dynamic_rows, length, width, offset};
+    return fca_assess(h, "pdmpc_fca_collisions", false, 1, &all, n, Hp, x, y, cos_yaw, sin_yaw, collisions, priorities);
+}
+
+int pdmpc_fca_collisions_grouped(pdmpc_handle* h, int32_t n_groups, const pdmpc_fca_group* groups, int32_t Hp, const double* x, const double* y,
+                                 const double* cos_yaw, const double* sin_yaw, int32_t* collisions, int32_t* priorities) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    char why[160];
+    int32_t n = 0;
+    if (const int rc = pdmpc_fca_check_groups(n_groups, groups, Hp, x, y, cos_yaw, sin_yaw, collisions, priorities, &n, why, (int32_t)sizeof why))
+        return fail(rc, std::string("pdmpc_fca_collisions_grouped: ") + why);
+    if (n > h->max_vehicles) return fail(PDMPC_ERR_CAPACITY, "pdmpc_fca_collisions_grouped: more vehicles than config.max_vehicles");
+    if (n == 0) return PDMPC_OK;
+    return fca_assess(h, "pdmpc_fca_collisions_grouped", true, n_groups, groups, n, Hp, x, y, cos_yaw, sin_yaw, collisions, priorities);
 }
 
 int pdmpc_fca_kernel_ms(pdmpc_handle* h, double* ms) {

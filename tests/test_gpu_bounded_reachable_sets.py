@@ -78,6 +78,17 @@ def test_device_equals_host_twin_for_every_batch_shape(Hp):
                 t_bound, t_couple = h.bounded_reachable_kernel_ms()
                 assert t_bound > 0.0 and (n < 2 or t_couple > 0.0)
         assert coupled > 0
+        # a small ungrouped coupler call directly behind a larger grouped one (both stage through one body): nothing of the larger
+        # call's group table is read
+        x, y, yaw, trim, lan = _batch(rng, polys, 65, mpa.n_trims)
+        h.bound_reachable_sets(x, y, yaw, trim, lan, 0)
+        assert sum(int(adj.sum()) for adj, _ in h.bounded_set_coupling_grouped([1, 0, 40, 24])) > 0
+        for n in (3, 1):
+            h.bound_reachable_sets(x[:n], y[:n], yaw[:n], trim[:n], lan[:n], 0)
+            host, _ = bound_reachable_sets_call(L, x[:n], y[:n], yaw[:n], trim[:n], lan[:n], 0)
+            adj_d, area_d = h.bounded_set_coupling()
+            adj_h, area_h = polygon_set_coupling_call([s[-1] for s in host])
+            assert np.array_equal(adj_d, adj_h) and np.array_equal(_bits(area_d), _bits(area_h)), n
     finally:
         h.close()
 

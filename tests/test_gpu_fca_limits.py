@@ -143,7 +143,67 @@ def test_one_vehicle_launches_no_items_and_clears_the_counts(handle):
     two = C.abutting_grid((-1.0, 0.0), side=2)
     two.refs, two.pairs, two.headings = two.refs[:2], C.full(2), tuple(h[:2] for h in two.headings)
     two.expected = [two.Hp, two.Hp]
-    exact(handle, two)
+    exact(handle, two)  # (two vehicles: no static polygon, no dynamic row)
+    none = C.abutting_grid((1.0, 0.0), side=1)  # one vehicle and nothing else: no pair, no obstacle item
+    assert none.expected == [0] and not none.obstacles and not len(none.pairs)
+    exact(handle, none)
+    exact(handle, _three_with_one_polygon_and_one_row())
+
+
+def _three_with_one_polygon_and_one_row():
+    """three standing vehicles 4 apart at Hp 2, ONE static polygon (under vehicle 0: a hit at both steps) and ONE dynamic row (under
+    vehicle 1 at step 0, far away at step 1); vehicle 2, the last, has no obstacle item: the smallest call with an entry in every list"""
+    refs = [np.tile([[4.0 * v, 0.0]], (2, 1)) for v in range(3)]
+    row = [C.box(3.75, -0.125, 4.25, 0.125), C.box(100.0, 100.0, 101.0, 101.0)]
+    return C.Case("one polygon, one row", refs, C.full(3), C.turned(3, 2, (1.0, 0.0)), [C.box(-0.25, -0.125, 0.25, 0.125)], [row], expected=[2, 1, 0])
+
+
+def _as_group(case):
+    return dict(reference_points=case.refs, pairs=case.pairs, length=case.sizes[0], width=case.sizes[1], offset=case.sizes[2], obstacles=case.obstacles,
+                dynamic_obstacle_area=case.dynamic, headings=case.headings)
+
+
+def test_polygon_sets_that_do_not_start_at_vertex_zero(handle):
+    """pdmpc_fca_collisions on polygon sets whose offset[0] is 3: the three vertices in front belong to no polygon (they lie where they
+    would turn every count if the call read its polygons from vertex 0 on)"""
+    import ctypes
+
+    from pdmpc import abi
+    from pdmpc.backend import fca_pack, load_library
+
+    case = _three_with_one_polygon_and_one_row()
+    args, (coll, prio), keep = fca_pack(case.refs, case.pairs, *case.sizes, case.obstacles, case.dynamic, headings=case.headings)
+    arrays = []
+
+    def behind_three_vertices(ps):
+        n, tot = ps.n_polygons, ps.offset[ps.n_polygons]
+        off = np.array([ps.offset[p] + 3 for p in range(n + 1)], dtype=np.int32)
+        x = np.array([1e3, 1e3 + 1, 1e3] + [ps.x[i] for i in range(tot)])
+        y = np.array([1e3, 1e3, 1e3 + 1] + [ps.y[i] for i in range(tot)])
+        arrays.extend([off, x, y])
+        return abi.PolygonSet(n_polygons=n, offset=off.ctypes.data_as(abi.c_int32_p), x=x.ctypes.data_as(abi.c_double_p), y=y.ctypes.data_as(abi.c_double_p))
+
+    obst, dyn = behind_three_vertices(keep.refs[-2]), behind_three_vertices(keep.refs[-1])
+    args[8], args[9] = ctypes.byref(obst), ctypes.byref(dyn)
+    L = load_library()
+    assert L.pdmpc_fca_collisions(handle.h, *args) == 0
+    assert coll.tolist() == case.expected and prio.tolist() == [1, 2, 3]
+    coll[:] = -1
+    assert L.pdmpc_fca_collisions_host(*args) == 0
+    assert coll.tolist() == case.expected
+
+
+def test_small_ungrouped_call_directly_behind_a_larger_grouped_one(handle):
+    """both entry points stage through one body: what the grouped call left in the staging block and in the group tables -- three
+    groups, 29 vehicles, polygons and rows -- is not read by the ungrouped calls behind it"""
+    big = [C.abutting_grid((1.0, 0.0), Hp=5), C.dynamic_rows(), C.abutting_grid((0.0, 1.0), Hp=5, side=3)]
+    got = handle.fca_collisions_grouped([_as_group(c) for c in big])
+    assert [g[0].tolist() for g in got] == [list(c.expected) for c in big]
+    exact(handle, _three_with_one_polygon_and_one_row())
+    got = handle.fca_collisions_grouped([_as_group(c) for c in big])
+    one = C.abutting_grid((1.0, 0.0), side=1)
+    exact(handle, one)
+    assert [g[0].tolist() for g in got] == [list(c.expected) for c in big]
 
 
 @pytest.mark.parametrize("origin", [(2.0 ** 10, 2.0 ** 10), (2.0 ** 20, -(2.0 ** 20))])

@@ -15,7 +15,7 @@ from pdmpc.mpa import get_mpa
 from pdmpc.native_controller import NativeSweep
 
 from test_gpu_parity import assert_records_equal
-from test_sweep import ERR_CAPACITY, ERR_INVALID, HP, _bits, _closed_loop_poses, assert_same_state, assert_sweep_problem, distance_members, reachable_members, road
+from test_sweep import ERR_CAPACITY, ERR_INVALID, HP, ONE_MEMBER_KINDS, _bits, _closed_loop_poses, assert_same_state, assert_sweep_problem, distance_members, reachable_members, road
 
 pytestmark = pytest.mark.gpu
 
@@ -64,6 +64,34 @@ def test_members_of_a_sweep_end_every_step_where_they_end_it_alone(members, opti
         sweep.close()
         for c in solo + swept:
             c.close()
+        h.close()
+
+
+@pytest.mark.parametrize("optimizer", ["graph_search", "sampled"])
+@pytest.mark.parametrize("kind", ["bounded_every_step_host_coupling", "fca"])
+def test_a_sweep_of_one_member_ends_every_step_where_the_member_ends_it_alone(kind, optimizer):
+    """A solo step is a sweep of one member: the same grouped device calls with one group, the controller in the scratch it owns and the
+    sweep in its own.  8 vehicles whose sets are bounded every step, and 8 with FCA priorities; the records carry the pops that weigh
+    the next step's searches."""
+    make, calls = ONE_MEMBER_KINDS[kind]
+    member = make(max_vehicles=8, max_nodes=1 << 17)
+    h, mpa, _ = shared_handle(8)
+    solo, swept = member.make(h, mpa, optimizer=optimizer), member.make(h, mpa, optimizer=optimizer)
+    sweep = NativeSweep([swept], h)
+    try:
+        for k in range(1, 4):
+            a = solo.step()
+            (b,) = sweep.step()
+            assert sweep.prep_calls() == calls, k
+            assert_records_equal(b, a, "step %d" % k)
+            assert a.tobytes() == b.tobytes() and a["n_popped"].tolist() == b["n_popped"].tolist(), k
+            assert_same_state(solo.state(), swept.state(), "step %d" % k)
+            assert solo.seeds() == swept.seeds() and solo.priorities() == swept.priorities(), k
+            assert_sweep_problem(sweep.problem(), [solo.problem()], "step %d" % k)
+    finally:
+        sweep.close()
+        solo.close()
+        swept.close()
         h.close()
 
 

@@ -96,7 +96,8 @@ def assert_same_state(a, b, ctx):
     assert a["needs_fallback"].tolist() == b["needs_fallback"].tolist() and a["k"] == b["k"], ctx
 
 
-def sweep_against_solo(members, n_steps):
+def sweep_against_solo(members, n_steps, prep_calls=None):
+    """(prep_calls: what pdmpc_sweep_last_prep_calls reports after every build)"""
     from oracle import oracle
 
     solo = [m.make() for m in members]
@@ -115,6 +116,7 @@ def sweep_against_solo(members, n_steps):
                 problems.append(p)
                 records.append(recs)
             sweep.build()
+            assert prep_calls is None or sweep.prep_calls() == prep_calls, (k, sweep.prep_calls())
             sp = sweep.problem()
             assert_sweep_problem(sp, problems, "step %d" % k)
             for c, p in zip(swept, problems):  # ... and every member's own problem is the one its own build leaves
@@ -136,6 +138,82 @@ def test_sweep_builds_and_applies_what_the_members_would_alone():
 
 def test_sweep_with_reachable_set_coupling_on_the_grouped_host_twins():
     sweep_against_solo(reachable_members(), 8)
+
+
+def fca_member(**kw):
+    """8 vehicles with FCA priorities (tests/test_fca_grouped.py: fca_members()[0])"""
+    return road(8, 4, "distance", priority_strategy="fca", **kw)
+
+
+# One member of every preparation kind, each the smallest of its kind among the members above, and the step-preparation calls a sweep of
+# that member alone makes without a handle: [lanelet bounding, bounded coupling, hull coupling, collision assessment]
+ONE_MEMBER_KINDS = {
+    "bounded_every_step_host_coupling": (
+        lambda **kw: road(8, 4, "distance", priority_strategy="coloring", max_num_CLs=2, is_deal_prediction_inconsistency=True, bound_reachable_sets=True, **kw),
+        [1, 0, 0, 0],
+    ),
+    "plain_hulls": (lambda **kw: road(10, 3, "reachable_set", **kw), [0, 0, 1, 0]),
+    "bounded_and_coupled_on_the_bounded_sets": (
+        lambda **kw: road(12, 2, "reachable_set", priority_strategy="coloring", max_num_CLs=2, is_deal_prediction_inconsistency=True, bound_reachable_sets=True, **kw),
+        [1, 1, 0, 0],
+    ),
+    "bounding_on_nothing_to_bound": (lambda **kw: circle("reachable_set", is_deal_prediction_inconsistency=True, bound_reachable_sets=True, **kw), [0, 0, 1, 0]),
+    "fca": (fca_member, [0, 0, 0, 1]),
+}
+
+
+@pytest.mark.parametrize("kind", sorted(ONE_MEMBER_KINDS))
+def test_a_sweep_of_one_member_is_the_member_alone(kind):
+    """A solo step is a sweep of one member: both go through the same step preparation, the sweep in its own scratch,
+    the controller in the one it owns; the problems, states and seeds are the same bits and the calls the ones of the member's kind."""
+    make, calls = ONE_MEMBER_KINDS[kind]
+    sweep_against_solo([make()], 3, prep_calls=calls)
+
+
+def test_controllers_move_between_stepping_alone_and_a_sweep_like_never_swept_twins():
+    """Alone, then in a sweep of two, then alone again, three steps each, next to twins that only ever step alone: what a controller's
+    own step-preparation scratch holds does not reach the sweep's and the reverse.  The two members use all of the scratch (lanelet
+    bounding, the coupler on the bounded sets, the collision assessment) and differ in size."""
+    from oracle import oracle
+
+    members = [ONE_MEMBER_KINDS["bounded_and_coupled_on_the_bounded_sets"][0](), fca_member()]
+    twins = [m.make() for m in members]
+    moved = [m.make() for m in members]
+
+    def alone(m, c):
+        c.build_step()
+        p = c.problem()
+        c.apply(oracle.plan_step(m.options, m.mpa, p)[0])
+        return p
+
+    def all_alone(phase):
+        for k in range(3):
+            for i, (m, a, b) in enumerate(zip(members, twins, moved)):
+                ctx = "%s, step %d member %d" % (phase, k + 1, i)
+                assert_same_problem(alone(m, a), alone(m, b), ctx)
+                assert_same_state(a.state(), b.state(), ctx)
+                assert a.priorities() == b.priorities() and a.seeds() == b.seeds(), ctx
+
+    sweep = None
+    try:
+        all_alone("alone before the sweep")
+        sweep = NativeSweep(moved)
+        for k in range(3):
+            problems = [alone(m, c) for m, c in zip(members, twins)]
+            sweep.build()
+            assert sweep.prep_calls() == [1, 1, 0, 1], k
+            assert_sweep_problem(sweep.problem(), problems, "in the sweep, step %d" % (k + 1))
+            sweep.apply(np.concatenate([oracle.plan_step(m.options, m.mpa, p)[0] for m, p in zip(members, problems)]))
+            for i, (a, b) in enumerate(zip(twins, moved)):
+                assert_same_state(a.state(), b.state(), "in the sweep, step %d member %d" % (k + 1, i))
+                assert a.priorities() == b.priorities() and a.seeds() == b.seeds(), (k, i)
+        sweep.close()
+        all_alone("alone after the sweep")
+    finally:
+        if sweep is not None:
+            sweep.close()
+        for c in twins + moved:
+            c.close()
 
 
 def _closed_loop_poses():
