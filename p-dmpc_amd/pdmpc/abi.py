@@ -18,6 +18,24 @@ CHECK_SAT, CHECK_INTERX = 0, 1
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
 c_uint8_p = C.POINTER(C.c_uint8)
+c_uint32_p = C.POINTER(C.c_uint32)
+
+
+def dp(a):
+    """double* of a contiguous float64 array (the four helpers: the pointer keeps its array alive)"""
+    return a.ctypes.data_as(c_double_p)
+
+
+def i32p(a):
+    return a.ctypes.data_as(c_int32_p)
+
+
+def u8p(a):
+    return a.ctypes.data_as(c_uint8_p)
+
+
+def u32p(a):
+    return a.ctypes.data_as(c_uint32_p)
 
 
 class Config(C.Structure):
@@ -128,6 +146,48 @@ class Stats(C.Structure):
     ]
 
 
+class FcaGroup(C.Structure):
+    """pdmpc_fca_group"""
+
+    _fields_ = [("n", C.c_int32), ("n_pairs", C.c_int32), ("pairs", c_int32_p), ("obstacles", C.POINTER(PolygonSet)),
+                ("dynamic_rows", C.POINTER(PolygonSet)), ("length", C.c_double), ("width", C.c_double), ("offset", C.c_double)]
+
+
+class ChoiceStruct(C.Structure):
+    """pdmpc_choice"""
+
+    _fields_ = [
+        ("n_cells", C.c_int32), ("n_graphs", C.c_int32), ("n_picks", C.c_int32), ("_pad", C.c_int32),
+        ("cell_offset", c_int32_p), ("cell_slot", c_int32_p), ("graph_offset", c_int32_p),
+        ("pick_graph", c_int32_p), ("pick_offset", c_int32_p), ("pick_slot", c_int32_p),
+    ]
+
+
+class ControllerConfig(C.Structure):
+    """pdmpc_controller_config"""
+
+    _fields_ = [
+        ("Hp", C.c_int32), ("coupling", C.c_int32), ("priority_strategy", C.c_int32), ("weight_strategy", C.c_int32), ("max_num_CLs", C.c_int32),
+        ("constraint_from_successor", C.c_int32), ("dt_seconds", C.c_double), ("offset", C.c_double), ("vehicle_length", C.c_double), ("vehicle_width", C.c_double),
+    ]
+
+
+class ScenarioStruct(C.Structure):
+    """pdmpc_scenario"""
+
+    _fields_ = [
+        ("n_vehicles", C.c_int32),
+        ("x_start", c_double_p), ("y_start", c_double_p), ("yaw_start", c_double_p), ("reference_speed", c_double_p),
+        ("path_offset", c_int32_p), ("path_x", c_double_p), ("path_y", c_double_p),
+        ("lanelets_offset", c_int32_p), ("lanelets_index", c_int32_p), ("points_index", c_int32_p), ("is_loop", c_int32_p),
+        ("tile_dx", c_double_p), ("tile_dy", c_double_p),
+        ("n_lanelets", C.c_int32), ("left_offset", c_int32_p), ("right_offset", c_int32_p),
+        ("left_x", c_double_p), ("left_y", c_double_p), ("right_x", c_double_p), ("right_y", c_double_p),
+        ("obstacles", PolygonSet),
+        ("n_trims", C.c_int32), ("trim_speed", c_double_p), ("trim_steering", c_double_p),
+    ]
+
+
 # numpy view of pdmpc_vehicle_out (same memory layout; used for the RCCL exchange and for fast decoding)
 VEHICLE_OUT_DTYPE = np.dtype(
     [
@@ -149,10 +209,6 @@ assert VEHICLE_OUT_DTYPE.itemsize == C.sizeof(VehicleOut), (VEHICLE_OUT_DTYPE.it
 
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
-
-
-def _dp(a):
-    return a.ctypes.data_as(c_double_p)
 
 
 class _Keep:
@@ -183,7 +239,7 @@ def pack_polygon_set(polys, keep):
         x[offs[i] : offs[i + 1]] = p[0]
         y[offs[i] : offs[i + 1]] = p[1]
     keep.refs += [offs, x, y]
-    return PolygonSet(n, offs.ctypes.data_as(c_int32_p), _dp(x), _dp(y))
+    return PolygonSet(n, i32p(offs), dp(x), dp(y))
 
 
 def pack_mpa(mpa):
@@ -218,7 +274,7 @@ def pack_mpa(mpa):
                 for v in range(ncol):
                     dst[r][v] = float(a[r, v])
     keep.refs += [trans, index, arr]
-    out = Mpa(n, Hp, trans.ctypes.data_as(c_uint8_p), index.ctypes.data_as(c_int32_p), len(mans), arr)
+    out = Mpa(n, Hp, u8p(trans), i32p(index), len(mans), arr)
     return out, keep
 
 
@@ -233,7 +289,7 @@ def pack_vehicle(it, Hp, keep, dst):
     vr = keep.f64(it.v_ref)
     if vr.shape != (Hp,):
         raise ValueError("v_ref must have Hp entries")
-    dst.ref_x, dst.ref_y, dst.v_ref = _dp(rx), _dp(ry), _dp(vr)
+    dst.ref_x, dst.ref_y, dst.v_ref = dp(rx), dp(ry), dp(vr)
     left = it.predicted_lanelet_boundary[0]
     right = it.predicted_lanelet_boundary[1]
     for side, name in ((left, "left"), (right, "right")):
@@ -245,8 +301,8 @@ def pack_vehicle(it, Hp, keep, dst):
             n = side.shape[1]
             sx, sy = keep.f64(side[0]), keep.f64(side[1])
         setattr(dst, "n_" + name, n)
-        setattr(dst, name + "_x", _dp(sx))
-        setattr(dst, name + "_y", _dp(sy))
+        setattr(dst, name + "_x", dp(sx))
+        setattr(dst, name + "_y", dp(sy))
     dst.obstacles = pack_polygon_set(list(it.obstacles), keep)
     dyn = []
     for row in it.dynamic_obstacle_area:
@@ -278,3 +334,8 @@ def out_array(n):
 
 def out_ptr(arr):
     return arr.ctypes.data_as(C.POINTER(VehicleOut))
+
+
+def records_copy(ptr, count):
+    """`count` records the library owns at `ptr` -> a copy as a VEHICLE_OUT_DTYPE array."""
+    return np.ctypeslib.as_array(C.cast(ptr, c_uint8_p), shape=(count * VEHICLE_OUT_DTYPE.itemsize,)).view(VEHICLE_OUT_DTYPE).copy()

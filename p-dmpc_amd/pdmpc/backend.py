@@ -11,144 +11,15 @@ import os
 import numpy as np
 
 from . import abi
+from .abi import ChoiceStruct, FcaGroup  # noqa: F401  (their home; importable from here as before)
+from .prototypes import PROTOTYPES, declare
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PDMPC_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libpdmpc_hip.so")
 
 _LIB = None
 
-EXPORTS = [
-    "pdmpc_create",
-    "pdmpc_destroy",
-    "pdmpc_upload_mpa",
-    "pdmpc_get_config",
-    "pdmpc_plan_batch",
-    "pdmpc_plan_batch_sampled",
-    "pdmpc_plan_joint",
-    "pdmpc_pack_batch",
-    "pdmpc_launch_packed",
-    "pdmpc_launch_range",
-    "pdmpc_begin_step",
-    "pdmpc_select_bank",
-    "pdmpc_reset_stats",
-    "pdmpc_fetch_results",
-    "pdmpc_synchronize",
-    "pdmpc_set_safe_launch",
-    "pdmpc_pack_step",
-    "pdmpc_plan_step",
-    "pdmpc_plan_step_literal",
-    "pdmpc_set_arena_limit",
-    "pdmpc_grow_arena",
-    "pdmpc_arena_nodes",
-    "pdmpc_result_device_buffer",
-    "pdmpc_import_results",
-    "pdmpc_export_results",
-    "pdmpc_export_results_async",
-    "pdmpc_stream",
-    "pdmpc_get_last_stats",
-    "pdmpc_group_create",
-    "pdmpc_group_create_ex",
-    "pdmpc_set_step_weights",
-    "pdmpc_set_device_share",
-    "pdmpc_last_call_timing",
-    "pdmpc_plan_step_lean",
-    "pdmpc_fetch_records_at",
-    "pdmpc_controller_last_timing",
-    "pdmpc_controller_timing_sum",
-    "pdmpc_controller_explore_follow_own",
-    "pdmpc_group_collective",
-    "pdmpc_group_destroy",
-    "pdmpc_group_size",
-    "pdmpc_group_handle",
-    "pdmpc_group_grow_arena",
-    "pdmpc_group_upload_mpa",
-    "pdmpc_group_plan_step",
-    "pdmpc_group_pack_step",
-    "pdmpc_group_launch",
-    "pdmpc_group_fetch",
-    "pdmpc_group_partition",
-    "pdmpc_group_last_timing",
-    "pdmpc_debug_heap_script",
-    "pdmpc_debug_pop_trace",
-    "pdmpc_debug_tree",
-    "pdmpc_debug_raw_tree",
-    "pdmpc_debug_edge_check",
-    "pdmpc_debug_progress",
-    "pdmpc_debug_counters",
-    "pdmpc_controller_create",
-    "pdmpc_controller_destroy",
-    "pdmpc_controller_step",
-    "pdmpc_controller_run",
-    "pdmpc_controller_build_step",
-    "pdmpc_controller_apply",
-    "pdmpc_controller_problem",
-    "pdmpc_controller_state",
-    "pdmpc_controller_records",
-    "pdmpc_controller_last_error",
-    "pdmpc_exploration_permutations",
-    "pdmpc_controller_explore_build",
-    "pdmpc_controller_explore_problem",
-    "pdmpc_controller_explore_choose",
-    "pdmpc_controller_explore_step",
-    "pdmpc_controller_explore_run",
-    "pdmpc_controller_explore_result",
-    "pdmpc_unique_priorities",
-    "pdmpc_unique_priorities_host",
-    "pdmpc_controller_optimal_build",
-    "pdmpc_controller_optimal_choose",
-    "pdmpc_controller_optimal_step",
-    "pdmpc_controller_optimal_run",
-    "pdmpc_controller_optimal_result",
-    "pdmpc_local_reachable_sets",
-    "pdmpc_upload_reachable_sets",
-    "pdmpc_reachable_set_coupling",
-    "pdmpc_reachable_set_coupling_host",
-    "pdmpc_reachable_set_coupling_kernel_ms",
-    "pdmpc_controller_set_reachability",
-    "pdmpc_controller_set_parallel_coupling",
-    "pdmpc_bound_reachable_sets",
-    "pdmpc_bound_reachable_sets_host",
-    "pdmpc_bounded_set_coupling",
-    "pdmpc_polygon_set_coupling_host",
-    "pdmpc_bounded_reachable_kernel_ms",
-    "pdmpc_reachable_set_coupling_grouped",
-    "pdmpc_bounded_set_coupling_grouped",
-    "pdmpc_reachable_set_coupling_grouped_host",
-    "pdmpc_polygon_set_coupling_grouped_host",
-    "pdmpc_sweep_create",
-    "pdmpc_sweep_destroy",
-    "pdmpc_sweep_build",
-    "pdmpc_sweep_problem",
-    "pdmpc_sweep_apply",
-    "pdmpc_sweep_step",
-    "pdmpc_sweep_run",
-    "pdmpc_sweep_last_timing",
-    "pdmpc_fca_collisions",
-    "pdmpc_fca_collisions_host",
-    "pdmpc_fca_kernel_ms",
-    "pdmpc_fca_collisions_grouped",
-    "pdmpc_fca_collisions_grouped_host",
-    "pdmpc_controller_priorities",
-    "pdmpc_sweep_last_prep_calls",
-    "pdmpc_controller_set_lanelet_bounding",
-    "pdmpc_plan_step_sampled",
-    "pdmpc_set_step_seeds",
-    "pdmpc_debug_random_numbers",
-    "pdmpc_controller_set_optimizer",
-    "pdmpc_controller_seeds",
-    "pdmpc_choose_host",
-    "pdmpc_choose_resident",
-    "pdmpc_plan_step_chosen",
-    "pdmpc_choice_kernel_ms",
-    "pdmpc_controller_set_device_choice",
-    "pdmpc_sweep_explore_build",
-    "pdmpc_sweep_explore_problem",
-    "pdmpc_sweep_explore_apply",
-    "pdmpc_sweep_explore_step",
-    "pdmpc_sweep_explore_run",
-    "pdmpc_last_error",
-    "pdmpc_version",
-]
+EXPORTS = list(PROTOTYPES)  # every function of include/pdmpc.h
 
 
 class BackendError(RuntimeError):
@@ -177,7 +48,7 @@ def unique_priorities_call(adjacency, max_out, handle=None):
     masks = np.zeros(max(cap, 1), dtype=np.uint32)
     prio = np.zeros(max(cap, 1) * n, dtype=np.int32)
     K = C.c_int64(0)
-    args = [n, A.ctypes.data_as(abi.c_uint8_p), cap, C.byref(K), masks.ctypes.data_as(C.POINTER(C.c_uint32)), prio.ctypes.data_as(abi.c_int32_p)]
+    args = [n, abi.u8p(A), cap, C.byref(K), abi.u32p(masks), abi.i32p(prio)]
     if handle is not None:
         rc = L.pdmpc_unique_priorities(handle.h, *args)
         what = "pdmpc_unique_priorities"
@@ -186,7 +57,7 @@ def unique_priorities_call(adjacency, max_out, handle=None):
         what = "pdmpc_unique_priorities_host"
     if rc == ERR_CAPACITY:
         raise CapacityError("%s: capacity (%d unique prioritizations, max_out %d)" % (what, K.value, cap), K.value)
-    _check(L, rc, what, message=handle is not None)
+    _check(L, rc, what, last_error="pdmpc_last_error" if handle is not None else None)
     k = K.value
     return prio[: k * n].reshape(k, n).T.astype(np.int64), masks[:k].astype(np.int64)
 
@@ -198,14 +69,14 @@ def local_reachable_sets_native(mpa):
     s, keep = abi.pack_mpa(mpa)
     n, Hp = mpa.n_trims, mpa.Hp
     off = np.zeros(n * Hp + 1, dtype=np.int32)
-    rc = L.pdmpc_local_reachable_sets(C.byref(s), 0, off.ctypes.data_as(abi.c_int32_p), None, None)
+    rc = L.pdmpc_local_reachable_sets(C.byref(s), 0, abi.i32p(off), None, None)
     if rc != ERR_CAPACITY:
-        _check(L, rc, "pdmpc_local_reachable_sets", message=False)
+        _check(L, rc, "pdmpc_local_reachable_sets", last_error=None)
     tot = int(off[-1])
     x = np.zeros(max(tot, 1))
     y = np.zeros(max(tot, 1))
-    rc = L.pdmpc_local_reachable_sets(C.byref(s), tot, off.ctypes.data_as(abi.c_int32_p), x.ctypes.data_as(abi.c_double_p), y.ctypes.data_as(abi.c_double_p))
-    _check(L, rc, "pdmpc_local_reachable_sets", message=False)
+    rc = L.pdmpc_local_reachable_sets(C.byref(s), tot, abi.i32p(off), abi.dp(x), abi.dp(y))
+    _check(L, rc, "pdmpc_local_reachable_sets", last_error=None)
     del keep
     return [[np.array([x[off[i * Hp + k] : off[i * Hp + k + 1]], y[off[i * Hp + k] : off[i * Hp + k + 1]]]) for k in range(Hp)] for i in range(n)]
 
@@ -241,15 +112,14 @@ def reachable_set_coupling_call(local_sets, x, y, yaw, trim, handle=None):
     x, y, c, s, t = _coupling_args(x, y, yaw, trim)
     n = x.size
     adj, area, shaped = _coupling_out(n)
-    ptrs = [x.ctypes.data_as(abi.c_double_p), y.ctypes.data_as(abi.c_double_p), c.ctypes.data_as(abi.c_double_p), s.ctypes.data_as(abi.c_double_p),
-            t.ctypes.data_as(abi.c_int32_p), adj.ctypes.data_as(abi.c_uint8_p), area.ctypes.data_as(abi.c_double_p)]
+    ptrs = [abi.dp(x), abi.dp(y), abi.dp(c), abi.dp(s), abi.i32p(t), abi.u8p(adj), abi.dp(area)]
     if handle is not None:
         _check(L, L.pdmpc_reachable_set_coupling(handle.h, n, *ptrs), "pdmpc_reachable_set_coupling")
     else:
         ps, keep = pack_local_sets(local_sets)
         rc = L.pdmpc_reachable_set_coupling_host(len(local_sets), len(local_sets[0]), C.byref(ps), n, *ptrs)
         del keep
-        _check(L, rc, "pdmpc_reachable_set_coupling_host", message=False)
+        _check(L, rc, "pdmpc_reachable_set_coupling_host", last_error=None)
     return shaped()
 
 
@@ -287,15 +157,14 @@ def reachable_set_coupling_grouped_call(local_sets, group_sizes, x, y, yaw, trim
     if int(off[-1]) != x.size:
         raise ValueError("the groups cover %d vehicles, %d were handed over" % (int(off[-1]), x.size))
     adj, area, blocks = _grouped_out(group_sizes)
-    ptrs = [off.ctypes.data_as(abi.c_int32_p), x.ctypes.data_as(abi.c_double_p), y.ctypes.data_as(abi.c_double_p), c.ctypes.data_as(abi.c_double_p),
-            s.ctypes.data_as(abi.c_double_p), t.ctypes.data_as(abi.c_int32_p), adj.ctypes.data_as(abi.c_uint8_p), area.ctypes.data_as(abi.c_double_p)]
+    ptrs = [abi.i32p(off), abi.dp(x), abi.dp(y), abi.dp(c), abi.dp(s), abi.i32p(t), abi.u8p(adj), abi.dp(area)]
     if handle is not None:
         _check(L, L.pdmpc_reachable_set_coupling_grouped(handle.h, len(group_sizes), *ptrs), "pdmpc_reachable_set_coupling_grouped")
     else:
         ps, keep = pack_local_sets(local_sets)
         rc = L.pdmpc_reachable_set_coupling_grouped_host(len(local_sets), len(local_sets[0]), C.byref(ps), len(group_sizes), *ptrs)
         del keep
-        _check(L, rc, "pdmpc_reachable_set_coupling_grouped_host", message=False)
+        _check(L, rc, "pdmpc_reachable_set_coupling_grouped_host", last_error=None)
     return blocks()
 
 
@@ -309,10 +178,9 @@ def polygon_set_coupling_grouped_call(sets, group_sizes):
         raise ValueError("the groups cover %d polygons, %d were handed over" % (int(off[-1]), len(sets)))
     ps = abi.pack_polygon_set([np.asarray(p, dtype=np.float64) for p in sets], keep)
     adj, area, blocks = _grouped_out(group_sizes)
-    rc = L.pdmpc_polygon_set_coupling_grouped_host(C.byref(ps), len(group_sizes), off.ctypes.data_as(abi.c_int32_p), adj.ctypes.data_as(abi.c_uint8_p),
-                                                   area.ctypes.data_as(abi.c_double_p))
+    rc = L.pdmpc_polygon_set_coupling_grouped_host(C.byref(ps), len(group_sizes), abi.i32p(off), abi.u8p(adj), abi.dp(area))
     del keep
-    _check(L, rc, "pdmpc_polygon_set_coupling_grouped_host", message=False)
+    _check(L, rc, "pdmpc_polygon_set_coupling_grouped_host", last_error=None)
     return blocks()
 
 
@@ -354,9 +222,8 @@ def fca_pack(reference_points, pairs, length, width, offset, obstacles=(), dynam
     keep.refs += [obst, dyn]
     coll = np.zeros(max(n, 1), dtype=np.int32)
     prio = np.zeros(max(n, 1), dtype=np.int32)
-    args = [n, Hp, x.ctypes.data_as(abi.c_double_p), y.ctypes.data_as(abi.c_double_p), c.ctypes.data_as(abi.c_double_p), s.ctypes.data_as(abi.c_double_p),
-            len(pr), pr.ctypes.data_as(abi.c_int32_p) if len(pr) else None, C.byref(obst), C.byref(dyn) if dyn is not None else None,
-            float(length), float(width), float(offset), coll.ctypes.data_as(abi.c_int32_p), prio.ctypes.data_as(abi.c_int32_p)]
+    args = [n, Hp, abi.dp(x), abi.dp(y), abi.dp(c), abi.dp(s), len(pr), abi.i32p(pr) if len(pr) else None, C.byref(obst),
+            C.byref(dyn) if dyn is not None else None, float(length), float(width), float(offset), abi.i32p(coll), abi.i32p(prio)]
     return args, (coll[:n], prio[:n]), keep
 
 
@@ -370,16 +237,9 @@ def fca_collisions_host(reference_points, pairs, length, width, offset, obstacle
     if handle is not None:
         _check(L, L.pdmpc_fca_collisions(handle.h, *args), "pdmpc_fca_collisions")
     else:
-        _check(L, L.pdmpc_fca_collisions_host(*args), "pdmpc_fca_collisions_host", message=False)
+        _check(L, L.pdmpc_fca_collisions_host(*args), "pdmpc_fca_collisions_host", last_error=None)
     del keep
     return out
-
-
-class FcaGroup(C.Structure):
-    """pdmpc_fca_group (include/pdmpc.h)"""
-
-    _fields_ = [("n", C.c_int32), ("n_pairs", C.c_int32), ("pairs", abi.c_int32_p), ("obstacles", C.POINTER(abi.PolygonSet)),
-                ("dynamic_rows", C.POINTER(abi.PolygonSet)), ("length", C.c_double), ("width", C.c_double), ("offset", C.c_double)]
 
 
 def fca_grouped_pack(groups, Hp=None):
@@ -413,8 +273,7 @@ def fca_grouped_pack(groups, Hp=None):
     coll = np.zeros(max(N, 1), dtype=np.int32)
     prio = np.zeros(max(N, 1), dtype=np.int32)
     keeps += [arr, x, y, c, s]
-    args = [len(groups), arr, Hp if Hp is not None else 0] + [a.ctypes.data_as(abi.c_double_p) for a in (x, y, c, s)] + [
-        coll.ctypes.data_as(abi.c_int32_p), prio.ctypes.data_as(abi.c_int32_p)]
+    args = [len(groups), arr, Hp if Hp is not None else 0] + [abi.dp(a) for a in (x, y, c, s)] + [abi.i32p(coll), abi.i32p(prio)]
     at = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
 
     def per_group():
@@ -432,7 +291,7 @@ def fca_collisions_grouped_call(groups, Hp=None, handle=None):
     if handle is not None:
         _check(L, L.pdmpc_fca_collisions_grouped(handle.h, *args), "pdmpc_fca_collisions_grouped")
     else:
-        _check(L, L.pdmpc_fca_collisions_grouped_host(*args), "pdmpc_fca_collisions_grouped_host", message=False)
+        _check(L, L.pdmpc_fca_collisions_grouped_host(*args), "pdmpc_fca_collisions_grouped_host", last_error=None)
     del keep
     return per_group()
 
@@ -456,20 +315,19 @@ def bound_reachable_sets_call(local_sets, x, y, yaw, trim, lanelet_polys, all_st
     S = (handle.options.Hp if handle is not None else len(local_sets[0])) if all_steps else 1
     off = np.zeros(n * S + 1, dtype=np.int32)
     flags = np.zeros(max(n * S, 1), dtype=np.uint8)
-    head = [x.ctypes.data_as(abi.c_double_p), y.ctypes.data_as(abi.c_double_p), c.ctypes.data_as(abi.c_double_p), s.ctypes.data_as(abi.c_double_p),
-            t.ctypes.data_as(abi.c_int32_p), C.byref(lp), int(bool(all_steps))]
+    head = [abi.dp(x), abi.dp(y), abi.dp(c), abi.dp(s), abi.i32p(t), C.byref(lp), int(bool(all_steps))]
     if handle is None:
         ps, keep = pack_local_sets(local_sets)
         fn = lambda *tail: L.pdmpc_bound_reachable_sets_host(len(local_sets), len(local_sets[0]), C.byref(ps), n, *head, *tail)  # noqa: E731
     else:
         fn = lambda *tail: L.pdmpc_bound_reachable_sets(handle.h, n, *head, *tail)  # noqa: E731
-    rc = fn(0, off.ctypes.data_as(abi.c_int32_p), None, None, None)
+    rc = fn(0, abi.i32p(off), None, None, None)
     if rc != ERR_CAPACITY or (n and int(off[-1]) == 0):
         _check(L, rc, "pdmpc_bound_reachable_sets")
     tot = int(off[-1])
     bx = np.zeros(max(tot, 1))
     by = np.zeros(max(tot, 1))
-    rc = fn(tot, off.ctypes.data_as(abi.c_int32_p), bx.ctypes.data_as(abi.c_double_p), by.ctypes.data_as(abi.c_double_p), flags.ctypes.data_as(abi.c_uint8_p))
+    rc = fn(tot, abi.i32p(off), abi.dp(bx), abi.dp(by), abi.u8p(flags))
     del lkeep
     _check(L, rc, "pdmpc_bound_reachable_sets")
     sets = [[np.array([bx[off[v * S + q] : off[v * S + q + 1]], by[off[v * S + q] : off[v * S + q + 1]]]) for q in range(S)] for v in range(n)]
@@ -483,20 +341,10 @@ def polygon_set_coupling_call(sets):
     n = len(sets)
     ps = abi.pack_polygon_set([np.asarray(p, dtype=np.float64) for p in sets], keep)
     adj, area, shaped = _coupling_out(n)
-    rc = L.pdmpc_polygon_set_coupling_host(C.byref(ps), n, adj.ctypes.data_as(abi.c_uint8_p), area.ctypes.data_as(abi.c_double_p))
+    rc = L.pdmpc_polygon_set_coupling_host(C.byref(ps), n, abi.u8p(adj), abi.dp(area))
     del keep
-    _check(L, rc, "pdmpc_polygon_set_coupling_host", message=False)
+    _check(L, rc, "pdmpc_polygon_set_coupling_host", last_error=None)
     return shaped()
-
-
-class ChoiceStruct(C.Structure):
-    """pdmpc_choice (include/pdmpc.h)."""
-
-    _fields_ = [
-        ("n_cells", C.c_int32), ("n_graphs", C.c_int32), ("n_picks", C.c_int32), ("_pad", C.c_int32),
-        ("cell_offset", abi.c_int32_p), ("cell_slot", abi.c_int32_p), ("graph_offset", abi.c_int32_p),
-        ("pick_graph", abi.c_int32_p), ("pick_offset", abi.c_int32_p), ("pick_slot", abi.c_int32_p),
-    ]
 
 
 class Choice:
@@ -517,7 +365,7 @@ class Choice:
         self.n_cells, self.n_graphs, self.n_picks = len(cells), len(self.graph_offset) - 1, len(picks)
 
     def struct(self):
-        p = lambda a: a.ctypes.data_as(abi.c_int32_p)  # noqa: E731
+        p = abi.i32p
         return ChoiceStruct(self.n_cells, self.n_graphs, self.n_picks, 0, p(self.cell_offset), p(self.cell_slot), p(self.graph_offset), p(self.pick_graph),
                             p(self.pick_offset), p(self.pick_slot))
 
@@ -536,12 +384,7 @@ def choose_host_call(status, final_cost, choice):
     fc = np.ascontiguousarray(final_cost, dtype=np.float64)
     chosen, cost, _ = choice.outputs()
     ch = choice.struct()
-    rc = L.pdmpc_choose_host(len(st), st.ctypes.data_as(abi.c_int32_p), fc.ctypes.data_as(abi.c_double_p), C.byref(ch), chosen.ctypes.data_as(abi.c_int32_p),
-                             cost.ctypes.data_as(abi.c_double_p))
-    if rc != 0:
-        err = BackendError("pdmpc_choose_host failed with status %d: %s" % (rc, (L.pdmpc_last_error() or b"").decode()))
-        err.status = rc
-        raise err
+    _check(L, L.pdmpc_choose_host(len(st), abi.i32p(st), abi.dp(fc), C.byref(ch), abi.i32p(chosen), abi.dp(cost)), "pdmpc_choose_host")
     return choice.shaped(chosen, cost)
 
 
@@ -562,98 +405,36 @@ def load_library(path=None):
             "HIP backend %s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(there is no CPU fallback)" % p
         )
-    L = C.CDLL(p)
-    H = C.c_void_p
-    L.pdmpc_create.argtypes = [C.POINTER(abi.Config), C.POINTER(H)]
-    L.pdmpc_destroy.argtypes = [H]
-    L.pdmpc_upload_mpa.argtypes = [H, C.POINTER(abi.Mpa)]
-    L.pdmpc_get_config.argtypes = [H, C.POINTER(abi.Config), C.POINTER(C.c_int32)]
-    L.pdmpc_plan_batch.argtypes = [H, C.c_int32, C.POINTER(abi.VehicleIn), C.POINTER(abi.VehicleOut)]
-    L.pdmpc_pack_batch.argtypes = [H, C.c_int32, C.POINTER(abi.VehicleIn)]
-    L.pdmpc_launch_packed.argtypes = [H]
-    L.pdmpc_launch_range.argtypes = [H, C.c_int32, C.c_int32]
-    L.pdmpc_begin_step.argtypes = [H]
-    L.pdmpc_select_bank.argtypes = [H, C.c_int32]
-    L.pdmpc_reset_stats.argtypes = [H]
-    L.pdmpc_fetch_results.argtypes = [H, C.c_int32, C.POINTER(abi.VehicleOut)]
-    L.pdmpc_synchronize.argtypes = [H]
-    L.pdmpc_set_safe_launch.argtypes = [H, C.c_int32]
-    L.pdmpc_pack_step.argtypes = [H, C.c_int32, C.POINTER(abi.VehicleIn), abi.c_int32_p, abi.c_int32_p, C.POINTER(abi.PolygonSet)]
-    L.pdmpc_plan_step.argtypes = [H, C.c_int32, C.POINTER(abi.VehicleIn), abi.c_int32_p, abi.c_int32_p, C.POINTER(abi.PolygonSet), C.POINTER(abi.VehicleOut)]
-    L.pdmpc_plan_step_literal.argtypes = L.pdmpc_plan_step.argtypes
-    L.pdmpc_set_arena_limit.argtypes = [H, C.c_int32]
-    L.pdmpc_grow_arena.argtypes = [H, C.c_int32]
-    L.pdmpc_arena_nodes.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
-    L.pdmpc_result_device_buffer.argtypes = [H, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-    L.pdmpc_import_results.argtypes = [H, C.c_int32, C.c_int32, C.c_void_p]
-    L.pdmpc_export_results.argtypes = [H, C.c_int32, C.c_int32, C.c_void_p]
-    L.pdmpc_export_results_async.argtypes = [H, C.c_int32, C.c_int32, C.c_void_p]
-    L.pdmpc_stream.argtypes = [H, C.POINTER(C.c_void_p)]
-    L.pdmpc_plan_batch_sampled.argtypes = [H, C.c_int32, C.POINTER(abi.VehicleIn), C.POINTER(C.c_uint32), C.POINTER(abi.VehicleOut)]
-    L.pdmpc_plan_step_sampled.argtypes = [H, C.c_int32, C.POINTER(abi.VehicleIn), abi.c_int32_p, abi.c_int32_p, C.POINTER(abi.PolygonSet), C.POINTER(C.c_uint32),
-                                          C.POINTER(abi.VehicleOut)]
-    L.pdmpc_set_step_seeds.argtypes = [H, C.c_int32, C.POINTER(C.c_uint32)]
-    L.pdmpc_debug_random_numbers.argtypes = [H, C.c_int32, C.POINTER(C.c_uint32), C.c_int32, abi.c_double_p]
-    L.pdmpc_plan_joint.argtypes = [H, C.c_int32, abi.c_int32_p, C.POINTER(abi.VehicleIn), C.POINTER(abi.VehicleOut)]
-    L.pdmpc_get_last_stats.argtypes = [H, C.POINTER(abi.Stats)]
-    L.pdmpc_debug_heap_script.argtypes = [H, C.c_int32, abi.c_int32_p, abi.c_int32_p, abi.c_double_p, C.c_int32, abi.c_int32_p, abi.c_int32_p, abi.c_double_p, abi.c_double_p]
-    L.pdmpc_debug_pop_trace.argtypes = [H, C.c_int32, C.c_int32, abi.c_int32_p, abi.c_int32_p]
-    L.pdmpc_debug_tree.argtypes = [H, C.c_int32, C.c_int32] + [abi.c_double_p] * 5 + [abi.c_int32_p] * 4
-    L.pdmpc_debug_raw_tree.argtypes = [H, C.c_int32, C.c_int32] + [abi.c_double_p] * 5 + [abi.c_int32_p] * 3 + [abi.c_double_p, abi.c_uint8_p, abi.c_int32_p]
-    L.pdmpc_debug_edge_check.argtypes = [H, C.c_int32, C.c_int32, abi.c_int32_p, abi.c_double_p, abi.c_double_p, abi.c_int32_p, abi.c_double_p, abi.c_double_p, abi.c_int32_p]
-    L.pdmpc_debug_progress.argtypes = [H, C.c_int32, C.POINTER(C.c_uint32)]
-    L.pdmpc_unique_priorities.argtypes = [H, C.c_int32, abi.c_uint8_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), abi.c_int32_p]
-    L.pdmpc_unique_priorities_host.argtypes = [C.c_int32, abi.c_uint8_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), abi.c_int32_p]
-    L.pdmpc_local_reachable_sets.argtypes = [C.POINTER(abi.Mpa), C.c_int32, abi.c_int32_p, abi.c_double_p, abi.c_double_p]
-    L.pdmpc_upload_reachable_sets.argtypes = [H, C.c_int32, C.c_int32, C.POINTER(abi.PolygonSet)]
-    L.pdmpc_reachable_set_coupling.argtypes = [H, C.c_int32] + [abi.c_double_p] * 4 + [abi.c_int32_p, abi.c_uint8_p, abi.c_double_p]
-    L.pdmpc_reachable_set_coupling_host.argtypes = [C.c_int32, C.c_int32, C.POINTER(abi.PolygonSet), C.c_int32] + [abi.c_double_p] * 4 + [abi.c_int32_p, abi.c_uint8_p, abi.c_double_p]
-    L.pdmpc_reachable_set_coupling_kernel_ms.argtypes = [H, abi.c_double_p]
-    L.pdmpc_controller_set_reachability.argtypes = [H, C.POINTER(abi.Mpa)]
-    L.pdmpc_controller_set_parallel_coupling.argtypes = [H, C.c_int32]
-    bound_tail = [abi.c_double_p] * 4 + [abi.c_int32_p, C.POINTER(abi.PolygonSet), C.c_int32, C.c_int32, abi.c_int32_p, abi.c_double_p, abi.c_double_p, abi.c_uint8_p]
-    L.pdmpc_bound_reachable_sets.argtypes = [H, C.c_int32] + bound_tail
-    L.pdmpc_bound_reachable_sets_host.argtypes = [C.c_int32, C.c_int32, C.POINTER(abi.PolygonSet), C.c_int32] + bound_tail
-    L.pdmpc_bounded_set_coupling.argtypes = [H, abi.c_uint8_p, abi.c_double_p]
-    L.pdmpc_polygon_set_coupling_host.argtypes = [C.POINTER(abi.PolygonSet), C.c_int32, abi.c_uint8_p, abi.c_double_p]
-    L.pdmpc_bounded_reachable_kernel_ms.argtypes = [H, abi.c_double_p]
-    L.pdmpc_reachable_set_coupling_grouped.argtypes = [H, C.c_int32, abi.c_int32_p] + [abi.c_double_p] * 4 + [abi.c_int32_p, abi.c_uint8_p, abi.c_double_p]
-    L.pdmpc_bounded_set_coupling_grouped.argtypes = [H, C.c_int32, abi.c_int32_p, abi.c_uint8_p, abi.c_double_p]
-    L.pdmpc_reachable_set_coupling_grouped_host.argtypes = [C.c_int32, C.c_int32, C.POINTER(abi.PolygonSet), C.c_int32, abi.c_int32_p] + [abi.c_double_p] * 4 + [
-        abi.c_int32_p, abi.c_uint8_p, abi.c_double_p]
-    L.pdmpc_polygon_set_coupling_grouped_host.argtypes = [C.POINTER(abi.PolygonSet), C.c_int32, abi.c_int32_p, abi.c_uint8_p, abi.c_double_p]
-    fca_tail = [C.c_int32, C.c_int32] + [abi.c_double_p] * 4 + [C.c_int32, abi.c_int32_p, C.POINTER(abi.PolygonSet), C.POINTER(abi.PolygonSet)] + \
-        [C.c_double] * 3 + [abi.c_int32_p, abi.c_int32_p]
-    L.pdmpc_fca_collisions.argtypes = [H] + fca_tail
-    L.pdmpc_fca_collisions_host.argtypes = fca_tail
-    L.pdmpc_fca_kernel_ms.argtypes = [H, abi.c_double_p]
-    fca_grouped_tail = [C.c_int32, C.POINTER(FcaGroup), C.c_int32] + [abi.c_double_p] * 4 + [abi.c_int32_p, abi.c_int32_p]
-    L.pdmpc_fca_collisions_grouped.argtypes = [H] + fca_grouped_tail
-    L.pdmpc_fca_collisions_grouped_host.argtypes = fca_grouped_tail
-    L.pdmpc_controller_set_lanelet_bounding.argtypes = [H, C.c_int32]
-    choice_tail = [C.POINTER(ChoiceStruct), abi.c_int32_p, abi.c_double_p]
-    L.pdmpc_choose_host.argtypes = [C.c_int32, abi.c_int32_p, abi.c_double_p] + choice_tail
-    L.pdmpc_choose_resident.argtypes = [H, C.c_int32] + choice_tail + [C.POINTER(abi.VehicleOut)]
-    L.pdmpc_plan_step_chosen.argtypes = [H, C.c_int32, C.POINTER(abi.VehicleIn), abi.c_int32_p, abi.c_int32_p, C.POINTER(abi.PolygonSet)] + choice_tail + [
-        C.POINTER(abi.VehicleOut)]
-    L.pdmpc_choice_kernel_ms.argtypes = [H, abi.c_double_p]
-    L.pdmpc_last_error.restype = C.c_char_p
-    L.pdmpc_version.restype = C.c_char_p
-    for name in EXPORTS:
-        if name.startswith("pdmpc_controller_"):
-            continue  # declared by pdmpc.native_controller
-        if name not in ("pdmpc_last_error", "pdmpc_version"):
-            getattr(L, name).restype = C.c_int
+    L = declare(C.CDLL(p))
     if path is None:
         _LIB = L
     return L
 
 
-def _check(L, rc, what, message=True):
-    """A failing status of `what` -> BackendError, with the library's message (message=False: a host twin, which leaves none)."""
+def _check(L, rc, what, last_error="pdmpc_last_error"):
+    """A failing status of `what` -> BackendError with .status, and with the message of the error string that belongs to the call:
+    pdmpc_last_error, "pdmpc_controller_last_error", or None for a host twin, which leaves none."""
     if rc != 0:
-        msg = ": " + (L.pdmpc_last_error() or b"").decode() if message else ""
-        raise BackendError("%s failed with status %d%s" % (what, rc, msg))
+        msg = ": " + (getattr(L, last_error)() or b"").decode() if last_error else ""
+        err = BackendError("%s failed with status %d%s" % (what, rc, msg))
+        err.status = rc
+        raise err
+
+
+def _step_args(Hp, iters, predecessors, fallback_shapes):
+    """The arguments of a step call after the vehicle count -> (vehicle array, pred_offset, pred_index, fallback sets, keep-alive)."""
+    n = len(iters)
+    arr, keep = abi.pack_vehicles(iters, Hp)
+    off = np.zeros(n + 1, dtype=np.int32)
+    for i, p in enumerate(predecessors):
+        off[i + 1] = off[i] + len(p)
+    idx = np.array([j for p in predecessors for j in p] + [0], dtype=np.int32)
+    fb = None
+    if fallback_shapes is not None:
+        fb = (abi.PolygonSet * n)()
+        for i, shapes in enumerate(fallback_shapes):
+            fb[i] = abi.pack_polygon_set(list(shapes), keep)
+    return arr, off, idx, fb, keep
 
 
 SHARD_AUTO, SHARD_COMPONENTS, SHARD_LEVELS = 0, 1, 2
@@ -671,9 +452,8 @@ def group_partition(preds, world, mode=SHARD_AUTO, weights=None):
     idx = np.array([j for p in preds for j in p] + [0], dtype=np.int32)
     w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
     rank_of, level_of, block = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(3))
-    L.pdmpc_group_partition.argtypes = [C.c_int32, abi.c_int32_p, abi.c_int32_p, abi.c_double_p, C.c_int32, C.c_int32, abi.c_int32_p, abi.c_int32_p, abi.c_int32_p]
-    _check(L, L.pdmpc_group_partition(n, off.ctypes.data_as(abi.c_int32_p), idx.ctypes.data_as(abi.c_int32_p), None if w is None else w.ctypes.data_as(abi.c_double_p), world, mode,
-                                      rank_of.ctypes.data_as(abi.c_int32_p), level_of.ctypes.data_as(abi.c_int32_p), block.ctypes.data_as(abi.c_int32_p)), "pdmpc_group_partition")
+    rc = L.pdmpc_group_partition(n, abi.i32p(off), abi.i32p(idx), None if w is None else abi.dp(w), world, mode, abi.i32p(rank_of), abi.i32p(level_of), abi.i32p(block))
+    _check(L, rc, "pdmpc_group_partition")
     return rank_of[:n], level_of[:n], block[:n]
 
 
@@ -693,11 +473,9 @@ class Group:
                               trace_pops=0)
         self.g = C.c_void_p()
         devs = None if devices is None else (C.c_int32 * n_devices)(*devices)
-        self.L.pdmpc_group_create_ex.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         _check(self.L, self.L.pdmpc_group_create_ex(C.byref(self.cfg), n_devices, devs, collective, C.byref(self.g)), "pdmpc_group_create_ex")
         self.n_devices = n_devices
         c = C.c_int32(0)
-        self.L.pdmpc_group_collective.argtypes = [C.c_void_p, C.c_void_p]
         _check(self.L, self.L.pdmpc_group_collective(self.g, C.byref(c)), "pdmpc_group_collective")
         self.collective = {COLLECTIVE_RCCL: "rccl", COLLECTIVE_COPY: "copy"}[c.value]
         self._mpa_keep = None
@@ -715,56 +493,48 @@ class Group:
 
     def upload_mpa(self, mpa):
         s, keep = abi.pack_mpa(mpa)
-        self.L.pdmpc_group_upload_mpa.argtypes = [C.c_void_p, C.c_void_p]
         _check(self.L, self.L.pdmpc_group_upload_mpa(self.g, C.byref(s)), "pdmpc_group_upload_mpa")
         self._mpa_keep = keep
 
     def plan_step(self, iters, predecessors, fallback_shapes=None, weights=None, mode=SHARD_AUTO):
         n = len(iters)
-        arr, off, idx, fb, keep = Handle._step_args(self, iters, predecessors, fallback_shapes)
+        arr, off, idx, fb, keep = _step_args(self.Hp, iters, predecessors, fallback_shapes)
         out = abi.out_array(n)
         w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
-        self.L.pdmpc_group_plan_step.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, abi.c_int32_p, abi.c_int32_p, C.c_void_p, abi.c_double_p, C.c_int32, C.c_void_p]
-        _check(self.L, self.L.pdmpc_group_plan_step(self.g, n, arr, off.ctypes.data_as(abi.c_int32_p), idx.ctypes.data_as(abi.c_int32_p), fb,
-                                                    None if w is None else w.ctypes.data_as(abi.c_double_p), mode, abi.out_ptr(out)), "pdmpc_group_plan_step")
+        rc = self.L.pdmpc_group_plan_step(self.g, n, arr, abi.i32p(off), abi.i32p(idx), fb, None if w is None else abi.dp(w), mode, abi.out_ptr(out))
+        _check(self.L, rc, "pdmpc_group_plan_step")
         del keep
         return out[:n]
 
     def pack_step(self, bank, iters, predecessors, fallback_shapes=None, weights=None, mode=SHARD_AUTO):
         """Make a step resident on the devices (group bank `bank`); launch(bank) plans it, fetch(bank, n) reads the records."""
         n = len(iters)
-        arr, off, idx, fb, keep = Handle._step_args(self, iters, predecessors, fallback_shapes)
+        arr, off, idx, fb, keep = _step_args(self.Hp, iters, predecessors, fallback_shapes)
         w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
-        self.L.pdmpc_group_pack_step.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, abi.c_int32_p, abi.c_int32_p, C.c_void_p, abi.c_double_p, C.c_int32]
-        _check(self.L, self.L.pdmpc_group_pack_step(self.g, bank, n, arr, off.ctypes.data_as(abi.c_int32_p), idx.ctypes.data_as(abi.c_int32_p), fb,
-                                                    None if w is None else w.ctypes.data_as(abi.c_double_p), mode), "pdmpc_group_pack_step")
+        rc = self.L.pdmpc_group_pack_step(self.g, bank, n, arr, abi.i32p(off), abi.i32p(idx), fb, None if w is None else abi.dp(w), mode)
+        _check(self.L, rc, "pdmpc_group_pack_step")
         del keep
 
     def grow_arena(self, max_nodes):
         """Arenas of at least max_nodes nodes per vehicle on every device (the resident path does not grow them by itself)."""
-        self.L.pdmpc_group_grow_arena.argtypes = [C.c_void_p, C.c_int32]
         _check(self.L, self.L.pdmpc_group_grow_arena(self.g, int(max_nodes)), "pdmpc_group_grow_arena")
 
     def launch(self, bank):
-        self.L.pdmpc_group_launch.argtypes = [C.c_void_p, C.c_int32]
         _check(self.L, self.L.pdmpc_group_launch(self.g, bank), "pdmpc_group_launch")
 
     def fetch(self, bank, n):
         out = abi.out_array(n)
-        self.L.pdmpc_group_fetch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         _check(self.L, self.L.pdmpc_group_fetch(self.g, bank, n, abi.out_ptr(out)), "pdmpc_group_fetch")
         return out[:n]
 
     def timing(self):
         t = (C.c_double * 6)()
-        self.L.pdmpc_group_last_timing.argtypes = [C.c_void_p, C.c_void_p]
         _check(self.L, self.L.pdmpc_group_last_timing(self.g, t), "pdmpc_group_last_timing")
         return dict(zip(("total", "partition", "pack", "enqueue", "wait", "read_back"), t))
 
     def reset_stats(self):
         for r in range(self.n_devices):
             h = C.c_void_p()
-            self.L.pdmpc_group_handle.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
             _check(self.L, self.L.pdmpc_group_handle(self.g, r, C.byref(h)), "pdmpc_group_handle")
             _check(self.L, self.L.pdmpc_reset_stats(h), "pdmpc_reset_stats")
 
@@ -782,7 +552,6 @@ class Group:
 
     def stats(self, rank=0):
         h = C.c_void_p()
-        self.L.pdmpc_group_handle.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         _check(self.L, self.L.pdmpc_group_handle(self.g, rank, C.byref(h)), "pdmpc_group_handle")
         st = abi.Stats()
         _check(self.L, self.L.pdmpc_get_last_stats(h, C.byref(st)), "pdmpc_get_last_stats")
@@ -851,14 +620,10 @@ class Handle:
         """A whole time step of the sampled optimizer in one call (pdmpc_plan_step_sampled): arguments as for plan_step, seeds[i] =
         time_step + vehicle_index of vehicle i (MonteCarloTreeSearch.m:32)."""
         n = len(iters)
-        arr, off, idx, fb, keep = self._step_args(iters, predecessors, fallback_shapes)
+        arr, off, idx, fb, keep = _step_args(self.Hp, iters, predecessors, fallback_shapes)
         out = abi.out_array(n)
         sd = (C.c_uint32 * max(n, 1))(*[int(s) for s in seeds])
-        _check(
-            self.L,
-            self.L.pdmpc_plan_step_sampled(self.h, n, arr, off.ctypes.data_as(abi.c_int32_p), idx.ctypes.data_as(abi.c_int32_p), fb, sd, abi.out_ptr(out)),
-            "pdmpc_plan_step_sampled",
-        )
+        _check(self.L, self.L.pdmpc_plan_step_sampled(self.h, n, arr, abi.i32p(off), abi.i32p(idx), fb, sd, abi.out_ptr(out)), "pdmpc_plan_step_sampled")
         del keep
         return self._checked(out[:n])
 
@@ -871,7 +636,7 @@ class Handle:
         """The sampled kernel's device generator on its own (pdmpc_debug_random_numbers) -> (len(seeds), n) doubles."""
         sd = (C.c_uint32 * max(len(seeds), 1))(*[int(s) for s in seeds])
         out = np.zeros(max(len(seeds) * n, 1))
-        _check(self.L, self.L.pdmpc_debug_random_numbers(self.h, len(seeds), sd, int(n), out.ctypes.data_as(abi.c_double_p)), "pdmpc_debug_random_numbers")
+        _check(self.L, self.L.pdmpc_debug_random_numbers(self.h, len(seeds), sd, int(n), abi.dp(out)), "pdmpc_debug_random_numbers")
         return out[: len(seeds) * n].reshape(len(seeds), n)
 
     def plan_joint(self, problems):
@@ -884,7 +649,7 @@ class Handle:
         n = len(iters)
         arr, keep = abi.pack_vehicles(iters, self.Hp)
         out = abi.out_array(n)
-        _check(self.L, self.L.pdmpc_plan_joint(self.h, len(problems), off.ctypes.data_as(abi.c_int32_p), arr, abi.out_ptr(out)), "pdmpc_plan_joint")
+        _check(self.L, self.L.pdmpc_plan_joint(self.h, len(problems), abi.i32p(off), arr, abi.out_ptr(out)), "pdmpc_plan_joint")
         del keep
         return self._checked(out[:n])
 
@@ -910,7 +675,7 @@ class Handle:
         n = getattr(self, "_bound_n", 0)
         adj = np.zeros(max(n * n, 1), dtype=np.uint8)
         area = np.zeros(max(n * n, 1), dtype=np.float64)
-        _check(self.L, self.L.pdmpc_bounded_set_coupling(self.h, adj.ctypes.data_as(abi.c_uint8_p), area.ctypes.data_as(abi.c_double_p)), "pdmpc_bounded_set_coupling")
+        _check(self.L, self.L.pdmpc_bounded_set_coupling(self.h, abi.u8p(adj), abi.dp(area)), "pdmpc_bounded_set_coupling")
         return adj[: n * n].reshape(n, n), area[: n * n].reshape(n, n)
 
     def reachable_set_coupling_grouped(self, group_sizes, x, y, yaw, trim):
@@ -923,14 +688,14 @@ class Handle:
         `group_sizes` vehicles -> [(adjacency, areas) per group]."""
         off = _group_offsets(group_sizes)
         adj, area, blocks = _grouped_out(group_sizes)
-        _check(self.L, self.L.pdmpc_bounded_set_coupling_grouped(self.h, len(group_sizes), off.ctypes.data_as(abi.c_int32_p), adj.ctypes.data_as(abi.c_uint8_p),
-                                                                 area.ctypes.data_as(abi.c_double_p)), "pdmpc_bounded_set_coupling_grouped")
+        rc = self.L.pdmpc_bounded_set_coupling_grouped(self.h, len(group_sizes), abi.i32p(off), abi.u8p(adj), abi.dp(area))
+        _check(self.L, rc, "pdmpc_bounded_set_coupling_grouped")
         return blocks()
 
     def bounded_reachable_kernel_ms(self):
         """kernel times (ms) of the last bound_reachable_sets and bounded_set_coupling"""
         ms = np.zeros(2)
-        _check(self.L, self.L.pdmpc_bounded_reachable_kernel_ms(self.h, ms.ctypes.data_as(abi.c_double_p)), "pdmpc_bounded_reachable_kernel_ms")
+        _check(self.L, self.L.pdmpc_bounded_reachable_kernel_ms(self.h, abi.dp(ms)), "pdmpc_bounded_reachable_kernel_ms")
         return float(ms[0]), float(ms[1])
 
     def fca_collisions(self, reference_points, pairs, length, width, offset, obstacles=(), dynamic_obstacle_area=(), headings=None):
@@ -965,59 +730,32 @@ class Handle:
     def set_step_weights(self, weights):
         """Expected work per vehicle of the next packed step (pdmpc_set_step_weights): its searches go out by priority, not slot order."""
         w = np.ascontiguousarray(weights, dtype=np.float64)
-        self.L.pdmpc_set_step_weights.argtypes = [C.c_void_p, C.c_int32, abi.c_double_p]
-        _check(self.L, self.L.pdmpc_set_step_weights(self.h, len(w), w.ctypes.data_as(abi.c_double_p)), "pdmpc_set_step_weights")
+        _check(self.L, self.L.pdmpc_set_step_weights(self.h, len(w), abi.dp(w)), "pdmpc_set_step_weights")
 
     def pack_step(self, iters, predecessors, fallback_shapes=None, weights=None):
         """predecessors: list (per vehicle) of lists of 0-based vehicle indices in this batch."""
         n = len(iters)
-        arr, off, idx, fb, keep = self._step_args(iters, predecessors, fallback_shapes)
+        arr, off, idx, fb, keep = _step_args(self.Hp, iters, predecessors, fallback_shapes)
         if weights is not None:
             self.set_step_weights(weights)
-        _check(
-            self.L,
-            self.L.pdmpc_pack_step(self.h, n, arr, off.ctypes.data_as(abi.c_int32_p), idx.ctypes.data_as(abi.c_int32_p), fb),
-            "pdmpc_pack_step",
-        )
+        _check(self.L, self.L.pdmpc_pack_step(self.h, n, arr, abi.i32p(off), abi.i32p(idx), fb), "pdmpc_pack_step")
         del keep
-
-    def _step_args(self, iters, predecessors, fallback_shapes):
-        n = len(iters)
-        arr, keep = abi.pack_vehicles(iters, self.Hp)
-        off = np.zeros(n + 1, dtype=np.int32)
-        for i, p in enumerate(predecessors):
-            off[i + 1] = off[i] + len(p)
-        idx = np.array([j for p in predecessors for j in p] + [0], dtype=np.int32)
-        fb = None
-        if fallback_shapes is not None:
-            fb = (abi.PolygonSet * n)()
-            for i, shapes in enumerate(fallback_shapes):
-                fb[i] = abi.pack_polygon_set(list(shapes), keep)
-        return arr, off, idx, fb, keep
 
     def plan_step(self, iters, predecessors, fallback_shapes=None, weights=None):
         """A whole time step in one call (pdmpc_plan_step): pack + launch + fetch, arenas grow if a search needs it."""
         n = len(iters)
-        arr, off, idx, fb, keep = self._step_args(iters, predecessors, fallback_shapes)
+        arr, off, idx, fb, keep = _step_args(self.Hp, iters, predecessors, fallback_shapes)
         out = abi.out_array(n)
         if weights is not None:
             self.set_step_weights(weights)
-        _check(
-            self.L,
-            self.L.pdmpc_plan_step(self.h, n, arr, off.ctypes.data_as(abi.c_int32_p), idx.ctypes.data_as(abi.c_int32_p), fb, abi.out_ptr(out)),
-            "pdmpc_plan_step",
-        )
+        _check(self.L, self.L.pdmpc_plan_step(self.h, n, arr, abi.i32p(off), abi.i32p(idx), fb, abi.out_ptr(out)), "pdmpc_plan_step")
         del keep
         return self._checked(out[:n])
 
     def _choice_call(self, what, call, choice):
         chosen, cost, picks = choice.outputs()
         ch = choice.struct()
-        rc = call(C.byref(ch), chosen.ctypes.data_as(abi.c_int32_p), cost.ctypes.data_as(abi.c_double_p), abi.out_ptr(picks))
-        if rc != 0:
-            err = BackendError("%s failed with status %d: %s" % (what, rc, (self.L.pdmpc_last_error() or b"").decode()))
-            err.status = rc
-            raise err
+        _check(self.L, call(C.byref(ch), abi.i32p(chosen), abi.dp(cost), abi.out_ptr(picks)), what)
         return choice.shaped(chosen, cost, picks)
 
     def choose_resident(self, n, choice):
@@ -1027,12 +765,10 @@ class Handle:
     def plan_step_chosen(self, iters, predecessors, fallback_shapes, choice, weights=None):
         """pdmpc_plan_step_chosen: pack, ONE launch of the searches, the choice on the device, one read-back -> (chosen, cell costs, picked records)."""
         n = len(iters)
-        arr, off, idx, fb, keep = self._step_args(iters, predecessors, fallback_shapes)
+        arr, off, idx, fb, keep = _step_args(self.Hp, iters, predecessors, fallback_shapes)
         if weights is not None:
             self.set_step_weights(weights)
-        out = self._choice_call(
-            "pdmpc_plan_step_chosen",
-            lambda *tail: self.L.pdmpc_plan_step_chosen(self.h, n, arr, off.ctypes.data_as(abi.c_int32_p), idx.ctypes.data_as(abi.c_int32_p), fb, *tail), choice)
+        out = self._choice_call("pdmpc_plan_step_chosen", lambda *tail: self.L.pdmpc_plan_step_chosen(self.h, n, arr, abi.i32p(off), abi.i32p(idx), fb, *tail), choice)
         del keep
         return out
 
@@ -1045,7 +781,7 @@ class Handle:
     def step_args(self, iters, predecessors, fallback_shapes=None):
         """The marshalled arguments of pdmpc_plan_step / pdmpc_plan_step_literal, reusable across calls (bench.py times the calls,
         not the Python marshalling): (n, vehicle array, pred_offset, pred_index, fallback sets, keep-alive)."""
-        arr, off, idx, fb, keep = self._step_args(iters, predecessors, fallback_shapes)
+        arr, off, idx, fb, keep = _step_args(self.Hp, iters, predecessors, fallback_shapes)
         return len(iters), arr, off, idx, fb, keep
 
     def plan_step_literal(self, args):
@@ -1053,11 +789,7 @@ class Handle:
         gives an unmodified controller (pdmpc_plan_step_literal).  args = step_args(...)."""
         n, arr, off, idx, fb, _ = args
         out = abi.out_array(n)
-        _check(
-            self.L,
-            self.L.pdmpc_plan_step_literal(self.h, n, arr, off.ctypes.data_as(abi.c_int32_p), idx.ctypes.data_as(abi.c_int32_p), fb, abi.out_ptr(out)),
-            "pdmpc_plan_step_literal",
-        )
+        _check(self.L, self.L.pdmpc_plan_step_literal(self.h, n, arr, abi.i32p(off), abi.i32p(idx), fb, abi.out_ptr(out)), "pdmpc_plan_step_literal")
         return self._checked(out[:n])
 
     def _checked(self, recs):
@@ -1141,18 +873,14 @@ class Handle:
         out = np.zeros(max(len(ops), 1), dtype=np.int32)
         n = C.c_int32()
         cp, cq = C.c_double(), C.c_double()
-        _check(
-            self.L,
-            self.L.pdmpc_debug_heap_script(self.h, len(ops), ops.ctypes.data_as(abi.c_int32_p), ids.ctypes.data_as(abi.c_int32_p), keys.ctypes.data_as(abi.c_double_p),
-                                           lds_entries, out.ctypes.data_as(abi.c_int32_p), C.byref(n), C.byref(cp), C.byref(cq)),
-            "pdmpc_debug_heap_script",
-        )
+        rc = self.L.pdmpc_debug_heap_script(self.h, len(ops), abi.i32p(ops), abi.i32p(ids), abi.dp(keys), lds_entries, abi.i32p(out), C.byref(n), C.byref(cp), C.byref(cq))
+        _check(self.L, rc, "pdmpc_debug_heap_script")
         return out[: n.value].copy(), cp.value, cq.value
 
     def pop_trace(self, vehicle, capacity=1 << 16):
         ids = np.zeros(capacity, dtype=np.int32)
         n = C.c_int32()
-        _check(self.L, self.L.pdmpc_debug_pop_trace(self.h, vehicle, capacity, ids.ctypes.data_as(abi.c_int32_p), C.byref(n)), "pdmpc_debug_pop_trace")
+        _check(self.L, self.L.pdmpc_debug_pop_trace(self.h, vehicle, capacity, abi.i32p(ids), C.byref(n)), "pdmpc_debug_pop_trace")
         return ids[: min(n.value, capacity)].copy()
 
     def raw_tree(self, vehicle, capacity=1 << 20):
@@ -1161,8 +889,8 @@ class Handle:
         i = {k: np.zeros(capacity, dtype=np.int32) for k in ("trim", "k", "parent")}
         val = np.zeros(capacity, dtype=np.uint8)
         n = C.c_int32()
-        args = [f[k].ctypes.data_as(abi.c_double_p) for k in ("x", "y", "yaw", "g", "h")] + [i[k].ctypes.data_as(abi.c_int32_p) for k in ("trim", "k", "parent")]
-        args += [f["key"].ctypes.data_as(abi.c_double_p), val.ctypes.data_as(abi.c_uint8_p)]
+        args = [abi.dp(f[k]) for k in ("x", "y", "yaw", "g", "h")] + [abi.i32p(i[k]) for k in ("trim", "k", "parent")]
+        args += [abi.dp(f["key"]), abi.u8p(val)]
         _check(self.L, self.L.pdmpc_debug_raw_tree(self.h, vehicle, capacity, *args, C.byref(n)), "pdmpc_debug_raw_tree")
         nn = min(n.value, capacity)
         d = {k: v[:nn].copy() for k, v in f.items()}
@@ -1184,17 +912,12 @@ class Handle:
         ao, ax, ay = flat(a_list)
         bo, bx, by = flat(b_list)
         hit = np.zeros(max(n, 1), dtype=np.int32)
-        _check(
-            self.L,
-            self.L.pdmpc_debug_edge_check(self.h, mode, n, ao.ctypes.data_as(abi.c_int32_p), ax.ctypes.data_as(abi.c_double_p), ay.ctypes.data_as(abi.c_double_p),
-                                          bo.ctypes.data_as(abi.c_int32_p), bx.ctypes.data_as(abi.c_double_p), by.ctypes.data_as(abi.c_double_p), hit.ctypes.data_as(abi.c_int32_p)),
-            "pdmpc_debug_edge_check",
-        )
+        rc = self.L.pdmpc_debug_edge_check(self.h, mode, n, abi.i32p(ao), abi.dp(ax), abi.dp(ay), abi.i32p(bo), abi.dp(bx), abi.dp(by), abi.i32p(hit))
+        _check(self.L, rc, "pdmpc_debug_edge_check")
         return hit[:n] != 0
 
     def debug_counters(self):
         out = (C.c_uint64 * 16)()
-        self.L.pdmpc_debug_counters.argtypes = [C.c_void_p, C.c_void_p]
         _check(self.L, self.L.pdmpc_debug_counters(self.h, out), "pdmpc_debug_counters")
         return list(out)
 
@@ -1207,7 +930,7 @@ class Handle:
         f = {k: np.zeros(capacity) for k in ("x", "y", "yaw", "g", "h")}
         i = {k: np.zeros(capacity, dtype=np.int32) for k in ("trim", "k", "parent")}
         n = C.c_int32()
-        args = [f[k].ctypes.data_as(abi.c_double_p) for k in ("x", "y", "yaw", "g", "h")] + [i[k].ctypes.data_as(abi.c_int32_p) for k in ("trim", "k", "parent")]
+        args = [abi.dp(f[k]) for k in ("x", "y", "yaw", "g", "h")] + [abi.i32p(i[k]) for k in ("trim", "k", "parent")]
         _check(self.L, self.L.pdmpc_debug_tree(self.h, vehicle, capacity, *args, C.byref(n)), "pdmpc_debug_tree")
         nn = min(n.value, capacity)
         d = {k: v[:nn].copy() for k, v in f.items()}

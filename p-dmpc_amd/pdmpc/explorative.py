@@ -77,14 +77,11 @@ def computation_level_permutations(n_levels, n_perm, seed):
 
 def native_computation_level_permutations(n_levels, n_perm, seed):
     """The same table from libpdmpc_hip.so (pdmpc_exploration_permutations, csrc/step_controller.cpp): the native twin."""
-    import ctypes as C
-
-    from . import backend
+    from . import abi, backend
 
     L = backend.load_library()
-    L.pdmpc_exploration_permutations.argtypes = [C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_int32)]
     out = np.zeros((n_perm, n_levels), dtype=np.int32)
-    rc = L.pdmpc_exploration_permutations(n_levels, n_perm, int(seed), out.ctypes.data_as(C.POINTER(C.c_int32)))
+    rc = L.pdmpc_exploration_permutations(n_levels, n_perm, int(seed), abi.i32p(out))
     if rc != 0:
         raise backend.BackendError("pdmpc_exploration_permutations failed: %d" % rc)
     return out.astype(np.int64)

@@ -10,7 +10,9 @@ import ctypes as C
 import numpy as np
 
 from . import abi
-from .backend import BackendError, load_library
+from .abi import ControllerConfig, ScenarioStruct  # noqa: F401  (their home; importable from here as before)
+from .backend import BackendError  # noqa: F401  (importable from here as before)
+from .backend import _check, load_library
 from .config import ConstraintFromSuccessor
 
 COUPLING = {"full": 0, "distance": 1, "none": 2, "reachable_set": 3}
@@ -21,86 +23,14 @@ OPTIMIZER = {"graph_search": 0, "sampled": 1}  # PDMPC_OPTIMIZER_*
 SUCCESSOR = {ConstraintFromSuccessor.none: 0, ConstraintFromSuccessor.area_of_standstill: 1, ConstraintFromSuccessor.area_of_previous_trajectory: 2}
 
 
-class ControllerConfig(C.Structure):
-    _fields_ = [
-        ("Hp", C.c_int32), ("coupling", C.c_int32), ("priority_strategy", C.c_int32), ("weight_strategy", C.c_int32), ("max_num_CLs", C.c_int32),
-        ("constraint_from_successor", C.c_int32), ("dt_seconds", C.c_double), ("offset", C.c_double), ("vehicle_length", C.c_double), ("vehicle_width", C.c_double),
-    ]
+TIMING_PARTS = ("build", "pack", "enqueue", "wait_and_read_back", "choose", "apply")  # pdmpc_controller_last_timing, pdmpc_sweep_last_timing
 
 
-class ScenarioStruct(C.Structure):
-    _fields_ = [
-        ("n_vehicles", C.c_int32),
-        ("x_start", abi.c_double_p), ("y_start", abi.c_double_p), ("yaw_start", abi.c_double_p), ("reference_speed", abi.c_double_p),
-        ("path_offset", abi.c_int32_p), ("path_x", abi.c_double_p), ("path_y", abi.c_double_p),
-        ("lanelets_offset", abi.c_int32_p), ("lanelets_index", abi.c_int32_p), ("points_index", abi.c_int32_p), ("is_loop", abi.c_int32_p),
-        ("tile_dx", abi.c_double_p), ("tile_dy", abi.c_double_p),
-        ("n_lanelets", C.c_int32), ("left_offset", abi.c_int32_p), ("right_offset", abi.c_int32_p),
-        ("left_x", abi.c_double_p), ("left_y", abi.c_double_p), ("right_x", abi.c_double_p), ("right_y", abi.c_double_p),
-        ("obstacles", abi.PolygonSet),
-        ("n_trims", C.c_int32), ("trim_speed", abi.c_double_p), ("trim_steering", abi.c_double_p),
-    ]
-
-
-def _declare(L):
-    H = C.c_void_p
-    if getattr(L, "_controller_declared", False):
-        return L
-    L.pdmpc_controller_create.argtypes = [H, C.POINTER(ControllerConfig), C.POINTER(ScenarioStruct), C.POINTER(H)]
-    L.pdmpc_controller_destroy.argtypes = [H]
-    L.pdmpc_controller_step.argtypes = [H]
-    L.pdmpc_controller_run.argtypes = [H, C.c_int32, abi.c_double_p]
-    L.pdmpc_controller_run.restype = C.c_int
-    L.pdmpc_controller_build_step.argtypes = [H]
-    L.pdmpc_controller_apply.argtypes = [H, C.POINTER(abi.VehicleOut)]
-    L.pdmpc_controller_problem.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.POINTER(abi.VehicleIn)), C.POINTER(abi.c_int32_p), C.POINTER(abi.c_int32_p),
-                                           C.POINTER(C.POINTER(abi.PolygonSet)), C.POINTER(abi.c_int32_p), C.POINTER(abi.c_int32_p)]
-    L.pdmpc_controller_state.argtypes = [H] + [abi.c_double_p] * 5 + [abi.c_int32_p, C.POINTER(C.c_int32)]
-    L.pdmpc_controller_records.argtypes = [H]
-    L.pdmpc_controller_records.restype = C.POINTER(abi.VehicleOut)
-    L.pdmpc_controller_last_error.restype = C.c_char_p
-    L.pdmpc_controller_explore_build.argtypes = [H, C.c_int32, C.c_uint32]
-    L.pdmpc_controller_explore_problem.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.POINTER(abi.VehicleIn)), C.POINTER(abi.c_int32_p), C.POINTER(abi.c_int32_p),
-                                                   C.POINTER(C.POINTER(abi.PolygonSet)), C.POINTER(abi.c_int32_p), C.POINTER(abi.c_int32_p), C.POINTER(abi.c_int32_p)]
-    L.pdmpc_controller_explore_choose.argtypes = [H, C.POINTER(abi.VehicleOut), abi.c_int32_p, C.POINTER(C.c_int32), abi.c_double_p]
-    L.pdmpc_controller_explore_step.argtypes = [H, C.c_int32]
-    L.pdmpc_controller_explore_run.argtypes = [H, C.c_int32, C.c_int32, abi.c_double_p]
-    L.pdmpc_controller_explore_result.argtypes = [H, abi.c_int32_p, C.POINTER(C.c_int32), C.POINTER(abi.c_double_p), C.POINTER(C.POINTER(abi.VehicleOut))]
-    L.pdmpc_controller_optimal_build.argtypes = [H, C.c_int32]
-    L.pdmpc_controller_optimal_choose.argtypes = [H, C.POINTER(abi.VehicleOut), abi.c_int32_p, abi.c_double_p]
-    L.pdmpc_controller_optimal_step.argtypes = [H, C.c_int32]
-    L.pdmpc_controller_optimal_run.argtypes = [H, C.c_int32, C.c_int32, abi.c_double_p]
-    L.pdmpc_controller_optimal_result.argtypes = [H, abi.c_int32_p, C.POINTER(C.c_int32), C.POINTER(abi.c_double_p), C.POINTER(C.POINTER(abi.VehicleOut))]
-    for name in ("pdmpc_controller_explore_build", "pdmpc_controller_explore_problem", "pdmpc_controller_explore_choose", "pdmpc_controller_explore_step",
-                 "pdmpc_controller_explore_run", "pdmpc_controller_explore_result", "pdmpc_controller_optimal_build", "pdmpc_controller_optimal_choose",
-                 "pdmpc_controller_optimal_step", "pdmpc_controller_optimal_run", "pdmpc_controller_optimal_result"):
-        getattr(L, name).restype = C.c_int
-    for name in ("pdmpc_controller_create", "pdmpc_controller_destroy", "pdmpc_controller_step", "pdmpc_controller_build_step", "pdmpc_controller_apply",
-                 "pdmpc_controller_problem", "pdmpc_controller_state"):
-        getattr(L, name).restype = C.c_int
-    L.pdmpc_sweep_create.argtypes = [H, C.c_int32, C.POINTER(H), C.POINTER(H)]
-    L.pdmpc_sweep_destroy.argtypes = [H]
-    L.pdmpc_sweep_build.argtypes = [H]
-    L.pdmpc_sweep_problem.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.POINTER(abi.VehicleIn)), C.POINTER(abi.c_int32_p), C.POINTER(abi.c_int32_p),
-                                      C.POINTER(C.POINTER(abi.PolygonSet)), C.POINTER(abi.c_int32_p), C.POINTER(abi.c_int32_p)]
-    L.pdmpc_sweep_apply.argtypes = [H, C.POINTER(abi.VehicleOut)]
-    L.pdmpc_sweep_step.argtypes = [H]
-    L.pdmpc_sweep_run.argtypes = [H, C.c_int32, abi.c_double_p]
-    L.pdmpc_sweep_last_timing.argtypes = [H, C.c_void_p]
-    L.pdmpc_sweep_last_prep_calls.argtypes = [H, abi.c_int32_p]
-    L.pdmpc_sweep_explore_build.argtypes = [H, C.c_int32]
-    L.pdmpc_sweep_explore_problem.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.POINTER(abi.VehicleIn)), C.POINTER(abi.c_int32_p), C.POINTER(abi.c_int32_p),
-                                              C.POINTER(C.POINTER(abi.PolygonSet))] + [C.POINTER(abi.c_int32_p)] * 4
-    L.pdmpc_sweep_explore_apply.argtypes = [H, C.POINTER(abi.VehicleOut)]
-    L.pdmpc_sweep_explore_step.argtypes = [H, C.c_int32]
-    L.pdmpc_sweep_explore_run.argtypes = [H, C.c_int32, C.c_int32, abi.c_double_p]
-    L.pdmpc_controller_set_device_choice.argtypes = [H, C.c_int32]
-    for name in ("pdmpc_sweep_create", "pdmpc_sweep_destroy", "pdmpc_sweep_build", "pdmpc_sweep_problem", "pdmpc_sweep_apply", "pdmpc_sweep_step", "pdmpc_sweep_run",
-                 "pdmpc_sweep_last_timing", "pdmpc_sweep_last_prep_calls", "pdmpc_sweep_explore_build", "pdmpc_sweep_explore_problem", "pdmpc_sweep_explore_apply", "pdmpc_sweep_explore_step",
-                 "pdmpc_sweep_explore_run", "pdmpc_controller_set_device_choice"):
-        getattr(L, name).restype = C.c_int
-    L._controller_declared = True
-    return L
+def _run(check, what, fn, obj, *counts):
+    """An n_steps call `fn` (n_steps: the last count) -> wall-clock milliseconds of every step."""
+    ms = np.zeros(max(counts[-1], 1))
+    check(fn(obj, *counts, abi.dp(ms)), what)
+    return ms[: counts[-1]]
 
 
 def _flat(arrays, dtype):
@@ -124,7 +54,7 @@ class NativeController:
     def __init__(self, options, scenario, mpa, handle=None, coupling="full", priority_strategy="constant", weight_strategy="distance", optimizer="graph_search"):
         if scenario.dynamic_obstacle_area:
             raise ValueError("the native controller takes static scenario obstacles only")
-        self.L = _declare(load_library())
+        self.L = load_library()
         self.options, self.mpa, self.n, self.Hp = options, mpa, options.amount, options.Hp
         veh = scenario.vehicles
         keep = []
@@ -132,12 +62,12 @@ class NativeController:
         def d(a):
             a = np.ascontiguousarray(a, dtype=np.float64)
             keep.append(a)
-            return a.ctypes.data_as(abi.c_double_p)
+            return abi.dp(a)
 
         def i32(a):
             a = np.ascontiguousarray(a, dtype=np.int32)
             keep.append(a)
-            return a.ctypes.data_as(abi.c_int32_p)
+            return abi.i32p(a)
 
         s = ScenarioStruct()
         s.n_vehicles = self.n
@@ -190,14 +120,10 @@ class NativeController:
 
     def set_optimizer(self, which):
         """"graph_search" (default) or "sampled" (pdmpc_controller_set_optimizer): what step / run, explore_* and optimal_* plan with."""
-        self.L.pdmpc_controller_set_optimizer.argtypes = [C.c_void_p, C.c_int32]
-        self.L.pdmpc_controller_set_optimizer.restype = C.c_int
         self._check(self.L.pdmpc_controller_set_optimizer(self.c, OPTIMIZER[which] if isinstance(which, str) else int(which)), "pdmpc_controller_set_optimizer")
 
     def seeds(self):
         """The sampled optimizer's seed per slot of the last built step or batch (pdmpc_controller_seeds)."""
-        self.L.pdmpc_controller_seeds.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.POINTER(C.c_uint32))]
-        self.L.pdmpc_controller_seeds.restype = C.c_int
         n = C.c_int32()
         p = C.POINTER(C.c_uint32)()
         self._check(self.L.pdmpc_controller_seeds(self.c, C.byref(n), C.byref(p)), "pdmpc_controller_seeds")
@@ -206,17 +132,13 @@ class NativeController:
     def priorities(self):
         """(priorities, collisions) of the last built step (pdmpc_controller_priorities): the 1-based priorities of a constant, random or
         FCA step and the collision counts of an FCA step; empty where the strategy has none."""
-        self.L.pdmpc_controller_priorities.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32), C.POINTER(abi.c_int32_p)] * 2
-        self.L.pdmpc_controller_priorities.restype = C.c_int
         n_p, n_c = C.c_int32(), C.c_int32()
         p, q = abi.c_int32_p(), abi.c_int32_p()
         self._check(self.L.pdmpc_controller_priorities(self.c, C.byref(n_p), C.byref(p), C.byref(n_c), C.byref(q)), "pdmpc_controller_priorities")
         return [int(p[i]) for i in range(n_p.value)], [int(q[i]) for i in range(n_c.value)]
 
     def _check(self, rc, what):
-        if rc != 0:
-            msg = self.L.pdmpc_controller_last_error()
-            raise BackendError("%s failed with status %d: %s" % (what, rc, msg.decode() if msg else ""))
+        _check(self.L, rc, what, "pdmpc_controller_last_error")
 
     def close(self):
         if self.c:
@@ -225,8 +147,7 @@ class NativeController:
 
     def records(self):
         """The records of the member's last step in its own slot order (pdmpc_controller_records), also after a sweep's step."""
-        p = self.L.pdmpc_controller_records(self.c)
-        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(self.n * abi.VEHICLE_OUT_DTYPE.itemsize,)).view(abi.VEHICLE_OUT_DTYPE).copy()
+        return abi.records_copy(self.L.pdmpc_controller_records(self.c), self.n)
 
     def __del__(self):
         try:
@@ -237,29 +158,24 @@ class NativeController:
     def step(self):
         """One whole MPC time step natively (build, one launch, apply); returns the records in slot order."""
         self._check(self.L.pdmpc_controller_step(self.c), "pdmpc_controller_step")
-        p = self.L.pdmpc_controller_records(self.c)
-        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(self.n * abi.VEHICLE_OUT_DTYPE.itemsize,)).view(abi.VEHICLE_OUT_DTYPE).copy()
+        return abi.records_copy(self.L.pdmpc_controller_records(self.c), self.n)
 
     def run(self, n_steps):
         """n_steps closed-loop steps in one native call -> wall-clock milliseconds of every step."""
-        ms = np.zeros(max(n_steps, 1))
-        self._check(self.L.pdmpc_controller_run(self.c, n_steps, ms.ctypes.data_as(abi.c_double_p)), "pdmpc_controller_run")
-        return ms[:n_steps]
+        return _run(self._check, "pdmpc_controller_run", self.L.pdmpc_controller_run, self.c, n_steps)
 
     def last_timing(self):
         """Host milliseconds of the last step by part (pdmpc_controller_last_timing)."""
         t = (C.c_double * 6)()
-        self.L.pdmpc_controller_last_timing.argtypes = [C.c_void_p, C.c_void_p]
         self._check(self.L.pdmpc_controller_last_timing(self.c, t), "pdmpc_controller_last_timing")
-        return dict(zip(("build", "pack", "enqueue", "wait_and_read_back", "choose", "apply"), (float(x) for x in t)))
+        return dict(zip(TIMING_PARTS, (float(x) for x in t)))
 
     def timing_mean(self, reset=True):
         """Mean host milliseconds per step by part over the steps since the last reset (pdmpc_controller_timing_sum)."""
         t = (C.c_double * 6)()
         k = C.c_int64(0)
-        self.L.pdmpc_controller_timing_sum.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
         self._check(self.L.pdmpc_controller_timing_sum(self.c, t, C.byref(k), 1 if reset else 0), "pdmpc_controller_timing_sum")
-        return dict(zip(("build", "pack", "enqueue", "wait_and_read_back", "choose", "apply"), (float(x) / max(k.value, 1) for x in t)))
+        return dict(zip(TIMING_PARTS, (float(x) / max(k.value, 1) for x in t)))
 
     def build_step(self):
         self._check(self.L.pdmpc_controller_build_step(self.c), "pdmpc_controller_build_step")
@@ -328,7 +244,7 @@ class NativeController:
         chosen = np.zeros(self.n, dtype=np.int32)
         g = C.c_int32()
         cost = np.zeros(self.n_perm * self.n)
-        self._check(self.L.pdmpc_controller_explore_choose(self.c, abi.out_ptr(recs), chosen.ctypes.data_as(abi.c_int32_p), C.byref(g), cost.ctypes.data_as(abi.c_double_p)),
+        self._check(self.L.pdmpc_controller_explore_choose(self.c, abi.out_ptr(recs), abi.i32p(chosen), C.byref(g), abi.dp(cost)),
                     "pdmpc_controller_explore_choose")
         return chosen, cost[: self.n_perm * g.value].reshape(self.n_perm, g.value)
 
@@ -338,12 +254,10 @@ class NativeController:
         self.n_perm = n_perm
         chosen = np.zeros(self.n, dtype=np.int32)
         p = C.POINTER(abi.VehicleOut)()
-        self._check(self.L.pdmpc_controller_explore_result(self.c, chosen.ctypes.data_as(abi.c_int32_p), None, None, C.byref(p)), "pdmpc_controller_explore_result")
-        recs = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(self.n * n_perm * abi.VEHICLE_OUT_DTYPE.itemsize,)).view(abi.VEHICLE_OUT_DTYPE).copy()
-        return recs, chosen
+        self._check(self.L.pdmpc_controller_explore_result(self.c, abi.i32p(chosen), None, None, C.byref(p)), "pdmpc_controller_explore_result")
+        return abi.records_copy(p, self.n * n_perm), chosen
 
     def explore_follow_own(self, on=True):
-        self.L.pdmpc_controller_explore_follow_own.argtypes = [C.c_void_p, C.c_int32]
         self._check(self.L.pdmpc_controller_explore_follow_own(self.c, 1 if on else 0), "pdmpc_controller_explore_follow_own")
 
     def set_device_choice(self, on=True):
@@ -355,7 +269,7 @@ class NativeController:
         chosen = np.zeros(self.n, dtype=np.int32)
         g = C.c_int32()
         cost = abi.c_double_p()
-        self._check(self.L.pdmpc_controller_explore_result(self.c, chosen.ctypes.data_as(abi.c_int32_p), C.byref(g), C.byref(cost), None), "pdmpc_controller_explore_result")
+        self._check(self.L.pdmpc_controller_explore_result(self.c, abi.i32p(chosen), C.byref(g), C.byref(cost), None), "pdmpc_controller_explore_result")
         return chosen, np.array([cost[q] for q in range(self.n_perm * g.value)]).reshape(self.n_perm, g.value)
 
     def optimal_result(self):
@@ -363,14 +277,12 @@ class NativeController:
         chosen = np.zeros(self.n, dtype=np.int32)
         k = C.c_int32()
         cost = abi.c_double_p()
-        self._check(self.L.pdmpc_controller_optimal_result(self.c, chosen.ctypes.data_as(abi.c_int32_p), C.byref(k), C.byref(cost), None), "pdmpc_controller_optimal_result")
+        self._check(self.L.pdmpc_controller_optimal_result(self.c, abi.i32p(chosen), C.byref(k), C.byref(cost), None), "pdmpc_controller_optimal_result")
         return chosen, np.array([cost[q] for q in range(self.n * k.value)]).reshape(self.n, k.value)
 
     def explore_run(self, n_perm, n_steps):
         self.n_perm = n_perm
-        ms = np.zeros(max(n_steps, 1))
-        self._check(self.L.pdmpc_controller_explore_run(self.c, n_perm, n_steps, ms.ctypes.data_as(abi.c_double_p)), "pdmpc_controller_explore_run")
-        return ms[:n_steps]
+        return _run(self._check, "pdmpc_controller_explore_run", self.L.pdmpc_controller_explore_run, self.c, n_perm, n_steps)
 
     # ---- the optimal-priority step: twin of pdmpc.optimal
     def optimal_build(self, max_instances):
@@ -390,7 +302,7 @@ class NativeController:
         recs = np.ascontiguousarray(records)
         chosen = np.zeros(self.n, dtype=np.int32)
         cost = np.zeros(self.n * self.n_perm)
-        self._check(self.L.pdmpc_controller_optimal_choose(self.c, abi.out_ptr(recs), chosen.ctypes.data_as(abi.c_int32_p), cost.ctypes.data_as(abi.c_double_p)),
+        self._check(self.L.pdmpc_controller_optimal_choose(self.c, abi.out_ptr(recs), abi.i32p(chosen), abi.dp(cost)),
                     "pdmpc_controller_optimal_choose")
         return chosen, cost.reshape(self.n, self.n_perm)
 
@@ -400,23 +312,20 @@ class NativeController:
         chosen = np.zeros(self.n, dtype=np.int32)
         k = C.c_int32()
         p = C.POINTER(abi.VehicleOut)()
-        self._check(self.L.pdmpc_controller_optimal_result(self.c, chosen.ctypes.data_as(abi.c_int32_p), C.byref(k), None, C.byref(p)), "pdmpc_controller_optimal_result")
+        self._check(self.L.pdmpc_controller_optimal_result(self.c, abi.i32p(chosen), C.byref(k), None, C.byref(p)), "pdmpc_controller_optimal_result")
         self.n_perm = k.value
-        recs = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(self.n * k.value * abi.VEHICLE_OUT_DTYPE.itemsize,)).view(abi.VEHICLE_OUT_DTYPE).copy()
-        return recs, chosen
+        return abi.records_copy(p, self.n * k.value), chosen
 
     def optimal_run(self, max_instances, n_steps):
         """n_steps optimal-priority steps in one native call (status + final cost of every plan, the chosen records only) -> ms per step."""
-        ms = np.zeros(max(n_steps, 1))
-        self._check(self.L.pdmpc_controller_optimal_run(self.c, max_instances, n_steps, ms.ctypes.data_as(abi.c_double_p)), "pdmpc_controller_optimal_run")
-        return ms[:n_steps]
+        return _run(self._check, "pdmpc_controller_optimal_run", self.L.pdmpc_controller_optimal_run, self.c, max_instances, n_steps)
 
     def state(self):
         n = self.n
         arr = [np.zeros(n) for _ in range(5)]
         nf = np.zeros(n, dtype=np.int32)
         k = C.c_int32()
-        self._check(self.L.pdmpc_controller_state(self.c, *[a.ctypes.data_as(abi.c_double_p) for a in arr], nf.ctypes.data_as(abi.c_int32_p), C.byref(k)), "pdmpc_controller_state")
+        self._check(self.L.pdmpc_controller_state(self.c, *[abi.dp(a) for a in arr], abi.i32p(nf), C.byref(k)), "pdmpc_controller_state")
         return {"x": arr[0], "y": arr[1], "yaw": arr[2], "speed": arr[3], "steering": arr[4], "needs_fallback": nf != 0, "k": k.value}
 
 
@@ -429,7 +338,7 @@ class NativeSweep:
     def __init__(self, members, handle=None):
         self.members = list(members)
         self.handle = handle
-        self.L = _declare(load_library())
+        self.L = load_library()
         self.n = sum(m.n for m in self.members)
         self.s = C.c_void_p()
         arr = (C.c_void_p * max(len(self.members), 1))(*[m.c for m in self.members])
@@ -437,11 +346,7 @@ class NativeSweep:
         self._check(rc, "pdmpc_sweep_create")
 
     def _check(self, rc, what):
-        if rc != 0:
-            msg = self.L.pdmpc_controller_last_error()
-            err = BackendError("%s failed with status %d: %s" % (what, rc, msg.decode() if msg else ""))
-            err.status = rc
-            raise err
+        _check(self.L, rc, what, "pdmpc_controller_last_error")
 
     def close(self):
         if self.s:
@@ -482,9 +387,7 @@ class NativeSweep:
 
     def run(self, n_steps):
         """n_steps lock-steps in one native call -> wall-clock milliseconds of every lock-step."""
-        ms = np.zeros(max(n_steps, 1))
-        self._check(self.L.pdmpc_sweep_run(self.s, n_steps, ms.ctypes.data_as(abi.c_double_p)), "pdmpc_sweep_run")
-        return ms[:n_steps]
+        return _run(self._check, "pdmpc_sweep_run", self.L.pdmpc_sweep_run, self.s, n_steps)
 
     # ---- the explorative step of a sweep (DESIGN.md §3.21)
     def explore_build(self, n_perm):
@@ -524,20 +427,19 @@ class NativeSweep:
 
     def explore_run(self, n_perm, n_steps):
         """n_steps explorative lock-steps in one native call -> wall-clock milliseconds of every lock-step."""
-        ms = np.zeros(max(n_steps, 1))
-        self._check(self.L.pdmpc_sweep_explore_run(self.s, n_perm, n_steps, ms.ctypes.data_as(abi.c_double_p)), "pdmpc_sweep_explore_run")
+        ms = _run(self._check, "pdmpc_sweep_explore_run", self.L.pdmpc_sweep_explore_run, self.s, n_perm, n_steps)
         self._n_perm(n_perm)
-        return ms[:n_steps]
+        return ms
 
     def prep_calls(self):
         """The step-preparation calls of the last build, whatever the number of members (pdmpc_sweep_last_prep_calls): [lanelet
         bounding, coupler on the bounded sets, coupler on the plain hulls, future collision assessment]."""
         calls = np.zeros(4, dtype=np.int32)
-        self._check(self.L.pdmpc_sweep_last_prep_calls(self.s, calls.ctypes.data_as(abi.c_int32_p)), "pdmpc_sweep_last_prep_calls")
+        self._check(self.L.pdmpc_sweep_last_prep_calls(self.s, abi.i32p(calls)), "pdmpc_sweep_last_prep_calls")
         return calls.tolist()
 
     def last_timing(self):
         """Host milliseconds of the last lock-step by part (pdmpc_sweep_last_timing)."""
         t = (C.c_double * 6)()
         self._check(self.L.pdmpc_sweep_last_timing(self.s, t), "pdmpc_sweep_last_timing")
-        return dict(zip(("build", "pack", "enqueue", "wait_and_read_back", "choose", "apply"), (float(x) for x in t)))
+        return dict(zip(TIMING_PARTS, (float(x) for x in t)))

@@ -150,14 +150,11 @@ def test_native_controller_equals_its_twin_on_the_circle_and_the_optimal_choice(
 
 def test_argument_checks():
     from pdmpc.backend import load_library
-    from pdmpc.native_controller import _declare
     from pdmpc.scenario import circle_scenario
 
-    L = _declare(load_library())
+    L = load_library()
     options = Config(scenario_type=ScenarioType.circle, amount=2, Hp=5)
     nat = NativeController(options, circle_scenario(options), get_mpa(options), None)
-    L.pdmpc_controller_set_optimizer.argtypes = [C.c_void_p, C.c_int32]
-    L.pdmpc_controller_set_optimizer.restype = C.c_int
     assert L.pdmpc_controller_set_optimizer(nat.c, 2) == ERR_INVALID
     assert L.pdmpc_controller_set_optimizer(nat.c, -1) == ERR_INVALID
     assert L.pdmpc_controller_set_optimizer(None, 1) == ERR_INVALID
@@ -168,8 +165,6 @@ def test_argument_checks():
     assert L.pdmpc_controller_set_optimizer(nat.c, 1) == 0 and L.pdmpc_controller_set_optimizer(nat.c, 0) == 0
     nat.close()
     # NULL handle, NULL seeds with n > 0
-    L.pdmpc_plan_step_sampled.restype = C.c_int
-    L.pdmpc_set_step_seeds.restype = C.c_int
     vin = (abi.VehicleIn * 1)()
     out = (abi.VehicleOut * 1)()
     assert L.pdmpc_plan_step_sampled(None, 1, vin, None, None, None, (C.c_uint32 * 1)(1), out) == ERR_INVALID

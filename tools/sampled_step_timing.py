@@ -110,7 +110,7 @@ def measure(name, options, sc, n_steps, native_steps, **kw):
         for (n, arr, off, idx, fb, _), seeds in args:
             out = abi.out_array(n)
             sd = (abi.C.c_uint32 * n)(*seeds)
-            rc = h.L.pdmpc_plan_step_sampled(h.h, n, arr, off.ctypes.data_as(abi.c_int32_p), idx.ctypes.data_as(abi.c_int32_p), fb, sd, abi.out_ptr(out))
+            rc = h.L.pdmpc_plan_step_sampled(h.h, n, arr, abi.i32p(off), abi.i32p(idx), fb, sd, abi.out_ptr(out))
             assert rc == 0
         rate["ii"].append(len(steps) / (time.perf_counter() - t0))
     st = h.stats()
