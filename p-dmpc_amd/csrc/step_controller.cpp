@@ -23,12 +23,15 @@
 // Every floating-point expression keeps the order of the Python twin (which keeps the reference's), and both call the
 // same libm, so the step problems the two build are bit-identical (tests/test_native_controller.py).
 //
-// One path for a controller alone and for a sweep of M: build_members prepares the step of a span of members -- the
-// device calls or their host twins, grouped by member, the only fork on the handle and the only capacity retry -- between the
-// per-member halves begin_step and finish_step (pdmpc_controller_build_step: M = 1, in the controller's own scratch); plan_built plans
-// what was built (weights, seeds, the backend call, timing[1..3]) for the step, the batch of prioritizations and both sweep steps;
-// timed_steps is the loop of every *_run.
+// Two records and one path.  A StepProblem is what pdmpc_plan_step takes -- inputs, fallbacks, predecessor slots --
+// with its seeds and weights, wherever it lives: a controller's step, each kept instance, its flattened batch, a sweep's concatenated
+// step and batch; the per-slot tags (instance, vehicle, level, member, member_slot) are plain vectors next to it.  An Instance is a
+// prioritization (both coupling matrices, levels, slot order): the controller's own (c->pri) and every kept one.  build_members prepares
+// the step of a span of members -- the device calls or their host twins, grouped by member, the only fork on the handle and the only
+// capacity retry -- between the per-member halves begin_step and finish_step (pdmpc_controller_build_step: M = 1, in the controller's
+// own scratch); plan_built plans a StepProblem (weights, seeds, the backend call, timing[1..3]); timed_steps is the loop of every *_run.
 #include <algorithm>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -88,7 +91,39 @@ struct VehicleDef {
     double tile_dx, tile_dy;
 };
 
-}  // namespace
+// A step problem in the C ABI's form (what pdmpc_plan_step takes; the polygon sets its entries point to live in the arena of the
+// controller that built them), with the sampled optimizer's seed and the expected work per slot.  One record wherever a problem lives.
+struct StepProblem {
+    std::vector<pdmpc_vehicle_in> in;
+    std::vector<pdmpc_polygon_set> fb;  // per slot: what its vehicle publishes if its search is exhausted
+    std::vector<int32_t> pred_offset, pred_index;
+    std::vector<uint32_t> seeds;   // time_step + vehicle_index (set_seeds; empty for a kept instance, which is never planned by itself)
+    std::vector<double> weights;   // plan_built's scratch
+    int n() const { return (int)in.size(); }
+    // a backend call on the problem: call(h, n_slots, in, pred_offset, pred_index, fallback, rest ...)
+    template <class Call, class... Rest>
+    int plan(Call call, pdmpc_handle* h, Rest... rest) const {
+        return call(h, n(), in.data(), pred_offset.data(), pred_index.data(), fb.data(), rest...);
+    }
+};
+// ... and the same five as every *_problem entry point hands them out
+void expose(const StepProblem& P, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index, const pdmpc_polygon_set** fallback) {
+    if (n_slots) *n_slots = P.n();
+    if (in) *in = P.in.data();
+    if (pred_offset) *pred_offset = P.pred_offset.data();
+    if (pred_index) *pred_index = P.pred_index.data();
+    if (fallback) *fallback = P.fb.data();
+}
+
+// A prioritization of the step's traffic state: the controller's own, and every instance of an explorative or optimal-priority batch
+struct Instance {
+    std::vector<uint8_t> directed, directed_seq;  // n x n row-major
+    std::vector<int32_t> levels, order, slot_of;
+    void take_couplings(const Instance& of) {
+        directed = of.directed;
+        directed_seq = of.directed_seq;
+    }
+};
 
 // A choice among the plans of a batch as pdmpc_choose_host / pdmpc_plan_step_chosen take it (pdmpc_choice): the lists, kept from step to step
 struct ChoiceLists {
@@ -118,7 +153,7 @@ struct ChoiceLists {
 };
 
 // What a member's step reads of the reachable sets (begin_step), and the scratch of ONE step preparation over a span of members
-// (prepare_members): a sweep owns one for its members, a controller one for the steps it takes alone.
+// (build_members): a sweep owns one for its members, a controller one for the steps it takes alone.
 struct StepPrep {
     bool reach_parallel = false, reach = false, bounded = false;
 };
@@ -142,6 +177,8 @@ struct PrepScratch {
         std::vector<int32_t> collisions, priorities;
     } fca;
 };
+
+}  // namespace
 
 struct pdmpc_controller {
     pdmpc_handle* h = nullptr;
@@ -167,20 +204,15 @@ struct pdmpc_controller {
     double timing_sum[6] = {0, 0, 0, 0, 0, 0};  // ... summed over the steps since the last pdmpc_controller_timing_sum(reset)
     int64_t timing_steps = 0;
     std::vector<double> last_pops;  // per vehicle: nodes its search popped in the last step (the next step's expected work, pdmpc_set_step_weights)
-    std::vector<double> weights;    // ... per slot of the problem about to be planned (plan_built's scratch)
     int optimizer = PDMPC_OPTIMIZER_GRAPH_SEARCH;  // pdmpc_controller_set_optimizer
-    std::vector<uint32_t> seeds;    // per slot of the last built step or batch: time_step + vehicle_index (the sampled optimizer's seeds)
     // per step
     std::vector<int32_t> trims;
     std::vector<Poly> occ_offset, occ_plain;
     std::vector<std::vector<double>> ref_x, ref_y, v_ref;
     std::vector<Poly> bnd_left, bnd_right;
-    std::vector<uint8_t> adjacency, directed, directed_seq;  // n x n row-major
-    std::vector<int32_t> levels, order, slot_of;
-    // the step problem in the C ABI's form (what pdmpc_plan_step takes); the arena keeps the pointed-to data alive
-    std::vector<pdmpc_vehicle_in> in;
-    std::vector<pdmpc_polygon_set> fb;
-    std::vector<int32_t> pred_offset, pred_index;
+    std::vector<uint8_t> adjacency;  // n x n row-major
+    Instance pri;                    // the controller's own prioritization (after a choice: every vehicle's row of its chosen instance's couplings)
+    StepProblem prob;                // ... and its step problem; the arena keeps the pointed-to data alive
     // the arrays of the step's polygon sets: chunks that are kept from step to step and handed out front to back (a set's arrays
     // never move; build_step starts over at the first chunk)
     struct Arena {
@@ -241,20 +273,12 @@ struct pdmpc_controller {
     bool empty_done = false;
     bool exploring = false;  // an explorative step is being built: its prioritizations share sets through the memos
     // explorative step (PrioritizedExplorativeController): the prioritizations of the current traffic state, flattened
-    struct Instance {
-        std::vector<uint8_t> directed, directed_seq;
-        std::vector<int32_t> levels, order, slot_of;
-    };
     std::vector<Instance> inst;
-    struct Part {  // an instance's step problem as assemble_step left it (explore_build's scratch, kept from step to step)
-        std::vector<pdmpc_vehicle_in> in;
-        std::vector<pdmpc_polygon_set> fb;
-        std::vector<int32_t> pred_offset, pred_index;
-    };
-    std::vector<Part> x_parts;
-    std::vector<pdmpc_vehicle_in> x_in;
-    std::vector<pdmpc_polygon_set> x_fb;
-    std::vector<int32_t> x_pred_offset, x_pred_index, x_instance, x_vehicle, x_level, x_slot;  // x_slot[p * n + vehicle] = slot in the flattened batch
+    std::vector<StepProblem> inst_prob;  // an instance's step problem as assemble_step left it (kept from step to step: no allocation once warm)
+    StepProblem x_prob;                  // the flattened batch, and per slot of it:
+    std::vector<int32_t> x_instance, x_vehicle, x_level;
+    std::vector<int32_t> x_slot;         // x_slot[p * n + vehicle] = slot in the flattened batch
+    bool batch_built_last = false;       // pdmpc_controller_seeds: the seeds of x_prob (else of prob), whichever was built last
     std::vector<pdmpc_vehicle_out> x_out;
     std::vector<int32_t> x_chosen;  // per vehicle: the instance its sub-graph chose
     std::vector<double> x_cost;     // n_perm x n_graphs (the optimal step: n x K, row v = vehicle v's sums)
@@ -845,20 +869,21 @@ int bound_with_room(std::vector<int32_t>& off, std::vector<double>& x, std::vect
     return rc;
 }
 
-// Plans a problem of N slots that has been built -- a controller's, its batch of prioritizations or a sweep's -- on h: last step's work
-// as the expected work of this one (pops_of(slot) + 1: heavy searches are dispatched first; weigh = false: no step has been planned
-// yet), the slots' seeds for the next pack if the optimizer is the sampled one (a sampled bank; nothing for the graph search), the
-// backend call `plan` (pdmpc_plan_step, _lean or _chosen), and its parts (pdmpc_last_call_timing) into timing[1..3].  w: scratch.
-template <class Pops, class Call>
-int plan_built(pdmpc_handle* h, int N, bool weigh, std::vector<double>& w, Pops&& pops_of, int optimizer, const std::vector<uint32_t>& seeds, double* timing, Call&& plan) {
+// Plans a problem that has been built -- a controller's, its batch of prioritizations or a sweep's -- on h: last step's work as the
+// expected work of this one (pops_of(slot) + 1: heavy searches are dispatched first; weigh = false: no step has been planned yet), the
+// slots' seeds for the next pack if the optimizer is the sampled one (a sampled bank; nothing for the graph search), the backend call
+// `call` with the problem's arrays and `rest` (pdmpc_plan_step, _lean or _chosen), and its parts (pdmpc_last_call_timing) into timing[1..3].
+template <class Pops, class Call, class... Rest>
+int plan_built(pdmpc_handle* h, StepProblem& P, bool weigh, Pops&& pops_of, int optimizer, double* timing, Call call, Rest... rest) {
     if (weigh) {
-        w.resize((size_t)N);
-        for (int s = 0; s < N; ++s) w[(size_t)s] = pops_of(s) + 1.0;
-        (void)pdmpc_set_step_weights(h, N, w.data());
+        const int N = P.n();
+        P.weights.resize((size_t)N);
+        for (int s = 0; s < N; ++s) P.weights[(size_t)s] = pops_of(s) + 1.0;
+        (void)pdmpc_set_step_weights(h, N, P.weights.data());
     }
     if (optimizer == PDMPC_OPTIMIZER_SAMPLED)
-        if (const int rc = pdmpc_set_step_seeds(h, (int32_t)seeds.size(), seeds.data())) return cfail(nullptr, rc, pdmpc_last_error());
-    if (const int rc = plan()) return cfail(nullptr, rc, pdmpc_last_error());
+        if (const int rc = pdmpc_set_step_seeds(h, (int32_t)P.seeds.size(), P.seeds.data())) return cfail(nullptr, rc, pdmpc_last_error());
+    if (const int rc = P.plan(call, h, rest...)) return cfail(nullptr, rc, pdmpc_last_error());
     double us[3] = {0, 0, 0};
     if (pdmpc_last_call_timing(h, us) == PDMPC_OK)
         for (int i = 0; i < 3; ++i) timing[1 + i] = us[i] * 1e-3;
@@ -876,164 +901,12 @@ int timed_steps(int32_t n_steps, double* ms, Step&& step) {
     return PDMPC_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-const char* pdmpc_controller_last_error(void) { return g_cerr.c_str(); }
-
-int pdmpc_controller_create(pdmpc_handle* handle, const pdmpc_controller_config* cfg, const pdmpc_scenario* sc, pdmpc_controller** out) {
-    if (!cfg || !sc || !out) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
-    if (sc->n_vehicles < 1 || cfg->Hp < 1 || cfg->Hp > PDMPC_HP_MAX || sc->n_trims < 1) return cfail(nullptr, PDMPC_ERR_INVALID, "bad sizes");
-    if (cfg->priority_strategy < PDMPC_PRIORITY_CONSTANT || cfg->priority_strategy > PDMPC_PRIORITY_FCA) return cfail(nullptr, PDMPC_ERR_INVALID, "unknown priority strategy");
-    if (cfg->weight_strategy < PDMPC_WEIGHT_DISTANCE || cfg->weight_strategy > PDMPC_WEIGHT_RANDOM) return cfail(nullptr, PDMPC_ERR_INVALID, "unknown weight strategy");
-    if (handle) {
-        // the backend reads Hp entries of every reference and writes one record per vehicle: a handle created for another
-        // horizon or a smaller batch must not be driven by this controller
-        pdmpc_config hc{};
-        int32_t has_mpa = 0;
-        if (pdmpc_get_config(handle, &hc, &has_mpa) != PDMPC_OK) return cfail(nullptr, PDMPC_ERR_INVALID, "bad backend handle");
-        if (hc.Hp != cfg->Hp) return cfail(nullptr, PDMPC_ERR_INVALID, "the handle was created for another horizon (config.Hp) than the controller");
-        if (hc.max_vehicles < sc->n_vehicles) return cfail(nullptr, PDMPC_ERR_CAPACITY, "the handle's max_vehicles is smaller than the scenario");
-        if (!has_mpa) return cfail(nullptr, PDMPC_ERR_NO_MPA, "pdmpc_upload_mpa has not been called on the handle");
-    }
-    pdmpc_controller* c = new pdmpc_controller();
-    c->h = handle;
-    c->cfg = *cfg;
-    c->n = sc->n_vehicles;
-    c->Hp = cfg->Hp;
-    c->trim_speed.assign(sc->trim_speed, sc->trim_speed + sc->n_trims);
-    c->trim_steering.assign(sc->trim_steering, sc->trim_steering + sc->n_trims);
-    for (int v = 0; v < c->n; ++v) {
-        VehicleDef d;
-        d.x_start = sc->x_start[v];
-        d.y_start = sc->y_start[v];
-        d.yaw_start = sc->yaw_start[v];
-        d.reference_speed = sc->reference_speed[v];
-        d.px.assign(sc->path_x + sc->path_offset[v], sc->path_x + sc->path_offset[v + 1]);
-        d.py.assign(sc->path_y + sc->path_offset[v], sc->path_y + sc->path_offset[v + 1]);
-        if (d.px.size() < 2) {
-            delete c;
-            return cfail(nullptr, PDMPC_ERR_INVALID, "a reference path needs at least two points");
-        }
-        if (sc->lanelets_offset) {
-            d.lanelets_index.assign(sc->lanelets_index + sc->lanelets_offset[v], sc->lanelets_index + sc->lanelets_offset[v + 1]);
-            d.points_index.assign(sc->points_index + sc->lanelets_offset[v], sc->points_index + sc->lanelets_offset[v + 1]);
-        }
-        d.is_loop = sc->is_loop ? sc->is_loop[v] != 0 : true;
-        d.tile_dx = sc->tile_dx ? sc->tile_dx[v] : 0.0;
-        d.tile_dy = sc->tile_dy ? sc->tile_dy[v] : 0.0;
-        c->veh.push_back(std::move(d));
-    }
-    for (int l = 0; l < sc->n_lanelets; ++l) {
-        Poly a, b;
-        a.x.assign(sc->left_x + sc->left_offset[l], sc->left_x + sc->left_offset[l + 1]);
-        a.y.assign(sc->left_y + sc->left_offset[l], sc->left_y + sc->left_offset[l + 1]);
-        b.x.assign(sc->right_x + sc->right_offset[l], sc->right_x + sc->right_offset[l + 1]);
-        b.y.assign(sc->right_y + sc->right_offset[l], sc->right_y + sc->right_offset[l + 1]);
-        c->bl_left.push_back(std::move(a));
-        c->bl_right.push_back(std::move(b));
-    }
-    for (int p = 0; p < sc->obstacles.n_polygons; ++p) {
-        Poly o;
-        o.x.assign(sc->obstacles.x + sc->obstacles.offset[p], sc->obstacles.x + sc->obstacles.offset[p + 1]);
-        o.y.assign(sc->obstacles.y + sc->obstacles.offset[p], sc->obstacles.y + sc->obstacles.offset[p + 1]);
-        c->static_obstacles.push_back(std::move(o));
-    }
-    c->fca_obst_off.assign(1, 0);
-    for (const Poly& o : c->static_obstacles) {
-        c->fca_obst_x.insert(c->fca_obst_x.end(), o.x.begin(), o.x.end());
-        c->fca_obst_y.insert(c->fca_obst_y.end(), o.y.begin(), o.y.end());
-        c->fca_obst_off.push_back((int32_t)c->fca_obst_x.size());
-    }
-    // Simulation.setup: initial speed = steering = 0 (Simulation.m:52-65)
-    c->mx.resize(c->n);
-    c->my.resize(c->n);
-    c->myaw.resize(c->n);
-    c->mspeed.assign(c->n, 0.0);
-    c->msteer.assign(c->n, 0.0);
-    for (int v = 0; v < c->n; ++v) {
-        c->mx[v] = c->veh[v].x_start;
-        c->my[v] = c->veh[v].y_start;
-        c->myaw[v] = c->veh[v].yaw_start;
-    }
-    c->info_old.assign(c->n, Plan());
-    c->infos.assign(c->n, Plan());
-    *out = c;
-    return PDMPC_OK;
-}
-
-int pdmpc_controller_set_parallel_coupling(pdmpc_controller* c, int32_t mode) {
-    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
-    if (mode != PDMPC_PARALLEL_PREVIOUS_TRAJECTORY && mode != PDMPC_PARALLEL_REACHABLE_SETS) return cfail(c, PDMPC_ERR_INVALID, "unknown parallel coupling mode");
-    c->parallel_mode = mode;
-    return PDMPC_OK;
-}
-
-int pdmpc_controller_set_optimizer(pdmpc_controller* c, int32_t which) {
-    if (!c) return cfail(c, PDMPC_ERR_INVALID, "null controller");
-    if (which != PDMPC_OPTIMIZER_GRAPH_SEARCH && which != PDMPC_OPTIMIZER_SAMPLED) return cfail(c, PDMPC_ERR_INVALID, "optimizer must be PDMPC_OPTIMIZER_GRAPH_SEARCH or PDMPC_OPTIMIZER_SAMPLED");
-    c->optimizer = which;
-    return PDMPC_OK;
-}
-
-int pdmpc_controller_priorities(pdmpc_controller* c, int32_t* n_priorities, const int32_t** priorities, int32_t* n_collisions, const int32_t** collisions) {
-    if (!c || !n_priorities || !priorities || !n_collisions || !collisions) return cfail(c, PDMPC_ERR_INVALID, "null argument");
-    const bool has = c->cfg.priority_strategy != PDMPC_PRIORITY_COLORING, fca = c->cfg.priority_strategy == PDMPC_PRIORITY_FCA;
-    *n_priorities = has ? (int32_t)c->prio.size() : 0;
-    *priorities = c->prio.data();
-    *n_collisions = fca ? (int32_t)c->fca_count.size() : 0;
-    *collisions = c->fca_count.data();
-    return PDMPC_OK;
-}
-
-int pdmpc_controller_seeds(pdmpc_controller* c, int32_t* n, const uint32_t** seeds) {
-    if (!c || !n || !seeds) return cfail(c, PDMPC_ERR_INVALID, "null argument");
-    *n = (int32_t)c->seeds.size();
-    *seeds = c->seeds.data();
-    return PDMPC_OK;
-}
-
-int pdmpc_controller_set_lanelet_bounding(pdmpc_controller* c, int32_t on) {
-    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
-    c->lanelet_bounding = on != 0;
-    return PDMPC_OK;
-}
-
-int pdmpc_controller_set_reachability(pdmpc_controller* c, const pdmpc_mpa* mpa) {
-    if (!c || !mpa) return cfail(c, PDMPC_ERR_INVALID, "null argument");
-    if (mpa->Hp != c->Hp) return cfail(c, PDMPC_ERR_INVALID, "the automaton's Hp differs from the controller's");
-    if (mpa->n_trims != (int32_t)c->trim_speed.size()) return cfail(c, PDMPC_ERR_INVALID, "the automaton's trims differ from the scenario's");
-    c->has_reach = false;
-    std::vector<int32_t> off((size_t)mpa->n_trims * mpa->Hp + 1, 0);
-    int rc = pdmpc_local_reachable_sets(mpa, 0, off.data(), nullptr, nullptr);
-    if (rc != PDMPC_OK && rc != PDMPC_ERR_CAPACITY) return cfail(c, rc, "pdmpc_local_reachable_sets failed");
-    std::vector<double> x((size_t)off.back() + 1), y((size_t)off.back() + 1);
-    rc = pdmpc_local_reachable_sets(mpa, off.back(), off.data(), x.data(), y.data());
-    if (rc) return cfail(c, rc, "pdmpc_local_reachable_sets failed");
-    if (c->h) {
-        const pdmpc_polygon_set ps = view_polygons(off, x, y);
-        rc = pdmpc_upload_reachable_sets(c->h, mpa->n_trims, mpa->Hp, &ps);
-        if (rc) return cfail(c, rc, std::string("pdmpc_upload_reachable_sets: ") + pdmpc_last_error());
-    }
-    c->reach_off = std::move(off);
-    c->reach_x = std::move(x);
-    c->reach_y = std::move(y);
-    c->has_reach = true;
-    return PDMPC_OK;
-}
-
-int pdmpc_controller_destroy(pdmpc_controller* c) {
-    delete c;
-    return PDMPC_OK;
-}
-
-namespace {
+// ---- a member's step around the step preparation: the seeds, the priorities, and the stages of pdmpc_controller_build_step in its order
 // RandStream('mt19937ar', Seed = time_step + vehicle_index) of every slot (MonteCarloTreeSearch.m:31-32; PrioritizedController.m:335-341
 // calls run_optimizer with obj.k, so every instance of a batch draws the same stream for the same vehicle)
-void set_seeds(pdmpc_controller* c, const std::vector<int32_t>& vehicle_of_slot) {
-    c->seeds.resize(vehicle_of_slot.size());
-    for (size_t s = 0; s < vehicle_of_slot.size(); ++s) c->seeds[s] = (uint32_t)(c->k + vehicle_of_slot[s] + 1);
+void set_seeds(const pdmpc_controller* c, StepProblem& P, const std::vector<int32_t>& vehicle_of_slot) {
+    P.seeds.resize(vehicle_of_slot.size());
+    for (size_t s = 0; s < vehicle_of_slot.size(); ++s) P.seeds[s] = (uint32_t)(c->k + vehicle_of_slot[s] + 1);
 }
 
 // RandomPrioritizer.m:15-25 (prioritizer.random_priorities): a Fisher-Yates shuffle of 1 .. n on the mt19937ar doubles of the time step
@@ -1046,7 +919,7 @@ void random_priorities(int time_step, int n, std::vector<int32_t>& p) {
 }
 
 // FcaPrioritizer.m:11-92 on the step's reference points and the scenario's obstacles: the two per-member halves around the ONE
-// grouped assessment of all FCA members of a step preparation (prepare_members) -- the reference points, their headings and the
+// grouped assessment of all FCA members of a step preparation (build_members) -- the reference points, their headings and the
 // coupled pairs in c->fca_*, and the counts and priorities taken over
 int fca_inputs(pdmpc_controller* c) {
     const int n = c->n, Hp = c->Hp;
@@ -1137,7 +1010,7 @@ void reachable_sets_at_poses(pdmpc_controller* c) {
 
 // lanelet bounding of those sets (bound_reachable_sets.m, HighLevelController.m:241-246): every step's sets when parallel
 // predecessors read them (all_steps), else step Hp only (the coupler's)
-// ... its two per-member halves around the bounding call of a step preparation (prepare_members): the raw lanelet polygons in
+// ... its two per-member halves around the bounding call of a step preparation (build_members): the raw lanelet polygons in
 // c->lan_*, and the bounded sets in c->bound_* taken over as the parallel predecessors' obstacles
 void lanelet_polygons(pdmpc_controller* c) {
     const int n = c->n;
@@ -1196,11 +1069,12 @@ void couple(pdmpc_controller* c) {
     }
 }
 
-// priorities -> c->directed (FCA: the counts and priorities of the member's group in the step preparation's assessment)
+// priorities -> c->pri.directed (FCA: the counts and priorities of the member's group in the step preparation's assessment)
 void direct_by_priorities(pdmpc_controller* c, const int32_t* fca_collisions, const int32_t* fca_priorities) {
     const int n = c->n;
+    std::vector<uint8_t>& directed = c->pri.directed;
     if (c->cfg.priority_strategy == PDMPC_PRIORITY_COLORING) {
-        coloring_directed(c->adjacency, n, c->directed);
+        coloring_directed(c->adjacency, n, directed);
         return;
     }
     // constant priorities = vehicle index (ConstantPrioritizer.m:14-20); random and FCA priorities as below
@@ -1212,10 +1086,10 @@ void direct_by_priorities(pdmpc_controller* c, const int32_t* fca_collisions, co
     } else if (c->cfg.priority_strategy == PDMPC_PRIORITY_FCA) {
         adopt_fca(c, fca_collisions, fca_priorities);
     }
-    c->directed.assign((size_t)n * n, 0);
+    directed.assign((size_t)n * n, 0);
     for (int i = 0; i < n; ++i)
         for_each_set(c->adjacency.data() + (size_t)i * n, n, [&](int j) {
-            if (!(c->prio[j] < c->prio[i])) at(c->directed, n, i, j) = 1;
+            if (!(c->prio[j] < c->prio[i])) at(directed, n, i, j) = 1;
         });
 }
 
@@ -1250,45 +1124,45 @@ int begin_step(pdmpc_controller* c, StepPrep& P) {
     P.bounded = bounded;
     return PDMPC_OK;
 }
-// c->directed -> sequential couplings, levels, slot order and the per-slot inputs of pdmpc_plan_step (the arena is the caller's
+// c->pri.directed -> sequential couplings, levels, slot order and the per-slot inputs of pdmpc_plan_step (the arena is the caller's
 // to clear: the explorative step keeps several problems alive side by side)
 int assemble_step(pdmpc_controller* c, bool seq_given = false) {
     const int n = c->n, Hp = c->Hp;
-    // (seq_given: c->directed_seq is the caller's -- the explorative step swaps single couplings of the base prioritization)
+    // (seq_given: c->pri.directed_seq is the caller's -- the explorative step swaps single couplings of the base prioritization)
     // who a vehicle is coupled with, as lists: the loops below visit a vehicle's few couplings, not rows and columns of the matrices
     Lists &dir_succ = c->ls_dir_succ, &dir_pred = c->ls_dir_pred, &seq_succ_own = c->ls_seq_succ, &seq_pred_own = c->ls_seq_pred;
-    lists_by_row(c->directed, n, dir_succ);
-    lists_by_column(c->directed, n, dir_succ, dir_pred);
+    lists_by_row(c->pri.directed, n, dir_succ);
+    lists_by_column(c->pri.directed, n, dir_succ, dir_pred);
     bool uncut = false;
-    if (!seq_given && !group(*c, c->directed, dir_succ, dir_pred, c->directed_seq, c->levels, uncut)) return cfail(c, PDMPC_ERR_INVALID, "coupling graph has a cycle");
+    if (!seq_given && !group(*c, c->pri.directed, dir_succ, dir_pred, c->pri.directed_seq, c->pri.levels, uncut)) return cfail(c, PDMPC_ERR_INVALID, "coupling graph has a cycle");
     if (!uncut) {  // (uncut: the sequential coupling is `directed` itself, levels and lists included)
-        lists_by_row(c->directed_seq, n, seq_succ_own);
-        lists_by_column(c->directed_seq, n, seq_succ_own, seq_pred_own);
-        if (!kahn_lists(seq_succ_own, n, c->levels, c->kahn_indeg, c->kahn_cur, c->kahn_next)) return cfail(c, PDMPC_ERR_INVALID, "coupling graph has a cycle");
+        lists_by_row(c->pri.directed_seq, n, seq_succ_own);
+        lists_by_column(c->pri.directed_seq, n, seq_succ_own, seq_pred_own);
+        if (!kahn_lists(seq_succ_own, n, c->pri.levels, c->kahn_indeg, c->kahn_cur, c->kahn_next)) return cfail(c, PDMPC_ERR_INVALID, "coupling graph has a cycle");
     }
     const Lists& seq_pred = uncut ? dir_pred : seq_pred_own;
     // slot order: by level, vehicles of a level in index order (a counting sort over the levels 1 .. n)
-    c->order.resize(n);
-    c->slot_of.assign(n, 0);
+    c->pri.order.resize(n);
+    c->pri.slot_of.assign(n, 0);
     {
         std::vector<int>& first = c->kahn_cur;  // (scratch) first[l] = slot of level l's first vehicle
         first.assign((size_t)n + 2, 0);
-        for (int i = 0; i < n; ++i) ++first[(size_t)c->levels[i] + 1];
+        for (int i = 0; i < n; ++i) ++first[(size_t)c->pri.levels[i] + 1];
         for (int l = 1; l <= n + 1; ++l) first[l] += first[l - 1];
         for (int i = 0; i < n; ++i) {
-            const int s = first[(size_t)c->levels[i]]++;
-            c->order[s] = i;
-            c->slot_of[i] = s;
+            const int s = first[(size_t)c->pri.levels[i]]++;
+            c->pri.order[s] = i;
+            c->pri.slot_of[i] = s;
         }
     }
     // ---- per slot inputs
-    c->in.assign(n, pdmpc_vehicle_in());
-    c->fb.assign(n, pdmpc_polygon_set());
-    c->pred_offset.assign(n + 1, 0);
-    c->pred_index.clear();
+    c->prob.in.assign(n, pdmpc_vehicle_in());
+    c->prob.fb.assign(n, pdmpc_polygon_set());
+    c->prob.pred_offset.assign(n + 1, 0);
+    c->prob.pred_index.clear();
     for (int s = 0; s < n; ++s) {
-        const int i = c->order[s];
-        pdmpc_vehicle_in& I = c->in[s];
+        const int i = c->pri.order[s];
+        pdmpc_vehicle_in& I = c->prob.in[s];
         std::memset(&I, 0, sizeof I);
         I.x0 = c->mx[i];
         I.y0 = c->my[i];
@@ -1327,7 +1201,7 @@ int assemble_step(pdmpc_controller* c, bool seq_given = false) {
         }
         for (const int32_t* q = dir_pred.begin(i); q != dir_pred.end(i); ++q) {
             const int j = *q;
-            if (at(c->directed_seq, n, j, i)) continue;
+            if (at(c->pri.directed_seq, n, j, i)) continue;
             // (parallel_coupling_reachability, :391-407: the predecessor's reachable sets exist from the first step on)
             if (c->parallel_mode == PDMPC_PARALLEL_REACHABLE_SETS || (c->info_old[j].present && c->k > 1)) {
                 dplp[ndp++] = j;
@@ -1394,8 +1268,8 @@ int assemble_step(pdmpc_controller* c, bool seq_given = false) {
         }
         I.hdv_reachable_sets = c->empty_set;
         // sequential predecessors as slots
-        for (const int32_t* q = seq_pred.begin(i); q != seq_pred.end(i); ++q) c->pred_index.push_back(c->slot_of[*q]);
-        c->pred_offset[s + 1] = (int32_t)c->pred_index.size();
+        for (const int32_t* q = seq_pred.begin(i); q != seq_pred.end(i); ++q) c->prob.pred_index.push_back(c->pri.slot_of[*q]);
+        c->prob.pred_offset[s + 1] = (int32_t)c->prob.pred_index.size();
         // what the vehicle publishes if its search is exhausted: its standstill rectangle (:602-611) or the previous plan
         // shifted by one step (:678-718)
         if (!c->fb_done[i]) {  // (a function of the vehicle alone: shared by the prioritizations of an explorative step)
@@ -1409,147 +1283,27 @@ int assemble_step(pdmpc_controller* c, bool seq_given = false) {
             c->fb_of[i] = fbs.finish();
             c->fb_done[i] = 1;
         }
-        c->fb[s] = c->fb_of[i];
+        c->prob.fb[s] = c->fb_of[i];
     }
-    c->pred_index.push_back(0);
+    c->prob.pred_index.push_back(0);
     return PDMPC_OK;
 }
 // ... and everything after the step preparation
 int finish_step(pdmpc_controller* c, const int32_t* fca_collisions, const int32_t* fca_priorities) {
     direct_by_priorities(c, fca_collisions, fca_priorities);
     if (const int rc = assemble_step(c)) return rc;
-    set_seeds(c, c->order);
-    return PDMPC_OK;
-}
-}  // namespace
-
-// records of the step in slot order -> plans, exhaustion handling, fallbacks of coupled vehicles, plant update
-int pdmpc_controller_apply(pdmpc_controller* c, const pdmpc_vehicle_out* recs) {
-    if (!c || !recs) return cfail(c, PDMPC_ERR_INVALID, "null argument");
-    const int n = c->n, Hp = c->Hp;
-    auto fallback_plan = [&](int i, Plan& p) -> bool {  // plan_fallback (:678-718): the previous plan shifted by one step
-        const Plan& old = c->info_old[i];
-        if (!old.present) return false;
-        p.present = true;
-        const size_t m = old.shapes.size();
-        p.shapes.resize(m);
-        p.trims.resize(m);
-        p.yx.resize(m);
-        p.yy.resize(m);
-        p.yyaw.resize(m);
-        for (size_t q = 0; q < m; ++q) {
-            const size_t from = std::min(q + 1, m - 1);
-            p.shapes[q] = old.shapes[from];
-            p.trims[q] = old.trims[from];
-            p.yx[q] = old.yx[from];
-            p.yy[q] = old.yy[from];
-            p.yyaw[q] = old.yyaw[from];
-        }
-        return true;
-    };
-    // The step's plans are built in c->infos — nothing else reads it — and swapped with c->info_old at the end: an error status or a
-    // fallback in the first step leaves the controller's plans as they were, and the vectors of a plan keep their capacity from
-    // step to step (they are overwritten entry by entry, not re-created).
-    std::vector<Plan>& infos = c->infos;
-    infos.resize((size_t)n);
-    if (c->last_pops.size() != (size_t)n) c->last_pops.assign((size_t)n, 0.0);
-    for (int s = 0; s < n; ++s) {
-        const int i = c->order[s];
-        const pdmpc_vehicle_out& r = recs[s];
-        if (r.status != PDMPC_OK && r.status != PDMPC_EXHAUSTED) return cfail(c, PDMPC_ERR_HIP, "a result record carries an error status: not a planning result");
-        Plan& p = infos[i];
-        p.present = p.needs_fallback = p.exhausted = false;
-        p.n_expanded = r.n_expanded;
-        c->last_pops[(size_t)i] = (double)r.n_popped;
-        if (r.status == PDMPC_OK) {
-            p.present = true;
-            p.shapes.resize((size_t)Hp);
-            p.trims.resize((size_t)Hp);
-            p.yx.resize((size_t)Hp);
-            p.yy.resize((size_t)Hp);
-            p.yyaw.resize((size_t)Hp);
-            for (int q = 0; q < Hp; ++q) {
-                Poly& sh = p.shapes[q];
-                sh.x.assign(r.shapes[q][0], r.shapes[q][0] + r.shape_cols[q]);
-                sh.y.assign(r.shapes[q][1], r.shapes[q][1] + r.shape_cols[q]);
-                p.trims[q] = r.predicted_trims[q];
-                p.yx[q] = r.y_predicted[q][0];
-                p.yy[q] = r.y_predicted[q][1];
-                p.yyaw[q] = r.y_predicted[q][2];
-            }
-        } else {  // PrioritizedController.m:344-352
-            p.exhausted = true;
-            const bool standstill = c->trim_speed[c->trims[i] - 1] == 0;
-            if (standstill && c->cfg.constraint_from_successor != PDMPC_SUCCESSOR_NONE) {  // handle_graph_search_exhaustion (:568-616)
-                p.present = true;
-                p.shapes.assign((size_t)Hp, c->occ_plain[i]);
-                p.trims.assign((size_t)Hp, c->trims[i]);
-                p.yx.assign((size_t)Hp, c->mx[i]);
-                p.yy.assign((size_t)Hp, c->my[i]);
-                p.yyaw.assign((size_t)Hp, c->myaw[i]);
-            } else {
-                if (!fallback_plan(i, p)) return cfail(c, PDMPC_ERR_INVALID, "a vehicle needs a fallback in its first step");
-                p.needs_fallback = true;
-            }
-        }
-    }
-    // handle_others_fallback / check_others_fallback
-    bool any = false;
-    for (int i = 0; i < n; ++i) any = any || infos[i].needs_fallback;
-    if (any) {
-        std::vector<int> fm((size_t)n * n, 0);
-        for (int a = 0; a < n; ++a)
-            for (int b = 0; b < n; ++b) {
-                int v = at(c->adjacency, n, a, b);
-                if (infos[a].needs_fallback && at(c->directed_seq, n, a, b)) v -= 1;
-                if (infos[b].needs_fallback && at(c->directed_seq, n, b, a)) v -= 1;
-                fm[(size_t)a * n + b] = v;
-            }
-        std::vector<uint8_t> reached(n, 0);
-        for (int f = 0; f < n; ++f) {
-            if (!infos[f].needs_fallback) continue;
-            std::vector<uint8_t> seen(n, 0);
-            std::vector<int> stack{f};
-            seen[f] = 1;
-            while (!stack.empty()) {
-                const int a = stack.back();
-                stack.pop_back();
-                for (int b = 0; b < n; ++b)
-                    if (fm[(size_t)a * n + b] != 0 && !seen[b]) {
-                        seen[b] = 1;
-                        stack.push_back(b);
-                    }
-            }
-            for (int v = 0; v < n; ++v) reached[v] |= seen[v];
-        }
-        for (int i = 0; i < n; ++i)
-            if (reached[i] && !infos[i].needs_fallback) {
-                Plan& p = infos[i];  // (keeps its search's n_expanded and exhausted)
-                if (!fallback_plan(i, p)) return cfail(c, PDMPC_ERR_INVALID, "a vehicle needs a fallback in its first step");
-                p.needs_fallback = false;  // plan_fallback(is_fallback_while_planning = false)
-            }
-    }
-    std::swap(c->info_old, c->infos);
-    // Simulation.apply (Simulation.m:86-100)
-    for (int i = 0; i < n; ++i) {
-        const Plan& p = c->info_old[i];
-        c->mx[i] = p.yx[0];
-        c->my[i] = p.yy[0];
-        c->myaw[i] = p.yyaw[0];
-        c->mspeed[i] = c->trim_speed[p.trims[0] - 1];
-        c->msteer[i] = c->trim_steering[p.trims[0] - 1];
-    }
+    set_seeds(c, c->prob, c->pri.order);
+    c->batch_built_last = false;
     return PDMPC_OK;
 }
 
-// One pass of HighLevelController.main_control_loop (:334-373) in simulation: build, plan on the GPU (one launch), apply.
-namespace {
+// ---- how a step ends that the controller takes alone
 // a failure inside a step the controller takes alone is the controller's error too (the global message has it either way)
 int own(pdmpc_controller* c, int rc) {
     if (rc) c->err = g_cerr;
     return rc;
 }
-// the end of such a step: the records in c->out applied (timing[5]), and the step's parts added to the controller's sums
+// the end of a step the controller takes alone: the records in c->out applied (timing[5]), and the step's parts added to the controller's sums
 int apply_and_account(pdmpc_controller* c) {
     const auto t = std::chrono::steady_clock::now();
     const int rc = pdmpc_controller_apply(c, c->out.data());
@@ -1565,132 +1319,8 @@ struct LeanRun {
     explicit LeanRun(pdmpc_controller* ctl) : c(ctl), was(ctl->lean_explore) { c->lean_explore = true; }
     ~LeanRun() { c->lean_explore = was; }
 };
-}  // namespace
 
-int pdmpc_controller_last_timing(pdmpc_controller* c, double* ms6) {
-    if (!c || !ms6) return cfail(c, PDMPC_ERR_INVALID, "null argument");
-    for (int i = 0; i < 6; ++i) ms6[i] = c->timing[i];
-    return PDMPC_OK;
-}
-
-int pdmpc_controller_timing_sum(pdmpc_controller* c, double* ms6, int64_t* n_steps, int32_t reset) {
-    if (!c) return cfail(c, PDMPC_ERR_INVALID, "null argument");
-    if (ms6)
-        for (int i = 0; i < 6; ++i) ms6[i] = c->timing_sum[i];
-    if (n_steps) *n_steps = c->timing_steps;
-    if (reset) {
-        for (int i = 0; i < 6; ++i) c->timing_sum[i] = 0;
-        c->timing_steps = 0;
-    }
-    return PDMPC_OK;
-}
-
-int pdmpc_controller_step(pdmpc_controller* c) {
-    if (!c || !c->h) return cfail(c, PDMPC_ERR_INVALID, "controller has no backend handle");
-    auto t = std::chrono::steady_clock::now();
-    int rc = pdmpc_controller_build_step(c);
-    if (rc) return rc;
-    c->timing[0] = ms_since(t);
-    c->timing[4] = 0;
-    c->out.resize(c->n);
-    rc = plan_built(c->h, c->n, c->last_pops.size() == (size_t)c->n, c->weights, [&](int s) { return c->last_pops[(size_t)c->order[(size_t)s]]; }, c->optimizer, c->seeds,
-                    c->timing, [&] { return pdmpc_plan_step(c->h, c->n, c->in.data(), c->pred_offset.data(), c->pred_index.data(), c->fb.data(), c->out.data()); });
-    if (rc) return own(c, rc);
-    return apply_and_account(c);
-}
-
-int pdmpc_controller_run(pdmpc_controller* c, int32_t n_steps, double* ms) {
-    return timed_steps(n_steps, ms, [&] { return pdmpc_controller_step(c); });
-}
-
-int pdmpc_controller_problem(pdmpc_controller* c, int32_t* n, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index,
-                             const pdmpc_polygon_set** fallback, const int32_t** order, const int32_t** levels) {
-    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
-    if (n) *n = c->n;
-    if (in) *in = c->in.data();
-    if (pred_offset) *pred_offset = c->pred_offset.data();
-    if (pred_index) *pred_index = c->pred_index.data();
-    if (fallback) *fallback = c->fb.data();
-    if (order) *order = c->order.data();
-    if (levels) *levels = c->levels.data();
-    return PDMPC_OK;
-}
-
-int pdmpc_controller_state(pdmpc_controller* c, double* x, double* y, double* yaw, double* speed, double* steering, int32_t* needs_fallback, int32_t* time_step) {
-    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
-    for (int i = 0; i < c->n; ++i) {
-        if (x) x[i] = c->mx[i];
-        if (y) y[i] = c->my[i];
-        if (yaw) yaw[i] = c->myaw[i];
-        if (speed) speed[i] = c->mspeed[i];
-        if (steering) steering[i] = c->msteer[i];
-        if (needs_fallback) needs_fallback[i] = c->info_old[i].present && c->info_old[i].needs_fallback;
-    }
-    if (time_step) *time_step = c->k;
-    return PDMPC_OK;
-}
-
-// PrioritizedExplorativeController.computation_level_permutations (:241-309): n_perm x n_levels table, row-major, row 0 = 1..n;
-// rows up to n_levels form a Latin square built "fewest possibilities first" with random choices from
-// RandStream("mt19937ar", Seed = seed) / randi (:249, :283-286), a row that meets a dead end is drawn again; further rows
-// (the reference stops at n_levels; BASELINE config C5 asks for 64) are Fisher-Yates shuffles from the same stream.
-// The twin of pdmpc.explorative.computation_level_permutations.
-int pdmpc_exploration_permutations(int32_t n_levels, int32_t n_perm, uint32_t seed, int32_t* out) {
-    if (n_levels < 1 || n_perm < 1 || !out) return cfail(nullptr, PDMPC_ERR_INVALID, "bad argument");
-    Mt19937ar rng(seed);
-    const int n = n_levels;
-    std::vector<std::vector<int32_t>> rows;
-    rows.emplace_back();
-    for (int j = 0; j < n; ++j) rows[0].push_back(j + 1);
-    while ((int)rows.size() < std::min(n_perm, n_levels)) {
-        std::vector<uint8_t> allowed((size_t)n * n, 1);  // [level][class]
-        for (int col = 0; col < n; ++col)
-            for (const auto& r : rows) allowed[(size_t)(r[(size_t)col] - 1) * n + col] = 0;
-        std::vector<int32_t> perm((size_t)n, 0);
-        bool ok = true;
-        for (int filled = 0; filled < n && ok; ++filled) {
-            int best_col = 0, best_cnt = n + 1;
-            for (int col = 0; col < n; ++col) {  // [n_possibilities, i_cell] = min(sum(is_level_allowed, 1)): the first minimum
-                int cnt = 0;
-                for (int l = 0; l < n; ++l) cnt += allowed[(size_t)l * n + col];
-                if (cnt < best_cnt) {
-                    best_cnt = cnt;
-                    best_col = col;
-                }
-            }
-            if (best_cnt == 0) {
-                ok = false;
-                break;
-            }
-            const int pick = rng.randi(best_cnt);  // 1-based position among find(is_level_allowed(:, i_cell))
-            int lvl = -1;
-            for (int l = 0, seen = 0; l < n; ++l)
-                if (allowed[(size_t)l * n + best_col] && ++seen == pick) {
-                    lvl = l;
-                    break;
-                }
-            perm[(size_t)best_col] = lvl + 1;
-            for (int col = 0; col < n; ++col) allowed[(size_t)lvl * n + col] = 0;
-            for (int l = 0; l < n; ++l) allowed[(size_t)l * n + best_col] = 1;
-        }
-        if (ok) rows.push_back(perm);
-    }
-    while ((int)rows.size() < n_perm) {
-        std::vector<int32_t> perm((size_t)n);
-        for (int j = 0; j < n; ++j) perm[(size_t)j] = j + 1;
-        for (int i = n - 1; i > 0; --i) std::swap(perm[(size_t)i], perm[(size_t)(rng.randi(i + 1) - 1)]);
-        rows.push_back(perm);
-    }
-    for (int p = 0; p < n_perm; ++p)
-        for (int j = 0; j < n; ++j) out[(size_t)p * n + j] = rows[(size_t)p][(size_t)j];
-    return PDMPC_OK;
-}
-
-// ---- the explorative step (SURVEY.md 8(f)-2; twin of pdmpc.explorative.build_exploration_batch / choose_solution / explore_step)
-// PrioritizedExplorativeController.m:25-91: the step's traffic state under n_perm prioritizations, one flattened batch: instance p
-// permutes the computation levels of the base prioritization (prepare_permutation :42-58: a vehicle of level L gets the position
-// of L in permutation p as its priority), slots ordered by (level, instance, slot).  Advances the time step like build_step.
-namespace {
+// ---- the batch of prioritizations of an explorative or optimal-priority step: its instances, kept and flattened
 struct Exploring {  // (the memos of the obstacle sets are on while a step's prioritizations are assembled)
     pdmpc_controller* c;
     explicit Exploring(pdmpc_controller* ctl) : c(ctl) { c->exploring = true; }
@@ -1700,29 +1330,22 @@ struct Exploring {  // (the memos of the obstacle sets are on while a step's pri
 // the batch of K instances: sized before the first keep_instance (copies into vectors that are kept from step to step: no allocation
 // once warm)
 void begin_instances(pdmpc_controller* c, int K) {
-    if (c->x_parts.size() < (size_t)K) c->x_parts.resize((size_t)K);
+    if (c->inst_prob.size() < (size_t)K) c->inst_prob.resize((size_t)K);
     if (c->inst.size() != (size_t)K) c->inst.resize((size_t)K);
 }
 
 // the problem assemble_step just left in the controller becomes instance p
 void keep_instance(pdmpc_controller* c, int p) {
-    pdmpc_controller::Part& P = c->x_parts[(size_t)p];
-    P.in = c->in;
-    P.fb = c->fb;
-    P.pred_offset = c->pred_offset;
-    P.pred_index = c->pred_index;
-    pdmpc_controller::Instance& I = c->inst[(size_t)p];
-    I.directed = c->directed;
-    I.directed_seq = c->directed_seq;
-    I.levels = c->levels;
-    I.order = c->order;
-    I.slot_of = c->slot_of;
+    c->inst_prob[(size_t)p] = c->prob;
+    c->inst_prob[(size_t)p].seeds.clear();  // (they are those of the step's own slot order, which need not be the instance's)
+    c->inst[(size_t)p] = c->pri;
 }
 
-// flatten instances 0 .. K-1 into one batch, slots ordered by (level, instance, slot); then instance 0 is the controller's problem again
+// flatten instances 0 .. K-1 into one batch, slots ordered by (level, instance, slot), and seed it; then instance 0 is the controller's
+// problem again
 void flatten_instances(pdmpc_controller* c, int K) {
     const int n = c->n;
-    const std::vector<pdmpc_controller::Part>& parts = c->x_parts;
+    StepProblem& X = c->x_prob;
     struct Key {
         int32_t level, p, s;
     };
@@ -1733,42 +1356,35 @@ void flatten_instances(pdmpc_controller* c, int K) {
     const int N = K * n;
     std::vector<int32_t> slot_of((size_t)N);  // [p * n + s]
     for (int i = 0; i < N; ++i) slot_of[(size_t)flat[(size_t)i].p * n + flat[(size_t)i].s] = i;
-    c->x_in.resize((size_t)N);
-    c->x_fb.resize((size_t)N);
-    c->x_pred_offset.assign((size_t)N + 1, 0);
-    c->x_pred_index.clear();
+    X.in.resize((size_t)N);
+    X.fb.resize((size_t)N);
+    X.pred_offset.assign((size_t)N + 1, 0);
+    X.pred_index.clear();
     c->x_instance.resize((size_t)N);
     c->x_vehicle.resize((size_t)N);
     c->x_level.resize((size_t)N);
     c->x_slot.assign((size_t)N, 0);
     for (int i = 0; i < N; ++i) {
         const Key& k = flat[(size_t)i];
-        const pdmpc_controller::Part& P = parts[(size_t)k.p];
-        c->x_in[(size_t)i] = P.in[(size_t)k.s];
-        c->x_fb[(size_t)i] = P.fb[(size_t)k.s];
-        for (int32_t q = P.pred_offset[(size_t)k.s]; q < P.pred_offset[(size_t)k.s + 1]; ++q) c->x_pred_index.push_back(slot_of[(size_t)k.p * n + P.pred_index[(size_t)q]]);
-        c->x_pred_offset[(size_t)i + 1] = (int32_t)c->x_pred_index.size();
+        const StepProblem& P = c->inst_prob[(size_t)k.p];
+        X.in[(size_t)i] = P.in[(size_t)k.s];
+        X.fb[(size_t)i] = P.fb[(size_t)k.s];
+        for (int32_t q = P.pred_offset[(size_t)k.s]; q < P.pred_offset[(size_t)k.s + 1]; ++q) X.pred_index.push_back(slot_of[(size_t)k.p * n + P.pred_index[(size_t)q]]);
+        X.pred_offset[(size_t)i + 1] = (int32_t)X.pred_index.size();
         c->x_instance[(size_t)i] = k.p;
         c->x_vehicle[(size_t)i] = c->inst[(size_t)k.p].order[(size_t)k.s];
         c->x_level[(size_t)i] = k.level;
         c->x_slot[(size_t)k.p * n + c->x_vehicle[(size_t)i]] = i;
     }
-    c->x_pred_index.push_back(0);
-    // the controller's own problem again (instance 0)
-    c->in = parts[0].in;
-    c->fb = parts[0].fb;
-    c->pred_offset = parts[0].pred_offset;
-    c->pred_index = parts[0].pred_index;
-    const pdmpc_controller::Instance& I0 = c->inst[0];
-    c->directed = I0.directed;
-    c->directed_seq = I0.directed_seq;
-    c->levels = I0.levels;
-    c->order = I0.order;
-    c->slot_of = I0.slot_of;
+    X.pred_index.push_back(0);
+    set_seeds(c, X, c->x_vehicle);
+    c->batch_built_last = true;
+    // the controller's own problem again (instance 0), with the seeds of its slots
+    c->prob = c->inst_prob[0];
+    c->pri = c->inst[0];
+    set_seeds(c, c->prob, c->pri.order);
 }
-}  // namespace
 
-namespace {
 // pdmpc_controller_explore_build behind its pdmpc_controller_build_step (build_members runs that part for all its members at once, then
 // this one per member): the step just built is instance 0, instances 1 .. n_perm - 1 permute its computation levels
 int permute_instances(pdmpc_controller* c, int32_t n_perm, uint32_t seed) {
@@ -1777,7 +1393,7 @@ int permute_instances(pdmpc_controller* c, int32_t n_perm, uint32_t seed) {
     // base levels: the computation levels of the controller's own prioritization -- kahn of the sequential coupling the step was
     // just built with, whatever the priority strategy (PrioritizedExplorativeController.m prepare_permutation :42-58 permutes
     // kahn(iter.directed_coupling_sequential))
-    const std::vector<int32_t> levels0 = c->levels;
+    const std::vector<int32_t> levels0 = c->pri.levels;
     const int n_levels = *std::max_element(levels0.begin(), levels0.end());
     std::vector<int32_t> perms((size_t)n_perm * n_levels);
     rc = pdmpc_exploration_permutations(n_levels, n_perm, seed, perms.data());
@@ -1791,17 +1407,16 @@ int permute_instances(pdmpc_controller* c, int32_t n_perm, uint32_t seed) {
         // prepare_permutation (:64-77): every coupling i -> j of the base prioritization whose permuted levels invert it is swapped
         // in ALL coupling matrices (swap_entries_all_coupling_matrices): a sequential coupling stays sequential, a parallel one
         // (cut by the grouping, or between vehicles of one level) stays parallel and keeps its direction
-        const pdmpc_controller::Instance& I0 = c->inst[0];
-        c->directed = I0.directed;
-        c->directed_seq = I0.directed_seq;
+        const Instance& I0 = c->inst[0];
+        c->pri.take_couplings(I0);
         for (int i = 0; i < n; ++i)
             for (int j = 0; j < n; ++j)
                 if (at(I0.directed, n, i, j) && where[(size_t)levels0[i]] > where[(size_t)levels0[j]]) {
-                    at(c->directed, n, i, j) = 0;
-                    at(c->directed, n, j, i) = 1;
+                    at(c->pri.directed, n, i, j) = 0;
+                    at(c->pri.directed, n, j, i) = 1;
                     if (at(I0.directed_seq, n, i, j)) {
-                        at(c->directed_seq, n, i, j) = 0;
-                        at(c->directed_seq, n, j, i) = 1;
+                        at(c->pri.directed_seq, n, i, j) = 0;
+                        at(c->pri.directed_seq, n, j, i) = 1;
                     }
                 }
         rc = assemble_step(c, true);
@@ -1809,13 +1424,10 @@ int permute_instances(pdmpc_controller* c, int32_t n_perm, uint32_t seed) {
         keep_instance(c, p);
     }
     flatten_instances(c, n_perm);
-    set_seeds(c, c->x_vehicle);
     return PDMPC_OK;
 }
-}  // namespace
 
 // ---- ONE step preparation over a span of members: a sweep's members, or the one controller that steps alone
-namespace {
 // the poses of the members `who` one after the other (and their lanelet polygons: with_lanelets)
 void gather(pdmpc_controller* const* members, PrepScratch::Call& C, const std::vector<int>& who, bool with_lanelets) {
     C.who = who;
@@ -2083,57 +1695,8 @@ int build_members(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, i
     }
     return PDMPC_OK;
 }
-}  // namespace
 
-// Everything one launch needs to plan the whole time step (controller.py: build_step_problem): vehicles in level order
-// (slot = position), per-slot predecessor slots, per-slot areas to publish on exhaustion.  A step alone is a sweep of one member.
-int pdmpc_controller_build_step(pdmpc_controller* c) {
-    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
-    const int rc = build_members(c->h, &c, 1, 0, c->prep);
-    if (rc) c->err = g_cerr;
-    return rc;
-}
-
-int pdmpc_controller_explore_build(pdmpc_controller* c, int32_t n_perm, uint32_t seed) {
-    if (!c || n_perm < 1) return cfail(c, PDMPC_ERR_INVALID, "bad argument");
-    Exploring exploring(c);
-    int rc = pdmpc_controller_build_step(c);  // instance 0: the controller's own prioritization
-    if (rc) return rc;
-    return permute_instances(c, n_perm, seed);
-}
-int pdmpc_controller_explore_problem(pdmpc_controller* c, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index,
-                                     const pdmpc_polygon_set** fallback, const int32_t** instance, const int32_t** vehicle, const int32_t** level) {
-    if (!c || c->x_in.empty()) return cfail(c, PDMPC_ERR_INVALID, "no exploration batch has been built");
-    if (n_slots) *n_slots = (int32_t)c->x_in.size();
-    if (in) *in = c->x_in.data();
-    if (pred_offset) *pred_offset = c->x_pred_offset.data();
-    if (pred_index) *pred_index = c->x_pred_index.data();
-    if (fallback) *fallback = c->x_fb.data();
-    if (instance) *instance = c->x_instance.data();
-    if (vehicle) *vehicle = c->x_vehicle.data();
-    if (level) *level = c->x_level.data();
-    return PDMPC_OK;
-}
-
-// compute_solution_cost / choose_solution (:94-176): per weakly connected sub-graph of the coupling graph the instance with the
-// smallest sum of the cost-to-come of the vehicles' final nodes after round(., 8); a vehicle whose search was exhausted makes its
-// instance infinitely expensive.  chosen[v] = instance of vehicle v's sub-graph; cost (may be NULL): n_perm x n_graphs, graphs
-// ordered by their smallest vehicle.  The chosen instances' couplings become the controller's (what apply's fallback handling sees).
-namespace {
-int explore_choose_on(pdmpc_controller* c, const int32_t* status, const double* final_cost, int32_t* chosen, int32_t* n_graphs, double* cost);
-}
-int pdmpc_controller_explore_choose(pdmpc_controller* c, const pdmpc_vehicle_out* recs, int32_t* chosen, int32_t* n_graphs, double* cost) {
-    if (!c || !recs || c->inst.empty()) return cfail(c, PDMPC_ERR_INVALID, "no exploration batch has been built");
-    const int N = (int)c->inst.size() * c->n;
-    std::vector<int32_t> st((size_t)N);
-    std::vector<double> fc((size_t)N);
-    for (int s = 0; s < N; ++s) {
-        st[(size_t)s] = recs[s].status;
-        fc[(size_t)s] = recs[s].path_nodes[c->Hp][4];
-    }
-    return explore_choose_on(c, st.data(), fc.data(), chosen, n_graphs, cost);
-}
-namespace {
+// ---- the choice among the plans of a batch, and the step over a batch
 // The explorative choice as data: graph g = a weakly connected sub-graph (ordered by smallest vehicle), its candidates the n_perm
 // instances, cell (g, p) = the slots of instance p whose vehicles belong to g in ascending slot order (the order the twin adds in).
 void explore_describe(pdmpc_controller* c, ChoiceLists& D) {
@@ -2169,8 +1732,21 @@ void explore_describe(pdmpc_controller* c, ChoiceLists& D) {
     for (int s = 0; s < N; ++s) D.cell_slot[(size_t)fill[(size_t)cell_of(s)]++] = s;
     D.clear_picks();
 }
+// every vehicle goes on with the couplings of the instance it chose (obj.iter = obj.iter_array_tmp{chosen_solution},
+// PrioritizedExplorativeController.m:157-158, PrioritizedOptimalController.m:100): its rows of both matrices -- follow_own (the step
+// applies the plans of the controller's OWN prioritization whatever was chosen): the couplings of instance 0 again, which is what
+// apply's fallback handling then sees
+void adopt_chosen_couplings(pdmpc_controller* c, bool follow_own) {
+    if (follow_own) return c->pri.take_couplings(c->inst[0]);
+    const size_t n = (size_t)c->n;
+    for (size_t i = 0; i < n; ++i) {
+        const Instance& I = c->inst[(size_t)c->x_chosen[i]];
+        std::copy_n(I.directed.begin() + i * n, n, c->pri.directed.begin() + i * n);
+        std::copy_n(I.directed_seq.begin() + i * n, n, c->pri.directed_seq.begin() + i * n);
+    }
+}
 // ... and what the sub-graphs chose becomes the controller's: cost table n_perm x n_graphs, the instance per vehicle, its couplings
-void explore_adopt(pdmpc_controller* c, const ChoiceLists& D, const int32_t* chosen, const double* cell_cost) {
+void explore_adopt(pdmpc_controller* c, const ChoiceLists& D, const int32_t* chosen, const double* cell_cost, bool follow_own) {
     const int n = c->n, K = (int)c->inst.size(), G = D.n_graphs();
     c->x_graphs = G;
     c->x_cost.resize((size_t)K * G);
@@ -2178,65 +1754,104 @@ void explore_adopt(pdmpc_controller* c, const ChoiceLists& D, const int32_t* cho
         for (int g = 0; g < G; ++g) c->x_cost[(size_t)p * G + g] = cell_cost[(size_t)g * K + p];
     c->x_chosen.resize((size_t)n);
     for (int i = 0; i < n; ++i) c->x_chosen[(size_t)i] = chosen[(size_t)D.graph_of[(size_t)i]];
-    // obj.iter = obj.iter_array_tmp{chosen_solution} (:157-158): every vehicle goes on with the couplings of its sub-graph's choice
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j) {
-            const pdmpc_controller::Instance& I = c->inst[(size_t)c->x_chosen[(size_t)i]];
-            at(c->directed, n, i, j) = at(I.directed, n, i, j);
-            at(c->directed_seq, n, i, j) = at(I.directed_seq, n, i, j);
-        }
+    adopt_chosen_couplings(c, follow_own);
 }
 
 // How a step over a batch of prioritizations chooses: the description of its choice (cells and graphs) and what adopts the result.
 struct BatchChoice {
     void (*describe)(pdmpc_controller*, ChoiceLists&);
-    void (*adopt)(pdmpc_controller*, const ChoiceLists&, const int32_t*, const double*);
+    void (*adopt)(pdmpc_controller*, const ChoiceLists&, const int32_t*, const double*, bool follow_own);
     bool graph_per_vehicle;  // the optimal-priority choice: vehicle v's graph is graph v (else its sub-graph)
 };
 // the choice on the host twin (status and cost-to-come of the final node per slot of the batch: all the choice looks at)
-int choose_on_host(pdmpc_controller* c, const BatchChoice& how, const int32_t* status, const double* final_cost) {
+int choose_on_host(pdmpc_controller* c, const BatchChoice& how, const int32_t* status, const double* final_cost, bool follow_own) {
     ChoiceLists& D = c->choice;
     how.describe(c, D);
     c->choice_chosen.resize((size_t)D.n_graphs());
     c->choice_cost.resize((size_t)D.n_cells());
     const pdmpc_choice ch = D.view();
-    const int rc = pdmpc_choose_host((int32_t)c->x_in.size(), status, final_cost, &ch, c->choice_chosen.data(), c->choice_cost.data());
+    const int rc = pdmpc_choose_host(c->x_prob.n(), status, final_cost, &ch, c->choice_chosen.data(), c->choice_cost.data());
     if (rc) return cfail(c, rc, pdmpc_last_error());
-    how.adopt(c, D, c->choice_chosen.data(), c->choice_cost.data());
+    how.adopt(c, D, c->choice_chosen.data(), c->choice_cost.data(), follow_own);
     return PDMPC_OK;
 }
-// the picks of a step that keeps the chosen plans only: per slot of the controller's own order its vehicle's record of the chosen
-// instance, or (follow_own) of instance 0
+// ... from the first N records of the batch: their status and the cost-to-come of their final node
+int choose_from_records(pdmpc_controller* c, const BatchChoice& how, const pdmpc_vehicle_out* recs, int N, bool follow_own) {
+    c->x_status.resize((size_t)N);
+    c->x_final_cost.resize((size_t)N);
+    for (int s = 0; s < N; ++s) {
+        c->x_status[(size_t)s] = recs[s].status;
+        c->x_final_cost[(size_t)s] = recs[s].path_nodes[c->Hp][4];
+    }
+    return choose_on_host(c, how, c->x_status.data(), c->x_final_cost.data(), follow_own);
+}
+
+// Reading a batch's records back into the controller's own slot order.  The slot in the batch of the record vehicle v keeps if it goes
+// on with instance p -- follow_own: the record of instance 0, whatever it goes on with
+inline int32_t kept_slot(const pdmpc_controller* c, bool follow_own, int p, int v) { return c->x_slot[(size_t)(follow_own ? 0 : p) * c->n + v]; }
+// ... once the choice is made: of the vehicle in slot s of the controller's own order
+inline int32_t kept_slot_at(const pdmpc_controller* c, bool follow_own, int s) {
+    const int v = c->pri.order[(size_t)s];
+    return kept_slot(c, follow_own, c->x_chosen[(size_t)v], v);
+}
+// ... those records out of the records of the whole batch (c->x_out) as the step's records (c->out)
+void gather_kept_records(pdmpc_controller* c, bool follow_own) {
+    c->out.resize((size_t)c->n);
+    for (int s = 0; s < c->n; ++s) c->out[(size_t)s] = c->x_out[(size_t)kept_slot_at(c, follow_own, s)];
+}
+// ... and before the choice is made, the picks of a step that chooses on the device and keeps the chosen plans only: per slot of the
+// controller's own order the records its vehicle may keep, one per instance
 void pick_chosen_plans(pdmpc_controller* c, ChoiceLists& D, bool follow_own, bool graph_per_vehicle) {
     const int n = c->n, K = (int)c->inst.size();
     D.clear_picks();
     for (int s = 0; s < n; ++s) {
-        const int v = c->order[(size_t)s];
+        const int v = c->pri.order[(size_t)s];
         D.pick_graph.push_back(follow_own ? -1 : (graph_per_vehicle ? v : D.graph_of[(size_t)v]));
-        for (int p = 0; p < (follow_own ? 1 : K); ++p) D.pick_slot.push_back(c->x_slot[(size_t)p * n + v]);
+        for (int p = 0; p < (follow_own ? 1 : K); ++p) D.pick_slot.push_back(kept_slot(c, follow_own, p, v));
         D.pick_offset.push_back((int32_t)D.pick_slot.size());
     }
 }
+
 const BatchChoice kExploreChoice = {explore_describe, explore_adopt, false};
 
-int explore_choose_on(pdmpc_controller* c, const int32_t* status, const double* final_cost, int32_t* chosen, int32_t* n_graphs, double* cost) {
-    if (const int rc = choose_on_host(c, kExploreChoice, status, final_cost)) return rc;
-    if (chosen) std::copy(c->x_chosen.begin(), c->x_chosen.end(), chosen);
-    if (n_graphs) *n_graphs = c->x_graphs;
-    if (cost) std::copy(c->x_cost.begin(), c->x_cost.end(), cost);
-    return PDMPC_OK;
+// compute_solution_cost / receive_solution_cost / choose_solution (:56-114): every vehicle sums the solution costs of ALL vehicles per
+// instance (its own first, then the others' messages in ascending index), rounds to 8 decimals and takes the first minimum
+// The optimal-priority choice as data: graph v = vehicle v, its candidates the K instances, cell (v, p) = vehicle v's slot of instance p,
+// then the other vehicles' slots of instance p in ascending vehicle index
+void optimal_describe(pdmpc_controller* c, ChoiceLists& D) {
+    const int n = c->n, K = (int)c->inst.size();
+    D.graph_of.clear();
+    D.graph_offset.resize((size_t)n + 1);
+    for (int v = 0; v <= n; ++v) D.graph_offset[(size_t)v] = v * K;
+    D.cell_offset.resize((size_t)n * K + 1);
+    for (int q = 0; q <= n * K; ++q) D.cell_offset[(size_t)q] = q * n;
+    D.cell_slot.resize((size_t)n * K * n);
+    int32_t* slot = D.cell_slot.data();
+    for (int v = 0; v < n; ++v)
+        for (int p = 0; p < K; ++p) {
+            *slot++ = c->x_slot[(size_t)p * n + v];
+            for (int j = 0; j < n; ++j)
+                if (j != v) *slot++ = c->x_slot[(size_t)p * n + j];
+        }
+    D.clear_picks();
 }
-}  // namespace
+void optimal_adopt(pdmpc_controller* c, const ChoiceLists&, const int32_t* chosen, const double* cell_cost, bool follow_own) {
+    const int n = c->n, K = (int)c->inst.size();
+    c->x_cost.assign(cell_cost, cell_cost + (size_t)n * K);  // row v = vehicle v's sums
+    c->x_chosen.assign(chosen, chosen + n);
+    c->x_graphs = K;
+    adopt_chosen_couplings(c, follow_own);
+}
+const BatchChoice kOptimalChoice = {optimal_describe, optimal_adopt, true};
 
 // One time step over a batch of prioritizations (explorative or optimal): the batch is built, ONE launch plans all of it, `choose`
 // picks per vehicle the instance it goes on with (c->x_chosen), and the chosen plans are applied.
-namespace {
 int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, bool follow_own, const BatchChoice& how) {
     c->timing[0] = ms_since(t);
-    const int N = (int)c->x_in.size();
-    auto plan = [&](auto&& call) {
-        const int rc = plan_built(c->h, N, c->last_pops.size() == (size_t)c->n, c->weights, [&](int s) { return c->last_pops[(size_t)c->x_vehicle[(size_t)s]]; }, c->optimizer,
-                                  c->seeds, c->timing, call);
+    const int N = c->x_prob.n();
+    auto plan = [&](auto call, auto... rest) {
+        const int rc = plan_built(c->h, c->x_prob, c->last_pops.size() == (size_t)c->n, [&](int s) { return c->last_pops[(size_t)c->x_vehicle[(size_t)s]]; }, c->optimizer,
+                                  c->timing, call, rest...);
         t = std::chrono::steady_clock::now();
         return own(c, rc);
     };
@@ -2252,58 +1867,467 @@ int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, boo
         c->choice_cost.resize((size_t)D.n_cells());
         c->out.resize((size_t)c->n);
         const pdmpc_choice ch = D.view();
-        rc = plan([&] {
-            return pdmpc_plan_step_chosen(c->h, N, c->x_in.data(), c->x_pred_offset.data(), c->x_pred_index.data(), c->x_fb.data(), &ch, c->choice_chosen.data(),
-                                          c->choice_cost.data(), c->out.data());
-        });
+        rc = plan(pdmpc_plan_step_chosen, &ch, c->choice_chosen.data(), c->choice_cost.data(), c->out.data());
         if (rc) return rc;
-        how.adopt(c, D, c->choice_chosen.data(), c->choice_cost.data());
+        how.adopt(c, D, c->choice_chosen.data(), c->choice_cost.data(), follow_own);
     } else if (c->lean_explore) {
         // the closed loop keeps the chosen plans only (obj.iter = obj.iter_array_tmp{chosen_solution}, :157-158): status and final
         // cost of every plan come back for the choice, the chosen vehicles' records afterwards — not 2.9 KB for each of the N plans
         c->x_out.clear();
         c->x_status.resize((size_t)N);
         c->x_final_cost.resize((size_t)N);
-        rc = plan([&] {
-            return pdmpc_plan_step_lean(c->h, N, c->x_in.data(), c->x_pred_offset.data(), c->x_pred_index.data(), c->x_fb.data(), c->x_status.data(), c->x_final_cost.data());
-        });
+        rc = plan(pdmpc_plan_step_lean, c->x_status.data(), c->x_final_cost.data());
         if (rc) return rc;
-        rc = choose_on_host(c, how, c->x_status.data(), c->x_final_cost.data());
+        rc = choose_on_host(c, how, c->x_status.data(), c->x_final_cost.data(), follow_own);
         if (rc) return rc;
         std::vector<int32_t> want((size_t)c->n);
-        for (int s = 0; s < c->n; ++s) {
-            const int v = c->order[(size_t)s];
-            want[(size_t)s] = c->x_slot[(size_t)(follow_own ? 0 : c->x_chosen[(size_t)v]) * c->n + v];
-        }
+        for (int s = 0; s < c->n; ++s) want[(size_t)s] = kept_slot_at(c, follow_own, s);
         c->out.resize((size_t)c->n);
         rc = pdmpc_fetch_records_at(c->h, c->n, want.data(), c->out.data());
         if (rc) return cfail(c, rc, pdmpc_last_error());
     } else {
         c->x_out.resize((size_t)N);
-        rc = plan([&] { return pdmpc_plan_step(c->h, N, c->x_in.data(), c->x_pred_offset.data(), c->x_pred_index.data(), c->x_fb.data(), c->x_out.data()); });
+        rc = plan(pdmpc_plan_step, c->x_out.data());
         if (rc) return rc;
-        c->x_status.resize((size_t)N);
-        c->x_final_cost.resize((size_t)N);
-        for (int s = 0; s < N; ++s) {
-            c->x_status[(size_t)s] = c->x_out[(size_t)s].status;
-            c->x_final_cost[(size_t)s] = c->x_out[(size_t)s].path_nodes[c->Hp][4];
-        }
-        rc = choose_on_host(c, how, c->x_status.data(), c->x_final_cost.data());
+        rc = choose_from_records(c, how, c->x_out.data(), N, follow_own);
         if (rc) return rc;
-        c->out.resize((size_t)c->n);
-        for (int s = 0; s < c->n; ++s) {
-            const int v = c->order[(size_t)s];
-            c->out[(size_t)s] = c->x_out[(size_t)c->x_slot[(size_t)(follow_own ? 0 : c->x_chosen[(size_t)v]) * c->n + v]];
-        }
-    }
-    if (follow_own) {  // (the couplings of instance 0 again: what apply's fallback handling sees)
-        c->directed = c->inst[0].directed;
-        c->directed_seq = c->inst[0].directed_seq;
+        gather_kept_records(c, follow_own);
     }
     c->timing[4] = ms_since(t);  // (from the backend call's return on)
     return apply_and_account(c);
 }
+
 }  // namespace
+
+extern "C" {
+
+const char* pdmpc_controller_last_error(void) { return g_cerr.c_str(); }
+
+int pdmpc_controller_create(pdmpc_handle* handle, const pdmpc_controller_config* cfg, const pdmpc_scenario* sc, pdmpc_controller** out) {
+    if (!cfg || !sc || !out) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
+    if (sc->n_vehicles < 1 || cfg->Hp < 1 || cfg->Hp > PDMPC_HP_MAX || sc->n_trims < 1) return cfail(nullptr, PDMPC_ERR_INVALID, "bad sizes");
+    if (cfg->priority_strategy < PDMPC_PRIORITY_CONSTANT || cfg->priority_strategy > PDMPC_PRIORITY_FCA) return cfail(nullptr, PDMPC_ERR_INVALID, "unknown priority strategy");
+    if (cfg->weight_strategy < PDMPC_WEIGHT_DISTANCE || cfg->weight_strategy > PDMPC_WEIGHT_RANDOM) return cfail(nullptr, PDMPC_ERR_INVALID, "unknown weight strategy");
+    if (handle) {
+        // the backend reads Hp entries of every reference and writes one record per vehicle: a handle created for another
+        // horizon or a smaller batch must not be driven by this controller
+        pdmpc_config hc{};
+        int32_t has_mpa = 0;
+        if (pdmpc_get_config(handle, &hc, &has_mpa) != PDMPC_OK) return cfail(nullptr, PDMPC_ERR_INVALID, "bad backend handle");
+        if (hc.Hp != cfg->Hp) return cfail(nullptr, PDMPC_ERR_INVALID, "the handle was created for another horizon (config.Hp) than the controller");
+        if (hc.max_vehicles < sc->n_vehicles) return cfail(nullptr, PDMPC_ERR_CAPACITY, "the handle's max_vehicles is smaller than the scenario");
+        if (!has_mpa) return cfail(nullptr, PDMPC_ERR_NO_MPA, "pdmpc_upload_mpa has not been called on the handle");
+    }
+    pdmpc_controller* c = new pdmpc_controller();
+    c->h = handle;
+    c->cfg = *cfg;
+    c->n = sc->n_vehicles;
+    c->Hp = cfg->Hp;
+    c->trim_speed.assign(sc->trim_speed, sc->trim_speed + sc->n_trims);
+    c->trim_steering.assign(sc->trim_steering, sc->trim_steering + sc->n_trims);
+    for (int v = 0; v < c->n; ++v) {
+        VehicleDef d;
+        d.x_start = sc->x_start[v];
+        d.y_start = sc->y_start[v];
+        d.yaw_start = sc->yaw_start[v];
+        d.reference_speed = sc->reference_speed[v];
+        d.px.assign(sc->path_x + sc->path_offset[v], sc->path_x + sc->path_offset[v + 1]);
+        d.py.assign(sc->path_y + sc->path_offset[v], sc->path_y + sc->path_offset[v + 1]);
+        if (d.px.size() < 2) {
+            delete c;
+            return cfail(nullptr, PDMPC_ERR_INVALID, "a reference path needs at least two points");
+        }
+        if (sc->lanelets_offset) {
+            d.lanelets_index.assign(sc->lanelets_index + sc->lanelets_offset[v], sc->lanelets_index + sc->lanelets_offset[v + 1]);
+            d.points_index.assign(sc->points_index + sc->lanelets_offset[v], sc->points_index + sc->lanelets_offset[v + 1]);
+        }
+        d.is_loop = sc->is_loop ? sc->is_loop[v] != 0 : true;
+        d.tile_dx = sc->tile_dx ? sc->tile_dx[v] : 0.0;
+        d.tile_dy = sc->tile_dy ? sc->tile_dy[v] : 0.0;
+        c->veh.push_back(std::move(d));
+    }
+    for (int l = 0; l < sc->n_lanelets; ++l) {
+        Poly a, b;
+        a.x.assign(sc->left_x + sc->left_offset[l], sc->left_x + sc->left_offset[l + 1]);
+        a.y.assign(sc->left_y + sc->left_offset[l], sc->left_y + sc->left_offset[l + 1]);
+        b.x.assign(sc->right_x + sc->right_offset[l], sc->right_x + sc->right_offset[l + 1]);
+        b.y.assign(sc->right_y + sc->right_offset[l], sc->right_y + sc->right_offset[l + 1]);
+        c->bl_left.push_back(std::move(a));
+        c->bl_right.push_back(std::move(b));
+    }
+    for (int p = 0; p < sc->obstacles.n_polygons; ++p) {
+        Poly o;
+        o.x.assign(sc->obstacles.x + sc->obstacles.offset[p], sc->obstacles.x + sc->obstacles.offset[p + 1]);
+        o.y.assign(sc->obstacles.y + sc->obstacles.offset[p], sc->obstacles.y + sc->obstacles.offset[p + 1]);
+        c->static_obstacles.push_back(std::move(o));
+    }
+    c->fca_obst_off.assign(1, 0);
+    for (const Poly& o : c->static_obstacles) {
+        c->fca_obst_x.insert(c->fca_obst_x.end(), o.x.begin(), o.x.end());
+        c->fca_obst_y.insert(c->fca_obst_y.end(), o.y.begin(), o.y.end());
+        c->fca_obst_off.push_back((int32_t)c->fca_obst_x.size());
+    }
+    // Simulation.setup: initial speed = steering = 0 (Simulation.m:52-65)
+    c->mx.resize(c->n);
+    c->my.resize(c->n);
+    c->myaw.resize(c->n);
+    c->mspeed.assign(c->n, 0.0);
+    c->msteer.assign(c->n, 0.0);
+    for (int v = 0; v < c->n; ++v) {
+        c->mx[v] = c->veh[v].x_start;
+        c->my[v] = c->veh[v].y_start;
+        c->myaw[v] = c->veh[v].yaw_start;
+    }
+    c->info_old.assign(c->n, Plan());
+    c->infos.assign(c->n, Plan());
+    *out = c;
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_set_parallel_coupling(pdmpc_controller* c, int32_t mode) {
+    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
+    if (mode != PDMPC_PARALLEL_PREVIOUS_TRAJECTORY && mode != PDMPC_PARALLEL_REACHABLE_SETS) return cfail(c, PDMPC_ERR_INVALID, "unknown parallel coupling mode");
+    c->parallel_mode = mode;
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_set_optimizer(pdmpc_controller* c, int32_t which) {
+    if (!c) return cfail(c, PDMPC_ERR_INVALID, "null controller");
+    if (which != PDMPC_OPTIMIZER_GRAPH_SEARCH && which != PDMPC_OPTIMIZER_SAMPLED) return cfail(c, PDMPC_ERR_INVALID, "optimizer must be PDMPC_OPTIMIZER_GRAPH_SEARCH or PDMPC_OPTIMIZER_SAMPLED");
+    c->optimizer = which;
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_priorities(pdmpc_controller* c, int32_t* n_priorities, const int32_t** priorities, int32_t* n_collisions, const int32_t** collisions) {
+    if (!c || !n_priorities || !priorities || !n_collisions || !collisions) return cfail(c, PDMPC_ERR_INVALID, "null argument");
+    const bool has = c->cfg.priority_strategy != PDMPC_PRIORITY_COLORING, fca = c->cfg.priority_strategy == PDMPC_PRIORITY_FCA;
+    *n_priorities = has ? (int32_t)c->prio.size() : 0;
+    *priorities = c->prio.data();
+    *n_collisions = fca ? (int32_t)c->fca_count.size() : 0;
+    *collisions = c->fca_count.data();
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_seeds(pdmpc_controller* c, int32_t* n, const uint32_t** seeds) {
+    if (!c || !n || !seeds) return cfail(c, PDMPC_ERR_INVALID, "null argument");
+    const std::vector<uint32_t>& last = (c->batch_built_last ? c->x_prob : c->prob).seeds;
+    *n = (int32_t)last.size();
+    *seeds = last.data();
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_set_lanelet_bounding(pdmpc_controller* c, int32_t on) {
+    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
+    c->lanelet_bounding = on != 0;
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_set_reachability(pdmpc_controller* c, const pdmpc_mpa* mpa) {
+    if (!c || !mpa) return cfail(c, PDMPC_ERR_INVALID, "null argument");
+    if (mpa->Hp != c->Hp) return cfail(c, PDMPC_ERR_INVALID, "the automaton's Hp differs from the controller's");
+    if (mpa->n_trims != (int32_t)c->trim_speed.size()) return cfail(c, PDMPC_ERR_INVALID, "the automaton's trims differ from the scenario's");
+    c->has_reach = false;
+    std::vector<int32_t> off((size_t)mpa->n_trims * mpa->Hp + 1, 0);
+    int rc = pdmpc_local_reachable_sets(mpa, 0, off.data(), nullptr, nullptr);
+    if (rc != PDMPC_OK && rc != PDMPC_ERR_CAPACITY) return cfail(c, rc, "pdmpc_local_reachable_sets failed");
+    std::vector<double> x((size_t)off.back() + 1), y((size_t)off.back() + 1);
+    rc = pdmpc_local_reachable_sets(mpa, off.back(), off.data(), x.data(), y.data());
+    if (rc) return cfail(c, rc, "pdmpc_local_reachable_sets failed");
+    if (c->h) {
+        const pdmpc_polygon_set ps = view_polygons(off, x, y);
+        rc = pdmpc_upload_reachable_sets(c->h, mpa->n_trims, mpa->Hp, &ps);
+        if (rc) return cfail(c, rc, std::string("pdmpc_upload_reachable_sets: ") + pdmpc_last_error());
+    }
+    c->reach_off = std::move(off);
+    c->reach_x = std::move(x);
+    c->reach_y = std::move(y);
+    c->has_reach = true;
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_destroy(pdmpc_controller* c) {
+    delete c;
+    return PDMPC_OK;
+}
+
+// records of the step in slot order -> plans, exhaustion handling, fallbacks of coupled vehicles, plant update
+int pdmpc_controller_apply(pdmpc_controller* c, const pdmpc_vehicle_out* recs) {
+    if (!c || !recs) return cfail(c, PDMPC_ERR_INVALID, "null argument");
+    const int n = c->n, Hp = c->Hp;
+    auto fallback_plan = [&](int i, Plan& p) -> bool {  // plan_fallback (:678-718): the previous plan shifted by one step
+        const Plan& old = c->info_old[i];
+        if (!old.present) return false;
+        p.present = true;
+        const size_t m = old.shapes.size();
+        p.shapes.resize(m);
+        p.trims.resize(m);
+        p.yx.resize(m);
+        p.yy.resize(m);
+        p.yyaw.resize(m);
+        for (size_t q = 0; q < m; ++q) {
+            const size_t from = std::min(q + 1, m - 1);
+            p.shapes[q] = old.shapes[from];
+            p.trims[q] = old.trims[from];
+            p.yx[q] = old.yx[from];
+            p.yy[q] = old.yy[from];
+            p.yyaw[q] = old.yyaw[from];
+        }
+        return true;
+    };
+    // The step's plans are built in c->infos — nothing else reads it — and swapped with c->info_old at the end: an error status or a
+    // fallback in the first step leaves the controller's plans as they were, and the vectors of a plan keep their capacity from
+    // step to step (they are overwritten entry by entry, not re-created).
+    std::vector<Plan>& infos = c->infos;
+    infos.resize((size_t)n);
+    if (c->last_pops.size() != (size_t)n) c->last_pops.assign((size_t)n, 0.0);
+    for (int s = 0; s < n; ++s) {
+        const int i = c->pri.order[s];
+        const pdmpc_vehicle_out& r = recs[s];
+        if (r.status != PDMPC_OK && r.status != PDMPC_EXHAUSTED) return cfail(c, PDMPC_ERR_HIP, "a result record carries an error status: not a planning result");
+        Plan& p = infos[i];
+        p.present = p.needs_fallback = p.exhausted = false;
+        p.n_expanded = r.n_expanded;
+        c->last_pops[(size_t)i] = (double)r.n_popped;
+        if (r.status == PDMPC_OK) {
+            p.present = true;
+            p.shapes.resize((size_t)Hp);
+            p.trims.resize((size_t)Hp);
+            p.yx.resize((size_t)Hp);
+            p.yy.resize((size_t)Hp);
+            p.yyaw.resize((size_t)Hp);
+            for (int q = 0; q < Hp; ++q) {
+                Poly& sh = p.shapes[q];
+                sh.x.assign(r.shapes[q][0], r.shapes[q][0] + r.shape_cols[q]);
+                sh.y.assign(r.shapes[q][1], r.shapes[q][1] + r.shape_cols[q]);
+                p.trims[q] = r.predicted_trims[q];
+                p.yx[q] = r.y_predicted[q][0];
+                p.yy[q] = r.y_predicted[q][1];
+                p.yyaw[q] = r.y_predicted[q][2];
+            }
+        } else {  // PrioritizedController.m:344-352
+            p.exhausted = true;
+            const bool standstill = c->trim_speed[c->trims[i] - 1] == 0;
+            if (standstill && c->cfg.constraint_from_successor != PDMPC_SUCCESSOR_NONE) {  // handle_graph_search_exhaustion (:568-616)
+                p.present = true;
+                p.shapes.assign((size_t)Hp, c->occ_plain[i]);
+                p.trims.assign((size_t)Hp, c->trims[i]);
+                p.yx.assign((size_t)Hp, c->mx[i]);
+                p.yy.assign((size_t)Hp, c->my[i]);
+                p.yyaw.assign((size_t)Hp, c->myaw[i]);
+            } else {
+                if (!fallback_plan(i, p)) return cfail(c, PDMPC_ERR_INVALID, "a vehicle needs a fallback in its first step");
+                p.needs_fallback = true;
+            }
+        }
+    }
+    // handle_others_fallback / check_others_fallback
+    bool any = false;
+    for (int i = 0; i < n; ++i) any = any || infos[i].needs_fallback;
+    if (any) {
+        std::vector<int> fm((size_t)n * n, 0);
+        for (int a = 0; a < n; ++a)
+            for (int b = 0; b < n; ++b) {
+                int v = at(c->adjacency, n, a, b);
+                if (infos[a].needs_fallback && at(c->pri.directed_seq, n, a, b)) v -= 1;
+                if (infos[b].needs_fallback && at(c->pri.directed_seq, n, b, a)) v -= 1;
+                fm[(size_t)a * n + b] = v;
+            }
+        std::vector<uint8_t> reached(n, 0);
+        for (int f = 0; f < n; ++f) {
+            if (!infos[f].needs_fallback) continue;
+            std::vector<uint8_t> seen(n, 0);
+            std::vector<int> stack{f};
+            seen[f] = 1;
+            while (!stack.empty()) {
+                const int a = stack.back();
+                stack.pop_back();
+                for (int b = 0; b < n; ++b)
+                    if (fm[(size_t)a * n + b] != 0 && !seen[b]) {
+                        seen[b] = 1;
+                        stack.push_back(b);
+                    }
+            }
+            for (int v = 0; v < n; ++v) reached[v] |= seen[v];
+        }
+        for (int i = 0; i < n; ++i)
+            if (reached[i] && !infos[i].needs_fallback) {
+                Plan& p = infos[i];  // (keeps its search's n_expanded and exhausted)
+                if (!fallback_plan(i, p)) return cfail(c, PDMPC_ERR_INVALID, "a vehicle needs a fallback in its first step");
+                p.needs_fallback = false;  // plan_fallback(is_fallback_while_planning = false)
+            }
+    }
+    std::swap(c->info_old, c->infos);
+    // Simulation.apply (Simulation.m:86-100)
+    for (int i = 0; i < n; ++i) {
+        const Plan& p = c->info_old[i];
+        c->mx[i] = p.yx[0];
+        c->my[i] = p.yy[0];
+        c->myaw[i] = p.yyaw[0];
+        c->mspeed[i] = c->trim_speed[p.trims[0] - 1];
+        c->msteer[i] = c->trim_steering[p.trims[0] - 1];
+    }
+    return PDMPC_OK;
+}
+
+// One pass of HighLevelController.main_control_loop (:334-373) in simulation: build, plan on the GPU (one launch), apply.
+int pdmpc_controller_last_timing(pdmpc_controller* c, double* ms6) {
+    if (!c || !ms6) return cfail(c, PDMPC_ERR_INVALID, "null argument");
+    for (int i = 0; i < 6; ++i) ms6[i] = c->timing[i];
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_timing_sum(pdmpc_controller* c, double* ms6, int64_t* n_steps, int32_t reset) {
+    if (!c) return cfail(c, PDMPC_ERR_INVALID, "null argument");
+    if (ms6)
+        for (int i = 0; i < 6; ++i) ms6[i] = c->timing_sum[i];
+    if (n_steps) *n_steps = c->timing_steps;
+    if (reset) {
+        for (int i = 0; i < 6; ++i) c->timing_sum[i] = 0;
+        c->timing_steps = 0;
+    }
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_step(pdmpc_controller* c) {
+    if (!c || !c->h) return cfail(c, PDMPC_ERR_INVALID, "controller has no backend handle");
+    auto t = std::chrono::steady_clock::now();
+    int rc = pdmpc_controller_build_step(c);
+    if (rc) return rc;
+    c->timing[0] = ms_since(t);
+    c->timing[4] = 0;
+    c->out.resize(c->n);
+    rc = plan_built(c->h, c->prob, c->last_pops.size() == (size_t)c->n, [&](int s) { return c->last_pops[(size_t)c->pri.order[(size_t)s]]; }, c->optimizer, c->timing,
+                    pdmpc_plan_step, c->out.data());
+    if (rc) return own(c, rc);
+    return apply_and_account(c);
+}
+
+int pdmpc_controller_run(pdmpc_controller* c, int32_t n_steps, double* ms) {
+    return timed_steps(n_steps, ms, [&] { return pdmpc_controller_step(c); });
+}
+
+int pdmpc_controller_problem(pdmpc_controller* c, int32_t* n, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index,
+                             const pdmpc_polygon_set** fallback, const int32_t** order, const int32_t** levels) {
+    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
+    expose(c->prob, n, in, pred_offset, pred_index, fallback);
+    if (n) *n = c->n;  // (also before the first build)
+    if (order) *order = c->pri.order.data();
+    if (levels) *levels = c->pri.levels.data();
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_state(pdmpc_controller* c, double* x, double* y, double* yaw, double* speed, double* steering, int32_t* needs_fallback, int32_t* time_step) {
+    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
+    for (int i = 0; i < c->n; ++i) {
+        if (x) x[i] = c->mx[i];
+        if (y) y[i] = c->my[i];
+        if (yaw) yaw[i] = c->myaw[i];
+        if (speed) speed[i] = c->mspeed[i];
+        if (steering) steering[i] = c->msteer[i];
+        if (needs_fallback) needs_fallback[i] = c->info_old[i].present && c->info_old[i].needs_fallback;
+    }
+    if (time_step) *time_step = c->k;
+    return PDMPC_OK;
+}
+
+// PrioritizedExplorativeController.computation_level_permutations (:241-309): n_perm x n_levels table, row-major, row 0 = 1..n;
+// rows up to n_levels form a Latin square built "fewest possibilities first" with random choices from
+// RandStream("mt19937ar", Seed = seed) / randi (:249, :283-286), a row that meets a dead end is drawn again; further rows
+// (the reference stops at n_levels; BASELINE config C5 asks for 64) are Fisher-Yates shuffles from the same stream.
+// The twin of pdmpc.explorative.computation_level_permutations.
+int pdmpc_exploration_permutations(int32_t n_levels, int32_t n_perm, uint32_t seed, int32_t* out) {
+    if (n_levels < 1 || n_perm < 1 || !out) return cfail(nullptr, PDMPC_ERR_INVALID, "bad argument");
+    Mt19937ar rng(seed);
+    const int n = n_levels;
+    std::vector<std::vector<int32_t>> rows;
+    rows.emplace_back();
+    for (int j = 0; j < n; ++j) rows[0].push_back(j + 1);
+    while ((int)rows.size() < std::min(n_perm, n_levels)) {
+        std::vector<uint8_t> allowed((size_t)n * n, 1);  // [level][class]
+        for (int col = 0; col < n; ++col)
+            for (const auto& r : rows) allowed[(size_t)(r[(size_t)col] - 1) * n + col] = 0;
+        std::vector<int32_t> perm((size_t)n, 0);
+        bool ok = true;
+        for (int filled = 0; filled < n && ok; ++filled) {
+            int best_col = 0, best_cnt = n + 1;
+            for (int col = 0; col < n; ++col) {  // [n_possibilities, i_cell] = min(sum(is_level_allowed, 1)): the first minimum
+                int cnt = 0;
+                for (int l = 0; l < n; ++l) cnt += allowed[(size_t)l * n + col];
+                if (cnt < best_cnt) {
+                    best_cnt = cnt;
+                    best_col = col;
+                }
+            }
+            if (best_cnt == 0) {
+                ok = false;
+                break;
+            }
+            const int pick = rng.randi(best_cnt);  // 1-based position among find(is_level_allowed(:, i_cell))
+            int lvl = -1;
+            for (int l = 0, seen = 0; l < n; ++l)
+                if (allowed[(size_t)l * n + best_col] && ++seen == pick) {
+                    lvl = l;
+                    break;
+                }
+            perm[(size_t)best_col] = lvl + 1;
+            for (int col = 0; col < n; ++col) allowed[(size_t)lvl * n + col] = 0;
+            for (int l = 0; l < n; ++l) allowed[(size_t)l * n + best_col] = 1;
+        }
+        if (ok) rows.push_back(perm);
+    }
+    while ((int)rows.size() < n_perm) {
+        std::vector<int32_t> perm((size_t)n);
+        for (int j = 0; j < n; ++j) perm[(size_t)j] = j + 1;
+        for (int i = n - 1; i > 0; --i) std::swap(perm[(size_t)i], perm[(size_t)(rng.randi(i + 1) - 1)]);
+        rows.push_back(perm);
+    }
+    for (int p = 0; p < n_perm; ++p)
+        for (int j = 0; j < n; ++j) out[(size_t)p * n + j] = rows[(size_t)p][(size_t)j];
+    return PDMPC_OK;
+}
+
+// Everything one launch needs to plan the whole time step (controller.py: build_step_problem): vehicles in level order
+// (slot = position), per-slot predecessor slots, per-slot areas to publish on exhaustion.  A step alone is a sweep of one member.
+int pdmpc_controller_build_step(pdmpc_controller* c) {
+    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
+    const int rc = build_members(c->h, &c, 1, 0, c->prep);
+    if (rc) c->err = g_cerr;
+    return rc;
+}
+
+// ---- the explorative step (SURVEY.md 8(f)-2; twin of pdmpc.explorative.build_exploration_batch / choose_solution / explore_step)
+// PrioritizedExplorativeController.m:25-91: the step's traffic state under n_perm prioritizations, one flattened batch: instance p
+// permutes the computation levels of the base prioritization (prepare_permutation :42-58: a vehicle of level L gets the position
+// of L in permutation p as its priority), slots ordered by (level, instance, slot).  Advances the time step like build_step.
+int pdmpc_controller_explore_build(pdmpc_controller* c, int32_t n_perm, uint32_t seed) {
+    if (!c || n_perm < 1) return cfail(c, PDMPC_ERR_INVALID, "bad argument");
+    Exploring exploring(c);
+    int rc = pdmpc_controller_build_step(c);  // instance 0: the controller's own prioritization
+    if (rc) return rc;
+    return permute_instances(c, n_perm, seed);
+}
+int pdmpc_controller_explore_problem(pdmpc_controller* c, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index,
+                                     const pdmpc_polygon_set** fallback, const int32_t** instance, const int32_t** vehicle, const int32_t** level) {
+    if (!c || c->x_prob.in.empty()) return cfail(c, PDMPC_ERR_INVALID, "no exploration batch has been built");
+    expose(c->x_prob, n_slots, in, pred_offset, pred_index, fallback);
+    if (instance) *instance = c->x_instance.data();
+    if (vehicle) *vehicle = c->x_vehicle.data();
+    if (level) *level = c->x_level.data();
+    return PDMPC_OK;
+}
+
+// compute_solution_cost / choose_solution (:94-176): per weakly connected sub-graph of the coupling graph the instance with the
+// smallest sum of the cost-to-come of the vehicles' final nodes after round(., 8); a vehicle whose search was exhausted makes its
+// instance infinitely expensive.  chosen[v] = instance of vehicle v's sub-graph; cost (may be NULL): n_perm x n_graphs, graphs
+// ordered by their smallest vehicle.  The chosen instances' couplings become the controller's (what apply's fallback handling sees).
+int pdmpc_controller_explore_choose(pdmpc_controller* c, const pdmpc_vehicle_out* recs, int32_t* chosen, int32_t* n_graphs, double* cost) {
+    if (!c || !recs || c->inst.empty()) return cfail(c, PDMPC_ERR_INVALID, "no exploration batch has been built");
+    if (const int rc = choose_from_records(c, kExploreChoice, recs, (int)c->inst.size() * c->n, false)) return rc;
+    if (chosen) std::copy(c->x_chosen.begin(), c->x_chosen.end(), chosen);
+    if (n_graphs) *n_graphs = c->x_graphs;
+    if (cost) std::copy(c->x_cost.begin(), c->x_cost.end(), cost);
+    return PDMPC_OK;
+}
 
 // One explorative time step: build the batch, plan all prioritizations with ONE launch, choose per sub-graph, apply the chosen plans.
 int pdmpc_controller_explore_step(pdmpc_controller* c, int32_t n_perm) {
@@ -2422,70 +2446,21 @@ int pdmpc_controller_optimal_build(pdmpc_controller* c, int32_t max_instances) {
         // ConstantPrioritizer on the given priorities + directed_coupling_from_priorities (Prioritizer.m:64-77): keep i -> j iff
         // priority(i) <= priority(j); then assemble_step groups (cuts to max_num_CLs levels) per instance
         const int32_t* pr = c->o_prio.data() + (size_t)p * n;
-        c->directed.assign((size_t)n * n, 0);
+        c->pri.directed.assign((size_t)n * n, 0);
         for (int i = 0; i < n; ++i)
             for (int j = 0; j < n; ++j)
-                if (at(c->adjacency, n, i, j) && !(pr[j] < pr[i])) at(c->directed, n, i, j) = 1;
+                if (at(c->adjacency, n, i, j) && !(pr[j] < pr[i])) at(c->pri.directed, n, i, j) = 1;
         rc = assemble_step(c);
         if (rc) return rc;
         keep_instance(c, p);
     }
     flatten_instances(c, (int)K);
-    set_seeds(c, c->x_vehicle);
     return PDMPC_OK;
 }
 
-// compute_solution_cost / receive_solution_cost / choose_solution (:56-114): every vehicle sums the solution costs of ALL vehicles per
-// instance (its own first, then the others' messages in ascending index), rounds to 8 decimals and takes the first minimum
-namespace {
-// The optimal-priority choice as data: graph v = vehicle v, its candidates the K instances, cell (v, p) = vehicle v's slot of instance p,
-// then the other vehicles' slots of instance p in ascending vehicle index
-void optimal_describe(pdmpc_controller* c, ChoiceLists& D) {
-    const int n = c->n, K = (int)c->inst.size();
-    D.graph_of.clear();
-    D.graph_offset.resize((size_t)n + 1);
-    for (int v = 0; v <= n; ++v) D.graph_offset[(size_t)v] = v * K;
-    D.cell_offset.resize((size_t)n * K + 1);
-    for (int q = 0; q <= n * K; ++q) D.cell_offset[(size_t)q] = q * n;
-    D.cell_slot.resize((size_t)n * K * n);
-    int32_t* slot = D.cell_slot.data();
-    for (int v = 0; v < n; ++v)
-        for (int p = 0; p < K; ++p) {
-            *slot++ = c->x_slot[(size_t)p * n + v];
-            for (int j = 0; j < n; ++j)
-                if (j != v) *slot++ = c->x_slot[(size_t)p * n + j];
-        }
-    D.clear_picks();
-}
-void optimal_adopt(pdmpc_controller* c, const ChoiceLists&, const int32_t* chosen, const double* cell_cost) {
-    const int n = c->n, K = (int)c->inst.size();
-    c->x_cost.assign(cell_cost, cell_cost + (size_t)n * K);  // row v = vehicle v's sums
-    c->x_chosen.assign(chosen, chosen + n);
-    c->x_graphs = K;
-    // obj.iter = obj.iter_array_tmp{chosen_solution} (:100): every vehicle goes on with the couplings of its chosen instance
-    for (int i = 0; i < n; ++i) {
-        const pdmpc_controller::Instance& I = c->inst[(size_t)c->x_chosen[(size_t)i]];
-        for (int j = 0; j < n; ++j) {
-            at(c->directed, n, i, j) = at(I.directed, n, i, j);
-            at(c->directed_seq, n, i, j) = at(I.directed_seq, n, i, j);
-        }
-    }
-}
-const BatchChoice kOptimalChoice = {optimal_describe, optimal_adopt, true};
-int optimal_choose_on(pdmpc_controller* c, const int32_t* status, const double* final_cost) { return choose_on_host(c, kOptimalChoice, status, final_cost); }
-}  // namespace
-
 int pdmpc_controller_optimal_choose(pdmpc_controller* c, const pdmpc_vehicle_out* recs, int32_t* chosen, double* cost) {
     if (!c || !recs || c->inst.empty() || c->o_masks.size() != c->inst.size()) return cfail(c, PDMPC_ERR_INVALID, "no optimal-priority batch has been built");
-    const int N = (int)c->inst.size() * c->n;
-    std::vector<int32_t> st((size_t)N);
-    std::vector<double> fc((size_t)N);
-    for (int s = 0; s < N; ++s) {
-        st[(size_t)s] = recs[s].status;
-        fc[(size_t)s] = recs[s].path_nodes[c->Hp][4];
-    }
-    const int rc = optimal_choose_on(c, st.data(), fc.data());
-    if (rc) return rc;
+    if (const int rc = choose_from_records(c, kOptimalChoice, recs, (int)c->inst.size() * c->n, false)) return rc;
     if (chosen) std::copy(c->x_chosen.begin(), c->x_chosen.end(), chosen);
     if (cost) std::copy(c->x_cost.begin(), c->x_cost.end(), cost);
     return PDMPC_OK;
@@ -2529,22 +2504,15 @@ struct pdmpc_sweep {
     bool built = false;
     double timing[6] = {0, 0, 0, 0, 0, 0};
     PrepScratch prep;  // of the members' ONE step preparation (its prep_calls: pdmpc_sweep_last_prep_calls)
-    // the concatenated problem
-    std::vector<pdmpc_vehicle_in> in;
-    std::vector<pdmpc_polygon_set> fb;
-    std::vector<int32_t> pred_offset, pred_index, member, member_slot;
-    std::vector<uint32_t> seeds;
-    std::vector<double> weights;
+    StepProblem prob;                          // the concatenated problem, and per slot of it:
+    std::vector<int32_t> member, member_slot;  // whose it is, and which of that member's slots
     std::vector<pdmpc_vehicle_out> out;
     // the concatenated explorative batch (pdmpc_sweep_explore_*): the members' flattened batches one after the other, and their choices
     struct Batch {
         int n_perm = 0;              // of the batch that is built (0: none)
         std::vector<int32_t> first;  // [M + 1] member m's first slot of the batch
-        std::vector<pdmpc_vehicle_in> in;
-        std::vector<pdmpc_polygon_set> fb;
-        std::vector<int32_t> pred_offset, pred_index, member, instance, vehicle, level;
-        std::vector<uint32_t> seeds;
-        std::vector<double> weights;
+        StepProblem prob;
+        std::vector<int32_t> member, instance, vehicle, level;  // per slot: whose it is, and the member's own tags of it
         std::vector<ChoiceLists> lists;                           // per member, slots of its own batch
         ChoiceLists all;                                          // ... concatenated, slots of the whole batch
         std::vector<int32_t> first_graph, first_cell, chosen;     // [M + 1] each member's part of `all`; what the graphs chose
@@ -2556,32 +2524,37 @@ struct pdmpc_sweep {
 namespace {
 int N_of(const pdmpc_sweep* s) { return s->first.back(); }
 
+// A member's problem P as the slots of S from `first` on (first = 0: S starts over; whatever S held from that slot on goes): shallow
+// copies, the seeds along with them, predecessor slots shifted by `first`, and behind the last one the entry that keeps pred_index
+// from ever being an empty array
+void append_problem(StepProblem& S, const StepProblem& P, int32_t first) {
+    assert(first == 0 || first == S.n());  // members are appended in order, each at the end of what is there
+    const size_t f = (size_t)first, n = (size_t)P.n();
+    S.pred_offset.resize(f + 1, 0);
+    S.pred_index.resize((size_t)S.pred_offset[f]);
+    S.in.resize(f);
+    S.fb.resize(f);
+    S.seeds.resize(f);
+    S.in.insert(S.in.end(), P.in.begin(), P.in.end());
+    S.fb.insert(S.fb.end(), P.fb.begin(), P.fb.end());
+    S.seeds.insert(S.seeds.end(), P.seeds.begin(), P.seeds.end());
+    const int32_t e0 = S.pred_offset[f];
+    for (size_t q = 0; q < n; ++q) S.pred_offset.push_back(e0 + P.pred_offset[q + 1]);
+    for (int32_t e = 0; e < P.pred_offset[n]; ++e) S.pred_index.push_back(first + P.pred_index[(size_t)e]);
+    S.pred_index.push_back(0);
+}
+
 int sweep_build(pdmpc_sweep* s) {
     const size_t M = s->members.size();
     if (const int rc = build_members(s->h, s->members.data(), M, 0, s->prep)) return rc;
-    // the concatenated problem: shallow copies, predecessor slots shifted by the member's first slot
-    const int N = N_of(s);
-    s->in.resize((size_t)N);
-    s->fb.resize((size_t)N);
-    s->member.resize((size_t)N);
-    s->member_slot.resize((size_t)N);
-    s->seeds.resize((size_t)N);
-    s->pred_offset.assign((size_t)N + 1, 0);
-    s->pred_index.clear();
+    s->member.clear();
+    s->member_slot.clear();
     for (size_t m = 0; m < M; ++m) {
         const pdmpc_controller* c = s->members[m];
-        const int f = s->first[m];
-        for (int q = 0; q < c->n; ++q) {
-            s->in[(size_t)f + q] = c->in[(size_t)q];
-            s->fb[(size_t)f + q] = c->fb[(size_t)q];
-            s->member[(size_t)f + q] = (int32_t)m;
-            s->member_slot[(size_t)f + q] = q;
-            s->seeds[(size_t)f + q] = c->seeds[(size_t)q];
-            for (int e = c->pred_offset[(size_t)q]; e < c->pred_offset[(size_t)q + 1]; ++e) s->pred_index.push_back(f + c->pred_index[(size_t)e]);
-            s->pred_offset[(size_t)f + q + 1] = (int32_t)s->pred_index.size();
-        }
+        append_problem(s->prob, c->prob, s->first[m]);
+        s->member.insert(s->member.end(), (size_t)c->n, (int32_t)m);
+        for (int q = 0; q < c->n; ++q) s->member_slot.push_back(q);
     }
-    s->pred_index.push_back(0);
     s->built = true;
     return PDMPC_OK;
 }
@@ -2623,51 +2596,28 @@ int explore_refusal(pdmpc_sweep* s, int32_t n_perm, bool needs_handle) {
     return PDMPC_OK;
 }
 
-// every member's explorative batch, and the batches one after the other: shallow copies, predecessor slots shifted by the member's first slot
+// every member's explorative batch, and the batches one after the other
 int sweep_explore_build(pdmpc_sweep* s, int n_perm) {
     pdmpc_sweep::Batch& X = s->x;
     X.n_perm = 0;
     const size_t M = s->members.size();
     if (const int rc = build_members(s->h, s->members.data(), M, n_perm, s->prep)) return rc;
     X.first.assign(1, 0);
-    for (size_t m = 0; m < M; ++m) X.first.push_back(X.first.back() + (int32_t)s->members[m]->x_in.size());
-    const int N = X.first.back();
-    X.in.resize((size_t)N);
-    X.fb.resize((size_t)N);
-    X.member.resize((size_t)N);
-    X.instance.resize((size_t)N);
-    X.vehicle.resize((size_t)N);
-    X.level.resize((size_t)N);
-    X.seeds.resize((size_t)N);
-    X.pred_offset.assign((size_t)N + 1, 0);
-    X.pred_index.clear();
+    X.member.clear();
+    X.instance.clear();
+    X.vehicle.clear();
+    X.level.clear();
     for (size_t m = 0; m < M; ++m) {
         const pdmpc_controller* c = s->members[m];
-        const int f = X.first[m];
-        for (int q = 0; q < X.first[m + 1] - f; ++q) {
-            X.in[(size_t)f + q] = c->x_in[(size_t)q];
-            X.fb[(size_t)f + q] = c->x_fb[(size_t)q];
-            X.member[(size_t)f + q] = (int32_t)m;
-            X.instance[(size_t)f + q] = c->x_instance[(size_t)q];
-            X.vehicle[(size_t)f + q] = c->x_vehicle[(size_t)q];
-            X.level[(size_t)f + q] = c->x_level[(size_t)q];
-            X.seeds[(size_t)f + q] = c->seeds[(size_t)q];
-            for (int e = c->x_pred_offset[(size_t)q]; e < c->x_pred_offset[(size_t)q + 1]; ++e) X.pred_index.push_back(f + c->x_pred_index[(size_t)e]);
-            X.pred_offset[(size_t)f + q + 1] = (int32_t)X.pred_index.size();
-        }
+        append_problem(X.prob, c->x_prob, X.first[m]);
+        X.first.push_back(X.prob.n());
+        X.member.insert(X.member.end(), (size_t)c->x_prob.n(), (int32_t)m);
+        X.instance.insert(X.instance.end(), c->x_instance.begin(), c->x_instance.end());
+        X.vehicle.insert(X.vehicle.end(), c->x_vehicle.begin(), c->x_vehicle.end());
+        X.level.insert(X.level.end(), c->x_level.begin(), c->x_level.end());
     }
-    X.pred_index.push_back(0);
     X.n_perm = n_perm;
     return PDMPC_OK;
-}
-
-// the chosen plans (or, follow-own, the plans of its own prioritization) become the member's records; then its apply
-int apply_chosen(pdmpc_controller* c) {
-    if (c->follow_own) {  // (the couplings of instance 0 again: what apply's fallback handling sees)
-        c->directed = c->inst[0].directed;
-        c->directed_seq = c->inst[0].directed_seq;
-    }
-    return pdmpc_controller_apply(c, c->out.data());
 }
 
 // the records of the whole batch: every member chooses on the host and applies its chosen plans
@@ -2676,13 +2626,9 @@ int sweep_explore_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records) {
     for (size_t m = 0; m < s->members.size(); ++m) {
         pdmpc_controller* c = s->members[m];
         c->x_out.assign(records + X.first[m], records + X.first[m + 1]);
-        if (const int rc = pdmpc_controller_explore_choose(c, c->x_out.data(), nullptr, nullptr, nullptr)) return rc;
-        c->out.resize((size_t)c->n);
-        for (int q = 0; q < c->n; ++q) {
-            const int v = c->order[(size_t)q];
-            c->out[(size_t)q] = c->x_out[(size_t)c->x_slot[(size_t)(c->follow_own ? 0 : c->x_chosen[(size_t)v]) * c->n + v]];
-        }
-        if (const int rc = apply_chosen(c)) return rc;
+        if (const int rc = choose_from_records(c, kExploreChoice, c->x_out.data(), X.first[m + 1] - X.first[m], c->follow_own)) return rc;
+        gather_kept_records(c, c->follow_own);
+        if (const int rc = pdmpc_controller_apply(c, c->out.data())) return rc;
     }
     return PDMPC_OK;
 }
@@ -2765,11 +2711,7 @@ int pdmpc_sweep_build(pdmpc_sweep* s) {
 int pdmpc_sweep_problem(pdmpc_sweep* s, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index,
                         const pdmpc_polygon_set** fallback, const int32_t** member, const int32_t** member_slot) {
     if (!s || !s->built) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_problem before pdmpc_sweep_build");
-    if (n_slots) *n_slots = N_of(s);
-    if (in) *in = s->in.data();
-    if (pred_offset) *pred_offset = s->pred_offset.data();
-    if (pred_index) *pred_index = s->pred_index.data();
-    if (fallback) *fallback = s->fb.data();
+    expose(s->prob, n_slots, in, pred_offset, pred_index, fallback);
     if (member) *member = s->member.data();
     if (member_slot) *member_slot = s->member_slot.data();
     return PDMPC_OK;
@@ -2790,15 +2732,13 @@ int pdmpc_sweep_step(pdmpc_sweep* s) {
     if (rc) return sweep_guard(s, rc);
     s->timing[0] = ms_since(t);
     s->timing[4] = 0;
-    const int N = N_of(s);
-    s->out.resize((size_t)N);
+    s->out.resize((size_t)N_of(s));
     // (the work of the last step as pdmpc_controller_step hands it over; a member's first step: 1 for each of its slots)
     auto pops_of = [&](int q) {
         const pdmpc_controller* c = s->members[(size_t)s->member[(size_t)q]];
-        return c->last_pops.size() == (size_t)c->n ? c->last_pops[(size_t)c->order[(size_t)s->member_slot[(size_t)q]]] : 0.0;
+        return c->last_pops.size() == (size_t)c->n ? c->last_pops[(size_t)c->pri.order[(size_t)s->member_slot[(size_t)q]]] : 0.0;
     };
-    rc = plan_built(s->h, N, true, s->weights, pops_of, s->members[0]->optimizer, s->seeds, s->timing,
-                    [&] { return pdmpc_plan_step(s->h, N, s->in.data(), s->pred_offset.data(), s->pred_index.data(), s->fb.data(), s->out.data()); });
+    rc = plan_built(s->h, s->prob, true, pops_of, s->members[0]->optimizer, s->timing, pdmpc_plan_step, s->out.data());
     if (rc) return sweep_guard(s, rc);
     t = std::chrono::steady_clock::now();
     rc = sweep_apply(s, s->out.data(), true);
@@ -2831,11 +2771,7 @@ int pdmpc_sweep_explore_problem(pdmpc_sweep* s, int32_t* n_slots, const pdmpc_ve
                                 const pdmpc_polygon_set** fallback, const int32_t** member, const int32_t** instance, const int32_t** vehicle, const int32_t** level) {
     if (!s || s->x.n_perm < 1) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_explore_problem before pdmpc_sweep_explore_build");
     const pdmpc_sweep::Batch& X = s->x;
-    if (n_slots) *n_slots = X.first.back();
-    if (in) *in = X.in.data();
-    if (pred_offset) *pred_offset = X.pred_offset.data();
-    if (pred_index) *pred_index = X.pred_index.data();
-    if (fallback) *fallback = X.fb.data();
+    expose(X.prob, n_slots, in, pred_offset, pred_index, fallback);
     if (member) *member = X.member.data();
     if (instance) *instance = X.instance.data();
     if (vehicle) *vehicle = X.vehicle.data();
@@ -2857,7 +2793,6 @@ int pdmpc_sweep_explore_step(pdmpc_sweep* s, int32_t n_perm) {
     if (rc) return sweep_guard(s, rc);
     pdmpc_sweep::Batch& X = s->x;
     s->timing[0] = ms_since(t);
-    const int N = X.first.back();
     const size_t M = s->members.size();
     // (the work of the last step as the members' own explorative steps hand it over)
     auto pops_of = [&](int q) {
@@ -2866,20 +2801,18 @@ int pdmpc_sweep_explore_step(pdmpc_sweep* s, int32_t n_perm) {
     };
     concatenate_choices(s);
     const pdmpc_choice ch = X.all.view();
-    rc = plan_built(s->h, N, true, X.weights, pops_of, s->members[0]->optimizer, X.seeds, s->timing, [&] {
-        return pdmpc_plan_step_chosen(s->h, N, X.in.data(), X.pred_offset.data(), X.pred_index.data(), X.fb.data(), &ch, X.chosen.data(), X.cell_cost.data(), X.picks.data());
-    });
+    rc = plan_built(s->h, X.prob, true, pops_of, s->members[0]->optimizer, s->timing, pdmpc_plan_step_chosen, &ch, X.chosen.data(), X.cell_cost.data(), X.picks.data());
     if (rc) return sweep_guard(s, rc);
     t = std::chrono::steady_clock::now();
     for (size_t m = 0; m < M; ++m) {  // every member adopts its part: as its own step that keeps the chosen plans only leaves it
         pdmpc_controller* c = s->members[m];
-        explore_adopt(c, X.lists[m], X.chosen.data() + X.first_graph[m], X.cell_cost.data() + X.first_cell[m]);
+        explore_adopt(c, X.lists[m], X.chosen.data() + X.first_graph[m], X.cell_cost.data() + X.first_cell[m], c->follow_own);
         c->x_out.clear();
         c->out.assign(X.picks.begin() + s->first[m], X.picks.begin() + s->first[m + 1]);
     }
     s->timing[4] = ms_since(t);
     t = std::chrono::steady_clock::now();
-    for (size_t m = 0; m < M && !rc; ++m) rc = apply_chosen(s->members[m]);
+    for (size_t m = 0; m < M && !rc; ++m) rc = pdmpc_controller_apply(s->members[m], s->members[m]->out.data());
     s->timing[5] = ms_since(t);
     return sweep_guard(s, rc);
 }

@@ -358,6 +358,35 @@ def test_a_sweep_alternates_plain_and_explorative_steps():
             c.close()
 
 
+def test_seeds_are_those_of_whichever_was_built_last_the_step_or_the_batch():
+    """The step and the batch of prioritizations each carry their own seeds; seeds() hands out those of the problem built last: one entry
+    per slot of that problem, time_step + vehicle + 1 (1-based vehicle index), whether a step follows a batch or a batch a step."""
+    from pdmpc.native_controller import NativeController
+    from pdmpc.scenario import circle_scenario
+
+    options = Config(scenario_type=ScenarioType.circle, amount=3, Hp=HP, max_nodes=1 << 30)
+    nat = NativeController(options, circle_scenario(options), get_mpa(options), None, coupling="full", optimizer="sampled")
+    try:
+        def assert_seeds(vehicle_of_slot, n_slots, what):
+            k = nat.state()["k"]
+            assert len(vehicle_of_slot) == n_slots, what
+            assert nat.seeds() == [k + v + 1 for v in vehicle_of_slot], what
+
+        nat.build_step()
+        assert_seeds(nat.problem()["order"], 3, "first step")
+        nat.explore_build(2, 7)
+        batch = nat.explore_problem()
+        assert max(batch["levels"]) > 1
+        assert_seeds(batch["vehicle"], 2 * 3, "explorative batch")
+        nat.build_step()
+        assert_seeds(nat.problem()["order"], 3, "step behind a batch")
+        K = nat.optimal_build(100)
+        assert K > 1
+        assert_seeds(nat.optimal_problem()["vehicle"], K * 3, "optimal-priority batch")
+    finally:
+        nat.close()
+
+
 def test_every_refusal_of_the_explorative_sweep_leaves_the_members_untouched():
     from oracle import oracle
 
