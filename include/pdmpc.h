@@ -167,8 +167,10 @@ typedef struct {
  * measured defaults; ONE environment variable, read once in pdmpc_create, overrides them for benchmarking and tests:
  *     PDMPC_TUNING="key=value,key=value,..."
  * keys: round0 round ramp ready share_min tile mid_min mid_fill (rounds and lists), tentative fast_arrival speculate helpers
- * helpers_oversub helpers_first seat_nodes waves compact (A/B switches; compact takes -1, 0 or 1), force_tie reverse_dispatch
+ * helpers_oversub helpers_first seat_nodes waves compact generic (A/B switches; compact takes -1, 0 or 1), force_tie reverse_dispatch
  * spin_limit (testing), debug_tail debug_lds debug_host debug_progress (diagnostics); csrc/handle.hpp: struct Tuning documents each.
+ * The search kernels have the defaults of tentative fast_arrival speculate force_tie reverse_dispatch debug_tail compiled
+ * in; any other value of one of them, or generic=1, runs the kernels' generic twins, which read them at run time.
  * No setting changes a result; an unknown key fails pdmpc_create. */
 
 /* ---- life cycle (replaces GraphSearch() construction in OptimizerInterface.get_optimizer, :26-27,

@@ -39,7 +39,7 @@ bool parse_tuning(const char* text, Tuning& T, std::string& err) {
                         {"tile", &T.tile}, {"mid_min", &T.mid_min}, {"mid_fill", &T.mid_fill}, {"tentative", &T.tentative}, {"fast_arrival", &T.fast_arrival}, {"helpers_first", &T.helpers_first}, {"seat_nodes", &T.seat_nodes},
                         {"helpers", &T.helpers}, {"helpers_oversub", &T.helpers_oversub}, {"speculate", &T.speculate}, {"waves", &T.waves}, {"compact", &T.compact}, {"spin_limit", &spin},
                         {"force_tie", &T.force_tie}, {"reverse_dispatch", &T.reverse_dispatch}, {"debug_tail", &T.debug_tail}, {"debug_lds", &T.debug_lds},
-                        {"debug_host", &T.debug_host}, {"debug_progress", &T.debug_progress}};
+                        {"debug_host", &T.debug_host}, {"debug_progress", &T.debug_progress}, {"generic", &T.generic}};
     std::string str(text ? text : "");
     size_t pos = 0;
     while (pos < str.size()) {
@@ -92,9 +92,14 @@ bool parse_tuning(const char* text, Tuning& T, std::string& err) {
 namespace {
 
 // The dynamic LDS size of a kernel is an attribute of the function ON THE DEVICE, not of a handle (hipFuncSetAttribute sets a
-// maximum): the largest size set so far is kept per device and kernel (0 bulk, 1 bulk wide, 2 bulk SAT, 3 bulk compact), shared by every handle.
+// maximum): the largest size set so far is kept per device, kernel (0 bulk, 1 bulk wide, 2 bulk SAT, 3 bulk compact) and instantiation
+// (0 product, 1 generic: two functions on the device; kernels in the order of PDMPC_BULK ...), shared by every handle.
 std::mutex g_lds_mutex;
-uint32_t g_lds_high_water[64][4];
+uint32_t g_lds_high_water[64][4][2];
+const char* const kBulkKernelNames[4][2] = {{"pdmpc_bulk_kernel", "pdmpc_bulk_kernel_any"},
+                                            {"pdmpc_bulk_kernel_wide", "pdmpc_bulk_kernel_wide_any"},
+                                            {"pdmpc_bulk_kernel_sat", "pdmpc_bulk_kernel_sat_any"},
+                                            {"pdmpc_bulk_kernel_compact", "pdmpc_bulk_kernel_compact_any"}};
 // The automaton's tables, the front of every LDS layout from `off` on: successor masks, maneuver index, poses, then the maneuver
 // areas (only with `areas`: else they are read from L2).  Returns the first free byte.
 template <class Layout>
@@ -163,8 +168,6 @@ int compute_lds_bulk(const pdmpc_handle* h, int n_launch, int soup_cap, LaunchLa
         const int waves = T.waves >= 0 ? std::min(T.waves, PDMPC_LK_COMPACT_WAVES) : PDMPC_LK_COMPACT_WAVES;
         const int ready = std::min(std::min(ready_want, 3 * PDMPC_WAVE * waves), (int)PDMPC_LK_COMPACT_READY_CAP);
         if (layout_bulk(h, kLdsMax / 2, waves, 0, soup_cap, L, nv, nl, (uint32_t)ready, true)) {
-            if (T.debug_lds)
-                fprintf(stderr, "pdmpc LDS layout (compact): launch %d waves %d near %u ready %d nv %u nl %u total %u\n", n_launch, waves, PDMPC_LK_COMPACT_BK_PER * (uint32_t)waves * PDMPC_WAVE, ready, nv, nl, L.total);
             out = {L, waves, (int)nl, (int)nv, 0, ready, true};
             return PDMPC_OK;
         }
@@ -174,9 +177,6 @@ int compute_lds_bulk(const pdmpc_handle* h, int n_launch, int soup_cap, LaunchLa
         LdsLayout L{};
         const int ready = std::min(ready_want, 3 * PDMPC_WAVE * waves);
         if (!layout_bulk(h, kLdsMax, waves, areas, soup_cap, L, nv, nl, (uint32_t)ready, false)) continue;
-        if (T.debug_lds)
-            fprintf(stderr, "pdmpc LDS layout: launch %d waves %d areas %d near %u ready %d nv %u nl %u total %u\n", n_launch, waves, areas, PDMPC_BK_PER * (uint32_t)waves * PDMPC_WAVE, ready,
-                    nv, nl, L.total);
         out = {L, waves, (int)nl, (int)nv, areas, ready, false};
         return PDMPC_OK;
     }
@@ -400,6 +400,25 @@ int prepare_boards(pdmpc_handle* h, int count, uint32_t& fin_base) {
     return PDMPC_OK;
 }
 
+// Which of the four search kernels a layout runs (g_lds_high_water), and which of its two instantiations: the product one exactly
+// when the launch's switches are the ones it has compiled in (pdmpc_device.h: ProductSwitches) -- not with a debug or test switch of
+// PDMPC_TUNING set, or maneuver areas that are not where that kernel expects them (a small soup grown until they move to L2) --, and never with generic=1.
+int bulk_variant(const pdmpc_handle* h, const LaunchLayout& lay) {
+    return lay.compact ? PDMPC_BULK_COMPACT : (h->cfg.checker == PDMPC_CHECK_SAT ? PDMPC_BULK_SAT : (h->n_words != 1 ? PDMPC_BULK_WIDE : PDMPC_BULK));
+}
+bool bulk_generic(const pdmpc_handle* h, const KernelArgs& a, const LaunchLayout& lay) { return h->tune.generic != 0 || !ProductSwitches::matches(a, bulk_variant(h, lay)); }
+
+// PDMPC_TUNING=debug_lds=1: the layout of a search launch and the kernel instantiation that runs it, one line on stderr
+void print_bulk_layout(const pdmpc_handle* h, const KernelArgs& a, const LaunchLayout& lay) {
+    const uint32_t near = (lay.compact ? PDMPC_LK_COMPACT_BK_PER : PDMPC_BK_PER) * (uint32_t)lay.n_waves * PDMPC_WAVE;
+    const char* kernel = kBulkKernelNames[bulk_variant(h, lay)][bulk_generic(h, a, lay) ? 1 : 0];
+    if (lay.compact)
+        fprintf(stderr, "pdmpc LDS layout (compact): launch %d waves %d near %u ready %d nv %d nl %d total %u kernel %s\n", a.n_searches, lay.n_waves, near, lay.ready, lay.NV, lay.NL, lay.lds.total, kernel);
+    else
+        fprintf(stderr, "pdmpc LDS layout: launch %d waves %d areas %d near %u ready %d nv %d nl %d total %u kernel %s\n", a.n_searches, lay.n_waves, lay.areas_in_lds, near, lay.ready, lay.NV, lay.NL,
+                lay.lds.total, kernel);
+}
+
 // The kernel launches of one launch_range; returns the hipError_t of the first that failed.
 // Oversubscribed launches (more searches than CUs).  A resident search spins for predecessors of the same launch; slots are in
 // level order (the packer sees to it: coupling_order.hpp), so as long as the hardware hands out workgroups in index order every
@@ -409,14 +428,15 @@ int prepare_boards(pdmpc_handle* h, int count, uint32_t& fin_base) {
 // progress then needs no assumption at all.
 int dispatch(const pdmpc_handle* h, const KernelArgs& a, const LaunchLayout& lay, bool search, bool safe) {
     const int first = a.first, count = a.n_searches;
-    const int variant = lay.compact ? 3 : (h->cfg.checker == PDMPC_CHECK_SAT ? 2 : (h->n_words != 1 ? 1 : 0));
+    const int variant = bulk_variant(h, lay), generic = bulk_generic(h, a, lay) ? 1 : 0;
     auto launch_search = [&](const KernelArgs* ka, int cnt) -> int {
+        typedef int (*launcher_t)(const KernelArgs*, int, void*, uint32_t*);
+        static const launcher_t launchers[4][2] = {{pdmpc_launch_bulk, pdmpc_launch_bulk_any},
+                                                   {pdmpc_launch_bulk_wide, pdmpc_launch_bulk_wide_any},
+                                                   {pdmpc_launch_bulk_sat, pdmpc_launch_bulk_sat_any},
+                                                   {pdmpc_launch_bulk_compact, pdmpc_launch_bulk_compact_any}};
         std::lock_guard<std::mutex> lock(g_lds_mutex);
-        uint32_t* hw = &g_lds_high_water[h->cfg.device & 63][variant];
-        if (variant == 3) return pdmpc_launch_bulk_compact(ka, cnt, (void*)h->stream, hw);
-        if (variant == 2) return pdmpc_launch_bulk_sat(ka, cnt, (void*)h->stream, hw);
-        if (variant == 1) return pdmpc_launch_bulk_wide(ka, cnt, (void*)h->stream, hw);
-        return pdmpc_launch_bulk(ka, cnt, (void*)h->stream, hw);
+        return launchers[variant][generic](ka, cnt, (void*)h->stream, &g_lds_high_water[h->cfg.device & 63][variant][generic]);
     };
     // a safe launch goes out in slices of `resident` searches, any other as a whole
     auto in_slices = [&](int resident, auto&& launch) -> int {
@@ -456,6 +476,7 @@ int launch_range(pdmpc_handle* h, int first, int count, bool safe) {
     set_launch_args(h, B, lay, first, count, safe, a);
     launch_policy(h->tune, count, h->n_cu, h->device_share, safe, search, lay, B.host.veh + first, a);
     if (a.n_helpers > 0 && (rc = prepare_boards(h, count, a.help_fin_base))) return rc;
+    if (search && h->tune.debug_lds) print_bulk_layout(h, a, lay);
     if ((rc = h->timer.begin(h->stream, search ? kLaunchSearch : kLaunchSampled))) return rc;
     const int lrc = dispatch(h, a, lay, search, safe);
     if (lrc != 0) {

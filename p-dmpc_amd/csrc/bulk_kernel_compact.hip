@@ -11,4 +11,4 @@
 #include <hip/hip_runtime.h>
 #include "bulk_search.hpp"
 
-PDMPC_BULK_KERNEL(pdmpc_bulk_kernel_compact, pdmpc_launch_bulk_compact, 1, PDMPC_CHECK_INTERX, PDMPC_LK_COMPACT_WAVES)
+PDMPC_BULK_KERNEL(pdmpc_bulk_kernel_compact, pdmpc_launch_bulk_compact, 1, PDMPC_CHECK_INTERX, PDMPC_LK_COMPACT_WAVES, PDMPC_BULK_COMPACT)

@@ -870,7 +870,7 @@ __device__ __forceinline__ void bk_replay(const KernelArgs& A, Ctx& X, const Fro
 }
 
 // The search (results in X).  The return value is unused (always false: equal keys are resolved inside the search, bk_replay).
-template <int NW, int CHECKER>
+template <int NW, int CHECKER, class SW>
 __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32* ref_ids) {
     const int tid = X.tid, lane = X.lane, wave = X.wave, slot = X.slot, Hp = X.Hp;
     volatile lds_u32* sh = X.l_shared;
@@ -934,7 +934,7 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
     CK.l_soff = X.C.l_soff;
     CK.l_hoff = X.C.l_hoff;
     CK.l_lit = P.l_lit;
-    CK.areas_in_lds = X.C.areas_in_lds;
+    CK.areas_in_lds = SW::areas_in_lds(A);
     CK.ll_base = X.C.ll_base;
     CK.ll_len = X.C.ll_len;
     CK.Hp = Hp;
@@ -968,7 +968,7 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
         sh_st_d(sh, BK_MID_MIN, inf);
         sh_st_d(sh, BK_L_MID, -1.0);
         sh[SH_NNODES] = 1;
-        sh[BK_TIEMODE] = A.bk_force_tie ? 1u : 0u;
+        sh[BK_TIEMODE] = SW::force_tie(A) ? 1u : 0u;
         ready[0] = 1u;
         r_flag[0] = 0u;
     }
@@ -984,7 +984,7 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    if (A.bk_tentative) bk_tentative_areas(A, P, sh_load64(sh, SH_PEND_LO), tid, (int)blockDim.x);  // (the pending set was fixed by the prologue)
+    if (SW::tentative(A)) bk_tentative_areas(A, P, sh_load64(sh, SH_PEND_LO), tid, (int)blockDim.x);  // (the pending set was fixed by the prologue)
     if (tid >= 64 && tid < 72) {
         const int ls = tid - 64;
         uint32_t mx = 0;
@@ -1011,7 +1011,7 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
     // the round loop no registers
     lds_vu64* tk = (lds_vu64*)(gp_path + 200);  // [12]: mark, start, work, arrival, select (without the refills), wait, p1, p2, p3, phase B, refill, time of the early publication
     enum { TK_MARK, TK_START, tk_work, tk_arrival, tk_select, tk_wait, tk_p1, tk_p2, tk_p3, tk_pb, tk_refill, tk_pub };
-    const bool ticking = A.debug_tail != 0 && tid == 0;
+    const bool ticking = SW::debug_tail(A) != 0 && tid == 0;
     if (ticking) {
         for (int i = 2; i < 12; ++i) tk[i] = 0ull;
         tk[TK_MARK] = tk[TK_START] = __builtin_amdgcn_s_memrealtime();
@@ -1031,16 +1031,16 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
     if (ticking)
         for (int i = 0; i < 7; ++i) tk2[i] = 0ull;
 #define BK_TICK2(i)                                                        \
-    if (ticking && A.debug_tail != 3) {                                                         \
+    if (ticking && SW::debug_tail(A) != 3) {                                                         \
         const unsigned long long now__ = __builtin_amdgcn_s_memrealtime(); \
         tk2[i] += now__ - tk2[6];                                          \
         tk2[6] = now__;                                                    \
     }
 #define BK_MARK2 \
-    if (ticking && A.debug_tail != 3) tk2[6] = __builtin_amdgcn_s_memrealtime();
+    if (ticking && SW::debug_tail(A) != 3) tk2[6] = __builtin_amdgcn_s_memrealtime();
     // (debug_tail=3: the same six counters take a round's passes apart instead: the share decision, the check items, the sincos items, P1's
     // last barrier, the boundary up to the selection, the selection)
-    const bool ticking3 = ticking && A.debug_tail == 3;
+    const bool ticking3 = ticking && SW::debug_tail(A) == 3;
 #define BK_TICK3(i)                                                        \
     if (ticking3) {                                                        \
         const unsigned long long now__ = __builtin_amdgcn_s_memrealtime(); \
@@ -1182,7 +1182,7 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
             // the checks were 5, and more helpers made every search of the launch slower, profiles/r05_helper_sweep.txt).
             BK_MARK3
             const BkTreeSrc tsrc{&S, ready};
-            const unsigned long long pend_now = A.bk_tentative ? sh_load64(sh, SH_PEND_LO) : 0ull;  // (their slots hold expected areas)
+            const unsigned long long pend_now = SW::tentative(A) ? sh_load64(sh, SH_PEND_LO) : 0ull;  // (their slots hold expected areas)
             bool share = A.n_helpers > 0 && Rn >= (uint32_t)A.bk_share_min && P.n_pred <= 64;
             uint32_t own_n = Rn, seats = 0, per_h = 0;
             if (share) {  // (uniform)
@@ -1285,7 +1285,7 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
-            if (ticking && A.debug_tail == 2) {  // (diagnostics: rounds, P1 time, entries and the owner's part by the seats the round had: none, 1-7, 8-31, 32-64)
+            if (ticking && SW::debug_tail(A) == 2) {  // (diagnostics: rounds, P1 time, entries and the owner's part by the seats the round had: none, 1-7, 8-31, 32-64)
                 const int bkt = !share ? 0 : (seats < 8u ? 1 : (seats < 32u ? 2 : 3));
                 double* r0 = X.O->path_nodes[PDMPC_HP_MAX - 5];
                 double* r1 = X.O->path_nodes[PDMPC_HP_MAX - 4];
@@ -1463,7 +1463,7 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
             if (tid == 0) {  // (nobody reads these words before the barrier that ends the round)
                 sh[FR_NNODES] = nn_base + (overflow ? 0u : NC);
                 sh[FR_PROCESSED] = sh[FR_PROCESSED] + Rn;
-                if (A.debug_tail == 1 && sh[FR_ROUNDS] < 32u) X.O->path_nodes[PDMPC_HP_MAX - 7 + (int)(sh[FR_ROUNDS] >> 3)][sh[FR_ROUNDS] & 7u] = (double)Rn;  // (diagnostics: the sizes of the first thirty-two rounds in rows HP_MAX - 7 .. HP_MAX - 4)
+                if (SW::debug_tail(A) == 1 && sh[FR_ROUNDS] < 32u) X.O->path_nodes[PDMPC_HP_MAX - 7 + (int)(sh[FR_ROUNDS] >> 3)][sh[FR_ROUNDS] & 7u] = (double)Rn;  // (diagnostics: the sizes of the first thirty-two rounds in rows HP_MAX - 7 .. HP_MAX - 4)
                 sh[FR_ROUNDS] = sh[FR_ROUNDS] + 1u;
                 if (overflow) sh[FR_FLAGS] = sh[FR_FLAGS] | FRF_OVERFLOW;
             }
@@ -1864,7 +1864,7 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
                 for (uint32_t i = (uint32_t)tid; i < nv; i += (uint32_t)bd) VS.g[i] = VS.l[i];
                 vs_copied = true;
             }
-            if (A.bk_fast_arrival && !dep_timeout) {
+            if (SW::fast_arrival(A) && !dep_timeout) {
                 __syncthreads();  // (as above: everybody has read the pending set this wait is about to rewrite)
                 if (wave == 0)
                     bk_wait_done(A.done_flag, P.pred, P.out, A.epoch, (uint32_t)slot, P.l_soup, P.l_soff, P.l_lit, (lds_d2*)(X.lsm + PDMPC_LK_PSHAPE), sh, Hp, P.n_pred, best != 0u,
@@ -2271,7 +2271,7 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
         atomicAdd(A.work_count + 3, (unsigned long long)sh[FR_ROUNDS]);
         A.tree_size[slot] = (int32_t)(nnodes_raw | 0x40000000u | (tie_replayed ? 0x20000000u : 0u));  // marks the arena as a raw tree (api.cpp reconstructs the reference's; replayed: the pop sequence is there too)
     }
-    if (tid_r == 0 && A.debug_tail) {  // diagnostics in the unused tail of the record (rows HP_MAX - 2 .. HP_MAX of path_nodes); PDMPC_DEBUG_TAIL=1
+    if (tid_r == 0 && SW::debug_tail(A)) {  // diagnostics in the unused tail of the record (rows HP_MAX - 2 .. HP_MAX of path_nodes); PDMPC_DEBUG_TAIL=1
         double* dbg = X.O->path_nodes[PDMPC_HP_MAX];
         dbg[0] = (double)sh[FR_ROUNDS];
         dbg[1] = (double)sh[FR_PROCESSED];
@@ -2322,7 +2322,7 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
 // round's posted records; the helper runs the owner's own check items on it, leaves one verdict word per entry and the round's number
 // in its seat's done word.  It keeps the seat until the search ends, then looks for another search.  A helper never waits for
 // anything but memory, so an owner that waits for its seats always gets them; helpers leave when every search of the launch has ended.
-template <int CHECKER>
+template <int CHECKER, class SW>
 __device__ __forceinline__ void bulk_helper_body(const KernelArgs& A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     LDS_AS unsigned char* lsm = (LDS_AS unsigned char*)smem;
@@ -2346,11 +2346,11 @@ __device__ __forceinline__ void bulk_helper_body(const KernelArgs& A) {
     CK.l_soff = l_soff;
     CK.l_hoff = l_hoff;
     CK.l_lit = l_lit;
-    CK.areas_in_lds = A.areas_in_lds;
+    CK.areas_in_lds = SW::areas_in_lds(A);
     CK.ll_base = 0;
     CK.ll_len = 0;
     CK.Hp = Hp;
-    if (A.areas_in_lds) stage16(lsm + A.lds.area, A.man_area, A.n_man * 3 * PDMPC_VMAX, tid);
+    if (SW::areas_in_lds(A)) stage16(lsm + A.lds.area, A.man_area, A.n_man * 3 * PDMPC_VMAX, tid);
     if (tid < SH_WORDS) hs[tid] = 0;
     __syncthreads();
     int my_slot = -1, my_seat = -1;  // (uniform)
@@ -2370,7 +2370,7 @@ __device__ __forceinline__ void bulk_helper_body(const KernelArgs& A) {
     uint32_t idle = 0;
     // (PDMPC_TUNING=debug_tail=1: where a helper's time goes, 100 MHz ticks summed over its ranges: idle, from the assignment to the
     // soup in place, the range's records, its check items, verdicts + report; work_count[8..12], [13] = ranges)
-    const bool hticking = A.debug_tail != 0 && tid == 0;
+    const bool hticking = SW::debug_tail(A) != 0 && tid == 0;
     unsigned long long hk_mark = hticking ? __builtin_amdgcn_s_memrealtime() : 0ull, hk[5] = {0, 0, 0, 0, 0}, hk_tiles = 0;
     const unsigned long long hk_start = hk_mark;
 #define HK_TICK(i)                                                        \
@@ -2483,7 +2483,7 @@ __device__ __forceinline__ void bulk_helper_body(const KernelArgs& A) {
             __syncthreads();
             P.pred = A.pred + V->pred_off;
             P.n_pred = V->n_pred;
-            if (A.bk_tentative) bk_tentative_areas(A, P, V->n_pred >= 64 ? ~0ull : ((1ull << V->n_pred) - 1ull), tid, bd);  // (as the owner: expected areas until the real ones are in)
+            if (SW::tentative(A)) bk_tentative_areas(A, P, V->n_pred >= 64 ? ~0ull : ((1ull << V->n_pred) - 1ull), tid, bd);  // (as the owner: expected areas until the real ones are in)
             cur_mask = 0;
             __syncthreads();
             if (tid < 8) {  // the chunk table of this soup (bulk_search)
@@ -2564,7 +2564,7 @@ __device__ __forceinline__ void bulk_helper_body(const KernelArgs& A) {
         if (Rt) {
             const BkPostSrc psrc{t_rec};
             const int ls = bk_chunk_shift(chm, Rt, (uint32_t)bd);
-            const unsigned long long pend = A.bk_tentative ? (P.n_pred >= 64 ? ~0ull : ((1ull << P.n_pred) - 1ull)) & ~mask : 0ull;
+            const unsigned long long pend = SW::tentative(A) ? (P.n_pred >= 64 ? ~0ull : ((1ull << P.n_pred) - 1ull)) & ~mask : 0ull;
             bk_check_items<CHECKER>(CK, psrc, t_flag, 0u, Rt, ls, chm[ls], pend, tid, bd);
         }
         __syncthreads();
@@ -2594,7 +2594,7 @@ __device__ __forceinline__ void bulk_helper_body(const KernelArgs& A) {
 #undef HK_TICK
 }
 
-template <int NW, int CHECKER>
+template <int NW, int CHECKER, class SW>
 __device__ __forceinline__ void bulk_body(const KernelArgs& A) {
     // The workgroups behind the searches are their helpers: one launch, so the helpers are dispatched with (for launches with more
     // searches than CUs: right behind) the searches they serve — a helper kernel of its own on a second stream now and then shared a
@@ -2602,17 +2602,17 @@ __device__ __forceinline__ void bulk_body(const KernelArgs& A) {
     // (bk_helpers_first of the helpers come in front of the searches: a launch of more searches than CUs, whose finished searches hold
     // their CUs while they wait for predecessors, leaves the helpers behind the searches no CU until the step is nearly over)
     if ((int)blockIdx.x < A.bk_helpers_first || (int)blockIdx.x >= A.bk_helpers_first + A.n_searches) {  // (uniform over the workgroup)
-        bulk_helper_body<CHECKER>(A);
+        bulk_helper_body<CHECKER, SW>(A);
         return;
     }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     Ctx X;
     const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
-    search_prologue(A, X, (LDS_AS unsigned char*)smem);
+    search_prologue<SW>(A, X, (LDS_AS unsigned char*)smem);
     X.rt_kernel_start = rt0;
     const int wave = X.wave;
     lds_u32* ref_ids = (lds_u32*)(X.lsm + PDMPC_LK_MISC) + 224;  // behind the chunk table (nothing else uses those words)
-    const bool tie = bulk_search<NW, CHECKER>(A, X, ref_ids);
+    const bool tie = bulk_search<NW, CHECKER, SW>(A, X, ref_ids);
     (void)tie;  // (equal keys are resolved inside the search: bk_replay)
     __syncthreads();
     if (wave != 0) return;
@@ -2634,11 +2634,13 @@ __device__ __forceinline__ void bulk_body(const KernelArgs& A) {
 // One kernel per (checker, successor-mask words) in a translation unit of its own (bulk_kernel.hip: InterX, one mask word — every
 // BASELINE road-network configuration; bulk_kernel_wide.hip: InterX, automata of more than 64 trims; bulk_kernel_sat.hip: the
 // separating-axis checker, any automaton), so that they compile side by side and each gets its own register allocation.
+// Each is instantiated twice (pdmpc_device.h: ProductSwitches): NAME with the product's switches compiled in (KERNEL: which of the
+// four it is, PDMPC_BULK ...), NAME_any reading them from KernelArgs; LAUNCHER and LAUNCHER_any launch them.
 #ifndef PDMPC_BULK_KERNEL_ATTR
 #define PDMPC_BULK_KERNEL_ATTR
 #endif
-#define PDMPC_BULK_KERNEL(NAME, LAUNCHER, NW, CHECKER, MAXWAVES)                                                                                   \
-    extern "C" __global__ __launch_bounds__(PDMPC_WAVE * (MAXWAVES)) PDMPC_BULK_KERNEL_ATTR void NAME(const KernelArgs A) { bulk_body<NW, CHECKER>(A); } \
+#define PDMPC_BULK_INSTANCE(NAME, LAUNCHER, NW, CHECKER, MAXWAVES, SW)                                                                   \
+    extern "C" __global__ __launch_bounds__(PDMPC_WAVE * (MAXWAVES)) PDMPC_BULK_KERNEL_ATTR void NAME(const KernelArgs A) { bulk_body<NW, CHECKER, SW>(A); } \
     extern "C" int LAUNCHER(const KernelArgs* args, int count, void* stream, uint32_t* lds_high_water) {                                \
         if (count <= 0) return 0;                                                                                                        \
         typedef void (*kernel_t)(const KernelArgs);                                                                                      \
@@ -2653,3 +2655,6 @@ __device__ __forceinline__ void bulk_body(const KernelArgs& A) {
         hipLaunchKernelGGL(fn, dim3(count + (args->n_helpers > 0 ? args->n_helpers : 0)), dim3(PDMPC_WAVE * args->n_waves), args->lds.total, (hipStream_t)stream, *args); \
         return (int)hipGetLastError();                                                                                                   \
     }
+#define PDMPC_BULK_KERNEL(NAME, LAUNCHER, NW, CHECKER, MAXWAVES, KERNEL)                    \
+    PDMPC_BULK_INSTANCE(NAME, LAUNCHER, NW, CHECKER, MAXWAVES, SwitchesProduct<KERNEL>)  \
+    PDMPC_BULK_INSTANCE(NAME##_any, LAUNCHER##_any, NW, CHECKER, MAXWAVES, SwitchesFromArgs)

@@ -257,6 +257,7 @@ struct Tuning {
     int debug_lds = 0;      // print the LDS layout of every launch
     int debug_host = 0;     // 1: a line per launch; 2: the host-time breakdown of the literal path
     int debug_progress = 0; // live counters in host-mapped memory (pdmpc_debug_progress)
+    int generic = 0;        // 1: every search launch runs the generic instantiation of its kernel, which reads all switches from KernelArgs (A/B and tests; pdmpc_device.h: ProductSwitches)
 };
 
 // The LDS layout of one launch_range (api.cpp: compute_lds_bulk for the graph search, compute_lds_sampled for the sampled optimizer):

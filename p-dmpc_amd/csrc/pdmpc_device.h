@@ -238,6 +238,24 @@ struct KernelArgs {
                                // dispatched before their predecessors -- the adversarial order the watchdog + resident slices must survive
 };
 
+// Every search kernel is built twice from one body (bulk_search.hpp).  The PRODUCT instantiation (pdmpc_bulk_kernel, _wide, _sat,
+// _compact) has the debug and test switches below compiled in at these values -- the defaults of Tuning --;
+// the maneuver areas are where the product's launches of that kernel have them: in LDS for the one-mask-word InterX kernel and
+// the separating-axis kernel, in L2 for the compact kernel (its layout leaves them there) and for the wide kernel (the only automaton
+// of more than 64 trims, the realistic one, has 527 maneuvers: their areas never fit; a wide automaton small enough to keep its areas
+// in LDS would always run pdmpc_bulk_kernel_wide_any).  KernelArgs::progress is read by no search kernel and selects nothing.  A uniform value that is a constant costs the
+// round loop no scalar register.  The GENERIC instantiation (the same names + _any) reads all of them from
+// KernelArgs.  api.cpp: dispatch launches the product instantiation exactly when matches() holds.
+enum { PDMPC_BULK = 0, PDMPC_BULK_WIDE = 1, PDMPC_BULK_SAT = 2, PDMPC_BULK_COMPACT = 3 };  // the four search kernels
+struct ProductSwitches {
+    static constexpr int32_t debug_tail = 0, bk_force_tie = 0, reverse_dispatch = 0, bk_tentative = 1, bk_fast_arrival = 1, speculate = 1;
+    static constexpr int32_t areas_in_lds(int kernel) { return kernel == PDMPC_BULK || kernel == PDMPC_BULK_SAT ? 1 : 0; }
+    static bool matches(const KernelArgs& a, int kernel) {
+        return a.debug_tail == debug_tail && a.bk_force_tie == bk_force_tie && a.reverse_dispatch == reverse_dispatch && a.bk_tentative == bk_tentative &&
+               a.bk_fast_arrival == bk_fast_arrival && a.speculate == speculate && a.areas_in_lds == areas_in_lds(kernel);
+    }
+};
+
 // The joint search of centralized control (joint_kernel.hip): one workgroup per problem, problem p = packed slots
 // [problem_off[p], problem_off[p + 1]).  Joint node i of a problem is the N records nodes[(first slot + v) * max_nodes + i], v < N:
 // vehicle v's pose and trim, k, parent, and the node's joint g and h in every one of them.  The open list keeps its first heap_lds
@@ -442,12 +460,17 @@ int pdmpc_launch_bounded_coupling(const BoundArgs* args, void* stream);
 int pdmpc_launch_bounded_coupling_grouped(const BoundArgs* args, void* stream);
 // bulk_kernel*.hip: the graph search as bulk-synchronous passes (count searches + args->n_helpers helper workgroups in ONE launch) for the
 // InterX checker with one successor-mask word / with any number of them, and for the separating-axis checker; lds_high_water = the
-// handle's record of the dynamic LDS size set so far on that kernel
+// handle's record of the dynamic LDS size set so far on that kernel.  Each launches the product instantiation, its _any twin the generic
+// one (ProductSwitches); every instantiation has a high-water mark of its own.
 int pdmpc_launch_bulk(const KernelArgs* args, int count, void* stream, uint32_t* lds_high_water);
+int pdmpc_launch_bulk_any(const KernelArgs* args, int count, void* stream, uint32_t* lds_high_water);
 int pdmpc_launch_bulk_wide(const KernelArgs* args, int count, void* stream, uint32_t* lds_high_water);
+int pdmpc_launch_bulk_wide_any(const KernelArgs* args, int count, void* stream, uint32_t* lds_high_water);
 int pdmpc_launch_bulk_sat(const KernelArgs* args, int count, void* stream, uint32_t* lds_high_water);
+int pdmpc_launch_bulk_sat_any(const KernelArgs* args, int count, void* stream, uint32_t* lds_high_water);
 // bulk_kernel_compact.hip: the InterX / one-mask-word kernel built for 8 wavefronts and at most 80 KB of LDS: two workgroups per CU
 int pdmpc_launch_bulk_compact(const KernelArgs* args, int count, void* stream, uint32_t* lds_high_water);
+int pdmpc_launch_bulk_compact_any(const KernelArgs* args, int count, void* stream, uint32_t* lds_high_water);
 // util_kernels.hip: (cost-to-come of the final node, status) of n result records into lean[2 * n]
 int pdmpc_launch_gather_lean(const pdmpc_vehicle_out* out, int n, int Hp, double* lean, void* stream);
 // sampled_kernel.hip: the sampled optimizer (MonteCarloTreeSearch.m), `count` workgroups of one wavefront

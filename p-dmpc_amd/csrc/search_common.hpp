@@ -128,14 +128,38 @@ struct ExpandEnv {
     int Hp, n, nw, lane;
 };
 
+// Where a search kernel gets its debug / test switches from (the template parameter SW of the prologue, the search and the helper
+// body): SwitchesFromArgs reads KernelArgs -- the generic instantiation --, SwitchesProduct has ProductSwitches' values compiled in,
+// so that everything they guard folds away and none of them is a live uniform value in the round loop (pdmpc_device.h).
+struct SwitchesFromArgs {
+    __device__ __forceinline__ static int debug_tail(const KernelArgs& A) { return A.debug_tail; }
+    __device__ __forceinline__ static bool force_tie(const KernelArgs& A) { return A.bk_force_tie != 0; }
+    __device__ __forceinline__ static bool reverse_dispatch(const KernelArgs& A) { return A.reverse_dispatch != 0; }
+    __device__ __forceinline__ static bool tentative(const KernelArgs& A) { return A.bk_tentative != 0; }
+    __device__ __forceinline__ static bool fast_arrival(const KernelArgs& A) { return A.bk_fast_arrival != 0; }
+    __device__ __forceinline__ static bool speculate(const KernelArgs& A) { return A.speculate != 0; }
+    __device__ __forceinline__ static int areas_in_lds(const KernelArgs& A) { return A.areas_in_lds; }
+};
+template <int KERNEL>
+struct SwitchesProduct {
+    __device__ __forceinline__ static constexpr int debug_tail(const KernelArgs&) { return ProductSwitches::debug_tail; }
+    __device__ __forceinline__ static constexpr bool force_tie(const KernelArgs&) { return ProductSwitches::bk_force_tie != 0; }
+    __device__ __forceinline__ static constexpr bool reverse_dispatch(const KernelArgs&) { return ProductSwitches::reverse_dispatch != 0; }
+    __device__ __forceinline__ static constexpr bool tentative(const KernelArgs&) { return ProductSwitches::bk_tentative != 0; }
+    __device__ __forceinline__ static constexpr bool fast_arrival(const KernelArgs&) { return ProductSwitches::bk_fast_arrival != 0; }
+    __device__ __forceinline__ static constexpr bool speculate(const KernelArgs&) { return ProductSwitches::speculate != 0; }
+    __device__ __forceinline__ static constexpr int areas_in_lds(const KernelArgs&) { return ProductSwitches::areas_in_lds(KERNEL); }
+};
+
 // Prologue shared by the kernels: carves the LDS allocation (offsets from KernelArgs::lds), stages the MPA tables, the vehicle
 // record and its obstacle soups, initialises the result record and the predecessor bookkeeping, and fills the context X.
+template <class SW>
 __device__ __forceinline__ void search_prologue(const KernelArgs& A, Ctx& X, LDS_AS unsigned char* lsm) {
     const int tid = threadIdx.x;
     const int lane = tid & (PDMPC_WAVE - 1);
     const int wave = uni_i(tid >> 6);
     const int blk = (int)blockIdx.x - A.bk_helpers_first;  // (helper workgroups in front: bulk_body)
-    const int slot = A.first + (A.reverse_dispatch ? A.n_searches - 1 - blk : blk);
+    const int slot = A.first + (SW::reverse_dispatch(A) ? A.n_searches - 1 - blk : blk);
     const int Hp = A.Hp;
     const int n = A.n_trims;
     const int nw = A.n_words;
@@ -183,7 +207,7 @@ __device__ __forceinline__ void search_prologue(const KernelArgs& A, Ctx& X, LDS
     C.l_soup = l_soup;
     C.l_soff = l_soff;
     C.l_hoff = l_hoff;
-    C.areas_in_lds = A.areas_in_lds;
+    C.areas_in_lds = SW::areas_in_lds(A);
     C.Hp = Hp;
     C.checker = A.checker;
     C.sh = (lds_d2*)(lsm + PDMPC_LK_SHAPE) + wave * (2 * PDMPC_VMAX + 1);
@@ -202,7 +226,7 @@ __device__ __forceinline__ void search_prologue(const KernelArgs& A, Ctx& X, LDS
         stage16(l_mask, A.succ_mask, (mask_bytes + 15) / 16, tid);
         stage16(l_mi, A.man_index, (n * n * 2 + 15) / 16, tid);
         stage16(l_pose, A.man_pose, A.n_man * 2, tid);
-        if (A.areas_in_lds) stage16(lsm + A.lds.area, A.man_area, A.n_man * 3 * PDMPC_VMAX, tid);
+        if (SW::areas_in_lds(A)) stage16(lsm + A.lds.area, A.man_area, A.n_man * 3 * PDMPC_VMAX, tid);
     }
     // ---- prologue 2: vehicle record, result record defaults
     if (tid < Hp) {
@@ -278,7 +302,7 @@ __device__ __forceinline__ void search_prologue(const KernelArgs& A, Ctx& X, LDS
     P.n_pred = n_pred;
     P.Hp = Hp;
     bool dep_timeout = false;
-    const bool speculate = A.speculate && n_pred <= 64;
+    const bool speculate = SW::speculate(A) && n_pred <= 64;
     if (n_pred > 0) {
         const d2 nanpt = d2{__longlong_as_double(0x7ff8000000000000LL), __longlong_as_double(0x7ff8000000000000LL)};
         for (int idx = tid; idx < Hp * pred_cols; idx += (int)blockDim.x) {
