@@ -183,6 +183,17 @@ int pdmpc_get_config(pdmpc_handle* handle, pdmpc_config* config, int32_t* mpa_up
 
 /* uploads mpa.maneuvers / mpa.transition_matrix_single once (MotionPrimitiveAutomaton.m:5-9) */
 int pdmpc_upload_mpa(pdmpc_handle* handle, const pdmpc_mpa* mpa);
+/* The automaton's reach (include/pdmpc_reach.h): dmax = the longest maneuver displacement hypot(dx, dy), amax = the
+ * largest hypot over the used columns of area, area_without_offset and area_large_offset.  Every point of every area a graph search
+ * checks at step k lies within (k - 1) dmax + amax of its root.  pdmpc_upload_mpa stores the two behind the maneuver areas. */
+int pdmpc_mpa_reach_host(const pdmpc_mpa* mpa, double* dmax, double* amax);
+/* The segments in reach of each step of a search rooted at (root_x, root_y), by the rule of include/pdmpc_reach.h: the host twin of
+ * the lists the graph-search kernel builds in LDS.  Step k = 1 .. Hp has the step_count[k - 1] soup columns of (x, y) from column
+ * step_first[k - 1] on (ranges may repeat: the lanelet boundary is the same for every step); its segment j joins columns j and j + 1 of
+ * that range.  Out: list[list_offset[k - 1] .. list_offset[k]) = the segments in reach of step k, ascending (list holds up to one entry
+ * per segment of every step). */
+int pdmpc_reach_lists_host(int32_t Hp, double dmax, double amax, double root_x, double root_y, const double* x, const double* y, const int32_t* step_first,
+                           const int32_t* step_count, int32_t* list_offset, int32_t* list);
 
 /* Plans n independent vehicles (one computation level).  Blocking.  With n == 1 this is
  * GraphSearch.run_optimizer (GraphSearch.m:14-17). */

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/pdmpc_geometry.h"
+#include "../../include/pdmpc_reach.h"
 #include "handle.hpp"
 
 namespace {
@@ -119,16 +120,26 @@ uint32_t layout_mpa(const pdmpc_handle* h, uint32_t off, bool areas, Layout& L) 
 // thread), d_traveled table, the LDS part of the open set (PDMPC_BK_PER entries per thread), the ready list with its collision
 // flags, the histogram / goal list / expansion lists, 2 KB of small tables, the areas of the published path, validity bytes, then
 // as many node records as fit.
-bool layout_bulk(const pdmpc_handle* h, size_t budget, int n_waves, int areas, int soup_cap, LdsLayout& L, uint32_t& nv, uint32_t& nl, uint32_t ready_cap, bool compact) {
+bool layout_bulk(const pdmpc_handle* h, size_t budget, int n_waves, int areas, int soup_cap, int ll_cap, LdsLayout& L, uint32_t& nv, uint32_t& nl, uint32_t ready_cap, bool compact, bool tight = false) {
     const uint32_t lk_waves = compact ? PDMPC_LK_COMPACT_WAVES : PDMPC_MAX_WAVES, lk_ready = compact ? PDMPC_LK_COMPACT_READY_CAP : 2048u, lk_per = compact ? PDMPC_LK_COMPACT_BK_PER : PDMPC_BK_PER;
     if (ready_cap > lk_ready || (uint32_t)n_waves > lk_waves) return false;
     // the regions of fixed size at the kernel's compile-time offsets (pdmpc_device.h: PDMPC_LK_*) ...
+    // ... the reach lists right behind them (InterX only: the separating-axis kernels have none and keep their layout; 2 B per soup
+    // column, the boundary's once per step: their address is a constant too.  tight: ONE list of the boundary, the last step's, serves
+    // every step — a superset of each step's own — and fewer node records are asked for: the layout of last resort, for a soup and
+    // tables that leave the LDS no room for more) ...
+    L.reach = pdmpc_lk_fixed(lk_waves, lk_ready, lk_per, &L);
+    L.reach_shared = tight ? 1u : 0u;
+    const uint32_t list_entries = h->cfg.checker == PDMPC_CHECK_INTERX ? (uint32_t)(std::max(soup_cap, 1) + (tight ? 0 : (h->cfg.Hp - 1) * std::max(ll_cap, 0))) : 0u;
     // ... the automaton's tables and the soup behind them
-    uint32_t off = layout_mpa(h, pdmpc_lk_fixed(lk_waves, lk_ready, lk_per, &L), areas, L);
+    uint32_t off = layout_mpa(h, align16(L.reach + list_entries * 2), areas, L);
     L.soup = off;
     off = align16(off + (uint32_t)std::max(soup_cap, 1) * 16);
     L.tree16 = L.bk_hist;  // (the sampled optimizer's region: not part of this layout)
-    const uint32_t min_nodes = 64 * (uint32_t)sizeof(NodeRec) + 1024;
+    // (LDS-resident node records are a cache of the arena's first NL nodes: every access takes the HBM copy for a node beyond NL
+    // (node_piece, node_store), and the joint search runs the same code with NL = 0.  64 is what keeps a light search's first rounds in
+    // LDS; the layout of last resort asks for 16 — the root and its children — because its alternative is PDMPC_ERR_CAPACITY)
+    const uint32_t min_nodes = (tight ? 16u : 64u) * (uint32_t)sizeof(NodeRec) + 1024;
     if ((size_t)off + min_nodes + 256 > budget) return false;
     const uint32_t rest = (uint32_t)(budget - off - 256);
     nv = std::min<uint32_t>(16384u, std::max<uint32_t>(compact ? 512u : 1024u, rest / 6));
@@ -149,7 +160,7 @@ bool bulk_has_helpers(const Tuning& T, int n_cu, int n_launch) {
     return n_launch <= n_cu - 2;
 }
 
-int compute_lds_bulk(const pdmpc_handle* h, int n_launch, int soup_cap, LaunchLayout& out) {
+int compute_lds_bulk(const pdmpc_handle* h, int n_launch, int soup_cap, int ll_cap, LaunchLayout& out) {
     const Tuning& T = h->tune;
     // large rounds pay where helper workgroups share them; without helpers the LDS is better spent on node records
     const int ready_want = bulk_has_helpers(T, h->n_cu, n_launch) ? T.ready : std::max(256, T.ready / 2);
@@ -167,7 +178,7 @@ int compute_lds_bulk(const pdmpc_handle* h, int n_launch, int soup_cap, LaunchLa
         LdsLayout L{};
         const int waves = T.waves >= 0 ? std::min(T.waves, PDMPC_LK_COMPACT_WAVES) : PDMPC_LK_COMPACT_WAVES;
         const int ready = std::min(std::min(ready_want, 3 * PDMPC_WAVE * waves), (int)PDMPC_LK_COMPACT_READY_CAP);
-        if (layout_bulk(h, kLdsMax / 2, waves, 0, soup_cap, L, nv, nl, (uint32_t)ready, true)) {
+        if (layout_bulk(h, kLdsMax / 2, waves, 0, soup_cap, ll_cap, L, nv, nl, (uint32_t)ready, true)) {
             out = {L, waves, (int)nl, (int)nv, 0, ready, true};
             return PDMPC_OK;
         }
@@ -176,9 +187,17 @@ int compute_lds_bulk(const pdmpc_handle* h, int n_launch, int soup_cap, LaunchLa
     for (int areas = 1; areas >= 0; --areas) {  // (the maneuver areas fall back to L2 when the soup leaves no room)
         LdsLayout L{};
         const int ready = std::min(ready_want, 3 * PDMPC_WAVE * waves);
-        if (!layout_bulk(h, kLdsMax, waves, areas, soup_cap, L, nv, nl, (uint32_t)ready, false)) continue;
+        if (!layout_bulk(h, kLdsMax, waves, areas, soup_cap, ll_cap, L, nv, nl, (uint32_t)ready, false)) continue;
         out = {L, waves, (int)nl, (int)nv, areas, ready, false};
         return PDMPC_OK;
+    }
+    {
+        LdsLayout L{};
+        const int ready = std::min(ready_want, 3 * PDMPC_WAVE * waves);
+        if (layout_bulk(h, kLdsMax, waves, 0, soup_cap, ll_cap, L, nv, nl, (uint32_t)ready, false, true)) {
+            out = {L, waves, (int)nl, (int)nv, 0, ready, false};
+            return PDMPC_OK;
+        }
     }
     char buf[256];
     snprintf(buf, sizeof buf, "obstacle soup (%d columns) + MPA tables do not fit into %zu B of LDS", soup_cap, kLdsMax);
@@ -470,7 +489,7 @@ int launch_range(pdmpc_handle* h, int first, int count, bool safe) {
     if (!B.perm.empty() && (first != 0 || count != B.n_packed)) return fail(PDMPC_ERR_INVALID, "range launches need a batch packed in level order (predecessors in lower slots)");
     if (count == 0) return PDMPC_OK;
     LaunchLayout lay;
-    int rc = search ? compute_lds_bulk(h, count, B.soup_cap, lay) : compute_lds_sampled(h, B.soup_cap, B.cand_cap, lay);
+    int rc = search ? compute_lds_bulk(h, count, B.soup_cap, B.ll_cap, lay) : compute_lds_sampled(h, B.soup_cap, B.cand_cap, lay);
     if (rc) return rc;
     KernelArgs a{};
     set_launch_args(h, B, lay, first, count, safe, a);
@@ -560,6 +579,43 @@ int pdmpc_destroy(pdmpc_handle* h) {
     return PDMPC_OK;
 }
 
+// The automaton's reach (include/pdmpc_reach.h): the longest maneuver displacement and the largest |area point| over the used columns
+// of the three area variants.
+static void mpa_reach(const pdmpc_mpa* mpa, double& dmax, double& amax) {
+    dmax = 0.0;
+    amax = 0.0;
+    for (int t = 0; t < mpa->n_maneuvers; ++t) {
+        const pdmpc_maneuver& m = mpa->maneuvers[t];
+        dmax = std::max(dmax, hypot(m.dx, m.dy));
+        const double(*src[3])[PDMPC_VMAX] = {m.area, m.area_without_offset, m.area_large_offset};
+        for (int a = 0; a < 3; ++a)
+            for (int v = 0; v < m.n_cols && v < PDMPC_VMAX; ++v) amax = std::max(amax, hypot(src[a][0][v], src[a][1][v]));
+    }
+}
+
+int pdmpc_mpa_reach_host(const pdmpc_mpa* mpa, double* dmax, double* amax) {
+    if (!mpa || !dmax || !amax || (mpa->n_maneuvers > 0 && !mpa->maneuvers)) return fail(PDMPC_ERR_INVALID, "pdmpc_mpa_reach_host: null argument");
+    mpa_reach(mpa, *dmax, *amax);
+    return PDMPC_OK;
+}
+
+int pdmpc_reach_lists_host(int32_t Hp, double dmax, double amax, double root_x, double root_y, const double* x, const double* y, const int32_t* step_first,
+                           const int32_t* step_count, int32_t* list_offset, int32_t* list) {
+    if (Hp < 1 || Hp > PDMPC_HP_MAX || !step_first || !step_count || !list_offset) return fail(PDMPC_ERR_INVALID, "pdmpc_reach_lists_host: bad argument");
+    int32_t n = 0;
+    for (int k = 1; k <= Hp; ++k) {
+        const int32_t a = step_first[k - 1], c = step_count[k - 1];
+        if (a < 0 || c < 0 || (c > 1 && (!x || !y || !list))) return fail(PDMPC_ERR_INVALID, "pdmpc_reach_lists_host: bad step ranges");
+        double box[4];
+        pdmpc_reach_box(dmax, amax, k, root_x, root_y, box);
+        list_offset[k - 1] = n;
+        for (int32_t j = 0; j + 1 < c; ++j)
+            if (pdmpc_reach_in(x[a + j], y[a + j], x[a + j + 1], y[a + j + 1], box[0], box[1], box[2], box[3])) list[n++] = j;
+    }
+    list_offset[Hp] = n;
+    return PDMPC_OK;
+}
+
 int pdmpc_upload_mpa(pdmpc_handle* h, const pdmpc_mpa* mpa) {
     if (!h || !mpa) return fail(PDMPC_ERR_INVALID, "null argument");
     if (mpa->n_trims < 1 || mpa->n_trims > 1023) return fail(PDMPC_ERR_INVALID, "n_trims must be in 1..1023");
@@ -581,7 +637,7 @@ int pdmpc_upload_mpa(pdmpc_handle* h, const pdmpc_mpa* mpa) {
     for (int i = 0; i < n * n; ++i) mi[i] = (int16_t)mpa->maneuver_index[i];
     const int T = mpa->n_maneuvers;
     std::vector<DevManPose> pose((size_t)std::max(T, 1));
-    std::vector<double> area((size_t)std::max(T, 1) * 3 * PDMPC_VMAX * 2, 0.0);
+    std::vector<double> area((size_t)std::max(T, 1) * 3 * PDMPC_VMAX * 2 + 2, 0.0);  // (+ the automaton's reach behind the areas)
     for (int t = 0; t < T; ++t) {
         const pdmpc_maneuver& m = mpa->maneuvers[t];
         if (m.n_cols < 2 || m.n_cols > PDMPC_VMAX) return fail(PDMPC_ERR_INVALID, "maneuver area column count out of range");
@@ -597,6 +653,7 @@ int pdmpc_upload_mpa(pdmpc_handle* h, const pdmpc_mpa* mpa) {
                 area[(((size_t)t * 3 + a) * PDMPC_VMAX + v) * 2 + 1] = src[a][1][v];
             }
     }
+    mpa_reach(mpa, area[(size_t)T * 3 * PDMPC_VMAX * 2], area[(size_t)T * 3 * PDMPC_VMAX * 2 + 1]);  // (Dmax, Amax: the graph search's reach lists)
     if (h->d_mask.ensure(mask.size()) || h->d_mi.ensure(mi.size()) || h->d_pose.ensure(pose.size()) || h->d_area.ensure(area.size()))
         return fail(PDMPC_ERR_HIP, "hipMalloc failed for the MPA tables");
     HIPCHK(hipMemcpy(h->d_mask.p, mask.data(), mask.size() * 8, hipMemcpyHostToDevice));

@@ -40,6 +40,8 @@
 
 #include "frontier_common.hpp"
 
+#include "../../include/pdmpc_reach.h"
+
 // shared words of the bulk kernel (aliases of words the frontier kernel uses for things this kernel does not have)
 #define BK_P2 3                   // ready entries a thread handles in the verdict pass (the ready list holds at most BK_P2 * blockDim entries)
 #define BK_PER PDMPC_BK_PER       // near entries per thread a selection pass holds in registers (near capacity = BK_PER * blockDim)
@@ -48,6 +50,7 @@
 namespace {
 
 typedef volatile LDS_AS unsigned long long lds_vu64;
+typedef LDS_AS uint16_t lds_u16;
 
 // exclusive prefix of v over the threads of the workgroup (thread order), total to every thread.  Every thread calls; ONE barrier:
 // consecutive calls alternate between two partials arrays (the caller passes them), so the partials of a call are not rewritten
@@ -92,6 +95,102 @@ struct BkCheck {
     const lds_i32* l_lit;  // literal soup length per step (the predecessors' slots of VMAX columns each follow)
     int areas_in_lds, ll_base, ll_len, Hp;
 };
+
+// The reach lists (include/pdmpc_reach.h): per step and soup the segments an edge check of that step can meet
+// at all, ascending, with their counts.  Squares, counts and lists live at compile-time offsets (PDMPC_LK_REACH; the lists of run-time
+// length behind the fixed regions, in front of the automaton's tables: no register holds their address): the list of a step's vehicle
+// obstacles / HDV sets at the index of that soup's first column, the boundary's list of step k at ll_base + (k - 1) * ll_len.
+#define BK_RLIST(lsm) ((lds_u16*)((lsm) + PDMPC_LK_FIXED_END))
+// (the base of the dynamic LDS allocation as the constant it is: what a check item reads of these regions costs no register)
+__device__ __forceinline__ LDS_AS unsigned char* bk_lds_base() {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    return (LDS_AS unsigned char*)smem;
+}
+#define BK_RBOX(lsm) ((lds_f64*)((lsm) + PDMPC_LK_REACH))
+#define BK_RCNT(lsm) ((lds_u32*)((lsm) + PDMPC_LK_REACH + PDMPC_LK_REACH_CNT))
+#define BK_RSTALE(lsm) ((volatile lds_u32*)((lsm) + PDMPC_LK_REACH + PDMPC_LK_REACH_STALE))
+#define BK_RSC(lsm) ((lds_i32*)((lsm) + PDMPC_LK_REACH + PDMPC_LK_REACH_SC))
+// What an InterX check item reads of its search besides the lists, as LDS words at constant addresses (the workgroup's scalar registers
+// are spent, DESIGN.md section 3.9: a value read here is one LDS load per item, not a reload per use).  Thread 0 writes them.
+__device__ __forceinline__ void bk_reach_scalars(const BkCheck& C, LDS_AS unsigned char* lsm, bool shared_boundary_list) {
+    lds_i32* sc = BK_RSC(lsm);
+    sc[0] = (int32_t)((LDS_AS unsigned char*)C.l_soup - lsm);
+    sc[1] = (int32_t)((LDS_AS unsigned char*)C.l_area - lsm);
+    sc[2] = C.Hp;
+    sc[3] = C.ll_base;
+    sc[4] = C.ll_len;
+    sc[5] = shared_boundary_list ? 0 : C.ll_len;  // (one list of the boundary for every step: the last step's, a superset of each step's own)
+}
+struct BkItemCtx {  // the same values for a check item, each read where it is used: from the LDS words (InterX) or from the caller's registers
+    const BkCheck& C;
+    int interx;
+    __device__ __forceinline__ int word(int i) const { return BK_RSC(bk_lds_base())[i]; }
+    __device__ __forceinline__ const lds_d2* l_soup() const { return interx ? (const lds_d2*)(bk_lds_base() + word(0)) : C.l_soup; }
+    __device__ __forceinline__ const lds_d2* l_area() const { return interx ? (const lds_d2*)(bk_lds_base() + word(1)) : C.l_area; }
+    __device__ __forceinline__ int Hp() const { return interx ? word(2) : C.Hp; }
+    __device__ __forceinline__ int ll_base() const { return interx ? word(3) : C.ll_base; }
+    __device__ __forceinline__ int ll_len() const { return interx ? word(4) : C.ll_len; }
+    __device__ __forceinline__ int ll_stride() const { return interx ? word(5) : C.ll_len; }
+};
+template <int CHECKER>
+__device__ __forceinline__ BkItemCtx bk_item_ctx(const BkCheck& C) {
+    return BkItemCtx{C, CHECKER == PDMPC_CHECK_INTERX ? 1 : 0};
+}
+// the squares of the steps around the search's root (tid < Hp; the automaton's reach sits behind its areas in HBM: read here only)
+__device__ __forceinline__ void bk_reach_boxes(const KernelArgs& A, const DevVehicle* V, LDS_AS unsigned char* lsm, int tid) {
+    if (tid < A.Hp) {
+        const double* reach = A.man_area + (size_t)A.n_man * 3 * PDMPC_VMAX * 2;
+        double box[4];
+        pdmpc_reach_box(reach[0], reach[1], tid + 1, V->x0, V->y0, box);
+        lds_f64* rb = BK_RBOX(lsm) + 4 * tid;
+        rb[0] = box[0];
+        rb[1] = box[1];
+        rb[2] = box[2];
+        rb[3] = box[3];
+    }
+}
+// One wavefront per (step, soup) — soups: bit 0 vehicle obstacles, 1 HDV sets, 2 lanelet boundary —: the segments 64 at a time, a ballot
+// and the lanes' ranks in it compact the indices of those in reach.  Every wavefront of the workgroup calls; no barrier inside.
+template <int SOUPS>
+__device__ __forceinline__ void bk_reach_build(const BkCheck& C, LDS_AS unsigned char* lsm, int lane, int wave, int n_waves) {
+    const lds_f64* rbox = BK_RBOX(lsm);
+    lds_u32* rcnt = BK_RCNT(lsm);
+    for (int u = wave; u < (SOUPS == 1 ? 1 : 3) * C.Hp; u += n_waves) {  // (uniform per wavefront)
+        const int k = SOUPS == 1 ? u : u / 3, s = SOUPS == 1 ? 0 : u - 3 * k;  // (k: 0-based step)
+        int base, n, at, kb = k;  // (kb: the step whose square decides)
+        if (s == 0) {
+            base = C.l_soff[k];
+            n = C.l_soff[k + 1] - base - 1;
+            at = base;
+        } else if (s == 1) {
+            base = C.l_hoff[k];
+            n = C.l_hoff[k + 1] - base - 1;
+            at = base;
+        } else {
+            const int stride = BK_RSC(lsm)[5];  // (0: every step writes the same list, the last step's, and the same count)
+            base = C.ll_base;
+            n = C.ll_len - 1;
+            at = base + k * stride;
+            kb = stride ? k : C.Hp - 1;
+        }
+        const double x_lo = rbox[4 * kb], x_hi = rbox[4 * kb + 1], y_lo = rbox[4 * kb + 2], y_hi = rbox[4 * kb + 3];
+        const lds_d2* q = C.l_soup + base;
+        lds_u16* lst = BK_RLIST(lsm) + at;
+        uint32_t cnt = 0;
+        for (int j0 = 0; j0 < n; j0 += PDMPC_WAVE) {
+            const int j = j0 + lane;
+            bool in = false;
+            if (j < n) {
+                const d2 q0 = q[j], q1 = q[j + 1];
+                in = pdmpc_reach_in(q0.x, q0.y, q1.x, q1.y, x_lo, x_hi, y_lo, y_hi) != 0;
+            }
+            const unsigned long long m = __ballot(in);
+            if (in) lst[cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint16_t)j;
+            cnt += (uint32_t)__builtin_popcountll(m);
+        }
+        if (lane == 0) rcnt[s * PDMPC_HP_MAX + k] = cnt;
+    }
+}
 
 // Tentative areas.  A predecessor that is still planning has its EXPECTED areas in its soup slots: what it publishes should its search
 // be exhausted, i.e. its previous plan shifted by one step (PrioritizedController.m:568-616, 678-718) — where it most likely ends up
@@ -176,8 +275,36 @@ __device__ __forceinline__ void bk_item_counts(int M_k, int Hk, int ll_len, int&
     n1 = CHECKER == PDMPC_CHECK_INTERX ? (Hk > 1 ? Hk - 1 : 0) : 0;
     n2 = ll_len > 1 ? ll_len - 1 : 0;
 }
+// what the check items of a node of step k (1-based) cover per soup: InterX the segments in reach (the lists' counts), the
+// separating-axis checker all columns / boundary segments
+template <int CHECKER>
+__device__ __forceinline__ void bk_reach_counts(const BkCheck& C, const lds_u32* rcnt, int k, int& n0, int& n1, int& n2) {
+    if (CHECKER == PDMPC_CHECK_INTERX) {
+        n0 = (int)rcnt[k - 1];
+        n1 = (int)rcnt[PDMPC_HP_MAX + k - 1];
+        n2 = (int)rcnt[2 * PDMPC_HP_MAX + k - 1];
+    } else {
+        bk_item_counts<CHECKER>(C.l_soff[k] - C.l_soff[k - 1], C.l_hoff[k] - C.l_hoff[k - 1], C.ll_len, n0, n1, n2);
+    }
+}
+// chm[ls] for S = 1 << ls: the chunks of the step with the most (threads 0 .. 7 of `t`)
+template <int CHECKER>
+__device__ __forceinline__ void bk_chunk_table(const BkCheck& C, const lds_u32* rcnt, lds_u32* chm, int t) {
+    if (t < 0 || t >= 8) return;
+    const int ls = t, Sg = 1 << ls;
+    uint32_t mx = 0;
+    for (int k = 1; k <= C.Hp; ++k) {
+        int n0, n1, n2;
+        bk_reach_counts<CHECKER>(C, rcnt, k, n0, n1, n2);
+        const uint32_t ch = (uint32_t)(((n0 + Sg - 1) >> ls) + ((n1 + Sg - 1) >> ls) + ((n2 + Sg - 1) >> ls));
+        mx = ch > mx ? ch : mx;
+    }
+    chm[ls] = mx;
+}
 template <int CHECKER, class Src>
 __device__ __forceinline__ void bk_check_items(const BkCheck& C, const Src& src, volatile lds_u32* r_flag, uint32_t r0, uint32_t R, int ls, uint32_t chmax, unsigned long long pend, int tid, int nthreads) {
+    const lds_u32* rcnt = BK_RCNT(bk_lds_base());
+    const lds_u16* rlist = BK_RLIST(bk_lds_base());
     const uint32_t items = R * chmax;
     const int Sg = 1 << ls;
     for (uint32_t item = (uint32_t)tid; item < items; item += (uint32_t)nthreads) {
@@ -186,13 +313,14 @@ __device__ __forceinline__ void bk_check_items(const BkCheck& C, const Src& src,
         uint32_t parent, packed;
         src.link(r, parent, packed);
         if (!parent) continue;  // the root has no edge (GraphSearch.m:137-139)
+        const BkItemCtx I = bk_item_ctx<CHECKER>(C);
         const int k = NODE_K(packed), m = NODE_MAN(packed), ncols = NODE_COLS(packed);
         const int so = C.l_soff[k - 1], ho = C.l_hoff[k - 1];
-        const int M_k = C.l_soff[k] - so, Hk = C.l_hoff[k] - ho;
+        const int M_k = C.l_soff[k] - so;
         int n0, n1, n2;
-        bk_item_counts<CHECKER>(M_k, Hk, C.ll_len, n0, n1, n2);
+        bk_reach_counts<CHECKER>(C, rcnt, k, n0, n1, n2);
         const uint32_t c0 = (uint32_t)((n0 + Sg - 1) >> ls), c1 = (uint32_t)((n1 + Sg - 1) >> ls), c2 = (uint32_t)((n2 + Sg - 1) >> ls);
-        int base, t0, left, which = 0;
+        int base, t0, left, which = 0, lat = 0;  // (lat: where the boundary's list of this step begins, relative to the boundary)
         if (c < c0) {
             base = so;
             t0 = (int)(c << ls);
@@ -202,10 +330,11 @@ __device__ __forceinline__ void bk_check_items(const BkCheck& C, const Src& src,
             t0 = (int)((c - c0) << ls);
             left = n1 - t0;
         } else if (c < c0 + c1 + c2) {
-            base = C.ll_base;
+            base = I.ll_base();
             t0 = (int)((c - c0 - c1) << ls);
             left = n2 - t0;
-            which = k == C.Hp ? 2 : 1;  // large offset at k == Hp, else without offset (GraphSearch.m:161-174)
+            lat = (k - 1) * I.ll_stride();
+            which = k == I.Hp() ? 2 : 1;  // large offset at k == Hp, else without offset (GraphSearch.m:161-174)
         } else {
             continue;
         }
@@ -214,14 +343,21 @@ __device__ __forceinline__ void bk_check_items(const BkCheck& C, const Src& src,
         src.pose(r, parent, pX, pY, cc, ss);
         const size_t abase = ((size_t)m * 3 + (size_t)which) * PDMPC_VMAX;
         d2 pt[PDMPC_VMAX];
+        if (C.areas_in_lds) {  // (one branch around the eight loads, not a choice per load: the places are reloaded once)
+#pragma unroll
+            for (int i = 0; i < PDMPC_VMAX; ++i) pt[i] = I.l_area()[abase + i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < PDMPC_VMAX; ++i) pt[i] = C.g_area[abase + i];
+        }
 #pragma unroll
         for (int i = 0; i < PDMPC_VMAX; ++i) {  // (columns beyond ncols are padding: transformed, never used)
-            const d2 a = C.areas_in_lds ? (d2)C.l_area[abase + i] : C.g_area[abase + i];
+            const d2 a = pt[i];
             pt[i].x = cc * a.x - ss * a.y + pX;  // GraphSearch.m:158 / :162 / :168
             pt[i].y = ss * a.x + cc * a.y + pY;  // :159 / :163 / :169
         }
-        const lds_d2* q = C.l_soup + base + t0;
         if (CHECKER == PDMPC_CHECK_SAT) {
+            const lds_d2* q = I.l_soup() + base + t0;
             uint32_t fnd = 0;  // 1: overlaps a real area, 2: an expected one (the slot of a predecessor that is still planning, `pend`)
             if (which == 0) {  // the polygons that begin in this chunk of the step's soup ([polygon, NaN] ..., then the predecessors' slots)
                 const int lit = C.l_lit[k - 1];
@@ -247,22 +383,24 @@ __device__ __forceinline__ void bk_check_items(const BkCheck& C, const Src& src,
             if (fnd) __hip_atomic_fetch_or((lds_u32*)&r_flag[r], fnd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             continue;
         }
-        d2 q0 = q[0];
+        // (InterX walks the chunk's entries of the soup's reach list: the segments that can decide anything)
+        const lds_u16* lst = rlist + base + lat + t0;
+        const lds_d2* sp = I.l_soup() + base;
         // (segments of the slots of predecessors that are still planning — `pend` — hold expected areas: a crossing there is tentative)
-        const int rel0 = (which == 0 && base == so) ? t0 - C.l_lit[k - 1] : -(1 << 20);
+        const int rel0 = (which == 0 && base == so) ? -C.l_lit[k - 1] : -(1 << 20);
         uint32_t found = 0;  // 1: crosses a real area, 2: crosses an expected one
         for (int t = 0; t < tn && !(found & 1u); ++t) {
             // (the area's points are made opaque per segment: the compiler would otherwise hoist the seven edges' dx1, dy1, S1 of the
             // C1 test out of this loop — 42 registers for a test that one segment in ten reaches)
             asm volatile("" : "+v"(pt[0].x), "+v"(pt[0].y), "+v"(pt[1].x), "+v"(pt[1].y), "+v"(pt[2].x), "+v"(pt[2].y), "+v"(pt[3].x), "+v"(pt[3].y), "+v"(pt[4].x), "+v"(pt[4].y),
                          "+v"(pt[5].x), "+v"(pt[5].y), "+v"(pt[6].x), "+v"(pt[6].y), "+v"(pt[7].x), "+v"(pt[7].y));
-            const d2 q1 = q[t + 1];
+            const int j = (int)lst[t];
+            const d2 q0 = sp[j], q1 = sp[j + 1];
             if (interx_segment_n<PDMPC_VMAX>(pt, ncols - 1, q0, q1)) {
-                const int rel = rel0 + t;
+                const int rel = rel0 + j;
                 const bool tent = rel >= 0 && ((pend >> (rel >> 3)) & 1ull) != 0ull;  // (rel >> 3 < 64: a search with more predecessors waits for them all)
                 found |= tent ? 2u : 1u;
             }
-            q0 = q1;
         }
         if (found) __hip_atomic_fetch_or((lds_u32*)&r_flag[r], found, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
@@ -292,9 +430,10 @@ template <int CHECKER>
 __device__ __forceinline__ void bk_recheck_items(const Search& S, const VState& VS, const BkCheck& C, const SpecCtx& P, const uint32_t* vlist, const lds_u32* vcnt, uint32_t cap,
                                                  uint32_t items, unsigned long long arr, const lds_u64s* chg, volatile lds_u32* sh, int tid, int nthreads) {
     for (uint32_t item = (uint32_t)tid; item < items; item += (uint32_t)nthreads) {
+        const BkItemCtx I = bk_item_ctx<CHECKER>(C);
         uint32_t v = item, n_k = 0;
         int ks = 1;
-        for (; ks <= C.Hp; ++ks) {  // the step whose items hold this one
+        for (; ks <= I.Hp(); ++ks) {  // the step whose items hold this one
             n_k = vcnt[ks - 1] < cap ? vcnt[ks - 1] : cap;
             const uint32_t m = n_k * (uint32_t)__builtin_popcountll(chg[ks - 1] & arr);
             if (v < m) break;
@@ -314,13 +453,20 @@ __device__ __forceinline__ void bk_recheck_items(const Search& S, const VState& 
         const double cc = pcs.x, ss = pcs.y, pX = pxy.x, pY = pxy.y;
         const size_t abase = (size_t)m * 3 * PDMPC_VMAX;
         d2 pt[PDMPC_VMAX];
+        if (C.areas_in_lds) {  // (as in bk_check_items)
+#pragma unroll
+            for (int i = 0; i < PDMPC_VMAX; ++i) pt[i] = I.l_area()[abase + i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < PDMPC_VMAX; ++i) pt[i] = C.g_area[abase + i];
+        }
 #pragma unroll
         for (int i = 0; i < PDMPC_VMAX; ++i) {
-            const d2 ar = C.areas_in_lds ? (d2)C.l_area[abase + i] : C.g_area[abase + i];
+            const d2 ar = pt[i];
             pt[i].x = cc * ar.x - ss * ar.y + pX;  // GraphSearch.m:158
             pt[i].y = ss * ar.x + cc * ar.y + pY;  // :159
         }
-        const lds_d2* poly = P.l_soup + P.l_soff[k - 1] + P.l_lit[k - 1] + p * PDMPC_VMAX;
+        const lds_d2* poly = I.l_soup() + P.l_soff[k - 1] + P.l_lit[k - 1] + p * PDMPC_VMAX;
         d2 q0 = poly[0];
         bool hit = false;
         if (CHECKER == PDMPC_CHECK_SAT) {  // are_constraints_satisfied_sat.m:24-35 for this one dynamic obstacle
@@ -557,9 +703,16 @@ __device__ __forceinline__ bool bk_poll_predecessors(const KernelArgs& A, const 
 // their soup slots (PrioritizedController.m:476-491); nthreads threads call (a workgroup, or one wave).
 // (chg, when given: [Hp] 64-bit masks — bit p of chg[k] is set when the area predecessor p publishes for step k + 1 differs from what
 // its slot held, i.e. from the area it was expected to take.  A collision-free edge of that step has been checked against exactly
-// those numbers: only the pairs (step, predecessor) marked here are due for the re-check, bk_recheck_items.)
+// those numbers: only the pairs (step, predecessor) marked here are due for the re-check, bk_recheck_items.
+// rbox, when given (InterX): the squares of the steps, include/pdmpc_reach.h — an area none of whose segments is in reach of its step
+// cannot take an edge of that step away, whatever the slot held: its bit is not set.  The two ballots and the __shfl_down sit in a
+// loop whose last trip is partial, i.e. with some lanes of the wavefront switched off.  That is safe because an area's eight columns
+// never straddle the boundary between active and inactive lanes: idx = tid + trip * nthreads with nthreads a multiple of 64 (the
+// workgroup, or the one wavefront of bk_wait_done) and the item count n_arr * Hp * VMAX a multiple of 8, so the columns v = 0 .. 7 of
+// one area are eight consecutive lanes of one wavefront, aligned to 8, and all of them are in the loop or none is: a ballot's byte g
+// holds exactly that area's columns, and lane v < 7 shuffles from a lane of its own group.)
 __device__ __forceinline__ void bk_incorporate_body(const pdmpc_vehicle_out* out, const int32_t* pred, lds_d2* l_soup, const lds_i32* l_soff, const lds_i32* l_lit, int Hp, unsigned long long arr, int tid,
-                                                    int nthreads, lds_u64s* chg) {
+                                                    int nthreads, lds_u64s* chg, const lds_f64* rbox) {
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);
     const int per = Hp * PDMPC_VMAX, n_arr = __builtin_popcountll(arr);
     for (int idx = tid; idx < n_arr * per; idx += nthreads) {  // (every arrived predecessor's loads side by side)
@@ -575,15 +728,24 @@ __device__ __forceinline__ void bk_incorporate_body(const pdmpc_vehicle_out* out
         lds_d2* slot = l_soup + l_soff[k] + l_lit[k] + p * PDMPC_VMAX + v;
         if (chg) {
             const d2 was = *slot;
-            if (__double_as_longlong(was.x) != __double_as_longlong(pt.x) || __double_as_longlong(was.y) != __double_as_longlong(pt.y))
+            const bool differs = __double_as_longlong(was.x) != __double_as_longlong(pt.x) || __double_as_longlong(was.y) != __double_as_longlong(pt.y);
+            if (rbox) {
+                const double nx = __shfl_down(pt.x, 1), ny = __shfl_down(pt.y, 1);  // (column v + 1: the same area for v < VMAX - 1)
+                const bool in = v + 1 < PDMPC_VMAX && pdmpc_reach_in(pt.x, pt.y, nx, ny, rbox[4 * k], rbox[4 * k + 1], rbox[4 * k + 2], rbox[4 * k + 3]) != 0;
+                const int g = (tid & (PDMPC_WAVE - 1)) & ~(PDMPC_VMAX - 1);
+                const unsigned long long md = __ballot(differs), mi = __ballot(in);
+                if (v == 0 && ((md >> g) & 0xffull) != 0ull && ((mi >> g) & 0xffull) != 0ull)
+                    __hip_atomic_fetch_or(chg + k, 1ull << p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            } else if (differs) {
                 __hip_atomic_fetch_or(chg + k, 1ull << p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
         }
         *slot = pt;
     }
 }
 __device__ __forceinline__ void bk_incorporate(const pdmpc_vehicle_out* out, const int32_t* pred, lds_d2* l_soup, const lds_i32* l_soff, const lds_i32* l_lit, int Hp, unsigned long long arr, int tid,
-                                               int nthreads, lds_u64s* chg) {
-    bk_incorporate_body(out, pred, l_soup, l_soff, l_lit, Hp, arr, tid, nthreads, chg);
+                                               int nthreads, lds_u64s* chg, const lds_f64* rbox) {
+    bk_incorporate_body(out, pred, l_soup, l_soff, l_lit, Hp, arr, tid, nthreads, chg, rbox);
 }
 
 // fr_check_wave with a memory: what to do with an open node a round has selected (1 process it, 3 it comes after the goal candidate,
@@ -670,7 +832,9 @@ __device__ __forceinline__ void bk_wait_done(const uint32_t* done_flag, const in
                                              bool sat, int lane) {
     const lds_u32* pcols = (const lds_u32*)(pshape + Hp * PDMPC_VMAX);
     lds_u64s* chg = (lds_u64s*)(pcols + PDMPC_HP_MAX);
+    LDS_AS unsigned char* reach = (LDS_AS unsigned char*)pshape + (PDMPC_LK_REACH - PDMPC_LK_PSHAPE);  // (the squares and the stale word of the reach lists)
     unsigned long long pend = sh_load64(sh, SH_PEND_LO), fd = sh_load64(sh, BK_FD_LO);
+    const unsigned long long fd_in = fd;
     unsigned long long got = first;  // (in the soup already: checked against the path before anybody is polled)
     uint32_t spins = 0, res = 0;
     for (;;) {
@@ -683,7 +847,7 @@ __device__ __forceinline__ void bk_wait_done(const uint32_t* done_flag, const in
                 __builtin_amdgcn_s_sleep(1);
                 continue;
             }
-            bk_incorporate_body(out, pred, l_soup, l_soff, l_lit, Hp, got, lane, PDMPC_WAVE, chg);
+            bk_incorporate_body(out, pred, l_soup, l_soff, l_lit, Hp, got, lane, PDMPC_WAVE, chg, sat ? (const lds_f64*)nullptr : (const lds_f64*)reach);
             wave_sync();
             pend &= ~got;
             fd |= got;
@@ -737,6 +901,7 @@ __device__ __forceinline__ void bk_wait_done(const uint32_t* done_flag, const in
         sh[BK_FD_LO] = (uint32_t)fd;
         sh[BK_FD_HI] = (uint32_t)(fd >> 32);
         sh[BK_WAITRES] = res;
+        if (fd != fd_in) *(volatile lds_u32*)(reach + PDMPC_LK_REACH_STALE) = 1u;  // (the soup has changed: the next round rebuilds its vehicle-obstacle lists)
         if (res == 2u) sh[BK_PUBLISHED] = 1u;
         sh[BK_IDLE] = sh[BK_IDLE] + spins + 1u;
     }
@@ -938,6 +1103,7 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
     CK.ll_base = X.C.ll_base;
     CK.ll_len = X.C.ll_len;
     CK.Hp = Hp;
+    const lds_u32* rcnt = BK_RCNT(X.lsm);
 
     // ---- root node (GraphSearch.m:34-46) and the chunk tables
     if (tid == 0) {
@@ -985,19 +1151,17 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     if (SW::tentative(A)) bk_tentative_areas(A, P, sh_load64(sh, SH_PEND_LO), tid, (int)blockDim.x);  // (the pending set was fixed by the prologue)
-    if (tid >= 64 && tid < 72) {
-        const int ls = tid - 64;
-        uint32_t mx = 0;
-        for (int k = 1; k <= Hp; ++k) {
-            const int M_k = CK.l_soff[k] - CK.l_soff[k - 1], Hk = CK.l_hoff[k] - CK.l_hoff[k - 1];
-            int n0, n1, n2;
-            bk_item_counts<CHECKER>(M_k, Hk, CK.ll_len, n0, n1, n2);
-            const int Sg = 1 << ls;
-            const uint32_t ch = (uint32_t)(((n0 + Sg - 1) >> ls) + ((n1 + Sg - 1) >> ls) + ((n2 + Sg - 1) >> ls));
-            mx = ch > mx ? ch : mx;
+    if (CHECKER == PDMPC_CHECK_INTERX) {  // the reach lists of the soup as it stands (expected areas included)
+        bk_reach_boxes(A, V, X.lsm, tid);
+        if (tid == 0) {
+            BK_RSTALE(X.lsm)[0] = 0u;
+            bk_reach_scalars(CK, X.lsm, A.lds.reach_shared != 0u);
         }
-        chm[ls] = mx;
+        __syncthreads();
+        bk_reach_build<7>(CK, X.lsm, lane, wave, n_waves);
+        __syncthreads();
     }
+    bk_chunk_table<CHECKER>(CK, rcnt, chm, tid - 64);
     __syncthreads();
 
     int status = PDMPC_OK;
@@ -1181,6 +1345,19 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
             // exactly one poller (rounds 3-4 let all helpers compete for tiles on one ticket word per search: a tile cost 15 us of which
             // the checks were 5, and more helpers made every search of the launch slower, profiles/r05_helper_sweep.txt).
             BK_MARK3
+            if (CHECKER == PDMPC_CHECK_INTERX && BK_RSTALE(X.lsm)[0] != 0u) {  // (uniform) areas have arrived since the lists were built
+                BkCheck CL = CK;  // (what the builder reads, from the LDS words: no scalar register of the round loop is touched)
+                {
+                    const BkItemCtx I = bk_item_ctx<CHECKER>(CK);
+                    CL.l_soup = I.l_soup();
+                    CL.Hp = I.Hp();
+                }
+                bk_reach_build<1>(CL, X.lsm, lane, wave, n_waves);
+                __syncthreads();  // (every wavefront has read the stale word by now)
+                bk_chunk_table<CHECKER>(CL, rcnt, chm, tid);
+                if (tid == 0) BK_RSTALE(X.lsm)[0] = 0u;
+                __syncthreads();
+            }
             const BkTreeSrc tsrc{&S, ready};
             const unsigned long long pend_now = SW::tentative(A) ? sh_load64(sh, SH_PEND_LO) : 0ull;  // (their slots hold expected areas)
             bool share = A.n_helpers > 0 && Rn >= (uint32_t)A.bk_share_min && P.n_pred <= 64;
@@ -1529,9 +1706,10 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
             __syncthreads();
             if (sh[SH_STATE] == ST_ARRIVED) {  // (uniform)
                 const unsigned long long arr = sh_load64(sh, SH_ARR_LO);
-                bk_incorporate(P.out, P.pred, P.l_soup, P.l_soff, P.l_lit, Hp, arr, tid, bd, chg);
+                bk_incorporate(P.out, P.pred, P.l_soup, P.l_soff, P.l_lit, Hp, arr, tid, bd, chg, CHECKER == PDMPC_CHECK_INTERX ? (const lds_f64*)BK_RBOX(X.lsm) : (const lds_f64*)nullptr);
                 __syncthreads();
                 if (tid == 0) {
+                    BK_RSTALE(X.lsm)[0] = 1u;  // (the next round rebuilds its vehicle-obstacle lists)
                     const unsigned long long pend = sh_load64(sh, SH_PEND_LO) & ~arr, fd = sh_load64(sh, BK_FD_LO) | arr;
                     sh[SH_PEND_LO] = (uint32_t)pend;
                     sh[SH_PEND_HI] = (uint32_t)(pend >> 32);
@@ -2350,6 +2528,7 @@ __device__ __forceinline__ void bulk_helper_body(const KernelArgs& A) {
     CK.ll_base = 0;
     CK.ll_len = 0;
     CK.Hp = Hp;
+    const lds_u32* rcnt = BK_RCNT(lsm);
     if (SW::areas_in_lds(A)) stage16(lsm + A.lds.area, A.man_area, A.n_man * 3 * PDMPC_VMAX, tid);
     if (tid < SH_WORDS) hs[tid] = 0;
     __syncthreads();
@@ -2485,20 +2664,16 @@ __device__ __forceinline__ void bulk_helper_body(const KernelArgs& A) {
             P.n_pred = V->n_pred;
             if (SW::tentative(A)) bk_tentative_areas(A, P, V->n_pred >= 64 ? ~0ull : ((1ull << V->n_pred) - 1ull), tid, bd);  // (as the owner: expected areas until the real ones are in)
             cur_mask = 0;
-            __syncthreads();
-            if (tid < 8) {  // the chunk table of this soup (bulk_search)
-                const int ls = tid;
-                uint32_t mx = 0;
-                for (int k = 1; k <= Hp; ++k) {
-                    const int M_k = l_soff[k] - l_soff[k - 1], Hk = l_hoff[k] - l_hoff[k - 1];
-                    int n0, n1, n2;
-                    bk_item_counts<CHECKER>(M_k, Hk, CK.ll_len, n0, n1, n2);
-                    const int Sg = 1 << ls;
-                    const uint32_t ch = (uint32_t)(((n0 + Sg - 1) >> ls) + ((n1 + Sg - 1) >> ls) + ((n2 + Sg - 1) >> ls));
-                    mx = ch > mx ? ch : mx;
-                }
-                chm[ls] = mx;
+            if (CHECKER == PDMPC_CHECK_INTERX) {  // (this helper's own lists of its own copy of the soup)
+                bk_reach_boxes(A, V, lsm, tid);
+                if (tid == 0) bk_reach_scalars(CK, lsm, A.lds.reach_shared != 0u);
             }
+            __syncthreads();
+            if (CHECKER == PDMPC_CHECK_INTERX) {
+                bk_reach_build<7>(CK, lsm, lane, wave, bd >> 6);
+                __syncthreads();
+            }
+            bk_chunk_table<CHECKER>(CK, rcnt, chm, tid);  // the chunk table of this soup (bulk_search)
             __syncthreads();
             if (hticking) hk_mark = __builtin_amdgcn_s_memrealtime();
             continue;
@@ -2549,8 +2724,14 @@ __device__ __forceinline__ void bulk_helper_body(const KernelArgs& A) {
         const unsigned long long mask = ((unsigned long long)hs[HS_MASK_HI] << 32) | hs[HS_MASK_LO];
         last_seq = seq;
         if (mask != cur_mask) {  // (within a launch a search's set of incorporated predecessors only grows)
-            bk_incorporate(P.out, P.pred, P.l_soup, P.l_soff, P.l_lit, Hp, mask & ~cur_mask, tid, bd, nullptr);  // (loads that are coherent by themselves)
+            bk_incorporate(P.out, P.pred, P.l_soup, P.l_soff, P.l_lit, Hp, mask & ~cur_mask, tid, bd, nullptr, nullptr);  // (loads that are coherent by themselves)
             cur_mask = mask;
+            if (CHECKER == PDMPC_CHECK_INTERX) {  // (uniform) the lists of the steps' vehicle obstacles follow the soup
+                __syncthreads();
+                bk_reach_build<1>(CK, lsm, lane, wave, bd >> 6);
+                __syncthreads();
+                bk_chunk_table<CHECKER>(CK, rcnt, chm, tid);
+            }
         }
         HK_TICK(1)
         // ---- the range: its records into LDS, its check items, its verdicts

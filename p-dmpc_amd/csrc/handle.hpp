@@ -182,6 +182,7 @@ struct PackedStep {
     bool pack_failed = false;  // the last pack into this bank did not finish: nothing to launch or fetch
     bool sampled = false;      // packed with seeds (pdmpc_set_step_seeds): a sampled bank, its launches run the sampled optimizer
     int soup_cap = 0;
+    int ll_cap = 0;    // most lanelet-boundary columns of any vehicle (the graph search's reach lists hold one boundary list per step)
     int cand_cap = 0;  // most segments any single edge check can see (one step's soups + the boundary)
     std::vector<int64_t> lit_cols;  // per slot: literal soup + boundary columns (for the bytes formula)
     std::vector<int32_t> perm;      // empty: slot s holds the caller's vehicle s; else slot s holds vehicle perm[s] (pack_common put the batch into level order)

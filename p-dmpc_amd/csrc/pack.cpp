@@ -82,7 +82,7 @@ struct Packer {
     size_t veh_bytes = 0, pts_base = 0;
     BlobRegions host;
     size_t n_pred_out = 0, n_pts = 0;  // entries of pred / POINTS (two doubles each) written
-    int soup_cap = 0, cand_cap = 0;
+    int soup_cap = 0, cand_cap = 0, ll_cap = 0;
 
     BlobRegions regions(unsigned char* blob) const { return {(DevVehicle*)blob, (int32_t*)(blob + veh_bytes), (double*)(blob + pts_base)}; }
     int vehicle_of(int slot) const { return B.perm.empty() ? slot : B.perm[(size_t)slot]; }  // (the caller's vehicle)
@@ -258,6 +258,7 @@ struct Packer {
         // what the LDS must hold of this vehicle: its soups of all steps with the predecessors' columns (soup_cap), of one step (cand_cap)
         const int need = (d.lit_off[Hp] - d.lit_off[0]) + Hp * d.n_pred * PDMPC_VMAX + (d.hdv_off[Hp] - d.hdv_off[0]) + d.ll_len;
         soup_cap = std::max(soup_cap, need);
+        ll_cap = std::max(ll_cap, (int)d.ll_len);
         for (int k = 0; k < Hp; ++k) cand_cap = std::max(cand_cap, (d.lit_off[k + 1] - d.lit_off[k]) + d.n_pred * PDMPC_VMAX + (d.hdv_off[k + 1] - d.hdv_off[k]) + d.ll_len);
         return PDMPC_OK;
     }
@@ -269,6 +270,7 @@ struct Packer {
         put(qnan, qnan);
         host.pred[n_pred_out++] = 0;
         B.soup_cap = soup_cap + 2;
+        B.ll_cap = ll_cap;
         B.cand_cap = (cand_cap + 4 + 3) & ~3;
         const size_t pts_bytes = (n_pts * 16 + 15) & ~(size_t)15;
         const size_t total = pts_base + pts_bytes;

@@ -33,6 +33,8 @@ PROTOTYPES = {
     "pdmpc_destroy": (INT, [OBJ]),
     "pdmpc_get_config": (INT, [OBJ, CONFIG, P(I32)]),
     "pdmpc_upload_mpa": (INT, [OBJ, MPA]),
+    "pdmpc_mpa_reach_host": (INT, [MPA, DP, DP]),
+    "pdmpc_reach_lists_host": (INT, [I32, F64, F64, F64, F64, DP, DP, IP, IP, IP, IP]),
     "pdmpc_plan_batch": (INT, [OBJ, I32, VIN, VOUT]),
     "pdmpc_set_arena_limit": (INT, [OBJ, I32]),
     "pdmpc_grow_arena": (INT, [OBJ, I32]),
