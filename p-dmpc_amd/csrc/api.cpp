@@ -221,7 +221,7 @@ int compute_lds_sampled(const pdmpc_handle* h, int soup_cap, int cand_cap, Launc
         L.shape = off;
         off += (2 * PDMPC_VMAX + 1) * 16;
         L.path = off;
-        off += align16((PDMPC_HP_MAX + 2) * 4 + 2 * (PDMPC_HP_MAX + 1) * 4 + PDMPC_SH_WORDS * 4 + PDMPC_HP_MAX * 4);
+        off += PDMPC_LK_PATH_BYTES;
         L.soup = off;
         off = align16(off + (uint32_t)std::max(soup_cap, 1) * 16);
         L.cand = off;

@@ -42,7 +42,6 @@
 
 #include "../../include/pdmpc_reach.h"
 
-// shared words of the bulk kernel (aliases of words the frontier kernel uses for things this kernel does not have)
 #define BK_P2 3                   // ready entries a thread handles in the verdict pass (the ready list holds at most BK_P2 * blockDim entries)
 #define BK_PER PDMPC_BK_PER       // near entries per thread a selection pass holds in registers (near capacity = BK_PER * blockDim)
 #define BK_FAST_PER 4             // ... and per lane of the first wavefront when it selects alone (a small open set: at most 256 entries)
@@ -129,7 +128,6 @@ struct BkItemCtx {  // the same values for a check item, each read where it is u
     __device__ __forceinline__ const lds_d2* l_area() const { return interx ? (const lds_d2*)(bk_lds_base() + word(1)) : C.l_area; }
     __device__ __forceinline__ int Hp() const { return interx ? word(2) : C.Hp; }
     __device__ __forceinline__ int ll_base() const { return interx ? word(3) : C.ll_base; }
-    __device__ __forceinline__ int ll_len() const { return interx ? word(4) : C.ll_len; }
     __device__ __forceinline__ int ll_stride() const { return interx ? word(5) : C.ll_len; }
 };
 template <int CHECKER>
@@ -198,25 +196,7 @@ __device__ __forceinline__ void bk_reach_build(const BkCheck& C, LDS_AS unsigned
 // into the open set when a predecessor arrives.  The result is a function of the final areas alone (every node that comes before
 // the goal ends up evaluated against them); what changes is that the plan found ahead of the arrivals usually survives them.
 #define VS_TENT 6u
-#define BK_TENT_MIN FR_JOIN_MAX  // (64 bit) smallest key among the parked nodes
-#define BK_NTENT FR_SEL2_BIN     // parked nodes
-#define BK_ARRIVALS FR_SEL2_CUM  // arrival events handled by this search
-#define BK_DEPTH FR_RD_HEAD       // deepest collision-free node so far (its step k)
-#define BK_IDLE FR_RD_TAIL        // polls a waiting search has made (the watchdog's count)
-// the mid list's words (words 10-15 of the serial block: the pop-ordered kernel's candidate list, unused by this search)
-#define BK_MID_N 10    // entries of mid
-#define BK_MID_MIN 12  // (64 bit) exact minimum key of mid
-#define BK_L_MID 14    // (64 bit) open entries that leave near, and children beyond near's limit, go to mid up to this key and to far above it (-1: no mid list)
-// the fast arrival path (bk_wait_done; words 16-19 of the serial block: the pop-ordered kernel's mail boxes, unused by this search)
-#define BK_FD_LO 16    // (64 bit) predecessors whose areas are in the soup and have passed the path of the finished plan, but whose re-check of the
-#define BK_FD_HI 17    //          other collision-free nodes is still to come (they stay in SH_PEND until the arrival block has seen them)
-#define BK_WAITRES 18  // result of bk_wait_done: 0 nothing yet, 1 an arrival crosses the path, 2 the last predecessor has passed: published
-#define BK_TIEMODE 20   // the search has met equal keys where the pop order decides (or PDMPC_BK_FORCE_TIE): it ends on bk_replay
-#define BK_RP_NEED 21   // bk_replay: a node (1-based) the reference's heap pops that no round has evaluated (0: none)
-#define BK_RP_GOAL 22   // ... the goal it ended on (1-based arena index, 0: exhausted)
-#define BK_RP_NPOP 23   // ... nodes popped
-#define BK_RP_NREF 24   // ... nodes of the reference's tree
-#define BK_PUBLISHED 19 // the done flag is out (bk_wait_done): the areas of the record in HBM are final and may be read; only counts and ids may still be written
+// (the shared words of the parked nodes, the mid list, the fast arrival path and the replay: lds_layout.hpp)
 
 // copies the expected areas of the predecessors in `who` into their soup slots
 __device__ __forceinline__ void bk_tentative_areas(const KernelArgs& A, const SpecCtx& P, unsigned long long who, int tid, int nthreads) {
@@ -574,8 +554,8 @@ __device__ __forceinline__ void bk_write_record(const KernelArgs& A, Ctx& X, uin
         }
         return;
     }
-    lds_d2* pshape = (lds_d2*)(X.lsm + PDMPC_LK_PSHAPE);
-    lds_u32* pcols = (lds_u32*)(pshape + Hp * PDMPC_VMAX);
+    lds_d2* pshape = BK_PSHAPE(X.lsm);
+    lds_u32* pcols = BK_PCOLS(pshape, Hp);
     if (again) {  // as the prologue left it: zeros, y_predicted NaN (ControlResultsInfo.m:40)
         double* od = (double*)O;
         const int nd = (int)(offsetof(pdmpc_vehicle_out, path_nodes) / 8) + (Hp + 1) * 8;  // (rows beyond the path are never written here: the diagnostics of the tail stay)
@@ -748,7 +728,7 @@ __device__ __forceinline__ void bk_incorporate(const pdmpc_vehicle_out* out, con
     bk_incorporate_body(out, pred, l_soup, l_soff, l_lit, Hp, arr, tid, nthreads, chg, rbox);
 }
 
-// fr_check_wave with a memory: what to do with an open node a round has selected (1 process it, 3 it comes after the goal candidate,
+// What to do with an open node a round has selected, with a memory (1 process it, 3 it comes after the goal candidate,
 // 4 one of its ancestors lost its edge to late areas), one node per lane, a = 0: none.
 // The answer follows from the branch between the node and the candidate's path — where it joins the path (depth dJ), the largest key on
 // it (M), whether a node on it is invalid — and a child's branch is its parent's plus itself.  Every processed node leaves these three
@@ -772,7 +752,8 @@ __device__ int bk_classify_wave(const unsigned long long* glink, ulonglong2* wal
     double M = -1.0;
     int dJ = k;
     bool dead = false;
-    // ---- no current stamp at the parent: the walk (the whole wave together, see fr_check_wave)
+    // ---- no current stamp at the parent: the walk (a wave-uniform loop over per-lane states: a per-lane loop in a divergent branch
+    // followed by a ballot is the shape hipcc 7.2 mis-threads, see sh_add_uniform)
     int st = (a == 0u || onp || hit) ? 1 : 0;  // 0: still walking
     uint32_t x = a0;
     while (__ballot(st == 0)) {
@@ -830,8 +811,8 @@ __device__ int bk_classify_wave(const unsigned long long* glink, ulonglong2* wal
 __device__ __forceinline__ void bk_wait_done(const uint32_t* done_flag, const int32_t* pred, const pdmpc_vehicle_out* out, uint32_t epoch, uint32_t slot, lds_d2* l_soup, const lds_i32* l_soff,
                                              const lds_i32* l_lit, lds_d2* pshape, volatile lds_u32* sh, int Hp, int n_pred, bool have_path, lds_vu64* tk_pub, unsigned long long first, uint32_t max_spins,
                                              bool sat, int lane) {
-    const lds_u32* pcols = (const lds_u32*)(pshape + Hp * PDMPC_VMAX);
-    lds_u64s* chg = (lds_u64s*)(pcols + PDMPC_HP_MAX);
+    const lds_u32* pcols = BK_PCOLS(pshape, Hp);
+    lds_u64s* chg = BK_PCHG(pshape, Hp);
     LDS_AS unsigned char* reach = (LDS_AS unsigned char*)pshape + (PDMPC_LK_REACH - PDMPC_LK_PSHAPE);  // (the squares and the stale word of the reach lists)
     unsigned long long pend = sh_load64(sh, SH_PEND_LO), fd = sh_load64(sh, BK_FD_LO);
     const unsigned long long fd_in = fd;
@@ -910,7 +891,7 @@ __device__ __forceinline__ void bk_wait_done(const uint32_t* done_flag, const in
 // Collision-free nodes at the horizon are offered as goal candidates again (after an invalidation that took the best one, or
 // when a round had more candidates than its list holds): every lane with a candidate walks that candidate's path by itself — all
 // of them Hp edges long, so the lanes of a wave finish together — instead of the wave walking them one after the other
-// (fr_offer_goal; a walk is Hp dependent reads of the tree: C2's last vehicles spent 30 us per arrival there).  Whole wave calls.
+// (a walk is Hp dependent reads of the tree: C2's last vehicles spent 30 us per arrival there).  Whole wave calls.
 __device__ __forceinline__ void bk_offer_goals_lanes(const Frontier& F, const Search& S, const VState& VS, bool cand, uint32_t id, int lane) {
     double m = 0.0;
     bool alive = cand;
@@ -1055,19 +1036,20 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
     lds_u32* near_id = (lds_u32*)(X.lsm + PDMPC_LK_NEAR_ID);
     lds_u32* ready = (lds_u32*)(X.lsm + PDMPC_LK_READY);
     volatile lds_u32* r_flag = (volatile lds_u32*)(ready + RC);
-    lds_u32* hist = (lds_u32*)(X.lsm + PDMPC_LK_HIST);      // [3072]: refill histogram [2048] | goal list [1024], expansion groups [1024], their children's offsets [1024]
-    lds_u32* vlist = hist + 1024;
-    lds_u32* voffs = hist + 2048;
-    lds_u32* gp_path = (lds_u32*)(X.lsm + PDMPC_LK_MISC);    // [32] path of the best goal candidate
-    lds_f64* gp_mp = (lds_f64*)(gp_path + 32);                // [HP_MAX + 1] largest key of that path below depth d
-    lds_vu64* wsum64 = (lds_vu64*)(gp_mp + 32);                // [32] scan partials
-    volatile lds_u32* wsum = (volatile lds_u32*)(wsum64 + 32); // [32] fr_partition's per-wave counts
-    lds_u32* chm = (lds_u32*)(wsum + 32);                      // [8] chunks per node for S = 1, 2, 4, 8, 16, ...
-    lds_u32* bins = gp_path + 256;                             // [BK_NB] the selection's histogram (second KB of the region)
+    LDS_AS BkHist* const LH = bk_hist(X.lsm);  // (lds_layout.hpp: what the tables of these two regions hold)
+    lds_u32* hist = LH->goal_list;  // the refill's histogram [FR_NBINS] over goal_list and vlist
+    lds_u32* vlist = LH->vlist;
+    lds_u32* voffs = LH->voffs;
+    LDS_AS BkMisc* const LM = bk_misc(X.lsm);
+    lds_u32* gp_path = LM->gp_path;
+    lds_f64* gp_mp = LM->gp_mp;
+    lds_vu64* wsum64 = LM->wsum64;
+    volatile lds_u32* wsum = LM->wsum;
+    lds_u32* chm = LM->chm;
+    lds_u32* bins = LM->bins;
 
     Frontier F;
     F.sh = sh;
-    F.ready = ready;
     F.hist = hist;
     F.goal_list = hist;
     F.near_key = A.arena.pb_key + voff;  // (HBM arrays: phase B's per-node state; near itself lives in LDS)
@@ -1076,7 +1058,6 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
     F.far_id = A.arena.far_id + voff;
     F.gkey = S.gkey;
     F.glink = A.arena.link + voff;
-    F.n_waves = n_waves;
 
     ExpandEnv EE;
     EE.l_mask = X.l_mask;
@@ -1085,8 +1066,6 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
     EE.l_rx = X.l_rx;
     EE.l_ry = X.l_ry;
     EE.l_dcum = X.l_dcum;
-    EE.l_term = nullptr;
-    EE.l_chxy = nullptr;
     EE.Hp = Hp;
     EE.n = X.n;
     EE.nw = X.nw;
@@ -1123,14 +1102,14 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
         ((ulonglong2*)A.arena.walk + voff)[0].y = 0ull;
         (A.arena.child0 + voff)[0] = 0u;
         vs_store(VS, 0, VS_UNKNOWN);
-        for (int w = 26; w < SH_WORDS; ++w) sh[w] = 0;
+        for (int w = SH_ROOT_CLEAR; w < PDMPC_SH_WORDS; ++w) sh[w] = 0;
         sh[FR_NNODES] = 1;
         sh_st_d(sh, FR_NEAR_MIN, inf);
         sh_st_d(sh, FR_FAR_MIN, inf);
         sh_st_d(sh, FR_L_FAR, inf);
         sh_st_d(sh, BK_TENT_MIN, inf);
         sh[BK_MID_N] = 0;
-        sh[BK_MID_N + 1] = 0;
+        sh[BK_MID_PAD] = 0;
         sh_st_d(sh, BK_MID_MIN, inf);
         sh_st_d(sh, BK_L_MID, -1.0);
         sh[SH_NNODES] = 1;
@@ -1173,25 +1152,25 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
     uint32_t t_checks = 0, t_pairs = 0;  // this thread's share of the work counters
     // where the time goes (100 MHz ticks, PDMPC_DEBUG_TAIL=1): accumulated by thread 0 in LDS words, so that the bookkeeping costs
     // the round loop no registers
-    lds_vu64* tk = (lds_vu64*)(gp_path + 200);  // [12]: mark, start, work, arrival, select (without the refills), wait, p1, p2, p3, phase B, refill, time of the early publication
+    lds_vu64* tk = LM->tk;
     enum { TK_MARK, TK_START, tk_work, tk_arrival, tk_select, tk_wait, tk_p1, tk_p2, tk_p3, tk_pb, tk_refill, tk_pub };
     const bool ticking = SW::debug_tail(A) != 0 && tid == 0;
     if (ticking) {
         for (int i = 2; i < 12; ++i) tk[i] = 0ull;
         tk[TK_MARK] = tk[TK_START] = __builtin_amdgcn_s_memrealtime();
     }
-    lds_u64s* chg = (lds_u64s*)((lds_u32*)((lds_d2*)(X.lsm + PDMPC_LK_PSHAPE) + Hp * PDMPC_VMAX) + PDMPC_HP_MAX);  // [HP_MAX] areas that differ from the expected ones (bk_incorporate_body)
+    lds_u64s* chg = BK_PCHG(BK_PSHAPE(X.lsm), Hp);
     // The collision-free nodes of step k (1..Hp) in the order the rounds found them, and the parked nodes: Hp + 1 lists of max_nodes
     // entries in the arena (a node is collision-free at most once: that verdict can only be withdrawn; it is parked at most once
     // between two verifications).  What a verification visits; their lengths are the LDS words vcnt[k - 1] and BK_NTENT.
-    lds_u32* vcnt = (lds_u32*)(chg + PDMPC_HP_MAX);  // [HP_MAX]
+    lds_u32* vcnt = BK_PVCNT(BK_PSHAPE(X.lsm), Hp);
 #define BK_VLIST(k) (A.arena.vlist + ((size_t)slot * (size_t)(Hp + 1) + (size_t)((k) - 1)) * A.max_nodes)
 #define BK_PLIST BK_VLIST(Hp + 1)
     if (tid < PDMPC_HP_MAX) {  // (read behind the barriers of the first round)
         chg[tid] = 0ull;
         vcnt[tid] = 0u;
     }
-    lds_vu64* tk2 = (lds_vu64*)(gp_path + 242);  // [7] (diagnostics) the arrival handling in detail: poll + copy, re-check items, parked nodes' return, bookkeeping + candidates, record + flag of a finished search, finding the nodes to re-check; mark
+    lds_vu64* tk2 = LM->tk2;
     if (ticking)
         for (int i = 0; i < 7; ++i) tk2[i] = 0ull;
 #define BK_TICK2(i)                                                        \
@@ -1997,7 +1976,7 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
             // them before the first one does — a wavefront can lag arbitrarily far behind the last barrier)
             __syncthreads();
             if (wave == 0 && sh[BK_PUBLISHED] == 0u)
-                bk_wait_done(A.done_flag, P.pred, P.out, A.epoch, (uint32_t)slot, P.l_soup, P.l_soff, P.l_lit, (lds_d2*)(X.lsm + PDMPC_LK_PSHAPE), sh, Hp, P.n_pred, best != 0u,
+                bk_wait_done(A.done_flag, P.pred, P.out, A.epoch, (uint32_t)slot, P.l_soup, P.l_soff, P.l_lit, BK_PSHAPE(X.lsm), sh, Hp, P.n_pred, best != 0u,
                              ticking ? (lds_vu64*)(tk + tk_pub) : (lds_vu64*)nullptr, sh_load64(sh, BK_FD_LO), 0u, CHECKER == PDMPC_CHECK_SAT, lane);
             __syncthreads();
             BK_TICK2(4)
@@ -2045,7 +2024,7 @@ __device__ __forceinline__ bool bulk_search(const KernelArgs& A, Ctx& X, lds_u32
             if (SW::fast_arrival(A) && !dep_timeout) {
                 __syncthreads();  // (as above: everybody has read the pending set this wait is about to rewrite)
                 if (wave == 0)
-                    bk_wait_done(A.done_flag, P.pred, P.out, A.epoch, (uint32_t)slot, P.l_soup, P.l_soff, P.l_lit, (lds_d2*)(X.lsm + PDMPC_LK_PSHAPE), sh, Hp, P.n_pred, best != 0u,
+                    bk_wait_done(A.done_flag, P.pred, P.out, A.epoch, (uint32_t)slot, P.l_soup, P.l_soff, P.l_lit, BK_PSHAPE(X.lsm), sh, Hp, P.n_pred, best != 0u,
                                  ticking ? (lds_vu64*)(tk + tk_pub) : (lds_vu64*)nullptr, 0ull, 4096u, CHECKER == PDMPC_CHECK_SAT, lane);
                 __syncthreads();
                 if (ticking && sh[BK_WAITRES] == 1u) {  // (diagnostics: an arrival crossed the finished plan's path)
@@ -2508,15 +2487,15 @@ __device__ __forceinline__ void bulk_helper_body(const KernelArgs& A) {
     const int Hp = A.Hp, n_s = A.n_searches;
     const uint32_t CAP = (uint32_t)A.bk_tile;  // records of a range (what fits the staging area)
     // the owners' carve (search_prologue): only the regions a check item reads are filled
-    lds_u32* l_path = (lds_u32*)(lsm + PDMPC_LK_PATH);
-    lds_i32* l_soff = (lds_i32*)(l_path + PDMPC_HP_MAX + 2);
-    lds_i32* l_hoff = l_soff + PDMPC_HP_MAX + 1;
-    volatile lds_u32* hs = (volatile lds_u32*)(l_hoff + PDMPC_HP_MAX + 1);
-    lds_i32* l_lit = (lds_i32*)(hs + SH_WORDS);
+    LDS_AS LdsPathRegion* l_pr = (LDS_AS LdsPathRegion*)(lsm + PDMPC_LK_PATH);
+    lds_i32* l_soff = l_pr->soff;
+    lds_i32* l_hoff = l_pr->hoff;
+    volatile lds_u32* hs = l_pr->shared;  // (HS_*: lds_layout.hpp)
+    lds_i32* l_lit = l_pr->lit;
     lds_d2* l_soup = (lds_d2*)(lsm + A.lds.soup);
     lds_d2* t_rec = (lds_d2*)(lsm + PDMPC_LK_NEAR_KEY);              // [bk_tile][3] the range's posted records
     volatile lds_u32* t_flag = (volatile lds_u32*)(lsm + PDMPC_LK_READY);  // [bk_tile] collision flags
-    lds_u32* chm = (lds_u32*)(lsm + PDMPC_LK_MISC) + 192;
+    lds_u32* chm = bk_misc(lsm)->chm;
     BkCheck CK;
     CK.l_area = (const lds_d2*)(lsm + A.lds.area);
     CK.g_area = (const d2*)A.man_area;
@@ -2530,7 +2509,7 @@ __device__ __forceinline__ void bulk_helper_body(const KernelArgs& A) {
     CK.Hp = Hp;
     const lds_u32* rcnt = BK_RCNT(lsm);
     if (SW::areas_in_lds(A)) stage16(lsm + A.lds.area, A.man_area, A.n_man * 3 * PDMPC_VMAX, tid);
-    if (tid < SH_WORDS) hs[tid] = 0;
+    if (tid < PDMPC_SH_WORDS) hs[tid] = 0;
     __syncthreads();
     int my_slot = -1, my_seat = -1;  // (uniform)
     uint32_t last_seq = 0;
@@ -2792,7 +2771,7 @@ __device__ __forceinline__ void bulk_body(const KernelArgs& A) {
     search_prologue<SW>(A, X, (LDS_AS unsigned char*)smem);
     X.rt_kernel_start = rt0;
     const int wave = X.wave;
-    lds_u32* ref_ids = (lds_u32*)(X.lsm + PDMPC_LK_MISC) + 224;  // behind the chunk table (nothing else uses those words)
+    lds_u32* ref_ids = bk_misc(X.lsm)->ref_ids;
     const bool tie = bulk_search<NW, CHECKER, SW>(A, X, ref_ids);
     (void)tie;  // (equal keys are resolved inside the search: bk_replay)
     __syncthreads();

@@ -11,7 +11,6 @@
 #include "../../include/pdmpc_math.h"
 #include "pdmpc_device.h"
 
-#define PROF_MEMBERS
 namespace {
 #include "wave_primitives.hpp"
 #include "search_state.hpp"

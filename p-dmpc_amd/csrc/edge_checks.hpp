@@ -1,4 +1,4 @@
-// Edge validity (GraphSearch.m:111-196): InterX and separating-axis checks of one swept area against the obstacle soups (device code, included by search_kernel.hip inside its anonymous namespace).
+// Edge validity (GraphSearch.m:111-196): InterX and separating-axis checks of one swept area against the obstacle soups (device code, included by the kernels' translation units inside their anonymous namespaces).
 #pragma once
 
 // ---------------------------------------------------------------------------------------------------
@@ -40,9 +40,6 @@ __device__ __forceinline__ bool interx_segment_n(const d2 (&pt)[NP], int ne, d2 
     return hit;
 }
 
-// interx_segment: one obstacle segment against the whole shape pt[0 .. V-1].
-__device__ __forceinline__ bool interx_segment(const d2 (&pt)[PDMPC_VMAX], int V, d2 q0, d2 q1) { return interx_segment_n<PDMPC_VMAX>(pt, V - 1, q0, q1); }
-
 // sh2 holds shape A in [0, VMAX) and shape B in [VMAX, 2*VMAX).
 __device__ bool interx_check(const lds_d2* sh2, int V, const lds_d2* soup, int so, int M_k, int ho, int Hk, int lo, int Ml, int lane) {
     if (V < 2) return false;
@@ -72,7 +69,7 @@ __device__ bool interx_check(const lds_d2* sh2, int V, const lds_d2* soup, int s
             d2 pt[PDMPC_VMAX];
 #pragma unroll
             for (int i = 0; i < PDMPC_VMAX; ++i) pt[i] = sh[i];
-            hit = interx_segment(pt, V, q0, q1);
+            hit = interx_segment_n<PDMPC_VMAX>(pt, V - 1, q0, q1);
         }
         if (wave_any(hit)) return true;
     }
@@ -229,69 +226,6 @@ struct CheckCtx {
     lds_u32* cand;  // this wave's candidate list
     LDS_AS unsigned long long* tally;  // this wave's work counters: edge checks, (shape segment, obstacle segment) pairs
 };
-
-// eval_edge_exact (GraphSearch.m:111-196) for node `id` (1-based): true = collision-free.  A pure function of the
-// tree and the obstacle soups, which is what allows helper waves to evaluate it ahead of the pop.
-// (cn = the node's record, pn = its parent's; the same record in every lane)
-template <int CHECKER>
-__device__ bool edge_valid_recs(const CheckCtx& C, const NodeRec& cn, const NodeRec& pn, int lane) {
-    const uint32_t par = uni_u(cn.parent);
-    if (!par) return true;  // root: no edge (GraphSearch.m:137-139)
-    const uint32_t cpk = uni_u(cn.packed);
-    const int cK = NODE_K(cpk);
-    const double pX = pn.x, pY = pn.y;
-    const double c = pn.cs, s = pn.sn;  // cos/sin(pYaw), cached when the parent was expanded
-    const int m = NODE_MAN(cpk);
-    const int ncols = NODE_COLS(cpk);
-    if (lane < ncols) {
-        const size_t ai = (size_t)m * 3 * PDMPC_VMAX + lane;
-        const size_t bi = ai + (size_t)((cK == C.Hp) ? 2 : 1) * PDMPC_VMAX;  // large offset at k == Hp, else without offset
-        d2 a, b;
-        if (C.areas_in_lds) {
-            a = C.l_area[ai];
-            b = C.l_area[bi];
-        } else {
-            a = C.g_area[ai];
-            b = C.g_area[bi];
-        }
-        d2 sa, sb;
-        sa.x = c * a.x - s * a.y + pX;  // GraphSearch.m:158
-        sa.y = s * a.x + c * a.y + pY;  // :159
-        sb.x = c * b.x - s * b.y + pX;  // :162 / :168
-        sb.y = s * b.x + c * b.y + pY;  // :163 / :169
-        C.sh[lane] = sa;
-        C.sh[PDMPC_VMAX + lane] = sb;
-    }
-    wave_sync();
-    const int so = uni_i(C.l_soff[cK - 1]);
-    const int M_k = uni_i(C.l_soff[cK]) - so;
-    bool hit;
-    if (CHECKER == PDMPC_CHECK_INTERX) {
-        const int ho = uni_i(C.l_hoff[cK - 1]);
-        const int Hk = uni_i(C.l_hoff[cK]) - ho;
-        if (lane == 0) {  // the pairs the reference's InterX forms for this edge (InterX.m:63-76): (V - 1) x (M - 1) per soup
-            C.tally[0] += 1;
-            C.tally[1] += (unsigned long long)(ncols - 1) * (unsigned long long)((M_k > 1 ? M_k - 1 : 0) + (Hk > 1 ? Hk - 1 : 0) + (C.ll_len > 1 ? C.ll_len - 1 : 0));
-        }
-        hit = interx_check(C.sh, ncols, C.l_soup, so, M_k, ho, Hk, C.ll_base, C.ll_len, lane);
-    } else {
-        // are_constraints_satisfied_sat.m:15-53
-        if (lane == 0) C.tally[0] += 1;
-        hit = sat_soup_wave(C.sh, ncols, C.l_soup + so, M_k, lane);
-        if (!hit) hit = sat_boundary_wave(C.sh + PDMPC_VMAX, ncols, C.l_soup + C.ll_base, C.ll_len, lane);
-    }
-    wave_sync();
-    return !hit;
-}
-
-template <int CHECKER>
-__device__ bool edge_valid(const Search& S, const CheckCtx& C, uint32_t id, int lane) {
-    const NodeRec cn = node_load(S, id - 1);
-    const uint32_t par = uni_u(cn.parent);
-    if (!par) return true;
-    const NodeRec pn = node_load(S, par - 1);
-    return edge_valid_recs<CHECKER>(C, cn, pn, lane);
-}
 
 // ---------------------------------------------------------------------------------------------------
 // The separating-axis checker in the form the bulk kernel uses (bulk_kernel.hip, bk_check_items): ONE LANE tests one pair — the

@@ -1,83 +1,17 @@
-// frontier_common.hpp — device code of the round-based search (bulk_search.hpp) that is not the round loop itself: shared-word
-// indices, LDS counter helpers, the list partition and histogram, the walks that decide whether an open node comes before the goal
-// candidate, goal-candidate resolution, and phase B (the reference's counts and ids).  Included after search_common.hpp.
-// (The name is history: rounds 2-3 had a "frontier kernel" — one node per wavefront — next to this code; docs/HISTORY.md.)
+// frontier_common.hpp — device code of the round-based search (bulk_search.hpp) that is not the round loop itself: LDS counter helpers,
+// the list partition and the refill's histogram, the walks along a goal candidate's path, goal-candidate resolution, and phase B
+// (the reference's counts and ids).  Included after search_common.hpp; the shared words it works on are declared in lds_layout.hpp.
 #pragma once
-#include <type_traits>
 
-// frontier words in the shared block (indices >= 32; the serial search uses the words below)
-#define FR_NNODES 32    // tree size (atomic reservation of node indices)
-#define FR_RD_HEAD 33   // ready list: next entry to claim
-#define FR_RD_TAIL 34   // ready list: entries reserved
-#define FR_VLIST_N 35   // (free since the verification reads lists kept by the rounds, bulk_search.hpp BK_VLIST; still in the debug stage record)
-#define FR_NEAR_N 36
-#define FR_FAR_N 37
-#define FR_FLAGS 38     // FRF_*
-#define FR_BEST_ID 40   // best goal candidate so far (1-based node, 0 = none)
-#define FR_SEL_BIN 41   // result of fr_select: bin ...
-#define FR_SEL_CUM 42   // ... and the number of entries up to and including it
-#define FR_SEL2_BIN 43  // second selection of the same histogram (spill boundary) ...
-#define FR_SEL2_CUM 44  // ... and its count
-#define FR_ROUNDS 45
-#define FR_PROCESSED 60
-#define FR_BEST_B1 46   // (64 bit) largest key on the best candidate's path
-#define FR_NEAR_MIN 48  // (64 bit) exact minimum key of near
-#define FR_NEAR_MAX 50  // (64 bit) upper bound of near's keys
-#define FR_FAR_MIN 52   // (64 bit) exact minimum key of far
-#define FR_FAR_MAX 54   // (64 bit) upper bound of far's keys
-#define FR_L_FAR 58     // (64 bit) children with key > this go to far
-#define FR_PATH_FOR 61  // the goal candidate whose path is in the relevance tables (0: none)
-#define FR_EVER_INVAL 63 // set once a late arrival has invalidated a node of this search
-#define FR_SLOWEST 30   // (64 bit, words 30-31 of the serial block: unused by both searches) debugging: slowest node
-#define FR_GOAL_N 39     // goal candidates of the running round (entries of goal_list)
-#define FR_ROUND_B1 28   // (64 bit, words 28-29 of the serial block: unused by both searches) smallest path maximum among them
 #define FR_GOAL_CAP 2048
-#define FR_JOIN_MAX 26    // (64 bit, words 26-27 of the serial block: unused by both searches) largest key among the round's entries
-#define FR_DEAD 57      // open entries dropped because an ancestor was invalidated
-#define FR_HELP_CLOSED 56 // shared round: entries of the shared part the helpers claimed before the owner closed it
-#define FR_DROPPED 62   // open entries dropped because they come after the best candidate (restored if that one is invalidated)
 #define FRF_OVERFLOW 1u
 #define FRF_TIE 2u
 #define FRF_INVALIDATED 4u
 #define FRF_BUG 8u
-#define FRF_GOALS_LOST 16u  // bulk kernel: a round had more goal candidates than its list holds: every collision-free node at the horizon is offered again
-#define FR_SCRATCH 64   // 64 scratch words behind the shared block (targets of the lanes that only take part pro forma, see sh_add_uniform)
+#define FRF_GOALS_LOST 16u  // a round had more goal candidates than its list holds: every collision-free node at the horizon is offered again
 #define FR_NBINS 2048
-#define FR_READY_CAP 1536
-
-// words of a helper workgroup's shared block
-#define HS_CMD 0     // 0 nothing found, 1 work, 2 every search has finished
-#define HS_SLOT 1
-#define HS_FIRST 2
-#define HS_COUNT 3
-#define HS_MASK_LO 4
-#define HS_MASK_HI 5
-#define HS_TICKET 6
-#define HS_EXPAND 7  // the claimed round wants its collision-free entries expanded
-#define HS_RUN_BASE 8   // first node index of the block the run's children get
-#define HS_RUN_TOTAL 9  // children of the run
 
 namespace {
-
-typedef LDS_AS unsigned long long lds_u64s;
-
-// live counters for debugging (host-mapped memory, PDMPC_DEBUG_PROGRESS=1): stage = where the workgroup is
-#define FR_PROGRESS(stage)                                                                    \
-    if (A.progress && threadIdx.x == 0) {                                                     \
-        volatile uint32_t* pg__ = A.progress + (size_t)X.slot * 64;                         \
-        pg__[0] = sh[FR_ROUNDS];                                                              \
-        pg__[1] = sh[FR_PROCESSED];                                                           \
-        pg__[2] = sh[FR_NNODES];                                                              \
-        pg__[3] = sh[FR_NEAR_N];                                                              \
-        pg__[4] = sh[FR_FAR_N];                                                               \
-        pg__[5] = sh[FR_FLAGS];                                                               \
-        pg__[6] = sh[FR_BEST_ID];                                                             \
-        pg__[7] = (stage);                                                                    \
-        pg__[8] = sh[FR_VLIST_N];                                                             \
-        pg__[9] = sh[FR_RD_HEAD];                                                             \
-        pg__[10] = sh[FR_RD_TAIL];                                                            \
-        pg__[11] += 1u;                                                                       \
-    }
 
 __device__ __forceinline__ double sh_ld_d(volatile lds_u32* sh, int w) { return __longlong_as_double((long long)*(volatile lds_u64s*)(sh + w)); }
 __device__ __forceinline__ void sh_st_d(volatile lds_u32* sh, int w, double v) { *(volatile lds_u64s*)(sh + w) = (unsigned long long)__double_as_longlong(v); }
@@ -126,7 +60,6 @@ __device__ __forceinline__ uint32_t fr_bin(double key, double lo, double scale) 
 
 struct Frontier {
     volatile lds_u32* sh;
-    lds_u32* ready;  // [FR_READY_CAP] 1-based nodes of the running round (0 = not written yet)
     lds_u32* hist;   // [FR_NBINS]
     lds_u32* goal_list;  // [FR_GOAL_CAP] goal candidates of the running round (lives in the histogram's first half: free during a round)
     unsigned long long* glink;  // [max_nodes] parent | packed << 32
@@ -135,7 +68,6 @@ struct Frontier {
     double* far_key;
     uint32_t* far_id;
     double* gkey;  // key of node i at gkey[i]
-    int n_waves;
 };
 
 // Smallest bin whose cumulative count reaches `target` (the last non-empty bin if the total is smaller), for two targets
@@ -256,40 +188,6 @@ __device__ void fr_histogram(const Frontier& F, const double* key, uint32_t n, d
     }
 }
 
-// What to do with the open nodes a round has selected, one node per lane (a: 1-based, 0 = this lane has none): 1 process it,
-// 3 drop it because the reference pops the goal candidate G first (gp_path[d] = node of G's path at depth d, gp_mp[d] =
-// largest key of that path below depth d; a leaves the path at some depth d and comes first iff the largest key on its own
-// branch is smaller than gp_mp[d]), 4 drop it because one of its ancestors collides with areas that arrived after it was
-// created (the reference never creates a).  Sets FRF_TIE on an equality that decides.
-// The whole wave walks together (a wave-uniform loop over per-lane states): a per-lane loop in a divergent branch followed
-// by a ballot is exactly the shape hipcc 7.2 mis-threads (see sh_add_uniform).
-__device__ int fr_check_wave(const unsigned long long* glink, const VState& VS, const double* gkey, const lds_u32* gp_path, const lds_f64* gp_mp, bool have_goal, bool check_alive,
-                             uint32_t a, volatile lds_u32* sh) {
-    int res = a ? 0 : 1;  // 0: still walking
-    uint32_t x = a ? a : 1u;
-    double mx = -1.0;
-    while (__ballot(res == 0)) {
-        const uint32_t i = x - 1u;
-        const uint64_t u = glink[i];
-        const int d = NODE_K((uint32_t)(u >> 32));
-        const bool on_path = have_goal && gp_path[d] == x;  // (the candidate's own ancestors are collision-free: it was validated after the last arrival)
-        const double m = gp_mp[d];
-        const bool dead = !on_path && x != a && check_alive && vs_load(VS, i) != VS_VALID;
-        const double k = gkey[i];
-        const uint32_t par = (uint32_t)(u & 0xffffffffull);
-        int now = 0;
-        now = on_path ? ((x == a || mx < m) ? 1 : 3) : now;
-        now = dead ? 4 : now;
-        now = (!on_path && !dead && par == 0u) ? 1 : now;  // reached the root: no candidate, every ancestor collision-free
-        if (res == 0 && on_path && x != a && mx == m) atomicOr((uint32_t*)&sh[FR_FLAGS], FRF_TIE);
-        const bool walking = res == 0;
-        res = walking ? now : res;
-        mx = (walking && k > mx) ? k : mx;
-        x = (walking && now == 0) ? par : x;
-    }
-    return res;
-}
-
 // X (1-based, at the horizon, edge known to be collision-free): largest key on its path, and whether every ancestor is
 // still collision-free (a predecessor's late areas may have invalidated one).  Uniform over the wave.
 __device__ bool fr_goal_path(const Search& S, const VState& VS, const double* gkey, uint32_t x, double& b1) {
@@ -320,18 +218,6 @@ __device__ int fr_before(const Search& S, const double* gkey, uint32_t x, uint32
         if (!x || !y) break;
     }
     return mx < my ? -1 : (my < mx ? 1 : 0);
-}
-
-// A valid node at the horizon has been found.  If its ancestors are all collision-free it becomes a goal candidate: the
-// largest key of its path goes into its record (the cos / sin slot, which a node at the horizon never needs) and its id into
-// the round's candidate list; the best candidate is chosen at the round boundary (fr_resolve_goals) — no lock, nothing a
-// wavefront could wait for while it processes a node.  Whole wave calls, uniform.
-__device__ void fr_offer_goal(const Frontier& F, const Search& S, const VState& VS, uint32_t x, int lane) {
-    double b1;
-    const bool alive = fr_goal_path(S, VS, F.gkey, x, b1);
-    if (lane == 0 && alive) node_store_cs(S, x - 1u, b1, 0.0);
-    const uint32_t pos = sh_add_uniform(F.sh, FR_GOAL_N, alive ? 1u : 0u, lane);
-    if (lane == 0 && alive && pos < (uint32_t)FR_GOAL_CAP) F.goal_list[pos] = x;
 }
 
 // Round boundary: the best of the round's goal candidates against the best one so far.  The reference pops the candidate
@@ -417,88 +303,6 @@ __device__ void fr_resolve_goals(const Frontier& F, const Search& S, int tid, in
         }
     }
     __syncthreads();
-}
-
-// Children of one expansion join the open set: near or far by key.  (They never join the running round: the reference pops
-// the smallest open key next, and a round that also swallowed everything its own nodes generate would walk whole subtrees
-// the reference leaves as soon as it reaches the horizon.)  Whole wave calls.
-// BULK: most lanes carry a child (the pass over the children helper workgroups created): the lists' key ranges are folded per
-// wave, not per lane.
-template <bool BULK = false>
-__device__ __forceinline__ void fr_push_children(const Frontier& F, bool active, uint32_t i0, double f, int lane) {
-    const double l_far = sh_ld_d(F.sh, FR_L_FAR);
-    const int cls = active ? (f > l_far ? 2 : 1) : -1;
-    const unsigned long long b1 = __ballot(cls == 1);
-    if (b1) {
-        const uint32_t base = sh_add_uniform(F.sh, FR_NEAR_N, (uint32_t)__builtin_popcountll(b1), lane);
-        if (cls == 1) {
-            const uint32_t pos = base + lane_rank(b1, lane);
-            F.near_key[pos] = f;
-            F.near_id[pos] = i0 + 1u;
-            if (!BULK) {
-                sh_min_d(F.sh, FR_NEAR_MIN, f);
-                sh_max_d(F.sh, FR_NEAR_MAX, f);
-            }
-        }
-        if (BULK) sh_minmax_wave(F.sh, FR_NEAR_MIN, FR_NEAR_MAX, cls == 1 ? f : __longlong_as_double(0x7FF0000000000000LL), cls == 1 ? f : 0.0, lane);
-    }
-    const unsigned long long b2 = __ballot(cls == 2);
-    if (b2) {
-        const uint32_t base = sh_add_uniform(F.sh, FR_FAR_N, (uint32_t)__builtin_popcountll(b2), lane);
-        if (cls == 2) {
-            const uint32_t pos = base + lane_rank(b2, lane);
-            F.far_key[pos] = f;
-            F.far_id[pos] = i0 + 1u;
-            if (!BULK) {
-                sh_min_d(F.sh, FR_FAR_MIN, f);
-                sh_max_d(F.sh, FR_FAR_MAX, f);
-            }
-        }
-        if (BULK) sh_minmax_wave(F.sh, FR_FAR_MIN, FR_FAR_MAX, cls == 2 ? f : __longlong_as_double(0x7FF0000000000000LL), cls == 2 ? f : 0.0, lane);
-    }
-}
-
-// Does the edge into node i0 (0-based, one node per lane) cross the areas of the predecessors in `arr`?  The arithmetic of
-// interx_check restricted to those polygons (InterX.m:63-76): the edge's area is transformed once, every polygon segment goes
-// through interx_segment.
-__device__ bool fr_node_hits_areas(const Search& S, const CheckCtx& C, const SpecCtx& P, uint32_t i0, unsigned long long arr) {
-    const NodeRec cn = node_load(S, i0);
-    if (!cn.parent) return false;
-    const NodeRec pn = node_load(S, cn.parent - 1);
-    const int m = NODE_MAN(cn.packed), ncols = NODE_COLS(cn.packed), k = NODE_K(cn.packed);
-    const double c = pn.cs, s = pn.sn, pX = pn.x, pY = pn.y;
-    const size_t abase = (size_t)m * 3 * PDMPC_VMAX;
-    const lds_d2* polys = P.l_soup + P.l_soff[k - 1] + P.l_lit[k - 1];
-    bool hit = false;
-    // the area's edges in two parts (0 .. H-1 and H .. VMAX-2): one node per lane means the points live in registers, and all
-    // VMAX of them at once would push the whole kernel into spilling
-    constexpr int H = PDMPC_VMAX / 2;
-    auto part = [&](auto np_tag, int first, int ne) {
-        constexpr int NP = decltype(np_tag)::value;
-        d2 pt[NP];
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {  // (columns beyond ncols are padding: transformed, never used)
-            const d2 a = C.areas_in_lds ? (d2)C.l_area[abase + first + i] : C.g_area[abase + first + i];
-            pt[i].x = c * a.x - s * a.y + pX;  // GraphSearch.m:158
-            pt[i].y = s * a.x + c * a.y + pY;  // :159
-        }
-        unsigned long long rem = arr;
-        while (rem) {
-            const int p = (int)__builtin_ctzll(rem);
-            rem &= rem - 1;
-            const lds_d2* poly = polys + p * PDMPC_VMAX;
-            d2 q0 = poly[0];
-#pragma unroll 1
-            for (int j = 0; j + 1 < PDMPC_VMAX; ++j) {
-                const d2 q1 = poly[j + 1];
-                hit = hit || interx_segment_n<NP>(pt, ne, q0, q1);
-                q0 = q1;
-            }
-        }
-    };
-    part(std::integral_constant<int, H + 1>{}, 0, ncols - 1 < H ? ncols - 1 : H);
-    if (ncols - 1 > H) part(std::integral_constant<int, PDMPC_VMAX - H>{}, H, ncols - 1 - H);
-    return hit;
 }
 
 // Phase B: position of every node relative to the goal path P_0..P_Hp (goal == 0: exhausted search, every generated node
@@ -627,7 +431,7 @@ __device__ PhaseB fr_phase_b(const KernelArgs& A, Ctx& X, const Frontier& F, con
                // TWO words, taken in turn: thread 0 starts the next pass's word while slower wavefronts may not have read this pass's
                // yet (with one word a wavefront that was held up behind the second barrier — two workgroups on a CU — read the 1 of
                // the NEXT pass, left the loop alone and took the workgroup's barriers apart)
-                const int sw = FR_SLOWEST + (guard & 1);
+                const int sw = FR_PB_ALL_A + (guard & 1);
                 if (tid == 0) F.sh[sw] = 1u;
                 __syncthreads();
                 if (!resolved) F.sh[sw] = 0u;

@@ -1,4 +1,4 @@
-// The libstdc++-faithful binary heap (priority_queue_interface_mex.cpp:19-31): exact for any keys, including the tie order among equal ones (device code, included by search_kernel.hip inside its anonymous namespace).
+// The libstdc++-faithful binary heap (priority_queue_interface_mex.cpp:19-31): exact for any keys, including the tie order among equal ones (device code, included by the kernels' translation units inside their anonymous namespaces).
 #pragma once
 
 // per-lane heap access (index may differ per lane).  LDSONLY: the caller knows every index is < HL.  Otherwise the

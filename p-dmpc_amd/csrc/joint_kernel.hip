@@ -20,8 +20,6 @@
 #include "../../include/pdmpc_math.h"
 #include "pdmpc_device.h"
 
-#define PROF_MEMBERS
-
 namespace {
 
 #include "wave_primitives.hpp"

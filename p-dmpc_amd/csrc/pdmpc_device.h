@@ -21,12 +21,10 @@
 #include "../../include/pdmpc.h"
 
 #define PDMPC_WAVE 64
-/* Twelve wavefronts per workgroup = three per SIMD.  With sixteen (128 VGPRs) the round-3 kernel spilled 44 VGPRs next to ~320 SGPRs held
- * in VGPR lanes, and in that regime hipcc 7.2 produced code that lost spilled values depending on unrelated source changes (DESIGN.md
- * section 3.4); at twelve no workload is slower.  The search kernels need 139-155 VGPRs today (profiles/r05_resource_usage.txt). */
+/* Wavefronts per workgroup follow the kernel's registers: 128 VGPRs or fewer give four wavefronts per SIMD, sixteen per workgroup; up to
+ * 168 give three and twelve (`make resources` prints what each kernel needs today). */
 #define PDMPC_MAX_WAVES 16     /* wavefronts per workgroup of the InterX search kernels (126 VGPRs: four per SIMD) */
 #define PDMPC_MAX_WAVES_SAT 12 /* ... of the separating-axis kernel (150 VGPRs: three per SIMD) */
-#define PDMPC_MAX_THREADS (PDMPC_WAVE * PDMPC_MAX_WAVES)
 #define PDMPC_SH_WORDS 128 /* 32-bit LDS words shared by the waves of a workgroup (state, counters of the search) */
 
 struct DevManPose {
@@ -90,6 +88,16 @@ struct LdsLayout {
                                            // reach, ascending (a step's vehicle obstacles / HDV sets at the index of that soup's first column, the boundary's list of step k at ll_base + (k - 1) * ll_len)
 };
 
+// The `path` region (LdsLayout::path): what the prologue of a search carves it into (search_common.hpp; a helper workgroup likewise)
+struct LdsPathRegion {
+    uint32_t path[PDMPC_HP_MAX + 2];   // scratch of the epilogue: the nodes of the plan's path; [HP_MAX + 1]: where the lanelet soup begins
+    int32_t soff[PDMPC_HP_MAX + 1];    // where each step's vehicle-obstacle soup begins ([Hp]: where the last one ends)
+    int32_t hoff[PDMPC_HP_MAX + 1];    // ... each step's HDV soup
+    uint32_t shared[PDMPC_SH_WORDS];   // the shared words (lds_layout.hpp)
+    int32_t lit[PDMPC_HP_MAX];         // literal soup length per step
+};
+#define PDMPC_LK_PATH_BYTES PDMPC_LK_ALIGN16((uint32_t)sizeof(LdsPathRegion)) /* (the sampled optimizer reserves the same) */
+
 // The regions of the graph search's layout whose sizes do not depend on the automaton or on the obstacles come first, at offsets that
 // are compile-time constants (sized for PDMPC_MAX_WAVES wavefronts and the largest ready list): the kernel addresses them with
 // immediates instead of holding two dozen LDS pointers in scalar registers it does not have (layout_bulk fills LdsLayout with the
@@ -112,7 +120,7 @@ struct LdsLayout {
 #define PDMPC_LKX_REF 0u
 #define PDMPC_LKX_SHAPE (PDMPC_LKX_REF + 3u * PDMPC_HP_MAX * 8u)
 #define PDMPC_LKX_PATH(W) (PDMPC_LKX_SHAPE + (uint32_t)(W) * (2u * PDMPC_VMAX + 1u) * 16u)
-#define PDMPC_LKX_CAND(W) (PDMPC_LKX_PATH(W) + PDMPC_LK_ALIGN16((PDMPC_HP_MAX + 2u) * 4u + 2u * (PDMPC_HP_MAX + 1u) * 4u + PDMPC_SH_WORDS * 4u + PDMPC_HP_MAX * 4u))
+#define PDMPC_LKX_CAND(W) (PDMPC_LKX_PATH(W) + PDMPC_LK_PATH_BYTES)
 #define PDMPC_LKX_EXPAND(W) (PDMPC_LKX_CAND(W) + PDMPC_LK_ALIGN16(12u * PDMPC_LKX_THREADS(W)))
 #define PDMPC_LKX_NEAR_KEY(W) (PDMPC_LKX_EXPAND(W) + (2u * PDMPC_HP_MAX * PDMPC_HP_MAX) * 8u + 16u * 16u)
 #define PDMPC_LKX_NEAR_ID(W, P) (PDMPC_LKX_NEAR_KEY(W) + PDMPC_LK_ALIGN16((uint32_t)(P) * PDMPC_LKX_THREADS(W) * 8u))
@@ -131,7 +139,6 @@ struct LdsLayout {
 #define PDMPC_BK_PER 4
 #endif
 /* entries of the LDS open list per thread (a selection pass holds them in registers) */
-#define PDMPC_LK_THREADS PDMPC_LKX_THREADS(PDMPC_LK_WAVES)
 #define PDMPC_LK_REF PDMPC_LKX_REF
 #define PDMPC_LK_SHAPE PDMPC_LKX_SHAPE
 #define PDMPC_LK_PATH PDMPC_LKX_PATH(PDMPC_LK_WAVES)

@@ -1,13 +1,11 @@
 // search_common.hpp — what the graph search's workgroups share besides the search itself (device code, included by
-// bulk_search.hpp): the validity bytes, the shared words of the predecessor bookkeeping, the copy of a predecessor's solved areas
+// bulk_search.hpp): the validity bytes, the LDS layout (lds_layout.hpp: shared words, small tables), the copy of a predecessor's solved areas
 // into the obstacle soup, the search context, and the prologue — LDS carve, MPA tables, vehicle record, obstacle soups
 // ([literal polygons + NaN][predecessors' areas padded to VMAX] per step, vectorize_all_obstacles.m:36-62), result record defaults,
 // predecessors that have finished already (PrioritizedController.m:476-491).
 #pragma once
 #include "../../include/pdmpc_math.h"
 #include "pdmpc_device.h"
-
-#define PROF_MEMBERS
 
 namespace {
 
@@ -39,17 +37,7 @@ __device__ __forceinline__ void vs_store(const VState& v, uint32_t i0, uint32_t 
 
 }  // namespace
 
-// LDS words shared between the waves of a workgroup (in the `path` region, after the offset tables); words 1, 2, 4 and 9-25 belong to
-// the search (bulk_search.hpp), words 26 and up to its rounds (frontier_common.hpp)
-#define SH_STATE 0     // ST_RUN searching, ST_ARRIVED predecessors have finished (SH_ARR says who)
-#define SH_NNODES 3    // tree size
-#define SH_PEND_LO 5   // predecessors whose areas are not in the soup yet (bit p = p-th predecessor)
-#define SH_PEND_HI 6
-#define SH_ARR_LO 7    // predecessors that just finished (to be copied into the soup)
-#define SH_ARR_HI 8
-#define SH_WORDS PDMPC_SH_WORDS
-#define ST_RUN 0u
-#define ST_ARRIVED 1u
+#include "lds_layout.hpp"
 
 namespace {
 
@@ -101,8 +89,7 @@ struct Ctx {
     lds_f64 *l_rx, *l_ry;
     volatile lds_u32* l_shared;
     VState VS;
-    lds_f64 *l_dcum, *l_term;
-    lds_d2* l_chxy;
+    lds_f64* l_dcum;
     Search S;
     CheckCtx C;
     SpecCtx P;
@@ -116,15 +103,14 @@ struct Ctx {
     bool rec_valid = false, rec_written = false;  // bulk kernel: the result record has been written ahead of the publication / at all
     bool published = false;                       // bulk kernel: the done flag is out already (the record's areas are final, only counts and ids may still be written)
     unsigned long long rt_kernel_start = 0;  // s_memrealtime at kernel entry (diagnostics of the bulk kernel)
-    bool path_ready = false;  // l_path already holds the nodes of the goal's path (the frontier kernel's counting pass has walked it)
+    bool path_ready = false;  // l_path already holds the nodes of the goal's path (phase B has walked it, fr_phase_b)
 };
 
 struct ExpandEnv {
     lds_mask64* l_mask;
     lds_i16* l_mi;
     lds_pose* l_pose;
-    lds_f64 *l_rx, *l_ry, *l_dcum, *l_term;
-    lds_d2* l_chxy;
+    lds_f64 *l_rx, *l_ry, *l_dcum;
     int Hp, n, nw, lane;
 };
 
@@ -172,18 +158,17 @@ __device__ __forceinline__ void search_prologue(const KernelArgs& A, Ctx& X, LDS
     lds_f64* l_rx = (lds_f64*)(lsm + PDMPC_LK_REF);
     lds_f64* l_ry = l_rx + PDMPC_HP_MAX;
     lds_f64* l_dtv = l_ry + PDMPC_HP_MAX;
-    lds_u32* l_path = (lds_u32*)(lsm + PDMPC_LK_PATH);
-    lds_i32* l_soff = (lds_i32*)(l_path + PDMPC_HP_MAX + 2);  // soup offsets [Hp+1], hdv offsets [Hp+1]
-    lds_i32* l_hoff = l_soff + PDMPC_HP_MAX + 1;
-    volatile lds_u32* l_shared = (volatile lds_u32*)(l_hoff + PDMPC_HP_MAX + 1);
-    lds_i32* l_lit = (lds_i32*)(l_shared + SH_WORDS);  // literal soup length per step
+    LDS_AS LdsPathRegion* l_pr = (LDS_AS LdsPathRegion*)(lsm + PDMPC_LK_PATH);
+    lds_u32* l_path = l_pr->path;
+    lds_i32* l_soff = l_pr->soff;  // soup offsets [Hp+1], hdv offsets [Hp+1]
+    lds_i32* l_hoff = l_pr->hoff;
+    volatile lds_u32* l_shared = l_pr->shared;
+    lds_i32* l_lit = l_pr->lit;  // literal soup length per step
     lds_d2* l_soup = (lds_d2*)(lsm + A.lds.soup);
     VState VS;
     VS.l = (volatile lds_u8*)(lsm + A.lds.vstate);
     VS.NV = (uint32_t)A.NV;
-    lds_f64* l_dcum = (lds_f64*)(lsm + PDMPC_LK_EXPAND);             // [HP_MAX][HP_MAX] cumulative dt*v_ref per (k_exp, t)
-    lds_f64* l_term = l_dcum + PDMPC_HP_MAX * PDMPC_HP_MAX;       // [16 children][HP_MAX] cost-to-go terms
-    lds_d2* l_chxy = (lds_d2*)(l_term + 16 * PDMPC_HP_MAX);       // [16] child positions
+    lds_f64* l_dcum = (lds_f64*)(lsm + PDMPC_LK_EXPAND);  // [HP_MAX][HP_MAX] cumulative dt*v_ref per (k_exp, t)
 
     Search S;
     S.ln = (lds_d2*)(lsm + A.lds.nodes);
@@ -245,7 +230,7 @@ __device__ __forceinline__ void search_prologue(const KernelArgs& A, Ctx& X, LDS
         }
     }
     if (tid == 0) {
-        for (int i = 0; i < SH_WORDS; ++i) l_shared[i] = 0;
+        for (int i = 0; i < PDMPC_SH_WORDS; ++i) l_shared[i] = 0;
     }
     {
         // zero the record; y_predicted starts as NaN (ControlResultsInfo.m:40)
@@ -384,8 +369,6 @@ __device__ __forceinline__ void search_prologue(const KernelArgs& A, Ctx& X, LDS
     X.l_shared = l_shared;
     X.VS = VS;
     X.l_dcum = l_dcum;
-    X.l_term = l_term;
-    X.l_chxy = l_chxy;
     X.S = S;
     X.C = C;
     X.P = P;

@@ -1,4 +1,4 @@
-// Per-vehicle search state: the tree's node records (LDS for the first NL nodes, HBM for all) and the open-list arrays of the binary heap (device code, included by search_kernel.hip inside its anonymous namespace).
+// Per-vehicle search state: the tree's node records (LDS for the first NL nodes, HBM for all) and the open-list arrays of the binary heap (device code, included by the kernels' translation units inside their anonymous namespaces).
 #pragma once
 
 // per-lane constants of the sift-down rounds (computed once per kernel)
@@ -30,7 +30,6 @@ struct Search {
     uint32_t heap_len;
     int lane;
     PopLane pl;
-    PROF_MEMBERS
 };
 
 union NodeBits {

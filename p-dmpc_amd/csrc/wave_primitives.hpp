@@ -1,4 +1,4 @@
-// Wavefront-level primitives: uniform broadcasts, LDS pointer types, staging (device code, included by search_kernel.hip inside its anonymous namespace).
+// Wavefront-level primitives: uniform broadcasts, LDS pointer types, staging (device code, included by the kernels' translation units inside their anonymous namespaces).
 #pragma once
 
 typedef double d2 __attribute__((ext_vector_type(2)));
@@ -47,5 +47,3 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
-
-__device__ __forceinline__ uint32_t lds_load_u32(const volatile lds_u32* p) { return *p; }
