@@ -446,6 +446,20 @@ int pdmpc_plan_joint(pdmpc_handle* handle, int32_t n_problems, const int32_t* pr
 int pdmpc_unique_priorities(pdmpc_handle* handle, int32_t n, const uint8_t* adjacency, int64_t max_out, int64_t* n_out, uint32_t* masks,
                             int32_t* priorities);
 int pdmpc_unique_priorities_host(int32_t n, const uint8_t* adjacency, int64_t max_out, int64_t* n_out, uint32_t* masks, int32_t* priorities);
+/* ... of n_groups graphs in one call: graph g is adjacency[g], group_n[g] x group_n[g], with the rules above.
+ * n_out[g] = K_g is always reported (-1 for a graph outside the limits n <= 64, E <= 32); masks holds the graphs' lists one after the
+ * other (sum of K_g entries, ascending within a graph), priorities their K_g x group_n[g] rows one after the other: block g is bit for
+ * bit what pdmpc_unique_priorities returns for graph g alone.  max_out[g] (only read) bounds K_g: if any K_g > max_out[g], or any graph is
+ * outside the limits, the call returns PDMPC_ERR_CAPACITY, every count is reported and NOTHING is written.  PDMPC_ERR_INVALID for
+ * n_groups < 1, a group_n[g] < 1, a max_out[g] < 0 and null arguments (masks / priorities may be NULL when every max_out[g] is 0).
+ * On the device the orientations of all graphs are tested in one launch per pass, in tiles of 4096 orientations (a graph of E edges has
+ * ceil(2^E / 4096) of them): a call whose graphs have 2^24 or more tiles together (sixteen graphs of 32 edges) returns
+ * PDMPC_ERR_CAPACITY without a launch and with every count -1.  One staging copy and one read-back of the counts per call, whatever
+ * n_groups is.  pdmpc_unique_priorities_grouped_host: the C++ twin and checker, the host enumeration graph by graph. */
+int pdmpc_unique_priorities_grouped(pdmpc_handle* handle, int32_t n_groups, const int32_t* group_n, const uint8_t** adjacency, int64_t* max_out,
+                                    int64_t* n_out, uint32_t* masks, int32_t* priorities);
+int pdmpc_unique_priorities_grouped_host(int32_t n_groups, const int32_t* group_n, const uint8_t** adjacency, int64_t* max_out, int64_t* n_out,
+                                         uint32_t* masks, int32_t* priorities);
 
 /* ---- reachable sets (csrc/reachable_sets.cpp, csrc/reachable_kernel.hip) ----
  * pdmpc_local_reachable_sets: MotionPrimitiveAutomaton.local_reachable_sets_conv (reachability_analysis_offline_DP,
@@ -648,8 +662,8 @@ int pdmpc_controller_explore_run(pdmpc_controller* c, int32_t n_perm, int32_t n_
 int pdmpc_controller_explore_follow_own(pdmpc_controller* c, int32_t on);
 int pdmpc_controller_explore_result(pdmpc_controller* c, int32_t* chosen, int32_t* n_graphs, const double** cost, const pdmpc_vehicle_out** records);
 /* The optimal-priority time step (PrioritizedOptimalController.m:25-114, PrioritizedOptimalSequentialController.m): the step's traffic
- * state under EVERY unique prioritization of its coupling graph (pdmpc_unique_priorities on the controller's device; the host twin for
- * a controller without a handle), flattened into one batch whose slots are ordered by (level, instance, slot).  Instance p plans with
+ * state under EVERY unique prioritization of its coupling graph (pdmpc_unique_priorities_grouped with one graph on the controller's
+ * device; the host twin for a controller without a handle), flattened into one batch whose slots are ordered by (level, instance, slot).  Instance p plans with
  * constant priorities = prioritization p, grouped as the controller groups (max_num_CLs); instance 0 (mask 0) is the problem
  * pdmpc_controller_build_step builds with constant priorities.  optimal_build advances the time step like build_step and leaves the
  * batch readable with pdmpc_controller_explore_problem; PDMPC_ERR_CAPACITY if more than max_instances prioritizations exist (and for
@@ -709,8 +723,8 @@ int pdmpc_controller_set_device_choice(pdmpc_controller* c, int32_t on);
  * priorities, each with its own pairs, obstacles and sizes), ONE pdmpc_plan_step for the concatenated problem,
  * every member's apply.  After a sweep step each member is byte for byte where its own pdmpc_controller_step would have left it
  * (state, records in its own slot order, problem, seeds, time step, expected work, fallback bookkeeping): a member can be taken out of
- * a sweep and stepped alone afterwards.  The plain prioritized step and the explorative step (below) are part of a sweep, with the
- * graph search or the sampled optimizer; the optimal-priority step is not (its batch sizes differ per step and per member).
+ * a sweep and stepped alone afterwards.  The plain prioritized step, the explorative step and the optimal-priority step (both below)
+ * are part of a sweep, with the graph search or the sampled optimizer.
  * pdmpc_sweep_create checks before anything advances: members on the sweep's handle, or all without one; one Hp; one optimizer
  * (PDMPC_ERR_INVALID each); no member twice (PDMPC_ERR_INVALID); sum of the members' vehicles <= the handle's max_vehicles
  * (PDMPC_ERR_CAPACITY).  Members may differ in everything else.
@@ -753,6 +767,30 @@ int pdmpc_sweep_explore_problem(pdmpc_sweep* s, int32_t* n_slots, const pdmpc_ve
 int pdmpc_sweep_explore_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records);
 int pdmpc_sweep_explore_step(pdmpc_sweep* s, int32_t n_perm);
 int pdmpc_sweep_explore_run(pdmpc_sweep* s, int32_t n_perm, int32_t n_steps, double* ms);
+/* The optimal-priority step of a sweep: the step preparation grouped as for pdmpc_sweep_build up to every member's
+ * coupling, ONE pdmpc_unique_priorities_grouped over the members' coupling graphs (its host twin for a sweep without a handle), every
+ * member's optimal-priority batch (pdmpc_controller_optimal_build's instances: K_m differs per member and per step), the batches one
+ * after the other, ONE pdmpc_plan_step_chosen with the members' optimal-priority choices concatenated, every member's apply of its chosen
+ * plans.  After it each member is byte for byte where its own pdmpc_controller_optimal_step(max_instances) would have left it (state,
+ * chosen instance per vehicle, the n x K cost table, kept records, the couplings of the chosen instances, seeds, time step, expected
+ * work, fallback bookkeeping); pdmpc_controller_optimal_result / _records read a member's part (the sweep keeps the chosen records only).
+ * A sweep may alternate plain, explorative and optimal-priority steps.  optimal_problem: the concatenated batch; member / instance /
+ * vehicle / level per slot.  optimal_apply takes the records of all its slots, chooses per member on the host and applies (works
+ * without a handle).  optimal_last_calls: calls2[0] the enumeration calls of the last build (1, whatever the number of members),
+ * calls2[1] the launches of the searches of the last optimal_step (0 after a build alone).
+ * Refused before any member advances: a null or broken sweep, max_instances < 1, optimal_step / optimal_run without a handle
+ * (PDMPC_ERR_INVALID); a member with more than 64 vehicles (PDMPC_ERR_CAPACITY).  Known only once the couplings exist, so returned by
+ * the build AFTER the members have advanced, and leaving the sweep refusing further steps as any failed step does (the handle goes on
+ * working): a member with more than 32 coupling edges, a member with more than max_instances unique prioritizations, and a sum of
+ * K_m * n_m above the handle's max_vehicles (PDMPC_ERR_CAPACITY each). */
+int pdmpc_sweep_optimal_build(pdmpc_sweep* s, int32_t max_instances);
+int pdmpc_sweep_optimal_problem(pdmpc_sweep* s, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index,
+                                const pdmpc_polygon_set** fallback, const int32_t** member, const int32_t** instance, const int32_t** vehicle,
+                                const int32_t** level);
+int pdmpc_sweep_optimal_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records);
+int pdmpc_sweep_optimal_step(pdmpc_sweep* s, int32_t max_instances);
+int pdmpc_sweep_optimal_run(pdmpc_sweep* s, int32_t max_instances, int32_t n_steps, double* ms);
+int pdmpc_sweep_optimal_last_calls(pdmpc_sweep* s, int32_t* calls2);
 
 /* ---- several GPUs behind the same boundary (csrc/group.cpp) ----
  * The reference's vehicles exchange their solved areas after every computation level: each publishes a Predictions message that every

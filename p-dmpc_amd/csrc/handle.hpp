@@ -360,11 +360,18 @@ struct TimedLaunch {
     }
 };
 
-// pdmpc_unique_priorities (priority_kernel.hip)
+// pdmpc_unique_priorities / pdmpc_unique_priorities_grouped (priority_kernel.hip): grown when a call needs more, kept otherwise
 struct PrioState {
     DevBuf<uint32_t> count, mask;  // acyclic masks per tile, the acyclic masks
     DevBuf<int64_t> off;           // exclusive offsets of the tiles (entry n_tiles: the total)
     DevBuf<int32_t> order;         // the priorities of every acyclic mask
+    // the grouped call: a PriorityArgs per graph, the tile prefix and the row bases (prio_layout in step_prep.cpp) with their pinned
+    // staging, and where every graph's masks start (read back in one copy)
+    DevBuf<unsigned char> table;
+    PinnedBuf<unsigned char> h_table;
+    DevBuf<int64_t> group_off;
+    PinnedBuf<int64_t> h_group_off;
+    std::vector<int32_t> edges;    // E per graph (-1: outside the limits)
 };
 
 // pdmpc_upload_reachable_sets / pdmpc_reachable_set_coupling (reachable_kernel.hip): the local hulls, and the coupler's workspace

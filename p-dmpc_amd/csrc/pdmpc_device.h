@@ -329,6 +329,16 @@ struct PriorityArgs {                          // passed by value: the kernels r
     uint32_t all_edges;                        // the E low bits
     uint64_t n_masks;                          // 2^E
 };
+// The grouped call (pdmpc_unique_priorities_grouped): one PriorityArgs per graph and the prefix tables, in the handle's memory.  A launch
+// holds fewer than 2^32 threads, so the tiles of all graphs of a call are fewer than 2^24.
+#define PDMPC_PRIO_MAX_TILES (((int64_t)1 << 24) - 1)
+struct PriorityGroups {
+    int32_t n_groups;
+    const PriorityArgs* graph;    // [n_groups]
+    const int64_t* tile_first;    // [n_groups + 1] prefix sums of the graphs' tile counts ceil(2^E_g / PDMPC_PRIO_TILE)
+    int64_t* mask_first;          // [n_groups + 1] where graph g's masks start in the concatenated list (the offsets pass writes it)
+    const int64_t* row_first;     // [n_groups] where graph g's rows start in priorities: sum over g' < g of K_g' n_g'
+};
 
 // The reachable-set coupler (reachable_kernel.hip; ReachableSetCoupler.m:5-56): every vehicle's step-Hp hull moved to its pose,
 // then the pairs i < j.  All arrays are the handle's, sized at pdmpc_upload_reachable_sets.
@@ -507,6 +517,12 @@ int pdmpc_launch_priority_count(const PriorityArgs* args, int64_t n_tiles, uint3
 int pdmpc_launch_priority_scan(const uint32_t* tile_count, int64_t n_tiles, int64_t* tile_off, void* stream);
 int pdmpc_launch_priority_write(const PriorityArgs* args, int64_t n_tiles, const int64_t* tile_off, int64_t capacity, uint32_t* masks, void* stream);
 int pdmpc_launch_priority_order(const PriorityArgs* args, const uint32_t* masks, int64_t count, int32_t* priorities, void* stream);
+// ... and of several graphs in one call: the same passes over the tiles of all graphs (n_tiles <= PDMPC_PRIO_MAX_TILES), and behind the
+// scan the pass that gathers the graphs' mask offsets into g->mask_first
+int pdmpc_launch_priority_count_grouped(const PriorityGroups* g, int64_t n_tiles, uint32_t* tile_count, void* stream);
+int pdmpc_launch_priority_group_offsets(const PriorityGroups* g, const int64_t* tile_off, void* stream);
+int pdmpc_launch_priority_write_grouped(const PriorityGroups* g, int64_t n_tiles, const int64_t* tile_off, int64_t capacity, uint32_t* masks, void* stream);
+int pdmpc_launch_priority_order_grouped(const PriorityGroups* g, const uint32_t* masks, int64_t count, int32_t* priorities, void* stream);
 int pdmpc_launch_edge_check(int mode, int n_cases, const int32_t* a_off, const double* a_x, const double* a_y, const int32_t* b_off, const double* b_x,
                             const double* b_y, int32_t* hit, void* stream);
 #ifdef __cplusplus

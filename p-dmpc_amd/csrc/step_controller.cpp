@@ -176,6 +176,20 @@ struct PrepScratch {
         std::vector<double> x, y, cos_yaw, sin_yaw;
         std::vector<int32_t> collisions, priorities;
     } fca;
+    // the grouped enumeration of an optimal-priority step: the members' coupling graphs, and their lists one after the other
+    struct Prio {
+        int32_t calls = 0;  // enumeration calls of the last build
+        std::vector<int32_t> group_n;
+        std::vector<const uint8_t*> adjacency;
+        std::vector<int64_t> max_out, n_out;
+        std::vector<uint32_t> masks;
+        std::vector<int32_t> priorities;
+    } prio;
+};
+// the batch of prioritizations build_members puts behind every member's step: none, the explorative one (n_perm > 0) or the
+// optimal-priority one (max_instances > 0)
+struct BatchKind {
+    int n_perm = 0, max_instances = 0;
 };
 
 }  // namespace
@@ -1427,6 +1441,28 @@ int permute_instances(pdmpc_controller* c, int32_t n_perm, uint32_t seed) {
     return PDMPC_OK;
 }
 
+// pdmpc_controller_optimal_build behind its pdmpc_controller_build_step and the enumeration (build_members runs those for all its
+// members at once, then this one per member): the step's traffic state under each of the K unique prioritizations (masks, K x n priorities)
+int optimal_instances(pdmpc_controller* c, int64_t K, const uint32_t* masks, const int32_t* priorities) {
+    const int n = c->n;
+    c->o_masks.assign(masks, masks + K);
+    c->o_prio.assign(priorities, priorities + K * n);
+    begin_instances(c, (int)K);
+    for (int p = 0; p < (int)K; ++p) {
+        // ConstantPrioritizer on the given priorities + directed_coupling_from_priorities (Prioritizer.m:64-77): keep i -> j iff
+        // priority(i) <= priority(j); then assemble_step groups (cuts to max_num_CLs levels) per instance
+        const int32_t* pr = c->o_prio.data() + (size_t)p * n;
+        c->pri.directed.assign((size_t)n * n, 0);
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < n; ++j)
+                if (at(c->adjacency, n, i, j) && !(pr[j] < pr[i])) at(c->pri.directed, n, i, j) = 1;
+        if (const int rc = assemble_step(c)) return rc;
+        keep_instance(c, p);
+    }
+    flatten_instances(c, (int)K);
+    return PDMPC_OK;
+}
+
 // ---- ONE step preparation over a span of members: a sweep's members, or the one controller that steps alone
 // the poses of the members `who` one after the other (and their lanelet polygons: with_lanelets)
 void gather(pdmpc_controller* const* members, PrepScratch::Call& C, const std::vector<int>& who, bool with_lanelets) {
@@ -1628,9 +1664,12 @@ int gather_fca(pdmpc_controller* const* members, PrepScratch::Fca& F, const std:
 }
 
 // The step problems of M members (of one Hp, all on the handle h or all without one), built with ONE step preparation for all of them:
-// with a handle the grouped device calls, without one the host twins.  This is the only place that asks which.  n_perm > 0: every
+// with a handle the grouped device calls, without one the host twins.  This is the only place that asks which.  batch.n_perm > 0: every
 // member's explorative batch of n_perm prioritizations behind its step (pdmpc_controller_explore_build's statements, in its order).
-int build_members(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, int n_perm, PrepScratch& S) {
+// batch.max_instances > 0: every member's optimal-priority batch behind the steps -- ONE enumeration of the unique prioritizations of all
+// members' coupling graphs, then pdmpc_controller_optimal_build's instances per member.
+int build_members(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, BatchKind batch, PrepScratch& S) {
+    const int n_perm = batch.n_perm;
     struct ExploringAll {  // (the members' memos of the obstacle sets are on while their prioritizations are assembled)
         pdmpc_controller* const* members;
         size_t M;
@@ -1640,9 +1679,10 @@ int build_members(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, i
         void set(bool v) {
             for (size_t m = 0; on && m < M; ++m) members[m]->exploring = v;
         }
-    } exploring(members, M, n_perm > 0);
+    } exploring(members, M, n_perm > 0 || batch.max_instances > 0);
     S.prep.assign(M, StepPrep());
     std::fill(S.prep_calls, S.prep_calls + 4, 0);
+    S.prio.calls = 0;
     for (size_t m = 0; m < M; ++m)
         if (const int rc = begin_step(members[m], S.prep[m])) return rc;
     // who takes part in which grouped call: bounded (step Hp only / every step: one bounding call each) or the plain hulls
@@ -1692,6 +1732,32 @@ int build_members(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, i
         }
         if (!rc && n_perm > 0) rc = permute_instances(c, n_perm, (uint32_t)c->k);  // RandStream("mt19937ar", Seed = obj.k) (:249)
         if (rc) return rc;
+    }
+    if (batch.max_instances < 1) return PDMPC_OK;
+    // every unique prioritization of every member's coupling graph: one call whatever M is
+    PrepScratch::Prio& Q = S.prio;
+    Q.group_n.resize(M);
+    Q.adjacency.resize(M);
+    Q.max_out.assign(M, batch.max_instances);
+    Q.n_out.assign(M, 0);
+    size_t rows = 0;
+    for (size_t m = 0; m < M; ++m) {
+        Q.group_n[m] = members[m]->n;
+        Q.adjacency[m] = members[m]->adjacency.data();
+        rows += (size_t)batch.max_instances * members[m]->n;
+    }
+    Q.masks.resize(M * (size_t)batch.max_instances);
+    Q.priorities.resize(rows);
+    Q.calls += 1;
+    rc = h ? pdmpc_unique_priorities_grouped(h, (int32_t)M, Q.group_n.data(), Q.adjacency.data(), Q.max_out.data(), Q.n_out.data(), Q.masks.data(), Q.priorities.data())
+           : pdmpc_unique_priorities_grouped_host((int32_t)M, Q.group_n.data(), Q.adjacency.data(), Q.max_out.data(), Q.n_out.data(), Q.masks.data(), Q.priorities.data());
+    if (rc) return h ? cfail(nullptr, rc, pdmpc_last_error()) : rc;
+    const uint32_t* masks = Q.masks.data();
+    const int32_t* priorities = Q.priorities.data();
+    for (size_t m = 0; m < M; ++m) {
+        if ((rc = optimal_instances(members[m], Q.n_out[m], masks, priorities))) return rc;
+        masks += Q.n_out[m];
+        priorities += Q.n_out[m] * members[m]->n;
     }
     return PDMPC_OK;
 }
@@ -2290,7 +2356,7 @@ int pdmpc_exploration_permutations(int32_t n_levels, int32_t n_perm, uint32_t se
 // (slot = position), per-slot predecessor slots, per-slot areas to publish on exhaustion.  A step alone is a sweep of one member.
 int pdmpc_controller_build_step(pdmpc_controller* c) {
     if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
-    const int rc = build_members(c->h, &c, 1, 0, c->prep);
+    const int rc = build_members(c->h, &c, 1, BatchKind{}, c->prep);
     if (rc) c->err = g_cerr;
     return rc;
 }
@@ -2365,14 +2431,18 @@ int pdmpc_controller_explore_result(pdmpc_controller* c, int32_t* chosen, int32_
     return PDMPC_OK;
 }
 
+}  // extern "C"
+
+namespace {
 // Prioritizer.unique_priorities (Prioritizer.m:97-140) on the host: the twin of the device enumeration (csrc/priority_kernel.hip) and its
 // checker.  Every orientation is tested by peeling its sources off vertex by vertex over explicit edge lists (the kernel peels bit sets);
 // the priorities follow the smallest-index-first topological order (toposort(..., 'Order', 'stable')).
-int pdmpc_unique_priorities_host(int32_t n, const uint8_t* adjacency, int64_t max_out, int64_t* n_out, uint32_t* masks, int32_t* priorities) {
-    if (n_out) *n_out = -1;
-    if (n < 1 || !adjacency || !n_out || max_out < 0 || (max_out > 0 && (!masks || !priorities)))
-        return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_unique_priorities_host: bad argument");
-    if (n > 64) return cfail(nullptr, PDMPC_ERR_CAPACITY, "pdmpc_unique_priorities_host: more than 64 vehicles");
+// the enumeration behind pdmpc_unique_priorities_host and its grouped sibling (arguments checked by them): PDMPC_OK, or
+// PDMPC_ERR_CAPACITY with *why set
+int enumerate_on_host(int32_t n, const uint8_t* adjacency, int64_t max_out, int64_t* n_out, uint32_t* masks, int32_t* priorities, const char** why) {
+    *n_out = -1;
+    *why = "more than 64 vehicles";
+    if (n > 64) return PDMPC_ERR_CAPACITY;
     std::vector<int> er, ec;  // [edge_row, edge_col] = find(triu(adjacency, 1)): by column, then by row
     for (int c = 0; c < n; ++c)
         for (int r = 0; r < c; ++r)
@@ -2381,7 +2451,8 @@ int pdmpc_unique_priorities_host(int32_t n, const uint8_t* adjacency, int64_t ma
                 ec.push_back(c);
             }
     const int E = (int)er.size();
-    if (E > 32) return cfail(nullptr, PDMPC_ERR_CAPACITY, "pdmpc_unique_priorities_host: more than 32 coupling edges");
+    *why = "more than 32 coupling edges";
+    if (E > 32) return PDMPC_ERR_CAPACITY;
     const uint64_t n_masks = 1ull << E;
     std::vector<int> head((size_t)E), tail((size_t)E), indeg((size_t)n), order((size_t)n);
     std::vector<uint8_t> placed((size_t)n);
@@ -2416,7 +2487,50 @@ int pdmpc_unique_priorities_host(int32_t n, const uint8_t* adjacency, int64_t ma
         ++K;
     }
     *n_out = K;
-    if (K > max_out) return cfail(nullptr, PDMPC_ERR_CAPACITY, "pdmpc_unique_priorities_host: more unique prioritizations than max_out");
+    *why = "more unique prioritizations than max_out";
+    if (K > max_out) return PDMPC_ERR_CAPACITY;
+    return PDMPC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pdmpc_unique_priorities_host(int32_t n, const uint8_t* adjacency, int64_t max_out, int64_t* n_out, uint32_t* masks, int32_t* priorities) {
+    if (n_out) *n_out = -1;
+    if (n < 1 || !adjacency || !n_out || max_out < 0 || (max_out > 0 && (!masks || !priorities)))
+        return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_unique_priorities_host: bad argument");
+    const char* why = "";
+    if (const int rc = enumerate_on_host(n, adjacency, max_out, n_out, masks, priorities, &why)) return cfail(nullptr, rc, std::string("pdmpc_unique_priorities_host: ") + why);
+    return PDMPC_OK;
+}
+
+// ... of several graphs (the twin of pdmpc_unique_priorities_grouped): every graph counted first, and only if every count fits its
+// max_out the lists written one after the other
+int pdmpc_unique_priorities_grouped_host(int32_t n_groups, const int32_t* group_n, const uint8_t** adjacency, int64_t* max_out, int64_t* n_out, uint32_t* masks,
+                                         int32_t* priorities) {
+    if (n_groups < 1 || !group_n || !adjacency || !max_out || !n_out) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_unique_priorities_grouped_host: bad argument");
+    for (int g = 0; g < n_groups; ++g) {
+        n_out[g] = -1;
+        if (group_n[g] < 1 || !adjacency[g] || max_out[g] < 0 || (max_out[g] > 0 && (!masks || !priorities)))
+            return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_unique_priorities_grouped_host: bad argument for graph " + std::to_string(g));
+    }
+    int refused = -1;
+    const char *why = "", *first_why = "";
+    for (int g = 0; g < n_groups; ++g) {  // (max_out 0: nothing is written, the count is reported)
+        (void)enumerate_on_host(group_n[g], adjacency[g], 0, &n_out[g], nullptr, nullptr, &why);
+        if ((n_out[g] < 0 || n_out[g] > max_out[g]) && refused < 0) {
+            refused = g;
+            first_why = why;
+        }
+    }
+    if (refused >= 0) return cfail(nullptr, PDMPC_ERR_CAPACITY, "pdmpc_unique_priorities_grouped_host: graph " + std::to_string(refused) + ": " + first_why);
+    for (int g = 0; g < n_groups; ++g) {
+        int64_t K = 0;
+        if (const int rc = enumerate_on_host(group_n[g], adjacency[g], max_out[g], &K, masks, priorities, &why))
+            return cfail(nullptr, rc, std::string("pdmpc_unique_priorities_grouped_host: ") + why);
+        masks += K;
+        priorities += K * group_n[g];
+    }
     return PDMPC_OK;
 }
 
@@ -2425,37 +2539,11 @@ int pdmpc_unique_priorities_host(int32_t n, const uint8_t* adjacency, int64_t ma
 // prepare_permutation = prioritize() with constant priorities = prioritization p, then group(); slots ordered by (level, instance, slot).
 int pdmpc_controller_optimal_build(pdmpc_controller* c, int32_t max_instances) {
     if (!c || max_instances < 1) return cfail(c, PDMPC_ERR_INVALID, "bad argument");
-    Exploring exploring(c);
-    int rc = pdmpc_controller_build_step(c);  // traffic info and coupling of the step (and the controller's own problem, replaced below)
-    if (rc) return rc;
-    const int n = c->n;
-    c->o_masks.resize((size_t)max_instances);
-    c->o_prio.resize((size_t)max_instances * n);
-    int64_t K = 0;
-    if (c->h) {
-        rc = pdmpc_unique_priorities(c->h, n, c->adjacency.data(), max_instances, &K, c->o_masks.data(), c->o_prio.data());
-        if (rc) return cfail(c, rc, pdmpc_last_error());
-    } else {
-        rc = pdmpc_unique_priorities_host(n, c->adjacency.data(), max_instances, &K, c->o_masks.data(), c->o_prio.data());
-        if (rc) return cfail(c, rc, g_cerr);
-    }
-    c->o_masks.resize((size_t)K);
-    c->o_prio.resize((size_t)K * n);
-    begin_instances(c, (int)K);
-    for (int p = 0; p < (int)K; ++p) {
-        // ConstantPrioritizer on the given priorities + directed_coupling_from_priorities (Prioritizer.m:64-77): keep i -> j iff
-        // priority(i) <= priority(j); then assemble_step groups (cuts to max_num_CLs levels) per instance
-        const int32_t* pr = c->o_prio.data() + (size_t)p * n;
-        c->pri.directed.assign((size_t)n * n, 0);
-        for (int i = 0; i < n; ++i)
-            for (int j = 0; j < n; ++j)
-                if (at(c->adjacency, n, i, j) && !(pr[j] < pr[i])) at(c->pri.directed, n, i, j) = 1;
-        rc = assemble_step(c);
-        if (rc) return rc;
-        keep_instance(c, p);
-    }
-    flatten_instances(c, (int)K);
-    return PDMPC_OK;
+    // traffic info and coupling of the step (and the controller's own problem, replaced by instance 0), the enumeration, the instances: a
+    // sweep of one member
+    const int rc = build_members(c->h, &c, 1, BatchKind{0, max_instances}, c->prep);
+    if (rc) c->err = g_cerr;
+    return rc;
 }
 
 int pdmpc_controller_optimal_choose(pdmpc_controller* c, const pdmpc_vehicle_out* recs, int32_t* chosen, double* cost) {
@@ -2507,9 +2595,12 @@ struct pdmpc_sweep {
     StepProblem prob;                          // the concatenated problem, and per slot of it:
     std::vector<int32_t> member, member_slot;  // whose it is, and which of that member's slots
     std::vector<pdmpc_vehicle_out> out;
-    // the concatenated explorative batch (pdmpc_sweep_explore_*): the members' flattened batches one after the other, and their choices
+    int32_t optimal_calls[2] = {0, 0};  // pdmpc_sweep_optimal_last_calls
+    // the concatenated batch of prioritizations (pdmpc_sweep_explore_*, pdmpc_sweep_optimal_*): the members' flattened batches one after
+    // the other, and their choices
     struct Batch {
-        int n_perm = 0;              // of the batch that is built (0: none)
+        int n_perm = 0;              // of the explorative batch that is built (0: none)
+        bool optimal = false;        // an optimal-priority batch is built (the members' K differ: first[])
         std::vector<int32_t> first;  // [M + 1] member m's first slot of the batch
         StepProblem prob;
         std::vector<int32_t> member, instance, vehicle, level;  // per slot: whose it is, and the member's own tags of it
@@ -2546,7 +2637,7 @@ void append_problem(StepProblem& S, const StepProblem& P, int32_t first) {
 
 int sweep_build(pdmpc_sweep* s) {
     const size_t M = s->members.size();
-    if (const int rc = build_members(s->h, s->members.data(), M, 0, s->prep)) return rc;
+    if (const int rc = build_members(s->h, s->members.data(), M, BatchKind{}, s->prep)) return rc;
     s->member.clear();
     s->member_slot.clear();
     for (size_t m = 0; m < M; ++m) {
@@ -2596,12 +2687,24 @@ int explore_refusal(pdmpc_sweep* s, int32_t n_perm, bool needs_handle) {
     return PDMPC_OK;
 }
 
-// every member's explorative batch, and the batches one after the other
-int sweep_explore_build(pdmpc_sweep* s, int n_perm) {
+// what pdmpc_sweep_optimal_* refuse before any member advances
+int optimal_refusal(pdmpc_sweep* s, int32_t max_instances, bool needs_handle) {
+    if (!s) return cfail(nullptr, PDMPC_ERR_INVALID, "null sweep");
+    if (needs_handle && !s->h) return cfail(nullptr, PDMPC_ERR_INVALID, "the sweep has no backend handle");
+    if (s->broken) return cfail(nullptr, PDMPC_ERR_INVALID, "an earlier step of the sweep failed: its members have advanced unevenly");
+    if (max_instances < 1) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_optimal: max_instances < 1");
+    for (const pdmpc_controller* c : s->members)
+        if (c->n > 64) return cfail(nullptr, PDMPC_ERR_CAPACITY, "pdmpc_sweep_optimal: a member has more than 64 vehicles");
+    return PDMPC_OK;
+}
+
+// every member's batch of prioritizations (explorative or optimal-priority), and the batches one after the other
+int sweep_batch_build(pdmpc_sweep* s, BatchKind kind) {
     pdmpc_sweep::Batch& X = s->x;
     X.n_perm = 0;
+    X.optimal = false;
     const size_t M = s->members.size();
-    if (const int rc = build_members(s->h, s->members.data(), M, n_perm, s->prep)) return rc;
+    if (const int rc = build_members(s->h, s->members.data(), M, kind, s->prep)) return rc;
     X.first.assign(1, 0);
     X.member.clear();
     X.instance.clear();
@@ -2616,25 +2719,59 @@ int sweep_explore_build(pdmpc_sweep* s, int n_perm) {
         X.vehicle.insert(X.vehicle.end(), c->x_vehicle.begin(), c->x_vehicle.end());
         X.level.insert(X.level.end(), c->x_level.begin(), c->x_level.end());
     }
-    X.n_perm = n_perm;
+    X.n_perm = kind.n_perm;
+    X.optimal = kind.max_instances > 0;
+    return PDMPC_OK;
+}
+int sweep_explore_build(pdmpc_sweep* s, int n_perm) { return sweep_batch_build(s, BatchKind{n_perm, 0}); }
+
+// the optimal-priority batches: what is known only once the couplings exist is refused here (the enumeration refuses a member with more
+// than 32 coupling edges or more than max_instances prioritizations)
+int sweep_optimal_build(pdmpc_sweep* s, int max_instances) {
+    s->optimal_calls[0] = s->optimal_calls[1] = 0;
+    const int rc = sweep_batch_build(s, BatchKind{0, max_instances});
+    s->optimal_calls[0] = s->prep.prio.calls;
+    if (rc) return rc;
+    if (s->h) {
+        pdmpc_config hc{};
+        int32_t has_mpa = 0;
+        if (pdmpc_get_config(s->h, &hc, &has_mpa) != PDMPC_OK) return cfail(nullptr, PDMPC_ERR_INVALID, "bad backend handle");
+        if (s->x.prob.n() > hc.max_vehicles)
+            return cfail(nullptr, PDMPC_ERR_CAPACITY, "pdmpc_sweep_optimal: the members' unique prioritizations are more plans than the handle's max_vehicles");
+    }
     return PDMPC_OK;
 }
 
+// the concatenated batch as pdmpc_sweep_explore_problem / pdmpc_sweep_optimal_problem hand it out
+int expose_batch(const pdmpc_sweep::Batch& X, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index,
+                 const pdmpc_polygon_set** fallback, const int32_t** member, const int32_t** instance, const int32_t** vehicle, const int32_t** level) {
+    expose(X.prob, n_slots, in, pred_offset, pred_index, fallback);
+    if (member) *member = X.member.data();
+    if (instance) *instance = X.instance.data();
+    if (vehicle) *vehicle = X.vehicle.data();
+    if (level) *level = X.level.data();
+    return PDMPC_OK;
+}
+
+// does every vehicle of member c follow the controller's own prioritization whatever is chosen? (the explorative step's measurement
+// switch; never the optimal-priority step)
+inline bool follows_own(const pdmpc_controller* c, const BatchChoice& how) { return &how == &kExploreChoice && c->follow_own; }
+
 // the records of the whole batch: every member chooses on the host and applies its chosen plans
-int sweep_explore_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records) {
+int sweep_batch_apply(pdmpc_sweep* s, const BatchChoice& how, const pdmpc_vehicle_out* records) {
     const pdmpc_sweep::Batch& X = s->x;
     for (size_t m = 0; m < s->members.size(); ++m) {
         pdmpc_controller* c = s->members[m];
         c->x_out.assign(records + X.first[m], records + X.first[m + 1]);
-        if (const int rc = choose_from_records(c, kExploreChoice, c->x_out.data(), X.first[m + 1] - X.first[m], c->follow_own)) return rc;
-        gather_kept_records(c, c->follow_own);
+        if (const int rc = choose_from_records(c, how, c->x_out.data(), X.first[m + 1] - X.first[m], follows_own(c, how))) return rc;
+        gather_kept_records(c, follows_own(c, how));
         if (const int rc = pdmpc_controller_apply(c, c->out.data())) return rc;
     }
     return PDMPC_OK;
 }
 
-// the members' choices as ONE pdmpc_choice over the slots of the whole batch
-void concatenate_choices(pdmpc_sweep* s) {
+// the members' choices, each described by `how`, as ONE pdmpc_choice over the slots of the whole batch
+void concatenate_choices(pdmpc_sweep* s, const BatchChoice& how) {
     pdmpc_sweep::Batch& X = s->x;
     const size_t M = s->members.size();
     X.lists.resize(M);
@@ -2648,8 +2785,8 @@ void concatenate_choices(pdmpc_sweep* s) {
     for (size_t m = 0; m < M; ++m) {
         pdmpc_controller* c = s->members[m];
         ChoiceLists& D = X.lists[m];
-        explore_describe(c, D);
-        pick_chosen_plans(c, D, c->follow_own, false);
+        how.describe(c, D);
+        pick_chosen_plans(c, D, follows_own(c, how), how.graph_per_vehicle);
         const int32_t f = X.first[m], g0 = X.first_graph[m], c0 = X.first_cell[m], s0 = (int32_t)A.cell_slot.size(), p0 = (int32_t)A.pick_slot.size();
         for (int q = 1; q <= D.n_cells(); ++q) A.cell_offset.push_back(s0 + D.cell_offset[(size_t)q]);
         for (int32_t slot : D.cell_slot) A.cell_slot.push_back(f + slot);
@@ -2663,6 +2800,35 @@ void concatenate_choices(pdmpc_sweep* s) {
     X.chosen.resize((size_t)X.first_graph.back());
     X.cell_cost.resize((size_t)X.first_cell.back());
     X.picks.resize((size_t)N_of(s));
+}
+// The lock-step behind a built batch (explorative or optimal-priority; t: when its build began): ONE pdmpc_plan_step_chosen for the
+// concatenated batch with the members' choices concatenated, every member adopts its part -- as its own step that keeps the chosen
+// plans only leaves it -- and applies it.
+int sweep_batch_step(pdmpc_sweep* s, std::chrono::steady_clock::time_point t, const BatchChoice& how) {
+    pdmpc_sweep::Batch& X = s->x;
+    s->timing[0] = ms_since(t);
+    const size_t M = s->members.size();
+    // (the work of the last step as the members' own steps over a batch hand it over)
+    auto pops_of = [&](int q) {
+        const pdmpc_controller* c = s->members[(size_t)X.member[(size_t)q]];
+        return c->last_pops.size() == (size_t)c->n ? c->last_pops[(size_t)X.vehicle[(size_t)q]] : 0.0;
+    };
+    concatenate_choices(s, how);
+    const pdmpc_choice ch = X.all.view();
+    int rc = plan_built(s->h, X.prob, true, pops_of, s->members[0]->optimizer, s->timing, pdmpc_plan_step_chosen, &ch, X.chosen.data(), X.cell_cost.data(), X.picks.data());
+    if (rc) return rc;
+    t = std::chrono::steady_clock::now();
+    for (size_t m = 0; m < M; ++m) {
+        pdmpc_controller* c = s->members[m];
+        how.adopt(c, X.lists[m], X.chosen.data() + X.first_graph[m], X.cell_cost.data() + X.first_cell[m], follows_own(c, how));
+        c->x_out.clear();
+        c->out.assign(X.picks.begin() + s->first[m], X.picks.begin() + s->first[m + 1]);
+    }
+    s->timing[4] = ms_since(t);
+    t = std::chrono::steady_clock::now();
+    for (size_t m = 0; m < M && !rc; ++m) rc = pdmpc_controller_apply(s->members[m], s->members[m]->out.data());
+    s->timing[5] = ms_since(t);
+    return rc;
 }
 }  // namespace
 
@@ -2770,55 +2936,64 @@ int pdmpc_sweep_explore_build(pdmpc_sweep* s, int32_t n_perm) {
 int pdmpc_sweep_explore_problem(pdmpc_sweep* s, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index,
                                 const pdmpc_polygon_set** fallback, const int32_t** member, const int32_t** instance, const int32_t** vehicle, const int32_t** level) {
     if (!s || s->x.n_perm < 1) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_explore_problem before pdmpc_sweep_explore_build");
-    const pdmpc_sweep::Batch& X = s->x;
-    expose(X.prob, n_slots, in, pred_offset, pred_index, fallback);
-    if (member) *member = X.member.data();
-    if (instance) *instance = X.instance.data();
-    if (vehicle) *vehicle = X.vehicle.data();
-    if (level) *level = X.level.data();
-    return PDMPC_OK;
+    return expose_batch(s->x, n_slots, in, pred_offset, pred_index, fallback, member, instance, vehicle, level);
 }
 
 int pdmpc_sweep_explore_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records) {
     if (!s || !records) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
     if (s->broken) return cfail(nullptr, PDMPC_ERR_INVALID, "an earlier step of the sweep failed: its members have advanced unevenly");
     if (s->x.n_perm < 1) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_explore_apply before pdmpc_sweep_explore_build");
-    return sweep_guard(s, sweep_explore_apply(s, records));
+    return sweep_guard(s, sweep_batch_apply(s, kExploreChoice, records));
 }
 
 int pdmpc_sweep_explore_step(pdmpc_sweep* s, int32_t n_perm) {
     if (const int rc = explore_refusal(s, n_perm, true)) return rc;
-    auto t = std::chrono::steady_clock::now();
-    int rc = sweep_explore_build(s, n_perm);
-    if (rc) return sweep_guard(s, rc);
-    pdmpc_sweep::Batch& X = s->x;
-    s->timing[0] = ms_since(t);
-    const size_t M = s->members.size();
-    // (the work of the last step as the members' own explorative steps hand it over)
-    auto pops_of = [&](int q) {
-        const pdmpc_controller* c = s->members[(size_t)X.member[(size_t)q]];
-        return c->last_pops.size() == (size_t)c->n ? c->last_pops[(size_t)X.vehicle[(size_t)q]] : 0.0;
-    };
-    concatenate_choices(s);
-    const pdmpc_choice ch = X.all.view();
-    rc = plan_built(s->h, X.prob, true, pops_of, s->members[0]->optimizer, s->timing, pdmpc_plan_step_chosen, &ch, X.chosen.data(), X.cell_cost.data(), X.picks.data());
-    if (rc) return sweep_guard(s, rc);
-    t = std::chrono::steady_clock::now();
-    for (size_t m = 0; m < M; ++m) {  // every member adopts its part: as its own step that keeps the chosen plans only leaves it
-        pdmpc_controller* c = s->members[m];
-        explore_adopt(c, X.lists[m], X.chosen.data() + X.first_graph[m], X.cell_cost.data() + X.first_cell[m], c->follow_own);
-        c->x_out.clear();
-        c->out.assign(X.picks.begin() + s->first[m], X.picks.begin() + s->first[m + 1]);
-    }
-    s->timing[4] = ms_since(t);
-    t = std::chrono::steady_clock::now();
-    for (size_t m = 0; m < M && !rc; ++m) rc = pdmpc_controller_apply(s->members[m], s->members[m]->out.data());
-    s->timing[5] = ms_since(t);
-    return sweep_guard(s, rc);
+    const auto t = std::chrono::steady_clock::now();
+    if (const int rc = sweep_explore_build(s, n_perm)) return sweep_guard(s, rc);
+    return sweep_guard(s, sweep_batch_step(s, t, kExploreChoice));
 }
 
 int pdmpc_sweep_explore_run(pdmpc_sweep* s, int32_t n_perm, int32_t n_steps, double* ms) {
     return timed_steps(n_steps, ms, [&] { return pdmpc_sweep_explore_step(s, n_perm); });
+}
+
+// ---- the optimal-priority step of a sweep
+int pdmpc_sweep_optimal_build(pdmpc_sweep* s, int32_t max_instances) {
+    if (const int rc = optimal_refusal(s, max_instances, false)) return rc;
+    return sweep_guard(s, sweep_optimal_build(s, max_instances));
+}
+
+int pdmpc_sweep_optimal_problem(pdmpc_sweep* s, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index,
+                                const pdmpc_polygon_set** fallback, const int32_t** member, const int32_t** instance, const int32_t** vehicle, const int32_t** level) {
+    if (!s || !s->x.optimal) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_optimal_problem before pdmpc_sweep_optimal_build");
+    return expose_batch(s->x, n_slots, in, pred_offset, pred_index, fallback, member, instance, vehicle, level);
+}
+
+int pdmpc_sweep_optimal_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records) {
+    if (!s || !records) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
+    if (s->broken) return cfail(nullptr, PDMPC_ERR_INVALID, "an earlier step of the sweep failed: its members have advanced unevenly");
+    if (!s->x.optimal) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_optimal_apply before pdmpc_sweep_optimal_build");
+    return sweep_guard(s, sweep_batch_apply(s, kOptimalChoice, records));
+}
+
+int pdmpc_sweep_optimal_step(pdmpc_sweep* s, int32_t max_instances) {
+    if (const int rc = optimal_refusal(s, max_instances, true)) return rc;
+    const auto t = std::chrono::steady_clock::now();
+    if (const int rc = sweep_optimal_build(s, max_instances)) return sweep_guard(s, rc);
+    const int rc = sweep_batch_step(s, t, kOptimalChoice);
+    pdmpc_stats st{};
+    if (!rc) s->optimal_calls[1] = pdmpc_get_last_stats(s->h, &st) == PDMPC_OK ? (int32_t)st.n_launches : 1;
+    return sweep_guard(s, rc);
+}
+
+int pdmpc_sweep_optimal_run(pdmpc_sweep* s, int32_t max_instances, int32_t n_steps, double* ms) {
+    return timed_steps(n_steps, ms, [&] { return pdmpc_sweep_optimal_step(s, max_instances); });
+}
+
+int pdmpc_sweep_optimal_last_calls(pdmpc_sweep* s, int32_t* calls2) {
+    if (!s || !calls2) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
+    std::copy(s->optimal_calls, s->optimal_calls + 2, calls2);
+    return PDMPC_OK;
 }
 
 }  // extern "C"

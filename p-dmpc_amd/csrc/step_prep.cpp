@@ -1,7 +1,7 @@
 // step_prep.cpp — the step-preparation calls of the C ABI: device work that runs once per time step before the searches are packed
 // (unique prioritizations, reachable-set coupling, lanelet bounding and the coupling on the bounded sets, future collision assessment).
 //
-// Every call but pdmpc_unique_priorities follows one recipe: carve ONE pinned staging block and ONE device workspace with the same
+// Every call but pdmpc_unique_priorities(_grouped) follows one recipe: carve ONE pinned staging block and ONE device workspace with the same
 // offsets (Carver), stage the inputs, copy them in once, launch between an event pair (timed_launch), copy the result back, synchronise.
 #include "handle.hpp"
 
@@ -88,27 +88,21 @@ size_t stage_groups(PairGroup* pg, int32_t n_groups, const int32_t* group_offset
     return block;
 }
 
-}  // namespace
-
-extern "C" {
-
-// Prioritizer.unique_priorities (Prioritizer.m:97-140) on the device: priority_kernel.hip.  The acyclic orientations are counted
+// ---- Prioritizer.unique_priorities (Prioritizer.m:97-140) on the device: priority_kernel.hip.  The acyclic orientations are counted
 // first; the true count K is reported whatever max_out is, and only a K that fits is written (never a truncated list).
-int pdmpc_unique_priorities(pdmpc_handle* h, int32_t n, const uint8_t* adjacency, int64_t max_out, int64_t* n_out, uint32_t* masks, int32_t* priorities) {
-    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
-    if (n_out) *n_out = -1;
-    if (n < 1 || !adjacency || !n_out || max_out < 0 || (max_out > 0 && (!masks || !priorities)))
-        return fail(PDMPC_ERR_INVALID, "pdmpc_unique_priorities: bad argument");
-    if (n > PDMPC_PRIO_MAX_N) return fail(PDMPC_ERR_CAPACITY, "pdmpc_unique_priorities: more than 64 vehicles");
-    PriorityArgs A;
-    std::memset(&A, 0, sizeof A);
-    A.n = n;
+// E of find(triu(adjacency, 1))
+int count_edges(int n, const uint8_t* adjacency) {
     int E = 0;
-    for (int c = 0; c < n; ++c)  // find(triu(adjacency, 1)): by column, then by row
+    for (int c = 0; c < n; ++c)
         for (int r = 0; r < c; ++r)
             if (adjacency[(size_t)r * n + c]) ++E;
-    if (E > PDMPC_PRIO_MAX_E) return fail(PDMPC_ERR_CAPACITY, "pdmpc_unique_priorities: more than 32 coupling edges");
-    for (int c = 0, e = 0; c < n; ++c)
+    return E;
+}
+// a graph within the limits (n <= PDMPC_PRIO_MAX_N, E <= PDMPC_PRIO_MAX_E) as the kernels read it -> its tiles
+int64_t stage_graph(PriorityArgs& A, int n, int E, const uint8_t* adjacency) {
+    std::memset(&A, 0, sizeof A);
+    A.n = n;
+    for (int c = 0, e = 0; c < n; ++c)  // find(triu(adjacency, 1)): by column, then by row
         for (int r = 0; r < c; ++r)
             if (adjacency[(size_t)r * n + c]) {
                 const uint32_t bit = 1u << (E - 1 - e);  // dec2bin(m, E): edge 1 is the most significant bit
@@ -121,31 +115,159 @@ int pdmpc_unique_priorities(pdmpc_handle* h, int32_t n, const uint8_t* adjacency
     A.E = E;
     A.all_edges = E == 32 ? 0xffffffffu : (1u << E) - 1u;
     A.n_masks = 1ull << E;
-    const int64_t n_tiles = (int64_t)((A.n_masks + PDMPC_PRIO_TILE - 1) / PDMPC_PRIO_TILE);
+    return (int64_t)((A.n_masks + PDMPC_PRIO_TILE - 1) / PDMPC_PRIO_TILE);
+}
+
+// PrioState::table and its pinned staging for M graphs
+struct PrioLayout {
+    size_t graph, tile_first, in_bytes, row_first, total;
+};
+PrioLayout prio_layout(int M) {
+    Carver c;
+    PrioLayout L;
+    L.graph = c.take<PriorityArgs>((size_t)M);
+    L.tile_first = c.take<int64_t>((size_t)M + 1);
+    L.in_bytes = c.at;  // (what the count pass needs: the first copy)
+    L.row_first = c.take<int64_t>((size_t)M + 1);
+    L.total = c.at;
+    return L;
+}
+
+// pdmpc_unique_priorities (grouped == false: M = 1, the graph in the kernel arguments) and its grouped sibling (the graphs and their
+// tile prefix staged in ONE copy): count, scan, ONE read-back of the count(s), the capacity rule, write, order, the lists copied out.
+// group_n / adjacency were checked by the entry points; edges[g] < 0 marks a graph outside the limits: it has no tiles and n_out -1.
+int enumerate_priorities(pdmpc_handle* h, const char* who, bool grouped, int32_t M, const int32_t* group_n, const uint8_t* const* adjacency, const int32_t* edges,
+                         const int64_t* max_out, int64_t* n_out, uint32_t* masks, int32_t* priorities) {
+    const std::string w(who);
     ON_DEVICE(h->cfg.device);
     PrioState& P = h->prio;
-    if (P.count.ensure((size_t)n_tiles) || P.off.ensure((size_t)n_tiles + 1))
-        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the tile counts of pdmpc_unique_priorities");
-    int lrc = pdmpc_launch_priority_count(&A, n_tiles, P.count.p, (void*)h->stream);
-    if (!lrc) lrc = pdmpc_launch_priority_scan(P.count.p, n_tiles, P.off.p, (void*)h->stream);
-    if (lrc) return fail(PDMPC_ERR_HIP, std::string("priority kernel launch failed: ") + hipGetErrorString((hipError_t)lrc));
-    int64_t K = 0;
-    HIPCHK(hipMemcpyAsync(&K, P.off.p + n_tiles, sizeof K, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(sync_stream(h));
-    *n_out = K;
-    if (K > max_out) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "pdmpc_unique_priorities: %lld unique prioritizations, max_out is %lld", (long long)K, (long long)max_out);
+    PriorityArgs one;
+    PriorityGroups G{};
+    const PrioLayout L = prio_layout(M);
+    int64_t* tile_first = nullptr;
+    int64_t n_tiles = 0;
+    bool outside = false;
+    if (grouped) {
+        if (P.h_table.ensure(L.total) || P.table.ensure(L.total) || P.group_off.ensure((size_t)M + 1) || P.h_group_off.ensure((size_t)M + 1))
+            return fail(PDMPC_ERR_HIP, "hipMalloc failed for the graph table of " + w);
+        PriorityArgs* graph = (PriorityArgs*)(P.h_table.p + L.graph);
+        tile_first = (int64_t*)(P.h_table.p + L.tile_first);
+        for (int g = 0; g < M; ++g) {
+            tile_first[g] = n_tiles;
+            n_out[g] = -1;
+            if (edges[g] < 0) {
+                std::memset(&graph[g], 0, sizeof graph[g]);
+                outside = true;
+            } else
+                n_tiles += stage_graph(graph[g], group_n[g], edges[g], adjacency[g]);
+        }
+        tile_first[M] = n_tiles;
+        if (n_tiles > PDMPC_PRIO_MAX_TILES) return fail(PDMPC_ERR_CAPACITY, w + ": the graphs have 2^24 or more tiles of PDMPC_PRIO_TILE orientations");
+        G.n_groups = M;
+        G.graph = (const PriorityArgs*)(P.table.p + L.graph);
+        G.tile_first = (const int64_t*)(P.table.p + L.tile_first);
+        G.mask_first = P.group_off.p;
+        G.row_first = (const int64_t*)(P.table.p + L.row_first);
+    } else
+        n_tiles = stage_graph(one, group_n[0], edges[0], adjacency[0]);
+    int64_t total = 0;
+    if (n_tiles > 0) {
+        if (P.count.ensure((size_t)n_tiles) || P.off.ensure((size_t)n_tiles + 1)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the tile counts of " + w);
+        int lrc;
+        if (grouped) {
+            HIPCHK(hipMemcpyAsync(P.table.p, P.h_table.p, L.in_bytes, hipMemcpyHostToDevice, h->stream));
+            lrc = pdmpc_launch_priority_count_grouped(&G, n_tiles, P.count.p, (void*)h->stream);
+        } else
+            lrc = pdmpc_launch_priority_count(&one, n_tiles, P.count.p, (void*)h->stream);
+        if (!lrc) lrc = pdmpc_launch_priority_scan(P.count.p, n_tiles, P.off.p, (void*)h->stream);
+        if (!lrc && grouped) lrc = pdmpc_launch_priority_group_offsets(&G, P.off.p, (void*)h->stream);
+        if (lrc) return fail(PDMPC_ERR_HIP, std::string("priority kernel launch failed: ") + hipGetErrorString((hipError_t)lrc));
+        if (grouped)
+            HIPCHK(hipMemcpyAsync(P.h_group_off.p, P.group_off.p, ((size_t)M + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+        else
+            HIPCHK(hipMemcpyAsync(&total, P.off.p + n_tiles, sizeof total, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(sync_stream(h));
+    }
+    int over = -1;  // the first graph with more unique prioritizations than its max_out
+    if (grouped) {
+        const int64_t* first = P.h_group_off.p;
+        for (int g = 0; g < M; ++g) {
+            if (edges[g] < 0) continue;
+            n_out[g] = first[g + 1] - first[g];
+            if (n_out[g] > max_out[g] && over < 0) over = g;
+        }
+        total = n_tiles > 0 ? first[M] : 0;
+    } else {
+        n_out[0] = total;
+        if (total > max_out[0]) over = 0;
+    }
+    if (over >= 0) {
+        char buf[200];
+        if (grouped)
+            snprintf(buf, sizeof buf, "%s: graph %d has %lld unique prioritizations, its max_out is %lld", who, over, (long long)n_out[over], (long long)max_out[over]);
+        else
+            snprintf(buf, sizeof buf, "%s: %lld unique prioritizations, max_out is %lld", who, (long long)total, (long long)max_out[0]);
         return fail(PDMPC_ERR_CAPACITY, buf);
     }
-    if (P.mask.ensure((size_t)K) || P.order.ensure((size_t)K * n)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the output of pdmpc_unique_priorities");
-    lrc = pdmpc_launch_priority_write(&A, n_tiles, P.off.p, K, P.mask.p, (void*)h->stream);
-    if (!lrc) lrc = pdmpc_launch_priority_order(&A, P.mask.p, K, P.order.p, (void*)h->stream);
+    if (outside) return fail(PDMPC_ERR_CAPACITY, w + ": a graph has more than 64 vehicles or more than 32 coupling edges");
+    int64_t rows = 0;  // entries of priorities
+    if (grouped) {
+        int64_t* row_first = (int64_t*)(P.h_table.p + L.row_first);
+        for (int g = 0; g < M; ++g) {
+            row_first[g] = rows;
+            rows += n_out[g] * group_n[g];
+        }
+        row_first[M] = rows;
+    } else
+        rows = total * group_n[0];
+    if (P.mask.ensure((size_t)total) || P.order.ensure((size_t)rows)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the output of " + w);
+    int lrc;
+    if (grouped) {
+        HIPCHK(hipMemcpyAsync(P.table.p + L.row_first, P.h_table.p + L.row_first, L.total - L.row_first, hipMemcpyHostToDevice, h->stream));
+        lrc = pdmpc_launch_priority_write_grouped(&G, n_tiles, P.off.p, total, P.mask.p, (void*)h->stream);
+        if (!lrc) lrc = pdmpc_launch_priority_order_grouped(&G, P.mask.p, total, P.order.p, (void*)h->stream);
+    } else {
+        lrc = pdmpc_launch_priority_write(&one, n_tiles, P.off.p, total, P.mask.p, (void*)h->stream);
+        if (!lrc) lrc = pdmpc_launch_priority_order(&one, P.mask.p, total, P.order.p, (void*)h->stream);
+    }
     if (lrc) return fail(PDMPC_ERR_HIP, std::string("priority kernel launch failed: ") + hipGetErrorString((hipError_t)lrc));
-    HIPCHK(hipMemcpyAsync(masks, P.mask.p, (size_t)K * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(priorities, P.order.p, (size_t)K * n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(masks, P.mask.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(priorities, P.order.p, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(sync_stream(h));
     return PDMPC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pdmpc_unique_priorities(pdmpc_handle* h, int32_t n, const uint8_t* adjacency, int64_t max_out, int64_t* n_out, uint32_t* masks, int32_t* priorities) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    if (n_out) *n_out = -1;
+    if (n < 1 || !adjacency || !n_out || max_out < 0 || (max_out > 0 && (!masks || !priorities)))
+        return fail(PDMPC_ERR_INVALID, "pdmpc_unique_priorities: bad argument");
+    if (n > PDMPC_PRIO_MAX_N) return fail(PDMPC_ERR_CAPACITY, "pdmpc_unique_priorities: more than 64 vehicles");
+    const int32_t E = count_edges(n, adjacency);
+    if (E > PDMPC_PRIO_MAX_E) return fail(PDMPC_ERR_CAPACITY, "pdmpc_unique_priorities: more than 32 coupling edges");
+    return enumerate_priorities(h, "pdmpc_unique_priorities", false, 1, &n, &adjacency, &E, &max_out, n_out, masks, priorities);
+}
+
+// ... of several graphs in one call: one staging copy, one launch per pass and one read-back of the counts, whatever the number of graphs
+int pdmpc_unique_priorities_grouped(pdmpc_handle* h, int32_t n_groups, const int32_t* group_n, const uint8_t** adjacency, int64_t* max_out, int64_t* n_out, uint32_t* masks,
+                                    int32_t* priorities) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    if (n_groups < 1 || !group_n || !adjacency || !max_out || !n_out) return fail(PDMPC_ERR_INVALID, "pdmpc_unique_priorities_grouped: bad argument");
+    for (int g = 0; g < n_groups; ++g) {
+        n_out[g] = -1;
+        if (group_n[g] < 1 || !adjacency[g] || max_out[g] < 0 || (max_out[g] > 0 && (!masks || !priorities)))
+            return fail(PDMPC_ERR_INVALID, "pdmpc_unique_priorities_grouped: bad argument for graph " + std::to_string(g));
+    }
+    std::vector<int32_t>& edges = h->prio.edges;
+    edges.resize((size_t)n_groups);
+    for (int g = 0; g < n_groups; ++g) {
+        edges[(size_t)g] = group_n[g] > PDMPC_PRIO_MAX_N ? -1 : count_edges(group_n[g], adjacency[g]);
+        if (edges[(size_t)g] > PDMPC_PRIO_MAX_E) edges[(size_t)g] = -1;
+    }
+    return enumerate_priorities(h, "pdmpc_unique_priorities_grouped", true, n_groups, group_n, adjacency, edges.data(), max_out, n_out, masks, priorities);
 }
 
 // ---- the reachable-set coupler on the device (reachable_kernel.hip)

@@ -30,9 +30,10 @@ class CapacityError(BackendError):
     """PDMPC_ERR_CAPACITY from pdmpc_unique_priorities(_host): `count` is the true number of unique prioritizations (-1 when the
     graph is outside the limits: more than 64 vehicles or 32 coupling edges)."""
 
-    def __init__(self, msg, count):
+    def __init__(self, msg, count, counts=None):
         super().__init__(msg)
         self.count = count
+        self.counts = [count] if counts is None else list(counts)  # of a grouped call: every graph's count
 
 
 ERR_CAPACITY = -4
@@ -60,6 +61,43 @@ def unique_priorities_call(adjacency, max_out, handle=None):
     _check(L, rc, what, last_error="pdmpc_last_error" if handle is not None else None)
     k = K.value
     return prio[: k * n].reshape(k, n).T.astype(np.int64), masks[:k].astype(np.int64)
+
+
+def unique_priorities_grouped_call(graphs, max_out, handle=None, masks_out=None, priorities_out=None):
+    """pdmpc_unique_priorities_grouped on `handle`'s device, or pdmpc_unique_priorities_grouped_host without one: every graph of
+    `graphs` in ONE call -> [(priorities n_g x K_g, masks [K_g])] per graph, as unique_priorities_call returns a graph's.  max_out: one
+    bound for all graphs or one per graph.  Raises CapacityError for PDMPC_ERR_CAPACITY: `counts` holds every graph's count (-1 outside
+    the limits), `count` the first that does not fit.  masks_out / priorities_out (tests): the arrays the call writes into."""
+    L = load_library()
+    As = [np.ascontiguousarray(np.asarray(a) != 0, dtype=np.uint8) for a in graphs]
+    M = len(As)
+    sizes = np.array([a.shape[0] for a in As], dtype=np.int32)
+    caps = np.full(M, max_out, dtype=np.int64) if np.isscalar(max_out) else np.ascontiguousarray(max_out, dtype=np.int64)
+    if caps.shape != (M,):
+        raise ValueError("max_out: one bound, or one per graph")
+    room = np.maximum(caps, 0)
+    masks = np.zeros(max(int(room.sum()), 1), dtype=np.uint32) if masks_out is None else masks_out
+    prio = np.zeros(max(int((room * sizes).sum()), 1), dtype=np.int32) if priorities_out is None else priorities_out
+    counts = np.zeros(max(M, 1), dtype=np.int64)
+    ptrs = (abi.c_uint8_p * max(M, 1))(*[abi.u8p(a) for a in As])
+    args = [M, abi.i32p(sizes), ptrs, caps.ctypes.data_as(C.POINTER(C.c_int64)), counts.ctypes.data_as(C.POINTER(C.c_int64)), abi.u32p(masks), abi.i32p(prio)]
+    if handle is not None:
+        rc = L.pdmpc_unique_priorities_grouped(handle.h, *args)
+        what = "pdmpc_unique_priorities_grouped"
+    else:
+        rc = L.pdmpc_unique_priorities_grouped_host(*args)
+        what = "pdmpc_unique_priorities_grouped_host"
+    if rc == ERR_CAPACITY:
+        got = [int(k) for k in counts[:M]]
+        bad = [k for k, cap in zip(got, caps) if k < 0 or k > cap]
+        raise CapacityError("%s: capacity (unique prioritizations %s, max_out %s)" % (what, got, caps.tolist()), bad[0] if bad else -1, got)
+    _check(L, rc, what, last_error="pdmpc_last_error" if handle is not None else "pdmpc_controller_last_error")
+    out, at, row = [], 0, 0
+    for n, k in zip(sizes.tolist(), counts[:M].tolist()):
+        out.append((prio[row : row + k * n].reshape(k, n).T.astype(np.int64), masks[at : at + k].astype(np.int64)))
+        at += k
+        row += k * n
+    return out
 
 
 def local_reachable_sets_native(mpa):
@@ -720,6 +758,10 @@ class Handle:
     def unique_priorities(self, adjacency, max_out):
         """Prioritizer.unique_priorities on this handle's device (pdmpc_unique_priorities) -> (priorities n x K, masks [K])."""
         return unique_priorities_call(adjacency, max_out, handle=self)
+
+    def unique_priorities_grouped(self, graphs, max_out, **out):
+        """... of several graphs in ONE call (pdmpc_unique_priorities_grouped) -> [(priorities n_g x K_g, masks [K_g])]."""
+        return unique_priorities_grouped_call(graphs, max_out, handle=self, **out)
 
     # ---- device-resident path ----
     def pack_batch(self, iters):

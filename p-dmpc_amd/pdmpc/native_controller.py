@@ -431,6 +431,60 @@ class NativeSweep:
         self._n_perm(n_perm)
         return ms
 
+    # ---- the optimal-priority step of a sweep
+    def _n_instances(self):
+        """every member's K after an optimal build or step -> the K per member"""
+        ks = []
+        for m in self.members:
+            n = C.c_int32()
+            m._check(self.L.pdmpc_controller_explore_problem(m.c, C.byref(n), None, None, None, None, None, None, None), "pdmpc_controller_explore_problem")
+            m.n_perm = n.value // m.n
+            ks.append(m.n_perm)
+        return ks
+
+    def optimal_build(self, max_instances):
+        """Every member's optimal-priority batch behind ONE enumeration of all members' coupling graphs -> K per member."""
+        self._check(self.L.pdmpc_sweep_optimal_build(self.s, max_instances), "pdmpc_sweep_optimal_build")
+        return self._n_instances()
+
+    def optimal_problem(self):
+        """The concatenated batch of the last optimal_build, decoded as explore_problem decodes the explorative one."""
+        n = C.c_int32()
+        vin = C.POINTER(abi.VehicleIn)()
+        po, pi, mem, inst, veh, lvl = (abi.c_int32_p() for _ in range(6))
+        fb = C.POINTER(abi.PolygonSet)()
+        self._check(self.L.pdmpc_sweep_optimal_problem(self.s, C.byref(n), C.byref(vin), C.byref(po), C.byref(pi), C.byref(fb), C.byref(mem), C.byref(inst), C.byref(veh),
+                                                       C.byref(lvl)), "pdmpc_sweep_optimal_problem")
+        iters, preds, fallback = self.members[0]._decode(n.value, vin, po, pi, fb)
+        col = lambda a: [int(a[q]) for q in range(n.value)]  # noqa: E731
+        return {"iters": iters, "preds": preds, "fallback": fallback, "member": col(mem), "instance": col(inst), "vehicle": col(veh), "levels": col(lvl)}
+
+    def optimal_apply(self, records):
+        """The records of every slot of the concatenated batch: the choice per member on the host, every member's apply."""
+        recs = np.ascontiguousarray(records)
+        want = sum(m.n * m.n_perm for m in self.members)
+        if recs.shape[0] != want:
+            raise ValueError("the optimal-priority batch of this sweep has %d slots, not %d" % (want, recs.shape[0]))
+        self._check(self.L.pdmpc_sweep_optimal_apply(self.s, abi.out_ptr(recs)), "pdmpc_sweep_optimal_apply")
+
+    def optimal_step(self, max_instances):
+        """One optimal-priority lock-step natively -> every member's kept (chosen) records in its own slot order."""
+        self._check(self.L.pdmpc_sweep_optimal_step(self.s, max_instances), "pdmpc_sweep_optimal_step")
+        self._n_instances()
+        return [m.records() for m in self.members]
+
+    def optimal_run(self, max_instances, n_steps):
+        """n_steps optimal-priority lock-steps in one native call -> wall-clock milliseconds of every lock-step."""
+        ms = _run(self._check, "pdmpc_sweep_optimal_run", self.L.pdmpc_sweep_optimal_run, self.s, max_instances, n_steps)
+        self._n_instances()
+        return ms
+
+    def optimal_calls(self):
+        """[enumeration calls of the last optimal build, launches of the searches of the last optimal_step] (pdmpc_sweep_optimal_last_calls)."""
+        calls = np.zeros(2, dtype=np.int32)
+        self._check(self.L.pdmpc_sweep_optimal_last_calls(self.s, abi.i32p(calls)), "pdmpc_sweep_optimal_last_calls")
+        return calls.tolist()
+
     def prep_calls(self):
         """The step-preparation calls of the last build, whatever the number of members (pdmpc_sweep_last_prep_calls): [lanelet
         bounding, coupler on the bounded sets, coupler on the plain hulls, future collision assessment]."""

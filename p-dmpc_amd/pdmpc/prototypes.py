@@ -26,6 +26,7 @@ FCA = [I32, I32, DP, DP, DP, DP, I32, IP, POLYS, POLYS, F64, F64, F64, IP, IP]
 FCA_GROUPED = [I32, P(abi.FcaGroup), I32, DP, DP, DP, DP, IP, IP]
 CHOSEN = [CHOICE, IP, DP]  # choice, chosen, cell_cost
 UNIQUE = [I32, BP, I64, P(I64), UP, IP]
+UNIQUE_GROUPED = [I32, IP, P(BP), P(I64), P(I64), UP, IP]  # n_groups, group_n, adjacency, max_out, n_out, masks, priorities
 
 PROTOTYPES = {
     # ---- life cycle
@@ -87,6 +88,8 @@ PROTOTYPES = {
     # ---- the unique prioritizations of a coupling graph
     "pdmpc_unique_priorities": (INT, [OBJ] + UNIQUE),
     "pdmpc_unique_priorities_host": (INT, UNIQUE),
+    "pdmpc_unique_priorities_grouped": (INT, [OBJ] + UNIQUE_GROUPED),
+    "pdmpc_unique_priorities_grouped_host": (INT, UNIQUE_GROUPED),
     # ---- reachable sets
     "pdmpc_local_reachable_sets": (INT, [MPA, I32, IP, DP, DP]),
     "pdmpc_upload_reachable_sets": (INT, [OBJ] + TABLE),
@@ -156,6 +159,12 @@ PROTOTYPES = {
     "pdmpc_sweep_explore_apply": (INT, [OBJ, VOUT]),
     "pdmpc_sweep_explore_step": (INT, [OBJ, I32]),
     "pdmpc_sweep_explore_run": (INT, [OBJ, I32, I32, DP]),
+    "pdmpc_sweep_optimal_build": (INT, [OBJ, I32]),
+    "pdmpc_sweep_optimal_problem": (INT, [OBJ] + STEP_OUT + [P(IP)] * 4),
+    "pdmpc_sweep_optimal_apply": (INT, [OBJ, VOUT]),
+    "pdmpc_sweep_optimal_step": (INT, [OBJ, I32]),
+    "pdmpc_sweep_optimal_run": (INT, [OBJ, I32, I32, DP]),
+    "pdmpc_sweep_optimal_last_calls": (INT, [OBJ, IP]),
     # ---- several GPUs behind the same boundary
     "pdmpc_group_create": (INT, [CONFIG, I32, IP, P(OBJ)]),
     "pdmpc_group_create_ex": (INT, [CONFIG, I32, IP, I32, P(OBJ)]),

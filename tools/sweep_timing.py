@@ -4,7 +4,10 @@ another by the parent commit's library.
 Workload: M in {1, 2, 4, 8} C2-like members (20 vehicles, Hp 8, seeds 1 .. M) on one handle, steps 21-40 of each closed loop, with
   (a) distance coupling,
   (b) reachable-set coupling with lanelet bounding,
-  (c) distance coupling, FCA priorities.
+  (c) distance coupling, FCA priorities,
+  (d) the optimal-priority step (pdmpc_sweep_optimal_run): M road-network members of 6 vehicles at Hp 6 (seeds 1 .. M, distance coupling,
+      max_instances 600), and M circle members of 4 vehicles at Hp 5 (full coupling, K = 24), steps 4-15; the baseline steps every member
+      with pdmpc_controller_optimal_run(max_instances, 1).
 Sweep: the median wall time per lock-step of pdmpc_sweep_run and the six parts of pdmpc_sweep_last_timing.
 Baseline: a built checkout of the parent commit in a directory of its own (--baseline-root: its p-dmpc_amd/pdmpc package and its
 p-dmpc_amd/csrc/libpdmpc_hip.so); per lock-step every member takes one pdmpc_controller_run(1), the lock-step's time is their sum.
@@ -14,7 +17,7 @@ Five alternating runs of baseline and sweep, each in a fresh process; reported a
 (max - min).  For (b) also one grouped device call (pdmpc_bound_reachable_sets on all members' vehicles + pdmpc_bounded_set_coupling_grouped)
 against M ungrouped pairs of calls on the members' recorded states, in kernel time (HIP events) and as whole calls.
 
-    python tools/sweep_timing.py --baseline-root DIR [--rounds 5] [--modes a,b,c] [--out profiles/sweep_timing.txt]
+    python tools/sweep_timing.py --baseline-root DIR [--rounds 5] [--modes a,b,c,d] [--out profiles/sweep_timing.txt]
 """
 import argparse
 import json
@@ -27,6 +30,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MS = (1, 2, 4, 8)
 MODES = {"a": dict(coupling="distance"), "b": dict(coupling="reachable_set", bound_reachable_sets=True), "c": dict(coupling="distance", priority_strategy="fca")}
 TITLES = {"a": "distance coupling", "b": "reachable-set coupling with lanelet bounding", "c": "distance coupling, FCA priorities"}
+OPTIMAL = {"road": dict(amount=6, Hp=6, max_instances=600, coupling="distance"), "circle": dict(amount=4, Hp=5, max_instances=24, coupling="full")}  # (d)
+OPTIMAL_WARMUP, OPTIMAL_TIMED = 3, 12
 SWEEP_BASELINE = ("c",)  # the modes whose baseline is the parent's library stepping the same sweep
 PARTS = ("build", "pack", "enqueue", "wait_and_read_back", "choose", "apply")
 WARMUP, TIMED = 20, 20
@@ -51,12 +56,61 @@ def members_on_one_handle(M, mode):
     return options, mpa, h, scs, [NativeController(options, sc, mpa, h, coupling=coupling, **ctl) for sc in scs]
 
 
+def optimal_members(M, which):
+    """(d): M optimal-priority members on one handle that holds every member's batch"""
+    from pdmpc.backend import Handle
+    from pdmpc.config import Config, ScenarioType
+    from pdmpc.mpa import get_mpa
+    from pdmpc.native_controller import NativeController
+    from pdmpc.road_network import commonroad_scenario
+    from pdmpc.scenario import circle_scenario
+
+    o = OPTIMAL[which]
+    road = which == "road"
+    options = Config(scenario_type=ScenarioType.commonroad if road else ScenarioType.circle, amount=o["amount"], Hp=o["Hp"],
+                     max_vehicles=o["amount"] * o["max_instances"] * M, max_nodes=1 << 12)
+    mpa = get_mpa(options)
+    h = Handle(options)
+    h.upload_mpa(mpa)
+    scs = [commonroad_scenario(options, seed=s) if road else circle_scenario(options) for s in range(1, M + 1)]
+    return h, [NativeController(options, sc, mpa, h, coupling=o["coupling"]) for sc in scs], o["max_instances"]
+
+
+def optimal_worker(kind, out):
+    """(d) on the tree this process imports: the parent's library steps every member alone, this one's steps the sweep"""
+    import numpy as np
+
+    for which in OPTIMAL:
+        for M in MS:
+            h, cs, K = optimal_members(M, which)
+            if kind == "baseline":
+                ms = [sum(float(c.optimal_run(K, 1)[0]) for c in cs) for _ in range(OPTIMAL_WARMUP + OPTIMAL_TIMED)][OPTIMAL_WARMUP:]
+                out["d%s%d" % (which, M)] = {"median": float(np.median(ms))}
+            else:
+                from pdmpc.native_controller import NativeSweep
+
+                sweep = NativeSweep(cs, h)
+                sweep.optimal_run(K, OPTIMAL_WARMUP)
+                ms, parts = [], []
+                for _ in range(OPTIMAL_TIMED):
+                    ms.append(float(sweep.optimal_run(K, 1)[0]))
+                    t = sweep.last_timing()
+                    parts.append([t[p] for p in PARTS])
+                out["d%s%d" % (which, M)] = {"median": float(np.median(ms)), "parts": [float(x) for x in np.median(np.array(parts), axis=0)]}
+                sweep.close()
+            for c in cs:
+                c.close()
+            h.close()
+
+
 def worker(kind, modes):
     """One run: every mode and M on the tree this process imports -> one JSON line."""
     import numpy as np
 
     out = {}
-    for mode in modes:
+    if "d" in modes:
+        optimal_worker(kind, out)
+    for mode in [m for m in modes if m != "d"]:
         for M in MS:
             options, mpa, h, scs, cs = members_on_one_handle(M, mode)
             if kind == "baseline" and mode not in SWEEP_BASELINE:
@@ -149,10 +203,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sweep_timing.txt"))
-    ap.add_argument("--modes", default=",".join(MODES))
+    ap.add_argument("--modes", default=",".join(list(MODES) + ["d"]))
     ap.add_argument("--worker")
     args = ap.parse_args()
-    modes = [m for m in MODES if m in args.modes.split(",")]
+    modes = [m for m in list(MODES) + ["d"] if m in args.modes.split(",")]
     if args.worker:
         tree = os.environ.get("PDMPC_TREE", ROOT)
         sys.path[:0] = [tree, os.path.join(tree, "p-dmpc_amd")]
@@ -174,10 +228,16 @@ def main():
     lines = ["sweep against the parent commit's library: M C2-like members (20 vehicles, Hp 8, seeds 1..M), steps %d-%d, ms per lock-step;"
              % (WARMUP + 1, WARMUP + TIMED),
              "median and spread (max - min) of %d alternating runs' medians; baseline = sum of the members' pdmpc_controller_run(1) unless a block says otherwise" % args.rounds]
-    for mode in modes:
-        lines.append("(%s) %s" % (mode, TITLES[mode]) + ("; baseline = the parent commit's library stepping the same sweep" if mode in SWEEP_BASELINE else ""))
+    blocks = [(m, "%s%%d" % m, "(%s) %s" % (m, TITLES[m])) for m in modes if m != "d"]
+    if "d" in modes:
+        lines_d = {"road": "(d) optimal-priority step: road-network members of 6 vehicles, Hp 6, max_instances 600",
+                   "circle": "(d) optimal-priority step: circle members of 4 vehicles, Hp 5, K = 24"}
+        blocks += [("d", "d%s%%d" % w, lines_d[w] + "; steps %d-%d; baseline = sum of the members' pdmpc_controller_optimal_run(max_instances, 1)"
+                    % (OPTIMAL_WARMUP + 1, OPTIMAL_WARMUP + OPTIMAL_TIMED)) for w in OPTIMAL]
+    for mode, key_of, title in blocks:
+        lines.append(title + ("; baseline = the parent commit's library stepping the same sweep" if mode in SWEEP_BASELINE else ""))
         for M in MS:
-            key = "%s%d" % (mode, M)
+            key = key_of % M
             b = [r[key]["median"] for r in base]
             s = [r[key]["median"] for r in sweep]
             mb, ms_, sb, ss = float(np.median(b)), float(np.median(s)), max(b) - min(b), max(s) - min(s)
