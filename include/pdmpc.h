@@ -442,7 +442,7 @@ int pdmpc_plan_joint(pdmpc_handle* handle, int32_t n_problems, const int32_t* pr
  * (toposort(..., 'Order', 'stable')).  *n_out = K, the number of acyclic orientations, whatever max_out is (-1 for a graph outside
  * the limits).  PDMPC_ERR_CAPACITY without a launch for n > 64 or E > 32, and PDMPC_ERR_CAPACITY with nothing written for K > max_out:
  * the list is never truncated.  pdmpc_unique_priorities runs on the handle's device (csrc/priority_kernel.hip);
- * pdmpc_unique_priorities_host is its C++ twin and checker (csrc/step_controller.cpp, no GPU needed). */
+ * pdmpc_unique_priorities_host is its C++ twin and checker (csrc/step_priorities.hpp behind csrc/step_controller.cpp, no GPU needed). */
 int pdmpc_unique_priorities(pdmpc_handle* handle, int32_t n, const uint8_t* adjacency, int64_t max_out, int64_t* n_out, uint32_t* masks,
                             int32_t* priorities);
 int pdmpc_unique_priorities_host(int32_t n, const uint8_t* adjacency, int64_t max_out, int64_t* n_out, uint32_t* masks, int32_t* priorities);
@@ -563,7 +563,7 @@ int pdmpc_fca_collisions_grouped(pdmpc_handle* handle, int32_t n_groups, const p
 int pdmpc_fca_collisions_grouped_host(int32_t n_groups, const pdmpc_fca_group* groups, int32_t Hp, const double* x, const double* y, const double* cos_yaw,
                                       const double* sin_yaw, int32_t* collisions, int32_t* priorities);
 
-/* ---- the caller's side of the boundary, natively (csrc/step_controller.cpp) ----
+/* ---- the caller's side of the boundary, natively (csrc/step_controller.cpp and its stages csrc/step_*.hpp) ----
  * One MPC time step of the prioritized sequential controller around pdmpc_plan_step, without any interpreter in the loop:
  * traffic info, coupling, priorities, grouping, computation levels, obstacle assembly, ONE launch, exhaustion handling,
  * fallbacks, plant update (HighLevelController.main_control_loop, hlc/controller/HighLevelController.m:334-373;
@@ -716,7 +716,7 @@ int pdmpc_controller_priorities(pdmpc_controller* c, int32_t* n_priorities, cons
  * the same byte for byte.  Default off; nothing changes for a controller without a handle. */
 int pdmpc_controller_set_device_choice(pdmpc_controller* c, int32_t on);
 
-/* ---- several closed loops in lock-step (csrc/step_controller.cpp) ----
+/* ---- several closed loops in lock-step (csrc/step_controller.cpp, the end of the file) ----
  * A sweep borrows n_members controllers that were created on the same handle (or all without one) and steps them together: every
  * member's build_step, with the device's step preparation grouped over the members (pdmpc_bound_reachable_sets on the concatenated
  * vehicles, pdmpc_*_coupling_grouped: a pair of two members is never looked at; pdmpc_fca_collisions_grouped for the members with FCA

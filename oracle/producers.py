@@ -1,7 +1,7 @@
 """Independent restatement of the reference's INPUT PRODUCERS.  TEST INFRASTRUCTURE ONLY.
 
 The product builds the optimizer's per-step inputs twice (p-dmpc_amd/pdmpc/{reference_trajectory,road_network,controller}.py
-and csrc/step_controller.cpp), both by the same hand.  This file is a third statement of the same reference functions, written
+and csrc/step_inputs.hpp, a stage of csrc/step_controller.cpp), both by the same hand.  This file is a third statement of the same reference functions, written
 from the .m files alone, in MATLAB's own array style (whole-array expressions, 1-based indices carried as such, cells as lists)
 rather than the scalar loops of the product, so that a misreading of the reference on the product's side shows up as a
 difference in tests/test_oracle_producers.py instead of being copied along:

@@ -1,873 +1,33 @@
 // step_controller.cpp — the caller's side of the optimizer boundary, natively: one MPC time step of the prioritized
 // sequential controller around pdmpc_plan_step.  Host code only (no device code in this file).
 //
-// What it restates (file:line relative to the reference root), the C++ twin of p-dmpc_amd/pdmpc/controller.py:
-//   traffic info per step     HighLevelController.update_controlled_vehicles_traffic_info (hlc/controller/HighLevelController.m:167-270)
-//   trim from measurement     MotionPrimitiveAutomaton.trim_from_values (hlc/model/motion_primitive_automaton/MotionPrimitiveAutomaton.m:193-236)
-//   occupied areas            hlc/controller/common/get_occupied_areas.m:21-31, utility/translate_global.m:19-22
-//   reference trajectory      hlc/controller/common/get_reference_trajectory.m:27-46, sample_reference_trajectory.m:1-99,
-//                             get_arc_distance_to_endpoint.m:39-114, projection_2d.m:14-42
-//   predicted lanelets        hlc/controller/common/get_predicted_lanelets.m:25-62, get_lanelets_boundary.m:18-68
-//   coupling                  Coupler.m:31-32 (full), DistanceCoupler.m:15-50 (distance), ReachableSetCoupler.m:5-56 (reachable sets,
-//                             reachable_sets.cpp / reachable_kernel.hip)
-//   priorities -> DAG         ConstantPrioritizer.m:14-20, Prioritizer.m:36-77, ColoringPrioritizer.m:11-131, RandomPrioritizer.m:15-25,
-//                             FcaPrioritizer.m:11-92 (fca.cpp / fca_kernel.hip)
-//   grouping                  PrioritizedController.group (hlc/controller/prioritized/PrioritizedController.m:375-389),
-//                             weight/DistanceWeigher.m:12-39, weight/ConstantWeigher.m:15-17, weight/RandomWeigher.m:13-21,
-//                             cut/GreedyCutter.m:5-86
-//   computation levels        utility/kahn.m:1-24
-//   obstacle assembly         PrioritizedController.plan / consider_predecessors / consider_successors (:297-324, 449-566)
+// What it restates (file:line relative to the reference root), the C++ twin of p-dmpc_amd/pdmpc/controller.py, in stages, each a header
+// that names only the ones before it and says at its head what it restates (`make host-parts` compiles each alone):
+// step_types.hpp (the records), step_inputs.hpp (what a step reads of the traffic), step_priorities.hpp (couplings -> a prioritization),
+// step_state.hpp (the controller as the parts that are written together), step_assembly.hpp (a member's StepProblem), step_batch.hpp (the
+// batches of prioritizations and the choice among their plans).  This file: the step preparation over a span of members (build_members),
+// planning a built problem (plan_built), the steps and their loops, the sweep, every entry point of the C ABI, and
 //   exhaustion, fallbacks     handle_graph_search_exhaustion / plan_fallback (:568-616, 678-718), check_others_fallback (:623-676),
 //                             HighLevelController.handle_others_fallback (HighLevelController.m:449-463)
 //   plant                     Simulation.apply (plant/Simulation.m:86-100)
 // Every floating-point expression keeps the order of the Python twin (which keeps the reference's), and both call the
 // same libm, so the step problems the two build are bit-identical (tests/test_native_controller.py).
-//
-// Two records and one path.  A StepProblem is what pdmpc_plan_step takes -- inputs, fallbacks, predecessor slots --
-// with its seeds and weights, wherever it lives: a controller's step, each kept instance, its flattened batch, a sweep's concatenated
-// step and batch; the per-slot tags (instance, vehicle, level, member, member_slot) are plain vectors next to it.  An Instance is a
-// prioritization (both coupling matrices, levels, slot order): the controller's own (c->pri) and every kept one.  build_members prepares
-// the step of a span of members -- the device calls or their host twins, grouped by member, the only fork on the handle and the only
-// capacity retry -- between the per-member halves begin_step and finish_step (pdmpc_controller_build_step: M = 1, in the controller's
-// own scratch); plan_built plans a StepProblem (weights, seeds, the backend call, timing[1..3]); timed_steps is the loop of every *_run.
 #include <algorithm>
 #include <cassert>
 #include <chrono>
-#include <cmath>
 #include <cstdint>
-#include <cstring>
-#include <limits>
 #include <string>
-#include <utility>
-#include <memory>
 #include <vector>
 
 #include "../../include/pdmpc.h"
-#include "../../include/pdmpc_geometry.h"
-#include "mt19937ar.hpp"
+#include "step_types.hpp"  // the stages, in their order
+#include "step_inputs.hpp"
+#include "step_priorities.hpp"
+#include "step_state.hpp"
+#include "step_assembly.hpp"
+#include "step_batch.hpp"
 
 namespace {
-
-struct Poly {  // 2 x V, MATLAB [x; y]
-    std::vector<double> x, y;
-    int n() const { return (int)x.size(); }
-};
-
-// (offsets, x, y) vectors viewed as a polygon set of off.size() - 1 polygons (no copy: the vectors outlive the view)
-pdmpc_polygon_set view_polygons(const std::vector<int32_t>& off, const std::vector<double>& x, const std::vector<double>& y) {
-    pdmpc_polygon_set ps;
-    ps.n_polygons = (int32_t)off.size() - 1;
-    ps.offset = off.data();
-    ps.x = x.data();
-    ps.y = y.data();
-    return ps;
-}
-
-// the non-zero entries of a matrix as lists: by row (idx[off[i] .. off[i + 1]) = the columns of row i) or by column (the rows of
-// column j), ascending in both forms
-struct Lists {
-    std::vector<int32_t> off, idx, fill;  // (fill: scratch of lists_by_column)
-    int size(int i) const { return off[i + 1] - off[i]; }
-    const int32_t* begin(int i) const { return idx.data() + off[i]; }
-    const int32_t* end(int i) const { return idx.data() + off[i + 1]; }
-};
-
-struct Plan {  // what the controller keeps of a vehicle's ControlResultsInfo (ControlResultsInfo.m:5-17)
-    bool present = false;
-    bool needs_fallback = false;
-    bool exhausted = false;
-    std::vector<Poly> shapes;         // Hp
-    std::vector<int32_t> trims;       // Hp
-    std::vector<double> yx, yy, yyaw; // Hp
-    int32_t n_expanded = 0;
-};
-
-struct VehicleDef {
-    double x_start, y_start, yaw_start, reference_speed;
-    std::vector<double> px, py;             // reference path
-    std::vector<int32_t> lanelets_index;    // 1-based lanelet ids along the loop (empty: no lanelets, circle scenario)
-    std::vector<int32_t> points_index;      // 1-based index of the last path point of each of those lanelets
-    bool is_loop;
-    double tile_dx, tile_dy;
-};
-
-// A step problem in the C ABI's form (what pdmpc_plan_step takes; the polygon sets its entries point to live in the arena of the
-// controller that built them), with the sampled optimizer's seed and the expected work per slot.  One record wherever a problem lives.
-struct StepProblem {
-    std::vector<pdmpc_vehicle_in> in;
-    std::vector<pdmpc_polygon_set> fb;  // per slot: what its vehicle publishes if its search is exhausted
-    std::vector<int32_t> pred_offset, pred_index;
-    std::vector<uint32_t> seeds;   // time_step + vehicle_index (set_seeds; empty for a kept instance, which is never planned by itself)
-    std::vector<double> weights;   // plan_built's scratch
-    int n() const { return (int)in.size(); }
-    // a backend call on the problem: call(h, n_slots, in, pred_offset, pred_index, fallback, rest ...)
-    template <class Call, class... Rest>
-    int plan(Call call, pdmpc_handle* h, Rest... rest) const {
-        return call(h, n(), in.data(), pred_offset.data(), pred_index.data(), fb.data(), rest...);
-    }
-};
-// ... and the same five as every *_problem entry point hands them out
-void expose(const StepProblem& P, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index, const pdmpc_polygon_set** fallback) {
-    if (n_slots) *n_slots = P.n();
-    if (in) *in = P.in.data();
-    if (pred_offset) *pred_offset = P.pred_offset.data();
-    if (pred_index) *pred_index = P.pred_index.data();
-    if (fallback) *fallback = P.fb.data();
-}
-
-// A prioritization of the step's traffic state: the controller's own, and every instance of an explorative or optimal-priority batch
-struct Instance {
-    std::vector<uint8_t> directed, directed_seq;  // n x n row-major
-    std::vector<int32_t> levels, order, slot_of;
-    void take_couplings(const Instance& of) {
-        directed = of.directed;
-        directed_seq = of.directed_seq;
-    }
-};
-
-// A choice among the plans of a batch as pdmpc_choose_host / pdmpc_plan_step_chosen take it (pdmpc_choice): the lists, kept from step to step
-struct ChoiceLists {
-    std::vector<int32_t> cell_offset, cell_slot, graph_offset, pick_graph, pick_offset, pick_slot;
-    std::vector<int32_t> graph_of;  // the explorative choice: per vehicle its sub-graph
-    int n_cells() const { return cell_offset.empty() ? 0 : (int)cell_offset.size() - 1; }
-    int n_graphs() const { return graph_offset.empty() ? 0 : (int)graph_offset.size() - 1; }
-    int n_picks() const { return (int)pick_graph.size(); }
-    void clear_picks() {
-        pick_graph.clear();
-        pick_slot.clear();
-        pick_offset.assign(1, 0);
-    }
-    pdmpc_choice view() const {
-        pdmpc_choice ch{};
-        ch.n_cells = n_cells();
-        ch.n_graphs = n_graphs();
-        ch.n_picks = n_picks();
-        ch.cell_offset = cell_offset.data();
-        ch.cell_slot = cell_slot.data();
-        ch.graph_offset = graph_offset.data();
-        ch.pick_graph = pick_graph.data();
-        ch.pick_offset = pick_offset.data();
-        ch.pick_slot = pick_slot.data();
-        return ch;
-    }
-};
-
-// What a member's step reads of the reachable sets (begin_step), and the scratch of ONE step preparation over a span of members
-// (build_members): a sweep owns one for its members, a controller one for the steps it takes alone.
-struct StepPrep {
-    bool reach_parallel = false, reach = false, bounded = false;
-};
-struct PrepScratch {
-    std::vector<StepPrep> prep;            // per member
-    int32_t prep_calls[4] = {0, 0, 0, 0};  // of the last build: lanelet bounding, bounded coupling, hull coupling, collision assessment
-    // one grouped bounding / coupler call: the vehicles of the members that take part, member after member
-    struct Call {
-        std::vector<int> who;                // members
-        std::vector<int32_t> group_offset;   // [who.size() + 1]
-        std::vector<double> x, y, cos_yaw, sin_yaw;
-        std::vector<int32_t> trim, lan_off, set_off;
-        std::vector<double> lan_x, lan_y, set_x, set_y;
-        std::vector<uint8_t> adjacency;      // the blocks
-    } call;
-    // the grouped collision assessment: the FCA members' reference points, member after member, and what it returns
-    struct Fca {
-        std::vector<pdmpc_fca_group> groups;
-        std::vector<pdmpc_polygon_set> obstacles;  // [groups.size()] views of the members' scenario obstacles
-        std::vector<double> x, y, cos_yaw, sin_yaw;
-        std::vector<int32_t> collisions, priorities;
-    } fca;
-    // the grouped enumeration of an optimal-priority step: the members' coupling graphs, and their lists one after the other
-    struct Prio {
-        int32_t calls = 0;  // enumeration calls of the last build
-        std::vector<int32_t> group_n;
-        std::vector<const uint8_t*> adjacency;
-        std::vector<int64_t> max_out, n_out;
-        std::vector<uint32_t> masks;
-        std::vector<int32_t> priorities;
-    } prio;
-};
-// the batch of prioritizations build_members puts behind every member's step: none, the explorative one (n_perm > 0) or the
-// optimal-priority one (max_instances > 0)
-struct BatchKind {
-    int n_perm = 0, max_instances = 0;
-};
-
-}  // namespace
-
-struct pdmpc_controller {
-    pdmpc_handle* h = nullptr;
-    pdmpc_controller_config cfg{};
-    int n = 0, Hp = 0;
-    std::vector<VehicleDef> veh;
-    std::vector<Poly> bl_left, bl_right;  // per lanelet boundary polylines (RoadDataCommonRoad.get_lanelet_boundary)
-    std::vector<Poly> static_obstacles;
-    std::vector<double> trim_speed, trim_steering;
-    // state
-    int k = 0;
-    std::vector<double> mx, my, myaw, mspeed, msteer;  // measurements
-    std::vector<Plan> info_old, infos;
-    bool follow_own = false;                // the explorative step applies the plans of the controller's OWN prioritization (instance 0) whatever the choice: the traffic then follows pdmpc_controller_step's closed loop (measurement: the same steps as a recorded replay)
-    bool lean_explore = false;              // the explorative step reads back status + final cost of every plan and the chosen plans' records only
-    bool device_choice = false;             // pdmpc_controller_set_device_choice: the lean step chooses and gathers on the device (pdmpc_plan_step_chosen)
-    std::vector<int32_t> x_status;
-    std::vector<double> x_final_cost;
-    ChoiceLists choice;                     // the choice of the last explorative / optimal-priority step as data, and what came back for it:
-    std::vector<int32_t> choice_chosen;     // [graphs] the candidate every graph chose
-    std::vector<double> choice_cost;        // [cells]
-    double timing[6] = {0, 0, 0, 0, 0, 0};  // pdmpc_controller_last_timing
-    double timing_sum[6] = {0, 0, 0, 0, 0, 0};  // ... summed over the steps since the last pdmpc_controller_timing_sum(reset)
-    int64_t timing_steps = 0;
-    std::vector<double> last_pops;  // per vehicle: nodes its search popped in the last step (the next step's expected work, pdmpc_set_step_weights)
-    int optimizer = PDMPC_OPTIMIZER_GRAPH_SEARCH;  // pdmpc_controller_set_optimizer
-    // per step
-    std::vector<int32_t> trims;
-    std::vector<Poly> occ_offset, occ_plain;
-    std::vector<std::vector<double>> ref_x, ref_y, v_ref;
-    std::vector<Poly> bnd_left, bnd_right;
-    std::vector<uint8_t> adjacency;  // n x n row-major
-    Instance pri;                    // the controller's own prioritization (after a choice: every vehicle's row of its chosen instance's couplings)
-    StepProblem prob;                // ... and its step problem; the arena keeps the pointed-to data alive
-    // the arrays of the step's polygon sets: chunks that are kept from step to step and handed out front to back (a set's arrays
-    // never move; build_step starts over at the first chunk)
-    struct Arena {
-        struct Chunk {
-            std::unique_ptr<double[]> mem;  // (doubles: 8-byte alignment for both kinds of arrays)
-            size_t cap = 0;
-        };
-        std::vector<Chunk> chunks;
-        size_t cur = 0, used = 0;
-        void reset() { cur = used = 0; }
-        void* take(size_t bytes) {
-            const size_t need = (bytes + 7) / 8;
-            while (cur < chunks.size() && used + need > chunks[cur].cap) {
-                ++cur;
-                used = 0;
-            }
-            if (cur == chunks.size()) {
-                Chunk ch;
-                ch.cap = std::max(need, (size_t)1 << 17);
-                ch.mem.reset(new double[ch.cap]);
-                chunks.push_back(std::move(ch));
-                used = 0;
-            }
-            void* p = chunks[cur].mem.get() + used;
-            used += need;
-            return p;
-        }
-    } arena;
-    std::vector<int32_t> sb_off;  // SetBuilder's scratch (one builder at a time)
-    std::vector<double> sb_x, sb_y;
-    std::vector<pdmpc_vehicle_out> out;
-    // sets that do not depend on the prioritization are built once per time step and shared by the prioritizations of an explorative step
-    std::vector<pdmpc_polygon_set> fb_of;
-    std::vector<uint8_t> fb_done;
-    // obstacle sets of a vehicle by who contributes to them (a function of the vehicle and of those lists alone): the prioritizations
-    // of an explorative step differ in a few couplings, so most of their vehicles share their sets — one build, one pointer, and
-    // pdmpc_pack_step packs a set it has seen under the same pointer once (pack.cpp: pack_common)
-    struct MemoKey {  // who contributes, as bit masks over the vehicles (up to 512: larger scenarios build every set)
-        uint64_t w[16];
-    };
-    struct Memo {  // a vehicle's sets built so far this step, by key (a handful: searched front to back)
-        std::vector<MemoKey> keys;
-        std::vector<pdmpc_polygon_set> sets;
-        const pdmpc_polygon_set* find(const MemoKey& k) const {
-            for (size_t q = 0; q < keys.size(); ++q)
-                if (std::memcmp(keys[q].w, k.w, sizeof k.w) == 0) return &sets[q];
-            return nullptr;
-        }
-        void clear() {
-            keys.clear();
-            sets.clear();
-        }
-    };
-    std::vector<Memo> obst_memo, dyn_memo;
-    Lists ls_dir_succ, ls_dir_pred, ls_seq_succ, ls_seq_pred;  // assemble_step's scratch (kept: no allocation per prioritization)
-    std::vector<int> kahn_indeg, kahn_cur, kahn_next;
-    pdmpc_polygon_set empty_set{};
-    bool empty_done = false;
-    bool exploring = false;  // an explorative step is being built: its prioritizations share sets through the memos
-    // explorative step (PrioritizedExplorativeController): the prioritizations of the current traffic state, flattened
-    std::vector<Instance> inst;
-    std::vector<StepProblem> inst_prob;  // an instance's step problem as assemble_step left it (kept from step to step: no allocation once warm)
-    StepProblem x_prob;                  // the flattened batch, and per slot of it:
-    std::vector<int32_t> x_instance, x_vehicle, x_level;
-    std::vector<int32_t> x_slot;         // x_slot[p * n + vehicle] = slot in the flattened batch
-    bool batch_built_last = false;       // pdmpc_controller_seeds: the seeds of x_prob (else of prob), whichever was built last
-    std::vector<pdmpc_vehicle_out> x_out;
-    std::vector<int32_t> x_chosen;  // per vehicle: the instance its sub-graph chose
-    std::vector<double> x_cost;     // n_perm x n_graphs (the optimal step: n x K, row v = vehicle v's sums)
-    int x_graphs = 0;
-    // optimal-priority step (PrioritizedOptimalController): the unique prioritizations of the step's coupling graph
-    std::vector<uint32_t> o_masks;  // [K] the acyclic orientations (pdmpc_unique_priorities)
-    std::vector<int32_t> o_prio;    // [K x n] their priorities
-    // reachable sets (pdmpc_controller_set_reachability): the automaton's local hulls, polygon trim * Hp + k, and per
-    // step every vehicle's Hp sets at its pose, closed (HighLevelController.m:219-263)
-    int parallel_mode = PDMPC_PARALLEL_PREVIOUS_TRAJECTORY;
-    bool has_reach = false;
-    std::vector<int32_t> reach_off;
-    std::vector<double> reach_x, reach_y;
-    std::vector<std::vector<Poly>> reach_sets;
-    std::vector<double> reach_cos, reach_sin;
-    // lanelet bounding of those sets (pdmpc_controller_set_lanelet_bounding): the raw lanelet polygons and the bounded sets of the step
-    bool lanelet_bounding = false;
-    std::vector<int32_t> bound_off, lan_off;
-    std::vector<double> bound_x, bound_y, lan_x, lan_y;
-    // priorities of the random and FCA strategies (1-based per vehicle) and the FCA inputs of the step: every reference point with the
-    // cos / sin of its calculate_yaw heading, the coupled pairs a < b, the scenario's obstacles as one polygon set
-    std::vector<int32_t> prio, fca_pairs, fca_count, fca_obst_off;
-    std::vector<double> fca_x, fca_y, fca_cos, fca_sin, fca_obst_x, fca_obst_y;
-    PrepScratch prep;  // of the steps the controller builds alone (as a member of a sweep it is prepared in the sweep's)
-    std::string err;
-};
-
-namespace {
-
-thread_local std::string g_cerr;
-
-inline uint8_t& at(std::vector<uint8_t>& m, int n, int i, int j) { return m[(size_t)i * n + j]; }
-inline uint8_t at(const std::vector<uint8_t>& m, int n, int i, int j) { return m[(size_t)i * n + j]; }
-
-// f(j) for the non-zero entries j of a matrix row, ascending.  Rows of the coupling matrices are mostly zero (a vehicle is coupled with
-// the few around it): eight entries per test.
-template <class F>
-inline void for_each_set(const uint8_t* row, int n, F&& f) {
-    int j = 0;
-    for (; j + 8 <= n; j += 8) {
-        uint64_t w;
-        std::memcpy(&w, row + j, 8);
-        if (w == 0) continue;
-        for (int q = 0; q < 8; ++q)
-            if (row[j + q]) f(j + q);
-    }
-    for (; j < n; ++j)
-        if (row[j]) f(j);
-}
-
-void lists_by_row(const std::vector<uint8_t>& M, int n, Lists& L) {
-    L.off.assign((size_t)n + 1, 0);
-    L.idx.clear();
-    for (int i = 0; i < n; ++i) {
-        for_each_set(M.data() + (size_t)i * n, n, [&](int j) { L.idx.push_back(j); });
-        L.off[i + 1] = (int32_t)L.idx.size();
-    }
-}
-void lists_by_column(const std::vector<uint8_t>& M, int n, const Lists& by_row, Lists& L) {
-    (void)M;
-    L.off.assign((size_t)n + 1, 0);
-    for (int32_t j : by_row.idx) ++L.off[j + 1];
-    for (int j = 0; j < n; ++j) L.off[j + 1] += L.off[j];
-    L.idx.resize(by_row.idx.size());
-    L.fill.assign(L.off.begin(), L.off.end() - 1);
-    for (int i = 0; i < n; ++i)
-        for (const int32_t* q = by_row.begin(i); q != by_row.end(i); ++q) L.idx[L.fill[*q]++] = i;
-}
-
-// utility/kahn.m:1-24: computation level (1-based) of every vertex of the DAG A (A[i][j] = 1: i before j)
-bool kahn(const std::vector<uint8_t>& A, int n, std::vector<int32_t>& L) {
-    // level = 1 + the longest path from a source (what removing all current sources, level by level, assigns); in-degrees are
-    // counted once and decremented along the removed vertices' rows
-    L.assign(n, 0);
-    std::vector<int> indeg(n, 0), cur, next;
-    for (int i = 0; i < n; ++i) for_each_set(A.data() + (size_t)i * n, n, [&](int j) { ++indeg[j]; });
-    for (int j = 0; j < n; ++j)
-        if (indeg[j] == 0) cur.push_back(j);
-    int n_done = 0, level = 1;
-    while (n_done < n) {
-        if (cur.empty()) return false;  // a cycle
-        next.clear();
-        for (int v : cur) {
-            L[v] = level;
-            ++n_done;
-        }
-        for (int v : cur)
-            for_each_set(A.data() + (size_t)v * n, n, [&](int j) {
-                if (--indeg[j] == 0) next.push_back(j);
-            });
-        cur.swap(next);
-        ++level;
-    }
-    return true;
-}
-
-// kahn over the successor lists of the matrix
-bool kahn_lists(const Lists& succ, int n, std::vector<int32_t>& L, std::vector<int>& indeg, std::vector<int>& cur, std::vector<int>& next) {
-    L.assign(n, 0);
-    indeg.assign(n, 0);
-    cur.clear();
-    for (int32_t j : succ.idx) ++indeg[j];
-    for (int j = 0; j < n; ++j)
-        if (indeg[j] == 0) cur.push_back(j);
-    int n_done = 0, level = 1;
-    while (n_done < n) {
-        if (cur.empty()) return false;  // a cycle
-        next.clear();
-        for (int v : cur) {
-            L[v] = level;
-            ++n_done;
-        }
-        for (int v : cur)
-            for (const int32_t* q = succ.begin(v); q != succ.end(v); ++q)
-                if (--indeg[*q] == 0) next.push_back(*q);
-        cur.swap(next);
-        ++level;
-    }
-    return true;
-}
-
-// MotionPrimitiveAutomaton.trim_from_values (:193-236): 1-based index of the closest trim
-int trim_from_values(const pdmpc_controller& c, double speed, double steering) {
-    const int nt = (int)c.trim_speed.size();
-    if (steering == 0) {
-        int best = -1;
-        double bd = 0;
-        for (int t = 0; t < nt; ++t) {
-            if (c.trim_steering[t] != 0) continue;
-            const double d = std::fabs(c.trim_speed[t] - speed);
-            if (best < 0 || d < bd) {
-                best = t;
-                bd = d;
-            }
-        }
-        return best + 1;
-    }
-    double sp_min = c.trim_speed[0], sp_max = c.trim_speed[0], st_min = c.trim_steering[0], st_max = c.trim_steering[0];
-    for (int t = 1; t < nt; ++t) {
-        sp_min = std::min(sp_min, c.trim_speed[t]);
-        sp_max = std::max(sp_max, c.trim_speed[t]);
-        st_min = std::min(st_min, c.trim_steering[t]);
-        st_max = std::max(st_max, c.trim_steering[t]);
-    }
-    const double sp_s = sp_max - sp_min, st_s = st_max - st_min;
-    int best = 0;
-    double bd = 0;
-    for (int t = 0; t < nt; ++t) {
-        const double a = (c.trim_speed[t] - sp_min) / sp_s - (speed - sp_min) / sp_s;
-        const double b = (c.trim_steering[t] - st_min) / st_s - (steering - st_min) / st_s;
-        const double d = std::hypot(a, b);
-        if (t == 0 || d < bd) {
-            best = t;
-            bd = d;
-        }
-    }
-    return best + 1;
-}
-
-// get_occupied_areas.m:21-31 -> closed rectangles with and without the offset (translate_global.m:19-22)
-void occupied_areas(double x, double y, double yaw, double length, double width, double offset, Poly& with_offset, Poly& plain) {
-    static const double sx[5] = {-1, -1, 1, 1, -1}, sy[5] = {-1, 1, 1, -1, -1};
-    const double c = std::cos(yaw), s = std::sin(yaw);
-    with_offset.x.resize(5);
-    with_offset.y.resize(5);
-    plain.x.resize(5);
-    plain.y.resize(5);
-    for (int q = 0; q < 5; ++q) {
-        const double xa = sx[q] * (length / 2 + offset), ya = sy[q] * (width / 2 + offset);
-        with_offset.x[q] = c * xa + (-s) * ya + x;
-        with_offset.y[q] = s * xa + c * ya + y;
-        const double xb = sx[q] * (length / 2), yb = sy[q] * (width / 2);
-        plain.x[q] = c * xb + (-s) * yb + x;
-        plain.y[q] = s * xb + c * yb + y;
-    }
-}
-
-inline double norm2(double a, double b) { return std::sqrt(a * a + b * b); }
-
-// projection_2d.m:14-42 -> projected point and lambda
-void projection_2d(double x1, double y1, double x2, double y2, double x3, double y3, double& xp, double& yp, double& lambda) {
-    const double b = std::sqrt((x2 - x1) * (x2 - x1) + (y2 - y1) * (y2 - y1));
-    if (b != 0) {
-        const double xn = (x2 - x1) / b, yn = (y2 - y1) / b;
-        const double x31 = x3 - x1, y31 = y3 - y1;
-        const double dot = xn * x31 + yn * y31;
-        xp = x1 + dot * xn;
-        yp = y1 + dot * yn;
-        lambda = dot / b;
-    } else {
-        xp = x1;
-        yp = y1;
-        lambda = 0.0;
-    }
-}
-
-// get_arc_distance_to_endpoint.m:39-114 (the part the sampler uses): projected point and 1-based idx_next
-void arc_projection(double px, double py, const std::vector<double>& cx, const std::vector<double>& cy, double& xp, double& yp, int& idx_next) {
-    const int np = (int)cx.size();
-    int ic = 0;
-    double best = 0;
-    auto sq_of = [&](int i) { return (cx[i] - px) * (cx[i] - px) + (cy[i] - py) * (cy[i] - py); };
-    for (int i = 0; i < np; ++i) {
-        const double d = sq_of(i);
-        if (i == 0 || d < best) {
-            best = d;
-            ic = i;
-        }
-    }
-    int f, s;
-    if (ic == 0) {
-        f = 0;
-        s = 1;
-    } else if (ic == np - 1) {
-        f = np - 2;
-        s = np - 1;
-    } else if (sq_of(ic - 1) <= sq_of(ic + 1)) {
-        f = ic - 1;
-        s = ic;
-    } else {
-        f = ic;
-        s = ic + 1;
-    }
-    double lam;
-    projection_2d(cx[f], cy[f], cx[s], cy[s], px, py, xp, yp, lam);
-    const int idx_closest = ic + 1;
-    idx_next = idx_closest;
-    if ((0 <= lam && lam <= 0.5) || lam >= 1) idx_next = idx_closest < np ? idx_closest + 1 : 1;
-    idx_next = std::max(2, idx_next);
-}
-
-// sample_reference_trajectory.m:1-99 (indices 1-based)
-void sample_reference(int n_samples, const std::vector<double>& rx, const std::vector<double>& ry, double x_cur, double y_cur, const std::vector<double>& step,
-                      std::vector<double>& out_x, std::vector<double>& out_y, std::vector<int32_t>& points_index, int& current_point_index) {
-    out_x.assign(n_samples, 0.0);
-    out_y.assign(n_samples, 0.0);
-    points_index.assign(n_samples, 0);
-    double cx, cy;
-    int point_index;
-    arc_projection(x_cur, y_cur, rx, ry, cx, cy, point_index);
-    current_point_index = point_index;
-    const int n_line = (int)rx.size();
-    const bool is_loop = norm2(rx[0] - rx[n_line - 1], ry[0] - ry[n_line - 1]) < 1e-8;
-    bool at_end = point_index == n_line;
-    int last = point_index - 1;
-    if (is_loop && at_end) point_index = 1;
-    auto X = [&](int i) { return rx[i - 1]; };
-    auto Y = [&](int i) { return ry[i - 1]; };
-    for (int i = 0; i < n_samples; ++i) {
-        double remaining = norm2(cx - X(point_index), cy - Y(point_index));
-        if (remaining > step[i] || point_index == n_line) {
-            while (X(point_index) == X(last) && Y(point_index) == Y(last) && last > 1) --last;
-            const double dx = X(point_index) - X(last), dy = Y(point_index) - Y(last);
-            const double nn = norm2(dx, dy);
-            cx = cx + step[i] * (dx / nn);
-            cy = cy + step[i] * (dy / nn);
-        } else {
-            double reflength = remaining;
-            while (remaining < step[i]) {
-                reflength = remaining;
-                cx = X(point_index);
-                cy = Y(point_index);
-                last = point_index;
-                point_index = std::min(point_index + 1, n_line);
-                at_end = point_index == n_line;
-                if (is_loop && at_end) point_index = 1;
-                remaining = remaining + norm2(cx - X(point_index), cy - Y(point_index));
-            }
-            const double dx = X(point_index) - X(last), dy = Y(point_index) - Y(last);
-            const double nn = norm2(dx, dy);
-            cx = cx + (step[i] - reflength) * (dx / nn);
-            cy = cy + (step[i] - reflength) * (dy / nn);
-        }
-        out_x[i] = cx;
-        out_y[i] = cy;
-        points_index[i] = point_index;
-    }
-}
-
-// get_predicted_lanelets.m:25-62 + get_lanelets_boundary.m:18-68 for vehicle v
-void lanelet_boundary(const pdmpc_controller& c, int v, const std::vector<int32_t>& ref_points_index, int current_point_index, Poly& left, Poly& right) {
-    const VehicleDef& V = c.veh[v];
-    left.x.clear();
-    left.y.clear();
-    right.x.clear();
-    right.y.clear();
-    if (V.lanelets_index.empty()) return;
-    const int n_total = (int)V.px.size(), n_lan = (int)V.lanelets_index.size();
-    int rpi[PDMPC_HP_MAX + 1], seen[PDMPC_HP_MAX + 2], predicted[PDMPC_HP_MAX + 2];
-    int n_rpi = 0, n_seen = 0, n_pred = 0;
-    for (int32_t p : ref_points_index) rpi[n_rpi++] = p;
-    int index_add = rpi[n_rpi - 1] + 4;
-    if (index_add > n_total) index_add -= n_total;
-    rpi[n_rpi++] = index_add;
-    for (int t = 0; t < n_rpi; ++t) {
-        const int p = rpi[t];
-        int q = 1;
-        for (int u = 0; u < n_lan; ++u) q += p > V.points_index[u];
-        if (std::find(seen, seen + n_seen, q) == seen + n_seen) seen[n_seen++] = q;  // unique(..., 'stable')
-    }
-    if (n_seen == 1) {
-        int nxt = seen[0] + 1;
-        if (nxt > n_lan) nxt = 1;
-        seen[n_seen++] = nxt;
-    }
-    (void)current_point_index;
-    for (int t = 0; t < n_seen; ++t) predicted[n_pred++] = V.lanelets_index[std::min(seen[t], n_lan) - 1];
-    auto append = [](Poly& dst, const Poly& src, int from, int to) {
-        dst.x.insert(dst.x.end(), src.x.begin() + from, src.x.begin() + to);
-        dst.y.insert(dst.y.end(), src.y.begin() + from, src.y.begin() + to);
-    };
-    // up to four points of the predecessor lanelet in front   :39-65
-    int pos = (int)(std::find(V.lanelets_index.begin(), V.lanelets_index.end(), predicted[0]) - V.lanelets_index.begin());
-    int pred = -1;
-    if (pos != 0)
-        pred = V.lanelets_index[pos - 1];
-    else if (V.is_loop)
-        pred = V.lanelets_index.back();
-    if (pred >= 0) {
-        const Poly& pl = c.bl_left[pred - 1];
-        const Poly& pr = c.bl_right[pred - 1];
-        const int num_added = std::min(4, std::min(pr.n() - 1, pl.n() - 1));
-        append(left, pl, pl.n() - 1 - num_added, pl.n() - 1);
-        append(right, pr, pr.n() - 1 - num_added, pr.n() - 1);
-    }
-    // then the boundaries of the predicted lanelets back to back, each without its last point but the final one   :26-32
-    for (int q = 0; q < n_pred; ++q) {
-        const Poly& bl = c.bl_left[predicted[q] - 1];
-        const Poly& br = c.bl_right[predicted[q] - 1];
-        const bool final_one = q + 1 == n_pred;
-        append(left, bl, 0, final_one ? bl.n() : bl.n() - 1);
-        append(right, br, 0, final_one ? br.n() : br.n() - 1);
-    }
-    for (int i = 0; i < left.n(); ++i) {
-        left.x[i] = left.x[i] + V.tile_dx;
-        left.y[i] = left.y[i] + V.tile_dy;
-    }
-    for (int i = 0; i < right.n(); ++i) {
-        right.x[i] = right.x[i] + V.tile_dx;
-        right.y[i] = right.y[i] + V.tile_dy;
-    }
-}
-
-// ColoringPrioritizer.prioritize (:11-27): directed coupling from a colouring of the undirected graph
-void coloring_directed(const std::vector<uint8_t>& adjacency, int n, std::vector<uint8_t>& directed) {
-    // neighbour lists of the graph without self-loops; the degrees the selection compares are the matrix's column sums (:38-45)
-    Lists nb;
-    nb.off.assign((size_t)n + 1, 0);
-    nb.idx.clear();
-    std::vector<int> degree(n, 0), color(n, 0);
-    std::vector<long> deg(n, 0);  // column counts of the matrix as given (order_topo, :93)
-    for (int i = 0; i < n; ++i) {
-        for_each_set(adjacency.data() + (size_t)i * n, n, [&](int j) {
-            ++deg[j];
-            if (j == i) return;
-            nb.idx.push_back(j);
-            degree[j] += adjacency[(size_t)i * n + j];
-        });
-        nb.off[i + 1] = (int32_t)nb.idx.size();
-    }
-    for (int i = 0; i < n; ++i)
-        if (degree[i] == 0) color[i] = 1;  // :45
-    // per vertex the distinct colours its neighbours carry, as a bit set (kept up to date as vertices are coloured: the selection
-    // below is then a scan of the vertices, not of the matrix — 512 vehicles: 63 ms -> well under 1 ms per step)
-    const int cw = (n + 2 + 63) / 64;
-    std::vector<int> ncol(n, 0);                   // distinct colours among the coloured neighbours
-    std::vector<uint64_t> has((size_t)n * cw, 0);  // bit c of has[i]: a neighbour of i carries colour c
-    auto mark = [&](int j, int col) {
-        uint64_t& w = has[(size_t)j * cw + (col >> 6)];
-        const uint64_t bit = 1ull << (col & 63);
-        if (!(w & bit)) {
-            w |= bit;
-            ++ncol[j];
-        }
-    };
-    // vertex_sdo_ldo (:65-89) scans the uncoloured vertices for the most distinct neighbour colours and, among equals, moves on to
-    // a vertex only if its degree is strictly larger than the current pick's: the pick is the first uncoloured vertex with the
-    // largest (colours, degree) pair.  key = that pair for an uncoloured vertex, -1 for a coloured one.
-    // The largest key is found over blocks of 32 vertices whose maxima are kept up to date (keys of uncoloured vertices only grow;
-    // the picked vertex's block is rescanned).
-    constexpr int KB = 32;
-    const int nblk = (n + KB - 1) / KB;
-    std::vector<int64_t> key(n), bmax((size_t)nblk, -1);
-    auto key_of = [&](int i) { return color[i] != 0 ? (int64_t)-1 : ((int64_t)ncol[i] << 32) | (int64_t)(uint32_t)degree[i]; };
-    int left = 0;
-    for (int i = 0; i < n; ++i) left += color[i] == 0;
-    for (int i = 0; i < n; ++i)
-        if (color[i] != 0)
-            for (const int32_t* q = nb.begin(i); q != nb.end(i); ++q) mark(*q, color[i]);
-    for (int i = 0; i < n; ++i) {
-        key[i] = key_of(i);
-        bmax[i / KB] = std::max(bmax[i / KB], key[i]);
-    }
-    while (left > 0) {
-        int blk = 0;
-        for (int b = 1; b < nblk; ++b)
-            if (bmax[b] > bmax[blk]) blk = b;  // the first block that holds the largest key
-        int idx = blk * KB;
-        while (key[idx] != bmax[blk]) ++idx;
-        int cpick = 1;
-        while (has[(size_t)idx * cw + (cpick >> 6)] >> (cpick & 63) & 1) ++cpick;  // the smallest colour no neighbour carries
-        color[idx] = cpick;
-        --left;
-        key[idx] = -1;
-        bmax[blk] = -1;
-        for (int i = blk * KB; i < std::min(n, blk * KB + KB); ++i) bmax[blk] = std::max(bmax[blk], key[i]);
-        for (const int32_t* q = nb.begin(idx); q != nb.end(idx); ++q) {
-            const int j = *q;
-            mark(j, cpick);
-            key[j] = key_of(j);
-            bmax[j / KB] = std::max(bmax[j / KB], key[j]);
-        }
-    }
-    // level matrix rows = colours in ascending order; order_topo (:91-131)
-    int cmax = 0;
-    for (int i = 0; i < n; ++i) cmax = std::max(cmax, color[i]);
-    std::vector<int> row_of_colour((size_t)cmax + 1, -1);
-    for (int i = 0; i < n; ++i) row_of_colour[color[i]] = 0;
-    int nl = 0;
-    for (int col = 0; col <= cmax; ++col)
-        if (row_of_colour[col] == 0) row_of_colour[col] = nl++;
-    std::vector<int> row(n);  // the level-matrix row a vertex stands in
-    for (int v = 0; v < n; ++v) row[v] = row_of_colour[color[v]];
-    std::vector<int> order;
-    std::vector<int> place((size_t)nl, -1);  // position of a row in `order`
-    long total = 0;
-    for (long d : deg) total += d;
-    if (total == 0) {
-        for (int g = 0; g < nl; ++g) order.push_back(g);
-    } else {
-        while (total != 0) {
-            int max_idx = 0;
-            for (int i = 1; i < n; ++i)
-                if (deg[i] > deg[max_idx]) max_idx = i;  // first index of the maximum
-            const int lvl = row[max_idx];
-            order.push_back(lvl);
-            for (int i = 0; i < n; ++i)
-                if (row[i] == lvl) deg[i] = 0;
-            total = 0;
-            for (long d : deg) total += d;
-        }
-        for (int g = 0; g < nl; ++g)
-            if (std::find(order.begin(), order.end(), g) == order.end()) order.push_back(g);
-    }
-    for (size_t q = 0; q < order.size(); ++q)
-        if (place[order[q]] < 0) place[order[q]] = (int)q;  // (find: the first position)
-    std::vector<int> level(n, 0);
-    for (int v = 0; v < n; ++v) level[v] = place[row[v]] + 1;
-    directed.assign((size_t)n * n, 0);
-    for (int i = 0; i < n; ++i)
-        for_each_set(adjacency.data() + (size_t)i * n, n, [&](int j) {
-            if (i != j && !(level[i] > level[j])) at(directed, n, i, j) = 1;  // Prioritizer.m:52-55
-        });
-}
-
-// PrioritizedController.group (:375-389): weigh + GreedyCutter.cut (cut/GreedyCutter.m:5-86)
-// (dir_succ / dir_pred: `directed` as lists by row / by column; uncut = nothing had to be cut: seq is `directed` and L its levels)
-bool group(pdmpc_controller& c, const std::vector<uint8_t>& directed, const Lists& dir_succ, const Lists& dir_pred, std::vector<uint8_t>& seq,
-           std::vector<int32_t>& L, bool& uncut) {
-    const int n = c.n;
-    uncut = false;
-    if (!kahn_lists(dir_succ, n, L, c.kahn_indeg, c.kahn_cur, c.kahn_next)) return false;
-    int depth = 0;
-    for (int v : L) depth = std::max(depth, v);
-    if (depth <= c.cfg.max_num_CLs) {
-        seq = directed;  // every sub-graph of the DAG is at most as deep: the cutter accepts every edge
-        uncut = true;
-        return true;
-    }
-    seq.assign((size_t)n * n, 0);
-    if (c.cfg.max_num_CLs == 1) return true;
-    // weights; [row, col] = find(M): column-major order
-    struct Edge { int a, b; double w; };
-    std::vector<Edge> edges;
-    const double vmax = *std::max_element(c.trim_speed.begin(), c.trim_speed.end());
-    const double max_distance = 2 * vmax * c.cfg.dt_seconds * c.Hp;
-    Mt19937ar rng((uint32_t)c.k);  // RandomWeigher (weight/RandomWeigher.m:13-21): one draw per edge in find() order, seeded with the time step
-    for (int b = 0; b < n; ++b)
-        for (const int32_t* q = dir_pred.begin(b); q != dir_pred.end(b); ++q) {
-            const int a = *q;
-            double w = 0.5;  // ConstantWeigher
-            if (c.cfg.weight_strategy == PDMPC_WEIGHT_DISTANCE) {
-                const double dx = c.mx[a] - c.mx[b], dy = c.my[a] - c.my[b];
-                w = 1 - std::sqrt(dx * dx + dy * dy) / max_distance;
-            } else if (c.cfg.weight_strategy == PDMPC_WEIGHT_RANDOM) {
-                w = rng.rand();
-            }
-            if (w != 0) edges.push_back({a, b, w});  // (find() on the weighted matrix skips exact zeros)
-        }
-    std::stable_sort(edges.begin(), edges.end(), [](const Edge& p, const Edge& q) { return p.w > q.w; });
-    // GreedyCutter.cut (:25-86) accepts an edge if the graph stays acyclic and at most max_num_CLs levels deep.  The levels are
-    // longest-path layers (kahn), edges are only ever added, so the layers only grow: instead of a trial copy of the matrix and a
-    // kahn pass per edge (128 vehicles: 6 ms per step), the new layers are relaxed from the edge's head through the accepted
-    // successors; reaching the edge's tail again is a cycle, a layer beyond the limit a rejection (both undo the relaxation).
-    std::vector<int32_t> levels((size_t)n, 1);  // (kahn of the graph without edges)
-    std::vector<std::vector<int>> succ(n);
-    std::vector<std::pair<int, int32_t>> undo;
-    std::vector<int> work;
-    for (const Edge& e : edges) {
-        if (levels[e.a] < levels[e.b]) {
-            at(seq, n, e.a, e.b) = 1;
-            succ[e.a].push_back(e.b);
-            continue;
-        }
-        undo.clear();
-        work.clear();
-        bool ok = levels[e.a] + 1 <= c.cfg.max_num_CLs;
-        if (ok) {
-            undo.emplace_back(e.b, levels[e.b]);
-            levels[e.b] = levels[e.a] + 1;
-            work.push_back(e.b);
-        }
-        while (ok && !work.empty()) {
-            const int u = work.back();
-            work.pop_back();
-            for (int w : succ[u]) {
-                if (levels[w] >= levels[u] + 1) continue;
-                if (w == e.a || levels[u] + 1 > c.cfg.max_num_CLs) {  // a cycle / too deep
-                    ok = false;
-                    break;
-                }
-                undo.emplace_back(w, levels[w]);
-                levels[w] = levels[u] + 1;
-                work.push_back(w);
-            }
-        }
-        if (ok) {
-            at(seq, n, e.a, e.b) = 1;
-            succ[e.a].push_back(e.b);
-        } else {
-            for (auto it = undo.rbegin(); it != undo.rend(); ++it) levels[it->first] = it->second;
-        }
-    }
-    return true;
-}
-
-inline double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
-
-struct SetBuilder {  // builds a pdmpc_polygon_set whose arrays live in the controller's arena; one builder at a time
-    pdmpc_controller& c;
-    explicit SetBuilder(pdmpc_controller& ctl) : c(ctl) {
-        c.sb_off.assign(1, 0);
-        c.sb_x.clear();
-        c.sb_y.clear();
-    }
-    void add(const Poly& p) {
-        c.sb_x.insert(c.sb_x.end(), p.x.begin(), p.x.end());
-        c.sb_y.insert(c.sb_y.end(), p.y.begin(), p.y.end());
-        c.sb_off.push_back((int32_t)c.sb_x.size());
-    }
-    pdmpc_polygon_set finish() {
-        pdmpc_polygon_set s;
-        s.n_polygons = (int32_t)c.sb_off.size() - 1;
-        const size_t np = c.sb_x.size();
-        int32_t* off = (int32_t*)c.arena.take(c.sb_off.size() * sizeof(int32_t));
-        double* x = (double*)c.arena.take((np + 1) * sizeof(double));  // (one entry more: never an empty array)
-        double* y = (double*)c.arena.take((np + 1) * sizeof(double));
-        std::memcpy(off, c.sb_off.data(), c.sb_off.size() * sizeof(int32_t));
-        if (np) {
-            std::memcpy(x, c.sb_x.data(), np * sizeof(double));
-            std::memcpy(y, c.sb_y.data(), np * sizeof(double));
-        }
-        x[np] = y[np] = 0.0;
-        s.offset = off;
-        s.x = x;
-        s.y = y;
-        return s;
-    }
-};
-
-int cfail(pdmpc_controller* c, int code, const std::string& msg) {
-    g_cerr = msg;
-    if (c) c->err = msg;
-    return code;
-}
 
 // ---- the shared paths of the steps below (templates: outside the extern "C" block)
 // A bounding call that writes its sets into (x, y) of capacity x.size() and their offsets into off: after PDMPC_ERR_CAPACITY it is
@@ -915,554 +75,6 @@ int timed_steps(int32_t n_steps, double* ms, Step&& step) {
     return PDMPC_OK;
 }
 
-// ---- a member's step around the step preparation: the seeds, the priorities, and the stages of pdmpc_controller_build_step in its order
-// RandStream('mt19937ar', Seed = time_step + vehicle_index) of every slot (MonteCarloTreeSearch.m:31-32; PrioritizedController.m:335-341
-// calls run_optimizer with obj.k, so every instance of a batch draws the same stream for the same vehicle)
-void set_seeds(const pdmpc_controller* c, StepProblem& P, const std::vector<int32_t>& vehicle_of_slot) {
-    P.seeds.resize(vehicle_of_slot.size());
-    for (size_t s = 0; s < vehicle_of_slot.size(); ++s) P.seeds[s] = (uint32_t)(c->k + vehicle_of_slot[s] + 1);
-}
-
-// RandomPrioritizer.m:15-25 (prioritizer.random_priorities): a Fisher-Yates shuffle of 1 .. n on the mt19937ar doubles of the time step
-void random_priorities(int time_step, int n, std::vector<int32_t>& p) {
-    Mt19937ar rng((uint32_t)time_step);
-    for (int i = n - 1; i > 0; --i) {
-        const int j = (int)(rng.rand() * (i + 1));
-        std::swap(p[i], p[j]);
-    }
-}
-
-// FcaPrioritizer.m:11-92 on the step's reference points and the scenario's obstacles: the two per-member halves around the ONE
-// grouped assessment of all FCA members of a step preparation (build_members) -- the reference points, their headings and the
-// coupled pairs in c->fca_*, and the counts and priorities taken over
-int fca_inputs(pdmpc_controller* c) {
-    const int n = c->n, Hp = c->Hp;
-    if (Hp < 2) return cfail(c, PDMPC_ERR_INVALID, "FCA priorities need Hp >= 2 (calculate_yaw needs two reference points)");
-    c->fca_x.resize((size_t)n * Hp);
-    c->fca_y.resize((size_t)n * Hp);
-    c->fca_cos.resize((size_t)n * Hp);
-    c->fca_sin.resize((size_t)n * Hp);
-    for (int v = 0; v < n; ++v) {
-        const double *px = c->ref_x[v].data(), *py = c->ref_y[v].data();
-        for (int q = 0; q < Hp; ++q) {
-            // calculate_yaw.m: central differences, one-sided at the ends (prioritizer.calculate_yaw)
-            const int a = q == 0 ? 0 : (q == Hp - 1 ? Hp - 2 : q - 1), b = q == 0 ? 1 : (q == Hp - 1 ? Hp - 1 : q + 1);
-            const double yaw = std::atan2(py[b] - py[a], px[b] - px[a]);
-            const size_t i = (size_t)v * Hp + q;
-            c->fca_x[i] = px[q];
-            c->fca_y[i] = py[q];
-            c->fca_cos[i] = std::cos(yaw);
-            c->fca_sin[i] = std::sin(yaw);
-        }
-    }
-    c->fca_pairs.clear();
-    for (int a = 0; a < n; ++a)
-        for_each_set(c->adjacency.data() + (size_t)a * n + a + 1, n - a - 1, [&](int q) {
-            c->fca_pairs.push_back(a);
-            c->fca_pairs.push_back(a + 1 + q);
-        });
-    c->fca_count.resize(n);
-    return PDMPC_OK;
-}
-void adopt_fca(pdmpc_controller* c, const int32_t* collisions, const int32_t* priorities) {
-    std::copy(collisions, collisions + c->n, c->fca_count.begin());
-    std::copy(priorities, priorities + c->n, c->prio.begin());
-}
-
-// ---- the stages of pdmpc_controller_build_step, in its order
-void traffic_info(pdmpc_controller* c) {
-    const int n = c->n, Hp = c->Hp;
-    c->trims.assign(n, 0);
-    // (resized, not re-created: the per-vehicle vectors keep their capacity from step to step; every one of them is rewritten below)
-    c->occ_offset.resize(n);
-    c->occ_plain.resize(n);
-    c->ref_x.resize(n);
-    c->ref_y.resize(n);
-    c->v_ref.resize(n);
-    c->bnd_left.resize(n);
-    c->bnd_right.resize(n);
-    std::vector<double> step(Hp);
-    std::vector<int32_t> pidx;
-    for (int v = 0; v < n; ++v) {
-        c->trims[v] = trim_from_values(*c, c->mspeed[v], c->msteer[v]);
-        occupied_areas(c->mx[v], c->my[v], c->myaw[v], c->cfg.vehicle_length, c->cfg.vehicle_width, c->cfg.offset, c->occ_offset[v], c->occ_plain[v]);
-        // get_reference_trajectory.m:27-46
-        std::vector<double>& vref = c->v_ref[v];
-        vref.assign(Hp, c->veh[v].reference_speed);
-        const double v_current = c->trim_speed[c->trims[v] - 1];
-        for (int q = 0; q < Hp; ++q) step[q] = (((q == 0 ? v_current : vref[q - 1]) + vref[q]) / 2) * c->cfg.dt_seconds;
-        int cpi = 0;
-        sample_reference(Hp, c->veh[v].px, c->veh[v].py, c->mx[v], c->my[v], step, c->ref_x[v], c->ref_y[v], pidx, cpi);
-        lanelet_boundary(*c, v, pidx, cpi, c->bnd_left[v], c->bnd_right[v]);
-    }
-}
-
-// reachable sets at the vehicles' poses (reachable_sets_at_pose, MotionPrimitiveAutomaton.m:649-687), closed by repeating the first
-// vertex (HighLevelController.m:258-263)
-void reachable_sets_at_poses(pdmpc_controller* c) {
-    const int n = c->n, Hp = c->Hp;
-    c->reach_sets.resize(n);
-    c->reach_cos.resize(n);
-    c->reach_sin.resize(n);
-    for (int v = 0; v < n; ++v) {
-        const double cy = std::cos(c->myaw[v]), sy = std::sin(c->myaw[v]);
-        c->reach_cos[v] = cy;
-        c->reach_sin[v] = sy;
-        std::vector<Poly>& sets = c->reach_sets[v];
-        sets.resize(Hp);
-        for (int q = 0; q < Hp; ++q) {
-            const int p = (c->trims[v] - 1) * Hp + q, a = c->reach_off[p], m = c->reach_off[p + 1] - a;
-            Poly& P = sets[q];
-            P.x.resize(m + 1);
-            P.y.resize(m + 1);
-            for (int r = 0; r < m; ++r) pdmpc_move_point(cy, sy, c->mx[v], c->my[v], c->reach_x[a + r], c->reach_y[a + r], &P.x[r], &P.y[r]);
-            P.x[m] = P.x[0];
-            P.y[m] = P.y[0];
-        }
-    }
-}
-
-// lanelet bounding of those sets (bound_reachable_sets.m, HighLevelController.m:241-246): every step's sets when parallel
-// predecessors read them (all_steps), else step Hp only (the coupler's)
-// ... its two per-member halves around the bounding call of a step preparation (build_members): the raw lanelet polygons in
-// c->lan_*, and the bounded sets in c->bound_* taken over as the parallel predecessors' obstacles
-void lanelet_polygons(pdmpc_controller* c) {
-    const int n = c->n;
-    c->lan_off.assign((size_t)n + 1, 0);
-    c->lan_x.clear();
-    c->lan_y.clear();
-    for (int v = 0; v < n; ++v) {  // the left boundary, then the reversed right boundary (get_lanelets_boundary.m:69-74)
-        const Poly &L = c->bnd_left[v], &R = c->bnd_right[v];
-        c->lan_x.insert(c->lan_x.end(), L.x.begin(), L.x.end());
-        c->lan_y.insert(c->lan_y.end(), L.y.begin(), L.y.end());
-        c->lan_x.insert(c->lan_x.end(), R.x.rbegin(), R.x.rend());
-        c->lan_y.insert(c->lan_y.end(), R.y.rbegin(), R.y.rend());
-        c->lan_off[v + 1] = (int32_t)c->lan_x.size();
-    }
-    c->lan_x.push_back(0.0);  // (never empty)
-    c->lan_y.push_back(0.0);
-}
-void adopt_bounded_sets(pdmpc_controller* c, bool all_steps) {
-    const int n = c->n, Hp = c->Hp;
-    if (all_steps) {  // the parallel predecessors' obstacles are the bounded sets
-        for (int v = 0; v < n; ++v)
-            for (int q = 0; q < Hp; ++q) {
-                const int o = v * Hp + q, a = c->bound_off[o], m = c->bound_off[o + 1] - a;
-                Poly& P = c->reach_sets[v][q];
-                P.x.assign(c->bound_x.begin() + a, c->bound_x.begin() + a + m);
-                P.y.assign(c->bound_y.begin() + a, c->bound_y.begin() + a + m);
-            }
-    }
-}
-
-// c->adjacency by the host rules: full and distance coupling (ReachableSetCoupler.m:5-56 is a call of the step preparation, which has
-// written the member's block into c->adjacency already)
-void couple(pdmpc_controller* c) {
-    const int n = c->n;
-    if (c->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET) return;
-    c->adjacency.assign((size_t)n * n, 0);
-    if (c->cfg.coupling == PDMPC_COUPLING_FULL) {
-        for (int a = 0; a < n; ++a)
-            for (int b = 0; b < n; ++b) at(c->adjacency, n, a, b) = a != b;
-    } else if (c->cfg.coupling == PDMPC_COUPLING_DISTANCE) {
-        const double vmax = *std::max_element(c->trim_speed.begin(), c->trim_speed.end());
-        const double max_distance = 2 * vmax * c->cfg.dt_seconds * c->Hp;
-        // (hypot(dx, dy) >= max(|dx|, |dy|), also as rounded: a pair farther apart along one axis alone is not coupled — most pairs of
-        // a tiled network.  That test runs over the whole row, the distance itself over the survivors.)
-        for (int a = 0; a < n; ++a) {
-            uint8_t* row = c->adjacency.data() + (size_t)a * n;
-            const double xa = c->mx[a], ya = c->my[a];
-            const double *px = c->mx.data(), *py = c->my.data();
-            for (int b = a + 1; b < n; ++b) row[b] = (uint8_t)(!(std::fabs(xa - px[b]) > max_distance) & !(std::fabs(ya - py[b]) > max_distance));
-            for_each_set(row + a + 1, n - a - 1, [&](int q) {
-                const int b = a + 1 + q;
-                row[b] = std::hypot(xa - px[b], ya - py[b]) <= max_distance;
-                at(c->adjacency, n, b, a) = row[b];
-            });
-        }
-    }
-}
-
-// priorities -> c->pri.directed (FCA: the counts and priorities of the member's group in the step preparation's assessment)
-void direct_by_priorities(pdmpc_controller* c, const int32_t* fca_collisions, const int32_t* fca_priorities) {
-    const int n = c->n;
-    std::vector<uint8_t>& directed = c->pri.directed;
-    if (c->cfg.priority_strategy == PDMPC_PRIORITY_COLORING) {
-        coloring_directed(c->adjacency, n, directed);
-        return;
-    }
-    // constant priorities = vehicle index (ConstantPrioritizer.m:14-20); random and FCA priorities as below
-    // (Prioritizer.directed_coupling_from_priorities, Prioritizer.m:64-77: keep i -> j iff priority(j) is not below priority(i))
-    c->prio.resize(n);
-    for (int v = 0; v < n; ++v) c->prio[v] = v + 1;
-    if (c->cfg.priority_strategy == PDMPC_PRIORITY_RANDOM) {
-        random_priorities(c->k, n, c->prio);
-    } else if (c->cfg.priority_strategy == PDMPC_PRIORITY_FCA) {
-        adopt_fca(c, fca_collisions, fca_priorities);
-    }
-    directed.assign((size_t)n * n, 0);
-    for (int i = 0; i < n; ++i)
-        for_each_set(c->adjacency.data() + (size_t)i * n, n, [&](int j) {
-            if (!(c->prio[j] < c->prio[i])) at(directed, n, i, j) = 1;
-        });
-}
-
-// A member's step in three parts around the step preparation, which runs once for all members that are built together: everything
-// before it (advances the time step; P: what the step reads of the reachable sets),
-int begin_step(pdmpc_controller* c, StepPrep& P) {
-    const int n = c->n;
-    const bool reach_parallel = c->parallel_mode == PDMPC_PARALLEL_REACHABLE_SETS;
-    const bool reach = c->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET || reach_parallel;  // a feature reads the reachable sets
-    if (reach && !c->has_reach)
-        return cfail(c, PDMPC_ERR_INVALID, "reachable-set coupling / parallel coupling by reachable sets need pdmpc_controller_set_reachability first");
-    c->k += 1;
-    c->arena.reset();
-    if (c->exploring) {
-        c->obst_memo.resize((size_t)n);
-        c->dyn_memo.resize((size_t)n);
-        for (int v = 0; v < n; ++v) {
-            c->obst_memo[(size_t)v].clear();
-            c->dyn_memo[(size_t)v].clear();
-        }
-    }
-    c->fb_of.assign(n, pdmpc_polygon_set());
-    c->fb_done.assign(n, 0);
-    c->empty_done = false;
-    traffic_info(c);
-    if (reach) reachable_sets_at_poses(c);
-    bool bounded = false;  // (not on scenarios without lanelets)
-    if (reach && c->lanelet_bounding)
-        for (int v = 0; v < n && !bounded; ++v) bounded = !c->veh[v].lanelets_index.empty();
-    P.reach_parallel = reach_parallel;
-    P.reach = reach;
-    P.bounded = bounded;
-    return PDMPC_OK;
-}
-// c->pri.directed -> sequential couplings, levels, slot order and the per-slot inputs of pdmpc_plan_step (the arena is the caller's
-// to clear: the explorative step keeps several problems alive side by side)
-int assemble_step(pdmpc_controller* c, bool seq_given = false) {
-    const int n = c->n, Hp = c->Hp;
-    // (seq_given: c->pri.directed_seq is the caller's -- the explorative step swaps single couplings of the base prioritization)
-    // who a vehicle is coupled with, as lists: the loops below visit a vehicle's few couplings, not rows and columns of the matrices
-    Lists &dir_succ = c->ls_dir_succ, &dir_pred = c->ls_dir_pred, &seq_succ_own = c->ls_seq_succ, &seq_pred_own = c->ls_seq_pred;
-    lists_by_row(c->pri.directed, n, dir_succ);
-    lists_by_column(c->pri.directed, n, dir_succ, dir_pred);
-    bool uncut = false;
-    if (!seq_given && !group(*c, c->pri.directed, dir_succ, dir_pred, c->pri.directed_seq, c->pri.levels, uncut)) return cfail(c, PDMPC_ERR_INVALID, "coupling graph has a cycle");
-    if (!uncut) {  // (uncut: the sequential coupling is `directed` itself, levels and lists included)
-        lists_by_row(c->pri.directed_seq, n, seq_succ_own);
-        lists_by_column(c->pri.directed_seq, n, seq_succ_own, seq_pred_own);
-        if (!kahn_lists(seq_succ_own, n, c->pri.levels, c->kahn_indeg, c->kahn_cur, c->kahn_next)) return cfail(c, PDMPC_ERR_INVALID, "coupling graph has a cycle");
-    }
-    const Lists& seq_pred = uncut ? dir_pred : seq_pred_own;
-    // slot order: by level, vehicles of a level in index order (a counting sort over the levels 1 .. n)
-    c->pri.order.resize(n);
-    c->pri.slot_of.assign(n, 0);
-    {
-        std::vector<int>& first = c->kahn_cur;  // (scratch) first[l] = slot of level l's first vehicle
-        first.assign((size_t)n + 2, 0);
-        for (int i = 0; i < n; ++i) ++first[(size_t)c->pri.levels[i] + 1];
-        for (int l = 1; l <= n + 1; ++l) first[l] += first[l - 1];
-        for (int i = 0; i < n; ++i) {
-            const int s = first[(size_t)c->pri.levels[i]]++;
-            c->pri.order[s] = i;
-            c->pri.slot_of[i] = s;
-        }
-    }
-    // ---- per slot inputs
-    c->prob.in.assign(n, pdmpc_vehicle_in());
-    c->prob.fb.assign(n, pdmpc_polygon_set());
-    c->prob.pred_offset.assign(n + 1, 0);
-    c->prob.pred_index.clear();
-    for (int s = 0; s < n; ++s) {
-        const int i = c->pri.order[s];
-        pdmpc_vehicle_in& I = c->prob.in[s];
-        std::memset(&I, 0, sizeof I);
-        I.x0 = c->mx[i];
-        I.y0 = c->my[i];
-        I.yaw0 = c->myaw[i];
-        I.trim0 = c->trims[i];
-        I.ref_x = c->ref_x[i].data();
-        I.ref_y = c->ref_y[i].data();
-        I.v_ref = c->v_ref[i].data();
-        I.n_left = c->bnd_left[i].n();
-        I.n_right = c->bnd_right[i].n();
-        I.left_x = c->bnd_left[i].x.data();
-        I.left_y = c->bnd_left[i].y.data();
-        I.right_x = c->bnd_right[i].x.data();
-        I.right_y = c->bnd_right[i].y.data();
-        auto add_shifted = [](SetBuilder& b, const std::vector<Poly>& shapes) {  // del_first_rpt_last without the temporary
-            for (size_t q = 1; q < shapes.size(); ++q) b.add(shapes[q]);
-            b.add(shapes.back());
-        };
-        // who contributes (in the order the sets are built in): consider_predecessors (:449-506) — sequential predecessors are handed
-        // over on the device; the others contribute their previous plan shifted by one step (parallel_coupling_previous_trajectory,
-        // :409-447) —, then consider_successors (:508-566)
-        const bool memo = c->exploring && n <= 512;  // (one prioritization: every set is built once anyway)
-        pdmpc_controller::MemoKey ok, dk;
-        if (memo) {
-            std::memset(&ok, 0, sizeof ok);
-            std::memset(&dk, 0, sizeof dk);
-        }
-        int ol[512], dpl[512], dsl[512], no = 0, ndp = 0, nds = 0;  // (the contributors in the order the sets are built in)
-        std::vector<int> big;  // (n > 512: the lists on the heap)
-        int *olp = ol, *dplp = dpl, *dslp = dsl;
-        if (n > 512) {
-            big.resize((size_t)3 * n);
-            olp = big.data();
-            dplp = big.data() + n;
-            dslp = big.data() + 2 * n;
-        }
-        for (const int32_t* q = dir_pred.begin(i); q != dir_pred.end(i); ++q) {
-            const int j = *q;
-            if (at(c->pri.directed_seq, n, j, i)) continue;
-            // (parallel_coupling_reachability, :391-407: the predecessor's reachable sets exist from the first step on)
-            if (c->parallel_mode == PDMPC_PARALLEL_REACHABLE_SETS || (c->info_old[j].present && c->k > 1)) {
-                dplp[ndp++] = j;
-                if (memo) dk.w[j >> 6] |= 1ull << (j & 63);
-            }
-        }
-        for (const int32_t* q = dir_succ.begin(i); q != dir_succ.end(i); ++q) {
-            const int j = *q;
-            if (c->cfg.constraint_from_successor == PDMPC_SUCCESSOR_AREA_OF_STANDSTILL) {
-                if (std::fabs(c->mspeed[j]) < 0.01) {  // :536-540
-                    olp[no++] = j;
-                    if (memo) ok.w[j >> 6] |= 1ull << (j & 63);
-                }
-            } else if (c->cfg.constraint_from_successor == PDMPC_SUCCESSOR_AREA_OF_PREVIOUS_TRAJECTORY) {
-                if (c->info_old[j].present) {
-                    dslp[nds++] = j;
-                    if (memo) dk.w[8 + (j >> 6)] |= 1ull << (j & 63);
-                }
-            }
-        }
-        auto build_obst = [&]() {
-            SetBuilder obst(*c);
-            for (const Poly& o : c->static_obstacles) obst.add(o);
-            for (int q = 0; q < no; ++q) obst.add(c->occ_offset[olp[q]]);
-            return obst.finish();
-        };
-        auto build_dyn = [&]() {
-            SetBuilder dyn(*c);
-            for (int q = 0; q < ndp; ++q) {
-                if (c->parallel_mode == PDMPC_PARALLEL_REACHABLE_SETS) {
-                    for (const Poly& p : c->reach_sets[dplp[q]]) dyn.add(p);
-                } else {
-                    add_shifted(dyn, c->info_old[dplp[q]].shapes);
-                }
-            }
-            for (int q = 0; q < nds; ++q) add_shifted(dyn, c->info_old[dslp[q]].shapes);
-            return dyn.finish();
-        };
-        if (memo) {
-            auto& om = c->obst_memo[(size_t)i];
-            if (const pdmpc_polygon_set* hit = om.find(ok)) {
-                I.obstacles = *hit;
-            } else {
-                I.obstacles = build_obst();
-                om.keys.push_back(ok);
-                om.sets.push_back(I.obstacles);
-            }
-            auto& dm = c->dyn_memo[(size_t)i];
-            if (const pdmpc_polygon_set* hit = dm.find(dk)) {
-                I.dynamic_obstacles = *hit;
-            } else {
-                I.dynamic_obstacles = build_dyn();
-                dm.keys.push_back(dk);
-                dm.sets.push_back(I.dynamic_obstacles);
-            }
-        } else {
-            I.obstacles = build_obst();
-            I.dynamic_obstacles = build_dyn();
-        }
-        if (!c->empty_done) {
-            SetBuilder none(*c);
-            c->empty_set = none.finish();
-            c->empty_done = true;
-        }
-        I.hdv_reachable_sets = c->empty_set;
-        // sequential predecessors as slots
-        for (const int32_t* q = seq_pred.begin(i); q != seq_pred.end(i); ++q) c->prob.pred_index.push_back(c->pri.slot_of[*q]);
-        c->prob.pred_offset[s + 1] = (int32_t)c->prob.pred_index.size();
-        // what the vehicle publishes if its search is exhausted: its standstill rectangle (:602-611) or the previous plan
-        // shifted by one step (:678-718)
-        if (!c->fb_done[i]) {  // (a function of the vehicle alone: shared by the prioritizations of an explorative step)
-            SetBuilder fbs(*c);
-            const bool standstill = c->trim_speed[c->trims[i] - 1] == 0;
-            if (standstill && c->cfg.constraint_from_successor != PDMPC_SUCCESSOR_NONE) {
-                for (int q = 0; q < Hp; ++q) fbs.add(c->occ_plain[i]);
-            } else if (c->info_old[i].present) {
-                add_shifted(fbs, c->info_old[i].shapes);
-            }
-            c->fb_of[i] = fbs.finish();
-            c->fb_done[i] = 1;
-        }
-        c->prob.fb[s] = c->fb_of[i];
-    }
-    c->prob.pred_index.push_back(0);
-    return PDMPC_OK;
-}
-// ... and everything after the step preparation
-int finish_step(pdmpc_controller* c, const int32_t* fca_collisions, const int32_t* fca_priorities) {
-    direct_by_priorities(c, fca_collisions, fca_priorities);
-    if (const int rc = assemble_step(c)) return rc;
-    set_seeds(c, c->prob, c->pri.order);
-    c->batch_built_last = false;
-    return PDMPC_OK;
-}
-
-// ---- how a step ends that the controller takes alone
-// a failure inside a step the controller takes alone is the controller's error too (the global message has it either way)
-int own(pdmpc_controller* c, int rc) {
-    if (rc) c->err = g_cerr;
-    return rc;
-}
-// the end of a step the controller takes alone: the records in c->out applied (timing[5]), and the step's parts added to the controller's sums
-int apply_and_account(pdmpc_controller* c) {
-    const auto t = std::chrono::steady_clock::now();
-    const int rc = pdmpc_controller_apply(c, c->out.data());
-    c->timing[5] = ms_since(t);
-    for (int i = 0; i < 6; ++i) c->timing_sum[i] += c->timing[i];
-    c->timing_steps += 1;
-    return rc;
-}
-// (nobody looks at the plans that were not chosen: the explorative and optimal-priority steps keep them all, their *_run loops do not)
-struct LeanRun {
-    pdmpc_controller* c;
-    bool was;
-    explicit LeanRun(pdmpc_controller* ctl) : c(ctl), was(ctl->lean_explore) { c->lean_explore = true; }
-    ~LeanRun() { c->lean_explore = was; }
-};
-
-// ---- the batch of prioritizations of an explorative or optimal-priority step: its instances, kept and flattened
-struct Exploring {  // (the memos of the obstacle sets are on while a step's prioritizations are assembled)
-    pdmpc_controller* c;
-    explicit Exploring(pdmpc_controller* ctl) : c(ctl) { c->exploring = true; }
-    ~Exploring() { c->exploring = false; }
-};
-
-// the batch of K instances: sized before the first keep_instance (copies into vectors that are kept from step to step: no allocation
-// once warm)
-void begin_instances(pdmpc_controller* c, int K) {
-    if (c->inst_prob.size() < (size_t)K) c->inst_prob.resize((size_t)K);
-    if (c->inst.size() != (size_t)K) c->inst.resize((size_t)K);
-}
-
-// the problem assemble_step just left in the controller becomes instance p
-void keep_instance(pdmpc_controller* c, int p) {
-    c->inst_prob[(size_t)p] = c->prob;
-    c->inst_prob[(size_t)p].seeds.clear();  // (they are those of the step's own slot order, which need not be the instance's)
-    c->inst[(size_t)p] = c->pri;
-}
-
-// flatten instances 0 .. K-1 into one batch, slots ordered by (level, instance, slot), and seed it; then instance 0 is the controller's
-// problem again
-void flatten_instances(pdmpc_controller* c, int K) {
-    const int n = c->n;
-    StepProblem& X = c->x_prob;
-    struct Key {
-        int32_t level, p, s;
-    };
-    std::vector<Key> flat;
-    for (int p = 0; p < K; ++p)
-        for (int s = 0; s < n; ++s) flat.push_back(Key{c->inst[(size_t)p].levels[(size_t)c->inst[(size_t)p].order[(size_t)s]], p, s});
-    std::stable_sort(flat.begin(), flat.end(), [](const Key& a, const Key& b) { return a.level < b.level; });  // (generated in (p, s) order)
-    const int N = K * n;
-    std::vector<int32_t> slot_of((size_t)N);  // [p * n + s]
-    for (int i = 0; i < N; ++i) slot_of[(size_t)flat[(size_t)i].p * n + flat[(size_t)i].s] = i;
-    X.in.resize((size_t)N);
-    X.fb.resize((size_t)N);
-    X.pred_offset.assign((size_t)N + 1, 0);
-    X.pred_index.clear();
-    c->x_instance.resize((size_t)N);
-    c->x_vehicle.resize((size_t)N);
-    c->x_level.resize((size_t)N);
-    c->x_slot.assign((size_t)N, 0);
-    for (int i = 0; i < N; ++i) {
-        const Key& k = flat[(size_t)i];
-        const StepProblem& P = c->inst_prob[(size_t)k.p];
-        X.in[(size_t)i] = P.in[(size_t)k.s];
-        X.fb[(size_t)i] = P.fb[(size_t)k.s];
-        for (int32_t q = P.pred_offset[(size_t)k.s]; q < P.pred_offset[(size_t)k.s + 1]; ++q) X.pred_index.push_back(slot_of[(size_t)k.p * n + P.pred_index[(size_t)q]]);
-        X.pred_offset[(size_t)i + 1] = (int32_t)X.pred_index.size();
-        c->x_instance[(size_t)i] = k.p;
-        c->x_vehicle[(size_t)i] = c->inst[(size_t)k.p].order[(size_t)k.s];
-        c->x_level[(size_t)i] = k.level;
-        c->x_slot[(size_t)k.p * n + c->x_vehicle[(size_t)i]] = i;
-    }
-    X.pred_index.push_back(0);
-    set_seeds(c, X, c->x_vehicle);
-    c->batch_built_last = true;
-    // the controller's own problem again (instance 0), with the seeds of its slots
-    c->prob = c->inst_prob[0];
-    c->pri = c->inst[0];
-    set_seeds(c, c->prob, c->pri.order);
-}
-
-// pdmpc_controller_explore_build behind its pdmpc_controller_build_step (build_members runs that part for all its members at once, then
-// this one per member): the step just built is instance 0, instances 1 .. n_perm - 1 permute its computation levels
-int permute_instances(pdmpc_controller* c, int32_t n_perm, uint32_t seed) {
-    int rc = PDMPC_OK;
-    const int n = c->n;
-    // base levels: the computation levels of the controller's own prioritization -- kahn of the sequential coupling the step was
-    // just built with, whatever the priority strategy (PrioritizedExplorativeController.m prepare_permutation :42-58 permutes
-    // kahn(iter.directed_coupling_sequential))
-    const std::vector<int32_t> levels0 = c->pri.levels;
-    const int n_levels = *std::max_element(levels0.begin(), levels0.end());
-    std::vector<int32_t> perms((size_t)n_perm * n_levels);
-    rc = pdmpc_exploration_permutations(n_levels, n_perm, seed, perms.data());
-    if (rc) return rc;
-    begin_instances(c, n_perm);
-    keep_instance(c, 0);
-    std::vector<int32_t> where;
-    for (int p = 1; p < n_perm; ++p) {
-        where.assign((size_t)n_levels + 1, 0);
-        for (int j = 0; j < n_levels; ++j) where[(size_t)perms[(size_t)p * n_levels + j]] = j + 1;
-        // prepare_permutation (:64-77): every coupling i -> j of the base prioritization whose permuted levels invert it is swapped
-        // in ALL coupling matrices (swap_entries_all_coupling_matrices): a sequential coupling stays sequential, a parallel one
-        // (cut by the grouping, or between vehicles of one level) stays parallel and keeps its direction
-        const Instance& I0 = c->inst[0];
-        c->pri.take_couplings(I0);
-        for (int i = 0; i < n; ++i)
-            for (int j = 0; j < n; ++j)
-                if (at(I0.directed, n, i, j) && where[(size_t)levels0[i]] > where[(size_t)levels0[j]]) {
-                    at(c->pri.directed, n, i, j) = 0;
-                    at(c->pri.directed, n, j, i) = 1;
-                    if (at(I0.directed_seq, n, i, j)) {
-                        at(c->pri.directed_seq, n, i, j) = 0;
-                        at(c->pri.directed_seq, n, j, i) = 1;
-                    }
-                }
-        rc = assemble_step(c, true);
-        if (rc) return rc;
-        keep_instance(c, p);
-    }
-    flatten_instances(c, n_perm);
-    return PDMPC_OK;
-}
-
-// pdmpc_controller_optimal_build behind its pdmpc_controller_build_step and the enumeration (build_members runs those for all its
-// members at once, then this one per member): the step's traffic state under each of the K unique prioritizations (masks, K x n priorities)
-int optimal_instances(pdmpc_controller* c, int64_t K, const uint32_t* masks, const int32_t* priorities) {
-    const int n = c->n;
-    c->o_masks.assign(masks, masks + K);
-    c->o_prio.assign(priorities, priorities + K * n);
-    begin_instances(c, (int)K);
-    for (int p = 0; p < (int)K; ++p) {
-        // ConstantPrioritizer on the given priorities + directed_coupling_from_priorities (Prioritizer.m:64-77): keep i -> j iff
-        // priority(i) <= priority(j); then assemble_step groups (cuts to max_num_CLs levels) per instance
-        const int32_t* pr = c->o_prio.data() + (size_t)p * n;
-        c->pri.directed.assign((size_t)n * n, 0);
-        for (int i = 0; i < n; ++i)
-            for (int j = 0; j < n; ++j)
-                if (at(c->adjacency, n, i, j) && !(pr[j] < pr[i])) at(c->pri.directed, n, i, j) = 1;
-        if (const int rc = assemble_step(c)) return rc;
-        keep_instance(c, p);
-    }
-    flatten_instances(c, (int)K);
-    return PDMPC_OK;
-}
-
 // ---- ONE step preparation over a span of members: a sweep's members, or the one controller that steps alone
 // the poses of the members `who` one after the other (and their lanelet polygons: with_lanelets)
 void gather(pdmpc_controller* const* members, PrepScratch::Call& C, const std::vector<int>& who, bool with_lanelets) {
@@ -1478,18 +90,18 @@ void gather(pdmpc_controller* const* members, PrepScratch::Call& C, const std::v
     C.lan_y.clear();
     for (int m : who) {
         pdmpc_controller* c = members[m];
-        C.x.insert(C.x.end(), c->mx.begin(), c->mx.end());
-        C.y.insert(C.y.end(), c->my.begin(), c->my.end());
-        C.cos_yaw.insert(C.cos_yaw.end(), c->reach_cos.begin(), c->reach_cos.end());
-        C.sin_yaw.insert(C.sin_yaw.end(), c->reach_sin.begin(), c->reach_sin.end());
-        C.trim.insert(C.trim.end(), c->trims.begin(), c->trims.end());
+        C.x.insert(C.x.end(), c->tr.mx.begin(), c->tr.mx.end());
+        C.y.insert(C.y.end(), c->tr.my.begin(), c->tr.my.end());
+        C.cos_yaw.insert(C.cos_yaw.end(), c->reach.cos_yaw.begin(), c->reach.cos_yaw.end());
+        C.sin_yaw.insert(C.sin_yaw.end(), c->reach.sin_yaw.begin(), c->reach.sin_yaw.end());
+        C.trim.insert(C.trim.end(), c->in.trims.begin(), c->in.trims.end());
         C.group_offset.push_back((int32_t)C.x.size());
         if (with_lanelets) {
-            lanelet_polygons(c);
-            const int32_t base = (int32_t)C.lan_x.size(), nl = c->lan_off[(size_t)c->n];
-            C.lan_x.insert(C.lan_x.end(), c->lan_x.begin(), c->lan_x.begin() + nl);
-            C.lan_y.insert(C.lan_y.end(), c->lan_y.begin(), c->lan_y.begin() + nl);
-            for (int v = 0; v < c->n; ++v) C.lan_off.push_back(base + c->lan_off[(size_t)v + 1]);
+            lanelet_polygons(c->sc, c->in, c->reach);
+            const int32_t base = (int32_t)C.lan_x.size(), nl = c->reach.lan_off[(size_t)c->sc.n];
+            C.lan_x.insert(C.lan_x.end(), c->reach.lan_x.begin(), c->reach.lan_x.begin() + nl);
+            C.lan_y.insert(C.lan_y.end(), c->reach.lan_y.begin(), c->reach.lan_y.begin() + nl);
+            for (int v = 0; v < c->sc.n; ++v) C.lan_off.push_back(base + c->reach.lan_off[(size_t)v + 1]);
         }
     }
     C.lan_x.push_back(0.0);  // (never empty)
@@ -1498,19 +110,19 @@ void gather(pdmpc_controller* const* members, PrepScratch::Call& C, const std::v
     for (size_t g = 0; g + 1 < C.group_offset.size(); ++g) entries += (size_t)(C.group_offset[g + 1] - C.group_offset[g]) * (C.group_offset[g + 1] - C.group_offset[g]);
     C.adjacency.assign(entries + 1, 0);
 }
-// the blocks of a grouped coupler call -> c->adjacency of the members that couple by reachable sets
+// the blocks of a grouped coupler call -> c->in.adjacency of the members that couple by reachable sets
 void scatter_blocks(pdmpc_controller* const* members, const PrepScratch::Call& C) {
     size_t block = 0;
     for (int m : C.who) {
         pdmpc_controller* c = members[m];
-        const size_t nn = (size_t)c->n * c->n;
-        if (c->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET) c->adjacency.assign(C.adjacency.begin() + block, C.adjacency.begin() + block + nn);
+        const size_t nn = (size_t)c->sc.n * c->sc.n;
+        if (c->sc.cfg.coupling == PDMPC_COUPLING_REACHABLE_SET) c->in.adjacency.assign(C.adjacency.begin() + block, C.adjacency.begin() + block + nn);
         block += nn;
     }
 }
 bool any_couples_by_sets(pdmpc_controller* const* members, const std::vector<int>& who) {
     for (int m : who)
-        if (members[m]->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET) return true;
+        if (members[m]->sc.cfg.coupling == PDMPC_COUPLING_REACHABLE_SET) return true;
     return false;
 }
 
@@ -1520,7 +132,7 @@ int bound_on_device(pdmpc_handle* h, pdmpc_controller* const* members, PrepScrat
     if (who.empty()) return PDMPC_OK;
     PrepScratch::Call& C = S.call;
     gather(members, C, who, true);
-    const int Hp = members[who[0]]->Hp, sets_each = all_steps ? Hp : 1, n = C.group_offset.back();
+    const int Hp = members[who[0]]->sc.Hp, sets_each = all_steps ? Hp : 1, n = C.group_offset.back();
     const pdmpc_polygon_set lan = view_polygons(C.lan_off, C.lan_x, C.lan_y);
     C.set_off.assign((size_t)n * sets_each + 1, 0);
     S.prep_calls[0] += 1;
@@ -1530,17 +142,17 @@ int bound_on_device(pdmpc_handle* h, pdmpc_controller* const* members, PrepScrat
     if (rc) return cfail(nullptr, rc, std::string("pdmpc_bound_reachable_sets: ") + pdmpc_last_error());
     for (size_t g = 0; g < who.size(); ++g) {  // every member's own sets, offsets from 0, as a bounding call for it alone leaves them
         pdmpc_controller* c = members[who[g]];
-        const size_t o0 = (size_t)C.group_offset[g] * sets_each, sets = (size_t)c->n * sets_each;
+        const size_t o0 = (size_t)C.group_offset[g] * sets_each, sets = (size_t)c->sc.n * sets_each;
         const int32_t a = C.set_off[o0], total = C.set_off[o0 + sets] - a;
-        c->bound_off.resize(sets + 1);
-        for (size_t o = 0; o <= sets; ++o) c->bound_off[o] = C.set_off[o0 + o] - a;
-        if (c->bound_x.size() < (size_t)total) {
-            c->bound_x.resize((size_t)total);
-            c->bound_y.resize((size_t)total);
+        c->reach.bound_off.resize(sets + 1);
+        for (size_t o = 0; o <= sets; ++o) c->reach.bound_off[o] = C.set_off[o0 + o] - a;
+        if (c->reach.bound_x.size() < (size_t)total) {
+            c->reach.bound_x.resize((size_t)total);
+            c->reach.bound_y.resize((size_t)total);
         }
-        std::copy(C.set_x.begin() + a, C.set_x.begin() + a + total, c->bound_x.begin());
-        std::copy(C.set_y.begin() + a, C.set_y.begin() + a + total, c->bound_y.begin());
-        adopt_bounded_sets(c, all_steps);
+        std::copy(C.set_x.begin() + a, C.set_x.begin() + a + total, c->reach.bound_x.begin());
+        std::copy(C.set_y.begin() + a, C.set_y.begin() + a + total, c->reach.bound_y.begin());
+        adopt_bounded_sets(c->sc, c->reach, all_steps);
     }
     if (!any_couples_by_sets(members, who)) return PDMPC_OK;
     S.prep_calls[1] += 1;
@@ -1557,16 +169,16 @@ int bound_on_host(pdmpc_controller* const* members, PrepScratch& S, const std::v
     for (int m : who) {
         pdmpc_controller* c = members[m];
         const bool all_steps = S.prep[(size_t)m].reach_parallel;
-        lanelet_polygons(c);
-        const pdmpc_polygon_set lan = view_polygons(c->lan_off, c->lan_x, c->lan_y), local = view_polygons(c->reach_off, c->reach_x, c->reach_y);
-        c->bound_off.assign((size_t)c->n * (all_steps ? c->Hp : 1) + 1, 0);
+        lanelet_polygons(c->sc, c->in, c->reach);
+        const pdmpc_polygon_set lan = view_polygons(c->reach.lan_off, c->reach.lan_x, c->reach.lan_y), local = view_polygons(c->sc.reach_off, c->sc.reach_x, c->sc.reach_y);
+        c->reach.bound_off.assign((size_t)c->sc.n * (all_steps ? c->sc.Hp : 1) + 1, 0);
         S.prep_calls[0] += 1;
-        const int rc = bound_with_room(c->bound_off, c->bound_x, c->bound_y, [&](int32_t cap, double* ox, double* oy) {
-            return pdmpc_bound_reachable_sets_host((int32_t)c->trim_speed.size(), c->Hp, &local, c->n, c->mx.data(), c->my.data(), c->reach_cos.data(), c->reach_sin.data(),
-                                                   c->trims.data(), &lan, all_steps, cap, c->bound_off.data(), ox, oy, nullptr);
+        const int rc = bound_with_room(c->reach.bound_off, c->reach.bound_x, c->reach.bound_y, [&](int32_t cap, double* ox, double* oy) {
+            return pdmpc_bound_reachable_sets_host((int32_t)c->sc.trim_speed.size(), c->sc.Hp, &local, c->sc.n, c->tr.mx.data(), c->tr.my.data(), c->reach.cos_yaw.data(), c->reach.sin_yaw.data(),
+                                                   c->in.trims.data(), &lan, all_steps, cap, c->reach.bound_off.data(), ox, oy, nullptr);
         });
         if (rc) return cfail(c, rc, "pdmpc_bound_reachable_sets_host failed");
-        adopt_bounded_sets(c, all_steps);
+        adopt_bounded_sets(c->sc, c->reach, all_steps);
     }
     if (!any_couples_by_sets(members, who)) return PDMPC_OK;
     gather(members, C, who, false);
@@ -1575,11 +187,11 @@ int bound_on_host(pdmpc_controller* const* members, PrepScratch& S, const std::v
     C.set_y.clear();
     for (int m : who) {
         pdmpc_controller* c = members[m];
-        const int sets_each = S.prep[(size_t)m].reach_parallel ? c->Hp : 1;
-        for (int v = 0; v < c->n; ++v) {
-            const int o = v * sets_each + sets_each - 1, a = c->bound_off[o], cnt = c->bound_off[o + 1] - a;
-            C.set_x.insert(C.set_x.end(), c->bound_x.begin() + a, c->bound_x.begin() + a + cnt);
-            C.set_y.insert(C.set_y.end(), c->bound_y.begin() + a, c->bound_y.begin() + a + cnt);
+        const int sets_each = S.prep[(size_t)m].reach_parallel ? c->sc.Hp : 1;
+        for (int v = 0; v < c->sc.n; ++v) {
+            const int o = v * sets_each + sets_each - 1, a = c->reach.bound_off[o], cnt = c->reach.bound_off[o + 1] - a;
+            C.set_x.insert(C.set_x.end(), c->reach.bound_x.begin() + a, c->reach.bound_x.begin() + a + cnt);
+            C.set_y.insert(C.set_y.end(), c->reach.bound_y.begin() + a, c->reach.bound_y.begin() + a + cnt);
             C.set_off.push_back((int32_t)C.set_x.size());
         }
     }
@@ -1615,12 +227,12 @@ int couple_hulls_on_host(pdmpc_controller* const* members, PrepScratch& S, const
         other.clear();
         for (int m : rest) {
             const pdmpc_controller* c = members[m];
-            (c->reach_off == c0->reach_off && c->reach_x == c0->reach_x && c->reach_y == c0->reach_y ? same : other).push_back(m);
+            (c->sc.reach_off == c0->sc.reach_off && c->sc.reach_x == c0->sc.reach_x && c->sc.reach_y == c0->sc.reach_y ? same : other).push_back(m);
         }
         gather(members, C, same, false);
-        const pdmpc_polygon_set ps = view_polygons(c0->reach_off, c0->reach_x, c0->reach_y);
+        const pdmpc_polygon_set ps = view_polygons(c0->sc.reach_off, c0->sc.reach_x, c0->sc.reach_y);
         S.prep_calls[2] += 1;
-        const int rc = pdmpc_reachable_set_coupling_grouped_host((int32_t)c0->trim_speed.size(), c0->Hp, &ps, (int32_t)same.size(), C.group_offset.data(), C.x.data(),
+        const int rc = pdmpc_reachable_set_coupling_grouped_host((int32_t)c0->sc.trim_speed.size(), c0->sc.Hp, &ps, (int32_t)same.size(), C.group_offset.data(), C.x.data(),
                                                                  C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(), C.trim.data(), C.adjacency.data(), nullptr);
         if (rc) return cfail(nullptr, rc, "pdmpc_reachable_set_coupling_grouped_host failed");
         scatter_blocks(members, C);
@@ -1641,22 +253,22 @@ int gather_fca(pdmpc_controller* const* members, PrepScratch::Fca& F, const std:
     size_t n = 0;
     for (size_t g = 0; g < who.size(); ++g) {
         pdmpc_controller* c = members[who[g]];
-        if (const int rc = fca_inputs(c)) return rc;
-        F.x.insert(F.x.end(), c->fca_x.begin(), c->fca_x.end());
-        F.y.insert(F.y.end(), c->fca_y.begin(), c->fca_y.end());
-        F.cos_yaw.insert(F.cos_yaw.end(), c->fca_cos.begin(), c->fca_cos.end());
-        F.sin_yaw.insert(F.sin_yaw.end(), c->fca_sin.begin(), c->fca_sin.end());
-        F.obstacles[g] = view_polygons(c->fca_obst_off, c->fca_obst_x, c->fca_obst_y);
+        if (!fca_inputs(c->sc, c->in, c->fca)) return cfail(c, PDMPC_ERR_INVALID, "FCA priorities need Hp >= 2 (calculate_yaw needs two reference points)");
+        F.x.insert(F.x.end(), c->fca.x.begin(), c->fca.x.end());
+        F.y.insert(F.y.end(), c->fca.y.begin(), c->fca.y.end());
+        F.cos_yaw.insert(F.cos_yaw.end(), c->fca.cos_yaw.begin(), c->fca.cos_yaw.end());
+        F.sin_yaw.insert(F.sin_yaw.end(), c->fca.sin_yaw.begin(), c->fca.sin_yaw.end());
+        F.obstacles[g] = view_polygons(c->fca.obst_off, c->fca.obst_x, c->fca.obst_y);
         pdmpc_fca_group& G = F.groups[g];
-        G.n = c->n;
-        G.n_pairs = (int32_t)(c->fca_pairs.size() / 2);
-        G.pairs = c->fca_pairs.data();
+        G.n = c->sc.n;
+        G.n_pairs = (int32_t)(c->fca.pairs.size() / 2);
+        G.pairs = c->fca.pairs.data();
         G.obstacles = &F.obstacles[g];
         G.dynamic_rows = nullptr;
-        G.length = c->cfg.vehicle_length;
-        G.width = c->cfg.vehicle_width;
-        G.offset = c->cfg.offset;
-        n += (size_t)c->n;
+        G.length = c->sc.cfg.vehicle_length;
+        G.width = c->sc.cfg.vehicle_width;
+        G.offset = c->sc.cfg.offset;
+        n += (size_t)c->sc.n;
     }
     F.collisions.assign(n, 0);
     F.priorities.assign(n, 0);
@@ -1677,7 +289,7 @@ int build_members(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, B
         ExploringAll(pdmpc_controller* const* ms, size_t n, bool o) : members(ms), M(n), on(o) { set(on); }
         ~ExploringAll() { set(false); }
         void set(bool v) {
-            for (size_t m = 0; on && m < M; ++m) members[m]->exploring = v;
+            for (size_t m = 0; on && m < M; ++m) members[m]->as.exploring = v;
         }
     } exploring(members, M, n_perm > 0 || batch.max_instances > 0);
     S.prep.assign(M, StepPrep());
@@ -1691,7 +303,7 @@ int build_members(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, B
         const StepPrep& P = S.prep[m];
         if (P.bounded)
             (P.reach_parallel ? bounded_all : bounded_last).push_back((int)m);
-        else if (members[m]->cfg.coupling == PDMPC_COUPLING_REACHABLE_SET)
+        else if (members[m]->sc.cfg.coupling == PDMPC_COUPLING_REACHABLE_SET)
             hulls.push_back((int)m);
     }
     int rc = PDMPC_OK;
@@ -1708,13 +320,13 @@ int build_members(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, B
     if (rc) return rc;
     std::vector<int> assessed;  // the members with FCA priorities: assessed together once every member's adjacency is there
     for (size_t m = 0; m < M; ++m) {
-        couple(members[m]);
-        if (members[m]->cfg.priority_strategy == PDMPC_PRIORITY_FCA) assessed.push_back((int)m);
+        couple(members[m]->sc, members[m]->tr, members[m]->in);
+        if (members[m]->sc.cfg.priority_strategy == PDMPC_PRIORITY_FCA) assessed.push_back((int)m);
     }
     PrepScratch::Fca& F = S.fca;
     if (!assessed.empty()) {
         if ((rc = gather_fca(members, F, assessed))) return rc;
-        const int Hp = members[0]->Hp;
+        const int Hp = members[0]->sc.Hp;
         S.prep_calls[3] += 1;
         rc = h ? pdmpc_fca_collisions_grouped(h, (int32_t)F.groups.size(), F.groups.data(), Hp, F.x.data(), F.y.data(), F.cos_yaw.data(), F.sin_yaw.data(), F.collisions.data(),
                                               F.priorities.data())
@@ -1727,10 +339,10 @@ int build_members(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, B
         const bool fca = g < assessed.size() && assessed[g] == (int)m;
         rc = finish_step(c, fca ? F.collisions.data() + v0 : nullptr, fca ? F.priorities.data() + v0 : nullptr);
         if (fca) {
-            v0 += (size_t)c->n;
+            v0 += (size_t)c->sc.n;
             ++g;
         }
-        if (!rc && n_perm > 0) rc = permute_instances(c, n_perm, (uint32_t)c->k);  // RandStream("mt19937ar", Seed = obj.k) (:249)
+        if (!rc && n_perm > 0) rc = permute_instances(c, n_perm, (uint32_t)c->tr.k);  // RandStream("mt19937ar", Seed = obj.k) (:249)
         if (rc) return rc;
     }
     if (batch.max_instances < 1) return PDMPC_OK;
@@ -1742,9 +354,9 @@ int build_members(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, B
     Q.n_out.assign(M, 0);
     size_t rows = 0;
     for (size_t m = 0; m < M; ++m) {
-        Q.group_n[m] = members[m]->n;
-        Q.adjacency[m] = members[m]->adjacency.data();
-        rows += (size_t)batch.max_instances * members[m]->n;
+        Q.group_n[m] = members[m]->sc.n;
+        Q.adjacency[m] = members[m]->in.adjacency.data();
+        rows += (size_t)batch.max_instances * members[m]->sc.n;
     }
     Q.masks.resize(M * (size_t)batch.max_instances);
     Q.priorities.resize(rows);
@@ -1757,166 +369,42 @@ int build_members(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, B
     for (size_t m = 0; m < M; ++m) {
         if ((rc = optimal_instances(members[m], Q.n_out[m], masks, priorities))) return rc;
         masks += Q.n_out[m];
-        priorities += Q.n_out[m] * members[m]->n;
+        priorities += Q.n_out[m] * members[m]->sc.n;
     }
     return PDMPC_OK;
 }
 
-// ---- the choice among the plans of a batch, and the step over a batch
-// The explorative choice as data: graph g = a weakly connected sub-graph (ordered by smallest vehicle), its candidates the n_perm
-// instances, cell (g, p) = the slots of instance p whose vehicles belong to g in ascending slot order (the order the twin adds in).
-void explore_describe(pdmpc_controller* c, ChoiceLists& D) {
-    const int n = c->n, K = (int)c->inst.size();
-    std::vector<int> label((size_t)n);
-    for (int i = 0; i < n; ++i) label[(size_t)i] = i;
-    auto find = [&](int a) {
-        while (label[(size_t)a] != a) a = label[(size_t)a] = label[(size_t)label[(size_t)a]];
-        return a;
-    };
-    const std::vector<uint8_t>& seq0 = c->inst[0].directed_seq;  // conncomp(directed_coupling_sequential) of the base prioritization (:94-112)
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j)
-            if (at(seq0, n, i, j) || at(seq0, n, j, i)) {
-                const int a = find(i), b = find(j);
-                if (a != b) label[(size_t)std::max(a, b)] = std::min(a, b);
-            }
-    std::vector<int> roots;
-    for (int i = 0; i < n; ++i)
-        if (find(i) == i) roots.push_back(i);  // ascending: the graphs ordered by their smallest vehicle
-    D.graph_of.resize((size_t)n);
-    for (int i = 0; i < n; ++i) D.graph_of[(size_t)i] = (int32_t)(std::lower_bound(roots.begin(), roots.end(), find(i)) - roots.begin());
-    const int G = (int)roots.size(), N = K * n;
-    D.graph_offset.resize((size_t)G + 1);
-    for (int g = 0; g <= G; ++g) D.graph_offset[(size_t)g] = g * K;
-    // cell (g, p) at g * K + p: counted, then filled in slot order
-    D.cell_offset.assign((size_t)G * K + 1, 0);
-    auto cell_of = [&](int s) { return D.graph_of[(size_t)c->x_vehicle[(size_t)s]] * K + c->x_instance[(size_t)s]; };
-    for (int s = 0; s < N; ++s) D.cell_offset[(size_t)cell_of(s) + 1] += 1;
-    for (int q = 0; q < G * K; ++q) D.cell_offset[(size_t)q + 1] += D.cell_offset[(size_t)q];
-    D.cell_slot.resize((size_t)N);
-    std::vector<int32_t> fill(D.cell_offset.begin(), D.cell_offset.end() - 1);
-    for (int s = 0; s < N; ++s) D.cell_slot[(size_t)fill[(size_t)cell_of(s)]++] = s;
-    D.clear_picks();
+// ---- how a step ends that the controller takes alone
+// a failure inside a step the controller takes alone is the controller's error too (the global message has it either way)
+int own(pdmpc_controller* c, int rc) {
+    if (rc) c->err = g_cerr;
+    return rc;
 }
-// every vehicle goes on with the couplings of the instance it chose (obj.iter = obj.iter_array_tmp{chosen_solution},
-// PrioritizedExplorativeController.m:157-158, PrioritizedOptimalController.m:100): its rows of both matrices -- follow_own (the step
-// applies the plans of the controller's OWN prioritization whatever was chosen): the couplings of instance 0 again, which is what
-// apply's fallback handling then sees
-void adopt_chosen_couplings(pdmpc_controller* c, bool follow_own) {
-    if (follow_own) return c->pri.take_couplings(c->inst[0]);
-    const size_t n = (size_t)c->n;
-    for (size_t i = 0; i < n; ++i) {
-        const Instance& I = c->inst[(size_t)c->x_chosen[i]];
-        std::copy_n(I.directed.begin() + i * n, n, c->pri.directed.begin() + i * n);
-        std::copy_n(I.directed_seq.begin() + i * n, n, c->pri.directed_seq.begin() + i * n);
-    }
+// the end of a step the controller takes alone: the records in c->out applied (timing[5]), and the step's parts added to the controller's sums
+int apply_and_account(pdmpc_controller* c) {
+    const auto t = std::chrono::steady_clock::now();
+    const int rc = pdmpc_controller_apply(c, c->out.data());
+    c->timing[5] = ms_since(t);
+    for (int i = 0; i < 6; ++i) c->timing_sum[i] += c->timing[i];
+    c->timing_steps += 1;
+    return rc;
 }
-// ... and what the sub-graphs chose becomes the controller's: cost table n_perm x n_graphs, the instance per vehicle, its couplings
-void explore_adopt(pdmpc_controller* c, const ChoiceLists& D, const int32_t* chosen, const double* cell_cost, bool follow_own) {
-    const int n = c->n, K = (int)c->inst.size(), G = D.n_graphs();
-    c->x_graphs = G;
-    c->x_cost.resize((size_t)K * G);
-    for (int p = 0; p < K; ++p)
-        for (int g = 0; g < G; ++g) c->x_cost[(size_t)p * G + g] = cell_cost[(size_t)g * K + p];
-    c->x_chosen.resize((size_t)n);
-    for (int i = 0; i < n; ++i) c->x_chosen[(size_t)i] = chosen[(size_t)D.graph_of[(size_t)i]];
-    adopt_chosen_couplings(c, follow_own);
-}
-
-// How a step over a batch of prioritizations chooses: the description of its choice (cells and graphs) and what adopts the result.
-struct BatchChoice {
-    void (*describe)(pdmpc_controller*, ChoiceLists&);
-    void (*adopt)(pdmpc_controller*, const ChoiceLists&, const int32_t*, const double*, bool follow_own);
-    bool graph_per_vehicle;  // the optimal-priority choice: vehicle v's graph is graph v (else its sub-graph)
+// a switch that is on for a scope: lean_explore (nobody looks at the plans that were not chosen: the explorative and optimal-priority
+// steps keep them all, their *_run loops do not), as.exploring (the memos of the obstacle sets, while a step's prioritizations are assembled)
+struct SwitchedOn {
+    bool& flag;
+    bool was;
+    explicit SwitchedOn(bool& f) : flag(f), was(f) { flag = true; }
+    ~SwitchedOn() { flag = was; }
 };
-// the choice on the host twin (status and cost-to-come of the final node per slot of the batch: all the choice looks at)
-int choose_on_host(pdmpc_controller* c, const BatchChoice& how, const int32_t* status, const double* final_cost, bool follow_own) {
-    ChoiceLists& D = c->choice;
-    how.describe(c, D);
-    c->choice_chosen.resize((size_t)D.n_graphs());
-    c->choice_cost.resize((size_t)D.n_cells());
-    const pdmpc_choice ch = D.view();
-    const int rc = pdmpc_choose_host(c->x_prob.n(), status, final_cost, &ch, c->choice_chosen.data(), c->choice_cost.data());
-    if (rc) return cfail(c, rc, pdmpc_last_error());
-    how.adopt(c, D, c->choice_chosen.data(), c->choice_cost.data(), follow_own);
-    return PDMPC_OK;
-}
-// ... from the first N records of the batch: their status and the cost-to-come of their final node
-int choose_from_records(pdmpc_controller* c, const BatchChoice& how, const pdmpc_vehicle_out* recs, int N, bool follow_own) {
-    c->x_status.resize((size_t)N);
-    c->x_final_cost.resize((size_t)N);
-    for (int s = 0; s < N; ++s) {
-        c->x_status[(size_t)s] = recs[s].status;
-        c->x_final_cost[(size_t)s] = recs[s].path_nodes[c->Hp][4];
-    }
-    return choose_on_host(c, how, c->x_status.data(), c->x_final_cost.data(), follow_own);
-}
-
-// Reading a batch's records back into the controller's own slot order.  The slot in the batch of the record vehicle v keeps if it goes
-// on with instance p -- follow_own: the record of instance 0, whatever it goes on with
-inline int32_t kept_slot(const pdmpc_controller* c, bool follow_own, int p, int v) { return c->x_slot[(size_t)(follow_own ? 0 : p) * c->n + v]; }
-// ... once the choice is made: of the vehicle in slot s of the controller's own order
-inline int32_t kept_slot_at(const pdmpc_controller* c, bool follow_own, int s) {
-    const int v = c->pri.order[(size_t)s];
-    return kept_slot(c, follow_own, c->x_chosen[(size_t)v], v);
-}
-// ... those records out of the records of the whole batch (c->x_out) as the step's records (c->out)
-void gather_kept_records(pdmpc_controller* c, bool follow_own) {
-    c->out.resize((size_t)c->n);
-    for (int s = 0; s < c->n; ++s) c->out[(size_t)s] = c->x_out[(size_t)kept_slot_at(c, follow_own, s)];
-}
-// ... and before the choice is made, the picks of a step that chooses on the device and keeps the chosen plans only: per slot of the
-// controller's own order the records its vehicle may keep, one per instance
-void pick_chosen_plans(pdmpc_controller* c, ChoiceLists& D, bool follow_own, bool graph_per_vehicle) {
-    const int n = c->n, K = (int)c->inst.size();
-    D.clear_picks();
-    for (int s = 0; s < n; ++s) {
-        const int v = c->pri.order[(size_t)s];
-        D.pick_graph.push_back(follow_own ? -1 : (graph_per_vehicle ? v : D.graph_of[(size_t)v]));
-        for (int p = 0; p < (follow_own ? 1 : K); ++p) D.pick_slot.push_back(kept_slot(c, follow_own, p, v));
-        D.pick_offset.push_back((int32_t)D.pick_slot.size());
-    }
-}
-
-const BatchChoice kExploreChoice = {explore_describe, explore_adopt, false};
-
-// compute_solution_cost / receive_solution_cost / choose_solution (:56-114): every vehicle sums the solution costs of ALL vehicles per
-// instance (its own first, then the others' messages in ascending index), rounds to 8 decimals and takes the first minimum
-// The optimal-priority choice as data: graph v = vehicle v, its candidates the K instances, cell (v, p) = vehicle v's slot of instance p,
-// then the other vehicles' slots of instance p in ascending vehicle index
-void optimal_describe(pdmpc_controller* c, ChoiceLists& D) {
-    const int n = c->n, K = (int)c->inst.size();
-    D.graph_of.clear();
-    D.graph_offset.resize((size_t)n + 1);
-    for (int v = 0; v <= n; ++v) D.graph_offset[(size_t)v] = v * K;
-    D.cell_offset.resize((size_t)n * K + 1);
-    for (int q = 0; q <= n * K; ++q) D.cell_offset[(size_t)q] = q * n;
-    D.cell_slot.resize((size_t)n * K * n);
-    int32_t* slot = D.cell_slot.data();
-    for (int v = 0; v < n; ++v)
-        for (int p = 0; p < K; ++p) {
-            *slot++ = c->x_slot[(size_t)p * n + v];
-            for (int j = 0; j < n; ++j)
-                if (j != v) *slot++ = c->x_slot[(size_t)p * n + j];
-        }
-    D.clear_picks();
-}
-void optimal_adopt(pdmpc_controller* c, const ChoiceLists&, const int32_t* chosen, const double* cell_cost, bool follow_own) {
-    const int n = c->n, K = (int)c->inst.size();
-    c->x_cost.assign(cell_cost, cell_cost + (size_t)n * K);  // row v = vehicle v's sums
-    c->x_chosen.assign(chosen, chosen + n);
-    c->x_graphs = K;
-    adopt_chosen_couplings(c, follow_own);
-}
-const BatchChoice kOptimalChoice = {optimal_describe, optimal_adopt, true};
 
 // One time step over a batch of prioritizations (explorative or optimal): the batch is built, ONE launch plans all of it, `choose`
-// picks per vehicle the instance it goes on with (c->x_chosen), and the chosen plans are applied.
+// picks per vehicle the instance it goes on with (c->x.chosen), and the chosen plans are applied.
 int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, bool follow_own, const BatchChoice& how) {
     c->timing[0] = ms_since(t);
-    const int N = c->x_prob.n();
+    const int N = c->x.prob.n();
     auto plan = [&](auto call, auto... rest) {
-        const int rc = plan_built(c->h, c->x_prob, c->last_pops.size() == (size_t)c->n, [&](int s) { return c->last_pops[(size_t)c->x_vehicle[(size_t)s]]; }, c->optimizer,
+        const int rc = plan_built(c->h, c->x.prob, c->tr.last_pops.size() == (size_t)c->sc.n, [&](int s) { return c->tr.last_pops[(size_t)c->x.vehicle[(size_t)s]]; }, c->optimizer,
                                   c->timing, call, rest...);
         t = std::chrono::steady_clock::now();
         return own(c, rc);
@@ -1925,37 +413,37 @@ int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, boo
     if (c->lean_explore && c->device_choice) {
         // the closed loop keeps the chosen plans only, and the choice and their gather run on the device directly behind the search: ONE
         // call and one read-back (the chosen records, the choice and the cost table)
-        c->x_out.clear();
-        ChoiceLists& D = c->choice;
+        c->x.out.clear();
+        ChoiceLists& D = c->x.choice;
         how.describe(c, D);
         pick_chosen_plans(c, D, follow_own, how.graph_per_vehicle);
-        c->choice_chosen.resize((size_t)D.n_graphs());
-        c->choice_cost.resize((size_t)D.n_cells());
-        c->out.resize((size_t)c->n);
+        c->x.choice_chosen.resize((size_t)D.n_graphs());
+        c->x.choice_cost.resize((size_t)D.n_cells());
+        c->out.resize((size_t)c->sc.n);
         const pdmpc_choice ch = D.view();
-        rc = plan(pdmpc_plan_step_chosen, &ch, c->choice_chosen.data(), c->choice_cost.data(), c->out.data());
+        rc = plan(pdmpc_plan_step_chosen, &ch, c->x.choice_chosen.data(), c->x.choice_cost.data(), c->out.data());
         if (rc) return rc;
-        how.adopt(c, D, c->choice_chosen.data(), c->choice_cost.data(), follow_own);
+        how.adopt(c, D, c->x.choice_chosen.data(), c->x.choice_cost.data(), follow_own);
     } else if (c->lean_explore) {
         // the closed loop keeps the chosen plans only (obj.iter = obj.iter_array_tmp{chosen_solution}, :157-158): status and final
         // cost of every plan come back for the choice, the chosen vehicles' records afterwards — not 2.9 KB for each of the N plans
-        c->x_out.clear();
-        c->x_status.resize((size_t)N);
-        c->x_final_cost.resize((size_t)N);
-        rc = plan(pdmpc_plan_step_lean, c->x_status.data(), c->x_final_cost.data());
+        c->x.out.clear();
+        c->x.status.resize((size_t)N);
+        c->x.final_cost.resize((size_t)N);
+        rc = plan(pdmpc_plan_step_lean, c->x.status.data(), c->x.final_cost.data());
         if (rc) return rc;
-        rc = choose_on_host(c, how, c->x_status.data(), c->x_final_cost.data(), follow_own);
+        rc = choose_on_host(c, how, c->x.status.data(), c->x.final_cost.data(), follow_own);
         if (rc) return rc;
-        std::vector<int32_t> want((size_t)c->n);
-        for (int s = 0; s < c->n; ++s) want[(size_t)s] = kept_slot_at(c, follow_own, s);
-        c->out.resize((size_t)c->n);
-        rc = pdmpc_fetch_records_at(c->h, c->n, want.data(), c->out.data());
+        std::vector<int32_t> want((size_t)c->sc.n);
+        for (int s = 0; s < c->sc.n; ++s) want[(size_t)s] = kept_slot_at(c, follow_own, s);
+        c->out.resize((size_t)c->sc.n);
+        rc = pdmpc_fetch_records_at(c->h, c->sc.n, want.data(), c->out.data());
         if (rc) return cfail(c, rc, pdmpc_last_error());
     } else {
-        c->x_out.resize((size_t)N);
-        rc = plan(pdmpc_plan_step, c->x_out.data());
+        c->x.out.resize((size_t)N);
+        rc = plan(pdmpc_plan_step, c->x.out.data());
         if (rc) return rc;
-        rc = choose_from_records(c, how, c->x_out.data(), N, follow_own);
+        rc = choose_from_records(c, how, c->x.out.data(), N, follow_own);
         if (rc) return rc;
         gather_kept_records(c, follow_own);
     }
@@ -1986,12 +474,12 @@ int pdmpc_controller_create(pdmpc_handle* handle, const pdmpc_controller_config*
     }
     pdmpc_controller* c = new pdmpc_controller();
     c->h = handle;
-    c->cfg = *cfg;
-    c->n = sc->n_vehicles;
-    c->Hp = cfg->Hp;
-    c->trim_speed.assign(sc->trim_speed, sc->trim_speed + sc->n_trims);
-    c->trim_steering.assign(sc->trim_steering, sc->trim_steering + sc->n_trims);
-    for (int v = 0; v < c->n; ++v) {
+    c->sc.cfg = *cfg;
+    c->sc.n = sc->n_vehicles;
+    c->sc.Hp = cfg->Hp;
+    c->sc.trim_speed.assign(sc->trim_speed, sc->trim_speed + sc->n_trims);
+    c->sc.trim_steering.assign(sc->trim_steering, sc->trim_steering + sc->n_trims);
+    for (int v = 0; v < c->sc.n; ++v) {
         VehicleDef d;
         d.x_start = sc->x_start[v];
         d.y_start = sc->y_start[v];
@@ -2010,7 +498,7 @@ int pdmpc_controller_create(pdmpc_handle* handle, const pdmpc_controller_config*
         d.is_loop = sc->is_loop ? sc->is_loop[v] != 0 : true;
         d.tile_dx = sc->tile_dx ? sc->tile_dx[v] : 0.0;
         d.tile_dy = sc->tile_dy ? sc->tile_dy[v] : 0.0;
-        c->veh.push_back(std::move(d));
+        c->sc.veh.push_back(std::move(d));
     }
     for (int l = 0; l < sc->n_lanelets; ++l) {
         Poly a, b;
@@ -2018,34 +506,34 @@ int pdmpc_controller_create(pdmpc_handle* handle, const pdmpc_controller_config*
         a.y.assign(sc->left_y + sc->left_offset[l], sc->left_y + sc->left_offset[l + 1]);
         b.x.assign(sc->right_x + sc->right_offset[l], sc->right_x + sc->right_offset[l + 1]);
         b.y.assign(sc->right_y + sc->right_offset[l], sc->right_y + sc->right_offset[l + 1]);
-        c->bl_left.push_back(std::move(a));
-        c->bl_right.push_back(std::move(b));
+        c->sc.bl_left.push_back(std::move(a));
+        c->sc.bl_right.push_back(std::move(b));
     }
     for (int p = 0; p < sc->obstacles.n_polygons; ++p) {
         Poly o;
         o.x.assign(sc->obstacles.x + sc->obstacles.offset[p], sc->obstacles.x + sc->obstacles.offset[p + 1]);
         o.y.assign(sc->obstacles.y + sc->obstacles.offset[p], sc->obstacles.y + sc->obstacles.offset[p + 1]);
-        c->static_obstacles.push_back(std::move(o));
+        c->sc.static_obstacles.push_back(std::move(o));
     }
-    c->fca_obst_off.assign(1, 0);
-    for (const Poly& o : c->static_obstacles) {
-        c->fca_obst_x.insert(c->fca_obst_x.end(), o.x.begin(), o.x.end());
-        c->fca_obst_y.insert(c->fca_obst_y.end(), o.y.begin(), o.y.end());
-        c->fca_obst_off.push_back((int32_t)c->fca_obst_x.size());
+    c->fca.obst_off.assign(1, 0);
+    for (const Poly& o : c->sc.static_obstacles) {
+        c->fca.obst_x.insert(c->fca.obst_x.end(), o.x.begin(), o.x.end());
+        c->fca.obst_y.insert(c->fca.obst_y.end(), o.y.begin(), o.y.end());
+        c->fca.obst_off.push_back((int32_t)c->fca.obst_x.size());
     }
     // Simulation.setup: initial speed = steering = 0 (Simulation.m:52-65)
-    c->mx.resize(c->n);
-    c->my.resize(c->n);
-    c->myaw.resize(c->n);
-    c->mspeed.assign(c->n, 0.0);
-    c->msteer.assign(c->n, 0.0);
-    for (int v = 0; v < c->n; ++v) {
-        c->mx[v] = c->veh[v].x_start;
-        c->my[v] = c->veh[v].y_start;
-        c->myaw[v] = c->veh[v].yaw_start;
+    c->tr.mx.resize(c->sc.n);
+    c->tr.my.resize(c->sc.n);
+    c->tr.myaw.resize(c->sc.n);
+    c->tr.mspeed.assign(c->sc.n, 0.0);
+    c->tr.msteer.assign(c->sc.n, 0.0);
+    for (int v = 0; v < c->sc.n; ++v) {
+        c->tr.mx[v] = c->sc.veh[v].x_start;
+        c->tr.my[v] = c->sc.veh[v].y_start;
+        c->tr.myaw[v] = c->sc.veh[v].yaw_start;
     }
-    c->info_old.assign(c->n, Plan());
-    c->infos.assign(c->n, Plan());
+    c->tr.info_old.assign(c->sc.n, Plan());
+    c->tr.infos.assign(c->sc.n, Plan());
     *out = c;
     return PDMPC_OK;
 }
@@ -2053,7 +541,7 @@ int pdmpc_controller_create(pdmpc_handle* handle, const pdmpc_controller_config*
 int pdmpc_controller_set_parallel_coupling(pdmpc_controller* c, int32_t mode) {
     if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
     if (mode != PDMPC_PARALLEL_PREVIOUS_TRAJECTORY && mode != PDMPC_PARALLEL_REACHABLE_SETS) return cfail(c, PDMPC_ERR_INVALID, "unknown parallel coupling mode");
-    c->parallel_mode = mode;
+    c->reach.parallel_mode = mode;
     return PDMPC_OK;
 }
 
@@ -2066,17 +554,17 @@ int pdmpc_controller_set_optimizer(pdmpc_controller* c, int32_t which) {
 
 int pdmpc_controller_priorities(pdmpc_controller* c, int32_t* n_priorities, const int32_t** priorities, int32_t* n_collisions, const int32_t** collisions) {
     if (!c || !n_priorities || !priorities || !n_collisions || !collisions) return cfail(c, PDMPC_ERR_INVALID, "null argument");
-    const bool has = c->cfg.priority_strategy != PDMPC_PRIORITY_COLORING, fca = c->cfg.priority_strategy == PDMPC_PRIORITY_FCA;
-    *n_priorities = has ? (int32_t)c->prio.size() : 0;
-    *priorities = c->prio.data();
-    *n_collisions = fca ? (int32_t)c->fca_count.size() : 0;
-    *collisions = c->fca_count.data();
+    const bool has = c->sc.cfg.priority_strategy != PDMPC_PRIORITY_COLORING, fca = c->sc.cfg.priority_strategy == PDMPC_PRIORITY_FCA;
+    *n_priorities = has ? (int32_t)c->fca.prio.size() : 0;
+    *priorities = c->fca.prio.data();
+    *n_collisions = fca ? (int32_t)c->fca.count.size() : 0;
+    *collisions = c->fca.count.data();
     return PDMPC_OK;
 }
 
 int pdmpc_controller_seeds(pdmpc_controller* c, int32_t* n, const uint32_t** seeds) {
     if (!c || !n || !seeds) return cfail(c, PDMPC_ERR_INVALID, "null argument");
-    const std::vector<uint32_t>& last = (c->batch_built_last ? c->x_prob : c->prob).seeds;
+    const std::vector<uint32_t>& last = (c->x.built_last ? c->x.prob : c->prob).seeds;
     *n = (int32_t)last.size();
     *seeds = last.data();
     return PDMPC_OK;
@@ -2084,15 +572,15 @@ int pdmpc_controller_seeds(pdmpc_controller* c, int32_t* n, const uint32_t** see
 
 int pdmpc_controller_set_lanelet_bounding(pdmpc_controller* c, int32_t on) {
     if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
-    c->lanelet_bounding = on != 0;
+    c->reach.lanelet_bounding = on != 0;
     return PDMPC_OK;
 }
 
 int pdmpc_controller_set_reachability(pdmpc_controller* c, const pdmpc_mpa* mpa) {
     if (!c || !mpa) return cfail(c, PDMPC_ERR_INVALID, "null argument");
-    if (mpa->Hp != c->Hp) return cfail(c, PDMPC_ERR_INVALID, "the automaton's Hp differs from the controller's");
-    if (mpa->n_trims != (int32_t)c->trim_speed.size()) return cfail(c, PDMPC_ERR_INVALID, "the automaton's trims differ from the scenario's");
-    c->has_reach = false;
+    if (mpa->Hp != c->sc.Hp) return cfail(c, PDMPC_ERR_INVALID, "the automaton's Hp differs from the controller's");
+    if (mpa->n_trims != (int32_t)c->sc.trim_speed.size()) return cfail(c, PDMPC_ERR_INVALID, "the automaton's trims differ from the scenario's");
+    c->reach.has = false;
     std::vector<int32_t> off((size_t)mpa->n_trims * mpa->Hp + 1, 0);
     int rc = pdmpc_local_reachable_sets(mpa, 0, off.data(), nullptr, nullptr);
     if (rc != PDMPC_OK && rc != PDMPC_ERR_CAPACITY) return cfail(c, rc, "pdmpc_local_reachable_sets failed");
@@ -2104,10 +592,10 @@ int pdmpc_controller_set_reachability(pdmpc_controller* c, const pdmpc_mpa* mpa)
         rc = pdmpc_upload_reachable_sets(c->h, mpa->n_trims, mpa->Hp, &ps);
         if (rc) return cfail(c, rc, std::string("pdmpc_upload_reachable_sets: ") + pdmpc_last_error());
     }
-    c->reach_off = std::move(off);
-    c->reach_x = std::move(x);
-    c->reach_y = std::move(y);
-    c->has_reach = true;
+    c->sc.reach_off = std::move(off);
+    c->sc.reach_x = std::move(x);
+    c->sc.reach_y = std::move(y);
+    c->reach.has = true;
     return PDMPC_OK;
 }
 
@@ -2119,17 +607,13 @@ int pdmpc_controller_destroy(pdmpc_controller* c) {
 // records of the step in slot order -> plans, exhaustion handling, fallbacks of coupled vehicles, plant update
 int pdmpc_controller_apply(pdmpc_controller* c, const pdmpc_vehicle_out* recs) {
     if (!c || !recs) return cfail(c, PDMPC_ERR_INVALID, "null argument");
-    const int n = c->n, Hp = c->Hp;
+    const int n = c->sc.n, Hp = c->sc.Hp;
     auto fallback_plan = [&](int i, Plan& p) -> bool {  // plan_fallback (:678-718): the previous plan shifted by one step
-        const Plan& old = c->info_old[i];
+        const Plan& old = c->tr.info_old[i];
         if (!old.present) return false;
         p.present = true;
         const size_t m = old.shapes.size();
-        p.shapes.resize(m);
-        p.trims.resize(m);
-        p.yx.resize(m);
-        p.yy.resize(m);
-        p.yyaw.resize(m);
+        p.resize(m);
         for (size_t q = 0; q < m; ++q) {
             const size_t from = std::min(q + 1, m - 1);
             p.shapes[q] = old.shapes[from];
@@ -2140,12 +624,12 @@ int pdmpc_controller_apply(pdmpc_controller* c, const pdmpc_vehicle_out* recs) {
         }
         return true;
     };
-    // The step's plans are built in c->infos — nothing else reads it — and swapped with c->info_old at the end: an error status or a
+    // The step's plans are built in c->tr.infos — nothing else reads it — and swapped with c->tr.info_old at the end: an error status or a
     // fallback in the first step leaves the controller's plans as they were, and the vectors of a plan keep their capacity from
     // step to step (they are overwritten entry by entry, not re-created).
-    std::vector<Plan>& infos = c->infos;
+    std::vector<Plan>& infos = c->tr.infos;
     infos.resize((size_t)n);
-    if (c->last_pops.size() != (size_t)n) c->last_pops.assign((size_t)n, 0.0);
+    if (c->tr.last_pops.size() != (size_t)n) c->tr.last_pops.assign((size_t)n, 0.0);
     for (int s = 0; s < n; ++s) {
         const int i = c->pri.order[s];
         const pdmpc_vehicle_out& r = recs[s];
@@ -2153,14 +637,10 @@ int pdmpc_controller_apply(pdmpc_controller* c, const pdmpc_vehicle_out* recs) {
         Plan& p = infos[i];
         p.present = p.needs_fallback = p.exhausted = false;
         p.n_expanded = r.n_expanded;
-        c->last_pops[(size_t)i] = (double)r.n_popped;
+        c->tr.last_pops[(size_t)i] = (double)r.n_popped;
         if (r.status == PDMPC_OK) {
             p.present = true;
-            p.shapes.resize((size_t)Hp);
-            p.trims.resize((size_t)Hp);
-            p.yx.resize((size_t)Hp);
-            p.yy.resize((size_t)Hp);
-            p.yyaw.resize((size_t)Hp);
+            p.resize((size_t)Hp);
             for (int q = 0; q < Hp; ++q) {
                 Poly& sh = p.shapes[q];
                 sh.x.assign(r.shapes[q][0], r.shapes[q][0] + r.shape_cols[q]);
@@ -2172,14 +652,14 @@ int pdmpc_controller_apply(pdmpc_controller* c, const pdmpc_vehicle_out* recs) {
             }
         } else {  // PrioritizedController.m:344-352
             p.exhausted = true;
-            const bool standstill = c->trim_speed[c->trims[i] - 1] == 0;
-            if (standstill && c->cfg.constraint_from_successor != PDMPC_SUCCESSOR_NONE) {  // handle_graph_search_exhaustion (:568-616)
+            const bool standstill = c->sc.trim_speed[c->in.trims[i] - 1] == 0;
+            if (standstill && c->sc.cfg.constraint_from_successor != PDMPC_SUCCESSOR_NONE) {  // handle_graph_search_exhaustion (:568-616)
                 p.present = true;
-                p.shapes.assign((size_t)Hp, c->occ_plain[i]);
-                p.trims.assign((size_t)Hp, c->trims[i]);
-                p.yx.assign((size_t)Hp, c->mx[i]);
-                p.yy.assign((size_t)Hp, c->my[i]);
-                p.yyaw.assign((size_t)Hp, c->myaw[i]);
+                p.shapes.assign((size_t)Hp, c->in.occ_plain[i]);
+                p.trims.assign((size_t)Hp, c->in.trims[i]);
+                p.yx.assign((size_t)Hp, c->tr.mx[i]);
+                p.yy.assign((size_t)Hp, c->tr.my[i]);
+                p.yyaw.assign((size_t)Hp, c->tr.myaw[i]);
             } else {
                 if (!fallback_plan(i, p)) return cfail(c, PDMPC_ERR_INVALID, "a vehicle needs a fallback in its first step");
                 p.needs_fallback = true;
@@ -2193,7 +673,7 @@ int pdmpc_controller_apply(pdmpc_controller* c, const pdmpc_vehicle_out* recs) {
         std::vector<int> fm((size_t)n * n, 0);
         for (int a = 0; a < n; ++a)
             for (int b = 0; b < n; ++b) {
-                int v = at(c->adjacency, n, a, b);
+                int v = at(c->in.adjacency, n, a, b);
                 if (infos[a].needs_fallback && at(c->pri.directed_seq, n, a, b)) v -= 1;
                 if (infos[b].needs_fallback && at(c->pri.directed_seq, n, b, a)) v -= 1;
                 fm[(size_t)a * n + b] = v;
@@ -2222,15 +702,15 @@ int pdmpc_controller_apply(pdmpc_controller* c, const pdmpc_vehicle_out* recs) {
                 p.needs_fallback = false;  // plan_fallback(is_fallback_while_planning = false)
             }
     }
-    std::swap(c->info_old, c->infos);
+    std::swap(c->tr.info_old, c->tr.infos);
     // Simulation.apply (Simulation.m:86-100)
     for (int i = 0; i < n; ++i) {
-        const Plan& p = c->info_old[i];
-        c->mx[i] = p.yx[0];
-        c->my[i] = p.yy[0];
-        c->myaw[i] = p.yyaw[0];
-        c->mspeed[i] = c->trim_speed[p.trims[0] - 1];
-        c->msteer[i] = c->trim_steering[p.trims[0] - 1];
+        const Plan& p = c->tr.info_old[i];
+        c->tr.mx[i] = p.yx[0];
+        c->tr.my[i] = p.yy[0];
+        c->tr.myaw[i] = p.yyaw[0];
+        c->tr.mspeed[i] = c->sc.trim_speed[p.trims[0] - 1];
+        c->tr.msteer[i] = c->sc.trim_steering[p.trims[0] - 1];
     }
     return PDMPC_OK;
 }
@@ -2261,8 +741,8 @@ int pdmpc_controller_step(pdmpc_controller* c) {
     if (rc) return rc;
     c->timing[0] = ms_since(t);
     c->timing[4] = 0;
-    c->out.resize(c->n);
-    rc = plan_built(c->h, c->prob, c->last_pops.size() == (size_t)c->n, [&](int s) { return c->last_pops[(size_t)c->pri.order[(size_t)s]]; }, c->optimizer, c->timing,
+    c->out.resize(c->sc.n);
+    rc = plan_built(c->h, c->prob, c->tr.last_pops.size() == (size_t)c->sc.n, [&](int s) { return c->tr.last_pops[(size_t)c->pri.order[(size_t)s]]; }, c->optimizer, c->timing,
                     pdmpc_plan_step, c->out.data());
     if (rc) return own(c, rc);
     return apply_and_account(c);
@@ -2276,7 +756,7 @@ int pdmpc_controller_problem(pdmpc_controller* c, int32_t* n, const pdmpc_vehicl
                              const pdmpc_polygon_set** fallback, const int32_t** order, const int32_t** levels) {
     if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
     expose(c->prob, n, in, pred_offset, pred_index, fallback);
-    if (n) *n = c->n;  // (also before the first build)
+    if (n) *n = c->sc.n;  // (also before the first build)
     if (order) *order = c->pri.order.data();
     if (levels) *levels = c->pri.levels.data();
     return PDMPC_OK;
@@ -2284,71 +764,21 @@ int pdmpc_controller_problem(pdmpc_controller* c, int32_t* n, const pdmpc_vehicl
 
 int pdmpc_controller_state(pdmpc_controller* c, double* x, double* y, double* yaw, double* speed, double* steering, int32_t* needs_fallback, int32_t* time_step) {
     if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
-    for (int i = 0; i < c->n; ++i) {
-        if (x) x[i] = c->mx[i];
-        if (y) y[i] = c->my[i];
-        if (yaw) yaw[i] = c->myaw[i];
-        if (speed) speed[i] = c->mspeed[i];
-        if (steering) steering[i] = c->msteer[i];
-        if (needs_fallback) needs_fallback[i] = c->info_old[i].present && c->info_old[i].needs_fallback;
+    for (int i = 0; i < c->sc.n; ++i) {
+        if (x) x[i] = c->tr.mx[i];
+        if (y) y[i] = c->tr.my[i];
+        if (yaw) yaw[i] = c->tr.myaw[i];
+        if (speed) speed[i] = c->tr.mspeed[i];
+        if (steering) steering[i] = c->tr.msteer[i];
+        if (needs_fallback) needs_fallback[i] = c->tr.info_old[i].present && c->tr.info_old[i].needs_fallback;
     }
-    if (time_step) *time_step = c->k;
+    if (time_step) *time_step = c->tr.k;
     return PDMPC_OK;
 }
 
-// PrioritizedExplorativeController.computation_level_permutations (:241-309): n_perm x n_levels table, row-major, row 0 = 1..n;
-// rows up to n_levels form a Latin square built "fewest possibilities first" with random choices from
-// RandStream("mt19937ar", Seed = seed) / randi (:249, :283-286), a row that meets a dead end is drawn again; further rows
-// (the reference stops at n_levels; BASELINE config C5 asks for 64) are Fisher-Yates shuffles from the same stream.
-// The twin of pdmpc.explorative.computation_level_permutations.
 int pdmpc_exploration_permutations(int32_t n_levels, int32_t n_perm, uint32_t seed, int32_t* out) {
     if (n_levels < 1 || n_perm < 1 || !out) return cfail(nullptr, PDMPC_ERR_INVALID, "bad argument");
-    Mt19937ar rng(seed);
-    const int n = n_levels;
-    std::vector<std::vector<int32_t>> rows;
-    rows.emplace_back();
-    for (int j = 0; j < n; ++j) rows[0].push_back(j + 1);
-    while ((int)rows.size() < std::min(n_perm, n_levels)) {
-        std::vector<uint8_t> allowed((size_t)n * n, 1);  // [level][class]
-        for (int col = 0; col < n; ++col)
-            for (const auto& r : rows) allowed[(size_t)(r[(size_t)col] - 1) * n + col] = 0;
-        std::vector<int32_t> perm((size_t)n, 0);
-        bool ok = true;
-        for (int filled = 0; filled < n && ok; ++filled) {
-            int best_col = 0, best_cnt = n + 1;
-            for (int col = 0; col < n; ++col) {  // [n_possibilities, i_cell] = min(sum(is_level_allowed, 1)): the first minimum
-                int cnt = 0;
-                for (int l = 0; l < n; ++l) cnt += allowed[(size_t)l * n + col];
-                if (cnt < best_cnt) {
-                    best_cnt = cnt;
-                    best_col = col;
-                }
-            }
-            if (best_cnt == 0) {
-                ok = false;
-                break;
-            }
-            const int pick = rng.randi(best_cnt);  // 1-based position among find(is_level_allowed(:, i_cell))
-            int lvl = -1;
-            for (int l = 0, seen = 0; l < n; ++l)
-                if (allowed[(size_t)l * n + best_col] && ++seen == pick) {
-                    lvl = l;
-                    break;
-                }
-            perm[(size_t)best_col] = lvl + 1;
-            for (int col = 0; col < n; ++col) allowed[(size_t)lvl * n + col] = 0;
-            for (int l = 0; l < n; ++l) allowed[(size_t)l * n + best_col] = 1;
-        }
-        if (ok) rows.push_back(perm);
-    }
-    while ((int)rows.size() < n_perm) {
-        std::vector<int32_t> perm((size_t)n);
-        for (int j = 0; j < n; ++j) perm[(size_t)j] = j + 1;
-        for (int i = n - 1; i > 0; --i) std::swap(perm[(size_t)i], perm[(size_t)(rng.randi(i + 1) - 1)]);
-        rows.push_back(perm);
-    }
-    for (int p = 0; p < n_perm; ++p)
-        for (int j = 0; j < n; ++j) out[(size_t)p * n + j] = rows[(size_t)p][(size_t)j];
+    exploration_permutations(n_levels, n_perm, seed, out);
     return PDMPC_OK;
 }
 
@@ -2356,9 +786,7 @@ int pdmpc_exploration_permutations(int32_t n_levels, int32_t n_perm, uint32_t se
 // (slot = position), per-slot predecessor slots, per-slot areas to publish on exhaustion.  A step alone is a sweep of one member.
 int pdmpc_controller_build_step(pdmpc_controller* c) {
     if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
-    const int rc = build_members(c->h, &c, 1, BatchKind{}, c->prep);
-    if (rc) c->err = g_cerr;
-    return rc;
+    return own(c, build_members(c->h, &c, 1, BatchKind{}, c->prep));
 }
 
 // ---- the explorative step (twin of pdmpc.explorative.build_exploration_batch / choose_solution / explore_step)
@@ -2367,18 +795,18 @@ int pdmpc_controller_build_step(pdmpc_controller* c) {
 // of L in permutation p as its priority), slots ordered by (level, instance, slot).  Advances the time step like build_step.
 int pdmpc_controller_explore_build(pdmpc_controller* c, int32_t n_perm, uint32_t seed) {
     if (!c || n_perm < 1) return cfail(c, PDMPC_ERR_INVALID, "bad argument");
-    Exploring exploring(c);
+    SwitchedOn exploring(c->as.exploring);
     int rc = pdmpc_controller_build_step(c);  // instance 0: the controller's own prioritization
     if (rc) return rc;
     return permute_instances(c, n_perm, seed);
 }
 int pdmpc_controller_explore_problem(pdmpc_controller* c, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index,
                                      const pdmpc_polygon_set** fallback, const int32_t** instance, const int32_t** vehicle, const int32_t** level) {
-    if (!c || c->x_prob.in.empty()) return cfail(c, PDMPC_ERR_INVALID, "no exploration batch has been built");
-    expose(c->x_prob, n_slots, in, pred_offset, pred_index, fallback);
-    if (instance) *instance = c->x_instance.data();
-    if (vehicle) *vehicle = c->x_vehicle.data();
-    if (level) *level = c->x_level.data();
+    if (!c || c->x.prob.in.empty()) return cfail(c, PDMPC_ERR_INVALID, "no exploration batch has been built");
+    expose(c->x.prob, n_slots, in, pred_offset, pred_index, fallback);
+    if (instance) *instance = c->x.instance.data();
+    if (vehicle) *vehicle = c->x.vehicle.data();
+    if (level) *level = c->x.level.data();
     return PDMPC_OK;
 }
 
@@ -2387,11 +815,11 @@ int pdmpc_controller_explore_problem(pdmpc_controller* c, int32_t* n_slots, cons
 // instance infinitely expensive.  chosen[v] = instance of vehicle v's sub-graph; cost (may be NULL): n_perm x n_graphs, graphs
 // ordered by their smallest vehicle.  The chosen instances' couplings become the controller's (what apply's fallback handling sees).
 int pdmpc_controller_explore_choose(pdmpc_controller* c, const pdmpc_vehicle_out* recs, int32_t* chosen, int32_t* n_graphs, double* cost) {
-    if (!c || !recs || c->inst.empty()) return cfail(c, PDMPC_ERR_INVALID, "no exploration batch has been built");
-    if (const int rc = choose_from_records(c, kExploreChoice, recs, (int)c->inst.size() * c->n, false)) return rc;
-    if (chosen) std::copy(c->x_chosen.begin(), c->x_chosen.end(), chosen);
-    if (n_graphs) *n_graphs = c->x_graphs;
-    if (cost) std::copy(c->x_cost.begin(), c->x_cost.end(), cost);
+    if (!c || !recs || c->x.inst.empty()) return cfail(c, PDMPC_ERR_INVALID, "no exploration batch has been built");
+    if (const int rc = choose_from_records(c, kExploreChoice, recs, (int)c->x.inst.size() * c->sc.n, false)) return rc;
+    if (chosen) std::copy(c->x.chosen.begin(), c->x.chosen.end(), chosen);
+    if (n_graphs) *n_graphs = c->x.graphs;
+    if (cost) std::copy(c->x.cost.begin(), c->x.cost.end(), cost);
     return PDMPC_OK;
 }
 
@@ -2399,7 +827,7 @@ int pdmpc_controller_explore_choose(pdmpc_controller* c, const pdmpc_vehicle_out
 int pdmpc_controller_explore_step(pdmpc_controller* c, int32_t n_perm) {
     if (!c || !c->h) return cfail(c, PDMPC_ERR_INVALID, "controller has no backend handle");
     const auto t = std::chrono::steady_clock::now();
-    const int rc = pdmpc_controller_explore_build(c, n_perm, (uint32_t)(c->k + 1));  // RandStream("mt19937ar", Seed = obj.k) (:249)
+    const int rc = pdmpc_controller_explore_build(c, n_perm, (uint32_t)(c->tr.k + 1));  // RandStream("mt19937ar", Seed = obj.k) (:249)
     if (rc) return rc;
     return batch_step(c, t, c->follow_own, kExploreChoice);
 }
@@ -2418,82 +846,18 @@ int pdmpc_controller_explore_follow_own(pdmpc_controller* c, int32_t on) {
 
 int pdmpc_controller_explore_run(pdmpc_controller* c, int32_t n_perm, int32_t n_steps, double* ms) {
     if (!c) return cfail(c, PDMPC_ERR_INVALID, "null argument");
-    LeanRun lean(c);
+    SwitchedOn lean(c->lean_explore);
     return timed_steps(n_steps, ms, [&] { return pdmpc_controller_explore_step(c, n_perm); });
 }
 
 int pdmpc_controller_explore_result(pdmpc_controller* c, int32_t* chosen, int32_t* n_graphs, const double** cost, const pdmpc_vehicle_out** records) {
-    if (!c || c->x_chosen.empty()) return cfail(c, PDMPC_ERR_INVALID, "no explorative step has been chosen");
-    if (chosen) std::copy(c->x_chosen.begin(), c->x_chosen.end(), chosen);
-    if (n_graphs) *n_graphs = c->x_graphs;
-    if (cost) *cost = c->x_cost.data();
-    if (records) *records = c->x_out.empty() ? nullptr : c->x_out.data();
+    if (!c || c->x.chosen.empty()) return cfail(c, PDMPC_ERR_INVALID, "no explorative step has been chosen");
+    if (chosen) std::copy(c->x.chosen.begin(), c->x.chosen.end(), chosen);
+    if (n_graphs) *n_graphs = c->x.graphs;
+    if (cost) *cost = c->x.cost.data();
+    if (records) *records = c->x.out.empty() ? nullptr : c->x.out.data();
     return PDMPC_OK;
 }
-
-}  // extern "C"
-
-namespace {
-// Prioritizer.unique_priorities (Prioritizer.m:97-140) on the host: the twin of the device enumeration (csrc/priority_kernel.hip) and its
-// checker.  Every orientation is tested by peeling its sources off vertex by vertex over explicit edge lists (the kernel peels bit sets);
-// the priorities follow the smallest-index-first topological order (toposort(..., 'Order', 'stable')).
-// the enumeration behind pdmpc_unique_priorities_host and its grouped sibling (arguments checked by them): PDMPC_OK, or
-// PDMPC_ERR_CAPACITY with *why set
-int enumerate_on_host(int32_t n, const uint8_t* adjacency, int64_t max_out, int64_t* n_out, uint32_t* masks, int32_t* priorities, const char** why) {
-    *n_out = -1;
-    *why = "more than 64 vehicles";
-    if (n > 64) return PDMPC_ERR_CAPACITY;
-    std::vector<int> er, ec;  // [edge_row, edge_col] = find(triu(adjacency, 1)): by column, then by row
-    for (int c = 0; c < n; ++c)
-        for (int r = 0; r < c; ++r)
-            if (adjacency[(size_t)r * n + c]) {
-                er.push_back(r);
-                ec.push_back(c);
-            }
-    const int E = (int)er.size();
-    *why = "more than 32 coupling edges";
-    if (E > 32) return PDMPC_ERR_CAPACITY;
-    const uint64_t n_masks = 1ull << E;
-    std::vector<int> head((size_t)E), tail((size_t)E), indeg((size_t)n), order((size_t)n);
-    std::vector<uint8_t> placed((size_t)n);
-    // the lexicographically smallest topological order of orientation m, false if m has a cycle (Kahn, smallest available vertex first)
-    auto toposort = [&](uint64_t m) {
-        std::fill(indeg.begin(), indeg.end(), 0);
-        for (int e = 0; e < E; ++e) {
-            const bool flip = (m >> (E - 1 - e)) & 1u;  // dec2bin(m, E) == '1': edge 1 is the most significant bit
-            tail[(size_t)e] = flip ? ec[(size_t)e] : er[(size_t)e];
-            head[(size_t)e] = flip ? er[(size_t)e] : ec[(size_t)e];
-            ++indeg[(size_t)head[(size_t)e]];
-        }
-        std::fill(placed.begin(), placed.end(), 0);
-        for (int pos = 0; pos < n; ++pos) {
-            int v = 0;
-            while (v < n && (placed[(size_t)v] || indeg[(size_t)v] != 0)) ++v;
-            if (v == n) return false;
-            placed[(size_t)v] = 1;
-            order[(size_t)pos] = v;
-            for (int e = 0; e < E; ++e)
-                if (tail[(size_t)e] == v) --indeg[(size_t)head[(size_t)e]];
-        }
-        return true;
-    };
-    int64_t K = 0;
-    for (uint64_t m = 0; m < n_masks; ++m) {
-        if (!toposort(m)) continue;
-        if (K < max_out) {
-            masks[K] = (uint32_t)m;
-            for (int pos = 0; pos < n; ++pos) priorities[(size_t)K * n + order[(size_t)pos]] = pos + 1;  // priority(topological_order) = 1:n
-        }
-        ++K;
-    }
-    *n_out = K;
-    *why = "more unique prioritizations than max_out";
-    if (K > max_out) return PDMPC_ERR_CAPACITY;
-    return PDMPC_OK;
-}
-}  // namespace
-
-extern "C" {
 
 int pdmpc_unique_priorities_host(int32_t n, const uint8_t* adjacency, int64_t max_out, int64_t* n_out, uint32_t* masks, int32_t* priorities) {
     if (n_out) *n_out = -1;
@@ -2541,16 +905,14 @@ int pdmpc_controller_optimal_build(pdmpc_controller* c, int32_t max_instances) {
     if (!c || max_instances < 1) return cfail(c, PDMPC_ERR_INVALID, "bad argument");
     // traffic info and coupling of the step (and the controller's own problem, replaced by instance 0), the enumeration, the instances: a
     // sweep of one member
-    const int rc = build_members(c->h, &c, 1, BatchKind{0, max_instances}, c->prep);
-    if (rc) c->err = g_cerr;
-    return rc;
+    return own(c, build_members(c->h, &c, 1, BatchKind{0, max_instances}, c->prep));
 }
 
 int pdmpc_controller_optimal_choose(pdmpc_controller* c, const pdmpc_vehicle_out* recs, int32_t* chosen, double* cost) {
-    if (!c || !recs || c->inst.empty() || c->o_masks.size() != c->inst.size()) return cfail(c, PDMPC_ERR_INVALID, "no optimal-priority batch has been built");
-    if (const int rc = choose_from_records(c, kOptimalChoice, recs, (int)c->inst.size() * c->n, false)) return rc;
-    if (chosen) std::copy(c->x_chosen.begin(), c->x_chosen.end(), chosen);
-    if (cost) std::copy(c->x_cost.begin(), c->x_cost.end(), cost);
+    if (!c || !recs || c->x.inst.empty() || c->x.o_masks.size() != c->x.inst.size()) return cfail(c, PDMPC_ERR_INVALID, "no optimal-priority batch has been built");
+    if (const int rc = choose_from_records(c, kOptimalChoice, recs, (int)c->x.inst.size() * c->sc.n, false)) return rc;
+    if (chosen) std::copy(c->x.chosen.begin(), c->x.chosen.end(), chosen);
+    if (cost) std::copy(c->x.cost.begin(), c->x.cost.end(), cost);
     return PDMPC_OK;
 }
 
@@ -2565,16 +927,16 @@ int pdmpc_controller_optimal_step(pdmpc_controller* c, int32_t max_instances) {
 
 int pdmpc_controller_optimal_run(pdmpc_controller* c, int32_t max_instances, int32_t n_steps, double* ms) {
     if (!c) return cfail(c, PDMPC_ERR_INVALID, "null argument");
-    LeanRun lean(c);
+    SwitchedOn lean(c->lean_explore);
     return timed_steps(n_steps, ms, [&] { return pdmpc_controller_optimal_step(c, max_instances); });
 }
 
 int pdmpc_controller_optimal_result(pdmpc_controller* c, int32_t* chosen, int32_t* n_instances, const double** cost, const pdmpc_vehicle_out** records) {
-    if (!c || c->x_chosen.empty() || c->o_masks.size() != c->inst.size()) return cfail(c, PDMPC_ERR_INVALID, "no optimal-priority step has been chosen");
-    if (chosen) std::copy(c->x_chosen.begin(), c->x_chosen.end(), chosen);
-    if (n_instances) *n_instances = (int32_t)c->inst.size();
-    if (cost) *cost = c->x_cost.data();
-    if (records) *records = c->x_out.empty() ? nullptr : c->x_out.data();
+    if (!c || c->x.chosen.empty() || c->x.o_masks.size() != c->x.inst.size()) return cfail(c, PDMPC_ERR_INVALID, "no optimal-priority step has been chosen");
+    if (chosen) std::copy(c->x.chosen.begin(), c->x.chosen.end(), chosen);
+    if (n_instances) *n_instances = (int32_t)c->x.inst.size();
+    if (cost) *cost = c->x.cost.data();
+    if (records) *records = c->x.out.empty() ? nullptr : c->x.out.data();
     return PDMPC_OK;
 }
 
@@ -2614,6 +976,13 @@ struct pdmpc_sweep {
 
 namespace {
 int N_of(const pdmpc_sweep* s) { return s->first.back(); }
+// more plans than the handle's max_vehicles (without a handle: any number) are refused with `text`
+int refuse_beyond_handle(pdmpc_handle* h, int64_t plans, const char* text) {
+    pdmpc_config hc{};
+    int32_t has_mpa = 0;
+    if (h && pdmpc_get_config(h, &hc, &has_mpa) != PDMPC_OK) return cfail(nullptr, PDMPC_ERR_INVALID, "bad backend handle");
+    return h && plans > hc.max_vehicles ? cfail(nullptr, PDMPC_ERR_CAPACITY, text) : PDMPC_OK;
+}
 
 // A member's problem P as the slots of S from `first` on (first = 0: S starts over; whatever S held from that slot on goes): shallow
 // copies, the seeds along with them, predecessor slots shifted by `first`, and behind the last one the entry that keeps pred_index
@@ -2643,8 +1012,8 @@ int sweep_build(pdmpc_sweep* s) {
     for (size_t m = 0; m < M; ++m) {
         const pdmpc_controller* c = s->members[m];
         append_problem(s->prob, c->prob, s->first[m]);
-        s->member.insert(s->member.end(), (size_t)c->n, (int32_t)m);
-        for (int q = 0; q < c->n; ++q) s->member_slot.push_back(q);
+        s->member.insert(s->member.end(), (size_t)c->sc.n, (int32_t)m);
+        for (int q = 0; q < c->sc.n; ++q) s->member_slot.push_back(q);
     }
     s->built = true;
     return PDMPC_OK;
@@ -2655,7 +1024,7 @@ int sweep_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records, bool keep_reco
         pdmpc_controller* c = s->members[m];
         const pdmpc_vehicle_out* r = records + s->first[m];
         if (keep_records) {  // (pdmpc_controller_records: the member's own records, in its own slot order)
-            c->out.assign(r, r + c->n);
+            c->out.assign(r, r + c->sc.n);
             r = c->out.data();
         }
         if (const int rc = pdmpc_controller_apply(c, r)) return rc;
@@ -2668,33 +1037,35 @@ int sweep_guard(pdmpc_sweep* s, int rc) {
     if (rc) s->broken = true;
     return rc;
 }
+// ... and what every entry point that steps a sweep refuses first, in this order: an argument that is missing (its text), an earlier
+// failure, and (before: its text) a step whose build has not run
+int sweep_refusal(const pdmpc_sweep* s, bool missing, const char* missing_text, bool unbuilt = false, const char* before = nullptr) {
+    if (missing) return cfail(nullptr, PDMPC_ERR_INVALID, missing_text);
+    if (s->broken) return cfail(nullptr, PDMPC_ERR_INVALID, "an earlier step of the sweep failed: its members have advanced unevenly");
+    if (unbuilt) return cfail(nullptr, PDMPC_ERR_INVALID, before);
+    return PDMPC_OK;
+}
+// ... of a step over a batch of prioritizations
+int batch_refusal(const pdmpc_sweep* s, bool needs_handle) {
+    if (!s) return cfail(nullptr, PDMPC_ERR_INVALID, "null sweep");
+    return sweep_refusal(s, needs_handle && !s->h, "the sweep has no backend handle");
+}
 
 // ---- the explorative step of a sweep
 
 // what pdmpc_sweep_explore_* refuse before any member advances
 int explore_refusal(pdmpc_sweep* s, int32_t n_perm, bool needs_handle) {
-    if (!s) return cfail(nullptr, PDMPC_ERR_INVALID, "null sweep");
-    if (needs_handle && !s->h) return cfail(nullptr, PDMPC_ERR_INVALID, "the sweep has no backend handle");
-    if (s->broken) return cfail(nullptr, PDMPC_ERR_INVALID, "an earlier step of the sweep failed: its members have advanced unevenly");
+    if (const int rc = batch_refusal(s, needs_handle)) return rc;
     if (n_perm < 1) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_explore: n_perm < 1");
-    if (s->h) {
-        pdmpc_config hc{};
-        int32_t has_mpa = 0;
-        if (pdmpc_get_config(s->h, &hc, &has_mpa) != PDMPC_OK) return cfail(nullptr, PDMPC_ERR_INVALID, "bad backend handle");
-        if ((int64_t)N_of(s) * n_perm > hc.max_vehicles)
-            return cfail(nullptr, PDMPC_ERR_CAPACITY, "pdmpc_sweep_explore: the members' prioritizations are more plans than the handle's max_vehicles");
-    }
-    return PDMPC_OK;
+    return refuse_beyond_handle(s->h, (int64_t)N_of(s) * n_perm, "pdmpc_sweep_explore: the members' prioritizations are more plans than the handle's max_vehicles");
 }
 
 // what pdmpc_sweep_optimal_* refuse before any member advances
 int optimal_refusal(pdmpc_sweep* s, int32_t max_instances, bool needs_handle) {
-    if (!s) return cfail(nullptr, PDMPC_ERR_INVALID, "null sweep");
-    if (needs_handle && !s->h) return cfail(nullptr, PDMPC_ERR_INVALID, "the sweep has no backend handle");
-    if (s->broken) return cfail(nullptr, PDMPC_ERR_INVALID, "an earlier step of the sweep failed: its members have advanced unevenly");
+    if (const int rc = batch_refusal(s, needs_handle)) return rc;
     if (max_instances < 1) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_optimal: max_instances < 1");
     for (const pdmpc_controller* c : s->members)
-        if (c->n > 64) return cfail(nullptr, PDMPC_ERR_CAPACITY, "pdmpc_sweep_optimal: a member has more than 64 vehicles");
+        if (c->sc.n > 64) return cfail(nullptr, PDMPC_ERR_CAPACITY, "pdmpc_sweep_optimal: a member has more than 64 vehicles");
     return PDMPC_OK;
 }
 
@@ -2712,18 +1083,17 @@ int sweep_batch_build(pdmpc_sweep* s, BatchKind kind) {
     X.level.clear();
     for (size_t m = 0; m < M; ++m) {
         const pdmpc_controller* c = s->members[m];
-        append_problem(X.prob, c->x_prob, X.first[m]);
+        append_problem(X.prob, c->x.prob, X.first[m]);
         X.first.push_back(X.prob.n());
-        X.member.insert(X.member.end(), (size_t)c->x_prob.n(), (int32_t)m);
-        X.instance.insert(X.instance.end(), c->x_instance.begin(), c->x_instance.end());
-        X.vehicle.insert(X.vehicle.end(), c->x_vehicle.begin(), c->x_vehicle.end());
-        X.level.insert(X.level.end(), c->x_level.begin(), c->x_level.end());
+        X.member.insert(X.member.end(), (size_t)c->x.prob.n(), (int32_t)m);
+        X.instance.insert(X.instance.end(), c->x.instance.begin(), c->x.instance.end());
+        X.vehicle.insert(X.vehicle.end(), c->x.vehicle.begin(), c->x.vehicle.end());
+        X.level.insert(X.level.end(), c->x.level.begin(), c->x.level.end());
     }
     X.n_perm = kind.n_perm;
     X.optimal = kind.max_instances > 0;
     return PDMPC_OK;
 }
-int sweep_explore_build(pdmpc_sweep* s, int n_perm) { return sweep_batch_build(s, BatchKind{n_perm, 0}); }
 
 // the optimal-priority batches: what is known only once the couplings exist is refused here (the enumeration refuses a member with more
 // than 32 coupling edges or more than max_instances prioritizations)
@@ -2732,14 +1102,7 @@ int sweep_optimal_build(pdmpc_sweep* s, int max_instances) {
     const int rc = sweep_batch_build(s, BatchKind{0, max_instances});
     s->optimal_calls[0] = s->prep.prio.calls;
     if (rc) return rc;
-    if (s->h) {
-        pdmpc_config hc{};
-        int32_t has_mpa = 0;
-        if (pdmpc_get_config(s->h, &hc, &has_mpa) != PDMPC_OK) return cfail(nullptr, PDMPC_ERR_INVALID, "bad backend handle");
-        if (s->x.prob.n() > hc.max_vehicles)
-            return cfail(nullptr, PDMPC_ERR_CAPACITY, "pdmpc_sweep_optimal: the members' unique prioritizations are more plans than the handle's max_vehicles");
-    }
-    return PDMPC_OK;
+    return refuse_beyond_handle(s->h, s->x.prob.n(), "pdmpc_sweep_optimal: the members' unique prioritizations are more plans than the handle's max_vehicles");
 }
 
 // the concatenated batch as pdmpc_sweep_explore_problem / pdmpc_sweep_optimal_problem hand it out
@@ -2762,8 +1125,8 @@ int sweep_batch_apply(pdmpc_sweep* s, const BatchChoice& how, const pdmpc_vehicl
     const pdmpc_sweep::Batch& X = s->x;
     for (size_t m = 0; m < s->members.size(); ++m) {
         pdmpc_controller* c = s->members[m];
-        c->x_out.assign(records + X.first[m], records + X.first[m + 1]);
-        if (const int rc = choose_from_records(c, how, c->x_out.data(), X.first[m + 1] - X.first[m], follows_own(c, how))) return rc;
+        c->x.out.assign(records + X.first[m], records + X.first[m + 1]);
+        if (const int rc = choose_from_records(c, how, c->x.out.data(), X.first[m + 1] - X.first[m], follows_own(c, how))) return rc;
         gather_kept_records(c, follows_own(c, how));
         if (const int rc = pdmpc_controller_apply(c, c->out.data())) return rc;
     }
@@ -2811,7 +1174,7 @@ int sweep_batch_step(pdmpc_sweep* s, std::chrono::steady_clock::time_point t, co
     // (the work of the last step as the members' own steps over a batch hand it over)
     auto pops_of = [&](int q) {
         const pdmpc_controller* c = s->members[(size_t)X.member[(size_t)q]];
-        return c->last_pops.size() == (size_t)c->n ? c->last_pops[(size_t)X.vehicle[(size_t)q]] : 0.0;
+        return c->tr.last_pops.size() == (size_t)c->sc.n ? c->tr.last_pops[(size_t)X.vehicle[(size_t)q]] : 0.0;
     };
     concatenate_choices(s, how);
     const pdmpc_choice ch = X.all.view();
@@ -2821,7 +1184,7 @@ int sweep_batch_step(pdmpc_sweep* s, std::chrono::steady_clock::time_point t, co
     for (size_t m = 0; m < M; ++m) {
         pdmpc_controller* c = s->members[m];
         how.adopt(c, X.lists[m], X.chosen.data() + X.first_graph[m], X.cell_cost.data() + X.first_cell[m], follows_own(c, how));
-        c->x_out.clear();
+        c->x.out.clear();
         c->out.assign(X.picks.begin() + s->first[m], X.picks.begin() + s->first[m + 1]);
     }
     s->timing[4] = ms_since(t);
@@ -2842,23 +1205,18 @@ int pdmpc_sweep_create(pdmpc_handle* h, int32_t n_members, pdmpc_controller* con
         const pdmpc_controller* c = members[m];
         if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_create: null member");
         if (c->h != h) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_create: a member was not created on the sweep's handle");
-        if (c->Hp != members[0]->Hp) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_create: the members differ in Hp");
+        if (c->sc.Hp != members[0]->sc.Hp) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_create: the members differ in Hp");
         if (c->optimizer != members[0]->optimizer) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_create: the members select different optimizers");
         for (int q = 0; q < m; ++q)
             if (members[q] == c) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_create: a member is listed twice");
-        total += c->n;
+        total += c->sc.n;
     }
-    if (h) {
-        pdmpc_config hc{};
-        int32_t has_mpa = 0;
-        if (pdmpc_get_config(h, &hc, &has_mpa) != PDMPC_OK) return cfail(nullptr, PDMPC_ERR_INVALID, "bad backend handle");
-        if (total > hc.max_vehicles) return cfail(nullptr, PDMPC_ERR_CAPACITY, "pdmpc_sweep_create: the members have more vehicles than the handle's max_vehicles");
-    }
+    if (const int rc = refuse_beyond_handle(h, total, "pdmpc_sweep_create: the members have more vehicles than the handle's max_vehicles")) return rc;
     pdmpc_sweep* s = new pdmpc_sweep();
     s->h = h;
     s->members.assign(members, members + n_members);
     s->first.assign(1, 0);
-    for (int m = 0; m < n_members; ++m) s->first.push_back(s->first.back() + members[m]->n);
+    for (int m = 0; m < n_members; ++m) s->first.push_back(s->first.back() + members[m]->sc.n);
     *out = s;
     return PDMPC_OK;
 }
@@ -2869,8 +1227,7 @@ int pdmpc_sweep_destroy(pdmpc_sweep* s) {
 }
 
 int pdmpc_sweep_build(pdmpc_sweep* s) {
-    if (!s) return cfail(nullptr, PDMPC_ERR_INVALID, "null sweep");
-    if (s->broken) return cfail(nullptr, PDMPC_ERR_INVALID, "an earlier step of the sweep failed: its members have advanced unevenly");
+    if (const int rc = sweep_refusal(s, !s, "null sweep")) return rc;
     return sweep_guard(s, sweep_build(s));
 }
 
@@ -2884,15 +1241,12 @@ int pdmpc_sweep_problem(pdmpc_sweep* s, int32_t* n_slots, const pdmpc_vehicle_in
 }
 
 int pdmpc_sweep_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records) {
-    if (!s || !records) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
-    if (s->broken) return cfail(nullptr, PDMPC_ERR_INVALID, "an earlier step of the sweep failed: its members have advanced unevenly");
-    if (!s->built) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_apply before pdmpc_sweep_build");
+    if (const int rc = sweep_refusal(s, !s || !records, "null argument", s && !s->built, "pdmpc_sweep_apply before pdmpc_sweep_build")) return rc;
     return sweep_guard(s, sweep_apply(s, records, false));
 }
 
 int pdmpc_sweep_step(pdmpc_sweep* s) {
-    if (!s || !s->h) return cfail(nullptr, PDMPC_ERR_INVALID, "the sweep has no backend handle");
-    if (s->broken) return cfail(nullptr, PDMPC_ERR_INVALID, "an earlier step of the sweep failed: its members have advanced unevenly");
+    if (const int rc = sweep_refusal(s, !s || !s->h, "the sweep has no backend handle")) return rc;
     auto t = std::chrono::steady_clock::now();
     int rc = sweep_build(s);
     if (rc) return sweep_guard(s, rc);
@@ -2902,7 +1256,7 @@ int pdmpc_sweep_step(pdmpc_sweep* s) {
     // (the work of the last step as pdmpc_controller_step hands it over; a member's first step: 1 for each of its slots)
     auto pops_of = [&](int q) {
         const pdmpc_controller* c = s->members[(size_t)s->member[(size_t)q]];
-        return c->last_pops.size() == (size_t)c->n ? c->last_pops[(size_t)c->pri.order[(size_t)s->member_slot[(size_t)q]]] : 0.0;
+        return c->tr.last_pops.size() == (size_t)c->sc.n ? c->tr.last_pops[(size_t)c->pri.order[(size_t)s->member_slot[(size_t)q]]] : 0.0;
     };
     rc = plan_built(s->h, s->prob, true, pops_of, s->members[0]->optimizer, s->timing, pdmpc_plan_step, s->out.data());
     if (rc) return sweep_guard(s, rc);
@@ -2930,7 +1284,7 @@ int pdmpc_sweep_last_prep_calls(pdmpc_sweep* s, int32_t* calls4) {
 
 int pdmpc_sweep_explore_build(pdmpc_sweep* s, int32_t n_perm) {
     if (const int rc = explore_refusal(s, n_perm, false)) return rc;
-    return sweep_guard(s, sweep_explore_build(s, n_perm));
+    return sweep_guard(s, sweep_batch_build(s, BatchKind{n_perm, 0}));
 }
 
 int pdmpc_sweep_explore_problem(pdmpc_sweep* s, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index,
@@ -2940,16 +1294,14 @@ int pdmpc_sweep_explore_problem(pdmpc_sweep* s, int32_t* n_slots, const pdmpc_ve
 }
 
 int pdmpc_sweep_explore_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records) {
-    if (!s || !records) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
-    if (s->broken) return cfail(nullptr, PDMPC_ERR_INVALID, "an earlier step of the sweep failed: its members have advanced unevenly");
-    if (s->x.n_perm < 1) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_explore_apply before pdmpc_sweep_explore_build");
+    if (const int rc = sweep_refusal(s, !s || !records, "null argument", s && s->x.n_perm < 1, "pdmpc_sweep_explore_apply before pdmpc_sweep_explore_build")) return rc;
     return sweep_guard(s, sweep_batch_apply(s, kExploreChoice, records));
 }
 
 int pdmpc_sweep_explore_step(pdmpc_sweep* s, int32_t n_perm) {
     if (const int rc = explore_refusal(s, n_perm, true)) return rc;
     const auto t = std::chrono::steady_clock::now();
-    if (const int rc = sweep_explore_build(s, n_perm)) return sweep_guard(s, rc);
+    if (const int rc = sweep_batch_build(s, BatchKind{n_perm, 0})) return sweep_guard(s, rc);
     return sweep_guard(s, sweep_batch_step(s, t, kExploreChoice));
 }
 
@@ -2970,9 +1322,7 @@ int pdmpc_sweep_optimal_problem(pdmpc_sweep* s, int32_t* n_slots, const pdmpc_ve
 }
 
 int pdmpc_sweep_optimal_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records) {
-    if (!s || !records) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
-    if (s->broken) return cfail(nullptr, PDMPC_ERR_INVALID, "an earlier step of the sweep failed: its members have advanced unevenly");
-    if (!s->x.optimal) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_optimal_apply before pdmpc_sweep_optimal_build");
+    if (const int rc = sweep_refusal(s, !s || !records, "null argument", s && !s->x.optimal, "pdmpc_sweep_optimal_apply before pdmpc_sweep_optimal_build")) return rc;
     return sweep_guard(s, sweep_batch_apply(s, kOptimalChoice, records));
 }
 

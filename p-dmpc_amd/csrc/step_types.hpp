@@ -1,0 +1,204 @@
+// step_types.hpp — the records of the native step controller (step_controller.cpp, stage 1 of 6): polygons, matrix lists, plans,
+// vehicles, a step problem, a prioritization, a choice, and the parts of the controller's state that a step's inputs are made of.  Names
+// nothing but the C ABI.
+// (Every stage header compiles alone under -Wunused-function -Wunused-member-function, `make host-parts`: its helpers are inline, and a
+// member function that only a later stage calls is [[maybe_unused]].  Those warnings pass over both markers, so that compile checks the
+// layering only; the same target compiles all stages and the .cpp as one text with the markers taken out, which is the check for dead helpers.)
+#pragma once
+#include <chrono>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "../../include/pdmpc.h"
+
+namespace {
+struct Poly {  // 2 x V, MATLAB [x; y]
+    std::vector<double> x, y;
+    [[maybe_unused]] int n() const { return (int)x.size(); }
+};
+
+// (offsets, x, y) vectors viewed as a polygon set of off.size() - 1 polygons (no copy: the vectors outlive the view)
+inline pdmpc_polygon_set view_polygons(const std::vector<int32_t>& off, const std::vector<double>& x, const std::vector<double>& y) {
+    pdmpc_polygon_set ps;
+    ps.n_polygons = (int32_t)off.size() - 1;
+    ps.offset = off.data();
+    ps.x = x.data();
+    ps.y = y.data();
+    return ps;
+}
+
+// the non-zero entries of a matrix as lists: by row (idx[off[i] .. off[i + 1]) = the columns of row i) or by column (the rows of
+// column j), ascending in both forms
+struct Lists {
+    std::vector<int32_t> off, idx, fill;  // (fill: scratch of lists_by_column)
+    const int32_t* begin(int i) const { return idx.data() + off[i]; }
+    const int32_t* end(int i) const { return idx.data() + off[i + 1]; }
+};
+
+struct Plan {  // what the controller keeps of a vehicle's ControlResultsInfo (ControlResultsInfo.m:5-17)
+    bool present = false;
+    bool needs_fallback = false;
+    bool exhausted = false;
+    std::vector<Poly> shapes;         // Hp
+    std::vector<int32_t> trims;       // Hp
+    std::vector<double> yx, yy, yyaw; // Hp
+    int32_t n_expanded = 0;
+    [[maybe_unused]] void resize(size_t m) { shapes.resize(m), trims.resize(m), yx.resize(m), yy.resize(m), yyaw.resize(m); }
+};
+
+struct VehicleDef {
+    double x_start, y_start, yaw_start, reference_speed;
+    std::vector<double> px, py;             // reference path
+    std::vector<int32_t> lanelets_index;    // 1-based lanelet ids along the loop (empty: no lanelets, circle scenario)
+    std::vector<int32_t> points_index;      // 1-based index of the last path point of each of those lanelets
+    bool is_loop;
+    double tile_dx, tile_dy;
+};
+
+// A step problem in the C ABI's form (what pdmpc_plan_step takes; the polygon sets its entries point to live in the arena of the
+// controller that built them), with the sampled optimizer's seed and the expected work per slot.  One record wherever a problem lives.
+struct StepProblem {
+    std::vector<pdmpc_vehicle_in> in;
+    std::vector<pdmpc_polygon_set> fb;  // per slot: what its vehicle publishes if its search is exhausted
+    std::vector<int32_t> pred_offset, pred_index;
+    std::vector<uint32_t> seeds;   // time_step + vehicle_index (set_seeds; empty for a kept instance, which is never planned by itself)
+    std::vector<double> weights;   // plan_built's scratch
+    int n() const { return (int)in.size(); }
+    // a backend call on the problem: call(h, n_slots, in, pred_offset, pred_index, fallback, rest ...)
+    template <class Call, class... Rest>
+    int plan(Call call, pdmpc_handle* h, Rest... rest) const {
+        return call(h, n(), in.data(), pred_offset.data(), pred_index.data(), fb.data(), rest...);
+    }
+};
+// ... and the same five as every *_problem entry point hands them out
+inline void expose(const StepProblem& P, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index, const pdmpc_polygon_set** fallback) {
+    if (n_slots) *n_slots = P.n();
+    if (in) *in = P.in.data();
+    if (pred_offset) *pred_offset = P.pred_offset.data();
+    if (pred_index) *pred_index = P.pred_index.data();
+    if (fallback) *fallback = P.fb.data();
+}
+
+// A prioritization of the step's traffic state: the controller's own, and every instance of an explorative or optimal-priority batch
+struct Instance {
+    std::vector<uint8_t> directed, directed_seq;  // n x n row-major
+    std::vector<int32_t> levels, order, slot_of;
+    [[maybe_unused]] void take_couplings(const Instance& of) {
+        directed = of.directed;
+        directed_seq = of.directed_seq;
+    }
+};
+
+// A choice among the plans of a batch as pdmpc_choose_host / pdmpc_plan_step_chosen take it (pdmpc_choice): the lists, kept from step to step
+struct ChoiceLists {
+    std::vector<int32_t> cell_offset, cell_slot, graph_offset, pick_graph, pick_offset, pick_slot;
+    std::vector<int32_t> graph_of;  // the explorative choice: per vehicle its sub-graph
+    int n_cells() const { return cell_offset.empty() ? 0 : (int)cell_offset.size() - 1; }
+    int n_graphs() const { return graph_offset.empty() ? 0 : (int)graph_offset.size() - 1; }
+    int n_picks() const { return (int)pick_graph.size(); }
+    [[maybe_unused]] void clear_picks() {
+        pick_graph.clear();
+        pick_slot.clear();
+        pick_offset.assign(1, 0);
+    }
+    [[maybe_unused]] pdmpc_choice view() const {
+        pdmpc_choice ch{};
+        ch.n_cells = n_cells();
+        ch.n_graphs = n_graphs();
+        ch.n_picks = n_picks();
+        ch.cell_offset = cell_offset.data();
+        ch.cell_slot = cell_slot.data();
+        ch.graph_offset = graph_offset.data();
+        ch.pick_graph = pick_graph.data();
+        ch.pick_offset = pick_offset.data();
+        ch.pick_slot = pick_slot.data();
+        return ch;
+    }
+};
+
+inline uint8_t& at(std::vector<uint8_t>& m, int n, int i, int j) { return m[(size_t)i * n + j]; }
+inline uint8_t at(const std::vector<uint8_t>& m, int n, int i, int j) { return m[(size_t)i * n + j]; }
+
+// f(j) for the non-zero entries j of a matrix row, ascending.  Rows of the coupling matrices are mostly zero (a vehicle is coupled with
+// the few around it): eight entries per test.
+template <class F>
+inline void for_each_set(const uint8_t* row, int n, F&& f) {
+    int j = 0;
+    for (; j + 8 <= n; j += 8) {
+        uint64_t w;
+        std::memcpy(&w, row + j, 8);
+        if (w == 0) continue;
+        for (int q = 0; q < 8; ++q)
+            if (row[j + q]) f(j + q);
+    }
+    for (; j < n; ++j)
+        if (row[j]) f(j);
+}
+
+inline void lists_by_row(const std::vector<uint8_t>& M, int n, Lists& L) {
+    L.off.assign((size_t)n + 1, 0);
+    L.idx.clear();
+    for (int i = 0; i < n; ++i) {
+        for_each_set(M.data() + (size_t)i * n, n, [&](int j) { L.idx.push_back(j); });
+        L.off[i + 1] = (int32_t)L.idx.size();
+    }
+}
+inline void lists_by_column(int n, const Lists& by_row, Lists& L) {
+    L.off.assign((size_t)n + 1, 0);
+    for (int32_t j : by_row.idx) ++L.off[j + 1];
+    for (int j = 0; j < n; ++j) L.off[j + 1] += L.off[j];
+    L.idx.resize(by_row.idx.size());
+    L.fill.assign(L.off.begin(), L.off.end() - 1);
+    for (int i = 0; i < n; ++i)
+        for (const int32_t* q = by_row.begin(i); q != by_row.end(i); ++q) L.idx[L.fill[*q]++] = i;
+}
+
+inline double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
+
+// ---- the controller's state that a step's inputs are made of, by who writes it (the rest: step_state.hpp; step_inputs.hpp fills them)
+// the scenario and the automaton: written by pdmpc_controller_create / pdmpc_controller_set_reachability only
+struct Scenario {
+    pdmpc_controller_config cfg{};
+    int n = 0, Hp = 0;
+    std::vector<VehicleDef> veh;
+    std::vector<Poly> bl_left, bl_right;  // per lanelet boundary polylines (RoadDataCommonRoad.get_lanelet_boundary)
+    std::vector<Poly> static_obstacles;
+    std::vector<double> trim_speed, trim_steering;
+    // the automaton's local reachable hulls, polygon trim * Hp + k (pdmpc_controller_set_reachability)
+    std::vector<int32_t> reach_off;
+    std::vector<double> reach_x, reach_y;
+};
+// what is carried from step to step: written by pdmpc_controller_apply (k: advanced by begin_step)
+struct Traffic {
+    int k = 0;
+    std::vector<double> mx, my, myaw, mspeed, msteer;  // measurements
+    std::vector<Plan> info_old, infos;
+    std::vector<double> last_pops;  // per vehicle: nodes its search popped in the last step (the next step's expected work, pdmpc_set_step_weights)
+};
+// what a step reads of the traffic: rewritten by traffic_info and the coupling every step
+struct StepInputs {
+    std::vector<int32_t> trims;
+    std::vector<Poly> occ_offset, occ_plain;
+    std::vector<std::vector<double>> ref_x, ref_y, v_ref;
+    std::vector<Poly> bnd_left, bnd_right;
+    std::vector<uint8_t> adjacency;  // n x n row-major
+};
+// reachable sets: the switches, and per step every vehicle's Hp sets at its pose, closed (HighLevelController.m:219-263)
+struct ReachState {
+    int parallel_mode = PDMPC_PARALLEL_PREVIOUS_TRAJECTORY;
+    bool has = false;  // the scenario holds the local hulls
+    std::vector<std::vector<Poly>> sets;
+    std::vector<double> cos_yaw, sin_yaw;
+    // lanelet bounding of those sets (pdmpc_controller_set_lanelet_bounding): the raw lanelet polygons and the bounded sets of the step
+    bool lanelet_bounding = false;
+    std::vector<int32_t> bound_off, lan_off;
+    std::vector<double> bound_x, bound_y, lan_x, lan_y;
+};
+// priorities of the random and FCA strategies (1-based per vehicle) and the FCA inputs of the step: every reference point with the
+// cos / sin of its calculate_yaw heading, the coupled pairs a < b, the collision counts, the scenario's obstacles as one polygon set
+struct FcaInputs {
+    std::vector<int32_t> prio, pairs, count, obst_off;
+    std::vector<double> x, y, cos_yaw, sin_yaw, obst_x, obst_y;
+};
+}  // namespace

@@ -76,7 +76,7 @@ def computation_level_permutations(n_levels, n_perm, seed):
 
 
 def native_computation_level_permutations(n_levels, n_perm, seed):
-    """The same table from libpdmpc_hip.so (pdmpc_exploration_permutations, csrc/step_controller.cpp): the native twin."""
+    """The same table from libpdmpc_hip.so (pdmpc_exploration_permutations, csrc/step_priorities.hpp): the native twin."""
     from . import abi, backend
 
     L = backend.load_library()

@@ -1,4 +1,4 @@
-"""ctypes wrapper of the native step controller (csrc/step_controller.cpp, declared in include/pdmpc.h).
+"""ctypes wrapper of the native step controller (csrc/step_controller.cpp and its stages csrc/step_*.hpp, declared in include/pdmpc.h).
 
 `NativeController` is the C++ twin of `pdmpc.controller.PrioritizedSequentialController` (constant and colouring priorities,
 full / distance / reachable-set coupling, parallel predecessors by previous plan or by reachable sets, GreedyCutter grouping): a whole MPC time step — traffic info, coupling, levels, obstacle assembly,
@@ -398,26 +398,34 @@ class NativeSweep:
         for m in self.members:
             m.n_perm = n_perm
 
-    def explore_problem(self):
-        """The concatenated batch of the last explore_build, decoded as NativeController.explore_problem decodes a member's, plus the
-        member per slot."""
+    def _batch_problem(self, name):
+        """the concatenated batch behind the entry point `name`, decoded as NativeController.explore_problem decodes a member's, plus the
+        member per slot"""
         n = C.c_int32()
         vin = C.POINTER(abi.VehicleIn)()
         po, pi, mem, inst, veh, lvl = (abi.c_int32_p() for _ in range(6))
         fb = C.POINTER(abi.PolygonSet)()
-        self._check(self.L.pdmpc_sweep_explore_problem(self.s, C.byref(n), C.byref(vin), C.byref(po), C.byref(pi), C.byref(fb), C.byref(mem), C.byref(inst), C.byref(veh),
-                                                       C.byref(lvl)), "pdmpc_sweep_explore_problem")
+        self._check(getattr(self.L, name)(self.s, C.byref(n), C.byref(vin), C.byref(po), C.byref(pi), C.byref(fb), C.byref(mem), C.byref(inst), C.byref(veh), C.byref(lvl)), name)
         iters, preds, fallback = self.members[0]._decode(n.value, vin, po, pi, fb)
         col = lambda a: [int(a[q]) for q in range(n.value)]  # noqa: E731
         return {"iters": iters, "preds": preds, "fallback": fallback, "member": col(mem), "instance": col(inst), "vehicle": col(veh), "levels": col(lvl)}
 
-    def explore_apply(self, records):
-        """The records of every slot of the concatenated batch: the choice per member on the host, every member's apply."""
+    def _batch_apply(self, name, kind, records):
+        """the records of every slot of the concatenated batch (`kind`, for the message) to the entry point `name`"""
         recs = np.ascontiguousarray(records)
         want = sum(m.n * m.n_perm for m in self.members)
         if recs.shape[0] != want:
-            raise ValueError("the explorative batch of this sweep has %d slots, not %d" % (want, recs.shape[0]))
-        self._check(self.L.pdmpc_sweep_explore_apply(self.s, abi.out_ptr(recs)), "pdmpc_sweep_explore_apply")
+            raise ValueError("the %s batch of this sweep has %d slots, not %d" % (kind, want, recs.shape[0]))
+        self._check(getattr(self.L, name)(self.s, abi.out_ptr(recs)), name)
+
+    def explore_problem(self):
+        """The concatenated batch of the last explore_build, decoded as NativeController.explore_problem decodes a member's, plus the
+        member per slot."""
+        return self._batch_problem("pdmpc_sweep_explore_problem")
+
+    def explore_apply(self, records):
+        """The records of every slot of the concatenated batch: the choice per member on the host, every member's apply."""
+        self._batch_apply("pdmpc_sweep_explore_apply", "explorative", records)
 
     def explore_step(self, n_perm):
         """One explorative lock-step natively -> every member's kept (chosen) records in its own slot order."""
@@ -449,23 +457,11 @@ class NativeSweep:
 
     def optimal_problem(self):
         """The concatenated batch of the last optimal_build, decoded as explore_problem decodes the explorative one."""
-        n = C.c_int32()
-        vin = C.POINTER(abi.VehicleIn)()
-        po, pi, mem, inst, veh, lvl = (abi.c_int32_p() for _ in range(6))
-        fb = C.POINTER(abi.PolygonSet)()
-        self._check(self.L.pdmpc_sweep_optimal_problem(self.s, C.byref(n), C.byref(vin), C.byref(po), C.byref(pi), C.byref(fb), C.byref(mem), C.byref(inst), C.byref(veh),
-                                                       C.byref(lvl)), "pdmpc_sweep_optimal_problem")
-        iters, preds, fallback = self.members[0]._decode(n.value, vin, po, pi, fb)
-        col = lambda a: [int(a[q]) for q in range(n.value)]  # noqa: E731
-        return {"iters": iters, "preds": preds, "fallback": fallback, "member": col(mem), "instance": col(inst), "vehicle": col(veh), "levels": col(lvl)}
+        return self._batch_problem("pdmpc_sweep_optimal_problem")
 
     def optimal_apply(self, records):
         """The records of every slot of the concatenated batch: the choice per member on the host, every member's apply."""
-        recs = np.ascontiguousarray(records)
-        want = sum(m.n * m.n_perm for m in self.members)
-        if recs.shape[0] != want:
-            raise ValueError("the optimal-priority batch of this sweep has %d slots, not %d" % (want, recs.shape[0]))
-        self._check(self.L.pdmpc_sweep_optimal_apply(self.s, abi.out_ptr(recs)), "pdmpc_sweep_optimal_apply")
+        self._batch_apply("pdmpc_sweep_optimal_apply", "optimal-priority", records)
 
     def optimal_step(self, max_instances):
         """One optimal-priority lock-step natively -> every member's kept (chosen) records in its own slot order."""

@@ -13,7 +13,7 @@ Restates the host side of the reference's optimal-priority controller
 
 The reference plans the orientations one after the other.  Here all K instances are flattened into ONE batch exactly as the
 explorative step flattens its permutations (pdmpc.explorative.flatten_instances): slots ordered by (level, instance, slot).
-The native twin is pdmpc_controller_optimal_* (csrc/step_controller.cpp); the enumeration runs on the device there
+The native twin is pdmpc_controller_optimal_* (csrc/step_controller.cpp, csrc/step_batch.hpp); the enumeration runs on the device there
 (pdmpc_unique_priorities, csrc/priority_kernel.hip).
 """
 import heapq

@@ -1,4 +1,4 @@
-"""Host cost of building a step problem in the native controller (csrc/step_controller.cpp), without a GPU: the closed loop is driven by the
+"""Host cost of building a step problem in the native controller (csrc/step_controller.cpp: build_members and the stages csrc/step_*.hpp), without a GPU: the closed loop is driven by the
 oracle as planner for a few steps, then pdmpc_controller_build_step is timed on the reached traffic state (the build does not advance the
 state, so it can be repeated).  usage: python tools/dbg_build_cost.py c3|c4 [steps]"""
 import sys, time, os
