@@ -194,6 +194,15 @@ int pdmpc_mpa_reach_host(const pdmpc_mpa* mpa, double* dmax, double* amax);
  * per segment of every step). */
 int pdmpc_reach_lists_host(int32_t Hp, double dmax, double amax, double root_x, double root_y, const double* x, const double* y, const int32_t* step_first,
                            const int32_t* step_count, int32_t* list_offset, int32_t* list);
+/* The automaton's reach rectangles (include/pdmpc_reach.h, the oriented rule): rects[(r * Hp + k - 1) * 4 ..] = (x_lo, x_hi,
+ * y_lo, y_hi), in the frame of a root at the origin with yaw 0 in trim r + 1, of every point of every area (three variants, used columns)
+ * a graph search can check at step k = 1 .. Hp under the transition masks of steps 1 .. k; NaN where there is none.  rects holds
+ * n_trims * Hp * 4 doubles, 1 <= Hp <= mpa.Hp.  pdmpc_upload_mpa stores the table of config.Hp behind dmax and amax. */
+int pdmpc_mpa_reach_rects_host(const pdmpc_mpa* mpa, int32_t Hp, double* rects);
+/* pdmpc_reach_lists_host by the oriented rule: the root has yaw root_yaw and trim root_trim (1-based), rects is the table of
+ * pdmpc_mpa_reach_rects_host for n_trims trims and this Hp.  The host twin of the lists the graph-search kernel builds. */
+int pdmpc_reach_lists_oriented_host(int32_t Hp, int32_t n_trims, const double* rects, int32_t root_trim, double root_x, double root_y, double root_yaw, const double* x, const double* y,
+                                    const int32_t* step_first, const int32_t* step_count, int32_t* list_offset, int32_t* list);
 
 /* Plans n independent vehicles (one computation level).  Blocking.  With n == 1 this is
  * GraphSearch.run_optimizer (GraphSearch.m:14-17). */

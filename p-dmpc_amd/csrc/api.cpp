@@ -616,6 +616,130 @@ int pdmpc_reach_lists_host(int32_t Hp, double dmax, double amax, double root_x, 
     return PDMPC_OK;
 }
 
+// The automaton's reach rectangles (include/pdmpc_reach.h, the oriented rule): rects[(r * Hp + K - 1) * 4 ..] = (x_lo, x_hi, y_lo, y_hi), in
+// the frame of a root at the origin with yaw 0 in trim r, of every point of every area (three variants, used columns) of a maneuver
+// of step K that the transition masks of steps 1 .. K allow; NaN where no such maneuver exists.  Paths are not enumerated: convex
+// hulls compose — hull(i, k -> K) = hull of the union over the successors j of i at step k of maneuver(i, j) applied to
+// hull(j, k + 1 -> K), the areas of the maneuvers leaving i at step K being the base case — and the bounding box of the hull is the
+// bounding box of the union.  n * Hp^2 / 2 hulls of a few hundred points.
+namespace {
+typedef std::pair<double, double> ReachPt;
+// convex hull in place (Andrew's monotone chain; collinear points dropped, which moves no bounding box)
+void reach_hull(std::vector<ReachPt>& P, std::vector<ReachPt>& H) {
+    std::sort(P.begin(), P.end());
+    P.erase(std::unique(P.begin(), P.end()), P.end());
+    const size_t n = P.size();
+    if (n < 3) return;
+    auto cross = [](const ReachPt& o, const ReachPt& a, const ReachPt& b) { return (a.first - o.first) * (b.second - o.second) - (a.second - o.second) * (b.first - o.first); };
+    H.clear();
+    for (size_t i = 0; i < n; ++i) {
+        while (H.size() >= 2 && cross(H[H.size() - 2], H.back(), P[i]) <= 0) H.pop_back();
+        H.push_back(P[i]);
+    }
+    const size_t lower = H.size() + 1;
+    for (size_t i = n - 1; i-- > 0;) {
+        while (H.size() >= lower && cross(H[H.size() - 2], H.back(), P[i]) <= 0) H.pop_back();
+        H.push_back(P[i]);
+    }
+    H.pop_back();
+    P.swap(H);
+}
+void mpa_reach_rects(const pdmpc_mpa* mpa, int Hp, double* rects) {
+    const int n = mpa->n_trims, T = mpa->n_maneuvers;
+    const double qnan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<double> cs((size_t)std::max(T, 1)), sn((size_t)std::max(T, 1));
+    for (int t = 0; t < T; ++t) pdmpc_sincos(mpa->maneuvers[t].dyaw, &sn[t], &cs[t]);
+    auto maneuver = [&](int k, int i, int j) {  // of step k (1-based) from trim i to trim j, or -1
+        if (!mpa->transition[((size_t)(k - 1) * n + i) * n + j]) return -1;
+        const int t = mpa->maneuver_index[(size_t)i * n + j];
+        return t >= 0 && t < T ? t : -1;
+    };
+    // (hull(i, k -> K) depends on the masks of steps k .. K alone, and most steps share one mask — the recursive-feasibility mask differs
+    // near the horizon only —: a table per distinct sequence of masks, not per (k, K))
+    std::vector<int> slice((size_t)Hp);
+    for (int k = 0; k < Hp; ++k) {
+        slice[k] = k;
+        for (int q = 0; q < k; ++q)
+            if (!memcmp(mpa->transition + (size_t)q * n * n, mpa->transition + (size_t)k * n * n, (size_t)n * n)) {
+                slice[k] = slice[q];
+                break;
+            }
+    }
+    typedef std::vector<std::vector<ReachPt>> Table;  // one hull per trim
+    std::map<std::vector<int>, size_t> known;
+    std::vector<Table> tables;
+    std::vector<ReachPt> scratch;
+    for (int K = 1; K <= Hp; ++K) {
+        size_t at = 0;
+        for (int k = K; k >= 1; --k) {
+            const std::vector<int> key(slice.begin() + (k - 1), slice.begin() + K);
+            const auto found = known.find(key);
+            if (found != known.end()) {
+                at = found->second;
+                continue;
+            }
+            Table t((size_t)n);
+            for (int i = 0; i < n; ++i) {
+                for (int j = 0; j < n; ++j) {
+                    const int mi = maneuver(k, i, j);
+                    if (mi < 0) continue;
+                    const pdmpc_maneuver& m = mpa->maneuvers[mi];
+                    if (k == K) {
+                        const double(*src[3])[PDMPC_VMAX] = {m.area, m.area_without_offset, m.area_large_offset};
+                        for (int a = 0; a < 3; ++a)
+                            for (int v = 0; v < m.n_cols && v < PDMPC_VMAX; ++v) t[i].push_back(ReachPt(src[a][0][v], src[a][1][v]));
+                    } else {
+                        for (const ReachPt& p : tables[at][j]) t[i].push_back(ReachPt(cs[mi] * p.first - sn[mi] * p.second + m.dx, sn[mi] * p.first + cs[mi] * p.second + m.dy));
+                    }
+                }
+                reach_hull(t[i], scratch);
+            }
+            at = tables.size();
+            tables.push_back(std::move(t));
+            known[key] = at;
+        }
+        const Table& cur = tables[at];
+        for (int i = 0; i < n; ++i) {
+            double* r = rects + ((size_t)i * Hp + (K - 1)) * 4;
+            r[0] = r[1] = r[2] = r[3] = qnan;
+            for (const ReachPt& p : cur[i]) {
+                r[0] = p.first < r[0] || r[0] != r[0] ? p.first : r[0];
+                r[1] = p.first > r[1] || r[1] != r[1] ? p.first : r[1];
+                r[2] = p.second < r[2] || r[2] != r[2] ? p.second : r[2];
+                r[3] = p.second > r[3] || r[3] != r[3] ? p.second : r[3];
+            }
+        }
+    }
+}
+}  // namespace
+
+int pdmpc_mpa_reach_rects_host(const pdmpc_mpa* mpa, int32_t Hp, double* rects) {
+    if (!mpa || !rects || !mpa->transition || !mpa->maneuver_index || (mpa->n_maneuvers > 0 && !mpa->maneuvers)) return fail(PDMPC_ERR_INVALID, "pdmpc_mpa_reach_rects_host: null argument");
+    if (mpa->n_trims < 1 || Hp < 1 || Hp > PDMPC_HP_MAX || Hp > mpa->Hp) return fail(PDMPC_ERR_INVALID, "pdmpc_mpa_reach_rects_host: Hp out of range");
+    mpa_reach_rects(mpa, Hp, rects);
+    return PDMPC_OK;
+}
+
+int pdmpc_reach_lists_oriented_host(int32_t Hp, int32_t n_trims, const double* rects, int32_t root_trim, double root_x, double root_y, double root_yaw, const double* x, const double* y,
+                                    const int32_t* step_first, const int32_t* step_count, int32_t* list_offset, int32_t* list) {
+    if (Hp < 1 || Hp > PDMPC_HP_MAX || !rects || root_trim < 1 || root_trim > n_trims || !step_first || !step_count || !list_offset)
+        return fail(PDMPC_ERR_INVALID, "pdmpc_reach_lists_oriented_host: bad argument");
+    double cs, sn;
+    pdmpc_sincos(root_yaw, &sn, &cs);
+    int32_t n = 0;
+    for (int k = 1; k <= Hp; ++k) {
+        const int32_t a = step_first[k - 1], c = step_count[k - 1];
+        if (a < 0 || c < 0 || (c > 1 && (!x || !y || !list))) return fail(PDMPC_ERR_INVALID, "pdmpc_reach_lists_oriented_host: bad step ranges");
+        double box[4];
+        pdmpc_reach_rect_box(rects + ((size_t)(root_trim - 1) * Hp + (k - 1)) * 4, root_x, root_y, box);
+        list_offset[k - 1] = n;
+        for (int32_t j = 0; j + 1 < c; ++j)
+            if (pdmpc_reach_in_oriented(x[a + j], y[a + j], x[a + j + 1], y[a + j + 1], root_x, root_y, cs, sn, box[0], box[1], box[2], box[3])) list[n++] = j;
+    }
+    list_offset[Hp] = n;
+    return PDMPC_OK;
+}
+
 int pdmpc_upload_mpa(pdmpc_handle* h, const pdmpc_mpa* mpa) {
     if (!h || !mpa) return fail(PDMPC_ERR_INVALID, "null argument");
     if (mpa->n_trims < 1 || mpa->n_trims > 1023) return fail(PDMPC_ERR_INVALID, "n_trims must be in 1..1023");
@@ -637,7 +761,7 @@ int pdmpc_upload_mpa(pdmpc_handle* h, const pdmpc_mpa* mpa) {
     for (int i = 0; i < n * n; ++i) mi[i] = (int16_t)mpa->maneuver_index[i];
     const int T = mpa->n_maneuvers;
     std::vector<DevManPose> pose((size_t)std::max(T, 1));
-    std::vector<double> area((size_t)std::max(T, 1) * 3 * PDMPC_VMAX * 2 + 2, 0.0);  // (+ the automaton's reach behind the areas)
+    std::vector<double> area((size_t)std::max(T, 1) * 3 * PDMPC_VMAX * 2 + 2 + (size_t)n * Hp * 4, 0.0);  // (+ the automaton's reach behind the areas: Dmax, Amax, the rectangles)
     for (int t = 0; t < T; ++t) {
         const pdmpc_maneuver& m = mpa->maneuvers[t];
         if (m.n_cols < 2 || m.n_cols > PDMPC_VMAX) return fail(PDMPC_ERR_INVALID, "maneuver area column count out of range");
@@ -654,6 +778,7 @@ int pdmpc_upload_mpa(pdmpc_handle* h, const pdmpc_mpa* mpa) {
             }
     }
     mpa_reach(mpa, area[(size_t)T * 3 * PDMPC_VMAX * 2], area[(size_t)T * 3 * PDMPC_VMAX * 2 + 1]);  // (Dmax, Amax: the graph search's reach lists)
+    mpa_reach_rects(mpa, Hp, &area[(size_t)T * 3 * PDMPC_VMAX * 2 + 2]);  // ([trim][step] rectangles of the oriented rule, include/pdmpc_reach.h)
     if (h->d_mask.ensure(mask.size()) || h->d_mi.ensure(mi.size()) || h->d_pose.ensure(pose.size()) || h->d_area.ensure(area.size()))
         return fail(PDMPC_ERR_HIP, "hipMalloc failed for the MPA tables");
     HIPCHK(hipMemcpy(h->d_mask.p, mask.data(), mask.size() * 8, hipMemcpyHostToDevice));

@@ -96,7 +96,7 @@ struct BkCheck {
 };
 
 // The reach lists (include/pdmpc_reach.h): per step and soup the segments an edge check of that step can meet
-// at all, ascending, with their counts.  Squares, counts and lists live at compile-time offsets (PDMPC_LK_REACH; the lists of run-time
+// at all, ascending, with their counts.  Rectangles, root, counts and lists live at compile-time offsets (PDMPC_LK_REACH; the lists of run-time
 // length behind the fixed regions, in front of the automaton's tables: no register holds their address): the list of a step's vehicle
 // obstacles / HDV sets at the index of that soup's first column, the boundary's list of step k at ll_base + (k - 1) * ll_len.
 #define BK_RLIST(lsm) ((lds_u16*)((lsm) + PDMPC_LK_FIXED_END))
@@ -109,6 +109,7 @@ __device__ __forceinline__ LDS_AS unsigned char* bk_lds_base() {
 #define BK_RCNT(lsm) ((lds_u32*)((lsm) + PDMPC_LK_REACH + PDMPC_LK_REACH_CNT))
 #define BK_RSTALE(lsm) ((volatile lds_u32*)((lsm) + PDMPC_LK_REACH + PDMPC_LK_REACH_STALE))
 #define BK_RSC(lsm) ((lds_i32*)((lsm) + PDMPC_LK_REACH + PDMPC_LK_REACH_SC))
+#define BK_RROOT(lsm) ((lds_f64*)((lsm) + PDMPC_LK_REACH + PDMPC_LK_REACH_ROOT))
 // What an InterX check item reads of its search besides the lists, as LDS words at constant addresses (the workgroup's scalar registers
 // are spent, DESIGN.md section 3.9: a value read here is one LDS load per item, not a reload per use).  Thread 0 writes them.
 __device__ __forceinline__ void bk_reach_scalars(const BkCheck& C, LDS_AS unsigned char* lsm, bool shared_boundary_list) {
@@ -118,7 +119,7 @@ __device__ __forceinline__ void bk_reach_scalars(const BkCheck& C, LDS_AS unsign
     sc[2] = C.Hp;
     sc[3] = C.ll_base;
     sc[4] = C.ll_len;
-    sc[5] = shared_boundary_list ? 0 : C.ll_len;  // (one list of the boundary for every step: the last step's, a superset of each step's own)
+    sc[5] = shared_boundary_list ? 0 : C.ll_len;  // (one list of the boundary for every step, built against the rectangle around all steps' rectangles: a superset of each step's own)
 }
 struct BkItemCtx {  // the same values for a check item, each read where it is used: from the LDS words (InterX) or from the caller's registers
     const BkCheck& C;
@@ -134,17 +135,45 @@ template <int CHECKER>
 __device__ __forceinline__ BkItemCtx bk_item_ctx(const BkCheck& C) {
     return BkItemCtx{C, CHECKER == PDMPC_CHECK_INTERX ? 1 : 0};
 }
-// the squares of the steps around the search's root (tid < Hp; the automaton's reach sits behind its areas in HBM: read here only)
+// the widened rectangles of the steps in the root's frame (tid < Hp; the automaton's reach sits behind its areas in HBM — Dmax, Amax, then
+// [trim][step] rectangles —: read here only) and, once per search, the root: position, cos and sin of its yaw (thread Hp)
 __device__ __forceinline__ void bk_reach_boxes(const KernelArgs& A, const DevVehicle* V, LDS_AS unsigned char* lsm, int tid) {
     if (tid < A.Hp) {
-        const double* reach = A.man_area + (size_t)A.n_man * 3 * PDMPC_VMAX * 2;
+        // (32-bit index arithmetic: the 64-bit form of this address cost the generic kernels two spilled registers)
+        const int at = A.n_man * (3 * PDMPC_VMAX * 2) + 2 + ((V->trim0 - 1) * A.Hp + tid) * 4;
+        const double r[4] = {A.man_area[at], A.man_area[at + 1], A.man_area[at + 2], A.man_area[at + 3]};
         double box[4];
-        pdmpc_reach_box(reach[0], reach[1], tid + 1, V->x0, V->y0, box);
+        pdmpc_reach_rect_box(r, V->x0, V->y0, box);
         lds_f64* rb = BK_RBOX(lsm) + 4 * tid;
         rb[0] = box[0];
         rb[1] = box[1];
         rb[2] = box[2];
         rb[3] = box[3];
+    } else if (tid == A.Hp) {
+        double cs, sn;
+        pdmpc_sincos(V->yaw0, &sn, &cs);
+        lds_f64* rr = BK_RROOT(lsm);
+        rr[0] = V->x0;
+        rr[1] = V->y0;
+        rr[2] = cs;
+        rr[3] = sn;
+        if (A.lds.reach_shared != 0u) {  // (the layout of last resort: ONE list of the boundary for every step — a later step's rectangle need not hold an earlier one's)
+            const double* rect = A.man_area + (A.n_man * (3 * PDMPC_VMAX * 2) + 2 + (V->trim0 - 1) * A.Hp * 4);
+            double lo_x = 0.0, hi_x = 0.0, lo_y = 0.0, hi_y = 0.0;
+            for (int k = 0; k < A.Hp; ++k) {
+                const double r[4] = {rect[4 * k], rect[4 * k + 1], rect[4 * k + 2], rect[4 * k + 3]};
+                double box[4];
+                pdmpc_reach_rect_box(r, V->x0, V->y0, box);
+                lo_x = k == 0 || !(box[0] >= lo_x) ? box[0] : lo_x;  // (a NaN stays: the rule then culls nothing)
+                hi_x = k == 0 || !(box[1] <= hi_x) ? box[1] : hi_x;
+                lo_y = k == 0 || !(box[2] >= lo_y) ? box[2] : lo_y;
+                hi_y = k == 0 || !(box[3] <= hi_y) ? box[3] : hi_y;
+            }
+            rr[4] = lo_x;
+            rr[5] = hi_x;
+            rr[6] = lo_y;
+            rr[7] = hi_y;
+        }
     }
 }
 // One wavefront per (step, soup) — soups: bit 0 vehicle obstacles, 1 HDV sets, 2 lanelet boundary —: the segments 64 at a time, a ballot
@@ -155,7 +184,8 @@ __device__ __forceinline__ void bk_reach_build(const BkCheck& C, LDS_AS unsigned
     lds_u32* rcnt = BK_RCNT(lsm);
     for (int u = wave; u < (SOUPS == 1 ? 1 : 3) * C.Hp; u += n_waves) {  // (uniform per wavefront)
         const int k = SOUPS == 1 ? u : u / 3, s = SOUPS == 1 ? 0 : u - 3 * k;  // (k: 0-based step)
-        int base, n, at, kb = k;  // (kb: the step whose square decides)
+        int base, n, at, kb = k;  // (kb: the step whose rectangle decides)
+        bool one_list = false;  // (the boundary in the layout of last resort)
         if (s == 0) {
             base = C.l_soff[k];
             n = C.l_soff[k + 1] - base - 1;
@@ -165,13 +195,15 @@ __device__ __forceinline__ void bk_reach_build(const BkCheck& C, LDS_AS unsigned
             n = C.l_hoff[k + 1] - base - 1;
             at = base;
         } else {
-            const int stride = BK_RSC(lsm)[5];  // (0: every step writes the same list, the last step's, and the same count)
+            const int stride = BK_RSC(lsm)[5];  // (0: every step writes the same list and the same count)
             base = C.ll_base;
             n = C.ll_len - 1;
             at = base + k * stride;
             kb = stride ? k : C.Hp - 1;
+            one_list = stride == 0;
         }
-        const double x_lo = rbox[4 * kb], x_hi = rbox[4 * kb + 1], y_lo = rbox[4 * kb + 2], y_hi = rbox[4 * kb + 3];
+        const lds_f64* rb = one_list ? BK_RROOT(lsm) + 4 : rbox + 4 * kb;  // (one list for every step: the rectangle around the rectangles of all of them)
+        const lds_f64* root = BK_RROOT(lsm);
         const lds_d2* q = C.l_soup + base;
         lds_u16* lst = BK_RLIST(lsm) + at;
         uint32_t cnt = 0;
@@ -179,8 +211,8 @@ __device__ __forceinline__ void bk_reach_build(const BkCheck& C, LDS_AS unsigned
             const int j = j0 + lane;
             bool in = false;
             if (j < n) {
-                const d2 q0 = q[j], q1 = q[j + 1];
-                in = pdmpc_reach_in(q0.x, q0.y, q1.x, q1.y, x_lo, x_hi, y_lo, y_hi) != 0;
+                const d2 q0 = q[j], q1 = q[j + 1];  // (root and rectangle from LDS per trip: eight values held across the loop cost the generic kernels scratch memory)
+                in = pdmpc_reach_in_oriented(q0.x, q0.y, q1.x, q1.y, root[0], root[1], root[2], root[3], rb[0], rb[1], rb[2], rb[3]) != 0;
             }
             const unsigned long long m = __ballot(in);
             if (in) lst[cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint16_t)j;
@@ -684,7 +716,7 @@ __device__ __forceinline__ bool bk_poll_predecessors(const KernelArgs& A, const 
 // (chg, when given: [Hp] 64-bit masks — bit p of chg[k] is set when the area predecessor p publishes for step k + 1 differs from what
 // its slot held, i.e. from the area it was expected to take.  A collision-free edge of that step has been checked against exactly
 // those numbers: only the pairs (step, predecessor) marked here are due for the re-check, bk_recheck_items.
-// rbox, when given (InterX): the squares of the steps, include/pdmpc_reach.h — an area none of whose segments is in reach of its step
+// rbox, when given (InterX): the rectangles of the steps with the root behind them, include/pdmpc_reach.h — an area none of whose segments is in reach of its step
 // cannot take an edge of that step away, whatever the slot held: its bit is not set.  The two ballots and the __shfl_down sit in a
 // loop whose last trip is partial, i.e. with some lanes of the wavefront switched off.  That is safe because an area's eight columns
 // never straddle the boundary between active and inactive lanes: idx = tid + trip * nthreads with nthreads a multiple of 64 (the
@@ -711,7 +743,8 @@ __device__ __forceinline__ void bk_incorporate_body(const pdmpc_vehicle_out* out
             const bool differs = __double_as_longlong(was.x) != __double_as_longlong(pt.x) || __double_as_longlong(was.y) != __double_as_longlong(pt.y);
             if (rbox) {
                 const double nx = __shfl_down(pt.x, 1), ny = __shfl_down(pt.y, 1);  // (column v + 1: the same area for v < VMAX - 1)
-                const bool in = v + 1 < PDMPC_VMAX && pdmpc_reach_in(pt.x, pt.y, nx, ny, rbox[4 * k], rbox[4 * k + 1], rbox[4 * k + 2], rbox[4 * k + 3]) != 0;
+                const lds_f64* root = rbox + (PDMPC_LK_REACH_ROOT >> 3);
+                const bool in = v + 1 < PDMPC_VMAX && pdmpc_reach_in_oriented(pt.x, pt.y, nx, ny, root[0], root[1], root[2], root[3], rbox[4 * k], rbox[4 * k + 1], rbox[4 * k + 2], rbox[4 * k + 3]) != 0;
                 const int g = (tid & (PDMPC_WAVE - 1)) & ~(PDMPC_VMAX - 1);
                 const unsigned long long md = __ballot(differs), mi = __ballot(in);
                 if (v == 0 && ((md >> g) & 0xffull) != 0ull && ((mi >> g) & 0xffull) != 0ull)

@@ -82,8 +82,8 @@ struct LdsLayout {
     uint32_t bk_hist;                      // uint32[3072]: refill histogram [2048] | goal list [1024], expansion groups [1024], their children's offsets [1024]
     uint32_t bk_misc;                      // 2 KB: path tables of the best goal candidate, scan partials, chunk table, tick counters, the reference's ids along the path | the selection's 256-bin histogram
     uint32_t bk_pshape;                    // double2[Hp][VMAX] + uint32[HP_MAX] + uint64[HP_MAX]: the areas along the path of the record written last and their column counts (what an arrival is checked against first); per step the predecessors whose areas differ from the expected ones
-    uint32_t reach_shared;                 // 1: the boundary has ONE reach list, the last step's, for every step (the layout of last resort, api.cpp: layout_bulk)
-    uint32_t bk_reach;                     // the squares and counts of the reach lists (PDMPC_LK_REACH_*)
+    uint32_t reach_shared;                 // 1: the boundary has ONE reach list for every step, a superset of each step's own (the layout of last resort, api.cpp: layout_bulk)
+    uint32_t bk_reach;                     // the rectangles, counts and root of the reach lists (PDMPC_LK_REACH_*)
     uint32_t reach;                        // uint16[soup columns + (Hp - 1) * boundary columns] at PDMPC_LK_FIXED_END, in front of the MPA tables: per step and soup the segments in
                                            // reach, ascending (a step's vehicle obstacles / HDV sets at the index of that soup's first column, the boundary's list of step k at ll_base + (k - 1) * ll_len)
 };
@@ -129,12 +129,14 @@ struct LdsPathRegion {
 #define PDMPC_LKX_MISC(W, RC, P) (PDMPC_LKX_HIST(W, RC, P) + 3072u * 4u)
 #define PDMPC_LKX_PSHAPE(W, RC, P) (PDMPC_LKX_MISC(W, RC, P) + 2048u)
 #define PDMPC_LKX_REACH(W, RC, P) (PDMPC_LKX_PSHAPE(W, RC, P) + PDMPC_LK_ALIGN16(PDMPC_HP_MAX * PDMPC_VMAX * 16u + PDMPC_HP_MAX * 4u + PDMPC_HP_MAX * 8u + PDMPC_HP_MAX * 4u))
-/* the reach lists' fixed part (include/pdmpc_reach.h): double[HP_MAX][4] the square of every step, uint32[3][HP_MAX] segments in reach per
-   soup (vehicle obstacles, HDV sets, lanelet boundary) and step, uint32[4]: [0] the vehicle-obstacle lists are older than the soup */
+/* the reach lists' fixed part (include/pdmpc_reach.h): double[HP_MAX][4] the widened rectangle of every step in the root's frame, uint32[3][HP_MAX]
+   segments in reach per soup (vehicle obstacles, HDV sets, lanelet boundary) and step, uint32[4]: [0] the vehicle-obstacle lists are older
+   than the soup, int32[8] the check items' words, double[8] the root: x, y, cos and sin of its yaw, and the rectangle around all steps' (the boundary's one list, reach_shared) */
 #define PDMPC_LK_REACH_CNT (PDMPC_HP_MAX * 4u * 8u)
 #define PDMPC_LK_REACH_STALE (PDMPC_LK_REACH_CNT + 3u * PDMPC_HP_MAX * 4u)
 #define PDMPC_LK_REACH_SC (PDMPC_LK_REACH_STALE + 16u) /* int32[8]: what a check item would otherwise read from scalar registers: byte offsets of the soup and of the automaton's areas, Hp, ll_base, ll_len, the distance between the boundary's lists of two steps (ll_len, or 0: one list) */
-#define PDMPC_LKX_FIXED_END(W, RC, P) (PDMPC_LKX_REACH(W, RC, P) + PDMPC_LK_REACH_SC + 32u)
+#define PDMPC_LK_REACH_ROOT (PDMPC_LK_REACH_SC + 32u)
+#define PDMPC_LKX_FIXED_END(W, RC, P) (PDMPC_LKX_REACH(W, RC, P) + PDMPC_LK_REACH_ROOT + 64u)
 #ifndef PDMPC_BK_PER
 #define PDMPC_BK_PER 4
 #endif

@@ -36,6 +36,8 @@ PROTOTYPES = {
     "pdmpc_upload_mpa": (INT, [OBJ, MPA]),
     "pdmpc_mpa_reach_host": (INT, [MPA, DP, DP]),
     "pdmpc_reach_lists_host": (INT, [I32, F64, F64, F64, F64, DP, DP, IP, IP, IP, IP]),
+    "pdmpc_mpa_reach_rects_host": (INT, [MPA, I32, DP]),
+    "pdmpc_reach_lists_oriented_host": (INT, [I32, I32, DP, I32, F64, F64, F64, DP, DP, IP, IP, IP, IP]),
     "pdmpc_plan_batch": (INT, [OBJ, I32, VIN, VOUT]),
     "pdmpc_set_arena_limit": (INT, [OBJ, I32]),
     "pdmpc_grow_arena": (INT, [OBJ, I32]),
