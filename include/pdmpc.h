@@ -290,7 +290,7 @@ int pdmpc_plan_step_chosen(pdmpc_handle* handle, int32_t n_vehicles, const pdmpc
                            const pdmpc_polygon_set* fallback_shapes, const pdmpc_choice* choice, int32_t* chosen, double* cell_cost, pdmpc_vehicle_out* picks);
 /* kernel time (HIP events, ms) of the two launches of the last pdmpc_choose_resident / pdmpc_plan_step_chosen */
 int pdmpc_choice_kernel_ms(pdmpc_handle* handle, double* ms);
-/* host wall-clock microseconds of the last pdmpc_plan_batch / pdmpc_plan_step on this handle: [0] pack (flatten + queue the
+/* host wall-clock microseconds of the last pdmpc_plan_batch / pdmpc_plan_step / pdmpc_plan_joint on this handle: [0] pack (flatten + queue the
  * host-to-device copy), [1] enqueue the launch, [2] wait for the kernel + copy the records back */
 int pdmpc_last_call_timing(pdmpc_handle* handle, double* us3);
 int pdmpc_launch_packed(pdmpc_handle* handle);
@@ -391,6 +391,10 @@ int pdmpc_debug_raw_tree(pdmpc_handle* handle, int32_t vehicle, int32_t capacity
 /* the device's work counters since pdmpc_create / pdmpc_reset_stats, raw: [0..6] as pdmpc_stats reports them, [8..12] with
  * PDMPC_TUNING=debug_tail=1 the helper workgroups' time in 100 MHz ticks (idle, claim -> soup, records, checks, verdicts + report), [13] tiles */
 int pdmpc_debug_counters(pdmpc_handle* handle, uint64_t* out16);
+/* where the last pack put the caller's vehicle `vehicle` in the batch's point pool: lit_off[Hp + 1] and hdv_off[Hp + 1] (the per-step
+ * soups of its obstacles and HDV sets), ll2 = {offset, length} of its lanelet boundary.  Vehicles that handed over the same arrays
+ * report the same offsets (one copy in the pool). */
+int pdmpc_debug_packed_offsets(pdmpc_handle* handle, int32_t vehicle, int32_t* lit_off, int32_t* hdv_off, int32_t* ll2);
 
 /* live counters of a running frontier launch (needs PDMPC_DEBUG_PROGRESS=1 in the environment; callable from another thread
  * while pdmpc_plan_* blocks): rounds, nodes processed, tree size, near / far entries, flags, best candidate, stage */
@@ -439,7 +443,10 @@ int pdmpc_debug_random_numbers(pdmpc_handle* handle, int32_t count, const uint32
  * status / n_expanded / n_popped / tree_path shared by the problem, its own predicted_trims, y_predicted, shapes; path_nodes rows
  * (x_v, y_v, yaw_v, trim_v, g, h, k, 1) with the joint g and h.  The arena holds config.max_nodes joint nodes per problem and grows
  * as for pdmpc_plan_batch (PDMPC_ARENA_OVERFLOW only at the limit).  PDMPC_ERR_INVALID for a handle whose checker is not
- * PDMPC_CHECK_SAT, for a problem of 0 or more than PDMPC_JOINT_MAX vehicles, and for a NULL out with vehicles to plan. */
+ * PDMPC_CHECK_SAT, for a problem of 0 or more than PDMPC_JOINT_MAX vehicles, and for a NULL out with vehicles to plan.
+ * LDS holds one copy of every DISTINCT obstacle set of a problem: vehicles of a problem that hand over the same obstacles and
+ * dynamic_obstacles arrays (same pointers, same counts) share one copy, and likewise vehicles with the same boundary arrays, so N
+ * vehicles that see the scenario's sets need the room of one (PDMPC_ERR_CAPACITY only if the distinct sets of one problem do not fit). */
 int pdmpc_plan_joint(pdmpc_handle* handle, int32_t n_problems, const int32_t* problem_offset, const pdmpc_vehicle_in* in,
                      pdmpc_vehicle_out* out);
 
@@ -724,6 +731,25 @@ int pdmpc_controller_priorities(pdmpc_controller* c, int32_t* n_priorities, cons
  * explorative step with and without follow-own and the optimal-priority step; state, chosen instances, cost table and kept records are
  * the same byte for byte.  Default off; nothing changes for a controller without a handle. */
 int pdmpc_controller_set_device_choice(pdmpc_controller* c, int32_t on);
+/* Centralized control natively (CentralizedController.m:33-59; the twin is pdmpc.centralized.CentralizedController; csrc/step_centralized.hpp;
+ * DESIGN.md §3.15): one joint graph search over all vehicles of the controller per time step, no coupling, no priorities, no levels.
+ * centralized_build advances the time step and runs the traffic info of a step (trim from the measurement, reference sampling,
+ * predicted lanelet boundaries); centralized_problem hands out the joint problem: *n = the vehicle count, in[v] = vehicle v (vehicle
+ * order), every entry's obstacles the scenario's set UNDER THE SAME POINTERS (pdmpc_plan_joint stages it once), dynamic_obstacles and
+ * hdv_reachable_sets empty; valid until the next build.  centralized_apply takes the n records in vehicle order and is Simulation.apply
+ * (Simulation.m:86-100): pose = y_predicted(:, 1), speed and steering those of predicted_trims(1); no fallbacks, no previous plans.
+ * centralized_step = build + ONE pdmpc_plan_joint of one problem + apply (the records: pdmpc_controller_records); centralized_run =
+ * n_steps of them, ms as for pdmpc_controller_run.  pdmpc_controller_last_timing / _timing_sum get their parts as for a plain step.
+ * The reference has no fallback for this controller (:61-70): if any record carries PDMPC_EXHAUSTED, apply (and so step and run)
+ * returns PDMPC_EXHAUSTED, applies nothing and leaves the plant state where it was; the time step stays advanced;
+ * pdmpc_controller_last_error names the step, and centralized_run stops there.
+ * Refused before anything advances: more than PDMPC_JOINT_MAX vehicles (PDMPC_ERR_CAPACITY); a handle whose checker is not
+ * PDMPC_CHECK_SAT, and centralized_step / _run without a handle (PDMPC_ERR_INVALID).  Build, problem and apply work without a handle. */
+int pdmpc_controller_centralized_build(pdmpc_controller* c);
+int pdmpc_controller_centralized_problem(pdmpc_controller* c, int32_t* n, const pdmpc_vehicle_in** in);
+int pdmpc_controller_centralized_apply(pdmpc_controller* c, const pdmpc_vehicle_out* records);
+int pdmpc_controller_centralized_step(pdmpc_controller* c);
+int pdmpc_controller_centralized_run(pdmpc_controller* c, int32_t n_steps, double* ms);
 
 /* ---- several closed loops in lock-step (csrc/step_controller.cpp, the end of the file) ----
  * A sweep borrows n_members controllers that were created on the same handle (or all without one) and steps them together: every
@@ -800,6 +826,27 @@ int pdmpc_sweep_optimal_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records);
 int pdmpc_sweep_optimal_step(pdmpc_sweep* s, int32_t max_instances);
 int pdmpc_sweep_optimal_run(pdmpc_sweep* s, int32_t max_instances, int32_t n_steps, double* ms);
 int pdmpc_sweep_optimal_last_calls(pdmpc_sweep* s, int32_t* calls2);
+/* Centralized members in a sweep: every live member's pdmpc_controller_centralized_build, the members' joint problems
+ * as the problems of ONE pdmpc_plan_joint -- one launch for the whole sweep, one wavefront per member --, every member's
+ * centralized_apply.  Members may differ in vehicle count (1 to PDMPC_JOINT_MAX), scenario and everything else pdmpc_sweep_create
+ * allows.  After a step each member is byte for byte where its own pdmpc_controller_centralized_step would have left it (state,
+ * records, problem, time step): a member can be taken out and stepped alone.
+ * centralized_problem: *n_problems live members' problems; problem p = in[problem_offset[p] .. problem_offset[p + 1]), member[p] = whose
+ * it is.  centralized_apply takes the records in that order (works without a handle).
+ * A member whose search is exhausted is not applied, is recorded (centralized_status: exhausted_at[m] = the time step at which member
+ * m's search ran empty, 0 for a live member) and is left out of all later steps -- it is not built and its time step does not advance
+ * --; the other members go on and the step returns PDMPC_OK.  Once no member is live, centralized_step returns PDMPC_EXHAUSTED (and
+ * centralized_run stops there).
+ * When one problem outgrows its arena, pdmpc_plan_joint plans the call again for ALL problems with larger arenas (its rule); an
+ * overflow at the arena limit, or any error, breaks the sweep as every failed step does.
+ * Refused before any member advances: a member with more than PDMPC_JOINT_MAX vehicles (PDMPC_ERR_CAPACITY); a handle whose checker is
+ * not PDMPC_CHECK_SAT, a broken sweep, and centralized_step / _run without a handle (PDMPC_ERR_INVALID). */
+int pdmpc_sweep_centralized_build(pdmpc_sweep* s);
+int pdmpc_sweep_centralized_problem(pdmpc_sweep* s, int32_t* n_problems, const int32_t** problem_offset, const pdmpc_vehicle_in** in, const int32_t** member);
+int pdmpc_sweep_centralized_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records);
+int pdmpc_sweep_centralized_step(pdmpc_sweep* s);
+int pdmpc_sweep_centralized_run(pdmpc_sweep* s, int32_t n_steps, double* ms);
+int pdmpc_sweep_centralized_status(pdmpc_sweep* s, int32_t* exhausted_at); /* [n_members]: 0, or the time step at which the member's search ran empty */
 
 /* ---- several GPUs behind the same boundary (csrc/group.cpp) ----
  * The reference's vehicles exchange their solved areas after every computation level: each publishes a Predictions message that every

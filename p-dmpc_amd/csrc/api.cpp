@@ -242,7 +242,7 @@ int compute_lds_sampled(const pdmpc_handle* h, int soup_cap, int cand_cap, Launc
 }
 
 // LDS layout of the joint search (one wavefront per problem): MPA tables, every vehicle's reference, the node's areas, offsets and the
-// path, successor lists, the problem's soups, then the LDS part of the open list.  Aimed at 64 KB (two workgroups per CU and more);
+// path, successor lists, the problem's distinct soups (soup_cap: pdmpc_joint_soup_columns), then the LDS part of the open list.  Aimed at 64 KB (two workgroups per CU and more);
 // a problem whose tables and soups do not leave room for 256 heap entries there may take up to the whole 160 KB.
 int layout_joint(pdmpc_handle* h, int soup_cap, JointLds& L, uint32_t& heap_lds, int& areas_in_lds) {
     for (int pass = 0; pass < 4; ++pass) {
@@ -1426,20 +1426,18 @@ int pdmpc_plan_joint(pdmpc_handle* h, int32_t n_problems, const int32_t* problem
     const int n = n_problems > 0 ? problem_offset[n_problems] : 0;
     if (n > 0 && (!in || !out)) return fail(PDMPC_ERR_INVALID, "pdmpc_plan_joint: null vehicle or record array");
     ON_DEVICE(h->cfg.device);
+    auto t0 = std::chrono::steady_clock::now();
     int rc = pdmpc_pack_batch(h, n, in);
     if (rc) return rc;
+    h->last_us[0] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();  // (pdmpc_last_call_timing, as timed_pack)
+    h->last_us[1] = h->last_us[2] = 0;
     if (n == 0) return PDMPC_OK;
     PackedStep& B = h->banks[h->bank];
     const int Hp = h->cfg.Hp;
     int soup_cap = 0;
-    for (int p = 0; p < n_problems; ++p) {
-        int need = 0;
-        for (int i = problem_offset[p]; i < problem_offset[p + 1]; ++i) {
-            const DevVehicle& d = B.host.veh[i];
-            need += (d.lit_off[Hp] - d.lit_off[0]) + d.ll_len;
-        }
-        soup_cap = std::max(soup_cap, need);
-    }
+    // every distinct soup and boundary of a problem once: what the kernel's prologue stages (pdmpc_device.h: the rule of both)
+    for (int p = 0; p < n_problems; ++p)
+        soup_cap = std::max(soup_cap, pdmpc_joint_soup_columns(B.host.veh + problem_offset[p], problem_offset[p + 1] - problem_offset[p], Hp));
     JointLds L{};
     uint32_t heap_lds = 0;
     int areas_in_lds = 0;
@@ -1455,6 +1453,7 @@ int pdmpc_plan_joint(pdmpc_handle* h, int32_t n_problems, const int32_t* problem
         a.far_id = h->arena.far_id.p;
         a.heap_lds = heap_lds;
         a.lds = L;
+        t0 = std::chrono::steady_clock::now();
         if ((rc = h->timer.begin(h->stream, kLaunchJoint))) return rc;
         const int lrc = pdmpc_launch_joint(&a, n_problems, (void*)h->stream);
         if (lrc != 0) {
@@ -1463,7 +1462,10 @@ int pdmpc_plan_joint(pdmpc_handle* h, int32_t n_problems, const int32_t* problem
             return fail(PDMPC_ERR_HIP, buf);
         }
         if ((rc = h->timer.end(h->stream))) return rc;
+        const auto t1 = std::chrono::steady_clock::now();
         if ((rc = pdmpc_fetch_results(h, n, out))) return rc;
+        h->last_us[1] += std::chrono::duration<double, std::micro>(t1 - t0).count();
+        h->last_us[2] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t1).count();
         bool overflow = false;
         for (int i = 0; i < n; ++i) overflow = overflow || out[i].status == PDMPC_ARENA_OVERFLOW;
         if (!overflow) break;
@@ -1537,6 +1539,20 @@ int pdmpc_debug_counters(pdmpc_handle* h, uint64_t* out16) {
     ON_DEVICE(h->cfg.device);
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(out16, h->d_work_count.p, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return PDMPC_OK;
+}
+
+int pdmpc_debug_packed_offsets(pdmpc_handle* h, int32_t vehicle, int32_t* lit_off, int32_t* hdv_off, int32_t* ll2) {
+    if (!h || !lit_off || !hdv_off || !ll2) return fail(PDMPC_ERR_INVALID, "null argument");
+    const PackedStep& B = h->banks[h->bank];
+    if (B.pack_failed || vehicle < 0 || vehicle >= B.n_packed) return fail(PDMPC_ERR_INVALID, "pdmpc_debug_packed_offsets: no such vehicle in the packed batch");
+    const DevVehicle& d = B.host.veh[B.inv.empty() ? vehicle : B.inv[(size_t)vehicle]];
+    for (int k = 0; k <= h->cfg.Hp; ++k) {
+        lit_off[k] = d.lit_off[k];
+        hdv_off[k] = d.hdv_off[k];
+    }
+    ll2[0] = d.ll_off;
+    ll2[1] = d.ll_len;
     return PDMPC_OK;
 }
 

@@ -468,7 +468,8 @@ struct pdmpc_handle {
     double last_us[3] = {0, 0, 0};       // pdmpc_last_call_timing: pack, enqueue, wait + read-back of the last pdmpc_plan_batch / pdmpc_plan_step
     double dbg_us[4] = {0, 0, 0, 0};     // debug_host 2: pack, launch, fetch (host clock) and kernel (events) time of the plan_batch calls
     uint64_t sync_serial = 0;            // stream synchronisations through sync_stream so far (PackedStep::staged_serial)
-    SoupTable soups;                     // pack_common's scratch
+    SoupTable soups;                     // pack_common's scratch: vehicles by all their arrays,
+    SoupTable obstacle_soups, boundary_soups;  // ... by their obstacle arrays, by their boundary arrays
     std::vector<double> next_weights;    // pdmpc_set_step_weights: expected work per vehicle of the NEXT packed step (the caller's order); consumed by that pack
     std::vector<uint32_t> next_seeds;    // pdmpc_set_step_seeds: the sampled optimizer's seed per vehicle of the NEXT packed step (the caller's order) ...
     bool seeds_set = false;              // ... consumed by that pack, which makes its bank a sampled bank

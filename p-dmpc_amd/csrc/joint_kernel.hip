@@ -90,18 +90,33 @@ extern "C" __global__ __launch_bounds__(PDMPC_WAVE) void pdmpc_joint_kernel(cons
                 l_ref[(v * 3 + 1) * PDMPC_HP_MAX + lane] = V->ref_y[lane];
                 l_ref[(v * 3 + 2) * PDMPC_HP_MAX + lane] = V->v_ref[lane];
             }
-            const int a0 = uni_i(V->lit_off[0]);
-            const int a1 = uni_i(V->lit_off[Hp]);
-            if (lane <= Hp) l_soff[v * (PDMPC_HP_MAX + 1) + lane] = off + (V->lit_off[lane] - a0);
-            stage16(l_soup + off, (const d2*)A.points + a0, a1 - a0, lane);
-            off += a1 - a0;
-            const int lo = uni_i(V->ll_off), ll = uni_i(V->ll_len);
-            stage16(l_soup + off, (const d2*)A.points + lo, ll, lane);
-            if (lane == 0) {
-                l_llb[v] = off;
-                l_lll[v] = ll;
+            // one LDS copy per distinct soup of the problem (pdmpc_device.h: the rule layout_joint budgets by).  A row that is taken over
+            // is read by the lanes that wrote it: LDS accesses of a wavefront complete in order
+            const int su = uni_i(pdmpc_joint_soup_owner(A.veh + first, v, Hp));
+            if (su >= 0) {
+                if (lane <= Hp) l_soff[v * (PDMPC_HP_MAX + 1) + lane] = l_soff[su * (PDMPC_HP_MAX + 1) + lane];
+            } else {
+                const int a0 = uni_i(V->lit_off[0]);
+                const int a1 = uni_i(V->lit_off[Hp]);
+                if (lane <= Hp) l_soff[v * (PDMPC_HP_MAX + 1) + lane] = off + (V->lit_off[lane] - a0);
+                stage16(l_soup + off, (const d2*)A.points + a0, a1 - a0, lane);
+                off += a1 - a0;
             }
-            off += ll;
+            const int bu = uni_i(pdmpc_joint_boundary_owner(A.veh + first, v));
+            const int ll = uni_i(V->ll_len);
+            if (bu >= 0) {
+                if (lane == 0) {
+                    l_llb[v] = l_llb[bu];
+                    l_lll[v] = ll;
+                }
+            } else {
+                stage16(l_soup + off, (const d2*)A.points + uni_i(V->ll_off), ll, lane);
+                if (lane == 0) {
+                    l_llb[v] = off;
+                    l_lll[v] = ll;
+                }
+                off += ll;
+            }
         }
     }
     for (int v = 0; v < N; ++v) {

@@ -134,6 +134,29 @@ struct Packer {
         key.c[5] = fbv ? fbv->n_polygons : 0;
         return key;
     }
+    // ... and vehicles that agree in a PART of their arrays share that part (the vehicles of a centralized step on a road network see
+    // the same obstacles inside boundaries of their own): the obstacle, dynamic-obstacle and HDV arrays with their counts decide
+    // lit_off / hdv_off, the boundary arrays decide ll_off / ll_len.  Fallback areas are shared by the whole key above only.
+    static SoupKey obstacle_key(const pdmpc_vehicle_in& v) {
+        SoupKey key;
+        std::memset(&key, 0, sizeof key);
+        const void* ptrs[9] = {v.obstacles.offset, v.obstacles.x, v.obstacles.y, v.dynamic_obstacles.offset, v.dynamic_obstacles.x, v.dynamic_obstacles.y, v.hdv_reachable_sets.offset,
+                               v.hdv_reachable_sets.x, v.hdv_reachable_sets.y};
+        for (int q = 0; q < 9; ++q) key.p[q] = ptrs[q];
+        key.c[0] = v.obstacles.n_polygons;
+        key.c[1] = v.dynamic_obstacles.n_polygons;
+        key.c[2] = v.hdv_reachable_sets.n_polygons;
+        return key;
+    }
+    static SoupKey boundary_key(const pdmpc_vehicle_in& v) {
+        SoupKey key;
+        std::memset(&key, 0, sizeof key);
+        const void* ptrs[4] = {v.left_x, v.left_y, v.right_x, v.right_y};
+        for (int q = 0; q < 4; ++q) key.p[q] = ptrs[q];
+        key.c[3] = v.n_left;
+        key.c[4] = v.n_right;
+        return key;
+    }
 
     // the sets of a vehicle that brings new arrays
     int check_soups(const pdmpc_vehicle_in& v, const pdmpc_polygon_set* fbv) const {
@@ -188,30 +211,43 @@ struct Packer {
         B.lit_cols[(size_t)slot] = B.lit_cols[(size_t)seen_slot];
     }
 
-    int append_soups(int slot, const pdmpc_vehicle_in& v, const pdmpc_polygon_set* fbv, DevVehicle& d) {
+    // the soups of a vehicle that was not seen before as a whole: each part appended, or taken over from the slot that packed the same
+    // arrays (-1: none)
+    int append_soups(int slot, const pdmpc_vehicle_in& v, const pdmpc_polygon_set* fbv, DevVehicle& d, int obstacles_of, int boundary_of) {
         const int Hp = h->cfg.Hp;
         const double qnan = std::numeric_limits<double>::quiet_NaN();
         const int n_dyn = v.dynamic_obstacles.n_polygons / Hp;
         const int n_hdv = v.hdv_reachable_sets.n_polygons / Hp;
-        // vehicle_obstacles{k} = [static..., dynamic(:, k)...], each followed by [NaN; NaN]   vectorize_all_obstacles.m:36-62
-        for (int k = 0; k < Hp; ++k) {
-            d.lit_off[k] = (int32_t)n_pts;
-            for (int p = 0; p < v.obstacles.n_polygons; ++p) append_poly(v.obstacles, p, true);
-            for (int r = 0; r < n_dyn; ++r) append_poly(v.dynamic_obstacles, r * Hp + k, true);
+        if (obstacles_of >= 0) {
+            const DevVehicle& f = host.veh[(size_t)obstacles_of];
+            std::memcpy(d.lit_off, f.lit_off, sizeof d.lit_off);
+            std::memcpy(d.hdv_off, f.hdv_off, sizeof d.hdv_off);
+        } else {
+            // vehicle_obstacles{k} = [static..., dynamic(:, k)...], each followed by [NaN; NaN]   vectorize_all_obstacles.m:36-62
+            for (int k = 0; k < Hp; ++k) {
+                d.lit_off[k] = (int32_t)n_pts;
+                for (int p = 0; p < v.obstacles.n_polygons; ++p) append_poly(v.obstacles, p, true);
+                for (int r = 0; r < n_dyn; ++r) append_poly(v.dynamic_obstacles, r * Hp + k, true);
+            }
+            d.lit_off[Hp] = (int32_t)n_pts;
+            for (int k = 0; k < Hp; ++k) {
+                d.hdv_off[k] = (int32_t)n_pts;
+                for (int r = 0; r < n_hdv; ++r) append_poly(v.hdv_reachable_sets, r * Hp + k, true);
+            }
+            d.hdv_off[Hp] = (int32_t)n_pts;
         }
-        d.lit_off[Hp] = (int32_t)n_pts;
-        for (int k = 0; k < Hp; ++k) {
-            d.hdv_off[k] = (int32_t)n_pts;
-            for (int r = 0; r < n_hdv; ++r) append_poly(v.hdv_reachable_sets, r * Hp + k, true);
+        if (boundary_of >= 0) {
+            d.ll_off = host.veh[(size_t)boundary_of].ll_off;
+            d.ll_len = host.veh[(size_t)boundary_of].ll_len;
+        } else {
+            // lanelet_boundary = [left, NaN, right, NaN]                                          vectorize_all_obstacles.m:27-30
+            d.ll_off = (int32_t)n_pts;
+            for (int q = 0; q < v.n_left; ++q) put(v.left_x[q], v.left_y[q]);
+            put(qnan, qnan);
+            for (int q = 0; q < v.n_right; ++q) put(v.right_x[q], v.right_y[q]);
+            put(qnan, qnan);
+            d.ll_len = (int32_t)n_pts - d.ll_off;
         }
-        d.hdv_off[Hp] = (int32_t)n_pts;
-        // lanelet_boundary = [left, NaN, right, NaN]                                          vectorize_all_obstacles.m:27-30
-        d.ll_off = (int32_t)n_pts;
-        for (int q = 0; q < v.n_left; ++q) put(v.left_x[q], v.left_y[q]);
-        put(qnan, qnan);
-        for (int q = 0; q < v.n_right; ++q) put(v.right_x[q], v.right_y[q]);
-        put(qnan, qnan);
-        d.ll_len = (int32_t)n_pts - d.ll_off;
         B.lit_cols[(size_t)slot] = (d.lit_off[Hp] - d.lit_off[0]) + d.ll_len;
         if (fbv) {
             for (int k = 0; k < Hp; ++k) {
@@ -253,7 +289,13 @@ struct Packer {
             share_soups(slot, seen_slot, d);
         } else {
             if (seen_slot < 0) h->soups.insert(key, slot, at);  // (a key met again with other y arrays keeps its first entry, as the map did)
-            if ((rc = append_soups(slot, v, fbv, d))) return rc;
+            // the parts it shares with a slot packed before (the first slot that brought a part's arrays is the one entered)
+            const SoupKey okey = obstacle_key(v), bkey = boundary_key(v);
+            size_t oat = 0, bat = 0;
+            const int obstacles_of = h->obstacle_soups.find(okey, oat), boundary_of = h->boundary_soups.find(bkey, bat);
+            if (obstacles_of < 0) h->obstacle_soups.insert(okey, slot, oat);
+            if (boundary_of < 0) h->boundary_soups.insert(bkey, slot, bat);
+            if ((rc = append_soups(slot, v, fbv, d, obstacles_of, boundary_of))) return rc;
         }
         // what the LDS must hold of this vehicle: its soups of all steps with the predecessors' columns (soup_cap), of one step (cand_cap)
         const int need = (d.lit_off[Hp] - d.lit_off[0]) + Hp * d.n_pred * PDMPC_VMAX + (d.hdv_off[Hp] - d.hdv_off[0]) + d.ll_len;
@@ -313,6 +355,8 @@ int pack_common(pdmpc_handle* h, int n, const pdmpc_vehicle_in* in, const int32_
     if ((rc = P.open())) return rc;
     if ((rc = slot_order(h, n, pred_offset, pred_index, weights, B))) return rc;
     h->soups.reset(n);
+    h->obstacle_soups.reset(n);
+    h->boundary_soups.reset(n);
     for (int slot = 0; slot < n; ++slot)
         if ((rc = P.pack_vehicle(slot))) return rc;
     if ((rc = P.close())) return rc;

@@ -287,11 +287,44 @@ struct JointLds {  // byte offsets into the dynamic LDS allocation (api.cpp: lay
     uint32_t shape;                        // double2 [PDMPC_JOINT_MAX][2][PDMPC_VMAX]: area, boundary-check area of the node's edge
     uint32_t ints;                         // int32: soup offsets [JOINT_MAX][HP_MAX + 1], boundary base / length / columns [3][JOINT_MAX], path [HP_MAX + 1]
     uint32_t succ;                         // int32 [PDMPC_JOINT_MAX][n_trims]: successor trims of the node being expanded
-    uint32_t soup;                         // double2 [soup_cap]: the problem's obstacle soups, vehicle after vehicle
+    uint32_t soup;                         // double2 [soup_cap]: the problem's obstacle soups and boundaries, vehicle after vehicle, every distinct one once
     uint32_t heap_key, heap_id;            // the LDS part of the open list: double [heap_lds], uint32 [heap_lds]
     uint32_t total;
 };
 #define PDMPC_JOINT_INTS (PDMPC_JOINT_MAX * (PDMPC_HP_MAX + 1) + 3 * PDMPC_JOINT_MAX + PDMPC_HP_MAX + 1)
+
+// ONE LDS copy per distinct soup of a joint problem.  Vehicle v of a problem (veh: its first packed slot) takes over the LDS soup of
+// the first earlier vehicle u < v whose per-step pool offsets lit_off[0 .. Hp] equal its own -- the packer gives vehicles that hand
+// over the same obstacle arrays the same offsets (pack.cpp) --, and its boundary of the first earlier vehicle with the same ll_off and
+// ll_len.  -1: v brings its own.  The rule of the kernel's prologue (what is staged) AND of layout_joint's soup_cap (what is
+// budgeted), which is why it is written here once.
+#ifdef __HIP__
+#define PDMPC_HOST_DEVICE __attribute__((host)) __attribute__((device))
+#else
+#define PDMPC_HOST_DEVICE
+#endif
+PDMPC_HOST_DEVICE static inline int pdmpc_joint_soup_owner(const DevVehicle* veh, int v, int Hp) {
+    for (int u = 0; u < v; ++u) {
+        bool same = true;
+        for (int k = 0; k <= Hp && same; ++k) same = veh[u].lit_off[k] == veh[v].lit_off[k];
+        if (same) return u;
+    }
+    return -1;
+}
+PDMPC_HOST_DEVICE static inline int pdmpc_joint_boundary_owner(const DevVehicle* veh, int v) {
+    for (int u = 0; u < v; ++u)
+        if (veh[u].ll_off == veh[v].ll_off && veh[u].ll_len == veh[v].ll_len) return u;
+    return -1;
+}
+// the soup columns a joint problem of N vehicles stages (the sum the prologue's `off` ends at)
+PDMPC_HOST_DEVICE static inline int pdmpc_joint_soup_columns(const DevVehicle* veh, int N, int Hp) {
+    int need = 0;
+    for (int v = 0; v < N; ++v) {
+        if (pdmpc_joint_soup_owner(veh, v, Hp) < 0) need += veh[v].lit_off[Hp] - veh[v].lit_off[0];
+        if (pdmpc_joint_boundary_owner(veh, v) < 0) need += veh[v].ll_len;
+    }
+    return need;
+}
 
 struct JointArgs {
     const uint64_t* succ_mask;

@@ -5,7 +5,7 @@
 // that names only the ones before it and says at its head what it restates (`make host-parts` compiles each alone):
 // step_types.hpp (the records), step_inputs.hpp (what a step reads of the traffic), step_priorities.hpp (couplings -> a prioritization),
 // step_state.hpp (the controller as the parts that are written together), step_assembly.hpp (a member's StepProblem), step_batch.hpp (the
-// batches of prioritizations and the choice among their plans).  This file: the step preparation over a span of members (build_members),
+// batches of prioritizations and the choice among their plans), step_centralized.hpp (centralized control: the joint problem).  This file: the step preparation over a span of members (build_members),
 // planning a built problem (plan_built), the steps and their loops, the sweep, every entry point of the C ABI, and
 //   exhaustion, fallbacks     handle_graph_search_exhaustion / plan_fallback (:568-616, 678-718), check_others_fallback (:623-676),
 //                             HighLevelController.handle_others_fallback (HighLevelController.m:449-463)
@@ -26,6 +26,7 @@
 #include "step_state.hpp"
 #include "step_assembly.hpp"
 #include "step_batch.hpp"
+#include "step_centralized.hpp"
 
 namespace {
 
@@ -449,6 +450,13 @@ int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, boo
     }
     c->timing[4] = ms_since(t);  // (from the backend call's return on)
     return apply_and_account(c);
+}
+
+// the parts of the last pdmpc_plan_joint on h (pdmpc_last_call_timing) into timing[1..3]
+void joint_call_timing(pdmpc_handle* h, double* timing) {
+    double us[3] = {0, 0, 0};
+    if (pdmpc_last_call_timing(h, us) == PDMPC_OK)
+        for (int i = 0; i < 3; ++i) timing[1 + i] = us[i] * 1e-3;
 }
 
 }  // namespace
@@ -940,6 +948,51 @@ int pdmpc_controller_optimal_result(pdmpc_controller* c, int32_t* chosen, int32_
     return PDMPC_OK;
 }
 
+// ---- centralized control (step_centralized.hpp)
+int pdmpc_controller_centralized_build(pdmpc_controller* c) {
+    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
+    if (const int rc = centralized_refusal(c)) return rc;
+    centralized_build(c);
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_centralized_problem(pdmpc_controller* c, int32_t* n, const pdmpc_vehicle_in** in) {
+    if (!c || !c->cen.built) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_centralized_problem before pdmpc_controller_centralized_build");
+    if (n) *n = c->sc.n;
+    if (in) *in = c->cen.in.data();
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_centralized_apply(pdmpc_controller* c, const pdmpc_vehicle_out* recs) {
+    if (!c || !recs) return cfail(c, PDMPC_ERR_INVALID, "null argument");
+    if (!c->cen.built) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_centralized_apply before pdmpc_controller_centralized_build");
+    return centralized_apply(c, recs);
+}
+
+// One pass of the main control loop with CentralizedController.controller: build, ONE joint search of one problem, apply.
+int pdmpc_controller_centralized_step(pdmpc_controller* c) {
+    if (!c || !c->h) return cfail(c, PDMPC_ERR_INVALID, "controller has no backend handle");
+    if (const int rc = centralized_refusal(c)) return rc;
+    auto t = std::chrono::steady_clock::now();
+    centralized_build(c);
+    c->timing[0] = ms_since(t);
+    c->timing[4] = 0;
+    c->out.resize((size_t)c->sc.n);
+    const int32_t problem_offset[2] = {0, c->sc.n};
+    if (const int rc = pdmpc_plan_joint(c->h, 1, problem_offset, c->cen.in.data(), c->out.data())) return cfail(c, rc, std::string("pdmpc_plan_joint: ") + pdmpc_last_error());
+    joint_call_timing(c->h, c->timing);
+    t = std::chrono::steady_clock::now();
+    const int rc = centralized_apply(c, c->out.data());
+    c->timing[5] = ms_since(t);
+    for (int i = 0; i < 6; ++i) c->timing_sum[i] += c->timing[i];
+    c->timing_steps += 1;
+    return rc;
+}
+
+int pdmpc_controller_centralized_run(pdmpc_controller* c, int32_t n_steps, double* ms) {
+    return timed_steps(n_steps, ms, [&] { return pdmpc_controller_centralized_step(c); });
+}
+
 const pdmpc_vehicle_out* pdmpc_controller_records(pdmpc_controller* c) { return c && !c->out.empty() ? c->out.data() : nullptr; }
 
 }  // extern "C"
@@ -958,6 +1011,14 @@ struct pdmpc_sweep {
     std::vector<int32_t> member, member_slot;  // whose it is, and which of that member's slots
     std::vector<pdmpc_vehicle_out> out;
     int32_t optimal_calls[2] = {0, 0};  // pdmpc_sweep_optimal_last_calls
+    // centralized members (pdmpc_sweep_centralized_*): the live members' joint problems one after the other as ONE pdmpc_plan_joint takes them
+    struct Centralized {
+        bool built = false;
+        std::vector<int32_t> problem_offset, member;  // [n_problems + 1], [n_problems]: whose problem it is
+        std::vector<pdmpc_vehicle_in> in;
+        std::vector<pdmpc_vehicle_out> out;
+        std::vector<int32_t> exhausted_at;  // [M] 0: live; else the time step at which the member's search ran empty
+    } cen;
     // the concatenated batch of prioritizations (pdmpc_sweep_explore_*, pdmpc_sweep_optimal_*): the members' flattened batches one after
     // the other, and their choices
     struct Batch {
@@ -1193,6 +1254,56 @@ int sweep_batch_step(pdmpc_sweep* s, std::chrono::steady_clock::time_point t, co
     s->timing[5] = ms_since(t);
     return rc;
 }
+
+// ---- centralized members
+// what pdmpc_sweep_centralized_* refuse before any member advances
+int sweep_centralized_refusal(pdmpc_sweep* s, bool needs_handle) {
+    if (const int rc = batch_refusal(s, needs_handle)) return rc;
+    for (pdmpc_controller* c : s->members)
+        if (const int rc = centralized_refusal(c)) return rc;
+    return PDMPC_OK;
+}
+// every live member's joint problem, one after the other
+void sweep_centralized_build(pdmpc_sweep* s) {
+    pdmpc_sweep::Centralized& X = s->cen;
+    X.problem_offset.assign(1, 0);
+    X.member.clear();
+    X.in.clear();
+    for (size_t m = 0; m < s->members.size(); ++m) {
+        if (X.exhausted_at[m]) continue;
+        pdmpc_controller* c = s->members[m];
+        centralized_build(c);
+        X.in.insert(X.in.end(), c->cen.in.begin(), c->cen.in.end());
+        X.problem_offset.push_back((int32_t)X.in.size());
+        X.member.push_back((int32_t)m);
+    }
+    X.built = true;
+}
+// the records of the built problems: every member's apply; a member whose search ran empty is retired, the others go on
+int sweep_centralized_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records, bool keep_records) {
+    pdmpc_sweep::Centralized& X = s->cen;
+    for (size_t p = 0; p < X.member.size(); ++p) {
+        const size_t m = (size_t)X.member[p];
+        pdmpc_controller* c = s->members[m];
+        const pdmpc_vehicle_out* r = records + X.problem_offset[p];
+        if (keep_records) {  // (pdmpc_controller_records, as the member's own step leaves them)
+            c->out.assign(r, r + c->sc.n);
+            r = c->out.data();
+        }
+        const int rc = centralized_apply(c, r);
+        if (rc == PDMPC_EXHAUSTED)
+            X.exhausted_at[m] = c->tr.k;
+        else if (rc)
+            return rc;
+    }
+    X.built = false;  // (one apply per build: a retired member's problem is not applied again)
+    return PDMPC_OK;
+}
+bool any_live(const pdmpc_sweep* s) {
+    for (int32_t k : s->cen.exhausted_at)
+        if (!k) return true;
+    return false;
+}
 }  // namespace
 
 extern "C" {
@@ -1217,6 +1328,7 @@ int pdmpc_sweep_create(pdmpc_handle* h, int32_t n_members, pdmpc_controller* con
     s->members.assign(members, members + n_members);
     s->first.assign(1, 0);
     for (int m = 0; m < n_members; ++m) s->first.push_back(s->first.back() + members[m]->sc.n);
+    s->cen.exhausted_at.assign((size_t)n_members, 0);
     *out = s;
     return PDMPC_OK;
 }
@@ -1338,6 +1450,55 @@ int pdmpc_sweep_optimal_step(pdmpc_sweep* s, int32_t max_instances) {
 
 int pdmpc_sweep_optimal_run(pdmpc_sweep* s, int32_t max_instances, int32_t n_steps, double* ms) {
     return timed_steps(n_steps, ms, [&] { return pdmpc_sweep_optimal_step(s, max_instances); });
+}
+
+// ---- centralized members of a sweep
+int pdmpc_sweep_centralized_build(pdmpc_sweep* s) {
+    if (const int rc = sweep_centralized_refusal(s, false)) return rc;
+    sweep_centralized_build(s);
+    return PDMPC_OK;
+}
+
+int pdmpc_sweep_centralized_problem(pdmpc_sweep* s, int32_t* n_problems, const int32_t** problem_offset, const pdmpc_vehicle_in** in, const int32_t** member) {
+    if (!s || !s->cen.built) return cfail(nullptr, PDMPC_ERR_INVALID, "pdmpc_sweep_centralized_problem before pdmpc_sweep_centralized_build");
+    if (n_problems) *n_problems = (int32_t)s->cen.member.size();
+    if (problem_offset) *problem_offset = s->cen.problem_offset.data();
+    if (in) *in = s->cen.in.data();
+    if (member) *member = s->cen.member.data();
+    return PDMPC_OK;
+}
+
+int pdmpc_sweep_centralized_apply(pdmpc_sweep* s, const pdmpc_vehicle_out* records) {
+    if (const int rc = sweep_refusal(s, !s || !records, "null argument", s && !s->cen.built, "pdmpc_sweep_centralized_apply before pdmpc_sweep_centralized_build")) return rc;
+    return sweep_guard(s, sweep_centralized_apply(s, records, false));
+}
+
+int pdmpc_sweep_centralized_step(pdmpc_sweep* s) {
+    if (const int rc = sweep_centralized_refusal(s, true)) return rc;
+    if (!any_live(s)) return cfail(nullptr, PDMPC_EXHAUSTED, "pdmpc_sweep_centralized_step: every member's search is exhausted");
+    auto t = std::chrono::steady_clock::now();
+    sweep_centralized_build(s);
+    pdmpc_sweep::Centralized& X = s->cen;
+    s->timing[0] = ms_since(t);
+    s->timing[4] = 0;
+    X.out.resize(X.in.size());
+    int rc = pdmpc_plan_joint(s->h, (int32_t)X.member.size(), X.problem_offset.data(), X.in.data(), X.out.data());
+    if (rc) return sweep_guard(s, cfail(nullptr, rc, std::string("pdmpc_plan_joint: ") + pdmpc_last_error()));
+    joint_call_timing(s->h, s->timing);
+    t = std::chrono::steady_clock::now();
+    rc = sweep_centralized_apply(s, X.out.data(), true);
+    s->timing[5] = ms_since(t);
+    return sweep_guard(s, rc);
+}
+
+int pdmpc_sweep_centralized_run(pdmpc_sweep* s, int32_t n_steps, double* ms) {
+    return timed_steps(n_steps, ms, [&] { return pdmpc_sweep_centralized_step(s); });
+}
+
+int pdmpc_sweep_centralized_status(pdmpc_sweep* s, int32_t* exhausted_at) {
+    if (!s || !exhausted_at) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
+    std::copy(s->cen.exhausted_at.begin(), s->cen.exhausted_at.end(), exhausted_at);
+    return PDMPC_OK;
 }
 
 int pdmpc_sweep_optimal_last_calls(pdmpc_sweep* s, int32_t* calls2) {

@@ -1,4 +1,4 @@
-// step_state.hpp — the state of the native step controller (step_controller.cpp, stage 4 of 6): the scratch of a step preparation, of the
+// step_state.hpp — the state of the native step controller (step_controller.cpp, stage 4 of 7): the scratch of a step preparation, of the
 // assembly and of a batch, and the controller itself as the parts that are written together.
 //
 // Two records and one path.  A StepProblem is what pdmpc_plan_step takes -- inputs, fallbacks, predecessor slots --
@@ -143,6 +143,13 @@ struct Batch {
     std::vector<int32_t> choice_chosen;  // [graphs] the candidate every graph chose
     std::vector<double> choice_cost;     // [cells]
 };
+
+// The joint problem of a centralized step (CentralizedController.m:33-59; step_centralized.hpp): one entry per vehicle in vehicle order,
+// every entry's obstacles the scenario's set under the same pointers (the arena keeps it alive until the next build)
+struct Centralized {
+    std::vector<pdmpc_vehicle_in> in;
+    bool built = false;
+};
 }  // namespace
 
 struct pdmpc_controller {
@@ -154,6 +161,7 @@ struct pdmpc_controller {
     FcaInputs fca;
     Assembly as;
     Batch x;
+    Centralized cen;
     bool follow_own = false;                // the explorative step applies the plans of the controller's OWN prioritization (instance 0) whatever the choice: the traffic then follows pdmpc_controller_step's closed loop (measurement: the same steps as a recorded replay)
     bool lean_explore = false;              // the explorative step reads back status + final cost of every plan and the chosen plans' records only
     bool device_choice = false;             // pdmpc_controller_set_device_choice: the lean step chooses and gathers on the device (pdmpc_plan_step_chosen)

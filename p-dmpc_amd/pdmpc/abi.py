@@ -222,6 +222,16 @@ class _Keep:
         self.refs.append(a)
         return a
 
+    def polygon_set(self, polys):
+        """pack_polygon_set, once per list of the same array objects: vehicles whose lists hold the same arrays (the scenario's
+        obstacles in every vehicle of a centralized step) hand the packer the same pointers, and it packs such a set once."""
+        sets = self.__dict__.setdefault("sets", {})
+        key = tuple(id(p) for p in polys)
+        if key not in sets:
+            self.refs.append(polys)  # (the ids stay those of these objects as long as the memo lives)
+            sets[key] = pack_polygon_set(polys, self)
+        return sets[key]
+
 
 def pack_polygon_set(polys, keep):
     """polys: list of (2, V) arrays -> PolygonSet."""
@@ -303,19 +313,19 @@ def pack_vehicle(it, Hp, keep, dst):
         setattr(dst, "n_" + name, n)
         setattr(dst, name + "_x", dp(sx))
         setattr(dst, name + "_y", dp(sy))
-    dst.obstacles = pack_polygon_set(list(it.obstacles), keep)
+    dst.obstacles = keep.polygon_set(list(it.obstacles))
     dyn = []
     for row in it.dynamic_obstacle_area:
         if len(row) != Hp:
             raise ValueError("dynamic_obstacle_area rows must have Hp entries")
         dyn += list(row)
-    dst.dynamic_obstacles = pack_polygon_set(dyn, keep)
+    dst.dynamic_obstacles = keep.polygon_set(dyn)
     hdv = []
     for row in it.hdv_reachable_sets:
         if len(row) != Hp:
             raise ValueError("hdv_reachable_sets rows must have Hp entries")
         hdv += list(row)
-    dst.hdv_reachable_sets = pack_polygon_set(hdv, keep)
+    dst.hdv_reachable_sets = keep.polygon_set(hdv)
 
 
 def pack_vehicles(iters, Hp):

@@ -691,6 +691,13 @@ class Handle:
         del keep
         return self._checked(out[:n])
 
+    def packed_offsets(self, vehicle):
+        """Where the last pack put `vehicle` in the point pool (pdmpc_debug_packed_offsets) -> (lit_off, hdv_off, (ll_off, ll_len))."""
+        lit, hdv = (np.zeros(abi.HP_MAX + 1, dtype=np.int32) for _ in range(2))
+        ll = np.zeros(2, dtype=np.int32)
+        _check(self.L, self.L.pdmpc_debug_packed_offsets(self.h, int(vehicle), abi.i32p(lit), abi.i32p(hdv), abi.i32p(ll)), "pdmpc_debug_packed_offsets")
+        return lit[: self.Hp + 1].tolist(), hdv[: self.Hp + 1].tolist(), (int(ll[0]), int(ll[1]))
+
     def upload_reachable_sets(self, local_sets):
         """pdmpc_upload_reachable_sets: the automaton's local hulls ([trim][k] (2, m), e.g. mpa.local_reachable_sets_conv)."""
         ps, keep = pack_local_sets(local_sets)

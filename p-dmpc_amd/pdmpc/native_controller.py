@@ -50,6 +50,25 @@ def _polys(ps):
     return out
 
 
+def _decode_iters(Hp, n, vin):
+    """n VehicleIn -> list[VehicleIter] (for tests)."""
+    from .iteration_data import VehicleIter
+
+    iters = []
+    for s in range(n):
+        v = vin[s]
+        dyn = _polys(v.dynamic_obstacles)
+        left = np.array([[v.left_x[q] for q in range(v.n_left)], [v.left_y[q] for q in range(v.n_left)]]) if v.n_left else None
+        right = np.array([[v.right_x[q] for q in range(v.n_right)], [v.right_y[q] for q in range(v.n_right)]]) if v.n_right else None
+        iters.append(VehicleIter(
+            x0=np.array([v.x0, v.y0, v.yaw0, 0.0]), trim_index=int(v.trim0),
+            reference_trajectory_points=np.array([[v.ref_x[q], v.ref_y[q]] for q in range(Hp)]), v_ref=np.array([v.v_ref[q] for q in range(Hp)]),
+            predicted_lanelet_boundary=(left, right), obstacles=_polys(v.obstacles),
+            dynamic_obstacle_area=[dyn[r * Hp : (r + 1) * Hp] for r in range(len(dyn) // Hp)],
+        ))
+    return iters
+
+
 class NativeController:
     def __init__(self, options, scenario, mpa, handle=None, coupling="full", priority_strategy="constant", weight_strategy="distance", optimizer="graph_search"):
         if scenario.dynamic_obstacle_area:
@@ -198,21 +217,8 @@ class NativeController:
         return {"order": order_l, "iters": iters, "preds": preds, "fallback": fallback, "level_sizes": level_sizes, "levels": [lv[v] for v in order_l]}
 
     def _decode(self, n, vin, po, pi, fb):
-        from .iteration_data import VehicleIter
-
-        Hp = self.Hp
-        iters, preds, fallback = [], [], []
+        iters, preds, fallback = _decode_iters(self.Hp, n, vin), [], []
         for s in range(n):
-            v = vin[s]
-            dyn = _polys(v.dynamic_obstacles)
-            left = np.array([[v.left_x[q] for q in range(v.n_left)], [v.left_y[q] for q in range(v.n_left)]]) if v.n_left else None
-            right = np.array([[v.right_x[q] for q in range(v.n_right)], [v.right_y[q] for q in range(v.n_right)]]) if v.n_right else None
-            iters.append(VehicleIter(
-                x0=np.array([v.x0, v.y0, v.yaw0, 0.0]), trim_index=int(v.trim0),
-                reference_trajectory_points=np.array([[v.ref_x[q], v.ref_y[q]] for q in range(Hp)]), v_ref=np.array([v.v_ref[q] for q in range(Hp)]),
-                predicted_lanelet_boundary=(left, right), obstacles=_polys(v.obstacles),
-                dynamic_obstacle_area=[dyn[r * Hp : (r + 1) * Hp] for r in range(len(dyn) // Hp)],
-            ))
             preds.append([int(pi[q]) for q in range(po[s], po[s + 1])])
             f = _polys(fb[s])
             fallback.append(f if f else None)
@@ -319,6 +325,36 @@ class NativeController:
     def optimal_run(self, max_instances, n_steps):
         """n_steps optimal-priority steps in one native call (status + final cost of every plan, the chosen records only) -> ms per step."""
         return _run(self._check, "pdmpc_controller_optimal_run", self.L.pdmpc_controller_optimal_run, self.c, max_instances, n_steps)
+
+    # ---- centralized control: twin of pdmpc.centralized.CentralizedController (pdmpc_controller_centralized_*)
+    def centralized_build(self):
+        """The joint problem of the next time step (CentralizedController.build_iters); advances the time step."""
+        self._check(self.L.pdmpc_controller_centralized_build(self.c), "pdmpc_controller_centralized_build")
+
+    def centralized_problem(self, raw=False):
+        """The joint problem of the last centralized_build -> list[VehicleIter] in vehicle order (raw: the VehicleIn array itself,
+        valid until the next build)."""
+        n = C.c_int32()
+        vin = C.POINTER(abi.VehicleIn)()
+        self._check(self.L.pdmpc_controller_centralized_problem(self.c, C.byref(n), C.byref(vin)), "pdmpc_controller_centralized_problem")
+        return (n.value, vin) if raw else _decode_iters(self.Hp, n.value, vin)
+
+    def centralized_apply(self, records):
+        """The records of the joint problem in vehicle order: the plant update.  An exhausted search raises BackendError with
+        .status == abi.EXHAUSTED and applies nothing."""
+        recs = np.ascontiguousarray(records)
+        if recs.shape[0] != self.n:
+            raise ValueError("a joint problem of %d vehicles takes %d records, not %d" % (self.n, self.n, recs.shape[0]))
+        self._check(self.L.pdmpc_controller_centralized_apply(self.c, abi.out_ptr(recs)), "pdmpc_controller_centralized_apply")
+
+    def centralized_step(self):
+        """One centralized time step natively (build, ONE joint search, apply) -> the records in vehicle order."""
+        self._check(self.L.pdmpc_controller_centralized_step(self.c), "pdmpc_controller_centralized_step")
+        return self.records()
+
+    def centralized_run(self, n_steps):
+        """n_steps centralized steps in one native call -> wall-clock milliseconds of every step."""
+        return _run(self._check, "pdmpc_controller_centralized_run", self.L.pdmpc_controller_centralized_run, self.c, n_steps)
 
     def state(self):
         n = self.n
@@ -480,6 +516,47 @@ class NativeSweep:
         calls = np.zeros(2, dtype=np.int32)
         self._check(self.L.pdmpc_sweep_optimal_last_calls(self.s, abi.i32p(calls)), "pdmpc_sweep_optimal_last_calls")
         return calls.tolist()
+
+    # ---- centralized members
+    def centralized_build(self):
+        """Every live member's joint problem (pdmpc_sweep_centralized_build)."""
+        self._check(self.L.pdmpc_sweep_centralized_build(self.s), "pdmpc_sweep_centralized_build")
+
+    def centralized_problem(self, raw=False):
+        """The live members' joint problems of the last centralized_build -> {"problems": list of list[VehicleIter], "problem_offset",
+        "member": whose each problem is} (raw: the VehicleIn array in place of the decoded problems)."""
+        n = C.c_int32()
+        off, mem = abi.c_int32_p(), abi.c_int32_p()
+        vin = C.POINTER(abi.VehicleIn)()
+        self._check(self.L.pdmpc_sweep_centralized_problem(self.s, C.byref(n), C.byref(off), C.byref(vin), C.byref(mem)), "pdmpc_sweep_centralized_problem")
+        offs = [int(off[p]) for p in range(n.value + 1)]
+        out = {"problem_offset": offs, "member": [int(mem[p]) for p in range(n.value)]}
+        if raw:
+            out["in"] = vin
+        else:
+            iters = _decode_iters(self.members[0].Hp, offs[-1], vin)
+            out["problems"] = [iters[offs[p] : offs[p + 1]] for p in range(n.value)]
+        return out
+
+    def centralized_apply(self, records):
+        """The records of the built problems, problem after problem: every member's apply; an exhausted member is retired."""
+        recs = np.ascontiguousarray(records)
+        self._check(self.L.pdmpc_sweep_centralized_apply(self.s, abi.out_ptr(recs)), "pdmpc_sweep_centralized_apply")
+
+    def centralized_step(self):
+        """One centralized lock-step natively (ONE pdmpc_plan_joint for all live members) -> centralized_status()."""
+        self._check(self.L.pdmpc_sweep_centralized_step(self.s), "pdmpc_sweep_centralized_step")
+        return self.centralized_status()
+
+    def centralized_run(self, n_steps):
+        """n_steps centralized lock-steps in one native call -> wall-clock milliseconds of every lock-step."""
+        return _run(self._check, "pdmpc_sweep_centralized_run", self.L.pdmpc_sweep_centralized_run, self.s, n_steps)
+
+    def centralized_status(self):
+        """Per member 0, or the time step at which its search ran empty (pdmpc_sweep_centralized_status)."""
+        st = np.zeros(max(len(self.members), 1), dtype=np.int32)
+        self._check(self.L.pdmpc_sweep_centralized_status(self.s, abi.i32p(st)), "pdmpc_sweep_centralized_status")
+        return st[: len(self.members)].tolist()
 
     def prep_calls(self):
         """The step-preparation calls of the last build, whatever the number of members (pdmpc_sweep_last_prep_calls): [lanelet

@@ -78,6 +78,7 @@ PROTOTYPES = {
     "pdmpc_debug_edge_check": (INT, [OBJ, I32, I32, IP, DP, DP, IP, DP, DP, IP]),
     "pdmpc_debug_raw_tree": (INT, [OBJ, I32, I32] + [DP] * 5 + [IP] * 3 + [DP, BP, IP]),
     "pdmpc_debug_counters": (INT, [OBJ, P(C.c_uint64)]),
+    "pdmpc_debug_packed_offsets": (INT, [OBJ, I32, IP, IP, IP]),
     "pdmpc_debug_progress": (INT, [OBJ, I32, UP]),
     "pdmpc_debug_heap_script": (INT, [OBJ, I32, IP, IP, DP, I32, IP, IP, DP, DP]),
     # ---- the sampled optimizer
@@ -146,6 +147,11 @@ PROTOTYPES = {
     "pdmpc_controller_seeds": (INT, [OBJ, P(I32), P(UP)]),
     "pdmpc_controller_priorities": (INT, [OBJ, P(I32), P(IP), P(I32), P(IP)]),
     "pdmpc_controller_set_device_choice": (INT, [OBJ, I32]),
+    "pdmpc_controller_centralized_build": (INT, [OBJ]),
+    "pdmpc_controller_centralized_problem": (INT, [OBJ, P(I32), P(VIN)]),
+    "pdmpc_controller_centralized_apply": (INT, [OBJ, VOUT]),
+    "pdmpc_controller_centralized_step": (INT, [OBJ]),
+    "pdmpc_controller_centralized_run": (INT, [OBJ, I32, DP]),
     # ---- several closed loops in lock-step
     "pdmpc_sweep_create": (INT, [OBJ, I32, P(OBJ), P(OBJ)]),
     "pdmpc_sweep_destroy": (INT, [OBJ]),
@@ -167,6 +173,12 @@ PROTOTYPES = {
     "pdmpc_sweep_optimal_step": (INT, [OBJ, I32]),
     "pdmpc_sweep_optimal_run": (INT, [OBJ, I32, I32, DP]),
     "pdmpc_sweep_optimal_last_calls": (INT, [OBJ, IP]),
+    "pdmpc_sweep_centralized_build": (INT, [OBJ]),
+    "pdmpc_sweep_centralized_problem": (INT, [OBJ, P(I32), P(IP), P(VIN), P(IP)]),
+    "pdmpc_sweep_centralized_apply": (INT, [OBJ, VOUT]),
+    "pdmpc_sweep_centralized_step": (INT, [OBJ]),
+    "pdmpc_sweep_centralized_run": (INT, [OBJ, I32, DP]),
+    "pdmpc_sweep_centralized_status": (INT, [OBJ, IP]),
     # ---- several GPUs behind the same boundary
     "pdmpc_group_create": (INT, [CONFIG, I32, IP, P(OBJ)]),
     "pdmpc_group_create_ex": (INT, [CONFIG, I32, IP, I32, P(OBJ)]),

@@ -1,7 +1,7 @@
 """What one joint search of centralized control costs on the GPU (pdmpc_plan_joint) and in the Python reference
 (tests/joint_reference.py), on the same problems.
 
-    python tools/joint_timing.py [--repeat R] [--out FILE]
+    python tools/joint_timing.py [--repeat R] [--out FILE] [--batched M [M ...]]
 
 Workloads:
   systemtest  Config_systemtests_centralized.json on the circle: 2 vehicles, single_speed, Hp 5, the 20 problems of its closed loop
@@ -9,6 +9,10 @@ Workloads:
 Per workload: kernel ms per joint search (HIP events of the launch, median of R repeats), pops and tree size per search, and the
 reference's seconds for the same searches.  Run under `rocprofv3 --kernel-trace --stats -- python tools/joint_timing.py` for the
 profiler's kernel summary.
+
+--batched M: instead of the workloads above, M joint problems (the systemtest's 20, repeated) in ONE pdmpc_plan_joint -- one launch, one
+wavefront per problem, what a sweep of M centralized closed loops hands over per time step -- against the same M problems in M calls
+of one problem each: kernel ms (HIP events) and wall ms of the calls (the Python marshalling of the problems included in both).
 """
 import argparse
 import os
@@ -30,8 +34,8 @@ from pdmpc.scenario import circle_scenario  # noqa: E402
 import joint_reference as jr  # noqa: E402
 
 
-def closed_loop_problems(N, Hp, steps):
-    options = centralized_options(Config(scenario_type=ScenarioType.circle, amount=N, Hp=Hp, mpa_type=MpaType.single_speed, T_end=4, max_vehicles=8))
+def closed_loop_problems(N, Hp, steps, max_vehicles=8):
+    options = centralized_options(Config(scenario_type=ScenarioType.circle, amount=N, Hp=Hp, mpa_type=MpaType.single_speed, T_end=4, max_vehicles=max_vehicles))
     mpa = centralized_mpa(options)
     out = []
     ref_s = 0.0
@@ -74,20 +78,55 @@ def measure(name, options, mpa, probs, ref_s, repeat, lines):
     lines.append("  reference / GPU: %.1fx" % (ref_s * 1e3 / max(sum(per), 1e-9)))
 
 
+def measure_batched(M, repeat, lines):
+    """M problems in one launch against M launches of one problem"""
+    options, mpa, probs, _ = closed_loop_problems(2, 5, 20, max_vehicles=2 * M)
+    batch = [probs[i % len(probs)] for i in range(M)]
+    h = Handle(options)
+    h.upload_mpa(mpa)
+    h.plan_joint(batch)  # (code object load, and the arena grows to what the largest problem needs)
+    one_k, one_w, many_k, many_w = [], [], [], []
+    for _ in range(repeat):
+        t = time.perf_counter()
+        h.plan_joint(batch)
+        one_w.append(1e3 * (time.perf_counter() - t))
+        st = h.stats()
+        assert st["n_launches"] == 1, st
+        one_k.append(st["kernel_ms"])
+        t = time.perf_counter()
+        k = 0.0
+        for prob in batch:
+            h.plan_joint([prob])
+            k += h.stats()["kernel_ms"]
+        many_w.append(1e3 * (time.perf_counter() - t))
+        many_k.append(k)
+    h.close()
+    med = statistics.median
+    lines.append("batched: %d joint searches of 2 vehicles, Hp 5 (the systemtest's 20 problems, repeated)" % M)
+    lines.append("  ONE launch of %d problems: kernel ms median %.3f  min %.3f   wall ms of the call median %.3f" % (M, med(one_k), min(one_k), med(one_w)))
+    lines.append("  %d launches of one problem: kernel ms (sum) median %.3f  min %.3f   wall ms of the calls median %.3f" % (M, med(many_k), min(many_k), med(many_w)))
+    lines.append("  single launches / one launch: kernel %.1fx  wall %.1fx" % (med(many_k) / max(med(one_k), 1e-9), med(many_w) / max(med(one_w), 1e-9)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--batched", type=int, nargs="+", default=None, metavar="M")
     a = ap.parse_args()
     lines = []
-    options, mpa, probs, ref_s = closed_loop_problems(2, 5, 20)
-    measure("systemtest (circle, 2 vehicles)", options, mpa, probs, ref_s, a.repeat, lines)
-    options, mpa, probs, _ = closed_loop_problems(3, 4, 3)
-    prob = probs[2]
-    t = time.perf_counter()
-    jr.plan_joint(options, mpa, [prob])
-    ref_s = time.perf_counter() - t
-    measure("n3 (circle, 3 vehicles)", options, mpa, [prob], ref_s, a.repeat, lines)
+    if a.batched:
+        for M in a.batched:
+            measure_batched(M, a.repeat, lines)
+    else:
+        options, mpa, probs, ref_s = closed_loop_problems(2, 5, 20)
+        measure("systemtest (circle, 2 vehicles)", options, mpa, probs, ref_s, a.repeat, lines)
+        options, mpa, probs, _ = closed_loop_problems(3, 4, 3)
+        prob = probs[2]
+        t = time.perf_counter()
+        jr.plan_joint(options, mpa, [prob])
+        ref_s = time.perf_counter() - t
+        measure("n3 (circle, 3 vehicles)", options, mpa, [prob], ref_s, a.repeat, lines)
     text = "\n".join(lines)
     print(text)
     if a.out:
