@@ -168,7 +168,7 @@ typedef struct {
  *     PDMPC_TUNING="key=value,key=value,..."
  * keys: round0 round ramp ready share_min tile mid_min mid_fill (rounds and lists), tentative fast_arrival speculate helpers
  * helpers_oversub helpers_first seat_nodes waves compact generic (A/B switches; compact takes -1, 0 or 1), force_tie reverse_dispatch
- * spin_limit (testing), debug_tail debug_lds debug_host debug_progress (diagnostics); csrc/handle.hpp: struct Tuning documents each.
+ * spin_limit (testing), debug_tail debug_lds debug_host debug_progress (diagnostics); csrc/launch_plan.hpp: struct Tuning documents each.
  * The search kernels have the defaults of tentative fast_arrival speculate force_tie reverse_dispatch debug_tail compiled
  * in; any other value of one of them, or generic=1, runs the kernels' generic twins, which read them at run time.
  * No setting changes a result; an unknown key fails pdmpc_create. */
@@ -177,6 +177,36 @@ typedef struct {
  *      and the MEX instance table of priority_queue_interface_mex.cpp:48-53,111) ---- */
 int pdmpc_create(const pdmpc_config* config, pdmpc_handle** out_handle);
 int pdmpc_destroy(pdmpc_handle* handle);
+
+/* The plan of a launch, without a device (csrc/launch_plan.hpp): what pdmpc_launch_range / pdmpc_plan_joint decide
+ * before they launch -- the LDS layout, the kernel, the sizes of the rounds, the helper workgroups, the slices of the safe mode -- from the
+ * same functions they call.  tuning: a PDMPC_TUNING string (NULL or empty: the defaults).  query: the configuration (checker, Hp), the
+ * automaton (n_trims, n_man: maneuvers), the device (n_cu compute units, device_share: pdmpc_set_device_share, max_nodes: the arena's),
+ * the launch (kind: 0 graph search, 1 sampled optimizer, 2 joint search; count: searches / vehicles / problems; n_chained: how many of
+ * them have predecessors; safe: pdmpc_set_safe_launch) and the packed batch (soup_cap: obstacle columns -- for a joint launch the most
+ * distinct soup columns of a problem + 2 --, ll_cap: boundary columns, cand_cap: segments of one edge check).  plan: the layout's
+ * numbers, the launch policy (the fields of the same names in csrc/pdmpc_device.h: KernelArgs), variant / generic / kernel (which search
+ * kernel, static name), slice (searches per kernel launch), heap_lds (joint), then every region's byte offset (graph search and sampled
+ * optimizer: LdsLayout; joint: JointLds, the others 0).  PDMPC_ERR_INVALID: a tuning error (pdmpc_last_error: the text pdmpc_create
+ * gives); PDMPC_ERR_CAPACITY: the soup and the automaton's tables do not fit into LDS. */
+typedef struct {
+    int32_t checker, Hp, n_trims, n_man;
+    int32_t n_cu, device_share, max_nodes;
+    int32_t kind;
+    int32_t count, n_chained;
+    int32_t soup_cap, ll_cap, cand_cap, safe;
+} pdmpc_launch_query;
+typedef struct {
+    int32_t n_waves, NL, NV, areas_in_lds, ready, compact;
+    int32_t bk_ready_cap, bk_round0, bk_round, bk_ramp, bk_tile, bk_share_min, n_helpers, bk_helpers_first, bk_seat_nodes, reverse_dispatch;
+    int32_t variant, generic, slice, heap_lds;
+    uint32_t spin_limit;
+    uint32_t mask, man_index, pose, area, ref, shape, path, soup, cand, vstate, expand, tree16, rand, nodes, total;
+    uint32_t bk_near_key, bk_near_id, bk_ready, bk_hist, bk_misc, bk_pshape, reach_shared, bk_reach, reach;
+    uint32_t ints, succ, heap_key, heap_id;
+    const char* kernel;
+} pdmpc_launch_plan;
+int pdmpc_launch_plan_host(const char* tuning, const pdmpc_launch_query* query, pdmpc_launch_plan* plan);
 
 /* the configuration the handle runs with (defaults filled in, max_nodes = current arena size) and whether the MPA is uploaded */
 int pdmpc_get_config(pdmpc_handle* handle, pdmpc_config* config, int32_t* mpa_uploaded);

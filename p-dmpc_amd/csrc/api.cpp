@@ -28,250 +28,12 @@ namespace {
 
 thread_local std::string g_err;  // pdmpc_last_error: every translation unit reports through pdmpc_set_last_error (fail, handle.hpp)
 
-inline uint32_t align16(uint32_t v) { return (v + 15u) & ~15u; }
-
-const size_t kLdsMax = 160 * 1024;  // gfx950: 160 KiB per CU (MI355X_MICROARCH.md)
-
-// parses PDMPC_TUNING; an unknown key or a malformed entry is an error (a typo must not silently measure the default)
-bool parse_tuning(const char* text, Tuning& T, std::string& err) {
-    struct Key { const char* name; int* dst; };
-    int spin = (int)T.spin_limit;
-    const Key keys[] = {{"round0", &T.round0}, {"round", &T.round}, {"ramp", &T.ramp}, {"ready", &T.ready}, {"share_min", &T.share_min},
-                        {"tile", &T.tile}, {"mid_min", &T.mid_min}, {"mid_fill", &T.mid_fill}, {"tentative", &T.tentative}, {"fast_arrival", &T.fast_arrival}, {"helpers_first", &T.helpers_first}, {"seat_nodes", &T.seat_nodes},
-                        {"helpers", &T.helpers}, {"helpers_oversub", &T.helpers_oversub}, {"speculate", &T.speculate}, {"waves", &T.waves}, {"compact", &T.compact}, {"spin_limit", &spin},
-                        {"force_tie", &T.force_tie}, {"reverse_dispatch", &T.reverse_dispatch}, {"debug_tail", &T.debug_tail}, {"debug_lds", &T.debug_lds},
-                        {"debug_host", &T.debug_host}, {"debug_progress", &T.debug_progress}, {"generic", &T.generic}};
-    std::string str(text ? text : "");
-    size_t pos = 0;
-    while (pos < str.size()) {
-        size_t end = str.find(',', pos);
-        if (end == std::string::npos) end = str.size();
-        const std::string item = str.substr(pos, end - pos);
-        pos = end + 1;
-        if (item.empty()) continue;
-        const size_t eq = item.find('=');
-        if (eq == std::string::npos || eq == 0 || eq + 1 >= item.size()) {
-            err = "PDMPC_TUNING: '" + item + "' is not key=value";
-            return false;
-        }
-        const std::string name = item.substr(0, eq);
-        char* tail = nullptr;
-        const long v = strtol(item.c_str() + eq + 1, &tail, 10);
-        if (!tail || *tail) {
-            err = "PDMPC_TUNING: value of '" + name + "' is not an integer";
-            return false;
-        }
-        bool found = false;
-        for (const Key& k : keys)
-            if (name == k.name) {
-                *k.dst = (int)v;
-                found = true;
-            }
-        if (!found) {
-            err = "PDMPC_TUNING: unknown key '" + name + "'";
-            return false;
-        }
-    }
-    if (T.compact < -1 || T.compact > 1) {
-        err = "PDMPC_TUNING: compact takes -1, 0 or 1";
-        return false;
-    }
-    if (T.round0 >= 0) T.round0 = std::max(1, T.round0);
-    if (T.round >= 0) T.round = std::max(1, T.round);
-    if (T.ramp >= 0) T.ramp = std::max(1, T.ramp);
-    T.ready = std::min(2048, std::max(256, T.ready)) & ~63;
-    if (T.share_min >= 0) T.share_min = std::max(32, T.share_min);
-    if (T.tile >= 0) T.tile = std::min(768, std::max(8, T.tile));
-    T.mid_min = std::max(0, T.mid_min);
-    T.mid_fill = std::max(256, T.mid_fill);
-    if (T.waves >= 0) T.waves = std::min(PDMPC_MAX_WAVES, std::max(4, T.waves));
-    T.spin_limit = (uint32_t)std::max(1024, spin);
-    return true;
-}
-}  // namespace
-
-namespace {
-
 // The dynamic LDS size of a kernel is an attribute of the function ON THE DEVICE, not of a handle (hipFuncSetAttribute sets a
 // maximum): the largest size set so far is kept per device, kernel (0 bulk, 1 bulk wide, 2 bulk SAT, 3 bulk compact) and instantiation
 // (0 product, 1 generic: two functions on the device; kernels in the order of PDMPC_BULK ...), shared by every handle.
 std::mutex g_lds_mutex;
 uint32_t g_lds_high_water[64][4][2];
-const char* const kBulkKernelNames[4][2] = {{"pdmpc_bulk_kernel", "pdmpc_bulk_kernel_any"},
-                                            {"pdmpc_bulk_kernel_wide", "pdmpc_bulk_kernel_wide_any"},
-                                            {"pdmpc_bulk_kernel_sat", "pdmpc_bulk_kernel_sat_any"},
-                                            {"pdmpc_bulk_kernel_compact", "pdmpc_bulk_kernel_compact_any"}};
-// The automaton's tables, the front of every LDS layout from `off` on: successor masks, maneuver index, poses, then the maneuver
-// areas (only with `areas`: else they are read from L2).  Returns the first free byte.
-template <class Layout>
-uint32_t layout_mpa(const pdmpc_handle* h, uint32_t off, bool areas, Layout& L) {
-    L.mask = off;
-    off = align16(off + (uint32_t)h->mask_bytes);
-    L.man_index = off;
-    off = align16(off + (uint32_t)h->mi_bytes);
-    L.pose = off;
-    off = align16(off + (uint32_t)(h->n_man * sizeof(DevManPose)));
-    L.area = off;
-    if (areas) off = align16(off + (uint32_t)(h->n_man * 3 * PDMPC_VMAX * 16));
-    return off;
-}
 
-// LDS layout of the graph search: MPA tables, reference, per-wave tallies, shared words, obstacle soup, phase B's chunk state (12 B per
-// thread), d_traveled table, the LDS part of the open set (PDMPC_BK_PER entries per thread), the ready list with its collision
-// flags, the histogram / goal list / expansion lists, 2 KB of small tables, the areas of the published path, validity bytes, then
-// as many node records as fit.
-bool layout_bulk(const pdmpc_handle* h, size_t budget, int n_waves, int areas, int soup_cap, int ll_cap, LdsLayout& L, uint32_t& nv, uint32_t& nl, uint32_t ready_cap, bool compact, bool tight = false) {
-    const uint32_t lk_waves = compact ? PDMPC_LK_COMPACT_WAVES : PDMPC_MAX_WAVES, lk_ready = compact ? PDMPC_LK_COMPACT_READY_CAP : 2048u, lk_per = compact ? PDMPC_LK_COMPACT_BK_PER : PDMPC_BK_PER;
-    if (ready_cap > lk_ready || (uint32_t)n_waves > lk_waves) return false;
-    // the regions of fixed size at the kernel's compile-time offsets (pdmpc_device.h: PDMPC_LK_*) ...
-    // ... the reach lists right behind them (InterX only: the separating-axis kernels have none and keep their layout; 2 B per soup
-    // column, the boundary's once per step: their address is a constant too.  tight: ONE list of the boundary, the last step's, serves
-    // every step — a superset of each step's own — and fewer node records are asked for: the layout of last resort, for a soup and
-    // tables that leave the LDS no room for more) ...
-    L.reach = pdmpc_lk_fixed(lk_waves, lk_ready, lk_per, &L);
-    L.reach_shared = tight ? 1u : 0u;
-    const uint32_t list_entries = h->cfg.checker == PDMPC_CHECK_INTERX ? (uint32_t)(std::max(soup_cap, 1) + (tight ? 0 : (h->cfg.Hp - 1) * std::max(ll_cap, 0))) : 0u;
-    // ... the automaton's tables and the soup behind them
-    uint32_t off = layout_mpa(h, align16(L.reach + list_entries * 2), areas, L);
-    L.soup = off;
-    off = align16(off + (uint32_t)std::max(soup_cap, 1) * 16);
-    L.tree16 = L.bk_hist;  // (the sampled optimizer's region: not part of this layout)
-    // (LDS-resident node records are a cache of the arena's first NL nodes: every access takes the HBM copy for a node beyond NL
-    // (node_piece, node_store), and the joint search runs the same code with NL = 0.  64 is what keeps a light search's first rounds in
-    // LDS; the layout of last resort asks for 16 — the root and its children — because its alternative is PDMPC_ERR_CAPACITY)
-    const uint32_t min_nodes = (tight ? 16u : 64u) * (uint32_t)sizeof(NodeRec) + 1024;
-    if ((size_t)off + min_nodes + 256 > budget) return false;
-    const uint32_t rest = (uint32_t)(budget - off - 256);
-    nv = std::min<uint32_t>(16384u, std::max<uint32_t>(compact ? 512u : 1024u, rest / 6));
-    nv = std::min(nv, h->arena.max_nodes) & ~15u;
-    nl = std::min((rest - nv) / (uint32_t)sizeof(NodeRec), h->arena.max_nodes);
-    L.vstate = off;
-    off += align16(nv);
-    L.nodes = off;
-    off += nl * (uint32_t)sizeof(NodeRec);
-    L.total = align16(off);
-    return L.total <= budget;
-}
-
-// helper workgroups serve the launches that leave CUs idle (launch_policy)
-bool bulk_has_helpers(const Tuning& T, int n_cu, int n_launch) {
-    if (!T.speculate || T.helpers == 0) return false;
-    if (n_launch > n_cu) return T.helpers_oversub != 0;  // (the tail of a launch with more searches than CUs)
-    return n_launch <= n_cu - 2;
-}
-
-int compute_lds_bulk(const pdmpc_handle* h, int n_launch, int soup_cap, int ll_cap, LaunchLayout& out) {
-    const Tuning& T = h->tune;
-    // large rounds pay where helper workgroups share them; without helpers the LDS is better spent on node records
-    const int ready_want = bulk_has_helpers(T, h->n_cu, n_launch) ? T.ready : std::max(256, T.ready / 2);
-    // Sixteen wavefronts where the kernel's registers allow four per SIMD (measured against twelve: C2 +1.5 %, C3 +1.3 %, C4 +7.5 %;
-    // C5, five light searches per CU one after the other, -1.7 %: it keeps twelve and the LDS-resident nodes that go with them)
-    const int cap = h->cfg.checker == PDMPC_CHECK_SAT ? PDMPC_MAX_WAVES_SAT : PDMPC_MAX_WAVES;
-    // Two workgroups per CU (bulk_kernel_compact.hip: 8 wavefronts, at most half the LDS, a near list of 1 024 entries, the automaton's
-    // areas in L2) for launches of more than two searches per CU — C5's class: light searches one after the other on every CU, each
-    // bound by the latency of its own passes; two side by side fill each other's gaps (C5 557 -> 710 steps/s).  NOT for launches whose
-    // step is one heavy search (C4, 512 searches: 94.6 -> 31 steps/s with it — half the lanes, a quarter of the near list, rounds of
-    // 240 entries that are never shared).  InterX with one mask word only; falls back to the full layout if the soup does not fit.
-    const bool want_compact = h->cfg.checker == PDMPC_CHECK_INTERX && h->n_words == 1 && (T.compact > 0 || (T.compact < 0 && n_launch > 2 * h->n_cu));
-    uint32_t nv = 0, nl = 0;
-    if (want_compact) {
-        LdsLayout L{};
-        const int waves = T.waves >= 0 ? std::min(T.waves, PDMPC_LK_COMPACT_WAVES) : PDMPC_LK_COMPACT_WAVES;
-        const int ready = std::min(std::min(ready_want, 3 * PDMPC_WAVE * waves), (int)PDMPC_LK_COMPACT_READY_CAP);
-        if (layout_bulk(h, kLdsMax / 2, waves, 0, soup_cap, ll_cap, L, nv, nl, (uint32_t)ready, true)) {
-            out = {L, waves, (int)nl, (int)nv, 0, ready, true};
-            return PDMPC_OK;
-        }
-    }
-    const int waves = T.waves >= 0 ? std::min(T.waves, cap) : (n_launch > 2 * h->n_cu ? std::min(12, cap) : cap);
-    for (int areas = 1; areas >= 0; --areas) {  // (the maneuver areas fall back to L2 when the soup leaves no room)
-        LdsLayout L{};
-        const int ready = std::min(ready_want, 3 * PDMPC_WAVE * waves);
-        if (!layout_bulk(h, kLdsMax, waves, areas, soup_cap, ll_cap, L, nv, nl, (uint32_t)ready, false)) continue;
-        out = {L, waves, (int)nl, (int)nv, areas, ready, false};
-        return PDMPC_OK;
-    }
-    {
-        LdsLayout L{};
-        const int ready = std::min(ready_want, 3 * PDMPC_WAVE * waves);
-        if (layout_bulk(h, kLdsMax, waves, 0, soup_cap, ll_cap, L, nv, nl, (uint32_t)ready, false, true)) {
-            out = {L, waves, (int)nl, (int)nv, 0, ready, false};
-            return PDMPC_OK;
-        }
-    }
-    char buf[256];
-    snprintf(buf, sizeof buf, "obstacle soup (%d columns) + MPA tables do not fit into %zu B of LDS", soup_cap, kLdsMax);
-    return fail(PDMPC_ERR_CAPACITY, buf);
-}
-
-// LDS layout of the sampled optimizer (one wavefront per vehicle): MPA tables, reference, the wave's two shapes, offsets, obstacle
-// soup (with the predecessors' columns the packer counts into soup_cap), the candidate segments of one edge check, its tree
-// (288 nodes x (16 children + parent + trim) x 2 B; the random generator's state before the tree is set up) and its Hp * 250 random
-// numbers (32 000 B at Hp 16).  80 KB first (two workgroups per CU), then the whole 160 KB (one); the automaton's areas go to L2
-// before a layout takes the larger budget.
-int compute_lds_sampled(const pdmpc_handle* h, int soup_cap, int cand_cap, LaunchLayout& out) {
-    static_assert(288u * 16u * 2u >= 624u * 4u, "the tree region holds the generator's state");
-    for (int pass = 0; pass < 4; ++pass) {
-        const int areas = pass == 0 || pass == 2;
-        const size_t budget = pass < 2 ? kLdsMax / 2 : kLdsMax;
-        LdsLayout L{};
-        uint32_t off = layout_mpa(h, 0, areas, L);
-        L.ref = off;
-        off += 3 * PDMPC_HP_MAX * 8;
-        L.shape = off;
-        off += (2 * PDMPC_VMAX + 1) * 16;
-        L.path = off;
-        off += PDMPC_LK_PATH_BYTES;
-        L.soup = off;
-        off = align16(off + (uint32_t)std::max(soup_cap, 1) * 16);
-        L.cand = off;
-        off += align16((uint32_t)std::max(cand_cap, 1) * 4u);
-        L.expand = off;
-        off += (2 * PDMPC_HP_MAX * PDMPC_HP_MAX) * 8 + 16 * 16;
-        L.tree16 = off;
-        off += align16(288u * 18u * 2u);
-        L.rand = off;
-        off += align16((uint32_t)h->cfg.Hp * 250u * 8u);
-        L.total = align16(off);
-        if (L.total <= budget) {
-            out = {L, 1, 0, 0, areas, h->tune.ready, false};  // (one wavefront, no ready list: the kernel reads none of the rounds' arguments)
-            return PDMPC_OK;
-        }
-    }
-    return fail(PDMPC_ERR_CAPACITY, "obstacle soup + MPA tables do not fit into the LDS budget of the sampled optimizer");
-}
-
-// LDS layout of the joint search (one wavefront per problem): MPA tables, every vehicle's reference, the node's areas, offsets and the
-// path, successor lists, the problem's distinct soups (soup_cap: pdmpc_joint_soup_columns), then the LDS part of the open list.  Aimed at 64 KB (two workgroups per CU and more);
-// a problem whose tables and soups do not leave room for 256 heap entries there may take up to the whole 160 KB.
-int layout_joint(pdmpc_handle* h, int soup_cap, JointLds& L, uint32_t& heap_lds, int& areas_in_lds) {
-    for (int pass = 0; pass < 4; ++pass) {
-        const bool areas = pass == 0 || pass == 2;
-        const size_t budget = pass < 2 ? 64 * 1024 : kLdsMax;
-        uint32_t off = layout_mpa(h, 0, areas, L);
-        L.ref = off;
-        off += PDMPC_JOINT_MAX * 3 * PDMPC_HP_MAX * 8;
-        L.shape = off;
-        off += PDMPC_JOINT_MAX * 2 * PDMPC_VMAX * 16;
-        L.ints = off;
-        off = align16(off + PDMPC_JOINT_INTS * 4);
-        L.succ = off;
-        off = align16(off + (uint32_t)(PDMPC_JOINT_MAX * h->n_trims * 4));
-        L.soup = off;
-        off = align16(off + (uint32_t)std::max(soup_cap, 1) * 16);
-        if (off + 256 * 12 > budget) continue;
-        const uint32_t entries = std::min<uint32_t>(8192u, (uint32_t)((budget - off) / 12) & ~63u);
-        L.heap_key = off;
-        off += entries * 8;
-        L.heap_id = off;
-        off += entries * 4;
-        L.total = align16(off);
-        heap_lds = entries;
-        areas_in_lds = areas ? 1 : 0;
-        return PDMPC_OK;
-    }
-    return fail(PDMPC_ERR_CAPACITY, "the MPA tables and a joint problem's obstacle soups do not fit into LDS");
-}
 // what the graph search, the sampled optimizer and the joint search (KernelArgs, JointArgs) all read: the automaton, the packed
 // batch, the records, the arenas' size, the tree sizes and work counters
 template <class Args>
@@ -294,103 +56,30 @@ void set_batch_args(const pdmpc_handle* h, const PackedStep& B, int areas_in_lds
     a.work_count = h->d_work_count.p;
 }
 
-// The launch policy: the sizes of a launch's rounds, its helper workgroups and where they sit -- bk_ready_cap, bk_round0, bk_round, bk_ramp,
-// bk_tile, bk_share_min, n_helpers and bk_helpers_first of `a`, and nothing else of it.  No HIP call, nothing of the handle touched: every
-// value it gives leaves the records bit-identical (struct Tuning), so only a benchmark sees it.  `slots`: the host records of the
-// launch's slots (read only where the place of the helpers depends on how many of them have predecessors).
-void launch_policy(const Tuning& T, int count, int n_cu, int device_share, bool safe, bool search, const LaunchLayout& lay, const DevVehicle* slots, KernelArgs& a) {
-    // rounds: measured on C2 / C3 (20 / 128 searches, helpers): cap 256, ramp 4 -> 646 / 589 steps/s; 512, 2 -> 735 / 786; 1000, 2 -> 769 / 909; 1000, 1 -> 620 / 772
-    const bool helped = search && !safe && bulk_has_helpers(T, n_cu, count);
-    a.bk_ready_cap = std::min(lay.ready, 3 * PDMPC_WAVE * lay.n_waves);  // (the verdict pass handles three entries per thread)
-    a.bk_round0 = T.round0 > 0 ? T.round0 : 24;  // (C3's class: below, once the helpers are counted)
-    a.bk_round = std::min(lay.ready / 2 - 16, std::max(a.bk_round0, T.round > 0 ? T.round : (helped ? 1000 : 256)));
-    a.bk_ramp = T.ramp > 0 ? T.ramp : (helped ? 2 : 4);
-    a.bk_tile = T.tile > 0 ? T.tile : 256;
-    if (lay.compact) a.bk_tile = std::min(a.bk_tile, 256);  // (a helper stages its range in the near list's room: 12 KB in the compact layout)
-    // Helper workgroups: the trailing workgroups of the launch, on the CUs it leaves idle, check tiles of the searches' large rounds.
-    // A launch with more searches than CUs gets them for its tail, when CUs fall idle while a few long searches still run (measured on
-    // C4, 512 searches: none 25.6 steps/s, 32 helpers 41.5, 96: 42.8-45.9; C5, 1 280 searches: none 478 steps/s, 64 behind the searches 543,
-    // 200: 549, with rounds shared from 64 nodes on 560 — the last levels' searches, which run when the CUs fall idle, are the tail of
-    // the step).  In the safe mode a launch gets none: they would sit where a slice's search could run.
-    a.n_helpers = 0;
-    if (helped) {
-        if (count <= n_cu) {
-            // every CU the launch leaves idle: a seated helper polls a word of its own, so helpers cost the searches nothing (measured on
-            // C2, 20 searches: 32 helpers 1 110 steps/s, 64: 1 120, 96: 1 190, 128: 1 200, 200: 1 210, 230: 1 235; with the ticket word of
-            // rounds 3-4 that all helpers polled and claimed from, 64 helpers were slower than 32 and 200 cost 40 %)
-            int want = n_cu - count;
-            if (T.helpers >= 0) want = T.helpers;
-            a.n_helpers = std::max(0, std::min(want, n_cu - count));
-            if (a.n_helpers < 2) a.n_helpers = 0;
-        } else {
-            a.n_helpers = 200;  // (seated helpers cost the searches nothing: measured on C4 96 -> 76.9 steps/s, 160-250 -> 77.7)
-            if (T.helpers_oversub >= 0) a.n_helpers = std::min(T.helpers_oversub, 3 * n_cu);
-            if (T.helpers >= 0) a.n_helpers = std::min(a.n_helpers, T.helpers);
-        }
-    }
-    // ... and where do they sit?  Behind the searches they get the CUs the searches leave.  In a launch of more searches than CUs whose
-    // searches wait for one another, finished searches hold their CUs until their predecessors are through, and the helpers behind them
-    // start when the step is half over (C4: a helper lived 5-6 of the step's 11 ms, and the step's 10^5-node search ran most of its
-    // rounds with fewer than eight seats).  Half the CUs' worth of helpers in front of the searches: C4 82.8 -> 90.2 steps/s (32: 84.2,
-    // 64: 86.5, 128: 90.2, 160: 88.0, 200: 54.6).  A launch of independent searches keeps every CU for them.
-    // (handles that share a device — the logical ranks of a group — launch side by side: the idle CUs are the device's, not the
-    // launch's, and helper workgroups in FRONT of every launch's searches would fill the chip before any search starts)
-    if (device_share > 1) a.n_helpers = a.n_helpers / device_share >= 2 ? a.n_helpers / device_share : 0;
-    a.bk_helpers_first = 0;
-    if (count > n_cu && a.n_helpers > 0 && device_share == 1) {
-        int want = T.helpers_first;
-        if (want < 0 && count > 2 * n_cu) want = 0;  // (five searches per CU, C5: the searches need every CU — 128 in front 331 steps/s, 32: 515, none: 560)
-        if (want < 0) {
-            int chained = 0;
-            for (int i = 0; i < count; ++i) chained += slots[i].n_pred > 0 ? 1 : 0;
-            want = 2 * chained >= count ? n_cu / 2 : 0;
-        }
-        a.bk_helpers_first = std::max(0, std::min(want, a.n_helpers));
-    }
-    // rounds are shared from 64 nodes on where helpers are plenty (C2: a dozen per search), from a few hundred on where there are
-    // about as many helpers as searches or fewer (measured C3, 128 + 128: 64 -> 1 026 steps/s, 128-192 -> 1 070, 384 -> 986; C4, 512 + 96:
-    // 64 -> 65.5, 192 -> 67, 512 -> 69; C5, 1 280 + 200 behind the searches, whose helpers only meet the medium searches of the tail: 32-128 -> 560)
-    a.bk_share_min = T.share_min > 0 ? T.share_min : (a.n_helpers >= 4 * count ? 64 : (count <= n_cu ? 128 : (count <= 2 * n_cu ? 512 : 64)));
-    // (sixteen wavefronts: C3 — 128 searches + 128 helpers — 1 135 steps/s with young rounds of 24 nodes and sharing from 160 on, 1 175 with 32
-    // and 128; 28: 1 154, 36: 1 137.  C2 / C4 / C5 with 32: -0.6 % / -1 % / +0.6 %: they stay at 24)
-    if (T.round0 < 0 && helped && ((count <= n_cu && a.n_helpers < 4 * count) || count > 2 * n_cu)) {  // (C5, 1 280 searches: 558 -> 565)
-        a.bk_round0 = 32;
-        a.bk_round = std::max(a.bk_round, a.bk_round0);
-    }
+// what planning reads of the handle and of a packed bank (launch_plan.hpp: LaunchDims)
+LaunchDims launch_dims(const pdmpc_handle* h, const PackedStep& B) {
+    return {h->cfg.checker, h->cfg.Hp, h->n_trims, h->n_words, h->n_man, h->mask_bytes, h->mi_bytes, h->n_cu, h->device_share, h->arena.max_nodes,
+            B.sampled, B.soup_cap, B.ll_cap, B.cand_cap};
 }
 
-// what a launch reads besides the batch and its layout: the handle's buffers, the tuning's switches, the launch's number
-void set_launch_args(pdmpc_handle* h, const PackedStep& B, const LaunchLayout& lay, int first, int count, bool safe, KernelArgs& a) {
-    const Tuning& T = h->tune;
-    set_batch_args(h, B, lay.areas_in_lds, a);
+// what a launch reads besides the batch: its plan (set_plan_args), the handle's buffers, the launch's number
+void set_launch_args(pdmpc_handle* h, const PackedStep& B, const LaunchPlan& plan, int first, int count, KernelArgs& a) {
+    set_batch_args(h, B, plan.areas_in_lds, a);
+    set_plan_args(h->tune, plan, a);
     a.checker = h->cfg.checker;
     a.pred = B.dev.pred;
     a.done_flag = h->d_flag.p;
     a.epoch = h->epoch;
     a.first = first;
     a.arena = h->arena.view();
-    a.lds = lay.lds;
-    a.NL = lay.NL;
-    a.NV = lay.NV;
     a.soup_cap = B.soup_cap;
     a.cand_cap = B.cand_cap;
-    a.n_waves = lay.n_waves;
     a.tie_count = h->d_tie_count.p;
-    a.spin_limit = safe ? (1u << 22) : T.spin_limit;
-    a.debug_tail = T.debug_tail;
-    if (T.debug_progress && !h->progress) {
+    if (h->tune.debug_progress && !h->progress) {
         if (hipHostMalloc((void**)&h->progress, (size_t)h->max_vehicles * 64 * 4, hipHostMallocMapped) != hipSuccess) h->progress = nullptr;
         if (h->progress) std::memset(h->progress, 0, (size_t)h->max_vehicles * 64 * 4);
     }
     a.progress = h->progress;
-    a.speculate = T.speculate;
-    a.reverse_dispatch = (!safe && T.reverse_dispatch) ? 1 : 0;
-    a.bk_mid_min = T.mid_min;
-    a.bk_mid_fill = T.mid_fill;
-    a.bk_tentative = T.tentative;
-    a.bk_fast_arrival = T.fast_arrival;
-    a.bk_seat_nodes = std::max(1, T.seat_nodes);
-    a.bk_force_tie = T.force_tie;
     a.bk_post = h->d_bk_post.p;
     a.help_board = h->d_help_board.p;
     a.help_verdict = h->d_help_verdict.p;
@@ -419,66 +108,36 @@ int prepare_boards(pdmpc_handle* h, int count, uint32_t& fin_base) {
     return PDMPC_OK;
 }
 
-// Which of the four search kernels a layout runs (g_lds_high_water), and which of its two instantiations: the product one exactly
-// when the launch's switches are the ones it has compiled in (pdmpc_device.h: ProductSwitches) -- not with a debug or test switch of
-// PDMPC_TUNING set, or maneuver areas that are not where that kernel expects them (a small soup grown until they move to L2) --, and never with generic=1.
-int bulk_variant(const pdmpc_handle* h, const LaunchLayout& lay) {
-    return lay.compact ? PDMPC_BULK_COMPACT : (h->cfg.checker == PDMPC_CHECK_SAT ? PDMPC_BULK_SAT : (h->n_words != 1 ? PDMPC_BULK_WIDE : PDMPC_BULK));
-}
-bool bulk_generic(const pdmpc_handle* h, const KernelArgs& a, const LaunchLayout& lay) { return h->tune.generic != 0 || !ProductSwitches::matches(a, bulk_variant(h, lay)); }
-
-// PDMPC_TUNING=debug_lds=1: the layout of a search launch and the kernel instantiation that runs it, one line on stderr
-void print_bulk_layout(const pdmpc_handle* h, const KernelArgs& a, const LaunchLayout& lay) {
-    const uint32_t near = (lay.compact ? PDMPC_LK_COMPACT_BK_PER : PDMPC_BK_PER) * (uint32_t)lay.n_waves * PDMPC_WAVE;
-    const char* kernel = kBulkKernelNames[bulk_variant(h, lay)][bulk_generic(h, a, lay) ? 1 : 0];
-    if (lay.compact)
-        fprintf(stderr, "pdmpc LDS layout (compact): launch %d waves %d near %u ready %d nv %d nl %d total %u kernel %s\n", a.n_searches, lay.n_waves, near, lay.ready, lay.NV, lay.NL, lay.lds.total, kernel);
-    else
-        fprintf(stderr, "pdmpc LDS layout: launch %d waves %d areas %d near %u ready %d nv %d nl %d total %u kernel %s\n", a.n_searches, lay.n_waves, lay.areas_in_lds, near, lay.ready, lay.NV, lay.NL,
-                lay.lds.total, kernel);
-}
-
-// The kernel launches of one launch_range; returns the hipError_t of the first that failed.
+// The kernel launches of one launch_range, plan.slice searches each; returns the hipError_t of the first that failed.
 // Oversubscribed launches (more searches than CUs).  A resident search spins for predecessors of the same launch; slots are in
 // level order (the packer sees to it: coupling_order.hpp), so as long as the hardware hands out workgroups in index order every
 // predecessor was dispatched before its successors and the launch cannot stall.  That order is not a documented guarantee: should a
 // launch ever stall, the watchdog (spin_limit) ends the waiting searches with an error status and plan_packed_growing plans the call
 // again with safe == true, in slices that are resident as a whole (a slice's predecessors are in it or in an earlier slice) -- forward
 // progress then needs no assumption at all.
-int dispatch(const pdmpc_handle* h, const KernelArgs& a, const LaunchLayout& lay, bool search, bool safe) {
-    const int first = a.first, count = a.n_searches;
-    const int variant = bulk_variant(h, lay), generic = bulk_generic(h, a, lay) ? 1 : 0;
-    auto launch_search = [&](const KernelArgs* ka, int cnt) -> int {
-        typedef int (*launcher_t)(const KernelArgs*, int, void*, uint32_t*);
-        static const launcher_t launchers[4][2] = {{pdmpc_launch_bulk, pdmpc_launch_bulk_any},
-                                                   {pdmpc_launch_bulk_wide, pdmpc_launch_bulk_wide_any},
-                                                   {pdmpc_launch_bulk_sat, pdmpc_launch_bulk_sat_any},
-                                                   {pdmpc_launch_bulk_compact, pdmpc_launch_bulk_compact_any}};
-        std::lock_guard<std::mutex> lock(g_lds_mutex);
-        return launchers[variant][generic](ka, cnt, (void*)h->stream, &g_lds_high_water[h->cfg.device & 63][variant][generic]);
-    };
-    // a safe launch goes out in slices of `resident` searches, any other as a whole
-    auto in_slices = [&](int resident, auto&& launch) -> int {
-        int lrc = 0;
-        for (int done = 0; done < count && lrc == 0; done += resident) {
-            KernelArgs part = a;
-            part.first = first + done;
-            part.n_searches = std::min(resident, count - done);
-            lrc = launch(&part, part.n_searches);
+int dispatch(const pdmpc_handle* h, const KernelArgs& a, const LaunchPlan& plan, bool search) {
+    typedef int (*launcher_t)(const KernelArgs*, int, void*, uint32_t*);
+    static const launcher_t launchers[4][2] = {{pdmpc_launch_bulk, pdmpc_launch_bulk_any},
+                                               {pdmpc_launch_bulk_wide, pdmpc_launch_bulk_wide_any},
+                                               {pdmpc_launch_bulk_sat, pdmpc_launch_bulk_sat_any},
+                                               {pdmpc_launch_bulk_compact, pdmpc_launch_bulk_compact_any}};
+    const int variant = plan.variant, generic = plan.generic ? 1 : 0;
+    int lrc = 0;
+    for (int done = 0; done < a.n_searches && lrc == 0; done += plan.slice) {
+        KernelArgs part = a;
+        part.first = a.first + done;
+        part.n_searches = std::min(plan.slice, a.n_searches - done);
+        if (!search) {
+            lrc = pdmpc_launch_sampled(&part, part.n_searches, (void*)h->stream);
+        } else {
+            std::lock_guard<std::mutex> lock(g_lds_mutex);
+            lrc = launchers[variant][generic](&part, part.n_searches, (void*)h->stream, &g_lds_high_water[h->cfg.device & 63][variant][generic]);
         }
-        return lrc;
-    };
-    if (!search) {
-        // (no arenas: the tree is the fixed 288-node tree in LDS.  Resident slices: two workgroups per CU at <= 80 KB, else one)
-        const int resident = lay.lds.total <= kLdsMax / 2 ? 2 * h->n_cu : h->n_cu;
-        return in_slices(safe ? resident : count, [&](const KernelArgs* ka, int cnt) { return pdmpc_launch_sampled(ka, cnt, (void*)h->stream); });
     }
-    if (safe && count > h->n_cu) return in_slices(h->n_cu, launch_search);
-    return launch_search(&a, count);
+    return lrc;
 }
 
-// safe == true: the recovery path after a predecessor time-out (plan_packed_growing): slices that are resident as a whole,
-// no helper workgroups next to an oversubscribed launch, the default spin limit.
+// safe == true: the recovery path after a predecessor time-out (plan_packed_growing; launch_plan.hpp: plan_launch).
 // The bank's kind decides the kernel: the graph search, or the sampled optimizer for a bank packed with seeds.
 int launch_range(pdmpc_handle* h, int first, int count, bool safe) {
     if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
@@ -488,25 +147,29 @@ int launch_range(pdmpc_handle* h, int first, int count, bool safe) {
     if (first < 0 || count < 0 || first + count > B.n_packed) return fail(PDMPC_ERR_INVALID, "launch range outside the packed batch");
     if (!B.perm.empty() && (first != 0 || count != B.n_packed)) return fail(PDMPC_ERR_INVALID, "range launches need a batch packed in level order (predecessors in lower slots)");
     if (count == 0) return PDMPC_OK;
-    LaunchLayout lay;
-    int rc = search ? compute_lds_bulk(h, count, B.soup_cap, B.ll_cap, lay) : compute_lds_sampled(h, B.soup_cap, B.cand_cap, lay);
-    if (rc) return rc;
+    const LaunchDims dims = launch_dims(h, B);
+    int n_chained = 0;
+    if (search && !safe && policy_reads_chained(h->tune, count, dims.n_cu, dims.device_share))
+        for (int i = 0; i < count; ++i) n_chained += B.host.veh[first + i].n_pred > 0 ? 1 : 0;
+    LaunchPlan plan;
+    std::string err;
+    int rc = plan_launch(h->tune, dims, search ? kPlanSearch : kPlanSampled, count, n_chained, safe, plan, err);
+    if (rc) return fail(rc, err);
     KernelArgs a{};
-    set_launch_args(h, B, lay, first, count, safe, a);
-    launch_policy(h->tune, count, h->n_cu, h->device_share, safe, search, lay, B.host.veh + first, a);
-    if (a.n_helpers > 0 && (rc = prepare_boards(h, count, a.help_fin_base))) return rc;
-    if (search && h->tune.debug_lds) print_bulk_layout(h, a, lay);
+    set_launch_args(h, B, plan, first, count, a);
+    if (plan.n_helpers > 0 && (rc = prepare_boards(h, count, a.help_fin_base))) return rc;
+    if (search && h->tune.debug_lds) fputs(format_bulk_layout(plan, count).c_str(), stderr);
     if ((rc = h->timer.begin(h->stream, search ? kLaunchSearch : kLaunchSampled))) return rc;
-    const int lrc = dispatch(h, a, lay, search, safe);
+    const int lrc = dispatch(h, a, plan, search);
     if (lrc != 0) {
         h->boards_dirty = true;  // (the searches that were to count themselves finished never ran: the next launch starts from cleared counters)
         char buf[256];
-        snprintf(buf, sizeof buf, "kernel launch failed: %s (LDS %u B)", hipGetErrorString((hipError_t)lrc), lay.lds.total);
+        snprintf(buf, sizeof buf, "kernel launch failed: %s (LDS %u B)", hipGetErrorString((hipError_t)lrc), plan.lds.total);
         return fail(PDMPC_ERR_HIP, buf);
     }
     if ((rc = h->timer.end(h->stream))) return rc;
-    h->stats.lds_bytes = lay.lds.total;
-    h->stats.lds_nodes = lay.NL;
+    h->stats.lds_bytes = plan.lds.total;
+    h->stats.lds_nodes = plan.NL;
     return PDMPC_OK;
 }
 
@@ -569,6 +232,27 @@ int pdmpc_create(const pdmpc_config* config, pdmpc_handle** out_handle) {
     (void)hipMemsetAsync(h->d_out.p, 0, h->d_out.cap * sizeof(pdmpc_vehicle_out), h->stream);
     (void)hipStreamSynchronize(h->stream);
     *out_handle = h;
+    return PDMPC_OK;
+}
+
+int pdmpc_launch_plan_host(const char* tuning, const pdmpc_launch_query* q, pdmpc_launch_plan* plan) {
+    if (!q || !plan) return fail(PDMPC_ERR_INVALID, "pdmpc_launch_plan_host: null argument");
+    if (q->kind < kPlanSearch || q->kind > kPlanJoint) return fail(PDMPC_ERR_INVALID, "pdmpc_launch_plan_host: unknown kind");
+    Tuning T;
+    std::string err;
+    if (!parse_tuning(tuning, T, err)) return fail(PDMPC_ERR_INVALID, err);
+    LaunchDims d{q->checker, q->Hp, q->n_trims, 0, q->n_man, 0, 0, q->n_cu, q->device_share, (uint32_t)q->max_nodes, q->kind == kPlanSampled, q->soup_cap, q->ll_cap, q->cand_cap};
+    mpa_table_sizes(d);
+    LaunchPlan p;
+    if (const int rc = plan_launch(T, d, (PlanKind)q->kind, q->count, q->n_chained, q->safe != 0, p, err)) return fail(rc, err);
+    const LdsLayout& L = p.lds;
+    const JointLds& J = p.joint;
+    const bool joint = q->kind == kPlanJoint;
+    *plan = {p.n_waves, p.NL, p.NV, p.areas_in_lds, p.ready, p.compact ? 1 : 0, p.bk_ready_cap, p.bk_round0, p.bk_round, p.bk_ramp, p.bk_tile, p.bk_share_min,
+             p.n_helpers, p.bk_helpers_first, p.bk_seat_nodes, p.reverse_dispatch, p.variant, p.generic ? 1 : 0, p.slice, (int32_t)p.heap_lds, p.spin_limit,
+             joint ? J.mask : L.mask, joint ? J.man_index : L.man_index, joint ? J.pose : L.pose, joint ? J.area : L.area, joint ? J.ref : L.ref, joint ? J.shape : L.shape,
+             L.path, joint ? J.soup : L.soup, L.cand, L.vstate, L.expand, L.tree16, L.rand, L.nodes, joint ? J.total : L.total, L.bk_near_key, L.bk_near_id, L.bk_ready,
+             L.bk_hist, L.bk_misc, L.bk_pshape, L.reach_shared, L.bk_reach, L.reach, J.ints, J.succ, J.heap_key, J.heap_id, p.kernel};
     return PDMPC_OK;
 }
 
@@ -747,7 +431,9 @@ int pdmpc_upload_mpa(pdmpc_handle* h, const pdmpc_mpa* mpa) {
     if (!mpa->transition || !mpa->maneuver_index || (mpa->n_maneuvers > 0 && !mpa->maneuvers)) return fail(PDMPC_ERR_INVALID, "null table");
     ON_DEVICE(h->cfg.device);
     const int n = mpa->n_trims, Hp = h->cfg.Hp;
-    const int nw = (n + 63) / 64;
+    LaunchDims sizes{h->cfg.checker, Hp, n};
+    mpa_table_sizes(sizes);
+    const int nw = sizes.n_words;
     std::vector<uint64_t> mask((size_t)Hp * n * nw + 2, 0);
     for (int k = 0; k < Hp; ++k)
         for (int i = 0; i < n; ++i)
@@ -788,8 +474,8 @@ int pdmpc_upload_mpa(pdmpc_handle* h, const pdmpc_mpa* mpa) {
     h->n_trims = n;
     h->n_words = nw;
     h->n_man = T;
-    h->mask_bytes = (size_t)Hp * n * nw * 8;
-    h->mi_bytes = (size_t)n * n * 2;
+    h->mask_bytes = sizes.mask_bytes;
+    h->mi_bytes = sizes.mi_bytes;
     // B_mpa = 8*T*(3 + 6*VMAX) + n*n*Hp/8
     h->mpa_alg_bytes = (int64_t)8 * T * (3 + 6 * PDMPC_VMAX) + (int64_t)n * n * Hp / 8;
     h->has_mpa = true;
@@ -1152,22 +838,24 @@ int grow_after_overflow(pdmpc_handle* h, bool& grown) {
     return rc;
 }
 
-int plan_packed_growing(pdmpc_handle* h, int32_t n, const Sink& sink) {
+// `launch(safe)` enqueues what the call plans.  search: the searches (or sampled plans) of the packed bank, whose records can carry the
+// watchdog's status; else pdmpc_plan_joint's problems, which have no predecessors to wait for, no time-out path and no debug lines.
+extern "C++" template <class Launch>  // (this namespace sits inside the extern "C" block)
+int plan_growing(pdmpc_handle* h, int32_t n, const Sink& sink, bool search, Launch&& launch) {
     bool safe = h->safe_launches;
     for (;;) {
-        const bool dbg = h->tune.debug_host == 1;
+        const bool dbg = search && h->tune.debug_host == 1;
         if (dbg) fprintf(stderr, "pdmpc: launching %d vehicles, arena %u nodes%s\n", n, h->arena.max_nodes, safe ? " (resident slices)" : "");
         ON_DEVICE(h->cfg.device);
-        h->epoch += 1;  // a new step: results of earlier launches no longer satisfy predecessor waits
         const auto t0 = std::chrono::steady_clock::now();
-        int rc = launch_range(h, 0, h->banks[h->bank].n_packed, safe);
+        int rc = launch(safe);
         if (rc) return rc;
         const auto t1 = std::chrono::steady_clock::now();
         rc = sink.fetch(h, n);
         if (rc) return rc;
         h->last_us[1] += std::chrono::duration<double, std::micro>(t1 - t0).count();
         h->last_us[2] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t1).count();
-        if (h->tune.debug_host == 2) {  // (PDMPC_DEBUG_HOST=2: where a call's host time goes, printed by pdmpc_plan_step_literal)
+        if (search && h->tune.debug_host == 2) {  // (PDMPC_DEBUG_HOST=2: where a call's host time goes, printed by pdmpc_plan_step_literal)
             h->dbg_us[1] += std::chrono::duration<double, std::micro>(t1 - t0).count();
             h->dbg_us[2] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t1).count();
             float ms = 0.f;
@@ -1175,6 +863,7 @@ int plan_packed_growing(pdmpc_handle* h, int32_t n, const Sink& sink) {
         }
         bool overflow = false, timed_out = false;
         sink.verdict(h, n, overflow, timed_out);
+        timed_out = timed_out && search;
         if (dbg) fprintf(stderr, "pdmpc: fetched, overflow %d, timed out %d\n", (int)overflow, (int)timed_out);
         if (timed_out && safe)
             return fail(PDMPC_ERR_HIP, "a search gave up waiting for a predecessor although the call was planned in resident slices without helper workgroups (records carry PDMPC_ERR_HIP)");
@@ -1193,7 +882,15 @@ int plan_packed_growing(pdmpc_handle* h, int32_t n, const Sink& sink) {
     }
 }
 
-// The prologue of pdmpc_plan_batch / _step / _step_lean: the pack, timed for pdmpc_last_call_timing.
+// ... of the bank's searches: every attempt is a new step
+int plan_packed_growing(pdmpc_handle* h, int32_t n, const Sink& sink) {
+    return plan_growing(h, n, sink, true, [h](bool safe) {
+        h->epoch += 1;  // a new step: results of earlier launches no longer satisfy predecessor waits
+        return launch_range(h, 0, h->banks[h->bank].n_packed, safe);
+    });
+}
+
+// The prologue of pdmpc_plan_batch / _step / _step_lean / _joint: the pack, timed for pdmpc_last_call_timing.
 int timed_pack(pdmpc_handle* h, int32_t n, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index, const pdmpc_polygon_set* fallback_shapes) {
     const auto t0 = std::chrono::steady_clock::now();
     const int rc = pdmpc_pack_step(h, n, in, pred_offset, pred_index, fallback_shapes);
@@ -1426,54 +1123,40 @@ int pdmpc_plan_joint(pdmpc_handle* h, int32_t n_problems, const int32_t* problem
     const int n = n_problems > 0 ? problem_offset[n_problems] : 0;
     if (n > 0 && (!in || !out)) return fail(PDMPC_ERR_INVALID, "pdmpc_plan_joint: null vehicle or record array");
     ON_DEVICE(h->cfg.device);
-    auto t0 = std::chrono::steady_clock::now();
-    int rc = pdmpc_pack_batch(h, n, in);
-    if (rc) return rc;
-    h->last_us[0] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();  // (pdmpc_last_call_timing, as timed_pack)
-    h->last_us[1] = h->last_us[2] = 0;
-    if (n == 0) return PDMPC_OK;
+    int rc = timed_pack(h, n, in, nullptr, nullptr, nullptr);
+    if (rc || n == 0) return rc;
     PackedStep& B = h->banks[h->bank];
-    const int Hp = h->cfg.Hp;
-    int soup_cap = 0;
+    LaunchDims dims = launch_dims(h, B);
+    dims.soup_cap = 0;
     // every distinct soup and boundary of a problem once: what the kernel's prologue stages (pdmpc_device.h: the rule of both)
     for (int p = 0; p < n_problems; ++p)
-        soup_cap = std::max(soup_cap, pdmpc_joint_soup_columns(B.host.veh + problem_offset[p], problem_offset[p + 1] - problem_offset[p], Hp));
-    JointLds L{};
-    uint32_t heap_lds = 0;
-    int areas_in_lds = 0;
-    if ((rc = layout_joint(h, soup_cap + 2, L, heap_lds, areas_in_lds))) return rc;
+        dims.soup_cap = std::max(dims.soup_cap, pdmpc_joint_soup_columns(B.host.veh + problem_offset[p], problem_offset[p + 1] - problem_offset[p], dims.Hp));
+    dims.soup_cap += 2;
+    LaunchPlan plan;
+    std::string err;
+    if ((rc = plan_launch(h->tune, dims, kPlanJoint, n_problems, 0, false, plan, err))) return fail(rc, err);
     if (h->d_joint_off.ensure((size_t)n_problems + 1)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the problem offsets");
     HIPCHK(hipMemcpyAsync(h->d_joint_off.p, problem_offset, ((size_t)n_problems + 1) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    for (;;) {
+    // (an arena too small for some problem: the call is planned again with arenas twice as large, pdmpc_plan_batch's rule)
+    rc = plan_growing(h, n, Sink::records(out), false, [&](bool) -> int {
         JointArgs a{};
-        set_batch_args(h, B, areas_in_lds, a);
+        set_batch_args(h, B, plan.areas_in_lds, a);
         a.problem_off = h->d_joint_off.p;
         a.nodes = h->arena.nodes.p;
         a.far_key = h->arena.far_key.p;
         a.far_id = h->arena.far_id.p;
-        a.heap_lds = heap_lds;
-        a.lds = L;
-        t0 = std::chrono::steady_clock::now();
-        if ((rc = h->timer.begin(h->stream, kLaunchJoint))) return rc;
+        a.heap_lds = plan.heap_lds;
+        a.lds = plan.joint;
+        if (const int trc = h->timer.begin(h->stream, kLaunchJoint)) return trc;
         const int lrc = pdmpc_launch_joint(&a, n_problems, (void*)h->stream);
         if (lrc != 0) {
             char buf[256];
-            snprintf(buf, sizeof buf, "joint kernel launch failed: %s (LDS %u B)", hipGetErrorString((hipError_t)lrc), L.total);
+            snprintf(buf, sizeof buf, "joint kernel launch failed: %s (LDS %u B)", hipGetErrorString((hipError_t)lrc), plan.joint.total);
             return fail(PDMPC_ERR_HIP, buf);
         }
-        if ((rc = h->timer.end(h->stream))) return rc;
-        const auto t1 = std::chrono::steady_clock::now();
-        if ((rc = pdmpc_fetch_results(h, n, out))) return rc;
-        h->last_us[1] += std::chrono::duration<double, std::micro>(t1 - t0).count();
-        h->last_us[2] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t1).count();
-        bool overflow = false;
-        for (int i = 0; i < n; ++i) overflow = overflow || out[i].status == PDMPC_ARENA_OVERFLOW;
-        if (!overflow) break;
-        // the arena is too small for some problem: plan the call again with arenas twice as large (pdmpc_plan_batch's rule)
-        bool grown = false;
-        if ((rc = grow_after_overflow(h, grown))) return rc;
-        if (!grown) break;
-    }
+        return h->timer.end(h->stream);
+    });
+    if (rc) return rc;
     // counters per problem (every vehicle's record carries its problem's n_popped / n_expanded); the per-plan byte formula and
     // obstacle-column count that pdmpc_fetch_results evaluates are the single-vehicle search's and do not
     // describe a joint search: they are reported as 0
@@ -1487,7 +1170,7 @@ int pdmpc_plan_joint(pdmpc_handle* h, int32_t n_problems, const int32_t* problem
         s.nodes_popped += o.n_popped;
         s.nodes_generated += std::max(o.n_expanded - 1, 0);
     }
-    s.lds_bytes = L.total;
+    s.lds_bytes = plan.joint.total;
     s.lds_nodes = 0;
     return PDMPC_OK;
 }

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/pdmpc.h"
+#include "launch_plan.hpp"  // struct Tuning, the plan of a launch (host only)
 #include "pdmpc_device.h"
 
 extern "C" void pdmpc_set_last_error(const char* msg);  // api.cpp: the string pdmpc_last_error returns
@@ -228,48 +229,6 @@ struct SoupTable {
         slot.push_back(packed_in);
         table[at] = (int32_t)keys.size();
     }
-};
-
-// Tuning knobs and A/B / test switches of the graph search.  The defaults are the measured optima quoted next to their use; every
-// setting leaves the results bit-identical.  ONE environment variable overrides them, read once in pdmpc_create (a launch makes no
-// getenv call):  PDMPC_TUNING="key=value,key=value,..."  with the keys below (include/pdmpc.h documents the variable).
-struct Tuning {
-    int round0 = -1;        // nodes a round of a young search takes (-1: 24; 32 for a launch that leaves CUs idle but has fewer than four helpers per search, C3, and for one of more than two searches per CU, C5)
-    int round = -1;         // the most a round takes (-1: 1000 with helper workgroups, else 256)
-    int ramp = -1;          // a round grows by 1 / ramp of the nodes processed so far (-1: 2 with helper workgroups, else 4)
-    int ready = 2048;       // entries of the ready list with helper workgroups (half of it without): the most a round can take
-    int share_min = -1;     // a round with at least this many nodes is shared with the helper workgroups (-1: by the number of helpers per search, api.cpp: launch_policy)
-    int tile = -1;          // the most nodes of a shared round one seated helper takes (-1: 256; what it stages in LDS: at most 768)
-    int mid_min = 24576;    // far lists longer than this feed near through the mid list (a band of far's smallest keys)
-    int mid_fill = 12288;   // entries a refill of mid aims at
-    int tentative = 1;      // expected areas of predecessors that are still planning (A/B switch)
-    int fast_arrival = 1;   // finished searches check arrivals against their plan's path first and publish early (A/B switch)
-    int helpers = -1;       // helper workgroups of a launch with at most one search per CU (-1: by launch size, 0: none)
-    int helpers_oversub = -1;  // ... of a launch with more searches than CUs (-1: 200)
-    int seat_nodes = 256;   // a search may hold its share of the launch's helpers (helpers / searches) per this many nodes it has processed
-    int helpers_first = -1; // ... of them dispatched in front of the searches (-1: half the CUs when most searches of the launch have predecessors)
-    int speculate = 1;      // 0: every search waits for all its predecessors before it starts
-    int compact = -1;       // 1: the kernel built for two workgroups per CU (8 wavefronts, <= 80 KB of LDS: bulk_kernel_compact.hip) where it applies (InterX, one mask word, the soup fits); 0: never; -1: for launches of more than two searches per CU
-    int waves = -1;         // wavefronts per workgroup (4 .. PDMPC_MAX_WAVES; -1: 16 for the InterX kernels — 12 for a launch of more than two searches per CU —, 12 for the separating-axis kernel)
-    uint32_t spin_limit = 1u << 22;  // the watchdog's limit of polls / rounds (debugging: fail fast)
-    int force_tie = 0;      // testing only: every search ends on the replay through the reference's binary heap (as if it had met equal keys)
-    int reverse_dispatch = 0;  // testing only: workgroup b takes slot n - 1 - b (successors dispatched before their predecessors)
-    int debug_tail = 0;     // round / node / tick counters of every search in the unused rows of its record's path_nodes (tools/fr_step_profile.py)
-    int debug_lds = 0;      // print the LDS layout of every launch
-    int debug_host = 0;     // 1: a line per launch; 2: the host-time breakdown of the literal path
-    int debug_progress = 0; // live counters in host-mapped memory (pdmpc_debug_progress)
-    int generic = 0;        // 1: every search launch runs the generic instantiation of its kernel, which reads all switches from KernelArgs (A/B and tests; pdmpc_device.h: ProductSwitches)
-};
-
-// The LDS layout of one launch_range (api.cpp: compute_lds_bulk for the graph search, compute_lds_sampled for the sampled optimizer):
-// computed per launch and held by it, not by the handle.
-struct LaunchLayout {
-    LdsLayout lds{};
-    int n_waves = 0;       // wavefronts per workgroup
-    int NL = 0, NV = 0;    // node records / validity bytes in LDS
-    int areas_in_lds = 0;  // the automaton's maneuver areas are in LDS (else read from L2)
-    int ready = 0;         // entries of the ready list
-    bool compact = false;  // the compact kernel's (two workgroups per CU)
 };
 
 // The event pairs around the search launches of a handle (launch_range, pdmpc_plan_joint) and their times for pdmpc_get_last_stats:

@@ -63,7 +63,7 @@ struct NodeRec {
 #define NODE_MAN(p) ((int)(((p) >> 15) & 4095u))
 #define NODE_COLS(p) ((int)(((p) >> 27) & 15u))
 
-// byte offsets of the regions of the dynamic LDS allocation (all multiples of 16; api.cpp: layout_bulk / compute_lds_sampled)
+// byte offsets of the regions of the dynamic LDS allocation (all multiples of 16; launch_plan.hpp: layout_bulk / compute_lds_sampled)
 struct LdsLayout {
     uint32_t mask, man_index, pose, area;  // MPA tables
     uint32_t ref;                          // ref_x[16], ref_y[16], dtv[16]
@@ -82,7 +82,7 @@ struct LdsLayout {
     uint32_t bk_hist;                      // uint32[3072]: refill histogram [2048] | goal list [1024], expansion groups [1024], their children's offsets [1024]
     uint32_t bk_misc;                      // 2 KB: path tables of the best goal candidate, scan partials, chunk table, tick counters, the reference's ids along the path | the selection's 256-bin histogram
     uint32_t bk_pshape;                    // double2[Hp][VMAX] + uint32[HP_MAX] + uint64[HP_MAX]: the areas along the path of the record written last and their column counts (what an arrival is checked against first); per step the predecessors whose areas differ from the expected ones
-    uint32_t reach_shared;                 // 1: the boundary has ONE reach list for every step, a superset of each step's own (the layout of last resort, api.cpp: layout_bulk)
+    uint32_t reach_shared;                 // 1: the boundary has ONE reach list for every step, a superset of each step's own (the layout of last resort, launch_plan.hpp: layout_bulk)
     uint32_t bk_reach;                     // the rectangles, counts and root of the reach lists (PDMPC_LK_REACH_*)
     uint32_t reach;                        // uint16[soup columns + (Hp - 1) * boundary columns] at PDMPC_LK_FIXED_END, in front of the MPA tables: per step and soup the segments in
                                            // reach, ascending (a step's vehicle obstacles / HDV sets at the index of that soup's first column, the boundary's list of step k at ll_base + (k - 1) * ll_len)
@@ -266,7 +266,7 @@ struct KernelArgs {
 // of more than 64 trims, the realistic one, has 527 maneuvers: their areas never fit; a wide automaton small enough to keep its areas
 // in LDS would always run pdmpc_bulk_kernel_wide_any).  KernelArgs::progress is read by no search kernel and selects nothing.  A uniform value that is a constant costs the
 // round loop no scalar register.  The GENERIC instantiation (the same names + _any) reads all of them from
-// KernelArgs.  api.cpp: dispatch launches the product instantiation exactly when matches() holds.
+// KernelArgs.  launch_plan.hpp: bulk_generic plans the product instantiation exactly when matches() holds.
 enum { PDMPC_BULK = 0, PDMPC_BULK_WIDE = 1, PDMPC_BULK_SAT = 2, PDMPC_BULK_COMPACT = 3 };  // the four search kernels
 struct ProductSwitches {
     static constexpr int32_t debug_tail = 0, bk_force_tie = 0, reverse_dispatch = 0, bk_tentative = 1, bk_fast_arrival = 1, speculate = 1;
@@ -281,7 +281,7 @@ struct ProductSwitches {
 // [problem_off[p], problem_off[p + 1]).  Joint node i of a problem is the N records nodes[(first slot + v) * max_nodes + i], v < N:
 // vehicle v's pose and trim, k, parent, and the node's joint g and h in every one of them.  The open list keeps its first heap_lds
 // entries in LDS and the rest in far_key / far_id of the problem's first slot.
-struct JointLds {  // byte offsets into the dynamic LDS allocation (api.cpp: layout_joint)
+struct JointLds {  // byte offsets into the dynamic LDS allocation (launch_plan.hpp: layout_joint)
     uint32_t mask, man_index, pose, area;  // MPA tables (area: only if areas_in_lds)
     uint32_t ref;                          // double [PDMPC_JOINT_MAX][3][PDMPC_HP_MAX]: ref_x, ref_y, v_ref per vehicle
     uint32_t shape;                        // double2 [PDMPC_JOINT_MAX][2][PDMPC_VMAX]: area, boundary-check area of the node's edge

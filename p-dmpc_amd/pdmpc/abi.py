@@ -146,6 +146,25 @@ class Stats(C.Structure):
     ]
 
 
+class LaunchQuery(C.Structure):
+    """pdmpc_launch_query"""
+
+    _fields_ = [(f, C.c_int32) for f in ("checker", "Hp", "n_trims", "n_man", "n_cu", "device_share", "max_nodes", "kind", "count", "n_chained",
+                                         "soup_cap", "ll_cap", "cand_cap", "safe")]
+
+
+class LaunchPlan(C.Structure):
+    """pdmpc_launch_plan"""
+
+    _fields_ = ([(f, C.c_int32) for f in ("n_waves", "NL", "NV", "areas_in_lds", "ready", "compact", "bk_ready_cap", "bk_round0", "bk_round", "bk_ramp",
+                                          "bk_tile", "bk_share_min", "n_helpers", "bk_helpers_first", "bk_seat_nodes", "reverse_dispatch", "variant",
+                                          "generic", "slice", "heap_lds")]
+                + [(f, C.c_uint32) for f in ("spin_limit", "mask", "man_index", "pose", "area", "ref", "shape", "path", "soup", "cand", "vstate", "expand",
+                                             "tree16", "rand", "nodes", "total", "bk_near_key", "bk_near_id", "bk_ready", "bk_hist", "bk_misc", "bk_pshape",
+                                             "reach_shared", "bk_reach", "reach", "ints", "succ", "heap_key", "heap_id")]
+                + [("kernel", C.c_char_p)])
+
+
 class FcaGroup(C.Structure):
     """pdmpc_fca_group"""
 

@@ -32,6 +32,7 @@ PROTOTYPES = {
     # ---- life cycle
     "pdmpc_create": (INT, [CONFIG, P(OBJ)]),
     "pdmpc_destroy": (INT, [OBJ]),
+    "pdmpc_launch_plan_host": (INT, [STR, P(abi.LaunchQuery), P(abi.LaunchPlan)]),
     "pdmpc_get_config": (INT, [OBJ, CONFIG, P(I32)]),
     "pdmpc_upload_mpa": (INT, [OBJ, MPA]),
     "pdmpc_mpa_reach_host": (INT, [MPA, DP, DP]),

@@ -62,7 +62,7 @@ P = ctypes.POINTER
 OPAQUE = ("pdmpc_handle", "pdmpc_group", "pdmpc_controller", "pdmpc_sweep")
 STRUCTS = {"pdmpc_config": abi.Config, "pdmpc_maneuver": abi.Maneuver, "pdmpc_mpa": abi.Mpa, "pdmpc_polygon_set": abi.PolygonSet,
            "pdmpc_vehicle_in": abi.VehicleIn, "pdmpc_vehicle_out": abi.VehicleOut, "pdmpc_stats": abi.Stats, "pdmpc_choice": abi.ChoiceStruct,
-           "pdmpc_fca_group": abi.FcaGroup, "pdmpc_controller_config": abi.ControllerConfig, "pdmpc_scenario": abi.ScenarioStruct}
+           "pdmpc_launch_query": abi.LaunchQuery, "pdmpc_launch_plan": abi.LaunchPlan, "pdmpc_fca_group": abi.FcaGroup, "pdmpc_controller_config": abi.ControllerConfig, "pdmpc_scenario": abi.ScenarioStruct}
 # the ctypes type of every C spelling the header uses for a return value or an argument
 C_TYPES = {"int": ctypes.c_int, "const char*": ctypes.c_char_p, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
            "double": ctypes.c_double, "void*": ctypes.c_void_p, "const void*": ctypes.c_void_p, "void**": P(ctypes.c_void_p), "size_t*": P(ctypes.c_size_t),

@@ -1,7 +1,7 @@
 """Every compiled variant of the graph search (bulk_search.hpp) under the features that change its code path, at its LDS layout limits
 and at the horizon limits, against the oracle: records byte-identical (and pop sequence and tree where check_batch asks for them).
 
-The search is built four ways and the launch picks a layout at run time (compute_lds_bulk, csrc/api.cpp):
+The search is built four ways and the launch picks a layout at run time (compute_lds_bulk, csrc/launch_plan.hpp):
 
     bulk     InterX, one successor-mask word (bulk_kernel.hip, NW=1)          single_speed automaton (12 trims)
     wide     InterX, more than 64 trims (bulk_kernel_wide.hip, NW=0)          realistic automaton (71 trims, 2 mask words)

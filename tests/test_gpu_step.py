@@ -193,7 +193,7 @@ def test_config_c4_512_vehicles_hp10_colouring_levels():
 @pytest.mark.parametrize("tuning", ["helpers_first=0", "helpers_first=200,seat_nodes=16", "helpers_oversub=40,helpers_first=40,share_min=64"])
 def test_c4_with_the_helper_workgroups_in_other_places(tuning, monkeypatch):
     """A launch of more searches than CUs puts half a chip's worth of helper workgroups in FRONT of the searches when most searches
-    have predecessors (api.cpp: launch_range, helpers_first) — the searches' workgroup indices then start behind them.  The same
+    have predecessors (launch_plan.hpp: launch_policy, helpers_first) — the searches' workgroup indices then start behind them.  The same
     closed loop with none in front, with all of them in front, and with a few that share small rounds: the oracle's records."""
     from pdmpc.road_network import boundary_provider, commonroad_scenario
 
