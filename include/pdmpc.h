@@ -408,10 +408,21 @@ int pdmpc_debug_tree(pdmpc_handle* handle, int32_t vehicle, int32_t capacity, do
 /* The collision primitives on given polygons, n_cases at once (one wavefront each, the device functions the search kernels
  * inline): mode 0 = InterX(a, b) (graph_search/InterX.m:48-103, isReturnPoints = false; b may hold NaN separators),
  * mode 1 = intersect_sat(a, b) (graph_search/intersect_sat.m:1-42), mode 2 = intersect_lanelet_boundary(a, [left, NaN, right, NaN])
- * (optimizer/common/intersect_lanelet_boundary.m:1-56).  Case c: a = columns a_off[c] .. a_off[c+1]-1 of (a_x, a_y), at most
- * PDMPC_VMAX; b likewise, at most 1024 columns.  hit[c] = 1 if the reference function returns true. */
+ * (optimizer/common/intersect_lanelet_boundary.m:1-56), mode 3 = intersect_sat(a, p) for any polygon p of the NaN-separated soup b
+ * (are_constraints_satisfied_sat.m:15-35).  Case c: a = columns a_off[c] .. a_off[c+1]-1 of (a_x, a_y), at most
+ * PDMPC_VMAX; b likewise, at most 1024 columns; PDMPC_ERR_INVALID for more, before any launch.  hit[c] = 1 if the reference function
+ * returns true.  Every mode runs the wave-wide form and the per-lane form of its check; should they disagree, hit[c] = 2 + the per-lane
+ * answer. */
 int pdmpc_debug_edge_check(pdmpc_handle* handle, int32_t mode, int32_t n_cases, const int32_t* a_off, const double* a_x, const double* a_y,
                            const int32_t* b_off, const double* b_x, const double* b_y, int32_t* hit);
+/* The InterX check of one edge on its three soups (are_constraints_satisfied_interx.m:17-37): InterX(A, vehicle soup) || InterX(A, HDV
+ * soup) || InterX(B, lanelet boundary).  Case c: shape A = columns a_off[c] .. a_off[c+1]-1 of (a_x, a_y) and shape B = the same columns
+ * of (b_x, b_y), at most PDMPC_VMAX; its soups 3c, 3c+1, 3c+2 = columns s_off[3c+q] .. s_off[3c+q+1]-1 of (s_x, s_y), at most 1024
+ * columns together; PDMPC_ERR_INVALID for more, before any launch.  hit[c] as for pdmpc_debug_edge_check. */
+int pdmpc_debug_interx_soups(pdmpc_handle* handle, int32_t n_cases, const int32_t* a_off, const double* a_x, const double* a_y, const double* b_x,
+                             const double* b_y, const int32_t* s_off, const double* s_x, const double* s_y, int32_t* hit);
+/* include/pdmpc_math.h's pdmpc_sincos in a kernel: s[i], c[i] = sin, cos of x[i], i < n */
+int pdmpc_debug_sincos(pdmpc_handle* handle, int32_t n, const double* x, double* s, double* c);
 
 /* the arena of vehicle v as the kernel left it (the frontier kernel's own creation order, incl. nodes the reference never
  * creates), with every node's open-list key and validity byte (0 never evaluated, 1 collision-free, 2 colliding) */

@@ -1459,7 +1459,7 @@ int pdmpc_debug_pop_trace(pdmpc_handle* h, int32_t vehicle, int32_t capacity, in
 int pdmpc_debug_edge_check(pdmpc_handle* h, int32_t mode, int32_t n_cases, const int32_t* a_off, const double* a_x, const double* a_y, const int32_t* b_off,
                            const double* b_x, const double* b_y, int32_t* hit) {
     if (!h || n_cases < 0 || (n_cases > 0 && (!a_off || !a_x || !a_y || !b_off || !b_x || !b_y || !hit))) return fail(PDMPC_ERR_INVALID, "null argument");
-    if (mode < 0 || mode > 2) return fail(PDMPC_ERR_INVALID, "mode must be 0 (InterX), 1 (intersect_sat) or 2 (intersect_lanelet_boundary)");
+    if (mode < 0 || mode > 3) return fail(PDMPC_ERR_INVALID, "mode must be 0 (InterX), 1 (intersect_sat), 2 (intersect_lanelet_boundary) or 3 (intersect_sat against a soup)");
     if (n_cases == 0) return PDMPC_OK;
     for (int c = 0; c < n_cases; ++c) {
         const int na = a_off[c + 1] - a_off[c], nb = b_off[c + 1] - b_off[c];
@@ -1487,6 +1487,59 @@ int pdmpc_debug_edge_check(pdmpc_handle* h, int32_t mode, int32_t n_cases, const
     if (lrc != 0) return fail(PDMPC_ERR_HIP, "edge-check launch failed");
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(hit, d_hit.p, (size_t)n_cases * 4, hipMemcpyDeviceToHost));
+    return PDMPC_OK;
+}
+
+int pdmpc_debug_interx_soups(pdmpc_handle* h, int32_t n_cases, const int32_t* a_off, const double* a_x, const double* a_y, const double* b_x, const double* b_y,
+                             const int32_t* s_off, const double* s_x, const double* s_y, int32_t* hit) {
+    if (!h || n_cases < 0 || (n_cases > 0 && (!a_off || !a_x || !a_y || !b_x || !b_y || !s_off || !s_x || !s_y || !hit))) return fail(PDMPC_ERR_INVALID, "null argument");
+    if (n_cases == 0) return PDMPC_OK;
+    for (int c = 0; c < n_cases; ++c) {
+        const int V = a_off[c + 1] - a_off[c];
+        if (V < 0 || V > PDMPC_VMAX) return fail(PDMPC_ERR_INVALID, "shapes: at most PDMPC_VMAX columns");
+        for (int q = 0; q < 3; ++q)
+            if (s_off[3 * c + q + 1] < s_off[3 * c + q]) return fail(PDMPC_ERR_INVALID, "soup offsets must not decrease");
+        if (s_off[3 * c + 3] - s_off[3 * c] > 1024) return fail(PDMPC_ERR_INVALID, "the three soups of a case: at most 1024 columns together");
+    }
+    if (a_off[0] < 0 || s_off[0] < 0) return fail(PDMPC_ERR_INVALID, "negative offset");
+    ON_DEVICE(h->cfg.device);
+    const size_t ta = (size_t)a_off[n_cases], ts = (size_t)s_off[3 * n_cases];
+    DevBuf<int32_t> d_ao, d_so, d_hit;
+    DevBuf<double> d_ax, d_ay, d_bx, d_by, d_sx, d_sy;
+    if (d_ao.ensure_exact((size_t)n_cases + 1) | d_so.ensure_exact((size_t)3 * n_cases + 1) | d_hit.ensure_exact((size_t)n_cases) | d_ax.ensure_exact(ta) | d_ay.ensure_exact(ta) |
+        d_bx.ensure_exact(ta) | d_by.ensure_exact(ta) | d_sx.ensure_exact(ts) | d_sy.ensure_exact(ts))
+        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the edge-check cases");
+    HIPCHK(hipMemcpy(d_ao.p, a_off, ((size_t)n_cases + 1) * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_so.p, s_off, ((size_t)3 * n_cases + 1) * 4, hipMemcpyHostToDevice));
+    if (ta) {
+        HIPCHK(hipMemcpy(d_ax.p, a_x, ta * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_ay.p, a_y, ta * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_bx.p, b_x, ta * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_by.p, b_y, ta * 8, hipMemcpyHostToDevice));
+    }
+    if (ts) {
+        HIPCHK(hipMemcpy(d_sx.p, s_x, ts * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_sy.p, s_y, ts * 8, hipMemcpyHostToDevice));
+    }
+    const int lrc = pdmpc_launch_interx_soups(n_cases, d_ao.p, d_ax.p, d_ay.p, d_bx.p, d_by.p, d_so.p, d_sx.p, d_sy.p, d_hit.p, (void*)h->stream);
+    if (lrc != 0) return fail(PDMPC_ERR_HIP, "edge-check launch failed");
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(hit, d_hit.p, (size_t)n_cases * 4, hipMemcpyDeviceToHost));
+    return PDMPC_OK;
+}
+
+int pdmpc_debug_sincos(pdmpc_handle* h, int32_t n, const double* x, double* s, double* c) {
+    if (!h || n < 0 || (n > 0 && (!x || !s || !c))) return fail(PDMPC_ERR_INVALID, "pdmpc_debug_sincos: bad argument");
+    if (n == 0) return PDMPC_OK;
+    ON_DEVICE(h->cfg.device);
+    DevBuf<double> d_x, d_s, d_c;
+    if (d_x.ensure_exact((size_t)n) | d_s.ensure_exact((size_t)n) | d_c.ensure_exact((size_t)n)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the sin/cos test");
+    HIPCHK(hipMemcpy(d_x.p, x, (size_t)n * 8, hipMemcpyHostToDevice));
+    const int lrc = pdmpc_launch_debug_sincos(d_x.p, n, d_s.p, d_c.p, (void*)h->stream);
+    if (lrc != 0) return fail(PDMPC_ERR_HIP, "sin/cos launch failed");
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(s, d_s.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(c, d_c.p, (size_t)n * 8, hipMemcpyDeviceToHost));
     return PDMPC_OK;
 }
 

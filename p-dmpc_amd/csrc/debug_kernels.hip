@@ -6,6 +6,10 @@
 //   mode 0  InterX(a, b) with isReturnPoints = false            (graph_search/InterX.m:48-103; b may hold NaN separators)
 //   mode 1  intersect_sat(a, b)                                  (graph_search/intersect_sat.m:1-42; b: one polygon or a 2-point segment)
 //   mode 2  intersect_lanelet_boundary(a, [left, NaN, right, NaN]) (optimizer/common/intersect_lanelet_boundary.m:1-56)
+//   mode 3  any(intersect_sat(a, polygon)) over the polygons of the NaN-separated soup b (are_constraints_satisfied_sat.m:15-35):
+//           sat_soup_wave, which finds the polygons by balloting for separators, next to the graph search's form (a lane per polygon start)
+// pdmpc_debug_interx_soups runs interx_check on its whole index space: shape A against a vehicle soup and an HDV soup, shape B against
+// the boundary (are_constraints_satisfied_interx.m:17-37), and pdmpc_debug_sincos runs include/pdmpc_math.h's pdmpc_sincos in a kernel.
 #include <hip/hip_runtime.h>
 
 #include "../../include/pdmpc_math.h"
@@ -51,8 +55,10 @@ extern "C" __global__ __launch_bounds__(PDMPC_WAVE) void pdmpc_edge_check_kernel
         r = interx_check(sh2, na, soup, 0, nb, 0, 0, 0, 0, lane);
     else if (mode == 1)
         r = sat_pair_wave(sh2, na, soup, nb, lane);
-    else
+    else if (mode == 2)
         r = sat_boundary_wave(sh2, na, soup, nb, lane);
+    else
+        r = sat_soup_wave(sh2, na, soup, nb, lane);
     // ... and the per-lane forms of the graph search's check items (bulk_search.hpp, bk_check_items): a lane tests its pair alone
     bool r2 = false;
     {
@@ -65,10 +71,20 @@ extern "C" __global__ __launch_bounds__(PDMPC_WAVE) void pdmpc_edge_check_kernel
                 for (int j = lane; j + 1 < nb; j += PDMPC_WAVE) mine = mine || interx_segment_n<PDMPC_VMAX>(pt, na - 1, soup[j], soup[j + 1]);
         } else if (mode == 1) {
             if (lane == 0) mine = sat_pair_lane(pt, na, soup, nb);
-        } else {
+        } else if (mode == 2) {
             double min_x, max_x, min_y, max_y;
             sat_area_bbox(pt, na, min_x, max_x, min_y, max_y);
             for (int j = lane; j + 1 < nb; j += PDMPC_WAVE) mine = mine || sat_boundary_segment_lane(pt, na, min_x, max_x, min_y, max_y, soup[j], soup[j + 1]);
+        } else {
+            // a polygon begins at a column that is no separator and follows one (or is the first), and ends in front of the next separator
+            for (int j = lane; j < nb; j += PDMPC_WAVE) {
+                const bool start = !is_nan(soup[j].x) && (j == 0 || is_nan(soup[j - 1].x));
+                if (start) {
+                    int e = j + 1;
+                    while (e < nb && !is_nan(soup[e].x)) ++e;
+                    mine = mine || sat_pair_lane(pt, na, soup + j, e - j);
+                }
+            }
         }
         r2 = wave_any(mine);
     }
@@ -83,6 +99,78 @@ extern "C" int pdmpc_launch_edge_check(int mode, int n_cases, const int32_t* a_o
                                        const double* b_y, int32_t* hit, void* stream) {
     if (n_cases <= 0) return 0;
     hipLaunchKernelGGL(pdmpc_edge_check_kernel, dim3(n_cases), dim3(PDMPC_WAVE), 0, (hipStream_t)stream, mode, n_cases, a_off, a_x, a_y, b_off, b_x, b_y, hit);
+    return (int)hipGetLastError();
+}
+
+// interx_check with all three soups: case c's soups 3c (vehicle obstacles), 3c + 1 (HDV sets) and 3c + 2 (lanelet boundary) lie one behind the
+// other in LDS as in the search kernels' l_soup; shape A = columns a_off[c] .. of (a_x, a_y), shape B the same columns of (b_x, b_y).
+extern "C" __global__ __launch_bounds__(PDMPC_WAVE) void pdmpc_interx_soups_kernel(int n_cases, const int32_t* a_off, const double* a_x, const double* a_y, const double* b_x,
+                                                                                  const double* b_y, const int32_t* s_off, const double* s_x, const double* s_y, int32_t* hit) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[(2 * PDMPC_VMAX + DBG_MAX_B + 2) * 16];
+    const int lane = threadIdx.x;
+    const int c = blockIdx.x;
+    if (c >= n_cases) return;
+    LDS_AS unsigned char* lsm = (LDS_AS unsigned char*)smem;
+    lds_d2* sh2 = (lds_d2*)lsm;           // shape A in [0, VMAX), shape B in [VMAX, 2 VMAX)
+    lds_d2* soup = sh2 + 2 * PDMPC_VMAX;  // [vehicle soup, HDV soup, boundary]
+    const int a0 = a_off[c], V = a_off[c + 1] - a0;
+    const int s0 = s_off[3 * c], M_k = s_off[3 * c + 1] - s0, Hk = s_off[3 * c + 2] - s_off[3 * c + 1], Ml = s_off[3 * c + 3] - s_off[3 * c + 2];
+    const int ho = M_k, lo = M_k + Hk, total = lo + Ml;
+    for (int i = lane; i < V; i += PDMPC_WAVE) {
+        d2 p;
+        p.x = a_x[a0 + i];
+        p.y = a_y[a0 + i];
+        sh2[i] = p;
+        p.x = b_x[a0 + i];
+        p.y = b_y[a0 + i];
+        sh2[PDMPC_VMAX + i] = p;
+    }
+    for (int i = lane; i < total; i += PDMPC_WAVE) {
+        d2 p;
+        p.x = s_x[s0 + i];
+        p.y = s_y[s0 + i];
+        soup[i] = p;
+    }
+    wave_sync();
+    const bool r = interx_check(sh2, V, soup, 0, M_k, ho, Hk, lo, Ml, lane);
+    // ... and soup by soup, a lane per segment, with the shape's points in registers (the graph search's check items)
+    bool mine = false;
+    if (V >= 2) {
+        d2 pa[PDMPC_VMAX], pb[PDMPC_VMAX];
+#pragma unroll
+        for (int i = 0; i < PDMPC_VMAX; ++i) {
+            pa[i] = i < V ? (d2)sh2[i] : d2{0.0, 0.0};
+            pb[i] = i < V ? (d2)sh2[PDMPC_VMAX + i] : d2{0.0, 0.0};
+        }
+        for (int j = lane; j + 1 < M_k; j += PDMPC_WAVE) mine = mine || interx_segment_n<PDMPC_VMAX>(pa, V - 1, soup[j], soup[j + 1]);
+        for (int j = lane; j + 1 < Hk; j += PDMPC_WAVE) mine = mine || interx_segment_n<PDMPC_VMAX>(pa, V - 1, soup[ho + j], soup[ho + j + 1]);
+        for (int j = lane; j + 1 < Ml; j += PDMPC_WAVE) mine = mine || interx_segment_n<PDMPC_VMAX>(pb, V - 1, soup[lo + j], soup[lo + j + 1]);
+    }
+    const bool r2 = wave_any(mine);
+    if (lane == 0) hit[c] = r != r2 ? 2 + (r2 ? 1 : 0) : (r ? 1 : 0);
+}
+
+extern "C" int pdmpc_launch_interx_soups(int n_cases, const int32_t* a_off, const double* a_x, const double* a_y, const double* b_x, const double* b_y, const int32_t* s_off,
+                                         const double* s_x, const double* s_y, int32_t* hit, void* stream) {
+    if (n_cases <= 0) return 0;
+    hipLaunchKernelGGL(pdmpc_interx_soups_kernel, dim3(n_cases), dim3(PDMPC_WAVE), 0, (hipStream_t)stream, n_cases, a_off, a_x, a_y, b_x, b_y, s_off, s_x, s_y, hit);
+    return (int)hipGetLastError();
+}
+
+// include/pdmpc_math.h's sin/cos as the search kernels call it: s[i], c[i] = pdmpc_sincos(x[i])
+extern "C" __global__ __launch_bounds__(256) void pdmpc_debug_sincos_kernel(const double* x, int n, double* s, double* c) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (size_t)n; i += (size_t)gridDim.x * blockDim.x) {
+        double sn, cs;
+        pdmpc_sincos(x[i], &sn, &cs);
+        s[i] = sn;
+        c[i] = cs;
+    }
+}
+
+extern "C" int pdmpc_launch_debug_sincos(const double* x, int n, double* s, double* c, void* stream) {
+    if (n <= 0) return 0;
+    const int blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(pdmpc_debug_sincos_kernel, dim3(blocks < 4096 ? blocks : 4096), dim3(256), 0, (hipStream_t)stream, x, n, s, c);
     return (int)hipGetLastError();
 }
 

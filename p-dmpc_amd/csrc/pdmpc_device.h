@@ -560,6 +560,10 @@ int pdmpc_launch_priority_write_grouped(const PriorityGroups* g, int64_t n_tiles
 int pdmpc_launch_priority_order_grouped(const PriorityGroups* g, const uint32_t* masks, int64_t count, int32_t* priorities, void* stream);
 int pdmpc_launch_edge_check(int mode, int n_cases, const int32_t* a_off, const double* a_x, const double* a_y, const int32_t* b_off, const double* b_x,
                             const double* b_y, int32_t* hit, void* stream);
+// debug_kernels.hip: interx_check on three soups per case (s_off[3 * n_cases + 1]), shape B in (b_x, b_y) at shape A's offsets; pdmpc_sincos on n arguments
+int pdmpc_launch_interx_soups(int n_cases, const int32_t* a_off, const double* a_x, const double* a_y, const double* b_x, const double* b_y, const int32_t* s_off,
+                              const double* s_x, const double* s_y, int32_t* hit, void* stream);
+int pdmpc_launch_debug_sincos(const double* x, int n, double* s, double* c, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -459,6 +459,16 @@ def _check(L, rc, what, last_error="pdmpc_last_error"):
         raise err
 
 
+def _flat_columns(lst):
+    """A list of (2, n_i) arrays -> (offsets[len + 1], x, y) of their columns one behind the other (one spare element, so no array is empty)."""
+    off = np.zeros(len(lst) + 1, dtype=np.int32)
+    for i, p in enumerate(lst):
+        off[i + 1] = off[i] + np.asarray(p).reshape(2, -1).shape[1]
+    x = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.float64).reshape(2, -1)[0] for p in lst] + [np.zeros(1)]))
+    y = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.float64).reshape(2, -1)[1] for p in lst] + [np.zeros(1)]))
+    return off, x, y
+
+
 def _step_args(Hp, iters, predecessors, fallback_shapes):
     """The arguments of a step call after the vehicle count -> (vehicle array, pred_offset, pred_index, fallback sets, keep-alive)."""
     n = len(iters)
@@ -949,21 +959,41 @@ class Handle:
 
     def edge_check(self, mode, a_list, b_list):
         """Run a collision primitive on the device for len(a_list) cases: mode 0 InterX, 1 intersect_sat, 2 intersect_lanelet_boundary
-        (b = [left, NaN, right, NaN]).  a_list / b_list: lists of (2, n) arrays.  Returns a bool array."""
+        (b = [left, NaN, right, NaN]), 3 intersect_sat against every polygon of a NaN-separated soup.  a_list / b_list: lists of (2, n)
+        arrays.  Returns a bool array."""
+        return self.edge_check_raw(mode, a_list, b_list) != 0
+
+    def edge_check_raw(self, mode, a_list, b_list):
+        """edge_check with the call's own codes: 0 / 1, or
+        2 + the per-lane answer where the wave-wide and the per-lane form of a check disagree.  Returns an int32 array."""
         n = len(a_list)
-        def flat(lst):
-            off = np.zeros(n + 1, dtype=np.int32)
-            for i, p in enumerate(lst):
-                off[i + 1] = off[i] + np.asarray(p).shape[1]
-            x = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.float64)[0] for p in lst] + [np.zeros(1)]))
-            y = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.float64)[1] for p in lst] + [np.zeros(1)]))
-            return off, x, y
-        ao, ax, ay = flat(a_list)
-        bo, bx, by = flat(b_list)
+        ao, ax, ay = _flat_columns(a_list)
+        bo, bx, by = _flat_columns(b_list)
         hit = np.zeros(max(n, 1), dtype=np.int32)
         rc = self.L.pdmpc_debug_edge_check(self.h, mode, n, abi.i32p(ao), abi.dp(ax), abi.dp(ay), abi.i32p(bo), abi.dp(bx), abi.dp(by), abi.i32p(hit))
         _check(self.L, rc, "pdmpc_debug_edge_check")
-        return hit[:n] != 0
+        return hit[:n].copy()
+
+    def interx_soups(self, a_list, b_list, soups):
+        """The InterX check of an edge on its three soups (pdmpc_debug_interx_soups): a_list / b_list = shapes A and B of every case
+        (equal column counts), soups = one (vehicle soup, HDV soup, boundary) triple of (2, n) arrays per case.  Codes as edge_check_raw."""
+        n = len(a_list)
+        assert len(b_list) == n and len(soups) == n and all(len(t) == 3 for t in soups)
+        assert all(np.asarray(a).shape == np.asarray(b).shape for a, b in zip(a_list, b_list))
+        ao, ax, ay = _flat_columns(a_list)
+        _, bx, by = _flat_columns(b_list)
+        so, sx, sy = _flat_columns([s for t in soups for s in t])
+        hit = np.zeros(max(n, 1), dtype=np.int32)
+        rc = self.L.pdmpc_debug_interx_soups(self.h, n, abi.i32p(ao), abi.dp(ax), abi.dp(ay), abi.dp(bx), abi.dp(by), abi.i32p(so), abi.dp(sx), abi.dp(sy), abi.i32p(hit))
+        _check(self.L, rc, "pdmpc_debug_interx_soups")
+        return hit[:n].copy()
+
+    def debug_sincos(self, x):
+        """include/pdmpc_math.h's pdmpc_sincos on the device (pdmpc_debug_sincos) -> (sin, cos) of every element of x."""
+        x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        s, c = np.zeros_like(x), np.zeros_like(x)
+        _check(self.L, self.L.pdmpc_debug_sincos(self.h, x.size, abi.dp(x), abi.dp(s), abi.dp(c)), "pdmpc_debug_sincos")
+        return s, c
 
     def debug_counters(self):
         out = (C.c_uint64 * 16)()

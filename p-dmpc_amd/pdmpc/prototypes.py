@@ -77,6 +77,8 @@ PROTOTYPES = {
     "pdmpc_debug_pop_trace": (INT, [OBJ, I32, I32, IP, IP]),
     "pdmpc_debug_tree": (INT, [OBJ, I32, I32] + [DP] * 5 + [IP] * 4),
     "pdmpc_debug_edge_check": (INT, [OBJ, I32, I32, IP, DP, DP, IP, DP, DP, IP]),
+    "pdmpc_debug_interx_soups": (INT, [OBJ, I32, IP, DP, DP, DP, DP, IP, DP, DP, IP]),
+    "pdmpc_debug_sincos": (INT, [OBJ, I32, DP, DP, DP]),
     "pdmpc_debug_raw_tree": (INT, [OBJ, I32, I32] + [DP] * 5 + [IP] * 3 + [DP, BP, IP]),
     "pdmpc_debug_counters": (INT, [OBJ, P(C.c_uint64)]),
     "pdmpc_debug_packed_offsets": (INT, [OBJ, I32, IP, IP, IP]),

@@ -437,3 +437,211 @@ def check_area(errors, family, twin, got, ref, A, B, lattice=False, what=None):
     if lattice:
         assert err <= 1e-12, (family, twin, what, float(got), float(ref), float(err))
     return tol
+
+
+# ---- the search's edge checks (csrc/edge_checks.hpp: InterX, intersect_sat, intersect_lanelet_boundary) from the definitions.
+# Operands are (2, n) arrays of doubles as the checks take them (a soup may hold NaN columns).  Doubles are dyadic rationals: all of a case's
+# coordinates are put on one integer grid (a power of two times each), and everything below is Python-integer arithmetic, which is exact.
+
+EPS = float(np.finfo(np.float64).eps)
+
+
+def _grid(*arrays):
+    """(2, n) arrays -> lists of integer points on a common grid (None for a column with a NaN), the same order"""
+    den = 1
+    for a in arrays:
+        for v in np.asarray(a, dtype=np.float64).ravel().tolist():
+            if v == v:
+                den = max(den, v.as_integer_ratio()[1])
+    out = []
+    for a in arrays:
+        a = np.asarray(a, dtype=np.float64).reshape(2, -1)
+        pts = []
+        for x, y in zip(a[0].tolist(), a[1].tolist()):
+            if x != x or y != y:
+                pts.append(None)
+            else:
+                nx, dx = x.as_integer_ratio()
+                ny, dy = y.as_integer_ratio()
+                pts.append((nx * (den // dx), ny * (den // dy)))
+        out.append(pts)
+    return den, out
+
+
+def largest_coordinate(*arrays):
+    """R: the largest |coordinate| of the operands, NaN left out"""
+    return max([float(np.nanmax(np.abs(a))) for a in arrays if np.size(a) and not np.all(np.isnan(a))] + [0.0])
+
+
+def interx_slack(*arrays):
+    """64 · eps · R² on an orientation value dx·(y − y0) − dy·(x − x0): four products and three differences of numbers up to 2R, each
+    rounding at most eps/2 of a magnitude of at most 4R², with a factor of margin"""
+    R = largest_coordinate(*arrays)
+    return 64 * EPS * R * R
+
+
+def sat_slack(*arrays):
+    """32 · eps · R on the normalised gap of two projections: sum of squares, root, quotient, two products, sum and difference bound the
+    error by about 14 · eps · R; the rest is margin"""
+    return 32 * EPS * largest_coordinate(*arrays)
+
+
+def proper_crossing(a, b, c, d):
+    """The segments a -> b and c -> d cross properly: both ends of each lie strictly on opposite sides of the other (InterX.m:63-76 with
+    `< 0`).  Touching, a shared vertex and collinear overlap are no crossing."""
+    return _segments_cross(a, b, c, d)
+
+
+def interx_exact(shape, soup, slack=None):
+    """InterX of the polyline `shape` and the polyline soup `soup` (NaN columns end a polyline) -> (crosses, decided).
+    decided: double arithmetic cannot change the answer.  A (shape edge, soup segment) pair is robust if all four orientation values exceed
+    the slack in magnitude, or if one of the two sign tests has both values beyond the slack with equal sign (no crossing, whatever the other
+    test says); the case is decided if some pair robustly crosses or every pair is robust and none crosses.  slack = 0 (a lattice where
+    every operation is exact in doubles): always decided.  slack None: interx_slack of the operands."""
+    if slack is None:
+        slack = interx_slack(shape, soup)
+    den, (P, Q) = _grid(shape, soup)
+    s = Fraction(slack) * den * den  # the orientation values below are den² times the real ones
+    crosses, all_robust, robust_cross = False, True, False
+    for i in range(len(P) - 1):
+        a, b = P[i], P[i + 1]
+        if a is None or b is None:
+            continue
+        for j in range(len(Q) - 1):
+            c, d = Q[j], Q[j + 1]
+            if c is None or d is None:
+                continue
+            o1, o2, o3, o4 = cross(a, b, c), cross(a, b, d), cross(c, d, a), cross(c, d, b)
+            hit = ((o1 > 0 and o2 < 0) or (o1 < 0 and o2 > 0)) and ((o3 > 0 and o4 < 0) or (o3 < 0 and o4 > 0))
+            crosses = crosses or hit
+            if slack == 0:
+                continue
+            big = [abs(o) > s for o in (o1, o2, o3, o4)]
+            if all(big):
+                robust_cross = robust_cross or hit
+            elif not ((big[0] and big[1] and (o1 > 0) == (o2 > 0)) or (big[2] and big[3] and (o3 > 0) == (o4 > 0))):
+                all_robust = False
+    return crosses, (slack == 0 or robust_cross or (all_robust and not crosses))
+
+
+def _open(pts):
+    """the points of a polygon without a repeated closing vertex"""
+    return pts[:-1] if len(pts) > 1 and pts[0] == pts[-1] else pts
+
+
+def _gap_on_grid(P, Q):
+    """the largest normalised gap over the edge normals of P and Q as (sign, g², |n|²): the gap is sign · sqrt(g² / |n|²); None without a
+    valid axis (fewer than two distinct points in both)"""
+    best = None
+    for poly_ in (P, Q):
+        m = len(poly_)
+        for i in range(m):
+            a, b = poly_[i], poly_[(i + 1) % m]
+            nx, ny = -(b[1] - a[1]), b[0] - a[0]
+            n2 = nx * nx + ny * ny
+            if n2 == 0:
+                continue
+            dp = [nx * p[0] + ny * p[1] for p in P]
+            dq = [nx * p[0] + ny * p[1] for p in Q]
+            g = max(min(dp) - max(dq), min(dq) - max(dp))
+            key = (1 if g > 0 else -1 if g < 0 else 0, g * g, n2)
+            if best is None or _gap_less(best, key):
+                best = key
+    return best
+
+
+def _gap_less(u, v):
+    """sign_u · g_u² / n_u² < sign_v · g_v² / n_v², in integers"""
+    return u[0] * u[1] * v[2] < v[0] * v[1] * u[2]
+
+
+def sat_gap_exact(a, b):
+    """The exact normalised gap of the polygons a and b ((2, n) arrays, closed or open): for every edge normal of both, the gap between the
+    two projections, max(min_a − max_b, min_b − max_a) / |n|; the largest of them.  The polygons are separate iff it is > 0 (touching
+    collides).  -> (sign, squared gap as a Fraction), or None if neither has two distinct points.  A segment is a two-point polygon."""
+    den, (P, Q) = _grid(a, b)
+    best = _gap_on_grid(_open(P), _open(Q))
+    if best is None:
+        return None
+    return best[0], Fraction(best[1], best[2] * den * den)
+
+
+def gap_value(gap, bits=200):
+    """the signed gap of sat_gap_exact as a Fraction good to `bits` bits (the root is the only inexact step)"""
+    sign, sq = gap
+    num, den = sq.numerator << (2 * bits), sq.denominator
+    return sign * Fraction(math.isqrt(num // den), 1 << bits)
+
+
+def sat_exact(a, b, slack=None):
+    """intersect_sat(a, b) -> (collide, decided): collide iff the exact gap is <= 0, decided iff |gap| > slack (sat_slack by default;
+    slack = 0, for operands whose axes and projections are exact in doubles: always decided, touching included)"""
+    if slack is None:
+        slack = sat_slack(a, b)
+    sign, sq = sat_gap_exact(a, b)
+    return sign <= 0, slack == 0 or sq > Fraction(slack) ** 2
+
+
+def sat_soup_exact(a, soup, slack=None):
+    """any(intersect_sat(a, polygon)) over the polygons of a NaN-separated soup (polygons of one point have no axis of their own and are the
+    caller's to leave out) -> (collide, decided): decided if some polygon collides beyond the slack or every polygon is decided"""
+    if slack is None:
+        slack = sat_slack(a, soup)
+    collide, all_decided, robust = False, True, False
+    for q in split_soup(soup):
+        c, d = sat_exact(a, q, slack)
+        collide, all_decided, robust = collide or c, all_decided and d, robust or (c and d)
+    return collide, robust or all_decided
+
+
+def boundary_exact(shape, left, right, slack=None):
+    """intersect_lanelet_boundary(shape, left, right) for a convex shape -> (collide, decided): some boundary segment (two real points in a
+    row) and the shape have a gap <= 0.  The bounding-box filter in front of it changes nothing in exact arithmetic: a segment strictly
+    beyond a side of the box is separate from the shape, and the edge normals of a convex polygon and a segment are a complete set of axes."""
+    if slack is None:
+        slack = sat_slack(shape, left, right)
+    collide, all_decided, robust = False, True, False
+    for side in (left, right):
+        side = np.asarray(side, dtype=np.float64).reshape(2, -1)
+        for j in range(side.shape[1] - 1):
+            seg = side[:, j : j + 2]
+            if np.isnan(seg).any():
+                continue
+            c, d = sat_exact(shape, seg, slack)
+            collide, all_decided, robust = collide or c, all_decided and d, robust or (c and d)
+    return collide, robust or all_decided
+
+
+def split_soup(soup):
+    """the polygons of a NaN-separated soup, in order, empty ones (two separators in a row) left out"""
+    soup = np.asarray(soup, dtype=np.float64).reshape(2, -1)
+    out, start = [], 0
+    nan = np.isnan(soup[0])
+    for j in range(soup.shape[1] + 1):
+        if j == soup.shape[1] or nan[j]:
+            if j > start:
+                out.append(soup[:, start:j])
+            start = j + 1
+    return out
+
+
+def sat_gap_double(a, b):
+    """The same largest gap in double arithmetic, operation by operation as intersect_sat.m:19-34 (Python floats are IEEE doubles and
+    math.sqrt rounds correctly) — to record how far doubles stray from the exact gap, not to decide anything."""
+    a = np.asarray(a, dtype=np.float64).reshape(2, -1)
+    b = np.asarray(b, dtype=np.float64).reshape(2, -1)
+    best = None
+    for p in (a, b):
+        m = p.shape[1]
+        for i in range(m):
+            k = 0 if i + 1 == m else i + 1
+            ax, ay = -(float(p[1, k]) - float(p[1, i])), float(p[0, k]) - float(p[0, i])
+            nrm = math.sqrt(ax * ax + ay * ay)
+            if nrm == 0:
+                continue
+            nx, ny = ax / nrm, ay / nrm
+            da = [nx * x + ny * y for x, y in zip(a[0].tolist(), a[1].tolist())]
+            db = [nx * x + ny * y for x, y in zip(b[0].tolist(), b[1].tolist())]
+            g = max(min(da) - max(db), min(db) - max(da))
+            best = g if best is None or g > best else best
+    return best

@@ -227,4 +227,9 @@ magnitude.  Written by tests/test_exact_reachable_geometry.py (python, host) and
 MI355X), each run with PDMPC_EXACT_GEOMETRY_REPORT=<this file>; a run replaces its own section.
 Bounding families: |area(r) - area(K n L)| of the sets flagged 0; 'r in K' / 'r in L': |area(r n K) - area(r)| and
 |area(r n L) - area(r)| of every set not restored.  On lattices of up to 8 units every family also holds 1e-12 absolute (asserted).
+Sections 'edge checks, ...': the search's collision primitives (InterX, intersect_sat, intersect_lanelet_boundary) against proper
+crossings and the exact normalised gap, written by tests/test_exact_edge_checks.py (the oracle) and tests/test_gpu_edge_check_limits.py
+(the device) in the same way.  Per family: cases, the ones with an exact verdict (judged), the ones double arithmetic could decide either
+way (undecided, by 64 eps R^2 on an orientation value and 32 eps R on a gap) and the decided ones answered wrongly (asserted: 0).
+'double gap' rows: |gap in double arithmetic - exact gap| of the SAT families, in units of eps * R; the bound behind the slack is 14.
 """

@@ -1,7 +1,9 @@
 """The collision primitives on the device, directly: the reference's own known-answer vectors
-(tests/unittests/hlc/intersect_unittest.m:8-54) and 10^4 random polygon / polyline pairs per primitive against the oracle —
-touching, collinear, NaN-separated and zero-length edges included.  Goes through pdmpc_debug_edge_check, which runs the
-device functions the search kernels inline (csrc/edge_checks.hpp), one wavefront per case."""
+(tests/unittests/hlc/intersect_unittest.m:8-54) and 10^4 random polygon / polyline pairs per primitive against the oracle.  The InterX
+pairs include touching, collinear, NaN-separated, zero-length and lattice cases; the SAT pairs are regular polygons of 5 to 7 columns in
+general position and on a lattice.  Touching and zero-length edges under SAT, shapes of 2 to 8 columns, the SAT soup, all three soups of
+InterX, and exact arithmetic as a second reference are in tests/test_gpu_edge_check_limits.py.  Goes through pdmpc_debug_edge_check,
+which runs the device functions the search kernels inline (csrc/edge_checks.hpp), one wavefront per case."""
 import json
 import os
 
@@ -97,9 +99,8 @@ def test_interx_random_pairs(handle, special):
 
 @pytest.mark.parametrize("special", [0, 2, 3, 4])
 def test_interx_large_soups(handle, special):
-    """Soups long enough (more than PDMPC_CULL_MIN segments) for the bounding-box cull in front of InterX pass 1: the cull is
-    exact, so the results equal the oracle's bit for bit, including obstacles that are collinear with a shape edge far away
-    (where rounding noise alone decides InterX.m:63-76)."""
+    """Soups of 300 to 1000 columns, five to sixteen rounds of 64 segments in interx_check: the results equal the oracle's bit for bit,
+    including obstacles that are collinear with a shape edge far away (where rounding noise alone decides InterX.m:63-76)."""
     from oracle import oracle
 
     rng = np.random.default_rng(400 + special)
