@@ -150,5 +150,5 @@ __device__ __forceinline__ LDS_AS BkHist* bk_hist(LDS_AS unsigned char* lsm) { r
 // arithmetic behind an inlined call gave the search kernels another register allocation.
 #define BK_PSHAPE(lsm) ((lds_d2*)((lsm) + PDMPC_LK_PSHAPE))                                /* [Hp][VMAX] the areas (bk_write_record; what an arrival is checked against first, bk_wait_done) */
 #define BK_PCOLS(pshape, Hp) ((lds_u32*)((pshape) + (Hp) * PDMPC_VMAX))                    /* [HP_MAX] their column counts */
-#define BK_PCHG(pshape, Hp) ((lds_u64s*)(BK_PCOLS(pshape, Hp) + PDMPC_HP_MAX))             /* [HP_MAX] per step the predecessors whose areas differ from the expected ones (bk_incorporate_body) */
+#define BK_PCHG(pshape, Hp) ((lds_u64s*)(BK_PCOLS(pshape, Hp) + PDMPC_HP_MAX))             /* [HP_MAX] per step the predecessors whose areas differ from the expected ones (bk_incorporate) */
 #define BK_PVCNT(pshape, Hp) ((lds_u32*)(BK_PCHG(pshape, Hp) + PDMPC_HP_MAX))              /* [HP_MAX] collision-free nodes per step: the lengths of the verification's lists (BK_VLIST) */

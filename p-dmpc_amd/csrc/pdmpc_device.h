@@ -200,6 +200,52 @@ static inline uint32_t pdmpc_lk_fixed(uint32_t W, uint32_t RC, uint32_t P, LdsLa
 #define PDMPC_HB_ASSIGN 8 /* [64] per seat: round << 40 | first entry << 20 | entries: the range that seat checks */
 #define PDMPC_HB_DONE 72  /* [64] per seat: the last round whose range that seat has finished */
 #define PDMPC_HB_WORDS 136
+/* The board's words, declared once: owner (bulk_search.hpp) and helper (bk_helper.hpp) pack and read them through these alone.
+ * ASSIGN = round << 40 | first entry << 20 | entries: 24 + 20 + 20 bits.  first + entries <= PDMPC_HELP_CAP < 2^20.  The round is the owner's
+ * 32-bit help_seq cut to 24 bits; the helper echoes those 24 bits into its DONE word and the owner compares that word with all 32 bits of
+ * help_seq, so the 2^24-th shared round of ONE search would find no seat done and end on the watchdog (a search shares at most one round
+ * per round, and spin_limit ends it long before).  SEATS = launch id << 32 | seats taken: another launch's word counts as no seat.
+ * VERDICT (help_verdict, one 32-bit word per entry) from a check item's flag bits (1 collides, 2 crosses expected areas only): 1
+ * collision-free, 2 collides, 3 expected areas only; 0 is "no verdict" and never written. */
+#define PDMPC_VALUE_FN constexpr __attribute__((always_inline)) inline /* host and device; always inlined, so that a use compiles to what the literal expression did */
+#define PDMPC_HB_ASSIGN_WORD(round, first, count) (((unsigned long long)(round) << 40) | ((unsigned long long)(first) << 20) | (unsigned long long)(count)) /* (a macro at its use in the kernel, like the two below) */
+PDMPC_VALUE_FN unsigned long long pdmpc_hb_assign(uint32_t round, uint32_t first, uint32_t count) { return PDMPC_HB_ASSIGN_WORD(round, first, count); }
+PDMPC_VALUE_FN uint32_t pdmpc_hb_assign_round(unsigned long long w) { return (uint32_t)(w >> 40); }
+PDMPC_VALUE_FN uint32_t pdmpc_hb_assign_first(unsigned long long w) { return (uint32_t)((w >> 20) & 0xfffffull); }
+PDMPC_VALUE_FN uint32_t pdmpc_hb_assign_count(unsigned long long w) { return (uint32_t)(w & 0xfffffull); }
+PDMPC_VALUE_FN unsigned long long pdmpc_hb_seats(uint32_t launch_id, uint32_t taken) { return ((unsigned long long)launch_id << 32) | (unsigned long long)taken; }
+PDMPC_VALUE_FN uint32_t pdmpc_hb_seats_launch(unsigned long long w) { return (uint32_t)(w >> 32); }
+PDMPC_VALUE_FN unsigned long long pdmpc_hb_seats_count(unsigned long long w) { return w & 0xffffffffull; }
+/* (these are macros at their uses in the kernels and functions for everybody else: behind an inlined call the same expression gave
+ * the search kernels other device code at some of its uses) */
+#define PDMPC_HB_SEATS_TAKEN(w, launch_id) ((uint32_t)((w) >> 32) == (launch_id) ? (uint32_t)((w) & 0xffffffffull) : 0u) /* the seats taken if the word is this launch's, else 0 */
+PDMPC_VALUE_FN uint32_t pdmpc_hb_seats_taken(unsigned long long w, uint32_t launch_id) { return PDMPC_HB_SEATS_TAKEN(w, launch_id); }
+PDMPC_VALUE_FN uint32_t pdmpc_hb_verdict(uint32_t flags) { return (flags & 1u) ? 2u : ((flags & 2u) ? 3u : 1u); }
+PDMPC_VALUE_FN bool pdmpc_hb_verdict_missing(uint32_t v) { return v < 1u || v > 3u; }
+PDMPC_VALUE_FN uint32_t pdmpc_hb_verdict_flags(uint32_t v) { return v == 2u ? 1u : (v == 3u ? 2u : 0u); }
+/* bit p = the p-th predecessor: all n_pred of them (a search with more than 64 waits for them all and keeps no such set) */
+#define PDMPC_ALL_PREDECESSORS(n_pred) ((n_pred) >= 64 ? ~0ull : ((1ull << (n_pred)) - 1ull))
+PDMPC_VALUE_FN unsigned long long pdmpc_all_predecessors(int n_pred) { return PDMPC_ALL_PREDECESSORS(n_pred); }
+PDMPC_VALUE_FN bool pdmpc_hb_assign_round_trips(uint32_t round, uint32_t first, uint32_t count) {
+    return pdmpc_hb_assign_round(pdmpc_hb_assign(round, first, count)) == round && pdmpc_hb_assign_first(pdmpc_hb_assign(round, first, count)) == first &&
+           pdmpc_hb_assign_count(pdmpc_hb_assign(round, first, count)) == count;
+}
+static_assert(PDMPC_HELP_CAP < (1 << 20), "a first entry and an entry count each fit their 20 bits of the assignment word");
+static_assert(pdmpc_hb_assign_round_trips(0u, 0u, 0u) && pdmpc_hb_assign_round_trips(1u, 1u, 1u) && pdmpc_hb_assign_round_trips(1u, PDMPC_HELP_CAP, PDMPC_HELP_CAP) &&
+                  pdmpc_hb_assign_round_trips((1u << 24) - 1u, (1u << 20) - 1u, (1u << 20) - 1u) && pdmpc_hb_assign_round_trips((1u << 24) - 1u, 0u, 0u) &&
+                  pdmpc_hb_assign_round_trips(0u, (1u << 20) - 1u, 0u) && pdmpc_hb_assign_round_trips(0u, 0u, (1u << 20) - 1u),
+              "the fields of the assignment word do not overlap");
+static_assert(pdmpc_hb_assign_round(pdmpc_hb_assign(1u << 24, 0u, 0u)) == 0u, "the round is cut to 24 bits");
+static_assert(pdmpc_hb_seats_taken(pdmpc_hb_seats(7u, 0u), 7u) == 0u && pdmpc_hb_seats_taken(pdmpc_hb_seats(7u, 0u) + 3ull, 7u) == 3u && pdmpc_hb_seats_taken(pdmpc_hb_seats(7u, 5u), 8u) == 0u &&
+                  pdmpc_hb_seats_taken(pdmpc_hb_seats(0xffffffffu, PDMPC_HB_SEATS_MAX), 0xffffffffu) == PDMPC_HB_SEATS_MAX,
+              "a seat is counted for its own launch only");
+static_assert(pdmpc_hb_verdict(0u) == 1u && pdmpc_hb_verdict(1u) == 2u && pdmpc_hb_verdict(2u) == 3u && pdmpc_hb_verdict(3u) == 2u, "a crossing of a real area decides");
+static_assert(pdmpc_hb_verdict_flags(1u) == 0u && pdmpc_hb_verdict_flags(2u) == 1u && pdmpc_hb_verdict_flags(3u) == 2u && pdmpc_hb_verdict_missing(0u) && pdmpc_hb_verdict_missing(4u) &&
+                  !pdmpc_hb_verdict_missing(1u) && !pdmpc_hb_verdict_missing(3u),
+              "the owner reads a verdict back as the flag bits P2 expects");
+static_assert(pdmpc_all_predecessors(0) == 0ull && pdmpc_all_predecessors(1) == 1ull && pdmpc_all_predecessors(63) == 0x7fffffffffffffffull && pdmpc_all_predecessors(64) == ~0ull &&
+                  pdmpc_all_predecessors(65) == ~0ull,
+              "one bit per predecessor, all 64 from 64 on");
 
 struct KernelArgs {
     // MPA

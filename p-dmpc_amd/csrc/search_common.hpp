@@ -1,8 +1,8 @@
-// search_common.hpp — what the graph search's workgroups share besides the search itself (device code, included by
-// bulk_search.hpp): the validity bytes, the LDS layout (lds_layout.hpp: shared words, small tables), the copy of a predecessor's solved areas
-// into the obstacle soup, the search context, and the prologue — LDS carve, MPA tables, vehicle record, obstacle soups
-// ([literal polygons + NaN][predecessors' areas padded to VMAX] per step, vectorize_all_obstacles.m:36-62), result record defaults,
-// predecessors that have finished already (PrioritizedController.m:476-491).
+// search_common.hpp — what the owner of a graph search has besides the search itself (device code, included by bulk_search.hpp): the
+// validity bytes, the LDS layout (lds_layout.hpp: shared words, small tables), the copy of a predecessor's solved areas into the obstacle
+// soup, what it shares with its helper workgroups (bk_shared.hpp, included below), the search context, and the owner's prologue — LDS
+// carve, MPA tables, vehicle record, obstacle soups (bk_shared.hpp: BK_STAGE_SOUPS), result record defaults, predecessors that have
+// finished already (PrioritizedController.m:476-491).
 #pragma once
 #include "../../include/pdmpc_math.h"
 #include "pdmpc_device.h"
@@ -79,6 +79,8 @@ __device__ __forceinline__ void incorporate_areas(const SpecCtx& P, unsigned lon
 
 }  // namespace
 
+#include "bk_shared.hpp"
+
 // Everything the search loops need from the prologue (LDS carve, per-vehicle state) and what they hand to the epilogue.
 struct Ctx {
     int tid, lane, wave, slot, Hp, n, nw;
@@ -137,8 +139,9 @@ struct SwitchesProduct {
     __device__ __forceinline__ static constexpr int areas_in_lds(const KernelArgs&) { return ProductSwitches::areas_in_lds(KERNEL); }
 };
 
-// Prologue shared by the kernels: carves the LDS allocation (offsets from KernelArgs::lds), stages the MPA tables, the vehicle
-// record and its obstacle soups, initialises the result record and the predecessor bookkeeping, and fills the context X.
+// The prologue of a search's owner (bulk_body; the sampled and the joint kernel have their own): carves the LDS allocation (offsets from
+// KernelArgs::lds), stages the MPA tables, the vehicle record and its obstacle soups, initialises the result record and the predecessor
+// bookkeeping, and fills the context X.
 template <class SW>
 __device__ __forceinline__ void search_prologue(const KernelArgs& A, Ctx& X, LDS_AS unsigned char* lsm) {
     const int tid = threadIdx.x;
@@ -243,30 +246,12 @@ __device__ __forceinline__ void search_prologue(const KernelArgs& A, Ctx& X, LDS
     }
     __syncthreads();
 
-    // ---- prologue 3: obstacle soup of every step: [literal polygons + NaN][predecessor areas padded to VMAX]
+    // ---- prologue 3: the obstacle soups, in the layout the helpers mirror (bk_shared.hpp)
     const int n_pred = V->n_pred;
     const int pred_cols = n_pred * PDMPC_VMAX;
     {
         int off = 0;
-        for (int k = 0; k < Hp; ++k) {
-            const int a = V->lit_off[k], b = V->lit_off[k + 1];
-            if (tid == 0) {
-                l_soff[k] = off;
-                l_lit[k] = b - a;
-            }
-            stage16(l_soup + off, (const d2*)A.points + a, b - a, tid);
-            off += (b - a) + pred_cols;
-        }
-        if (tid == 0) l_soff[Hp] = off;
-        for (int k = 0; k < Hp; ++k) {
-            const int a = V->hdv_off[k], b = V->hdv_off[k + 1];
-            if (tid == 0) l_hoff[k] = off;
-            stage16(l_soup + off, (const d2*)A.points + a, b - a, tid);
-            off += (b - a);
-        }
-        if (tid == 0) l_hoff[Hp] = off;
-        // lanelet soup last
-        stage16(l_soup + off, (const d2*)A.points + V->ll_off, V->ll_len, tid);
+        BK_STAGE_SOUPS(A, V, l_soup, l_soff, l_hoff, l_lit, Hp, pred_cols, tid, off)
         if (tid == 0) l_path[PDMPC_HP_MAX + 1] = (uint32_t)off;
     }
     __syncthreads();
@@ -289,11 +274,7 @@ __device__ __forceinline__ void search_prologue(const KernelArgs& A, Ctx& X, LDS
     bool dep_timeout = false;
     const bool speculate = SW::speculate(A) && n_pred <= 64;
     if (n_pred > 0) {
-        const d2 nanpt = d2{__longlong_as_double(0x7ff8000000000000LL), __longlong_as_double(0x7ff8000000000000LL)};
-        for (int idx = tid; idx < Hp * pred_cols; idx += (int)blockDim.x) {
-            const int k = idx / pred_cols;
-            l_soup[l_soff[k] + l_lit[k] + (idx - k * pred_cols)] = nanpt;
-        }
+        BK_CLEAR_PRED_SLOTS(l_soup, l_soff, l_lit, Hp, pred_cols, tid, (int)blockDim.x)
         if (!speculate) {
             // blocking wait (more than 64 predecessors, or speculation switched off)
             for (int p = 0; p < n_pred; ++p) {
@@ -312,9 +293,9 @@ __device__ __forceinline__ void search_prologue(const KernelArgs& A, Ctx& X, LDS
             bool d = false;
             if (lane < n_pred) d = __hip_atomic_load(A.done_flag + P.pred[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == A.epoch;
             ready = __ballot(d);
-            if (!speculate) ready = (n_pred >= 64) ? ~0ull : ((1ull << n_pred) - 1ull);
+            if (!speculate) ready = PDMPC_ALL_PREDECESSORS(n_pred);
             if (lane == 0) {
-                const unsigned long long all = (n_pred >= 64) ? ~0ull : ((1ull << n_pred) - 1ull);
+                const unsigned long long all = PDMPC_ALL_PREDECESSORS(n_pred);
                 const unsigned long long pend = speculate ? (all & ~ready) : 0ull;
                 l_shared[SH_PEND_LO] = (uint32_t)pend;
                 l_shared[SH_PEND_HI] = (uint32_t)(pend >> 32);

@@ -223,6 +223,48 @@ def test_step_with_predecessors(variant, monkeypatch, capfd):
     assert_variant(layouts(capfd), variant, mpa)
 
 
+HELPED_STEP_SEED = 13  # problem_set seed at which every variant shares rounds, has helpers check entries AND meets arrivals (see below)
+HELPED_STEP_TUNING = "share_min=64,tile=32,round0=128"  # (TUNINGS[1]: rounds of 128 nodes, shared from 64 entries on, 32 entries per seat)
+
+
+def helped_step(variant, seed):
+    """test_step_with_predecessors' step (12 problems, levels 4 + 8, two repetitions) under HELPED_STEP_TUNING, PDMPC_TUNING already
+    set: the counters summed over the repetitions, and the records of both against the oracle's."""
+    options, mpa, iters = variant_problems(variant, 12, seed=seed)
+    preds = [[] for _ in range(4)] + [sorted({i % 4, (i + 1) % 4}) for i in range(8)]
+    prob = {"iters": iters, "preds": preds, "fallback": [None] * 12, "level_sizes": [4, 8]}
+    ref, _ = _oracle().plan_step(unbounded(options), mpa, prob, n_threads=THREADS)
+    options.max_vehicles = 12
+    options.max_nodes = 1 << 15
+    h = Handle(options)
+    h.upload_mpa(mpa)
+    total = {"safe_replans": 0, "shared_rounds": 0, "helper_checked": 0, "nodes_processed": 0, "speculation_arrivals": 0}
+    for rep in range(2):
+        gpu = h.plan_step(iters, preds, [[] for _ in iters])
+        assert_records_equal(gpu, ref, "helped step %d (%s, seed %d)" % (rep, variant, seed))
+        st = h.stats()
+        for k in total:
+            total[k] += st[k]
+    h.close()
+    return total, mpa
+
+
+@pytest.mark.parametrize("variant", NAMES)
+def test_helpers_mirror_a_search_with_predecessors(variant, monkeypatch, capfd):
+    """Seated helper workgroups AND predecessors on every instantiation: the second level's searches share their rounds, so their
+    helpers mirror a soup with predecessor slots -- NaN slots, expected areas, the areas that arrive (HB_MASK), the lists rebuilt after
+    an arrival -- and their verdicts go into records that must be the oracle's byte for byte.  The owner/helper contract of
+    csrc/bk_shared.hpp is what this holds together."""
+    set_tuning(monkeypatch, variant, HELPED_STEP_TUNING)
+    total, mpa = helped_step(variant, HELPED_STEP_SEED)
+    print("helped step (%s): %s" % (variant, total))
+    assert total["safe_replans"] == 0, total
+    assert total["shared_rounds"] > 0, total
+    assert 0 < total["helper_checked"] < total["nodes_processed"], total
+    assert total["speculation_arrivals"] > 0, total
+    assert_variant(layouts(capfd), variant, mpa, HELPED_STEP_TUNING)
+
+
 @pytest.mark.parametrize("variant", ["bulk", "wide"])
 def test_road_network_closed_loop(variant, monkeypatch, capfd):
     """Ten vehicles on the lab map for five steps, every step against the oracle; arrival verification ran on this instantiation
