@@ -53,7 +53,7 @@ PDMPC_HD static inline int pdmpc_reach_in(double x0, double y0, double x1, doubl
  *
  * The upload of the automaton computes, per trim r and step k, the bounding rectangle (x_lo, x_hi, y_lo, y_hi) — in the frame of a
  * root at the origin with yaw 0 in trim r — of the convex hull of every area the search can place at step k (all three area
- * variants, the transition masks of the steps; csrc/api.cpp: mpa_reach_rects).  A segment is rotated into the root's frame with the
+ * variants, the transition masks of the steps; csrc/mpa_reach.hpp: mpa_reach_rects).  A segment is rotated into the root's frame with the
  * cos and sin of the root's yaw (pdmpc_sincos: the same bits on host and device) and is out of reach if its bounding box THERE lies
  * strictly outside the rectangle, widened by the relative margin above (the hull composes maneuvers in another order than the
  * search accumulates a pose) and by 2^-48 of the end points' distances from the root (the rounding of the rotation itself, which

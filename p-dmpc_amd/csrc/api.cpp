@@ -5,6 +5,9 @@
 // kernel on the handle's stream and time it with HIP events, copy results back.
 // There is no CPU implementation of the search in this library: without a gfx950 device every planning
 // entry point fails with PDMPC_ERR_NO_DEVICE.
+// What needs no device lives in host-only headers that report through (return code, std::string& err) and are failed here: the plan of a launch
+// (launch_plan.hpp), the automaton's reach and the reach lists (mpa_reach.hpp), the checked choice on the host (choice_host.hpp) and the
+// reference's tree read out of a raw arena (reference_tree.hpp).  This file keeps the checks that need the handle, the copies and the launches.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,20 +16,22 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
-#include <limits>
-#include <map>
 #include <mutex>
 #include <string>
-#include <utility>
+#include <type_traits>
 #include <vector>
 
-#include "../../include/pdmpc_geometry.h"
-#include "../../include/pdmpc_reach.h"
+#include "choice_host.hpp"
 #include "handle.hpp"
+#include "mpa_reach.hpp"
+#include "reference_tree.hpp"
 
 namespace {
 
 thread_local std::string g_err;  // pdmpc_last_error: every translation unit reports through pdmpc_set_last_error (fail, handle.hpp)
+
+// what a host-only part returned, its message in err, as this library reports it
+int failed(int rc, const std::string& err) { return rc ? fail(rc, err) : PDMPC_OK; }
 
 // The dynamic LDS size of a kernel is an attribute of the function ON THE DEVICE, not of a handle (hipFuncSetAttribute sets a
 // maximum): the largest size set so far is kept per device, kernel (0 bulk, 1 bulk wide, 2 bulk SAT, 3 bulk compact) and instantiation
@@ -238,22 +243,8 @@ int pdmpc_create(const pdmpc_config* config, pdmpc_handle** out_handle) {
 int pdmpc_launch_plan_host(const char* tuning, const pdmpc_launch_query* q, pdmpc_launch_plan* plan) {
     if (!q || !plan) return fail(PDMPC_ERR_INVALID, "pdmpc_launch_plan_host: null argument");
     if (q->kind < kPlanSearch || q->kind > kPlanJoint) return fail(PDMPC_ERR_INVALID, "pdmpc_launch_plan_host: unknown kind");
-    Tuning T;
     std::string err;
-    if (!parse_tuning(tuning, T, err)) return fail(PDMPC_ERR_INVALID, err);
-    LaunchDims d{q->checker, q->Hp, q->n_trims, 0, q->n_man, 0, 0, q->n_cu, q->device_share, (uint32_t)q->max_nodes, q->kind == kPlanSampled, q->soup_cap, q->ll_cap, q->cand_cap};
-    mpa_table_sizes(d);
-    LaunchPlan p;
-    if (const int rc = plan_launch(T, d, (PlanKind)q->kind, q->count, q->n_chained, q->safe != 0, p, err)) return fail(rc, err);
-    const LdsLayout& L = p.lds;
-    const JointLds& J = p.joint;
-    const bool joint = q->kind == kPlanJoint;
-    *plan = {p.n_waves, p.NL, p.NV, p.areas_in_lds, p.ready, p.compact ? 1 : 0, p.bk_ready_cap, p.bk_round0, p.bk_round, p.bk_ramp, p.bk_tile, p.bk_share_min,
-             p.n_helpers, p.bk_helpers_first, p.bk_seat_nodes, p.reverse_dispatch, p.variant, p.generic ? 1 : 0, p.slice, (int32_t)p.heap_lds, p.spin_limit,
-             joint ? J.mask : L.mask, joint ? J.man_index : L.man_index, joint ? J.pose : L.pose, joint ? J.area : L.area, joint ? J.ref : L.ref, joint ? J.shape : L.shape,
-             L.path, joint ? J.soup : L.soup, L.cand, L.vstate, L.expand, L.tree16, L.rand, L.nodes, joint ? J.total : L.total, L.bk_near_key, L.bk_near_id, L.bk_ready,
-             L.bk_hist, L.bk_misc, L.bk_pshape, L.reach_shared, L.bk_reach, L.reach, J.ints, J.succ, J.heap_key, J.heap_id, p.kernel};
-    return PDMPC_OK;
+    return failed(plan_query(tuning, *q, *plan, err), err);
 }
 
 int pdmpc_destroy(pdmpc_handle* h) {
@@ -261,20 +252,6 @@ int pdmpc_destroy(pdmpc_handle* h) {
     DeviceGuard device_guard__(h->cfg.device);
     delete h;
     return PDMPC_OK;
-}
-
-// The automaton's reach (include/pdmpc_reach.h): the longest maneuver displacement and the largest |area point| over the used columns
-// of the three area variants.
-static void mpa_reach(const pdmpc_mpa* mpa, double& dmax, double& amax) {
-    dmax = 0.0;
-    amax = 0.0;
-    for (int t = 0; t < mpa->n_maneuvers; ++t) {
-        const pdmpc_maneuver& m = mpa->maneuvers[t];
-        dmax = std::max(dmax, hypot(m.dx, m.dy));
-        const double(*src[3])[PDMPC_VMAX] = {m.area, m.area_without_offset, m.area_large_offset};
-        for (int a = 0; a < 3; ++a)
-            for (int v = 0; v < m.n_cols && v < PDMPC_VMAX; ++v) amax = std::max(amax, hypot(src[a][0][v], src[a][1][v]));
-    }
 }
 
 int pdmpc_mpa_reach_host(const pdmpc_mpa* mpa, double* dmax, double* amax) {
@@ -286,116 +263,9 @@ int pdmpc_mpa_reach_host(const pdmpc_mpa* mpa, double* dmax, double* amax) {
 int pdmpc_reach_lists_host(int32_t Hp, double dmax, double amax, double root_x, double root_y, const double* x, const double* y, const int32_t* step_first,
                            const int32_t* step_count, int32_t* list_offset, int32_t* list) {
     if (Hp < 1 || Hp > PDMPC_HP_MAX || !step_first || !step_count || !list_offset) return fail(PDMPC_ERR_INVALID, "pdmpc_reach_lists_host: bad argument");
-    int32_t n = 0;
-    for (int k = 1; k <= Hp; ++k) {
-        const int32_t a = step_first[k - 1], c = step_count[k - 1];
-        if (a < 0 || c < 0 || (c > 1 && (!x || !y || !list))) return fail(PDMPC_ERR_INVALID, "pdmpc_reach_lists_host: bad step ranges");
-        double box[4];
-        pdmpc_reach_box(dmax, amax, k, root_x, root_y, box);
-        list_offset[k - 1] = n;
-        for (int32_t j = 0; j + 1 < c; ++j)
-            if (pdmpc_reach_in(x[a + j], y[a + j], x[a + j + 1], y[a + j + 1], box[0], box[1], box[2], box[3])) list[n++] = j;
-    }
-    list_offset[Hp] = n;
-    return PDMPC_OK;
+    std::string err;
+    return failed(reach_lists(Hp, dmax, amax, root_x, root_y, x, y, step_first, step_count, list_offset, list, err), err);
 }
-
-// The automaton's reach rectangles (include/pdmpc_reach.h, the oriented rule): rects[(r * Hp + K - 1) * 4 ..] = (x_lo, x_hi, y_lo, y_hi), in
-// the frame of a root at the origin with yaw 0 in trim r, of every point of every area (three variants, used columns) of a maneuver
-// of step K that the transition masks of steps 1 .. K allow; NaN where no such maneuver exists.  Paths are not enumerated: convex
-// hulls compose — hull(i, k -> K) = hull of the union over the successors j of i at step k of maneuver(i, j) applied to
-// hull(j, k + 1 -> K), the areas of the maneuvers leaving i at step K being the base case — and the bounding box of the hull is the
-// bounding box of the union.  n * Hp^2 / 2 hulls of a few hundred points.
-namespace {
-typedef std::pair<double, double> ReachPt;
-// convex hull in place (Andrew's monotone chain; collinear points dropped, which moves no bounding box)
-void reach_hull(std::vector<ReachPt>& P, std::vector<ReachPt>& H) {
-    std::sort(P.begin(), P.end());
-    P.erase(std::unique(P.begin(), P.end()), P.end());
-    const size_t n = P.size();
-    if (n < 3) return;
-    auto cross = [](const ReachPt& o, const ReachPt& a, const ReachPt& b) { return (a.first - o.first) * (b.second - o.second) - (a.second - o.second) * (b.first - o.first); };
-    H.clear();
-    for (size_t i = 0; i < n; ++i) {
-        while (H.size() >= 2 && cross(H[H.size() - 2], H.back(), P[i]) <= 0) H.pop_back();
-        H.push_back(P[i]);
-    }
-    const size_t lower = H.size() + 1;
-    for (size_t i = n - 1; i-- > 0;) {
-        while (H.size() >= lower && cross(H[H.size() - 2], H.back(), P[i]) <= 0) H.pop_back();
-        H.push_back(P[i]);
-    }
-    H.pop_back();
-    P.swap(H);
-}
-void mpa_reach_rects(const pdmpc_mpa* mpa, int Hp, double* rects) {
-    const int n = mpa->n_trims, T = mpa->n_maneuvers;
-    const double qnan = std::numeric_limits<double>::quiet_NaN();
-    std::vector<double> cs((size_t)std::max(T, 1)), sn((size_t)std::max(T, 1));
-    for (int t = 0; t < T; ++t) pdmpc_sincos(mpa->maneuvers[t].dyaw, &sn[t], &cs[t]);
-    auto maneuver = [&](int k, int i, int j) {  // of step k (1-based) from trim i to trim j, or -1
-        if (!mpa->transition[((size_t)(k - 1) * n + i) * n + j]) return -1;
-        const int t = mpa->maneuver_index[(size_t)i * n + j];
-        return t >= 0 && t < T ? t : -1;
-    };
-    // (hull(i, k -> K) depends on the masks of steps k .. K alone, and most steps share one mask — the recursive-feasibility mask differs
-    // near the horizon only —: a table per distinct sequence of masks, not per (k, K))
-    std::vector<int> slice((size_t)Hp);
-    for (int k = 0; k < Hp; ++k) {
-        slice[k] = k;
-        for (int q = 0; q < k; ++q)
-            if (!memcmp(mpa->transition + (size_t)q * n * n, mpa->transition + (size_t)k * n * n, (size_t)n * n)) {
-                slice[k] = slice[q];
-                break;
-            }
-    }
-    typedef std::vector<std::vector<ReachPt>> Table;  // one hull per trim
-    std::map<std::vector<int>, size_t> known;
-    std::vector<Table> tables;
-    std::vector<ReachPt> scratch;
-    for (int K = 1; K <= Hp; ++K) {
-        size_t at = 0;
-        for (int k = K; k >= 1; --k) {
-            const std::vector<int> key(slice.begin() + (k - 1), slice.begin() + K);
-            const auto found = known.find(key);
-            if (found != known.end()) {
-                at = found->second;
-                continue;
-            }
-            Table t((size_t)n);
-            for (int i = 0; i < n; ++i) {
-                for (int j = 0; j < n; ++j) {
-                    const int mi = maneuver(k, i, j);
-                    if (mi < 0) continue;
-                    const pdmpc_maneuver& m = mpa->maneuvers[mi];
-                    if (k == K) {
-                        const double(*src[3])[PDMPC_VMAX] = {m.area, m.area_without_offset, m.area_large_offset};
-                        for (int a = 0; a < 3; ++a)
-                            for (int v = 0; v < m.n_cols && v < PDMPC_VMAX; ++v) t[i].push_back(ReachPt(src[a][0][v], src[a][1][v]));
-                    } else {
-                        for (const ReachPt& p : tables[at][j]) t[i].push_back(ReachPt(cs[mi] * p.first - sn[mi] * p.second + m.dx, sn[mi] * p.first + cs[mi] * p.second + m.dy));
-                    }
-                }
-                reach_hull(t[i], scratch);
-            }
-            at = tables.size();
-            tables.push_back(std::move(t));
-            known[key] = at;
-        }
-        const Table& cur = tables[at];
-        for (int i = 0; i < n; ++i) {
-            double* r = rects + ((size_t)i * Hp + (K - 1)) * 4;
-            r[0] = r[1] = r[2] = r[3] = qnan;
-            for (const ReachPt& p : cur[i]) {
-                r[0] = p.first < r[0] || r[0] != r[0] ? p.first : r[0];
-                r[1] = p.first > r[1] || r[1] != r[1] ? p.first : r[1];
-                r[2] = p.second < r[2] || r[2] != r[2] ? p.second : r[2];
-                r[3] = p.second > r[3] || r[3] != r[3] ? p.second : r[3];
-            }
-        }
-    }
-}
-}  // namespace
 
 int pdmpc_mpa_reach_rects_host(const pdmpc_mpa* mpa, int32_t Hp, double* rects) {
     if (!mpa || !rects || !mpa->transition || !mpa->maneuver_index || (mpa->n_maneuvers > 0 && !mpa->maneuvers)) return fail(PDMPC_ERR_INVALID, "pdmpc_mpa_reach_rects_host: null argument");
@@ -408,20 +278,8 @@ int pdmpc_reach_lists_oriented_host(int32_t Hp, int32_t n_trims, const double* r
                                     const int32_t* step_first, const int32_t* step_count, int32_t* list_offset, int32_t* list) {
     if (Hp < 1 || Hp > PDMPC_HP_MAX || !rects || root_trim < 1 || root_trim > n_trims || !step_first || !step_count || !list_offset)
         return fail(PDMPC_ERR_INVALID, "pdmpc_reach_lists_oriented_host: bad argument");
-    double cs, sn;
-    pdmpc_sincos(root_yaw, &sn, &cs);
-    int32_t n = 0;
-    for (int k = 1; k <= Hp; ++k) {
-        const int32_t a = step_first[k - 1], c = step_count[k - 1];
-        if (a < 0 || c < 0 || (c > 1 && (!x || !y || !list))) return fail(PDMPC_ERR_INVALID, "pdmpc_reach_lists_oriented_host: bad step ranges");
-        double box[4];
-        pdmpc_reach_rect_box(rects + ((size_t)(root_trim - 1) * Hp + (k - 1)) * 4, root_x, root_y, box);
-        list_offset[k - 1] = n;
-        for (int32_t j = 0; j + 1 < c; ++j)
-            if (pdmpc_reach_in_oriented(x[a + j], y[a + j], x[a + j + 1], y[a + j + 1], root_x, root_y, cs, sn, box[0], box[1], box[2], box[3])) list[n++] = j;
-    }
-    list_offset[Hp] = n;
-    return PDMPC_OK;
+    std::string err;
+    return failed(reach_lists_oriented(Hp, rects, root_trim, root_x, root_y, root_yaw, x, y, step_first, step_count, list_offset, list, err), err);
 }
 
 int pdmpc_upload_mpa(pdmpc_handle* h, const pdmpc_mpa* mpa) {
@@ -649,55 +507,11 @@ int fetch_lean(pdmpc_handle* h, int32_t n, int32_t* status, double* cost) {
 
 // ---- the choice among the plans of a batch (pdmpc_choice, include/pdmpc.h; choice_kernel.hip)
 
-// what pdmpc_choice promises, checked before anything is launched or summed
-int check_choice(int32_t n, const pdmpc_choice* ch) {
-    if (!ch || n < 0 || ch->n_cells < 0 || ch->n_graphs < 0 || ch->n_picks < 0) return fail(PDMPC_ERR_INVALID, "pdmpc_choice: bad argument");
-    if ((ch->n_cells > 0 && !ch->cell_offset) || (ch->n_graphs > 0 && !ch->graph_offset) || (ch->n_picks > 0 && (!ch->pick_graph || !ch->pick_offset)))
-        return fail(PDMPC_ERR_INVALID, "pdmpc_choice: null list");
-    auto monotone = [](const int32_t* off, int count) {
-        if (off[0] < 0) return false;
-        for (int i = 0; i < count; ++i)
-            if (off[i + 1] < off[i]) return false;
-        return true;
-    };
-    auto slots_within = [n](const int32_t* slot, int first, int end) {
-        if (end > first && !slot) return false;
-        for (int q = first; q < end; ++q)
-            if (slot[q] < 0 || slot[q] >= n) return false;
-        return true;
-    };
-    if (ch->n_cells > 0) {
-        if (!monotone(ch->cell_offset, ch->n_cells)) return fail(PDMPC_ERR_INVALID, "pdmpc_choice: cell offsets are negative or decrease");
-        if (!slots_within(ch->cell_slot, 0, ch->cell_offset[ch->n_cells])) return fail(PDMPC_ERR_INVALID, "pdmpc_choice: a cell lists a slot outside the batch");
-    }
-    if (ch->n_graphs > 0) {
-        if (!monotone(ch->graph_offset, ch->n_graphs)) return fail(PDMPC_ERR_INVALID, "pdmpc_choice: graph offsets are negative or decrease");
-        if (ch->graph_offset[ch->n_graphs] > ch->n_cells) return fail(PDMPC_ERR_INVALID, "pdmpc_choice: a graph's candidates lie outside the cells");
-    }
-    if (ch->n_picks > 0) {
-        if (!monotone(ch->pick_offset, ch->n_picks)) return fail(PDMPC_ERR_INVALID, "pdmpc_choice: pick offsets are negative or decrease");
-        for (int i = 0; i < ch->n_picks; ++i) {
-            const int g = ch->pick_graph[i];
-            if (g < -1 || g >= ch->n_graphs) return fail(PDMPC_ERR_INVALID, "pdmpc_choice: pick_graph outside [-1, n_graphs)");
-            const int want = g < 0 ? 1 : ch->graph_offset[g + 1] - ch->graph_offset[g];
-            if (want < 1 || ch->pick_offset[i + 1] - ch->pick_offset[i] != want)
-                return fail(PDMPC_ERR_INVALID, "pdmpc_choice: a pick lists another number of slots than its graph has candidates");
-        }
-        if (!slots_within(ch->pick_slot, 0, ch->pick_offset[ch->n_picks])) return fail(PDMPC_ERR_INVALID, "pdmpc_choice: a pick lists a slot outside the batch");
-    }
-    return PDMPC_OK;
+// what pdmpc_choice promises (choice_host.hpp: check_choice), checked before anything is launched or summed
+int checked_choice(int32_t n, const pdmpc_choice* ch) {
+    std::string err;
+    return failed(check_choice(n, ch, err), err);
 }
-
-// The block a choice reads back in one copy: the status counters, chosen[n_graphs], cell_cost[n_cells], the picked records.
-struct ChoiceLayout {
-    size_t chosen = 0, cell_cost = 0, picks = 0, bytes = 0;  // (the counters are at 0)
-    explicit ChoiceLayout(const pdmpc_choice& ch) {
-        chosen = PDMPC_CHOICE_COUNTERS * sizeof(int32_t);
-        cell_cost = (chosen + (size_t)ch.n_graphs * sizeof(int32_t) + 7) & ~(size_t)7;
-        picks = cell_cost + (size_t)ch.n_cells * sizeof(double);
-        bytes = picks + (size_t)ch.n_picks * sizeof(pdmpc_vehicle_out);
-    }
-};
 
 // The lists of a checked choice on the n records of the current bank, staged in pinned memory with the caller's slots mapped to the
 // bank's (a batch that pack_common put into its own order) and queued for the device; A: what the kernels take.
@@ -925,34 +739,16 @@ int pdmpc_plan_step_lean(pdmpc_handle* h, int32_t n, const pdmpc_vehicle_in* in,
 
 int pdmpc_choose_host(int32_t n, const int32_t* status, const double* final_cost, const pdmpc_choice* ch, int32_t* chosen, double* cell_cost) {
     if (n > 0 && (!status || !final_cost)) return fail(PDMPC_ERR_INVALID, "null argument");
-    if (const int rc = check_choice(n, ch)) return rc;
+    if (const int rc = checked_choice(n, ch)) return rc;
     for (int i = 0; i < n; ++i)
         if (status[i] != PDMPC_OK && status[i] != PDMPC_EXHAUSTED) return fail(PDMPC_ERR_HIP, "a result record carries an error status: not a planning result");
-    std::vector<double> sums((size_t)ch->n_cells);
-    for (int c = 0; c < ch->n_cells; ++c) {
-        double sum = 0.0;
-        for (int q = ch->cell_offset[c]; q < ch->cell_offset[c + 1]; ++q) {  // (list order: the order of addition)
-            const int s = ch->cell_slot[q];
-            sum += status[s] == PDMPC_OK ? final_cost[s] : std::numeric_limits<double>::infinity();
-        }
-        sums[(size_t)c] = std::nearbyint(sum * 1e8) / 1e8;
-    }
-    if (chosen)
-        for (int g = 0; g < ch->n_graphs; ++g) {
-            const double* cand = sums.data() + ch->graph_offset[g];
-            const int count = ch->graph_offset[g + 1] - ch->graph_offset[g];
-            int best = 0;
-            for (int p = 1; p < count; ++p)
-                if (cand[p] < cand[best]) best = p;  // [~, i] = min(.): the first minimum
-            chosen[g] = best;
-        }
-    if (cell_cost && ch->n_cells > 0) std::memcpy(cell_cost, sums.data(), sums.size() * sizeof(double));
+    choose_host(status, final_cost, ch, chosen, cell_cost);
     return PDMPC_OK;
 }
 
 int pdmpc_choose_resident(pdmpc_handle* h, int32_t n, const pdmpc_choice* ch, int32_t* chosen, double* cell_cost, pdmpc_vehicle_out* picks) {
     if (!h || (ch && ch->n_picks > 0 && !picks)) return fail(PDMPC_ERR_INVALID, "null argument");
-    if (const int rc = check_choice(n, ch)) return rc;
+    if (const int rc = checked_choice(n, ch)) return rc;
     ON_DEVICE(h->cfg.device);
     const ChoiceLayout L(*ch);
     ChoiceArgs A;
@@ -964,7 +760,7 @@ int pdmpc_choose_resident(pdmpc_handle* h, int32_t n, const pdmpc_choice* ch, in
 int pdmpc_plan_step_chosen(pdmpc_handle* h, int32_t n, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index, const pdmpc_polygon_set* fallback_shapes,
                            const pdmpc_choice* ch, int32_t* chosen, double* cell_cost, pdmpc_vehicle_out* picks) {
     if (!h || (ch && ch->n_picks > 0 && !picks)) return fail(PDMPC_ERR_INVALID, "null argument");
-    if (const int rc = check_choice(n, ch)) return rc;
+    if (const int rc = checked_choice(n, ch)) return rc;
     int rc = timed_pack(h, n, in, pred_offset, pred_index, fallback_shapes);
     if (rc) return rc;
     ON_DEVICE(h->cfg.device);
@@ -1263,19 +1059,45 @@ int pdmpc_get_last_stats(pdmpc_handle* h, pdmpc_stats* stats) {
     return PDMPC_OK;
 }
 
+// ---- the debug calls that run one kernel on the caller's arrays: pdmpc_debug_random_numbers, _heap_script, _edge_check, _interx_soups, _sincos
+namespace {
+// One array of such a call: n elements of the caller's, copied to the device before the launch (T const: an operand) or back from it after the
+// launch (an output); on the device it has max(n, count) elements, exactly (DevBuf::ensure_exact).
+extern "C++" template <class T>  // (this namespace sits inside the extern "C" block)
+struct Staged {
+    T* host;
+    size_t n, count = 0;
+    DevBuf<std::remove_const_t<T>> dev;
+};
+
+// The recipe of those calls: the device buffers, the non-empty operands up, `launch` on the handle's stream, a wait for it, the outputs back.
+extern "C++" template <class Launch, class... T>
+int run_staged(pdmpc_handle* h, const char* malloc_failed, const char* launch_failed, Launch&& launch, Staged<T>&... bufs) {
+    if ((0 | ... | bufs.dev.ensure_exact(std::max(bufs.n, bufs.count)))) return fail(PDMPC_ERR_HIP, malloc_failed);
+    hipError_t e = hipSuccess;
+    auto copy = [&e](auto& b, bool up) {
+        typedef std::remove_pointer_t<decltype(b.host)> Elem;
+        if (e != hipSuccess || !b.n || up != std::is_const<Elem>::value) return;
+        e = up ? hipMemcpy(b.dev.p, b.host, b.n * sizeof(Elem), hipMemcpyHostToDevice) : hipMemcpy((void*)b.host, b.dev.p, b.n * sizeof(Elem), hipMemcpyDeviceToHost);
+    };
+    (copy(bufs, true), ...);
+    HIPCHK(e);
+    if (launch() != 0) return fail(PDMPC_ERR_HIP, launch_failed);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    (copy(bufs, false), ...);
+    HIPCHK(e);
+    return PDMPC_OK;
+}
+}  // namespace
+
 int pdmpc_debug_random_numbers(pdmpc_handle* h, int32_t count, const uint32_t* seeds, int32_t n, double* out) {
     if (!h || count < 0 || n < 0 || n > 4000 || (count > 0 && n > 0 && (!seeds || !out))) return fail(PDMPC_ERR_INVALID, "pdmpc_debug_random_numbers: bad argument");
     if (count == 0 || n == 0) return PDMPC_OK;
     ON_DEVICE(h->cfg.device);
-    DevBuf<uint32_t> d_seeds;
-    DevBuf<double> d_out;
-    if (d_seeds.ensure_exact((size_t)count) | d_out.ensure_exact((size_t)count * n)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the generator test");
-    HIPCHK(hipMemcpy(d_seeds.p, seeds, (size_t)count * 4, hipMemcpyHostToDevice));
-    const int lrc = pdmpc_launch_debug_mt19937(d_seeds.p, count, n, d_out.p, (void*)h->stream);
-    if (lrc != 0) return fail(PDMPC_ERR_HIP, "generator launch failed");
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(out, d_out.p, (size_t)count * n * 8, hipMemcpyDeviceToHost));
-    return PDMPC_OK;
+    Staged<const uint32_t> d_seeds{seeds, (size_t)count};
+    Staged<double> d_out{out, (size_t)count * n};
+    auto launch = [&] { return pdmpc_launch_debug_mt19937(d_seeds.dev.p, count, n, d_out.dev.p, (void*)h->stream); };
+    return run_staged(h, "hipMalloc failed for the generator test", "generator launch failed", launch, d_seeds, d_out);
 }
 
 int pdmpc_debug_heap_script(pdmpc_handle* h, int32_t n, const int32_t* op, const int32_t* id, const double* key, int32_t lds_entries,
@@ -1284,176 +1106,21 @@ int pdmpc_debug_heap_script(pdmpc_handle* h, int32_t n, const int32_t* op, const
     if (lds_entries < 64 || lds_entries > 8192 || (lds_entries & 1)) return fail(PDMPC_ERR_INVALID, "lds_entries must be even and in 64..8192");
     ON_DEVICE(h->cfg.device);
     const size_t m = (size_t)std::max(n, 1);
-    DevBuf<int32_t> d_op, d_id, d_out;
-    DevBuf<double> d_key, d_gkey;
-    DevBuf<uint32_t> d_gid;
-    DevBuf<unsigned long long> d_stats;
-    if (d_op.ensure_exact(m) | d_id.ensure_exact(m) | d_out.ensure_exact(m) | d_key.ensure_exact(m) | d_gkey.ensure_exact(m + 2) | d_gid.ensure_exact(m + 2) | d_stats.ensure_exact(4))
-        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the heap script");
-    HIPCHK(hipMemcpy(d_op.p, op, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_id.p, id, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_key.p, key, (size_t)n * 8, hipMemcpyHostToDevice));
-    int lrc = pdmpc_launch_heap_script(d_op.p, d_id.p, d_key.p, n, d_out.p, d_stats.p, d_gkey.p, d_gid.p, lds_entries, (void*)h->stream);
-    if (lrc != 0) return fail(PDMPC_ERR_HIP, "heap script launch failed");
-    HIPCHK(hipStreamSynchronize(h->stream));
-    unsigned long long st[4];
-    HIPCHK(hipMemcpy(st, d_stats.p, sizeof st, hipMemcpyDeviceToHost));
     int cnt = 0;
     for (int i = 0; i < n; ++i) cnt += op[i] == 1;
+    unsigned long long st[4];
+    Staged<const int32_t> d_op{op, (size_t)n, m}, d_id{id, (size_t)n, m};
+    Staged<const double> d_key{key, (size_t)n, m};
+    Staged<int32_t> d_out{popped, (size_t)cnt, m};
+    Staged<double> d_gkey{nullptr, 0, m + 2};  // (the heap's part in HBM: on the device only)
+    Staged<uint32_t> d_gid{nullptr, 0, m + 2};
+    Staged<unsigned long long> d_stats{st, 4};
+    auto launch = [&] { return pdmpc_launch_heap_script(d_op.dev.p, d_id.dev.p, d_key.dev.p, n, d_out.dev.p, d_stats.dev.p, d_gkey.dev.p, d_gid.dev.p, lds_entries, (void*)h->stream); };
+    if (const int rc = run_staged(h, "hipMalloc failed for the heap script", "heap script launch failed", launch, d_op, d_id, d_out, d_key, d_gkey, d_gid, d_stats)) return rc;
     *n_popped = cnt;
-    if (cnt > 0) HIPCHK(hipMemcpy(popped, d_out.p, (size_t)cnt * 4, hipMemcpyDeviceToHost));
     if (cycles_per_pop) *cycles_per_pop = st[1] ? (double)st[0] / (double)st[1] : 0.0;
     if (cycles_per_push) *cycles_per_push = st[3] ? (double)st[2] / (double)st[3] : 0.0;
     return PDMPC_OK;
-}
-
-namespace {
-#define PDMPC_TREE_FRONTIER 0x40000000  /* d_tree_size marker: the arena holds the frontier kernel's raw tree (creation order differs from the reference's) */
-#define PDMPC_TREE_REPLAYED 0x20000000  /* ... and the search ended on the replay through the binary heap (equal keys): its pop sequence, in arena indices, is in the mid list's array */
-#define PDMPC_TREE_SIZE(sz) ((sz) & ~(PDMPC_TREE_FRONTIER | PDMPC_TREE_REPLAYED))
-
-// The frontier kernel processes open nodes in parallel, so its arena holds the reference's tree plus some nodes the
-// reference never creates, in another order.  This turns it back into the reference's tree and pop sequence, on the host
-// and independently of the kernel's phase B (it sorts the popped nodes instead of counting them), for the debug read-backs
-// the parity tests use.  Order (bulk_search.hpp): X is popped before Y iff X is an ancestor of Y or the largest key on
-// the path (LCA, X] is smaller than the largest key on (LCA, Y].
-// the slot a debug read-back's vehicle was planned in (the packer may have put the batch into level order)
-int debug_slot(const pdmpc_handle* h, int vehicle) {
-    const PackedStep& B = h->banks[h->bank];
-    return !B.inv.empty() && vehicle < B.n_packed ? B.inv[(size_t)vehicle] : vehicle;
-}
-
-// the column arrays of pdmpc_debug_tree / pdmpc_debug_raw_tree (a null column is not written)
-struct TreeColumns {
-    double *x, *y, *yaw, *g, *hh;
-    int32_t *trim, *k, *parent;
-    void put(size_t i, const NodeRec& r, int32_t parent_id) const {
-        if (x) x[i] = r.x;
-        if (y) y[i] = r.y;
-        if (yaw) yaw[i] = r.yaw;
-        if (g) g[i] = r.g;
-        if (hh) hh[i] = r.h;
-        if (parent) parent[i] = parent_id;
-        if (trim) trim[i] = NODE_TRIM(r.packed);
-        if (k) k[i] = NODE_K(r.packed);
-    }
-};
-
-// the first min(sz, capacity) records of a slot's arena as they are (and their keys / validity bytes where asked for)
-int copy_raw_tree(pdmpc_handle* h, int slot, int32_t sz, int32_t capacity, const TreeColumns& cols, double* key, uint8_t* validity, int32_t* n) {
-    *n = sz;
-    const size_t m = (size_t)std::max(std::min(sz, capacity), 0);
-    if (m == 0) return PDMPC_OK;
-    const size_t off = (size_t)slot * h->arena.max_nodes;
-    std::vector<NodeRec> rec(m);
-    HIPCHK(hipMemcpy(rec.data(), h->arena.nodes.p + off, m * sizeof(NodeRec), hipMemcpyDeviceToHost));
-    if (key) HIPCHK(hipMemcpy(key, h->arena.key.p + off, m * 8, hipMemcpyDeviceToHost));
-    if (validity) HIPCHK(hipMemcpy(validity, h->arena.vstate.p + off, m, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < m; ++i) cols.put(i, rec[i], (int32_t)rec[i].parent);
-    return PDMPC_OK;
-}
-
-struct RefTree {
-    std::vector<NodeRec> rec;        // raw records
-    std::vector<uint32_t> pops;      // raw indices in the reference's pop order
-    std::vector<uint32_t> ref_nodes; // raw index of reference node id r (0-based position = id - 1)
-    std::vector<uint32_t> ref_id;    // raw index -> reference id (0: not in the reference's tree)
-};
-int reconstruct_reference_tree(pdmpc_handle* h, int vehicle, uint32_t raw_n, RefTree& T, bool replayed = false) {
-    const size_t off = (size_t)vehicle * h->arena.max_nodes;
-    const int Hp = h->cfg.Hp;
-    T.rec.resize(raw_n);
-    std::vector<double> key(raw_n);
-    std::vector<uint8_t> vs(raw_n);
-    HIPCHK(hipMemcpy(T.rec.data(), h->arena.nodes.p + off, (size_t)raw_n * sizeof(NodeRec), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(key.data(), h->arena.key.p + off, (size_t)raw_n * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(vs.data(), h->arena.vstate.p + off, (size_t)raw_n, hipMemcpyDeviceToHost));
-    pdmpc_vehicle_out out;
-    HIPCHK(hipMemcpy(&out, h->d_out.p + vehicle, sizeof out, hipMemcpyDeviceToHost));
-    const std::vector<NodeRec>& R = T.rec;
-    std::vector<uint8_t> alive(raw_n, 0);
-    alive[0] = 1;
-    for (uint32_t i = 1; i < raw_n; ++i) {
-        const uint32_t p = R[i].parent - 1;
-        alive[i] = alive[p] && vs[p] == 1;
-    }
-    auto depth = [&](uint32_t i) { return NODE_K(R[i].packed); };
-    // -1: x first, +1: y first, 0: same node
-    auto before = [&](uint32_t x, uint32_t y) -> int {
-        if (x == y) return 0;
-        double mx = -1.0, my = -1.0;
-        uint32_t a = x, b = y;
-        while (depth(a) > depth(b)) {
-            mx = std::max(mx, key[a]);
-            a = R[a].parent - 1;
-        }
-        while (depth(b) > depth(a)) {
-            my = std::max(my, key[b]);
-            b = R[b].parent - 1;
-        }
-        if (a == b) return depth(x) < depth(y) ? -1 : 1;  // ancestor first
-        while (a != b) {
-            mx = std::max(mx, key[a]);
-            my = std::max(my, key[b]);
-            a = R[a].parent - 1;
-            b = R[b].parent - 1;
-        }
-        return mx < my ? -1 : 1;
-    };
-    // the goal: the first collision-free node at the horizon
-    int64_t goal = -1;
-    if (out.status == PDMPC_OK)
-        for (uint32_t i = 0; i < raw_n; ++i)
-            if (alive[i] && vs[i] == 1 && depth(i) == Hp && (goal < 0 || before(i, (uint32_t)goal) < 0)) goal = i;
-    T.pops.clear();
-    if (replayed) {
-        // equal keys: the order is the binary heap's, which the kernel's replay has run (bulk_search.hpp, bk_replay) and left behind
-        T.pops.resize((size_t)std::max(out.n_popped, 0));
-        if (!T.pops.empty()) HIPCHK(hipMemcpy(T.pops.data(), h->arena.mid_id.p + off, T.pops.size() * 4, hipMemcpyDeviceToHost));
-    } else {
-        for (uint32_t i = 0; i < raw_n; ++i)
-            if (alive[i] && (goal < 0 || i == (uint32_t)goal || before(i, (uint32_t)goal) < 0)) T.pops.push_back(i);
-        std::sort(T.pops.begin(), T.pops.end(), [&](uint32_t x, uint32_t y) { return before(x, y) < 0; });
-    }
-    // children of a node are consecutive raw indices in ascending trim order
-    std::vector<uint32_t> first_child(raw_n, 0), n_child(raw_n, 0);
-    for (uint32_t i = raw_n; i-- > 1;) {
-        const uint32_t p = R[i].parent - 1;
-        first_child[p] = i;
-        n_child[p] += 1;
-    }
-    T.ref_id.assign(raw_n, 0);
-    T.ref_nodes.clear();
-    T.ref_nodes.push_back(0);
-    T.ref_id[0] = 1;
-    for (uint32_t x : T.pops) {
-        if (vs[x] != 1 || depth(x) == Hp) continue;  // discarded (GraphSearch.m:75-77) or the goal
-        for (uint32_t c = 0; c < n_child[x]; ++c) {
-            T.ref_nodes.push_back(first_child[x] + c);
-            T.ref_id[first_child[x] + c] = (uint32_t)T.ref_nodes.size();
-        }
-    }
-    return PDMPC_OK;
-}
-}  // namespace
-
-int pdmpc_debug_pop_trace(pdmpc_handle* h, int32_t vehicle, int32_t capacity, int32_t* ids, int32_t* n) {
-    if (!h || !ids || !n) return fail(PDMPC_ERR_INVALID, "null argument");
-    if (vehicle < 0 || vehicle >= h->max_vehicles) return fail(PDMPC_ERR_INVALID, "vehicle slot out of range");
-    vehicle = debug_slot(h, vehicle);
-    ON_DEVICE(h->cfg.device);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    int32_t sz = 0;
-    HIPCHK(hipMemcpy(&sz, h->d_tree_size.p + vehicle, 4, hipMemcpyDeviceToHost));
-    if (sz & PDMPC_TREE_FRONTIER) {
-        RefTree T;
-        int rc = reconstruct_reference_tree(h, vehicle, (uint32_t)PDMPC_TREE_SIZE(sz), T, (sz & PDMPC_TREE_REPLAYED) != 0);
-        if (rc) return rc;
-        *n = (int32_t)T.pops.size();
-        for (size_t i = 0; i < T.pops.size() && (int)i < capacity; ++i) ids[i] = (int32_t)T.ref_id[T.pops[i]];
-        return PDMPC_OK;
-    }
-    return fail(PDMPC_ERR_INVALID, "no graph search has run in that slot");
 }
 
 int pdmpc_debug_edge_check(pdmpc_handle* h, int32_t mode, int32_t n_cases, const int32_t* a_off, const double* a_x, const double* a_y, const int32_t* b_off,
@@ -1467,27 +1134,12 @@ int pdmpc_debug_edge_check(pdmpc_handle* h, int32_t mode, int32_t n_cases, const
         if (nb < 0 || nb > 1024) return fail(PDMPC_ERR_INVALID, "second operand: at most 1024 columns");
     }
     ON_DEVICE(h->cfg.device);
-    const size_t ta = (size_t)a_off[n_cases], tb = (size_t)b_off[n_cases];
-    DevBuf<int32_t> d_ao, d_bo, d_hit;
-    DevBuf<double> d_ax, d_ay, d_bx, d_by;
-    if (d_ao.ensure_exact((size_t)n_cases + 1) | d_bo.ensure_exact((size_t)n_cases + 1) | d_hit.ensure_exact((size_t)n_cases) | d_ax.ensure_exact(ta) | d_ay.ensure_exact(ta) |
-        d_bx.ensure_exact(tb) | d_by.ensure_exact(tb))
-        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the edge-check cases");
-    HIPCHK(hipMemcpy(d_ao.p, a_off, ((size_t)n_cases + 1) * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_bo.p, b_off, ((size_t)n_cases + 1) * 4, hipMemcpyHostToDevice));
-    if (ta) {
-        HIPCHK(hipMemcpy(d_ax.p, a_x, ta * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_ay.p, a_y, ta * 8, hipMemcpyHostToDevice));
-    }
-    if (tb) {
-        HIPCHK(hipMemcpy(d_bx.p, b_x, tb * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_by.p, b_y, tb * 8, hipMemcpyHostToDevice));
-    }
-    const int lrc = pdmpc_launch_edge_check(mode, n_cases, d_ao.p, d_ax.p, d_ay.p, d_bo.p, d_bx.p, d_by.p, d_hit.p, (void*)h->stream);
-    if (lrc != 0) return fail(PDMPC_ERR_HIP, "edge-check launch failed");
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(hit, d_hit.p, (size_t)n_cases * 4, hipMemcpyDeviceToHost));
-    return PDMPC_OK;
+    const size_t nc = (size_t)n_cases, ta = (size_t)a_off[n_cases], tb = (size_t)b_off[n_cases];
+    Staged<const int32_t> d_ao{a_off, nc + 1}, d_bo{b_off, nc + 1};
+    Staged<const double> d_ax{a_x, ta}, d_ay{a_y, ta}, d_bx{b_x, tb}, d_by{b_y, tb};
+    Staged<int32_t> d_hit{hit, nc};
+    auto launch = [&] { return pdmpc_launch_edge_check(mode, n_cases, d_ao.dev.p, d_ax.dev.p, d_ay.dev.p, d_bo.dev.p, d_bx.dev.p, d_by.dev.p, d_hit.dev.p, (void*)h->stream); };
+    return run_staged(h, "hipMalloc failed for the edge-check cases", "edge-check launch failed", launch, d_ao, d_bo, d_hit, d_ax, d_ay, d_bx, d_by);
 }
 
 int pdmpc_debug_interx_soups(pdmpc_handle* h, int32_t n_cases, const int32_t* a_off, const double* a_x, const double* a_y, const double* b_x, const double* b_y,
@@ -1503,44 +1155,90 @@ int pdmpc_debug_interx_soups(pdmpc_handle* h, int32_t n_cases, const int32_t* a_
     }
     if (a_off[0] < 0 || s_off[0] < 0) return fail(PDMPC_ERR_INVALID, "negative offset");
     ON_DEVICE(h->cfg.device);
-    const size_t ta = (size_t)a_off[n_cases], ts = (size_t)s_off[3 * n_cases];
-    DevBuf<int32_t> d_ao, d_so, d_hit;
-    DevBuf<double> d_ax, d_ay, d_bx, d_by, d_sx, d_sy;
-    if (d_ao.ensure_exact((size_t)n_cases + 1) | d_so.ensure_exact((size_t)3 * n_cases + 1) | d_hit.ensure_exact((size_t)n_cases) | d_ax.ensure_exact(ta) | d_ay.ensure_exact(ta) |
-        d_bx.ensure_exact(ta) | d_by.ensure_exact(ta) | d_sx.ensure_exact(ts) | d_sy.ensure_exact(ts))
-        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the edge-check cases");
-    HIPCHK(hipMemcpy(d_ao.p, a_off, ((size_t)n_cases + 1) * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_so.p, s_off, ((size_t)3 * n_cases + 1) * 4, hipMemcpyHostToDevice));
-    if (ta) {
-        HIPCHK(hipMemcpy(d_ax.p, a_x, ta * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_ay.p, a_y, ta * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_bx.p, b_x, ta * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_by.p, b_y, ta * 8, hipMemcpyHostToDevice));
-    }
-    if (ts) {
-        HIPCHK(hipMemcpy(d_sx.p, s_x, ts * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_sy.p, s_y, ts * 8, hipMemcpyHostToDevice));
-    }
-    const int lrc = pdmpc_launch_interx_soups(n_cases, d_ao.p, d_ax.p, d_ay.p, d_bx.p, d_by.p, d_so.p, d_sx.p, d_sy.p, d_hit.p, (void*)h->stream);
-    if (lrc != 0) return fail(PDMPC_ERR_HIP, "edge-check launch failed");
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(hit, d_hit.p, (size_t)n_cases * 4, hipMemcpyDeviceToHost));
-    return PDMPC_OK;
+    const size_t nc = (size_t)n_cases, ta = (size_t)a_off[n_cases], ts = (size_t)s_off[3 * n_cases];
+    Staged<const int32_t> d_ao{a_off, nc + 1}, d_so{s_off, 3 * nc + 1};
+    Staged<const double> d_ax{a_x, ta}, d_ay{a_y, ta}, d_bx{b_x, ta}, d_by{b_y, ta}, d_sx{s_x, ts}, d_sy{s_y, ts};
+    Staged<int32_t> d_hit{hit, nc};
+    auto launch = [&] { return pdmpc_launch_interx_soups(n_cases, d_ao.dev.p, d_ax.dev.p, d_ay.dev.p, d_bx.dev.p, d_by.dev.p, d_so.dev.p, d_sx.dev.p, d_sy.dev.p, d_hit.dev.p, (void*)h->stream); };
+    return run_staged(h, "hipMalloc failed for the edge-check cases", "edge-check launch failed", launch, d_ao, d_so, d_hit, d_ax, d_ay, d_bx, d_by, d_sx, d_sy);
 }
 
 int pdmpc_debug_sincos(pdmpc_handle* h, int32_t n, const double* x, double* s, double* c) {
     if (!h || n < 0 || (n > 0 && (!x || !s || !c))) return fail(PDMPC_ERR_INVALID, "pdmpc_debug_sincos: bad argument");
     if (n == 0) return PDMPC_OK;
     ON_DEVICE(h->cfg.device);
-    DevBuf<double> d_x, d_s, d_c;
-    if (d_x.ensure_exact((size_t)n) | d_s.ensure_exact((size_t)n) | d_c.ensure_exact((size_t)n)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the sin/cos test");
-    HIPCHK(hipMemcpy(d_x.p, x, (size_t)n * 8, hipMemcpyHostToDevice));
-    const int lrc = pdmpc_launch_debug_sincos(d_x.p, n, d_s.p, d_c.p, (void*)h->stream);
-    if (lrc != 0) return fail(PDMPC_ERR_HIP, "sin/cos launch failed");
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(s, d_s.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(c, d_c.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    Staged<const double> d_x{x, (size_t)n};
+    Staged<double> d_s{s, (size_t)n}, d_c{c, (size_t)n};
+    auto launch = [&] { return pdmpc_launch_debug_sincos(d_x.dev.p, n, d_s.dev.p, d_c.dev.p, (void*)h->stream); };
+    return run_staged(h, "hipMalloc failed for the sin/cos test", "sin/cos launch failed", launch, d_x, d_s, d_c);
+}
+
+// ---- the debug read-backs of a slot's tree
+namespace {
+// the slot a debug read-back's vehicle was planned in (the packer may have put the batch into level order)
+int debug_slot(const pdmpc_handle* h, int vehicle) {
+    const PackedStep& B = h->banks[h->bank];
+    return !B.inv.empty() && vehicle < B.n_packed ? B.inv[(size_t)vehicle] : vehicle;
+}
+
+// the first min(sz, capacity) records of a slot's arena as they are (and their keys / validity bytes where asked for)
+int copy_raw_tree(pdmpc_handle* h, int slot, int32_t sz, int32_t capacity, const TreeColumns& cols, double* key, uint8_t* validity, int32_t* n) {
+    *n = sz;
+    const size_t m = (size_t)std::max(std::min(sz, capacity), 0);
+    if (m == 0) return PDMPC_OK;
+    const size_t off = (size_t)slot * h->arena.max_nodes;
+    std::vector<NodeRec> rec(m);
+    HIPCHK(hipMemcpy(rec.data(), h->arena.nodes.p + off, m * sizeof(NodeRec), hipMemcpyDeviceToHost));
+    if (key) HIPCHK(hipMemcpy(key, h->arena.key.p + off, m * 8, hipMemcpyDeviceToHost));
+    if (validity) HIPCHK(hipMemcpy(validity, h->arena.vstate.p + off, m, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < m; ++i) cols.put(i, rec[i], (int32_t)rec[i].parent);
     return PDMPC_OK;
+}
+
+// A slot's raw arena (tree_size word sz, PDMPC_TREE_FRONTIER set) copied to the host — rec: its records — and read as the reference's tree
+// (reference_tree.hpp: the five copies happen here, the arithmetic there).
+int fetch_reference_tree(pdmpc_handle* h, int slot, int32_t sz, std::vector<NodeRec>& rec, RefTree& T) {
+    const uint32_t raw_n = (uint32_t)PDMPC_TREE_SIZE(sz);
+    if (raw_n > h->arena.max_nodes) return fail(PDMPC_ERR_INVALID, "the slot's tree is larger than its arena");
+    const size_t off = (size_t)slot * h->arena.max_nodes;
+    rec.resize(raw_n);
+    std::vector<double> key(raw_n);
+    std::vector<uint8_t> vs(raw_n);
+    HIPCHK(hipMemcpy(rec.data(), h->arena.nodes.p + off, (size_t)raw_n * sizeof(NodeRec), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(key.data(), h->arena.key.p + off, (size_t)raw_n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(vs.data(), h->arena.vstate.p + off, (size_t)raw_n, hipMemcpyDeviceToHost));
+    pdmpc_vehicle_out out;
+    HIPCHK(hipMemcpy(&out, h->d_out.p + slot, sizeof out, hipMemcpyDeviceToHost));
+    const bool replayed = (sz & PDMPC_TREE_REPLAYED) != 0;
+    std::vector<uint32_t> pops;  // (replayed: the binary heap's pop sequence, which the kernel's replay left in the mid list's array)
+    if (replayed) {
+        if (out.n_popped > (int32_t)h->arena.max_nodes) return fail(PDMPC_ERR_INVALID, "the slot's record counts more pops than its arena holds nodes");
+        pops.resize((size_t)std::max(out.n_popped, 0));
+        if (!pops.empty()) HIPCHK(hipMemcpy(pops.data(), h->arena.mid_id.p + off, pops.size() * 4, hipMemcpyDeviceToHost));
+    }
+    std::string err;
+    return failed(reconstruct_reference_tree(rec.data(), raw_n, key.data(), vs.data(), h->cfg.Hp, out.status, replayed ? &pops : nullptr, T, err), err);
+}
+}  // namespace
+
+int pdmpc_debug_pop_trace(pdmpc_handle* h, int32_t vehicle, int32_t capacity, int32_t* ids, int32_t* n) {
+    if (!h || !ids || !n) return fail(PDMPC_ERR_INVALID, "null argument");
+    if (vehicle < 0 || vehicle >= h->max_vehicles) return fail(PDMPC_ERR_INVALID, "vehicle slot out of range");
+    vehicle = debug_slot(h, vehicle);
+    ON_DEVICE(h->cfg.device);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    int32_t sz = 0;
+    HIPCHK(hipMemcpy(&sz, h->d_tree_size.p + vehicle, 4, hipMemcpyDeviceToHost));
+    if (sz & PDMPC_TREE_FRONTIER) {
+        std::vector<NodeRec> rec;
+        RefTree T;
+        int rc = fetch_reference_tree(h, vehicle, sz, rec, T);
+        if (rc) return rc;
+        *n = (int32_t)T.pops.size();
+        for (size_t i = 0; i < T.pops.size() && (int)i < capacity; ++i) ids[i] = (int32_t)T.ref_id[T.pops[i]];
+        return PDMPC_OK;
+    }
+    return fail(PDMPC_ERR_INVALID, "no graph search has run in that slot");
 }
 
 int pdmpc_debug_raw_tree(pdmpc_handle* h, int32_t vehicle, int32_t capacity, double* x, double* y, double* yaw, double* g, double* hh, int32_t* trim,
@@ -1573,12 +1271,13 @@ int pdmpc_debug_tree(pdmpc_handle* h, int32_t vehicle, int32_t capacity, double*
     HIPCHK(hipMemcpy(&sz, h->d_tree_size.p + vehicle, 4, hipMemcpyDeviceToHost));
     const TreeColumns cols{x, y, yaw, g, hh, trim, k, parent};
     if (sz & PDMPC_TREE_FRONTIER) {
+        std::vector<NodeRec> rec;
         RefTree T;
-        int rc = reconstruct_reference_tree(h, vehicle, (uint32_t)PDMPC_TREE_SIZE(sz), T, (sz & PDMPC_TREE_REPLAYED) != 0);
+        int rc = fetch_reference_tree(h, vehicle, sz, rec, T);
         if (rc) return rc;
         *n = (int32_t)T.ref_nodes.size();
         for (size_t i = 0; i < T.ref_nodes.size() && (int)i < capacity; ++i) {
-            const NodeRec& r = T.rec[T.ref_nodes[i]];
+            const NodeRec& r = rec[T.ref_nodes[i]];
             cols.put(i, r, r.parent ? (int32_t)T.ref_id[r.parent - 1] : 0);
         }
         return PDMPC_OK;
@@ -1587,3 +1286,4 @@ int pdmpc_debug_tree(pdmpc_handle* h, int32_t vehicle, int32_t capacity, double*
 }
 
 }  // extern "C"
+

@@ -2028,7 +2028,7 @@ __device__ __forceinline__ void bulk_search(const KernelArgs& A, Ctx& X, lds_u32
         atomicAdd(P.counters + 2, (int)sh[BK_ARRIVALS]);
         atomicAdd(A.work_count + 2, (unsigned long long)sh[FR_PROCESSED]);
         atomicAdd(A.work_count + 3, (unsigned long long)sh[FR_ROUNDS]);
-        A.tree_size[slot] = (int32_t)(nnodes_raw | 0x40000000u | (tie_replayed ? 0x20000000u : 0u));  // marks the arena as a raw tree (api.cpp reconstructs the reference's; replayed: the pop sequence is there too)
+        A.tree_size[slot] = (int32_t)(nnodes_raw | PDMPC_TREE_FRONTIER | (tie_replayed ? PDMPC_TREE_REPLAYED : 0u));  // marks the arena as a raw tree (reference_tree.hpp reconstructs the reference's; replayed: the pop sequence is there too)
     }
     if (tid_r == 0 && SW::debug_tail(A)) {  // diagnostics in the unused tail of the record (rows HP_MAX - 2 .. HP_MAX of path_nodes); PDMPC_DEBUG_TAIL=1
         double* dbg = X.O->path_nodes[PDMPC_HP_MAX];

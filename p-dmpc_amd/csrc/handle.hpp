@@ -375,7 +375,7 @@ struct FcaState {
 };
 
 // pdmpc_choose_resident / pdmpc_plan_step_chosen (choice_kernel.hip): the staged lists, the read-back block (counters, chosen, cell
-// costs, picked records: ChoiceLayout in api.cpp) and the status tally; grown when a call needs more, kept otherwise
+// costs, picked records: ChoiceLayout in choice_host.hpp) and the status tally; grown when a call needs more, kept otherwise
 struct ChoiceState {
     DevBuf<int32_t> in, tally;
     PinnedBuf<int32_t> h_in;

@@ -474,3 +474,22 @@ inline std::string format_bulk_layout(const LaunchPlan& p, int count) {
                  p.lds.total, p.kernel);
     return buf;
 }
+
+// pdmpc_launch_plan_host (include/pdmpc.h), the window: the plan of the launch a query describes, as the record a test reads
+inline int plan_query(const char* tuning, const pdmpc_launch_query& q, pdmpc_launch_plan& plan, std::string& err) {
+    Tuning T;
+    if (!parse_tuning(tuning, T, err)) return PDMPC_ERR_INVALID;
+    LaunchDims d{q.checker, q.Hp, q.n_trims, 0, q.n_man, 0, 0, q.n_cu, q.device_share, (uint32_t)q.max_nodes, q.kind == kPlanSampled, q.soup_cap, q.ll_cap, q.cand_cap};
+    mpa_table_sizes(d);
+    LaunchPlan p;
+    if (const int rc = plan_launch(T, d, (PlanKind)q.kind, q.count, q.n_chained, q.safe != 0, p, err)) return rc;
+    const LdsLayout& L = p.lds;
+    const JointLds& J = p.joint;
+    const bool joint = q.kind == kPlanJoint;
+    plan = {p.n_waves, p.NL, p.NV, p.areas_in_lds, p.ready, p.compact ? 1 : 0, p.bk_ready_cap, p.bk_round0, p.bk_round, p.bk_ramp, p.bk_tile, p.bk_share_min,
+            p.n_helpers, p.bk_helpers_first, p.bk_seat_nodes, p.reverse_dispatch, p.variant, p.generic ? 1 : 0, p.slice, (int32_t)p.heap_lds, p.spin_limit,
+            joint ? J.mask : L.mask, joint ? J.man_index : L.man_index, joint ? J.pose : L.pose, joint ? J.area : L.area, joint ? J.ref : L.ref, joint ? J.shape : L.shape,
+            L.path, joint ? J.soup : L.soup, L.cand, L.vstate, L.expand, L.tree16, L.rand, L.nodes, joint ? J.total : L.total, L.bk_near_key, L.bk_near_id, L.bk_ready,
+            L.bk_hist, L.bk_misc, L.bk_pshape, L.reach_shared, L.bk_reach, L.reach, J.ints, J.succ, J.heap_key, J.heap_id, p.kernel};
+    return PDMPC_OK;
+}

@@ -268,7 +268,10 @@ struct KernelArgs {
     // arenas
     NodeArena arena;
     uint32_t max_nodes;
-    int32_t* tree_size;  // per slot: nodes in the arena after the search | 0x40000000 (| 0x20000000: ended on a replay) (debug read-back)
+    int32_t* tree_size;  // per slot: nodes in the arena after the search | PDMPC_TREE_FRONTIER (| PDMPC_TREE_REPLAYED) (debug read-back)
+#define PDMPC_TREE_FRONTIER 0x40000000  /* d_tree_size marker: the arena holds the frontier kernel's raw tree (creation order differs from the reference's) */
+#define PDMPC_TREE_REPLAYED 0x20000000  /* ... and the search ended on the replay through the binary heap (equal keys): its pop sequence, in arena indices, is in the mid list's array */
+#define PDMPC_TREE_SIZE(sz) ((sz) & ~(PDMPC_TREE_FRONTIER | PDMPC_TREE_REPLAYED))
     // LDS
     LdsLayout lds;
     int32_t NL, NV, soup_cap, cand_cap;
