@@ -952,6 +952,68 @@ int pdmpc_group_partition(int32_t n_vehicles, const int32_t* pred_offset, const 
  * [3] launches and collectives enqueued, [4] wait, [5] read-back */
 int pdmpc_group_last_timing(pdmpc_group* group, double* ms6);
 
+/* ---- the sampled optimizer, the lean read-back and the choice on a group (csrc/group.cpp, group_route.hpp, group_choice_kernel.hip;
+ * DESIGN.md section 6.1) ----
+ * After the launches of a step a rank HOLDS the records it planned: those of its whole components in the order of its part; the
+ * records of the component planned by levels pass through every rank, rank 0 holds them behind its own.  The calls below leave the
+ * records there -- until the group's next launch, or a launch on one of its handles -- and move only what the caller keeps.
+ *
+ * pdmpc_group_set_step_seeds: the sampled optimizer's seed per vehicle, in the caller's order, for the NEXT pack of the group
+ * (pdmpc_group_plan_step*, pdmpc_group_pack_step), which consumes them also if it fails -- pdmpc_set_step_seeds for a group.  The seeds
+ * travel with the sub-problems, every rank packs a sampled bank for its share, and the records are pdmpc_plan_step_sampled's on one
+ * handle, bit for bit, in every sharding mode.  A seed count other than the packed step's: PDMPC_ERR_INVALID. */
+int pdmpc_group_set_step_seeds(pdmpc_group* group, int32_t n_vehicles, const uint32_t* seeds);
+/* pdmpc_plan_step_lean / pdmpc_fetch_records_at over the group: status[v] and final_cost[v] = path_nodes[Hp][4] in the caller's order
+ * (every rank's kernel writes the 16-byte entries of the records it holds into host memory; no record leaves a device but in the
+ * level exchanges of a shared component), then the records wanted, each read from the rank that holds it.  Arena overflow as in
+ * pdmpc_group_plan_step: arenas doubled on every rank, the step planned again; a predecessor time-out stays a status.
+ * pdmpc_group_fetch_records_at reads the step launched last (by any pdmpc_group_* launch): PDMPC_ERR_INVALID if there is none. */
+int pdmpc_group_plan_step_lean(pdmpc_group* group, int32_t n_vehicles, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index,
+                               const pdmpc_polygon_set* fallback_shapes, const double* weights, int32_t mode, int32_t* status, double* final_cost);
+int pdmpc_group_fetch_records_at(pdmpc_group* group, int32_t count, const int32_t* vehicles, pdmpc_vehicle_out* out);
+/* pdmpc_plan_step_chosen / pdmpc_choose_resident over the group; the contract is pdmpc_choice's, unchanged, and pdmpc_choose_host the
+ * checker.  A cell may list slots of several ranks and a graph's candidates usually lie on several: behind its launches every rank
+ * writes a 16-byte entry per record it holds, ONE all-gather of the entries runs through the group's collective on the handles'
+ * streams, every rank computes the cells and first minima from the same entries in the list's order (the same bits on every rank, and
+ * the host twin's), and copies the picked records IT holds to their places in one block of host memory; rank 0 adds chosen, cell_cost
+ * and the status counters.  The host waits once per planned attempt; the only whole records that leave a device are the picks.
+ * pdmpc_group_choose_resident chooses on group bank `bank`, which must be the one launched last (else PDMPC_ERR_INVALID), and refuses
+ * what pdmpc_choose_resident refuses. */
+int pdmpc_group_plan_step_chosen(pdmpc_group* group, int32_t n_vehicles, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index,
+                                 const pdmpc_polygon_set* fallback_shapes, const double* weights, int32_t mode, const pdmpc_choice* choice, int32_t* chosen,
+                                 double* cell_cost, pdmpc_vehicle_out* picks);
+int pdmpc_group_choose_resident(pdmpc_group* group, int32_t bank, int32_t n_vehicles, const pdmpc_choice* choice, int32_t* chosen, double* cell_cost,
+                                pdmpc_vehicle_out* picks);
+/* The test window of the choice over ranks: record v is uploaded to rank rank_of[v] (a rank's records in ascending v); with
+ * rank_of[v] == -1 to every rank, as a record of the shared component (rank 0 holds it); then exactly the entries, exchange and
+ * kernels of pdmpc_group_choose_resident.  rank_of outside [-1, world): PDMPC_ERR_INVALID. */
+int pdmpc_group_debug_choose(pdmpc_group* group, int32_t n_records, const pdmpc_vehicle_out* records, const int32_t* rank_of, const pdmpc_choice* choice,
+                             int32_t* chosen, double* cell_cost, pdmpc_vehicle_out* picks);
+/* The host code's own accounting of the last pdmpc_group_* call that launched or read back: [0] bytes EACH rank put into collectives,
+ * [1] bytes that reached the host, by copies and by kernel writes to host memory, [2] times the host blocked (a wait on all streams
+ * counts once, a blocking copy once), [3] attempts planned again after an arena overflow.  With E = 16 (an entry), R =
+ * sizeof(pdmpc_vehicle_out), world ranks and per = the most records a rank holds:
+ *   a choice (resident, debug)   [0] (per + 1) E   [1] 4 PDMPC_CHOICE-counters + 4 n_graphs (padded to 8) + 8 n_cells + n_picks R   [2] 1
+ *   plan_step_lean               [0] the level exchanges' records only   [1] (n + world) E per attempt   [2] 1 per attempt
+ *   fetch_records_at             [0] 0   [1] count R   [2] 1 */
+int pdmpc_group_last_exchange(pdmpc_group* group, int64_t* out4);
+/* The route on its own (no GPU needed): rank[v] = the rank that holds vehicle v's record after the launches of the step so
+ * partitioned (pdmpc_group_partition's arguments), position[v] = its index among the records that rank holds. */
+int pdmpc_group_route_host(int32_t n_vehicles, const int32_t* pred_offset, const int32_t* pred_index, const double* weights, int32_t n_devices, int32_t mode,
+                           int32_t* rank, int32_t* position);
+/* The native controller and the sweep on a group (csrc/step_controller.cpp: plan_built).  The controller -- the sweep and every member
+ * -- must have been created on pdmpc_group_handle(group, 0), and mode must be a PDMPC_SHARD_* (else PDMPC_ERR_INVALID); group == NULL
+ * returns it to its handle.  The step preparation stays on that handle (reachable-set coupling, bounding, FCA, unique prioritizations);
+ * what is PLANNED goes over the group: pdmpc_controller_step / _run and pdmpc_sweep_step / _run through pdmpc_group_plan_step (last
+ * step's pops are the partition's weights too), the explorative and optimal-priority steps through pdmpc_group_plan_step_lean +
+ * pdmpc_group_fetch_records_at or, with the choice on the device (pdmpc_controller_set_device_choice; always in a sweep),
+ * pdmpc_group_plan_step_chosen, the sampled optimizer through pdmpc_group_set_step_seeds.  After every step the controller's state,
+ * records, problem, seeds, chosen instances and cost table are byte for byte what the same call leaves without a group.
+ * Centralized steps (pdmpc_plan_joint) keep running on the handle.  pdmpc_controller_last_timing's backend parts are then
+ * pdmpc_group_last_timing's: [1] partition and pack, [2] launches and collectives enqueued, [3] wait and read-back. */
+int pdmpc_controller_set_group(pdmpc_controller* c, pdmpc_group* group, int32_t mode);
+int pdmpc_sweep_set_group(pdmpc_sweep* s, pdmpc_group* group, int32_t mode);
+
 const char* pdmpc_last_error(void);
 const char* pdmpc_version(void);
 

@@ -22,6 +22,13 @@
 // LOGICAL ranks that share a physical device (two handles, two streams, two sets of arenas on one GPU), so every line of the
 // multi-rank protocol (slot remapping, block partition of a level, import of the other ranks' blocks) runs on a 1-GPU box
 // (tests/test_group.py).  Every entry point leaves the caller's current device as it found it (DeviceScope).
+//
+// What need not be exchanged.  A caller that keeps a few of a batch's plans (the explorative and the optimal-priority step, a sweep of
+// them) gets the three read-backs of a handle over the group: the step's launches without the end-of-step
+// all-gather leave every record with the rank that planned it (group_route.hpp says which, and where), and then either 16 bytes per
+// record reach the host and the wanted records follow from their holders (pdmpc_group_plan_step_lean, _fetch_records_at), or the ranks
+// all-gather those 16-byte entries, each makes the same choice and copies the picked records it holds into one block of host memory
+// (pdmpc_group_plan_step_chosen; kernels in group_choice_kernel.hip).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -39,7 +46,10 @@
 #include <vector>
 
 #include "../../include/pdmpc.h"
+#include "choice_host.hpp"
 #include "coupling_order.hpp"
+#include "group_choice.h"
+#include "group_route.hpp"
 
 extern "C" void pdmpc_set_last_error(const char* msg);  // api.cpp
 
@@ -106,113 +116,12 @@ struct DeviceScope {
 };
 
 // ---------------------------------------------------------------------------------------------------------------
-// Partition (pure host logic; pdmpc_group_partition exposes it).
-
-struct Partition {
-    std::vector<std::vector<int>> parts;  // per device: the slots (caller's indices) of its whole components, in level order
-    std::vector<int> shared;              // slots of the component planned by levels over all devices, in LEVEL ORDER
-    std::vector<int> level_sizes;         // ... and its computation levels
-    std::vector<int> level_of;            // [n] computation level (1-based) within the whole problem's coupling DAG
-};
-
-// union-find over the predecessor lists: component label per slot = smallest slot of the component (distributed.weak_components)
-std::vector<int> weak_components(int n, const int32_t* off, const int32_t* idx) {
-    std::vector<int> parent((size_t)n);
-    std::iota(parent.begin(), parent.end(), 0);
-    auto find = [&](int a) {
-        while (parent[(size_t)a] != a) {
-            parent[(size_t)a] = parent[(size_t)parent[(size_t)a]];
-            a = parent[(size_t)a];
-        }
-        return a;
-    };
-    if (off)
-        for (int s = 0; s < n; ++s)
-            for (int q = off[s]; q < off[s + 1]; ++q) {
-                const int p = idx[q];
-                if (p < 0 || p >= n) continue;
-                const int ra = find(s), rb = find(p);
-                if (ra != rb) parent[(size_t)std::max(ra, rb)] = std::min(ra, rb);
-            }
-    std::vector<int> label((size_t)n);
-    for (int s = 0; s < n; ++s) label[(size_t)s] = find(s);
-    return label;
-}
-
+// The partition and the route are pure host logic (group_route.hpp; pdmpc_group_partition and pdmpc_group_route_host expose them).
+using Partition = GroupPartition;
 int make_partition(int n, const int32_t* off, const int32_t* idx, const double* weights, int world, int mode, Partition& P) {
-    P.parts.assign((size_t)world, {});
-    P.shared.clear();
-    P.level_sizes.clear();
-    // (without predecessor lists the weights only balance the devices: every slot is its own component, in the caller's order)
-    CouplingOrder order;
-    if (order.build(n, off, idx, off ? weights : nullptr) != CouplingOrder::kOk) return gfail(PDMPC_ERR_INVALID, "the sequential coupling graph has a cycle");
-    P.level_of = order.level;
-    const std::vector<int> label = weak_components(n, off, idx);
-    std::vector<int> comp_ids;  // labels in ascending order
-    std::vector<std::vector<int>> comp((size_t)n);
-    for (int s = 0; s < n; ++s) {
-        if (comp[(size_t)label[(size_t)s]].empty()) comp_ids.push_back(label[(size_t)s]);
-        comp[(size_t)label[(size_t)s]].push_back(s);
-    }
-    std::sort(comp_ids.begin(), comp_ids.end());
-    auto weight = [&](int c) {
-        double w = 0;
-        for (int s : comp[(size_t)c]) w += weights ? weights[s] : 1.0;
-        return w;
-    };
-    int heavy = -1;
-    if (mode == PDMPC_SHARD_LEVELS) {
-        for (int s = 0; s < n; ++s) P.shared.push_back(s);
-        comp_ids.clear();
-    } else if (mode == PDMPC_SHARD_AUTO && world > 1 && !comp_ids.empty()) {
-        // distributed.hybrid_partition: the heaviest component (ties: the smaller label) is shared if it outweighs the mean load per device
-        double total = 0, wh = -1;
-        for (int c : comp_ids) {
-            const double w = weight(c);
-            total += w;
-            if (w > wh) {
-                wh = w;
-                heavy = c;
-            }
-        }
-        if ((int)comp[(size_t)heavy].size() >= 2 * world && wh > total / world) {
-            P.shared = comp[(size_t)heavy];
-            comp_ids.erase(std::find(comp_ids.begin(), comp_ids.end(), heavy));
-        }
-    }
-    // whole components: longest processing time first (ties: the smaller label), each to the least loaded device (ties: the lower rank)
-    std::stable_sort(comp_ids.begin(), comp_ids.end(), [&](int a, int b) { return weight(a) > weight(b); });
-    std::vector<double> load((size_t)world, 0.0);
-    for (int c : comp_ids) {
-        int r = 0;
-        for (int q = 1; q < world; ++q)
-            if (load[(size_t)q] < load[(size_t)r]) r = q;
-        for (int s : comp[(size_t)c]) P.parts[(size_t)r].push_back(s);
-        load[(size_t)r] += weight(c);
-    }
-    // a device's slots in a topological order of the coupling DAG: the sub-problem handed to pdmpc_pack_step then has its
-    // predecessors in lower slots whatever order the caller's slots are in, so the handle does not permute it and the device-resident
-    // record path (pdmpc_export_results_async) applies; group_fetch scatters back through these lists.  Without weights that is
-    // level order (ascending caller index within a level); with weights, PRIORITY order (coupling_order.hpp: the packer does the same
-    // for a single handle, pdmpc_set_step_weights): a device with more searches than CUs starts its heavy searches with the launch,
-    // not behind the searches that wait.
-    for (auto& p : P.parts) {
-        std::sort(p.begin(), p.end());
-        order.sort(p);
-    }
-    // the shared component in level order (levels by longest path, ascending vehicle index within a level: find(levels == i))
-    if (!P.shared.empty()) {
-        std::stable_sort(P.shared.begin(), P.shared.end(), [&](int a, int b) { return P.level_of[(size_t)a] < P.level_of[(size_t)b]; });
-        int cur = -1;
-        for (int s : P.shared) {
-            if (P.level_of[(size_t)s] != cur) {
-                cur = P.level_of[(size_t)s];
-                P.level_sizes.push_back(0);
-            }
-            P.level_sizes.back() += 1;
-        }
-    }
-    return PDMPC_OK;
+    std::string err;
+    const int rc = ::make_partition(n, off, idx, weights, world, mode, P, err);
+    return rc ? gfail(rc, err) : PDMPC_OK;
 }
 
 // the step problem restricted to `slots`: predecessor indices remapped to positions (predecessors outside the selection cannot occur:
@@ -248,11 +157,12 @@ const size_t kRec = sizeof(pdmpc_vehicle_out);
 
 struct pdmpc_group;
 namespace {
-// the exchange between the ranks of a group: `per` records from every rank's send buffer into every rank's receive buffer
-// (rank r's block at r * per), enqueued on the handles' streams
+// the exchange between the ranks of a group: `bytes` bytes from every rank's send buffer into every rank's receive buffer
+// (rank r's block at r * bytes), enqueued on the handles' streams.  Whole records between the levels of a shared component and at
+// the end of pdmpc_group_plan_step; 16-byte entries for a choice over the ranks.
 struct Collective {
     const char* name;
-    int (*all_gather)(pdmpc_group* g, size_t per);
+    int (*all_gather)(pdmpc_group* g, unsigned char* const* send, unsigned char* const* recv, size_t bytes);
 };
 }  // namespace
 
@@ -270,10 +180,31 @@ struct pdmpc_group {
     size_t shared_cap = 0;
     std::vector<unsigned char> host;          // read-back staging
     double timing[6] = {0, 0, 0, 0, 0, 0};
+    // ---- lean read-back and the choice over the ranks
+    int32_t Hp = 0;                           // the handles' prediction horizon: the row of path_nodes whose g is a plan's cost
+    int resident_bank = -1;                   // the bank whose records the ranks HOLD (group_route.hpp) since the last launch of either kind
+    std::vector<const pdmpc_vehicle_out*> rec;  // per rank: its handle's record buffer
+    std::vector<uint32_t> next_seeds;         // pdmpc_group_set_step_seeds: consumed by the next pack
+    bool seeds_set = false;
+    int64_t xchg[4] = {0, 0, 0, 0};           // pdmpc_group_last_exchange
+    std::vector<unsigned char*> esend, erecv;  // per rank: its block of entries / every rank's block
+    size_t esend_cap = 0, erecv_cap = 0;      // bytes these hold
+    std::vector<unsigned char*> lists;        // per rank: the staged lists of a choice (int32 words)
+    size_t lists_cap = 0;                     // bytes
+    std::vector<unsigned char*> made;         // per rank: chosen and cell_cost as the cells pass leaves them (ChoiceLayout's offsets)
+    size_t made_cap = 0;                      // bytes
+    int32_t* pin_lists = nullptr;             // pinned: the lists on their way to the ranks
+    size_t pin_lists_cap = 0;
+    unsigned char* pin_out = nullptr;         // pinned and mapped into every device: what kernels write for the host, and the staging of record copies
+    std::vector<unsigned char*> pin_out_dev;  // ... as rank r's kernels address it
+    size_t pin_out_cap = 0;
+    std::vector<pdmpc_vehicle_out*> placed;   // per rank: records placed by pdmpc_group_debug_choose
+    size_t placed_cap = 0;
     struct Plan {                             // a packed step (pdmpc_group_pack_step): how it is split and how large its blocks are
         bool valid = false;
         int n = 0;
         Partition P;
+        GroupRoute route;                     // who holds which record after its launches
         size_t per_w = 0;
     };
     std::vector<Plan> plans;
@@ -340,17 +271,17 @@ int ensure_buffers(pdmpc_group* g, size_t per, size_t n_shared) {
 }
 
 // one all-gather of `per` records per device over the whole group, on the handles' streams: RCCL ...
-int all_gather_rccl(pdmpc_group* g, size_t per) {
+int all_gather_rccl(pdmpc_group* g, unsigned char* const* send, unsigned char* const* recv, size_t bytes) {
     const size_t world = g->h.size();
     GNCCL(g_rccl.GroupStart());
-    for (size_t r = 0; r < world; ++r) GNCCL(g_rccl.AllGather(g->send[r], g->recv[r], per * kRec, ncclChar, g->comm[r], g->stream[r]));
+    for (size_t r = 0; r < world; ++r) GNCCL(g_rccl.AllGather(send[r], recv[r], bytes, ncclChar, g->comm[r], g->stream[r]));
     GNCCL(g_rccl.GroupEnd());
     return PDMPC_OK;
 }
 // ... or peer copies.  Rank q's stream waits for every rank's block (an event per rank, recorded behind its export), copies the
 // blocks into its own receive buffer, and says so; a rank's stream goes on (its next export overwrites its send buffer) once
 // everybody has copied.  Nothing waits on the host.
-int all_gather_copy(pdmpc_group* g, size_t per) {
+int all_gather_copy(pdmpc_group* g, unsigned char* const* send, unsigned char* const* recv, size_t bytes) {
     const size_t world = g->h.size();
     for (size_t r = 0; r < world; ++r) {
         GHIP(hipSetDevice(g->dev[r]));
@@ -360,11 +291,11 @@ int all_gather_copy(pdmpc_group* g, size_t per) {
         GHIP(hipSetDevice(g->dev[q]));
         for (size_t r = 0; r < world; ++r) {
             if (r != q) GHIP(hipStreamWaitEvent(g->stream[q], g->ev_sent[r], 0));
-            unsigned char* dst = g->recv[q] + r * per * kRec;
+            unsigned char* dst = recv[q] + r * bytes;
             if (g->dev[q] == g->dev[r])
-                GHIP(hipMemcpyAsync(dst, g->send[r], per * kRec, hipMemcpyDeviceToDevice, g->stream[q]));
+                GHIP(hipMemcpyAsync(dst, send[r], bytes, hipMemcpyDeviceToDevice, g->stream[q]));
             else
-                GHIP(hipMemcpyPeerAsync(dst, g->dev[q], g->send[r], g->dev[r], per * kRec, g->stream[q]));
+                GHIP(hipMemcpyPeerAsync(dst, g->dev[q], send[r], g->dev[r], bytes, g->stream[q]));
         }
         GHIP(hipEventRecord(g->ev_got[q], g->stream[q]));
     }
@@ -377,7 +308,15 @@ int all_gather_copy(pdmpc_group* g, size_t per) {
 }
 const Collective kCollRccl = {"rccl", all_gather_rccl};
 const Collective kCollCopy = {"copy", all_gather_copy};
-inline int all_gather(pdmpc_group* g, size_t per) { return g->coll->all_gather(g, per); }
+// ... of `per` records per rank, and of a block of entries per rank; both counted for pdmpc_group_last_exchange
+inline int all_gather(pdmpc_group* g, size_t per) {
+    g->xchg[0] += (int64_t)(per * kRec);
+    return g->coll->all_gather(g, g->send.data(), g->recv.data(), per * kRec);
+}
+inline int all_gather_entries(pdmpc_group* g, size_t per) {
+    g->xchg[0] += (int64_t)((per + 1) * sizeof(GroupEntry));
+    return g->coll->all_gather(g, g->esend.data(), g->erecv.data(), (per + 1) * sizeof(GroupEntry));
+}
 
 using clk = std::chrono::steady_clock;
 inline double ms_between(clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
@@ -390,9 +329,17 @@ int group_pack(pdmpc_group* g, int bank, int n, const pdmpc_vehicle_in* in, cons
     pdmpc_group::Plan& L = g->plans[(size_t)bank];
     L.valid = false;
     if (g->last_bank == bank) g->last_bank = -1;
+    if (g->resident_bank == bank) g->resident_bank = -1;
+    // the seeds set for this pack are consumed by it, also if it fails (as a handle's: pack.cpp)
+    const bool sampled = g->seeds_set;
+    const std::vector<uint32_t> seeds = std::move(g->next_seeds);
+    g->next_seeds.clear();
+    g->seeds_set = false;
+    if (sampled && (int)seeds.size() != n) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_set_step_seeds: the seeds are not one per vehicle of the packed step");
     L.n = n;
     Partition& P = L.P;
     GRC(make_partition(n, off, idx, weights, world, mode, P));
+    route_partition(P, n, L.route);
     SubProblem S;
     std::vector<SubProblem> W((size_t)world);
     if (!P.shared.empty()) make_sub(P.shared, n, in, off, idx, fb, S);
@@ -407,13 +354,22 @@ int group_pack(pdmpc_group* g, int bank, int n, const pdmpc_vehicle_in* in, cons
     // the shared component on every device, a device's whole components on that device
     const int nS = (int)P.shared.size();
     for (int r = 0; r < world; ++r) {
+        // (a sampled bank: the seeds travel with the slots, so every rank packs them for its share)
         if (nS) {
             GRC(pdmpc_select_bank(g->h[(size_t)r], bank_shared(bank)));
+            if (sampled) {
+                const std::vector<uint32_t> sub = route_seeds(P.shared, seeds);
+                GRC(pdmpc_set_step_seeds(g->h[(size_t)r], nS, sub.data()));
+            }
             GRC(pdmpc_pack_step(g->h[(size_t)r], nS, S.in.data(), S.pred_off.data(), S.pred_idx.data(), S.any_fallback ? S.fallback.data() : nullptr));
         }
         const SubProblem& w = W[(size_t)r];
         if (!w.in.empty()) {
             GRC(pdmpc_select_bank(g->h[(size_t)r], bank_whole(bank)));
+            if (sampled) {
+                const std::vector<uint32_t> sub = route_seeds(P.parts[(size_t)r], seeds);
+                GRC(pdmpc_set_step_seeds(g->h[(size_t)r], (int)w.in.size(), sub.data()));
+            }
             GRC(pdmpc_pack_step(g->h[(size_t)r], (int)w.in.size(), w.in.data(), w.pred_off.data(), w.pred_idx.data(), w.any_fallback ? w.fallback.data() : nullptr));
         }
         GRC(pdmpc_select_bank(g->h[(size_t)r], 0));
@@ -425,10 +381,19 @@ int group_pack(pdmpc_group* g, int bank, int n, const pdmpc_vehicle_in* in, cons
     return PDMPC_OK;
 }
 
-// plan the packed step: everything enqueued on the handles' streams, one wait at the end
-int group_launch(pdmpc_group* g, int bank) {
+// one wait of the host, on all streams
+int group_wait(pdmpc_group* g) {
+    for (size_t r = 0; r < g->h.size(); ++r) GRC(pdmpc_synchronize(g->h[r]));
+    g->xchg[2] += 1;
+    return PDMPC_OK;
+}
+
+// The launches of a packed step enqueued on the handles' streams: the shared component level by level with its exchanges, then the
+// whole components.  gather_records: the all-gather of the whole components' records that pdmpc_group_fetch reads; without it the
+// records stay with the ranks that planned them (Plan::route) and nothing but the level exchanges has moved a record.
+int group_enqueue(pdmpc_group* g, int bank, bool gather_records) {
     if ((size_t)bank >= g->plans.size() || !g->plans[(size_t)bank].valid) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_launch: nothing packed in that bank");
-    const auto t2 = clk::now();
+    g->last_bank = g->resident_bank = -1;
     const int world = (int)g->h.size();
     const pdmpc_group::Plan& L = g->plans[(size_t)bank];
     const Partition& P = L.P;
@@ -473,13 +438,27 @@ int group_launch(pdmpc_group* g, int bank) {
         any_whole = true;
         GRC(pdmpc_select_bank(g->h[(size_t)r], bank_whole(bank)));
         GRC(pdmpc_launch_packed(g->h[(size_t)r]));
-        GRC(pdmpc_export_results_async(g->h[(size_t)r], 0, nr, g->send[(size_t)r]));
+        if (gather_records) GRC(pdmpc_export_results_async(g->h[(size_t)r], 0, nr, g->send[(size_t)r]));
     }
-    if (any_whole) GRC(all_gather(g, L.per_w));
+    if (any_whole && gather_records) GRC(all_gather(g, L.per_w));
+    return PDMPC_OK;
+}
+
+// what every launch ends with, after the wait: the handles back on their bank 0, the bank's records held by the ranks
+int group_launched(pdmpc_group* g, int bank, bool gathered_records) {
+    for (size_t r = 0; r < g->h.size(); ++r) GRC(pdmpc_select_bank(g->h[r], 0));
+    g->resident_bank = bank;
+    if (gathered_records) g->last_bank = bank;
+    return PDMPC_OK;
+}
+
+// plan the packed step: everything enqueued on the handles' streams, one wait at the end
+int group_launch(pdmpc_group* g, int bank) {
+    const auto t2 = clk::now();
+    GRC(group_enqueue(g, bank, true));
     const auto t3 = clk::now();
-    for (int r = 0; r < world; ++r) GRC(pdmpc_synchronize(g->h[(size_t)r]));
-    for (int r = 0; r < world; ++r) GRC(pdmpc_select_bank(g->h[(size_t)r], 0));
-    g->last_bank = bank;
+    GRC(group_wait(g));
+    GRC(group_launched(g, bank, true));
     g->timing[3] = ms_between(t2, t3);
     g->timing[4] = ms_between(t3, clk::now());
     return PDMPC_OK;
@@ -501,17 +480,238 @@ int group_fetch(pdmpc_group* g, int bank, int n, pdmpc_vehicle_out* out) {
     if (any_whole) {
         g->host.resize(L.per_w * kRec * (size_t)world);
         GHIP(hipMemcpy(g->host.data(), g->recv[0], g->host.size(), hipMemcpyDeviceToHost));
+        g->xchg[1] += (int64_t)g->host.size();
+        g->xchg[2] += 1;
         for (int r = 0; r < world; ++r)
             for (size_t i = 0; i < P.parts[(size_t)r].size(); ++i) std::memcpy(&out[P.parts[(size_t)r][i]], g->host.data() + ((size_t)r * L.per_w + i) * kRec, kRec);
     }
     if (nS) {
         g->host.resize((size_t)nS * kRec);
         GHIP(hipMemcpy(g->host.data(), g->shared_buf, g->host.size(), hipMemcpyDeviceToHost));
+        g->xchg[1] += (int64_t)g->host.size();
+        g->xchg[2] += 1;
         for (int i = 0; i < nS; ++i) std::memcpy(&out[P.shared[(size_t)i]], g->host.data() + (size_t)i * kRec, kRec);
     }
     g->timing[5] = ms_between(t4, clk::now());
     return PDMPC_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Lean read-back and the choice over the ranks (group_route.hpp; group_choice_kernel.hip).
+
+// The reference's tree is unbounded (Tree.m:54-70): after a step in which some search outgrew its arena, arenas twice as large on every
+// device (as pdmpc_plan_step does for one).  grown == false: no room, the arenas stay and the statuses tell.
+int grow_all(pdmpc_group* g, const char* who, bool& grown) {
+    grown = false;
+    // (the devices' arenas may differ after a failed attempt to grow: the step fits when the SMALLEST arena holds every search)
+    int32_t nodes = 0;
+    for (pdmpc_handle* h : g->h) {
+        int32_t nr = 0;
+        GRC(pdmpc_arena_nodes(h, &nr, nullptr));
+        nodes = nodes ? std::min(nodes, nr) : nr;
+    }
+    if ((int64_t)nodes * 2 > (1ll << 30)) return PDMPC_OK;
+    for (size_t r = 0; r < g->h.size(); ++r) {
+        int32_t nr = 0;
+        GRC(pdmpc_arena_nodes(g->h[r], &nr, nullptr));
+        if (nr >= nodes * 2) continue;
+        if (pdmpc_grow_arena(g->h[r], nodes * 2) != PDMPC_OK) {
+            // no room to grow on this device: the records keep their PDMPC_ARENA_OVERFLOW statuses AND the error string says why
+            char b[192];
+            snprintf(b, sizeof b, "%s: the arenas of rank %zu (device %d) cannot grow to %d nodes per vehicle", who, r, g->dev[r], nodes * 2);
+            pdmpc_set_last_error(b);
+            return PDMPC_OK;
+        }
+    }
+    grown = true;
+    return PDMPC_OK;
+}
+
+// the records rank r holds (GroupRoute's positions index them): n_a in rec_a, the rest in rec_b
+struct Held {
+    const pdmpc_vehicle_out* rec_a;
+    const pdmpc_vehicle_out* rec_b;
+    int32_t n_a, n_b;
+};
+Held held_of_bank(const pdmpc_group* g, const pdmpc_group::Plan& L, size_t r) {
+    const int32_t n_a = (int32_t)L.P.parts[r].size();
+    return {g->rec[r], r == 0 ? (const pdmpc_vehicle_out*)g->shared_buf : nullptr, n_a, L.route.held[r] - n_a};
+}
+Held held_placed(const pdmpc_group* g, const GroupRoute& R, size_t r) { return {g->placed[r], nullptr, R.held[r], 0}; }
+
+// pinned memory mapped into every device of the group; no stream has work in flight when a group call begins, so it may move
+int ensure_pin_out(pdmpc_group* g, size_t bytes) {
+    if (bytes <= g->pin_out_cap) return PDMPC_OK;
+    if (g->pin_out) (void)hipHostFree(g->pin_out);
+    g->pin_out = nullptr;
+    g->pin_out_cap = 0;
+    const size_t cap = bytes + bytes / 2 + 4096;
+    GHIP(hipHostMalloc((void**)&g->pin_out, cap, hipHostMallocPortable | hipHostMallocMapped));
+    for (size_t r = 0; r < g->h.size(); ++r) {
+        GHIP(hipSetDevice(g->dev[r]));
+        void* d = nullptr;
+        GHIP(hipHostGetDevicePointer(&d, g->pin_out, 0));
+        g->pin_out_dev[r] = (unsigned char*)d;
+    }
+    g->pin_out_cap = cap;
+    return PDMPC_OK;
+}
+
+// per rank a device buffer of at least `want` bytes (`cap` bytes today)
+int ensure_per_rank(pdmpc_group* g, std::vector<unsigned char*>& buf, size_t& cap, size_t want) {
+    if (want <= cap) return PDMPC_OK;
+    const size_t next = want + want / 2 + 256;
+    for (size_t r = 0; r < g->h.size(); ++r) {
+        GHIP(hipSetDevice(g->dev[r]));
+        if (buf[r]) (void)hipFree(buf[r]);
+        buf[r] = nullptr;
+        GHIP(hipMalloc((void**)&buf[r], next));
+        GHIP(hipMemset(buf[r], 0, next));
+    }
+    cap = next;
+    return PDMPC_OK;
+}
+// a block of header + per entries to send, every rank's block to receive
+int ensure_entries(pdmpc_group* g, int32_t per) {
+    const size_t block = ((size_t)per + 1) * sizeof(GroupEntry);
+    GRC(ensure_per_rank(g, g->esend, g->esend_cap, block));
+    return ensure_per_rank(g, g->erecv, g->erecv_cap, block * g->h.size());
+}
+
+// every rank's block of entries (header + the records it holds) into `to(r)`
+template <class HeldOf, class To>
+int enqueue_entries(pdmpc_group* g, HeldOf&& held_of, To&& to) {
+    for (size_t r = 0; r < g->h.size(); ++r) {
+        const Held H = held_of(r);
+        GroupEntriesArgs A{H.rec_a, H.rec_b, H.n_a, H.n_b, g->Hp, 0, (GroupEntry*)to(r)};
+        GHIP(hipSetDevice(g->dev[r]));
+        const int lrc = pdmpc_launch_group_entries(&A, (void*)g->stream[r]);
+        if (lrc) return gfail(PDMPC_ERR_HIP, std::string("the entries kernel's launch failed: ") + hipGetErrorString((hipError_t)lrc));
+    }
+    return PDMPC_OK;
+}
+
+// A checked choice staged for the ranks: its lists with slots as entry indices (route_slots), uploaded to every rank on its stream.
+struct StagedChoice {
+    const pdmpc_choice* ch;
+    ChoiceLayout L;
+    size_t cell_offset, cell_entry, graph_offset, pick_graph, pick_offset, pick_entry, words;
+    explicit StagedChoice(const pdmpc_choice& c) : ch(&c), L(c) {
+        const int n_cell_slots = c.n_cells > 0 ? c.cell_offset[c.n_cells] : 0, n_pick_slots = c.n_picks > 0 ? c.pick_offset[c.n_picks] : 0;
+        cell_offset = 0;
+        cell_entry = cell_offset + (size_t)c.n_cells + 1;
+        graph_offset = cell_entry + (size_t)n_cell_slots;
+        pick_graph = graph_offset + (size_t)c.n_graphs + 1;
+        pick_offset = pick_graph + (size_t)c.n_picks;
+        pick_entry = pick_offset + (size_t)c.n_picks + 1;
+        words = pick_entry + (size_t)n_pick_slots;
+    }
+};
+int stage_group_choice(pdmpc_group* g, const GroupRoute& R, const StagedChoice& S) {
+    const pdmpc_choice& ch = *S.ch;
+    if (S.words > g->pin_lists_cap) {
+        if (g->pin_lists) (void)hipHostFree(g->pin_lists);
+        g->pin_lists = nullptr;
+        g->pin_lists_cap = 0;
+        const size_t cap = S.words + S.words / 2 + 256;
+        GHIP(hipHostMalloc((void**)&g->pin_lists, cap * sizeof(int32_t), hipHostMallocPortable));
+        g->pin_lists_cap = cap;
+    }
+    GRC(ensure_per_rank(g, g->lists, g->lists_cap, S.words * sizeof(int32_t)));
+    GRC(ensure_per_rank(g, g->made, g->made_cap, S.L.picks));
+    GRC(ensure_pin_out(g, S.L.bytes));
+    GRC(ensure_entries(g, R.per));
+    int32_t* w = g->pin_lists;
+    w[S.cell_offset] = w[S.graph_offset] = w[S.pick_offset] = 0;
+    if (ch.n_cells > 0) {
+        std::memcpy(w + S.cell_offset, ch.cell_offset, ((size_t)ch.n_cells + 1) * sizeof(int32_t));
+        route_slots(R, ch.cell_slot, ch.cell_offset[ch.n_cells], w + S.cell_entry);
+    }
+    if (ch.n_graphs > 0) std::memcpy(w + S.graph_offset, ch.graph_offset, ((size_t)ch.n_graphs + 1) * sizeof(int32_t));
+    if (ch.n_picks > 0) {
+        std::memcpy(w + S.pick_graph, ch.pick_graph, (size_t)ch.n_picks * sizeof(int32_t));
+        std::memcpy(w + S.pick_offset, ch.pick_offset, ((size_t)ch.n_picks + 1) * sizeof(int32_t));
+        route_slots(R, ch.pick_slot, ch.pick_offset[ch.n_picks], w + S.pick_entry);
+    }
+    for (size_t r = 0; r < g->h.size(); ++r) {
+        GHIP(hipSetDevice(g->dev[r]));
+        GHIP(hipMemcpyAsync(g->lists[r], w, S.words * sizeof(int32_t), hipMemcpyHostToDevice, g->stream[r]));
+    }
+    return PDMPC_OK;
+}
+
+// The choice behind whatever the streams hold: every rank's entries, ONE all-gather of them (16 bytes per record), the cells and first
+// minima on every rank, the gather of the picks each rank holds into the one block the host reads.  Nothing waits on the host.
+template <class HeldOf>
+int enqueue_group_choice(pdmpc_group* g, const GroupRoute& R, const StagedChoice& S, HeldOf&& held_of) {
+    const pdmpc_choice& ch = *S.ch;
+    GRC(enqueue_entries(g, held_of, [&](size_t r) { return g->esend[r]; }));
+    GRC(all_gather_entries(g, (size_t)R.per));
+    for (size_t r = 0; r < g->h.size(); ++r) {
+        const Held H = held_of(r);
+        GroupChoiceArgs A{};
+        A.gathered = (const GroupEntry*)g->erecv[r];
+        A.world = (int32_t)g->h.size();
+        A.per = R.per;
+        A.rank = (int32_t)r;
+        A.n_cells = ch.n_cells;
+        A.n_graphs = ch.n_graphs;
+        A.n_picks = ch.n_picks;
+        A.first_graph_cell = ch.n_graphs > 0 ? ch.graph_offset[0] : 0;
+        A.end_graph_cell = ch.n_graphs > 0 ? ch.graph_offset[ch.n_graphs] : 0;
+        A.cell_offset = (const int32_t*)g->lists[r] + S.cell_offset;
+        A.cell_entry = (const int32_t*)g->lists[r] + S.cell_entry;
+        A.graph_offset = (const int32_t*)g->lists[r] + S.graph_offset;
+        A.pick_graph = (const int32_t*)g->lists[r] + S.pick_graph;
+        A.pick_offset = (const int32_t*)g->lists[r] + S.pick_offset;
+        A.pick_entry = (const int32_t*)g->lists[r] + S.pick_entry;
+        A.chosen = (int32_t*)(g->made[r] + S.L.chosen);
+        A.cell_cost = (double*)(g->made[r] + S.L.cell_cost);
+        A.rec_a = H.rec_a;
+        A.rec_b = H.rec_b;
+        A.n_a = H.n_a;
+        A.host_block = g->pin_out_dev[r];
+        A.off_chosen = S.L.chosen;
+        A.off_cell_cost = S.L.cell_cost;
+        A.off_picks = S.L.picks;
+        GHIP(hipSetDevice(g->dev[r]));
+        int lrc = pdmpc_launch_group_cells(&A, (void*)g->stream[r]);
+        if (!lrc && (r == 0 || ch.n_picks > 0)) lrc = pdmpc_launch_group_gather(&A, (void*)g->stream[r]);
+        if (lrc) return gfail(PDMPC_ERR_HIP, std::string("a choice kernel's launch failed: ") + hipGetErrorString((hipError_t)lrc));
+    }
+    g->xchg[1] += (int64_t)S.L.bytes;
+    return PDMPC_OK;
+}
+
+// a choice the host has waited for into the caller's arrays; a record that is no planning result fails it as it fails the choice on the host
+int deliver_group_choice(const pdmpc_group* g, const StagedChoice& S, int32_t* chosen, double* cell_cost, pdmpc_vehicle_out* picks) {
+    const pdmpc_choice& ch = *S.ch;
+    const unsigned char* blk = g->pin_out;
+    const int32_t* counters = (const int32_t*)blk;
+    if (counters[PDMPC_CHOICE_OVERFLOW] || counters[PDMPC_CHOICE_TIMED_OUT] || counters[PDMPC_CHOICE_OTHER])
+        return gfail(PDMPC_ERR_HIP, "a result record carries an error status: not a planning result");
+    if (chosen && ch.n_graphs > 0) std::memcpy(chosen, blk + S.L.chosen, (size_t)ch.n_graphs * sizeof(int32_t));
+    if (cell_cost && ch.n_cells > 0) std::memcpy(cell_cost, blk + S.L.cell_cost, (size_t)ch.n_cells * sizeof(double));
+    if (ch.n_picks > 0) std::memcpy(picks, blk + S.L.picks, (size_t)ch.n_picks * sizeof(pdmpc_vehicle_out));
+    return PDMPC_OK;
+}
+
+int checked_group_choice(int32_t n, const pdmpc_choice* ch) {
+    std::string err;
+    const int rc = check_choice(n, ch, err);
+    return rc ? gfail(rc, err) : PDMPC_OK;
+}
+
+// the bank whose records the ranks hold, or a refusal
+int resident_plan(pdmpc_group* g, int bank, const char* who, const pdmpc_group::Plan** L) {
+    if (bank < 0 || (size_t)bank >= g->plans.size() || !g->plans[(size_t)bank].valid || bank != g->resident_bank)
+        return gfail(PDMPC_ERR_INVALID, std::string(who) + ": the ranks hold the records of the bank launched last; launch this bank first");
+    *L = &g->plans[(size_t)bank];
+    return PDMPC_OK;
+}
+
+inline void new_call(pdmpc_group* g) { g->xchg[0] = g->xchg[1] = g->xchg[2] = g->xchg[3] = 0; }  // pdmpc_group_last_exchange counts from here
+inline bool known_mode(int mode) { return mode == PDMPC_SHARD_AUTO || mode == PDMPC_SHARD_COMPONENTS || mode == PDMPC_SHARD_LEVELS; }
 
 }  // namespace
 
@@ -551,6 +751,7 @@ int pdmpc_group_create_ex(const pdmpc_config* config, int32_t n_devices, const i
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return gfail(PDMPC_ERR_NO_DEVICE, "no HIP device visible: this backend has no CPU fallback");
     DeviceScope keep;
     pdmpc_group* g = new pdmpc_group();
+    g->Hp = config->Hp;
     bool repeated = false;
     for (int r = 0; r < n_devices; ++r) {
         const int d = devices ? devices[r] : r;
@@ -578,6 +779,8 @@ int pdmpc_group_create_ex(const pdmpc_config* config, int32_t n_devices, const i
     }
     g->send.assign((size_t)n_devices, nullptr);
     g->recv.assign((size_t)n_devices, nullptr);
+    for (auto* v : {&g->esend, &g->erecv, &g->lists, &g->made, &g->pin_out_dev}) v->assign((size_t)n_devices, nullptr);
+    g->placed.assign((size_t)n_devices, nullptr);
     for (int r = 0; r < n_devices; ++r) {
         pdmpc_config c = *config;
         c.device = g->dev[(size_t)r];
@@ -593,6 +796,10 @@ int pdmpc_group_create_ex(const pdmpc_config* config, int32_t n_devices, const i
         void* st = nullptr;
         (void)pdmpc_stream(h, &st);
         g->stream.push_back((hipStream_t)st);
+        void* records = nullptr;  // (allocated with the handle for max_vehicles records: it does not move)
+        size_t nbytes = 0;
+        (void)pdmpc_result_device_buffer(h, &records, &nbytes);
+        g->rec.push_back((const pdmpc_vehicle_out*)records);
     }
     if (g->coll == &kCollRccl) {
         g->comm.assign((size_t)n_devices, nullptr);
@@ -650,7 +857,12 @@ int pdmpc_group_destroy(pdmpc_group* g) {
         if (r < g->dev.size()) (void)hipSetDevice(g->dev[r]);
         if (g->send[r]) (void)hipFree(g->send[r]);
         if (g->recv[r]) (void)hipFree(g->recv[r]);
+        for (auto* v : {&g->esend, &g->erecv, &g->lists, &g->made})
+            if (r < v->size() && (*v)[r]) (void)hipFree((*v)[r]);
+        if (r < g->placed.size() && g->placed[r]) (void)hipFree(g->placed[r]);
     }
+    if (g->pin_lists) (void)hipHostFree(g->pin_lists);
+    if (g->pin_out) (void)hipHostFree(g->pin_out);
     if (g->shared_buf) {
         (void)hipSetDevice(g->dev[0]);
         (void)hipFree(g->shared_buf);
@@ -686,10 +898,17 @@ int pdmpc_group_plan_step(pdmpc_group* g, int32_t n, const pdmpc_vehicle_in* in,
     if (mode != PDMPC_SHARD_AUTO && mode != PDMPC_SHARD_COMPONENTS && mode != PDMPC_SHARD_LEVELS) return gfail(PDMPC_ERR_INVALID, "unknown sharding mode");
     if (n == 0) return PDMPC_OK;
     DeviceScope keep;
+    new_call(g);
     // The reference's tree is unbounded (Tree.m:54-70): a step in which some search outgrew its arena is planned again with arenas twice
-    // as large on every device (as pdmpc_plan_step does for one).
+    // as large on every device (as pdmpc_plan_step does for one) -- a sampled step with the seeds its first pack consumed.
+    const bool sampled = g->seeds_set;
+    const std::vector<uint32_t> seeds = g->next_seeds;
     for (;;) {
         const auto t0 = clk::now();
+        if (sampled) {
+            g->next_seeds = seeds;
+            g->seeds_set = true;
+        }
         GRC(group_pack(g, 0, n, in, pred_offset, pred_index, fallback_shapes, weights, mode));
         GRC(group_launch(g, 0));
         GRC(group_fetch(g, 0, n, out));
@@ -697,26 +916,10 @@ int pdmpc_group_plan_step(pdmpc_group* g, int32_t n, const pdmpc_vehicle_in* in,
         bool overflow = false;
         for (int i = 0; i < n; ++i) overflow = overflow || out[i].status == PDMPC_ARENA_OVERFLOW;
         if (!overflow) return PDMPC_OK;
-        // (the devices' arenas may differ after a failed attempt to grow: the step fits when the SMALLEST arena holds every search)
-        int32_t nodes = 0;
-        for (pdmpc_handle* h : g->h) {
-            int32_t nr = 0;
-            GRC(pdmpc_arena_nodes(h, &nr, nullptr));
-            nodes = nodes ? std::min(nodes, nr) : nr;
-        }
-        if ((int64_t)nodes * 2 > (1ll << 30)) return PDMPC_OK;  // (statuses tell)
-        for (size_t r = 0; r < g->h.size(); ++r) {
-            int32_t nr = 0;
-            GRC(pdmpc_arena_nodes(g->h[r], &nr, nullptr));
-            if (nr >= nodes * 2) continue;
-            if (pdmpc_grow_arena(g->h[r], nodes * 2) != PDMPC_OK) {
-                // no room to grow on this device: the records keep their PDMPC_ARENA_OVERFLOW statuses AND the error string says why
-                char b[160];
-                snprintf(b, sizeof b, "pdmpc_group_plan_step: the arenas of rank %zu (device %d) cannot grow to %d nodes per vehicle", r, g->dev[r], nodes * 2);
-                pdmpc_set_last_error(b);
-                return PDMPC_OK;
-            }
-        }
+        bool grown = false;
+        GRC(grow_all(g, "pdmpc_group_plan_step", grown));
+        if (!grown) return PDMPC_OK;  // (statuses tell)
+        g->xchg[3] += 1;
     }
 }
 
@@ -733,12 +936,14 @@ int pdmpc_group_pack_step(pdmpc_group* g, int32_t bank, int32_t n, const pdmpc_v
 int pdmpc_group_launch(pdmpc_group* g, int32_t bank) {
     if (!g || bank < 0) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_launch: bad argument");
     DeviceScope keep;
+    new_call(g);
     return group_launch(g, bank);
 }
 
 int pdmpc_group_fetch(pdmpc_group* g, int32_t bank, int32_t n, pdmpc_vehicle_out* out) {
     if (!g || bank < 0 || (n > 0 && !out)) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_fetch: bad argument");
     DeviceScope keep;
+    new_call(g);
     return group_fetch(g, bank, n, out);
 }
 
@@ -757,6 +962,196 @@ int pdmpc_group_last_timing(pdmpc_group* g, double* ms6) {
     if (!g || !ms6) return gfail(PDMPC_ERR_INVALID, "null argument");
     for (int i = 0; i < 6; ++i) ms6[i] = g->timing[i];
     return PDMPC_OK;
+}
+
+int pdmpc_group_last_exchange(pdmpc_group* g, int64_t* out4) {
+    if (!g || !out4) return gfail(PDMPC_ERR_INVALID, "null argument");
+    for (int i = 0; i < 4; ++i) out4[i] = g->xchg[i];
+    return PDMPC_OK;
+}
+
+int pdmpc_group_route_host(int32_t n, const int32_t* pred_offset, const int32_t* pred_index, const double* weights, int32_t n_devices, int32_t mode, int32_t* rank,
+                           int32_t* position) {
+    if (n < 0 || n_devices < 1 || (n > 0 && (!rank || !position))) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_route_host: bad argument");
+    if (pred_offset && !pred_index) return gfail(PDMPC_ERR_INVALID, "pred_index missing");
+    if (!known_mode(mode)) return gfail(PDMPC_ERR_INVALID, "unknown sharding mode");
+    Partition P;
+    GRC(make_partition(n, pred_offset, pred_index, weights, n_devices, mode, P));
+    GroupRoute R;
+    route_partition(P, n, R);
+    for (int v = 0; v < n; ++v) {
+        rank[v] = R.rank[(size_t)v];
+        position[v] = R.pos[(size_t)v];
+    }
+    return PDMPC_OK;
+}
+
+int pdmpc_group_set_step_seeds(pdmpc_group* g, int32_t n, const uint32_t* seeds) {
+    if (!g || n < 0 || (n > 0 && !seeds)) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_set_step_seeds: bad argument");
+    g->next_seeds.assign(seeds, seeds + n);
+    g->seeds_set = true;
+    return PDMPC_OK;
+}
+
+int pdmpc_group_plan_step_lean(pdmpc_group* g, int32_t n, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index,
+                               const pdmpc_polygon_set* fallback_shapes, const double* weights, int32_t mode, int32_t* status, double* final_cost) {
+    if (!g || n < 0 || (n > 0 && (!in || !status || !final_cost))) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_plan_step_lean: null argument");
+    if (pred_offset && !pred_index) return gfail(PDMPC_ERR_INVALID, "pred_index missing");
+    if (!known_mode(mode)) return gfail(PDMPC_ERR_INVALID, "unknown sharding mode");
+    DeviceScope keep;
+    new_call(g);
+    const auto t0 = clk::now();
+    GRC(group_pack(g, 0, n, in, pred_offset, pred_index, fallback_shapes, weights, mode));
+    if (n == 0) return PDMPC_OK;
+    const GroupRoute& R = g->plans[0].route;
+    const size_t world = g->h.size(), block = ((size_t)R.per + 1) * sizeof(GroupEntry);
+    GRC(ensure_pin_out(g, world * block));
+    for (;;) {
+        // every rank writes the entries of the records it holds straight into host memory: no record and no collective ends this step
+        const auto t2 = clk::now();
+        GRC(group_enqueue(g, 0, false));
+        GRC(enqueue_entries(g, [&](size_t r) { return held_of_bank(g, g->plans[0], r); }, [&](size_t r) { return g->pin_out_dev[r] + r * block; }));
+        const auto t3 = clk::now();
+        GRC(group_wait(g));
+        GRC(group_launched(g, 0, false));
+        const auto t4 = clk::now();
+        g->xchg[1] += (int64_t)(((size_t)n + world) * sizeof(GroupEntry));
+        const GroupEntry* ent = (const GroupEntry*)g->pin_out;
+        bool overflow = false;
+        for (int v = 0; v < n; ++v) {
+            const GroupEntry& e = ent[R.entry(v)];
+            status[v] = e.status;
+            final_cost[v] = e.cost;
+            overflow = overflow || e.status == PDMPC_ARENA_OVERFLOW;
+        }
+        g->timing[3] = ms_between(t2, t3);
+        g->timing[4] = ms_between(t3, t4);
+        g->timing[5] = ms_between(t4, clk::now());
+        g->timing[0] = ms_between(t0, clk::now());
+        if (!overflow) return PDMPC_OK;
+        bool grown = false;
+        GRC(grow_all(g, "pdmpc_group_plan_step_lean", grown));
+        if (!grown) return PDMPC_OK;  // (statuses tell)
+        g->xchg[3] += 1;
+    }
+}
+
+int pdmpc_group_fetch_records_at(pdmpc_group* g, int32_t count, const int32_t* vehicles, pdmpc_vehicle_out* out) {
+    if (!g || count < 0 || (count > 0 && (!vehicles || !out))) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_fetch_records_at: null argument");
+    const pdmpc_group::Plan* L = nullptr;
+    GRC(resident_plan(g, g->resident_bank, "pdmpc_group_fetch_records_at", &L));
+    for (int i = 0; i < count; ++i)
+        if (vehicles[i] < 0 || vehicles[i] >= L->n) return gfail(PDMPC_ERR_INVALID, "vehicle index outside the packed step");
+    DeviceScope keep;
+    new_call(g);
+    const auto t4 = clk::now();
+    if (count == 0) return PDMPC_OK;
+    GRC(ensure_pin_out(g, (size_t)count * kRec));
+    // each wanted record from the rank that holds it, on that rank's stream
+    for (int i = 0; i < count; ++i) {
+        const size_t r = (size_t)L->route.rank[(size_t)vehicles[i]];
+        const int32_t p = L->route.pos[(size_t)vehicles[i]];
+        const Held H = held_of_bank(g, *L, r);
+        const pdmpc_vehicle_out* src = p < H.n_a ? H.rec_a + p : H.rec_b + (p - H.n_a);
+        GHIP(hipSetDevice(g->dev[r]));
+        GHIP(hipMemcpyAsync(g->pin_out + (size_t)i * kRec, src, kRec, hipMemcpyDeviceToHost, g->stream[r]));
+    }
+    GRC(group_wait(g));
+    g->xchg[1] += (int64_t)((size_t)count * kRec);
+    std::memcpy(out, g->pin_out, (size_t)count * kRec);
+    g->timing[5] = ms_between(t4, clk::now());
+    return PDMPC_OK;
+}
+
+int pdmpc_group_plan_step_chosen(pdmpc_group* g, int32_t n, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index,
+                                 const pdmpc_polygon_set* fallback_shapes, const double* weights, int32_t mode, const pdmpc_choice* ch, int32_t* chosen,
+                                 double* cell_cost, pdmpc_vehicle_out* picks) {
+    if (!g || n < 0 || (n > 0 && !in) || (ch && ch->n_picks > 0 && !picks)) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_plan_step_chosen: null argument");
+    if (pred_offset && !pred_index) return gfail(PDMPC_ERR_INVALID, "pred_index missing");
+    if (!known_mode(mode)) return gfail(PDMPC_ERR_INVALID, "unknown sharding mode");
+    GRC(checked_group_choice(n, ch));
+    DeviceScope keep;
+    new_call(g);
+    const auto t0 = clk::now();
+    GRC(group_pack(g, 0, n, in, pred_offset, pred_index, fallback_shapes, weights, mode));
+    const pdmpc_group::Plan& L = g->plans[0];
+    const StagedChoice S(*ch);
+    GRC(stage_group_choice(g, L.route, S));  // (once: a step that is planned again with larger arenas chooses on the same lists)
+    for (;;) {
+        const auto t2 = clk::now();
+        GRC(group_enqueue(g, 0, false));
+        GRC(enqueue_group_choice(g, L.route, S, [&](size_t r) { return held_of_bank(g, L, r); }));
+        const auto t3 = clk::now();
+        GRC(group_wait(g));
+        GRC(group_launched(g, 0, false));
+        g->timing[3] = ms_between(t2, t3);
+        g->timing[4] = ms_between(t3, clk::now());
+        if (!((const int32_t*)g->pin_out)[PDMPC_CHOICE_OVERFLOW]) break;
+        bool grown = false;
+        GRC(grow_all(g, "pdmpc_group_plan_step_chosen", grown));
+        if (!grown) break;  // (the choice fails below: a record that outgrew its arena is no planning result)
+        g->xchg[3] += 1;
+    }
+    const auto t4 = clk::now();
+    const int rc = deliver_group_choice(g, S, chosen, cell_cost, picks);
+    g->timing[5] = ms_between(t4, clk::now());
+    g->timing[0] = ms_between(t0, clk::now());
+    return rc;
+}
+
+int pdmpc_group_choose_resident(pdmpc_group* g, int32_t bank, int32_t n, const pdmpc_choice* ch, int32_t* chosen, double* cell_cost, pdmpc_vehicle_out* picks) {
+    if (!g || (ch && ch->n_picks > 0 && !picks)) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_choose_resident: null argument");
+    GRC(checked_group_choice(n, ch));
+    const pdmpc_group::Plan* L = nullptr;
+    GRC(resident_plan(g, bank, "pdmpc_group_choose_resident", &L));
+    if (n != L->n) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_choose_resident: the bank holds another number of vehicles");
+    DeviceScope keep;
+    new_call(g);
+    const StagedChoice S(*ch);
+    GRC(stage_group_choice(g, L->route, S));
+    GRC(enqueue_group_choice(g, L->route, S, [&](size_t r) { return held_of_bank(g, *L, r); }));
+    GRC(group_wait(g));
+    return deliver_group_choice(g, S, chosen, cell_cost, picks);
+}
+
+int pdmpc_group_debug_choose(pdmpc_group* g, int32_t n, const pdmpc_vehicle_out* records, const int32_t* rank_of, const pdmpc_choice* ch, int32_t* chosen,
+                             double* cell_cost, pdmpc_vehicle_out* picks) {
+    if (!g || n < 0 || (n > 0 && (!records || !rank_of)) || (ch && ch->n_picks > 0 && !picks)) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_debug_choose: null argument");
+    GRC(checked_group_choice(n, ch));
+    GroupRoute R;
+    const size_t world = g->h.size();
+    if (!route_placed(n, rank_of, (int)world, R)) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_debug_choose: rank_of outside [-1, world)");
+    DeviceScope keep;
+    // the records where the route says they are: a rank's own in ascending order; the records of every rank (rank_of == -1) behind
+    // them on EVERY rank, as the level exchange leaves a shared component's (rank 0 is their holder)
+    std::vector<pdmpc_vehicle_out> own, everywhere;
+    for (int v = 0; v < n; ++v)
+        if (rank_of[v] < 0) everywhere.push_back(records[v]);
+    const size_t want = (size_t)R.per + everywhere.size() + 1;
+    if (want > g->placed_cap) {
+        for (size_t r = 0; r < world; ++r) {
+            GHIP(hipSetDevice(g->dev[r]));
+            if (g->placed[r]) (void)hipFree(g->placed[r]);
+            g->placed[r] = nullptr;
+            GHIP(hipMalloc((void**)&g->placed[r], want * 2 * kRec));
+        }
+        g->placed_cap = want * 2;
+    }
+    for (size_t r = 0; r < world; ++r) {
+        own.clear();
+        for (int v = 0; v < n; ++v)
+            if (rank_of[v] == (int32_t)r) own.push_back(records[v]);
+        GHIP(hipSetDevice(g->dev[r]));
+        if (!own.empty()) GHIP(hipMemcpy(g->placed[r], own.data(), own.size() * kRec, hipMemcpyHostToDevice));
+        if (!everywhere.empty()) GHIP(hipMemcpy(g->placed[r] + own.size(), everywhere.data(), everywhere.size() * kRec, hipMemcpyHostToDevice));
+    }
+    // ... and from here on exactly what a step's choice runs
+    new_call(g);
+    const StagedChoice S(*ch);
+    GRC(stage_group_choice(g, R, S));
+    GRC(enqueue_group_choice(g, R, S, [&](size_t r) { return held_placed(g, R, r); }));
+    GRC(group_wait(g));
+    return deliver_group_choice(g, S, chosen, cell_cost, picks);
 }
 
 }  // extern "C"

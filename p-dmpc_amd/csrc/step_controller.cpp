@@ -44,17 +44,41 @@ int bound_with_room(std::vector<int32_t>& off, std::vector<double>& x, std::vect
     return rc;
 }
 
-// Plans a problem that has been built -- a controller's, its batch of prioritizations or a sweep's -- on h: last step's work as the
+// the twin over a group of each backend call a built problem is planned with
+using PlanRecords = int (*)(pdmpc_handle*, int32_t, const pdmpc_vehicle_in*, const int32_t*, const int32_t*, const pdmpc_polygon_set*, pdmpc_vehicle_out*);
+using PlanLean = int (*)(pdmpc_handle*, int32_t, const pdmpc_vehicle_in*, const int32_t*, const int32_t*, const pdmpc_polygon_set*, int32_t*, double*);
+using PlanChosen = int (*)(pdmpc_handle*, int32_t, const pdmpc_vehicle_in*, const int32_t*, const int32_t*, const pdmpc_polygon_set*, const pdmpc_choice*, int32_t*, double*,
+                           pdmpc_vehicle_out*);
+inline auto group_twin(PlanRecords) { return &pdmpc_group_plan_step; }
+inline auto group_twin(PlanLean) { return &pdmpc_group_plan_step_lean; }
+inline auto group_twin(PlanChosen) { return &pdmpc_group_plan_step_chosen; }
+
+// Plans a problem that has been built -- a controller's, its batch of prioritizations or a sweep's -- on `on`: last step's work as the
 // expected work of this one (pops_of(slot) + 1: heavy searches are dispatched first; weigh = false: no step has been planned yet), the
 // slots' seeds for the next pack if the optimizer is the sampled one (a sampled bank; nothing for the graph search), the backend call
 // `call` with the problem's arrays and `rest` (pdmpc_plan_step, _lean or _chosen), and its parts (pdmpc_last_call_timing) into timing[1..3].
+// Over a group the same through the call's twin: the expected work is the partition's weights too, the seeds travel with the
+// sub-problems, and the parts are pdmpc_group_last_timing's (pack incl. the partition; enqueue; wait and read-back).
 template <class Pops, class Call, class... Rest>
-int plan_built(pdmpc_handle* h, StepProblem& P, bool weigh, Pops&& pops_of, int optimizer, double* timing, Call call, Rest... rest) {
+int plan_built(const PlanTarget& on, StepProblem& P, bool weigh, Pops&& pops_of, int optimizer, double* timing, Call call, Rest... rest) {
+    pdmpc_handle* h = on.h;
     if (weigh) {
         const int N = P.n();
         P.weights.resize((size_t)N);
         for (int s = 0; s < N; ++s) P.weights[(size_t)s] = pops_of(s) + 1.0;
-        (void)pdmpc_set_step_weights(h, N, P.weights.data());
+        if (!on.g) (void)pdmpc_set_step_weights(h, N, P.weights.data());
+    }
+    if (on.g) {
+        if (optimizer == PDMPC_OPTIMIZER_SAMPLED)
+            if (const int rc = pdmpc_group_set_step_seeds(on.g, (int32_t)P.seeds.size(), P.seeds.data())) return cfail(nullptr, rc, pdmpc_last_error());
+        if (const int rc = P.plan_on_group(group_twin(call), on.g, weigh ? P.weights.data() : nullptr, on.mode, rest...)) return cfail(nullptr, rc, pdmpc_last_error());
+        double ms[6] = {0, 0, 0, 0, 0, 0};
+        if (pdmpc_group_last_timing(on.g, ms) == PDMPC_OK) {
+            timing[1] = ms[1] + ms[2];
+            timing[2] = ms[3];
+            timing[3] = ms[4] + ms[5];
+        }
+        return PDMPC_OK;
     }
     if (optimizer == PDMPC_OPTIMIZER_SAMPLED)
         if (const int rc = pdmpc_set_step_seeds(h, (int32_t)P.seeds.size(), P.seeds.data())) return cfail(nullptr, rc, pdmpc_last_error());
@@ -376,6 +400,7 @@ int build_members(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, B
 }
 
 // ---- how a step ends that the controller takes alone
+PlanTarget target_of(const pdmpc_controller* c) { return {c->h, c->group, c->group_mode}; }
 // a failure inside a step the controller takes alone is the controller's error too (the global message has it either way)
 int own(pdmpc_controller* c, int rc) {
     if (rc) c->err = g_cerr;
@@ -405,7 +430,7 @@ int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, boo
     c->timing[0] = ms_since(t);
     const int N = c->x.prob.n();
     auto plan = [&](auto call, auto... rest) {
-        const int rc = plan_built(c->h, c->x.prob, c->tr.last_pops.size() == (size_t)c->sc.n, [&](int s) { return c->tr.last_pops[(size_t)c->x.vehicle[(size_t)s]]; }, c->optimizer,
+        const int rc = plan_built(target_of(c), c->x.prob, c->tr.last_pops.size() == (size_t)c->sc.n, [&](int s) { return c->tr.last_pops[(size_t)c->x.vehicle[(size_t)s]]; }, c->optimizer,
                                   c->timing, call, rest...);
         t = std::chrono::steady_clock::now();
         return own(c, rc);
@@ -438,7 +463,7 @@ int batch_step(pdmpc_controller* c, std::chrono::steady_clock::time_point t, boo
         std::vector<int32_t> want((size_t)c->sc.n);
         for (int s = 0; s < c->sc.n; ++s) want[(size_t)s] = kept_slot_at(c, follow_own, s);
         c->out.resize((size_t)c->sc.n);
-        rc = pdmpc_fetch_records_at(c->h, c->sc.n, want.data(), c->out.data());
+        rc = c->group ? pdmpc_group_fetch_records_at(c->group, c->sc.n, want.data(), c->out.data()) : pdmpc_fetch_records_at(c->h, c->sc.n, want.data(), c->out.data());
         if (rc) return cfail(c, rc, pdmpc_last_error());
     } else {
         c->x.out.resize((size_t)N);
@@ -750,7 +775,7 @@ int pdmpc_controller_step(pdmpc_controller* c) {
     c->timing[0] = ms_since(t);
     c->timing[4] = 0;
     c->out.resize(c->sc.n);
-    rc = plan_built(c->h, c->prob, c->tr.last_pops.size() == (size_t)c->sc.n, [&](int s) { return c->tr.last_pops[(size_t)c->pri.order[(size_t)s]]; }, c->optimizer, c->timing,
+    rc = plan_built(target_of(c), c->prob, c->tr.last_pops.size() == (size_t)c->sc.n, [&](int s) { return c->tr.last_pops[(size_t)c->pri.order[(size_t)s]]; }, c->optimizer, c->timing,
                     pdmpc_plan_step, c->out.data());
     if (rc) return own(c, rc);
     return apply_and_account(c);
@@ -1001,6 +1026,8 @@ const pdmpc_vehicle_out* pdmpc_controller_records(pdmpc_controller* c) { return 
 // device and ONE pdmpc_plan_step for all of them.  Sweep slots are the members' problems one after the other, each in its own slot order.
 struct pdmpc_sweep {
     pdmpc_handle* h = nullptr;
+    pdmpc_group* group = nullptr;  // pdmpc_sweep_set_group: the concatenated problems are planned over this group (h is its rank 0)
+    int32_t group_mode = PDMPC_SHARD_AUTO;
     std::vector<pdmpc_controller*> members;
     std::vector<int32_t> first;  // [M + 1] member m's first sweep slot (= its first vehicle among the concatenated vehicles)
     bool broken = false;         // a step failed half way: the members have advanced unevenly
@@ -1037,6 +1064,15 @@ struct pdmpc_sweep {
 
 namespace {
 int N_of(const pdmpc_sweep* s) { return s->first.back(); }
+PlanTarget target_of(const pdmpc_sweep* s) { return {s->h, s->group, s->group_mode}; }
+// what pdmpc_controller_set_group and pdmpc_sweep_set_group refuse: an unknown sharding mode, a group whose rank 0 is another handle
+int group_refusal(pdmpc_group* g, int32_t mode, pdmpc_handle* h, const char* who) {
+    if (mode != PDMPC_SHARD_AUTO && mode != PDMPC_SHARD_COMPONENTS && mode != PDMPC_SHARD_LEVELS) return cfail(nullptr, PDMPC_ERR_INVALID, std::string(who) + ": unknown sharding mode");
+    pdmpc_handle* h0 = nullptr;
+    if (pdmpc_group_handle(g, 0, &h0) != PDMPC_OK || !h0 || h0 != h)
+        return cfail(nullptr, PDMPC_ERR_INVALID, std::string(who) + ": not created on the handle of the group's rank 0 (pdmpc_group_handle(group, 0))");
+    return PDMPC_OK;
+}
 // more plans than the handle's max_vehicles (without a handle: any number) are refused with `text`
 int refuse_beyond_handle(pdmpc_handle* h, int64_t plans, const char* text) {
     pdmpc_config hc{};
@@ -1239,7 +1275,7 @@ int sweep_batch_step(pdmpc_sweep* s, std::chrono::steady_clock::time_point t, co
     };
     concatenate_choices(s, how);
     const pdmpc_choice ch = X.all.view();
-    int rc = plan_built(s->h, X.prob, true, pops_of, s->members[0]->optimizer, s->timing, pdmpc_plan_step_chosen, &ch, X.chosen.data(), X.cell_cost.data(), X.picks.data());
+    int rc = plan_built(target_of(s), X.prob, true, pops_of, s->members[0]->optimizer, s->timing, pdmpc_plan_step_chosen, &ch, X.chosen.data(), X.cell_cost.data(), X.picks.data());
     if (rc) return rc;
     t = std::chrono::steady_clock::now();
     for (size_t m = 0; m < M; ++m) {
@@ -1370,7 +1406,7 @@ int pdmpc_sweep_step(pdmpc_sweep* s) {
         const pdmpc_controller* c = s->members[(size_t)s->member[(size_t)q]];
         return c->tr.last_pops.size() == (size_t)c->sc.n ? c->tr.last_pops[(size_t)c->pri.order[(size_t)s->member_slot[(size_t)q]]] : 0.0;
     };
-    rc = plan_built(s->h, s->prob, true, pops_of, s->members[0]->optimizer, s->timing, pdmpc_plan_step, s->out.data());
+    rc = plan_built(target_of(s), s->prob, true, pops_of, s->members[0]->optimizer, s->timing, pdmpc_plan_step, s->out.data());
     if (rc) return sweep_guard(s, rc);
     t = std::chrono::steady_clock::now();
     rc = sweep_apply(s, s->out.data(), true);
@@ -1380,6 +1416,27 @@ int pdmpc_sweep_step(pdmpc_sweep* s) {
 
 int pdmpc_sweep_run(pdmpc_sweep* s, int32_t n_steps, double* ms) {
     return timed_steps(n_steps, ms, [&] { return pdmpc_sweep_step(s); });
+}
+
+int pdmpc_controller_set_group(pdmpc_controller* c, pdmpc_group* g, int32_t mode) {
+    if (!c) return cfail(c, PDMPC_ERR_INVALID, "null argument");
+    if (g)
+        if (const int rc = group_refusal(g, mode, c->h, "pdmpc_controller_set_group")) return own(c, rc);
+    c->group = g;
+    c->group_mode = g ? mode : PDMPC_SHARD_AUTO;
+    return PDMPC_OK;
+}
+
+int pdmpc_sweep_set_group(pdmpc_sweep* s, pdmpc_group* g, int32_t mode) {
+    if (!s) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
+    if (g) {
+        if (const int rc = group_refusal(g, mode, s->h, "pdmpc_sweep_set_group")) return rc;
+        for (const pdmpc_controller* c : s->members)
+            if (const int rc = group_refusal(g, mode, c->h, "pdmpc_sweep_set_group: a member")) return rc;
+    }
+    s->group = g;
+    s->group_mode = g ? mode : PDMPC_SHARD_AUTO;
+    return PDMPC_OK;
 }
 
 int pdmpc_sweep_last_timing(pdmpc_sweep* s, double* ms6) {

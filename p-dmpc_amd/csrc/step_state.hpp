@@ -154,6 +154,8 @@ struct Centralized {
 
 struct pdmpc_controller {
     pdmpc_handle* h = nullptr;
+    pdmpc_group* group = nullptr;           // pdmpc_controller_set_group: built problems are planned over this group (h is its rank 0)
+    int32_t group_mode = PDMPC_SHARD_AUTO;
     Scenario sc;       // written by pdmpc_controller_create / _set_reachability
     Traffic tr;        // carried from step to step: written by pdmpc_controller_apply
     StepInputs in;     // rewritten every step (begin_step, the step preparation's coupling)

@@ -70,6 +70,11 @@ struct StepProblem {
     int plan(Call call, pdmpc_handle* h, Rest... rest) const {
         return call(h, n(), in.data(), pred_offset.data(), pred_index.data(), fb.data(), rest...);
     }
+    // ... and its twin over a group: call(g, n_slots, in, pred_offset, pred_index, fallback, weights, mode, rest ...)
+    template <class Call, class... Rest>
+    int plan_on_group(Call call, pdmpc_group* g, const double* expected_work, int32_t mode, Rest... rest) const {
+        return call(g, n(), in.data(), pred_offset.data(), pred_index.data(), fb.data(), expected_work, mode, rest...);
+    }
 };
 // ... and the same five as every *_problem entry point hands them out
 inline void expose(const StepProblem& P, int32_t* n_slots, const pdmpc_vehicle_in** in, const int32_t** pred_offset, const int32_t** pred_index, const pdmpc_polygon_set** fallback) {
@@ -79,6 +84,13 @@ inline void expose(const StepProblem& P, int32_t* n_slots, const pdmpc_vehicle_i
     if (pred_index) *pred_index = P.pred_index.data();
     if (fallback) *fallback = P.fb.data();
 }
+// Where a built problem is planned: on the handle, or (g set) over a group whose rank 0 is that handle (pdmpc_controller_set_group,
+// pdmpc_sweep_set_group).  The step preparation stays on the handle either way.
+struct PlanTarget {
+    pdmpc_handle* h = nullptr;
+    pdmpc_group* g = nullptr;
+    int32_t mode = PDMPC_SHARD_AUTO;
+};
 
 // A prioritization of the step's traffic state: the controller's own, and every instance of an explorative or optimal-priority batch
 struct Instance {

@@ -505,6 +505,22 @@ def group_partition(preds, world, mode=SHARD_AUTO, weights=None):
     return rank_of[:n], level_of[:n], block[:n]
 
 
+def group_route(preds, world, mode=SHARD_AUTO, weights=None):
+    """pdmpc_group_route_host (no GPU needed): per vehicle the rank that holds its record after the launches of the step so
+    partitioned, and its position among the records that rank holds."""
+    L = load_library()
+    n = len(preds)
+    off = np.zeros(n + 1, dtype=np.int32)
+    for i, p in enumerate(preds):
+        off[i + 1] = off[i] + len(p)
+    idx = np.array([j for p in preds for j in p] + [0], dtype=np.int32)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    rank, pos = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(2))
+    rc = L.pdmpc_group_route_host(n, abi.i32p(off), abi.i32p(idx), None if w is None else abi.dp(w), world, mode, abi.i32p(rank), abi.i32p(pos))
+    _check(L, rc, "pdmpc_group_route_host")
+    return rank[:n], pos[:n]
+
+
 class Group:
     """One pdmpc_group: a handle per GPU of this process, bound by an RCCL communicator; plan_step plans a time step over them
     (include/pdmpc.h: pdmpc_group_*)."""
@@ -580,6 +596,68 @@ class Group:
         _check(self.L, self.L.pdmpc_group_last_timing(self.g, t), "pdmpc_group_last_timing")
         return dict(zip(("total", "partition", "pack", "enqueue", "wait", "read_back"), t))
 
+    def rank0(self):
+        """The handle of rank 0 (pdmpc_group_handle) as the object NativeController and NativeSweep take for `handle`: what a
+        controller that is to step on the group (set_group) is created on.  The group owns it."""
+        h = C.c_void_p()
+        _check(self.L, self.L.pdmpc_group_handle(self.g, 0, C.byref(h)), "pdmpc_group_handle")
+        return GroupHandle(self, h)
+
+    def set_step_seeds(self, seeds):
+        """pdmpc_group_set_step_seeds: the next pack makes sampled banks on the ranks (the sampled optimizer), seeds in the caller's order."""
+        s = np.ascontiguousarray(seeds, dtype=np.uint32)
+        _check(self.L, self.L.pdmpc_group_set_step_seeds(self.g, len(s), abi.u32p(s)), "pdmpc_group_set_step_seeds")
+
+    def _group_step_args(self, iters, predecessors, fallback_shapes, weights, mode):
+        arr, off, idx, fb, keep = _step_args(self.Hp, iters, predecessors, fallback_shapes)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        return (self.g, len(iters), arr, abi.i32p(off), abi.i32p(idx), fb, None if w is None else abi.dp(w), mode), (keep, off, idx, w)
+
+    def plan_step_lean(self, iters, predecessors, fallback_shapes=None, weights=None, mode=SHARD_AUTO):
+        """pdmpc_group_plan_step_lean -> (status, final cost) per vehicle; the records stay on the ranks for fetch_records_at."""
+        n = len(iters)
+        args, keep = self._group_step_args(iters, predecessors, fallback_shapes, weights, mode)
+        status, cost = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1))
+        _check(self.L, self.L.pdmpc_group_plan_step_lean(*args, abi.i32p(status), abi.dp(cost)), "pdmpc_group_plan_step_lean")
+        del keep
+        return status[:n], cost[:n]
+
+    def fetch_records_at(self, vehicles):
+        """pdmpc_group_fetch_records_at: the records of these vehicles of the step launched last, each from the rank that holds it."""
+        v = np.ascontiguousarray(vehicles, dtype=np.int32)
+        out = abi.out_array(max(len(v), 1))
+        _check(self.L, self.L.pdmpc_group_fetch_records_at(self.g, len(v), abi.i32p(v), abi.out_ptr(out)), "pdmpc_group_fetch_records_at")
+        return out[: len(v)]
+
+    def _choice_call(self, what, call, choice):
+        chosen, cost, picks = choice.outputs()
+        ch = choice.struct()
+        _check(self.L, call(C.byref(ch), abi.i32p(chosen), abi.dp(cost), abi.out_ptr(picks)), what)
+        return choice.shaped(chosen, cost, picks)
+
+    def plan_step_chosen(self, iters, predecessors, fallback_shapes, choice, weights=None, mode=SHARD_AUTO):
+        """pdmpc_group_plan_step_chosen: the step over the ranks and the choice on them -> (chosen, cell costs, picked records)."""
+        args, keep = self._group_step_args(iters, predecessors, fallback_shapes, weights, mode)
+        out = self._choice_call("pdmpc_group_plan_step_chosen", lambda *tail: self.L.pdmpc_group_plan_step_chosen(*args, *tail), choice)
+        del keep
+        return out
+
+    def choose_resident(self, bank, n, choice):
+        """pdmpc_group_choose_resident: the choice on the records the ranks hold of group bank `bank` (the one launched last)."""
+        return self._choice_call("pdmpc_group_choose_resident", lambda *tail: self.L.pdmpc_group_choose_resident(self.g, bank, n, *tail), choice)
+
+    def debug_choose(self, records, rank_of, choice):
+        """pdmpc_group_debug_choose: the choice over the ranks on records placed by hand (rank_of[v]; -1: on every rank)."""
+        rec = np.ascontiguousarray(records)
+        ro = np.ascontiguousarray(rank_of, dtype=np.int32)
+        return self._choice_call("pdmpc_group_debug_choose", lambda *tail: self.L.pdmpc_group_debug_choose(self.g, len(rec), abi.out_ptr(rec), abi.i32p(ro), *tail), choice)
+
+    def last_exchange(self):
+        """pdmpc_group_last_exchange: the last call's bytes per rank into collectives, bytes to the host, host waits, re-plans."""
+        x = (C.c_int64 * 4)()
+        _check(self.L, self.L.pdmpc_group_last_exchange(self.g, x), "pdmpc_group_last_exchange")
+        return dict(zip(("collective_bytes", "host_bytes", "host_waits", "replans"), (int(v) for v in x)))
+
     def reset_stats(self):
         for r in range(self.n_devices):
             h = C.c_void_p()
@@ -604,6 +682,13 @@ class Group:
         st = abi.Stats()
         _check(self.L, self.L.pdmpc_get_last_stats(h, C.byref(st)), "pdmpc_get_last_stats")
         return {k: getattr(st, k) for k, _ in abi.Stats._fields_}
+
+
+class GroupHandle:
+    """A handle that belongs to a Group (Group.rank0): .h for the calls that take a pdmpc_handle; it keeps its group alive."""
+
+    def __init__(self, group, h):
+        self.group, self.h = group, h
 
 
 class Handle:

@@ -266,6 +266,12 @@ class NativeController:
     def explore_follow_own(self, on=True):
         self._check(self.L.pdmpc_controller_explore_follow_own(self.c, 1 if on else 0), "pdmpc_controller_explore_follow_own")
 
+    def set_group(self, group, mode=0):
+        """pdmpc_controller_set_group: the steps plan over `group` (a backend.Group whose rank 0 handle -- group.rank0() -- the controller
+        was created on) with sharding `mode` (backend.SHARD_*); None: back on the handle.  The state after every step is the handle's."""
+        self._check(self.L.pdmpc_controller_set_group(self.c, group.g if group is not None else None, mode), "pdmpc_controller_set_group")
+        self._group = group  # (kept alive as long as the controller plans on it)
+
     def set_device_choice(self, on=True):
         """explore_run / optimal_run choose and gather the chosen plans on the device, ONE call per step (pdmpc_controller_set_device_choice)."""
         self._check(self.L.pdmpc_controller_set_device_choice(self.c, 1 if on else 0), "pdmpc_controller_set_device_choice")
@@ -415,6 +421,12 @@ class NativeSweep:
         if recs.shape[0] != self.n:
             raise ValueError("a sweep of %d slots takes %d records, not %d" % (self.n, self.n, recs.shape[0]))
         self._check(self.L.pdmpc_sweep_apply(self.s, abi.out_ptr(recs)), "pdmpc_sweep_apply")
+
+    def set_group(self, group, mode=0):
+        """pdmpc_sweep_set_group: the lock-steps plan over `group` (the sweep and its members were created on group.rank0()); None: back
+        on the handle."""
+        self._check(self.L.pdmpc_sweep_set_group(self.s, group.g if group is not None else None, mode), "pdmpc_sweep_set_group")
+        self._group = group
 
     def step(self):
         """One lock-step natively -> every member's records in its own slot order."""
@@ -570,3 +582,6 @@ class NativeSweep:
         t = (C.c_double * 6)()
         self._check(self.L.pdmpc_sweep_last_timing(self.s, t), "pdmpc_sweep_last_timing")
         return dict(zip(TIMING_PARTS, (float(x) for x in t)))
+
+
+Sweep = NativeSweep  # (the short name)

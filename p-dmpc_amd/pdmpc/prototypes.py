@@ -197,6 +197,17 @@ PROTOTYPES = {
     "pdmpc_group_fetch": (INT, [OBJ, I32, I32, VOUT]),
     "pdmpc_group_partition": (INT, [I32, IP, IP, DP, I32, I32, IP, IP, IP]),
     "pdmpc_group_last_timing": (INT, [OBJ, DP]),
+    # ---- the sampled optimizer, the lean read-back and the choice on a group
+    "pdmpc_group_set_step_seeds": (INT, [OBJ, I32, UP]),
+    "pdmpc_group_plan_step_lean": (INT, [OBJ] + STEP + [DP, I32, IP, DP]),
+    "pdmpc_group_fetch_records_at": (INT, [OBJ, I32, IP, VOUT]),
+    "pdmpc_group_plan_step_chosen": (INT, [OBJ] + STEP + [DP, I32] + CHOSEN + [VOUT]),
+    "pdmpc_group_choose_resident": (INT, [OBJ, I32, I32] + CHOSEN + [VOUT]),
+    "pdmpc_group_debug_choose": (INT, [OBJ, I32, VOUT, IP] + CHOSEN + [VOUT]),
+    "pdmpc_group_last_exchange": (INT, [OBJ, P(I64)]),
+    "pdmpc_group_route_host": (INT, [I32, IP, IP, DP, I32, I32, IP, IP]),
+    "pdmpc_controller_set_group": (INT, [OBJ, OBJ, I32]),
+    "pdmpc_sweep_set_group": (INT, [OBJ, OBJ, I32]),
     "pdmpc_last_error": (STR, []),
     "pdmpc_version": (STR, []),
 }
