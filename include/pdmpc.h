@@ -473,6 +473,36 @@ int pdmpc_set_step_seeds(pdmpc_handle* handle, int32_t n_vehicles, const uint32_
 /* the sampled optimizer's device generator on its own: out[i * n + j] = the j-th double of mt19937ar(seeds[i]) (n <= 4000) */
 int pdmpc_debug_random_numbers(pdmpc_handle* handle, int32_t count, const uint32_t* seeds, int32_t n, double* out);
 
+/* The sampled optimizer's expansion budget: n_expansions_max of MonteCarloTreeSearch.m:8, which the reference's constructor (:16-26)
+ * overrides from config/mcts.json -- the optimizer's one quality / time knob.  The budget is the handle's, as its
+ * automaton is: the NEXT pack of a sampled bank reads it and it stays with that bank (resident banks keep the budget they were packed
+ * with; a re-plan after a watchdog time-out keeps it too).  A slot then draws the first Hp * budget numbers of mt19937ar(seed).
+ * PDMPC_SAMPLED_BUDGET_DEFAULT runs pdmpc_sampled_kernel exactly as before; any other budget runs pdmpc_sampled_budget_kernel, whose
+ * tree lives in LDS where it fits and in a per-handle HBM buffer otherwise (allocated by the pack; PDMPC_ERR_CAPACITY if that fails).
+ * PDMPC_SAMPLED_BUDGET_MAX keeps node ids in 16 bits (nodes <= 1 + budget + Hp - 1) and a slot's tree at about 590 KB.
+ * PDMPC_ERR_INVALID for a NULL handle or pointer and for a budget outside 1..PDMPC_SAMPLED_BUDGET_MAX (the handle keeps its budget). */
+#define PDMPC_SAMPLED_BUDGET_DEFAULT 250
+#define PDMPC_SAMPLED_BUDGET_MAX 16384
+int pdmpc_set_sampled_budget(pdmpc_handle* handle, int32_t n_expansions_max);
+int pdmpc_get_sampled_budget(pdmpc_handle* handle, int32_t* n_expansions_max);
+/* The name of the kernel the handle's last sampled launch ran ("" before the first one): a static string. */
+const char* pdmpc_last_sampled_kernel(pdmpc_handle* handle);
+/* The plan of a sampled launch with a budget, without a device: pdmpc_launch_plan_host's query (kind is ignored) and record, and what
+ * the budget adds in extra[4].  PDMPC_SAMPLED_BUDGET_DEFAULT gives pdmpc_launch_plan_host's plan of kind 1, field for field.
+ * extra[0] node capacity: rows of a slot's tree, more than budget + Hp, so that the tree never ends a search the reference would continue;
+ * extra[1] tree_in_lds: 1 if the layout holds the tree (the 80 KB layout first, then the 160 KB one), 0 if it is in HBM; extra[2] bytes of
+ * the HBM tree per slot (0 with the tree in LDS); extra[3] the random-number chunk: numbers drawn at a time (Hp * 250 for the default
+ * kernel, one twist of 312 otherwise).  Errors as for pdmpc_launch_plan_host, and PDMPC_ERR_INVALID for a budget outside
+ * 1..PDMPC_SAMPLED_BUDGET_MAX. */
+int pdmpc_sampled_plan_host(const char* tuning, const pdmpc_launch_query* query, int32_t n_expansions_max, pdmpc_launch_plan* plan,
+                            int64_t* extra);
+/* ... and the same plan for the handle's current bank (the dimensions pdmpc_launch_range reads: the automaton, the device, the packed
+ * obstacle columns) at any budget: where a budget would put this bank's trees.  PDMPC_ERR_INVALID for a NULL argument, an empty bank or a
+ * bank packed without seeds. */
+int pdmpc_sampled_plan_bank(pdmpc_handle* handle, int32_t n_expansions_max, pdmpc_launch_plan* plan, int64_t* extra);
+/* the chunked generator of pdmpc_sampled_budget_kernel on its own: out[i * n + j] = the j-th double of mt19937ar(seeds[i]), any n >= 0 */
+int pdmpc_debug_random_stream(pdmpc_handle* handle, int32_t count, const uint32_t* seeds, int32_t n, double* out);
+
 /* ---- centralized control: one joint graph search over several vehicles (CentralizedController.m:34-46, GraphSearch.do_graph_search
  *      with iter.amount = N; separating-axis checker only) ----
  * n_problems independent joint searches in one launch.  Problem p = vehicles in[problem_offset[p] .. problem_offset[p+1]), 1 to
@@ -756,7 +786,9 @@ int pdmpc_controller_set_lanelet_bounding(pdmpc_controller* c, int32_t on);
 /* The optimizer of the controller's steps (OptimizerType): the graph search (default) or the sampled optimizer
  * (MonteCarloTreeSearch.m, pdmpc_set_step_seeds + the plan calls).  pdmpc_controller_step / _run, _explore_step / _run and
  * _optimal_step / _run follow it.  The sampled optimizer's seeds are time_step + vehicle_index (1-based, MonteCarloTreeSearch.m:31-32,
- * PrioritizedController.m:335-341), the same for every instance of an explorative or optimal batch. */
+ * PrioritizedController.m:335-341), the same for every instance of an explorative or optimal batch.  Its expansion budget is the
+ * handle's (pdmpc_set_sampled_budget; on a group pdmpc_group_set_sampled_budget): the controller, its explorative and optimal steps
+ * and sweeps plan on a handle and so follow the budget that handle has when the step is packed. */
 enum { PDMPC_OPTIMIZER_GRAPH_SEARCH = 0, PDMPC_OPTIMIZER_SAMPLED = 1 };
 int pdmpc_controller_set_optimizer(pdmpc_controller* c, int32_t which); /* PDMPC_OPTIMIZER_*; anything else: PDMPC_ERR_INVALID */
 /* the sampled optimizer's seed per slot of the last built step or batch (pdmpc_controller_build_step / _explore_build / _optimal_build),
@@ -963,6 +995,10 @@ int pdmpc_group_last_timing(pdmpc_group* group, double* ms6);
  * travel with the sub-problems, every rank packs a sampled bank for its share, and the records are pdmpc_plan_step_sampled's on one
  * handle, bit for bit, in every sharding mode.  A seed count other than the packed step's: PDMPC_ERR_INVALID. */
 int pdmpc_group_set_step_seeds(pdmpc_group* group, int32_t n_vehicles, const uint32_t* seeds);
+/* pdmpc_set_sampled_budget on every rank's handle: the sampled packs of the group from now on.  A pack with seeds that finds ranks
+ * with different budgets (one set on a single rank's handle) returns PDMPC_ERR_INVALID.  PDMPC_ERR_INVALID for a NULL group and for a
+ * budget outside 1..PDMPC_SAMPLED_BUDGET_MAX (no rank is changed). */
+int pdmpc_group_set_sampled_budget(pdmpc_group* group, int32_t n_expansions_max);
 /* pdmpc_plan_step_lean / pdmpc_fetch_records_at over the group: status[v] and final_cost[v] = path_nodes[Hp][4] in the caller's order
  * (every rank's kernel writes the 16-byte entries of the records it holds into host memory; no record leaves a device but in the
  * level exchanges of a shared component), then the records wanted, each read from the rank that holds it.  Arena overflow as in

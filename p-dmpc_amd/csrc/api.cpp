@@ -61,12 +61,6 @@ void set_batch_args(const pdmpc_handle* h, const PackedStep& B, int areas_in_lds
     a.work_count = h->d_work_count.p;
 }
 
-// what planning reads of the handle and of a packed bank (launch_plan.hpp: LaunchDims)
-LaunchDims launch_dims(const pdmpc_handle* h, const PackedStep& B) {
-    return {h->cfg.checker, h->cfg.Hp, h->n_trims, h->n_words, h->n_man, h->mask_bytes, h->mi_bytes, h->n_cu, h->device_share, h->arena.max_nodes,
-            B.sampled, B.soup_cap, B.ll_cap, B.cand_cap};
-}
-
 // what a launch reads besides the batch: its plan (set_plan_args), the handle's buffers, the launch's number
 void set_launch_args(pdmpc_handle* h, const PackedStep& B, const LaunchPlan& plan, int first, int count, KernelArgs& a) {
     set_batch_args(h, B, plan.areas_in_lds, a);
@@ -95,6 +89,38 @@ void set_launch_args(pdmpc_handle* h, const PackedStep& B, const LaunchPlan& pla
     a.n_searches = count;
 }
 
+// what sampled_budget_kernel.hip reads of a sampled launch's arguments (its own record: KernelArgs does not grow with the budget)
+SampledBudgetArgs sampled_budget_args(const KernelArgs& a, int budget, int node_cap, uint16_t* tree) {
+    SampledBudgetArgs s{};
+    s.succ_mask = a.succ_mask;
+    s.man_index = a.man_index;
+    s.man_pose = a.man_pose;
+    s.man_area = a.man_area;
+    s.n_trims = a.n_trims;
+    s.n_words = a.n_words;
+    s.n_man = a.n_man;
+    s.Hp = a.Hp;
+    s.checker = a.checker;
+    s.areas_in_lds = a.areas_in_lds;
+    s.veh = a.veh;
+    s.points = a.points;
+    s.pred = a.pred;
+    s.out = a.out;
+    s.done_flag = a.done_flag;
+    s.epoch = a.epoch;
+    s.first = a.first;
+    s.n_searches = a.n_searches;
+    s.reverse_dispatch = a.reverse_dispatch;
+    s.spin_limit = a.spin_limit;
+    s.tree_size = a.tree_size;
+    s.work_count = a.work_count;
+    s.lds = a.lds;
+    s.budget = budget;
+    s.node_cap = node_cap;
+    s.tree = tree;
+    return s;
+}
+
 // The helper boards of a launch with helper workgroups: where its count of finished searches starts (KernelArgs::help_fin_base).
 int prepare_boards(pdmpc_handle* h, int count, uint32_t& fin_base) {
     fin_base = 0;
@@ -120,7 +146,7 @@ int prepare_boards(pdmpc_handle* h, int count, uint32_t& fin_base) {
 // launch ever stall, the watchdog (spin_limit) ends the waiting searches with an error status and plan_packed_growing plans the call
 // again with safe == true, in slices that are resident as a whole (a slice's predecessors are in it or in an earlier slice) -- forward
 // progress then needs no assumption at all.
-int dispatch(const pdmpc_handle* h, const KernelArgs& a, const LaunchPlan& plan, bool search) {
+int dispatch(const pdmpc_handle* h, const KernelArgs& a, const LaunchPlan& plan, bool search, const SampledBudgetArgs* budgeted = nullptr) {
     typedef int (*launcher_t)(const KernelArgs*, int, void*, uint32_t*);
     static const launcher_t launchers[4][2] = {{pdmpc_launch_bulk, pdmpc_launch_bulk_any},
                                                {pdmpc_launch_bulk_wide, pdmpc_launch_bulk_wide_any},
@@ -132,7 +158,12 @@ int dispatch(const pdmpc_handle* h, const KernelArgs& a, const LaunchPlan& plan,
         KernelArgs part = a;
         part.first = a.first + done;
         part.n_searches = std::min(plan.slice, a.n_searches - done);
-        if (!search) {
+        if (budgeted) {
+            SampledBudgetArgs sb = *budgeted;
+            sb.first = part.first;
+            sb.n_searches = part.n_searches;
+            lrc = pdmpc_launch_sampled_budget(&sb, sb.n_searches, (void*)h->stream);
+        } else if (!search) {
             lrc = pdmpc_launch_sampled(&part, part.n_searches, (void*)h->stream);
         } else {
             std::lock_guard<std::mutex> lock(g_lds_mutex);
@@ -157,15 +188,25 @@ int launch_range(pdmpc_handle* h, int first, int count, bool safe) {
     if (search && !safe && policy_reads_chained(h->tune, count, dims.n_cu, dims.device_share))
         for (int i = 0; i < count; ++i) n_chained += B.host.veh[first + i].n_pred > 0 ? 1 : 0;
     LaunchPlan plan;
+    SampledExtra extra;
     std::string err;
-    int rc = plan_launch(h->tune, dims, search ? kPlanSearch : kPlanSampled, count, n_chained, safe, plan, err);
+    // (a sampled bank plans with the budget it was packed with: the first launch, a resident one and the re-plan in slices alike)
+    int rc = search ? plan_launch(h->tune, dims, kPlanSearch, count, n_chained, safe, plan, err) : plan_sampled(h->tune, dims, B.budget, count, safe, plan, extra, err);
     if (rc) return fail(rc, err);
     KernelArgs a{};
     set_launch_args(h, B, plan, first, count, a);
+    const bool budgeted = !search && B.budget != PDMPC_SAMPLED_BUDGET_DEFAULT;
+    SampledBudgetArgs sb{};
+    if (budgeted) {
+        const size_t tree_words = (size_t)extra.node_cap * PDMPC_SB_ROW;
+        if (!extra.tree_in_lds && h->d_sampled_tree.cap < (size_t)B.n_packed * tree_words) return fail(PDMPC_ERR_CAPACITY, "the sampled optimizer's trees in HBM were not allocated by this bank's pack");
+        sb = sampled_budget_args(a, B.budget, extra.node_cap, extra.tree_in_lds ? nullptr : h->d_sampled_tree.p);
+    }
+    if (!search) h->last_sampled_kernel = plan.kernel;
     if (plan.n_helpers > 0 && (rc = prepare_boards(h, count, a.help_fin_base))) return rc;
     if (search && h->tune.debug_lds) fputs(format_bulk_layout(plan, count).c_str(), stderr);
     if ((rc = h->timer.begin(h->stream, search ? kLaunchSearch : kLaunchSampled))) return rc;
-    const int lrc = dispatch(h, a, plan, search);
+    const int lrc = dispatch(h, a, plan, search, budgeted ? &sb : nullptr);
     if (lrc != 0) {
         h->boards_dirty = true;  // (the searches that were to count themselves finished never ran: the next launch starts from cleared counters)
         char buf[256];
@@ -246,6 +287,43 @@ int pdmpc_launch_plan_host(const char* tuning, const pdmpc_launch_query* q, pdmp
     std::string err;
     return failed(plan_query(tuning, *q, *plan, err), err);
 }
+
+int pdmpc_sampled_plan_host(const char* tuning, const pdmpc_launch_query* q, int32_t n_expansions_max, pdmpc_launch_plan* plan, int64_t* extra) {
+    if (!q || !plan || !extra) return fail(PDMPC_ERR_INVALID, "pdmpc_sampled_plan_host: null argument");
+    std::string err;
+    return failed(plan_sampled_query(tuning, *q, n_expansions_max, *plan, extra, err), err);
+}
+
+int pdmpc_sampled_plan_bank(pdmpc_handle* h, int32_t n_expansions_max, pdmpc_launch_plan* plan, int64_t* extra) {
+    if (!h || !plan || !extra) return fail(PDMPC_ERR_INVALID, "pdmpc_sampled_plan_bank: null argument");
+    const PackedStep& B = h->banks[h->bank];
+    if (B.pack_failed || B.n_packed == 0 || !B.sampled) return fail(PDMPC_ERR_INVALID, "pdmpc_sampled_plan_bank: the current bank holds no sampled batch");
+    LaunchPlan p;
+    SampledExtra x;
+    std::string err;
+    if (const int rc = plan_sampled(h->tune, launch_dims(h, B), n_expansions_max, B.n_packed, h->safe_launches, p, x, err)) return fail(rc, err);
+    plan_record(p, false, *plan);
+    extra[0] = x.node_cap;
+    extra[1] = x.tree_in_lds;
+    extra[2] = x.tree_hbm_bytes;
+    extra[3] = x.rand_chunk;
+    return PDMPC_OK;
+}
+
+int pdmpc_set_sampled_budget(pdmpc_handle* h, int32_t n_expansions_max) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "pdmpc_set_sampled_budget: null handle");
+    if (n_expansions_max < 1 || n_expansions_max > PDMPC_SAMPLED_BUDGET_MAX) return fail(PDMPC_ERR_INVALID, "pdmpc_set_sampled_budget: the budget must be in 1..PDMPC_SAMPLED_BUDGET_MAX");
+    h->sampled_budget = n_expansions_max;
+    return PDMPC_OK;
+}
+
+int pdmpc_get_sampled_budget(pdmpc_handle* h, int32_t* n_expansions_max) {
+    if (!h || !n_expansions_max) return fail(PDMPC_ERR_INVALID, "pdmpc_get_sampled_budget: null argument");
+    *n_expansions_max = h->sampled_budget;
+    return PDMPC_OK;
+}
+
+const char* pdmpc_last_sampled_kernel(pdmpc_handle* h) { return h ? h->last_sampled_kernel : ""; }
 
 int pdmpc_destroy(pdmpc_handle* h) {
     if (!h) return PDMPC_OK;
@@ -1097,6 +1175,16 @@ int pdmpc_debug_random_numbers(pdmpc_handle* h, int32_t count, const uint32_t* s
     Staged<const uint32_t> d_seeds{seeds, (size_t)count};
     Staged<double> d_out{out, (size_t)count * n};
     auto launch = [&] { return pdmpc_launch_debug_mt19937(d_seeds.dev.p, count, n, d_out.dev.p, (void*)h->stream); };
+    return run_staged(h, "hipMalloc failed for the generator test", "generator launch failed", launch, d_seeds, d_out);
+}
+
+int pdmpc_debug_random_stream(pdmpc_handle* h, int32_t count, const uint32_t* seeds, int32_t n, double* out) {
+    if (!h || count < 0 || n < 0 || (count > 0 && n > 0 && (!seeds || !out))) return fail(PDMPC_ERR_INVALID, "pdmpc_debug_random_stream: bad argument");
+    if (count == 0 || n == 0) return PDMPC_OK;
+    ON_DEVICE(h->cfg.device);
+    Staged<const uint32_t> d_seeds{seeds, (size_t)count};
+    Staged<double> d_out{out, (size_t)count * n};
+    auto launch = [&] { return pdmpc_launch_debug_random_stream(d_seeds.dev.p, count, n, d_out.dev.p, (void*)h->stream); };
     return run_staged(h, "hipMalloc failed for the generator test", "generator launch failed", launch, d_seeds, d_out);
 }
 

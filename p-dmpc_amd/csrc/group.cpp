@@ -336,6 +336,15 @@ int group_pack(pdmpc_group* g, int bank, int n, const pdmpc_vehicle_in* in, cons
     g->next_seeds.clear();
     g->seeds_set = false;
     if (sampled && (int)seeds.size() != n) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_set_step_seeds: the seeds are not one per vehicle of the packed step");
+    if (sampled) {
+        // one budget for the step: the ranks plan shares of ONE sampled step (pdmpc_group_set_sampled_budget sets them all)
+        int32_t first = 0, other = 0;
+        GRC(pdmpc_get_sampled_budget(g->h[0], &first));
+        for (int r = 1; r < world; ++r) {
+            GRC(pdmpc_get_sampled_budget(g->h[(size_t)r], &other));
+            if (other != first) return gfail(PDMPC_ERR_INVALID, "the ranks of the group have different sampled budgets (pdmpc_group_set_sampled_budget sets every rank)");
+        }
+    }
     L.n = n;
     Partition& P = L.P;
     GRC(make_partition(n, off, idx, weights, world, mode, P));
@@ -990,6 +999,13 @@ int pdmpc_group_set_step_seeds(pdmpc_group* g, int32_t n, const uint32_t* seeds)
     if (!g || n < 0 || (n > 0 && !seeds)) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_set_step_seeds: bad argument");
     g->next_seeds.assign(seeds, seeds + n);
     g->seeds_set = true;
+    return PDMPC_OK;
+}
+
+int pdmpc_group_set_sampled_budget(pdmpc_group* g, int32_t n_expansions_max) {
+    if (!g) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_set_sampled_budget: null group");
+    if (n_expansions_max < 1 || n_expansions_max > PDMPC_SAMPLED_BUDGET_MAX) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_set_sampled_budget: the budget must be in 1..PDMPC_SAMPLED_BUDGET_MAX");
+    for (pdmpc_handle* h : g->h) GRC(pdmpc_set_sampled_budget(h, n_expansions_max));
     return PDMPC_OK;
 }
 

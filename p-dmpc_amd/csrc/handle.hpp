@@ -182,6 +182,7 @@ struct PackedStep {
     int n_packed = 0;
     bool pack_failed = false;  // the last pack into this bank did not finish: nothing to launch or fetch
     bool sampled = false;      // packed with seeds (pdmpc_set_step_seeds): a sampled bank, its launches run the sampled optimizer
+    int budget = PDMPC_SAMPLED_BUDGET_DEFAULT;  // ... with the expansion budget the handle had when it was packed (pdmpc_set_sampled_budget)
     int soup_cap = 0;
     int ll_cap = 0;    // most lanelet-boundary columns of any vehicle (the graph search's reach lists hold one boundary list per step)
     int cand_cap = 0;  // most segments any single edge check can see (one step's soups + the boundary)
@@ -432,6 +433,9 @@ struct pdmpc_handle {
     std::vector<double> next_weights;    // pdmpc_set_step_weights: expected work per vehicle of the NEXT packed step (the caller's order); consumed by that pack
     std::vector<uint32_t> next_seeds;    // pdmpc_set_step_seeds: the sampled optimizer's seed per vehicle of the NEXT packed step (the caller's order) ...
     bool seeds_set = false;              // ... consumed by that pack, which makes its bank a sampled bank
+    int sampled_budget = PDMPC_SAMPLED_BUDGET_DEFAULT;  // pdmpc_set_sampled_budget: what the next pack of a sampled bank gives its bank
+    DevBuf<uint16_t> d_sampled_tree;     // the trees of a sampled bank whose budget does not fit LDS (sampled_budget.h), grown by the pack that needs more
+    const char* last_sampled_kernel = "";  // pdmpc_last_sampled_kernel
     PinnedBuf<double> h_lean;            // fetch_lean: (cost, status) per slot
     DevBuf<double> d_lean;
     PinnedBuf<pdmpc_vehicle_out> h_out;  // pdmpc_fetch_results: the records land in pinned memory (a copy into the caller's pageable array goes through the runtime's staging otherwise)
@@ -450,6 +454,12 @@ struct pdmpc_handle {
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
+
+// what planning reads of the handle and of a packed bank (launch_plan.hpp: LaunchDims)
+inline LaunchDims launch_dims(const pdmpc_handle* h, const PackedStep& B) {
+    return {h->cfg.checker, h->cfg.Hp, h->n_trims, h->n_words, h->n_man, h->mask_bytes, h->mi_bytes, h->n_cu, h->device_share, h->arena.max_nodes,
+            B.sampled, B.soup_cap, B.ll_cap, B.cand_cap};
+}
 
 // hipStreamSynchronize on the launch stream, counted: a bank whose staging copy was queued before is free again (pack_common)
 inline hipError_t sync_stream(pdmpc_handle* h) {

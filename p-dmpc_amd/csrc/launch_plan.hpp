@@ -9,6 +9,7 @@
 #include <string>
 
 #include "pdmpc_device.h"
+#include "sampled_budget.h"
 
 // Tuning knobs and A/B / test switches of the graph search.  The defaults are the measured optima quoted next to their use; every
 // setting leaves the results bit-identical.  ONE environment variable overrides them, read once in pdmpc_create (a launch makes no
@@ -287,6 +288,56 @@ inline int compute_lds_sampled(const Tuning& T, const LaunchDims& d, LaunchPlan&
     return PDMPC_ERR_CAPACITY;
 }
 
+// What a sampled launch decides besides its LaunchPlan (extra[4] of pdmpc_sampled_plan_host, include/pdmpc.h): the tree's rows, where the tree
+// lives, and how the random numbers are drawn.
+struct SampledExtra {
+    int node_cap = 288, tree_in_lds = 1;
+    int64_t tree_hbm_bytes = 0;  // per slot (0: the tree is in LDS)
+    int rand_chunk = 0;          // doubles drawn at a time
+};
+
+// LDS layout of the sampled optimizer with a budget other than 250 (sampled_budget_kernel.hip): compute_lds_sampled's regions, with a tree of
+// pdmpc_sb_node_cap(budget) rows of 36 B and, for the random numbers, the generator's 624 state words alone.  The tree goes in LDS
+// when the 80 KB, then the 160 KB, layout holds it (the automaton's areas go to L2 before a layout takes the larger budget, as
+// there); else it goes to HBM and the same ladder is walked without it.
+inline int layout_sampled_budget(const Tuning& T, const LaunchDims& d, uint32_t budget, LaunchPlan& out, SampledExtra& extra, std::string& err) {
+    const uint32_t tree_bytes = pdmpc_sb_tree_bytes(budget);
+    for (int pass = 0; pass < 8; ++pass) {
+        const int areas = (pass & 1) == 0;
+        const size_t lds_budget = (pass & 2) == 0 ? kLdsMax / 2 : kLdsMax;
+        const bool tree_in_lds = pass < 4;
+        LdsLayout L{};
+        uint32_t off = layout_mpa(d, 0, areas, L);
+        L.ref = off;
+        off += 3 * PDMPC_HP_MAX * 8;
+        L.shape = off;
+        off += (2 * PDMPC_VMAX + 1) * 16;
+        L.path = off;
+        off += PDMPC_LK_PATH_BYTES;
+        L.soup = off;
+        off = align16(off + (uint32_t)std::max(d.soup_cap, 1) * 16);
+        L.cand = off;
+        off += align16((uint32_t)std::max(d.cand_cap, 1) * 4u);
+        L.expand = off;
+        off += (2 * PDMPC_HP_MAX * PDMPC_HP_MAX) * 8 + 16 * 16;
+        L.rand = off;
+        off += align16(PDMPC_SB_MT_BYTES);
+        L.tree16 = off;
+        if (tree_in_lds) {
+            if ((size_t)off + tree_bytes > lds_budget) continue;
+            off += align16(tree_bytes);
+        }
+        L.total = align16(off);
+        if (L.total <= lds_budget) {
+            static_cast<LaunchLayout&>(out) = {L, 1, 0, 0, areas, T.ready, false};
+            extra = {(int)pdmpc_sb_node_cap(budget), tree_in_lds ? 1 : 0, tree_in_lds ? 0 : (int64_t)tree_bytes, PDMPC_SB_TWIST};
+            return PDMPC_OK;
+        }
+    }
+    err = "obstacle soup + MPA tables do not fit into the LDS budget of the sampled optimizer";
+    return PDMPC_ERR_CAPACITY;
+}
+
 // LDS layout of the joint search (one wavefront per problem): MPA tables, every vehicle's reference, the node's areas, offsets and the
 // path, successor lists, the problem's distinct soups (soup_cap: pdmpc_joint_soup_columns), then the LDS part of the open list.  Aimed at 64 KB (two workgroups per CU and more);
 // a problem whose tables and soups do not leave room for 256 heap entries there may take up to the whole 160 KB.
@@ -463,6 +514,36 @@ inline int plan_launch(const Tuning& T, const LaunchDims& d, PlanKind kind, int 
     return PDMPC_OK;
 }
 
+// The plan of a sampled launch of `count` vehicles with expansion budget `budget` (pdmpc_set_sampled_budget).  The reference's 250 is
+// plan_launch's plan, field for field: pdmpc_sampled_kernel on compute_lds_sampled's layout.  Any other budget runs
+// sampled_budget_kernel.hip on layout_sampled_budget's.
+inline int plan_sampled(const Tuning& T, const LaunchDims& d, int budget, int count, bool safe, LaunchPlan& p, SampledExtra& extra, std::string& err) {
+    if (budget < 1 || budget > PDMPC_SAMPLED_BUDGET_MAX) {
+        err = "the sampled optimizer's budget must be in 1..PDMPC_SAMPLED_BUDGET_MAX";
+        return PDMPC_ERR_INVALID;
+    }
+    if (budget == PDMPC_SAMPLED_BUDGET_DEFAULT) {
+        extra = SampledExtra{};
+        extra.rand_chunk = d.Hp * PDMPC_SAMPLED_BUDGET_DEFAULT;  // (the whole stream at once, into LDS)
+        return plan_launch(T, d, kPlanSampled, count, 0, safe, p, err);
+    }
+    p = LaunchPlan{};
+    p.slice = count;
+    if (const int rc = layout_sampled_budget(T, d, (uint32_t)budget, p, extra, err)) return rc;
+    // the kernel ends its loop on n_nodes + Hp < node_cap like pdmpc_sampled_kernel; with n_nodes <= budget that must never bind
+    if (!(budget + d.Hp < extra.node_cap) || 1 + budget + PDMPC_HP_MAX - 1 > 0xffff) {
+        err = "plan_sampled: the tree's capacity does not cover the budget";
+        return PDMPC_ERR_INVALID;
+    }
+    launch_policy(T, count, d.n_cu, d.device_share, safe, false, 0, p);
+    p.spin_limit = safe ? (1u << 22) : T.spin_limit;
+    p.reverse_dispatch = (!safe && T.reverse_dispatch) ? 1 : 0;
+    p.bk_seat_nodes = std::max(1, T.seat_nodes);
+    p.kernel = extra.tree_in_lds ? "pdmpc_sampled_budget_kernel" : "pdmpc_sampled_budget_kernel_hbm";
+    if (safe) p.slice = p.lds.total <= kLdsMax / 2 ? 2 * d.n_cu : d.n_cu;
+    return PDMPC_OK;
+}
+
 // PDMPC_TUNING=debug_lds=1: the layout of a search launch and the kernel instantiation that runs it, one line (tests parse it)
 inline std::string format_bulk_layout(const LaunchPlan& p, int count) {
     const uint32_t near = (p.compact ? PDMPC_LK_COMPACT_BK_PER : PDMPC_BK_PER) * (uint32_t)p.n_waves * PDMPC_WAVE;
@@ -475,6 +556,17 @@ inline std::string format_bulk_layout(const LaunchPlan& p, int count) {
     return buf;
 }
 
+// a plan as the record of the windows (pdmpc_launch_plan)
+inline void plan_record(const LaunchPlan& p, bool joint, pdmpc_launch_plan& plan) {
+    const LdsLayout& L = p.lds;
+    const JointLds& J = p.joint;
+    plan = {p.n_waves, p.NL, p.NV, p.areas_in_lds, p.ready, p.compact ? 1 : 0, p.bk_ready_cap, p.bk_round0, p.bk_round, p.bk_ramp, p.bk_tile, p.bk_share_min,
+            p.n_helpers, p.bk_helpers_first, p.bk_seat_nodes, p.reverse_dispatch, p.variant, p.generic ? 1 : 0, p.slice, (int32_t)p.heap_lds, p.spin_limit,
+            joint ? J.mask : L.mask, joint ? J.man_index : L.man_index, joint ? J.pose : L.pose, joint ? J.area : L.area, joint ? J.ref : L.ref, joint ? J.shape : L.shape,
+            L.path, joint ? J.soup : L.soup, L.cand, L.vstate, L.expand, L.tree16, L.rand, L.nodes, joint ? J.total : L.total, L.bk_near_key, L.bk_near_id, L.bk_ready,
+            L.bk_hist, L.bk_misc, L.bk_pshape, L.reach_shared, L.bk_reach, L.reach, J.ints, J.succ, J.heap_key, J.heap_id, p.kernel};
+}
+
 // pdmpc_launch_plan_host (include/pdmpc.h), the window: the plan of the launch a query describes, as the record a test reads
 inline int plan_query(const char* tuning, const pdmpc_launch_query& q, pdmpc_launch_plan& plan, std::string& err) {
     Tuning T;
@@ -483,13 +575,23 @@ inline int plan_query(const char* tuning, const pdmpc_launch_query& q, pdmpc_lau
     mpa_table_sizes(d);
     LaunchPlan p;
     if (const int rc = plan_launch(T, d, (PlanKind)q.kind, q.count, q.n_chained, q.safe != 0, p, err)) return rc;
-    const LdsLayout& L = p.lds;
-    const JointLds& J = p.joint;
-    const bool joint = q.kind == kPlanJoint;
-    plan = {p.n_waves, p.NL, p.NV, p.areas_in_lds, p.ready, p.compact ? 1 : 0, p.bk_ready_cap, p.bk_round0, p.bk_round, p.bk_ramp, p.bk_tile, p.bk_share_min,
-            p.n_helpers, p.bk_helpers_first, p.bk_seat_nodes, p.reverse_dispatch, p.variant, p.generic ? 1 : 0, p.slice, (int32_t)p.heap_lds, p.spin_limit,
-            joint ? J.mask : L.mask, joint ? J.man_index : L.man_index, joint ? J.pose : L.pose, joint ? J.area : L.area, joint ? J.ref : L.ref, joint ? J.shape : L.shape,
-            L.path, joint ? J.soup : L.soup, L.cand, L.vstate, L.expand, L.tree16, L.rand, L.nodes, joint ? J.total : L.total, L.bk_near_key, L.bk_near_id, L.bk_ready,
-            L.bk_hist, L.bk_misc, L.bk_pshape, L.reach_shared, L.bk_reach, L.reach, J.ints, J.succ, J.heap_key, J.heap_id, p.kernel};
+    plan_record(p, q.kind == kPlanJoint, plan);
+    return PDMPC_OK;
+}
+
+// pdmpc_sampled_plan_host (include/pdmpc.h): the window on plan_sampled
+inline int plan_sampled_query(const char* tuning, const pdmpc_launch_query& q, int budget, pdmpc_launch_plan& plan, int64_t* extra, std::string& err) {
+    Tuning T;
+    if (!parse_tuning(tuning, T, err)) return PDMPC_ERR_INVALID;
+    LaunchDims d{q.checker, q.Hp, q.n_trims, 0, q.n_man, 0, 0, q.n_cu, q.device_share, (uint32_t)q.max_nodes, true, q.soup_cap, q.ll_cap, q.cand_cap};
+    mpa_table_sizes(d);
+    LaunchPlan p;
+    SampledExtra x;
+    if (const int rc = plan_sampled(T, d, budget, q.count, q.safe != 0, p, x, err)) return rc;
+    plan_record(p, false, plan);
+    extra[0] = x.node_cap;
+    extra[1] = x.tree_in_lds;
+    extra[2] = x.tree_hbm_bytes;
+    extra[3] = x.rand_chunk;
     return PDMPC_OK;
 }

@@ -330,6 +330,22 @@ struct Packer {
 
 }  // namespace
 
+// A sampled bank whose budget's tree does not fit LDS: the handle's HBM trees grow to a slot's rows for every packed slot (sampled_budget.h).
+// (The buffer is the handle's and only grows: resident banks of other budgets launch on it one after the other, and no row is read
+// before the launch that reads it has written it.)
+static int reserve_sampled_trees(pdmpc_handle* h, const PackedStep& B) {
+    LaunchPlan plan;
+    SampledExtra extra;
+    std::string err;
+    if (const int rc = plan_sampled(h->tune, launch_dims(h, B), B.budget, std::max(B.n_packed, 1), false, plan, extra, err)) return fail(rc, err);
+    if (extra.tree_in_lds) return PDMPC_OK;
+    const size_t want = (size_t)B.n_packed * (size_t)extra.node_cap * PDMPC_SB_ROW;
+    if (want <= h->d_sampled_tree.cap) return PDMPC_OK;
+    HIPCHK(sync_stream(h));  // (a launch of a resident bank may still read the buffer that is freed)
+    if (h->d_sampled_tree.ensure_exact(want)) return fail(PDMPC_ERR_CAPACITY, "not enough HBM for the sampled optimizer's trees at this budget");
+    return PDMPC_OK;
+}
+
 int pack_common(pdmpc_handle* h, int n, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index, const pdmpc_polygon_set* fallback) {
     if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
     // the weights are this pack's, whether it succeeds or not: a failed pack must not leave them to reorder the next one
@@ -349,6 +365,7 @@ int pack_common(pdmpc_handle* h, int n, const pdmpc_vehicle_in* in, const int32_
     B.n_packed = 0;  // (a pack that fails leaves the bank empty: the batch that was in it is being overwritten)
     B.pack_failed = true;
     B.sampled = sampled;
+    B.budget = h->sampled_budget;
     if (sampled && (int)seeds.size() != n) return fail(PDMPC_ERR_INVALID, "pdmpc_set_step_seeds: the seeds are not one per vehicle of the packed step");
     Packer P{h, B, n, in, pred_offset, pred_index, fallback, sampled ? &seeds : nullptr};
     int rc;
@@ -360,6 +377,11 @@ int pack_common(pdmpc_handle* h, int n, const pdmpc_vehicle_in* in, const int32_
     for (int slot = 0; slot < n; ++slot)
         if ((rc = P.pack_vehicle(slot))) return rc;
     if ((rc = P.close())) return rc;
+    if (sampled && B.budget != PDMPC_SAMPLED_BUDGET_DEFAULT && (rc = reserve_sampled_trees(h, B))) {
+        B.n_packed = 0;
+        B.pack_failed = true;
+        return rc;
+    }
     h->timer.reset();
     std::memset(&h->stats, 0, sizeof h->stats);
     return PDMPC_OK;

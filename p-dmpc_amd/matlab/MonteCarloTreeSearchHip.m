@@ -7,7 +7,15 @@ classdef MonteCarloTreeSearchHip < OptimizerInterface
     % OptimizerType.HipSampled (one more enum member and one more case in OptimizerInterface.get_optimizer,
     % see INTEGRATION.md).
     %
+    % n_expansions_max is the reference's property (MonteCarloTreeSearch.m:8), read from config/mcts.json where that file exists
+    % (:16-26) and handed to the library with pdmpc_mex('set_sampled_budget', ...): 250 runs the kernel the reference's default
+    % always ran, any other value in 1 .. 16384 the kernel with a run-time budget (DESIGN.md section 3.18).
+    %
     % Shipped as source like GraphSearchHip.m; the tested twin is pdmpc.optimizer.MonteCarloTreeSearchHip.
+
+    properties (SetAccess = private)
+        n_expansions_max (1, 1) double = 250; % MonteCarloTreeSearch.m:8
+    end
 
     properties (Access = private)
         handle uint64 = uint64(0);
@@ -20,6 +28,23 @@ classdef MonteCarloTreeSearchHip < OptimizerInterface
             obj = obj@OptimizerInterface();
             checker = double(options.are_any_obstacles_non_convex); % OptimizerInterface.m:36-46
             obj.handle = pdmpc_mex('create', options.Hp, checker, options.dt_seconds);
+
+            % MonteCarloTreeSearch.m:16-26: config/mcts.json, kept out of version control, overrides the default
+            file_path = fullfile('config', 'mcts.json'); % (relative to the working directory, as there)
+
+            if isfile(file_path)
+                mcts_config = jsondecode(fileread(file_path));
+
+                if isfield(mcts_config, 'n_expansions_max')
+                    obj.n_expansions_max = mcts_config.n_expansions_max;
+                end
+
+            end
+
+            if obj.n_expansions_max ~= 250
+                pdmpc_mex('set_sampled_budget', obj.handle, obj.n_expansions_max);
+            end
+
         end
 
         function delete(obj)

@@ -20,6 +20,18 @@ LIB_PATH = os.environ.get("PDMPC_LIB") or os.path.join(os.path.dirname(_HERE), "
 _LIB = None
 
 EXPORTS = list(PROTOTYPES)  # every function of include/pdmpc.h
+SAMPLED_BUDGET_DEFAULT, SAMPLED_BUDGET_MAX = 250, 16384  # PDMPC_SAMPLED_BUDGET_*
+
+
+def sampled_plan_host(query, n_expansions_max, tuning=None):
+    """pdmpc_sampled_plan_host (no GPU): the plan of a sampled launch with a budget -> (rc, {field: value} incl. kernel, extra dict)."""
+    L = load_library()
+    q, p = abi.LaunchQuery(**query), abi.LaunchPlan()
+    x = (C.c_int64 * 4)()
+    rc = L.pdmpc_sampled_plan_host(tuning.encode() if tuning is not None else None, C.byref(q), int(n_expansions_max), C.byref(p), x)
+    plan = {f: getattr(p, f) for f, _ in abi.LaunchPlan._fields_}
+    plan["kernel"] = plan["kernel"].decode() if plan["kernel"] else ""
+    return rc, plan, dict(zip(("node_cap", "tree_in_lds", "tree_hbm_bytes", "rand_chunk"), (int(v) for v in x)))
 
 
 class BackendError(RuntimeError):
@@ -543,6 +555,9 @@ class Group:
         _check(self.L, self.L.pdmpc_group_collective(self.g, C.byref(c)), "pdmpc_group_collective")
         self.collective = {COLLECTIVE_RCCL: "rccl", COLLECTIVE_COPY: "copy"}[c.value]
         self._mpa_keep = None
+        budget = int(getattr(options, "n_expansions_max", SAMPLED_BUDGET_DEFAULT))
+        if budget != SAMPLED_BUDGET_DEFAULT:
+            self.set_sampled_budget(budget)
 
     def close(self):
         if self.g:
@@ -607,6 +622,10 @@ class Group:
         """pdmpc_group_set_step_seeds: the next pack makes sampled banks on the ranks (the sampled optimizer), seeds in the caller's order."""
         s = np.ascontiguousarray(seeds, dtype=np.uint32)
         _check(self.L, self.L.pdmpc_group_set_step_seeds(self.g, len(s), abi.u32p(s)), "pdmpc_group_set_step_seeds")
+
+    def set_sampled_budget(self, n_expansions_max):
+        """pdmpc_group_set_sampled_budget: the sampled optimizer's expansion budget on every rank."""
+        _check(self.L, self.L.pdmpc_group_set_sampled_budget(self.g, int(n_expansions_max)), "pdmpc_group_set_sampled_budget")
 
     def _group_step_args(self, iters, predecessors, fallback_shapes, weights, mode):
         arr, off, idx, fb, keep = _step_args(self.Hp, iters, predecessors, fallback_shapes)
@@ -713,6 +732,39 @@ class Handle:
         self.h = C.c_void_p()
         _check(self.L, self.L.pdmpc_create(C.byref(self.cfg), C.byref(self.h)), "pdmpc_create")
         self._mpa_keep = None
+        budget = int(getattr(options, "n_expansions_max", SAMPLED_BUDGET_DEFAULT))
+        if budget != SAMPLED_BUDGET_DEFAULT:
+            self.set_sampled_budget(budget)
+
+    def set_sampled_budget(self, n_expansions_max):
+        """pdmpc_set_sampled_budget: the sampled optimizer's expansion budget (MonteCarloTreeSearch.m:8) of the banks packed from now on."""
+        _check(self.L, self.L.pdmpc_set_sampled_budget(self.h, int(n_expansions_max)), "pdmpc_set_sampled_budget")
+
+    def sampled_budget(self):
+        """pdmpc_get_sampled_budget."""
+        n = C.c_int32(0)
+        _check(self.L, self.L.pdmpc_get_sampled_budget(self.h, C.byref(n)), "pdmpc_get_sampled_budget")
+        return int(n.value)
+
+    def last_sampled_kernel(self):
+        """pdmpc_last_sampled_kernel: the kernel the last sampled launch ran ("" before the first one)."""
+        return self.L.pdmpc_last_sampled_kernel(self.h).decode()
+
+    def sampled_plan_bank(self, n_expansions_max):
+        """pdmpc_sampled_plan_bank: the plan of the current (sampled) bank at a budget -> ({field: value} incl. kernel, extra dict)."""
+        p = abi.LaunchPlan()
+        x = (C.c_int64 * 4)()
+        _check(self.L, self.L.pdmpc_sampled_plan_bank(self.h, int(n_expansions_max), C.byref(p), x), "pdmpc_sampled_plan_bank")
+        plan = {f: getattr(p, f) for f, _ in abi.LaunchPlan._fields_}
+        plan["kernel"] = plan["kernel"].decode() if plan["kernel"] else ""
+        return plan, dict(zip(("node_cap", "tree_in_lds", "tree_hbm_bytes", "rand_chunk"), (int(v) for v in x)))
+
+    def debug_random_stream(self, seeds, n):
+        """The chunked generator of pdmpc_sampled_budget_kernel on its own (pdmpc_debug_random_stream) -> (len(seeds), n) doubles."""
+        sd = (C.c_uint32 * max(len(seeds), 1))(*[int(s) for s in seeds])
+        out = np.zeros(max(len(seeds) * n, 1))
+        _check(self.L, self.L.pdmpc_debug_random_stream(self.h, len(seeds), sd, int(n), abi.dp(out)), "pdmpc_debug_random_stream")
+        return out[: len(seeds) * n].reshape(len(seeds), n)
 
     def close(self):
         if self.h:

@@ -56,6 +56,9 @@ class Config:
     # predicted-lanelet polygon before they are coupled on or enter a search as a parallel predecessor.  Off by default
     # so that configurations written before the feature existed plan as they did.
     bound_reachable_sets: bool = False
+    # MonteCarloTreeSearch.m:8 (n_expansions_max; the reference's constructor, :16-26, overrides it from config/mcts.json): the sampled
+    # optimizer's expansion budget, 1 .. 16384 (PDMPC_SAMPLED_BUDGET_MAX)
+    n_expansions_max: int = 250
     # backend sizing (no reference counterpart)
     device: int = 0
     max_nodes: int = 0

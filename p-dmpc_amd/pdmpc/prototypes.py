@@ -89,6 +89,12 @@ PROTOTYPES = {
     "pdmpc_plan_step_sampled": (INT, [OBJ] + STEP + [UP, VOUT]),
     "pdmpc_set_step_seeds": (INT, [OBJ, I32, UP]),
     "pdmpc_debug_random_numbers": (INT, [OBJ, I32, UP, I32, DP]),
+    "pdmpc_set_sampled_budget": (INT, [OBJ, I32]),
+    "pdmpc_get_sampled_budget": (INT, [OBJ, IP]),
+    "pdmpc_last_sampled_kernel": (STR, [OBJ]),
+    "pdmpc_sampled_plan_host": (INT, [STR, P(abi.LaunchQuery), I32, P(abi.LaunchPlan), P(I64)]),
+    "pdmpc_sampled_plan_bank": (INT, [OBJ, I32, P(abi.LaunchPlan), P(I64)]),
+    "pdmpc_debug_random_stream": (INT, [OBJ, I32, UP, I32, DP]),
     # ---- centralized control
     "pdmpc_plan_joint": (INT, [OBJ, I32, IP, VIN, VOUT]),
     # ---- the unique prioritizations of a coupling graph
@@ -199,6 +205,7 @@ PROTOTYPES = {
     "pdmpc_group_last_timing": (INT, [OBJ, DP]),
     # ---- the sampled optimizer, the lean read-back and the choice on a group
     "pdmpc_group_set_step_seeds": (INT, [OBJ, I32, UP]),
+    "pdmpc_group_set_sampled_budget": (INT, [OBJ, I32]),
     "pdmpc_group_plan_step_lean": (INT, [OBJ] + STEP + [DP, I32, IP, DP]),
     "pdmpc_group_fetch_records_at": (INT, [OBJ, I32, IP, VOUT]),
     "pdmpc_group_plan_step_chosen": (INT, [OBJ] + STEP + [DP, I32] + CHOSEN + [VOUT]),

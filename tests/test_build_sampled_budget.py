@@ -1,0 +1,47 @@
+"""Build-time properties of the sampled optimizer's kernels with a run-time budget (csrc/sampled_budget_kernel.hip; no GPU needed: hipcc
+cross-compiles gfx950 code objects)."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "p-dmpc_amd", "csrc")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+SAMPLED_BUDGET_KERNELS = ("pdmpc_sampled_budget_kernel", "pdmpc_sampled_budget_kernel_hbm", "pdmpc_debug_random_stream_kernel")
+
+
+@pytest.mark.timeout(300)
+def test_sampled_budget_kernels_use_no_scratch_memory_and_spill_no_vector_register():
+    """`make` builds sampled_budget_kernel.hip and `make resources` lists it with the other kernels; its kernels -- the tree in LDS, the
+    tree in HBM, the generator alone -- use no scratch memory and spill no vector register, and a wavefront's registers leave room for
+    four per SIMD like pdmpc_sampled_kernel's."""
+    if not os.path.exists(HIPCC) and shutil.which("hipcc") is None:
+        pytest.skip("no hipcc")
+    with open(os.path.join(CSRC, "Makefile")) as f:
+        lines = f.read().splitlines()
+    for var in ("SRCS", "RESOURCE_SRCS"):
+        listed = [line for line in lines if line.startswith(var)]
+        assert listed and "sampled_budget_kernel.hip" in listed[0], "%s does not cover sampled_budget_kernel.hip" % var
+    out = subprocess.run(["make", "-s", "-C", CSRC, "resources", "RESOURCE_SRCS=sampled_budget_kernel.hip"], capture_output=True, text=True, check=True).stdout
+    seen, name = {}, None
+    for line in out.splitlines():
+        m = re.search(r"Function Name: (\w+)", line)
+        if m:
+            name = m.group(1)
+            seen[name] = {}
+        for key, pat in (("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("vgpr_spill", r"VGPRs Spill: (\d+)"), ("vgprs", r" VGPRs: (\d+)"),
+                         ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
+            m = re.search(pat, line)
+            if m and name:
+                seen[name][key] = int(m.group(1))
+    for kernel in SAMPLED_BUDGET_KERNELS:
+        assert kernel in seen, seen.keys()
+        assert seen[kernel]["scratch"] == 0 and seen[kernel]["vgpr_spill"] == 0, (kernel, seen[kernel])
+        assert seen[kernel]["vgprs"] <= 128, (kernel, seen[kernel])
+    # the search kernels' LDS is dynamic (the launch plan sizes it); the generator alone holds its 624 state words
+    assert seen["pdmpc_sampled_budget_kernel"]["lds"] == 0 and seen["pdmpc_sampled_budget_kernel_hbm"]["lds"] == 0
+    assert seen["pdmpc_debug_random_stream_kernel"]["lds"] == 624 * 4

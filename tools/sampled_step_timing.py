@@ -10,7 +10,11 @@ C2-like: 20 vehicles, Hp 8, distance coupling, road network seed 1.  C4-like: 51
 Each way is run RUNS times, alternating (i) and (ii); the median and the spread (min .. max) are printed.  Every (ii) step is checked
 against (i) byte for byte first.  --quick: one short run per way (for a profiler run).
 
-    python tools/sampled_step_timing.py [--quick]
+--budget B[,B...]: instead, the launch (kernel) time of the C2-like recorded steps at each expansion budget (pdmpc_set_sampled_budget):
+medians of RUNS alternating runs over the budgets, the kernel and its LDS, and the time of one launch of the step's vehicles as
+independent searches (no predecessors: the time of the slowest single search).  profiles/sampled_budget_timing.txt is its output.
+
+    python tools/sampled_step_timing.py [--quick] [--budget 64,250,251,1000,4096,16384]
 """
 import copy
 import os
@@ -134,7 +138,47 @@ def measure(name, options, sc, n_steps, native_steps, **kw):
     sys.stdout.flush()
 
 
+def measure_budgets(budgets):
+    options = Config(scenario_type=ScenarioType.commonroad, amount=20, Hp=8, max_vehicles=32, max_nodes=1 << 12)
+    sc = commonroad_scenario(options, seed=1)
+    mpa = get_mpa(options)
+    steps = record_steps(options, mpa, sc, 3 if QUICK else 10)
+    h = Handle(options)
+    h.upload_mpa(mpa)
+    step_ms, solo_ms, info = {b: [] for b in budgets}, {b: [] for b in budgets}, {}
+
+    def launch_ms(call):
+        call()
+        st = h.stats()
+        return st["kernel_ms"], st
+
+    for run in range(RUNS + 1):  # (the first pass over the budgets warms up and is dropped)
+        for b in budgets:
+            h.set_sampled_budget(b)
+            tot = solo = 0.0
+            for prob, seeds in steps:
+                fb = [f if f is not None else [] for f in prob["fallback"]]
+                ms, st = launch_ms(lambda: h.plan_step_sampled(prob["iters"], prob["preds"], fb, seeds))
+                tot += ms
+                info[b] = (h.last_sampled_kernel(), st["lds_bytes"], st["safe_replans"])
+                ms, _ = launch_ms(lambda: h.plan_batch_sampled(prob["iters"], seeds))
+                solo = max(solo, ms)
+            if run:
+                step_ms[b].append(tot / len(steps))
+                solo_ms[b].append(solo)
+    h.close()
+    print("C2-like: 20 vehicles, Hp 8, %d recorded steps; kernel time per step, median of %d alternating runs (min .. max)" % (len(steps), RUNS))
+    print("  watchdog re-plans in resident slices since the handle was created: %d" % max(v[2] for v in info.values()))
+    for b in budgets:
+        print("  budget %5d  %-32s LDS %6d B  step %9.3f ms (%.3f .. %.3f)  independent searches, slowest launch %9.3f ms (%.3f .. %.3f)"
+              % (b, info[b][0], info[b][1], float(np.median(step_ms[b])), min(step_ms[b]), max(step_ms[b]), float(np.median(solo_ms[b])), min(solo_ms[b]), max(solo_ms[b])))
+    sys.stdout.flush()
+
+
 if __name__ == "__main__":
+    if "--budget" in sys.argv:
+        measure_budgets([int(b) for b in sys.argv[sys.argv.index("--budget") + 1].split(",")])
+        sys.exit(0)
     options = Config(scenario_type=ScenarioType.commonroad, amount=20, Hp=8, max_vehicles=32, max_nodes=1 << 12)
     measure("C2-like", options, commonroad_scenario(options, seed=1), 3 if QUICK else 10, 5 if QUICK else 20)
     options = Config(scenario_type=ScenarioType.commonroad, amount=512, Hp=10, max_vehicles=512, max_nodes=1 << 12)
