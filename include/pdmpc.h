@@ -503,6 +503,46 @@ int pdmpc_sampled_plan_bank(pdmpc_handle* handle, int32_t n_expansions_max, pdmp
 /* the chunked generator of pdmpc_sampled_budget_kernel on its own: out[i * n + j] = the j-th double of mt19937ar(seeds[i]), any n >= 0 */
 int pdmpc_debug_random_stream(pdmpc_handle* handle, int32_t count, const uint32_t* seeds, int32_t n, double* out);
 
+/* Seed ensembles of the sampled optimizer: every vehicle of a sampled bank is planned by E members side by side,
+ * each the whole sampled search on a random stream of its own, and the cheapest collision-free plan becomes the vehicle's record ON
+ * THE DEVICE, before the done flag its successors wait for.  E (1..PDMPC_SAMPLED_ENSEMBLE_MAX) is the handle's, like the budget: the
+ * NEXT pack of a sampled bank reads it and it stays with that bank (resident launches and the re-plan in slices after a watchdog
+ * time-out keep it).  The default is 1, and with E == 1 nothing changes: the same kernels, the same bytes.
+ *  - Member e (0-based) of a vehicle with seed s draws from mt19937ar(PDMPC_SAMPLED_MEMBER_SEED(s, e)); member 0 is the reference's
+ *    stream.  Every member runs the search as it is (the same descents, checks and floating-point order) at the handle's budget
+ *    against the same obstacles, the predecessors' published areas among them.
+ *  - The winner is the member with status PDMPC_OK and the smallest final cost (path_nodes[Hp][4], compared as doubles with <; on
+ *    equality the lowest member index).  The vehicle's record is the winner's, byte for byte what pdmpc_plan_step_sampled returns
+ *    for the vehicle with the winner's seed and the same predecessor records.
+ *  - No member OK: the record is member 0's, status PDMPC_EXHAUSTED, with the vehicle's fallback areas as before.  Any member timed
+ *    out waiting for predecessors: the record's status is PDMPC_ERR_HIP and the host re-plans in slices as before.
+ *  - Forward progress: the grid is count * E workgroups, block b is member b % E of slot b / E, so all members of a slot lie below
+ *    the blocks of its successors.  No member ever waits for a member: each writes its record and a 16-byte entry, draws a ticket,
+ *    and only the one that arrives last picks the winner, copies its record and sets the slot's done flag.  A workgroup still depends
+ *    only on workgroups dispatched before it (see pdmpc_plan_step).
+ * PDMPC_ERR_INVALID for a NULL argument and for a size outside 1..PDMPC_SAMPLED_ENSEMBLE_MAX (the handle keeps its value).  A pack
+ * with E > 1 allocates E records, entries and -- where the budget puts trees in HBM -- trees per slot: PDMPC_ERR_CAPACITY if that
+ * fails (the bank is then empty and the handle goes on working). */
+#define PDMPC_SAMPLED_ENSEMBLE_MAX 16
+#define PDMPC_SAMPLED_ENSEMBLE_STRIDE 1000003u
+#define PDMPC_SAMPLED_MEMBER_SEED(seed, e) ((uint32_t)((uint32_t)(seed) + (uint32_t)(e) * PDMPC_SAMPLED_ENSEMBLE_STRIDE)) /* modulo 2^32 */
+int pdmpc_set_sampled_ensemble(pdmpc_handle* handle, int32_t n_members);
+int pdmpc_get_sampled_ensemble(pdmpc_handle* handle, int32_t* n_members);
+/* PDMPC_SAMPLED_MEMBER_SEED as a call (what a host twin of another language evaluates) */
+uint32_t pdmpc_sampled_member_seed(uint32_t seed, int32_t member);
+/* The members of the current bank's last launch, in the caller's vehicle order: winner[v] (the member whose record the vehicle got: 0
+ * if none was OK, the first timed-out member after a time-out), member_status[v * E + e] and member_cost[v * E + e] (+inf where the
+ * member is not OK).  Any output may be NULL.  One small copy of the 16-byte entries, not of records.  PDMPC_ERR_INVALID for a NULL
+ * handle, a vehicle count other than the bank's, and a bank that was not packed as an ensemble (E > 1) or not launched since. */
+int pdmpc_sampled_ensemble_result(pdmpc_handle* handle, int32_t n_vehicles, int32_t* winner, int32_t* member_status, double* member_cost);
+/* pdmpc_sampled_plan_host with an ensemble size: extra is an int64[8].  n_members == 1 gives that call's plan and extra[0..3] field
+ * for field.  Otherwise the plan is the ensemble kernel's (pdmpc_sampled_ensemble_kernel, _hbm with the trees in HBM) on the budget
+ * kernel's layout at ANY budget, the default included; slice counts slots.  extra[4] bytes of member records per slot and extra[5] bytes
+ * of HBM trees per slot (both times E; 0 for one member), extra[6] the workgroups of a kernel launch: min(slice, count) * n_members,
+ * extra[7] n_members.  PDMPC_ERR_INVALID also for n_members outside 1..PDMPC_SAMPLED_ENSEMBLE_MAX. */
+int pdmpc_sampled_ensemble_plan_host(const char* tuning, const pdmpc_launch_query* query, int32_t n_expansions_max, int32_t n_members,
+                                     pdmpc_launch_plan* plan, int64_t* extra);
+
 /* ---- centralized control: one joint graph search over several vehicles (CentralizedController.m:34-46, GraphSearch.do_graph_search
  *      with iter.amount = N; separating-axis checker only) ----
  * n_problems independent joint searches in one launch.  Problem p = vehicles in[problem_offset[p] .. problem_offset[p+1]), 1 to
@@ -788,7 +828,9 @@ int pdmpc_controller_set_lanelet_bounding(pdmpc_controller* c, int32_t on);
  * _optimal_step / _run follow it.  The sampled optimizer's seeds are time_step + vehicle_index (1-based, MonteCarloTreeSearch.m:31-32,
  * PrioritizedController.m:335-341), the same for every instance of an explorative or optimal batch.  Its expansion budget is the
  * handle's (pdmpc_set_sampled_budget; on a group pdmpc_group_set_sampled_budget): the controller, its explorative and optimal steps
- * and sweeps plan on a handle and so follow the budget that handle has when the step is packed. */
+ * and sweeps plan on a handle and so follow the budget that handle has when the step is packed.  The same holds for its ensemble
+ * size (pdmpc_set_sampled_ensemble; on a group pdmpc_group_set_sampled_ensemble): every vehicle of a step, an explorative or optimal
+ * batch or a sweep is then planned by that many members and gets the winner's record. */
 enum { PDMPC_OPTIMIZER_GRAPH_SEARCH = 0, PDMPC_OPTIMIZER_SAMPLED = 1 };
 int pdmpc_controller_set_optimizer(pdmpc_controller* c, int32_t which); /* PDMPC_OPTIMIZER_*; anything else: PDMPC_ERR_INVALID */
 /* the sampled optimizer's seed per slot of the last built step or batch (pdmpc_controller_build_step / _explore_build / _optimal_build),
@@ -999,6 +1041,10 @@ int pdmpc_group_set_step_seeds(pdmpc_group* group, int32_t n_vehicles, const uin
  * with different budgets (one set on a single rank's handle) returns PDMPC_ERR_INVALID.  PDMPC_ERR_INVALID for a NULL group and for a
  * budget outside 1..PDMPC_SAMPLED_BUDGET_MAX (no rank is changed). */
 int pdmpc_group_set_sampled_budget(pdmpc_group* group, int32_t n_expansions_max);
+/* pdmpc_set_sampled_ensemble on every rank's handle, with the same rules: a pack with seeds that finds ranks with different ensemble
+ * sizes returns PDMPC_ERR_INVALID; PDMPC_ERR_INVALID for a NULL group and for a size outside 1..PDMPC_SAMPLED_ENSEMBLE_MAX (no rank
+ * is changed).  The members of a slot run on the rank that holds the slot: what crosses ranks is the winner's record, as before. */
+int pdmpc_group_set_sampled_ensemble(pdmpc_group* group, int32_t n_members);
 /* pdmpc_plan_step_lean / pdmpc_fetch_records_at over the group: status[v] and final_cost[v] = path_nodes[Hp][4] in the caller's order
  * (every rank's kernel writes the 16-byte entries of the records it holds into host memory; no record leaves a device but in the
  * level exchanges of a shared component), then the records wanted, each read from the rank that holds it.  Arena overflow as in

@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -146,7 +147,7 @@ int prepare_boards(pdmpc_handle* h, int count, uint32_t& fin_base) {
 // launch ever stall, the watchdog (spin_limit) ends the waiting searches with an error status and plan_packed_growing plans the call
 // again with safe == true, in slices that are resident as a whole (a slice's predecessors are in it or in an earlier slice) -- forward
 // progress then needs no assumption at all.
-int dispatch(const pdmpc_handle* h, const KernelArgs& a, const LaunchPlan& plan, bool search, const SampledBudgetArgs* budgeted = nullptr) {
+int dispatch(const pdmpc_handle* h, const KernelArgs& a, const LaunchPlan& plan, bool search, const SampledBudgetArgs* budgeted = nullptr, int members = 1) {
     typedef int (*launcher_t)(const KernelArgs*, int, void*, uint32_t*);
     static const launcher_t launchers[4][2] = {{pdmpc_launch_bulk, pdmpc_launch_bulk_any},
                                                {pdmpc_launch_bulk_wide, pdmpc_launch_bulk_wide_any},
@@ -162,7 +163,13 @@ int dispatch(const pdmpc_handle* h, const KernelArgs& a, const LaunchPlan& plan,
             SampledBudgetArgs sb = *budgeted;
             sb.first = part.first;
             sb.n_searches = part.n_searches;
-            lrc = pdmpc_launch_sampled_budget(&sb, sb.n_searches, (void*)h->stream);
+            if (members > 1) {
+                // (plan.slice counts slots: a slice is resident with all its members)
+                const SampledEnsembleArgs en{sb, members, h->d_member_out.p, h->d_member_entry.p, h->d_member_ticket.p, h->d_member_nodes.p, h->d_member_chosen.p};
+                lrc = pdmpc_launch_sampled_ensemble(&en, sb.n_searches, (void*)h->stream);
+            } else {
+                lrc = pdmpc_launch_sampled_budget(&sb, sb.n_searches, (void*)h->stream);
+            }
         } else if (!search) {
             lrc = pdmpc_launch_sampled(&part, part.n_searches, (void*)h->stream);
         } else {
@@ -190,23 +197,32 @@ int launch_range(pdmpc_handle* h, int first, int count, bool safe) {
     LaunchPlan plan;
     SampledExtra extra;
     std::string err;
-    // (a sampled bank plans with the budget it was packed with: the first launch, a resident one and the re-plan in slices alike)
-    int rc = search ? plan_launch(h->tune, dims, kPlanSearch, count, n_chained, safe, plan, err) : plan_sampled(h->tune, dims, B.budget, count, safe, plan, extra, err);
+    // (a sampled bank plans with the budget and the ensemble size it was packed with: the first launch, a resident one and the re-plan in slices alike)
+    int rc = search ? plan_launch(h->tune, dims, kPlanSearch, count, n_chained, safe, plan, err) : plan_sampled(h->tune, dims, B.budget, B.members, count, safe, plan, extra, err);
     if (rc) return fail(rc, err);
     KernelArgs a{};
     set_launch_args(h, B, plan, first, count, a);
-    const bool budgeted = !search && B.budget != PDMPC_SAMPLED_BUDGET_DEFAULT;
+    const bool ensemble = !search && B.members > 1;
+    const bool budgeted = !search && (B.budget != PDMPC_SAMPLED_BUDGET_DEFAULT || ensemble);
     SampledBudgetArgs sb{};
     if (budgeted) {
-        const size_t tree_words = (size_t)extra.node_cap * PDMPC_SB_ROW;
-        if (!extra.tree_in_lds && h->d_sampled_tree.cap < (size_t)B.n_packed * tree_words) return fail(PDMPC_ERR_CAPACITY, "the sampled optimizer's trees in HBM were not allocated by this bank's pack");
+        const size_t n_members = (size_t)B.n_packed * (size_t)B.members;
+        if (!extra.tree_in_lds && h->d_sampled_tree.cap < n_members * (size_t)extra.node_cap * PDMPC_SB_ROW) return fail(PDMPC_ERR_CAPACITY, "the sampled optimizer's trees in HBM were not allocated by this bank's pack");
+        if (ensemble && (h->d_member_out.cap < n_members || h->d_member_entry.cap < n_members || h->d_member_nodes.cap < n_members || h->d_member_ticket.cap < (size_t)B.n_packed || h->d_member_chosen.cap < (size_t)B.n_packed))
+            return fail(PDMPC_ERR_CAPACITY, "the records of the ensemble's members were not allocated by this bank's pack");
         sb = sampled_budget_args(a, B.budget, extra.node_cap, extra.tree_in_lds ? nullptr : h->d_sampled_tree.p);
+    }
+    if (ensemble) {
+        // every slot's ticket is zero when its members start, whatever the last launch of these slots left: a launch that failed, a
+        // resident re-launch and the re-plan in slices all pass here
+        HIPCHK(hipMemsetAsync(h->d_member_ticket.p + first, 0, (size_t)count * sizeof(uint32_t), h->stream));
+        h->ensemble_bank = h->bank;
     }
     if (!search) h->last_sampled_kernel = plan.kernel;
     if (plan.n_helpers > 0 && (rc = prepare_boards(h, count, a.help_fin_base))) return rc;
     if (search && h->tune.debug_lds) fputs(format_bulk_layout(plan, count).c_str(), stderr);
     if ((rc = h->timer.begin(h->stream, search ? kLaunchSearch : kLaunchSampled))) return rc;
-    const int lrc = dispatch(h, a, plan, search, budgeted ? &sb : nullptr);
+    const int lrc = dispatch(h, a, plan, search, budgeted ? &sb : nullptr, B.members);
     if (lrc != 0) {
         h->boards_dirty = true;  // (the searches that were to count themselves finished never ran: the next launch starts from cleared counters)
         char buf[256];
@@ -291,7 +307,13 @@ int pdmpc_launch_plan_host(const char* tuning, const pdmpc_launch_query* q, pdmp
 int pdmpc_sampled_plan_host(const char* tuning, const pdmpc_launch_query* q, int32_t n_expansions_max, pdmpc_launch_plan* plan, int64_t* extra) {
     if (!q || !plan || !extra) return fail(PDMPC_ERR_INVALID, "pdmpc_sampled_plan_host: null argument");
     std::string err;
-    return failed(plan_sampled_query(tuning, *q, n_expansions_max, *plan, extra, err), err);
+    return failed(plan_sampled_query(tuning, *q, n_expansions_max, 1, *plan, 4, extra, err), err);
+}
+
+int pdmpc_sampled_ensemble_plan_host(const char* tuning, const pdmpc_launch_query* q, int32_t n_expansions_max, int32_t n_members, pdmpc_launch_plan* plan, int64_t* extra) {
+    if (!q || !plan || !extra) return fail(PDMPC_ERR_INVALID, "pdmpc_sampled_ensemble_plan_host: null argument");
+    std::string err;
+    return failed(plan_sampled_query(tuning, *q, n_expansions_max, n_members, *plan, 8, extra, err), err);
 }
 
 int pdmpc_sampled_plan_bank(pdmpc_handle* h, int32_t n_expansions_max, pdmpc_launch_plan* plan, int64_t* extra) {
@@ -301,12 +323,9 @@ int pdmpc_sampled_plan_bank(pdmpc_handle* h, int32_t n_expansions_max, pdmpc_lau
     LaunchPlan p;
     SampledExtra x;
     std::string err;
-    if (const int rc = plan_sampled(h->tune, launch_dims(h, B), n_expansions_max, B.n_packed, h->safe_launches, p, x, err)) return fail(rc, err);
+    if (const int rc = plan_sampled(h->tune, launch_dims(h, B), n_expansions_max, B.members, B.n_packed, h->safe_launches, p, x, err)) return fail(rc, err);
     plan_record(p, false, *plan);
-    extra[0] = x.node_cap;
-    extra[1] = x.tree_in_lds;
-    extra[2] = x.tree_hbm_bytes;
-    extra[3] = x.rand_chunk;
+    sampled_extra_record(x, 4, extra);
     return PDMPC_OK;
 }
 
@@ -324,6 +343,46 @@ int pdmpc_get_sampled_budget(pdmpc_handle* h, int32_t* n_expansions_max) {
 }
 
 const char* pdmpc_last_sampled_kernel(pdmpc_handle* h) { return h ? h->last_sampled_kernel : ""; }
+
+int pdmpc_set_sampled_ensemble(pdmpc_handle* h, int32_t n_members) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "pdmpc_set_sampled_ensemble: null handle");
+    if (n_members < 1 || n_members > PDMPC_SAMPLED_ENSEMBLE_MAX) return fail(PDMPC_ERR_INVALID, "pdmpc_set_sampled_ensemble: the ensemble size must be in 1..PDMPC_SAMPLED_ENSEMBLE_MAX");
+    h->sampled_members = n_members;
+    return PDMPC_OK;
+}
+
+int pdmpc_get_sampled_ensemble(pdmpc_handle* h, int32_t* n_members) {
+    if (!h || !n_members) return fail(PDMPC_ERR_INVALID, "pdmpc_get_sampled_ensemble: null argument");
+    *n_members = h->sampled_members;
+    return PDMPC_OK;
+}
+
+uint32_t pdmpc_sampled_member_seed(uint32_t seed, int32_t member) { return PDMPC_SAMPLED_MEMBER_SEED(seed, member); }
+
+int pdmpc_sampled_ensemble_result(pdmpc_handle* h, int32_t n_vehicles, int32_t* winner, int32_t* member_status, double* member_cost) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "pdmpc_sampled_ensemble_result: null handle");
+    const PackedStep& B = h->banks[h->bank];
+    if (B.pack_failed || !B.sampled || B.members < 2 || h->ensemble_bank != h->bank) return fail(PDMPC_ERR_INVALID, "pdmpc_sampled_ensemble_result: the current bank was not packed as an ensemble or not launched since");
+    if (n_vehicles != B.n_packed) return fail(PDMPC_ERR_INVALID, "pdmpc_sampled_ensemble_result: not the bank's vehicle count");
+    ON_DEVICE(h->cfg.device);
+    const int E = B.members;
+    std::vector<EnsembleEntry> en((size_t)n_vehicles * (size_t)E);
+    std::vector<int32_t> chosen((size_t)n_vehicles);
+    if (en.empty()) return PDMPC_OK;
+    HIPCHK(hipMemcpyAsync(en.data(), h->d_member_entry.p, en.size() * sizeof(EnsembleEntry), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(chosen.data(), h->d_member_chosen.p, chosen.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(sync_stream(h));
+    for (int v = 0; v < n_vehicles; ++v) {
+        const size_t slot = (size_t)(B.perm.empty() ? v : B.inv[(size_t)v]);
+        const EnsembleEntry* row = en.data() + slot * (size_t)E;
+        for (int e = 0; e < E; ++e) {
+            if (member_status) member_status[(size_t)v * E + e] = row[e].status;
+            if (member_cost) member_cost[(size_t)v * E + e] = row[e].status == PDMPC_OK ? row[e].cost : std::numeric_limits<double>::infinity();
+        }
+        if (winner) winner[v] = chosen[slot];
+    }
+    return PDMPC_OK;
+}
 
 int pdmpc_destroy(pdmpc_handle* h) {
     if (!h) return PDMPC_OK;

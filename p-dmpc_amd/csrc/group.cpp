@@ -344,6 +344,12 @@ int group_pack(pdmpc_group* g, int bank, int n, const pdmpc_vehicle_in* in, cons
             GRC(pdmpc_get_sampled_budget(g->h[(size_t)r], &other));
             if (other != first) return gfail(PDMPC_ERR_INVALID, "the ranks of the group have different sampled budgets (pdmpc_group_set_sampled_budget sets every rank)");
         }
+        // ... and one ensemble size
+        GRC(pdmpc_get_sampled_ensemble(g->h[0], &first));
+        for (int r = 1; r < world; ++r) {
+            GRC(pdmpc_get_sampled_ensemble(g->h[(size_t)r], &other));
+            if (other != first) return gfail(PDMPC_ERR_INVALID, "the ranks of the group have different ensemble sizes (pdmpc_group_set_sampled_ensemble sets every rank)");
+        }
     }
     L.n = n;
     Partition& P = L.P;
@@ -1006,6 +1012,13 @@ int pdmpc_group_set_sampled_budget(pdmpc_group* g, int32_t n_expansions_max) {
     if (!g) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_set_sampled_budget: null group");
     if (n_expansions_max < 1 || n_expansions_max > PDMPC_SAMPLED_BUDGET_MAX) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_set_sampled_budget: the budget must be in 1..PDMPC_SAMPLED_BUDGET_MAX");
     for (pdmpc_handle* h : g->h) GRC(pdmpc_set_sampled_budget(h, n_expansions_max));
+    return PDMPC_OK;
+}
+
+int pdmpc_group_set_sampled_ensemble(pdmpc_group* g, int32_t n_members) {
+    if (!g) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_set_sampled_ensemble: null group");
+    if (n_members < 1 || n_members > PDMPC_SAMPLED_ENSEMBLE_MAX) return gfail(PDMPC_ERR_INVALID, "pdmpc_group_set_sampled_ensemble: the ensemble size must be in 1..PDMPC_SAMPLED_ENSEMBLE_MAX");
+    for (pdmpc_handle* h : g->h) GRC(pdmpc_set_sampled_ensemble(h, n_members));
     return PDMPC_OK;
 }
 

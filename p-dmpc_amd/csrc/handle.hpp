@@ -183,6 +183,7 @@ struct PackedStep {
     bool pack_failed = false;  // the last pack into this bank did not finish: nothing to launch or fetch
     bool sampled = false;      // packed with seeds (pdmpc_set_step_seeds): a sampled bank, its launches run the sampled optimizer
     int budget = PDMPC_SAMPLED_BUDGET_DEFAULT;  // ... with the expansion budget the handle had when it was packed (pdmpc_set_sampled_budget)
+    int members = 1;                            // ... and the ensemble size (pdmpc_set_sampled_ensemble)
     int soup_cap = 0;
     int ll_cap = 0;    // most lanelet-boundary columns of any vehicle (the graph search's reach lists hold one boundary list per step)
     int cand_cap = 0;  // most segments any single edge check can see (one step's soups + the boundary)
@@ -436,6 +437,16 @@ struct pdmpc_handle {
     int sampled_budget = PDMPC_SAMPLED_BUDGET_DEFAULT;  // pdmpc_set_sampled_budget: what the next pack of a sampled bank gives its bank
     DevBuf<uint16_t> d_sampled_tree;     // the trees of a sampled bank whose budget does not fit LDS (sampled_budget.h), grown by the pack that needs more
     const char* last_sampled_kernel = "";  // pdmpc_last_sampled_kernel
+    // Seed ensembles (sampled_ensemble.h): what the next pack of a sampled bank gives its bank, and the members' scratch.  Like d_out
+    // and d_sampled_tree the scratch is the handle's, shared by its banks and only grown, by the pack that needs more: a launch reads
+    // nothing of it that it has not written.
+    int sampled_members = 1;
+    int ensemble_bank = -1;                  // the bank whose launch wrote the entries last (pdmpc_sampled_ensemble_result), -1: none since its pack
+    DevBuf<pdmpc_vehicle_out> d_member_out;  // [slot * E + e]
+    DevBuf<EnsembleEntry> d_member_entry;    // [slot * E + e]
+    DevBuf<int32_t> d_member_nodes;          // [slot * E + e]
+    DevBuf<uint32_t> d_member_ticket;        // [slot], cleared on the stream ahead of every launch of an ensemble bank
+    DevBuf<int32_t> d_member_chosen;         // [slot] the member the kernel chose
     PinnedBuf<double> h_lean;            // fetch_lean: (cost, status) per slot
     DevBuf<double> d_lean;
     PinnedBuf<pdmpc_vehicle_out> h_out;  // pdmpc_fetch_results: the records land in pinned memory (a copy into the caller's pageable array goes through the runtime's staging otherwise)

@@ -10,6 +10,7 @@
 
 #include "pdmpc_device.h"
 #include "sampled_budget.h"
+#include "sampled_ensemble.h"
 
 // Tuning knobs and A/B / test switches of the graph search.  The defaults are the measured optima quoted next to their use; every
 // setting leaves the results bit-identical.  ONE environment variable overrides them, read once in pdmpc_create (a launch makes no
@@ -294,6 +295,11 @@ struct SampledExtra {
     int node_cap = 288, tree_in_lds = 1;
     int64_t tree_hbm_bytes = 0;  // per slot (0: the tree is in LDS)
     int rand_chunk = 0;          // doubles drawn at a time
+    // ... and a seed ensemble (pdmpc_set_sampled_ensemble; extra[4..7] of pdmpc_sampled_ensemble_plan_host)
+    int members = 1;
+    int64_t member_bytes = 0;        // member records per slot (0 for one member: the slot's record is the only one)
+    int64_t ensemble_tree_bytes = 0; // HBM trees per slot, all members'
+    int64_t grid = 0;                // workgroups of a kernel launch
 };
 
 // LDS layout of the sampled optimizer with a budget other than 250 (sampled_budget_kernel.hip): compute_lds_sampled's regions, with a tree of
@@ -514,18 +520,26 @@ inline int plan_launch(const Tuning& T, const LaunchDims& d, PlanKind kind, int 
     return PDMPC_OK;
 }
 
-// The plan of a sampled launch of `count` vehicles with expansion budget `budget` (pdmpc_set_sampled_budget).  The reference's 250 is
-// plan_launch's plan, field for field: pdmpc_sampled_kernel on compute_lds_sampled's layout.  Any other budget runs
-// sampled_budget_kernel.hip on layout_sampled_budget's.
-inline int plan_sampled(const Tuning& T, const LaunchDims& d, int budget, int count, bool safe, LaunchPlan& p, SampledExtra& extra, std::string& err) {
+// The plan of a sampled launch of `count` vehicles with expansion budget `budget` (pdmpc_set_sampled_budget) and `members` members per
+// vehicle (pdmpc_set_sampled_ensemble).  One member: the reference's 250 is plan_launch's plan, field for field (pdmpc_sampled_kernel on
+// compute_lds_sampled's layout), and any other budget runs sampled_budget_kernel.hip on layout_sampled_budget's.  Two or more members
+// run sampled_ensemble_kernel.hip on layout_sampled_budget's at every budget, 250 included: count * members workgroups, and slices
+// of the safe mode that count slots -- as many as are resident with all their members.
+inline int plan_sampled(const Tuning& T, const LaunchDims& d, int budget, int members, int count, bool safe, LaunchPlan& p, SampledExtra& extra, std::string& err) {
     if (budget < 1 || budget > PDMPC_SAMPLED_BUDGET_MAX) {
         err = "the sampled optimizer's budget must be in 1..PDMPC_SAMPLED_BUDGET_MAX";
         return PDMPC_ERR_INVALID;
     }
-    if (budget == PDMPC_SAMPLED_BUDGET_DEFAULT) {
+    if (members < 1 || members > PDMPC_SAMPLED_ENSEMBLE_MAX) {
+        err = "the sampled optimizer's ensemble size must be in 1..PDMPC_SAMPLED_ENSEMBLE_MAX";
+        return PDMPC_ERR_INVALID;
+    }
+    if (budget == PDMPC_SAMPLED_BUDGET_DEFAULT && members == 1) {
         extra = SampledExtra{};
         extra.rand_chunk = d.Hp * PDMPC_SAMPLED_BUDGET_DEFAULT;  // (the whole stream at once, into LDS)
-        return plan_launch(T, d, kPlanSampled, count, 0, safe, p, err);
+        if (const int rc = plan_launch(T, d, kPlanSampled, count, 0, safe, p, err)) return rc;
+        extra.grid = std::min(p.slice, count);
+        return PDMPC_OK;
     }
     p = LaunchPlan{};
     p.slice = count;
@@ -539,8 +553,18 @@ inline int plan_sampled(const Tuning& T, const LaunchDims& d, int budget, int co
     p.spin_limit = safe ? (1u << 22) : T.spin_limit;
     p.reverse_dispatch = (!safe && T.reverse_dispatch) ? 1 : 0;
     p.bk_seat_nodes = std::max(1, T.seat_nodes);
-    p.kernel = extra.tree_in_lds ? "pdmpc_sampled_budget_kernel" : "pdmpc_sampled_budget_kernel_hbm";
-    if (safe) p.slice = p.lds.total <= kLdsMax / 2 ? 2 * d.n_cu : d.n_cu;
+    const int resident = p.lds.total <= kLdsMax / 2 ? 2 * d.n_cu : d.n_cu;  // workgroups
+    if (members == 1) {
+        p.kernel = extra.tree_in_lds ? "pdmpc_sampled_budget_kernel" : "pdmpc_sampled_budget_kernel_hbm";
+        if (safe) p.slice = resident;
+    } else {
+        p.kernel = extra.tree_in_lds ? "pdmpc_sampled_ensemble_kernel" : "pdmpc_sampled_ensemble_kernel_hbm";
+        if (safe) p.slice = std::max(1, resident / members);
+        extra.members = members;
+        extra.member_bytes = (int64_t)members * (int64_t)sizeof(pdmpc_vehicle_out);
+        extra.ensemble_tree_bytes = (int64_t)members * extra.tree_hbm_bytes;
+    }
+    extra.grid = (int64_t)std::min(p.slice, count) * members;
     return PDMPC_OK;
 }
 
@@ -579,19 +603,20 @@ inline int plan_query(const char* tuning, const pdmpc_launch_query& q, pdmpc_lau
     return PDMPC_OK;
 }
 
-// pdmpc_sampled_plan_host (include/pdmpc.h): the window on plan_sampled
-inline int plan_sampled_query(const char* tuning, const pdmpc_launch_query& q, int budget, pdmpc_launch_plan& plan, int64_t* extra, std::string& err) {
+// pdmpc_sampled_plan_host and pdmpc_sampled_ensemble_plan_host (include/pdmpc.h): the windows on plan_sampled.  n_extra: 4 or 8 numbers
+inline void sampled_extra_record(const SampledExtra& x, int n_extra, int64_t* extra) {
+    const int64_t all[8] = {x.node_cap, x.tree_in_lds, x.tree_hbm_bytes, x.rand_chunk, x.member_bytes, x.ensemble_tree_bytes, x.grid, x.members};
+    for (int i = 0; i < n_extra; ++i) extra[i] = all[i];
+}
+inline int plan_sampled_query(const char* tuning, const pdmpc_launch_query& q, int budget, int members, pdmpc_launch_plan& plan, int n_extra, int64_t* extra, std::string& err) {
     Tuning T;
     if (!parse_tuning(tuning, T, err)) return PDMPC_ERR_INVALID;
     LaunchDims d{q.checker, q.Hp, q.n_trims, 0, q.n_man, 0, 0, q.n_cu, q.device_share, (uint32_t)q.max_nodes, true, q.soup_cap, q.ll_cap, q.cand_cap};
     mpa_table_sizes(d);
     LaunchPlan p;
     SampledExtra x;
-    if (const int rc = plan_sampled(T, d, budget, q.count, q.safe != 0, p, x, err)) return rc;
+    if (const int rc = plan_sampled(T, d, budget, members, q.count, q.safe != 0, p, x, err)) return rc;
     plan_record(p, false, plan);
-    extra[0] = x.node_cap;
-    extra[1] = x.tree_in_lds;
-    extra[2] = x.tree_hbm_bytes;
-    extra[3] = x.rand_chunk;
+    sampled_extra_record(x, n_extra, extra);
     return PDMPC_OK;
 }

@@ -11,10 +11,16 @@ classdef MonteCarloTreeSearchHip < OptimizerInterface
     % (:16-26) and handed to the library with pdmpc_mex('set_sampled_budget', ...): 250 runs the kernel the reference's default
     % always ran, any other value in 1 .. 16384 the kernel with a run-time budget (DESIGN.md section 3.18).
     %
+    % n_members (no reference counterpart; config/mcts.json may set it too) is the seed ensemble of pdmpc_set_sampled_ensemble: every
+    % vehicle of a step planned with pdmpc_mex('plan_step_sampled', ...) is planned by that many members on random streams of their own
+    % -- member e draws from mt19937ar(seed + e * 1000003), member 0 is the reference's stream -- and gets the cheapest collision-free
+    % plan, chosen on the device.  1 (the default) plans as the reference does (DESIGN.md section 3.18).
+    %
     % Shipped as source like GraphSearchHip.m; the tested twin is pdmpc.optimizer.MonteCarloTreeSearchHip.
 
     properties (SetAccess = private)
         n_expansions_max (1, 1) double = 250; % MonteCarloTreeSearch.m:8
+        n_members (1, 1) double = 1; % members per vehicle, 1 .. 16 (PDMPC_SAMPLED_ENSEMBLE_MAX)
     end
 
     properties (Access = private)
@@ -39,10 +45,18 @@ classdef MonteCarloTreeSearchHip < OptimizerInterface
                     obj.n_expansions_max = mcts_config.n_expansions_max;
                 end
 
+                if isfield(mcts_config, 'n_members')
+                    obj.n_members = mcts_config.n_members;
+                end
+
             end
 
             if obj.n_expansions_max ~= 250
                 pdmpc_mex('set_sampled_budget', obj.handle, obj.n_expansions_max);
+            end
+
+            if obj.n_members ~= 1
+                pdmpc_mex('set_sampled_ensemble', obj.handle, obj.n_members);
             end
 
         end

@@ -19,6 +19,9 @@
 //            pdmpc_mex('set_sampled_budget', h, n_expansions_max)    the sampled optimizer's expansion budget of the plans from now
 //                                                                  on (MonteCarloTreeSearch.m:8, config/mcts.json; 1 .. 16384);
 //            pdmpc_mex('group_set_sampled_budget', g, n)             the same on every rank of a group
+//            pdmpc_mex('set_sampled_ensemble', h, n_members)         members per vehicle of the sampled plans from now on (1 .. 16; the
+//                                                                  cheapest collision-free member wins on the device);
+//            pdmpc_mex('group_set_sampled_ensemble', g, n_members)   the same on every rank of a group
 //            pdmpc_mex('destroy', h)
 // iter_struct(s): struct (array) with fields x0, trim_index, reference_trajectory_points (Hp x 2), v_ref, obstacles (cell),
 // dynamic_obstacle_area (n_d x Hp cell), lanelet_boundary (1 x 2 cell), hdv_reachable_sets (n_h x Hp cell).
@@ -165,6 +168,11 @@ public:
         if (cmd == "set_sampled_budget" || cmd == "group_set_sampled_budget") {
             const int32_t budget = (int32_t)inputs[2][0];
             if ((group ? pdmpc_group_set_sampled_budget(group, budget) : pdmpc_set_sampled_budget(h, budget)) != PDMPC_OK) fail("pdmpc_set_sampled_budget", pdmpc_last_error());
+            return;
+        }
+        if (cmd == "set_sampled_ensemble" || cmd == "group_set_sampled_ensemble") {
+            const int32_t n_members = (int32_t)inputs[2][0];
+            if ((group ? pdmpc_group_set_sampled_ensemble(group, n_members) : pdmpc_set_sampled_ensemble(h, n_members)) != PDMPC_OK) fail("pdmpc_set_sampled_ensemble", pdmpc_last_error());
             return;
         }
         pdmpc_config hc{};

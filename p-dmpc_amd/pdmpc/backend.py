@@ -21,6 +21,24 @@ _LIB = None
 
 EXPORTS = list(PROTOTYPES)  # every function of include/pdmpc.h
 SAMPLED_BUDGET_DEFAULT, SAMPLED_BUDGET_MAX = 250, 16384  # PDMPC_SAMPLED_BUDGET_*
+SAMPLED_ENSEMBLE_MAX, SAMPLED_ENSEMBLE_STRIDE = 16, 1000003  # PDMPC_SAMPLED_ENSEMBLE_*
+_SAMPLED_EXTRA = ("node_cap", "tree_in_lds", "tree_hbm_bytes", "rand_chunk", "member_bytes", "ensemble_tree_bytes", "grid", "n_members")
+
+
+def sampled_member_seed(seed, member):
+    """pdmpc_sampled_member_seed (no GPU): PDMPC_SAMPLED_MEMBER_SEED of include/pdmpc.h, evaluated by the library."""
+    return int(load_library().pdmpc_sampled_member_seed(int(seed) & 0xFFFFFFFF, int(member)))
+
+
+def sampled_ensemble_plan_host(query, n_expansions_max, n_members, tuning=None):
+    """pdmpc_sampled_ensemble_plan_host (no GPU): sampled_plan_host with an ensemble size; the extra dict has 8 entries."""
+    L = load_library()
+    q, p = abi.LaunchQuery(**query), abi.LaunchPlan()
+    x = (C.c_int64 * 8)()
+    rc = L.pdmpc_sampled_ensemble_plan_host(tuning.encode() if tuning is not None else None, C.byref(q), int(n_expansions_max), int(n_members), C.byref(p), x)
+    plan = {f: getattr(p, f) for f, _ in abi.LaunchPlan._fields_}
+    plan["kernel"] = plan["kernel"].decode() if plan["kernel"] else ""
+    return rc, plan, dict(zip(_SAMPLED_EXTRA, (int(v) for v in x)))
 
 
 def sampled_plan_host(query, n_expansions_max, tuning=None):
@@ -558,6 +576,8 @@ class Group:
         budget = int(getattr(options, "n_expansions_max", SAMPLED_BUDGET_DEFAULT))
         if budget != SAMPLED_BUDGET_DEFAULT:
             self.set_sampled_budget(budget)
+        if int(getattr(options, "n_members", 1)) != 1:
+            self.set_sampled_ensemble(options.n_members)
 
     def close(self):
         if self.g:
@@ -626,6 +646,10 @@ class Group:
     def set_sampled_budget(self, n_expansions_max):
         """pdmpc_group_set_sampled_budget: the sampled optimizer's expansion budget on every rank."""
         _check(self.L, self.L.pdmpc_group_set_sampled_budget(self.g, int(n_expansions_max)), "pdmpc_group_set_sampled_budget")
+
+    def set_sampled_ensemble(self, n_members):
+        """pdmpc_group_set_sampled_ensemble: the sampled optimizer's ensemble size on every rank."""
+        _check(self.L, self.L.pdmpc_group_set_sampled_ensemble(self.g, int(n_members)), "pdmpc_group_set_sampled_ensemble")
 
     def _group_step_args(self, iters, predecessors, fallback_shapes, weights, mode):
         arr, off, idx, fb, keep = _step_args(self.Hp, iters, predecessors, fallback_shapes)
@@ -735,6 +759,29 @@ class Handle:
         budget = int(getattr(options, "n_expansions_max", SAMPLED_BUDGET_DEFAULT))
         if budget != SAMPLED_BUDGET_DEFAULT:
             self.set_sampled_budget(budget)
+        if int(getattr(options, "n_members", 1)) != 1:
+            self.set_sampled_ensemble(options.n_members)
+
+    def set_sampled_ensemble(self, n_members):
+        """pdmpc_set_sampled_ensemble: members per vehicle of the sampled banks packed from now on (1: the reference's one stream)."""
+        _check(self.L, self.L.pdmpc_set_sampled_ensemble(self.h, int(n_members)), "pdmpc_set_sampled_ensemble")
+
+    def get_sampled_ensemble(self):
+        """pdmpc_get_sampled_ensemble."""
+        n = C.c_int32(0)
+        _check(self.L, self.L.pdmpc_get_sampled_ensemble(self.h, C.byref(n)), "pdmpc_get_sampled_ensemble")
+        return int(n.value)
+
+    def sampled_ensemble_result(self, n_vehicles, n_members=None):
+        """pdmpc_sampled_ensemble_result of the current bank's last launch, in the caller's vehicle order ->
+        (winner (n,), member_status (n, E), member_cost (n, E); +inf where a member is not OK).  n_members: the size the bank was
+        packed with, if the handle's has been changed since."""
+        E = self.get_sampled_ensemble() if n_members is None else int(n_members)
+        winner = np.zeros(max(n_vehicles, 1), dtype=np.int32)
+        status = np.zeros(max(n_vehicles * E, 1), dtype=np.int32)
+        cost = np.zeros(max(n_vehicles * E, 1))
+        _check(self.L, self.L.pdmpc_sampled_ensemble_result(self.h, int(n_vehicles), abi.i32p(winner), abi.i32p(status), abi.dp(cost)), "pdmpc_sampled_ensemble_result")
+        return winner[:n_vehicles], status[: n_vehicles * E].reshape(n_vehicles, E), cost[: n_vehicles * E].reshape(n_vehicles, E)
 
     def set_sampled_budget(self, n_expansions_max):
         """pdmpc_set_sampled_budget: the sampled optimizer's expansion budget (MonteCarloTreeSearch.m:8) of the banks packed from now on."""

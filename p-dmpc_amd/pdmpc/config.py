@@ -59,6 +59,9 @@ class Config:
     # MonteCarloTreeSearch.m:8 (n_expansions_max; the reference's constructor, :16-26, overrides it from config/mcts.json): the sampled
     # optimizer's expansion budget, 1 .. 16384 (PDMPC_SAMPLED_BUDGET_MAX)
     n_expansions_max: int = 250
+    # the sampled optimizer's seed ensemble (no reference counterpart; pdmpc_set_sampled_ensemble): members per vehicle, 1 .. 16
+    # (PDMPC_SAMPLED_ENSEMBLE_MAX); 1 plans as the reference does
+    n_members: int = 1
     # backend sizing (no reference counterpart)
     device: int = 0
     max_nodes: int = 0

@@ -95,6 +95,11 @@ PROTOTYPES = {
     "pdmpc_sampled_plan_host": (INT, [STR, P(abi.LaunchQuery), I32, P(abi.LaunchPlan), P(I64)]),
     "pdmpc_sampled_plan_bank": (INT, [OBJ, I32, P(abi.LaunchPlan), P(I64)]),
     "pdmpc_debug_random_stream": (INT, [OBJ, I32, UP, I32, DP]),
+    "pdmpc_set_sampled_ensemble": (INT, [OBJ, I32]),
+    "pdmpc_get_sampled_ensemble": (INT, [OBJ, IP]),
+    "pdmpc_sampled_member_seed": (U32, [U32, I32]),
+    "pdmpc_sampled_ensemble_result": (INT, [OBJ, I32, IP, IP, DP]),
+    "pdmpc_sampled_ensemble_plan_host": (INT, [STR, P(abi.LaunchQuery), I32, I32, P(abi.LaunchPlan), P(I64)]),
     # ---- centralized control
     "pdmpc_plan_joint": (INT, [OBJ, I32, IP, VIN, VOUT]),
     # ---- the unique prioritizations of a coupling graph
@@ -206,6 +211,7 @@ PROTOTYPES = {
     # ---- the sampled optimizer, the lean read-back and the choice on a group
     "pdmpc_group_set_step_seeds": (INT, [OBJ, I32, UP]),
     "pdmpc_group_set_sampled_budget": (INT, [OBJ, I32]),
+    "pdmpc_group_set_sampled_ensemble": (INT, [OBJ, I32]),
     "pdmpc_group_plan_step_lean": (INT, [OBJ] + STEP + [DP, I32, IP, DP]),
     "pdmpc_group_fetch_records_at": (INT, [OBJ, I32, IP, VOUT]),
     "pdmpc_group_plan_step_chosen": (INT, [OBJ] + STEP + [DP, I32] + CHOSEN + [VOUT]),
