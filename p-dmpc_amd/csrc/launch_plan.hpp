@@ -251,16 +251,32 @@ inline int compute_lds_bulk(const Tuning& T, const LaunchDims& d, int n_launch, 
     return PDMPC_ERR_CAPACITY;
 }
 
-// LDS layout of the sampled optimizer (one wavefront per vehicle): MPA tables, reference, the wave's two shapes, offsets, obstacle
-// soup (with the predecessors' columns the packer counts into soup_cap), the candidate segments of one edge check, its tree
-// (288 nodes x (16 children + parent + trim) x 2 B; the random generator's state before the tree is set up) and its Hp * 250 random
-// numbers (32 000 B at Hp 16).  80 KB first (two workgroups per CU), then the whole 160 KB (one); the automaton's areas go to L2
-// before a layout takes the larger budget.
-inline int compute_lds_sampled(const Tuning& T, const LaunchDims& d, LaunchPlan& out, std::string& err) {
-    static_assert(288u * 16u * 2u >= 624u * 4u, "the tree region holds the generator's state");
-    for (int pass = 0; pass < 4; ++pass) {
-        const int areas = pass == 0 || pass == 2;
-        const size_t budget = pass < 2 ? kLdsMax / 2 : kLdsMax;
+// What a sampled launch decides besides its LaunchPlan (extra[4] of pdmpc_sampled_plan_host, include/pdmpc.h): the tree's rows, where the tree
+// lives, and how the random numbers are drawn.
+struct SampledExtra {
+    int node_cap = PDMPC_SB_DEFAULT_ROWS, tree_in_lds = 1;
+    int64_t tree_hbm_bytes = 0;  // per slot (0: the tree is in LDS)
+    int rand_chunk = 0;          // doubles drawn at a time
+    // ... and a seed ensemble (pdmpc_set_sampled_ensemble; extra[4..7] of pdmpc_sampled_ensemble_plan_host)
+    int members = 1;
+    int64_t member_bytes = 0;        // member records per slot (0 for one member: the slot's record is the only one)
+    int64_t ensemble_tree_bytes = 0; // HBM trees per slot, all members'
+    int64_t grid = 0;                // workgroups of a kernel launch
+};
+
+// LDS layout of the sampled optimizer (one wavefront per vehicle; sampled_search.hpp): MPA tables, reference, the wave's two shapes,
+// offsets, obstacle soup (with the predecessors' columns the packer counts into soup_cap), the candidate segments of one edge check,
+// then the tree (`tree_bytes`: rows of 36 B) and the random numbers (`rand_bytes`).  80 KB first (two workgroups per CU), then the whole
+// 160 KB (one); the automaton's areas go to L2 before a layout takes the larger budget.
+//   pdmpc_sampled_kernel          288 rows, then the whole stream of Hp * 250 doubles (32 000 B at Hp 16); the tree's region is the
+//                                 generator's state before the tree is set up.  The tree never leaves the LDS.
+//   any other budget, ensembles   the generator's 624 state words, then pdmpc_sb_node_cap(budget) rows.  `hbm_allowed`: where no rung
+//                                 holds the tree it goes to HBM (tree_in_lds = false) and the same ladder is walked without it.
+inline int layout_sampled(const Tuning& T, const LaunchDims& d, uint32_t tree_bytes, uint32_t rand_bytes, bool hbm_allowed, LaunchPlan& out, bool& tree_in_lds, std::string& err) {
+    for (int pass = 0; pass < (hbm_allowed ? 8 : 4); ++pass) {
+        const int areas = (pass & 1) == 0;
+        const size_t budget = (pass & 2) == 0 ? kLdsMax / 2 : kLdsMax;
+        tree_in_lds = pass < 4;
         LdsLayout L{};
         uint32_t off = layout_mpa(d, 0, areas, L);
         L.ref = off;
@@ -275,10 +291,17 @@ inline int compute_lds_sampled(const Tuning& T, const LaunchDims& d, LaunchPlan&
         off += align16((uint32_t)std::max(d.cand_cap, 1) * 4u);
         L.expand = off;
         off += (2 * PDMPC_HP_MAX * PDMPC_HP_MAX) * 8 + 16 * 16;
-        L.tree16 = off;
-        off += align16(288u * 18u * 2u);
+        // (a tree that may leave the LDS lies behind everything else)
+        if (!hbm_allowed) {
+            L.tree16 = off;
+            off += align16(tree_bytes);
+        }
         L.rand = off;
-        off += align16((uint32_t)d.Hp * 250u * 8u);
+        off += align16(rand_bytes);
+        if (hbm_allowed) {
+            L.tree16 = off;
+            if (tree_in_lds) off += align16(tree_bytes);
+        }
         L.total = align16(off);
         if (L.total <= budget) {
             static_cast<LaunchLayout&>(out) = {L, 1, 0, 0, areas, T.ready, false};  // (one wavefront, no ready list: the kernel reads none of the rounds' arguments)
@@ -289,59 +312,11 @@ inline int compute_lds_sampled(const Tuning& T, const LaunchDims& d, LaunchPlan&
     return PDMPC_ERR_CAPACITY;
 }
 
-// What a sampled launch decides besides its LaunchPlan (extra[4] of pdmpc_sampled_plan_host, include/pdmpc.h): the tree's rows, where the tree
-// lives, and how the random numbers are drawn.
-struct SampledExtra {
-    int node_cap = 288, tree_in_lds = 1;
-    int64_t tree_hbm_bytes = 0;  // per slot (0: the tree is in LDS)
-    int rand_chunk = 0;          // doubles drawn at a time
-    // ... and a seed ensemble (pdmpc_set_sampled_ensemble; extra[4..7] of pdmpc_sampled_ensemble_plan_host)
-    int members = 1;
-    int64_t member_bytes = 0;        // member records per slot (0 for one member: the slot's record is the only one)
-    int64_t ensemble_tree_bytes = 0; // HBM trees per slot, all members'
-    int64_t grid = 0;                // workgroups of a kernel launch
-};
-
-// LDS layout of the sampled optimizer with a budget other than 250 (sampled_budget_kernel.hip): compute_lds_sampled's regions, with a tree of
-// pdmpc_sb_node_cap(budget) rows of 36 B and, for the random numbers, the generator's 624 state words alone.  The tree goes in LDS
-// when the 80 KB, then the 160 KB, layout holds it (the automaton's areas go to L2 before a layout takes the larger budget, as
-// there); else it goes to HBM and the same ladder is walked without it.
-inline int layout_sampled_budget(const Tuning& T, const LaunchDims& d, uint32_t budget, LaunchPlan& out, SampledExtra& extra, std::string& err) {
-    const uint32_t tree_bytes = pdmpc_sb_tree_bytes(budget);
-    for (int pass = 0; pass < 8; ++pass) {
-        const int areas = (pass & 1) == 0;
-        const size_t lds_budget = (pass & 2) == 0 ? kLdsMax / 2 : kLdsMax;
-        const bool tree_in_lds = pass < 4;
-        LdsLayout L{};
-        uint32_t off = layout_mpa(d, 0, areas, L);
-        L.ref = off;
-        off += 3 * PDMPC_HP_MAX * 8;
-        L.shape = off;
-        off += (2 * PDMPC_VMAX + 1) * 16;
-        L.path = off;
-        off += PDMPC_LK_PATH_BYTES;
-        L.soup = off;
-        off = align16(off + (uint32_t)std::max(d.soup_cap, 1) * 16);
-        L.cand = off;
-        off += align16((uint32_t)std::max(d.cand_cap, 1) * 4u);
-        L.expand = off;
-        off += (2 * PDMPC_HP_MAX * PDMPC_HP_MAX) * 8 + 16 * 16;
-        L.rand = off;
-        off += align16(PDMPC_SB_MT_BYTES);
-        L.tree16 = off;
-        if (tree_in_lds) {
-            if ((size_t)off + tree_bytes > lds_budget) continue;
-            off += align16(tree_bytes);
-        }
-        L.total = align16(off);
-        if (L.total <= lds_budget) {
-            static_cast<LaunchLayout&>(out) = {L, 1, 0, 0, areas, T.ready, false};
-            extra = {(int)pdmpc_sb_node_cap(budget), tree_in_lds ? 1 : 0, tree_in_lds ? 0 : (int64_t)tree_bytes, PDMPC_SB_TWIST};
-            return PDMPC_OK;
-        }
-    }
-    err = "obstacle soup + MPA tables do not fit into the LDS budget of the sampled optimizer";
-    return PDMPC_ERR_CAPACITY;
+// ... of pdmpc_sampled_kernel (plan_launch)
+inline int compute_lds_sampled(const Tuning& T, const LaunchDims& d, LaunchPlan& out, std::string& err) {
+    static_assert(PDMPC_SB_DEFAULT_ROWS * PDMPC_SB_ROW * 2u >= PDMPC_SB_MT_BYTES, "the tree region holds the generator's state");
+    bool tree_in_lds;
+    return layout_sampled(T, d, PDMPC_SB_DEFAULT_ROWS * PDMPC_SB_ROW * 2u, (uint32_t)d.Hp * PDMPC_SAMPLED_BUDGET_DEFAULT * 8u, false, out, tree_in_lds, err);
 }
 
 // LDS layout of the joint search (one wavefront per problem): MPA tables, every vehicle's reference, the node's areas, offsets and the
@@ -522,8 +497,8 @@ inline int plan_launch(const Tuning& T, const LaunchDims& d, PlanKind kind, int 
 
 // The plan of a sampled launch of `count` vehicles with expansion budget `budget` (pdmpc_set_sampled_budget) and `members` members per
 // vehicle (pdmpc_set_sampled_ensemble).  One member: the reference's 250 is plan_launch's plan, field for field (pdmpc_sampled_kernel on
-// compute_lds_sampled's layout), and any other budget runs sampled_budget_kernel.hip on layout_sampled_budget's.  Two or more members
-// run sampled_ensemble_kernel.hip on layout_sampled_budget's at every budget, 250 included: count * members workgroups, and slices
+// compute_lds_sampled's layout), and any other budget runs sampled_budget_kernel.hip on layout_sampled's with the tree last.  Two or more
+// members run sampled_ensemble_kernel.hip on that layout at every budget, 250 included: count * members workgroups, and slices
 // of the safe mode that count slots -- as many as are resident with all their members.
 inline int plan_sampled(const Tuning& T, const LaunchDims& d, int budget, int members, int count, bool safe, LaunchPlan& p, SampledExtra& extra, std::string& err) {
     if (budget < 1 || budget > PDMPC_SAMPLED_BUDGET_MAX) {
@@ -543,7 +518,9 @@ inline int plan_sampled(const Tuning& T, const LaunchDims& d, int budget, int me
     }
     p = LaunchPlan{};
     p.slice = count;
-    if (const int rc = layout_sampled_budget(T, d, (uint32_t)budget, p, extra, err)) return rc;
+    bool tree_in_lds;
+    if (const int rc = layout_sampled(T, d, pdmpc_sb_tree_bytes((uint32_t)budget), PDMPC_SB_MT_BYTES, true, p, tree_in_lds, err)) return rc;
+    extra = {(int)pdmpc_sb_node_cap((uint32_t)budget), tree_in_lds ? 1 : 0, tree_in_lds ? 0 : (int64_t)pdmpc_sb_tree_bytes((uint32_t)budget), PDMPC_SB_TWIST};
     // the kernel ends its loop on n_nodes + Hp < node_cap like pdmpc_sampled_kernel; with n_nodes <= budget that must never bind
     if (!(budget + d.Hp < extra.node_cap) || 1 + budget + PDMPC_HP_MAX - 1 > 0xffff) {
         err = "plan_sampled: the tree's capacity does not cover the budget";

@@ -1,6 +1,6 @@
-// sampled_budget.h — what the host and sampled_budget_kernel.hip share: the arguments of the sampled optimizer with a run-time expansion
-// budget (pdmpc_set_sampled_budget) and its launchers.  The budget of MonteCarloTreeSearch.m:8 (250) keeps
-// pdmpc_sampled_kernel and KernelArgs; every other budget runs the kernels declared here.
+// sampled_budget.h — what the host and the sampled optimizer's kernels share: the tree's rows (sampled_search.hpp), and the arguments
+// of the sampled optimizer with a run-time expansion budget (pdmpc_set_sampled_budget) with its launchers.  The
+// budget of MonteCarloTreeSearch.m:8 (250) keeps pdmpc_sampled_kernel and KernelArgs; every other budget runs the kernels declared here.
 #pragma once
 #include "pdmpc_device.h"
 
@@ -11,6 +11,7 @@
 #define PDMPC_SB_ROW 18
 #define PDMPC_SB_TWIST 312 /* doubles of one twist of mt19937ar: the chunk the kernel draws its random numbers in */
 #define PDMPC_SB_MT_BYTES (624u * 4u)
+#define PDMPC_SB_DEFAULT_ROWS 288 /* pdmpc_sampled_kernel's tree: > 1 + 250 + PDMPC_HP_MAX */
 
 // Rows a tree of budget B has room for.  A descent starts with fewer than B expansions and at most one node per expansion behind the
 // root, n_nodes <= B, so `n_nodes + Hp < capacity` -- the guard pdmpc_sampled_kernel ends its loop on at 288 rows -- holds for ever
@@ -37,7 +38,7 @@ struct SampledBudgetArgs {
     uint32_t spin_limit;
     int32_t* tree_size;
     unsigned long long* work_count;
-    // the layout (launch_plan.hpp: layout_sampled_budget): tree16 holds the tree if it is in LDS, rand the generator's 624 state words
+    // the layout (launch_plan.hpp: layout_sampled): tree16 holds the tree if it is in LDS, rand the generator's 624 state words
     LdsLayout lds;
     int32_t budget;    // n_expansions_max
     int32_t node_cap;  // rows of a slot's tree (pdmpc_sb_node_cap)

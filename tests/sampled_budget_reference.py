@@ -110,8 +110,8 @@ def _apply(pose, m, c, s):
     return (pose[0] + t0, pose[1] + t1, pose[2] + t2)
 
 
-def search(options, sm, it, seed, budget, checker=None):
-    """One vehicle -> its record.  budget = n_expansions_max."""
+def search(options, sm, it, seed, budget, checker=None, tree_sizes=None):
+    """One vehicle -> its record.  budget = n_expansions_max.  tree_sizes: a list that receives the tree's nodes, the root included."""
     Hp = options.Hp
     if checker is None:
         checker = abi.CHECK_INTERX if options.are_any_obstacles_non_convex else abi.CHECK_SAT
@@ -193,6 +193,8 @@ def search(options, sm, it, seed, budget, checker=None):
             if best is None or solution_cost < best[0]:
                 best = (solution_cost, node_id)
             del children[node_parent][child_position]  # avoid double exploration
+    if tree_sizes is not None:
+        tree_sizes.append(len(trims) - 1)
     rec["n_expanded"] = n_expansions  # :209
     rec["n_popped"] = n_traversals
     if best is None:  # :212-215
@@ -221,12 +223,13 @@ def search(options, sm, it, seed, budget, checker=None):
     return rec
 
 
-def plan_batch_sampled(options, mpa, iters, seeds, budget=DEFAULT_BUDGET, checker=None):
-    """The records pdmpc_plan_batch_sampled returns for `iters` on a handle with pdmpc_set_sampled_budget(budget)."""
+def plan_batch_sampled(options, mpa, iters, seeds, budget=DEFAULT_BUDGET, checker=None, tree_sizes=None):
+    """The records pdmpc_plan_batch_sampled returns for `iters` on a handle with pdmpc_set_sampled_budget(budget); tree_sizes: as in
+    search, one entry per vehicle."""
     sm = mpa if isinstance(mpa, SampledMpa) else SampledMpa(mpa)
     out = np.zeros(len(iters), dtype=abi.VEHICLE_OUT_DTYPE)
     for i, (it, seed) in enumerate(zip(iters, seeds)):
-        out[i] = search(options, sm, it, seed, budget, checker)
+        out[i] = search(options, sm, it, seed, budget, checker, tree_sizes)
     return out
 
 

@@ -1,5 +1,5 @@
-"""Build-time properties of the sampled optimizer's kernels with a run-time budget (csrc/sampled_budget_kernel.hip; no GPU needed: hipcc
-cross-compiles gfx950 code objects)."""
+"""Build-time properties of the sampled optimizer's kernels (csrc/sampled_search.hpp's body in sampled_kernel.hip, sampled_budget_kernel.hip
+and sampled_ensemble_kernel.hip; no GPU needed: hipcc cross-compiles gfx950 code objects)."""
 import os
 import re
 import shutil
@@ -12,13 +12,16 @@ CSRC = os.path.join(ROOT, "p-dmpc_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 SAMPLED_BUDGET_KERNELS = ("pdmpc_sampled_budget_kernel", "pdmpc_sampled_budget_kernel_hbm", "pdmpc_debug_random_stream_kernel")
+# ... and the other users of the one search body
+SAMPLED_SEARCH_KERNELS = ("pdmpc_sampled_kernel", "pdmpc_sampled_ensemble_kernel", "pdmpc_sampled_ensemble_kernel_hbm")
+SAMPLED_FILES = ("sampled_budget_kernel.hip", "sampled_kernel.hip", "sampled_ensemble_kernel.hip")
 
 
 @pytest.mark.timeout(300)
 def test_sampled_budget_kernels_use_no_scratch_memory_and_spill_no_vector_register():
     """`make` builds sampled_budget_kernel.hip and `make resources` lists it with the other kernels; its kernels -- the tree in LDS, the
     tree in HBM, the generator alone -- use no scratch memory and spill no vector register, and a wavefront's registers leave room for
-    four per SIMD like pdmpc_sampled_kernel's."""
+    four per SIMD.  The same holds for the search body's other kernels: pdmpc_sampled_kernel and the two ensemble kernels."""
     if not os.path.exists(HIPCC) and shutil.which("hipcc") is None:
         pytest.skip("no hipcc")
     with open(os.path.join(CSRC, "Makefile")) as f:
@@ -26,7 +29,7 @@ def test_sampled_budget_kernels_use_no_scratch_memory_and_spill_no_vector_regist
     for var in ("SRCS", "RESOURCE_SRCS"):
         listed = [line for line in lines if line.startswith(var)]
         assert listed and "sampled_budget_kernel.hip" in listed[0], "%s does not cover sampled_budget_kernel.hip" % var
-    out = subprocess.run(["make", "-s", "-C", CSRC, "resources", "RESOURCE_SRCS=sampled_budget_kernel.hip"], capture_output=True, text=True, check=True).stdout
+    out = subprocess.run(["make", "-s", "-C", CSRC, "resources", "RESOURCE_SRCS=" + " ".join(SAMPLED_FILES)], capture_output=True, text=True, check=True).stdout
     seen, name = {}, None
     for line in out.splitlines():
         m = re.search(r"Function Name: (\w+)", line)
@@ -38,7 +41,7 @@ def test_sampled_budget_kernels_use_no_scratch_memory_and_spill_no_vector_regist
             m = re.search(pat, line)
             if m and name:
                 seen[name][key] = int(m.group(1))
-    for kernel in SAMPLED_BUDGET_KERNELS:
+    for kernel in SAMPLED_BUDGET_KERNELS + SAMPLED_SEARCH_KERNELS:
         assert kernel in seen, seen.keys()
         assert seen[kernel]["scratch"] == 0 and seen[kernel]["vgpr_spill"] == 0, (kernel, seen[kernel])
         assert seen[kernel]["vgprs"] <= 128, (kernel, seen[kernel])

@@ -145,6 +145,40 @@ def test_the_budget_ends_the_search_on_a_free_road(free_road, budget):
     assert again.tobytes() == got.tobytes()
 
 
+@pytest.mark.parametrize("mode", ["interx", "sat"])
+def test_the_default_kernel_at_the_longest_horizon(mode):
+    """pdmpc_sampled_kernel at Hp = PDMPC_HP_MAX = 16 and its own budget of 250, on a free road: its stream drawn ahead is at its longest
+    (4 000 doubles: 13 twists, with the tree's region as the generator's state) and its tree at its tallest (a descent adds up to 16
+    rows; up to 265 of the 288).  Two vehicles, the second 0.3 m beside the first and coupled to it, so the first's areas cut some of
+    its edges: records and tree sizes byte for byte."""
+    options = problems.make_options(mode, Hp=16)
+    mpa = get_mpa(options)
+    rng = np.random.default_rng(9)
+    iters = [problems.road_problem(rng, options, mpa, n_dyn=0, n_static=0, with_boundary=False, convex=(mode == "sat")) for _ in range(2)]
+    beside = copy.copy(iters[1])
+    beside.x0 = np.array(beside.x0, dtype=np.float64) + np.array([0.0, 0.3, 0.0, 0.0])
+    beside.reference_trajectory_points = np.array(beside.reference_trajectory_points, dtype=np.float64) + np.array([0.0, 0.3])
+    iters[1] = beside
+    prob = {"iters": iters, "preds": [[], [0]], "fallback": [None, None], "level_sizes": [1, 1]}
+    seeds, sm, sizes = [11, 12], sbr.SampledMpa(mpa), []
+    want = sbr.plan_step_sampled(options, mpa, prob, seeds, lambda its, sd: sbr.plan_batch_sampled(options, sm, its, sd, budget=250, tree_sizes=sizes))
+    assert np.all(want["n_expanded"] >= 250) and np.all(want["status"] == 0) and sizes[0] == 1 + int(want["n_expanded"][0])
+    assert want[1].tobytes() != sbr.plan_batch_sampled(options, sm, [beside], seeds[1:], budget=250)[0].tobytes(), "the hand-over changes nothing"
+    h = handle_for(options, mpa, max_vehicles=4)
+    got = plan_step_gpu(h, prob, seeds)
+    assert h.last_sampled_kernel() == OLD_KERNEL
+    st = h.stats()
+    assert st["kernel"] == 3 and st["n_launches"] == 1 and st["safe_replans"] == 0
+    got_sizes = []
+    for v in range(2):
+        n = C.c_int32(-1)
+        assert h.L.pdmpc_debug_tree(h.h, v, 0, None, None, None, None, None, None, None, None, C.byref(n)) == 0
+        got_sizes.append(n.value)
+    h.close()
+    assert_records_equal(got, want, "%s, Hp 16, default budget" % mode)
+    assert got_sizes == sizes
+
+
 def boxed_in_problem():
     """tests/test_gpu_sampled_step.py's: slot 0 is boxed in by an obstacle, its fallback areas lie across slot 1's way."""
     from pdmpc.reference_trajectory import get_occupied_areas
