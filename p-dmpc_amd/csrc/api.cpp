@@ -29,10 +29,7 @@
 
 namespace {
 
-thread_local std::string g_err;  // pdmpc_last_error: every translation unit reports through pdmpc_set_last_error (fail, handle.hpp)
-
-// what a host-only part returned, its message in err, as this library reports it
-int failed(int rc, const std::string& err) { return rc ? fail(rc, err) : PDMPC_OK; }
+thread_local std::string g_err;  // pdmpc_last_error: every translation unit reports through pdmpc_set_last_error (fail, hip_host.hpp)
 
 // The dynamic LDS size of a kernel is an attribute of the function ON THE DEVICE, not of a handle (hipFuncSetAttribute sets a
 // maximum): the largest size set so far is kept per device, kernel (0 bulk, 1 bulk wide, 2 bulk SAT, 3 bulk compact) and instantiation
@@ -644,12 +641,6 @@ int fetch_lean(pdmpc_handle* h, int32_t n, int32_t* status, double* cost) {
 
 // ---- the choice among the plans of a batch (pdmpc_choice, include/pdmpc.h; choice_kernel.hip)
 
-// what pdmpc_choice promises (choice_host.hpp: check_choice), checked before anything is launched or summed
-int checked_choice(int32_t n, const pdmpc_choice* ch) {
-    std::string err;
-    return failed(check_choice(n, ch, err), err);
-}
-
 // The lists of a checked choice on the n records of the current bank, staged in pinned memory with the caller's slots mapped to the
 // bank's (a batch that pack_common put into its own order) and queued for the device; A: what the kernels take.
 int stage_choice(pdmpc_handle* h, int32_t n, const pdmpc_choice& ch, const ChoiceLayout& L, ChoiceArgs& A) {
@@ -657,27 +648,15 @@ int stage_choice(pdmpc_handle* h, int32_t n, const pdmpc_choice& ch, const Choic
     const bool permuted = !B.perm.empty();
     if (permuted ? n != B.n_packed : n > h->max_vehicles) return fail(PDMPC_ERR_INVALID, "pdmpc_choice: the batch is not the one resident in this bank");
     ChoiceState& S = h->choice;
-    const int n_cell_slots = ch.n_cells > 0 ? ch.cell_offset[ch.n_cells] : 0, n_pick_slots = ch.n_picks > 0 ? ch.pick_offset[ch.n_picks] : 0;
-    const size_t cell_offset = 0, cell_slot = cell_offset + (size_t)ch.n_cells + 1, graph_offset = cell_slot + (size_t)n_cell_slots, pick_graph = graph_offset + (size_t)ch.n_graphs + 1,
-                 pick_offset = pick_graph + (size_t)ch.n_picks, pick_slot = pick_offset + (size_t)ch.n_picks + 1, words = pick_slot + (size_t)n_pick_slots;
+    const ChoiceLists W(ch);
     const bool first_use = !S.tally.p;
-    if (S.h_in.ensure(words) || S.h_out.ensure(L.bytes)) return fail(PDMPC_ERR_HIP, "hipHostMalloc failed for the choice");
-    if (S.in.ensure(words) || S.out.ensure(L.bytes) || S.tally.ensure(PDMPC_CHOICE_COUNTERS)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the choice");
+    if (S.h_in.ensure(W.words) || S.h_out.ensure(L.bytes)) return fail(PDMPC_ERR_HIP, "hipHostMalloc failed for the choice");
+    if (S.in.ensure(W.words) || S.out.ensure(L.bytes) || S.tally.ensure(PDMPC_CHOICE_COUNTERS)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the choice");
     if (first_use) HIPCHK(hipMemsetAsync(S.tally.p, 0, PDMPC_CHOICE_COUNTERS * sizeof(int32_t), h->stream));
-    int32_t* w = S.h_in.p;
-    auto to_bank = [&](int32_t* dst, const int32_t* slot, int count) {
-        for (int q = 0; q < count; ++q) dst[q] = permuted ? B.inv[(size_t)slot[q]] : slot[q];
-    };
-    w[cell_offset] = w[graph_offset] = w[pick_offset] = 0;
-    if (ch.n_cells > 0) std::memcpy(w + cell_offset, ch.cell_offset, ((size_t)ch.n_cells + 1) * sizeof(int32_t));
-    to_bank(w + cell_slot, ch.cell_slot, n_cell_slots);
-    if (ch.n_graphs > 0) std::memcpy(w + graph_offset, ch.graph_offset, ((size_t)ch.n_graphs + 1) * sizeof(int32_t));
-    if (ch.n_picks > 0) {
-        std::memcpy(w + pick_graph, ch.pick_graph, (size_t)ch.n_picks * sizeof(int32_t));
-        std::memcpy(w + pick_offset, ch.pick_offset, ((size_t)ch.n_picks + 1) * sizeof(int32_t));
-    }
-    to_bank(w + pick_slot, ch.pick_slot, n_pick_slots);
-    HIPCHK(hipMemcpyAsync(S.in.p, w, words * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    stage_choice_lists(ch, W, S.h_in.p, [&](const int32_t* slot, int count, int32_t* to) {
+        for (int q = 0; q < count; ++q) to[q] = permuted ? B.inv[(size_t)slot[q]] : slot[q];
+    });
+    HIPCHK(hipMemcpyAsync(S.in.p, S.h_in.p, W.words * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     A = ChoiceArgs{};
     A.rec = h->d_out.p;
     A.n = n;
@@ -687,12 +666,12 @@ int stage_choice(pdmpc_handle* h, int32_t n, const pdmpc_choice& ch, const Choic
     A.n_picks = ch.n_picks;
     A.first_graph_cell = ch.n_graphs > 0 ? ch.graph_offset[0] : 0;
     A.end_graph_cell = ch.n_graphs > 0 ? ch.graph_offset[ch.n_graphs] : 0;
-    A.cell_offset = S.in.p + cell_offset;
-    A.cell_slot = S.in.p + cell_slot;
-    A.graph_offset = S.in.p + graph_offset;
-    A.pick_graph = S.in.p + pick_graph;
-    A.pick_offset = S.in.p + pick_offset;
-    A.pick_slot = S.in.p + pick_slot;
+    A.cell_offset = S.in.p + W.cell_offset;
+    A.cell_slot = S.in.p + W.cell_slot;
+    A.graph_offset = S.in.p + W.graph_offset;
+    A.pick_graph = S.in.p + W.pick_graph;
+    A.pick_offset = S.in.p + W.pick_offset;
+    A.pick_slot = S.in.p + W.pick_slot;
     A.tally = S.tally.p;
     A.counters = (int32_t*)S.out.p;
     A.chosen = (int32_t*)(S.out.p + L.chosen);
@@ -716,16 +695,10 @@ int fetch_choice(pdmpc_handle* h, const ChoiceArgs& A, const ChoiceLayout& L) {
     return PDMPC_OK;
 }
 
-// a fetched choice into the caller's arrays; a record that is no planning result fails it as it fails the choice on the host
-int deliver_choice(const pdmpc_handle* h, const pdmpc_choice& ch, const ChoiceLayout& L, int32_t* chosen, double* cell_cost, pdmpc_vehicle_out* picks) {
-    const unsigned char* blk = h->choice.h_out.p;
-    const int32_t* counters = (const int32_t*)blk;
-    if (counters[PDMPC_CHOICE_OVERFLOW] || counters[PDMPC_CHOICE_TIMED_OUT] || counters[PDMPC_CHOICE_OTHER])
-        return fail(PDMPC_ERR_HIP, "a result record carries an error status: not a planning result");
-    if (chosen && ch.n_graphs > 0) std::memcpy(chosen, blk + L.chosen, (size_t)ch.n_graphs * sizeof(int32_t));
-    if (cell_cost && ch.n_cells > 0) std::memcpy(cell_cost, blk + L.cell_cost, (size_t)ch.n_cells * sizeof(double));
-    if (ch.n_picks > 0) std::memcpy(picks, blk + L.picks, (size_t)ch.n_picks * sizeof(pdmpc_vehicle_out));
-    return PDMPC_OK;
+// a fetched choice into the caller's arrays (choice_host.hpp), or why it is none
+int deliver_fetched(const pdmpc_handle* h, const pdmpc_choice& ch, const ChoiceLayout& L, int32_t* chosen, double* cell_cost, pdmpc_vehicle_out* picks) {
+    std::string err;
+    return deliver_choice(ch, L, h->choice.h_out.p, chosen, cell_cost, picks, err) ? PDMPC_OK : fail(PDMPC_ERR_HIP, err);
 }
 
 // Where a plan's read-back lands: every record, (lean) the (status, cost) pair of every vehicle (fetch_lean), or (chosen) the block of
@@ -891,7 +864,7 @@ int pdmpc_choose_resident(pdmpc_handle* h, int32_t n, const pdmpc_choice* ch, in
     ChoiceArgs A;
     int rc = stage_choice(h, n, *ch, L, A);
     if (!rc) rc = fetch_choice(h, A, L);
-    return rc ? rc : deliver_choice(h, *ch, L, chosen, cell_cost, picks);
+    return rc ? rc : deliver_fetched(h, *ch, L, chosen, cell_cost, picks);
 }
 
 int pdmpc_plan_step_chosen(pdmpc_handle* h, int32_t n, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index, const pdmpc_polygon_set* fallback_shapes,
@@ -905,7 +878,7 @@ int pdmpc_plan_step_chosen(pdmpc_handle* h, int32_t n, const pdmpc_vehicle_in* i
     ChoiceArgs A;
     rc = stage_choice(h, n, *ch, L, A);  // (once: a launch that is repeated with larger arenas or in slices chooses on the same lists)
     if (!rc) rc = plan_packed_growing(h, n, Sink::chosen(&A, &L));
-    return rc ? rc : deliver_choice(h, *ch, L, chosen, cell_cost, picks);
+    return rc ? rc : deliver_fetched(h, *ch, L, chosen, cell_cost, picks);
 }
 
 int pdmpc_choice_kernel_ms(pdmpc_handle* h, double* ms) {

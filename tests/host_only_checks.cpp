@@ -1,5 +1,5 @@
 // host_only_checks.cpp — the host-only parts of p-dmpc_amd/csrc (reference_tree.hpp, mpa_reach.hpp, choice_host.hpp) against expectations that
-// do not share their rules: a literal best-first search, an enumeration of every trim path, values written out.  A stand-alone program
+// do not share their rules: a literal best-first search, an enumeration of every trim path, values and staged words written out.  A stand-alone program
 // (tests/test_host_only_parts.py builds it with the host compiler under the address and undefined-behaviour sanitizers and runs it): exit
 // status 0 and "host-only checks ok", or 1 and a line that names the first case that failed.
 #include <cmath>
@@ -344,6 +344,69 @@ void expect_refusal(const char* want, int32_t n, const pdmpc_choice* ch) {
     if (rc != PDMPC_ERR_INVALID || err != want) failed("check_choice: returned %d '%s', not PDMPC_ERR_INVALID '%s'", rc, err.c_str(), want);
 }
 
+// the words a choice is staged in for the kernels, against arrays written out by hand: cell_offset | cell slots | graph_offset | pick_graph |
+// pick_offset | pick slots
+void expect_words(const char* what, const pdmpc_choice& ch, const std::vector<int32_t>& perm, const std::vector<int32_t>& want) {
+    const ChoiceLists W(ch);
+    if (W.words != want.size()) failed("ChoiceLists (%s): %zu words, not %zu", what, W.words, want.size());
+    std::vector<int32_t> w(W.words, -99);  // (exactly as many: the sanitizer sees a word written beyond them)
+    stage_choice_lists(ch, W, w.data(), [&perm](const int32_t* slot, int count, int32_t* to) {
+        for (int q = 0; q < count; ++q) to[q] = perm.empty() ? slot[q] : perm[(size_t)slot[q]];
+    });
+    for (size_t q = 0; q < want.size(); ++q)
+        if (w[q] != want[q]) failed("stage_choice_lists (%s): word %zu is %d, not %d", what, q, w[q], want[q]);
+}
+
+void check_staged_lists(const pdmpc_choice& good) {
+    const ChoiceLists W(good);
+    if (W.cell_offset != 0 || W.cell_slot != 6 || W.graph_offset != 13 || W.pick_graph != 16 || W.pick_offset != 18 || W.pick_slot != 21 || W.words != 25)
+        failed("ChoiceLists: (%zu, %zu, %zu, %zu, %zu, %zu, %zu)", W.cell_offset, W.cell_slot, W.graph_offset, W.pick_graph, W.pick_offset, W.pick_slot, W.words);
+    expect_words("identity", good, {}, {0, 2, 4, 5, 6, 7, /**/ 0, 1, 2, 0, 4, 1, 3, /**/ 0, 3, 5, /**/ 0, -1, /**/ 0, 3, 4, /**/ 0, 2, 4, 3});
+    // slot s is found at perm[s]: offsets and pick_graph are no slots and stay
+    expect_words("permuted", good, {3, 0, 4, 1, 2}, {0, 2, 4, 5, 6, 7, /**/ 3, 0, 4, 3, 2, 0, 1, /**/ 0, 3, 5, /**/ 0, -1, /**/ 0, 3, 4, /**/ 3, 4, 2, 1});
+    // no cell, no graph, no pick: the three offset lists are their first entry, 0, and no list is read
+    const pdmpc_choice none{0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    expect_words("empty", none, {}, {0, 0, 0});
+}
+
+// a block as the device leaves it, built by hand, into the caller's arrays; a counter of records that are no planning results refuses it
+void check_delivery(const pdmpc_choice& good, const ChoiceLayout& L) {
+    const char* refusal = "a result record carries an error status: not a planning result";
+    std::vector<unsigned char> blk(L.bytes, 0);
+    const int32_t want_chosen[2] = {2, 0};
+    const double want_cost[5] = {3.0, std::numeric_limits<double>::infinity(), 0.12345679, 2.0, 2.0};
+    std::vector<pdmpc_vehicle_out> want_picks(2);
+    for (size_t i = 0; i < 2; ++i) std::memset(&want_picks[i], (int)(0x5a + i), sizeof(pdmpc_vehicle_out));
+    std::memcpy(blk.data() + 16, want_chosen, sizeof want_chosen);
+    std::memcpy(blk.data() + 24, want_cost, sizeof want_cost);
+    std::memcpy(blk.data() + 64, want_picks.data(), 2 * sizeof(pdmpc_vehicle_out));
+    for (int without = 0; without < 3; ++without) {  // 0: every array; 1: chosen null; 2: cell_cost null
+        int32_t chosen[2] = {-1, -1};
+        double cell_cost[5] = {-1, -1, -1, -1, -1};
+        std::vector<pdmpc_vehicle_out> picks(2);
+        std::string err = "unset";
+        if (!deliver_choice(good, L, blk.data(), without == 1 ? nullptr : chosen, without == 2 ? nullptr : cell_cost, picks.data(), err) || err != "unset")
+            failed("deliver_choice (%d): a block of planning results is refused: %s", without, err.c_str());
+        const int32_t untouched_chosen[2] = {-1, -1};
+        const double untouched_cost[5] = {-1, -1, -1, -1, -1};
+        if (std::memcmp(chosen, without == 1 ? untouched_chosen : want_chosen, sizeof chosen) != 0) failed("deliver_choice (%d): chosen differs", without);
+        if (std::memcmp(cell_cost, without == 2 ? untouched_cost : want_cost, sizeof cell_cost) != 0) failed("deliver_choice (%d): cell_cost differs", without);
+        if (std::memcmp(picks.data(), want_picks.data(), 2 * sizeof(pdmpc_vehicle_out)) != 0) failed("deliver_choice (%d): the picked records differ", without);
+    }
+    for (int counter : {(int)PDMPC_CHOICE_OVERFLOW, (int)PDMPC_CHOICE_TIMED_OUT, (int)PDMPC_CHOICE_OTHER}) {
+        std::vector<unsigned char> bad = blk;
+        const int32_t one = 1;
+        std::memcpy(bad.data() + (size_t)counter * sizeof one, &one, sizeof one);
+        int32_t chosen[2] = {-1, -1};
+        double cell_cost[5] = {-1, -1, -1, -1, -1};
+        std::vector<pdmpc_vehicle_out> picks(2);
+        std::string err;
+        if (deliver_choice(good, L, bad.data(), chosen, cell_cost, picks.data(), err)) failed("deliver_choice: a block with counter %d set is delivered", counter);
+        if (err != refusal) failed("deliver_choice: counter %d is refused with '%s'", counter, err.c_str());
+        if (chosen[0] != -1 || cell_cost[0] != -1) failed("deliver_choice: a refused block was delivered in part (counter %d)", counter);
+    }
+}
+
 void check_choices() {
     // five records; graph 0 chooses among cells 0 .. 2, graph 1 among cells 3 and 4; pick 0 follows graph 0, pick 1 its own slot
     const int32_t status[] = {PDMPC_OK, PDMPC_OK, PDMPC_EXHAUSTED, PDMPC_OK, PDMPC_OK};
@@ -364,6 +427,9 @@ void check_choices() {
     choose_host(status, cost, &good, nullptr, nullptr);  // (both outputs are optional)
     const ChoiceLayout L(good);
     if (L.chosen != 16 || L.cell_cost != 24 || L.picks != 64 || L.bytes != 64 + 2 * sizeof(pdmpc_vehicle_out)) failed("ChoiceLayout: (%zu, %zu, %zu, %zu)", L.chosen, L.cell_cost, L.picks, L.bytes);
+
+    check_staged_lists(good);
+    check_delivery(good, L);
 
     // every refusal once, in the order of the checks
     expect_refusal("pdmpc_choice: bad argument", 5, nullptr);

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from pdmpc import abi
-from pdmpc.backend import BackendError, Choice, Group, choose_host_call
+from pdmpc.backend import COLLECTIVE_COPY, COLLECTIVE_RCCL, BackendError, Choice, Group, choose_host_call
 from pdmpc.config import Config, ScenarioType
 
 from test_choice import ARENA_OVERFLOW, ERR_HIP, EXHAUSTED, OK, lean
@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 REC = abi.VEHICLE_OUT_DTYPE.itemsize
 ENTRY = 16  # bytes of a record's entry in the exchange
 COUNTERS = 4  # status counters of the block the host reads (int32 each)
+ERR_NO_DEVICE = -2
 WORLDS = [2, 4]
 
 
@@ -213,3 +214,61 @@ def test_the_exchange_grows_with_the_entries_not_with_the_records(group):
     assert seen[1]["collective_bytes"] - seen[0]["collective_bytes"] == ENTRY * 56  # 56 more records per rank
     assert seen[1]["collective_bytes"] < REC  # ... all of a rank's entries are less than ONE record
     assert seen[0]["host_bytes"] == seen[1]["host_bytes"] == 3 * REC + 8 * 8 + (COUNTERS * 4 + 4 + 7) // 8 * 8
+
+
+def _fresh_pair():
+    options = Config(scenario_type=ScenarioType.commonroad, Hp=HP, max_vehicles=16, max_nodes=1 << 10)
+    g = Group(options, n_devices=2, devices=[0, 0], collective=COLLECTIVE_COPY)
+    assert g.collective == "copy"
+    return g
+
+
+def test_every_buffer_of_a_choice_grows_and_the_small_choice_still_holds():
+    """The smallest choice (1 graph, 2 cells, 1 pick) on a fresh group of 2 logical ranks, then one that outgrows everything the first call
+    left, then the small one again: each equal to the host twin, the picked records byte for byte."""
+    rng = np.random.default_rng(8)
+    small = Choice([[0], [1]], [2], [(0, [0, 1])])
+    small_recs, small_ranks = records(rng, 2), np.array([0, 1], dtype=np.int32)
+    # The first call asks for 12 list words, blocks of 2 entries (32 bytes; 64 received), 40 bytes of chosen and cell costs, 2 placed records
+    # per rank and a host block of 40 bytes + 1 record.  A buffer grows to 3/2 of what is asked, and of 64 elements at least (DevBuf and
+    # PinnedBuf, csrc/hip_host.hpp): 96 words, 96 and 96 bytes, 96 bytes, 96 records, 60 bytes + 1.5 records.  So 100 records per rank
+    # (101 placed, blocks of 101 entries = 1 616 bytes), 100 cells in 2 graphs (315 list words, 824 bytes of chosen and cell costs) and
+    # 4 picks (a host block beyond 4 records) outgrow each of them.
+    n = 200
+    large_recs, large_ranks = records(rng, n), (np.arange(n) % 2).astype(np.int32)
+    large = Choice([[c] for c in range(100)], [50, 50], [(0, list(range(100, 150))), (1, list(range(150, 200))), (-1, [7]), (-1, [150])])
+    assert host_block_bytes(large) > 4 * REC > 1.5 * host_block_bytes(small)
+    g = _fresh_pair()
+    try:
+        assert_group_is_host(g, small_recs, small_ranks, small, "small, fresh group")
+        assert_group_is_host(g, large_recs, large_ranks, large, "large, every buffer grows")
+        assert_group_is_host(g, small_recs, small_ranks, small, "small, after the growth")
+    finally:
+        g.close()
+
+
+def test_groups_come_and_go_and_a_refused_create_leaves_a_working_library():
+    """Three groups made and destroyed in one process, a refused create in between (a device listed twice with the RCCL collective: an
+    argument refusal, nothing is launched), and the group made after it plans a 2-vehicle step as the single handle does."""
+    import problems
+    from pdmpc.backend import Handle
+    from test_gpu_parity import assert_records_equal
+
+    options, mpa, iters = problems.problem_set("interx", 11, 2, Hp=HP, max_vehicles=8, max_nodes=1 << 14)
+    preds = [[] for _ in iters]
+    single = Handle(options)
+    single.upload_mpa(mpa)
+    ref = single.plan_step(iters, preds, None)
+    single.close()
+    for round_ in range(3):
+        g = Group(options, n_devices=2, devices=[0, 0], collective=COLLECTIVE_COPY)
+        try:
+            g.upload_mpa(mpa)
+            assert_records_equal(g.plan_step(iters, preds, None), ref, "group %d" % round_)
+        finally:
+            g.close()
+        if round_ == 1:
+            with pytest.raises(BackendError) as e:
+                Group(options, n_devices=2, devices=[0, 0], collective=COLLECTIVE_RCCL)
+            assert e.value.status == ERR_NO_DEVICE
+            assert str(e.value).endswith("pdmpc_group_create: a device listed twice needs PDMPC_COLLECTIVE_COPY (RCCL has one rank per device)")
