@@ -26,6 +26,7 @@
 #include "handle.hpp"
 #include "mpa_reach.hpp"
 #include "reference_tree.hpp"
+#include "sampled_launch.hpp"
 
 namespace {
 
@@ -37,32 +38,12 @@ thread_local std::string g_err;  // pdmpc_last_error: every translation unit rep
 std::mutex g_lds_mutex;
 uint32_t g_lds_high_water[64][4][2];
 
-// what the graph search, the sampled optimizer and the joint search (KernelArgs, JointArgs) all read: the automaton, the packed
-// batch, the records, the arenas' size, the tree sizes and work counters
-template <class Args>
-void set_batch_args(const pdmpc_handle* h, const PackedStep& B, int areas_in_lds, Args& a) {
-    a.succ_mask = h->d_mask.p;
-    a.man_index = h->d_mi.p;
-    a.man_pose = h->d_pose.p;
-    a.man_area = h->d_area.p;
-    a.n_trims = h->n_trims;
-    a.n_words = h->n_words;
-    a.n_man = h->n_man;
-    a.Hp = h->cfg.Hp;
-    a.areas_in_lds = areas_in_lds;
-    a.dt = h->cfg.dt_seconds;
-    a.veh = B.dev.veh;
-    a.points = B.dev.pts;
-    a.out = h->d_out.p;
-    a.max_nodes = h->arena.max_nodes;
-    a.tree_size = h->d_tree_size.p;
-    a.work_count = h->d_work_count.p;
-}
-
-// what a launch reads besides the batch: its plan (set_plan_args), the handle's buffers, the launch's number
+// what a search launch reads besides the batch: its plan (set_plan_args), the handle's buffers, the launch's number
 void set_launch_args(pdmpc_handle* h, const PackedStep& B, const LaunchPlan& plan, int first, int count, KernelArgs& a) {
     set_batch_args(h, B, plan.areas_in_lds, a);
     set_plan_args(h->tune, plan, a);
+    a.dt = h->cfg.dt_seconds;
+    a.max_nodes = h->arena.max_nodes;
     a.checker = h->cfg.checker;
     a.pred = B.dev.pred;
     a.done_flag = h->d_flag.p;
@@ -87,38 +68,6 @@ void set_launch_args(pdmpc_handle* h, const PackedStep& B, const LaunchPlan& pla
     a.n_searches = count;
 }
 
-// what sampled_budget_kernel.hip reads of a sampled launch's arguments (its own record: KernelArgs does not grow with the budget)
-SampledBudgetArgs sampled_budget_args(const KernelArgs& a, int budget, int node_cap, uint16_t* tree) {
-    SampledBudgetArgs s{};
-    s.succ_mask = a.succ_mask;
-    s.man_index = a.man_index;
-    s.man_pose = a.man_pose;
-    s.man_area = a.man_area;
-    s.n_trims = a.n_trims;
-    s.n_words = a.n_words;
-    s.n_man = a.n_man;
-    s.Hp = a.Hp;
-    s.checker = a.checker;
-    s.areas_in_lds = a.areas_in_lds;
-    s.veh = a.veh;
-    s.points = a.points;
-    s.pred = a.pred;
-    s.out = a.out;
-    s.done_flag = a.done_flag;
-    s.epoch = a.epoch;
-    s.first = a.first;
-    s.n_searches = a.n_searches;
-    s.reverse_dispatch = a.reverse_dispatch;
-    s.spin_limit = a.spin_limit;
-    s.tree_size = a.tree_size;
-    s.work_count = a.work_count;
-    s.lds = a.lds;
-    s.budget = budget;
-    s.node_cap = node_cap;
-    s.tree = tree;
-    return s;
-}
-
 // The helper boards of a launch with helper workgroups: where its count of finished searches starts (KernelArgs::help_fin_base).
 int prepare_boards(pdmpc_handle* h, int count, uint32_t& fin_base) {
     fin_base = 0;
@@ -137,89 +86,61 @@ int prepare_boards(pdmpc_handle* h, int count, uint32_t& fin_base) {
     return PDMPC_OK;
 }
 
-// The kernel launches of one launch_range, plan.slice searches each; returns the hipError_t of the first that failed.
-// Oversubscribed launches (more searches than CUs).  A resident search spins for predecessors of the same launch; slots are in
-// level order (the packer sees to it: coupling_order.hpp), so as long as the hardware hands out workgroups in index order every
-// predecessor was dispatched before its successors and the launch cannot stall.  That order is not a documented guarantee: should a
-// launch ever stall, the watchdog (spin_limit) ends the waiting searches with an error status and plan_packed_growing plans the call
-// again with safe == true, in slices that are resident as a whole (a slice's predecessors are in it or in an earlier slice) -- forward
-// progress then needs no assumption at all.
-int dispatch(const pdmpc_handle* h, const KernelArgs& a, const LaunchPlan& plan, bool search, const SampledBudgetArgs* budgeted = nullptr, int members = 1) {
-    typedef int (*launcher_t)(const KernelArgs*, int, void*, uint32_t*);
-    static const launcher_t launchers[4][2] = {{pdmpc_launch_bulk, pdmpc_launch_bulk_any},
-                                               {pdmpc_launch_bulk_wide, pdmpc_launch_bulk_wide_any},
-                                               {pdmpc_launch_bulk_sat, pdmpc_launch_bulk_sat_any},
-                                               {pdmpc_launch_bulk_compact, pdmpc_launch_bulk_compact_any}};
-    const int variant = plan.variant, generic = plan.generic ? 1 : 0;
-    int lrc = 0;
-    for (int done = 0; done < a.n_searches && lrc == 0; done += plan.slice) {
-        KernelArgs part = a;
-        part.first = a.first + done;
-        part.n_searches = std::min(plan.slice, a.n_searches - done);
-        if (budgeted) {
-            SampledBudgetArgs sb = *budgeted;
-            sb.first = part.first;
-            sb.n_searches = part.n_searches;
-            if (members > 1) {
-                // (plan.slice counts slots: a slice is resident with all its members)
-                const SampledEnsembleArgs en{sb, members, h->d_member_out.p, h->d_member_entry.p, h->d_member_ticket.p, h->d_member_nodes.p, h->d_member_chosen.p};
-                lrc = pdmpc_launch_sampled_ensemble(&en, sb.n_searches, (void*)h->stream);
-            } else {
-                lrc = pdmpc_launch_sampled_budget(&sb, sb.n_searches, (void*)h->stream);
-            }
-        } else if (!search) {
-            lrc = pdmpc_launch_sampled(&part, part.n_searches, (void*)h->stream);
-        } else {
+// One launch of the graph search, in the two steps timed_launch times: prepare (the plan, the arguments, the helper boards) and go (the
+// kernels).
+struct SearchLaunch {
+    KernelArgs a{};
+
+    int prepare(pdmpc_handle* h, const PackedStep& B, int first, int count, bool safe, LaunchPlan& plan) {
+        const LaunchDims dims = launch_dims(h, B);
+        int n_chained = 0;
+        if (!safe && policy_reads_chained(h->tune, count, dims.n_cu, dims.device_share))
+            for (int i = 0; i < count; ++i) n_chained += B.host.veh[first + i].n_pred > 0 ? 1 : 0;
+        std::string err;
+        int rc = plan_launch(h->tune, dims, kPlanSearch, count, n_chained, safe, plan, err);
+        if (rc) return fail(rc, err);
+        set_launch_args(h, B, plan, first, count, a);
+        if (plan.n_helpers > 0 && (rc = prepare_boards(h, count, a.help_fin_base))) return rc;
+        if (h->tune.debug_lds) fputs(format_bulk_layout(plan, count).c_str(), stderr);
+        return PDMPC_OK;
+    }
+
+    // The kernel launches, plan.slice searches each; returns the hipError_t of the first that failed.
+    // Oversubscribed launches (more searches than CUs).  A resident search spins for predecessors of the same launch; slots are in
+    // level order (the packer sees to it: coupling_order.hpp), so as long as the hardware hands out workgroups in index order every
+    // predecessor was dispatched before its successors and the launch cannot stall.  That order is not a documented guarantee: should a
+    // launch ever stall, the watchdog (spin_limit) ends the waiting searches with an error status and plan_packed_growing plans the call
+    // again with safe == true, in slices that are resident as a whole (a slice's predecessors are in it or in an earlier slice) -- forward
+    // progress then needs no assumption at all.  (The sampled optimizer's launch slices the same way: sampled_launch.hpp.)
+    int go(const pdmpc_handle* h, const LaunchPlan& plan) const {
+        typedef int (*launcher_t)(const KernelArgs*, int, void*, uint32_t*);
+        static const launcher_t launchers[4][2] = {{pdmpc_launch_bulk, pdmpc_launch_bulk_any},
+                                                   {pdmpc_launch_bulk_wide, pdmpc_launch_bulk_wide_any},
+                                                   {pdmpc_launch_bulk_sat, pdmpc_launch_bulk_sat_any},
+                                                   {pdmpc_launch_bulk_compact, pdmpc_launch_bulk_compact_any}};
+        const int variant = plan.variant, generic = plan.generic ? 1 : 0;
+        int lrc = 0;
+        for (int done = 0; done < a.n_searches && lrc == 0; done += plan.slice) {
+            KernelArgs part = a;
+            part.first = a.first + done;
+            part.n_searches = std::min(plan.slice, a.n_searches - done);
             std::lock_guard<std::mutex> lock(g_lds_mutex);
             lrc = launchers[variant][generic](&part, part.n_searches, (void*)h->stream, &g_lds_high_water[h->cfg.device & 63][variant][generic]);
         }
+        return lrc;
     }
-    return lrc;
-}
+};
 
-// safe == true: the recovery path after a predecessor time-out (plan_packed_growing; launch_plan.hpp: plan_launch).
-// The bank's kind decides the kernel: the graph search, or the sampled optimizer for a bank packed with seeds.
-int launch_range(pdmpc_handle* h, int first, int count, bool safe) {
-    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
-    PackedStep& B = h->banks[h->bank];
-    const bool search = !B.sampled;
-    if (B.pack_failed) return fail(PDMPC_ERR_INVALID, "the last pack into this bank failed: nothing is packed");
-    if (first < 0 || count < 0 || first + count > B.n_packed) return fail(PDMPC_ERR_INVALID, "launch range outside the packed batch");
-    if (!B.perm.empty() && (first != 0 || count != B.n_packed)) return fail(PDMPC_ERR_INVALID, "range launches need a batch packed in level order (predecessors in lower slots)");
-    if (count == 0) return PDMPC_OK;
-    const LaunchDims dims = launch_dims(h, B);
-    int n_chained = 0;
-    if (search && !safe && policy_reads_chained(h->tune, count, dims.n_cu, dims.device_share))
-        for (int i = 0; i < count; ++i) n_chained += B.host.veh[first + i].n_pred > 0 ? 1 : 0;
+// What the launch of a bank is, whichever optimizer runs it (Launch: SearchLaunch, or SampledLaunch of sampled_launch.hpp): prepared,
+// then its kernels between the events of a pair (LaunchTimer), the failure text with the LDS size, the layout's figures for the stats.
+template <class Launch>
+int timed_launch(pdmpc_handle* h, const PackedStep& B, int first, int count, bool safe, LaunchKind kind) {
     LaunchPlan plan;
-    SampledExtra extra;
-    std::string err;
-    // (a sampled bank plans with the budget and the ensemble size it was packed with: the first launch, a resident one and the re-plan in slices alike)
-    int rc = search ? plan_launch(h->tune, dims, kPlanSearch, count, n_chained, safe, plan, err) : plan_sampled(h->tune, dims, B.budget, B.members, count, safe, plan, extra, err);
-    if (rc) return fail(rc, err);
-    KernelArgs a{};
-    set_launch_args(h, B, plan, first, count, a);
-    const bool ensemble = !search && B.members > 1;
-    const bool budgeted = !search && (B.budget != PDMPC_SAMPLED_BUDGET_DEFAULT || ensemble);
-    SampledBudgetArgs sb{};
-    if (budgeted) {
-        const size_t n_members = (size_t)B.n_packed * (size_t)B.members;
-        if (!extra.tree_in_lds && h->d_sampled_tree.cap < n_members * (size_t)extra.node_cap * PDMPC_SB_ROW) return fail(PDMPC_ERR_CAPACITY, "the sampled optimizer's trees in HBM were not allocated by this bank's pack");
-        if (ensemble && (h->d_member_out.cap < n_members || h->d_member_entry.cap < n_members || h->d_member_nodes.cap < n_members || h->d_member_ticket.cap < (size_t)B.n_packed || h->d_member_chosen.cap < (size_t)B.n_packed))
-            return fail(PDMPC_ERR_CAPACITY, "the records of the ensemble's members were not allocated by this bank's pack");
-        sb = sampled_budget_args(a, B.budget, extra.node_cap, extra.tree_in_lds ? nullptr : h->d_sampled_tree.p);
-    }
-    if (ensemble) {
-        // every slot's ticket is zero when its members start, whatever the last launch of these slots left: a launch that failed, a
-        // resident re-launch and the re-plan in slices all pass here
-        HIPCHK(hipMemsetAsync(h->d_member_ticket.p + first, 0, (size_t)count * sizeof(uint32_t), h->stream));
-        h->ensemble_bank = h->bank;
-    }
-    if (!search) h->last_sampled_kernel = plan.kernel;
-    if (plan.n_helpers > 0 && (rc = prepare_boards(h, count, a.help_fin_base))) return rc;
-    if (search && h->tune.debug_lds) fputs(format_bulk_layout(plan, count).c_str(), stderr);
-    if ((rc = h->timer.begin(h->stream, search ? kLaunchSearch : kLaunchSampled))) return rc;
-    const int lrc = dispatch(h, a, plan, search, budgeted ? &sb : nullptr, B.members);
+    Launch launch;
+    int rc = launch.prepare(h, B, first, count, safe, plan);
+    if (rc) return rc;
+    if ((rc = h->timer.begin(h->stream, kind))) return rc;
+    const int lrc = launch.go(h, plan);
     if (lrc != 0) {
         h->boards_dirty = true;  // (the searches that were to count themselves finished never ran: the next launch starts from cleared counters)
         char buf[256];
@@ -230,6 +151,18 @@ int launch_range(pdmpc_handle* h, int first, int count, bool safe) {
     h->stats.lds_bytes = plan.lds.total;
     h->stats.lds_nodes = plan.NL;
     return PDMPC_OK;
+}
+
+// safe == true: the recovery path after a predecessor time-out (plan_packed_growing; launch_plan.hpp: plan_launch).
+// The bank's kind decides the launch: the graph search's, or the sampled optimizer's for a bank packed with seeds.
+int launch_range(pdmpc_handle* h, int first, int count, bool safe) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    PackedStep& B = h->banks[h->bank];
+    if (B.pack_failed) return fail(PDMPC_ERR_INVALID, "the last pack into this bank failed: nothing is packed");
+    if (first < 0 || count < 0 || first + count > B.n_packed) return fail(PDMPC_ERR_INVALID, "launch range outside the packed batch");
+    if (!B.perm.empty() && (first != 0 || count != B.n_packed)) return fail(PDMPC_ERR_INVALID, "range launches need a batch packed in level order (predecessors in lower slots)");
+    if (count == 0) return PDMPC_OK;
+    return B.sampled.on ? timed_launch<SampledLaunch>(h, B, first, count, safe, kLaunchSampled) : timed_launch<SearchLaunch>(h, B, first, count, safe, kLaunchSearch);
 }
 
 // the device-resident record path addresses slots: the caller's vehicles only if the library kept the batch's order
@@ -316,11 +249,11 @@ int pdmpc_sampled_ensemble_plan_host(const char* tuning, const pdmpc_launch_quer
 int pdmpc_sampled_plan_bank(pdmpc_handle* h, int32_t n_expansions_max, pdmpc_launch_plan* plan, int64_t* extra) {
     if (!h || !plan || !extra) return fail(PDMPC_ERR_INVALID, "pdmpc_sampled_plan_bank: null argument");
     const PackedStep& B = h->banks[h->bank];
-    if (B.pack_failed || B.n_packed == 0 || !B.sampled) return fail(PDMPC_ERR_INVALID, "pdmpc_sampled_plan_bank: the current bank holds no sampled batch");
+    if (B.pack_failed || B.n_packed == 0 || !B.sampled.on) return fail(PDMPC_ERR_INVALID, "pdmpc_sampled_plan_bank: the current bank holds no sampled batch");
     LaunchPlan p;
     SampledExtra x;
     std::string err;
-    if (const int rc = plan_sampled(h->tune, launch_dims(h, B), n_expansions_max, B.members, B.n_packed, h->safe_launches, p, x, err)) return fail(rc, err);
+    if (const int rc = plan_sampled(h->tune, launch_dims(h, B), n_expansions_max, B.sampled.members, B.n_packed, h->safe_launches, p, x, err)) return fail(rc, err);
     plan_record(p, false, *plan);
     sampled_extra_record(x, 4, extra);
     return PDMPC_OK;
@@ -329,28 +262,28 @@ int pdmpc_sampled_plan_bank(pdmpc_handle* h, int32_t n_expansions_max, pdmpc_lau
 int pdmpc_set_sampled_budget(pdmpc_handle* h, int32_t n_expansions_max) {
     if (!h) return fail(PDMPC_ERR_INVALID, "pdmpc_set_sampled_budget: null handle");
     if (n_expansions_max < 1 || n_expansions_max > PDMPC_SAMPLED_BUDGET_MAX) return fail(PDMPC_ERR_INVALID, "pdmpc_set_sampled_budget: the budget must be in 1..PDMPC_SAMPLED_BUDGET_MAX");
-    h->sampled_budget = n_expansions_max;
+    h->sampled.budget = n_expansions_max;
     return PDMPC_OK;
 }
 
 int pdmpc_get_sampled_budget(pdmpc_handle* h, int32_t* n_expansions_max) {
     if (!h || !n_expansions_max) return fail(PDMPC_ERR_INVALID, "pdmpc_get_sampled_budget: null argument");
-    *n_expansions_max = h->sampled_budget;
+    *n_expansions_max = h->sampled.budget;
     return PDMPC_OK;
 }
 
-const char* pdmpc_last_sampled_kernel(pdmpc_handle* h) { return h ? h->last_sampled_kernel : ""; }
+const char* pdmpc_last_sampled_kernel(pdmpc_handle* h) { return h ? h->sampled.last_kernel : ""; }
 
 int pdmpc_set_sampled_ensemble(pdmpc_handle* h, int32_t n_members) {
     if (!h) return fail(PDMPC_ERR_INVALID, "pdmpc_set_sampled_ensemble: null handle");
     if (n_members < 1 || n_members > PDMPC_SAMPLED_ENSEMBLE_MAX) return fail(PDMPC_ERR_INVALID, "pdmpc_set_sampled_ensemble: the ensemble size must be in 1..PDMPC_SAMPLED_ENSEMBLE_MAX");
-    h->sampled_members = n_members;
+    h->sampled.members = n_members;
     return PDMPC_OK;
 }
 
 int pdmpc_get_sampled_ensemble(pdmpc_handle* h, int32_t* n_members) {
     if (!h || !n_members) return fail(PDMPC_ERR_INVALID, "pdmpc_get_sampled_ensemble: null argument");
-    *n_members = h->sampled_members;
+    *n_members = h->sampled.members;
     return PDMPC_OK;
 }
 
@@ -359,15 +292,15 @@ uint32_t pdmpc_sampled_member_seed(uint32_t seed, int32_t member) { return PDMPC
 int pdmpc_sampled_ensemble_result(pdmpc_handle* h, int32_t n_vehicles, int32_t* winner, int32_t* member_status, double* member_cost) {
     if (!h) return fail(PDMPC_ERR_INVALID, "pdmpc_sampled_ensemble_result: null handle");
     const PackedStep& B = h->banks[h->bank];
-    if (B.pack_failed || !B.sampled || B.members < 2 || h->ensemble_bank != h->bank) return fail(PDMPC_ERR_INVALID, "pdmpc_sampled_ensemble_result: the current bank was not packed as an ensemble or not launched since");
+    if (B.pack_failed || !B.sampled.on || B.sampled.members < 2 || h->sampled.ensemble_bank != h->bank) return fail(PDMPC_ERR_INVALID, "pdmpc_sampled_ensemble_result: the current bank was not packed as an ensemble or not launched since");
     if (n_vehicles != B.n_packed) return fail(PDMPC_ERR_INVALID, "pdmpc_sampled_ensemble_result: not the bank's vehicle count");
     ON_DEVICE(h->cfg.device);
-    const int E = B.members;
+    const int E = B.sampled.members;
     std::vector<EnsembleEntry> en((size_t)n_vehicles * (size_t)E);
     std::vector<int32_t> chosen((size_t)n_vehicles);
     if (en.empty()) return PDMPC_OK;
-    HIPCHK(hipMemcpyAsync(en.data(), h->d_member_entry.p, en.size() * sizeof(EnsembleEntry), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(chosen.data(), h->d_member_chosen.p, chosen.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(en.data(), h->sampled.member_entry.p, en.size() * sizeof(EnsembleEntry), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(chosen.data(), h->sampled.chosen.p, chosen.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(sync_stream(h));
     for (int v = 0; v < n_vehicles; ++v) {
         const size_t slot = (size_t)(B.perm.empty() ? v : B.inv[(size_t)v]);
@@ -492,8 +425,7 @@ int pdmpc_set_step_weights(pdmpc_handle* h, int32_t n, const double* weights) {
 
 int pdmpc_set_step_seeds(pdmpc_handle* h, int32_t n, const uint32_t* seeds) {
     if (!h || n < 0 || (n > 0 && !seeds)) return fail(PDMPC_ERR_INVALID, "pdmpc_set_step_seeds: bad argument");
-    h->next_seeds.assign(seeds, seeds + n);
-    h->seeds_set = true;
+    h->sampled.seeds.assign(seeds, n);
     return PDMPC_OK;
 }
 
@@ -1047,6 +979,8 @@ int pdmpc_plan_joint(pdmpc_handle* h, int32_t n_problems, const int32_t* problem
     rc = plan_growing(h, n, Sink::records(out), false, [&](bool) -> int {
         JointArgs a{};
         set_batch_args(h, B, plan.areas_in_lds, a);
+        a.dt = h->cfg.dt_seconds;
+        a.max_nodes = h->arena.max_nodes;
         a.problem_off = h->d_joint_off.p;
         a.nodes = h->arena.nodes.p;
         a.far_key = h->arena.far_key.p;

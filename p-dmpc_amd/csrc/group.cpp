@@ -50,6 +50,7 @@
 #include "group_choice.h"
 #include "group_route.hpp"
 #include "hip_host.hpp"  // (the handles are driven through the C ABI: no handle.hpp, no struct pdmpc_handle here)
+#include "launch_plan.hpp"  // (host only: PendingSeeds)
 
 namespace {
 
@@ -171,8 +172,7 @@ struct pdmpc_group {
     int32_t Hp = 0;                           // the handles' prediction horizon: the row of path_nodes whose g is a plan's cost
     int resident_bank = -1;                   // the bank whose records the ranks HOLD (group_route.hpp) since the last launch of either kind
     std::vector<const pdmpc_vehicle_out*> rec;  // per rank: its handle's record buffer
-    std::vector<uint32_t> next_seeds;         // pdmpc_group_set_step_seeds: consumed by the next pack
-    bool seeds_set = false;
+    PendingSeeds seeds;                       // pdmpc_group_set_step_seeds: taken by the next pack
     int64_t xchg[4] = {0, 0, 0, 0};           // pdmpc_group_last_exchange
     PinnedBuf<int32_t> pin_lists{hipHostMallocPortable};  // the lists on their way to the ranks
     // mapped into every device: what kernels write for the host, and the staging of record copies (RankBufs::pin_out: the ranks' views)
@@ -289,10 +289,8 @@ int group_pack(pdmpc_group* g, int bank, int n, const pdmpc_vehicle_in* in, cons
     if (g->last_bank == bank) g->last_bank = -1;
     if (g->resident_bank == bank) g->resident_bank = -1;
     // the seeds set for this pack are consumed by it, also if it fails (as a handle's: pack.cpp)
-    const bool sampled = g->seeds_set;
-    const std::vector<uint32_t> seeds = std::move(g->next_seeds);
-    g->next_seeds.clear();
-    g->seeds_set = false;
+    std::vector<uint32_t> seeds;
+    const bool sampled = g->seeds.take(seeds);
     if (sampled && (int)seeds.size() != n) return fail(PDMPC_ERR_INVALID, "pdmpc_group_set_step_seeds: the seeds are not one per vehicle of the packed step");
     if (sampled) {
         // one budget for the step: the ranks plan shares of ONE sampled step (pdmpc_group_set_sampled_budget sets them all)
@@ -828,14 +826,10 @@ int pdmpc_group_plan_step(pdmpc_group* g, int32_t n, const pdmpc_vehicle_in* in,
     DeviceGuard keep;
     new_call(g);
     // (a sampled step is packed again with the seeds its first pack consumed)
-    const bool sampled = g->seeds_set;
-    const std::vector<uint32_t> seeds = g->next_seeds;
+    const PendingSeeds pending = g->seeds;
     return plan_growing(g, "pdmpc_group_plan_step", [&](bool& overflow) {
         const auto t0 = clk::now();
-        if (sampled) {
-            g->next_seeds = seeds;
-            g->seeds_set = true;
-        }
+        g->seeds = pending;
         GRC(group_pack(g, 0, n, in, pred_offset, pred_index, fallback_shapes, weights, mode));
         GRC(group_launch(g, 0));
         GRC(group_fetch(g, 0, n, out));
@@ -907,8 +901,7 @@ int pdmpc_group_route_host(int32_t n, const int32_t* pred_offset, const int32_t*
 
 int pdmpc_group_set_step_seeds(pdmpc_group* g, int32_t n, const uint32_t* seeds) {
     if (!g || n < 0 || (n > 0 && !seeds)) return fail(PDMPC_ERR_INVALID, "pdmpc_group_set_step_seeds: bad argument");
-    g->next_seeds.assign(seeds, seeds + n);
-    g->seeds_set = true;
+    g->seeds.assign(seeds, n);
     return PDMPC_OK;
 }
 

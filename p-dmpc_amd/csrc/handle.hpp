@@ -76,9 +76,7 @@ struct PackedStep {
     uint64_t staged_serial = ~0ull;  // the handle's sync_serial when the copy out of h_blob was queued (pack_common)
     int n_packed = 0;
     bool pack_failed = false;  // the last pack into this bank did not finish: nothing to launch or fetch
-    bool sampled = false;      // packed with seeds (pdmpc_set_step_seeds): a sampled bank, its launches run the sampled optimizer
-    int budget = PDMPC_SAMPLED_BUDGET_DEFAULT;  // ... with the expansion budget the handle had when it was packed (pdmpc_set_sampled_budget)
-    int members = 1;                            // ... and the ensemble size (pdmpc_set_sampled_ensemble)
+    SampledBank sampled;       // packed with seeds (pdmpc_set_step_seeds): its launches run the sampled optimizer, with the handle's budget and ensemble size of then
     int soup_cap = 0;
     int ll_cap = 0;    // most lanelet-boundary columns of any vehicle (the graph search's reach lists hold one boundary list per step)
     int cand_cap = 0;  // most segments any single edge check can see (one step's soups + the boundary)
@@ -281,6 +279,34 @@ struct ChoiceState {
     TimedLaunch timed;
 };
 
+// The sampled optimizer (sampled_launch.hpp): what the next pack of a sampled bank gives its bank, what the last launch ran, and the
+// scratch of banks that need any (SampledNeed, launch_plan.hpp): the trees of a budget that does not fit LDS (sampled_budget.h) and
+// the members of a seed ensemble (sampled_ensemble.h).  Like d_out the scratch is the handle's, shared by its banks and only grown,
+// by the pack that needs more: resident banks of other budgets and sizes launch on it one after the other, and no launch reads
+// anything of it that it has not written -- the tickets are cleared ahead of every launch.
+struct SampledState {
+    PendingSeeds seeds;                    // pdmpc_set_step_seeds: taken by the next pack, which makes its bank a sampled bank
+    int budget = PDMPC_SAMPLED_BUDGET_DEFAULT;  // pdmpc_set_sampled_budget
+    int members = 1;                       // pdmpc_set_sampled_ensemble
+    int ensemble_bank = -1;                // the bank whose launch wrote the entries last (pdmpc_sampled_ensemble_result), -1: none since its pack
+    const char* last_kernel = "";          // pdmpc_last_sampled_kernel
+    DevBuf<uint16_t> tree;                 // SampledNeed::tree
+    DevBuf<pdmpc_vehicle_out> member_out;  // SampledNeed::per_member: [slot * E + e] ...
+    DevBuf<EnsembleEntry> member_entry;
+    DevBuf<int32_t> member_nodes;
+    DevBuf<uint32_t> ticket;               // SampledNeed::per_slot: [slot], cleared on the stream ahead of every launch of an ensemble bank ...
+    DevBuf<int32_t> chosen;                // ... the member the kernel chose
+    bool holds_trees(const SampledNeed& n) const { return tree.cap >= n.tree; }
+    bool holds_members(const SampledNeed& n) const {
+        return member_out.cap >= n.per_member && member_entry.cap >= n.per_member && member_nodes.cap >= n.per_member && ticket.cap >= n.per_slot && chosen.cap >= n.per_slot;
+    }
+    // (the stream idle: a launch of a resident bank may still use a buffer that is freed)
+    int grow_trees(const SampledNeed& n) { return tree.ensure_exact(n.tree); }
+    int grow_members(const SampledNeed& n) {
+        return member_out.ensure_exact(n.per_member) | member_entry.ensure_exact(n.per_member) | member_nodes.ensure_exact(n.per_member) | ticket.ensure_exact(n.per_slot) | chosen.ensure_exact(n.per_slot);
+    }
+};
+
 struct pdmpc_handle {
     pdmpc_config cfg{};
     Tuning tune{};
@@ -317,31 +343,17 @@ struct pdmpc_handle {
     BoundState bound;
     FcaState fca;
     ChoiceState choice;
+    SampledState sampled;
     int device_share = 1;                // handles of one process that launch on this device side by side (pdmpc_set_device_share: a group's logical ranks)
     bool boards_dirty = true;            // the helper boards / the finished counter need clearing before the helper workgroups may read them
     uint32_t help_fin_total = 0;         // value of the finished counter once every launch so far has ended
-    uint32_t launch_serial = 0;          // launches of this handle so far (KernelArgs::launch_id)
+    uint32_t launch_serial = 0;          // SEARCH launches of this handle so far: its only reader is KernelArgs::launch_id, which tells the helper boards' words of one search launch from an earlier one's (a sampled or joint launch has no boards and does not count)
     double last_us[3] = {0, 0, 0};       // pdmpc_last_call_timing: pack, enqueue, wait + read-back of the last pdmpc_plan_batch / pdmpc_plan_step
     double dbg_us[4] = {0, 0, 0, 0};     // debug_host 2: pack, launch, fetch (host clock) and kernel (events) time of the plan_batch calls
     uint64_t sync_serial = 0;            // stream synchronisations through sync_stream so far (PackedStep::staged_serial)
     SoupTable soups;                     // pack_common's scratch: vehicles by all their arrays,
     SoupTable obstacle_soups, boundary_soups;  // ... by their obstacle arrays, by their boundary arrays
     std::vector<double> next_weights;    // pdmpc_set_step_weights: expected work per vehicle of the NEXT packed step (the caller's order); consumed by that pack
-    std::vector<uint32_t> next_seeds;    // pdmpc_set_step_seeds: the sampled optimizer's seed per vehicle of the NEXT packed step (the caller's order) ...
-    bool seeds_set = false;              // ... consumed by that pack, which makes its bank a sampled bank
-    int sampled_budget = PDMPC_SAMPLED_BUDGET_DEFAULT;  // pdmpc_set_sampled_budget: what the next pack of a sampled bank gives its bank
-    DevBuf<uint16_t> d_sampled_tree;     // the trees of a sampled bank whose budget does not fit LDS (sampled_budget.h), grown by the pack that needs more
-    const char* last_sampled_kernel = "";  // pdmpc_last_sampled_kernel
-    // Seed ensembles (sampled_ensemble.h): what the next pack of a sampled bank gives its bank, and the members' scratch.  Like d_out
-    // and d_sampled_tree the scratch is the handle's, shared by its banks and only grown, by the pack that needs more: a launch reads
-    // nothing of it that it has not written.
-    int sampled_members = 1;
-    int ensemble_bank = -1;                  // the bank whose launch wrote the entries last (pdmpc_sampled_ensemble_result), -1: none since its pack
-    DevBuf<pdmpc_vehicle_out> d_member_out;  // [slot * E + e]
-    DevBuf<EnsembleEntry> d_member_entry;    // [slot * E + e]
-    DevBuf<int32_t> d_member_nodes;          // [slot * E + e]
-    DevBuf<uint32_t> d_member_ticket;        // [slot], cleared on the stream ahead of every launch of an ensemble bank
-    DevBuf<int32_t> d_member_chosen;         // [slot] the member the kernel chose
     PinnedBuf<double> h_lean;            // fetch_lean: (cost, status) per slot
     DevBuf<double> d_lean;
     PinnedBuf<pdmpc_vehicle_out> h_out;  // pdmpc_fetch_results: the records land in pinned memory (a copy into the caller's pageable array goes through the runtime's staging otherwise)
@@ -364,7 +376,27 @@ struct pdmpc_handle {
 // what planning reads of the handle and of a packed bank (launch_plan.hpp: LaunchDims)
 inline LaunchDims launch_dims(const pdmpc_handle* h, const PackedStep& B) {
     return {h->cfg.checker, h->cfg.Hp, h->n_trims, h->n_words, h->n_man, h->mask_bytes, h->mi_bytes, h->n_cu, h->device_share, h->arena.max_nodes,
-            B.sampled, B.soup_cap, B.ll_cap, B.cand_cap};
+            B.sampled.on, B.soup_cap, B.ll_cap, B.cand_cap};
+}
+
+// what the graph search, the sampled optimizer and the joint search (KernelArgs, SampledArgs, JointArgs) all read: the automaton, the
+// packed batch, the records, the tree sizes and work counters
+template <class Args>
+void set_batch_args(const pdmpc_handle* h, const PackedStep& B, int areas_in_lds, Args& a) {
+    a.succ_mask = h->d_mask.p;
+    a.man_index = h->d_mi.p;
+    a.man_pose = h->d_pose.p;
+    a.man_area = h->d_area.p;
+    a.n_trims = h->n_trims;
+    a.n_words = h->n_words;
+    a.n_man = h->n_man;
+    a.Hp = h->cfg.Hp;
+    a.areas_in_lds = areas_in_lds;
+    a.veh = B.dev.veh;
+    a.points = B.dev.pts;
+    a.out = h->d_out.p;
+    a.tree_size = h->d_tree_size.p;
+    a.work_count = h->d_work_count.p;
 }
 
 // hipStreamSynchronize on the launch stream, counted: a bank whose staging copy was queued before is free again (pack_common)

@@ -7,6 +7,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <utility>
+#include <vector>
 
 #include "pdmpc_device.h"
 #include "sampled_budget.h"
@@ -264,6 +266,51 @@ struct SampledExtra {
     int64_t grid = 0;                // workgroups of a kernel launch
 };
 
+// The sampled part of a packed bank: whether it was packed with seeds (its launches then run the sampled optimizer), and the expansion
+// budget and ensemble size its owner had when it was packed (pdmpc_set_sampled_budget, pdmpc_set_sampled_ensemble).
+struct SampledBank {
+    bool on = false;
+    int budget = PDMPC_SAMPLED_BUDGET_DEFAULT;
+    int members = 1;
+    // the reference's budget, one member: pdmpc_sampled_kernel, whose tree is always in LDS -- a bank that needs no scratch
+    bool reference() const { return budget == PDMPC_SAMPLED_BUDGET_DEFAULT && members == 1; }
+};
+
+// The scratch a sampled bank of n_packed slots needs besides its batch, in elements of each buffer.  The pack grows the buffers to
+// it and every launch checks them against it.
+struct SampledNeed {
+    size_t tree = 0;        // 16-bit words of the HBM trees: a slot's rows for every slot and member (0: the tree is in LDS)
+    size_t per_member = 0;  // an ensemble's member records, entries and tree sizes, [slot * E + e] (0: one member)
+    size_t per_slot = 0;    // ... and its tickets and chosen members, [slot]
+};
+inline SampledNeed sampled_need(const SampledBank& bank, int n_packed, const SampledExtra& extra) {
+    const size_t n_members = (size_t)n_packed * (size_t)bank.members;
+    SampledNeed need;
+    if (!extra.tree_in_lds) need.tree = n_members * (size_t)extra.node_cap * PDMPC_SB_ROW;
+    if (bank.members > 1) {
+        need.per_member = n_members;
+        need.per_slot = (size_t)n_packed;
+    }
+    return need;
+}
+
+// Seeds on their way to a pack: set by a call (pdmpc_set_step_seeds, pdmpc_group_set_step_seeds), taken by the next pack whether it
+// succeeds or fails -- a pack that fails leaves no sampled bank behind it, and no seeds for the pack after it.
+struct PendingSeeds {
+    std::vector<uint32_t> seeds;  // one per vehicle of the next packed step, the caller's order
+    bool set = false;
+    void assign(const uint32_t* from, int n) {
+        seeds.assign(from, from + n);
+        set = true;
+    }
+    // the seeds into `taken`, nothing left; false: none were set, the pack is not a sampled one
+    bool take(std::vector<uint32_t>& taken) {
+        taken = std::move(seeds);
+        seeds.clear();
+        return std::exchange(set, false);
+    }
+};
+
 // LDS layout of the sampled optimizer (one wavefront per vehicle; sampled_search.hpp): MPA tables, reference, the wave's two shapes,
 // offsets, obstacle soup (with the predecessors' columns the packer counts into soup_cap), the candidate segments of one edge check,
 // then the tree (`tree_bytes`: rows of 36 B) and the random numbers (`rand_bytes`).  80 KB first (two workgroups per CU), then the whole
@@ -420,8 +467,8 @@ inline void launch_policy(const Tuning& T, int count, int n_cu, int device_share
     }
 }
 
-// What a search or sampled launch reads of its plan and of the tuning's switches: every KernelArgs field that is a decision, none that
-// is a pointer or a counter of the handle.
+// What a search launch reads of its plan and of the tuning's switches: every KernelArgs field that is a decision, none that
+// is a pointer or a counter of its owner.
 inline void set_plan_args(const Tuning& T, const LaunchPlan& p, KernelArgs& a) {
     a.areas_in_lds = p.areas_in_lds;
     a.lds = p.lds;

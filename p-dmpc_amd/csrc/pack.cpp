@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "coupling_order.hpp"
-#include "handle.hpp"
+#include "sampled_launch.hpp"
 
 namespace {
 
@@ -330,38 +330,14 @@ struct Packer {
 
 }  // namespace
 
-// What a sampled bank needs besides its batch.  A budget whose tree does not fit LDS: the handle's HBM trees grow to a slot's rows for
-// every packed slot and member (sampled_budget.h).  An ensemble (sampled_ensemble.h): the members' records, entries, tree sizes and the
-// slots' tickets.  (The buffers are the handle's and only grow: resident banks of other budgets and sizes launch on them one after the
-// other, and no launch reads anything of them that it has not written -- the tickets are cleared ahead of every launch.)
-static int reserve_sampled_scratch(pdmpc_handle* h, const PackedStep& B) {
-    LaunchPlan plan;
-    SampledExtra extra;
-    std::string err;
-    if (const int rc = plan_sampled(h->tune, launch_dims(h, B), B.budget, B.members, std::max(B.n_packed, 1), false, plan, extra, err)) return fail(rc, err);
-    const size_t n_members = (size_t)B.n_packed * (size_t)B.members;
-    const size_t want_tree = extra.tree_in_lds ? 0 : n_members * (size_t)extra.node_cap * PDMPC_SB_ROW;
-    const bool ensemble = B.members > 1;
-    const bool grow = want_tree > h->d_sampled_tree.cap ||
-                      (ensemble && (n_members > h->d_member_out.cap || n_members > h->d_member_entry.cap || n_members > h->d_member_nodes.cap || (size_t)B.n_packed > h->d_member_ticket.cap || (size_t)B.n_packed > h->d_member_chosen.cap));
-    if (!grow) return PDMPC_OK;
-    HIPCHK(sync_stream(h));  // (a launch of a resident bank may still use a buffer that is freed)
-    if (h->d_sampled_tree.ensure_exact(want_tree)) return fail(PDMPC_ERR_CAPACITY, "not enough HBM for the sampled optimizer's trees at this budget");
-    if (ensemble && (h->d_member_out.ensure_exact(n_members) | h->d_member_entry.ensure_exact(n_members) | h->d_member_nodes.ensure_exact(n_members) | h->d_member_ticket.ensure_exact((size_t)B.n_packed) | h->d_member_chosen.ensure_exact((size_t)B.n_packed)))
-        return fail(PDMPC_ERR_CAPACITY, "not enough HBM for the records of the sampled optimizer's ensemble members");
-    return PDMPC_OK;
-}
-
 int pack_common(pdmpc_handle* h, int n, const pdmpc_vehicle_in* in, const int32_t* pred_offset, const int32_t* pred_index, const pdmpc_polygon_set* fallback) {
     if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
     // the weights are this pack's, whether it succeeds or not: a failed pack must not leave them to reorder the next one
     const std::vector<double> weights = std::move(h->next_weights);
     h->next_weights.clear();
     // ... and so are the seeds: a pack that fails leaves no sampled bank behind it
-    const bool sampled = h->seeds_set;
-    const std::vector<uint32_t> seeds = std::move(h->next_seeds);
-    h->next_seeds.clear();
-    h->seeds_set = false;
+    std::vector<uint32_t> seeds;
+    const bool sampled = h->sampled.seeds.take(seeds);
     if (!h->has_mpa) return fail(PDMPC_ERR_NO_MPA, "pdmpc_upload_mpa has not been called");
     if (n < 0 || (n > 0 && !in)) return fail(PDMPC_ERR_INVALID, "bad vehicle array");
     if (n > h->max_vehicles) return fail(PDMPC_ERR_CAPACITY, "batch larger than config.max_vehicles");
@@ -370,10 +346,8 @@ int pack_common(pdmpc_handle* h, int n, const pdmpc_vehicle_in* in, const int32_
     if (B.staged_serial == h->sync_serial) HIPCHK(sync_stream(h));
     B.n_packed = 0;  // (a pack that fails leaves the bank empty: the batch that was in it is being overwritten)
     B.pack_failed = true;
-    B.sampled = sampled;
-    B.budget = h->sampled_budget;
-    B.members = sampled ? h->sampled_members : 1;
-    if (h->ensemble_bank == h->bank) h->ensemble_bank = -1;
+    B.sampled = SampledBank{sampled, h->sampled.budget, sampled ? h->sampled.members : 1};
+    if (h->sampled.ensemble_bank == h->bank) h->sampled.ensemble_bank = -1;
     if (sampled && (int)seeds.size() != n) return fail(PDMPC_ERR_INVALID, "pdmpc_set_step_seeds: the seeds are not one per vehicle of the packed step");
     Packer P{h, B, n, in, pred_offset, pred_index, fallback, sampled ? &seeds : nullptr};
     int rc;
@@ -385,7 +359,7 @@ int pack_common(pdmpc_handle* h, int n, const pdmpc_vehicle_in* in, const int32_
     for (int slot = 0; slot < n; ++slot)
         if ((rc = P.pack_vehicle(slot))) return rc;
     if ((rc = P.close())) return rc;
-    if (sampled && (B.budget != PDMPC_SAMPLED_BUDGET_DEFAULT || B.members > 1) && (rc = reserve_sampled_scratch(h, B))) {
+    if ((rc = reserve_sampled_scratch(h, B))) {
         B.n_packed = 0;
         B.pack_failed = true;
         return rc;

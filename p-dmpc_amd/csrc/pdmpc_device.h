@@ -586,8 +586,6 @@ int pdmpc_launch_bulk_compact(const KernelArgs* args, int count, void* stream, u
 int pdmpc_launch_bulk_compact_any(const KernelArgs* args, int count, void* stream, uint32_t* lds_high_water);
 // util_kernels.hip: (cost-to-come of the final node, status) of n result records into lean[2 * n]
 int pdmpc_launch_gather_lean(const pdmpc_vehicle_out* out, int n, int Hp, double* lean, void* stream);
-// sampled_kernel.hip: the sampled optimizer (MonteCarloTreeSearch.m), `count` workgroups of one wavefront
-int pdmpc_launch_sampled(const KernelArgs* args, int count, void* stream);
 // debug_kernels.hip: the first n doubles of mt19937ar(seeds[i]) for every i, by the sampled kernel's device generator (out: [count][n])
 int pdmpc_launch_debug_mt19937(const uint32_t* seeds, int count, int n, double* out, void* stream);
 // debug_kernels.hip: the open-list command script on one wavefront, and the collision primitives on given polygons (one wavefront per case)

@@ -1,6 +1,6 @@
-// sampled_budget.h — what the host and the sampled optimizer's kernels share: the tree's rows (sampled_search.hpp), and the arguments
-// of the sampled optimizer with a run-time expansion budget (pdmpc_set_sampled_budget) with its launchers.  The
-// budget of MonteCarloTreeSearch.m:8 (250) keeps pdmpc_sampled_kernel and KernelArgs; every other budget runs the kernels declared here.
+// sampled_budget.h — what the host and the sampled optimizer's kernels share: the tree's rows (sampled_search.hpp), and the ONE
+// argument record of the sampled optimizer with its launchers.  The budget of MonteCarloTreeSearch.m:8 (250) runs
+// pdmpc_sampled_kernel, which has it compiled in; every other budget (pdmpc_set_sampled_budget) runs the pdmpc_sampled_budget kernels.
 #pragma once
 #include "pdmpc_device.h"
 
@@ -19,7 +19,9 @@
 static inline uint32_t pdmpc_sb_node_cap(uint32_t budget) { return (budget + PDMPC_HP_MAX + 2u + 7u) & ~7u; }
 static inline uint32_t pdmpc_sb_tree_bytes(uint32_t budget) { return pdmpc_sb_node_cap(budget) * PDMPC_SB_ROW * 2u; }
 
-struct SampledBudgetArgs {
+// What every sampled kernel takes (the ensemble's kernels inside SampledEnsembleArgs); the host fills it in one place
+// (sampled_launch.hpp: sampled_args).  The graph search's KernelArgs is no part of a sampled launch.
+struct SampledArgs {
     // the automaton
     const uint64_t* succ_mask;
     const int16_t* man_index;
@@ -40,16 +42,18 @@ struct SampledBudgetArgs {
     unsigned long long* work_count;
     // the layout (launch_plan.hpp: layout_sampled): tree16 holds the tree if it is in LDS, rand the generator's 624 state words
     LdsLayout lds;
-    int32_t budget;    // n_expansions_max
-    int32_t node_cap;  // rows of a slot's tree (pdmpc_sb_node_cap)
+    int32_t budget;    // n_expansions_max (pdmpc_sampled_kernel: 250, compiled in)
+    int32_t node_cap;  // rows of a slot's tree (pdmpc_sb_node_cap; pdmpc_sampled_kernel: PDMPC_SB_DEFAULT_ROWS, compiled in)
     uint16_t* tree;    // the trees in HBM, node_cap rows per slot (the _hbm kernel; null where the tree is in LDS)
 };
 
 #ifdef __cplusplus
 extern "C" {
 #endif
+// sampled_kernel.hip: the sampled optimizer (MonteCarloTreeSearch.m) at the reference's budget, `count` workgroups of one wavefront
+int pdmpc_launch_sampled(const SampledArgs* args, int count, void* stream);
 // sampled_budget_kernel.hip: `count` workgroups of one wavefront; the tree in LDS (tree == null) or in HBM
-int pdmpc_launch_sampled_budget(const SampledBudgetArgs* args, int count, void* stream);
+int pdmpc_launch_sampled_budget(const SampledArgs* args, int count, void* stream);
 // ... and its generator alone: out[i][0 .. n) = the first n doubles of mt19937ar(seeds[i]), one twist at a time
 int pdmpc_launch_debug_random_stream(const uint32_t* seeds, int count, int n, double* out, void* stream);
 #ifdef __cplusplus

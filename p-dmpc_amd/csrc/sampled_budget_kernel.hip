@@ -21,17 +21,17 @@ namespace {
 
 }  // namespace
 
-extern "C" __global__ __launch_bounds__(PDMPC_WAVE) void pdmpc_sampled_budget_kernel(const SampledBudgetArgs A) {
+extern "C" __global__ __launch_bounds__(PDMPC_WAVE) void pdmpc_sampled_budget_kernel(const SampledArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     sampled_slot_body<true, TwistByTwist, ArgumentLimits>(A, (LDS_AS unsigned char*)smem, nullptr);
 }
 
-extern "C" __global__ __launch_bounds__(PDMPC_WAVE) void pdmpc_sampled_budget_kernel_hbm(const SampledBudgetArgs A) {
+extern "C" __global__ __launch_bounds__(PDMPC_WAVE) void pdmpc_sampled_budget_kernel_hbm(const SampledArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     sampled_slot_body<false, TwistByTwist, ArgumentLimits>(A, (LDS_AS unsigned char*)smem, A.tree);
 }
 
-extern "C" int pdmpc_launch_sampled_budget(const SampledBudgetArgs* args, int count, void* stream) {
+extern "C" int pdmpc_launch_sampled_budget(const SampledArgs* args, int count, void* stream) {
     if (count <= 0) return 0;
     const bool in_lds = args->tree == nullptr;
     const void* fn = in_lds ? (const void*)pdmpc_sampled_budget_kernel : (const void*)pdmpc_sampled_budget_kernel_hbm;

@@ -12,7 +12,7 @@ struct EnsembleEntry {
 };
 
 struct SampledEnsembleArgs {
-    SampledBudgetArgs s;            // the search: out = the slots' records, tree = n_members trees per slot (member e of slot s: tree s * E + e)
+    SampledArgs s;            // the search: out = the slots' records, tree = n_members trees per slot (member e of slot s: tree s * E + e)
     int32_t n_members;              // E: block b is member b % E of slot b / E
     pdmpc_vehicle_out* member_out;  // [slot * E + e] every member's full record
     EnsembleEntry* entries;         // [slot * E + e]

@@ -20,7 +20,7 @@
 //                  published in it).  A member that timed out waiting for a predecessor: that member's record (PDMPC_ERR_HIP).
 //   No member waits for a member, and a member that does not draw the last ticket is finished: a workgroup depends only on the done
 //   flags of predecessor slots, whose blocks all lie below it.
-// Tickets: the host clears the tickets of the launched slots on the stream ahead of every launch (api.cpp: launch_range) -- also right
+// Tickets: the host clears the tickets of the launched slots on the stream ahead of every launch (sampled_launch.hpp: launch_sampled) -- also right
 // after a launch that failed half-way, which a last arriver that restores them is not.
 #include <hip/hip_runtime.h>
 
@@ -37,7 +37,7 @@ namespace {
 
 template <bool IN_LDS>
 __device__ __forceinline__ void sampled_ensemble_body(const SampledEnsembleArgs& G, LDS_AS unsigned char* lsm) {
-    const SampledBudgetArgs& A = G.s;
+    const SampledArgs& A = G.s;
     const int lane = threadIdx.x;
     const int E = G.n_members;
     const int b_slot = (int)blockIdx.x / E;

@@ -23,12 +23,12 @@ static_assert(PDMPC_SB_DEFAULT_ROWS * PDMPC_SB_ROW * 2 >= PDMPC_SB_MT_BYTES, "th
 
 }  // namespace
 
-extern "C" __global__ __launch_bounds__(PDMPC_WAVE) void pdmpc_sampled_kernel(const KernelArgs A) {
+extern "C" __global__ __launch_bounds__(PDMPC_WAVE) void pdmpc_sampled_kernel(const SampledArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     sampled_slot_body<true, DrawnAhead, ReferenceLimits>(A, (LDS_AS unsigned char*)smem, nullptr);
 }
 
-extern "C" int pdmpc_launch_sampled(const KernelArgs* args, int count, void* stream) {
+extern "C" int pdmpc_launch_sampled(const SampledArgs* args, int count, void* stream) {
     if (count <= 0) return 0;
     hipError_t e = hipFuncSetAttribute((const void*)pdmpc_sampled_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)args->lds.total);
     if (e != hipSuccess) return (int)e;

@@ -1,5 +1,6 @@
-// host_only_checks.cpp — the host-only parts of p-dmpc_amd/csrc (reference_tree.hpp, mpa_reach.hpp, choice_host.hpp) against expectations that
-// do not share their rules: a literal best-first search, an enumeration of every trim path, values and staged words written out.  A stand-alone program
+// host_only_checks.cpp — the host-only parts of p-dmpc_amd/csrc (reference_tree.hpp, mpa_reach.hpp, choice_host.hpp, and launch_plan.hpp's sampled
+// scratch and pending seeds) against expectations that do not share their rules: a literal best-first search, an enumeration of every trim path,
+// values, counts and staged words written out.  A stand-alone program
 // (tests/test_host_only_parts.py builds it with the host compiler under the address and undefined-behaviour sanitizers and runs it): exit
 // status 0 and "host-only checks ok", or 1 and a line that names the first case that failed.
 #include <cmath>
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "choice_host.hpp"
+#include "launch_plan.hpp"
 #include "mpa_reach.hpp"
 #include "reference_tree.hpp"
 
@@ -465,6 +467,60 @@ void check_choices() {
     expect_refusal("pdmpc_choice: a pick lists a slot outside the batch", 5, &ch);
 }
 
+// ---- the scratch of a sampled bank (sampled_need) and the seeds on their way to a pack (PendingSeeds)
+
+// A bank of 7 slots at (budget, members), planned for a small automaton: where the tree lives is the planner's, the counts are written out.
+// By sampled_budget.h a tree has (budget + PDMPC_HP_MAX + 2 + 7) & ~7 rows of PDMPC_SB_ROW = 18 words: 272 rows at 250 and at 251
+// (275 & ~7, 276 & ~7), 16 408 rows = 295 344 words at 16 384 (16 409 & ~7).  In HBM every slot and member has a tree of its own:
+// 7 * 295 344 = 2 067 408 words, 14 * 295 344 = 4 134 816, 112 * 295 344 = 33 078 528.  An ensemble of E keeps 7 * E member records,
+// entries and tree sizes and 7 tickets and chosen members; one member keeps none.
+void expect_need(int budget, int members, bool want_in_lds, size_t want_tree, size_t want_per_member, size_t want_per_slot) {
+    LaunchDims d{PDMPC_CHECK_INTERX, 5, 12, 0, 40, 0, 0, 256, 1, 32768u, true, 400, 60, 120};
+    mpa_table_sizes(d);
+    LaunchPlan plan;
+    SampledExtra extra;
+    std::string err;
+    if (const int rc = plan_sampled(Tuning{}, d, budget, members, 7, false, plan, extra, err)) failed("sampled need (%d, %d): plan_sampled returned %d: %s", budget, members, rc, err.c_str());
+    if ((extra.tree_in_lds != 0) != want_in_lds) failed("sampled need (%d, %d): tree_in_lds is %d", budget, members, extra.tree_in_lds);
+    const SampledNeed need = sampled_need(SampledBank{true, budget, members}, 7, extra);
+    if (need.tree != want_tree || need.per_member != want_per_member || need.per_slot != want_per_slot)
+        failed("sampled need (%d, %d): tree %zu per member %zu per slot %zu, expected %zu %zu %zu", budget, members, need.tree, need.per_member, need.per_slot, want_tree, want_per_member, want_per_slot);
+}
+
+void check_sampled_need() {
+    if (!SampledBank{true, 250, 1}.reference() || SampledBank{true, 251, 1}.reference() || SampledBank{true, 250, 2}.reference()) failed("SampledBank::reference");
+    expect_need(250, 1, true, 0, 0, 0);  // (the default: pdmpc_sampled_kernel, nothing needed)
+    expect_need(251, 1, true, 0, 0, 0);
+    expect_need(16384, 1, false, 2067408, 0, 0);
+    expect_need(250, 2, true, 0, 14, 7);
+    expect_need(251, 2, true, 0, 14, 7);
+    expect_need(251, 16, true, 0, 112, 7);
+    expect_need(16384, 2, false, 4134816, 14, 7);
+    expect_need(16384, 16, false, 33078528, 112, 7);
+    // an empty bank needs nothing, wherever its trees would live
+    SampledExtra hbm;
+    hbm.node_cap = 16408;
+    hbm.tree_in_lds = 0;
+    const SampledNeed none = sampled_need(SampledBank{true, 16384, 16}, 0, hbm);
+    if (none.tree != 0 || none.per_member != 0 || none.per_slot != 0) failed("sampled need of an empty bank");
+}
+
+void check_pending_seeds() {
+    PendingSeeds P;
+    std::vector<uint32_t> got{9u};
+    if (P.take(got) || !got.empty()) failed("pending seeds: a take with nothing set is a sampled one");
+    const uint32_t first[] = {1u, 2u, 3u}, second[] = {40u, 50u};
+    P.assign(first, 3);
+    if (!P.take(got) || got != std::vector<uint32_t>{1u, 2u, 3u}) failed("pending seeds: set then take does not yield the seeds");
+    if (P.set || !P.seeds.empty()) failed("pending seeds: a take leaves something behind");
+    if (P.take(got) || !got.empty()) failed("pending seeds: a second take is a sampled one");
+    P.assign(first, 3);
+    P.assign(second, 2);
+    if (!P.take(got) || got != std::vector<uint32_t>{40u, 50u}) failed("pending seeds: set twice does not keep the last");
+    P.assign(first, 0);  // (no vehicles, but set: the pack is a sampled one)
+    if (!P.take(got) || !got.empty() || P.take(got)) failed("pending seeds: an empty set of seeds");
+}
+
 }  // namespace
 
 int main() {
@@ -472,6 +528,8 @@ int main() {
     check_reach_rects();
     check_reach_lists();
     check_choices();
+    check_sampled_need();
+    check_pending_seeds();
     puts("host-only checks ok");
     return 0;
 }

@@ -34,7 +34,9 @@ def test_host_only_checks_under_sanitizers(tmp_path):
     """The reference's tree out of 300 random arenas against a literal best-first search (and malformed arenas refused, not indexed), the
     reach rectangles of 18 small automata against every trim path (agreement to 1e-12 absolute; the largest difference the program
     prints is 8.9e-16), both reach-list builders on a two-step soup, every refusal of check_choice and one choice written out, the words its lists are staged in (identity, a permutation, the empty
-    choice) and the delivery of a hand-built read-back block (either optional array absent; each non-result counter refused): under
+    choice) and the delivery of a hand-built read-back block (either optional array absent; each non-result counter refused), the scratch
+    a sampled bank needs (sampled_need: no scratch at the default, trees in LDS and in HBM, ensembles of 2 and 16 at both, against counts
+    written out) and the seeds pending for a pack (set, take, a second take, set twice): under
     -fsanitize=address,undefined, which turn any out-of-bounds read into a failure."""
     exe = str(tmp_path / "host_only_checks")
     flags = ["-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
