@@ -690,6 +690,63 @@ int pdmpc_fca_collisions_grouped(pdmpc_handle* handle, int32_t n_groups, const p
 int pdmpc_fca_collisions_grouped_host(int32_t n_groups, const pdmpc_fca_group* groups, int32_t Hp, const double* x, const double* y, const double* cos_yaw,
                                       const double* sin_yaw, int32_t* collisions, int32_t* priorities);
 
+/* ---- human-driven vehicles (HighLevelController.update_hdv_traffic_info, HighLevelController.m:394-447; include/pdmpc_hdv.h, csrc/hdv.cpp,
+ * csrc/hdv_kernel.hip) ----
+ * What a search's third obstacle soup (pdmpc_vehicle_in.hdv_reachable_sets) is filled from: for every human-driven vehicle (HDV) the
+ * lanelets closest to it, the chains (closest lanelet, successor) it may drive along, its reachable sets clipped to every chain, and
+ * which controlled vehicles (CAVs) it is adjacent to.
+ * The map: lanelet i (id i + 1) has the left points left_offset[i] .. left_offset[i + 1] - 1 and as many right points (at least one);
+ * its centre line is 0.5 * (left + right).  succ_offset / succ_index: the successor ids (1-based) of every lanelet in the map's
+ * order (succ_offset[0] = 0).  relationship: n_lanelets x n_lanelets bytes, read at (min id, max id): 0 none, 1 longitudinal, 2 side,
+ * 3 merging, 4 forking, 5 crossing (LaneletRelationshipType.m).  hdv_local_sets: pdmpc_local_reachable_sets of the HDVs' automaton,
+ * polygon trim * Hp + k.  A chain polygon (the boundary points of a lanelet and one successor) of more than
+ * PDMPC_LANELET_POLY_MAX_COLS vertices, a local set of more than PDMPC_REACHABLE_MAX_COLS or a map of more than 1024 lanelets is
+ * PDMPC_ERR_CAPACITY.
+ * A traffic call, for n_hdv HDVs at (x, y, cos_yaw, sin_yaw: the caller's cos / sin) in trim (1-based) on the copy of the map moved by
+ * (tile_dx, tile_dy), and n_cav CAVs at (cav_x, cav_y) on lanelet cav_lanelet (1-based) of the copy moved by (cav_tile_dx, cav_tile_dy):
+ *   closest lanelets  map_position_to_closest_lanelets.m:1-25 at (x - tile_dx, y - tile_dy), literally: in id order a lanelet whose
+ *                     distance is below the best so far starts the list anew, one within 0.1 of the best so far is appended.
+ *                     closest_offset[n_hdv + 1], closest_index (ids, room for n_hdv * PDMPC_HDV_MAX_CHAINS).
+ *   rows              one per (HDV, chain), HDV by HDV; a chain is (closest lanelet, one of its successors) in list and successor
+ *                     order, or the lanelet alone if it has no successor.  *n_rows, row_hdv[row] (room for n_hdv * PDMPC_HDV_MAX_CHAINS).
+ *   reachable lanes   polygon row * Hp + k = the HDV's step-(k + 1) set K at its pose intersected with the row's chain polygon (left
+ *                     points of both lanelets, then their right points reversed, moved by the tile offset) by the rule of
+ *                     pdmpc_bound_reachable_sets, closed; an empty intersection is a polygon of 0 vertices (flag PDMPC_BOUND_RESTORED).
+ *                     set_offset (room for n_hdv * PDMPC_HDV_MAX_CHAINS * Hp + 1) is always written; set_x / set_y (capacity entries
+ *                     each) and set_flags (one per polygon, or NULL) only if the lanes fit: PDMPC_ERR_CAPACITY otherwise, and the
+ *                     offsets size a second call.  This is the layout of pdmpc_vehicle_in.hdv_reachable_sets.
+ *   adjacency         n_cav x n_hdv bytes: 1 unless the HDV is behind the CAV (is_hdv_behind.m:13-92 with the CAV's own position;
+ *                     no predecessor lanelet found means "not on one"), 0 for a CAV on another copy of the map.
+ * Lists, rows, offsets and adjacency are written whenever the call gets that far: also when the capacity is too small.  An HDV with
+ * more than PDMPC_HDV_MAX_CHAINS closest lanelets or chains is PDMPC_ERR_CAPACITY with *n_rows = -1 and nothing else promised;
+ * PDMPC_ERR_INVALID for a call before the upload, a trim or lanelet id out of range, n < 0, Hp > PDMPC_HP_MAX or a null array that is
+ * needed; PDMPC_ERR_CAPACITY for more than 64 HDVs or 2^20 CAVs in one call (both twins; config.max_vehicles is not read):
+ * the device keeps 16 x Hp slots of PDMPC_BOUNDED_MAX_COLS vertices per HDV, 256 KB x Hp, allocated on the first call that needs them.
+ * pdmpc_hdv_traffic runs on the handle's device: one staging copy, four launches, one copy back, one synchronisation.  The copy back
+ * moves the room for `capacity` vertices (at most what the slots can hold), not the result's size, which the host learns only from it:
+ * give the call the room the result needs -- the last step's total and some slack, or the exact total of a sizing call -- not a
+ * generous buffer (2 HDVs at Hp 8 with unlimited room copy back 4 MB per call).  pdmpc_hdv_traffic_host is its C++ twin and checker with the map and the sets as arguments (no GPU needed);
+ * both give the same bits.  pdmpc_hdv_lanelet_distances_host: the distance of (px, py) to every lanelet's centre line, distance[n_lanelets]. */
+#define PDMPC_HDV_MAX_CHAINS 16
+int pdmpc_upload_hdv_map(pdmpc_handle* handle, int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x,
+                         const double* left_y, const double* right_x, const double* right_y, const int32_t* succ_offset, const int32_t* succ_index,
+                         const uint8_t* relationship, int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* hdv_local_sets);
+int pdmpc_hdv_traffic(pdmpc_handle* handle, int32_t n_hdv, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw, const int32_t* trim,
+                      const double* tile_dx, const double* tile_dy, int32_t n_cav, const double* cav_x, const double* cav_y, const int32_t* cav_lanelet,
+                      const double* cav_tile_dx, const double* cav_tile_dy, int32_t* closest_offset, int32_t* closest_index, int32_t capacity, int32_t* n_rows,
+                      int32_t* row_hdv, int32_t* set_offset, double* set_x, double* set_y, uint8_t* set_flags, uint8_t* adjacency);
+int pdmpc_hdv_traffic_host(int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x, const double* left_y,
+                           const double* right_x, const double* right_y, const int32_t* succ_offset, const int32_t* succ_index, const uint8_t* relationship,
+                           int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* hdv_local_sets, int32_t n_hdv, const double* x, const double* y,
+                           const double* cos_yaw, const double* sin_yaw, const int32_t* trim, const double* tile_dx, const double* tile_dy, int32_t n_cav,
+                           const double* cav_x, const double* cav_y, const int32_t* cav_lanelet, const double* cav_tile_dx, const double* cav_tile_dy,
+                           int32_t* closest_offset, int32_t* closest_index, int32_t capacity, int32_t* n_rows, int32_t* row_hdv, int32_t* set_offset, double* set_x,
+                           double* set_y, uint8_t* set_flags, uint8_t* adjacency);
+int pdmpc_hdv_lanelet_distances_host(int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x, const double* left_y,
+                                     const double* right_x, const double* right_y, double px, double py, double* distance);
+/* kernel time (HIP events, ms) of the last pdmpc_hdv_traffic: its four launches */
+int pdmpc_hdv_kernel_ms(pdmpc_handle* handle, double* ms);
+
 /* ---- the caller's side of the boundary, natively (csrc/step_controller.cpp and its stages csrc/step_*.hpp) ----
  * One MPC time step of the prioritized sequential controller around pdmpc_plan_step, without any interpreter in the loop:
  * traffic info, coupling, priorities, grouping, computation levels, obstacle assembly, ONE launch, exhaustion handling,
@@ -752,6 +809,23 @@ int pdmpc_controller_create(pdmpc_handle* handle, const pdmpc_controller_config*
 int pdmpc_controller_destroy(pdmpc_controller* c);
 /* one whole time step: build the step problem, plan it with ONE launch (pdmpc_plan_step), apply the result */
 int pdmpc_controller_step(pdmpc_controller* c);
+/* Human-driven vehicles in the controller's steps (HighLevelController.update_hdv_traffic_info).  set_hdvs: n_hdv HDVs
+ * from now on, on the map of the controller's scenario (its per-lanelet left / right points) with the lanelet graph given here
+ * (succ_offset / succ_index / relationship as for pdmpc_upload_hdv_map), hdv_mpa their own automaton (the reference: single_speed
+ * without the recursive-feasibility mask; its Hp the controller's), tile_dx / tile_dy [n_hdv] (or NULL: 0) the map copy each drives on.
+ * set_hdv_measurements: their measured poses [n_hdv], kept until set again.  Every built step (build_step, explore_build,
+ * optimal_build, and so every *_step and *_run, alone or as a member of a sweep) then makes ONE pdmpc_hdv_traffic call on the handle
+ * (a group's rank 0), the host twin without a handle, with trim 1 for every HDV and the CAVs' measured positions and current lanelets,
+ * and every search receives the rows of the HDVs adjacent to its vehicle, the same in every prioritization; the call's time counts into
+ * ms6[0].  hdv_info: lists, rows, sets and adjacency of the last built step (pointers into the controller, valid until the next build;
+ * any may be NULL).  PDMPC_ERR_INVALID: a scenario without lanelets, a handle with the separating-axis checker (the HDV soup is
+ * InterX's), a step before the first measurement, pdmpc_controller_centralized_build with HDVs set (the joint search has no HDV check). */
+int pdmpc_controller_set_hdvs(pdmpc_controller* c, int32_t n_hdv, const pdmpc_mpa* hdv_mpa, const int32_t* succ_offset, const int32_t* succ_index,
+                              const uint8_t* relationship, const double* tile_dx, const double* tile_dy);
+int pdmpc_controller_set_hdv_measurements(pdmpc_controller* c, const double* x, const double* y, const double* yaw);
+int pdmpc_controller_hdv_info(pdmpc_controller* c, int32_t* n_hdv, const int32_t** closest_offset, const int32_t** closest_index, int32_t* n_rows,
+                              const int32_t** row_hdv, const int32_t** set_offset, const double** set_x, const double** set_y, const uint8_t** set_flags,
+                              const uint8_t** adjacency);
 /* n_steps closed-loop time steps in one call; ms[i] (may be NULL) = wall-clock milliseconds of step i */
 int pdmpc_controller_run(pdmpc_controller* c, int32_t n_steps, double* ms);
 /* the two host halves on their own: build_step advances the time step counter and leaves the problem readable with

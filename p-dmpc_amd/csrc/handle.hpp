@@ -4,6 +4,7 @@
 #pragma once
 #include <vector>
 
+#include "hdv_host.hpp"    // the HDV map as it is taken over (host only)
 #include "hip_host.hpp"
 #include "launch_plan.hpp"  // struct Tuning, the plan of a launch (host only)
 #include "pdmpc_device.h"
@@ -269,6 +270,19 @@ struct FcaState {
     TimedLaunch timed;
 };
 
+// pdmpc_upload_hdv_map / pdmpc_hdv_traffic (hdv_kernel.hip): the map and the HDV automaton's local hulls in one device
+// table (hdv_table in step_prep.cpp), the call's workspace with its pinned staging (hdv_layout) and the slots of the lane pass; the
+// workspace and the slots are grown when a call needs more, kept otherwise
+struct HdvState {
+    bool valid = false;  // an upload succeeded
+    HdvMapData map;      // the host's copy: sizes, limits and the offsets of the table
+    int trims = 0, Hp = 0, local_tot = 0;
+    DevBuf<unsigned char> table, ws;
+    DevBuf<double> slots;  // x of every slot, then y
+    PinnedBuf<unsigned char> h_in, h_out;
+    TimedLaunch timed;
+};
+
 // pdmpc_choose_resident / pdmpc_plan_step_chosen (choice_kernel.hip): the staged lists, the read-back block (counters, chosen, cell
 // costs, picked records: ChoiceLayout in choice_host.hpp) and the status tally; grown when a call needs more, kept otherwise
 struct ChoiceState {
@@ -342,6 +356,7 @@ struct pdmpc_handle {
     ReachState reach;
     BoundState bound;
     FcaState fca;
+    HdvState hdv;
     ChoiceState choice;
     SampledState sampled;
     int device_share = 1;                // handles of one process that launch on this device side by side (pdmpc_set_device_share: a group's logical ranks)

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "../../include/pdmpc.h"
+#include "../../include/pdmpc_hdv.h"
 
 #define PDMPC_WAVE 64
 /* Wavefronts per workgroup follow the kernel's registers: 128 VGPRs or fewer give four wavefronts per SIMD, sixteen per workgroup; up to
@@ -523,6 +524,41 @@ struct FcaGroupedArgs {
     FcaGroups g;
 };
 
+// HDV traffic (hdv_kernel.hip; include/pdmpc_hdv.h): the closest lanelets and chains of every HDV, the reachable lane
+// of every (HDV, chain, step) and the CAV/HDV adjacency, in four launches of one call.  A (HDV h, chain c, step k) works in slot
+// (h PDMPC_HDV_MAX_CHAINS + c) Hp + k; the pack pass moves the slots of the chains that exist into the caller's layout: rows =
+// (HDV, chain) in order, polygon row Hp + k, vertices one polygon behind the other, nothing written at or beyond `capacity`.
+#define PDMPC_HDV_WAVE 64             // a workgroup of every pass is one wavefront
+#define PDMPC_HDV_OVER_LISTS 1        // status: an HDV has more than PDMPC_HDV_MAX_CHAINS closest lanelets or chains
+#define PDMPC_HDV_OVER_SLOT 2         // status: a reachable lane did not fit its slot
+struct HdvArgs {
+    pdmpc_hdv_map map;          // the uploaded map (device arrays)
+    int32_t n_hdv, n_cav, Hp, capacity;
+    const double* local_x;      // the HDV automaton's local hulls, polygon trim * Hp + k, x then y
+    const double* local_y;
+    const int32_t* local_off;   // [n_trims Hp + 1]
+    const double* in;           // [6 n_hdv]: x, y, cos(yaw), sin(yaw), tile_dx, tile_dy, one array after the other
+    const int32_t* trim;        // [n_hdv] 0-based
+    const double* cav;          // [4 n_cav]: x, y, tile_dx, tile_dy
+    const int32_t* cav_lanelet; // [n_cav] 1-based
+    int32_t* n_closest;         // [n_hdv] length of the list (the first PDMPC_HDV_MAX_CHAINS ids are kept)
+    int32_t* closest;           // [n_hdv PDMPC_HDV_MAX_CHAINS]
+    int32_t* n_chains;          // [n_hdv]
+    int32_t* chain_id;          // [n_hdv PDMPC_HDV_MAX_CHAINS]
+    int32_t* chain_succ;
+    double* slot_x;             // [slots PDMPC_BOUND_SLOT]
+    double* slot_y;
+    int32_t* slot_n;            // [slots] vertices (closing one included; 0: empty)
+    uint8_t* slot_flags;        // [slots] PDMPC_BOUND_* | PDMPC_BOUND_OVERFLOW
+    int32_t* status;            // [2]: rows, PDMPC_HDV_OVER_*
+    int32_t* row_hdv;           // [n_hdv PDMPC_HDV_MAX_CHAINS]
+    int32_t* set_off;           // [slots + 1]
+    uint8_t* set_flags;         // [slots]
+    double* set_x;              // [capacity]
+    double* set_y;
+    uint8_t* adjacency;         // [n_cav n_hdv]
+};
+
 // The choice among the plans of a batch (choice_kernel.hip; pdmpc_choice in include/pdmpc.h) on the result records
 // where the search left them.  The lists are the caller's with the slots mapped to record slots and checked on the host (api.cpp:
 // stage_choice); cells of no graph are the cells in front of first_graph_cell and from end_graph_cell on.
@@ -564,6 +600,8 @@ void pdmpc_fca_sort_index(int32_t n, const int32_t* collisions, int32_t* priorit
 // the vehicles of all groups, `why` (why_size bytes) names the group that was refused
 int pdmpc_fca_check_groups(int32_t n_groups, const pdmpc_fca_group* groups, int32_t Hp, const double* x, const double* y, const double* cos_yaw,
                            const double* sin_yaw, const int32_t* collisions, const int32_t* priorities, int32_t* n_total, char* why, int32_t why_size);
+// hdv_kernel.hip: closest lanelets and chains, reachable lanes, packing and adjacency on the handle's stream (n_hdv > 0)
+int pdmpc_launch_hdv_traffic(const HdvArgs* args, void* stream);
 // reachable_kernel.hip: the two passes of the reachable-set coupler on the handle's stream
 int pdmpc_launch_reachable_coupling(const ReachArgs* args, void* stream);
 int pdmpc_launch_reachable_coupling_grouped(const ReachArgs* args, void* stream);

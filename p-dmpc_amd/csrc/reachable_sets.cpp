@@ -249,6 +249,12 @@ unsigned bound_one(const double* kx, const double* ky, int m, const double* lx, 
 
 }  // namespace
 
+// bound_one for the host twin of the HDV traffic call (hdv.cpp), which bounds by the same rule
+unsigned pdmpc_bound_one_host(const double* kx, const double* ky, int m, const double* lx, const double* ly, int nl, std::vector<double>& ox, std::vector<double>& oy) {
+    BoundScratch scratch;
+    return bound_one(kx, ky, m, lx, ly, nl, scratch, ox, oy);
+}
+
 // area of the intersection of two simple clockwise polygons given open (reachability.polygon_overlap_area)
 double pdmpc_polygon_overlap_area_host(const double* ax, const double* ay, int ma, const double* bx, const double* by, int mb) {
     std::vector<double> r((size_t)2 * (ma + mb));

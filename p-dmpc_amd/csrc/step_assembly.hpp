@@ -250,7 +250,8 @@ inline int assemble_step(pdmpc_controller* c, bool seq_given = false) {
             c->as.empty_set = none.finish();
             c->as.empty_done = true;
         }
-        I.hdv_reachable_sets = c->as.empty_set;
+        // the rows of the HDVs adjacent to i, the same in every prioritization of the step (IterationData.filter :113)
+        I.hdv_reachable_sets = c->hdv.n > 0 ? c->hdv.set_of(i) : c->as.empty_set;
         // sequential predecessors as slots
         for (const int32_t* q = seq_pred.begin(i); q != seq_pred.end(i); ++q) c->prob.pred_index.push_back(c->pri.slot_of[*q]);
         c->prob.pred_offset[s + 1] = (int32_t)c->prob.pred_index.size();

@@ -11,6 +11,7 @@ namespace {
 // what every centralized entry point refuses before anything advances: more vehicles than a joint problem holds, and a handle whose
 // checker the joint search does not run
 inline int centralized_refusal(pdmpc_controller* c) {
+    if (c->hdv.n > 0) return cfail(c, PDMPC_ERR_INVALID, "centralized control: the joint search has no check against HDV sets (pdmpc_controller_set_hdvs)");
     if (c->sc.n > PDMPC_JOINT_MAX) return cfail(c, PDMPC_ERR_CAPACITY, "centralized control: the controller has more than PDMPC_JOINT_MAX vehicles");
     if (c->h) {
         pdmpc_config hc{};

@@ -16,6 +16,8 @@
 #include <cassert>
 #include <chrono>
 #include <cstdint>
+#include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -300,6 +302,72 @@ int gather_fca(pdmpc_controller* const* members, PrepScratch::Fca& F, const std:
     return PDMPC_OK;
 }
 
+// ---- human-driven vehicles: the traffic-info stage of a member with HDVs, ONE pdmpc_hdv_traffic per step on the handle
+// (on a group: its rank 0, which h is), the host twin without one.  A handle holds one map: the controller whose map it holds is noted
+// here, and a member that finds another's there uploads its own first (members of a sweep share the handle).
+std::mutex g_hdv_mutex;
+std::map<pdmpc_handle*, const pdmpc_controller*> g_hdv_map_of;
+
+int hdv_upload(pdmpc_handle* h, pdmpc_controller* c) {
+    const HdvTraffic& H = c->hdv;
+    std::lock_guard<std::mutex> lock(g_hdv_mutex);
+    auto it = g_hdv_map_of.find(h);
+    if (it != g_hdv_map_of.end() && it->second == c) return PDMPC_OK;
+    const pdmpc_polygon_set local = view_polygons(H.local_off, H.local_x, H.local_y);
+    const int rc = pdmpc_upload_hdv_map(h, (int32_t)H.lan_off.size() - 1, H.lan_off.data(), H.lan_off.data(), H.left_x.data(), H.left_y.data(), H.right_x.data(), H.right_y.data(),
+                                        H.succ_off.data(), H.succ_idx.data(), H.rel.data(), H.n_trims, c->sc.Hp, &local);
+    if (rc) return cfail(c, rc, std::string("pdmpc_upload_hdv_map: ") + pdmpc_last_error());
+    g_hdv_map_of[h] = c;
+    return PDMPC_OK;
+}
+void hdv_forget(const pdmpc_controller* c) {  // (its map may stay on a handle: whoever calls next finds another owner and uploads)
+    std::lock_guard<std::mutex> lock(g_hdv_mutex);
+    for (auto it = g_hdv_map_of.begin(); it != g_hdv_map_of.end();) it = it->second == c ? g_hdv_map_of.erase(it) : std::next(it);
+}
+
+int hdv_traffic_stage(pdmpc_handle* h, pdmpc_controller* c) {
+    HdvTraffic& H = c->hdv;
+    if (H.n == 0) return PDMPC_OK;
+    if (!H.measured) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_measurements before the first step with HDVs");
+    const int n = c->sc.n, Hp = c->sc.Hp;
+    const size_t lists = (size_t)H.n * PDMPC_HDV_MAX_CHAINS;
+    H.closest_off.assign((size_t)H.n + 1, 0);
+    H.closest_idx.resize(lists);
+    H.row_hdv.resize(lists);
+    H.set_off.assign(lists * Hp + 1, 0);
+    H.set_flags.resize(lists * Hp);
+    H.adjacency.assign((size_t)n * H.n, 0);
+    if (H.set_x.size() < 4096) {
+        H.set_x.resize(4096);
+        H.set_y.resize(4096);
+    }
+    if (h)
+        if (const int rc = hdv_upload(h, c)) return rc;
+    const pdmpc_polygon_set local = view_polygons(H.local_off, H.local_x, H.local_y);
+    auto call = [&]() {
+        const int32_t cap = (int32_t)H.set_x.size();
+        if (h)
+            return pdmpc_hdv_traffic(h, H.n, H.x.data(), H.y.data(), H.cos_yaw.data(), H.sin_yaw.data(), H.trim.data(), H.tile_dx.data(), H.tile_dy.data(), n, c->tr.mx.data(),
+                                     c->tr.my.data(), c->in.current_lanelet.data(), H.cav_tile_dx.data(), H.cav_tile_dy.data(), H.closest_off.data(), H.closest_idx.data(), cap,
+                                     &H.n_rows, H.row_hdv.data(), H.set_off.data(), H.set_x.data(), H.set_y.data(), H.set_flags.data(), H.adjacency.data());
+        return pdmpc_hdv_traffic_host((int32_t)H.lan_off.size() - 1, H.lan_off.data(), H.lan_off.data(), H.left_x.data(), H.left_y.data(), H.right_x.data(), H.right_y.data(),
+                                      H.succ_off.data(), H.succ_idx.data(), H.rel.data(), H.n_trims, Hp, &local, H.n, H.x.data(), H.y.data(), H.cos_yaw.data(), H.sin_yaw.data(),
+                                      H.trim.data(), H.tile_dx.data(), H.tile_dy.data(), n, c->tr.mx.data(), c->tr.my.data(), c->in.current_lanelet.data(), H.cav_tile_dx.data(),
+                                      H.cav_tile_dy.data(), H.closest_off.data(), H.closest_idx.data(), cap, &H.n_rows, H.row_hdv.data(), H.set_off.data(), H.set_x.data(),
+                                      H.set_y.data(), H.set_flags.data(), H.adjacency.data());
+    };
+    int rc = call();
+    if (rc == PDMPC_ERR_CAPACITY && H.n_rows >= 0 && (size_t)H.set_off[(size_t)H.n_rows * Hp] > H.set_x.size()) {  // (the offsets size the second call)
+        const size_t need = (size_t)H.set_off[(size_t)H.n_rows * Hp];
+        H.set_x.resize(need + need / 4);
+        H.set_y.resize(need + need / 4);
+        rc = call();
+    }
+    if (rc) return cfail(c, rc, h ? std::string("pdmpc_hdv_traffic: ") + pdmpc_last_error() : "pdmpc_hdv_traffic_host failed");
+    H.gather(n, Hp);
+    return PDMPC_OK;
+}
+
 // The step problems of M members (of one Hp, all on the handle h or all without one), built with ONE step preparation for all of them:
 // with a handle the grouped device calls, without one the host twins.  This is the only place that asks which.  batch.n_perm > 0: every
 // member's explorative batch of n_perm prioritizations behind its step (pdmpc_controller_explore_build's statements, in its order).
@@ -322,6 +390,8 @@ int build_members(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, B
     S.prio.calls = 0;
     for (size_t m = 0; m < M; ++m)
         if (const int rc = begin_step(members[m], S.prep[m])) return rc;
+    for (size_t m = 0; m < M; ++m)  // (a member with HDVs makes its own traffic call; folding the members' calls into one is a follow-up)
+        if (const int rc = hdv_traffic_stage(h, members[m])) return rc;
     // who takes part in which grouped call: bounded (step Hp only / every step: one bounding call each) or the plain hulls
     std::vector<int> bounded_last, bounded_all, hulls;
     for (size_t m = 0; m < M; ++m) {
@@ -632,7 +702,104 @@ int pdmpc_controller_set_reachability(pdmpc_controller* c, const pdmpc_mpa* mpa)
     return PDMPC_OK;
 }
 
+// ---- human-driven vehicles
+int pdmpc_controller_set_hdvs(pdmpc_controller* c, int32_t n_hdv, const pdmpc_mpa* hdv_mpa, const int32_t* succ_offset, const int32_t* succ_index, const uint8_t* relationship,
+                              const double* tile_dx, const double* tile_dy) {
+    if (!c || n_hdv < 1 || !hdv_mpa || !succ_offset || !relationship) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdvs: bad argument");
+    const int n_lan = (int)c->sc.bl_left.size();
+    bool lanelets = n_lan > 0;
+    for (const VehicleDef& V : c->sc.veh) lanelets = lanelets && !V.lanelets_index.empty();
+    if (!lanelets) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdvs: HDVs need a scenario with lanelets");
+    if (c->h) {  // the HDV soup is the InterX checker's (edge_checks.hpp); the separating-axis checker has no test against it
+        pdmpc_config hc{};
+        int32_t has_mpa = 0;
+        if (pdmpc_get_config(c->h, &hc, &has_mpa) != PDMPC_OK) return cfail(c, PDMPC_ERR_INVALID, "bad backend handle");
+        if (hc.checker == PDMPC_CHECK_SAT) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdvs: the separating-axis checker does not check HDV sets");
+    }
+    if (hdv_mpa->Hp != c->sc.Hp) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdvs: the HDV automaton's Hp differs from the controller's");
+    HdvTraffic H;
+    H.lan_off.assign((size_t)n_lan + 1, 0);
+    for (int i = 0; i < n_lan; ++i) {
+        const Poly &L = c->sc.bl_left[(size_t)i], &R = c->sc.bl_right[(size_t)i];
+        H.left_x.insert(H.left_x.end(), L.x.begin(), L.x.end());
+        H.left_y.insert(H.left_y.end(), L.y.begin(), L.y.end());
+        H.right_x.insert(H.right_x.end(), R.x.begin(), R.x.end());
+        H.right_y.insert(H.right_y.end(), R.y.begin(), R.y.end());
+        if (L.x.size() != R.x.size()) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdvs: a lanelet needs as many left as right points");
+        H.lan_off[(size_t)i + 1] = (int32_t)H.left_x.size();
+    }
+    if (succ_offset[0] != 0 || succ_offset[n_lan] < 0 || (succ_offset[n_lan] > 0 && !succ_index)) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdvs: bad successor lists");
+    H.succ_off.assign(succ_offset, succ_offset + n_lan + 1);
+    H.succ_idx.assign(succ_index, succ_index + succ_offset[n_lan]);
+    H.succ_idx.push_back(0);
+    H.rel.assign(relationship, relationship + (size_t)n_lan * n_lan);
+    H.n_trims = hdv_mpa->n_trims;
+    H.local_off.assign((size_t)hdv_mpa->n_trims * hdv_mpa->Hp + 1, 0);
+    int rc = pdmpc_local_reachable_sets(hdv_mpa, 0, H.local_off.data(), nullptr, nullptr);
+    if (rc != PDMPC_OK && rc != PDMPC_ERR_CAPACITY) return cfail(c, rc, "pdmpc_local_reachable_sets failed");
+    H.local_x.resize((size_t)H.local_off.back() + 1);
+    H.local_y.resize((size_t)H.local_off.back() + 1);
+    rc = pdmpc_local_reachable_sets(hdv_mpa, H.local_off.back(), H.local_off.data(), H.local_x.data(), H.local_y.data());
+    if (rc) return cfail(c, rc, "pdmpc_local_reachable_sets failed");
+    H.n = n_hdv;
+    H.tile_dx.assign((size_t)n_hdv, 0.0);
+    H.tile_dy.assign((size_t)n_hdv, 0.0);
+    if (tile_dx) H.tile_dx.assign(tile_dx, tile_dx + n_hdv);
+    if (tile_dy) H.tile_dy.assign(tile_dy, tile_dy + n_hdv);
+    H.trim.assign((size_t)n_hdv, 1);  // ManualVehicle.m:33: local_reachable_sets(1, :)
+    for (const VehicleDef& V : c->sc.veh) {
+        H.cav_tile_dx.push_back(V.tile_dx);
+        H.cav_tile_dy.push_back(V.tile_dy);
+    }
+    hdv_forget(c);
+    if (c->h) {  // (the map's own refusals -- limits, successor ids -- come from the one place that checks them)
+        c->hdv = H;
+        if ((rc = hdv_upload(c->h, c))) {
+            c->hdv = HdvTraffic();
+            return rc;
+        }
+    } else
+        c->hdv = std::move(H);
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_set_hdv_measurements(pdmpc_controller* c, const double* x, const double* y, const double* yaw) {
+    if (!c || !x || !y || !yaw) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_measurements: null argument");
+    HdvTraffic& H = c->hdv;
+    if (H.n == 0) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_measurements before pdmpc_controller_set_hdvs");
+    H.x.assign(x, x + H.n);
+    H.y.assign(y, y + H.n);
+    H.yaw.assign(yaw, yaw + H.n);
+    H.cos_yaw.resize((size_t)H.n);
+    H.sin_yaw.resize((size_t)H.n);
+    for (int q = 0; q < H.n; ++q) {
+        H.cos_yaw[(size_t)q] = std::cos(yaw[q]);
+        H.sin_yaw[(size_t)q] = std::sin(yaw[q]);
+    }
+    H.measured = true;
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_hdv_info(pdmpc_controller* c, int32_t* n_hdv, const int32_t** closest_offset, const int32_t** closest_index, int32_t* n_rows, const int32_t** row_hdv,
+                              const int32_t** set_offset, const double** set_x, const double** set_y, const uint8_t** set_flags, const uint8_t** adjacency) {
+    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
+    const HdvTraffic& H = c->hdv;
+    if (H.n == 0 || H.closest_off.empty()) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_hdv_info before a step was built with HDVs");
+    if (n_hdv) *n_hdv = H.n;
+    if (closest_offset) *closest_offset = H.closest_off.data();
+    if (closest_index) *closest_index = H.closest_idx.data();
+    if (n_rows) *n_rows = H.n_rows;
+    if (row_hdv) *row_hdv = H.row_hdv.data();
+    if (set_offset) *set_offset = H.set_off.data();
+    if (set_x) *set_x = H.set_x.data();
+    if (set_y) *set_y = H.set_y.data();
+    if (set_flags) *set_flags = H.set_flags.data();
+    if (adjacency) *adjacency = H.adjacency.data();
+    return PDMPC_OK;
+}
+
 int pdmpc_controller_destroy(pdmpc_controller* c) {
+    if (c) hdv_forget(c);
     delete c;
     return PDMPC_OK;
 }

@@ -131,13 +131,14 @@ inline void arc_projection(double px, double py, const std::vector<double>& cx, 
 
 // sample_reference_trajectory.m:1-99 (indices 1-based)
 inline void sample_reference(int n_samples, const std::vector<double>& rx, const std::vector<double>& ry, double x_cur, double y_cur, const std::vector<double>& step,
-                      std::vector<double>& out_x, std::vector<double>& out_y, std::vector<int32_t>& points_index) {
+                      std::vector<double>& out_x, std::vector<double>& out_y, std::vector<int32_t>& points_index, int* current_point_index = nullptr) {
     out_x.assign(n_samples, 0.0);
     out_y.assign(n_samples, 0.0);
     points_index.assign(n_samples, 0);
     double cx, cy;
     int point_index;
     arc_projection(x_cur, y_cur, rx, ry, cx, cy, point_index);
+    if (current_point_index) *current_point_index = point_index;  // (sample_reference_trajectory.m: before the loop's wrap-around)
     const int n_line = (int)rx.size();
     const bool is_loop = norm2(rx[0] - rx[n_line - 1], ry[0] - ry[n_line - 1]) < 1e-8;
     bool at_end = point_index == n_line;
@@ -276,6 +277,16 @@ inline void adopt_fca(int n, FcaInputs& fca, const int32_t* collisions, const in
     std::copy(priorities, priorities + n, fca.prio.begin());
 }
 
+// get_predicted_lanelets.m:44,61: the lanelet vehicle v is on, from the path point it is at (0: a scenario without lanelets)
+inline int32_t current_lanelet(const Scenario& sc, int v, int current_point_index) {
+    const VehicleDef& V = sc.veh[v];
+    const int n_lan = (int)V.lanelets_index.size();
+    if (n_lan == 0) return 0;
+    int q = 1;
+    for (int u = 0; u < n_lan; ++u) q += current_point_index > V.points_index[u];
+    return V.lanelets_index[std::min(q, n_lan) - 1];
+}
+
 // ---- the stages of a step before its priorities, in their order
 inline void traffic_info(const Scenario& sc, const Traffic& tr, StepInputs& in) {
     const int n = sc.n, Hp = sc.Hp;
@@ -288,6 +299,7 @@ inline void traffic_info(const Scenario& sc, const Traffic& tr, StepInputs& in) 
     in.v_ref.resize(n);
     in.bnd_left.resize(n);
     in.bnd_right.resize(n);
+    in.current_lanelet.assign(n, 0);
     std::vector<double> step(Hp);
     std::vector<int32_t> pidx;
     for (int v = 0; v < n; ++v) {
@@ -298,8 +310,10 @@ inline void traffic_info(const Scenario& sc, const Traffic& tr, StepInputs& in) 
         vref.assign(Hp, sc.veh[v].reference_speed);
         const double v_current = sc.trim_speed[in.trims[v] - 1];
         for (int q = 0; q < Hp; ++q) step[q] = (((q == 0 ? v_current : vref[q - 1]) + vref[q]) / 2) * sc.cfg.dt_seconds;
-        sample_reference(Hp, sc.veh[v].px, sc.veh[v].py, tr.mx[v], tr.my[v], step, in.ref_x[v], in.ref_y[v], pidx);
+        int cpi = 0;
+        sample_reference(Hp, sc.veh[v].px, sc.veh[v].py, tr.mx[v], tr.my[v], step, in.ref_x[v], in.ref_y[v], pidx, &cpi);
         lanelet_boundary(sc, v, pidx, in.bnd_left[v], in.bnd_right[v]);
+        in.current_lanelet[v] = current_lanelet(sc, v, cpi);
     }
 }
 

@@ -1,5 +1,6 @@
 // step_prep.cpp — the step-preparation calls of the C ABI: device work that runs once per time step before the searches are packed
-// (unique prioritizations, reachable-set coupling, lanelet bounding and the coupling on the bounded sets, future collision assessment).
+// (unique prioritizations, reachable-set coupling, lanelet bounding and the coupling on the bounded sets, future collision assessment,
+// HDV traffic).
 //
 // Every call but pdmpc_unique_priorities(_grouped) follows one recipe: carve ONE pinned staging block and ONE device workspace with the same
 // offsets (Carver), stage the inputs, copy them in once, launch between an event pair (timed_launch), copy the result back, synchronise.
@@ -767,6 +768,193 @@ int pdmpc_fca_collisions_grouped(pdmpc_handle* h, int32_t n_groups, const pdmpc_
 int pdmpc_fca_kernel_ms(pdmpc_handle* h, double* ms) {
     if (!h || !ms) return fail(PDMPC_ERR_INVALID, "null argument");
     *ms = (double)h->fca.timed.ms;
+    return PDMPC_OK;
+}
+
+// ---- human-driven vehicles on the device (hdv_kernel.hip)
+namespace {
+// HdvState::table: the map (HdvMapData's arrays) and the HDV automaton's local hulls (x of every vertex, then y)
+struct HdvTable {
+    size_t pt_off, pts, succ_off, succ_idx, rel, local_off, local_xy, total;
+};
+HdvTable hdv_table(const HdvMapData& m, int n_polygons, int local_tot) {
+    Carver c;
+    HdvTable T;
+    T.pt_off = c.take<int32_t>((size_t)m.n_lanelets + 1);
+    T.pts = c.take<double>((size_t)6 * m.n_pts);
+    T.succ_off = c.take<int32_t>((size_t)m.n_lanelets + 1);
+    T.succ_idx = c.take<int32_t>((size_t)m.n_succ);
+    T.rel = c.take<uint8_t>((size_t)m.n_lanelets * m.n_lanelets);
+    T.local_off = c.take<int32_t>((size_t)n_polygons + 1);
+    T.local_xy = c.take<double>((size_t)2 * local_tot);
+    T.total = c.end8();
+    return T;
+}
+// HdvState::ws and its pinned staging: the inputs are the block's first in_bytes, what the call reads back everything from `out` on
+// (the packed vertices last: x of `capacity` vertices, then y)
+struct HdvLayout {
+    size_t in, cav, trim, cav_lanelet, in_bytes, n_chains, chain_id, chain_succ, slot_n, slot_flags;
+    size_t out, status, n_closest, closest, row_hdv, set_off, set_flags, adjacency, set_xy, total;
+};
+HdvLayout hdv_layout(int n, int nc, int Hp, int capacity) {
+    const size_t lists = (size_t)n * PDMPC_HDV_MAX_CHAINS, slots = lists * Hp;
+    Carver c;
+    HdvLayout L;
+    L.in = c.take<double>((size_t)6 * n);
+    L.cav = c.take<double>((size_t)4 * nc);
+    L.trim = c.take<int32_t>((size_t)n);
+    L.cav_lanelet = c.take<int32_t>((size_t)nc);
+    L.in_bytes = c.end8();
+    L.n_chains = c.take<int32_t>((size_t)n);
+    L.chain_id = c.take<int32_t>(lists);
+    L.chain_succ = c.take<int32_t>(lists);
+    L.slot_n = c.take<int32_t>(slots);
+    L.slot_flags = c.take<uint8_t>(slots);
+    L.out = c.end8();
+    L.status = c.take<int32_t>(2);
+    L.n_closest = c.take<int32_t>((size_t)n);
+    L.closest = c.take<int32_t>(lists);
+    L.row_hdv = c.take<int32_t>(lists);
+    L.set_off = c.take<int32_t>(slots + 1);
+    L.set_flags = c.take<uint8_t>(slots);
+    L.adjacency = c.take<uint8_t>((size_t)nc * n);
+    L.set_xy = c.take<double>((size_t)2 * capacity);
+    L.total = c.at;
+    return L;
+}
+}  // namespace
+
+int pdmpc_upload_hdv_map(pdmpc_handle* h, int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x, const double* left_y,
+                         const double* right_x, const double* right_y, const int32_t* succ_offset, const int32_t* succ_index, const uint8_t* relationship,
+                         int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* hdv_local_sets) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    HdvState& S = h->hdv;
+    S.valid = false;
+    const char* why = nullptr;
+    int rc = S.map.points(n_lanelets, left_offset, right_offset, left_x, left_y, right_x, right_y, &why);
+    if (!rc) rc = S.map.graph(succ_offset, succ_index, relationship, &why);
+    if (!rc) rc = hdv_check_sets(n_trims, Hp, hdv_local_sets, &why);
+    if (rc) return fail(rc, std::string("pdmpc_upload_hdv_map: ") + why);
+    const int n_polygons = n_trims * Hp, p0 = hdv_local_sets->offset[0], local_tot = hdv_local_sets->offset[n_polygons] - p0;
+    const HdvMapData& m = S.map;
+    const HdvTable T = hdv_table(m, n_polygons, local_tot);
+    std::vector<unsigned char> stage(T.total, 0);
+    std::memcpy(stage.data() + T.pt_off, m.pt_off.data(), m.pt_off.size() * sizeof(int32_t));
+    std::memcpy(stage.data() + T.pts, m.pts.data(), m.pts.size() * sizeof(double));
+    std::memcpy(stage.data() + T.succ_off, m.succ_off.data(), m.succ_off.size() * sizeof(int32_t));
+    if (m.n_succ) std::memcpy(stage.data() + T.succ_idx, m.succ_idx.data(), m.succ_idx.size() * sizeof(int32_t));
+    std::memcpy(stage.data() + T.rel, m.rel.data(), m.rel.size());
+    int32_t* loff = (int32_t*)(stage.data() + T.local_off);
+    for (int p = 0; p <= n_polygons; ++p) loff[p] = hdv_local_sets->offset[p] - p0;
+    std::memcpy(stage.data() + T.local_xy, hdv_local_sets->x + p0, (size_t)local_tot * sizeof(double));
+    std::memcpy(stage.data() + T.local_xy + (size_t)local_tot * sizeof(double), hdv_local_sets->y + p0, (size_t)local_tot * sizeof(double));
+    ON_DEVICE(h->cfg.device);
+    if (S.table.ensure_exact(T.total)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the HDV map");
+    HIPCHK(hipMemcpy(S.table.p, stage.data(), T.total, hipMemcpyHostToDevice));
+    S.trims = n_trims;
+    S.Hp = Hp;
+    S.local_tot = local_tot;
+    S.valid = true;
+    return PDMPC_OK;
+}
+
+int pdmpc_hdv_traffic(pdmpc_handle* h, int32_t n_hdv, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw, const int32_t* trim,
+                      const double* tile_dx, const double* tile_dy, int32_t n_cav, const double* cav_x, const double* cav_y, const int32_t* cav_lanelet,
+                      const double* cav_tile_dx, const double* cav_tile_dy, int32_t* closest_offset, int32_t* closest_index, int32_t capacity, int32_t* n_rows,
+                      int32_t* row_hdv, int32_t* set_offset, double* set_x, double* set_y, uint8_t* set_flags, uint8_t* adjacency) {
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    HdvState& S = h->hdv;
+    if (!S.valid) return fail(PDMPC_ERR_INVALID, "pdmpc_hdv_traffic before pdmpc_upload_hdv_map");
+    const char* why = nullptr;
+    if (const int rc = hdv_check_call(S.map.n_lanelets, S.trims, n_hdv, x, y, cos_yaw, sin_yaw, trim, tile_dx, tile_dy, n_cav, cav_x, cav_y, cav_lanelet, cav_tile_dx,
+                                      cav_tile_dy, closest_offset, closest_index, capacity, n_rows, row_hdv, set_offset, adjacency, &why))
+        return fail(rc, std::string("pdmpc_hdv_traffic: ") + why);
+    *n_rows = 0;
+    closest_offset[0] = 0;
+    set_offset[0] = 0;
+    if (n_hdv == 0) return PDMPC_OK;
+    const int Hp = S.Hp, n = n_hdv, nc = n_cav;
+    const size_t lists = (size_t)n * PDMPC_HDV_MAX_CHAINS, slots = lists * Hp;
+    // (no more vertices are read back than the slots can hold, whatever room the caller has)
+    const int cap = (int)std::min<size_t>((size_t)capacity, set_x && set_y ? slots * PDMPC_BOUND_SLOT : 0);
+    ON_DEVICE(h->cfg.device);
+    const HdvLayout L = hdv_layout(n, nc, Hp, cap);
+    if (S.ws.ensure(L.total) || S.slots.ensure(2 * slots * PDMPC_BOUND_SLOT) || S.h_in.ensure(L.in_bytes) || S.h_out.ensure(L.total - L.out))
+        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the HDV traffic call");
+    unsigned char *hin = S.h_in.p, *ws = S.ws.p;
+    double* in = (double*)(hin + L.in);
+    stage_poses(in, (size_t)n, x, y, cos_yaw, sin_yaw, (int32_t*)(hin + L.trim), trim);
+    std::memcpy(in + 4 * (size_t)n, tile_dx, (size_t)n * sizeof(double));
+    std::memcpy(in + 5 * (size_t)n, tile_dy, (size_t)n * sizeof(double));
+    if (nc) {
+        stage_poses((double*)(hin + L.cav), (size_t)nc, cav_x, cav_y, cav_tile_dx, cav_tile_dy);
+        std::memcpy(hin + L.cav_lanelet, cav_lanelet, (size_t)nc * sizeof(int32_t));
+    }
+    const HdvTable T = hdv_table(S.map, S.trims * Hp, S.local_tot);
+    const unsigned char* tb = S.table.p;
+    HdvArgs A;
+    A.map = S.map.view((const int32_t*)(tb + T.pt_off), (const double*)(tb + T.pts), (const int32_t*)(tb + T.succ_off), (const int32_t*)(tb + T.succ_idx), tb + T.rel);
+    A.n_hdv = n;
+    A.n_cav = nc;
+    A.Hp = Hp;
+    A.capacity = cap;
+    A.local_x = (const double*)(tb + T.local_xy);
+    A.local_y = A.local_x + S.local_tot;
+    A.local_off = (const int32_t*)(tb + T.local_off);
+    A.in = (const double*)(ws + L.in);
+    A.trim = (const int32_t*)(ws + L.trim);
+    A.cav = (const double*)(ws + L.cav);
+    A.cav_lanelet = (const int32_t*)(ws + L.cav_lanelet);
+    A.n_closest = (int32_t*)(ws + L.n_closest);
+    A.closest = (int32_t*)(ws + L.closest);
+    A.n_chains = (int32_t*)(ws + L.n_chains);
+    A.chain_id = (int32_t*)(ws + L.chain_id);
+    A.chain_succ = (int32_t*)(ws + L.chain_succ);
+    A.slot_x = S.slots.p;
+    A.slot_y = S.slots.p + slots * PDMPC_BOUND_SLOT;
+    A.slot_n = (int32_t*)(ws + L.slot_n);
+    A.slot_flags = ws + L.slot_flags;
+    A.status = (int32_t*)(ws + L.status);
+    A.row_hdv = (int32_t*)(ws + L.row_hdv);
+    A.set_off = (int32_t*)(ws + L.set_off);
+    A.set_flags = ws + L.set_flags;
+    A.set_x = (double*)(ws + L.set_xy);
+    A.set_y = A.set_x + cap;
+    A.adjacency = ws + L.adjacency;
+    HIPCHK(hipMemcpyAsync(ws, hin, L.in_bytes, hipMemcpyHostToDevice, h->stream));
+    if (const int rc = timed_launch(h, S.timed, pdmpc_launch_hdv_traffic, A, "HDV traffic")) return rc;
+    HIPCHK(hipMemcpyAsync(S.h_out.p, ws + L.out, L.total - L.out, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(sync_stream(h));
+    S.timed.fold();
+    auto back = [&](size_t at) { return (const unsigned char*)S.h_out.p + (at - L.out); };  // the read-back block at the workspace's offsets
+    const int32_t* status = (const int32_t*)back(L.status);
+    *n_rows = -1;
+    if (status[1] & PDMPC_HDV_OVER_LISTS) return fail(PDMPC_ERR_CAPACITY, "pdmpc_hdv_traffic: an HDV has more than PDMPC_HDV_MAX_CHAINS closest lanelets or chains");
+    const int32_t *n_closest = (const int32_t*)back(L.n_closest), *closest = (const int32_t*)back(L.closest);
+    for (int g = 0; g < n; ++g) {
+        std::memcpy(closest_index + closest_offset[g], closest + (size_t)g * PDMPC_HDV_MAX_CHAINS, (size_t)n_closest[g] * sizeof(int32_t));
+        closest_offset[g + 1] = closest_offset[g] + n_closest[g];
+    }
+    const int rows = status[0];
+    *n_rows = rows;
+    std::memcpy(row_hdv, back(L.row_hdv), (size_t)rows * sizeof(int32_t));
+    std::memcpy(set_offset, back(L.set_off), ((size_t)rows * Hp + 1) * sizeof(int32_t));
+    if (nc) std::memcpy(adjacency, back(L.adjacency), (size_t)nc * n);
+    if (status[1] & PDMPC_HDV_OVER_SLOT) return fail(PDMPC_ERR_CAPACITY, "pdmpc_hdv_traffic: a reachable lane has more than PDMPC_BOUNDED_MAX_COLS vertices");
+    const int32_t total = set_offset[(size_t)rows * Hp];
+    if (capacity < total || (total && (!set_x || !set_y))) return fail(PDMPC_ERR_CAPACITY, "pdmpc_hdv_traffic: capacity too small for the reachable lanes");
+    const double* hx = (const double*)back(L.set_xy);
+    if (total) {
+        std::memcpy(set_x, hx, (size_t)total * sizeof(double));
+        std::memcpy(set_y, hx + cap, (size_t)total * sizeof(double));
+    }
+    if (set_flags) std::memcpy(set_flags, back(L.set_flags), (size_t)rows * Hp);
+    return PDMPC_OK;
+}
+
+int pdmpc_hdv_kernel_ms(pdmpc_handle* h, double* ms) {
+    if (!h || !ms) return fail(PDMPC_ERR_INVALID, "null argument");
+    *ms = (double)h->hdv.timed.ms;
     return PDMPC_OK;
 }
 

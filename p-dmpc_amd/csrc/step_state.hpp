@@ -161,6 +161,7 @@ struct pdmpc_controller {
     StepInputs in;     // rewritten every step (begin_step, the step preparation's coupling)
     ReachState reach;
     FcaInputs fca;
+    HdvTraffic hdv;    // written by pdmpc_controller_set_hdvs / _set_hdv_measurements and the step's traffic call
     Assembly as;
     Batch x;
     Centralized cen;

@@ -194,7 +194,56 @@ struct StepInputs {
     std::vector<Poly> occ_offset, occ_plain;
     std::vector<std::vector<double>> ref_x, ref_y, v_ref;
     std::vector<Poly> bnd_left, bnd_right;
+    std::vector<int32_t> current_lanelet;  // the lanelet id every vehicle is on (get_predicted_lanelets.m:44,61); 0 without lanelets
     std::vector<uint8_t> adjacency;  // n x n row-major
+};
+// Human-driven vehicles (pdmpc_controller_set_hdvs): what pdmpc_hdv_traffic is called with -- the scenario's lanelets
+// flattened, the lanelet graph, the local sets of the HDVs' automaton, tiles and the last measured poses --, what the step's ONE call
+// left (pdmpc_controller_hdv_info), and per CAV the rows of the HDVs adjacent to it as the set its searches receive.
+struct HdvTraffic {
+    int n = 0;  // HDVs; 0: none set, and a step is built as without this struct
+    bool measured = false;
+    std::vector<int32_t> lan_off, succ_off, succ_idx;
+    std::vector<double> left_x, left_y, right_x, right_y;
+    std::vector<uint8_t> rel;
+    int n_trims = 0;
+    std::vector<int32_t> local_off;
+    std::vector<double> local_x, local_y;
+    std::vector<double> tile_dx, tile_dy, x, y, yaw, cos_yaw, sin_yaw;
+    std::vector<int32_t> trim;
+    std::vector<double> cav_tile_dx, cav_tile_dy;
+    int32_t n_rows = 0;
+    std::vector<int32_t> closest_off, closest_idx, row_hdv, set_off;
+    std::vector<double> set_x, set_y;
+    std::vector<uint8_t> set_flags, adjacency;
+    std::vector<std::vector<int32_t>> cav_off;
+    std::vector<std::vector<double>> cav_x, cav_y;
+    // CAV v's set (valid until the next step's call)
+    [[maybe_unused]] pdmpc_polygon_set set_of(int v) const { return view_polygons(cav_off[(size_t)v], cav_x[(size_t)v], cav_y[(size_t)v]); }
+    // ... rebuilt from the call's output: the rows of the adjacent HDVs in row order, polygon row * Hp + k (vectorize_all_obstacles.m:33-62)
+    [[maybe_unused]] void gather(int n_cav, int Hp) {
+        cav_off.resize((size_t)n_cav);
+        cav_x.resize((size_t)n_cav);
+        cav_y.resize((size_t)n_cav);
+        for (int v = 0; v < n_cav; ++v) {
+            std::vector<int32_t>& off = cav_off[(size_t)v];
+            std::vector<double>&cx = cav_x[(size_t)v], &cy = cav_y[(size_t)v];
+            off.assign(1, 0);
+            cx.clear();
+            cy.clear();
+            for (int r = 0; r < n_rows; ++r) {
+                if (!adjacency[(size_t)v * n + row_hdv[(size_t)r]]) continue;
+                for (int k = 0; k < Hp; ++k) {
+                    const int32_t a = set_off[(size_t)r * Hp + k], b = set_off[(size_t)r * Hp + k + 1];
+                    cx.insert(cx.end(), set_x.begin() + a, set_x.begin() + b);
+                    cy.insert(cy.end(), set_y.begin() + a, set_y.begin() + b);
+                    off.push_back((int32_t)cx.size());
+                }
+            }
+            cx.push_back(0.0);  // (never an empty array)
+            cy.push_back(0.0);
+        }
+    }
 };
 // reachable sets: the switches, and per step every vehicle's Hp sets at its pose, closed (HighLevelController.m:219-263)
 struct ReachState {

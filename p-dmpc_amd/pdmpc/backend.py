@@ -951,6 +951,25 @@ class Handle:
         _check(self.L, self.L.pdmpc_fca_kernel_ms(self.h, C.byref(ms)), "pdmpc_fca_kernel_ms")
         return ms.value
 
+    def upload_hdv_map(self, hmap, local_sets):
+        """pdmpc_upload_hdv_map: the map (hdv.HdvMap) and the HDV automaton's local sets for hdv_traffic."""
+        from . import hdv
+
+        hdv.upload_hdv_map(self, hmap, local_sets)
+
+    def hdv_traffic(self, hdv_x, hdv_y, hdv_yaw, hdv_trim, hdv_tile, cav_x, cav_y, cav_lanelet, cav_tile, capacity=None, call_ms=None):
+        """pdmpc_hdv_traffic on this handle's device; see hdv.hdv_traffic_native."""
+        from . import hdv
+
+        return hdv.hdv_traffic_native(None, None, hdv_x, hdv_y, hdv_yaw, hdv_trim, hdv_tile, cav_x, cav_y, cav_lanelet, cav_tile, handle=self, capacity=capacity,
+                                      call_ms=call_ms)
+
+    def hdv_kernel_ms(self):
+        """kernel time (ms) of the last hdv_traffic"""
+        from . import hdv
+
+        return hdv.hdv_kernel_ms(self)
+
     def reachable_set_coupling_kernel_ms(self):
         ms = C.c_double(0.0)
         _check(self.L, self.L.pdmpc_reachable_set_coupling_kernel_ms(self.h, C.byref(ms)), "pdmpc_reachable_set_coupling_kernel_ms")

@@ -34,6 +34,8 @@ def centralized_mpa(options: Config):
 
 
 class CentralizedController(PrioritizedSequentialController):
+    hdvs_supported = False  # set_hdvs refuses: the joint kernel does not check HDV sets
+
     def __init__(
         self,
         options: Config,

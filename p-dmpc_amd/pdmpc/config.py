@@ -62,6 +62,9 @@ class Config:
     # the sampled optimizer's seed ensemble (no reference counterpart; pdmpc_set_sampled_ensemble): members per vehicle, 1 .. 16
     # (PDMPC_SAMPLED_ENSEMBLE_MAX); 1 plans as the reference does
     n_members: int = 1
+    # manual_control_config.amount (Config.m; HighLevelController.m:400): human-driven vehicles the controller does not control but plans
+    # around (PrioritizedSequentialController.set_hdvs); 0: none, and nothing changes
+    manual_control: int = 0
     # backend sizing (no reference counterpart)
     device: int = 0
     max_nodes: int = 0

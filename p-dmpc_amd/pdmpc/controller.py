@@ -76,6 +76,8 @@ class Measurement:  # plant PlantMeasurement
 
 
 class PrioritizedSequentialController:
+    hdvs_supported = True  # (the centralized controller's joint search has no HDV check)
+
     def __init__(
         self,
         options: Config,
@@ -109,6 +111,46 @@ class PrioritizedSequentialController:
         self.infos: List[Optional[ControlResultsInfo]] = [None] * self.n
         self.last_iters: List[Optional[VehicleIter]] = [None] * self.n
         self.last_levels = None
+        self.hdvs = None  # set_hdvs
+        self.hdv_info = None  # the traffic info of the last built step (hdv.hdv_traffic's dict)
+
+    # ---- human-driven vehicles (HighLevelController.update_hdv_traffic_info, HighLevelController.m:394-447)
+    def set_hdvs(self, hdv_local_sets, hmap, tile=None, traffic=None):
+        """options.manual_control HDVs from now on: hdv_local_sets = the local reachable sets of THEIR automaton ([trim][k] hulls; the
+        reference: single_speed without the recursive-feasibility mask), hmap = the map (hdv.HdvMap), tile[h] = the (dx, dy) of the
+        map copy HDV h drives on (default: none moved).  traffic: the call that computes the step's traffic info with the arguments
+        after the sets of hdv.hdv_traffic (default: the numpy twin; `handle.hdv_traffic` after handle.upload_hdv_map runs it on the
+        device, lambda *a: hdv.hdv_traffic_native(hmap, sets, *a) on the host twin -- all three give the same bits)."""
+        n_hdv = int(self.options.manual_control)
+        if n_hdv < 1:
+            raise ValueError("set_hdvs needs options.manual_control >= 1")
+        if any(getattr(v, "lanelets_index", None) is None for v in self.scenario.vehicles):
+            raise ValueError("HDVs need a scenario with lanelets")
+        if not self.options.are_any_obstacles_non_convex:  # OptimizerInterface.set_constraint_checker: the separating-axis checker
+            raise ValueError("HDV sets are checked by the InterX checker only")
+        if not self.hdvs_supported:
+            raise ValueError("this controller's searches have no check against HDV sets")
+        from . import hdv as _hdv
+
+        self.hdvs = dict(sets=hdv_local_sets, map=hmap, tile=[(0.0, 0.0)] * n_hdv if tile is None else [tuple(t) for t in tile],
+                         traffic=traffic if traffic is not None else (lambda *a: _hdv.hdv_traffic(hmap, hdv_local_sets, *a)), meas=None)
+
+    def set_hdv_measurements(self, x, y, yaw):
+        """The HDVs' measured poses (Plant.measure; CpmLab.measure returns them, Simulation.measure none): kept until set again."""
+        n_hdv = int(self.options.manual_control)
+        if self.hdvs is None or not (len(x) == len(y) == len(yaw) == n_hdv):
+            raise ValueError("set_hdv_measurements: %d poses after set_hdvs" % n_hdv)
+        self.hdvs["meas"] = ([float(v) for v in x], [float(v) for v in y], [float(v) for v in yaw])
+
+    def _hdv_traffic_info(self):
+        """ONE traffic call per step: trim 1 for every HDV (ManualVehicle.m:33), the CAVs' own measurements and current lanelets."""
+        h = self.hdvs
+        if h["meas"] is None:
+            raise ValueError("set_hdv_measurements before the first step with HDVs")
+        x, y, yaw = h["meas"]
+        tiles = getattr(self.scenario, "tile_offset", [(0.0, 0.0)] * self.n)
+        self.hdv_info = h["traffic"](x, y, yaw, [1] * len(x), h["tile"], [float(v) for v in self.x0[:, 0]], [float(v) for v in self.x0[:, 1]],
+                                     [int(c) for c in self.current_lanelet], [tuple(float(c) for c in t) for t in tiles])
 
     # ---- HighLevelController.update_controlled_vehicles_traffic_info (HighLevelController.m:167-270)
     def _traffic_info(self):
@@ -120,6 +162,7 @@ class PrioritizedSequentialController:
         self.ref_points = [None] * n
         self.v_ref = [None] * n
         self.boundary = [(None, None)] * n
+        self.current_lanelet = [0] * n
         for i, m in enumerate(self.meas):
             veh = self.scenario.vehicles[i]
             self.x0[i] = [m.x, m.y, m.yaw, m.speed]
@@ -132,6 +175,12 @@ class PrioritizedSequentialController:
             self.v_ref[i] = v_ref
             if o.scenario_type != ScenarioType.circle and self.boundary_provider is not None:
                 self.boundary[i] = self.boundary_provider(i, veh, points_index, cpi)
+            if self.hdvs is not None:  # get_predicted_lanelets.m:44,61: the lanelet the vehicle is on
+                from .road_network import get_predicted_lanelets
+
+                self.current_lanelet[i] = get_predicted_lanelets(veh.reference_path.shape[0], veh.points_index, veh.lanelets_index, points_index, cpi)[1]
+        if self.hdvs is not None:
+            self._hdv_traffic_info()
         # HighLevelController.m:219-263: the Hp reachable sets at the vehicle's pose, closed; only when a feature reads them.  With
         # Config.bound_reachable_sets they are bounded by the predicted lanelets on road networks (:241-246).
         self.reachable_sets = [None] * n
@@ -202,7 +251,13 @@ class PrioritizedSequentialController:
                 if old is not None:  # :542-557 (message of the previous step, shifted once)
                     dyn.append(del_first_rpt_last(old.shapes, 1))
         scen_dyn = [list(r) for r in self.scenario.dynamic_obstacle_area]
+        hdv_rows = []
+        if self.hdvs is not None:  # the rows of the HDVs adjacent to i, in row order (vectorize_all_obstacles.m:33-62, IterationData.filter :113)
+            from .hdv import cav_rows
+
+            hdv_rows = cav_rows(self.hdv_info, i)
         return VehicleIter(
+            hdv_reachable_sets=hdv_rows,
             x0=self.x0[i].copy(),
             trim_index=int(self.trims[i]),
             reference_trajectory_points=self.ref_points[i],

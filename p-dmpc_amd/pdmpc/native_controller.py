@@ -58,6 +58,7 @@ def _decode_iters(Hp, n, vin):
     for s in range(n):
         v = vin[s]
         dyn = _polys(v.dynamic_obstacles)
+        hdv_sets = _polys(v.hdv_reachable_sets)
         left = np.array([[v.left_x[q] for q in range(v.n_left)], [v.left_y[q] for q in range(v.n_left)]]) if v.n_left else None
         right = np.array([[v.right_x[q] for q in range(v.n_right)], [v.right_y[q] for q in range(v.n_right)]]) if v.n_right else None
         iters.append(VehicleIter(
@@ -65,6 +66,7 @@ def _decode_iters(Hp, n, vin):
             reference_trajectory_points=np.array([[v.ref_x[q], v.ref_y[q]] for q in range(Hp)]), v_ref=np.array([v.v_ref[q] for q in range(Hp)]),
             predicted_lanelet_boundary=(left, right), obstacles=_polys(v.obstacles),
             dynamic_obstacle_area=[dyn[r * Hp : (r + 1) * Hp] for r in range(len(dyn) // Hp)],
+            hdv_reachable_sets=[hdv_sets[r * Hp : (r + 1) * Hp] for r in range(len(hdv_sets) // Hp)],
         ))
     return iters
 
@@ -158,6 +160,45 @@ class NativeController:
 
     def _check(self, rc, what):
         _check(self.L, rc, what, "pdmpc_controller_last_error")
+
+    # ---- human-driven vehicles: twin of PrioritizedSequentialController.set_hdvs / set_hdv_measurements / hdv_info
+    def set_hdvs(self, hdv_mpa, successors, relationship, tile=None):
+        """pdmpc_controller_set_hdvs: options.manual_control HDVs on the scenario's lanelets with the lanelet graph given here
+        (successors: per lanelet its successor ids; relationship: (n, n) uint8), hdv_mpa their own automaton, tile[h] = (dx, dy)."""
+        n_hdv = int(self.options.manual_control)
+        so = np.zeros(len(successors) + 1, dtype=np.int32)
+        so[1:] = np.cumsum([len(s) for s in successors])
+        si = np.array([int(s) for row in successors for s in row] + [0], dtype=np.int32)
+        rel = np.ascontiguousarray(relationship, dtype=np.uint8)
+        ms, keep = abi.pack_mpa(hdv_mpa)
+        t = np.zeros((max(n_hdv, 1), 2)) if tile is None else np.ascontiguousarray(tile, dtype=np.float64).reshape(-1, 2)
+        tx, ty = np.ascontiguousarray(t[:, 0]), np.ascontiguousarray(t[:, 1])
+        rc = self.L.pdmpc_controller_set_hdvs(self.c, n_hdv, C.byref(ms), abi.i32p(so), abi.i32p(si), abi.u8p(rel), abi.dp(tx), abi.dp(ty))
+        del keep
+        self._check(rc, "pdmpc_controller_set_hdvs")
+
+    def set_hdv_measurements(self, x, y, yaw):
+        """pdmpc_controller_set_hdv_measurements: the HDVs' measured poses, kept until set again."""
+        n_hdv = int(self.options.manual_control)
+        a = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (x, y, yaw)]
+        if any(v.size != n_hdv for v in a):
+            raise ValueError("set_hdv_measurements: %d poses" % n_hdv)
+        self._check(self.L.pdmpc_controller_set_hdv_measurements(self.c, abi.dp(a[0]), abi.dp(a[1]), abi.dp(a[2])), "pdmpc_controller_set_hdv_measurements")
+
+    def hdv_info(self):
+        """pdmpc_controller_hdv_info: the traffic info of the last built step in the dict form of hdv.hdv_traffic."""
+        n, rows = C.c_int32(), C.c_int32()
+        co, ci, rh, so = (abi.c_int32_p() for _ in range(4))
+        sx, sy = abi.c_double_p(), abi.c_double_p()
+        fl, adj = abi.c_uint8_p(), abi.c_uint8_p()
+        self._check(self.L.pdmpc_controller_hdv_info(self.c, C.byref(n), C.byref(co), C.byref(ci), C.byref(rows), C.byref(rh), C.byref(so), C.byref(sx), C.byref(sy), C.byref(fl),
+                                                      C.byref(adj)), "pdmpc_controller_hdv_info")
+        H, R, Hp = n.value, rows.value, self.Hp
+        sets = [[np.array([[sx[q] for q in range(so[r * Hp + k], so[r * Hp + k + 1])], [sy[q] for q in range(so[r * Hp + k], so[r * Hp + k + 1])]]).reshape(2, -1)
+                 for k in range(Hp)] for r in range(R)]
+        return dict(closest=[[int(ci[q]) for q in range(co[h], co[h + 1])] for h in range(H)], row_hdv=[int(rh[r]) for r in range(R)], sets=sets,
+                    flags=np.array([fl[q] for q in range(R * Hp)], dtype=np.uint8).reshape(R, Hp),
+                    adjacency=np.array([adj[q] for q in range(self.n * H)], dtype=np.uint8).reshape(self.n, H))
 
     def close(self):
         if self.c:

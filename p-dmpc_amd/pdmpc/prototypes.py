@@ -25,6 +25,8 @@ BOUND = POSES + [POLYS, I32, I32, IP, DP, DP, BP]  # ..., lanelet_polygons, all_
 FCA = [I32, I32, DP, DP, DP, DP, I32, IP, POLYS, POLYS, F64, F64, F64, IP, IP]
 FCA_GROUPED = [I32, P(abi.FcaGroup), I32, DP, DP, DP, DP, IP, IP]
 CHOSEN = [CHOICE, IP, DP]  # choice, chosen, cell_cost
+HDV_MAP = [I32, IP, IP, DP, DP, DP, DP, IP, IP, BP] + TABLE  # n_lanelets, left/right offsets, left/right x y, successors, relationship, local sets
+HDV_CALL = [I32, DP, DP, DP, DP, IP, DP, DP, I32, DP, DP, IP, DP, DP, IP, IP, I32, IP, IP, IP, DP, DP, BP, BP]
 UNIQUE = [I32, BP, I64, P(I64), UP, IP]
 UNIQUE_GROUPED = [I32, IP, P(BP), P(I64), P(I64), UP, IP]  # n_groups, group_n, adjacency, max_out, n_out, masks, priorities
 
@@ -128,10 +130,19 @@ PROTOTYPES = {
     "pdmpc_fca_kernel_ms": (INT, [OBJ, DP]),
     "pdmpc_fca_collisions_grouped": (INT, [OBJ] + FCA_GROUPED),
     "pdmpc_fca_collisions_grouped_host": (INT, FCA_GROUPED),
+    # ---- human-driven vehicles
+    "pdmpc_upload_hdv_map": (INT, [OBJ] + HDV_MAP),
+    "pdmpc_hdv_traffic": (INT, [OBJ] + HDV_CALL),
+    "pdmpc_hdv_traffic_host": (INT, HDV_MAP + HDV_CALL),
+    "pdmpc_hdv_lanelet_distances_host": (INT, [I32, IP, IP, DP, DP, DP, DP, F64, F64, DP]),
+    "pdmpc_hdv_kernel_ms": (INT, [OBJ, DP]),
     # ---- the caller's side of the boundary, natively
     "pdmpc_controller_create": (INT, [OBJ, P(abi.ControllerConfig), P(abi.ScenarioStruct), P(OBJ)]),
     "pdmpc_controller_destroy": (INT, [OBJ]),
     "pdmpc_controller_step": (INT, [OBJ]),
+    "pdmpc_controller_set_hdvs": (INT, [OBJ, I32, MPA, IP, IP, BP, DP, DP]),
+    "pdmpc_controller_set_hdv_measurements": (INT, [OBJ, DP, DP, DP]),
+    "pdmpc_controller_hdv_info": (INT, [OBJ, IP, P(IP), P(IP), IP, P(IP), P(IP), P(DP), P(DP), P(BP), P(BP)]),
     "pdmpc_controller_run": (INT, [OBJ, I32, DP]),
     "pdmpc_controller_build_step": (INT, [OBJ]),
     "pdmpc_controller_apply": (INT, [OBJ, VOUT]),

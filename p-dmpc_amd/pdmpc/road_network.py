@@ -93,6 +93,56 @@ class LabMap:
         return b in self.succ[a - 1] or a in self.succ[b - 1]
 
 
+# LaneletRelationshipType.m:5-10 (0: no relationship, an empty cell of lanelet_relationships)
+RELATIONSHIP_NONE, RELATIONSHIP_LONGITUDINAL, RELATIONSHIP_SIDE, RELATIONSHIP_MERGING, RELATIONSHIP_FORKING, RELATIONSHIP_CROSSING = range(6)
+
+
+def lanelet_relationship_types(m: LabMap) -> np.ndarray:
+    """RoadDataCommonRoad.get_lanelet_relationships (RoadDataCommonRoad.m:66-245) as a table of types: (n, n) uint8, filled at
+    (i, j), i < j (0-based ids - 1), in the branch order of :101-225 from the map's pred / succ / adj alone.  Two parts are left out:
+    crossing (:226-241, which is_hdv_behind never reads) and the spreading of merging / forking to the adjacent lanes (:167-182,
+    :199-214), which needs intersection_lanelets, and the fixture does not hold them."""
+    n = m.n
+
+    def same_side(i, side):  # the adjacent lanelet in the same direction, as a list (get_all_adjacent_lanelets, :811-873)
+        lid, same = m.adj[i - 1, side]
+        return [int(lid)] if lid and same else []
+
+    def around(i):
+        pred = [int(p) for p in m.pred[i - 1] if p]
+        succ = [int(q) for q in m.succ[i - 1] if q]
+        return dict(left=same_side(i, 0), right=same_side(i, 1), pred=pred, succ=succ,
+                    pred_left=[a for p in pred for a in same_side(p, 0)], pred_right=[a for p in pred for a in same_side(p, 1)],
+                    succ_left=[a for q in succ for a in same_side(q, 0)], succ_right=[a for q in succ for a in same_side(q, 1)])
+
+    def meet(a, b):
+        return any(v in b for v in a)
+
+    info = [None] + [around(i) for i in range(1, n + 1)]
+    table = np.zeros((n, n), dtype=np.uint8)
+    for i in range(1, n):
+        I = info[i]
+        for j in range(i + 1, n + 1):
+            J = info[j]
+            if (j in I["pred"] or i in J["pred"] or meet(I["left"], J["pred"]) or meet(I["right"], J["pred"]) or meet(I["left"], J["succ"])
+                    or meet(I["right"], J["succ"]) or j in I["pred_left"] or j in I["succ_left"] or j in I["pred_right"] or j in I["succ_right"]):
+                t = RELATIONSHIP_LONGITUDINAL  # :101-140
+            elif j in I["left"] or j in I["right"] or (I["left"] and I["left"] == J["right"]) or (I["right"] and I["right"] == J["left"]):
+                t = RELATIONSHIP_SIDE  # :141-160
+            elif meet(I["succ"], J["succ"]):
+                t = RELATIONSHIP_MERGING  # :161-165
+            elif (meet(J["succ"], I["succ_left"]) or meet(J["succ"], I["succ_right"])) and not meet(I["pred"], J["pred"]):
+                t = RELATIONSHIP_MERGING  # :184-193
+            elif meet(I["pred"], J["pred"]):
+                t = RELATIONSHIP_FORKING  # :194-198
+            elif (meet(J["pred"], I["pred_left"]) or meet(J["pred"], I["pred_right"])) and not meet(I["succ"], J["succ"]):
+                t = RELATIONSHIP_FORKING  # :216-225
+            else:
+                t = RELATIONSHIP_NONE
+            table[i - 1, j - 1] = t
+    return table
+
+
 _MAP = None
 
 
