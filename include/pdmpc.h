@@ -744,8 +744,57 @@ int pdmpc_hdv_traffic_host(int32_t n_lanelets, const int32_t* left_offset, const
                            double* set_y, uint8_t* set_flags, uint8_t* adjacency);
 int pdmpc_hdv_lanelet_distances_host(int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x, const double* left_y,
                                      const double* right_x, const double* right_y, double px, double py, double* distance);
-/* kernel time (HIP events, ms) of the last pdmpc_hdv_traffic: its four launches */
+/* kernel time (HIP events, ms) of the last pdmpc_hdv_traffic (its four launches) or pdmpc_hdv_traffic_grouped (its five), whichever
+ * was called last */
 int pdmpc_hdv_kernel_ms(pdmpc_handle* handle, double* ms);
+
+/* Several maps on a handle, and several independent sets of HDVs and CAVs in one call.
+ * A handle has PDMPC_HDV_MAP_SLOTS map slots, each with its own map and HDV automaton hulls.  pdmpc_upload_hdv_map_slot fills one
+ * (pdmpc_upload_hdv_map is slot 0, which pdmpc_hdv_traffic reads); PDMPC_ERR_INVALID for a slot out of range.  Every successful upload
+ * gives its slot a new generation number, larger than any before it (0: never uploaded; a failed upload leaves the slot empty with
+ * generation 0); pdmpc_hdv_map_slot_state reports it, the uploads into all slots of the handle so far, and the Hp of the hulls the slot holds
+ * (0: empty; any of the three may be NULL).
+ * pdmpc_hdv_map_slot_holds: *holds = 1 if the slot holds exactly this map and these hulls -- the arguments compared byte for byte with
+ * the handle's host copy of what was uploaded, no hash --, else 0.  pdmpc_hdv_check_map_host: the checks of an upload alone (host only; pdmpc_last_error has the reason of a refusal).
+ *
+ * pdmpc_hdv_traffic_grouped: group g has the HDVs hdv_offset[g] .. hdv_offset[g + 1] - 1 and the CAVs cav_offset[g] .. of the call's
+ * arrays (offsets [n_groups + 1], from 0, non-decreasing) and drives on the map of slot group_slot[g].  Its slices of the outputs hold
+ * byte for byte what pdmpc_hdv_traffic returns for the group alone on a handle whose slot 0 holds that map: HDV indices (row_hdv) and
+ * vertex offsets (set_offset, from 0) are the group's own, nothing is computed across groups, a CAV meets the HDVs of its group only.
+ * With h0 = hdv_offset[g] the group's blocks start at: closest_offset (n_g + 1 entries) h0 + g; closest_index and row_hdv
+ * h0 * PDMPC_HDV_MAX_CHAINS; set_offset (n_rows[g] * Hp + 1 entries) h0 * PDMPC_HDV_MAX_CHAINS * Hp + g; set_flags
+ * h0 * PDMPC_HDV_MAX_CHAINS * Hp; set_x / set_y set_base[g] (set_base[n_groups]: all vertices); adjacency (n_cav_g x n_hdv_g) the sum
+ * of n_cav_h * n_hdv_h over h < g.  pdmpc_hdv_grouped_layout_host (host only) is the one statement of these starts: arrays of
+ * n_groups + 1 entries, the last the room the array needs; any may be NULL.  Groups without HDVs or CAVs (they write what has a size:
+ * an offset entry 0, n_rows[g] = 0), n_groups = 0, several groups on one slot and any slot order are fine.
+ * capacity is the room for the vertices of all groups together: too small is PDMPC_ERR_CAPACITY with every list, row, offset, set_base
+ * entry and adjacency byte written (the totals size a second call), and no more than the room for capacity vertices is copied back.
+ * PDMPC_ERR_INVALID: n_groups < 0, decreasing offsets, a slot out of range or never uploaded, slots in use whose Hp differ, a null array
+ * that is needed, a trim or lanelet id out of range for the group's map (pdmpc_last_error names the group).  PDMPC_ERR_CAPACITY: more than
+ * PDMPC_HDV_MAX_VEHICLES (64) HDVs or PDMPC_HDV_MAX_CAVS (2^20) CAVs in a group, more than PDMPC_HDV_GROUPED_MAX_VEHICLES in the call (the slots of the lane pass are
+ * 256 KB x Hp per HDV: 512 MB at the limit and Hp 16; they are grown to what a call needs), 2^31 or more (CAV, HDV) pairs; an HDV whose
+ * lists run over makes n_rows[g] = -1 for its group, whose other blocks then hold nothing, while the other groups' results are written.
+ * One staging copy, FIVE launches whatever n_groups is (closest, lane, scan, copy, adjacency), one copy back, one synchronisation.
+ * There is no grouped host twin: a reference is pdmpc_hdv_traffic_host called for every group. */
+#define PDMPC_HDV_MAP_SLOTS 8
+#define PDMPC_HDV_GROUPED_MAX_VEHICLES 128
+int pdmpc_upload_hdv_map_slot(pdmpc_handle* handle, int32_t slot, int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x,
+                              const double* left_y, const double* right_x, const double* right_y, const int32_t* succ_offset, const int32_t* succ_index,
+                              const uint8_t* relationship, int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* hdv_local_sets);
+int pdmpc_hdv_map_slot_state(pdmpc_handle* handle, int32_t slot, int64_t* generation, int64_t* uploads, int32_t* Hp);
+int pdmpc_hdv_map_slot_holds(pdmpc_handle* handle, int32_t slot, int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x,
+                             const double* left_y, const double* right_x, const double* right_y, const int32_t* succ_offset, const int32_t* succ_index,
+                             const uint8_t* relationship, int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* hdv_local_sets, int32_t* holds);
+int pdmpc_hdv_check_map_host(int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x, const double* left_y,
+                             const double* right_x, const double* right_y, const int32_t* succ_offset, const int32_t* succ_index, const uint8_t* relationship,
+                             int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* hdv_local_sets);
+int pdmpc_hdv_grouped_layout_host(int32_t n_groups, const int32_t* hdv_offset, const int32_t* cav_offset, int32_t Hp, int32_t* closest_at, int32_t* list_at,
+                                  int32_t* set_offset_at, int32_t* set_at, int64_t* adjacency_at);
+int pdmpc_hdv_traffic_grouped(pdmpc_handle* handle, int32_t n_groups, const int32_t* group_slot, const int32_t* hdv_offset, const int32_t* cav_offset, const double* x,
+                              const double* y, const double* cos_yaw, const double* sin_yaw, const int32_t* trim, const double* tile_dx, const double* tile_dy,
+                              const double* cav_x, const double* cav_y, const int32_t* cav_lanelet, const double* cav_tile_dx, const double* cav_tile_dy,
+                              int32_t* closest_offset, int32_t* closest_index, int32_t capacity, int32_t* n_rows, int32_t* row_hdv, int32_t* set_offset,
+                              int32_t* set_base, double* set_x, double* set_y, uint8_t* set_flags, uint8_t* adjacency);
 
 /* ---- the caller's side of the boundary, natively (csrc/step_controller.cpp and its stages csrc/step_*.hpp) ----
  * One MPC time step of the prioritized sequential controller around pdmpc_plan_step, without any interpreter in the loop:
@@ -814,8 +863,10 @@ int pdmpc_controller_step(pdmpc_controller* c);
  * (succ_offset / succ_index / relationship as for pdmpc_upload_hdv_map), hdv_mpa their own automaton (the reference: single_speed
  * without the recursive-feasibility mask; its Hp the controller's), tile_dx / tile_dy [n_hdv] (or NULL: 0) the map copy each drives on.
  * set_hdv_measurements: their measured poses [n_hdv], kept until set again.  Every built step (build_step, explore_build,
- * optimal_build, and so every *_step and *_run, alone or as a member of a sweep) then makes ONE pdmpc_hdv_traffic call on the handle
- * (a group's rank 0), the host twin without a handle, with trim 1 for every HDV and the CAVs' measured positions and current lanelets,
+ * optimal_build, and so every *_step and *_run) then takes part in ONE pdmpc_hdv_traffic_grouped call on the handle (a group's rank 0)
+ * -- a group of its own in it; the members of a sweep are the groups of one call, pdmpc_sweep_last_hdv_calls; its map stays in the
+ * map slot of the handle it was found in or uploaded to --, the host twin without a handle, with trim 1 for every HDV and the CAVs'
+ * measured positions and current lanelets,
  * and every search receives the rows of the HDVs adjacent to its vehicle, the same in every prioritization; the call's time counts into
  * ms6[0].  hdv_info: lists, rows, sets and adjacency of the last built step (pointers into the controller, valid until the next build;
  * any may be NULL).  PDMPC_ERR_INVALID: a scenario without lanelets, a handle with the separating-axis checker (the HDV soup is
@@ -973,6 +1024,11 @@ int pdmpc_sweep_last_timing(pdmpc_sweep* s, double* ms6);
  * host twins for a sweep without a handle (where lanelet bounding is one call per member and the hull coupler one per table of local
  * hulls).  A bounding call that is repeated with more room counts once. */
 int pdmpc_sweep_last_prep_calls(pdmpc_sweep* s, int32_t* calls4);
+/* ... and its HDV traffic stage: calls2[0] the traffic calls -- with a handle ONE pdmpc_hdv_traffic_grouped for all members with HDVs
+ * (a further one for every PDMPC_HDV_MAP_SLOTS distinct maps or PDMPC_HDV_GROUPED_MAX_VEHICLES HDVs beyond the first), without a handle
+ * one call of the host twin per such member --, calls2[1] the map uploads it made: members whose maps and hulls are equal byte for byte
+ * share a map slot of the handle, and a map that is still resident is not uploaded again.  A call repeated with more room counts once. */
+int pdmpc_sweep_last_hdv_calls(pdmpc_sweep* s, int32_t* calls2);
 /* The explorative step of a sweep: every member's explorative batch of n_perm prioritizations (seed = its time step),
  * the step preparation grouped as for pdmpc_sweep_build, the members' flattened batches one after the other (predecessor slots shifted by
  * the member's first slot), ONE pdmpc_plan_step_chosen with the members' choice descriptions concatenated -- one launch of the searches,

@@ -270,14 +270,23 @@ struct FcaState {
     TimedLaunch timed;
 };
 
-// pdmpc_upload_hdv_map / pdmpc_hdv_traffic (hdv_kernel.hip): the map and the HDV automaton's local hulls in one device
-// table (hdv_table in step_prep.cpp), the call's workspace with its pinned staging (hdv_layout) and the slots of the lane pass; the
-// workspace and the slots are grown when a call needs more, kept otherwise
+// pdmpc_upload_hdv_map(_slot) / pdmpc_hdv_traffic(_grouped) (hdv_kernel.hip): a map and the HDV automaton's local hulls
+// in one device table (hdv_table in step_prep.cpp), the call's workspace with its pinned staging (hdv_layout, hdv_grouped_ws) and the
+// slots of the lane pass; the workspace and the slots are grown when a call needs more, kept otherwise
+// A handle has PDMPC_HDV_MAP_SLOTS map slots (pdmpc_upload_hdv_map_slot), each with its own table and the host's copy of it;
+// pdmpc_hdv_traffic reads slot 0, a group of pdmpc_hdv_traffic_grouped the slot it names, through `maps`: one HdvMapRecord per slot
+// on the device, written at the upload.
+struct HdvMapSlot {
+    bool valid = false;      // an upload succeeded
+    int64_t generation = 0;  // of that upload (0: none): larger than any generation before it
+    HdvSlotData data;        // the host's copy: sizes, limits, the offsets of the table; what pdmpc_hdv_map_slot_holds compares with
+    DevBuf<unsigned char> table;
+};
 struct HdvState {
-    bool valid = false;  // an upload succeeded
-    HdvMapData map;      // the host's copy: sizes, limits and the offsets of the table
-    int trims = 0, Hp = 0, local_tot = 0;
-    DevBuf<unsigned char> table, ws;
+    HdvMapSlot map[PDMPC_HDV_MAP_SLOTS];
+    int64_t uploads = 0;   // successful uploads into any slot so far
+    DevBuf<HdvMapRecord> maps;
+    DevBuf<unsigned char> ws;
     DevBuf<double> slots;  // x of every slot, then y
     PinnedBuf<unsigned char> h_in, h_out;
     TimedLaunch timed;

@@ -3,10 +3,14 @@
 // the semantics of DESIGN.md §3.24).  Host code only.  Every decision and every vertex comes from the header functions the kernels
 // compile too (include/pdmpc_hdv.h, include/pdmpc_geometry.h), so both give the same bits.
 #include <cstring>
+#include <string>
 
+#include "hdv_grouped_host.hpp"
 #include "hdv_host.hpp"
 
 #include "../../include/pdmpc_geometry.h"
+
+extern "C" void pdmpc_set_last_error(const char* msg);  // api.cpp: the string pdmpc_last_error returns
 
 extern "C" {
 
@@ -19,6 +23,23 @@ int pdmpc_hdv_lanelet_distances_host(int32_t n_lanelets, const int32_t* left_off
     const pdmpc_hdv_map M = map.view();
     for (int i = 0; i < n_lanelets; ++i) distance[i] = pdmpc_hdv_lanelet_distance(&M, i, px, py);
     return PDMPC_OK;
+}
+
+int pdmpc_hdv_check_map_host(int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x, const double* left_y,
+                             const double* right_x, const double* right_y, const int32_t* succ_offset, const int32_t* succ_index, const uint8_t* relationship,
+                             int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* hdv_local_sets) {
+    HdvMapData map;
+    const char* why = nullptr;
+    int rc = map.points(n_lanelets, left_offset, right_offset, left_x, left_y, right_x, right_y, &why);
+    if (!rc) rc = map.graph(succ_offset, succ_index, relationship, &why);
+    if (!rc) rc = hdv_check_sets(n_trims, Hp, hdv_local_sets, &why);
+    if (rc) pdmpc_set_last_error((std::string("pdmpc_hdv_check_map_host: ") + why).c_str());  // (the reason, as an upload reports it)
+    return rc;
+}
+
+int pdmpc_hdv_grouped_layout_host(int32_t n_groups, const int32_t* hdv_offset, const int32_t* cav_offset, int32_t Hp, int32_t* closest_at, int32_t* list_at,
+                                  int32_t* set_offset_at, int32_t* set_at, int64_t* adjacency_at) {
+    return hdv_grouped_layout(n_groups, hdv_offset, cav_offset, Hp, closest_at, list_at, set_offset_at, set_at, adjacency_at);
 }
 
 int pdmpc_hdv_traffic_host(int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x, const double* left_y,

@@ -3,6 +3,7 @@
 // DESIGN.md §3.24.
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "../../include/pdmpc.h"
@@ -110,6 +111,50 @@ inline int hdv_check_sets(int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* 
     }
     return PDMPC_OK;
 }
+
+// The host's copy of what a map slot of a handle holds (pdmpc_upload_hdv_map_slot): the map, and the hulls with their offsets from 0
+// (x of every vertex, then y)
+struct HdvSlotData {
+    HdvMapData map;
+    int trims = 0, Hp = 0, local_tot = 0;
+    std::vector<int32_t> local_off;
+    std::vector<double> local_xy;
+
+    void keep_sets(int32_t n_trims, int32_t Hp_, const pdmpc_polygon_set* sets) {  // (after hdv_check_sets)
+        const int n_polygons = n_trims * Hp_, p0 = sets->offset[0];
+        trims = n_trims;
+        Hp = Hp_;
+        local_tot = sets->offset[n_polygons] - p0;
+        local_off.resize((size_t)n_polygons + 1);
+        for (int p = 0; p <= n_polygons; ++p) local_off[(size_t)p] = sets->offset[p] - p0;
+        local_xy.assign(sets->x + p0, sets->x + p0 + local_tot);
+        local_xy.insert(local_xy.end(), sets->y + p0, sets->y + p0 + local_tot);
+    }
+    // exactly this map and these hulls, as an upload takes them: every size, offset, point, successor, relationship and vertex compared
+    // with the copy, the doubles byte for byte (no hash: equal means equal)
+    bool holds(int32_t n, const int32_t* left_offset, const int32_t* right_offset, const double* left_x, const double* left_y, const double* right_x, const double* right_y,
+               const int32_t* succ_offset, const int32_t* succ_index, const uint8_t* relationship, int32_t n_trims, int32_t Hp_, const pdmpc_polygon_set* sets) const {
+        if (n != map.n_lanelets || n < 1 || !left_offset || !right_offset || !left_x || !left_y || !right_x || !right_y || !succ_offset || !relationship) return false;
+        if (n_trims != trims || Hp_ != Hp || !sets || !sets->offset || !sets->x || !sets->y || sets->n_polygons != n_trims * Hp_) return false;
+        const double *lx = map.pts.data(), *ly = lx + map.n_pts, *rx = ly + map.n_pts, *ry = rx + map.n_pts;
+        for (int i = 0; i < n; ++i) {
+            const int a = map.pt_off[(size_t)i], cnt = map.pt_off[(size_t)i + 1] - a;
+            if (left_offset[i + 1] - left_offset[i] != cnt || right_offset[i + 1] - right_offset[i] != cnt) return false;
+            const size_t bytes = (size_t)cnt * sizeof(double);
+            if (std::memcmp(lx + a, left_x + left_offset[i], bytes) || std::memcmp(ly + a, left_y + left_offset[i], bytes) ||
+                std::memcmp(rx + a, right_x + right_offset[i], bytes) || std::memcmp(ry + a, right_y + right_offset[i], bytes))
+                return false;
+        }
+        if (std::memcmp(map.succ_off.data(), succ_offset, ((size_t)n + 1) * sizeof(int32_t))) return false;
+        if (map.n_succ && (!succ_index || std::memcmp(map.succ_idx.data(), succ_index, (size_t)map.n_succ * sizeof(int32_t)))) return false;
+        if (std::memcmp(map.rel.data(), relationship, (size_t)n * n)) return false;
+        const int n_polygons = n_trims * Hp_, p0 = sets->offset[0];
+        for (int p = 0; p <= n_polygons; ++p)
+            if (sets->offset[p] - p0 != local_off[(size_t)p]) return false;
+        const size_t bytes = (size_t)local_tot * sizeof(double);
+        return !std::memcmp(local_xy.data(), sets->x + p0, bytes) && !std::memcmp(local_xy.data() + local_tot, sets->y + p0, bytes);
+    }
+};
 
 // the arguments of one traffic call against a map of n_lanelets lanelets and a table of n_trims trims
 inline int hdv_check_call(int32_t n_lanelets, int32_t n_trims, int32_t n_hdv, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw,

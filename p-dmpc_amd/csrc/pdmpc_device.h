@@ -558,6 +558,32 @@ struct HdvArgs {
     double* set_y;
     uint8_t* adjacency;         // [n_cav n_hdv]
 };
+// ... of several independent groups in one call (pdmpc_hdv_traffic_grouped; five launches).  The work arrays are HdvArgs' over the HDVs
+// and CAVs of all groups, group after group (a: n_hdv / n_cav the totals, map and local_* unused); an item finds its group through
+// group_of (an HDV's) or pair_first (a (CAV, HDV) pair's, searched) and its map in the handle's table of one record per map slot,
+// written at the upload.  The outputs keep the blocks of pdmpc_hdv_grouped_layout_host: group g's rows, offsets and HDV indices are
+// its own (from 0), its vertices start at set_base[g].
+#define PDMPC_HDV_SCAN_BLOCK 256      // lanes of the scan pass's one workgroup = slots of one of its tiles
+struct HdvMapRecord {
+    pdmpc_hdv_map map;
+    const double *local_x, *local_y;
+    const int32_t* local_off;
+};
+struct HdvGroup {
+    int32_t slot, h0, n_hdv, c0, n_cav;  // map slot; first HDV / CAV and their numbers
+};
+struct HdvGroupedArgs {
+    HdvArgs a;
+    const HdvMapRecord* maps;   // [PDMPC_HDV_MAP_SLOTS]
+    const HdvGroup* groups;     // [n_groups]
+    const int32_t* group_of;    // [n_hdv]
+    const int32_t* pair_first;  // [n_groups + 1] first (CAV, HDV) pair of every group; the last entry: all pairs
+    int32_t n_groups, n_pairs;  // n_pairs: the host's copy of pair_first[n_groups]
+    int32_t* slot_before;       // [slots] vertices of the group's slots in front (slots that exist)
+    int32_t* row_base;          // [n_hdv] rows of the group's HDVs in front
+    int32_t* n_rows;            // [n_groups] -1: an HDV of the group ran over its lists (the group writes nothing else)
+    int32_t* set_base;          // [n_groups + 1]
+};
 
 // The choice among the plans of a batch (choice_kernel.hip; pdmpc_choice in include/pdmpc.h) on the result records
 // where the search left them.  The lists are the caller's with the slots mapped to record slots and checked on the host (api.cpp:
@@ -602,6 +628,8 @@ int pdmpc_fca_check_groups(int32_t n_groups, const pdmpc_fca_group* groups, int3
                            const double* sin_yaw, const int32_t* collisions, const int32_t* priorities, int32_t* n_total, char* why, int32_t why_size);
 // hdv_kernel.hip: closest lanelets and chains, reachable lanes, packing and adjacency on the handle's stream (n_hdv > 0)
 int pdmpc_launch_hdv_traffic(const HdvArgs* args, void* stream);
+// ... of the groups of a grouped call: closest, lane, scan, copy and adjacency pass (a.n_hdv > 0)
+int pdmpc_launch_hdv_traffic_grouped(const HdvGroupedArgs* args, void* stream);
 // reachable_kernel.hip: the two passes of the reachable-set coupler on the handle's stream
 int pdmpc_launch_reachable_coupling(const ReachArgs* args, void* stream);
 int pdmpc_launch_reachable_coupling_grouped(const ReachArgs* args, void* stream);

@@ -16,12 +16,12 @@
 #include <cassert>
 #include <chrono>
 #include <cstdint>
-#include <map>
-#include <mutex>
+#include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/pdmpc.h"
+#include "hdv_grouped_host.hpp"  // the batches of the HDV traffic stage (host only)
 #include "step_types.hpp"  // the stages, in their order
 #include "step_inputs.hpp"
 #include "step_priorities.hpp"
@@ -302,59 +302,47 @@ int gather_fca(pdmpc_controller* const* members, PrepScratch::Fca& F, const std:
     return PDMPC_OK;
 }
 
-// ---- human-driven vehicles: the traffic-info stage of a member with HDVs, ONE pdmpc_hdv_traffic per step on the handle
-// (on a group: its rank 0, which h is), the host twin without one.  A handle holds one map: the controller whose map it holds is noted
-// here, and a member that finds another's there uploads its own first (members of a sweep share the handle).
-std::mutex g_hdv_mutex;
-std::map<pdmpc_handle*, const pdmpc_controller*> g_hdv_map_of;
-
-int hdv_upload(pdmpc_handle* h, pdmpc_controller* c) {
-    const HdvTraffic& H = c->hdv;
-    std::lock_guard<std::mutex> lock(g_hdv_mutex);
-    auto it = g_hdv_map_of.find(h);
-    if (it != g_hdv_map_of.end() && it->second == c) return PDMPC_OK;
-    const pdmpc_polygon_set local = view_polygons(H.local_off, H.local_x, H.local_y);
-    const int rc = pdmpc_upload_hdv_map(h, (int32_t)H.lan_off.size() - 1, H.lan_off.data(), H.lan_off.data(), H.left_x.data(), H.left_y.data(), H.right_x.data(), H.right_y.data(),
-                                        H.succ_off.data(), H.succ_idx.data(), H.rel.data(), H.n_trims, c->sc.Hp, &local);
-    if (rc) return cfail(c, rc, std::string("pdmpc_upload_hdv_map: ") + pdmpc_last_error());
-    g_hdv_map_of[h] = c;
-    return PDMPC_OK;
+// ---- human-driven vehicles: the traffic-info stage over all members.  With a handle (on a group: its rank 0, which h
+// is) the members with HDVs are the groups of ONE pdmpc_hdv_traffic_grouped (hdv_grouped_host.hpp: a further call per
+// PDMPC_HDV_MAP_SLOTS distinct maps or PDMPC_HDV_GROUPED_MAX_VEHICLES HDVs); members whose maps are equal share a map slot of the handle,
+// and a map that is still resident -- the slot's generation as the member noted it, or the handle's byte-for-byte check -- is not
+// uploaded again.  Without a handle every such member calls the host twin.
+template <class T>
+bool same_bytes(const std::vector<T>& a, const std::vector<T>& b) {
+    return a.size() == b.size() && (a.empty() || !std::memcmp(a.data(), b.data(), a.size() * sizeof(T)));
 }
-void hdv_forget(const pdmpc_controller* c) {  // (its map may stay on a handle: whoever calls next finds another owner and uploads)
-    std::lock_guard<std::mutex> lock(g_hdv_mutex);
-    for (auto it = g_hdv_map_of.begin(); it != g_hdv_map_of.end();) it = it->second == c ? g_hdv_map_of.erase(it) : std::next(it);
+bool same_hdv_map(const HdvTraffic& A, const HdvTraffic& B) {
+    return &A == &B || (A.n_trims == B.n_trims && same_bytes(A.lan_off, B.lan_off) && same_bytes(A.succ_off, B.succ_off) && same_bytes(A.succ_idx, B.succ_idx) &&
+                        same_bytes(A.rel, B.rel) && same_bytes(A.local_off, B.local_off) && same_bytes(A.left_x, B.left_x) && same_bytes(A.left_y, B.left_y) &&
+                        same_bytes(A.right_x, B.right_x) && same_bytes(A.right_y, B.right_y) && same_bytes(A.local_x, B.local_x) && same_bytes(A.local_y, B.local_y));
 }
-
-int hdv_traffic_stage(pdmpc_handle* h, pdmpc_controller* c) {
+// the room a member's results need (what its own traffic call would size)
+void hdv_size_results(pdmpc_controller* c) {
     HdvTraffic& H = c->hdv;
-    if (H.n == 0) return PDMPC_OK;
-    if (!H.measured) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_measurements before the first step with HDVs");
-    const int n = c->sc.n, Hp = c->sc.Hp;
     const size_t lists = (size_t)H.n * PDMPC_HDV_MAX_CHAINS;
     H.closest_off.assign((size_t)H.n + 1, 0);
     H.closest_idx.resize(lists);
     H.row_hdv.resize(lists);
-    H.set_off.assign(lists * Hp + 1, 0);
-    H.set_flags.resize(lists * Hp);
-    H.adjacency.assign((size_t)n * H.n, 0);
+    H.set_off.assign(lists * c->sc.Hp + 1, 0);
+    H.set_flags.resize(lists * c->sc.Hp);
+    H.adjacency.assign((size_t)c->sc.n * H.n, 0);
     if (H.set_x.size() < 4096) {
         H.set_x.resize(4096);
         H.set_y.resize(4096);
     }
-    if (h)
-        if (const int rc = hdv_upload(h, c)) return rc;
+}
+
+int hdv_traffic_on_host(pdmpc_controller* c) {
+    HdvTraffic& H = c->hdv;
+    const int n = c->sc.n, Hp = c->sc.Hp;
+    hdv_size_results(c);
     const pdmpc_polygon_set local = view_polygons(H.local_off, H.local_x, H.local_y);
     auto call = [&]() {
-        const int32_t cap = (int32_t)H.set_x.size();
-        if (h)
-            return pdmpc_hdv_traffic(h, H.n, H.x.data(), H.y.data(), H.cos_yaw.data(), H.sin_yaw.data(), H.trim.data(), H.tile_dx.data(), H.tile_dy.data(), n, c->tr.mx.data(),
-                                     c->tr.my.data(), c->in.current_lanelet.data(), H.cav_tile_dx.data(), H.cav_tile_dy.data(), H.closest_off.data(), H.closest_idx.data(), cap,
-                                     &H.n_rows, H.row_hdv.data(), H.set_off.data(), H.set_x.data(), H.set_y.data(), H.set_flags.data(), H.adjacency.data());
         return pdmpc_hdv_traffic_host((int32_t)H.lan_off.size() - 1, H.lan_off.data(), H.lan_off.data(), H.left_x.data(), H.left_y.data(), H.right_x.data(), H.right_y.data(),
                                       H.succ_off.data(), H.succ_idx.data(), H.rel.data(), H.n_trims, Hp, &local, H.n, H.x.data(), H.y.data(), H.cos_yaw.data(), H.sin_yaw.data(),
                                       H.trim.data(), H.tile_dx.data(), H.tile_dy.data(), n, c->tr.mx.data(), c->tr.my.data(), c->in.current_lanelet.data(), H.cav_tile_dx.data(),
-                                      H.cav_tile_dy.data(), H.closest_off.data(), H.closest_idx.data(), cap, &H.n_rows, H.row_hdv.data(), H.set_off.data(), H.set_x.data(),
-                                      H.set_y.data(), H.set_flags.data(), H.adjacency.data());
+                                      H.cav_tile_dy.data(), H.closest_off.data(), H.closest_idx.data(), (int32_t)H.set_x.size(), &H.n_rows, H.row_hdv.data(), H.set_off.data(),
+                                      H.set_x.data(), H.set_y.data(), H.set_flags.data(), H.adjacency.data());
     };
     int rc = call();
     if (rc == PDMPC_ERR_CAPACITY && H.n_rows >= 0 && (size_t)H.set_off[(size_t)H.n_rows * Hp] > H.set_x.size()) {  // (the offsets size the second call)
@@ -363,8 +351,147 @@ int hdv_traffic_stage(pdmpc_handle* h, pdmpc_controller* c) {
         H.set_y.resize(need + need / 4);
         rc = call();
     }
-    if (rc) return cfail(c, rc, h ? std::string("pdmpc_hdv_traffic: ") + pdmpc_last_error() : "pdmpc_hdv_traffic_host failed");
+    if (rc) return cfail(c, rc, "pdmpc_hdv_traffic_host failed");
     H.gather(n, Hp);
+    return PDMPC_OK;
+}
+
+// the members of batch B (their maps are in the slots B.slot) as the groups of one call, and every member's blocks back into its own
+// arrays, as its own call leaves them.  The capacity retry is here, once: the room is the last total and a quarter.
+int hdv_grouped_call(pdmpc_handle* h, pdmpc_controller* const* members, const HdvBatch& B, PrepScratch::Hdv& C) {
+    const int G = (int)B.members.size(), Hp = members[B.members[0]]->sc.Hp;
+    for (auto* v : {&C.slot, &C.trim, &C.cav_lanelet}) v->clear();
+    for (auto* v : {&C.x, &C.y, &C.cos_yaw, &C.sin_yaw, &C.tile_dx, &C.tile_dy, &C.cav_x, &C.cav_y, &C.cav_tile_dx, &C.cav_tile_dy}) v->clear();
+    C.hdv_offset.assign(1, 0);
+    C.cav_offset.assign(1, 0);
+    auto append = [](auto& to, const auto& from, size_t count) { to.insert(to.end(), from.begin(), from.begin() + (ptrdiff_t)count); };
+    for (int g = 0; g < G; ++g) {
+        pdmpc_controller* c = members[B.members[(size_t)g]];
+        const HdvTraffic& H = c->hdv;
+        const size_t nh = (size_t)H.n, nc = (size_t)c->sc.n;
+        C.slot.push_back(B.slot[(size_t)B.map_of[(size_t)g]]);
+        append(C.x, H.x, nh);
+        append(C.y, H.y, nh);
+        append(C.cos_yaw, H.cos_yaw, nh);
+        append(C.sin_yaw, H.sin_yaw, nh);
+        append(C.trim, H.trim, nh);
+        append(C.tile_dx, H.tile_dx, nh);
+        append(C.tile_dy, H.tile_dy, nh);
+        append(C.cav_x, c->tr.mx, nc);
+        append(C.cav_y, c->tr.my, nc);
+        append(C.cav_lanelet, c->in.current_lanelet, nc);
+        append(C.cav_tile_dx, H.cav_tile_dx, nc);
+        append(C.cav_tile_dy, H.cav_tile_dy, nc);
+        C.hdv_offset.push_back((int32_t)C.x.size());
+        C.cav_offset.push_back((int32_t)C.cav_x.size());
+    }
+    for (auto* v : {&C.closest_at, &C.list_at, &C.set_offset_at, &C.set_at}) v->assign((size_t)G + 1, 0);
+    C.adjacency_at.assign((size_t)G + 1, 0);
+    if (const int rc = pdmpc_hdv_grouped_layout_host(G, C.hdv_offset.data(), C.cav_offset.data(), Hp, C.closest_at.data(), C.list_at.data(), C.set_offset_at.data(), C.set_at.data(),
+                                                     C.adjacency_at.data()))
+        return cfail(nullptr, rc, "pdmpc_hdv_grouped_layout_host failed");
+    C.closest_off.assign((size_t)C.closest_at[(size_t)G], 0);
+    C.closest_idx.assign((size_t)C.list_at[(size_t)G] + 1, 0);
+    C.row_hdv.assign((size_t)C.list_at[(size_t)G] + 1, 0);
+    C.set_off.assign((size_t)C.set_offset_at[(size_t)G], 0);
+    C.set_flags.assign((size_t)C.set_at[(size_t)G] + 1, 0);
+    C.adjacency.assign((size_t)C.adjacency_at[(size_t)G] + 1, 0);
+    C.n_rows.assign((size_t)G, 0);
+    C.set_base.assign((size_t)G + 1, 0);
+    if (C.set_x.size() < 4096) {
+        C.set_x.resize(4096);
+        C.set_y.resize(4096);
+    }
+    auto call = [&]() {
+        return pdmpc_hdv_traffic_grouped(h, G, C.slot.data(), C.hdv_offset.data(), C.cav_offset.data(), C.x.data(), C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(), C.trim.data(),
+                                         C.tile_dx.data(), C.tile_dy.data(), C.cav_x.data(), C.cav_y.data(), C.cav_lanelet.data(), C.cav_tile_dx.data(), C.cav_tile_dy.data(),
+                                         C.closest_off.data(), C.closest_idx.data(), (int32_t)C.set_x.size(), C.n_rows.data(), C.row_hdv.data(), C.set_off.data(), C.set_base.data(),
+                                         C.set_x.data(), C.set_y.data(), C.set_flags.data(), C.adjacency.data());
+    };
+    int rc = call();
+    if (rc == PDMPC_ERR_CAPACITY && *std::min_element(C.n_rows.begin(), C.n_rows.end()) >= 0 && (size_t)C.set_base[(size_t)G] > C.set_x.size()) {  // (the totals size the second call)
+        const size_t need = (size_t)C.set_base[(size_t)G];
+        C.set_x.resize(need + need / 4);
+        C.set_y.resize(need + need / 4);
+        rc = call();
+    }
+    if (rc) return cfail(nullptr, rc, std::string("pdmpc_hdv_traffic_grouped: ") + pdmpc_last_error());
+    for (int g = 0; g < G; ++g) {
+        pdmpc_controller* c = members[B.members[(size_t)g]];
+        HdvTraffic& H = c->hdv;
+        hdv_size_results(c);
+        const size_t rows = (size_t)C.n_rows[(size_t)g], sets = rows * Hp, nh = (size_t)H.n;
+        const int32_t* so = C.set_off.data() + C.set_offset_at[(size_t)g];
+        const size_t total = (size_t)so[sets];
+        H.n_rows = (int32_t)rows;
+        std::copy_n(C.closest_off.begin() + C.closest_at[(size_t)g], nh + 1, H.closest_off.begin());
+        std::copy_n(C.closest_idx.begin() + C.list_at[(size_t)g], (size_t)H.closest_off[nh], H.closest_idx.begin());
+        std::copy_n(C.row_hdv.begin() + C.list_at[(size_t)g], rows, H.row_hdv.begin());
+        std::copy_n(so, sets + 1, H.set_off.begin());
+        std::copy_n(C.set_flags.begin() + C.set_at[(size_t)g], sets, H.set_flags.begin());
+        std::copy_n(C.adjacency.begin() + (ptrdiff_t)C.adjacency_at[(size_t)g], (size_t)c->sc.n * nh, H.adjacency.begin());
+        if (H.set_x.size() < total) {
+            H.set_x.resize(total + total / 4);
+            H.set_y.resize(total + total / 4);
+        }
+        std::copy_n(C.set_x.begin() + C.set_base[(size_t)g], total, H.set_x.begin());
+        std::copy_n(C.set_y.begin() + C.set_base[(size_t)g], total, H.set_y.begin());
+        H.gather(c->sc.n, Hp);
+    }
+    return PDMPC_OK;
+}
+
+int hdv_traffic_stage(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, PrepScratch& S) {
+    S.hdv_calls[0] = S.hdv_calls[1] = 0;
+    std::vector<int32_t> n_hdv(M, 0);
+    for (size_t m = 0; m < M; ++m) {
+        pdmpc_controller* c = members[m];
+        n_hdv[m] = c->hdv.n;
+        if (c->hdv.n && !c->hdv.measured) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_measurements before the first step with HDVs");
+        if (c->hdv.n && !h) {
+            S.hdv_calls[0] += 1;
+            if (const int rc = hdv_traffic_on_host(c)) return rc;
+        }
+    }
+    if (!h) return PDMPC_OK;
+    std::vector<HdvBatch> batches = hdv_split_batches((int)M, n_hdv.data(), [&](int a, int b) { return same_hdv_map(members[a]->hdv, members[b]->hdv); });
+    std::vector<HdvSlotNote> note(M);
+    int64_t generation[PDMPC_HDV_MAP_SLOTS];
+    auto read_generations = [&]() {
+        for (int s = 0; s < PDMPC_HDV_MAP_SLOTS; ++s)
+            if (const int rc = pdmpc_hdv_map_slot_state(h, s, &generation[s], nullptr, nullptr)) return cfail(nullptr, rc, pdmpc_last_error());
+        return (int)PDMPC_OK;
+    };
+    // a member's map as the handle's entry points take it
+    auto with_map = [&](int m, auto&& f) {
+        const HdvTraffic& H = members[m]->hdv;
+        const pdmpc_polygon_set local = view_polygons(H.local_off, H.local_x, H.local_y);
+        return f((int32_t)H.lan_off.size() - 1, H.lan_off.data(), H.lan_off.data(), H.left_x.data(), H.left_y.data(), H.right_x.data(), H.right_y.data(), H.succ_off.data(),
+                 H.succ_idx.data(), H.rel.data(), (int32_t)H.n_trims, (int32_t)members[m]->sc.Hp, &local);
+    };
+    for (HdvBatch& B : batches) {
+        if (const int rc = read_generations()) return rc;
+        for (int m : B.members) note[(size_t)m] = HdvSlotNote{members[m]->hdv.map_slot, members[m]->hdv.map_generation};
+        hdv_assign_slots(B, note.data(), generation, [&](int slot, int m) {
+            int32_t holds = 0;
+            (void)with_map(m, [&](auto... map) { return pdmpc_hdv_map_slot_holds(h, slot, map..., &holds); });
+            return holds != 0;
+        });
+        for (size_t d = 0; d < B.maps.size(); ++d) {
+            if (!B.upload[d]) continue;
+            S.hdv_calls[1] += 1;
+            if (const int rc = with_map(B.maps[d], [&](auto... map) { return pdmpc_upload_hdv_map_slot(h, B.slot[d], map...); }))
+                return cfail(members[B.maps[d]], rc, std::string("pdmpc_upload_hdv_map_slot: ") + pdmpc_last_error());
+        }
+        if (const int rc = read_generations()) return rc;
+        for (size_t i = 0; i < B.members.size(); ++i) {
+            HdvTraffic& H = members[B.members[i]]->hdv;
+            H.map_slot = B.slot[(size_t)B.map_of[i]];
+            H.map_generation = generation[H.map_slot];
+        }
+        S.hdv_calls[0] += 1;
+        if (const int rc = hdv_grouped_call(h, members, B, S.hdv)) return rc;
+    }
     return PDMPC_OK;
 }
 
@@ -390,8 +517,7 @@ int build_members(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, B
     S.prio.calls = 0;
     for (size_t m = 0; m < M; ++m)
         if (const int rc = begin_step(members[m], S.prep[m])) return rc;
-    for (size_t m = 0; m < M; ++m)  // (a member with HDVs makes its own traffic call; folding the members' calls into one is a follow-up)
-        if (const int rc = hdv_traffic_stage(h, members[m])) return rc;
+    if (const int rc = hdv_traffic_stage(h, members, M, S)) return rc;
     // who takes part in which grouped call: bounded (step Hp only / every step: one bounding call each) or the plain hulls
     std::vector<int> bounded_last, bounded_all, hulls;
     for (size_t m = 0; m < M; ++m) {
@@ -751,15 +877,13 @@ int pdmpc_controller_set_hdvs(pdmpc_controller* c, int32_t n_hdv, const pdmpc_mp
         H.cav_tile_dx.push_back(V.tile_dx);
         H.cav_tile_dy.push_back(V.tile_dy);
     }
-    hdv_forget(c);
-    if (c->h) {  // (the map's own refusals -- limits, successor ids -- come from the one place that checks them)
-        c->hdv = H;
-        if ((rc = hdv_upload(c->h, c))) {
-            c->hdv = HdvTraffic();
-            return rc;
-        }
-    } else
-        c->hdv = std::move(H);
+    if (c->h) {  // (the map's own refusals -- limits, successor ids -- come from the one place that checks them; the upload is the first step's)
+        const pdmpc_polygon_set local = view_polygons(H.local_off, H.local_x, H.local_y);
+        rc = pdmpc_hdv_check_map_host(n_lan, H.lan_off.data(), H.lan_off.data(), H.left_x.data(), H.left_y.data(), H.right_x.data(), H.right_y.data(), H.succ_off.data(),
+                                      H.succ_idx.data(), H.rel.data(), H.n_trims, c->sc.Hp, &local);
+        if (rc) return cfail(c, rc, std::string("pdmpc_controller_set_hdvs: ") + pdmpc_last_error());
+    }
+    c->hdv = std::move(H);  // (with no map slot noted: the next step looks for the map on the handle)
     return PDMPC_OK;
 }
 
@@ -799,7 +923,6 @@ int pdmpc_controller_hdv_info(pdmpc_controller* c, int32_t* n_hdv, const int32_t
 }
 
 int pdmpc_controller_destroy(pdmpc_controller* c) {
-    if (c) hdv_forget(c);
     delete c;
     return PDMPC_OK;
 }
@@ -1609,6 +1732,12 @@ int pdmpc_sweep_set_group(pdmpc_sweep* s, pdmpc_group* g, int32_t mode) {
 int pdmpc_sweep_last_timing(pdmpc_sweep* s, double* ms6) {
     if (!s || !ms6) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
     for (int i = 0; i < 6; ++i) ms6[i] = s->timing[i];
+    return PDMPC_OK;
+}
+
+int pdmpc_sweep_last_hdv_calls(pdmpc_sweep* s, int32_t* calls2) {
+    if (!s || !calls2) return cfail(nullptr, PDMPC_ERR_INVALID, "null argument");
+    std::copy(s->prep.hdv_calls, s->prep.hdv_calls + 2, calls2);
     return PDMPC_OK;
 }
 

@@ -4,7 +4,10 @@
 //
 // Every call but pdmpc_unique_priorities(_grouped) follows one recipe: carve ONE pinned staging block and ONE device workspace with the same
 // offsets (Carver), stage the inputs, copy them in once, launch between an event pair (timed_launch), copy the result back, synchronise.
+#include <atomic>
+
 #include "handle.hpp"
+#include "hdv_grouped_host.hpp"
 
 #include "../../include/pdmpc_geometry.h"
 
@@ -773,7 +776,7 @@ int pdmpc_fca_kernel_ms(pdmpc_handle* h, double* ms) {
 
 // ---- human-driven vehicles on the device (hdv_kernel.hip)
 namespace {
-// HdvState::table: the map (HdvMapData's arrays) and the HDV automaton's local hulls (x of every vertex, then y)
+// HdvMapSlot::table: the map (HdvMapData's arrays) and the HDV automaton's local hulls (x of every vertex, then y)
 struct HdvTable {
     size_t pt_off, pts, succ_off, succ_idx, rel, local_off, local_xy, total;
 };
@@ -822,39 +825,122 @@ HdvLayout hdv_layout(int n, int nc, int Hp, int capacity) {
     L.total = c.at;
     return L;
 }
+// what the kernels read of a map slot: the views into its device table
+HdvMapRecord hdv_record(const HdvMapSlot& M) {
+    const HdvTable T = hdv_table(M.data.map, M.data.trims * M.data.Hp, M.data.local_tot);
+    const unsigned char* tb = M.table.p;
+    HdvMapRecord R;
+    R.map = M.data.map.view((const int32_t*)(tb + T.pt_off), (const double*)(tb + T.pts), (const int32_t*)(tb + T.succ_off), (const int32_t*)(tb + T.succ_idx), tb + T.rel);
+    R.local_x = (const double*)(tb + T.local_xy);
+    R.local_y = R.local_x + M.data.local_tot;
+    R.local_off = (const int32_t*)(tb + T.local_off);
+    return R;
+}
+// ... of the grouped call for n HDVs and nc CAVs in G groups with `pairs` (CAV, HDV) pairs: hdv_layout's regions over all groups, the
+// groups' records and lookups among the inputs, the scan's results
+struct HdvGroupedLayout {
+    size_t in, cav, trim, cav_lanelet, groups, group_of, pair_first, in_bytes, n_chains, chain_id, chain_succ, slot_n, slot_flags, slot_before, row_base;
+    size_t out, status, n_rows, set_base, n_closest, closest, row_hdv, set_off, set_flags, adjacency, set_xy, total;
+};
+HdvGroupedLayout hdv_grouped_ws(int G, int n, int nc, size_t pairs, int Hp, int capacity) {
+    const size_t lists = (size_t)n * PDMPC_HDV_MAX_CHAINS, slots = lists * Hp;
+    Carver c;
+    HdvGroupedLayout L;
+    L.in = c.take<double>((size_t)6 * n);
+    L.cav = c.take<double>((size_t)4 * nc);
+    L.trim = c.take<int32_t>((size_t)n);
+    L.cav_lanelet = c.take<int32_t>((size_t)nc);
+    L.groups = c.take<HdvGroup>((size_t)G);
+    L.group_of = c.take<int32_t>((size_t)n);
+    L.pair_first = c.take<int32_t>((size_t)G + 1);
+    L.in_bytes = c.end8();
+    L.n_chains = c.take<int32_t>((size_t)n);
+    L.chain_id = c.take<int32_t>(lists);
+    L.chain_succ = c.take<int32_t>(lists);
+    L.slot_n = c.take<int32_t>(slots);
+    L.slot_flags = c.take<uint8_t>(slots);
+    L.slot_before = c.take<int32_t>(slots);
+    L.row_base = c.take<int32_t>((size_t)n);
+    L.out = c.end8();
+    L.status = c.take<int32_t>(2);
+    L.n_rows = c.take<int32_t>((size_t)G);
+    L.set_base = c.take<int32_t>((size_t)G + 1);
+    L.n_closest = c.take<int32_t>((size_t)n);
+    L.closest = c.take<int32_t>(lists);
+    L.row_hdv = c.take<int32_t>(lists);
+    L.set_off = c.take<int32_t>(slots + G + 1);
+    L.set_flags = c.take<uint8_t>(slots);
+    L.adjacency = c.take<uint8_t>(pairs);
+    L.set_xy = c.take<double>((size_t)2 * capacity);
+    L.total = c.at;
+    return L;
+}
 }  // namespace
 
-int pdmpc_upload_hdv_map(pdmpc_handle* h, int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x, const double* left_y,
-                         const double* right_x, const double* right_y, const int32_t* succ_offset, const int32_t* succ_index, const uint8_t* relationship,
-                         int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* hdv_local_sets) {
+int pdmpc_upload_hdv_map_slot(pdmpc_handle* h, int32_t slot, int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x,
+                              const double* left_y, const double* right_x, const double* right_y, const int32_t* succ_offset, const int32_t* succ_index,
+                              const uint8_t* relationship, int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* hdv_local_sets) {
     if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    if (slot < 0 || slot >= PDMPC_HDV_MAP_SLOTS) return fail(PDMPC_ERR_INVALID, "pdmpc_upload_hdv_map: map slot out of range");
     HdvState& S = h->hdv;
-    S.valid = false;
+    HdvMapSlot& M = S.map[slot];
+    M.valid = false;
+    M.generation = 0;
     const char* why = nullptr;
-    int rc = S.map.points(n_lanelets, left_offset, right_offset, left_x, left_y, right_x, right_y, &why);
-    if (!rc) rc = S.map.graph(succ_offset, succ_index, relationship, &why);
+    int rc = M.data.map.points(n_lanelets, left_offset, right_offset, left_x, left_y, right_x, right_y, &why);
+    if (!rc) rc = M.data.map.graph(succ_offset, succ_index, relationship, &why);
     if (!rc) rc = hdv_check_sets(n_trims, Hp, hdv_local_sets, &why);
     if (rc) return fail(rc, std::string("pdmpc_upload_hdv_map: ") + why);
-    const int n_polygons = n_trims * Hp, p0 = hdv_local_sets->offset[0], local_tot = hdv_local_sets->offset[n_polygons] - p0;
-    const HdvMapData& m = S.map;
-    const HdvTable T = hdv_table(m, n_polygons, local_tot);
+    M.data.keep_sets(n_trims, Hp, hdv_local_sets);
+    const HdvMapData& m = M.data.map;
+    const int local_tot = M.data.local_tot;
+    const HdvTable T = hdv_table(m, n_trims * Hp, local_tot);
     std::vector<unsigned char> stage(T.total, 0);
     std::memcpy(stage.data() + T.pt_off, m.pt_off.data(), m.pt_off.size() * sizeof(int32_t));
     std::memcpy(stage.data() + T.pts, m.pts.data(), m.pts.size() * sizeof(double));
     std::memcpy(stage.data() + T.succ_off, m.succ_off.data(), m.succ_off.size() * sizeof(int32_t));
     if (m.n_succ) std::memcpy(stage.data() + T.succ_idx, m.succ_idx.data(), m.succ_idx.size() * sizeof(int32_t));
     std::memcpy(stage.data() + T.rel, m.rel.data(), m.rel.size());
-    int32_t* loff = (int32_t*)(stage.data() + T.local_off);
-    for (int p = 0; p <= n_polygons; ++p) loff[p] = hdv_local_sets->offset[p] - p0;
-    std::memcpy(stage.data() + T.local_xy, hdv_local_sets->x + p0, (size_t)local_tot * sizeof(double));
-    std::memcpy(stage.data() + T.local_xy + (size_t)local_tot * sizeof(double), hdv_local_sets->y + p0, (size_t)local_tot * sizeof(double));
+    std::memcpy(stage.data() + T.local_off, M.data.local_off.data(), M.data.local_off.size() * sizeof(int32_t));
+    std::memcpy(stage.data() + T.local_xy, M.data.local_xy.data(), M.data.local_xy.size() * sizeof(double));
     ON_DEVICE(h->cfg.device);
-    if (S.table.ensure_exact(T.total)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the HDV map");
-    HIPCHK(hipMemcpy(S.table.p, stage.data(), T.total, hipMemcpyHostToDevice));
-    S.trims = n_trims;
-    S.Hp = Hp;
-    S.local_tot = local_tot;
-    S.valid = true;
+    // (every call synchronises before it returns: no launch reads a table or a record that is replaced here)
+    if (M.table.ensure_exact(T.total)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the HDV map");
+    if (!S.maps.p) {
+        if (S.maps.ensure_exact(PDMPC_HDV_MAP_SLOTS)) return fail(PDMPC_ERR_HIP, "hipMalloc failed for the HDV map records");
+        HIPCHK(hipMemset(S.maps.p, 0, S.maps.cap * sizeof(HdvMapRecord)));
+    }
+    HIPCHK(hipMemcpy(M.table.p, stage.data(), T.total, hipMemcpyHostToDevice));
+    const HdvMapRecord R = hdv_record(M);
+    HIPCHK(hipMemcpy(S.maps.p + slot, &R, sizeof R, hipMemcpyHostToDevice));
+    static std::atomic<int64_t> generations{0};  // (of all handles: a remembered generation is found again on the handle and in the slot it came from only)
+    M.generation = ++generations;
+    S.uploads += 1;
+    M.valid = true;
+    return PDMPC_OK;
+}
+
+int pdmpc_upload_hdv_map(pdmpc_handle* h, int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x, const double* left_y,
+                         const double* right_x, const double* right_y, const int32_t* succ_offset, const int32_t* succ_index, const uint8_t* relationship,
+                         int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* hdv_local_sets) {
+    return pdmpc_upload_hdv_map_slot(h, 0, n_lanelets, left_offset, right_offset, left_x, left_y, right_x, right_y, succ_offset, succ_index, relationship, n_trims, Hp,
+                                     hdv_local_sets);
+}
+
+int pdmpc_hdv_map_slot_state(pdmpc_handle* h, int32_t slot, int64_t* generation, int64_t* uploads, int32_t* Hp) {
+    if (!h || slot < 0 || slot >= PDMPC_HDV_MAP_SLOTS) return fail(PDMPC_ERR_INVALID, "pdmpc_hdv_map_slot_state: bad argument");
+    if (generation) *generation = h->hdv.map[slot].valid ? h->hdv.map[slot].generation : 0;
+    if (uploads) *uploads = h->hdv.uploads;
+    if (Hp) *Hp = h->hdv.map[slot].valid ? h->hdv.map[slot].data.Hp : 0;
+    return PDMPC_OK;
+}
+
+int pdmpc_hdv_map_slot_holds(pdmpc_handle* h, int32_t slot, int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x,
+                             const double* left_y, const double* right_x, const double* right_y, const int32_t* succ_offset, const int32_t* succ_index,
+                             const uint8_t* relationship, int32_t n_trims, int32_t Hp, const pdmpc_polygon_set* hdv_local_sets, int32_t* holds) {
+    if (!h || !holds || slot < 0 || slot >= PDMPC_HDV_MAP_SLOTS) return fail(PDMPC_ERR_INVALID, "pdmpc_hdv_map_slot_holds: bad argument");
+    const HdvMapSlot& M = h->hdv.map[slot];
+    *holds = M.valid && M.data.holds(n_lanelets, left_offset, right_offset, left_x, left_y, right_x, right_y, succ_offset, succ_index, relationship, n_trims, Hp, hdv_local_sets);
     return PDMPC_OK;
 }
 
@@ -864,16 +950,17 @@ int pdmpc_hdv_traffic(pdmpc_handle* h, int32_t n_hdv, const double* x, const dou
                       int32_t* row_hdv, int32_t* set_offset, double* set_x, double* set_y, uint8_t* set_flags, uint8_t* adjacency) {
     if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
     HdvState& S = h->hdv;
-    if (!S.valid) return fail(PDMPC_ERR_INVALID, "pdmpc_hdv_traffic before pdmpc_upload_hdv_map");
+    const HdvMapSlot& M0 = S.map[0];
+    if (!M0.valid) return fail(PDMPC_ERR_INVALID, "pdmpc_hdv_traffic before pdmpc_upload_hdv_map");
     const char* why = nullptr;
-    if (const int rc = hdv_check_call(S.map.n_lanelets, S.trims, n_hdv, x, y, cos_yaw, sin_yaw, trim, tile_dx, tile_dy, n_cav, cav_x, cav_y, cav_lanelet, cav_tile_dx,
+    if (const int rc = hdv_check_call(M0.data.map.n_lanelets, M0.data.trims, n_hdv, x, y, cos_yaw, sin_yaw, trim, tile_dx, tile_dy, n_cav, cav_x, cav_y, cav_lanelet, cav_tile_dx,
                                       cav_tile_dy, closest_offset, closest_index, capacity, n_rows, row_hdv, set_offset, adjacency, &why))
         return fail(rc, std::string("pdmpc_hdv_traffic: ") + why);
     *n_rows = 0;
     closest_offset[0] = 0;
     set_offset[0] = 0;
     if (n_hdv == 0) return PDMPC_OK;
-    const int Hp = S.Hp, n = n_hdv, nc = n_cav;
+    const int Hp = M0.data.Hp, n = n_hdv, nc = n_cav;
     const size_t lists = (size_t)n * PDMPC_HDV_MAX_CHAINS, slots = lists * Hp;
     // (no more vertices are read back than the slots can hold, whatever room the caller has)
     const int cap = (int)std::min<size_t>((size_t)capacity, set_x && set_y ? slots * PDMPC_BOUND_SLOT : 0);
@@ -890,17 +977,16 @@ int pdmpc_hdv_traffic(pdmpc_handle* h, int32_t n_hdv, const double* x, const dou
         stage_poses((double*)(hin + L.cav), (size_t)nc, cav_x, cav_y, cav_tile_dx, cav_tile_dy);
         std::memcpy(hin + L.cav_lanelet, cav_lanelet, (size_t)nc * sizeof(int32_t));
     }
-    const HdvTable T = hdv_table(S.map, S.trims * Hp, S.local_tot);
-    const unsigned char* tb = S.table.p;
+    const HdvMapRecord R = hdv_record(M0);
     HdvArgs A;
-    A.map = S.map.view((const int32_t*)(tb + T.pt_off), (const double*)(tb + T.pts), (const int32_t*)(tb + T.succ_off), (const int32_t*)(tb + T.succ_idx), tb + T.rel);
+    A.map = R.map;
     A.n_hdv = n;
     A.n_cav = nc;
     A.Hp = Hp;
     A.capacity = cap;
-    A.local_x = (const double*)(tb + T.local_xy);
-    A.local_y = A.local_x + S.local_tot;
-    A.local_off = (const int32_t*)(tb + T.local_off);
+    A.local_x = R.local_x;
+    A.local_y = R.local_y;
+    A.local_off = R.local_off;
     A.in = (const double*)(ws + L.in);
     A.trim = (const int32_t*)(ws + L.trim);
     A.cav = (const double*)(ws + L.cav);
@@ -949,6 +1035,163 @@ int pdmpc_hdv_traffic(pdmpc_handle* h, int32_t n_hdv, const double* x, const dou
         std::memcpy(set_y, hx + cap, (size_t)total * sizeof(double));
     }
     if (set_flags) std::memcpy(set_flags, back(L.set_flags), (size_t)rows * Hp);
+    return PDMPC_OK;
+}
+
+int pdmpc_hdv_traffic_grouped(pdmpc_handle* h, int32_t n_groups, const int32_t* group_slot, const int32_t* hdv_offset, const int32_t* cav_offset, const double* x,
+                              const double* y, const double* cos_yaw, const double* sin_yaw, const int32_t* trim, const double* tile_dx, const double* tile_dy,
+                              const double* cav_x, const double* cav_y, const int32_t* cav_lanelet, const double* cav_tile_dx, const double* cav_tile_dy,
+                              int32_t* closest_offset, int32_t* closest_index, int32_t capacity, int32_t* n_rows, int32_t* row_hdv, int32_t* set_offset,
+                              int32_t* set_base, double* set_x, double* set_y, uint8_t* set_flags, uint8_t* adjacency) {
+    const std::string who = "pdmpc_hdv_traffic_grouped: ";
+    if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
+    HdvState& S = h->hdv;
+    if (n_groups < 0 || capacity < 0 || !set_base || (n_groups && (!group_slot || !hdv_offset || !cav_offset || !closest_offset || !n_rows || !set_offset)))
+        return fail(PDMPC_ERR_INVALID, who + "bad argument");
+    if (n_groups == 0) {
+        set_base[0] = 0;
+        return PDMPC_OK;
+    }
+    if (hdv_offset[0] != 0 || cav_offset[0] != 0) return fail(PDMPC_ERR_INVALID, who + "offsets that do not start at 0");
+    int Hp = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const std::string group = who + "group " + std::to_string(g) + ": ";
+        if (hdv_offset[g + 1] < hdv_offset[g] || cav_offset[g + 1] < cav_offset[g]) return fail(PDMPC_ERR_INVALID, group + "offsets decrease");
+        if (group_slot[g] < 0 || group_slot[g] >= PDMPC_HDV_MAP_SLOTS) return fail(PDMPC_ERR_INVALID, group + "map slot out of range");
+        const HdvMapSlot& M = S.map[group_slot[g]];
+        if (!M.valid) return fail(PDMPC_ERR_INVALID, group + "no map was uploaded into its slot");
+        if (Hp && M.data.Hp != Hp) return fail(PDMPC_ERR_INVALID, group + "the Hp of its slot differs from the slots of the groups before");
+        Hp = M.data.Hp;
+    }
+    const int n = hdv_offset[n_groups], nc = cav_offset[n_groups];
+    std::vector<int32_t> closest_at((size_t)n_groups + 1), list_at((size_t)n_groups + 1), set_offset_at((size_t)n_groups + 1), set_at((size_t)n_groups + 1);
+    std::vector<int64_t> adjacency_at((size_t)n_groups + 1);
+    if (const int rc = hdv_grouped_layout(n_groups, hdv_offset, cav_offset, Hp, closest_at.data(), list_at.data(), set_offset_at.data(), set_at.data(), adjacency_at.data()))
+        return fail(rc, who + "bad offsets");
+    const int64_t pairs = adjacency_at[(size_t)n_groups];
+    for (int g = 0; g < n_groups; ++g)
+        if (hdv_offset[g + 1] - hdv_offset[g] > PDMPC_HDV_MAX_VEHICLES || cav_offset[g + 1] - cav_offset[g] > PDMPC_HDV_MAX_CAVS)
+            return fail(PDMPC_ERR_CAPACITY, who + "group " + std::to_string(g) + ": more than PDMPC_HDV_MAX_VEHICLES HDVs or PDMPC_HDV_MAX_CAVS CAVs");
+    if (n > PDMPC_HDV_GROUPED_MAX_VEHICLES) return fail(PDMPC_ERR_CAPACITY, who + "more than PDMPC_HDV_GROUPED_MAX_VEHICLES HDVs in the call");
+    if (pairs > INT32_MAX) return fail(PDMPC_ERR_CAPACITY, who + "2^31 or more (CAV, HDV) pairs");
+    if (n && (!x || !y || !cos_yaw || !sin_yaw || !trim || !tile_dx || !tile_dy || !closest_index || !row_hdv)) return fail(PDMPC_ERR_INVALID, who + "a null HDV array");
+    if (nc && (!cav_x || !cav_y || !cav_lanelet || !cav_tile_dx || !cav_tile_dy)) return fail(PDMPC_ERR_INVALID, who + "a null CAV array");
+    if (pairs && !adjacency) return fail(PDMPC_ERR_INVALID, who + "no adjacency array");
+    for (int g = 0; g < n_groups; ++g) {
+        const HdvSlotData& D = S.map[group_slot[g]].data;
+        for (int q = hdv_offset[g]; q < hdv_offset[g + 1]; ++q)
+            if (trim[q] < 1 || trim[q] > D.trims) return fail(PDMPC_ERR_INVALID, who + "group " + std::to_string(g) + ": trim out of range");
+        for (int v = cav_offset[g]; v < cav_offset[g + 1]; ++v)
+            if (cav_lanelet[v] < 1 || cav_lanelet[v] > D.map.n_lanelets) return fail(PDMPC_ERR_INVALID, who + "group " + std::to_string(g) + ": a CAV's lanelet id out of range");
+    }
+    for (int g = 0; g < n_groups; ++g) {  // what has a size whatever happens
+        n_rows[g] = 0;
+        closest_offset[closest_at[(size_t)g]] = 0;
+        set_offset[set_offset_at[(size_t)g]] = 0;
+        set_base[g] = 0;
+    }
+    set_base[n_groups] = 0;
+    if (n == 0) return PDMPC_OK;
+    const size_t lists = (size_t)n * PDMPC_HDV_MAX_CHAINS, slots = lists * Hp;
+    // (no more vertices are read back than the slots can hold, whatever room the caller has)
+    const int cap = (int)std::min<size_t>((size_t)capacity, set_x && set_y ? slots * PDMPC_BOUND_SLOT : 0);
+    ON_DEVICE(h->cfg.device);
+    const HdvGroupedLayout L = hdv_grouped_ws(n_groups, n, nc, (size_t)pairs, Hp, cap);
+    // (the slots of the lane pass: what this call needs, without head room -- 256 KB x Hp per HDV)
+    if (S.ws.ensure(L.total) || S.slots.ensure_exact(2 * slots * PDMPC_BOUND_SLOT) || S.h_in.ensure(L.in_bytes) || S.h_out.ensure(L.total - L.out))
+        return fail(PDMPC_ERR_HIP, "hipMalloc failed for the grouped HDV traffic call");
+    unsigned char *hin = S.h_in.p, *ws = S.ws.p;
+    double* in = (double*)(hin + L.in);
+    stage_poses(in, (size_t)n, x, y, cos_yaw, sin_yaw, (int32_t*)(hin + L.trim), trim);
+    std::memcpy(in + 4 * (size_t)n, tile_dx, (size_t)n * sizeof(double));
+    std::memcpy(in + 5 * (size_t)n, tile_dy, (size_t)n * sizeof(double));
+    if (nc) {
+        stage_poses((double*)(hin + L.cav), (size_t)nc, cav_x, cav_y, cav_tile_dx, cav_tile_dy);
+        std::memcpy(hin + L.cav_lanelet, cav_lanelet, (size_t)nc * sizeof(int32_t));
+    }
+    HdvGroup* groups = (HdvGroup*)(hin + L.groups);
+    int32_t *group_of = (int32_t*)(hin + L.group_of), *pair_first = (int32_t*)(hin + L.pair_first);
+    for (int g = 0; g < n_groups; ++g) {
+        groups[g] = HdvGroup{group_slot[g], hdv_offset[g], hdv_offset[g + 1] - hdv_offset[g], cav_offset[g], cav_offset[g + 1] - cav_offset[g]};
+        for (int q = hdv_offset[g]; q < hdv_offset[g + 1]; ++q) group_of[q] = g;
+        pair_first[g] = (int32_t)adjacency_at[(size_t)g];
+    }
+    pair_first[n_groups] = (int32_t)pairs;
+    HdvGroupedArgs GA;
+    std::memset(&GA, 0, sizeof GA);
+    HdvArgs& A = GA.a;
+    A.n_hdv = n;
+    A.n_cav = nc;
+    A.Hp = Hp;
+    A.capacity = cap;
+    A.in = (const double*)(ws + L.in);
+    A.trim = (const int32_t*)(ws + L.trim);
+    A.cav = (const double*)(ws + L.cav);
+    A.cav_lanelet = (const int32_t*)(ws + L.cav_lanelet);
+    A.n_closest = (int32_t*)(ws + L.n_closest);
+    A.closest = (int32_t*)(ws + L.closest);
+    A.n_chains = (int32_t*)(ws + L.n_chains);
+    A.chain_id = (int32_t*)(ws + L.chain_id);
+    A.chain_succ = (int32_t*)(ws + L.chain_succ);
+    A.slot_x = S.slots.p;
+    A.slot_y = S.slots.p + slots * PDMPC_BOUND_SLOT;
+    A.slot_n = (int32_t*)(ws + L.slot_n);
+    A.slot_flags = ws + L.slot_flags;
+    A.status = (int32_t*)(ws + L.status);
+    A.row_hdv = (int32_t*)(ws + L.row_hdv);
+    A.set_off = (int32_t*)(ws + L.set_off);
+    A.set_flags = ws + L.set_flags;
+    A.set_x = (double*)(ws + L.set_xy);
+    A.set_y = A.set_x + cap;
+    A.adjacency = ws + L.adjacency;
+    GA.maps = S.maps.p;
+    GA.groups = (const HdvGroup*)(ws + L.groups);
+    GA.group_of = (const int32_t*)(ws + L.group_of);
+    GA.pair_first = (const int32_t*)(ws + L.pair_first);
+    GA.n_groups = n_groups;
+    GA.n_pairs = (int32_t)pairs;
+    GA.slot_before = (int32_t*)(ws + L.slot_before);
+    GA.row_base = (int32_t*)(ws + L.row_base);
+    GA.n_rows = (int32_t*)(ws + L.n_rows);
+    GA.set_base = (int32_t*)(ws + L.set_base);
+    HIPCHK(hipMemcpyAsync(ws, hin, L.in_bytes, hipMemcpyHostToDevice, h->stream));
+    if (const int rc = timed_launch(h, S.timed, pdmpc_launch_hdv_traffic_grouped, GA, "grouped HDV traffic")) return rc;
+    HIPCHK(hipMemcpyAsync(S.h_out.p, ws + L.out, L.total - L.out, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(sync_stream(h));
+    S.timed.fold();
+    auto back = [&](size_t at) { return (const unsigned char*)S.h_out.p + (at - L.out); };  // the read-back block at the workspace's offsets
+    const int32_t* status = (const int32_t*)back(L.status);
+    const int32_t *rows_of = (const int32_t*)back(L.n_rows), *n_closest = (const int32_t*)back(L.n_closest), *closest = (const int32_t*)back(L.closest);
+    // the outputs stand on the device where the caller's arrays have them: every group's blocks are copied as they are
+    int over = -1;  // the first group with an HDV whose lists ran over
+    for (int g = 0; g < n_groups; ++g) {
+        const int h0 = hdv_offset[g], ng = hdv_offset[g + 1] - h0, rows = rows_of[g];
+        n_rows[g] = rows;
+        if (rows < 0) {
+            if (over < 0) over = g;
+            continue;
+        }
+        int32_t* co = closest_offset + closest_at[(size_t)g];
+        for (int q = 0; q < ng; ++q) {
+            std::memcpy(closest_index + list_at[(size_t)g] + co[q], closest + (size_t)(h0 + q) * PDMPC_HDV_MAX_CHAINS, (size_t)n_closest[h0 + q] * sizeof(int32_t));
+            co[q + 1] = co[q] + n_closest[h0 + q];
+        }
+        if (rows) std::memcpy(row_hdv + list_at[(size_t)g], (const int32_t*)back(L.row_hdv) + list_at[(size_t)g], (size_t)rows * sizeof(int32_t));
+        std::memcpy(set_offset + set_offset_at[(size_t)g], (const int32_t*)back(L.set_off) + set_offset_at[(size_t)g], ((size_t)rows * Hp + 1) * sizeof(int32_t));
+        if (set_flags && rows) std::memcpy(set_flags + set_at[(size_t)g], back(L.set_flags) + set_at[(size_t)g], (size_t)rows * Hp);
+    }
+    std::memcpy(set_base, back(L.set_base), ((size_t)n_groups + 1) * sizeof(int32_t));
+    if (pairs) std::memcpy(adjacency, back(L.adjacency), (size_t)pairs);
+    const int32_t total = set_base[n_groups];
+    const bool fits = capacity >= total && (!total || (set_x && set_y)) && !(status[1] & PDMPC_HDV_OVER_SLOT);
+    if (fits && total) {
+        const double* hx = (const double*)back(L.set_xy);
+        std::memcpy(set_x, hx, (size_t)total * sizeof(double));
+        std::memcpy(set_y, hx + cap, (size_t)total * sizeof(double));
+    }
+    if (over >= 0) return fail(PDMPC_ERR_CAPACITY, who + "group " + std::to_string(over) + ": an HDV has more than PDMPC_HDV_MAX_CHAINS closest lanelets or chains");
+    if (status[1] & PDMPC_HDV_OVER_SLOT) return fail(PDMPC_ERR_CAPACITY, who + "a reachable lane has more than PDMPC_BOUNDED_MAX_COLS vertices");
+    if (!fits) return fail(PDMPC_ERR_CAPACITY, who + "capacity too small for the reachable lanes");
     return PDMPC_OK;
 }
 

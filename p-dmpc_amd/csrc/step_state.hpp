@@ -33,6 +33,18 @@ struct PrepScratch {
         std::vector<double> lan_x, lan_y, set_x, set_y;
         std::vector<uint8_t> adjacency;      // the blocks
     } call;
+    int32_t hdv_calls[2] = {0, 0};  // ... its HDV traffic calls and the map uploads they needed (pdmpc_sweep_last_hdv_calls)
+    // one grouped HDV traffic call: the HDVs and CAVs of a batch of members, member after member, and what it returns in the blocks
+    // of pdmpc_hdv_grouped_layout_host
+    struct Hdv {
+        std::vector<int32_t> slot, hdv_offset, cav_offset, trim, cav_lanelet;
+        std::vector<double> x, y, cos_yaw, sin_yaw, tile_dx, tile_dy, cav_x, cav_y, cav_tile_dx, cav_tile_dy;
+        std::vector<int32_t> closest_at, list_at, set_offset_at, set_at;
+        std::vector<int64_t> adjacency_at;
+        std::vector<int32_t> closest_off, closest_idx, n_rows, row_hdv, set_off, set_base;
+        std::vector<double> set_x, set_y;
+        std::vector<uint8_t> set_flags, adjacency;
+    } hdv;
     // the grouped collision assessment: the FCA members' reference points, member after member, and what it returns
     struct Fca {
         std::vector<pdmpc_fca_group> groups;

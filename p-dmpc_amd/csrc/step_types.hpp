@@ -197,12 +197,14 @@ struct StepInputs {
     std::vector<int32_t> current_lanelet;  // the lanelet id every vehicle is on (get_predicted_lanelets.m:44,61); 0 without lanelets
     std::vector<uint8_t> adjacency;  // n x n row-major
 };
-// Human-driven vehicles (pdmpc_controller_set_hdvs): what pdmpc_hdv_traffic is called with -- the scenario's lanelets
+// Human-driven vehicles (pdmpc_controller_set_hdvs): what the traffic call is made with -- the scenario's lanelets
 // flattened, the lanelet graph, the local sets of the HDVs' automaton, tiles and the last measured poses --, what the step's ONE call
 // left (pdmpc_controller_hdv_info), and per CAV the rows of the HDVs adjacent to it as the set its searches receive.
 struct HdvTraffic {
     int n = 0;  // HDVs; 0: none set, and a step is built as without this struct
     bool measured = false;
+    int32_t map_slot = -1;       // the handle's map slot this map was found in or uploaded to by the last step's traffic stage, and
+    int64_t map_generation = 0;  // ... the slot's generation then: while it has not moved the map is still there (0: not known)
     std::vector<int32_t> lan_off, succ_off, succ_idx;
     std::vector<double> left_x, left_y, right_x, right_y;
     std::vector<uint8_t> rel;

@@ -951,11 +951,30 @@ class Handle:
         _check(self.L, self.L.pdmpc_fca_kernel_ms(self.h, C.byref(ms)), "pdmpc_fca_kernel_ms")
         return ms.value
 
-    def upload_hdv_map(self, hmap, local_sets):
-        """pdmpc_upload_hdv_map: the map (hdv.HdvMap) and the HDV automaton's local sets for hdv_traffic."""
+    def upload_hdv_map(self, hmap, local_sets, slot=0):
+        """pdmpc_upload_hdv_map_slot: the map (hdv.HdvMap) and the HDV automaton's local sets into one of the handle's map slots; slot 0
+        is what hdv_traffic reads, a group of hdv_traffic_grouped names its slot."""
         from . import hdv
 
-        hdv.upload_hdv_map(self, hmap, local_sets)
+        hdv.upload_hdv_map(self, hmap, local_sets, slot=slot)
+
+    def hdv_map_slot_state(self, slot=0):
+        """(the slot's generation: 0 before its first upload, a larger number after every upload; uploads into all slots so far)"""
+        from . import hdv
+
+        return hdv.hdv_map_slot_state(self, slot)
+
+    def hdv_map_slot_holds(self, slot, hmap, local_sets):
+        """pdmpc_hdv_map_slot_holds: the slot holds exactly this map and these local sets (compared byte for byte, no hash)"""
+        from . import hdv
+
+        return hdv.hdv_map_slot_holds(self, slot, hmap, local_sets)
+
+    def hdv_traffic_grouped(self, groups, capacity=None, call_ms=None, raw=None, guard=0):
+        """pdmpc_hdv_traffic_grouped on this handle's device -> per group the dict of hdv_traffic; see hdv.hdv_traffic_grouped_native."""
+        from . import hdv
+
+        return hdv.hdv_traffic_grouped_native(self, groups, capacity=capacity, call_ms=call_ms, raw=raw, guard=guard)
 
     def hdv_traffic(self, hdv_x, hdv_y, hdv_yaw, hdv_trim, hdv_tile, cav_x, cav_y, cav_lanelet, cav_tile, capacity=None, call_ms=None):
         """pdmpc_hdv_traffic on this handle's device; see hdv.hdv_traffic_native."""

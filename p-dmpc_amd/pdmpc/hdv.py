@@ -19,6 +19,7 @@ from . import abi
 from . import reachability as R
 
 MAX_CHAINS = 16  # PDMPC_HDV_MAX_CHAINS
+MAP_SLOTS = 8  # PDMPC_HDV_MAP_SLOTS
 CLOSEST_BAND = 0.1  # map_position_to_closest_lanelets.m:4 (added to a distance; the reference calls it "squared")
 POINT_TOLERANCE = 1e-6  # is_hdv_behind.m:6
 LONGITUDINAL, MERGING, FORKING = 1, 3, 4  # LaneletRelationshipType.m (road_network.RELATIONSHIP_*)
@@ -190,17 +191,158 @@ def lanelet_distances_native(hmap: HdvMap, px: float, py: float) -> np.ndarray:
     return d
 
 
-def upload_hdv_map(handle, hmap: HdvMap, local_sets):
-    """pdmpc_upload_hdv_map: the map and the HDV automaton's local sets ([trim][k] (2, m) hulls) onto the handle's device."""
+def upload_hdv_map(handle, hmap: HdvMap, local_sets, slot: int = 0):
+    """pdmpc_upload_hdv_map_slot: the map and the HDV automaton's local sets ([trim][k] (2, m) hulls) into map slot `slot` of the
+    handle (slot 0: pdmpc_upload_hdv_map, what pdmpc_hdv_traffic reads)."""
     from . import backend
 
     L = backend.load_library()
     args, keep = hmap.arrays()
     ps, pkeep = backend.pack_local_sets(local_sets)
-    rc = L.pdmpc_upload_hdv_map(handle.h, *args, len(local_sets), len(local_sets[0]), C.byref(ps))
+    rc = L.pdmpc_upload_hdv_map_slot(handle.h, int(slot), *args, len(local_sets), len(local_sets[0]), C.byref(ps))
     del keep, pkeep
-    backend._check(L, rc, "pdmpc_upload_hdv_map")
-    handle.hdv_shape = (hmap.n, len(local_sets[0]))
+    backend._check(L, rc, "pdmpc_upload_hdv_map_slot")
+    if slot == 0:
+        handle.hdv_shape = (hmap.n, len(local_sets[0]))
+
+
+def hdv_map_slot_state(handle, slot: int = 0):
+    """pdmpc_hdv_map_slot_state -> (generation of the slot, uploads into all slots of the handle so far)"""
+    from . import backend
+
+    L = backend.load_library()
+    gen, ups = C.c_int64(0), C.c_int64(0)
+    backend._check(L, L.pdmpc_hdv_map_slot_state(handle.h, int(slot), C.byref(gen), C.byref(ups), None), "pdmpc_hdv_map_slot_state")
+    return int(gen.value), int(ups.value)
+
+
+def hdv_map_slot_hp(handle, slot: int = 0) -> int:
+    """The Hp of the hulls map slot `slot` of the handle holds, whoever uploaded them (pdmpc_hdv_map_slot_state); 0: the slot is empty."""
+    from . import backend
+
+    L = backend.load_library()
+    hp = C.c_int32(0)
+    backend._check(L, L.pdmpc_hdv_map_slot_state(handle.h, int(slot), None, None, C.byref(hp)), "pdmpc_hdv_map_slot_state")
+    return int(hp.value)
+
+
+def hdv_map_slot_holds(handle, slot: int, hmap: HdvMap, local_sets) -> bool:
+    """pdmpc_hdv_map_slot_holds: does the slot hold exactly this map and these local sets, byte for byte?"""
+    from . import backend
+
+    L = backend.load_library()
+    args, keep = hmap.arrays()
+    ps, pkeep = backend.pack_local_sets(local_sets)
+    holds = C.c_int32(0)
+    rc = L.pdmpc_hdv_map_slot_holds(handle.h, int(slot), *args, len(local_sets), len(local_sets[0]), C.byref(ps), C.byref(holds))
+    del keep, pkeep
+    backend._check(L, rc, "pdmpc_hdv_map_slot_holds")
+    return bool(holds.value)
+
+
+def grouped_layout(hdv_offset, cav_offset, Hp: int):
+    """pdmpc_hdv_grouped_layout_host -> dict of the block starts (arrays of n_groups + 1 entries, the last the room the array needs):
+    closest (closest_offset), lists (closest_index, row_hdv), set_offset, sets (set_flags), adjacency."""
+    from . import backend
+
+    L = backend.load_library()
+    ho, co = np.ascontiguousarray(hdv_offset, dtype=np.int32), np.ascontiguousarray(cav_offset, dtype=np.int32)
+    G = ho.size - 1
+    out = {k: np.zeros(G + 1, dtype=np.int32) for k in ("closest", "lists", "set_offset", "sets")}
+    out["adjacency"] = np.zeros(G + 1, dtype=np.int64)
+    rc = L.pdmpc_hdv_grouped_layout_host(G, abi.i32p(ho), abi.i32p(co), int(Hp), abi.i32p(out["closest"]), abi.i32p(out["lists"]), abi.i32p(out["set_offset"]),
+                                         abi.i32p(out["sets"]), out["adjacency"].ctypes.data_as(C.POINTER(C.c_int64)))
+    backend._check(L, rc, "pdmpc_hdv_grouped_layout_host", last_error=None)
+    return out
+
+
+def hdv_traffic_grouped_native(handle, groups, capacity=None, call_ms=None, raw=None, guard=0):
+    """pdmpc_hdv_traffic_grouped on `handle`'s device.  groups: one (slot, hdv_x, hdv_y, hdv_yaw, hdv_trim, hdv_tile, cav_x, cav_y,
+    cav_lanelet, cav_tile) per group, the arguments of hdv_traffic behind the map slot the group drives on.  capacity None: a first
+    call sizes a second one; a number: ONE call with that room for the vertices of all groups, which raises backend.CapacityError
+    (count = the vertices needed) if it is too small.  raw: a dict that receives the call's arrays as it left them (set_base, n_rows,
+    set_offset, set_x, set_y, ... and `layout`), also when the call fails; guard: entries kept behind the `capacity` entries of set_x /
+    set_y (NaN before the call).  -> per group the dict of hdv_traffic, sliced by pdmpc_hdv_grouped_layout_host; None for a group
+    whose HDV ran over its lists (the call then raises unless raw is given)."""
+    from . import backend
+
+    L = backend.load_library()
+    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64).reshape(-1)  # noqa: E731
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)  # noqa: E731
+    cat = lambda parts, dtype: np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=dtype).reshape(-1) for p in parts] + [np.zeros(0, dtype=dtype)]))  # noqa: E731
+    G = len(groups)
+    slot = i32([g[0] for g in groups])
+    ho = np.zeros(G + 1, dtype=np.int32)
+    co = np.zeros(G + 1, dtype=np.int32)
+    for g, grp in enumerate(groups):
+        ho[g + 1] = ho[g] + len(f64(grp[1]))
+        co[g + 1] = co[g] + len(f64(grp[6]))
+    x, y, yaw = (cat([g[i] for g in groups], np.float64) for i in (1, 2, 3))
+    trim = cat([g[4] for g in groups], np.int32)
+    tile = cat([g[5] for g in groups], np.float64).reshape(-1, 2)
+    c = np.array([math.cos(float(a)) for a in yaw], dtype=np.float64)  # the host's libm, as the Python twin moves the sets
+    s = np.array([math.sin(float(a)) for a in yaw], dtype=np.float64)
+    tdx, tdy = np.ascontiguousarray(tile[:, 0]), np.ascontiguousarray(tile[:, 1])
+    cx, cy = (cat([g[i] for g in groups], np.float64) for i in (6, 7))
+    cl = cat([g[8] for g in groups], np.int32)
+    ctile = cat([g[9] for g in groups], np.float64).reshape(-1, 2)
+    cdx, cdy = np.ascontiguousarray(ctile[:, 0]), np.ascontiguousarray(ctile[:, 1])
+    # the arrays are sized by the Hp the handle itself reports for the groups' slots (a controller's traffic stage uploads maps too); an
+    # empty slot, a slot out of range and slots of different Hp are refused by the call before it writes anything
+    in_range = [int(k) for k in slot if 0 <= int(k) < MAP_SLOTS]
+    Hp = max([hdv_map_slot_hp(handle, k) for k in in_range] + [1])
+    lay = grouped_layout(ho, co, Hp)
+    closest_offset = np.zeros(max(int(lay["closest"][G]), 1), dtype=np.int32)
+    closest_index = np.zeros(max(int(lay["lists"][G]), 1), dtype=np.int32)
+    row_hdv = np.zeros(max(int(lay["lists"][G]), 1), dtype=np.int32)
+    set_offset = np.zeros(max(int(lay["set_offset"][G]), 1), dtype=np.int32)
+    flags = np.zeros(max(int(lay["sets"][G]), 1), dtype=np.uint8)
+    adjacency = np.zeros(max(int(lay["adjacency"][G]), 1), dtype=np.uint8)
+    n_rows = np.zeros(max(G, 1), dtype=np.int32)
+    set_base = np.zeros(G + 1, dtype=np.int32)
+    head = [handle.h, G, abi.i32p(slot), abi.i32p(ho), abi.i32p(co), abi.dp(x), abi.dp(y), abi.dp(c), abi.dp(s), abi.i32p(trim), abi.dp(tdx), abi.dp(tdy), abi.dp(cx),
+            abi.dp(cy), abi.i32p(cl), abi.dp(cdx), abi.dp(cdy), abi.i32p(closest_offset), abi.i32p(closest_index)]
+
+    def call(cap):
+        sx, sy = np.full(max(cap, 1) + guard, np.nan), np.full(max(cap, 1) + guard, np.nan)
+        tail = [cap, abi.i32p(n_rows), abi.i32p(row_hdv), abi.i32p(set_offset), abi.i32p(set_base), abi.dp(sx), abi.dp(sy), abi.u8p(flags), abi.u8p(adjacency)]
+        t0 = time.perf_counter()
+        rc = L.pdmpc_hdv_traffic_grouped(*head, *tail)
+        if call_ms is not None:
+            call_ms.append(1e3 * (time.perf_counter() - t0))
+        return rc, sx, sy
+
+    cap = 0 if capacity is None else int(capacity)
+    rc, sx, sy = call(cap)
+    sized = rc == backend.ERR_CAPACITY and int(set_base[G]) > cap  # (the totals are there: they size a second call)
+    if sized and capacity is None:
+        cap = int(set_base[G])
+        rc, sx, sy = call(cap)
+    if raw is not None:
+        raw.update(rc=rc, layout=lay, closest_offset=closest_offset, closest_index=closest_index, n_rows=n_rows[:G].copy(), row_hdv=row_hdv, set_offset=set_offset,
+                   set_base=set_base.copy(), set_x=sx, set_y=sy, set_flags=flags, adjacency=adjacency, Hp=Hp)
+    if sized and capacity is not None and rc == backend.ERR_CAPACITY and raw is None:
+        raise backend.CapacityError("pdmpc_hdv_traffic_grouped: %d vertices do not fit the capacity %d" % (int(set_base[G]), capacity), int(set_base[G]))
+    if raw is None:
+        backend._check(L, rc, "pdmpc_hdv_traffic_grouped")
+    out = []
+    for g in range(G):
+        rows, nh, ncv = int(n_rows[g]), int(ho[g + 1] - ho[g]), int(co[g + 1] - co[g])
+        if rows < 0:
+            out.append(None)
+            continue
+        cof = closest_offset[lay["closest"][g] : lay["closest"][g] + nh + 1]
+        cidx = closest_index[lay["lists"][g] :]
+        so = set_offset[lay["set_offset"][g] : lay["set_offset"][g] + rows * Hp + 1].copy()
+        b = int(set_base[g])
+        gx, gy = sx[b:], sy[b:]
+        fits = int(set_base[G]) <= cap
+        sets = [[np.array([gx[so[r * Hp + k] : so[r * Hp + k + 1]], gy[so[r * Hp + k] : so[r * Hp + k + 1]]]) for k in range(Hp)] for r in range(rows)] if fits else None
+        a0 = int(lay["adjacency"][g])
+        out.append(dict(closest=[cidx[cof[q] : cof[q + 1]].tolist() for q in range(nh)], row_hdv=row_hdv[lay["lists"][g] : lay["lists"][g] + rows].tolist(), sets=sets,
+                        flags=flags[lay["sets"][g] : lay["sets"][g] + rows * Hp].reshape(rows, Hp).copy(), adjacency=adjacency[a0 : a0 + ncv * nh].reshape(ncv, nh).copy(),
+                        set_offset=so))
+    return out
 
 
 def hdv_traffic_native(hmap, local_sets, hdv_x, hdv_y, hdv_yaw, hdv_trim, hdv_tile, cav_x, cav_y, cav_lanelet, cav_tile, handle=None, capacity=None, call_ms=None):

@@ -618,6 +618,13 @@ class NativeSweep:
         self._check(self.L.pdmpc_sweep_last_prep_calls(self.s, abi.i32p(calls)), "pdmpc_sweep_last_prep_calls")
         return calls.tolist()
 
+    def last_hdv_calls(self):
+        """(HDV traffic calls, map uploads) of the last build (pdmpc_sweep_last_hdv_calls): with a handle one grouped call for all
+        members with HDVs, and no upload of a map that is still resident in a map slot of the handle."""
+        calls = np.zeros(2, dtype=np.int32)
+        self._check(self.L.pdmpc_sweep_last_hdv_calls(self.s, abi.i32p(calls)), "pdmpc_sweep_last_hdv_calls")
+        return int(calls[0]), int(calls[1])
+
     def last_timing(self):
         """Host milliseconds of the last lock-step by part (pdmpc_sweep_last_timing)."""
         t = (C.c_double * 6)()

@@ -27,6 +27,8 @@ FCA_GROUPED = [I32, P(abi.FcaGroup), I32, DP, DP, DP, DP, IP, IP]
 CHOSEN = [CHOICE, IP, DP]  # choice, chosen, cell_cost
 HDV_MAP = [I32, IP, IP, DP, DP, DP, DP, IP, IP, BP] + TABLE  # n_lanelets, left/right offsets, left/right x y, successors, relationship, local sets
 HDV_CALL = [I32, DP, DP, DP, DP, IP, DP, DP, I32, DP, DP, IP, DP, DP, IP, IP, I32, IP, IP, IP, DP, DP, BP, BP]
+# n_groups, group_slot, hdv_offset, cav_offset | the HDVs | the CAVs | closest_offset, closest_index, capacity, n_rows, row_hdv, set_offset, set_base, set_x, set_y, set_flags, adjacency
+HDV_GROUPED = [I32, IP, IP, IP] + [DP, DP, DP, DP, IP, DP, DP] + [DP, DP, IP, DP, DP] + [IP, IP, I32, IP, IP, IP, IP, DP, DP, BP, BP]
 UNIQUE = [I32, BP, I64, P(I64), UP, IP]
 UNIQUE_GROUPED = [I32, IP, P(BP), P(I64), P(I64), UP, IP]  # n_groups, group_n, adjacency, max_out, n_out, masks, priorities
 
@@ -136,6 +138,12 @@ PROTOTYPES = {
     "pdmpc_hdv_traffic_host": (INT, HDV_MAP + HDV_CALL),
     "pdmpc_hdv_lanelet_distances_host": (INT, [I32, IP, IP, DP, DP, DP, DP, F64, F64, DP]),
     "pdmpc_hdv_kernel_ms": (INT, [OBJ, DP]),
+    "pdmpc_upload_hdv_map_slot": (INT, [OBJ, I32] + HDV_MAP),
+    "pdmpc_hdv_map_slot_state": (INT, [OBJ, I32, P(I64), P(I64), IP]),
+    "pdmpc_hdv_map_slot_holds": (INT, [OBJ, I32] + HDV_MAP + [IP]),
+    "pdmpc_hdv_check_map_host": (INT, HDV_MAP),
+    "pdmpc_hdv_grouped_layout_host": (INT, [I32, IP, IP, I32, IP, IP, IP, IP, P(I64)]),
+    "pdmpc_hdv_traffic_grouped": (INT, [OBJ] + HDV_GROUPED),
     # ---- the caller's side of the boundary, natively
     "pdmpc_controller_create": (INT, [OBJ, P(abi.ControllerConfig), P(abi.ScenarioStruct), P(OBJ)]),
     "pdmpc_controller_destroy": (INT, [OBJ]),
@@ -187,6 +195,7 @@ PROTOTYPES = {
     "pdmpc_sweep_run": (INT, [OBJ, I32, DP]),
     "pdmpc_sweep_last_timing": (INT, [OBJ, DP]),
     "pdmpc_sweep_last_prep_calls": (INT, [OBJ, IP]),
+    "pdmpc_sweep_last_hdv_calls": (INT, [OBJ, IP]),
     "pdmpc_sweep_explore_build": (INT, [OBJ, I32]),
     "pdmpc_sweep_explore_problem": (INT, [OBJ] + STEP_OUT + [P(IP)] * 4),
     "pdmpc_sweep_explore_apply": (INT, [OBJ, VOUT]),
