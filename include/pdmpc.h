@@ -744,8 +744,8 @@ int pdmpc_hdv_traffic_host(int32_t n_lanelets, const int32_t* left_offset, const
                            double* set_y, uint8_t* set_flags, uint8_t* adjacency);
 int pdmpc_hdv_lanelet_distances_host(int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x, const double* left_y,
                                      const double* right_x, const double* right_y, double px, double py, double* distance);
-/* kernel time (HIP events, ms) of the last pdmpc_hdv_traffic (its four launches) or pdmpc_hdv_traffic_grouped (its five), whichever
- * was called last */
+/* kernel time (HIP events, ms) of the last pdmpc_hdv_traffic (its four launches), pdmpc_hdv_traffic_grouped (its five),
+ * pdmpc_hdv_drive_grouped (its one) or pdmpc_hdv_drive_traffic_grouped (its six), whichever was called last */
 int pdmpc_hdv_kernel_ms(pdmpc_handle* handle, double* ms);
 
 /* Several maps on a handle, and several independent sets of HDVs and CAVs in one call.
@@ -795,6 +795,55 @@ int pdmpc_hdv_traffic_grouped(pdmpc_handle* handle, int32_t n_groups, const int3
                               const double* cav_x, const double* cav_y, const int32_t* cav_lanelet, const double* cav_tile_dx, const double* cav_tile_dy,
                               int32_t* closest_offset, int32_t* closest_index, int32_t capacity, int32_t* n_rows, int32_t* row_hdv, int32_t* set_offset,
                               int32_t* set_base, double* set_x, double* set_y, uint8_t* set_flags, uint8_t* adjacency);
+
+/* Simulated human drivers (include/pdmpc_hdv.h: "the driver model"; csrc/hdv_drive_host.hpp).  An HDV follows a route --
+ * route_lanelet[route_offset[h] .. route_offset[h + 1]): 1 .. PDMPC_HDV_ROUTE_MAX 1-based lanelet ids, each a successor of the one
+ * before it, on a route with closed[h] != 0 the first of the last too -- along the centre lines of its lanelets, and keeps a gap to the
+ * nearest vehicle ahead on the route: speed = min(v_des, max(0, (gap - gap_min) / headway)).  Its state is (r, j, u): u metres along
+ * segment j of route position r; state_seg holds r of every HDV of the call, then j of every HDV.  parameters[4] = look_ahead, gap_min,
+ * headway, lateral (PDMPC_HDV_*_DEFAULT of pdmpc_hdv.h).  One step of length dt: the gap is the smallest distance ahead, along the route
+ * within look_ahead (at most PDMPC_HDV_WINDOW_MAX segments), of a CAV (cav_x, cav_y) or of another HDV of the call at its pose BEFORE the
+ * step that lies within `lateral` of the route on the same map copy (equal tile_dx / tile_dy), +inf if there is none; then all HDVs
+ * move at once by speed * dt (the end of an open route stops an HDV there with speed 0).  Outputs: the new state, the pose (x, y and
+ * cos_yaw / sin_yaw = the direction of the segment it stands on: no libm), speed and gap.
+ * pdmpc_hdv_route_check_host: the route checks alone.  pdmpc_hdv_place_host: the state and pose start_distance[h] metres from the start
+ * of every route (the walk of the step).  pdmpc_hdv_drive_host: one step of the HDVs and CAVs of one member, no GPU.
+ * pdmpc_hdv_drive_grouped: the same step for the groups of pdmpc_hdv_traffic_grouped (parameters [4 n_groups], dt [n_groups]) on the
+ * handle's device, group g on the map of slot group_slot[g]: one staging copy, ONE launch (a wavefront per HDV), one copy back, one
+ * synchronisation; per group the bits of pdmpc_hdv_drive_host.  pdmpc_hdv_drive_traffic_grouped: that launch followed by the five of
+ * pdmpc_hdv_traffic_grouped, which read the poses it left on the device -- one staging copy, SIX launches whatever n_groups is, one copy
+ * back, one synchronisation.  Group g drives if drives[g] != 0: its x, y, cos_yaw, sin_yaw entries are outputs, like new_seg, new_u,
+ * speed and gap; a group with drives[g] == 0 needs no routes (route_offset does not move over its HDVs), leaves those entries alone
+ * and is exactly pdmpc_hdv_traffic_grouped's group.  The traffic outputs are pdmpc_hdv_traffic_grouped's.
+ * PDMPC_ERR_INVALID (pdmpc_last_error names the group, the HDV and the route position): a route that is empty, too long, leaves the
+ * map, steps to a non-successor or has no segment of positive length; a state that is not on its route; a parameter or dt that is not
+ * positive and finite; headway < dt (with headway >= dt an HDV closes at most gap - gap_min per step); a negative v_des; a start distance
+ * that is negative or at or beyond the end of an open route.  A refused call has launched nothing. */
+int pdmpc_hdv_route_check_host(int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x, const double* left_y,
+                               const double* right_x, const double* right_y, const int32_t* succ_offset, const int32_t* succ_index, const uint8_t* relationship,
+                               int32_t n_hdv, const int32_t* route_offset, const int32_t* route_lanelet, const uint8_t* closed);
+int pdmpc_hdv_place_host(int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x, const double* left_y, const double* right_x,
+                         const double* right_y, const int32_t* succ_offset, const int32_t* succ_index, const uint8_t* relationship, int32_t n_hdv,
+                         const int32_t* route_offset, const int32_t* route_lanelet, const uint8_t* closed, const double* start_distance, const double* tile_dx,
+                         const double* tile_dy, int32_t* state_seg, double* state_u, double* x, double* y, double* cos_yaw, double* sin_yaw);
+int pdmpc_hdv_drive_host(int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x, const double* left_y, const double* right_x,
+                         const double* right_y, const int32_t* succ_offset, const int32_t* succ_index, const uint8_t* relationship, int32_t n_hdv,
+                         const int32_t* route_offset, const int32_t* route_lanelet, const uint8_t* closed, const int32_t* state_seg, const double* state_u,
+                         const double* tile_dx, const double* tile_dy, const double* v_des, int32_t n_cav, const double* cav_x, const double* cav_y,
+                         const double* cav_tile_dx, const double* cav_tile_dy, const double* parameters, double dt, int32_t* new_seg, double* new_u, double* x, double* y,
+                         double* cos_yaw, double* sin_yaw, double* speed, double* gap);
+int pdmpc_hdv_drive_grouped(pdmpc_handle* handle, int32_t n_groups, const int32_t* group_slot, const int32_t* hdv_offset, const int32_t* cav_offset,
+                            const int32_t* route_offset, const int32_t* route_lanelet, const uint8_t* closed, const int32_t* state_seg, const double* state_u,
+                            const double* tile_dx, const double* tile_dy, const double* v_des, const double* cav_x, const double* cav_y, const double* cav_tile_dx,
+                            const double* cav_tile_dy, const double* parameters, const double* dt, int32_t* new_seg, double* new_u, double* x, double* y,
+                            double* cos_yaw, double* sin_yaw, double* speed, double* gap);
+int pdmpc_hdv_drive_traffic_grouped(pdmpc_handle* handle, int32_t n_groups, const int32_t* group_slot, const int32_t* hdv_offset, const int32_t* cav_offset,
+                                    const uint8_t* drives, const int32_t* route_offset, const int32_t* route_lanelet, const uint8_t* closed, const int32_t* state_seg,
+                                    const double* state_u, const double* v_des, const double* parameters, const double* dt, int32_t* new_seg, double* new_u,
+                                    double* speed, double* gap, double* x, double* y, double* cos_yaw, double* sin_yaw, const int32_t* trim, const double* tile_dx,
+                                    const double* tile_dy, const double* cav_x, const double* cav_y, const int32_t* cav_lanelet, const double* cav_tile_dx,
+                                    const double* cav_tile_dy, int32_t* closest_offset, int32_t* closest_index, int32_t capacity, int32_t* n_rows, int32_t* row_hdv,
+                                    int32_t* set_offset, int32_t* set_base, double* set_x, double* set_y, uint8_t* set_flags, uint8_t* adjacency);
 
 /* ---- the caller's side of the boundary, natively (csrc/step_controller.cpp and its stages csrc/step_*.hpp) ----
  * One MPC time step of the prioritized sequential controller around pdmpc_plan_step, without any interpreter in the loop:
@@ -874,6 +923,25 @@ int pdmpc_controller_step(pdmpc_controller* c);
 int pdmpc_controller_set_hdvs(pdmpc_controller* c, int32_t n_hdv, const pdmpc_mpa* hdv_mpa, const int32_t* succ_offset, const int32_t* succ_index,
                               const uint8_t* relationship, const double* tile_dx, const double* tile_dy);
 int pdmpc_controller_set_hdv_measurements(pdmpc_controller* c, const double* x, const double* y, const double* yaw);
+/* HDVs that move themselves (DESIGN.md 3.24 "Drivers").  set_hdv_drivers, after set_hdvs: HDV q follows the route route_lanelet[route_offset[q] ..
+ * route_offset[q + 1]) (closed[q] != 0: round and round) at up to v_des[q] with params[4] = look_ahead, gap_min, headway, lateral, from
+ * start_distance[q] metres along it; the routes are checked against the controller's map, dt is the controller's dt_seconds.  The
+ * placement is the measurement of the first built step; at every later built step (build_step, explore_build, optimal_build, every sweep
+ * build, on a group through rank 0's handle) the traffic stage first moves the HDVs one driver step against the CAVs' measured positions:
+ * with a handle ONE pdmpc_hdv_drive_traffic_grouped in the stage's batches and map slots (it counts as one call in
+ * pdmpc_sweep_last_hdv_calls), without one pdmpc_hdv_drive_host, then pdmpc_hdv_traffic_host, per member.  hdv_driver_state: state
+ * (r of every HDV, then j; u), pose (yaw = atan2(sin, cos), for read-back only), speed and gap of the last built step (speed 0 and gap
+ * +inf at the placement); any may be NULL.  set_hdv_recording: T rows of n_hdv recorded poses (row t at [t * n_hdv]); built step s (from
+ * 1) takes row min(s, T) - 1, with the cosines and sines set_hdv_measurements takes.  set_hdv_poses: measurements given as directions
+ * (cos_yaw, sin_yaw as they are, no libm): what a caller that drives the HDVs itself with pdmpc_hdv_drive_host hands over.
+ * PDMPC_ERR_INVALID: before set_hdvs; drivers and a recording exclude each other, and set_hdv_measurements / set_hdv_poses are refused
+ * with either (the message says why); a bad route (the HDV and the position are named), headway < dt, a start distance at or beyond
+ * the end of an open route. */
+int pdmpc_controller_set_hdv_drivers(pdmpc_controller* c, const int32_t* route_offset, const int32_t* route_lanelet, const uint8_t* closed, const double* start_distance,
+                                     const double* v_des, const double* params);
+int pdmpc_controller_hdv_driver_state(pdmpc_controller* c, int32_t* state_seg, double* state_u, double* x, double* y, double* yaw, double* speed, double* gap);
+int pdmpc_controller_set_hdv_recording(pdmpc_controller* c, int32_t T, const double* x, const double* y, const double* yaw);
+int pdmpc_controller_set_hdv_poses(pdmpc_controller* c, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw);
 int pdmpc_controller_hdv_info(pdmpc_controller* c, int32_t* n_hdv, const int32_t** closest_offset, const int32_t** closest_index, int32_t* n_rows,
                               const int32_t** row_hdv, const int32_t** set_offset, const double** set_x, const double** set_y, const uint8_t** set_flags,
                               const uint8_t** adjacency);

@@ -148,4 +148,180 @@ PDMPC_HD static inline int pdmpc_hdv_is_behind(const pdmpc_hdv_map* M, int id_ca
     return 0;
 }
 
+/* ---- the driver model: an HDV follows a route of lanelets and keeps a gap to the vehicle ahead ("Drivers").
+ *
+ * Not from the reference, whose Simulation plant has no HDVs (plant/Simulation.m:81-83): a car-following rule of one line,
+ *     speed = min(v_des, max(0, (gap - gap_min) / headway)),
+ * on the polyline of the route's centre lines.  One definition for the host twin (csrc/hdv.cpp), the kernel (csrc/hdv_kernel.hip:
+ * pdmpc_hdv_drive_kernel) and, operation by operation, pdmpc/hdv.py: + - * / and IEEE sqrt only, no libm, so the three give the same bits.
+ *
+ * Route: n 1-based lanelet ids, each a successor of the one before (a closed route: the first of the last too).  Its polyline is the
+ * lanelets' centre lines one after the other.  Lanelet r of the route with P points has the segments j = 0 .. P - 2 between its points
+ * and, if a lanelet follows (r < n - 1, or the route is closed), the joint j = P - 1 to the first point of the next: an ordinary
+ * segment (the lab map's lanelets miss their successors by up to 3e-5 m).  A segment of length 0 is skipped everywhere.
+ * State: (r, j, u): u metres along segment j of lanelet r.  A state stands on a segment of positive length. */
+#define PDMPC_HDV_ROUTE_MAX 64    /* lanelets of a route: the lab map's longest loop (get_reference_lanelets_loop) has 44 */
+#define PDMPC_HDV_WINDOW_MAX 64   /* segments of a look-ahead window (3 KB of LDS) */
+#define PDMPC_HDV_WALK_MAX 4096   /* segments one walk passes at most (a step's move, the placement): it stops there */
+/* parameters[4]: look_ahead, gap_min, headway, lateral.  The defaults: look ahead 2 m (4 s at the lab's 0.5 m/s); stop one vehicle
+ * length (0.22 m, the lab's vehicles) plus 0.08 m behind the reference point ahead; 1 s of headway; a vehicle counts as on the route
+ * within 0.125 m of its centre line: inside half the lab map's lane width (0.15 m), so that one on the neighbouring lane does not count. */
+#define PDMPC_HDV_LOOK_AHEAD_DEFAULT 2.0
+#define PDMPC_HDV_GAP_MIN_DEFAULT 0.3
+#define PDMPC_HDV_HEADWAY_DEFAULT 1.0
+#define PDMPC_HDV_LATERAL_DEFAULT 0.125
+
+typedef struct pdmpc_hdv_route {
+    const int32_t* id; /* [n] */
+    int32_t n, closed;
+} pdmpc_hdv_route;
+typedef struct pdmpc_hdv_drive_state {
+    int32_t r, j;
+    double u;
+} pdmpc_hdv_drive_state;
+/* a window: segment w runs from (ax, ay) along (dx, dy), len long; it starts `start` metres ahead of the HDV (segment 0: -u) */
+typedef struct pdmpc_hdv_window {
+    double ax[PDMPC_HDV_WINDOW_MAX], ay[PDMPC_HDV_WINDOW_MAX], dx[PDMPC_HDV_WINDOW_MAX], dy[PDMPC_HDV_WINDOW_MAX];
+    double len[PDMPC_HDV_WINDOW_MAX], start[PDMPC_HDV_WINDOW_MAX];
+} pdmpc_hdv_window;
+
+/* segments of lanelet r of the route */
+PDMPC_HD static inline int pdmpc_hdv_route_segments(const pdmpc_hdv_map* M, const pdmpc_hdv_route* R, int r) {
+    const int i = R->id[r] - 1;
+    return M->pt_off[i + 1] - M->pt_off[i] - 1 + (R->closed || r < R->n - 1 ? 1 : 0);
+}
+/* ... of the whole route */
+PDMPC_HD static inline int pdmpc_hdv_route_total(const pdmpc_hdv_map* M, const pdmpc_hdv_route* R) {
+    int total = 0;
+    for (int r = 0; r < R->n; ++r) total += pdmpc_hdv_route_segments(M, R, r);
+    return total;
+}
+/* segment (r, j): from (ax, ay) along (dx, dy) -> its length */
+PDMPC_HD static inline double pdmpc_hdv_route_segment(const pdmpc_hdv_map* M, const pdmpc_hdv_route* R, int r, int j, double* ax, double* ay, double* dx, double* dy) {
+    const int i = R->id[r] - 1;
+    const int a = M->pt_off[i] + j;
+    const int b = a + 1 < M->pt_off[i + 1] ? a + 1 : M->pt_off[R->id[r + 1 < R->n ? r + 1 : 0] - 1];
+    *ax = M->cx[a];
+    *ay = M->cy[a];
+    *dx = M->cx[b] - M->cx[a];
+    *dy = M->cy[b] - M->cy[a];
+    return sqrt(*dx * *dx + *dy * *dy);
+}
+/* the segment behind (r, j) -> 0 at the end of an open route ((r, j) stays) */
+PDMPC_HD static inline int pdmpc_hdv_route_next(const pdmpc_hdv_map* M, const pdmpc_hdv_route* R, int* r, int* j) {
+    int nr = *r, nj = *j + 1;
+    for (int tries = 0; tries <= R->n; ++tries) { /* (lanelets of one point without a joint have no segment) */
+        if (nj < pdmpc_hdv_route_segments(M, R, nr)) {
+            *r = nr;
+            *j = nj;
+            return 1;
+        }
+        nj = 0;
+        if (++nr == R->n) {
+            if (!R->closed) return 0;
+            nr = 0;
+        }
+    }
+    return 0;
+}
+
+/* Walk `distance` >= 0 metres forward from S over at most PDMPC_HDV_WALK_MAX segments: the sequential walk of the step and of the
+ * placement.  -> 1 if the end of an open route stopped it (S: the end of the last segment of positive length reached) */
+PDMPC_HD static inline int pdmpc_hdv_walk(const pdmpc_hdv_map* M, const pdmpc_hdv_route* R, pdmpc_hdv_drive_state* S, double distance) {
+    double ax, ay, dx, dy;
+    double len = pdmpc_hdv_route_segment(M, R, S->r, S->j, &ax, &ay, &dx, &dy);
+    double left = distance;
+    int r = S->r, j = S->j, passed = 0; /* passed: segments gone on to, of any length */
+    for (;;) {
+        const double room = len - S->u;
+        if (left < room) {
+            S->u = S->u + left;
+            return 0;
+        }
+        double next = 0.0; /* the next segment of positive length */
+        while (next == 0.0) {
+            if (passed == PDMPC_HDV_WALK_MAX) { /* the cap: it stands at the end of its segment */
+                S->u = len;
+                return 0;
+            }
+            if (!pdmpc_hdv_route_next(M, R, &r, &j)) { /* the end of an open route */
+                S->u = len;
+                return 1;
+            }
+            ++passed;
+            next = pdmpc_hdv_route_segment(M, R, r, j, &ax, &ay, &dx, &dy);
+        }
+        left = left - room;
+        S->r = r;
+        S->j = j;
+        S->u = 0.0;
+        len = next;
+    }
+}
+
+/* the pose of a state on the map copy moved by (tile_dx, tile_dy): the point, and (dx / len, dy / len) of the segment it stands on */
+PDMPC_HD static inline void pdmpc_hdv_state_pose(const pdmpc_hdv_map* M, const pdmpc_hdv_route* R, const pdmpc_hdv_drive_state* S, double tile_dx, double tile_dy, double* x,
+                                                 double* y, double* cos_yaw, double* sin_yaw) {
+    double ax, ay, dx, dy;
+    const double len = pdmpc_hdv_route_segment(M, R, S->r, S->j, &ax, &ay, &dx, &dy);
+    const double t = S->u / len;
+    *x = ax + t * dx + tile_dx;
+    *y = ay + t * dy + tile_dy;
+    *cos_yaw = dx / len;
+    *sin_yaw = dy / len;
+}
+
+/* The window of S: its own segment first, then the segments ahead until the running distance -- ONE sum in segment order, from -u --
+ * reaches look_ahead, PDMPC_HDV_WINDOW_MAX segments are listed, or an open route ends -> the number of segments (>= 1) */
+PDMPC_HD static inline int pdmpc_hdv_build_window(const pdmpc_hdv_map* M, const pdmpc_hdv_route* R, const pdmpc_hdv_drive_state* S, double look_ahead, pdmpc_hdv_window* W) {
+    int r = S->r, j = S->j, n = 0;
+    double run = -S->u;
+    for (int passed = 0; passed < PDMPC_HDV_WALK_MAX; ++passed) {
+        double ax, ay, dx, dy;
+        const double len = pdmpc_hdv_route_segment(M, R, r, j, &ax, &ay, &dx, &dy);
+        if (len != 0.0) {
+            W->ax[n] = ax;
+            W->ay[n] = ay;
+            W->dx[n] = dx;
+            W->dy[n] = dy;
+            W->len[n] = len;
+            W->start[n] = run;
+            run = run + len;
+            if (++n == PDMPC_HDV_WINDOW_MAX || run >= look_ahead) break;
+        }
+        if (!pdmpc_hdv_route_next(M, R, &r, &j)) break;
+    }
+    return n;
+}
+
+/* One (other vehicle, window segment) pair: the vehicle at (px, py) in map coordinates projected on segment w, t clamped to
+ * [0, 1] ([u / len, 1] on segment 0) -> the distance ahead along the route if it lies within `lateral` of the foot point and ahead,
+ * else +inf.  A NaN fails every comparison: no candidate. */
+PDMPC_HD static inline double pdmpc_hdv_gap_item(const pdmpc_hdv_window* W, int w, double u, double px, double py, double lateral) {
+    const double dx = W->dx[w], dy = W->dy[w], len = W->len[w];
+    const double qx = px - W->ax[w], qy = py - W->ay[w];
+    const double lo = w == 0 ? u / len : 0.0;
+    double t = (qx * dx + qy * dy) / (dx * dx + dy * dy);
+    if (!(t >= lo)) t = lo;
+    if (t > 1.0) t = 1.0;
+    const double ex = qx - t * dx, ey = qy - t * dy;
+    const double off = sqrt(ex * ex + ey * ey);
+    const double ahead = W->start[w] + t * len;
+    return off <= lateral && ahead > 0.0 ? ahead : (double)INFINITY;
+}
+
+/* speed = min(v_des, max(0, (gap - gap_min) / headway)) */
+PDMPC_HD static inline double pdmpc_hdv_speed(double gap, double v_des, double gap_min, double headway) {
+    double s = (gap - gap_min) / headway;
+    if (!(s > 0.0)) s = 0.0;
+    return s > v_des ? v_des : s;
+}
+
+/* The move of one step once the gap is known: S advances by speed dt -> the speed (0 where an open route ended) */
+PDMPC_HD static inline double pdmpc_hdv_move(const pdmpc_hdv_map* M, const pdmpc_hdv_route* R, pdmpc_hdv_drive_state* S, double gap, double v_des, const double* parameters,
+                                             double dt) {
+    const double speed = pdmpc_hdv_speed(gap, v_des, parameters[1], parameters[2]);
+    return pdmpc_hdv_walk(M, R, S, speed * dt) ? 0.0 : speed;
+}
+
 #endif /* PDMPC_HDV_H */

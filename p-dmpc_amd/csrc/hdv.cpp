@@ -5,6 +5,7 @@
 #include <cstring>
 #include <string>
 
+#include "hdv_drive_host.hpp"
 #include "hdv_grouped_host.hpp"
 #include "hdv_host.hpp"
 
@@ -124,6 +125,89 @@ int pdmpc_hdv_traffic_host(int32_t n_lanelets, const int32_t* left_offset, const
         std::memcpy(set_y + set_offset[o], ry[o].data(), ry[o].size() * sizeof(double));
     }
     if (set_flags) std::memcpy(set_flags, fl.data(), fl.size());
+    return PDMPC_OK;
+}
+
+// ---- the driver model (include/pdmpc_hdv.h; hdv_drive_host.hpp)
+namespace {
+// the map of a driver call, and the routes against it
+int drive_map(const char* who, HdvMapData& map, int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x, const double* left_y,
+              const double* right_x, const double* right_y, const int32_t* succ_offset, const int32_t* succ_index, const uint8_t* relationship, int32_t n_hdv,
+              const int32_t* route_offset, const int32_t* route_lanelet, const uint8_t* closed) {
+    const char* why = nullptr;
+    std::string text;
+    int rc = map.points(n_lanelets, left_offset, right_offset, left_x, left_y, right_x, right_y, &why);
+    if (!rc) rc = map.graph(succ_offset, succ_index, relationship, &why);
+    if (rc) text = why;
+    if (!rc && (!route_offset || route_offset[0] != 0)) rc = PDMPC_ERR_INVALID, text = "route offsets that do not start at 0";
+    if (!rc) rc = hdv_check_routes(map, n_hdv, route_offset, route_lanelet, closed, &text);
+    if (rc) pdmpc_set_last_error((std::string(who) + ": " + text).c_str());
+    return rc;
+}
+}  // namespace
+
+int pdmpc_hdv_route_check_host(int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x, const double* left_y,
+                               const double* right_x, const double* right_y, const int32_t* succ_offset, const int32_t* succ_index, const uint8_t* relationship,
+                               int32_t n_hdv, const int32_t* route_offset, const int32_t* route_lanelet, const uint8_t* closed) {
+    HdvMapData map;
+    return drive_map("pdmpc_hdv_route_check_host", map, n_lanelets, left_offset, right_offset, left_x, left_y, right_x, right_y, succ_offset, succ_index, relationship, n_hdv,
+                     route_offset, route_lanelet, closed);
+}
+
+int pdmpc_hdv_place_host(int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x, const double* left_y, const double* right_x,
+                         const double* right_y, const int32_t* succ_offset, const int32_t* succ_index, const uint8_t* relationship, int32_t n_hdv,
+                         const int32_t* route_offset, const int32_t* route_lanelet, const uint8_t* closed, const double* start_distance, const double* tile_dx,
+                         const double* tile_dy, int32_t* state_seg, double* state_u, double* x, double* y, double* cos_yaw, double* sin_yaw) {
+    const char* who = "pdmpc_hdv_place_host";
+    HdvMapData map;
+    if (const int rc = drive_map(who, map, n_lanelets, left_offset, right_offset, left_x, left_y, right_x, right_y, succ_offset, succ_index, relationship, n_hdv, route_offset,
+                                 route_lanelet, closed))
+        return rc;
+    if (n_hdv && (!start_distance || !tile_dx || !tile_dy || !state_seg || !state_u || !x || !y || !cos_yaw || !sin_yaw)) {
+        pdmpc_set_last_error((std::string(who) + ": null argument").c_str());
+        return PDMPC_ERR_INVALID;
+    }
+    const pdmpc_hdv_map M = map.view();
+    for (int h = 0; h < n_hdv; ++h) {
+        const pdmpc_hdv_route R = hdv_route(route_offset, route_lanelet, closed, h);
+        pdmpc_hdv_drive_state S;
+        std::string why;
+        if (const int rc = hdv_place(M, R, start_distance[h], &S, &why)) {
+            pdmpc_set_last_error((std::string(who) + ": HDV " + std::to_string(h) + ": " + why).c_str());
+            return rc;
+        }
+        state_seg[h] = S.r;
+        state_seg[n_hdv + h] = S.j;
+        state_u[h] = S.u;
+        pdmpc_hdv_state_pose(&M, &R, &S, tile_dx[h], tile_dy[h], &x[h], &y[h], &cos_yaw[h], &sin_yaw[h]);
+    }
+    return PDMPC_OK;
+}
+
+int pdmpc_hdv_drive_host(int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x, const double* left_y, const double* right_x,
+                         const double* right_y, const int32_t* succ_offset, const int32_t* succ_index, const uint8_t* relationship, int32_t n_hdv,
+                         const int32_t* route_offset, const int32_t* route_lanelet, const uint8_t* closed, const int32_t* state_seg, const double* state_u,
+                         const double* tile_dx, const double* tile_dy, const double* v_des, int32_t n_cav, const double* cav_x, const double* cav_y,
+                         const double* cav_tile_dx, const double* cav_tile_dy, const double* parameters, double dt, int32_t* new_seg, double* new_u, double* x, double* y,
+                         double* cos_yaw, double* sin_yaw, double* speed, double* gap) {
+    const char* who = "pdmpc_hdv_drive_host";
+    HdvMapData map;
+    if (const int rc = drive_map(who, map, n_lanelets, left_offset, right_offset, left_x, left_y, right_x, right_y, succ_offset, succ_index, relationship, n_hdv, route_offset,
+                                 route_lanelet, closed))
+        return rc;
+    std::string why = "null argument";
+    int rc = (n_hdv && (!tile_dx || !tile_dy || !new_seg || !new_u || !x || !y || !cos_yaw || !sin_yaw || !speed || !gap)) || n_cav < 0 ||
+                     (n_cav && (!cav_x || !cav_y || !cav_tile_dx || !cav_tile_dy))
+                 ? PDMPC_ERR_INVALID
+                 : PDMPC_OK;
+    if (!rc) rc = hdv_check_states(map, n_hdv, route_offset, route_lanelet, closed, state_seg, state_seg ? state_seg + n_hdv : nullptr, state_u, &why);
+    if (!rc) rc = hdv_check_drive(parameters, dt, n_hdv, v_des, &why);
+    if (rc) {
+        pdmpc_set_last_error((std::string(who) + ": " + why).c_str());
+        return rc;
+    }
+    hdv_drive_member(map.view(), n_hdv, route_offset, route_lanelet, closed, state_seg, state_u, tile_dx, tile_dy, v_des, n_cav, cav_x, cav_y, cav_tile_dx, cav_tile_dy,
+                     parameters, dt, new_seg, new_u, x, y, cos_yaw, sin_yaw, speed, gap);
     return PDMPC_OK;
 }
 

@@ -21,6 +21,9 @@
 //              the rows and the vertex base of every group, and the status words
 //   copy       one wavefront per slot that exists: its offset, flags and row, and its vertices, none at or beyond the capacity
 // so a slot's count is read twice, not once per slot behind it.
+//
+// The drive pass (pdmpc_hdv_drive_kernel, further down: the driver model of include/pdmpc_hdv.h) moves the HDVs of a grouped call one step
+// along their routes; alone it is pdmpc_hdv_drive_grouped, in front of the five passes pdmpc_hdv_drive_traffic_grouped: six launches.
 #include <hip/hip_runtime.h>
 
 #include "../../include/pdmpc_geometry.h"
@@ -332,6 +335,78 @@ extern "C" __global__ __launch_bounds__(PDMPC_HDV_WAVE) void pdmpc_hdv_adjacency
     G.a.adjacency[item] = (uint8_t)hdv_adjacency_item(G.a, &G.maps[grp.slot].map, grp.c0 + v, grp.h0 + h);
 }
 
+// ---- the drive pass (include/pdmpc_hdv.h: the driver model).  One wavefront per HDV h of the call.  The lanes compute where the HDVs of
+// h's group stand BEFORE the step (from the old states: nothing this launch writes is read by it); lane 0 lists the window in LDS; the
+// lanes stride over the (other vehicle, window segment) items -- the group's CAVs first, then its other HDVs -- and the smallest
+// distance ahead is taken across the wavefront (a minimum of doubles without NaN: any order gives the same bits); lane 0 moves the HDV
+// and writes its state, speed, gap and pose.  hdv_drive_host.hpp: hdv_drive_member is the same step on the host.
+extern "C" __global__ __launch_bounds__(PDMPC_HDV_WAVE) void pdmpc_hdv_drive_kernel(const HdvDriveArgs D) {
+    __shared__ pdmpc_hdv_window W;
+    __shared__ double ox[PDMPC_HDV_MAX_VEHICLES], oy[PDMPC_HDV_MAX_VEHICLES];
+    __shared__ int nw_shared;
+    const int h = (int)blockIdx.x, lane = (int)threadIdx.x, n = D.n_hdv, nc = D.n_cav;
+    const int g = D.group_of[h];
+    if (!D.drives[g]) return;  // (the whole wavefront)
+    const HdvGroup grp = D.groups[g];
+    const pdmpc_hdv_map* M = &D.maps[grp.slot].map;
+    const double* P = D.params + (size_t)g * PDMPC_HDV_DRIVE_PARAMS;
+    const double tdx = D.in[4 * n + h], tdy = D.in[5 * n + h];
+    for (int q = lane; q < grp.n_hdv; q += PDMPC_HDV_WAVE) {  // (n_hdv <= PDMPC_HDV_MAX_VEHICLES: checked by the call)
+        const int o = grp.h0 + q;
+        const pdmpc_hdv_route R{D.route_id + D.route_off[o], D.route_off[o + 1] - D.route_off[o], D.closed[o] ? 1 : 0};
+        const pdmpc_hdv_drive_state S{D.state_seg[o], D.state_seg[n + o], D.state_u[o]};
+        double c, s;
+        pdmpc_hdv_state_pose(M, &R, &S, D.in[4 * n + o], D.in[5 * n + o], &ox[q], &oy[q], &c, &s);
+    }
+    const pdmpc_hdv_route R{D.route_id + D.route_off[h], D.route_off[h + 1] - D.route_off[h], D.closed[h] ? 1 : 0};
+    pdmpc_hdv_drive_state S{D.state_seg[h], D.state_seg[n + h], D.state_u[h]};
+    if (lane == 0) nw_shared = pdmpc_hdv_build_window(M, &R, &S, P[0], &W);
+    __syncthreads();
+    const int nw = nw_shared, items = (grp.n_cav + grp.n_hdv) * nw;  // (<= (2^20 + 64) 64 < 2^31)
+    double best = (double)INFINITY;
+    for (int it = lane; it < items; it += PDMPC_HDV_WAVE) {
+        const int o = it / nw, w = it - o * nw;
+        double px, py, odx, ody;
+        if (o < grp.n_cav) {
+            const int v = grp.c0 + o;
+            px = D.cav[v];
+            py = D.cav[nc + v];
+            odx = D.cav[2 * nc + v];
+            ody = D.cav[3 * nc + v];
+        } else {
+            const int q = o - grp.n_cav;
+            if (grp.h0 + q == h) continue;
+            px = ox[q];
+            py = oy[q];
+            odx = D.in[4 * n + grp.h0 + q];
+            ody = D.in[5 * n + grp.h0 + q];
+        }
+        if (!(odx == tdx && ody == tdy)) continue;
+        const double ahead = pdmpc_hdv_gap_item(&W, w, S.u, px - tdx, py - tdy, P[3]);
+        if (ahead < best) best = ahead;
+    }
+    for (int o = PDMPC_HDV_WAVE / 2; o > 0; o >>= 1) {
+        const double other = __shfl_xor(best, o);
+        if (other < best) best = other;
+    }
+    if (lane != 0) return;
+    D.gap[h] = best;
+    D.speed[h] = pdmpc_hdv_move(M, &R, &S, best, D.v_des[h], P, P[4]);
+    D.new_seg[h] = S.r;
+    D.new_seg[n + h] = S.j;
+    D.new_u[h] = S.u;
+    double x, y, c, s;
+    pdmpc_hdv_state_pose(M, &R, &S, tdx, tdy, &x, &y, &c, &s);
+    const double pose[4] = {x, y, c, s};
+    for (int q = 0; q < 4; ++q) D.in[q * n + h] = D.pose[q * n + h] = pose[q];
+}
+
+extern "C" int pdmpc_launch_hdv_drive(const HdvDriveArgs* args, void* stream) {
+    if (args->n_hdv <= 0) return 0;
+    hipLaunchKernelGGL(pdmpc_hdv_drive_kernel, dim3((uint32_t)args->n_hdv), dim3(PDMPC_HDV_WAVE), 0, (hipStream_t)stream, *args);
+    return (int)hipGetLastError();
+}
+
 extern "C" int pdmpc_launch_hdv_traffic(const HdvArgs* args, void* stream) {
     const int n = args->n_hdv;
     if (n <= 0) return 0;
@@ -359,4 +434,9 @@ extern "C" int pdmpc_launch_hdv_traffic_grouped(const HdvGroupedArgs* args, void
         hipLaunchKernelGGL(pdmpc_hdv_adjacency_grouped_kernel, dim3(blocks), dim3(PDMPC_HDV_WAVE), 0, (hipStream_t)stream, *args);
     }
     return (int)hipGetLastError();
+}
+
+extern "C" int pdmpc_launch_hdv_drive_traffic_grouped(const HdvDriveTrafficArgs* args, void* stream) {
+    if (const int rc = pdmpc_launch_hdv_drive(&args->d, stream)) return rc;
+    return pdmpc_launch_hdv_traffic_grouped(&args->g, stream);
 }

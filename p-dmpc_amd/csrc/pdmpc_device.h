@@ -584,6 +584,33 @@ struct HdvGroupedArgs {
     int32_t* n_rows;            // [n_groups] -1: an HDV of the group ran over its lists (the group writes nothing else)
     int32_t* set_base;          // [n_groups + 1]
 };
+// The drive pass in front of them (pdmpc_hdv_drive_kernel; include/pdmpc_hdv.h: the driver model): one wavefront per HDV of the call moves
+// it one step along its route.  It reads the old states and the CAVs, and writes the new state, speed and gap and -- where the passes
+// behind it read them -- the new pose into `in`.  The HDVs of a group that does not drive (drives[g] == 0) keep the poses staged in `in`.
+#define PDMPC_HDV_DRIVE_PARAMS 5      // per group: look_ahead, gap_min, headway, lateral, dt
+struct HdvDriveArgs {
+    const HdvMapRecord* maps;   // [PDMPC_HDV_MAP_SLOTS]
+    const HdvGroup* groups;     // [n_groups]
+    const int32_t* group_of;    // [n_hdv]
+    const uint8_t* drives;      // [n_groups]
+    int32_t n_hdv, n_cav;       // of all groups
+    const int32_t* route_off;   // [n_hdv + 1]
+    const int32_t* route_id;    // 1-based lanelet ids, route after route
+    const uint8_t* closed;      // [n_hdv]
+    const int32_t* state_seg;   // [2 n_hdv]: r of every HDV, then j
+    const double* state_u;      // [n_hdv]
+    const double* v_des;        // [n_hdv]
+    const double* params;       // [PDMPC_HDV_DRIVE_PARAMS n_groups]
+    const double* cav;          // HdvArgs::cav
+    double* in;                 // HdvArgs::in: tile_dx / tile_dy are read, x, y, cos(yaw), sin(yaw) written
+    int32_t* new_seg;           // [2 n_hdv]
+    double *new_u, *speed, *gap;  // [n_hdv] each
+    double* pose;               // [4 n_hdv]: the new x, y, cos(yaw), sin(yaw) once more, where the call reads them back
+};
+struct HdvDriveTrafficArgs {
+    HdvDriveArgs d;
+    HdvGroupedArgs g;
+};
 
 // The choice among the plans of a batch (choice_kernel.hip; pdmpc_choice in include/pdmpc.h) on the result records
 // where the search left them.  The lists are the caller's with the slots mapped to record slots and checked on the host (api.cpp:
@@ -630,6 +657,9 @@ int pdmpc_fca_check_groups(int32_t n_groups, const pdmpc_fca_group* groups, int3
 int pdmpc_launch_hdv_traffic(const HdvArgs* args, void* stream);
 // ... of the groups of a grouped call: closest, lane, scan, copy and adjacency pass (a.n_hdv > 0)
 int pdmpc_launch_hdv_traffic_grouped(const HdvGroupedArgs* args, void* stream);
+// ... the drive pass alone (n_hdv > 0), and in front of the five passes of the grouped call: six launches
+int pdmpc_launch_hdv_drive(const HdvDriveArgs* args, void* stream);
+int pdmpc_launch_hdv_drive_traffic_grouped(const HdvDriveTrafficArgs* args, void* stream);
 // reachable_kernel.hip: the two passes of the reachable-set coupler on the handle's stream
 int pdmpc_launch_reachable_coupling(const ReachArgs* args, void* stream);
 int pdmpc_launch_reachable_coupling_grouped(const ReachArgs* args, void* stream);

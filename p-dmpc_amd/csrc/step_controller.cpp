@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/pdmpc.h"
+#include "hdv_drive_host.hpp"    // the checks of the HDV drivers' parameters (host only)
 #include "hdv_grouped_host.hpp"  // the batches of the HDV traffic stage (host only)
 #include "step_types.hpp"  // the stages, in their order
 #include "step_inputs.hpp"
@@ -356,10 +357,61 @@ int hdv_traffic_on_host(pdmpc_controller* c) {
     return PDMPC_OK;
 }
 
+// the yaw of the driven poses, for read-back only (the traffic passes read cos and sin as the driver step gave them)
+void hdv_driven_yaw(HdvTraffic& H) {
+    H.yaw.resize((size_t)H.n);
+    for (int q = 0; q < H.n; ++q) H.yaw[(size_t)q] = std::atan2(H.sin_yaw[(size_t)q], H.cos_yaw[(size_t)q]);
+}
+
+// What a member's HDVs are measured as at this built step.  A recording: its next row.  Drivers: *drives = 1 if they move this step
+// (every built step but the first after pdmpc_controller_set_hdv_drivers, whose measurement is the placement).
+void hdv_begin_build(pdmpc_controller* c, bool* drives) {
+    HdvTraffic& H = c->hdv;
+    *drives = false;
+    if (H.rec_T > 0) {
+        H.rec_builds += 1;
+        const size_t row = (size_t)(std::min(H.rec_builds, H.rec_T) - 1) * H.n;
+        H.x.assign(H.rec_x.begin() + row, H.rec_x.begin() + row + H.n);
+        H.y.assign(H.rec_y.begin() + row, H.rec_y.begin() + row + H.n);
+        H.yaw.assign(H.rec_yaw.begin() + row, H.rec_yaw.begin() + row + H.n);
+        H.cos_yaw.resize((size_t)H.n);
+        H.sin_yaw.resize((size_t)H.n);
+        for (int q = 0; q < H.n; ++q) {
+            H.cos_yaw[(size_t)q] = std::cos(H.yaw[(size_t)q]);
+            H.sin_yaw[(size_t)q] = std::sin(H.yaw[(size_t)q]);
+        }
+        H.measured = true;
+    }
+    if (H.driven) {
+        H.driven_builds += 1;
+        *drives = H.driven_builds > 1;
+    }
+}
+
+// the driver step of one member on the host (pdmpc_hdv_drive_host), in front of its traffic call
+int hdv_drive_on_host(pdmpc_controller* c) {
+    HdvTraffic& H = c->hdv;
+    const int rc = pdmpc_hdv_drive_host((int32_t)H.lan_off.size() - 1, H.lan_off.data(), H.lan_off.data(), H.left_x.data(), H.left_y.data(), H.right_x.data(), H.right_y.data(),
+                                        H.succ_off.data(), H.succ_idx.data(), H.rel.data(), H.n, H.route_off.data(), H.route_id.data(), H.route_closed.data(), H.seg.data(),
+                                        H.u.data(), H.tile_dx.data(), H.tile_dy.data(), H.v_des.data(), c->sc.n, c->tr.mx.data(), c->tr.my.data(), H.cav_tile_dx.data(),
+                                        H.cav_tile_dy.data(), H.drive_params, c->sc.cfg.dt_seconds, H.new_seg.data(), H.new_u.data(), H.x.data(), H.y.data(), H.cos_yaw.data(),
+                                        H.sin_yaw.data(), H.speed.data(), H.gap.data());
+    if (rc) return cfail(c, rc, std::string("pdmpc_hdv_drive_host: ") + pdmpc_last_error());
+    H.seg.swap(H.new_seg);
+    H.u.swap(H.new_u);
+    hdv_driven_yaw(H);
+    return PDMPC_OK;
+}
+
 // the members of batch B (their maps are in the slots B.slot) as the groups of one call, and every member's blocks back into its own
 // arrays, as its own call leaves them.  The capacity retry is here, once: the room is the last total and a quarter.
-int hdv_grouped_call(pdmpc_handle* h, pdmpc_controller* const* members, const HdvBatch& B, PrepScratch::Hdv& C) {
+int hdv_grouped_call(pdmpc_handle* h, pdmpc_controller* const* members, const HdvBatch& B, PrepScratch::Hdv& C, const std::vector<uint8_t>& drives_of) {
     const int G = (int)B.members.size(), Hp = members[B.members[0]]->sc.Hp;
+    bool any_drives = false;
+    for (auto* v : {&C.drives, &C.route_closed}) v->clear();
+    for (auto* v : {&C.route_id, &C.seg_r, &C.seg_j}) v->clear();
+    for (auto* v : {&C.u, &C.v_des, &C.params, &C.dt}) v->clear();
+    C.route_off.assign(1, 0);
     for (auto* v : {&C.slot, &C.trim, &C.cav_lanelet}) v->clear();
     for (auto* v : {&C.x, &C.y, &C.cos_yaw, &C.sin_yaw, &C.tile_dx, &C.tile_dy, &C.cav_x, &C.cav_y, &C.cav_tile_dx, &C.cav_tile_dy}) v->clear();
     C.hdv_offset.assign(1, 0);
@@ -384,7 +436,29 @@ int hdv_grouped_call(pdmpc_handle* h, pdmpc_controller* const* members, const Hd
         append(C.cav_tile_dy, H.cav_tile_dy, nc);
         C.hdv_offset.push_back((int32_t)C.x.size());
         C.cav_offset.push_back((int32_t)C.cav_x.size());
+        // the drive pass: a member that does not move this step has no routes (the offsets do not move over its HDVs)
+        const bool drives = drives_of[(size_t)B.members[(size_t)g]] != 0;
+        any_drives = any_drives || drives;
+        C.drives.push_back(drives ? 1 : 0);
+        for (size_t q = 0; q < nh; ++q) {
+            if (drives) C.route_id.insert(C.route_id.end(), H.route_id.begin() + H.route_off[q], H.route_id.begin() + H.route_off[q + 1]);
+            C.route_off.push_back((int32_t)C.route_id.size());
+            C.route_closed.push_back(drives ? H.route_closed[q] : 0);
+            C.seg_r.push_back(drives ? H.seg[q] : 0);
+            C.seg_j.push_back(drives ? H.seg[nh + q] : 0);
+            C.u.push_back(drives ? H.u[q] : 0.0);
+            C.v_des.push_back(drives ? H.v_des[q] : 0.0);
+        }
+        for (int q = 0; q < 4; ++q) C.params.push_back(drives ? H.drive_params[q] : 1.0);
+        C.dt.push_back(c->sc.cfg.dt_seconds);
     }
+    const size_t n_all = C.x.size();
+    C.seg = C.seg_r;
+    C.seg.insert(C.seg.end(), C.seg_j.begin(), C.seg_j.end());
+    C.seg.push_back(0);
+    C.route_id.push_back(0);
+    C.new_seg.assign(2 * n_all + 1, 0);
+    for (auto* v : {&C.new_u, &C.speed, &C.gap}) v->assign(n_all + 1, 0.0);
     for (auto* v : {&C.closest_at, &C.list_at, &C.set_offset_at, &C.set_at}) v->assign((size_t)G + 1, 0);
     C.adjacency_at.assign((size_t)G + 1, 0);
     if (const int rc = pdmpc_hdv_grouped_layout_host(G, C.hdv_offset.data(), C.cav_offset.data(), Hp, C.closest_at.data(), C.list_at.data(), C.set_offset_at.data(), C.set_at.data(),
@@ -403,6 +477,13 @@ int hdv_grouped_call(pdmpc_handle* h, pdmpc_controller* const* members, const Hd
         C.set_y.resize(4096);
     }
     auto call = [&]() {
+        if (any_drives)  // ONE call: the drive launch in front of the five (x, y, cos_yaw, sin_yaw of the members that drive are written)
+            return pdmpc_hdv_drive_traffic_grouped(h, G, C.slot.data(), C.hdv_offset.data(), C.cav_offset.data(), C.drives.data(), C.route_off.data(), C.route_id.data(),
+                                                   C.route_closed.data(), C.seg.data(), C.u.data(), C.v_des.data(), C.params.data(), C.dt.data(), C.new_seg.data(),
+                                                   C.new_u.data(), C.speed.data(), C.gap.data(), C.x.data(), C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(), C.trim.data(),
+                                                   C.tile_dx.data(), C.tile_dy.data(), C.cav_x.data(), C.cav_y.data(), C.cav_lanelet.data(), C.cav_tile_dx.data(),
+                                                   C.cav_tile_dy.data(), C.closest_off.data(), C.closest_idx.data(), (int32_t)C.set_x.size(), C.n_rows.data(), C.row_hdv.data(),
+                                                   C.set_off.data(), C.set_base.data(), C.set_x.data(), C.set_y.data(), C.set_flags.data(), C.adjacency.data());
         return pdmpc_hdv_traffic_grouped(h, G, C.slot.data(), C.hdv_offset.data(), C.cav_offset.data(), C.x.data(), C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(), C.trim.data(),
                                          C.tile_dx.data(), C.tile_dy.data(), C.cav_x.data(), C.cav_y.data(), C.cav_lanelet.data(), C.cav_tile_dx.data(), C.cav_tile_dy.data(),
                                          C.closest_off.data(), C.closest_idx.data(), (int32_t)C.set_x.size(), C.n_rows.data(), C.row_hdv.data(), C.set_off.data(), C.set_base.data(),
@@ -419,6 +500,21 @@ int hdv_grouped_call(pdmpc_handle* h, pdmpc_controller* const* members, const Hd
     for (int g = 0; g < G; ++g) {
         pdmpc_controller* c = members[B.members[(size_t)g]];
         HdvTraffic& H = c->hdv;
+        if (C.drives[(size_t)g]) {  // where the drive pass left the member's HDVs
+            const size_t h0 = (size_t)C.hdv_offset[(size_t)g], nh = (size_t)H.n;
+            for (size_t q = 0; q < nh; ++q) {
+                H.seg[q] = C.new_seg[h0 + q];
+                H.seg[nh + q] = C.new_seg[n_all + h0 + q];
+                H.u[q] = C.new_u[h0 + q];
+                H.speed[q] = C.speed[h0 + q];
+                H.gap[q] = C.gap[h0 + q];
+                H.x[q] = C.x[h0 + q];
+                H.y[q] = C.y[h0 + q];
+                H.cos_yaw[q] = C.cos_yaw[h0 + q];
+                H.sin_yaw[q] = C.sin_yaw[h0 + q];
+            }
+            hdv_driven_yaw(H);
+        }
         hdv_size_results(c);
         const size_t rows = (size_t)C.n_rows[(size_t)g], sets = rows * Hp, nh = (size_t)H.n;
         const int32_t* so = C.set_off.data() + C.set_offset_at[(size_t)g];
@@ -444,12 +540,20 @@ int hdv_grouped_call(pdmpc_handle* h, pdmpc_controller* const* members, const Hd
 int hdv_traffic_stage(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, PrepScratch& S) {
     S.hdv_calls[0] = S.hdv_calls[1] = 0;
     std::vector<int32_t> n_hdv(M, 0);
+    std::vector<uint8_t> drives(M, 0);
     for (size_t m = 0; m < M; ++m) {
         pdmpc_controller* c = members[m];
         n_hdv[m] = c->hdv.n;
+        if (c->hdv.n) {
+            bool d = false;
+            hdv_begin_build(c, &d);
+            drives[m] = d ? 1 : 0;
+        }
         if (c->hdv.n && !c->hdv.measured) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_measurements before the first step with HDVs");
         if (c->hdv.n && !h) {
             S.hdv_calls[0] += 1;
+            if (drives[m])
+                if (const int rc = hdv_drive_on_host(c)) return rc;
             if (const int rc = hdv_traffic_on_host(c)) return rc;
         }
     }
@@ -490,7 +594,7 @@ int hdv_traffic_stage(pdmpc_handle* h, pdmpc_controller* const* members, size_t 
             H.map_generation = generation[H.map_slot];
         }
         S.hdv_calls[0] += 1;
-        if (const int rc = hdv_grouped_call(h, members, B, S.hdv)) return rc;
+        if (const int rc = hdv_grouped_call(h, members, B, S.hdv, drives)) return rc;
     }
     return PDMPC_OK;
 }
@@ -887,10 +991,97 @@ int pdmpc_controller_set_hdvs(pdmpc_controller* c, int32_t n_hdv, const pdmpc_mp
     return PDMPC_OK;
 }
 
+int pdmpc_controller_set_hdv_drivers(pdmpc_controller* c, const int32_t* route_offset, const int32_t* route_lanelet, const uint8_t* closed, const double* start_distance,
+                                     const double* v_des, const double* params) {
+    const std::string who = "pdmpc_controller_set_hdv_drivers: ";
+    if (!c || !route_offset || !route_lanelet || !closed || !start_distance || !v_des || !params) return cfail(c, PDMPC_ERR_INVALID, who + "null argument");
+    HdvTraffic& H = c->hdv;
+    if (H.n == 0) return cfail(c, PDMPC_ERR_INVALID, who + "before pdmpc_controller_set_hdvs");
+    if (H.rec_T > 0) return cfail(c, PDMPC_ERR_INVALID, who + "the HDVs replay a recording (pdmpc_controller_set_hdv_recording)");
+    if (route_offset[0] != 0) return cfail(c, PDMPC_ERR_INVALID, who + "route offsets that do not start at 0");
+    for (int q = 0; q < H.n; ++q)
+        if (route_offset[q + 1] < route_offset[q]) return cfail(c, PDMPC_ERR_INVALID, who + "route offsets decrease");
+    std::string why;
+    if (const int rc = hdv_check_drive(params, c->sc.cfg.dt_seconds, H.n, v_des, &why)) return cfail(c, rc, who + why);
+    // the routes against the controller's map, and the placement: the "measurement" of the first step
+    std::vector<int32_t> seg((size_t)2 * H.n);
+    std::vector<double> u((size_t)H.n), x((size_t)H.n), y((size_t)H.n), cs((size_t)H.n), sn((size_t)H.n);
+    const int rc = pdmpc_hdv_place_host((int32_t)H.lan_off.size() - 1, H.lan_off.data(), H.lan_off.data(), H.left_x.data(), H.left_y.data(), H.right_x.data(), H.right_y.data(),
+                                        H.succ_off.data(), H.succ_idx.data(), H.rel.data(), H.n, route_offset, route_lanelet, closed, start_distance, H.tile_dx.data(),
+                                        H.tile_dy.data(), seg.data(), u.data(), x.data(), y.data(), cs.data(), sn.data());
+    if (rc) return cfail(c, rc, who + pdmpc_last_error());
+    H.route_off.assign(route_offset, route_offset + H.n + 1);
+    H.route_id.assign(route_lanelet, route_lanelet + route_offset[H.n]);
+    H.route_id.push_back(0);
+    H.route_closed.assign(closed, closed + H.n);
+    H.v_des.assign(v_des, v_des + H.n);
+    std::copy(params, params + 4, H.drive_params);
+    H.seg = seg;
+    H.u = u;
+    H.new_seg.assign((size_t)2 * H.n, 0);
+    H.new_u.assign((size_t)H.n, 0.0);
+    H.speed.assign((size_t)H.n, 0.0);
+    H.gap.assign((size_t)H.n, (double)INFINITY);
+    H.x = x;
+    H.y = y;
+    H.cos_yaw = cs;
+    H.sin_yaw = sn;
+    hdv_driven_yaw(H);
+    H.driven = true;
+    H.driven_builds = 0;
+    H.measured = true;
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_hdv_driver_state(pdmpc_controller* c, int32_t* state_seg, double* state_u, double* x, double* y, double* yaw, double* speed, double* gap) {
+    if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
+    const HdvTraffic& H = c->hdv;
+    if (!H.driven) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_hdv_driver_state before pdmpc_controller_set_hdv_drivers");
+    if (state_seg) std::copy(H.seg.begin(), H.seg.end(), state_seg);
+    if (state_u) std::copy(H.u.begin(), H.u.end(), state_u);
+    if (x) std::copy(H.x.begin(), H.x.end(), x);
+    if (y) std::copy(H.y.begin(), H.y.end(), y);
+    if (yaw) std::copy(H.yaw.begin(), H.yaw.end(), yaw);
+    if (speed) std::copy(H.speed.begin(), H.speed.end(), speed);
+    if (gap) std::copy(H.gap.begin(), H.gap.end(), gap);
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_set_hdv_recording(pdmpc_controller* c, int32_t T, const double* x, const double* y, const double* yaw) {
+    const std::string who = "pdmpc_controller_set_hdv_recording: ";
+    if (!c || T < 1 || !x || !y || !yaw) return cfail(c, PDMPC_ERR_INVALID, who + "bad argument");
+    HdvTraffic& H = c->hdv;
+    if (H.n == 0) return cfail(c, PDMPC_ERR_INVALID, who + "before pdmpc_controller_set_hdvs");
+    if (H.driven) return cfail(c, PDMPC_ERR_INVALID, who + "the HDVs have drivers (pdmpc_controller_set_hdv_drivers)");
+    H.rec_T = T;
+    H.rec_builds = 0;
+    H.rec_x.assign(x, x + (size_t)T * H.n);
+    H.rec_y.assign(y, y + (size_t)T * H.n);
+    H.rec_yaw.assign(yaw, yaw + (size_t)T * H.n);
+    return PDMPC_OK;
+}
+
+int pdmpc_controller_set_hdv_poses(pdmpc_controller* c, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw) {
+    if (!c || !x || !y || !cos_yaw || !sin_yaw) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_poses: null argument");
+    HdvTraffic& H = c->hdv;
+    if (H.n == 0) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_poses before pdmpc_controller_set_hdvs");
+    if (H.driven || H.rec_T > 0)
+        return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_poses: the HDVs move themselves (pdmpc_controller_set_hdv_drivers / _set_hdv_recording); their poses are not set");
+    H.x.assign(x, x + H.n);
+    H.y.assign(y, y + H.n);
+    H.cos_yaw.assign(cos_yaw, cos_yaw + H.n);
+    H.sin_yaw.assign(sin_yaw, sin_yaw + H.n);
+    hdv_driven_yaw(H);
+    H.measured = true;
+    return PDMPC_OK;
+}
+
 int pdmpc_controller_set_hdv_measurements(pdmpc_controller* c, const double* x, const double* y, const double* yaw) {
     if (!c || !x || !y || !yaw) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_measurements: null argument");
     HdvTraffic& H = c->hdv;
     if (H.n == 0) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_measurements before pdmpc_controller_set_hdvs");
+    if (H.driven || H.rec_T > 0)
+        return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_measurements: the HDVs move themselves (pdmpc_controller_set_hdv_drivers / _set_hdv_recording); their poses are not measured");
     H.x.assign(x, x + H.n);
     H.y.assign(y, y + H.n);
     H.yaw.assign(yaw, yaw + H.n);

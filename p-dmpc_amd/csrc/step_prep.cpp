@@ -1,12 +1,13 @@
 // step_prep.cpp — the step-preparation calls of the C ABI: device work that runs once per time step before the searches are packed
 // (unique prioritizations, reachable-set coupling, lanelet bounding and the coupling on the bounded sets, future collision assessment,
-// HDV traffic).
+// HDV traffic and the HDV drivers' step in front of it).
 //
 // Every call but pdmpc_unique_priorities(_grouped) follows one recipe: carve ONE pinned staging block and ONE device workspace with the same
 // offsets (Carver), stage the inputs, copy them in once, launch between an event pair (timed_launch), copy the result back, synchronise.
 #include <atomic>
 
 #include "handle.hpp"
+#include "hdv_drive_host.hpp"
 #include "hdv_grouped_host.hpp"
 
 #include "../../include/pdmpc_geometry.h"
@@ -838,11 +839,15 @@ HdvMapRecord hdv_record(const HdvMapSlot& M) {
 }
 // ... of the grouped call for n HDVs and nc CAVs in G groups with `pairs` (CAV, HDV) pairs: hdv_layout's regions over all groups, the
 // groups' records and lookups among the inputs, the scan's results
+// With a drive pass in front (n_route >= 0: the lanelet ids of all routes): the routes, old states, desired speeds and parameters among
+// the inputs, the new states, speeds, gaps and poses among what is read back.
 struct HdvGroupedLayout {
-    size_t in, cav, trim, cav_lanelet, groups, group_of, pair_first, in_bytes, n_chains, chain_id, chain_succ, slot_n, slot_flags, slot_before, row_base;
-    size_t out, status, n_rows, set_base, n_closest, closest, row_hdv, set_off, set_flags, adjacency, set_xy, total;
+    size_t in, cav, trim, cav_lanelet, groups, group_of, pair_first, drives, route_off, route_id, closed, state_seg, state_u, v_des, params, in_bytes;
+    size_t n_chains, chain_id, chain_succ, slot_n, slot_flags, slot_before, row_base;
+    size_t out, status, n_rows, set_base, n_closest, closest, row_hdv, set_off, set_flags, adjacency, new_seg, new_u, speed, gap, pose, set_xy, total;
 };
-HdvGroupedLayout hdv_grouped_ws(int G, int n, int nc, size_t pairs, int Hp, int capacity) {
+HdvGroupedLayout hdv_grouped_ws(int G, int n, int nc, size_t pairs, int Hp, int capacity, int n_route = -1) {
+    const size_t dn = n_route < 0 ? 0 : (size_t)n, dG = n_route < 0 ? 0 : (size_t)G;  // (no drive pass: its regions are empty)
     const size_t lists = (size_t)n * PDMPC_HDV_MAX_CHAINS, slots = lists * Hp;
     Carver c;
     HdvGroupedLayout L;
@@ -853,6 +858,14 @@ HdvGroupedLayout hdv_grouped_ws(int G, int n, int nc, size_t pairs, int Hp, int 
     L.groups = c.take<HdvGroup>((size_t)G);
     L.group_of = c.take<int32_t>((size_t)n);
     L.pair_first = c.take<int32_t>((size_t)G + 1);
+    L.drives = c.take<uint8_t>(dG);
+    L.route_off = c.take<int32_t>(dn ? dn + 1 : 0);
+    L.route_id = c.take<int32_t>(n_route < 0 ? 0 : (size_t)n_route);
+    L.closed = c.take<uint8_t>(dn);
+    L.state_seg = c.take<int32_t>(2 * dn);
+    L.state_u = c.take<double>(dn);
+    L.v_des = c.take<double>(dn);
+    L.params = c.take<double>(PDMPC_HDV_DRIVE_PARAMS * dG);
     L.in_bytes = c.end8();
     L.n_chains = c.take<int32_t>((size_t)n);
     L.chain_id = c.take<int32_t>(lists);
@@ -871,10 +884,25 @@ HdvGroupedLayout hdv_grouped_ws(int G, int n, int nc, size_t pairs, int Hp, int 
     L.set_off = c.take<int32_t>(slots + G + 1);
     L.set_flags = c.take<uint8_t>(slots);
     L.adjacency = c.take<uint8_t>(pairs);
+    L.new_seg = c.take<int32_t>(2 * dn);
+    L.new_u = c.take<double>(dn);
+    L.speed = c.take<double>(dn);
+    L.gap = c.take<double>(dn);
+    L.pose = c.take<double>(4 * dn);
     L.set_xy = c.take<double>((size_t)2 * capacity);
     L.total = c.at;
     return L;
 }
+// the drive pass of a grouped call: what pdmpc_hdv_drive_grouped and pdmpc_hdv_drive_traffic_grouped take beyond pdmpc_hdv_traffic_grouped
+struct HdvDriveCall {
+    const uint8_t* drives;  // [n_groups], or null: every group drives
+    const int32_t *route_offset, *route_lanelet;
+    const uint8_t* closed;
+    const int32_t* state_seg;
+    const double *state_u, *v_des, *parameters, *dt;
+    int32_t* new_seg;
+    double *new_u, *x, *y, *cos_yaw, *sin_yaw, *speed, *gap;
+};
 }  // namespace
 
 int pdmpc_upload_hdv_map_slot(pdmpc_handle* h, int32_t slot, int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x,
@@ -1038,18 +1066,20 @@ int pdmpc_hdv_traffic(pdmpc_handle* h, int32_t n_hdv, const double* x, const dou
     return PDMPC_OK;
 }
 
-int pdmpc_hdv_traffic_grouped(pdmpc_handle* h, int32_t n_groups, const int32_t* group_slot, const int32_t* hdv_offset, const int32_t* cav_offset, const double* x,
-                              const double* y, const double* cos_yaw, const double* sin_yaw, const int32_t* trim, const double* tile_dx, const double* tile_dy,
-                              const double* cav_x, const double* cav_y, const int32_t* cav_lanelet, const double* cav_tile_dx, const double* cav_tile_dy,
-                              int32_t* closest_offset, int32_t* closest_index, int32_t capacity, int32_t* n_rows, int32_t* row_hdv, int32_t* set_offset,
-                              int32_t* set_base, double* set_x, double* set_y, uint8_t* set_flags, uint8_t* adjacency) {
-    const std::string who = "pdmpc_hdv_traffic_grouped: ";
+// The grouped calls: the five passes of the traffic call (traffic), the drive pass in front of them (drive), or the drive pass alone.
+// Without the traffic passes the poses, trims, CAV lanelets and every traffic output are not read (null).
+static int hdv_grouped_call(pdmpc_handle* h, const std::string& who, bool traffic, const HdvDriveCall* drive, int32_t n_groups, const int32_t* group_slot,
+                            const int32_t* hdv_offset, const int32_t* cav_offset, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw,
+                            const int32_t* trim, const double* tile_dx, const double* tile_dy, const double* cav_x, const double* cav_y, const int32_t* cav_lanelet,
+                            const double* cav_tile_dx, const double* cav_tile_dy, int32_t* closest_offset, int32_t* closest_index, int32_t capacity, int32_t* n_rows,
+                            int32_t* row_hdv, int32_t* set_offset, int32_t* set_base, double* set_x, double* set_y, uint8_t* set_flags, uint8_t* adjacency) {
     if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
     HdvState& S = h->hdv;
-    if (n_groups < 0 || capacity < 0 || !set_base || (n_groups && (!group_slot || !hdv_offset || !cav_offset || !closest_offset || !n_rows || !set_offset)))
+    if (n_groups < 0 || capacity < 0 || (n_groups && (!group_slot || !hdv_offset || !cav_offset)) ||
+        (traffic && (!set_base || (n_groups && (!closest_offset || !n_rows || !set_offset)))))
         return fail(PDMPC_ERR_INVALID, who + "bad argument");
     if (n_groups == 0) {
-        set_base[0] = 0;
+        if (traffic) set_base[0] = 0;
         return PDMPC_OK;
     }
     if (hdv_offset[0] != 0 || cav_offset[0] != 0) return fail(PDMPC_ERR_INVALID, who + "offsets that do not start at 0");
@@ -1060,8 +1090,8 @@ int pdmpc_hdv_traffic_grouped(pdmpc_handle* h, int32_t n_groups, const int32_t* 
         if (group_slot[g] < 0 || group_slot[g] >= PDMPC_HDV_MAP_SLOTS) return fail(PDMPC_ERR_INVALID, group + "map slot out of range");
         const HdvMapSlot& M = S.map[group_slot[g]];
         if (!M.valid) return fail(PDMPC_ERR_INVALID, group + "no map was uploaded into its slot");
-        if (Hp && M.data.Hp != Hp) return fail(PDMPC_ERR_INVALID, group + "the Hp of its slot differs from the slots of the groups before");
-        Hp = M.data.Hp;
+        if (traffic && Hp && M.data.Hp != Hp) return fail(PDMPC_ERR_INVALID, group + "the Hp of its slot differs from the slots of the groups before");
+        Hp = traffic ? M.data.Hp : 1;
     }
     const int n = hdv_offset[n_groups], nc = cav_offset[n_groups];
     std::vector<int32_t> closest_at((size_t)n_groups + 1), list_at((size_t)n_groups + 1), set_offset_at((size_t)n_groups + 1), set_at((size_t)n_groups + 1);
@@ -1074,40 +1104,64 @@ int pdmpc_hdv_traffic_grouped(pdmpc_handle* h, int32_t n_groups, const int32_t* 
             return fail(PDMPC_ERR_CAPACITY, who + "group " + std::to_string(g) + ": more than PDMPC_HDV_MAX_VEHICLES HDVs or PDMPC_HDV_MAX_CAVS CAVs");
     if (n > PDMPC_HDV_GROUPED_MAX_VEHICLES) return fail(PDMPC_ERR_CAPACITY, who + "more than PDMPC_HDV_GROUPED_MAX_VEHICLES HDVs in the call");
     if (pairs > INT32_MAX) return fail(PDMPC_ERR_CAPACITY, who + "2^31 or more (CAV, HDV) pairs");
-    if (n && (!x || !y || !cos_yaw || !sin_yaw || !trim || !tile_dx || !tile_dy || !closest_index || !row_hdv)) return fail(PDMPC_ERR_INVALID, who + "a null HDV array");
-    if (nc && (!cav_x || !cav_y || !cav_lanelet || !cav_tile_dx || !cav_tile_dy)) return fail(PDMPC_ERR_INVALID, who + "a null CAV array");
-    if (pairs && !adjacency) return fail(PDMPC_ERR_INVALID, who + "no adjacency array");
-    for (int g = 0; g < n_groups; ++g) {
+    if (n && (!tile_dx || !tile_dy || (traffic && (!x || !y || !cos_yaw || !sin_yaw || !trim || !closest_index || !row_hdv)))) return fail(PDMPC_ERR_INVALID, who + "a null HDV array");
+    if (nc && (!cav_x || !cav_y || !cav_tile_dx || !cav_tile_dy || (traffic && !cav_lanelet))) return fail(PDMPC_ERR_INVALID, who + "a null CAV array");
+    if (traffic && pairs && !adjacency) return fail(PDMPC_ERR_INVALID, who + "no adjacency array");
+    // the drive pass: routes and states of the groups that drive against their maps (an HDV of a group that does not drive has no route)
+    int n_route = -1;
+    if (drive) {
+        if (!drive->route_offset || drive->route_offset[0] != 0 || !drive->parameters || !drive->dt ||
+            (n && (!drive->closed || !drive->state_seg || !drive->state_u || !drive->v_des || !drive->new_seg || !drive->new_u || !drive->x || !drive->y || !drive->cos_yaw ||
+                   !drive->sin_yaw || !drive->speed || !drive->gap)))
+            return fail(PDMPC_ERR_INVALID, who + "a null driver array, or route offsets that do not start at 0");
+        for (int q = 0; q < n; ++q)
+            if (drive->route_offset[q + 1] < drive->route_offset[q]) return fail(PDMPC_ERR_INVALID, who + "route offsets decrease");
+        n_route = drive->route_offset[n];
+        for (int g = 0; g < n_groups; ++g) {
+            if (drive->drives && !drive->drives[g]) continue;
+            const int h0 = hdv_offset[g], ng = hdv_offset[g + 1] - h0;
+            const HdvMapData& map = S.map[group_slot[g]].data.map;
+            std::string why;
+            int rc = hdv_check_routes(map, ng, drive->route_offset + h0, drive->route_lanelet, drive->closed + h0, &why);
+            if (!rc) rc = hdv_check_states(map, ng, drive->route_offset + h0, drive->route_lanelet, drive->closed + h0, drive->state_seg + h0, drive->state_seg + n + h0, drive->state_u + h0, &why);
+            if (!rc) rc = hdv_check_drive(drive->parameters + 4 * (size_t)g, drive->dt[g], ng, drive->v_des + h0, &why);
+            if (rc) return fail(rc, who + "group " + std::to_string(g) + ": " + why);
+        }
+    }
+    for (int g = 0; traffic && g < n_groups; ++g) {
         const HdvSlotData& D = S.map[group_slot[g]].data;
         for (int q = hdv_offset[g]; q < hdv_offset[g + 1]; ++q)
             if (trim[q] < 1 || trim[q] > D.trims) return fail(PDMPC_ERR_INVALID, who + "group " + std::to_string(g) + ": trim out of range");
         for (int v = cav_offset[g]; v < cav_offset[g + 1]; ++v)
             if (cav_lanelet[v] < 1 || cav_lanelet[v] > D.map.n_lanelets) return fail(PDMPC_ERR_INVALID, who + "group " + std::to_string(g) + ": a CAV's lanelet id out of range");
     }
-    for (int g = 0; g < n_groups; ++g) {  // what has a size whatever happens
+    for (int g = 0; traffic && g < n_groups; ++g) {  // what has a size whatever happens
         n_rows[g] = 0;
         closest_offset[closest_at[(size_t)g]] = 0;
         set_offset[set_offset_at[(size_t)g]] = 0;
         set_base[g] = 0;
     }
-    set_base[n_groups] = 0;
+    if (traffic) set_base[n_groups] = 0;
     if (n == 0) return PDMPC_OK;
     const size_t lists = (size_t)n * PDMPC_HDV_MAX_CHAINS, slots = lists * Hp;
     // (no more vertices are read back than the slots can hold, whatever room the caller has)
-    const int cap = (int)std::min<size_t>((size_t)capacity, set_x && set_y ? slots * PDMPC_BOUND_SLOT : 0);
+    const int cap = (int)std::min<size_t>((size_t)capacity, traffic && set_x && set_y ? slots * PDMPC_BOUND_SLOT : 0);
     ON_DEVICE(h->cfg.device);
-    const HdvGroupedLayout L = hdv_grouped_ws(n_groups, n, nc, (size_t)pairs, Hp, cap);
+    const HdvGroupedLayout L = hdv_grouped_ws(n_groups, n, nc, (size_t)pairs, Hp, cap, n_route);
     // (the slots of the lane pass: what this call needs, without head room -- 256 KB x Hp per HDV)
-    if (S.ws.ensure(L.total) || S.slots.ensure_exact(2 * slots * PDMPC_BOUND_SLOT) || S.h_in.ensure(L.in_bytes) || S.h_out.ensure(L.total - L.out))
+    if (S.ws.ensure(L.total) || (traffic && S.slots.ensure_exact(2 * slots * PDMPC_BOUND_SLOT)) || S.h_in.ensure(L.in_bytes) || S.h_out.ensure(L.total - L.out))
         return fail(PDMPC_ERR_HIP, "hipMalloc failed for the grouped HDV traffic call");
     unsigned char *hin = S.h_in.p, *ws = S.ws.p;
     double* in = (double*)(hin + L.in);
-    stage_poses(in, (size_t)n, x, y, cos_yaw, sin_yaw, (int32_t*)(hin + L.trim), trim);
+    if (traffic)
+        stage_poses(in, (size_t)n, x, y, cos_yaw, sin_yaw, (int32_t*)(hin + L.trim), trim);
+    else
+        std::memset(hin + L.in, 0, (size_t)4 * n * sizeof(double));
     std::memcpy(in + 4 * (size_t)n, tile_dx, (size_t)n * sizeof(double));
     std::memcpy(in + 5 * (size_t)n, tile_dy, (size_t)n * sizeof(double));
     if (nc) {
         stage_poses((double*)(hin + L.cav), (size_t)nc, cav_x, cav_y, cav_tile_dx, cav_tile_dy);
-        std::memcpy(hin + L.cav_lanelet, cav_lanelet, (size_t)nc * sizeof(int32_t));
+        if (traffic) std::memcpy(hin + L.cav_lanelet, cav_lanelet, (size_t)nc * sizeof(int32_t));
     }
     HdvGroup* groups = (HdvGroup*)(hin + L.groups);
     int32_t *group_of = (int32_t*)(hin + L.group_of), *pair_first = (int32_t*)(hin + L.pair_first);
@@ -1117,8 +1171,9 @@ int pdmpc_hdv_traffic_grouped(pdmpc_handle* h, int32_t n_groups, const int32_t* 
         pair_first[g] = (int32_t)adjacency_at[(size_t)g];
     }
     pair_first[n_groups] = (int32_t)pairs;
-    HdvGroupedArgs GA;
-    std::memset(&GA, 0, sizeof GA);
+    HdvDriveTrafficArgs DT;
+    std::memset(&DT, 0, sizeof DT);
+    HdvGroupedArgs& GA = DT.g;
     HdvArgs& A = GA.a;
     A.n_hdv = n;
     A.n_cav = nc;
@@ -1154,12 +1209,71 @@ int pdmpc_hdv_traffic_grouped(pdmpc_handle* h, int32_t n_groups, const int32_t* 
     GA.row_base = (int32_t*)(ws + L.row_base);
     GA.n_rows = (int32_t*)(ws + L.n_rows);
     GA.set_base = (int32_t*)(ws + L.set_base);
+    if (drive) {
+        uint8_t* drives = hin + L.drives;
+        for (int g = 0; g < n_groups; ++g) {
+            drives[g] = drive->drives ? (drive->drives[g] ? 1 : 0) : 1;
+            double* P = (double*)(hin + L.params) + (size_t)g * PDMPC_HDV_DRIVE_PARAMS;
+            std::memcpy(P, drive->parameters + 4 * (size_t)g, 4 * sizeof(double));
+            P[4] = drive->dt[g];
+        }
+        std::memcpy(hin + L.route_off, drive->route_offset, ((size_t)n + 1) * sizeof(int32_t));
+        if (n_route) std::memcpy(hin + L.route_id, drive->route_lanelet, (size_t)n_route * sizeof(int32_t));
+        std::memcpy(hin + L.closed, drive->closed, (size_t)n);
+        std::memcpy(hin + L.state_seg, drive->state_seg, (size_t)2 * n * sizeof(int32_t));
+        std::memcpy(hin + L.state_u, drive->state_u, (size_t)n * sizeof(double));
+        std::memcpy(hin + L.v_des, drive->v_des, (size_t)n * sizeof(double));
+        HdvDriveArgs& D = DT.d;
+        D.maps = S.maps.p;
+        D.groups = GA.groups;
+        D.group_of = GA.group_of;
+        D.drives = ws + L.drives;
+        D.n_hdv = n;
+        D.n_cav = nc;
+        D.route_off = (const int32_t*)(ws + L.route_off);
+        D.route_id = (const int32_t*)(ws + L.route_id);
+        D.closed = ws + L.closed;
+        D.state_seg = (const int32_t*)(ws + L.state_seg);
+        D.state_u = (const double*)(ws + L.state_u);
+        D.v_des = (const double*)(ws + L.v_des);
+        D.params = (const double*)(ws + L.params);
+        D.cav = A.cav;
+        D.in = (double*)(ws + L.in);
+        D.new_seg = (int32_t*)(ws + L.new_seg);
+        D.new_u = (double*)(ws + L.new_u);
+        D.speed = (double*)(ws + L.speed);
+        D.gap = (double*)(ws + L.gap);
+        D.pose = (double*)(ws + L.pose);
+    }
     HIPCHK(hipMemcpyAsync(ws, hin, L.in_bytes, hipMemcpyHostToDevice, h->stream));
-    if (const int rc = timed_launch(h, S.timed, pdmpc_launch_hdv_traffic_grouped, GA, "grouped HDV traffic")) return rc;
+    if (drive && traffic) {
+        if (const int rc = timed_launch(h, S.timed, pdmpc_launch_hdv_drive_traffic_grouped, DT, "grouped HDV drive and traffic")) return rc;
+    } else if (drive) {
+        if (const int rc = timed_launch(h, S.timed, pdmpc_launch_hdv_drive, DT.d, "grouped HDV drive")) return rc;
+    } else {
+        if (const int rc = timed_launch(h, S.timed, pdmpc_launch_hdv_traffic_grouped, GA, "grouped HDV traffic")) return rc;
+    }
     HIPCHK(hipMemcpyAsync(S.h_out.p, ws + L.out, L.total - L.out, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(sync_stream(h));
     S.timed.fold();
     auto back = [&](size_t at) { return (const unsigned char*)S.h_out.p + (at - L.out); };  // the read-back block at the workspace's offsets
+    if (drive)  // the groups that drove: their HDVs' blocks of every output, the others' entries are left as they are
+        for (int g = 0; g < n_groups; ++g) {
+            if (drive->drives && !drive->drives[g]) continue;
+            const size_t h0 = (size_t)hdv_offset[g], ng = (size_t)hdv_offset[g + 1] - h0;
+            const int32_t* seg = (const int32_t*)back(L.new_seg);
+            const double* pose = (const double*)back(L.pose);
+            std::memcpy(drive->new_seg + h0, seg + h0, ng * sizeof(int32_t));
+            std::memcpy(drive->new_seg + n + h0, seg + n + h0, ng * sizeof(int32_t));
+            std::memcpy(drive->new_u + h0, (const double*)back(L.new_u) + h0, ng * sizeof(double));
+            std::memcpy(drive->speed + h0, (const double*)back(L.speed) + h0, ng * sizeof(double));
+            std::memcpy(drive->gap + h0, (const double*)back(L.gap) + h0, ng * sizeof(double));
+            std::memcpy(drive->x + h0, pose + h0, ng * sizeof(double));
+            std::memcpy(drive->y + h0, pose + n + h0, ng * sizeof(double));
+            std::memcpy(drive->cos_yaw + h0, pose + 2 * (size_t)n + h0, ng * sizeof(double));
+            std::memcpy(drive->sin_yaw + h0, pose + 3 * (size_t)n + h0, ng * sizeof(double));
+        }
+    if (!traffic) return PDMPC_OK;
     const int32_t* status = (const int32_t*)back(L.status);
     const int32_t *rows_of = (const int32_t*)back(L.n_rows), *n_closest = (const int32_t*)back(L.n_closest), *closest = (const int32_t*)back(L.closest);
     // the outputs stand on the device where the caller's arrays have them: every group's blocks are copied as they are
@@ -1193,6 +1307,39 @@ int pdmpc_hdv_traffic_grouped(pdmpc_handle* h, int32_t n_groups, const int32_t* 
     if (status[1] & PDMPC_HDV_OVER_SLOT) return fail(PDMPC_ERR_CAPACITY, who + "a reachable lane has more than PDMPC_BOUNDED_MAX_COLS vertices");
     if (!fits) return fail(PDMPC_ERR_CAPACITY, who + "capacity too small for the reachable lanes");
     return PDMPC_OK;
+}
+
+int pdmpc_hdv_traffic_grouped(pdmpc_handle* h, int32_t n_groups, const int32_t* group_slot, const int32_t* hdv_offset, const int32_t* cav_offset, const double* x,
+                              const double* y, const double* cos_yaw, const double* sin_yaw, const int32_t* trim, const double* tile_dx, const double* tile_dy,
+                              const double* cav_x, const double* cav_y, const int32_t* cav_lanelet, const double* cav_tile_dx, const double* cav_tile_dy,
+                              int32_t* closest_offset, int32_t* closest_index, int32_t capacity, int32_t* n_rows, int32_t* row_hdv, int32_t* set_offset,
+                              int32_t* set_base, double* set_x, double* set_y, uint8_t* set_flags, uint8_t* adjacency) {
+    return hdv_grouped_call(h, "pdmpc_hdv_traffic_grouped: ", true, nullptr, n_groups, group_slot, hdv_offset, cav_offset, x, y, cos_yaw, sin_yaw, trim, tile_dx, tile_dy, cav_x,
+                            cav_y, cav_lanelet, cav_tile_dx, cav_tile_dy, closest_offset, closest_index, capacity, n_rows, row_hdv, set_offset, set_base, set_x, set_y, set_flags,
+                            adjacency);
+}
+
+int pdmpc_hdv_drive_grouped(pdmpc_handle* h, int32_t n_groups, const int32_t* group_slot, const int32_t* hdv_offset, const int32_t* cav_offset, const int32_t* route_offset,
+                            const int32_t* route_lanelet, const uint8_t* closed, const int32_t* state_seg, const double* state_u, const double* tile_dx, const double* tile_dy,
+                            const double* v_des, const double* cav_x, const double* cav_y, const double* cav_tile_dx, const double* cav_tile_dy, const double* parameters,
+                            const double* dt, int32_t* new_seg, double* new_u, double* x, double* y, double* cos_yaw, double* sin_yaw, double* speed, double* gap) {
+    const HdvDriveCall D{nullptr, route_offset, route_lanelet, closed, state_seg, state_u, v_des, parameters, dt, new_seg, new_u, x, y, cos_yaw, sin_yaw, speed, gap};
+    return hdv_grouped_call(h, "pdmpc_hdv_drive_grouped: ", false, &D, n_groups, group_slot, hdv_offset, cav_offset, nullptr, nullptr, nullptr, nullptr, nullptr, tile_dx, tile_dy,
+                            cav_x, cav_y, nullptr, cav_tile_dx, cav_tile_dy, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+int pdmpc_hdv_drive_traffic_grouped(pdmpc_handle* h, int32_t n_groups, const int32_t* group_slot, const int32_t* hdv_offset, const int32_t* cav_offset, const uint8_t* drives,
+                                    const int32_t* route_offset, const int32_t* route_lanelet, const uint8_t* closed, const int32_t* state_seg, const double* state_u,
+                                    const double* v_des, const double* parameters, const double* dt, int32_t* new_seg, double* new_u, double* speed, double* gap, double* x,
+                                    double* y, double* cos_yaw, double* sin_yaw, const int32_t* trim, const double* tile_dx, const double* tile_dy, const double* cav_x,
+                                    const double* cav_y, const int32_t* cav_lanelet, const double* cav_tile_dx, const double* cav_tile_dy, int32_t* closest_offset,
+                                    int32_t* closest_index, int32_t capacity, int32_t* n_rows, int32_t* row_hdv, int32_t* set_offset, int32_t* set_base, double* set_x,
+                                    double* set_y, uint8_t* set_flags, uint8_t* adjacency) {
+    if (!drives) return fail(PDMPC_ERR_INVALID, "pdmpc_hdv_drive_traffic_grouped: no drive flags");
+    const HdvDriveCall D{drives, route_offset, route_lanelet, closed, state_seg, state_u, v_des, parameters, dt, new_seg, new_u, x, y, cos_yaw, sin_yaw, speed, gap};
+    return hdv_grouped_call(h, "pdmpc_hdv_drive_traffic_grouped: ", true, &D, n_groups, group_slot, hdv_offset, cav_offset, x, y, cos_yaw, sin_yaw, trim, tile_dx, tile_dy, cav_x,
+                            cav_y, cav_lanelet, cav_tile_dx, cav_tile_dy, closest_offset, closest_index, capacity, n_rows, row_hdv, set_offset, set_base, set_x, set_y, set_flags,
+                            adjacency);
 }
 
 int pdmpc_hdv_kernel_ms(pdmpc_handle* h, double* ms) {

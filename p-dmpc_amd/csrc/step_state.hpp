@@ -44,6 +44,10 @@ struct PrepScratch {
         std::vector<int32_t> closest_off, closest_idx, n_rows, row_hdv, set_off, set_base;
         std::vector<double> set_x, set_y;
         std::vector<uint8_t> set_flags, adjacency;
+        // the drive pass in front (pdmpc_hdv_drive_traffic_grouped), when a member of the batch has drivers
+        std::vector<uint8_t> drives, route_closed;
+        std::vector<int32_t> route_off, route_id, seg_r, seg_j, seg, new_seg;
+        std::vector<double> u, v_des, params, dt, new_u, speed, gap;
     } hdv;
     // the grouped collision assessment: the FCA members' reference points, member after member, and what it returns
     struct Fca {

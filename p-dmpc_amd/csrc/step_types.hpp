@@ -220,6 +220,17 @@ struct HdvTraffic {
     std::vector<uint8_t> set_flags, adjacency;
     std::vector<std::vector<int32_t>> cav_off;
     std::vector<std::vector<double>> cav_x, cav_y;
+    // Drivers (pdmpc_controller_set_hdv_drivers; include/pdmpc_hdv.h: the driver model): the HDVs move themselves, one step at every built
+    // step but the first after the drivers were set (whose "measurement" is the placement).  seg / u: the state of the last built step.
+    bool driven = false;
+    int driven_builds = 0;  // built steps since the drivers were set
+    std::vector<int32_t> route_off, route_id, seg, new_seg;
+    std::vector<uint8_t> route_closed;
+    std::vector<double> u, new_u, v_des, speed, gap;
+    double drive_params[4] = {0.0, 0.0, 0.0, 0.0};
+    // A recording (pdmpc_controller_set_hdv_recording): row min(built steps, T) - 1 of T recorded poses is the measurement of a built step
+    int rec_T = 0, rec_builds = 0;
+    std::vector<double> rec_x, rec_y, rec_yaw;
     // CAV v's set (valid until the next step's call)
     [[maybe_unused]] pdmpc_polygon_set set_of(int v) const { return view_polygons(cav_off[(size_t)v], cav_x[(size_t)v], cav_y[(size_t)v]); }
     // ... rebuilt from the call's output: the rows of the adjacent HDVs in row order, polygon row * Hp + k (vectorize_all_obstacles.m:33-62)

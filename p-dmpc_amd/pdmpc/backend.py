@@ -976,12 +976,12 @@ class Handle:
 
         return hdv.hdv_traffic_grouped_native(self, groups, capacity=capacity, call_ms=call_ms, raw=raw, guard=guard)
 
-    def hdv_traffic(self, hdv_x, hdv_y, hdv_yaw, hdv_trim, hdv_tile, cav_x, cav_y, cav_lanelet, cav_tile, capacity=None, call_ms=None):
+    def hdv_traffic(self, hdv_x, hdv_y, hdv_yaw, hdv_trim, hdv_tile, cav_x, cav_y, cav_lanelet, cav_tile, capacity=None, call_ms=None, cos_sin=None):
         """pdmpc_hdv_traffic on this handle's device; see hdv.hdv_traffic_native."""
         from . import hdv
 
         return hdv.hdv_traffic_native(None, None, hdv_x, hdv_y, hdv_yaw, hdv_trim, hdv_tile, cav_x, cav_y, cav_lanelet, cav_tile, handle=self, capacity=capacity,
-                                      call_ms=call_ms)
+                                      call_ms=call_ms, cos_sin=cos_sin)
 
     def hdv_kernel_ms(self):
         """kernel time (ms) of the last hdv_traffic"""

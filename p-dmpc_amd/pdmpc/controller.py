@@ -120,7 +120,8 @@ class PrioritizedSequentialController:
         reference: single_speed without the recursive-feasibility mask), hmap = the map (hdv.HdvMap), tile[h] = the (dx, dy) of the
         map copy HDV h drives on (default: none moved).  traffic: the call that computes the step's traffic info with the arguments
         after the sets of hdv.hdv_traffic (default: the numpy twin; `handle.hdv_traffic` after handle.upload_hdv_map runs it on the
-        device, lambda *a: hdv.hdv_traffic_native(hmap, sets, *a) on the host twin -- all three give the same bits)."""
+        device, lambda *a, **kw: hdv.hdv_traffic_native(hmap, sets, *a, **kw) on the host twin -- all three give the same bits; HDVs that
+        are driven or handed over by set_hdv_poses pass it cos_sin=(cos_yaw, sin_yaw))."""
         n_hdv = int(self.options.manual_control)
         if n_hdv < 1:
             raise ValueError("set_hdvs needs options.manual_control >= 1")
@@ -133,24 +134,99 @@ class PrioritizedSequentialController:
         from . import hdv as _hdv
 
         self.hdvs = dict(sets=hdv_local_sets, map=hmap, tile=[(0.0, 0.0)] * n_hdv if tile is None else [tuple(t) for t in tile],
-                         traffic=traffic if traffic is not None else (lambda *a: _hdv.hdv_traffic(hmap, hdv_local_sets, *a)), meas=None)
+                         traffic=traffic if traffic is not None else (lambda *a, **kw: _hdv.hdv_traffic(hmap, hdv_local_sets, *a, **kw)), meas=None)
 
     def set_hdv_measurements(self, x, y, yaw):
         """The HDVs' measured poses (Plant.measure; CpmLab.measure returns them, Simulation.measure none): kept until set again."""
         n_hdv = int(self.options.manual_control)
         if self.hdvs is None or not (len(x) == len(y) == len(yaw) == n_hdv):
             raise ValueError("set_hdv_measurements: %d poses after set_hdvs" % n_hdv)
+        if self.hdvs.get("drivers") or self.hdvs.get("recording"):
+            raise ValueError("set_hdv_measurements: the HDVs move themselves (set_hdv_drivers / set_hdv_recording); their poses are not measured")
         self.hdvs["meas"] = ([float(v) for v in x], [float(v) for v in y], [float(v) for v in yaw])
+        self.hdvs["cos_sin"] = None
+
+    def set_hdv_poses(self, x, y, cos_yaw, sin_yaw):
+        """Measurements given as directions (pdmpc_controller_set_hdv_poses): cos and sin as they are, what a caller that drives the HDVs
+        itself with hdv.drive hands over."""
+        n_hdv = int(self.options.manual_control)
+        if self.hdvs is None or not (len(x) == len(y) == len(cos_yaw) == len(sin_yaw) == n_hdv):
+            raise ValueError("set_hdv_poses: %d poses after set_hdvs" % n_hdv)
+        if self.hdvs.get("drivers") or self.hdvs.get("recording"):
+            raise ValueError("set_hdv_poses: the HDVs move themselves (set_hdv_drivers / set_hdv_recording); their poses are not set")
+        c, s = [float(v) for v in cos_yaw], [float(v) for v in sin_yaw]
+        self.hdvs["meas"] = ([float(v) for v in x], [float(v) for v in y], [math.atan2(b, a) for a, b in zip(c, s)])
+        self.hdvs["cos_sin"] = (c, s)
+
+    def set_hdv_drivers(self, routes, start_distance, v_des, params=None, drive=None):
+        """pdmpc_controller_set_hdv_drivers (DESIGN.md §3.24 "Drivers"): HDV q follows routes[q] = (lanelet ids, closed) from
+        start_distance[q] metres along it at up to v_des[q]; params = (look_ahead, gap_min, headway, lateral).  The placement is the
+        measurement of the first built step; every later built step first moves the HDVs one driver step of options.dt_seconds
+        against the CAVs' measured positions.  drive: the step, with hdv.drive's arguments behind the map (default: the numpy twin;
+        lambda *a: hdv.drive_native(hmap, *a) is the host twin)."""
+        from . import hdv as _hdv
+
+        if self.hdvs is None:
+            raise ValueError("set_hdv_drivers before set_hdvs")
+        if self.hdvs.get("recording"):
+            raise ValueError("set_hdv_drivers: the HDVs replay a recording (set_hdv_recording)")
+        h = self.hdvs
+        n_hdv = int(self.options.manual_control)
+        if not (len(routes) == len(start_distance) == len(v_des) == n_hdv):
+            raise ValueError("set_hdv_drivers: %d routes, start distances and speeds" % n_hdv)
+        params = tuple(float(p) for p in (_hdv.DRIVE_DEFAULTS if params is None else params))
+        _hdv.check_drive(params, float(self.options.dt_seconds), v_des)
+        routes = [([int(i) for i in ids], bool(closed)) for ids, closed in routes]
+        for q, (ids, closed) in enumerate(routes):
+            _hdv.check_route(h["map"], ids, closed, q)
+        states = [_hdv.place(h["map"], ids, closed, float(d)) for (ids, closed), d in zip(routes, start_distance)]
+        h["drivers"] = dict(routes=routes, states=states, v_des=[float(v) for v in v_des], params=params, builds=0, speed=[0.0] * n_hdv, gap=[math.inf] * n_hdv,
+                            drive=drive if drive is not None else (lambda *a: _hdv.drive(h["map"], *a)))
+        self._take_driven([_hdv.state_pose(h["map"], ids, closed, s, t) for (ids, closed), s, t in zip(routes, states, h["tile"])])
+
+    def _take_driven(self, poses):
+        c, s = [p[2] for p in poses], [p[3] for p in poses]
+        self.hdvs["meas"] = ([p[0] for p in poses], [p[1] for p in poses], [math.atan2(b, a) for a, b in zip(c, s)])
+        self.hdvs["cos_sin"] = (c, s)
+
+    def hdv_driver_state(self):
+        """pdmpc_controller_hdv_driver_state -> dict: states [(r, j, u)], x, y, yaw, speed, gap of the last built step"""
+        d = self.hdvs["drivers"]
+        x, y, yaw = self.hdvs["meas"]
+        return dict(states=list(d["states"]), x=list(x), y=list(y), yaw=list(yaw), speed=list(d["speed"]), gap=list(d["gap"]))
+
+    def set_hdv_recording(self, x, y, yaw):
+        """pdmpc_controller_set_hdv_recording: (T, n_hdv) recorded poses; built step s (from 1) takes row min(s, T) - 1."""
+        n_hdv = int(self.options.manual_control)
+        a = [np.asarray(v, dtype=np.float64).reshape(-1, n_hdv) for v in (x, y, yaw)]
+        if self.hdvs is None or a[0].shape[0] < 1 or not (a[0].shape == a[1].shape == a[2].shape):
+            raise ValueError("set_hdv_recording: (T, %d) poses after set_hdvs" % n_hdv)
+        if self.hdvs.get("drivers"):
+            raise ValueError("set_hdv_recording: the HDVs have drivers (set_hdv_drivers)")
+        self.hdvs["recording"] = dict(x=a[0], y=a[1], yaw=a[2], builds=0)
 
     def _hdv_traffic_info(self):
-        """ONE traffic call per step: trim 1 for every HDV (ManualVehicle.m:33), the CAVs' own measurements and current lanelets."""
+        """ONE traffic call per step: trim 1 for every HDV (ManualVehicle.m:33), the CAVs' own measurements and current lanelets.  HDVs
+        with drivers move first (every built step but the first after set_hdv_drivers); a recording hands over its next row."""
         h = self.hdvs
+        tiles = [tuple(float(c) for c in t) for t in getattr(self.scenario, "tile_offset", [(0.0, 0.0)] * self.n)]
+        cav_x, cav_y = [float(v) for v in self.x0[:, 0]], [float(v) for v in self.x0[:, 1]]
+        rec, d = h.get("recording"), h.get("drivers")
+        if rec:
+            rec["builds"] += 1
+            row = min(rec["builds"], rec["x"].shape[0]) - 1
+            h["meas"], h["cos_sin"] = ([float(v) for v in rec["x"][row]], [float(v) for v in rec["y"][row]], [float(v) for v in rec["yaw"][row]]), None
+        if d:
+            d["builds"] += 1
+            if d["builds"] > 1:
+                r = d["drive"](d["routes"], d["states"], h["tile"], d["v_des"], cav_x, cav_y, tiles, d["params"], float(self.options.dt_seconds))
+                d["states"], d["speed"], d["gap"] = list(r["states"]), list(r["speed"]), list(r["gap"])
+                self._take_driven(list(zip(r["x"], r["y"], r["cos_yaw"], r["sin_yaw"])))
         if h["meas"] is None:
             raise ValueError("set_hdv_measurements before the first step with HDVs")
         x, y, yaw = h["meas"]
-        tiles = getattr(self.scenario, "tile_offset", [(0.0, 0.0)] * self.n)
-        self.hdv_info = h["traffic"](x, y, yaw, [1] * len(x), h["tile"], [float(v) for v in self.x0[:, 0]], [float(v) for v in self.x0[:, 1]],
-                                     [int(c) for c in self.current_lanelet], [tuple(float(c) for c in t) for t in tiles])
+        more = {} if h.get("cos_sin") is None else dict(cos_sin=h["cos_sin"])
+        self.hdv_info = h["traffic"](x, y, yaw, [1] * len(x), h["tile"], cav_x, cav_y, [int(c) for c in self.current_lanelet], tiles, **more)
 
     # ---- HighLevelController.update_controlled_vehicles_traffic_info (HighLevelController.m:167-270)
     def _traffic_info(self):

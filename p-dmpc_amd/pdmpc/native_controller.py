@@ -185,6 +185,43 @@ class NativeController:
             raise ValueError("set_hdv_measurements: %d poses" % n_hdv)
         self._check(self.L.pdmpc_controller_set_hdv_measurements(self.c, abi.dp(a[0]), abi.dp(a[1]), abi.dp(a[2])), "pdmpc_controller_set_hdv_measurements")
 
+    def set_hdv_poses(self, x, y, cos_yaw, sin_yaw):
+        """pdmpc_controller_set_hdv_poses: measurements given as directions (cos and sin as they are)."""
+        a = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (x, y, cos_yaw, sin_yaw)]
+        if any(v.size != int(self.options.manual_control) for v in a):
+            raise ValueError("set_hdv_poses: %d poses" % int(self.options.manual_control))
+        self._check(self.L.pdmpc_controller_set_hdv_poses(self.c, *[abi.dp(v) for v in a]), "pdmpc_controller_set_hdv_poses")
+
+    def set_hdv_drivers(self, routes, start_distance, v_des, params=None):
+        """pdmpc_controller_set_hdv_drivers: twin of PrioritizedSequentialController.set_hdv_drivers (routes [(lanelet ids, closed)])."""
+        from . import hdv
+
+        n_hdv = int(self.options.manual_control)
+        if not (len(routes) == len(start_distance) == len(v_des) == n_hdv):
+            raise ValueError("set_hdv_drivers: %d routes, start distances and speeds" % n_hdv)
+        off, lan, closed = hdv._route_arrays(routes)
+        d = np.array([float(v) for v in start_distance] + [0.0])
+        v = np.array([float(a) for a in v_des] + [0.0])
+        par = np.array([float(p) for p in (hdv.DRIVE_DEFAULTS if params is None else params)], dtype=np.float64)
+        self._check(self.L.pdmpc_controller_set_hdv_drivers(self.c, abi.i32p(off), abi.i32p(lan), abi.u8p(closed), abi.dp(d), abi.dp(v), abi.dp(par)),
+                    "pdmpc_controller_set_hdv_drivers")
+
+    def hdv_driver_state(self):
+        """pdmpc_controller_hdv_driver_state -> dict: states [(r, j, u)], x, y, yaw, speed, gap of the last built step"""
+        n = int(self.options.manual_control)
+        seg, out = np.zeros(2 * n, dtype=np.int32), [np.zeros(n) for _ in range(6)]
+        self._check(self.L.pdmpc_controller_hdv_driver_state(self.c, abi.i32p(seg), *[abi.dp(a) for a in out]), "pdmpc_controller_hdv_driver_state")
+        u, x, y, yaw, speed, gap = out
+        return dict(states=[(int(seg[q]), int(seg[n + q]), float(u[q])) for q in range(n)], x=x.tolist(), y=y.tolist(), yaw=yaw.tolist(), speed=speed.tolist(), gap=gap.tolist())
+
+    def set_hdv_recording(self, x, y, yaw):
+        """pdmpc_controller_set_hdv_recording: (T, n_hdv) recorded poses; built step s (from 1) takes row min(s, T) - 1."""
+        n = int(self.options.manual_control)
+        a = [np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1, n)) for v in (x, y, yaw)]
+        if not (a[0].shape == a[1].shape == a[2].shape):
+            raise ValueError("set_hdv_recording: (T, %d) poses" % n)
+        self._check(self.L.pdmpc_controller_set_hdv_recording(self.c, int(a[0].shape[0]), *[abi.dp(v) for v in a]), "pdmpc_controller_set_hdv_recording")
+
     def hdv_info(self):
         """pdmpc_controller_hdv_info: the traffic info of the last built step in the dict form of hdv.hdv_traffic."""
         n, rows = C.c_int32(), C.c_int32()

@@ -29,6 +29,9 @@ HDV_MAP = [I32, IP, IP, DP, DP, DP, DP, IP, IP, BP] + TABLE  # n_lanelets, left/
 HDV_CALL = [I32, DP, DP, DP, DP, IP, DP, DP, I32, DP, DP, IP, DP, DP, IP, IP, I32, IP, IP, IP, DP, DP, BP, BP]
 # n_groups, group_slot, hdv_offset, cav_offset | the HDVs | the CAVs | closest_offset, closest_index, capacity, n_rows, row_hdv, set_offset, set_base, set_x, set_y, set_flags, adjacency
 HDV_GROUPED = [I32, IP, IP, IP] + [DP, DP, DP, DP, IP, DP, DP] + [DP, DP, IP, DP, DP] + [IP, IP, I32, IP, IP, IP, IP, DP, DP, BP, BP]
+HDV_ROAD = HDV_MAP[:10]  # the map without the local sets
+HDV_ROUTES = [I32, IP, IP, BP]  # n_hdv, route_offset, route_lanelet, closed
+HDV_DRIVEN = [IP, DP, DP, DP, DP, DP, DP, DP]  # new_seg, new_u, x, y, cos_yaw, sin_yaw, speed, gap
 UNIQUE = [I32, BP, I64, P(I64), UP, IP]
 UNIQUE_GROUPED = [I32, IP, P(BP), P(I64), P(I64), UP, IP]  # n_groups, group_n, adjacency, max_out, n_out, masks, priorities
 
@@ -144,12 +147,23 @@ PROTOTYPES = {
     "pdmpc_hdv_check_map_host": (INT, HDV_MAP),
     "pdmpc_hdv_grouped_layout_host": (INT, [I32, IP, IP, I32, IP, IP, IP, IP, P(I64)]),
     "pdmpc_hdv_traffic_grouped": (INT, [OBJ] + HDV_GROUPED),
+    "pdmpc_hdv_route_check_host": (INT, HDV_ROAD + HDV_ROUTES),
+    "pdmpc_hdv_place_host": (INT, HDV_ROAD + HDV_ROUTES + [DP, DP, DP, IP, DP, DP, DP, DP, DP]),
+    # ... state_seg, state_u, tile_dx, tile_dy, v_des | n_cav, the CAVs | parameters, dt
+    "pdmpc_hdv_drive_host": (INT, HDV_ROAD + HDV_ROUTES + [IP, DP, DP, DP, DP] + [I32, DP, DP, DP, DP] + [DP, F64] + HDV_DRIVEN),
+    "pdmpc_hdv_drive_grouped": (INT, [OBJ, I32, IP, IP, IP] + HDV_ROUTES[1:] + [IP, DP, DP, DP, DP] + [DP, DP, DP, DP] + [DP, DP] + HDV_DRIVEN),
+    # n_groups, group_slot, hdv_offset, cav_offset, drives | routes | state_seg, state_u, v_des, parameters, dt | new_seg, new_u, speed, gap | the grouped traffic call
+    "pdmpc_hdv_drive_traffic_grouped": (INT, [OBJ, I32, IP, IP, IP, BP] + HDV_ROUTES[1:] + [IP, DP, DP, DP, DP] + [IP, DP, DP, DP] + HDV_GROUPED[4:]),
     # ---- the caller's side of the boundary, natively
     "pdmpc_controller_create": (INT, [OBJ, P(abi.ControllerConfig), P(abi.ScenarioStruct), P(OBJ)]),
     "pdmpc_controller_destroy": (INT, [OBJ]),
     "pdmpc_controller_step": (INT, [OBJ]),
     "pdmpc_controller_set_hdvs": (INT, [OBJ, I32, MPA, IP, IP, BP, DP, DP]),
     "pdmpc_controller_set_hdv_measurements": (INT, [OBJ, DP, DP, DP]),
+    "pdmpc_controller_set_hdv_drivers": (INT, [OBJ, IP, IP, BP, DP, DP, DP]),
+    "pdmpc_controller_hdv_driver_state": (INT, [OBJ, IP, DP, DP, DP, DP, DP, DP]),
+    "pdmpc_controller_set_hdv_recording": (INT, [OBJ, I32, DP, DP, DP]),
+    "pdmpc_controller_set_hdv_poses": (INT, [OBJ, DP, DP, DP, DP]),
     "pdmpc_controller_hdv_info": (INT, [OBJ, IP, P(IP), P(IP), IP, P(IP), P(IP), P(DP), P(DP), P(BP), P(BP)]),
     "pdmpc_controller_run": (INT, [OBJ, I32, DP]),
     "pdmpc_controller_build_step": (INT, [OBJ]),
