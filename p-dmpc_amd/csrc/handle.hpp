@@ -271,8 +271,9 @@ struct FcaState {
 };
 
 // pdmpc_upload_hdv_map(_slot) / pdmpc_hdv_traffic(_grouped) (hdv_kernel.hip): a map and the HDV automaton's local hulls
-// in one device table (hdv_table in step_prep.cpp), the call's workspace with its pinned staging (hdv_layout, hdv_grouped_ws) and the
-// slots of the lane pass; the workspace and the slots are grown when a call needs more, kept otherwise
+// in one device table (hdv_table), the workspace of the four calls with its pinned staging (ONE layout, hdv_ws: h_in holds its first
+// in_bytes, h_out what is read back from `out` on) and the slots of the lane pass (hdv_slot_doubles) -- all three in
+// hdv_call_host.hpp, with the stages of a call; the workspace and the slots are grown when a call needs more, kept otherwise
 // A handle has PDMPC_HDV_MAP_SLOTS map slots (pdmpc_upload_hdv_map_slot), each with its own table and the host's copy of it;
 // pdmpc_hdv_traffic reads slot 0, a group of pdmpc_hdv_traffic_grouped the slot it names, through `maps`: one HdvMapRecord per slot
 // on the device, written at the upload.

@@ -1,5 +1,5 @@
 // hdv_drive_host.hpp — the host side of the HDV driver model (include/pdmpc_hdv.h: "the driver model"): the checks of
-// routes, states and parameters that the host twin (hdv.cpp) and the device call (step_prep.cpp) share, the placement of an HDV at a
+// routes, states and parameters that the host twin (hdv.cpp) and the device calls' check stage (hdv_call_host.hpp) share, the placement of an HDV at a
 // distance along its route, and one step of all HDVs of a member on the host -- the body of pdmpc_hdv_drive_host, which the kernel
 // (hdv_kernel.hip: pdmpc_hdv_drive_kernel) restates with the same header functions.  Host only, no HIP header
 // (tests/hdv_drive_checks.cpp runs this file under the sanitizers).

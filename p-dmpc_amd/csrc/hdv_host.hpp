@@ -1,6 +1,6 @@
 // hdv_host.hpp — what the two sides of the HDV traffic call share on the host (hdv.cpp: the host twin; step_prep.cpp: the device call):
 // the map as it is taken over and checked once, the checks of a call's arguments, and the limits.  Host only, no HIP header.
-// DESIGN.md §3.24.
+// The device calls' own host side -- workspace layout, check, zero, stage, arguments, scatter -- is hdv_call_host.hpp.  DESIGN.md §3.24.
 #pragma once
 #include <cstdint>
 #include <cstring>

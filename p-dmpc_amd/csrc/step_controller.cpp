@@ -405,7 +405,7 @@ int hdv_drive_on_host(pdmpc_controller* c) {
 
 // the members of batch B (their maps are in the slots B.slot) as the groups of one call, and every member's blocks back into its own
 // arrays, as its own call leaves them.  The capacity retry is here, once: the room is the last total and a quarter.
-int hdv_grouped_call(pdmpc_handle* h, pdmpc_controller* const* members, const HdvBatch& B, PrepScratch::Hdv& C, const std::vector<uint8_t>& drives_of) {
+int hdv_call_for_batch(pdmpc_handle* h, pdmpc_controller* const* members, const HdvBatch& B, PrepScratch::Hdv& C, const std::vector<uint8_t>& drives_of) {
     const int G = (int)B.members.size(), Hp = members[B.members[0]]->sc.Hp;
     bool any_drives = false;
     for (auto* v : {&C.drives, &C.route_closed}) v->clear();
@@ -594,7 +594,7 @@ int hdv_traffic_stage(pdmpc_handle* h, pdmpc_controller* const* members, size_t 
             H.map_generation = generation[H.map_slot];
         }
         S.hdv_calls[0] += 1;
-        if (const int rc = hdv_grouped_call(h, members, B, S.hdv, drives)) return rc;
+        if (const int rc = hdv_call_for_batch(h, members, B, S.hdv, drives)) return rc;
     }
     return PDMPC_OK;
 }

@@ -3,41 +3,15 @@
 // HDV traffic and the HDV drivers' step in front of it).
 //
 // Every call but pdmpc_unique_priorities(_grouped) follows one recipe: carve ONE pinned staging block and ONE device workspace with the same
-// offsets (Carver), stage the inputs, copy them in once, launch between an event pair (timed_launch), copy the result back, synchronise.
+// offsets (Carver, carver.hpp), stage the inputs, copy them in once, launch between an event pair (timed_launch), copy the result back, synchronise.
 #include <atomic>
 
 #include "handle.hpp"
-#include "hdv_drive_host.hpp"
-#include "hdv_grouped_host.hpp"
+#include "hdv_call_host.hpp"
 
 #include "../../include/pdmpc_geometry.h"
 
 namespace {
-
-// Hands out the regions of one block in the order they are asked for.  A region starts at a multiple of its element's alignment
-// (or of `align`); the offsets hold for the pinned staging block and for the device workspace alike.
-struct Carver {
-    size_t at = 0;  // the first free byte: after the last region, the size of the block so far
-    template <class T>
-    size_t take(size_t count, size_t align = alignof(T)) {
-        at = (at + align - 1) & ~(align - 1);
-        const size_t offset = at;
-        at += count * sizeof(T);
-        return offset;
-    }
-    size_t end8() { return take<unsigned char>(0, 8); }  // the size so far, rounded up to 8
-};
-
-// poses as the kernels read them: x, y, cos_yaw, sin_yaw of m poses one array after the other, and the trims 0-based
-void stage_poses(double* in, size_t m, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw, int32_t* trim0 = nullptr,
-                 const int32_t* trim = nullptr) {
-    std::memcpy(in, x, m * sizeof(double));
-    std::memcpy(in + m, y, m * sizeof(double));
-    std::memcpy(in + 2 * m, cos_yaw, m * sizeof(double));
-    std::memcpy(in + 3 * m, sin_yaw, m * sizeof(double));
-    if (trim0)
-        for (size_t v = 0; v < m; ++v) trim0[v] = trim[v] - 1;
-}
 
 // one kernel launch between t's events, created on first use (t.fold() after the caller's synchronise)
 template <class Args>
@@ -775,57 +749,10 @@ int pdmpc_fca_kernel_ms(pdmpc_handle* h, double* ms) {
     return PDMPC_OK;
 }
 
-// ---- human-driven vehicles on the device (hdv_kernel.hip)
+// ---- human-driven vehicles on the device (hdv_kernel.hip).  The plan of a call is host-only code (hdv_call_host.hpp:
+// the workspace layout, the caller's arrays as records, check, zero, stage, arguments, scatter); the handle's buffers, the two copies,
+// the launch and the synchronisation are here.
 namespace {
-// HdvMapSlot::table: the map (HdvMapData's arrays) and the HDV automaton's local hulls (x of every vertex, then y)
-struct HdvTable {
-    size_t pt_off, pts, succ_off, succ_idx, rel, local_off, local_xy, total;
-};
-HdvTable hdv_table(const HdvMapData& m, int n_polygons, int local_tot) {
-    Carver c;
-    HdvTable T;
-    T.pt_off = c.take<int32_t>((size_t)m.n_lanelets + 1);
-    T.pts = c.take<double>((size_t)6 * m.n_pts);
-    T.succ_off = c.take<int32_t>((size_t)m.n_lanelets + 1);
-    T.succ_idx = c.take<int32_t>((size_t)m.n_succ);
-    T.rel = c.take<uint8_t>((size_t)m.n_lanelets * m.n_lanelets);
-    T.local_off = c.take<int32_t>((size_t)n_polygons + 1);
-    T.local_xy = c.take<double>((size_t)2 * local_tot);
-    T.total = c.end8();
-    return T;
-}
-// HdvState::ws and its pinned staging: the inputs are the block's first in_bytes, what the call reads back everything from `out` on
-// (the packed vertices last: x of `capacity` vertices, then y)
-struct HdvLayout {
-    size_t in, cav, trim, cav_lanelet, in_bytes, n_chains, chain_id, chain_succ, slot_n, slot_flags;
-    size_t out, status, n_closest, closest, row_hdv, set_off, set_flags, adjacency, set_xy, total;
-};
-HdvLayout hdv_layout(int n, int nc, int Hp, int capacity) {
-    const size_t lists = (size_t)n * PDMPC_HDV_MAX_CHAINS, slots = lists * Hp;
-    Carver c;
-    HdvLayout L;
-    L.in = c.take<double>((size_t)6 * n);
-    L.cav = c.take<double>((size_t)4 * nc);
-    L.trim = c.take<int32_t>((size_t)n);
-    L.cav_lanelet = c.take<int32_t>((size_t)nc);
-    L.in_bytes = c.end8();
-    L.n_chains = c.take<int32_t>((size_t)n);
-    L.chain_id = c.take<int32_t>(lists);
-    L.chain_succ = c.take<int32_t>(lists);
-    L.slot_n = c.take<int32_t>(slots);
-    L.slot_flags = c.take<uint8_t>(slots);
-    L.out = c.end8();
-    L.status = c.take<int32_t>(2);
-    L.n_closest = c.take<int32_t>((size_t)n);
-    L.closest = c.take<int32_t>(lists);
-    L.row_hdv = c.take<int32_t>(lists);
-    L.set_off = c.take<int32_t>(slots + 1);
-    L.set_flags = c.take<uint8_t>(slots);
-    L.adjacency = c.take<uint8_t>((size_t)nc * n);
-    L.set_xy = c.take<double>((size_t)2 * capacity);
-    L.total = c.at;
-    return L;
-}
 // what the kernels read of a map slot: the views into its device table
 HdvMapRecord hdv_record(const HdvMapSlot& M) {
     const HdvTable T = hdv_table(M.data.map, M.data.trims * M.data.Hp, M.data.local_tot);
@@ -837,72 +764,6 @@ HdvMapRecord hdv_record(const HdvMapSlot& M) {
     R.local_off = (const int32_t*)(tb + T.local_off);
     return R;
 }
-// ... of the grouped call for n HDVs and nc CAVs in G groups with `pairs` (CAV, HDV) pairs: hdv_layout's regions over all groups, the
-// groups' records and lookups among the inputs, the scan's results
-// With a drive pass in front (n_route >= 0: the lanelet ids of all routes): the routes, old states, desired speeds and parameters among
-// the inputs, the new states, speeds, gaps and poses among what is read back.
-struct HdvGroupedLayout {
-    size_t in, cav, trim, cav_lanelet, groups, group_of, pair_first, drives, route_off, route_id, closed, state_seg, state_u, v_des, params, in_bytes;
-    size_t n_chains, chain_id, chain_succ, slot_n, slot_flags, slot_before, row_base;
-    size_t out, status, n_rows, set_base, n_closest, closest, row_hdv, set_off, set_flags, adjacency, new_seg, new_u, speed, gap, pose, set_xy, total;
-};
-HdvGroupedLayout hdv_grouped_ws(int G, int n, int nc, size_t pairs, int Hp, int capacity, int n_route = -1) {
-    const size_t dn = n_route < 0 ? 0 : (size_t)n, dG = n_route < 0 ? 0 : (size_t)G;  // (no drive pass: its regions are empty)
-    const size_t lists = (size_t)n * PDMPC_HDV_MAX_CHAINS, slots = lists * Hp;
-    Carver c;
-    HdvGroupedLayout L;
-    L.in = c.take<double>((size_t)6 * n);
-    L.cav = c.take<double>((size_t)4 * nc);
-    L.trim = c.take<int32_t>((size_t)n);
-    L.cav_lanelet = c.take<int32_t>((size_t)nc);
-    L.groups = c.take<HdvGroup>((size_t)G);
-    L.group_of = c.take<int32_t>((size_t)n);
-    L.pair_first = c.take<int32_t>((size_t)G + 1);
-    L.drives = c.take<uint8_t>(dG);
-    L.route_off = c.take<int32_t>(dn ? dn + 1 : 0);
-    L.route_id = c.take<int32_t>(n_route < 0 ? 0 : (size_t)n_route);
-    L.closed = c.take<uint8_t>(dn);
-    L.state_seg = c.take<int32_t>(2 * dn);
-    L.state_u = c.take<double>(dn);
-    L.v_des = c.take<double>(dn);
-    L.params = c.take<double>(PDMPC_HDV_DRIVE_PARAMS * dG);
-    L.in_bytes = c.end8();
-    L.n_chains = c.take<int32_t>((size_t)n);
-    L.chain_id = c.take<int32_t>(lists);
-    L.chain_succ = c.take<int32_t>(lists);
-    L.slot_n = c.take<int32_t>(slots);
-    L.slot_flags = c.take<uint8_t>(slots);
-    L.slot_before = c.take<int32_t>(slots);
-    L.row_base = c.take<int32_t>((size_t)n);
-    L.out = c.end8();
-    L.status = c.take<int32_t>(2);
-    L.n_rows = c.take<int32_t>((size_t)G);
-    L.set_base = c.take<int32_t>((size_t)G + 1);
-    L.n_closest = c.take<int32_t>((size_t)n);
-    L.closest = c.take<int32_t>(lists);
-    L.row_hdv = c.take<int32_t>(lists);
-    L.set_off = c.take<int32_t>(slots + G + 1);
-    L.set_flags = c.take<uint8_t>(slots);
-    L.adjacency = c.take<uint8_t>(pairs);
-    L.new_seg = c.take<int32_t>(2 * dn);
-    L.new_u = c.take<double>(dn);
-    L.speed = c.take<double>(dn);
-    L.gap = c.take<double>(dn);
-    L.pose = c.take<double>(4 * dn);
-    L.set_xy = c.take<double>((size_t)2 * capacity);
-    L.total = c.at;
-    return L;
-}
-// the drive pass of a grouped call: what pdmpc_hdv_drive_grouped and pdmpc_hdv_drive_traffic_grouped take beyond pdmpc_hdv_traffic_grouped
-struct HdvDriveCall {
-    const uint8_t* drives;  // [n_groups], or null: every group drives
-    const int32_t *route_offset, *route_lanelet;
-    const uint8_t* closed;
-    const int32_t* state_seg;
-    const double *state_u, *v_des, *parameters, *dt;
-    int32_t* new_seg;
-    double *new_u, *x, *y, *cos_yaw, *sin_yaw, *speed, *gap;
-};
 }  // namespace
 
 int pdmpc_upload_hdv_map_slot(pdmpc_handle* h, int32_t slot, int32_t n_lanelets, const int32_t* left_offset, const int32_t* right_offset, const double* left_x,
@@ -984,328 +845,59 @@ int pdmpc_hdv_traffic(pdmpc_handle* h, int32_t n_hdv, const double* x, const dou
     if (const int rc = hdv_check_call(M0.data.map.n_lanelets, M0.data.trims, n_hdv, x, y, cos_yaw, sin_yaw, trim, tile_dx, tile_dy, n_cav, cav_x, cav_y, cav_lanelet, cav_tile_dx,
                                       cav_tile_dy, closest_offset, closest_index, capacity, n_rows, row_hdv, set_offset, adjacency, &why))
         return fail(rc, std::string("pdmpc_hdv_traffic: ") + why);
-    *n_rows = 0;
-    closest_offset[0] = 0;
-    set_offset[0] = 0;
-    if (n_hdv == 0) return PDMPC_OK;
-    const int Hp = M0.data.Hp, n = n_hdv, nc = n_cav;
-    const size_t lists = (size_t)n * PDMPC_HDV_MAX_CHAINS, slots = lists * Hp;
-    // (no more vertices are read back than the slots can hold, whatever room the caller has)
-    const int cap = (int)std::min<size_t>((size_t)capacity, set_x && set_y ? slots * PDMPC_BOUND_SLOT : 0);
+    const HdvGroups G{0, nullptr, nullptr, nullptr, tile_dx, tile_dy, cav_x, cav_y, cav_tile_dx, cav_tile_dy};
+    const HdvTrafficCall T{x, y, cos_yaw, sin_yaw, trim, cav_lanelet, closest_offset, closest_index, capacity, n_rows, row_hdv, set_offset, nullptr, set_x, set_y, set_flags, adjacency};
+    const HdvPlan P = hdv_plan_one(n_hdv, n_cav, M0.data.Hp, T);
+    hdv_zero_outputs(G, &T, P);
+    if (P.n == 0) return PDMPC_OK;
     ON_DEVICE(h->cfg.device);
-    const HdvLayout L = hdv_layout(n, nc, Hp, cap);
-    if (S.ws.ensure(L.total) || S.slots.ensure(2 * slots * PDMPC_BOUND_SLOT) || S.h_in.ensure(L.in_bytes) || S.h_out.ensure(L.total - L.out))
+    const HdvWs L = hdv_ws(0, P);
+    if (S.ws.ensure(L.total) || S.slots.ensure(hdv_slot_doubles(P)) || S.h_in.ensure(L.in_bytes) || S.h_out.ensure(L.total - L.out))
         return fail(PDMPC_ERR_HIP, "hipMalloc failed for the HDV traffic call");
-    unsigned char *hin = S.h_in.p, *ws = S.ws.p;
-    double* in = (double*)(hin + L.in);
-    stage_poses(in, (size_t)n, x, y, cos_yaw, sin_yaw, (int32_t*)(hin + L.trim), trim);
-    std::memcpy(in + 4 * (size_t)n, tile_dx, (size_t)n * sizeof(double));
-    std::memcpy(in + 5 * (size_t)n, tile_dy, (size_t)n * sizeof(double));
-    if (nc) {
-        stage_poses((double*)(hin + L.cav), (size_t)nc, cav_x, cav_y, cav_tile_dx, cav_tile_dy);
-        std::memcpy(hin + L.cav_lanelet, cav_lanelet, (size_t)nc * sizeof(int32_t));
-    }
+    hdv_stage(S.h_in.p, L, P, G, &T, nullptr);
     const HdvMapRecord R = hdv_record(M0);
-    HdvArgs A;
-    A.map = R.map;
-    A.n_hdv = n;
-    A.n_cav = nc;
-    A.Hp = Hp;
-    A.capacity = cap;
-    A.local_x = R.local_x;
-    A.local_y = R.local_y;
-    A.local_off = R.local_off;
-    A.in = (const double*)(ws + L.in);
-    A.trim = (const int32_t*)(ws + L.trim);
-    A.cav = (const double*)(ws + L.cav);
-    A.cav_lanelet = (const int32_t*)(ws + L.cav_lanelet);
-    A.n_closest = (int32_t*)(ws + L.n_closest);
-    A.closest = (int32_t*)(ws + L.closest);
-    A.n_chains = (int32_t*)(ws + L.n_chains);
-    A.chain_id = (int32_t*)(ws + L.chain_id);
-    A.chain_succ = (int32_t*)(ws + L.chain_succ);
-    A.slot_x = S.slots.p;
-    A.slot_y = S.slots.p + slots * PDMPC_BOUND_SLOT;
-    A.slot_n = (int32_t*)(ws + L.slot_n);
-    A.slot_flags = ws + L.slot_flags;
-    A.status = (int32_t*)(ws + L.status);
-    A.row_hdv = (int32_t*)(ws + L.row_hdv);
-    A.set_off = (int32_t*)(ws + L.set_off);
-    A.set_flags = ws + L.set_flags;
-    A.set_x = (double*)(ws + L.set_xy);
-    A.set_y = A.set_x + cap;
-    A.adjacency = ws + L.adjacency;
-    HIPCHK(hipMemcpyAsync(ws, hin, L.in_bytes, hipMemcpyHostToDevice, h->stream));
+    const HdvArgs A = hdv_args(L, P, S.ws.p, S.slots.p, &R);
+    HIPCHK(hipMemcpyAsync(S.ws.p, S.h_in.p, L.in_bytes, hipMemcpyHostToDevice, h->stream));
     if (const int rc = timed_launch(h, S.timed, pdmpc_launch_hdv_traffic, A, "HDV traffic")) return rc;
-    HIPCHK(hipMemcpyAsync(S.h_out.p, ws + L.out, L.total - L.out, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(S.h_out.p, S.ws.p + L.out, L.total - L.out, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(sync_stream(h));
     S.timed.fold();
-    auto back = [&](size_t at) { return (const unsigned char*)S.h_out.p + (at - L.out); };  // the read-back block at the workspace's offsets
-    const int32_t* status = (const int32_t*)back(L.status);
-    *n_rows = -1;
-    if (status[1] & PDMPC_HDV_OVER_LISTS) return fail(PDMPC_ERR_CAPACITY, "pdmpc_hdv_traffic: an HDV has more than PDMPC_HDV_MAX_CHAINS closest lanelets or chains");
-    const int32_t *n_closest = (const int32_t*)back(L.n_closest), *closest = (const int32_t*)back(L.closest);
-    for (int g = 0; g < n; ++g) {
-        std::memcpy(closest_index + closest_offset[g], closest + (size_t)g * PDMPC_HDV_MAX_CHAINS, (size_t)n_closest[g] * sizeof(int32_t));
-        closest_offset[g + 1] = closest_offset[g] + n_closest[g];
-    }
-    const int rows = status[0];
-    *n_rows = rows;
-    std::memcpy(row_hdv, back(L.row_hdv), (size_t)rows * sizeof(int32_t));
-    std::memcpy(set_offset, back(L.set_off), ((size_t)rows * Hp + 1) * sizeof(int32_t));
-    if (nc) std::memcpy(adjacency, back(L.adjacency), (size_t)nc * n);
-    if (status[1] & PDMPC_HDV_OVER_SLOT) return fail(PDMPC_ERR_CAPACITY, "pdmpc_hdv_traffic: a reachable lane has more than PDMPC_BOUNDED_MAX_COLS vertices");
-    const int32_t total = set_offset[(size_t)rows * Hp];
-    if (capacity < total || (total && (!set_x || !set_y))) return fail(PDMPC_ERR_CAPACITY, "pdmpc_hdv_traffic: capacity too small for the reachable lanes");
-    const double* hx = (const double*)back(L.set_xy);
-    if (total) {
-        std::memcpy(set_x, hx, (size_t)total * sizeof(double));
-        std::memcpy(set_y, hx + cap, (size_t)total * sizeof(double));
-    }
-    if (set_flags) std::memcpy(set_flags, back(L.set_flags), (size_t)rows * Hp);
+    if (const int rc = hdv_scatter_one(S.h_out.p, L, P, T, &why)) return fail(rc, why);
     return PDMPC_OK;
 }
 
-// The grouped calls: the five passes of the traffic call (traffic), the drive pass in front of them (drive), or the drive pass alone.
-// Without the traffic passes the poses, trims, CAV lanelets and every traffic output are not read (null).
-static int hdv_grouped_call(pdmpc_handle* h, const std::string& who, bool traffic, const HdvDriveCall* drive, int32_t n_groups, const int32_t* group_slot,
-                            const int32_t* hdv_offset, const int32_t* cav_offset, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw,
-                            const int32_t* trim, const double* tile_dx, const double* tile_dy, const double* cav_x, const double* cav_y, const int32_t* cav_lanelet,
-                            const double* cav_tile_dx, const double* cav_tile_dy, int32_t* closest_offset, int32_t* closest_index, int32_t capacity, int32_t* n_rows,
-                            int32_t* row_hdv, int32_t* set_offset, int32_t* set_base, double* set_x, double* set_y, uint8_t* set_flags, uint8_t* adjacency) {
+// The grouped calls: the five passes of the traffic call (T), the drive pass in front of them (D and T), or the drive pass alone (D).
+static int hdv_call(pdmpc_handle* h, const char* who, const HdvGroups& G, const HdvTrafficCall* T, const HdvDriveCall* D) {
     if (!h) return fail(PDMPC_ERR_INVALID, "null handle");
     HdvState& S = h->hdv;
-    if (n_groups < 0 || capacity < 0 || (n_groups && (!group_slot || !hdv_offset || !cav_offset)) ||
-        (traffic && (!set_base || (n_groups && (!closest_offset || !n_rows || !set_offset)))))
-        return fail(PDMPC_ERR_INVALID, who + "bad argument");
-    if (n_groups == 0) {
-        if (traffic) set_base[0] = 0;
-        return PDMPC_OK;
-    }
-    if (hdv_offset[0] != 0 || cav_offset[0] != 0) return fail(PDMPC_ERR_INVALID, who + "offsets that do not start at 0");
-    int Hp = 0;
-    for (int g = 0; g < n_groups; ++g) {
-        const std::string group = who + "group " + std::to_string(g) + ": ";
-        if (hdv_offset[g + 1] < hdv_offset[g] || cav_offset[g + 1] < cav_offset[g]) return fail(PDMPC_ERR_INVALID, group + "offsets decrease");
-        if (group_slot[g] < 0 || group_slot[g] >= PDMPC_HDV_MAP_SLOTS) return fail(PDMPC_ERR_INVALID, group + "map slot out of range");
-        const HdvMapSlot& M = S.map[group_slot[g]];
-        if (!M.valid) return fail(PDMPC_ERR_INVALID, group + "no map was uploaded into its slot");
-        if (traffic && Hp && M.data.Hp != Hp) return fail(PDMPC_ERR_INVALID, group + "the Hp of its slot differs from the slots of the groups before");
-        Hp = traffic ? M.data.Hp : 1;
-    }
-    const int n = hdv_offset[n_groups], nc = cav_offset[n_groups];
-    std::vector<int32_t> closest_at((size_t)n_groups + 1), list_at((size_t)n_groups + 1), set_offset_at((size_t)n_groups + 1), set_at((size_t)n_groups + 1);
-    std::vector<int64_t> adjacency_at((size_t)n_groups + 1);
-    if (const int rc = hdv_grouped_layout(n_groups, hdv_offset, cav_offset, Hp, closest_at.data(), list_at.data(), set_offset_at.data(), set_at.data(), adjacency_at.data()))
-        return fail(rc, who + "bad offsets");
-    const int64_t pairs = adjacency_at[(size_t)n_groups];
-    for (int g = 0; g < n_groups; ++g)
-        if (hdv_offset[g + 1] - hdv_offset[g] > PDMPC_HDV_MAX_VEHICLES || cav_offset[g + 1] - cav_offset[g] > PDMPC_HDV_MAX_CAVS)
-            return fail(PDMPC_ERR_CAPACITY, who + "group " + std::to_string(g) + ": more than PDMPC_HDV_MAX_VEHICLES HDVs or PDMPC_HDV_MAX_CAVS CAVs");
-    if (n > PDMPC_HDV_GROUPED_MAX_VEHICLES) return fail(PDMPC_ERR_CAPACITY, who + "more than PDMPC_HDV_GROUPED_MAX_VEHICLES HDVs in the call");
-    if (pairs > INT32_MAX) return fail(PDMPC_ERR_CAPACITY, who + "2^31 or more (CAV, HDV) pairs");
-    if (n && (!tile_dx || !tile_dy || (traffic && (!x || !y || !cos_yaw || !sin_yaw || !trim || !closest_index || !row_hdv)))) return fail(PDMPC_ERR_INVALID, who + "a null HDV array");
-    if (nc && (!cav_x || !cav_y || !cav_tile_dx || !cav_tile_dy || (traffic && !cav_lanelet))) return fail(PDMPC_ERR_INVALID, who + "a null CAV array");
-    if (traffic && pairs && !adjacency) return fail(PDMPC_ERR_INVALID, who + "no adjacency array");
-    // the drive pass: routes and states of the groups that drive against their maps (an HDV of a group that does not drive has no route)
-    int n_route = -1;
-    if (drive) {
-        if (!drive->route_offset || drive->route_offset[0] != 0 || !drive->parameters || !drive->dt ||
-            (n && (!drive->closed || !drive->state_seg || !drive->state_u || !drive->v_des || !drive->new_seg || !drive->new_u || !drive->x || !drive->y || !drive->cos_yaw ||
-                   !drive->sin_yaw || !drive->speed || !drive->gap)))
-            return fail(PDMPC_ERR_INVALID, who + "a null driver array, or route offsets that do not start at 0");
-        for (int q = 0; q < n; ++q)
-            if (drive->route_offset[q + 1] < drive->route_offset[q]) return fail(PDMPC_ERR_INVALID, who + "route offsets decrease");
-        n_route = drive->route_offset[n];
-        for (int g = 0; g < n_groups; ++g) {
-            if (drive->drives && !drive->drives[g]) continue;
-            const int h0 = hdv_offset[g], ng = hdv_offset[g + 1] - h0;
-            const HdvMapData& map = S.map[group_slot[g]].data.map;
-            std::string why;
-            int rc = hdv_check_routes(map, ng, drive->route_offset + h0, drive->route_lanelet, drive->closed + h0, &why);
-            if (!rc) rc = hdv_check_states(map, ng, drive->route_offset + h0, drive->route_lanelet, drive->closed + h0, drive->state_seg + h0, drive->state_seg + n + h0, drive->state_u + h0, &why);
-            if (!rc) rc = hdv_check_drive(drive->parameters + 4 * (size_t)g, drive->dt[g], ng, drive->v_des + h0, &why);
-            if (rc) return fail(rc, who + "group " + std::to_string(g) + ": " + why);
-        }
-    }
-    for (int g = 0; traffic && g < n_groups; ++g) {
-        const HdvSlotData& D = S.map[group_slot[g]].data;
-        for (int q = hdv_offset[g]; q < hdv_offset[g + 1]; ++q)
-            if (trim[q] < 1 || trim[q] > D.trims) return fail(PDMPC_ERR_INVALID, who + "group " + std::to_string(g) + ": trim out of range");
-        for (int v = cav_offset[g]; v < cav_offset[g + 1]; ++v)
-            if (cav_lanelet[v] < 1 || cav_lanelet[v] > D.map.n_lanelets) return fail(PDMPC_ERR_INVALID, who + "group " + std::to_string(g) + ": a CAV's lanelet id out of range");
-    }
-    for (int g = 0; traffic && g < n_groups; ++g) {  // what has a size whatever happens
-        n_rows[g] = 0;
-        closest_offset[closest_at[(size_t)g]] = 0;
-        set_offset[set_offset_at[(size_t)g]] = 0;
-        set_base[g] = 0;
-    }
-    if (traffic) set_base[n_groups] = 0;
-    if (n == 0) return PDMPC_OK;
-    const size_t lists = (size_t)n * PDMPC_HDV_MAX_CHAINS, slots = lists * Hp;
-    // (no more vertices are read back than the slots can hold, whatever room the caller has)
-    const int cap = (int)std::min<size_t>((size_t)capacity, traffic && set_x && set_y ? slots * PDMPC_BOUND_SLOT : 0);
+    const HdvSlotData* slot[PDMPC_HDV_MAP_SLOTS];
+    for (int s = 0; s < PDMPC_HDV_MAP_SLOTS; ++s) slot[s] = S.map[s].valid ? &S.map[s].data : nullptr;
+    HdvPlan P;
+    std::string why;
+    if (const int rc = hdv_check_grouped(who, G, T, D, slot, P, &why)) return fail(rc, why);
+    hdv_zero_outputs(G, T, P);
+    if (P.n == 0) return PDMPC_OK;
     ON_DEVICE(h->cfg.device);
-    const HdvGroupedLayout L = hdv_grouped_ws(n_groups, n, nc, (size_t)pairs, Hp, cap, n_route);
+    const HdvWs L = hdv_ws(G.n_groups, P);
     // (the slots of the lane pass: what this call needs, without head room -- 256 KB x Hp per HDV)
-    if (S.ws.ensure(L.total) || (traffic && S.slots.ensure_exact(2 * slots * PDMPC_BOUND_SLOT)) || S.h_in.ensure(L.in_bytes) || S.h_out.ensure(L.total - L.out))
+    if (S.ws.ensure(L.total) || (T && S.slots.ensure_exact(hdv_slot_doubles(P))) || S.h_in.ensure(L.in_bytes) || S.h_out.ensure(L.total - L.out))
         return fail(PDMPC_ERR_HIP, "hipMalloc failed for the grouped HDV traffic call");
-    unsigned char *hin = S.h_in.p, *ws = S.ws.p;
-    double* in = (double*)(hin + L.in);
-    if (traffic)
-        stage_poses(in, (size_t)n, x, y, cos_yaw, sin_yaw, (int32_t*)(hin + L.trim), trim);
-    else
-        std::memset(hin + L.in, 0, (size_t)4 * n * sizeof(double));
-    std::memcpy(in + 4 * (size_t)n, tile_dx, (size_t)n * sizeof(double));
-    std::memcpy(in + 5 * (size_t)n, tile_dy, (size_t)n * sizeof(double));
-    if (nc) {
-        stage_poses((double*)(hin + L.cav), (size_t)nc, cav_x, cav_y, cav_tile_dx, cav_tile_dy);
-        if (traffic) std::memcpy(hin + L.cav_lanelet, cav_lanelet, (size_t)nc * sizeof(int32_t));
-    }
-    HdvGroup* groups = (HdvGroup*)(hin + L.groups);
-    int32_t *group_of = (int32_t*)(hin + L.group_of), *pair_first = (int32_t*)(hin + L.pair_first);
-    for (int g = 0; g < n_groups; ++g) {
-        groups[g] = HdvGroup{group_slot[g], hdv_offset[g], hdv_offset[g + 1] - hdv_offset[g], cav_offset[g], cav_offset[g + 1] - cav_offset[g]};
-        for (int q = hdv_offset[g]; q < hdv_offset[g + 1]; ++q) group_of[q] = g;
-        pair_first[g] = (int32_t)adjacency_at[(size_t)g];
-    }
-    pair_first[n_groups] = (int32_t)pairs;
-    HdvDriveTrafficArgs DT;
-    std::memset(&DT, 0, sizeof DT);
-    HdvGroupedArgs& GA = DT.g;
-    HdvArgs& A = GA.a;
-    A.n_hdv = n;
-    A.n_cav = nc;
-    A.Hp = Hp;
-    A.capacity = cap;
-    A.in = (const double*)(ws + L.in);
-    A.trim = (const int32_t*)(ws + L.trim);
-    A.cav = (const double*)(ws + L.cav);
-    A.cav_lanelet = (const int32_t*)(ws + L.cav_lanelet);
-    A.n_closest = (int32_t*)(ws + L.n_closest);
-    A.closest = (int32_t*)(ws + L.closest);
-    A.n_chains = (int32_t*)(ws + L.n_chains);
-    A.chain_id = (int32_t*)(ws + L.chain_id);
-    A.chain_succ = (int32_t*)(ws + L.chain_succ);
-    A.slot_x = S.slots.p;
-    A.slot_y = S.slots.p + slots * PDMPC_BOUND_SLOT;
-    A.slot_n = (int32_t*)(ws + L.slot_n);
-    A.slot_flags = ws + L.slot_flags;
-    A.status = (int32_t*)(ws + L.status);
-    A.row_hdv = (int32_t*)(ws + L.row_hdv);
-    A.set_off = (int32_t*)(ws + L.set_off);
-    A.set_flags = ws + L.set_flags;
-    A.set_x = (double*)(ws + L.set_xy);
-    A.set_y = A.set_x + cap;
-    A.adjacency = ws + L.adjacency;
-    GA.maps = S.maps.p;
-    GA.groups = (const HdvGroup*)(ws + L.groups);
-    GA.group_of = (const int32_t*)(ws + L.group_of);
-    GA.pair_first = (const int32_t*)(ws + L.pair_first);
-    GA.n_groups = n_groups;
-    GA.n_pairs = (int32_t)pairs;
-    GA.slot_before = (int32_t*)(ws + L.slot_before);
-    GA.row_base = (int32_t*)(ws + L.row_base);
-    GA.n_rows = (int32_t*)(ws + L.n_rows);
-    GA.set_base = (int32_t*)(ws + L.set_base);
-    if (drive) {
-        uint8_t* drives = hin + L.drives;
-        for (int g = 0; g < n_groups; ++g) {
-            drives[g] = drive->drives ? (drive->drives[g] ? 1 : 0) : 1;
-            double* P = (double*)(hin + L.params) + (size_t)g * PDMPC_HDV_DRIVE_PARAMS;
-            std::memcpy(P, drive->parameters + 4 * (size_t)g, 4 * sizeof(double));
-            P[4] = drive->dt[g];
-        }
-        std::memcpy(hin + L.route_off, drive->route_offset, ((size_t)n + 1) * sizeof(int32_t));
-        if (n_route) std::memcpy(hin + L.route_id, drive->route_lanelet, (size_t)n_route * sizeof(int32_t));
-        std::memcpy(hin + L.closed, drive->closed, (size_t)n);
-        std::memcpy(hin + L.state_seg, drive->state_seg, (size_t)2 * n * sizeof(int32_t));
-        std::memcpy(hin + L.state_u, drive->state_u, (size_t)n * sizeof(double));
-        std::memcpy(hin + L.v_des, drive->v_des, (size_t)n * sizeof(double));
-        HdvDriveArgs& D = DT.d;
-        D.maps = S.maps.p;
-        D.groups = GA.groups;
-        D.group_of = GA.group_of;
-        D.drives = ws + L.drives;
-        D.n_hdv = n;
-        D.n_cav = nc;
-        D.route_off = (const int32_t*)(ws + L.route_off);
-        D.route_id = (const int32_t*)(ws + L.route_id);
-        D.closed = ws + L.closed;
-        D.state_seg = (const int32_t*)(ws + L.state_seg);
-        D.state_u = (const double*)(ws + L.state_u);
-        D.v_des = (const double*)(ws + L.v_des);
-        D.params = (const double*)(ws + L.params);
-        D.cav = A.cav;
-        D.in = (double*)(ws + L.in);
-        D.new_seg = (int32_t*)(ws + L.new_seg);
-        D.new_u = (double*)(ws + L.new_u);
-        D.speed = (double*)(ws + L.speed);
-        D.gap = (double*)(ws + L.gap);
-        D.pose = (double*)(ws + L.pose);
-    }
-    HIPCHK(hipMemcpyAsync(ws, hin, L.in_bytes, hipMemcpyHostToDevice, h->stream));
-    if (drive && traffic) {
-        if (const int rc = timed_launch(h, S.timed, pdmpc_launch_hdv_drive_traffic_grouped, DT, "grouped HDV drive and traffic")) return rc;
-    } else if (drive) {
-        if (const int rc = timed_launch(h, S.timed, pdmpc_launch_hdv_drive, DT.d, "grouped HDV drive")) return rc;
+    hdv_stage(S.h_in.p, L, P, G, T, D);
+    HdvDriveTrafficArgs A{};
+    A.g = hdv_grouped_args(G.n_groups, L, P, S.ws.p, S.slots.p, S.maps.p);
+    if (D) A.d = hdv_drive_args(L, P, S.ws.p, S.maps.p);
+    HIPCHK(hipMemcpyAsync(S.ws.p, S.h_in.p, L.in_bytes, hipMemcpyHostToDevice, h->stream));
+    if (D && T) {
+        if (const int rc = timed_launch(h, S.timed, pdmpc_launch_hdv_drive_traffic_grouped, A, "grouped HDV drive and traffic")) return rc;
+    } else if (D) {
+        if (const int rc = timed_launch(h, S.timed, pdmpc_launch_hdv_drive, A.d, "grouped HDV drive")) return rc;
     } else {
-        if (const int rc = timed_launch(h, S.timed, pdmpc_launch_hdv_traffic_grouped, GA, "grouped HDV traffic")) return rc;
+        if (const int rc = timed_launch(h, S.timed, pdmpc_launch_hdv_traffic_grouped, A.g, "grouped HDV traffic")) return rc;
     }
-    HIPCHK(hipMemcpyAsync(S.h_out.p, ws + L.out, L.total - L.out, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(S.h_out.p, S.ws.p + L.out, L.total - L.out, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(sync_stream(h));
     S.timed.fold();
-    auto back = [&](size_t at) { return (const unsigned char*)S.h_out.p + (at - L.out); };  // the read-back block at the workspace's offsets
-    if (drive)  // the groups that drove: their HDVs' blocks of every output, the others' entries are left as they are
-        for (int g = 0; g < n_groups; ++g) {
-            if (drive->drives && !drive->drives[g]) continue;
-            const size_t h0 = (size_t)hdv_offset[g], ng = (size_t)hdv_offset[g + 1] - h0;
-            const int32_t* seg = (const int32_t*)back(L.new_seg);
-            const double* pose = (const double*)back(L.pose);
-            std::memcpy(drive->new_seg + h0, seg + h0, ng * sizeof(int32_t));
-            std::memcpy(drive->new_seg + n + h0, seg + n + h0, ng * sizeof(int32_t));
-            std::memcpy(drive->new_u + h0, (const double*)back(L.new_u) + h0, ng * sizeof(double));
-            std::memcpy(drive->speed + h0, (const double*)back(L.speed) + h0, ng * sizeof(double));
-            std::memcpy(drive->gap + h0, (const double*)back(L.gap) + h0, ng * sizeof(double));
-            std::memcpy(drive->x + h0, pose + h0, ng * sizeof(double));
-            std::memcpy(drive->y + h0, pose + n + h0, ng * sizeof(double));
-            std::memcpy(drive->cos_yaw + h0, pose + 2 * (size_t)n + h0, ng * sizeof(double));
-            std::memcpy(drive->sin_yaw + h0, pose + 3 * (size_t)n + h0, ng * sizeof(double));
-        }
-    if (!traffic) return PDMPC_OK;
-    const int32_t* status = (const int32_t*)back(L.status);
-    const int32_t *rows_of = (const int32_t*)back(L.n_rows), *n_closest = (const int32_t*)back(L.n_closest), *closest = (const int32_t*)back(L.closest);
-    // the outputs stand on the device where the caller's arrays have them: every group's blocks are copied as they are
-    int over = -1;  // the first group with an HDV whose lists ran over
-    for (int g = 0; g < n_groups; ++g) {
-        const int h0 = hdv_offset[g], ng = hdv_offset[g + 1] - h0, rows = rows_of[g];
-        n_rows[g] = rows;
-        if (rows < 0) {
-            if (over < 0) over = g;
-            continue;
-        }
-        int32_t* co = closest_offset + closest_at[(size_t)g];
-        for (int q = 0; q < ng; ++q) {
-            std::memcpy(closest_index + list_at[(size_t)g] + co[q], closest + (size_t)(h0 + q) * PDMPC_HDV_MAX_CHAINS, (size_t)n_closest[h0 + q] * sizeof(int32_t));
-            co[q + 1] = co[q] + n_closest[h0 + q];
-        }
-        if (rows) std::memcpy(row_hdv + list_at[(size_t)g], (const int32_t*)back(L.row_hdv) + list_at[(size_t)g], (size_t)rows * sizeof(int32_t));
-        std::memcpy(set_offset + set_offset_at[(size_t)g], (const int32_t*)back(L.set_off) + set_offset_at[(size_t)g], ((size_t)rows * Hp + 1) * sizeof(int32_t));
-        if (set_flags && rows) std::memcpy(set_flags + set_at[(size_t)g], back(L.set_flags) + set_at[(size_t)g], (size_t)rows * Hp);
-    }
-    std::memcpy(set_base, back(L.set_base), ((size_t)n_groups + 1) * sizeof(int32_t));
-    if (pairs) std::memcpy(adjacency, back(L.adjacency), (size_t)pairs);
-    const int32_t total = set_base[n_groups];
-    const bool fits = capacity >= total && (!total || (set_x && set_y)) && !(status[1] & PDMPC_HDV_OVER_SLOT);
-    if (fits && total) {
-        const double* hx = (const double*)back(L.set_xy);
-        std::memcpy(set_x, hx, (size_t)total * sizeof(double));
-        std::memcpy(set_y, hx + cap, (size_t)total * sizeof(double));
-    }
-    if (over >= 0) return fail(PDMPC_ERR_CAPACITY, who + "group " + std::to_string(over) + ": an HDV has more than PDMPC_HDV_MAX_CHAINS closest lanelets or chains");
-    if (status[1] & PDMPC_HDV_OVER_SLOT) return fail(PDMPC_ERR_CAPACITY, who + "a reachable lane has more than PDMPC_BOUNDED_MAX_COLS vertices");
-    if (!fits) return fail(PDMPC_ERR_CAPACITY, who + "capacity too small for the reachable lanes");
+    if (const int rc = hdv_scatter(who, S.h_out.p, L, P, G, T, D, &why)) return fail(rc, why);
     return PDMPC_OK;
 }
 
@@ -1314,18 +906,18 @@ int pdmpc_hdv_traffic_grouped(pdmpc_handle* h, int32_t n_groups, const int32_t* 
                               const double* cav_x, const double* cav_y, const int32_t* cav_lanelet, const double* cav_tile_dx, const double* cav_tile_dy,
                               int32_t* closest_offset, int32_t* closest_index, int32_t capacity, int32_t* n_rows, int32_t* row_hdv, int32_t* set_offset,
                               int32_t* set_base, double* set_x, double* set_y, uint8_t* set_flags, uint8_t* adjacency) {
-    return hdv_grouped_call(h, "pdmpc_hdv_traffic_grouped: ", true, nullptr, n_groups, group_slot, hdv_offset, cav_offset, x, y, cos_yaw, sin_yaw, trim, tile_dx, tile_dy, cav_x,
-                            cav_y, cav_lanelet, cav_tile_dx, cav_tile_dy, closest_offset, closest_index, capacity, n_rows, row_hdv, set_offset, set_base, set_x, set_y, set_flags,
-                            adjacency);
+    const HdvGroups G{n_groups, group_slot, hdv_offset, cav_offset, tile_dx, tile_dy, cav_x, cav_y, cav_tile_dx, cav_tile_dy};
+    const HdvTrafficCall T{x, y, cos_yaw, sin_yaw, trim, cav_lanelet, closest_offset, closest_index, capacity, n_rows, row_hdv, set_offset, set_base, set_x, set_y, set_flags, adjacency};
+    return hdv_call(h, "pdmpc_hdv_traffic_grouped: ", G, &T, nullptr);
 }
 
 int pdmpc_hdv_drive_grouped(pdmpc_handle* h, int32_t n_groups, const int32_t* group_slot, const int32_t* hdv_offset, const int32_t* cav_offset, const int32_t* route_offset,
                             const int32_t* route_lanelet, const uint8_t* closed, const int32_t* state_seg, const double* state_u, const double* tile_dx, const double* tile_dy,
                             const double* v_des, const double* cav_x, const double* cav_y, const double* cav_tile_dx, const double* cav_tile_dy, const double* parameters,
                             const double* dt, int32_t* new_seg, double* new_u, double* x, double* y, double* cos_yaw, double* sin_yaw, double* speed, double* gap) {
+    const HdvGroups G{n_groups, group_slot, hdv_offset, cav_offset, tile_dx, tile_dy, cav_x, cav_y, cav_tile_dx, cav_tile_dy};
     const HdvDriveCall D{nullptr, route_offset, route_lanelet, closed, state_seg, state_u, v_des, parameters, dt, new_seg, new_u, x, y, cos_yaw, sin_yaw, speed, gap};
-    return hdv_grouped_call(h, "pdmpc_hdv_drive_grouped: ", false, &D, n_groups, group_slot, hdv_offset, cav_offset, nullptr, nullptr, nullptr, nullptr, nullptr, tile_dx, tile_dy,
-                            cav_x, cav_y, nullptr, cav_tile_dx, cav_tile_dy, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    return hdv_call(h, "pdmpc_hdv_drive_grouped: ", G, nullptr, &D);
 }
 
 int pdmpc_hdv_drive_traffic_grouped(pdmpc_handle* h, int32_t n_groups, const int32_t* group_slot, const int32_t* hdv_offset, const int32_t* cav_offset, const uint8_t* drives,
@@ -1336,10 +928,10 @@ int pdmpc_hdv_drive_traffic_grouped(pdmpc_handle* h, int32_t n_groups, const int
                                     int32_t* closest_index, int32_t capacity, int32_t* n_rows, int32_t* row_hdv, int32_t* set_offset, int32_t* set_base, double* set_x,
                                     double* set_y, uint8_t* set_flags, uint8_t* adjacency) {
     if (!drives) return fail(PDMPC_ERR_INVALID, "pdmpc_hdv_drive_traffic_grouped: no drive flags");
+    const HdvGroups G{n_groups, group_slot, hdv_offset, cav_offset, tile_dx, tile_dy, cav_x, cav_y, cav_tile_dx, cav_tile_dy};
+    const HdvTrafficCall T{x, y, cos_yaw, sin_yaw, trim, cav_lanelet, closest_offset, closest_index, capacity, n_rows, row_hdv, set_offset, set_base, set_x, set_y, set_flags, adjacency};
     const HdvDriveCall D{drives, route_offset, route_lanelet, closed, state_seg, state_u, v_des, parameters, dt, new_seg, new_u, x, y, cos_yaw, sin_yaw, speed, gap};
-    return hdv_grouped_call(h, "pdmpc_hdv_drive_traffic_grouped: ", true, &D, n_groups, group_slot, hdv_offset, cav_offset, x, y, cos_yaw, sin_yaw, trim, tile_dx, tile_dy, cav_x,
-                            cav_y, cav_lanelet, cav_tile_dx, cav_tile_dy, closest_offset, closest_index, capacity, n_rows, row_hdv, set_offset, set_base, set_x, set_y, set_flags,
-                            adjacency);
+    return hdv_call(h, "pdmpc_hdv_drive_traffic_grouped: ", G, &T, &D);
 }
 
 int pdmpc_hdv_kernel_ms(pdmpc_handle* h, double* ms) {

@@ -181,6 +181,37 @@ def test_capacity_protocol_with_the_drive_pass_in_front(handle):
     assert np.isnan(raw["set_x"][total - 1:]).all() and np.isnan(raw["set_y"][total - 1:]).all()
 
 
+def test_the_four_calls_take_turns_on_one_workspace(handle):
+    """pdmpc_hdv_traffic, pdmpc_hdv_traffic_grouped, pdmpc_hdv_drive_grouped and pdmpc_hdv_drive_traffic_grouped stage into and read back
+    from ONE workspace on the handle, under layouts of one function (csrc/hdv_call_host.hpp: hdv_ws) with other regions empty in each.
+    Ungrouped, grouped traffic, drive alone, drive and traffic, ungrouped again: each equals its host twin bit for bit, whatever the
+    call before it left in the workspace.  The lab map at Hp 1, two groups of (2 HDVs, 1 CAV) and (1 HDV, no CAV)."""
+    sets = H.local_sets(1)
+    handle.upload_hdv_map(D.lab(), sets, slot=LAB)
+    L, R = D.lab(), D.loop_route()
+    members = [(LAB, D.Member("two HDVs, a CAV ahead", L, [(R, 0.7, ZERO, 0.5), (R, 1.6, ZERO, 0.5)], [D.at(L, R, 1.3) + (ZERO,)])),
+               (LAB, D.Member("one HDV, no CAV", L, [(R, 3.0, ZERO, 0.5)], []))]
+    standing = [_traffic_reference(m, 1, False)[1] for _, m in members]  # the traffic at the poses the groups bring
+
+    def ungrouped(what):
+        g = _traffic_group(LAB, members[0][1], False)
+        cs = ([math.cos(a) for a in g["yaw"]], [math.sin(a) for a in g["yaw"]])
+        dev = hdv.hdv_traffic_native(L, sets, g["x"], g["y"], g["yaw"], g["trim"], g["tiles"], g["cav_x"], g["cav_y"], g["cav_lanelet"], g["cav_tile"], handle=handle, cos_sin=cs)
+        H.assert_same(dev, standing[0], what)
+
+    ungrouped("ungrouped, first")
+    plain = [_traffic_group(slot, m, False) for slot, m in members]
+    got = handle.hdv_traffic_grouped([(g["slot"], g["x"], g["y"], g["yaw"], g["trim"], g["tiles"], g["cav_x"], g["cav_y"], g["cav_lanelet"], g["cav_tile"]) for g in plain],
+                                     capacity=1 << 16)
+    for g, (t, ref) in enumerate(zip(got, standing)):
+        H.assert_same(t, ref, "grouped traffic, group %d" % g)
+    _assert_members(hdv.drive_grouped_native(handle, [m.group(slot) for slot, m in members]), members)
+    flags = [True, True]
+    _assert_combined(hdv.drive_traffic_grouped_native(handle, [_traffic_group(slot, m, f) for (slot, m), f in zip(members, flags)], capacity=1 << 16), members, flags, 1)
+    ungrouped("ungrouped, after the grouped calls")
+    assert sum(len(t["row_hdv"]) for t in standing) > 0 and int(standing[0]["adjacency"].size) == 2
+
+
 def test_refusals_leave_the_handle_working(handle):
     _upload(handle, 1)
     members = _members()

@@ -1,7 +1,8 @@
 """The host-only rules of the grouped HDV traffic call (csrc/hdv_grouped_host.hpp), without a GPU: the layout of the
 groups' blocks (pdmpc_hdv_grouped_layout_host) against a plain restatement, and tests/hdv_grouped_checks.cpp -- the layout again, the
-batching rule of the sweep's stage on a model of a handle, and the byte-for-byte content check of a map slot -- as a program of its own
-under the sanitizers (it carries their static runtime; nothing is preloaded)."""
+batching rule of the sweep's stage on a model of a handle, the byte-for-byte content check of a map slot, and the plan of the HDV device
+calls (csrc/hdv_call_host.hpp: workspace layout, arguments, stage and scatter, refusals) -- as a program of its own under the sanitizers
+(it carries their static runtime; nothing is preloaded)."""
 import os
 import shutil
 import subprocess
@@ -52,11 +53,14 @@ def test_layout_of_no_group_and_refusals():
 
 
 def test_the_layout_and_batching_header_names_no_hip():
-    code = [line.split("//")[0] for line in open(os.path.join(CSRC, "hdv_grouped_host.hpp"))]
-    assert not [line for line in code if "hip" in line.lower() or "handle.hpp" in line]
+    """... nor do the plan of the device calls (hdv_call_host.hpp) and the carver it shares with step_prep.cpp"""
     run = subprocess.run(["make", "-s", "-C", CSRC, "host-parts"], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout + run.stderr
-    assert "hdv_grouped_host.hpp" in [line.split()[-1] for line in run.stdout.splitlines() if line.startswith("also ok")], run.stdout
+    alone = [line.split()[-1] for line in run.stdout.splitlines() if line.startswith("also ok")]
+    for header in ("hdv_grouped_host.hpp", "hdv_call_host.hpp", "carver.hpp"):
+        code = [line.split("//")[0] for line in open(os.path.join(CSRC, header))]
+        assert not [line for line in code if "hip" in line.lower() or "handle.hpp" in line], header
+        assert header in alone, run.stdout
 
 
 @pytest.mark.skipif(shutil.which(HOST_CXX) is None, reason="no host compiler")
@@ -64,7 +68,13 @@ def test_hdv_grouped_checks_under_sanitizers(tmp_path):
     """tests/hdv_grouped_checks.cpp: the layout for the group sizes above at Hp 1 and 6 into arrays of exactly n_groups + 1 entries, no
     group, decreasing offsets; the batching rule -- 9 distinct maps give 8 + 1, members of 60, 60 and 60 HDVs 120 + 60, equal maps
     share a slot, a resident map costs no upload and a noted one no check, a moved generation forces the check, two controllers that
-    take turns upload once each --; the content check of a slot bit by bit.  Under -fsanitize=address,undefined."""
+    take turns upload once each --; the content check of a slot bit by bit.  The plan of the device calls: the workspace layout for these
+    groups with and without a drive pass and for the ungrouped call (alignment, no overlap, inputs in front of in_bytes, the read-back
+    from `out` on, sizes against sums written out, two layouts byte by byte); every pointer of the argument records at its region;
+    a call staged into a block of exactly in_bytes bytes and scattered from one of exactly total - out bytes into arrays of exactly the
+    stated sizes -- whole, one vertex short, a group over its lists, a slot over, the precedence of the three, with the drive pass,
+    without the traffic passes, ungrouped --; a table of refused calls against two model slots with code and full text, calls with two
+    faults among them.  Under -fsanitize=address,undefined."""
     exe = str(tmp_path / "hdv_grouped_checks")
     flags = ["-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
     build = subprocess.run([HOST_CXX] + flags + ["-o", exe, os.path.join(ROOT, "tests", "hdv_grouped_checks.cpp")], capture_output=True, text=True)
