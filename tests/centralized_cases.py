@@ -139,20 +139,26 @@ def twin_iters_from_a_moving_start(N, Hp, angle=0.0):
     return options, mpa, ctl.build_iters()
 
 
-def joint_soup_capacity(mpa, Hp):
-    """The soup columns (16 bytes each) layout_joint can give a problem when it takes the whole 160 KB of LDS and leaves the
-    automaton's areas in L2: 160 KB less the automaton's tables, the per-vehicle references, the node's areas, the offsets, the
-    successor lists and the smallest open list (256 entries of 12 bytes)."""
+JOINT_PASSES = ((64 * 1024, True), (64 * 1024, False), (160 * 1024, True), (160 * 1024, False))  # layout_joint's (budget, areas in LDS)
+
+
+def joint_soup_capacity(mpa, Hp, budget=160 * 1024, areas_in_lds=False):
+    """The soup columns (16 bytes each) layout_joint can give a problem in one of its passes (JOINT_PASSES; the default: the last one,
+    which takes the whole 160 KB of LDS and leaves the automaton's areas in L2): the budget less the automaton's tables, the
+    per-vehicle references, the node's areas, the offsets, the successor lists and the smallest open list (256 entries of 12
+    bytes).  A launch's soup_cap is the soup columns of its largest problem (pdmpc_joint_soup_columns) and two more."""
     a16 = lambda x: (x + 15) & ~15  # noqa: E731
     n = mpa.n_trims
     n_man = sum(1 for row in mpa.maneuvers for m in row if m is not None)
     off = a16(Hp * n * ((n + 63) // 64) * 8)
     off = a16(off + n * n * 2)
     off = a16(off + n_man * 32)
+    if areas_in_lds:
+        off = a16(off + n_man * 3 * abi.VMAX * 16)
     off += abi.JOINT_MAX * 3 * abi.HP_MAX * 8 + abi.JOINT_MAX * 2 * abi.VMAX * 16
     off = a16(off + (abi.JOINT_MAX * (abi.HP_MAX + 1) + 3 * abi.JOINT_MAX + abi.HP_MAX + 1) * 4)
     off = a16(off + abi.JOINT_MAX * n * 4)
-    return (160 * 1024 - 256 * 12 - off) // 16
+    return (budget - 256 * 12 - off) // 16
 
 
 def far_rectangles(count):

@@ -20,6 +20,7 @@ from pdmpc.config import Config
 import heap_cases as hc
 import joint_reference as jr
 import problems
+from joint_limit_cases import peak_open_list
 from test_gpu_joint import circle_iters
 from test_gpu_kernel_matrix import VARIANTS, first_true, is_capacity_error, set_tuning
 from test_gpu_parity import check_batch
@@ -71,18 +72,7 @@ def test_refusals_leave_the_handle_usable(handle):
 # ---------------------------------------------------------------- the replay of a graph search beyond its LDS part
 
 
-def peak_open_list(pops, parent):
-    """The longest open list of a search, from its trace: the root, then per pop minus one plus the popped node's children (ids and
-    parents 1-based).  Children beyond a cut trace are not counted: a lower bound then."""
-    n_children = np.bincount(np.asarray(parent), minlength=len(parent) + 1)
-    n, peak = 1, 1
-    for nd in pops:
-        n += int(n_children[nd]) - 1 if nd < len(n_children) else -1
-        peak = max(peak, n)
-    return peak
-
-
-LAYOUT = re.compile(r"pdmpc LDS layout( \(compact\))?: launch (\d+) waves (\d+)(?: areas \d)? near (\d+) ")
+LAYOUT =re.compile(r"pdmpc LDS layout( \(compact\))?: launch (\d+) waves (\d+)(?: areas \d)? near (\d+) ")
 
 # (variant of tests/test_gpu_kernel_matrix.py, problem_set seed, Hp, vehicle, extra tuning, wavefronts, near capacity, peak computed when this was written)
 REPLAY_CASES = [
