@@ -36,7 +36,7 @@ inline int hdv_grouped_layout(int32_t n_groups, const int32_t* hdv_offset, const
     return PDMPC_OK;
 }
 
-// ---- the members of a lock-step as batches (step_controller.cpp: hdv_traffic_stage)
+// ---- the members of a lock-step as batches (step_prepare.hpp: hdv_traffic_stage; step_hdv.hpp: the batch path)
 
 // what a controller remembers of the slot its map was found in or uploaded to: the slot still holds that map while the slot's
 // generation is the remembered one (every upload into a slot takes a new generation; 0: none)

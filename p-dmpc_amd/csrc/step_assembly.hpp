@@ -1,4 +1,4 @@
-// step_assembly.hpp — a member's step around the step preparation (step_controller.cpp, stage 5 of 7): its seeds, its priorities, and
+// step_assembly.hpp — a member's step around the step preparation (step_controller.cpp, stage 6 of 9): its seeds, its priorities, and
 // the stages begin_step, assemble_step and finish_step that build its StepProblem from the controller's parts.
 // What it restates (file:line relative to the reference root):
 //   obstacle assembly         PrioritizedController.plan / consider_predecessors / consider_successors (:297-324, 449-566)

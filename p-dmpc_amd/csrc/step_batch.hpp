@@ -1,4 +1,4 @@
-// step_batch.hpp — the batch of prioritizations of an explorative or optimal-priority step (step_controller.cpp, stage 6 of 7): its
+// step_batch.hpp — the batch of prioritizations of an explorative or optimal-priority step (step_controller.cpp, stage 7 of 9): its
 // instances, kept and flattened, and the choice among their plans as data.
 #pragma once
 #include <algorithm>

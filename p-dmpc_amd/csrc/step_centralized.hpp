@@ -1,4 +1,4 @@
-// step_centralized.hpp — centralized control (step_controller.cpp, stage 7 of 7): the joint problem of a controller's vehicles and the
+// step_centralized.hpp — centralized control (step_controller.cpp, stage 9 of 9): the joint problem of a controller's vehicles and the
 // plant update from its records.  No coupling, no priorities, no levels: the step preparation (build_members) has no part in it.
 // What it restates (file:line relative to the reference root), the C++ twin of p-dmpc_amd/pdmpc/centralized.py:
 //   the step                  CentralizedController.controller (hlc/controller/centralized/CentralizedController.m:33-59)

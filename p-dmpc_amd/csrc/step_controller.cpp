@@ -3,10 +3,12 @@
 //
 // What it restates (file:line relative to the reference root), the C++ twin of p-dmpc_amd/pdmpc/controller.py, in stages, each a header
 // that names only the ones before it and says at its head what it restates (`make host-parts` compiles each alone):
-// step_types.hpp (the records), step_inputs.hpp (what a step reads of the traffic), step_priorities.hpp (couplings -> a prioritization),
-// step_state.hpp (the controller as the parts that are written together), step_assembly.hpp (a member's StepProblem), step_batch.hpp (the
-// batches of prioritizations and the choice among their plans), step_centralized.hpp (centralized control: the joint problem).  This file: the step preparation over a span of members (build_members),
-// planning a built problem (plan_built), the steps and their loops, the sweep, every entry point of the C ABI, and
+// step_types.hpp (the records), step_inputs.hpp (what a step reads of the traffic), step_hdv.hpp (human-driven vehicles: a member's HDV
+// state, the solo and the batch path of the traffic stage), step_priorities.hpp (couplings -> a prioritization), step_state.hpp (the
+// controller as the parts that are written together), step_assembly.hpp (a member's StepProblem), step_batch.hpp (the batches of
+// prioritizations and the choice among their plans), step_prepare.hpp (the step preparation over a span of members: build_members),
+// step_centralized.hpp (centralized control: the joint problem).  This file: planning a built problem (plan_built), the steps and their
+// loops, the sweep, every entry point of the C ABI, and
 //   exhaustion, fallbacks     handle_graph_search_exhaustion / plan_fallback (:568-616, 678-718), check_others_fallback (:623-676),
 //                             HighLevelController.handle_others_fallback (HighLevelController.m:449-463)
 //   plant                     Simulation.apply (plant/Simulation.m:86-100)
@@ -21,32 +23,18 @@
 #include <vector>
 
 #include "../../include/pdmpc.h"
-#include "hdv_drive_host.hpp"    // the checks of the HDV drivers' parameters (host only)
-#include "hdv_grouped_host.hpp"  // the batches of the HDV traffic stage (host only)
 #include "step_types.hpp"  // the stages, in their order
 #include "step_inputs.hpp"
+#include "step_hdv.hpp"
 #include "step_priorities.hpp"
 #include "step_state.hpp"
 #include "step_assembly.hpp"
 #include "step_batch.hpp"
+#include "step_prepare.hpp"
 #include "step_centralized.hpp"
 
 namespace {
-
 // ---- the shared paths of the steps below (templates: outside the extern "C" block)
-// A bounding call that writes its sets into (x, y) of capacity x.size() and their offsets into off: after PDMPC_ERR_CAPACITY it is
-// made once more with the room it asked for (off.back()).  The one capacity retry of the step preparation.
-template <class Bound>
-int bound_with_room(std::vector<int32_t>& off, std::vector<double>& x, std::vector<double>& y, Bound&& bound) {
-    int rc = bound((int32_t)x.size(), x.empty() ? nullptr : x.data(), y.empty() ? nullptr : y.data());
-    if (rc == PDMPC_ERR_CAPACITY && off.back() > (int32_t)x.size()) {
-        x.resize((size_t)off.back());
-        y.resize((size_t)off.back());
-        rc = bound((int32_t)x.size(), x.data(), y.data());
-    }
-    return rc;
-}
-
 // the twin over a group of each backend call a built problem is planned with
 using PlanRecords = int (*)(pdmpc_handle*, int32_t, const pdmpc_vehicle_in*, const int32_t*, const int32_t*, const pdmpc_polygon_set*, pdmpc_vehicle_out*);
 using PlanLean = int (*)(pdmpc_handle*, int32_t, const pdmpc_vehicle_in*, const int32_t*, const int32_t*, const pdmpc_polygon_set*, int32_t*, double*);
@@ -103,602 +91,6 @@ int timed_steps(int32_t n_steps, double* ms, Step&& step) {
     return PDMPC_OK;
 }
 
-// ---- ONE step preparation over a span of members: a sweep's members, or the one controller that steps alone
-// the poses of the members `who` one after the other (and their lanelet polygons: with_lanelets)
-void gather(pdmpc_controller* const* members, PrepScratch::Call& C, const std::vector<int>& who, bool with_lanelets) {
-    C.who = who;
-    C.group_offset.assign(1, 0);
-    C.x.clear();
-    C.y.clear();
-    C.cos_yaw.clear();
-    C.sin_yaw.clear();
-    C.trim.clear();
-    C.lan_off.assign(1, 0);
-    C.lan_x.clear();
-    C.lan_y.clear();
-    for (int m : who) {
-        pdmpc_controller* c = members[m];
-        C.x.insert(C.x.end(), c->tr.mx.begin(), c->tr.mx.end());
-        C.y.insert(C.y.end(), c->tr.my.begin(), c->tr.my.end());
-        C.cos_yaw.insert(C.cos_yaw.end(), c->reach.cos_yaw.begin(), c->reach.cos_yaw.end());
-        C.sin_yaw.insert(C.sin_yaw.end(), c->reach.sin_yaw.begin(), c->reach.sin_yaw.end());
-        C.trim.insert(C.trim.end(), c->in.trims.begin(), c->in.trims.end());
-        C.group_offset.push_back((int32_t)C.x.size());
-        if (with_lanelets) {
-            lanelet_polygons(c->sc, c->in, c->reach);
-            const int32_t base = (int32_t)C.lan_x.size(), nl = c->reach.lan_off[(size_t)c->sc.n];
-            C.lan_x.insert(C.lan_x.end(), c->reach.lan_x.begin(), c->reach.lan_x.begin() + nl);
-            C.lan_y.insert(C.lan_y.end(), c->reach.lan_y.begin(), c->reach.lan_y.begin() + nl);
-            for (int v = 0; v < c->sc.n; ++v) C.lan_off.push_back(base + c->reach.lan_off[(size_t)v + 1]);
-        }
-    }
-    C.lan_x.push_back(0.0);  // (never empty)
-    C.lan_y.push_back(0.0);
-    size_t entries = 0;
-    for (size_t g = 0; g + 1 < C.group_offset.size(); ++g) entries += (size_t)(C.group_offset[g + 1] - C.group_offset[g]) * (C.group_offset[g + 1] - C.group_offset[g]);
-    C.adjacency.assign(entries + 1, 0);
-}
-// the blocks of a grouped coupler call -> c->in.adjacency of the members that couple by reachable sets
-void scatter_blocks(pdmpc_controller* const* members, const PrepScratch::Call& C) {
-    size_t block = 0;
-    for (int m : C.who) {
-        pdmpc_controller* c = members[m];
-        const size_t nn = (size_t)c->sc.n * c->sc.n;
-        if (c->sc.cfg.coupling == PDMPC_COUPLING_REACHABLE_SET) c->in.adjacency.assign(C.adjacency.begin() + block, C.adjacency.begin() + block + nn);
-        block += nn;
-    }
-}
-bool any_couples_by_sets(pdmpc_controller* const* members, const std::vector<int>& who) {
-    for (int m : who)
-        if (members[m]->sc.cfg.coupling == PDMPC_COUPLING_REACHABLE_SET) return true;
-    return false;
-}
-
-// lanelet bounding of the members `who` (one all_steps for all of them) in ONE device call on the concatenated vehicles, then the
-// coupler on the bounded step-Hp sets (on the device they are still there), grouped by member
-int bound_on_device(pdmpc_handle* h, pdmpc_controller* const* members, PrepScratch& S, const std::vector<int>& who, bool all_steps) {
-    if (who.empty()) return PDMPC_OK;
-    PrepScratch::Call& C = S.call;
-    gather(members, C, who, true);
-    const int Hp = members[who[0]]->sc.Hp, sets_each = all_steps ? Hp : 1, n = C.group_offset.back();
-    const pdmpc_polygon_set lan = view_polygons(C.lan_off, C.lan_x, C.lan_y);
-    C.set_off.assign((size_t)n * sets_each + 1, 0);
-    S.prep_calls[0] += 1;
-    int rc = bound_with_room(C.set_off, C.set_x, C.set_y, [&](int32_t cap, double* ox, double* oy) {
-        return pdmpc_bound_reachable_sets(h, n, C.x.data(), C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(), C.trim.data(), &lan, all_steps, cap, C.set_off.data(), ox, oy, nullptr);
-    });
-    if (rc) return cfail(nullptr, rc, std::string("pdmpc_bound_reachable_sets: ") + pdmpc_last_error());
-    for (size_t g = 0; g < who.size(); ++g) {  // every member's own sets, offsets from 0, as a bounding call for it alone leaves them
-        pdmpc_controller* c = members[who[g]];
-        const size_t o0 = (size_t)C.group_offset[g] * sets_each, sets = (size_t)c->sc.n * sets_each;
-        const int32_t a = C.set_off[o0], total = C.set_off[o0 + sets] - a;
-        c->reach.bound_off.resize(sets + 1);
-        for (size_t o = 0; o <= sets; ++o) c->reach.bound_off[o] = C.set_off[o0 + o] - a;
-        if (c->reach.bound_x.size() < (size_t)total) {
-            c->reach.bound_x.resize((size_t)total);
-            c->reach.bound_y.resize((size_t)total);
-        }
-        std::copy(C.set_x.begin() + a, C.set_x.begin() + a + total, c->reach.bound_x.begin());
-        std::copy(C.set_y.begin() + a, C.set_y.begin() + a + total, c->reach.bound_y.begin());
-        adopt_bounded_sets(c->sc, c->reach, all_steps);
-    }
-    if (!any_couples_by_sets(members, who)) return PDMPC_OK;
-    S.prep_calls[1] += 1;
-    rc = pdmpc_bounded_set_coupling_grouped(h, (int32_t)who.size(), C.group_offset.data(), C.adjacency.data(), nullptr);
-    if (rc) return cfail(nullptr, rc, std::string("pdmpc_bounded_set_coupling_grouped: ") + pdmpc_last_error());
-    scatter_blocks(members, C);
-    return PDMPC_OK;
-}
-// ... without a handle: every member's own bounding on the host twin (on its own table of local hulls), then the grouped host twin of
-// the coupler on the members' step-Hp sets
-int bound_on_host(pdmpc_controller* const* members, PrepScratch& S, const std::vector<int>& who) {
-    if (who.empty()) return PDMPC_OK;
-    PrepScratch::Call& C = S.call;
-    for (int m : who) {
-        pdmpc_controller* c = members[m];
-        const bool all_steps = S.prep[(size_t)m].reach_parallel;
-        lanelet_polygons(c->sc, c->in, c->reach);
-        const pdmpc_polygon_set lan = view_polygons(c->reach.lan_off, c->reach.lan_x, c->reach.lan_y), local = view_polygons(c->sc.reach_off, c->sc.reach_x, c->sc.reach_y);
-        c->reach.bound_off.assign((size_t)c->sc.n * (all_steps ? c->sc.Hp : 1) + 1, 0);
-        S.prep_calls[0] += 1;
-        const int rc = bound_with_room(c->reach.bound_off, c->reach.bound_x, c->reach.bound_y, [&](int32_t cap, double* ox, double* oy) {
-            return pdmpc_bound_reachable_sets_host((int32_t)c->sc.trim_speed.size(), c->sc.Hp, &local, c->sc.n, c->tr.mx.data(), c->tr.my.data(), c->reach.cos_yaw.data(), c->reach.sin_yaw.data(),
-                                                   c->in.trims.data(), &lan, all_steps, cap, c->reach.bound_off.data(), ox, oy, nullptr);
-        });
-        if (rc) return cfail(c, rc, "pdmpc_bound_reachable_sets_host failed");
-        adopt_bounded_sets(c->sc, c->reach, all_steps);
-    }
-    if (!any_couples_by_sets(members, who)) return PDMPC_OK;
-    gather(members, C, who, false);
-    C.set_off.assign(1, 0);
-    C.set_x.clear();
-    C.set_y.clear();
-    for (int m : who) {
-        pdmpc_controller* c = members[m];
-        const int sets_each = S.prep[(size_t)m].reach_parallel ? c->sc.Hp : 1;
-        for (int v = 0; v < c->sc.n; ++v) {
-            const int o = v * sets_each + sets_each - 1, a = c->reach.bound_off[o], cnt = c->reach.bound_off[o + 1] - a;
-            C.set_x.insert(C.set_x.end(), c->reach.bound_x.begin() + a, c->reach.bound_x.begin() + a + cnt);
-            C.set_y.insert(C.set_y.end(), c->reach.bound_y.begin() + a, c->reach.bound_y.begin() + a + cnt);
-            C.set_off.push_back((int32_t)C.set_x.size());
-        }
-    }
-    C.set_x.push_back(0.0);
-    C.set_y.push_back(0.0);
-    const pdmpc_polygon_set ps = view_polygons(C.set_off, C.set_x, C.set_y);
-    S.prep_calls[1] += 1;
-    const int rc = pdmpc_polygon_set_coupling_grouped_host(&ps, (int32_t)who.size(), C.group_offset.data(), C.adjacency.data(), nullptr);
-    if (rc) return cfail(nullptr, rc, "pdmpc_polygon_set_coupling_grouped_host failed");
-    scatter_blocks(members, C);
-    return PDMPC_OK;
-}
-// the coupler on the unbounded step-Hp hulls of the members `who` (ReachableSetCoupler.m:5-56), grouped by member: with a handle the
-// members share its table of local hulls (as they share its automaton) ...
-int couple_hulls_on_device(pdmpc_handle* h, pdmpc_controller* const* members, PrepScratch& S, const std::vector<int>& who) {
-    if (who.empty()) return PDMPC_OK;
-    PrepScratch::Call& C = S.call;
-    gather(members, C, who, false);
-    S.prep_calls[2] += 1;
-    const int rc = pdmpc_reachable_set_coupling_grouped(h, (int32_t)who.size(), C.group_offset.data(), C.x.data(), C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(), C.trim.data(),
-                                                        C.adjacency.data(), nullptr);
-    if (rc) return cfail(nullptr, rc, std::string("pdmpc_reachable_set_coupling_grouped: ") + pdmpc_last_error());
-    scatter_blocks(members, C);
-    return PDMPC_OK;
-}
-// ... without one, members that hold the same table share a call of the grouped host twin
-int couple_hulls_on_host(pdmpc_controller* const* members, PrepScratch& S, const std::vector<int>& who) {
-    PrepScratch::Call& C = S.call;
-    std::vector<int> rest = who, same, other;
-    while (!rest.empty()) {
-        const pdmpc_controller* c0 = members[rest[0]];
-        same.clear();
-        other.clear();
-        for (int m : rest) {
-            const pdmpc_controller* c = members[m];
-            (c->sc.reach_off == c0->sc.reach_off && c->sc.reach_x == c0->sc.reach_x && c->sc.reach_y == c0->sc.reach_y ? same : other).push_back(m);
-        }
-        gather(members, C, same, false);
-        const pdmpc_polygon_set ps = view_polygons(c0->sc.reach_off, c0->sc.reach_x, c0->sc.reach_y);
-        S.prep_calls[2] += 1;
-        const int rc = pdmpc_reachable_set_coupling_grouped_host((int32_t)c0->sc.trim_speed.size(), c0->sc.Hp, &ps, (int32_t)same.size(), C.group_offset.data(), C.x.data(),
-                                                                 C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(), C.trim.data(), C.adjacency.data(), nullptr);
-        if (rc) return cfail(nullptr, rc, "pdmpc_reachable_set_coupling_grouped_host failed");
-        scatter_blocks(members, C);
-        rest = other;
-    }
-    return PDMPC_OK;
-}
-
-// the inputs of the future collision assessment of the members `who` (their adjacency is there) as ONE grouped call takes them: every
-// member with its own coupled pairs, scenario obstacles and vehicle sizes, the reference points member after member
-int gather_fca(pdmpc_controller* const* members, PrepScratch::Fca& F, const std::vector<int>& who) {
-    F.groups.assign(who.size(), pdmpc_fca_group());
-    F.obstacles.resize(who.size());
-    F.x.clear();
-    F.y.clear();
-    F.cos_yaw.clear();
-    F.sin_yaw.clear();
-    size_t n = 0;
-    for (size_t g = 0; g < who.size(); ++g) {
-        pdmpc_controller* c = members[who[g]];
-        if (!fca_inputs(c->sc, c->in, c->fca)) return cfail(c, PDMPC_ERR_INVALID, "FCA priorities need Hp >= 2 (calculate_yaw needs two reference points)");
-        F.x.insert(F.x.end(), c->fca.x.begin(), c->fca.x.end());
-        F.y.insert(F.y.end(), c->fca.y.begin(), c->fca.y.end());
-        F.cos_yaw.insert(F.cos_yaw.end(), c->fca.cos_yaw.begin(), c->fca.cos_yaw.end());
-        F.sin_yaw.insert(F.sin_yaw.end(), c->fca.sin_yaw.begin(), c->fca.sin_yaw.end());
-        F.obstacles[g] = view_polygons(c->fca.obst_off, c->fca.obst_x, c->fca.obst_y);
-        pdmpc_fca_group& G = F.groups[g];
-        G.n = c->sc.n;
-        G.n_pairs = (int32_t)(c->fca.pairs.size() / 2);
-        G.pairs = c->fca.pairs.data();
-        G.obstacles = &F.obstacles[g];
-        G.dynamic_rows = nullptr;
-        G.length = c->sc.cfg.vehicle_length;
-        G.width = c->sc.cfg.vehicle_width;
-        G.offset = c->sc.cfg.offset;
-        n += (size_t)c->sc.n;
-    }
-    F.collisions.assign(n, 0);
-    F.priorities.assign(n, 0);
-    return PDMPC_OK;
-}
-
-// ---- human-driven vehicles: the traffic-info stage over all members.  With a handle (on a group: its rank 0, which h
-// is) the members with HDVs are the groups of ONE pdmpc_hdv_traffic_grouped (hdv_grouped_host.hpp: a further call per
-// PDMPC_HDV_MAP_SLOTS distinct maps or PDMPC_HDV_GROUPED_MAX_VEHICLES HDVs); members whose maps are equal share a map slot of the handle,
-// and a map that is still resident -- the slot's generation as the member noted it, or the handle's byte-for-byte check -- is not
-// uploaded again.  Without a handle every such member calls the host twin.
-template <class T>
-bool same_bytes(const std::vector<T>& a, const std::vector<T>& b) {
-    return a.size() == b.size() && (a.empty() || !std::memcmp(a.data(), b.data(), a.size() * sizeof(T)));
-}
-bool same_hdv_map(const HdvTraffic& A, const HdvTraffic& B) {
-    return &A == &B || (A.n_trims == B.n_trims && same_bytes(A.lan_off, B.lan_off) && same_bytes(A.succ_off, B.succ_off) && same_bytes(A.succ_idx, B.succ_idx) &&
-                        same_bytes(A.rel, B.rel) && same_bytes(A.local_off, B.local_off) && same_bytes(A.left_x, B.left_x) && same_bytes(A.left_y, B.left_y) &&
-                        same_bytes(A.right_x, B.right_x) && same_bytes(A.right_y, B.right_y) && same_bytes(A.local_x, B.local_x) && same_bytes(A.local_y, B.local_y));
-}
-// the room a member's results need (what its own traffic call would size)
-void hdv_size_results(pdmpc_controller* c) {
-    HdvTraffic& H = c->hdv;
-    const size_t lists = (size_t)H.n * PDMPC_HDV_MAX_CHAINS;
-    H.closest_off.assign((size_t)H.n + 1, 0);
-    H.closest_idx.resize(lists);
-    H.row_hdv.resize(lists);
-    H.set_off.assign(lists * c->sc.Hp + 1, 0);
-    H.set_flags.resize(lists * c->sc.Hp);
-    H.adjacency.assign((size_t)c->sc.n * H.n, 0);
-    if (H.set_x.size() < 4096) {
-        H.set_x.resize(4096);
-        H.set_y.resize(4096);
-    }
-}
-
-int hdv_traffic_on_host(pdmpc_controller* c) {
-    HdvTraffic& H = c->hdv;
-    const int n = c->sc.n, Hp = c->sc.Hp;
-    hdv_size_results(c);
-    const pdmpc_polygon_set local = view_polygons(H.local_off, H.local_x, H.local_y);
-    auto call = [&]() {
-        return pdmpc_hdv_traffic_host((int32_t)H.lan_off.size() - 1, H.lan_off.data(), H.lan_off.data(), H.left_x.data(), H.left_y.data(), H.right_x.data(), H.right_y.data(),
-                                      H.succ_off.data(), H.succ_idx.data(), H.rel.data(), H.n_trims, Hp, &local, H.n, H.x.data(), H.y.data(), H.cos_yaw.data(), H.sin_yaw.data(),
-                                      H.trim.data(), H.tile_dx.data(), H.tile_dy.data(), n, c->tr.mx.data(), c->tr.my.data(), c->in.current_lanelet.data(), H.cav_tile_dx.data(),
-                                      H.cav_tile_dy.data(), H.closest_off.data(), H.closest_idx.data(), (int32_t)H.set_x.size(), &H.n_rows, H.row_hdv.data(), H.set_off.data(),
-                                      H.set_x.data(), H.set_y.data(), H.set_flags.data(), H.adjacency.data());
-    };
-    int rc = call();
-    if (rc == PDMPC_ERR_CAPACITY && H.n_rows >= 0 && (size_t)H.set_off[(size_t)H.n_rows * Hp] > H.set_x.size()) {  // (the offsets size the second call)
-        const size_t need = (size_t)H.set_off[(size_t)H.n_rows * Hp];
-        H.set_x.resize(need + need / 4);
-        H.set_y.resize(need + need / 4);
-        rc = call();
-    }
-    if (rc) return cfail(c, rc, "pdmpc_hdv_traffic_host failed");
-    H.gather(n, Hp);
-    return PDMPC_OK;
-}
-
-// the yaw of the driven poses, for read-back only (the traffic passes read cos and sin as the driver step gave them)
-void hdv_driven_yaw(HdvTraffic& H) {
-    H.yaw.resize((size_t)H.n);
-    for (int q = 0; q < H.n; ++q) H.yaw[(size_t)q] = std::atan2(H.sin_yaw[(size_t)q], H.cos_yaw[(size_t)q]);
-}
-
-// What a member's HDVs are measured as at this built step.  A recording: its next row.  Drivers: *drives = 1 if they move this step
-// (every built step but the first after pdmpc_controller_set_hdv_drivers, whose measurement is the placement).
-void hdv_begin_build(pdmpc_controller* c, bool* drives) {
-    HdvTraffic& H = c->hdv;
-    *drives = false;
-    if (H.rec_T > 0) {
-        H.rec_builds += 1;
-        const size_t row = (size_t)(std::min(H.rec_builds, H.rec_T) - 1) * H.n;
-        H.x.assign(H.rec_x.begin() + row, H.rec_x.begin() + row + H.n);
-        H.y.assign(H.rec_y.begin() + row, H.rec_y.begin() + row + H.n);
-        H.yaw.assign(H.rec_yaw.begin() + row, H.rec_yaw.begin() + row + H.n);
-        H.cos_yaw.resize((size_t)H.n);
-        H.sin_yaw.resize((size_t)H.n);
-        for (int q = 0; q < H.n; ++q) {
-            H.cos_yaw[(size_t)q] = std::cos(H.yaw[(size_t)q]);
-            H.sin_yaw[(size_t)q] = std::sin(H.yaw[(size_t)q]);
-        }
-        H.measured = true;
-    }
-    if (H.driven) {
-        H.driven_builds += 1;
-        *drives = H.driven_builds > 1;
-    }
-}
-
-// the driver step of one member on the host (pdmpc_hdv_drive_host), in front of its traffic call
-int hdv_drive_on_host(pdmpc_controller* c) {
-    HdvTraffic& H = c->hdv;
-    const int rc = pdmpc_hdv_drive_host((int32_t)H.lan_off.size() - 1, H.lan_off.data(), H.lan_off.data(), H.left_x.data(), H.left_y.data(), H.right_x.data(), H.right_y.data(),
-                                        H.succ_off.data(), H.succ_idx.data(), H.rel.data(), H.n, H.route_off.data(), H.route_id.data(), H.route_closed.data(), H.seg.data(),
-                                        H.u.data(), H.tile_dx.data(), H.tile_dy.data(), H.v_des.data(), c->sc.n, c->tr.mx.data(), c->tr.my.data(), H.cav_tile_dx.data(),
-                                        H.cav_tile_dy.data(), H.drive_params, c->sc.cfg.dt_seconds, H.new_seg.data(), H.new_u.data(), H.x.data(), H.y.data(), H.cos_yaw.data(),
-                                        H.sin_yaw.data(), H.speed.data(), H.gap.data());
-    if (rc) return cfail(c, rc, std::string("pdmpc_hdv_drive_host: ") + pdmpc_last_error());
-    H.seg.swap(H.new_seg);
-    H.u.swap(H.new_u);
-    hdv_driven_yaw(H);
-    return PDMPC_OK;
-}
-
-// the members of batch B (their maps are in the slots B.slot) as the groups of one call, and every member's blocks back into its own
-// arrays, as its own call leaves them.  The capacity retry is here, once: the room is the last total and a quarter.
-int hdv_call_for_batch(pdmpc_handle* h, pdmpc_controller* const* members, const HdvBatch& B, PrepScratch::Hdv& C, const std::vector<uint8_t>& drives_of) {
-    const int G = (int)B.members.size(), Hp = members[B.members[0]]->sc.Hp;
-    bool any_drives = false;
-    for (auto* v : {&C.drives, &C.route_closed}) v->clear();
-    for (auto* v : {&C.route_id, &C.seg_r, &C.seg_j}) v->clear();
-    for (auto* v : {&C.u, &C.v_des, &C.params, &C.dt}) v->clear();
-    C.route_off.assign(1, 0);
-    for (auto* v : {&C.slot, &C.trim, &C.cav_lanelet}) v->clear();
-    for (auto* v : {&C.x, &C.y, &C.cos_yaw, &C.sin_yaw, &C.tile_dx, &C.tile_dy, &C.cav_x, &C.cav_y, &C.cav_tile_dx, &C.cav_tile_dy}) v->clear();
-    C.hdv_offset.assign(1, 0);
-    C.cav_offset.assign(1, 0);
-    auto append = [](auto& to, const auto& from, size_t count) { to.insert(to.end(), from.begin(), from.begin() + (ptrdiff_t)count); };
-    for (int g = 0; g < G; ++g) {
-        pdmpc_controller* c = members[B.members[(size_t)g]];
-        const HdvTraffic& H = c->hdv;
-        const size_t nh = (size_t)H.n, nc = (size_t)c->sc.n;
-        C.slot.push_back(B.slot[(size_t)B.map_of[(size_t)g]]);
-        append(C.x, H.x, nh);
-        append(C.y, H.y, nh);
-        append(C.cos_yaw, H.cos_yaw, nh);
-        append(C.sin_yaw, H.sin_yaw, nh);
-        append(C.trim, H.trim, nh);
-        append(C.tile_dx, H.tile_dx, nh);
-        append(C.tile_dy, H.tile_dy, nh);
-        append(C.cav_x, c->tr.mx, nc);
-        append(C.cav_y, c->tr.my, nc);
-        append(C.cav_lanelet, c->in.current_lanelet, nc);
-        append(C.cav_tile_dx, H.cav_tile_dx, nc);
-        append(C.cav_tile_dy, H.cav_tile_dy, nc);
-        C.hdv_offset.push_back((int32_t)C.x.size());
-        C.cav_offset.push_back((int32_t)C.cav_x.size());
-        // the drive pass: a member that does not move this step has no routes (the offsets do not move over its HDVs)
-        const bool drives = drives_of[(size_t)B.members[(size_t)g]] != 0;
-        any_drives = any_drives || drives;
-        C.drives.push_back(drives ? 1 : 0);
-        for (size_t q = 0; q < nh; ++q) {
-            if (drives) C.route_id.insert(C.route_id.end(), H.route_id.begin() + H.route_off[q], H.route_id.begin() + H.route_off[q + 1]);
-            C.route_off.push_back((int32_t)C.route_id.size());
-            C.route_closed.push_back(drives ? H.route_closed[q] : 0);
-            C.seg_r.push_back(drives ? H.seg[q] : 0);
-            C.seg_j.push_back(drives ? H.seg[nh + q] : 0);
-            C.u.push_back(drives ? H.u[q] : 0.0);
-            C.v_des.push_back(drives ? H.v_des[q] : 0.0);
-        }
-        for (int q = 0; q < 4; ++q) C.params.push_back(drives ? H.drive_params[q] : 1.0);
-        C.dt.push_back(c->sc.cfg.dt_seconds);
-    }
-    const size_t n_all = C.x.size();
-    C.seg = C.seg_r;
-    C.seg.insert(C.seg.end(), C.seg_j.begin(), C.seg_j.end());
-    C.seg.push_back(0);
-    C.route_id.push_back(0);
-    C.new_seg.assign(2 * n_all + 1, 0);
-    for (auto* v : {&C.new_u, &C.speed, &C.gap}) v->assign(n_all + 1, 0.0);
-    for (auto* v : {&C.closest_at, &C.list_at, &C.set_offset_at, &C.set_at}) v->assign((size_t)G + 1, 0);
-    C.adjacency_at.assign((size_t)G + 1, 0);
-    if (const int rc = pdmpc_hdv_grouped_layout_host(G, C.hdv_offset.data(), C.cav_offset.data(), Hp, C.closest_at.data(), C.list_at.data(), C.set_offset_at.data(), C.set_at.data(),
-                                                     C.adjacency_at.data()))
-        return cfail(nullptr, rc, "pdmpc_hdv_grouped_layout_host failed");
-    C.closest_off.assign((size_t)C.closest_at[(size_t)G], 0);
-    C.closest_idx.assign((size_t)C.list_at[(size_t)G] + 1, 0);
-    C.row_hdv.assign((size_t)C.list_at[(size_t)G] + 1, 0);
-    C.set_off.assign((size_t)C.set_offset_at[(size_t)G], 0);
-    C.set_flags.assign((size_t)C.set_at[(size_t)G] + 1, 0);
-    C.adjacency.assign((size_t)C.adjacency_at[(size_t)G] + 1, 0);
-    C.n_rows.assign((size_t)G, 0);
-    C.set_base.assign((size_t)G + 1, 0);
-    if (C.set_x.size() < 4096) {
-        C.set_x.resize(4096);
-        C.set_y.resize(4096);
-    }
-    auto call = [&]() {
-        if (any_drives)  // ONE call: the drive launch in front of the five (x, y, cos_yaw, sin_yaw of the members that drive are written)
-            return pdmpc_hdv_drive_traffic_grouped(h, G, C.slot.data(), C.hdv_offset.data(), C.cav_offset.data(), C.drives.data(), C.route_off.data(), C.route_id.data(),
-                                                   C.route_closed.data(), C.seg.data(), C.u.data(), C.v_des.data(), C.params.data(), C.dt.data(), C.new_seg.data(),
-                                                   C.new_u.data(), C.speed.data(), C.gap.data(), C.x.data(), C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(), C.trim.data(),
-                                                   C.tile_dx.data(), C.tile_dy.data(), C.cav_x.data(), C.cav_y.data(), C.cav_lanelet.data(), C.cav_tile_dx.data(),
-                                                   C.cav_tile_dy.data(), C.closest_off.data(), C.closest_idx.data(), (int32_t)C.set_x.size(), C.n_rows.data(), C.row_hdv.data(),
-                                                   C.set_off.data(), C.set_base.data(), C.set_x.data(), C.set_y.data(), C.set_flags.data(), C.adjacency.data());
-        return pdmpc_hdv_traffic_grouped(h, G, C.slot.data(), C.hdv_offset.data(), C.cav_offset.data(), C.x.data(), C.y.data(), C.cos_yaw.data(), C.sin_yaw.data(), C.trim.data(),
-                                         C.tile_dx.data(), C.tile_dy.data(), C.cav_x.data(), C.cav_y.data(), C.cav_lanelet.data(), C.cav_tile_dx.data(), C.cav_tile_dy.data(),
-                                         C.closest_off.data(), C.closest_idx.data(), (int32_t)C.set_x.size(), C.n_rows.data(), C.row_hdv.data(), C.set_off.data(), C.set_base.data(),
-                                         C.set_x.data(), C.set_y.data(), C.set_flags.data(), C.adjacency.data());
-    };
-    int rc = call();
-    if (rc == PDMPC_ERR_CAPACITY && *std::min_element(C.n_rows.begin(), C.n_rows.end()) >= 0 && (size_t)C.set_base[(size_t)G] > C.set_x.size()) {  // (the totals size the second call)
-        const size_t need = (size_t)C.set_base[(size_t)G];
-        C.set_x.resize(need + need / 4);
-        C.set_y.resize(need + need / 4);
-        rc = call();
-    }
-    if (rc) return cfail(nullptr, rc, std::string("pdmpc_hdv_traffic_grouped: ") + pdmpc_last_error());
-    for (int g = 0; g < G; ++g) {
-        pdmpc_controller* c = members[B.members[(size_t)g]];
-        HdvTraffic& H = c->hdv;
-        if (C.drives[(size_t)g]) {  // where the drive pass left the member's HDVs
-            const size_t h0 = (size_t)C.hdv_offset[(size_t)g], nh = (size_t)H.n;
-            for (size_t q = 0; q < nh; ++q) {
-                H.seg[q] = C.new_seg[h0 + q];
-                H.seg[nh + q] = C.new_seg[n_all + h0 + q];
-                H.u[q] = C.new_u[h0 + q];
-                H.speed[q] = C.speed[h0 + q];
-                H.gap[q] = C.gap[h0 + q];
-                H.x[q] = C.x[h0 + q];
-                H.y[q] = C.y[h0 + q];
-                H.cos_yaw[q] = C.cos_yaw[h0 + q];
-                H.sin_yaw[q] = C.sin_yaw[h0 + q];
-            }
-            hdv_driven_yaw(H);
-        }
-        hdv_size_results(c);
-        const size_t rows = (size_t)C.n_rows[(size_t)g], sets = rows * Hp, nh = (size_t)H.n;
-        const int32_t* so = C.set_off.data() + C.set_offset_at[(size_t)g];
-        const size_t total = (size_t)so[sets];
-        H.n_rows = (int32_t)rows;
-        std::copy_n(C.closest_off.begin() + C.closest_at[(size_t)g], nh + 1, H.closest_off.begin());
-        std::copy_n(C.closest_idx.begin() + C.list_at[(size_t)g], (size_t)H.closest_off[nh], H.closest_idx.begin());
-        std::copy_n(C.row_hdv.begin() + C.list_at[(size_t)g], rows, H.row_hdv.begin());
-        std::copy_n(so, sets + 1, H.set_off.begin());
-        std::copy_n(C.set_flags.begin() + C.set_at[(size_t)g], sets, H.set_flags.begin());
-        std::copy_n(C.adjacency.begin() + (ptrdiff_t)C.adjacency_at[(size_t)g], (size_t)c->sc.n * nh, H.adjacency.begin());
-        if (H.set_x.size() < total) {
-            H.set_x.resize(total + total / 4);
-            H.set_y.resize(total + total / 4);
-        }
-        std::copy_n(C.set_x.begin() + C.set_base[(size_t)g], total, H.set_x.begin());
-        std::copy_n(C.set_y.begin() + C.set_base[(size_t)g], total, H.set_y.begin());
-        H.gather(c->sc.n, Hp);
-    }
-    return PDMPC_OK;
-}
-
-int hdv_traffic_stage(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, PrepScratch& S) {
-    S.hdv_calls[0] = S.hdv_calls[1] = 0;
-    std::vector<int32_t> n_hdv(M, 0);
-    std::vector<uint8_t> drives(M, 0);
-    for (size_t m = 0; m < M; ++m) {
-        pdmpc_controller* c = members[m];
-        n_hdv[m] = c->hdv.n;
-        if (c->hdv.n) {
-            bool d = false;
-            hdv_begin_build(c, &d);
-            drives[m] = d ? 1 : 0;
-        }
-        if (c->hdv.n && !c->hdv.measured) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_measurements before the first step with HDVs");
-        if (c->hdv.n && !h) {
-            S.hdv_calls[0] += 1;
-            if (drives[m])
-                if (const int rc = hdv_drive_on_host(c)) return rc;
-            if (const int rc = hdv_traffic_on_host(c)) return rc;
-        }
-    }
-    if (!h) return PDMPC_OK;
-    std::vector<HdvBatch> batches = hdv_split_batches((int)M, n_hdv.data(), [&](int a, int b) { return same_hdv_map(members[a]->hdv, members[b]->hdv); });
-    std::vector<HdvSlotNote> note(M);
-    int64_t generation[PDMPC_HDV_MAP_SLOTS];
-    auto read_generations = [&]() {
-        for (int s = 0; s < PDMPC_HDV_MAP_SLOTS; ++s)
-            if (const int rc = pdmpc_hdv_map_slot_state(h, s, &generation[s], nullptr, nullptr)) return cfail(nullptr, rc, pdmpc_last_error());
-        return (int)PDMPC_OK;
-    };
-    // a member's map as the handle's entry points take it
-    auto with_map = [&](int m, auto&& f) {
-        const HdvTraffic& H = members[m]->hdv;
-        const pdmpc_polygon_set local = view_polygons(H.local_off, H.local_x, H.local_y);
-        return f((int32_t)H.lan_off.size() - 1, H.lan_off.data(), H.lan_off.data(), H.left_x.data(), H.left_y.data(), H.right_x.data(), H.right_y.data(), H.succ_off.data(),
-                 H.succ_idx.data(), H.rel.data(), (int32_t)H.n_trims, (int32_t)members[m]->sc.Hp, &local);
-    };
-    for (HdvBatch& B : batches) {
-        if (const int rc = read_generations()) return rc;
-        for (int m : B.members) note[(size_t)m] = HdvSlotNote{members[m]->hdv.map_slot, members[m]->hdv.map_generation};
-        hdv_assign_slots(B, note.data(), generation, [&](int slot, int m) {
-            int32_t holds = 0;
-            (void)with_map(m, [&](auto... map) { return pdmpc_hdv_map_slot_holds(h, slot, map..., &holds); });
-            return holds != 0;
-        });
-        for (size_t d = 0; d < B.maps.size(); ++d) {
-            if (!B.upload[d]) continue;
-            S.hdv_calls[1] += 1;
-            if (const int rc = with_map(B.maps[d], [&](auto... map) { return pdmpc_upload_hdv_map_slot(h, B.slot[d], map...); }))
-                return cfail(members[B.maps[d]], rc, std::string("pdmpc_upload_hdv_map_slot: ") + pdmpc_last_error());
-        }
-        if (const int rc = read_generations()) return rc;
-        for (size_t i = 0; i < B.members.size(); ++i) {
-            HdvTraffic& H = members[B.members[i]]->hdv;
-            H.map_slot = B.slot[(size_t)B.map_of[i]];
-            H.map_generation = generation[H.map_slot];
-        }
-        S.hdv_calls[0] += 1;
-        if (const int rc = hdv_call_for_batch(h, members, B, S.hdv, drives)) return rc;
-    }
-    return PDMPC_OK;
-}
-
-// The step problems of M members (of one Hp, all on the handle h or all without one), built with ONE step preparation for all of them:
-// with a handle the grouped device calls, without one the host twins.  This is the only place that asks which.  batch.n_perm > 0: every
-// member's explorative batch of n_perm prioritizations behind its step (pdmpc_controller_explore_build's statements, in its order).
-// batch.max_instances > 0: every member's optimal-priority batch behind the steps -- ONE enumeration of the unique prioritizations of all
-// members' coupling graphs, then pdmpc_controller_optimal_build's instances per member.
-int build_members(pdmpc_handle* h, pdmpc_controller* const* members, size_t M, BatchKind batch, PrepScratch& S) {
-    const int n_perm = batch.n_perm;
-    struct ExploringAll {  // (the members' memos of the obstacle sets are on while their prioritizations are assembled)
-        pdmpc_controller* const* members;
-        size_t M;
-        bool on;
-        ExploringAll(pdmpc_controller* const* ms, size_t n, bool o) : members(ms), M(n), on(o) { set(on); }
-        ~ExploringAll() { set(false); }
-        void set(bool v) {
-            for (size_t m = 0; on && m < M; ++m) members[m]->as.exploring = v;
-        }
-    } exploring(members, M, n_perm > 0 || batch.max_instances > 0);
-    S.prep.assign(M, StepPrep());
-    std::fill(S.prep_calls, S.prep_calls + 4, 0);
-    S.prio.calls = 0;
-    for (size_t m = 0; m < M; ++m)
-        if (const int rc = begin_step(members[m], S.prep[m])) return rc;
-    if (const int rc = hdv_traffic_stage(h, members, M, S)) return rc;
-    // who takes part in which grouped call: bounded (step Hp only / every step: one bounding call each) or the plain hulls
-    std::vector<int> bounded_last, bounded_all, hulls;
-    for (size_t m = 0; m < M; ++m) {
-        const StepPrep& P = S.prep[m];
-        if (P.bounded)
-            (P.reach_parallel ? bounded_all : bounded_last).push_back((int)m);
-        else if (members[m]->sc.cfg.coupling == PDMPC_COUPLING_REACHABLE_SET)
-            hulls.push_back((int)m);
-    }
-    int rc = PDMPC_OK;
-    if (h) {
-        rc = bound_on_device(h, members, S, bounded_last, false);
-        if (!rc) rc = bound_on_device(h, members, S, bounded_all, true);
-        if (!rc) rc = couple_hulls_on_device(h, members, S, hulls);
-    } else {
-        bounded_last.insert(bounded_last.end(), bounded_all.begin(), bounded_all.end());
-        std::sort(bounded_last.begin(), bounded_last.end());
-        rc = bound_on_host(members, S, bounded_last);
-        if (!rc) rc = couple_hulls_on_host(members, S, hulls);
-    }
-    if (rc) return rc;
-    std::vector<int> assessed;  // the members with FCA priorities: assessed together once every member's adjacency is there
-    for (size_t m = 0; m < M; ++m) {
-        couple(members[m]->sc, members[m]->tr, members[m]->in);
-        if (members[m]->sc.cfg.priority_strategy == PDMPC_PRIORITY_FCA) assessed.push_back((int)m);
-    }
-    PrepScratch::Fca& F = S.fca;
-    if (!assessed.empty()) {
-        if ((rc = gather_fca(members, F, assessed))) return rc;
-        const int Hp = members[0]->sc.Hp;
-        S.prep_calls[3] += 1;
-        rc = h ? pdmpc_fca_collisions_grouped(h, (int32_t)F.groups.size(), F.groups.data(), Hp, F.x.data(), F.y.data(), F.cos_yaw.data(), F.sin_yaw.data(), F.collisions.data(),
-                                              F.priorities.data())
-               : pdmpc_fca_collisions_grouped_host((int32_t)F.groups.size(), F.groups.data(), Hp, F.x.data(), F.y.data(), F.cos_yaw.data(), F.sin_yaw.data(), F.collisions.data(),
-                                                   F.priorities.data());
-        if (rc) return cfail(nullptr, rc, h ? std::string("pdmpc_fca_collisions_grouped: ") + pdmpc_last_error() : "pdmpc_fca_collisions_grouped_host failed");
-    }
-    for (size_t m = 0, g = 0, v0 = 0; m < M; ++m) {
-        pdmpc_controller* c = members[m];
-        const bool fca = g < assessed.size() && assessed[g] == (int)m;
-        rc = finish_step(c, fca ? F.collisions.data() + v0 : nullptr, fca ? F.priorities.data() + v0 : nullptr);
-        if (fca) {
-            v0 += (size_t)c->sc.n;
-            ++g;
-        }
-        if (!rc && n_perm > 0) rc = permute_instances(c, n_perm, (uint32_t)c->tr.k);  // RandStream("mt19937ar", Seed = obj.k) (:249)
-        if (rc) return rc;
-    }
-    if (batch.max_instances < 1) return PDMPC_OK;
-    // every unique prioritization of every member's coupling graph: one call whatever M is
-    PrepScratch::Prio& Q = S.prio;
-    Q.group_n.resize(M);
-    Q.adjacency.resize(M);
-    Q.max_out.assign(M, batch.max_instances);
-    Q.n_out.assign(M, 0);
-    size_t rows = 0;
-    for (size_t m = 0; m < M; ++m) {
-        Q.group_n[m] = members[m]->sc.n;
-        Q.adjacency[m] = members[m]->in.adjacency.data();
-        rows += (size_t)batch.max_instances * members[m]->sc.n;
-    }
-    Q.masks.resize(M * (size_t)batch.max_instances);
-    Q.priorities.resize(rows);
-    Q.calls += 1;
-    rc = h ? pdmpc_unique_priorities_grouped(h, (int32_t)M, Q.group_n.data(), Q.adjacency.data(), Q.max_out.data(), Q.n_out.data(), Q.masks.data(), Q.priorities.data())
-           : pdmpc_unique_priorities_grouped_host((int32_t)M, Q.group_n.data(), Q.adjacency.data(), Q.max_out.data(), Q.n_out.data(), Q.masks.data(), Q.priorities.data());
-    if (rc) return h ? cfail(nullptr, rc, pdmpc_last_error()) : rc;
-    const uint32_t* masks = Q.masks.data();
-    const int32_t* priorities = Q.priorities.data();
-    for (size_t m = 0; m < M; ++m) {
-        if ((rc = optimal_instances(members[m], Q.n_out[m], masks, priorities))) return rc;
-        masks += Q.n_out[m];
-        priorities += Q.n_out[m] * members[m]->sc.n;
-    }
-    return PDMPC_OK;
-}
-
 // ---- how a step ends that the controller takes alone
 PlanTarget target_of(const pdmpc_controller* c) { return {c->h, c->group, c->group_mode}; }
 // a failure inside a step the controller takes alone is the controller's error too (the global message has it either way)
@@ -706,6 +98,8 @@ int own(pdmpc_controller* c, int rc) {
     if (rc) c->err = g_cerr;
     return rc;
 }
+// what a stage on narrow state refused (its code and its text) as the controller's error
+int refused(pdmpc_controller* c, int rc, const std::string& why) { return rc ? cfail(c, rc, why) : (int)PDMPC_OK; }
 // the end of a step the controller takes alone: the records in c->out applied (timing[5]), and the step's parts added to the controller's sums
 int apply_and_account(pdmpc_controller* c) {
     const auto t = std::chrono::steady_clock::now();
@@ -982,9 +376,7 @@ int pdmpc_controller_set_hdvs(pdmpc_controller* c, int32_t n_hdv, const pdmpc_mp
         H.cav_tile_dy.push_back(V.tile_dy);
     }
     if (c->h) {  // (the map's own refusals -- limits, successor ids -- come from the one place that checks them; the upload is the first step's)
-        const pdmpc_polygon_set local = view_polygons(H.local_off, H.local_x, H.local_y);
-        rc = pdmpc_hdv_check_map_host(n_lan, H.lan_off.data(), H.lan_off.data(), H.left_x.data(), H.left_y.data(), H.right_x.data(), H.right_y.data(), H.succ_off.data(),
-                                      H.succ_idx.data(), H.rel.data(), H.n_trims, c->sc.Hp, &local);
+        rc = hdv_with_map(H, c->sc.Hp, pdmpc_hdv_check_map_host);
         if (rc) return cfail(c, rc, std::string("pdmpc_controller_set_hdvs: ") + pdmpc_last_error());
     }
     c->hdv = std::move(H);  // (with no map slot noted: the next step looks for the map on the handle)
@@ -993,106 +385,38 @@ int pdmpc_controller_set_hdvs(pdmpc_controller* c, int32_t n_hdv, const pdmpc_mp
 
 int pdmpc_controller_set_hdv_drivers(pdmpc_controller* c, const int32_t* route_offset, const int32_t* route_lanelet, const uint8_t* closed, const double* start_distance,
                                      const double* v_des, const double* params) {
-    const std::string who = "pdmpc_controller_set_hdv_drivers: ";
-    if (!c || !route_offset || !route_lanelet || !closed || !start_distance || !v_des || !params) return cfail(c, PDMPC_ERR_INVALID, who + "null argument");
-    HdvTraffic& H = c->hdv;
-    if (H.n == 0) return cfail(c, PDMPC_ERR_INVALID, who + "before pdmpc_controller_set_hdvs");
-    if (H.rec_T > 0) return cfail(c, PDMPC_ERR_INVALID, who + "the HDVs replay a recording (pdmpc_controller_set_hdv_recording)");
-    if (route_offset[0] != 0) return cfail(c, PDMPC_ERR_INVALID, who + "route offsets that do not start at 0");
-    for (int q = 0; q < H.n; ++q)
-        if (route_offset[q + 1] < route_offset[q]) return cfail(c, PDMPC_ERR_INVALID, who + "route offsets decrease");
+    if (!c || !route_offset || !route_lanelet || !closed || !start_distance || !v_des || !params) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_drivers: null argument");
     std::string why;
-    if (const int rc = hdv_check_drive(params, c->sc.cfg.dt_seconds, H.n, v_des, &why)) return cfail(c, rc, who + why);
-    // the routes against the controller's map, and the placement: the "measurement" of the first step
-    std::vector<int32_t> seg((size_t)2 * H.n);
-    std::vector<double> u((size_t)H.n), x((size_t)H.n), y((size_t)H.n), cs((size_t)H.n), sn((size_t)H.n);
-    const int rc = pdmpc_hdv_place_host((int32_t)H.lan_off.size() - 1, H.lan_off.data(), H.lan_off.data(), H.left_x.data(), H.left_y.data(), H.right_x.data(), H.right_y.data(),
-                                        H.succ_off.data(), H.succ_idx.data(), H.rel.data(), H.n, route_offset, route_lanelet, closed, start_distance, H.tile_dx.data(),
-                                        H.tile_dy.data(), seg.data(), u.data(), x.data(), y.data(), cs.data(), sn.data());
-    if (rc) return cfail(c, rc, who + pdmpc_last_error());
-    H.route_off.assign(route_offset, route_offset + H.n + 1);
-    H.route_id.assign(route_lanelet, route_lanelet + route_offset[H.n]);
-    H.route_id.push_back(0);
-    H.route_closed.assign(closed, closed + H.n);
-    H.v_des.assign(v_des, v_des + H.n);
-    std::copy(params, params + 4, H.drive_params);
-    H.seg = seg;
-    H.u = u;
-    H.new_seg.assign((size_t)2 * H.n, 0);
-    H.new_u.assign((size_t)H.n, 0.0);
-    H.speed.assign((size_t)H.n, 0.0);
-    H.gap.assign((size_t)H.n, (double)INFINITY);
-    H.x = x;
-    H.y = y;
-    H.cos_yaw = cs;
-    H.sin_yaw = sn;
-    hdv_driven_yaw(H);
-    H.driven = true;
-    H.driven_builds = 0;
-    H.measured = true;
-    return PDMPC_OK;
+    return refused(c, hdv_set_drivers(c->hdv, c->sc.cfg.dt_seconds, route_offset, route_lanelet, closed, start_distance, v_des, params, &why), why);
 }
 
 int pdmpc_controller_hdv_driver_state(pdmpc_controller* c, int32_t* state_seg, double* state_u, double* x, double* y, double* yaw, double* speed, double* gap) {
     if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
     const HdvTraffic& H = c->hdv;
     if (!H.driven) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_hdv_driver_state before pdmpc_controller_set_hdv_drivers");
-    if (state_seg) std::copy(H.seg.begin(), H.seg.end(), state_seg);
-    if (state_u) std::copy(H.u.begin(), H.u.end(), state_u);
-    if (x) std::copy(H.x.begin(), H.x.end(), x);
-    if (y) std::copy(H.y.begin(), H.y.end(), y);
-    if (yaw) std::copy(H.yaw.begin(), H.yaw.end(), yaw);
-    if (speed) std::copy(H.speed.begin(), H.speed.end(), speed);
-    if (gap) std::copy(H.gap.begin(), H.gap.end(), gap);
+    auto out = [](const auto& from, auto* to) {  // (any of them may be NULL)
+        if (to) std::copy(from.begin(), from.end(), to);
+    };
+    out(H.seg, state_seg), out(H.u, state_u), out(H.x, x), out(H.y, y), out(H.yaw, yaw), out(H.speed, speed), out(H.gap, gap);
     return PDMPC_OK;
 }
 
 int pdmpc_controller_set_hdv_recording(pdmpc_controller* c, int32_t T, const double* x, const double* y, const double* yaw) {
-    const std::string who = "pdmpc_controller_set_hdv_recording: ";
-    if (!c || T < 1 || !x || !y || !yaw) return cfail(c, PDMPC_ERR_INVALID, who + "bad argument");
-    HdvTraffic& H = c->hdv;
-    if (H.n == 0) return cfail(c, PDMPC_ERR_INVALID, who + "before pdmpc_controller_set_hdvs");
-    if (H.driven) return cfail(c, PDMPC_ERR_INVALID, who + "the HDVs have drivers (pdmpc_controller_set_hdv_drivers)");
-    H.rec_T = T;
-    H.rec_builds = 0;
-    H.rec_x.assign(x, x + (size_t)T * H.n);
-    H.rec_y.assign(y, y + (size_t)T * H.n);
-    H.rec_yaw.assign(yaw, yaw + (size_t)T * H.n);
-    return PDMPC_OK;
+    if (!c || T < 1 || !x || !y || !yaw) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_recording: bad argument");
+    std::string why;
+    return refused(c, hdv_set_recording(c->hdv, T, x, y, yaw, &why), why);
 }
 
 int pdmpc_controller_set_hdv_poses(pdmpc_controller* c, const double* x, const double* y, const double* cos_yaw, const double* sin_yaw) {
     if (!c || !x || !y || !cos_yaw || !sin_yaw) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_poses: null argument");
-    HdvTraffic& H = c->hdv;
-    if (H.n == 0) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_poses before pdmpc_controller_set_hdvs");
-    if (H.driven || H.rec_T > 0)
-        return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_poses: the HDVs move themselves (pdmpc_controller_set_hdv_drivers / _set_hdv_recording); their poses are not set");
-    H.x.assign(x, x + H.n);
-    H.y.assign(y, y + H.n);
-    H.cos_yaw.assign(cos_yaw, cos_yaw + H.n);
-    H.sin_yaw.assign(sin_yaw, sin_yaw + H.n);
-    hdv_driven_yaw(H);
-    H.measured = true;
-    return PDMPC_OK;
+    std::string why;
+    return refused(c, hdv_set_poses(c->hdv, "pdmpc_controller_set_hdv_poses", "set", x, y, nullptr, cos_yaw, sin_yaw, &why), why);
 }
 
 int pdmpc_controller_set_hdv_measurements(pdmpc_controller* c, const double* x, const double* y, const double* yaw) {
     if (!c || !x || !y || !yaw) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_measurements: null argument");
-    HdvTraffic& H = c->hdv;
-    if (H.n == 0) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_measurements before pdmpc_controller_set_hdvs");
-    if (H.driven || H.rec_T > 0)
-        return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_set_hdv_measurements: the HDVs move themselves (pdmpc_controller_set_hdv_drivers / _set_hdv_recording); their poses are not measured");
-    H.x.assign(x, x + H.n);
-    H.y.assign(y, y + H.n);
-    H.yaw.assign(yaw, yaw + H.n);
-    H.cos_yaw.resize((size_t)H.n);
-    H.sin_yaw.resize((size_t)H.n);
-    for (int q = 0; q < H.n; ++q) {
-        H.cos_yaw[(size_t)q] = std::cos(yaw[q]);
-        H.sin_yaw[(size_t)q] = std::sin(yaw[q]);
-    }
-    H.measured = true;
-    return PDMPC_OK;
+    std::string why;
+    return refused(c, hdv_set_poses(c->hdv, "pdmpc_controller_set_hdv_measurements", "measured", x, y, yaw, nullptr, nullptr, &why), why);
 }
 
 int pdmpc_controller_hdv_info(pdmpc_controller* c, int32_t* n_hdv, const int32_t** closest_offset, const int32_t** closest_index, int32_t* n_rows, const int32_t** row_hdv,
@@ -1100,16 +424,11 @@ int pdmpc_controller_hdv_info(pdmpc_controller* c, int32_t* n_hdv, const int32_t
     if (!c) return cfail(nullptr, PDMPC_ERR_INVALID, "null controller");
     const HdvTraffic& H = c->hdv;
     if (H.n == 0 || H.closest_off.empty()) return cfail(c, PDMPC_ERR_INVALID, "pdmpc_controller_hdv_info before a step was built with HDVs");
-    if (n_hdv) *n_hdv = H.n;
-    if (closest_offset) *closest_offset = H.closest_off.data();
-    if (closest_index) *closest_index = H.closest_idx.data();
-    if (n_rows) *n_rows = H.n_rows;
-    if (row_hdv) *row_hdv = H.row_hdv.data();
-    if (set_offset) *set_offset = H.set_off.data();
-    if (set_x) *set_x = H.set_x.data();
-    if (set_y) *set_y = H.set_y.data();
-    if (set_flags) *set_flags = H.set_flags.data();
-    if (adjacency) *adjacency = H.adjacency.data();
+    auto out = [](auto* to, auto value) {  // (any of them may be NULL)
+        if (to) *to = value;
+    };
+    out(n_hdv, H.n), out(closest_offset, H.closest_off.data()), out(closest_index, H.closest_idx.data()), out(n_rows, H.n_rows), out(row_hdv, H.row_hdv.data());
+    out(set_offset, H.set_off.data()), out(set_x, H.set_x.data()), out(set_y, H.set_y.data()), out(set_flags, H.set_flags.data()), out(adjacency, H.adjacency.data());
     return PDMPC_OK;
 }
 

@@ -1,4 +1,4 @@
-// step_inputs.hpp — what a step reads of the traffic (step_controller.cpp, stage 2 of 7): the reference's functions that fill the parts
+// step_inputs.hpp — what a step reads of the traffic (step_controller.cpp, stage 2 of 9): the reference's functions that fill the parts
 // of the controller's state a step's inputs are made of (step_types.hpp).  Every function takes the parts it reads and writes; the
 // controller is not known here.
 // What it restates (file:line relative to the reference root):

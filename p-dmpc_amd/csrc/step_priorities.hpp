@@ -1,4 +1,4 @@
-// step_priorities.hpp — from couplings to a prioritization (step_controller.cpp, stage 3 of 7): computation levels, the colouring, the
+// step_priorities.hpp — from couplings to a prioritization (step_controller.cpp, stage 4 of 9): computation levels, the colouring, the
 // grouping with its weighers and cutter, random priorities, the level permutations of the explorative step, the unique prioritizations
 // of the optimal-priority step.  Plain arrays and Lists in, plain arrays out: nothing of the controller's state is known here.
 // What it restates (file:line relative to the reference root):

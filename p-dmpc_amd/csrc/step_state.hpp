@@ -1,18 +1,19 @@
-// step_state.hpp — the state of the native step controller (step_controller.cpp, stage 4 of 7): the scratch of a step preparation, of the
+// step_state.hpp — the state of the native step controller (step_controller.cpp, stage 5 of 9): the scratch of a step preparation, of the
 // assembly and of a batch, and the controller itself as the parts that are written together.
 //
 // Two records and one path.  A StepProblem is what pdmpc_plan_step takes -- inputs, fallbacks, predecessor slots --
 // with its seeds and weights, wherever it lives: a controller's step, each kept instance, its flattened batch, a sweep's concatenated
 // step and batch; the per-slot tags (instance, vehicle, level, member, member_slot) are plain vectors next to it.  An Instance is a
-// prioritization (both coupling matrices, levels, slot order): the controller's own (c->pri) and every kept one.  build_members prepares
-// the step of a span of members -- the device calls or their host twins, grouped by member, the only fork on the handle and the only
-// capacity retry -- between the per-member halves begin_step and finish_step (pdmpc_controller_build_step: M = 1, in the controller's
-// own scratch); plan_built plans a StepProblem (weights, seeds, the backend call, timing[1..3]); timed_steps is the loop of every *_run.
+// prioritization (both coupling matrices, levels, slot order): the controller's own (c->pri) and every kept one.  build_members
+// (step_prepare.hpp) prepares the step of a span of members -- the device calls or their host twins, grouped by member, the only fork on
+// the handle, every call that sizes its output under the one capacity retry (with_room, step_hdv.hpp) -- between the per-member halves
+// begin_step and finish_step (pdmpc_controller_build_step: M = 1, in the controller's own scratch); plan_built plans a StepProblem (weights, seeds, the backend call, timing[1..3]); timed_steps is the loop of every *_run.
 #pragma once
 #include <memory>
 #include <string>
 
 #include "step_inputs.hpp"
+#include "step_hdv.hpp"
 #include "step_priorities.hpp"
 
 namespace {
@@ -34,21 +35,7 @@ struct PrepScratch {
         std::vector<uint8_t> adjacency;      // the blocks
     } call;
     int32_t hdv_calls[2] = {0, 0};  // ... its HDV traffic calls and the map uploads they needed (pdmpc_sweep_last_hdv_calls)
-    // one grouped HDV traffic call: the HDVs and CAVs of a batch of members, member after member, and what it returns in the blocks
-    // of pdmpc_hdv_grouped_layout_host
-    struct Hdv {
-        std::vector<int32_t> slot, hdv_offset, cav_offset, trim, cav_lanelet;
-        std::vector<double> x, y, cos_yaw, sin_yaw, tile_dx, tile_dy, cav_x, cav_y, cav_tile_dx, cav_tile_dy;
-        std::vector<int32_t> closest_at, list_at, set_offset_at, set_at;
-        std::vector<int64_t> adjacency_at;
-        std::vector<int32_t> closest_off, closest_idx, n_rows, row_hdv, set_off, set_base;
-        std::vector<double> set_x, set_y;
-        std::vector<uint8_t> set_flags, adjacency;
-        // the drive pass in front (pdmpc_hdv_drive_traffic_grouped), when a member of the batch has drivers
-        std::vector<uint8_t> drives, route_closed;
-        std::vector<int32_t> route_off, route_id, seg_r, seg_j, seg, new_seg;
-        std::vector<double> u, v_des, params, dt, new_u, speed, gap;
-    } hdv;
+    HdvCallScratch hdv;             // ... and the scratch of one grouped call of them (step_hdv.hpp)
     // the grouped collision assessment: the FCA members' reference points, member after member, and what it returns
     struct Fca {
         std::vector<pdmpc_fca_group> groups;

@@ -1,4 +1,4 @@
-// step_types.hpp — the records of the native step controller (step_controller.cpp, stage 1 of 7): polygons, matrix lists, plans,
+// step_types.hpp — the records of the native step controller (step_controller.cpp, stage 1 of 9): polygons, matrix lists, plans,
 // vehicles, a step problem, a prioritization, a choice, and the parts of the controller's state that a step's inputs are made of.  Names
 // nothing but the C ABI.
 // (Every stage header compiles alone under -Wunused-function -Wunused-member-function, `make host-parts`: its helpers are inline, and a
